@@ -28,6 +28,9 @@ the GEMM); `--no-profile` switches the per-launch events off.  At N = 1 the end-
 (Reranker_base_executor.py:898-939: H2D ids -> forward -> D2H logits/order for ONE query) and the CPU baseline follow,
 outside the timed region.
 
+`--dump-outputs DIR` (rank 0): what the last timed step returned (logits, scores, order, loss, ...) as DIR/<name>.npy, right
+after the timed loop; inputs and weights are seeded, so two builds run with the same arguments can be compared array for array.
+
 `python bench.py --gpus N` without a launcher environment starts `python -m torch.distributed.run --nproc-per-node N`
 on itself as a CHILD process before anything touches the GPU and exits with the child's code.
 """
@@ -93,6 +96,8 @@ def parse_args(argv=None):
                     help="std multiplier of the Linear matrices of the synthetic weights (1 = HF init: near-uniform attention; 2.5 = the "
                          "peaked-attention regime of tests/golden c3_sep).  The line then also reports how many attention workgroups "
                          "the fixed-reference schedule had to recompute online (`attention_redo`)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--tuning", action="append", default=[], metavar="KEY=INT",
                     help="process-wide A/B switch of the library (rr_set_tuning), e.g. --tuning ln_fold=0; diagnostic")
     a = ap.parse_args(argv)
@@ -103,6 +108,33 @@ def parse_args(argv=None):
     if a.queries_per_gpu is None:
         a.queries_per_gpu = 1 if a.scaling == "strong" else (4 if a.workload == "c5" else (2 if a.workload == "L" else 8))
     return a
+
+
+DUMP_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out, d):
+    """The tensors of one step's result dict as d/<name>.npy: floating point as float32 (float64 stays float64), integer
+    and boolean as float64 (exact for every index and count the path returns).  An array beyond its share of DUMP_BYTES is
+    replaced by a fixed, seeded sample of its flattened elements, with the sampled positions in d/<name>.index.npy."""
+    import numpy as np
+    import torch
+    arrs = {}
+    for k, v in out.items():
+        if isinstance(v, torch.Tensor):
+            a = v.detach().cpu()
+            a = a.numpy().astype(np.float64 if a.dtype == torch.float64 or not a.is_floating_point() else np.float32)
+            arrs[k] = a
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BYTES // (2 * max(1, len(arrs)))
+    for k, a in sorted(arrs.items()):
+        if a.nbytes > share:
+            n = share // 8                     # the float64 positions fit the same share
+            idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(a.size, n, replace=False))
+            np.save(os.path.join(d, k + ".index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, k + ".npy"), a)
+    return sorted(arrs)
 
 
 def spawn_ranks(args):
@@ -451,6 +483,7 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     eng.set_profiling(False)
+    dumped = dump_outputs(out, args.dump_outputs) if args.dump_outputs and rank == 0 else None   # before any later call reuses the buffers
     prof = eng.get_profile(reset=True) if not args.no_profile else None
     step_ms = [a.elapsed_time(b) for a, b in ev]
     if distributed:
@@ -510,6 +543,8 @@ def main():
         }
         if redo is not None:
             res["attention_redo"] = redo
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if args.fp8:
             fl, fq, fd = (eng.get_option(k) for k in ("fp8_first_layer", "fp8_qkv", "fp8_ffn_down"))
             res["config"]["fp8_layers"] = (f"e4m3 QKV / FFN-up operands in text-encoder layers {fl}..{arch['layers'] - 1} of {arch['layers']} "

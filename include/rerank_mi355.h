@@ -112,7 +112,7 @@ typedef struct rr_model* rr_handle;
 /* Per-kernel-class device time accumulated while profiling is on (rr_set_profiling). */
 typedef enum rr_kernel_class {
   RR_K_GEMM = 0, RR_K_ATTENTION = 1, RR_K_LAYERNORM = 2, RR_K_EMBED = 3, RR_K_TAIL = 4, RR_K_HEAD = 5,
-  RR_K_GEMM_FP8 = 6,          /* the e4m3 GEMM launches of rr_config.fp8 (priced against the fp8 matrix-core peak) */
+  RR_K_GEMM_FP8 = 6,          /* 8-bit GEMM launches (e4m3 or int8) of rr_config.fp8 (priced against the 8-bit matrix-core peak) */
   RR_K_COUNT = 7
 } rr_kernel_class;
 
@@ -210,9 +210,22 @@ int rr_set_padded_seq_len(rr_handle h, int padded_seq_len);
  *                                                     with a checkpoint you have validated).  A perturbation injected early is
  *                                                     amplified by every later layer, so e4m3 goes into the LAST layers first;
  *                                                     the default (the last layer only) is the largest subset that ranks with a margin that survives
- *                                                     a re-draw of unrelated roundings (DESIGN.md "fp8")
+ *                                                     a re-draw of unrelated roundings (DESIGN.md "fp8").  int8 handles
+ *                                                     ("q8_format" 1): default layers-12
  *   "fp8_qkv"        0 | 1                  1         rr_config.fp8 only: 0 = of an e4m3 layer only the FFN takes e4m3 operands,
  *                                                     its QKV projection keeps 16-bit ones
+ *   "q8_format"      0 | 1                  0         rr_config.fp8 only: the 8-bit operand format.  0 = e4m3 (the block-scaled
+ *                                                     MFMA); 1 = int8 (W8A8: v_mfma_i32_*_i8, int32 accumulation, activations
+ *                                                     per row by the producing LayerNorm (amax / 127), weights per output
+ *                                                     channel, each LayerNorm's gain outliers migrated into the consumer weights
+ *                                                     by powers of two at rr_finalize_weights).  Same GEMMs as e4m3 (QKV of
+ *                                                     layers >= 1, FFN-up); "fp8_first_layer" / "fp8_qkv" apply unchanged, the
+ *                                                     default of "fp8_first_layer" for int8 handles is layers - 12 (the
+ *                                                     last 12 layers: the largest suffix that keeps the fp32 top-5 with
+ *                                                     margin on the ranking fixtures; the whole stack runs 1.10x the 16-bit
+ *                                                     line but does not, DESIGN.md "int8"); "fp8_ffn_down" = 1 is refused.
+ *                                                     Latched by rr_finalize_weights (it packs ONE format): a later change
+ *                                                     returns RR_ERR_BAD_ARG
  *   "attn_fixed_ref" 0 | 1 | 2 | 3          3         softmax schedule of large attention grids: 0 online only, 1 fixed reference
  *                                                     with 32 query rows per wave, 2 with 64, 3: 2 where 256-row workgroups pad no
  *                                                     more rows than 128-row ones, else 1

@@ -120,9 +120,25 @@ int rr_op_gemm_lnfold(const uint16_t* A_raw, const uint16_t* W_folded, const flo
 int rr_op_layernorm_q8(const float* x, const float* gamma, const float* beta, float eps, int rows, int cols, uint8_t* out8,
                        float* row_scale, float* stats, void* hip_stream);
 int rr_util_quantize_rows_e4m3(const float* w_host, int rows, int cols, uint8_t* out_host, float* scales_host);
+/* int8 forms of the 8-bit configuration (handle option "q8_format" = 1):
+ *   rr_op_gemm_i8_rc: out[M,N] = epi(row_scale[m] * col_scale[n] * (A8 . W8^T) + bias), A8 [M,K] / W8 [N,K] signed int8 codes,
+ *     int32 accumulation (exact), converted to f32 once; epilogue 0 (16-bit, operand type of rr_set_op_dtype), 1 (erf-GELU ->
+ *     16-bit), 2 (f32); either scale vector may be NULL (= 1).  K % 128 == 0, N % 4 == 0; >= 512 tiles of 256 x 256 (and N % 8
+ *     == 0, epilogue 0 / 1) run the persistent ring, the rest the two-stage kernel.
+ *   rr_op_layernorm_i8: out8[row] = clamp(rint(LN(x[row]) / row_scale[row]), +-127), row_scale = row amax / 127 (1 for a zero
+ *     row), stats (may be NULL) = (mean, rstd).
+ *   rr_util_quantize_rows_i8: the HOST per-output-channel packer (amax / 127, rint, +-127); rr_util_smooth_scales: the host
+ *     smoothing rule s_j = 2^round(log2(max(|gamma_j|, |beta_j|) / median)), clamped to [1, 2^10].  Both usable without a GPU. */
+int rr_op_gemm_i8_rc(const int8_t* A8, const int8_t* W8, const float* bias, const float* row_scale, const float* col_scale,
+                     int M, int N, int K, int epilogue, void* out, void* hip_stream);
+int rr_op_layernorm_i8(const float* x, const float* gamma, const float* beta, float eps, int rows, int cols, int8_t* out8,
+                       float* row_scale, float* stats, void* hip_stream);
+int rr_util_quantize_rows_i8(const float* w_host, int rows, int cols, int8_t* out_host, float* scales_host);
+int rr_util_smooth_scales(const float* gamma_host, const float* beta_host, int n, float* s_host);
 int rr_set_gemm_variant(int variant);
 /* Process-wide DIAGNOSTIC switches (A/B tools, tests): the default every handle option of the same name follows until
- * rr_set_option pins it ("ln_lite", "ln_fold", "resid_split", "resid_lo8", "ce_cls_only", "fp8_ffn_down", "attn_fixed_ref": see rr_set_option),
+ * rr_set_option pins it ("ln_lite", "ln_fold", "resid_split", "resid_lo8", "ce_cls_only", "fp8_ffn_down", "q8_format", "attn_fixed_ref": see rr_set_option),
+ * "q8_smooth" (1: the int8 packer of rr_finalize_weights migrates LayerNorm gain outliers into the weights; 0: plain per-channel int8),
  * plus switches that select between bit-identical kernels or only move time: "resid_fast" (default 1: plain fp32 residual GEMMs
  * on the split forms' epilogue), "resid_touch" (0: L2 touch of the next residual pass), "gemm_desync" (0: start skew of the XCDs,
  * percent of a tile period), "persistent_gemm" (1), "gemm_ring_min_tiles" (128: smallest problem, in 256 x 256 tiles, on the

@@ -94,6 +94,10 @@ _SIGS = {
     "rr_op_gemm_fp8_resid": (C.c_int, [_P, _P, _P, C.c_float, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rr_op_layernorm_q8": (C.c_int, [_P, _P, _P, C.c_float, C.c_int, C.c_int, _P, _P, _P, _P]),
     "rr_util_quantize_rows_e4m3": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
+    "rr_op_gemm_i8_rc": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "rr_op_layernorm_i8": (C.c_int, [_P, _P, _P, C.c_float, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "rr_util_quantize_rows_i8": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
+    "rr_util_smooth_scales": (C.c_int, [_P, _P, C.c_int, _P]),
     "rr_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
     "rr_set_attn_stamps": (C.c_int, [_P]),
     "rr_set_attn_redo_stats": (C.c_int, [_P]),

@@ -101,6 +101,9 @@ __global__ __launch_bounds__(256) void ln_finalize_kernel(const float2* __restri
 // ROW (row amax / 448: the whole e4m3 range is used whatever the row's magnitude; no calibration state), y / scale rounded
 // to nearest even by v_cvt_pk_fp8_f32 (OCP e4m3fn on gfx950).  Also leaves (mean, rstd) for the residual epilogue's ln_apply.
 // 5 bytes per element instead of 6.  A zero row gets scale 1 (all-zero codes).
+// I8: the int8 operand of "q8_format" 1 — scale = row amax / 127, code = rint(y / scale) (nearest even) clamped to +-127
+// (never -128: the code range stays symmetric), same buffers and statistics.
+template <bool I8>
 __global__ __launch_bounds__(256) void layernorm_q8_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, float eps, int rows, int cols,
                                                            uint8_t* __restrict__ o8, float* __restrict__ row_scale,
@@ -129,7 +132,7 @@ __global__ __launch_bounds__(256) void layernorm_q8_kernel(const float* __restri
     }
   }
   amax = wave_max(amax);
-  const float scale = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
+  const float scale = amax > 0.f ? amax * (I8 ? 1.0f / 127.0f : 1.0f / 448.0f) : 1.0f;
   const float inv = 1.0f / scale;
   if (lane == 0) row_scale[row] = scale;
   // A lane's four codes of column group c4 are one dword; stored directly that is 4 bytes per lane and instruction.  The
@@ -141,12 +144,17 @@ __global__ __launch_bounds__(256) void layernorm_q8_kernel(const float* __restri
   for (int i = 0; i < MAX_V4; ++i) {
     const int c4 = lane + 64 * i;
     if (c4 < n4) {
-      const float a = __builtin_amdgcn_fmed3f(v[i].x * inv, -448.f, 448.f), b = __builtin_amdgcn_fmed3f(v[i].y * inv, -448.f, 448.f);
-      const float c = __builtin_amdgcn_fmed3f(v[i].z * inv, -448.f, 448.f), d = __builtin_amdgcn_fmed3f(v[i].w * inv, -448.f, 448.f);
-      int w = 0;
-      w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, w, false);
-      w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-      ln_[c4] = (uint32_t)w;
+      if constexpr (I8) {
+        auto q = [&](float f) { return (uint32_t)((int)__builtin_rintf(__builtin_amdgcn_fmed3f(f * inv, -127.f, 127.f)) & 0xff); };
+        ln_[c4] = q(v[i].x) | (q(v[i].y) << 8) | (q(v[i].z) << 16) | (q(v[i].w) << 24);
+      } else {
+        const float a = __builtin_amdgcn_fmed3f(v[i].x * inv, -448.f, 448.f), b = __builtin_amdgcn_fmed3f(v[i].y * inv, -448.f, 448.f);
+        const float c = __builtin_amdgcn_fmed3f(v[i].z * inv, -448.f, 448.f), d = __builtin_amdgcn_fmed3f(v[i].w * inv, -448.f, 448.f);
+        int w = 0;
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, w, false);
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
+        ln_[c4] = (uint32_t)w;
+      }
     }
   }
   uint8_t* const orow = o8 + (size_t)row * cols;
@@ -499,8 +507,17 @@ hipError_t rr_launch_layernorm_stats(const float* x, const float* gamma, const f
 hipError_t rr_launch_layernorm_q8(const float* x, const float* gamma, const float* beta, float eps, int rows, int cols,
                                   uint8_t* out8, float* row_scale, float* stats_out, hipStream_t st) {
   if (rows <= 0 || cols <= 0 || (cols & 3) || cols > 64 * 4 * MAX_V4 || !out8 || !row_scale) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(layernorm_q8_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, x, gamma, beta, eps, rows, cols, out8,
+  hipLaunchKernelGGL(layernorm_q8_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, st, x, gamma, beta, eps, rows, cols, out8,
                      row_scale, (float2*)stats_out);
+  return hipGetLastError();
+}
+
+// LayerNorm -> int8 rows (scale = row amax / 127, codes rint, +-127) + per-row scales (+ (mean, rstd)); cols % 4 == 0
+hipError_t rr_launch_layernorm_i8(const float* x, const float* gamma, const float* beta, float eps, int rows, int cols,
+                                  int8_t* out8, float* row_scale, float* stats_out, hipStream_t st) {
+  if (rows <= 0 || cols <= 0 || (cols & 3) || cols > 64 * 4 * MAX_V4 || !out8 || !row_scale) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(layernorm_q8_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, st, x, gamma, beta, eps, rows, cols,
+                     (uint8_t*)out8, row_scale, (float2*)stats_out);
   return hipGetLastError();
 }
 

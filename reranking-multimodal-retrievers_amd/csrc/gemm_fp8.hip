@@ -18,6 +18,13 @@
 //    likewise B; C/D as every 32x32 MFMA (col = l&31, row = (reg&3) + 8 (reg>>2) + 4 (l>>5)).  Issued "swapped" (A-operand
 //    = weight rows) so a lane ends up with 4 consecutive output columns per register group.
 //  * gemm_kernel_f8 — small problems: 16x16x128 form, two-stage LDS-DMA, direct epilogue (lane map: tools/fp8_mfma_probe.hip).
+//
+// int8 (W8A8, handle option "q8_format" = 1): both kernels with I8 = true.  Same ring, DMA pieces, swizzle, barriers and waits
+// (a K-tile row is still 128 bytes = 128 codes); each lane's 32-byte fragment of a k-step feeds two v_mfma_i32_32x32x32_i8
+// (16x16x64_i8 in the small kernel) as its two 16-byte halves: A and B are fetched by the same pattern, so both sides see k in
+// the same order and the two products sum every k once (tools/i8_mfma_probe.hip, exact integer data).  The accumulators are
+// int32 (exact: |acc| <= 127^2 K < 2^31 for any K below 133 000), kept in the f32 registers' bits and converted to f32
+// once, at the start of the epilogue; the epilogue itself is the e4m3 one.  Epilogues 0, 1, 2 only.
 #include "rr_common.h"
 
 #include <atomic>
@@ -27,6 +34,7 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16_;
+typedef __attribute__((ext_vector_type(16))) int i32x16;
 constexpr int BKB = 128;     // K-tile: 128 bytes = 128 fp8 per row
 
 template <int N>
@@ -34,9 +42,41 @@ __device__ __forceinline__ void wait_vmcnt8() { asm volatile("s_waitcnt vmcnt(%0
 
 __device__ __forceinline__ float gelu13(float x) { return gelu_erf_fast(x); }   // rr_common.h (the name is historical)
 
+__device__ __forceinline__ i32x4 lo16(const i32x8& f) { return i32x4{f[0], f[1], f[2], f[3]}; }
+__device__ __forceinline__ i32x4 hi16(const i32x8& f) { return i32x4{f[4], f[5], f[6], f[7]}; }
+
+// One k-step of a 32x32 / 16x16 accumulator tile (a: the MFMA's A operand).  e4m3: one block-scaled MFMA (block scales 2^0);
+// int8: two i8 MFMAs on the fragment halves, int32 accumulators carried in the f32 registers' bits.
+template <bool I8>
+__device__ __forceinline__ f32x16 mma32(const i32x8& a, const i32x8& b, f32x16 c) {
+  if constexpr (I8) {
+    i32x16 ci = __builtin_bit_cast(i32x16, c);
+    ci = __builtin_amdgcn_mfma_i32_32x32x32_i8(lo16(a), lo16(b), ci, 0, 0, 0);
+    ci = __builtin_amdgcn_mfma_i32_32x32x32_i8(hi16(a), hi16(b), ci, 0, 0, 0);
+    return __builtin_bit_cast(f32x16, ci);
+  } else {
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, 127, 0, 127);
+  }
+}
+template <bool I8>
+__device__ __forceinline__ f32x4 mma16(const i32x8& a, const i32x8& b, f32x4 c) {
+  if constexpr (I8) {
+    i32x4 ci = __builtin_bit_cast(i32x4, c);
+    ci = __builtin_amdgcn_mfma_i32_16x16x64_i8(lo16(a), lo16(b), ci, 0, 0, 0);
+    ci = __builtin_amdgcn_mfma_i32_16x16x64_i8(hi16(a), hi16(b), ci, 0, 0, 0);
+    return __builtin_bit_cast(f32x4, ci);
+  } else {
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, 127, 0, 127);
+  }
+}
+// int32 accumulator bits -> f32 value (round to nearest even), in place.  Whole-vector conversion: a per-element
+// __builtin_bit_cast(int, v[r]) of an ext_vector element reads element 0 for every r (hipcc, seen in the ISA).
+__device__ __forceinline__ void acc_i32_to_f32(f32x4& v) { v = __builtin_convertvector(__builtin_bit_cast(i32x4, v), f32x4); }
+__device__ __forceinline__ void acc_i32_to_f32(f32x16& v) { v = __builtin_convertvector(__builtin_bit_cast(i32x16, v), f32x16); }
+
 // EPI: 0 = 16bit(acc*s + b), 1 = 16bit(gelu(acc*s + b)), 2 = f32(acc*s + b);  s = scale * row_scale[m] * col_scale[n]
 // (row_scale / col_scale may be null = 1)
-template <int BM, int BN, int WM, int WN, int EPI, int DT>
+template <int BM, int BN, int WM, int WN, int EPI, int DT, bool I8 = false>
 __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel_f8(const uint8_t* __restrict__ A, int lda,
                                                               const uint8_t* __restrict__ W, int ldw,
                                                               const float* __restrict__ bias, float scale,
@@ -115,7 +155,13 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel_f8(const uint8_t* __r
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
-        acc[nt][mt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[nt], af[mt], acc[nt][mt], 0, 0, 0, 127, 0, 127);
+        acc[nt][mt] = mma16<I8>(wf[nt], af[mt], acc[nt][mt]);
+  }
+  if constexpr (I8) {
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+      for (int j = 0; j < MT; ++j) acc_i32_to_f32(acc[i][j]);
   }
 
   // ---- direct epilogue: lane owns 4 consecutive n of one output row m
@@ -158,7 +204,7 @@ struct F8Extra {
   const float* rgamma = nullptr;
   const float* rbeta = nullptr;
 };
-template <int EPI, int DT>
+template <int EPI, int DT, bool I8 = false>
 __global__ __launch_bounds__(512) void gemm_kernel_hp8(const uint8_t* __restrict__ A, int lda,
                                                       const uint8_t* __restrict__ W, int ldw,
                                                       const float* __restrict__ bias, float scale,
@@ -244,7 +290,7 @@ __global__ __launch_bounds__(512) void gemm_kernel_hp8(const uint8_t* __restrict
 
 #define RR_BLK(Q, AF, BF)                                                                                           \
   _Pragma("unroll") for (int mb = 0; mb < 2; ++mb)                                                                  \
-      acc[Q][mb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(BF, AF[mb], acc[Q][mb], 0, 0, 0, 127, 0, 127);
+      acc[Q][mb] = mma32<I8>(BF, AF[mb], acc[Q][mb]);
 #define RR_SBAR() __builtin_amdgcn_sched_barrier(0)
 #define RR_PRIO(p) __builtin_amdgcn_s_setprio(p);
 #define RR_SYNC(NLIT)                                    \
@@ -383,6 +429,12 @@ __global__ __launch_bounds__(512) void gemm_kernel_hp8(const uint8_t* __restrict
   int tid_o_ = tid;
   asm volatile("" : "+v"(tid_o_));
   const int tid = tid_o_, lane = tid_o_ & 63, h = (tid_o_ & 63) >> 5;
+  if constexpr (I8) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int mb = 0; mb < 2; ++mb) acc_i32_to_f32(acc[q][mb]);
+  }
   if constexpr (EPI == 3) {
     // e4m3 out: one byte per element, two 128-row passes through a [128][256 + 16] byte image.  A lane owns 4 consecutive
     // columns = one dword.  ds_write_b32 has 32 banks and its lane groups are 32 rows of one column: at the 272-byte pitch
@@ -673,10 +725,11 @@ hipError_t rr_launch_amax(const void* x, int x_is_f32, size_t n, float* out, hip
 bool rr_gemm_fp8_ring_ok(int M, int N, int Kd) {
   return M > 0 && N > 0 && Kd > 0 && !(Kd % BKB) && !(N & 15) && ((M + 255) / 256) * ((N + 255) / 256) >= 512;
 }
-hipError_t rr_launch_gemm_fp8(const uint8_t* A, int lda, const uint8_t* W, int ldw, const float* bias, float scale,
-                              const float* row_scale, const float* col_scale, void* C, int ldc, int M, int N, int Kd,
-                              int epilogue, int dt, hipStream_t st, float out_mul, const float* resid, int ldr,
-                              const float* rstats, const float* rgamma, const float* rbeta) {
+template <bool I8>
+static hipError_t launch_gemm8(const uint8_t* A, int lda, const uint8_t* W, int ldw, const float* bias, float scale,
+                               const float* row_scale, const float* col_scale, void* C, int ldc, int M, int N, int Kd,
+                               int epilogue, int dt, hipStream_t st, float out_mul, const float* resid, int ldr,
+                               const float* rstats, const float* rgamma, const float* rbeta) {
   if (M <= 0 || N <= 0 || Kd <= 0 || (Kd % BKB) || (N & 3) || (lda & 15) || (ldw & 15) || (ldc & 3)) return hipErrorInvalidValue;
   if (epilogue < 0 || epilogue > 4 || (dt != 0 && dt != 1)) return hipErrorInvalidValue;
   if (epilogue >= 3) {
@@ -710,7 +763,7 @@ hipError_t rr_launch_gemm_fp8(const uint8_t* A, int lda, const uint8_t* W, int l
     const dim3 grid((unsigned)n_cu), block(512);
 #define RR_HP8(E, D)                                                                                                  \
   {                                                                                                                  \
-    auto kern = gemm_kernel_hp8<E, D>;                                                                               \
+    auto kern = gemm_kernel_hp8<E, D, I8>;                                                                             \
     static std::atomic<unsigned long long> mask{0};                                                                  \
     if (!(dev >= 0 && dev < 64 && ((mask.load() >> dev) & 1ull))) {                                                  \
       if ((e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)) != hipSuccess) return e; \
@@ -721,8 +774,8 @@ hipError_t rr_launch_gemm_fp8(const uint8_t* A, int lda, const uint8_t* W, int l
   }
     if (epilogue == 0) { if (dt == 0) RR_HP8(0, 0) else RR_HP8(0, 1) }
     else if (epilogue == 1) { if (dt == 0) RR_HP8(1, 0) else RR_HP8(1, 1) }
-    else if (epilogue == 3) RR_HP8(3, 0)                    /* (the operand type does not enter an e4m3 / f32 output) */
-    else RR_HP8(4, 0)
+    else if (epilogue == 3) { if constexpr (!I8) RR_HP8(3, 0) }   /* (the operand type does not enter an e4m3 / f32 output) */
+    else { if constexpr (!I8) RR_HP8(4, 0) }
 #undef RR_HP8
     return hipGetLastError();
   }
@@ -730,7 +783,7 @@ hipError_t rr_launch_gemm_fp8(const uint8_t* A, int lda, const uint8_t* W, int l
   const dim3 grid_exact((unsigned)nwg), block(WM * WN * 64);     // the XCD tile map is a bijection on [0, nwg)
 #define RR_F8(E, D)                                                                                                  \
   {                                                                                                                  \
-    auto kern = gemm_kernel_f8<BM, BN, WM, WN, E, D>;                                                                \
+    auto kern = gemm_kernel_f8<BM, BN, WM, WN, E, D, I8>;                                                             \
     static std::atomic<unsigned long long> mask{0};                                                                  \
     if (!(dev >= 0 && dev < 64 && ((mask.load() >> dev) & 1ull))) {                                                  \
       if ((e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)) != hipSuccess) return e; \
@@ -749,4 +802,21 @@ hipError_t rr_launch_gemm_fp8(const uint8_t* A, int lda, const uint8_t* W, int l
   }
 #undef RR_F8
   return hipGetLastError();
+}
+
+hipError_t rr_launch_gemm_fp8(const uint8_t* A, int lda, const uint8_t* W, int ldw, const float* bias, float scale,
+                              const float* row_scale, const float* col_scale, void* C, int ldc, int M, int N, int Kd,
+                              int epilogue, int dt, hipStream_t st, float out_mul, const float* resid, int ldr,
+                              const float* rstats, const float* rgamma, const float* rbeta) {
+  return launch_gemm8<false>(A, lda, W, ldw, bias, scale, row_scale, col_scale, C, ldc, M, N, Kd, epilogue, dt, st, out_mul, resid,
+                             ldr, rstats, rgamma, rbeta);
+}
+
+// int8 (W8A8) form: A8 / W8 hold signed codes, accumulation in int32; otherwise as rr_launch_gemm_fp8 with epilogues 0, 1, 2.
+hipError_t rr_launch_gemm_i8(const int8_t* A, int lda, const int8_t* W, int ldw, const float* bias, float scale,
+                             const float* row_scale, const float* col_scale, void* C, int ldc, int M, int N, int Kd,
+                             int epilogue, int dt, hipStream_t st) {
+  if (epilogue < 0 || epilogue > 2) return hipErrorInvalidValue;
+  return launch_gemm8<true>((const uint8_t*)A, lda, (const uint8_t*)W, ldw, bias, scale, row_scale, col_scale, C, ldc, M, N, Kd,
+                            epilogue, dt, st, 1.0f, nullptr, 0, nullptr, nullptr, nullptr);
 }

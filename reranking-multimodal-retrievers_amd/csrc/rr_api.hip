@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <algorithm>
 #include <cstring>
 #include <exception>
 #include <map>
@@ -116,6 +117,35 @@ void host_quantize_rows(const float* W, size_t rows, size_t cols, uint8_t* out, 
   }
 }
 
+// rows of W [rows, cols] -> int8 codes with one scale per row (amax / 127; a zero row gets scale 1): round to nearest even,
+// clamped to +-127 (the code range stays symmetric, -128 never occurs)
+void host_quantize_rows_i8(const float* W, size_t rows, size_t cols, int8_t* out, float* scales) {
+  for (size_t r = 0; r < rows; ++r) {
+    float amax = 0.f;
+    for (size_t k = 0; k < cols; ++k) amax = fmaxf(amax, fabsf(W[r * cols + k]));
+    const float sc = amax > 0.f ? amax * (1.0f / 127.0f) : 1.0f, inv = 1.0f / sc;
+    scales[r] = sc;
+    for (size_t k = 0; k < cols; ++k) out[r * cols + k] = (int8_t)nearbyintf(fminf(fmaxf(W[r * cols + k] * inv, -127.0f), 127.0f));
+  }
+}
+// Outlier smoothing of the int8 configuration ("gamma migration", Wei et al. 2022, Outlier Suppression): per channel j of a
+// LayerNorm that feeds an int8 GEMM, s_j = 2^round(log2(m_j / median m)) clamped to [1, 2^10], m_j = max(|gamma_j|, |beta_j|)
+// (median: element n/2 of the sorted m; ties of the rounding go up).  The quantising LayerNorm reads gamma / s, beta / s, the
+// consumer weight columns are multiplied by s before their per-channel quantisation: a power of two, so both are exact in fp32
+// and the product is unchanged before quantisation; the channels whose LayerNorm gain is an outlier stop setting the row's scale.
+void host_smooth_scales(const float* gamma, const float* beta, size_t n, float* s) {
+  std::vector<float> mv(n);
+  for (size_t j = 0; j < n; ++j) mv[j] = fmaxf(fabsf(gamma[j]), fabsf(beta[j]));
+  std::vector<float> sorted(mv);
+  std::nth_element(sorted.begin(), sorted.begin() + n / 2, sorted.end());
+  const double med = n ? (double)sorted[n / 2] : 0.0;
+  for (size_t j = 0; j < n; ++j) {
+    int e = 0;
+    if (med > 0.0 && mv[j] > 0.f) e = (int)std::floor(std::log2((double)mv[j] / med) + 0.5);
+    s[j] = ldexpf(1.0f, e < 0 ? 0 : e > 10 ? 10 : e);
+  }
+}
+
 struct HostTensor {
   std::vector<int64_t> shape;
   std::vector<float> data;
@@ -131,9 +161,12 @@ struct LayerW {
   // layer's attention-output LayerNorm.
   bf16_t *wqkv_f = nullptr, *w1_f = nullptr;
   float *cqkv_f = nullptr, *dqkv_f = nullptr, *c1_f = nullptr, *d1_f = nullptr;
-  // fp8 mode (cfg.fp8): e4m3 weights, one scale per output channel
+  // fp8 mode (cfg.fp8): e4m3 weights, one scale per output channel — int8 codes when the handle's "q8_format" is 1 (w2_8 null:
+  // FFN-down keeps 16-bit operands there)
   uint8_t *wqkv8 = nullptr, *w1_8 = nullptr, *w2_8 = nullptr;
   float *sqkv = nullptr, *s1 = nullptr, *s2 = nullptr;
+  // int8: the quantising LayerNorms' private affine gamma / s, beta / s (host_smooth_scales); residuals keep ln1g / ln2g
+  float *ln1g_q = nullptr, *ln1b_q = nullptr, *ln2g_q = nullptr, *ln2b_q = nullptr;
   // cross-attention (transformer mapping network only)
   bf16_t *wq_c = nullptr, *wkv_c = nullptr, *wo_c = nullptr;
   float *bq_c = nullptr, *bkv_c = nullptr, *bo_c = nullptr, *lncg = nullptr, *lncb = nullptr;
@@ -149,9 +182,9 @@ struct ProfEvent {
 
 // Options of a handle that change which arithmetic a forward runs (include/rerank_mi355.h, rr_set_option)
 enum RrOption { RR_OPT_LN_LITE = 0, RR_OPT_LN_FOLD, RR_OPT_CE_CLS_ONLY, RR_OPT_FP8_FFN_DOWN, RR_OPT_RESID_SPLIT, RR_OPT_ATTN_FIXED_REF,
-                RR_OPT_FP8_FIRST_LAYER, RR_OPT_FP8_QKV, RR_OPT_RESID_LO8, RR_OPT_COUNT };
+                RR_OPT_FP8_FIRST_LAYER, RR_OPT_FP8_QKV, RR_OPT_RESID_LO8, RR_OPT_Q8_FORMAT, RR_OPT_COUNT };
 static const char* const kOptionKeys[RR_OPT_COUNT] = {"ln_lite", "ln_fold", "ce_cls_only", "fp8_ffn_down", "resid_split", "attn_fixed_ref",
-                                                      "fp8_first_layer", "fp8_qkv", "resid_lo8"};
+                                                      "fp8_first_layer", "fp8_qkv", "resid_lo8", "q8_format"};
 // largest value of an option (the smallest is always -1 = "not set")
 static int option_max(int which) { return which == RR_OPT_ATTN_FIXED_REF ? 3 : which == RR_OPT_FP8_FIRST_LAYER ? 4096 : 1; }
 
@@ -193,7 +226,8 @@ struct rr_model {
   int padded_S = 0;                    // rr_set_padded_seq_len: the padded text length whose cross-encoder positions a shorter forward keeps (0 = off)
   // Per-handle numerics options (rr_set_option): -1 = follow the process-wide diagnostic switch of the same name (rr_set_tuning),
   // 0 / 1 / ... = pinned for this handle.  Two handles of one process may differ (no global state on the path).
-  int opt[RR_OPT_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
+  int opt[RR_OPT_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+  int q8_fmt = -1;                     // "q8_format" as latched by rr_finalize_weights (-1 before): 0 e4m3, 1 int8 weights were packed
   bool pinned_blocks = false;          // a stream capture was seen on this handle: outgrown blocks are retired, not freed
   std::vector<void*> retired;          // outgrown workspace / bias blocks that a captured graph may still reference; freed by rr_destroy
 
@@ -484,6 +518,33 @@ int up_fp8(rr_model* m, const std::vector<float>& W, size_t cols, uint8_t** w_ou
   return up_f32(m, sc, s_out);
 }
 
+extern int g_q8_smooth;
+// int8 ("q8_format" 1): the smoothing powers of two of a LayerNorm (all 1 with the diagnostic switch "q8_smooth" 0)
+std::vector<float> q8_smoothing(const std::vector<float>& gamma, const std::vector<float>& beta) {
+  std::vector<float> s(gamma.size(), 1.0f);
+  if (g_q8_smooth) host_smooth_scales(gamma.data(), beta.data(), gamma.size(), s.data());
+  return s;
+}
+std::vector<float> div_by(const std::vector<float>& v, const std::vector<float>& s) {
+  std::vector<float> o(v.size());
+  for (size_t j = 0; j < v.size(); ++j) o[j] = v[j] / s[j];
+  return o;
+}
+// W [N, cols] with its columns multiplied by the smoothing s [cols] -> int8 codes, one scale per output channel
+int up_i8(rr_model* m, const std::vector<float>& W, const std::vector<float>& s, uint8_t** w_out, float** s_out) {
+  const size_t cols = s.size(), rows = W.size() / cols;
+  std::vector<float> Ws(W.size());
+  for (size_t r = 0; r < rows; ++r)
+    for (size_t k = 0; k < cols; ++k) Ws[r * cols + k] = W[r * cols + k] * s[k];
+  std::vector<int8_t> q(W.size());
+  std::vector<float> sc(rows);
+  host_quantize_rows_i8(Ws.data(), rows, cols, q.data(), sc.data());
+  int rc = dev_alloc(m, (void**)w_out, q.size());
+  if (rc) return rc;
+  RR_HIP(m, hipMemcpy(*w_out, q.data(), q.size(), hipMemcpyHostToDevice));
+  return up_f32(m, sc, s_out);
+}
+
 // prev_ln: state_dict prefix of the LayerNorm whose output feeds this layer's QKV ("" = none: first layer of a stack)
 int pack_layer(rr_model* m, const std::string& p, int heads, int Hd, bool cross, LayerW* L, const std::string& prev_ln = "") {
   const float qs = 1.4426950408889634f / sqrtf((float)(Hd / heads));   // log2(e)/sqrt(dh): the attention kernels take base-2 exponentials of Q K^T as it is
@@ -507,7 +568,23 @@ int pack_layer(rr_model* m, const std::string& p, int heads, int Hd, bool cross,
   }
   RR_TRY(up_bf16(m, HT(m, p + ".intermediate.dense.weight"), &L->w1));
   RR_TRY(up_f32(m, HT(m, p + ".intermediate.dense.bias"), &L->b1));
-  if (!cross && m->cfg.fp8) {
+  if (!cross && m->cfg.fp8 && m->q8_fmt == 1) {
+    // int8: FFN-up behind this layer's attention-output LayerNorm; QKV behind the previous layer's output LayerNorm (none in
+    // front of the first layer of a stack, whose QKV never takes int8 operands: packed unsmoothed); this layer's output
+    // LayerNorm gets its private affine for the next layer's QKV
+    const std::vector<float>&g1 = HT(m, a + ".output.LayerNorm.weight"), &b1 = HT(m, a + ".output.LayerNorm.bias");
+    const std::vector<float>&g2 = HT(m, p + ".output.LayerNorm.weight"), &b2 = HT(m, p + ".output.LayerNorm.bias");
+    const std::vector<float> s1 = q8_smoothing(g1, b1), s2 = q8_smoothing(g2, b2);
+    const std::vector<float> sp = prev_ln.empty() ? std::vector<float>((size_t)Hd, 1.0f)
+                                                  : q8_smoothing(HT(m, prev_ln + ".weight"), HT(m, prev_ln + ".bias"));
+    RR_TRY(up_i8(m, cat({&HT(m, a + ".self.query.weight"), &HT(m, a + ".self.key.weight"), &HT(m, a + ".self.value.weight")}, qs),
+                 sp, &L->wqkv8, &L->sqkv));
+    RR_TRY(up_i8(m, HT(m, p + ".intermediate.dense.weight"), s1, &L->w1_8, &L->s1));
+    RR_TRY(up_f32(m, div_by(g1, s1), &L->ln1g_q));
+    RR_TRY(up_f32(m, div_by(b1, s1), &L->ln1b_q));
+    RR_TRY(up_f32(m, div_by(g2, s2), &L->ln2g_q));
+    RR_TRY(up_f32(m, div_by(b2, s2), &L->ln2b_q));
+  } else if (!cross && m->cfg.fp8) {
     RR_TRY(up_fp8(m, cat({&HT(m, a + ".self.query.weight"), &HT(m, a + ".self.key.weight"), &HT(m, a + ".self.value.weight")}, qs),
                   (size_t)Hd, &L->wqkv8, &L->sqkv));
     RR_TRY(up_fp8(m, HT(m, p + ".intermediate.dense.weight"), (size_t)Hd, &L->w1_8, &L->s1));
@@ -771,7 +848,22 @@ int g_fp8_ffn_down = 0;                  // tuning (rr_set_tuning "fp8_ffn_down"
 // roundings fall (the degree of the GELU polynomial moved it from 0.137 to 0.193) — no margin; with one it is 0.09 - 0.10.
 int g_fp8_first_layer = -1;
 constexpr int FP8_SAFE_LAYERS = 1;
-inline int fp8_first_layer_of(int opt, int layers) { return opt >= 0 ? (opt < layers ? opt : layers) : (layers > FP8_SAFE_LAYERS ? layers - FP8_SAFE_LAYERS : 0); }
+// The default for int8 handles ("q8_format" 1): the last INT8_SAFE_LAYERS layers, the largest suffix that ranks with margin on the
+// c5 ranking fixtures (tests/tools/int8_subset_study.py, profiles/r06_int8_subset_study.json; DESIGN.md "int8").  TWELVE: on the binding
+// list c5_sep_wide q0 the centred drift is 0.150 with 12 int8 layers, 0.206 with 18 and 0.197 with all 24, against a half-gap of
+// 0.180 (16 / 8 layers: 0.100 / 0.074) — the whole stack does not rank with margin, twelve layers do.
+constexpr int INT8_SAFE_LAYERS = 12;
+inline int fp8_first_layer_of(int opt, int layers, bool i8 = false) {
+  const int safe = i8 ? INT8_SAFE_LAYERS : FP8_SAFE_LAYERS;
+  return opt >= 0 ? (opt < layers ? opt : layers) : (layers > safe ? layers - safe : 0);
+}
+// tuning / option "q8_format": the 8-bit operand format of rr_config.fp8 — 0 e4m3 (block-scaled MFMA), 1 int8 (W8A8: int8 MFMA,
+// int32 accumulation, per-row activation / per-channel weight scales, LayerNorm gains migrated into the weights).  Latched by
+// rr_finalize_weights, which packs the weights in that one format.
+int g_q8_format = 0;
+// tuning "q8_smooth" (diagnostic, read by rr_finalize_weights): 1 = the int8 packer migrates LayerNorm gain outliers into the
+// consumer weights (host_smooth_scales), 0 = plain per-channel int8 (shows what the smoothing is worth)
+int g_q8_smooth = 1;
 int g_fp8_qkv = 1;                       // tuning / option "fp8_qkv": 0 = only the FFN of an fp8 layer takes e4m3 operands, its QKV projection stays 16-bit
 constexpr float FP8_GELU_MUL = 8.0f;     // static scale of the e4m3 GELU output feeding it
 int g_ln_fold = 1;   // tuning (rr_set_tuning "ln_fold"): 1 = LayerNorm folded into the consumer GEMMs, 0 = LayerNorm kernels
@@ -801,6 +893,7 @@ inline int opt_of(const rr_model* m, int which) {
     case RR_OPT_FP8_FIRST_LAYER: return g_fp8_first_layer;
     case RR_OPT_FP8_QKV: return g_fp8_qkv;
     case RR_OPT_RESID_LO8: return g_resid_lo8;
+    case RR_OPT_Q8_FORMAT: return m->q8_fmt >= 0 ? m->q8_fmt : g_q8_format;
     default: return -1;      // RR_OPT_ATTN_FIXED_REF: -1 lets the attention launcher take its own process-wide mode
   }
 }
@@ -815,11 +908,18 @@ inline int opt_of(const rr_model* m, int which) {
 // (attention output, FFN down) write their fp32 rows, the same rows in 16 bits and per-row statistics partials; a
 // rows x 8-byte finalize merges the partials; QKV / FFN-up read the raw 16-bit rows and apply (mean, rstd) in their
 // epilogue: LN(x) W^T + b = rstd (x W'^T - mean c) + d.
-enum OperandKind { OP_NORMALISED = 0, OP_RAW_FOLDED = 1, OP_E4M3 = 2 };   // what w.h16 holds on entry to a layer (see run_layer)
+enum OperandKind { OP_NORMALISED = 0, OP_RAW_FOLDED = 1, OP_E4M3 = 2 };   // what w.h16 holds on entry to a layer (see run_layer; OP_E4M3: the 8-bit codes of "q8_format")
 
 #define RR_GEMM_FP8(m, st, A8, lda, W8, bias, rsc, csc, C, ldc, M, N, K, epi)                                       \
   RR_RUN(m, st, RR_K_GEMM_FP8, gemm_flops(M, N, K), 1.0 * (M) * (K) + 1.0 * (N) * (K) + 2.0 * (M) * (N) + 4.0 * (M), \
-         rr_launch_gemm_fp8((const uint8_t*)(A8), lda, W8, K, bias, 1.0f, rsc, csc, C, ldc, M, N, K, epi, m->dt, st))
+         (m)->q8_fmt == 1                                                                                              \
+             ? rr_launch_gemm_i8((const int8_t*)(A8), lda, (const int8_t*)(W8), K, bias, 1.0f, rsc, csc, C, ldc, M, N, K, epi, m->dt, st) \
+             : rr_launch_gemm_fp8((const uint8_t*)(A8), lda, W8, K, bias, 1.0f, rsc, csc, C, ldc, M, N, K, epi, m->dt, st))
+// the LayerNorm that quantises a GEMM operand: e4m3 with the true affine, int8 with its private (smoothed) one
+#define RR_LN_Q8(m, st, x, L, which, eps, rows, Hd, stats)                                                              \
+  RR_RUN(m, st, RR_K_LAYERNORM, 0.0, 5.0 * (rows) * (Hd),                                                              \
+         (m)->q8_fmt == 1 ? rr_launch_layernorm_i8(x, (L).which##g_q, (L).which##b_q, eps, rows, Hd, (int8_t*)w.h16, w.rowscale, stats, st) \
+                          : rr_launch_layernorm_q8(x, (L).which##g, (L).which##b, eps, rows, Hd, (uint8_t*)w.h16, w.rowscale, stats, st))
 
 // Packed execution (rr_forward_packed): the pairs of a call are grouped into SEGMENTS of equal row length; a segment's pairs
 // lie back to back in every activation buffer, the segments one after the other, so the row-wise kernels (every GEMM, the
@@ -903,13 +1003,14 @@ int run_layer(rr_model* m, hipStream_t st, const LayerW& L, int batch, int Tseq,
     // configs[4]: the two LayerNorm outputs are quantised to e4m3 (one scale per row) by the LayerNorm kernel itself and
     // feed FFN-up / the next layer's QKV on the block-scaled matrix core; attention output and FFN-down stay 16-bit
     RR_GEMM_LN(m, st, w.ctx, Hd, L.wo, L.bo, rs, w.pre, Hd, rows, Hd, Hd, 4.0);
-    RR_RUN(m, st, RR_K_LAYERNORM, 0.0, 5.0 * rows * Hd,
-           rr_launch_layernorm_q8(w.pre, L.ln1g, L.ln1b, eps, rows, Hd, (uint8_t*)w.h16, w.rowscale, w.stats_a, st));
+    RR_LN_Q8(m, st, w.pre, L, ln1, eps, rows, Hd, w.stats_a);
     const ResidSrc r1{w.pre, w.stats_a, L.ln1g, L.ln1b};
     // FFN-down on the e4m3 ring as well (rr_set_tuning "fp8_ffn_down", default 1) where both GEMMs of the FFN run the
     // persistent kernel: the GELU epilogue of FFN-up emits e4m3 bytes under ONE static power-of-two scale (GELU's range is
     // [-0.17, max pre-activation]: x 8 keeps 3 mantissa bits down to 2e-3 and saturates at 56), FFN-down multiplies its
     // accumulators by 1/8 and its per-channel weight scales and adds the LayerNorm-recomputed residual row in its epilogue
+    if (m->q8_fmt == 1 && opt_of(m, RR_OPT_FP8_FFN_DOWN))
+      return fail(m, RR_ERR_BAD_ARG, "fp8_ffn_down = 1 needs q8_format 0 (there is no int8 FFN-down)");
     const bool down8 = opt_of(m, RR_OPT_FP8_FFN_DOWN) && L.w2_8 && (I % 128 == 0) && rr_gemm_fp8_ring_ok(rows, I, Hd) && rr_gemm_fp8_ring_ok(rows, Hd, I);
     if (down8) {
       RR_RUN(m, st, RR_K_GEMM_FP8, gemm_flops(rows, I, Hd), 1.0 * rows * Hd + 1.0 * I * Hd + 1.0 * rows * I + 4.0 * rows,
@@ -928,8 +1029,7 @@ int run_layer(rr_model* m, hipStream_t st, const LayerW& L, int batch, int Tseq,
                                        m->dt, st));
       in_kind = OP_NORMALISED;
     } else {
-      RR_RUN(m, st, RR_K_LAYERNORM, 0.0, 5.0 * rows * Hd,
-             rr_launch_layernorm_q8(w.pre2, L.ln2g, L.ln2b, eps, rows, Hd, (uint8_t*)w.h16, w.rowscale, w.stats_b, st));
+      RR_LN_Q8(m, st, w.pre2, L, ln2, eps, rows, Hd, w.stats_b);
       in_kind = OP_E4M3;
     }
     rs = ResidSrc{w.pre2, w.stats_b, L.ln2g, L.ln2b};
@@ -1300,6 +1400,12 @@ static int rr_finalize_weights_impl(rr_handle h) {
     RR_HIP(m, hipHostMalloc((void**)&m->range_flag_host, sizeof(int), hipHostMallocDefault));
     *m->range_flag_host = 0;
   }
+  {
+    const int q8 = opt_of(m, RR_OPT_Q8_FORMAT);
+    if (c.fp8 && q8 == 1 && opt_of(m, RR_OPT_FP8_FFN_DOWN) == 1)
+      return fail(m, RR_ERR_BAD_ARG, "fp8_ffn_down = 1 needs q8_format 0 (there is no int8 FFN-down)");
+    m->q8_fmt = q8;                       // latched: the 8-bit weights below are packed in this one format
+  }
   if (c.model_kind != RR_MODEL_FULL_CONTEXT) {
     RR_TRY(up_bf16(m, HT(m, "cross_encoder_input_mapping.weight"), &m->w_cemap));
     RR_TRY(up_f32(m, HT(m, "cross_encoder_input_mapping.bias"), &m->b_cemap));
@@ -1609,7 +1715,7 @@ static int forward_full(rr_handle h, const int64_t* input_ids, const int64_t* at
   {
     ResidSrc rs{w.h32, nullptr, nullptr, nullptr};      // embeddings LayerNorm output, materialised
     int folded = OP_NORMALISED;
-    const int fp8_from = c.fp8 ? fp8_first_layer_of(opt_of(m, RR_OPT_FP8_FIRST_LAYER), c.layers) : 0;   // layers below it keep 16-bit operands
+    const int fp8_from = c.fp8 ? fp8_first_layer_of(opt_of(m, RR_OPT_FP8_FIRST_LAYER), c.layers, m->q8_fmt == 1) : 0;   // layers below it keep 16-bit operands
     for (int l = 0; l < c.layers; ++l)                    // the last layer's normalised rows feed the 768 -> 128 projection
       RR_TRY(run_layer(m, st, m->text_layers[l], n, S, Hd, c.heads, I, c.ln_eps, w.text_bias, w, rs, folded,
                        l == c.layers - 1, m->debug, nullptr, 0, tv, c.fp8 ? (l >= fp8_from ? 1 : 0) : -1,
@@ -1979,6 +2085,12 @@ int rr_set_option(rr_handle h, const char* key, int value) {
     if (i < 0) return fail(h, RR_ERR_BAD_ARG, "rr_set_option: unknown key '%s'", key ? key : "(null)");
     if (value < -1 || value > option_max(i))
       return fail(h, RR_ERR_BAD_ARG, "rr_set_option: %s = %d out of range", key, value);
+    if (i == RR_OPT_Q8_FORMAT && h->q8_fmt >= 0 && (value < 0 ? g_q8_format : value) != h->q8_fmt)
+      return fail(h, RR_ERR_BAD_ARG, "rr_set_option: q8_format is latched by rr_finalize_weights (the weights are packed as %s)",
+                  h->q8_fmt ? "int8" : "e4m3");
+    if (h->cfg.fp8 && value == 1 && ((i == RR_OPT_FP8_FFN_DOWN && opt_of(h, RR_OPT_Q8_FORMAT) == 1) ||
+                                     (i == RR_OPT_Q8_FORMAT && opt_of(h, RR_OPT_FP8_FFN_DOWN) == 1)))
+      return fail(h, RR_ERR_BAD_ARG, "rr_set_option: fp8_ffn_down = 1 needs q8_format 0 (there is no int8 FFN-down)");
     h->opt[i] = value;
     return RR_OK;
   });
@@ -1992,7 +2104,7 @@ int rr_get_option(rr_handle h, const char* key, int* value_out) {
     // a reader is shown that mode
     const int v = opt_of(h, i);
     *value_out = (i == RR_OPT_ATTN_FIXED_REF && v < 0) ? rr_get_attn_fixed_ref()
-                 : i == RR_OPT_FP8_FIRST_LAYER ? fp8_first_layer_of(v, h->cfg.layers)
+                 : i == RR_OPT_FP8_FIRST_LAYER ? fp8_first_layer_of(v, h->cfg.layers, opt_of(h, RR_OPT_Q8_FORMAT) == 1)
                  : i == RR_OPT_RESID_LO8 ? (int)resid_lo8_of(v, h->dt) : v;
     return RR_OK;
   });
@@ -2006,6 +2118,8 @@ int rr_set_tuning(const char* key, int value) {
   if (!strcmp(key, "fp8_ffn_down")) { g_fp8_ffn_down = value != 0; return RR_OK; }
   if (!strcmp(key, "fp8_first_layer")) { g_fp8_first_layer = value < 0 ? -1 : value; return RR_OK; }
   if (!strcmp(key, "fp8_qkv")) { g_fp8_qkv = value != 0; return RR_OK; }
+  if (!strcmp(key, "q8_format")) { if (value < 0 || value > 1) return RR_ERR_BAD_ARG; g_q8_format = value; return RR_OK; }
+  if (!strcmp(key, "q8_smooth")) { g_q8_smooth = value != 0; return RR_OK; }
   if (!strcmp(key, "ce_cls_only")) { g_ce_cls_only = value != 0; return RR_OK; }
   if (!strcmp(key, "persistent_gemm")) return rr_set_gemm_persistent(value);
   if (!strcmp(key, "resid_touch")) return rr_set_resid_touch(value);
@@ -2073,6 +2187,20 @@ static int rr_op_layernorm_q8_impl(const float* x, const float* gamma, const flo
                                    uint8_t* out8, float* row_scale, float* stats, void* hip_stream) {
   if (!x || !gamma || !beta || !out8 || !row_scale) return RR_ERR_BAD_ARG;
   hipError_t e = rr_launch_layernorm_q8(x, gamma, beta, eps, rows, cols, out8, row_scale, stats, (hipStream_t)hip_stream);
+  return e == hipSuccess ? RR_OK : (e == hipErrorInvalidValue ? RR_ERR_BAD_SHAPE : RR_ERR_HIP);
+}
+static int rr_op_gemm_i8_rc_impl(const int8_t* A8, const int8_t* W8, const float* bias, const float* row_scale,
+                                 const float* col_scale, int M, int N, int K, int epilogue, void* out, void* hip_stream) {
+  if (!A8 || !W8 || !out) return RR_ERR_BAD_ARG;
+  if (epilogue < 0 || epilogue > 2) return RR_ERR_BAD_ARG;
+  hipError_t e = rr_launch_gemm_i8(A8, K, W8, K, bias, 1.0f, row_scale, col_scale, out, N, M, N, K, epilogue, g_op_dt,
+                                   (hipStream_t)hip_stream);
+  return e == hipSuccess ? RR_OK : (e == hipErrorInvalidValue ? RR_ERR_BAD_SHAPE : RR_ERR_HIP);
+}
+static int rr_op_layernorm_i8_impl(const float* x, const float* gamma, const float* beta, float eps, int rows, int cols,
+                                   int8_t* out8, float* row_scale, float* stats, void* hip_stream) {
+  if (!x || !gamma || !beta || !out8 || !row_scale) return RR_ERR_BAD_ARG;
+  hipError_t e = rr_launch_layernorm_i8(x, gamma, beta, eps, rows, cols, out8, row_scale, stats, (hipStream_t)hip_stream);
   return e == hipSuccess ? RR_OK : (e == hipErrorInvalidValue ? RR_ERR_BAD_SHAPE : RR_ERR_HIP);
 }
 static int rr_op_quantize_fp8_impl(const void* x, int x_is_f32, float scale, uint8_t* out, size_t n, void* hip_stream) {
@@ -2284,6 +2412,22 @@ int rr_op_layernorm_q8(const float* x, const float* gamma, const float* beta, fl
 int rr_util_quantize_rows_e4m3(const float* w_host, int rows, int cols, uint8_t* out_host, float* scales_host) {
   if (!w_host || !out_host || !scales_host || rows <= 0 || cols <= 0) return RR_ERR_BAD_ARG;
   return guarded(nullptr, [&]() -> int { host_quantize_rows(w_host, (size_t)rows, (size_t)cols, out_host, scales_host); return RR_OK; });
+}
+int rr_op_gemm_i8_rc(const int8_t* A8, const int8_t* W8, const float* bias, const float* row_scale, const float* col_scale,
+                     int M, int N, int K, int epilogue, void* out, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_gemm_i8_rc_impl(A8, W8, bias, row_scale, col_scale, M, N, K, epilogue, out, hip_stream); });
+}
+int rr_op_layernorm_i8(const float* x, const float* gamma, const float* beta, float eps, int rows, int cols, int8_t* out8,
+                       float* row_scale, float* stats, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_layernorm_i8_impl(x, gamma, beta, eps, rows, cols, out8, row_scale, stats, hip_stream); });
+}
+int rr_util_quantize_rows_i8(const float* w_host, int rows, int cols, int8_t* out_host, float* scales_host) {
+  if (!w_host || !out_host || !scales_host || rows <= 0 || cols <= 0) return RR_ERR_BAD_ARG;
+  return guarded(nullptr, [&]() -> int { host_quantize_rows_i8(w_host, (size_t)rows, (size_t)cols, out_host, scales_host); return RR_OK; });
+}
+int rr_util_smooth_scales(const float* gamma_host, const float* beta_host, int n, float* s_host) {
+  if (!gamma_host || !beta_host || !s_host || n <= 0) return RR_ERR_BAD_ARG;
+  return guarded(nullptr, [&]() -> int { host_smooth_scales(gamma_host, beta_host, (size_t)n, s_host); return RR_OK; });
 }
 int rr_activation_range_flag(rr_handle h, int reset, int* flag_out, void* hip_stream) {
   if (!h || !flag_out) return RR_ERR_BAD_ARG;

@@ -384,6 +384,12 @@ hipError_t rr_launch_gemm_fp8(const uint8_t* A, int lda, const uint8_t* W, int l
 bool rr_gemm_fp8_ring_ok(int M, int N, int Kd);   // the shapes whose e4m3 GEMM runs on the persistent ring (epilogues 3 / 4 exist there only)
 hipError_t rr_launch_layernorm_q8(const float* x, const float* gamma, const float* beta, float eps, int rows, int cols,
                                   uint8_t* out8, float* row_scale, float* stats_out, hipStream_t st);
+// int8 forms (W8A8, handle option "q8_format" = 1): signed codes, one scale per row / output channel, epilogues 0 - 2 only
+hipError_t rr_launch_gemm_i8(const int8_t* A, int lda, const int8_t* W, int ldw, const float* bias, float scale,
+                             const float* row_scale, const float* col_scale, void* C, int ldc, int M, int N, int Kd,
+                             int epilogue, int dt, hipStream_t st);
+hipError_t rr_launch_layernorm_i8(const float* x, const float* gamma, const float* beta, float eps, int rows, int cols,
+                                  int8_t* out8, float* row_scale, float* stats_out, hipStream_t st);
 
 // Multi-head attention, head dim 64.  q rows: q + (bq*Tq + t)*q_stride + head*64, where
 // bq = (b + q_batch_off) / q_batch_div;  k,v rows: (b*Tk + t)*kv_stride + head*64;  key_bias [B,Tk] f32 additive

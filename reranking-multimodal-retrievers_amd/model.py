@@ -219,6 +219,8 @@ class RerankEngine:
         L.check(self.lib.rr_create(C.byref(c), C.byref(h)), None, "rr_create")
         self.h = h
         self.finalized = False
+        if arch.get("q8_format") is not None:      # 8-bit operand format of rr_config.fp8 (0 e4m3, 1 int8): latched at finalize
+            self.set_option("q8_format", int(arch["q8_format"]))
 
     def __del__(self):
         h = getattr(self, "h", None)
@@ -568,10 +570,13 @@ class RerankEngine:
 
     def set_option(self, key: str, value: int):
         """Pin a numerics option of THIS engine (rr_set_option: "ln_lite", "ln_fold", "resid_split", "resid_lo8", "ce_cls_only",
-        "fp8_ffn_down", "fp8_first_layer", "fp8_qkv", "attn_fixed_ref"); -1 = follow the process-wide diagnostic switch again."""
+        "fp8_ffn_down", "fp8_first_layer", "fp8_qkv", "q8_format", "attn_fixed_ref"); -1 = follow the process-wide diagnostic
+        switch again.  "q8_format" (0 e4m3, 1 int8; also arch["q8_format"]) is latched by load_state_dict: changing it afterwards
+        raises."""
         L.check(self.lib.rr_set_option(self.h, key.encode(), int(value)), self.h, "rr_set_option")
 
     def get_option(self, key: str) -> int:
+        """The EFFECTIVE value of a numerics option (rr_get_option; keys as set_option, "q8_format" included)."""
         import ctypes
         v = ctypes.c_int(0)
         L.check(self.lib.rr_get_option(self.h, key.encode(), ctypes.byref(v)), self.h, "rr_get_option")

@@ -362,6 +362,61 @@ int rr_forward_interaction_fusion(rr_handle h, const float* query_li, const floa
 int rr_head(rr_handle h, const float* logits, const float* logits2, const float* labels, int Bq, int K,
             float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream);
 
+/* rr_forward_joint_packed / rr_forward_interaction_packed: rr_forward_joint(_fusion) and rr_forward_interaction(_fusion) over
+ * PACKED rows, with the conventions of rr_forward_packed: the caller groups the pairs into n_segments (1..64) segments of equal
+ * length seg_len[i] (every pair's non-pad positions must fit it), hands over the per-pair tensors segment after segment and,
+ * inside a segment, pair after pair at THAT length, and gets logits_out (/ logits2_out) DEVICE float32 [n] in that packed pair
+ * order back; it scatters them and runs the head (rr_head_joint / rr_head) on the [Bq, K] block.  Per-query tensors are handed
+ * over PER PAIR in packed order.  preflmr_scores (NULL = no attention fusion) stays PADDED along the context axis, in packed
+ * pair order: the reference's softmax over the context tokens runs over the whole padded axis (rerank_model.py:305,
+ * interaction_rerank_model.py:134), so the bias of a shorter pair still needs the scores of its pad positions.
+ * For rr_reserve count n_queries = n_pairs; with_fusion covers the packed bias.  No reference counterpart (it pads).
+ * RR_ERR_BAD_SHAPE: more than 64 segments, an empty segment, a length above the padded length.
+ *
+ * rr_forward_joint_packed (Python: RerankEngine.forward_joint_packed):
+ *   joint_input_ids / joint_attention_mask : DEVICE int64, sum_i seg_pairs[i] * seg_len[i] entries, the first seg_len[i]
+ *       columns of the [query_len | context] joint sequence rr_forward_joint takes (padded_seq_len columns there);
+ *   image_cls / image_patches : DEVICE float32 [n, vision_hidden] / [n, n_patches, vision_hidden] (mandatory, as for
+ *       rr_forward_joint);
+ *   preflmr_scores : DEVICE float32 [n, padded_seq_len - query_len, query_len + prefix_len + n_patches] — the context rows
+ *       (2 .. 2 + padded_seq_len - query_len) of rr_forward_joint_fusion's scores.
+ *   Every seg_len[i] must exceed query_len (the whole query part is kept) and reach the mapping network's cross-attention
+ *   window min(padded_seq_len, 32) (RR_ERR_BAD_SHAPE).  The joint sequence [query | image | context] is padded at its end,
+ *   so no position moves, and the text encoder, the masks, the fusion bias and the cross encoder compute what the padded call
+ *   computes for every pair.  NOT bit for bit in general: image features are per pair here, so the mapping network's first
+ *   layer runs its GEMMs over n instead of Bq queries' rows, and a GEMM of another row count may run other tile shapes with
+ *   another fp32 summation order (as in rr_forward_packed with vision tokens).  Measured with "resid_split" = 0: bit for bit
+ *   on the 6-pair fixtures, 9.8e-5 (1.6e-4 with fusion) at 200 pairs of the c3 geometry — within the 1e-3 parity gate
+ *   (tests/test_gpu_packed_families.py).
+ * rr_forward_interaction_packed (Python: RerankEngine.forward_interaction_packed), NORMAL and MORES handles:
+ *   query_li [n, Lq, li_dim], query_mask [n, Lq] : DEVICE float32 per pair;
+ *   context_li [sum seg_pairs[i] * seg_len[i], li_dim], context_mask [sum seg_pairs[i] * seg_len[i]] : DEVICE float32, the
+ *       first seg_len[i] context tokens of every pair;
+ *   preflmr_scores : DEVICE float32 [n, padded_context_len, Lq] (NORMAL only: MORES returns RR_ERR_UNSUPPORTED as
+ *       rr_forward_interaction_fusion does, mores_model.py:72-73).
+ *   NORMAL: Lq + padded_context_len must not exceed ce_max_pos (RR_ERR_BAD_SHAPE).  MORES: the query side keeps its n * Lq
+ *   rows; the doc-side Linear, every layer's K / V projection and the cross-attention (per segment, Tk = seg_len) run over the
+ *   packed doc rows.  A pair's logits equal rr_forward_interaction(_fusion)'s for it BIT FOR BIT, NORMAL with and without
+ *   fusion and MORES, while "resid_split" = 0 (or both calls are on the same side of its row-count rule): padding sits at the
+ *   end of [query | context], no position moves, the attention of a packed call runs the schedule the padded call's grid
+ *   selects, and a fusion bias always runs the online form, as in the padded call (tests/test_gpu_packed_families.py: the
+ *   fixtures and 200 pairs of the int_base geometry). */
+int rr_forward_joint_packed(rr_handle h, const int64_t* joint_input_ids, const int64_t* joint_attention_mask,
+                            const float* image_cls, const float* image_patches, const float* preflmr_scores,
+                            float fusion_multiplier, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len,
+                            int padded_seq_len, int query_len, int64_t instruction_token_id,
+                            float* logits_out, float* logits2_out, void* hip_stream);
+int rr_forward_interaction_packed(rr_handle h, const float* query_li, const float* context_li, const float* query_mask,
+                                  const float* context_mask, const float* preflmr_scores, float fusion_multiplier,
+                                  int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int padded_context_len,
+                                  int Lq, float* logits_out, float* logits2_out, void* hip_stream);
+
+/* rr_head_joint: rr_head with the head RerankModel.forward runs (rr_forward_joint): `loss_fn(logits, logits)`
+ * (rerank_model.py:328) — the labels are the logits themselves (2H_BCE: the two heads as class-probability targets).  The
+ * head of a packed joint call, after the scatter.  negative_sampling with loss_out: RR_ERR_UNSUPPORTED, as rr_forward_joint. */
+int rr_head_joint(rr_handle h, const float* logits, const float* logits2, int Bq, int K, float* loss_out, float* scores_out,
+                  int32_t* order_out, void* hip_stream);
+
 /* ---- Host-side pair-input assembly (no GPU involved): WordPiece tokenisation of the (query, candidate) texts into the
  * int64 [N, S] tensors rr_forward takes.  Replaces prepare_full_context_inputs (src/models/rerank/utils.py:129-167) and
  * the BertTokenizer encode / decode / batch_encode_plus calls under it (transformers 4.38.2 slow tokenizer semantics).

@@ -64,6 +64,10 @@ _SIGS = {
     "rr_reserve": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "rr_activation_range_flag": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), _P]),
     "rr_forward_packed": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
+    "rr_forward_joint_packed": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_float, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int64,
+                                          _P, _P, _P]),
+    "rr_forward_interaction_packed": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_float, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P,
+                                                _P]),
     "rr_forward": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int,
                              _P, _P, _P, _P, _P, _P]),
     "rr_encode_image": (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
@@ -76,6 +80,7 @@ _SIGS = {
     "rr_forward_interaction_fusion": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P,
                                                 C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "rr_head": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "rr_head_joint": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "rr_debug_read": (C.c_int64, [_P, C.c_char_p, _P, C.c_int64]),
     "rr_set_debug": (C.c_int, [_P, C.c_int]),
     "rr_set_profiling": (C.c_int, [_P, C.c_int]),

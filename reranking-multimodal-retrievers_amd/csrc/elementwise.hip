@@ -381,12 +381,13 @@ __global__ __launch_bounds__(256) void vit_embed_ln_kernel(const float* __restri
 //   kc < Tc = S - ql.  One workgroup per pair.
 // `row0` = first score row that belongs to the sequence (2 for the joint RerankModel sequence, 0 for the Interaction
 // reranker, interaction_rerank_model.py:131-142, whose scores are [N, Lc, Lq] already).
-__global__ __launch_bounds__(256) void fusion_adj_kernel(const float* __restrict__ scores, int S, int Tq, int Tc, float mult,
-                                                         int pair0, float* __restrict__ adj, int ld, int row0) {
-  extern __shared__ float colstat[];                 // [Tq] max, [Tq] 1/sum
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* ts = scores + ((size_t)(pair0 + b) * S + row0) * Tq;
-  float* A = adj + (size_t)b * (Tq + Tc) * ld;
+// `Tk` <= Tc: context tokens the bias is WRITTEN for (packed calls, rr_forward_*_packed: a segment's pairs end after Tk
+// context tokens, the bias of a pair is [Tq + Tk][ld]); the softmax over the context tokens still runs over all Tc of the
+// padded sequence, as the reference normalises (rerank_model.py:305, interaction_rerank_model.py:134).  Tk = Tc: the
+// padded call.  One workgroup builds the bias A of one pair from its scores ts.
+__device__ __forceinline__ void fusion_adj_pair(const float* __restrict__ ts, float* __restrict__ A, int Tq, int Tc, int Tk, int ld,
+                                                float mult, float* colstat) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int i = tid; i < Tq; i += 256) {              // column statistics (softmax over the context tokens)
     float mx = -INFINITY;
     for (int kc = 0; kc < Tc; ++kc) mx = fmaxf(mx, ts[(size_t)kc * Tq + i]);
@@ -401,10 +402,10 @@ __global__ __launch_bounds__(256) void fusion_adj_kernel(const float* __restrict
     const float mx = colstat[i], inv = colstat[Tq + i];
     for (int j = lane; j < ld; j += 64) {
       const int kc = j - Tq;
-      row[j] = (kc >= 0 && kc < Tc) ? mult * (expf(ts[(size_t)kc * Tq + i] - mx) * inv) : 0.f;
+      row[j] = (kc >= 0 && kc < Tk) ? mult * (expf(ts[(size_t)kc * Tq + i] - mx) * inv) : 0.f;
     }
   }
-  for (int kc = wave; kc < Tc; kc += 4) {            // lower rows: [softmax over query/image tokens | 0]
+  for (int kc = wave; kc < Tk; kc += 4) {            // lower rows: [softmax over query/image tokens | 0]
     const float* r = ts + (size_t)kc * Tq;
     float mx = -INFINITY;
     for (int j = lane; j < Tq; j += 64) mx = fmaxf(mx, r[j]);
@@ -416,6 +417,32 @@ __global__ __launch_bounds__(256) void fusion_adj_kernel(const float* __restrict
     float* row = A + (size_t)(Tq + kc) * ld;
     for (int j = lane; j < ld; j += 64) row[j] = j < Tq ? mult * (expf(r[j] - mx) * inv) : 0.f;
   }
+}
+
+__global__ __launch_bounds__(256) void fusion_adj_kernel(const float* __restrict__ scores, int S, int Tq, int Tc, float mult,
+                                                         int pair0, float* __restrict__ adj, int ld, int row0) {
+  extern __shared__ float colstat[];                 // [Tq] max, [Tq] 1/sum
+  const int b = blockIdx.x;
+  fusion_adj_pair(scores + ((size_t)(pair0 + b) * S + row0) * Tq, adj + (size_t)b * (Tq + Tc) * ld, Tq, Tc, Tc, ld, mult, colstat);
+}
+
+// Packed calls: ONE launch over all pairs of all segments (a launch per segment would leave the chip nearly idle: a segment
+// holds a few dozen pairs, one workgroup each).  Segment s holds pairs [p_end[s-1], p_end[s]) of the packed order, writes
+// [Tq + tk[s]][ld[s]] per pair from float off[s] of adj on.
+struct FusionSegs {
+  int nseg;
+  int p_end[RR_FUSION_MAX_SEGS], tk[RR_FUSION_MAX_SEGS], ld[RR_FUSION_MAX_SEGS];
+  long long off[RR_FUSION_MAX_SEGS];
+};
+__global__ __launch_bounds__(256) void fusion_adj_segs_kernel(const float* __restrict__ scores, int S, int Tq, int Tc, float mult,
+                                                              float* __restrict__ adj, int row0, FusionSegs t) {
+  extern __shared__ float colstat[];
+  const int b = blockIdx.x;
+  int s = 0;
+  while (s + 1 < t.nseg && b >= t.p_end[s]) ++s;
+  const int p0 = s ? t.p_end[s - 1] : 0, Tk = t.tk[s], ld = t.ld[s];
+  fusion_adj_pair(scores + ((size_t)b * S + row0) * Tq, adj + t.off[s] + (size_t)(b - p0) * (Tq + Tk) * ld, Tq, Tc, Tk, ld, mult,
+                  colstat);
 }
 
 // ---- interaction rerankers: key bias over the concatenated [query tokens | context tokens] sequence from the
@@ -617,6 +644,28 @@ hipError_t rr_launch_fusion_adj(const float* scores, int S, int Tq, int Tc, floa
   if (n <= 0 || Tq <= 0 || Tc <= 0 || row0 < 0 || row0 + Tc > S || ld < Tq + Tc || (ld & 63) || Tq > 8192) return hipErrorInvalidValue;
   hipLaunchKernelGGL(fusion_adj_kernel, dim3(n), dim3(256), 2 * Tq * sizeof(float), st, scores, S, Tq, Tc, mult, pair0, adj, ld,
                      row0);
+  return hipGetLastError();
+}
+
+hipError_t rr_launch_fusion_adj_segs(const float* scores, int S, int Tq, int Tc, float mult, int nseg, const int* seg_n,
+                                     const int* seg_tk, float* adj, hipStream_t st, int row0) {
+  if (nseg <= 0 || nseg > RR_FUSION_MAX_SEGS || Tq <= 0 || Tc <= 0 || row0 < 0 || row0 + Tc > S || Tq > 8192)
+    return hipErrorInvalidValue;
+  FusionSegs t{};
+  t.nseg = nseg;
+  long long pairs = 0, off = 0;
+  for (int s = 0; s < nseg; ++s) {
+    if (seg_n[s] <= 0 || seg_tk[s] <= 0 || seg_tk[s] > Tc) return hipErrorInvalidValue;
+    pairs += seg_n[s];
+    t.p_end[s] = (int)pairs;
+    t.tk[s] = seg_tk[s];
+    t.ld[s] = (Tq + seg_tk[s] + 63) / 64 * 64;
+    t.off[s] = off;
+    off += (long long)seg_n[s] * (Tq + seg_tk[s]) * t.ld[s];
+  }
+  if (pairs > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(fusion_adj_segs_kernel, dim3((unsigned)pairs), dim3(256), 2 * Tq * sizeof(float), st, scores, S, Tq, Tc, mult,
+                     adj, row0, t);
   return hipGetLastError();
 }
 

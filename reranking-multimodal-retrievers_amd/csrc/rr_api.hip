@@ -942,9 +942,10 @@ int run_layer(rr_model* m, hipStream_t st, const LayerW& L, int batch, int Tseq,
   // fp8_layer: -1 = every layer that holds e4m3 weights runs the fp8 configuration (cfg.fp8), 0 / 1 = the caller's per-layer
   // choice ("fp8_first_layer"); next_fp8: the NEXT layer of the stack runs the fp8 configuration, whose residual epilogues read
   // fp32 rows — a folded layer in front of it leaves its output rows as fp32 (w.pre2) instead of the (hi, lo) pair.
+  // segs + dense_bias (packed attention fusion, rr_forward_*_packed): the bias holds the segments one after the other, segment
+  // i as [n_i][len_i][round_up(len_i, 64)] (dense_ld is not read)
   int rows = batch * Tseq;
   if (segs) {
-    if (dense_bias) return fail(m, RR_ERR_UNSUPPORTED, "internal: dense attention bias with packed segments");
     size_t r = 0;
     for (const SegView& g : *segs) r += (size_t)g.n * g.len;
     rows = (int)r;
@@ -967,7 +968,19 @@ int run_layer(rr_model* m, hipStream_t st, const LayerW& L, int batch, int Tseq,
   } else {
     RR_GEMM(m, st, w.h16, Hd, L.wqkv, L.bqkv, nullptr, 0, w.qkv, 3 * Hd, rows, 3 * Hd, Hd, EPI_BIAS_BF16, 2.0);
   }
-  if (segs) {
+  if (segs && dense_bias) {
+    // the padded call with a dense bias runs the online form whatever its grid (the fixed-reference schedule excludes it):
+    // one online launch per segment on offset pointers is that call's arithmetic for every pair
+    const float* db = dense_bias;
+    for (const SegView& g : *segs) {
+      const int ld = (g.len + 63) / 64 * 64;
+      const size_t o = g.row0;
+      RR_RUN(m, st, RR_K_ATTENTION, 4.0 * g.n * (double)g.len * g.len * Hd, 2.0 * 4.0 * g.n * g.len * Hd + 4.0 * g.n * g.len * ld,
+             rr_launch_attention(w.qkv + o * 3 * Hd, 3 * Hd, 1, 0, w.qkv + o * 3 * Hd + Hd, w.qkv + o * 3 * Hd + 2 * Hd, 3 * Hd,
+                                 key_bias + o, g.n, heads, g.len, g.len, w.ctx + o * Hd, Hd, m->dt, st, db, ld, 0, attn_mode));
+      db += (size_t)g.n * g.len * ld;
+    }
+  } else if (segs) {
     // the schedule (online / fixed reference) of the PADDED call over the same pairs: batch pairs of Tseq rows; all segments
     // in ONE launch (rr_launch_attention_segs) where that schedule is the fixed-reference one
     const long sched = (((long)batch * heads + 7) / 8) * 8 * ((Tseq + 127) / 128);
@@ -1142,8 +1155,10 @@ int run_heads(rr_model* m, hipStream_t st, Work& w, const std::vector<Seg>& segs
 // embeddings(inputs_embeds) -> Lc layers.  Input: w.li16 [n*T, D], w.ce_bias [n, T]; output: w.h32 [n*T, Hc].
 // `segs`: one entry for the plain forward.  vis_pos0 >= 0: the vision tokens of every pair take the positions from vis_pos0 on
 // (length-bucketed / packed calls: behind the PADDED text), -1: plain positions 0 .. T-1.
+// pad_T > 0: the padded call's rows per pair (packed joint / interaction calls, whose cross-encoder positions do not move;
+// the full-context packed call derives it from vis_pos0).  Packed with `adj`: the bias is laid out per segment (run_layer).
 int run_cross_encoder(rr_model* m, hipStream_t st, Work& w, const std::vector<Seg>& segs, const float* adj = nullptr,
-                      int adj_ld = 0, int vis_pos0 = -1) {
+                      int adj_ld = 0, int vis_pos0 = -1, int pad_T = 0) {
   const rr_config& c = m->cfg;
   const int D = c.li_dim, Hc = c.ce_hidden, Ic = c.ce_intermediate;
   const Seg& last = segs.back();
@@ -1160,7 +1175,7 @@ int run_cross_encoder(rr_model* m, hipStream_t st, Work& w, const std::vector<Se
                                  vis_pos0 >= 0 ? vis_pos0 : 0, cls_only ? 1 : 0));
     view.push_back(SegView{g.n, g.T, g.rt0});
   }
-  const bool packed = segs.size() > 1;
+  const bool packed = segs.size() > 1 || pad_T > 0;
   m->cls_rows = nullptr;
   if (cls_only) {
     // Only the CLS row of every pair leaves the cross-encoder (the classifiers read hidden state [:, 0], utils.py:105-108):
@@ -1212,7 +1227,7 @@ int run_cross_encoder(rr_model* m, hipStream_t st, Work& w, const std::vector<Se
     ResidSrc rs{w.h32, nullptr, nullptr, nullptr};
     int folded = OP_NORMALISED;
     for (int l = 0; l < c.ce_layers; ++l)
-      RR_TRY(run_layer(m, st, m->ce_layers[l], n, packed ? vis_pos0 + (last.T - last.S) : last.T,   // (packed: the padded call's rows per pair, for the attention schedule)
+      RR_TRY(run_layer(m, st, m->ce_layers[l], n, packed ? (pad_T > 0 ? pad_T : vis_pos0 + (last.T - last.S)) : last.T,   // (packed: the padded call's rows per pair, for the attention schedule)
                        Hc, c.ce_heads, Ic, c.ln_eps, w.ce_bias, w, rs, folded,
                        l == c.ce_layers - 1, true,          // the CLS heads read the fp32 rows of the last layer
                        adj, adj_ld,                         // attention fusion: the same bias in every layer
@@ -1603,6 +1618,27 @@ static int range_guard_exit(rr_model* m, hipStream_t st) {
   return RR_OK;
 }
 
+// Attention-fusion bias of a packed call into m->adj, one launch: scores [n][Tc][Tq] (the context rows, packed pair order, padded
+// context axis), segment g's pairs end after g.S - s_off context tokens (joint: g.S - q_len; interaction: g.S), so its rows
+// are g.T = Tq + that; layout per segment as run_layer reads it: [g.n][g.T][round_up(g.T, 64)]
+static int fusion_bias_packed(rr_model* m, hipStream_t st, const std::vector<Seg>& segs, const float* scores, int Tc, int Tq, int s_off,
+                              float mult) {
+  size_t need = 0;
+  double rd = 0.0;
+  std::vector<int> sn, tk;
+  for (const Seg& g : segs) {
+    if (g.T != Tq + g.S - s_off) return fail(m, RR_ERR_BAD_ARG, "internal: fusion bias rows %d != %d + %d", g.T, Tq, g.S - s_off);
+    need += (size_t)g.n * g.T * ((g.T + 63) / 64 * 64) * sizeof(float);
+    rd += 4.0 * g.n * (double)Tc * Tq;
+    sn.push_back(g.n);
+    tk.push_back(g.S - s_off);
+  }
+  RR_TRY(ensure_adj(m, need, st));
+  RR_RUN(m, st, RR_K_TAIL, 0.0, rd + (double)need,
+         rr_launch_fusion_adj_segs(scores, Tc, Tq, Tc, mult, (int)segs.size(), sn.data(), tk.data(), m->adj, st, 0));
+  return RR_OK;
+}
+
 static int forward_full(rr_handle h, const int64_t* input_ids, const int64_t* attention_mask,
                         const int64_t* token_type_ids, const float* image_cls, const float* image_patches, int Bq, int K,
                         int S, const float* labels, int pair_begin, int pair_end, float* logits_out,
@@ -1644,8 +1680,8 @@ static int forward_full(rr_handle h, const int64_t* input_ids, const int64_t* at
     vis_pos0 = m->padded_S;
   }
   if (packed) {
-    if (joint || K != 1) return fail(m, RR_ERR_BAD_ARG, "internal: packed forward is per pair and not joint");
-    vis_pos0 = S;
+    if (K != 1) return fail(m, RR_ERR_BAD_ARG, "internal: packed forward is per pair");
+    if (!joint) vis_pos0 = S;     // (joint: [query | image | context] is padded at its end, no position moves)
   }
   const bool full = pair_begin == 0 && pair_end == N;
   if (c.loss_kind == RR_LOSS_NEGATIVE_SAMPLING && labels)
@@ -1700,8 +1736,10 @@ static int forward_full(rr_handle h, const int64_t* input_ids, const int64_t* at
   const int txt_split = joint ? q_len : (1 << 30), txt_shift = joint ? P : 0;   // [query | image | context] reorder
   const int vis_off = joint ? q_len : S;                                           // where the image tokens go
   if (joint) {
-    RR_RUN(m, st, RR_K_EMBED, 0.0, 24.0 * R + 4.0 * RT,
-           rr_launch_joint_masks(ids, am, n, S, P, q_len, instruction_token, w.text_bias, w.li_mask, w.ce_bias, st));
+    for (const Seg& g : segs)
+      RR_RUN(m, st, RR_K_EMBED, 0.0, 24.0 * g.n * g.S + 4.0 * g.n * g.T,
+             rr_launch_joint_masks(ids + g.r0, am + g.r0, g.n, g.S, P, q_len, instruction_token, w.text_bias + g.r0,
+                                   w.li_mask + g.r0, w.ce_bias + g.rt0, st));
   } else {
     for (const Seg& g : segs)
       RR_RUN(m, st, RR_K_EMBED, 0.0, 16.0 * g.n * g.S + 8.0 * g.n * g.T,
@@ -1735,7 +1773,7 @@ static int forward_full(rr_handle h, const int64_t* input_ids, const int64_t* at
   for (const Seg& g : segs)
     RR_RUN(m, st, RR_K_TAIL, 0.0, 6.0 * g.n * g.S * D + 8.0 * g.n * g.S,
            rr_launch_li_normalize(w.li32 + g.r0 * D, ids + g.r0, g.S, g.n, g.S, D, g.T, 0, 0, 1, 0, w.li16 + g.rt0 * D, m->dt, 1,
-                                  joint ? w.li_mask : nullptr, txt_split, txt_shift, st));
+                                  joint ? w.li_mask + g.r0 : nullptr, txt_split, txt_shift, st));
 
   if (vision) {
     const int np = c.n_patches, PL = c.prefix_len, Vh = c.vision_hidden, mid = D * PL / 2, outd = D * PL;
@@ -1747,7 +1785,7 @@ static int forward_full(rr_handle h, const int64_t* input_ids, const int64_t* at
     RR_GEMM(m, st, w.vp_mid16, mid, m->w_vp2, m->b_vp2, nullptr, 0, w.vp_out32, outd, nq, outd, mid, EPI_BIAS_F32, 4.0);
     for (const Seg& g : segs)           // (packed: per pair, K = 1 -> pair p0 + i reads prefix p0 + i)
       RR_RUN(m, st, RR_K_TAIL, 0.0, 6.0 * g.n * PL * D,
-             rr_launch_li_normalize(w.vp_out32, nullptr, 0, g.n, PL, D, g.T, packed ? g.S : vis_off, pair_begin + (int)g.p0, K,
+             rr_launch_li_normalize(w.vp_out32, nullptr, 0, g.n, PL, D, g.T, (packed && !joint) ? g.S : vis_off, pair_begin + (int)g.p0, K,
                                     q_lo, w.li16 + g.rt0 * D, m->dt, 1, nullptr, 1 << 30, 0, st));
     // mapping network: input linear + self-attention block depend on the image only => per query
     RR_RUN(m, st, RR_K_TAIL, 0.0, 6.0 * nq * np * Vh, rr_launch_f32_to_bf16(pat, w.pat16, (size_t)nq * np * Vh, m->dt, st));
@@ -1804,7 +1842,7 @@ static int forward_full(rr_handle h, const int64_t* input_ids, const int64_t* at
     RR_GEMM(m, st, w.m16, Hd, m->w_mout, m->b_mout, nullptr, 0, w.mo32, D, n * np, D, Hd, EPI_BIAS_F32, 4.0);
     for (const Seg& g : segs)
       RR_RUN(m, st, RR_K_TAIL, 0.0, 6.0 * g.n * np * D,
-             rr_launch_li_normalize(w.mo32 + g.p0 * np * D, nullptr, 0, g.n, np, D, g.T, (packed ? g.S : vis_off) + PL, 0, 1, 0,
+             rr_launch_li_normalize(w.mo32 + g.p0 * np * D, nullptr, 0, g.n, np, D, g.T, ((packed && !joint) ? g.S : vis_off) + PL, 0, 1, 0,
                                     w.li16 + g.rt0 * D, m->dt, 1, nullptr, 1 << 30, 0, st));
   }
   m->tap_li = w.li16;
@@ -1814,14 +1852,18 @@ static int forward_full(rr_handle h, const int64_t* input_ids, const int64_t* at
   int adj_ld = 0;
   if (preflmr_scores) {   // rerank_model.py:276-319: scores [N, S, q_len + P] -> additive bias [n, T, ld]
     if (!joint) return fail(m, RR_ERR_BAD_ARG, "attention fusion belongs to the joint (RerankModel) forward");
-    adj_ld = (T + 63) / 64 * 64;
-    const size_t need_adj = (size_t)n * T * adj_ld * sizeof(float);
-    RR_TRY(ensure_adj(m, need_adj, st));
-    RR_RUN(m, st, RR_K_TAIL, 0.0, 4.0 * n * (double)S * (q_len + P) + (double)need_adj,
-           rr_launch_fusion_adj(preflmr_scores, S, q_len + P, S - q_len, fusion_multiplier, pair_begin, n, m->adj, adj_ld, st));
+    if (packed) {         // scores [n, S - q_len, q_len + P] (the context rows only); the bias segment after segment
+      RR_TRY(fusion_bias_packed(m, st, segs, preflmr_scores, S - q_len, q_len + P, q_len, fusion_multiplier));
+    } else {
+      adj_ld = (T + 63) / 64 * 64;
+      const size_t need_adj = (size_t)n * T * adj_ld * sizeof(float);
+      RR_TRY(ensure_adj(m, need_adj, st));
+      RR_RUN(m, st, RR_K_TAIL, 0.0, 4.0 * n * (double)S * (q_len + P) + (double)need_adj,
+             rr_launch_fusion_adj(preflmr_scores, S, q_len + P, S - q_len, fusion_multiplier, pair_begin, n, m->adj, adj_ld, st));
+    }
     adj = m->adj;
   }
-  RR_TRY(run_cross_encoder(m, st, w, segs, adj, adj_ld, vis_pos0));
+  RR_TRY(run_cross_encoder(m, st, w, segs, adj, adj_ld, vis_pos0, (packed && joint) ? T : 0));
   RR_TRY(run_heads(m, st, w, segs, Bq, K, pair_begin, full, joint ? logits_out : labels, logits_out, logits2_out,
                    loss_out, scores_out, order_out, joint != 0));
   return range_guard_exit(m, st);
@@ -1889,7 +1931,10 @@ static int forward_interaction(rr_handle h, const float* query_li, const float* 
                                const float* context_mask, int Bq, int K, int Lq, int Lc, const float* labels,
                                int pair_begin, int pair_end, float* logits_out, float* logits2_out, float* loss_out,
                                float* scores_out, int32_t* order_out, void* hip_stream, const float* preflmr_scores,
-                               float fusion_multiplier) {
+                               float fusion_multiplier, const std::vector<std::pair<int, int>>* packed = nullptr) {
+  // `packed` (rr_forward_interaction_packed): segments (pairs, context tokens per pair); context_li / context_mask then hold the
+  // segments' pairs back to back at THEIR context length, query_li / query_mask one entry per pair, Bq = pairs, K = 1, Lc = the
+  // padded context length
   if (!h) return RR_ERR_BAD_ARG;
   rr_model* m = h;
   const rr_config& c = m->cfg;
@@ -1924,21 +1969,46 @@ static int forward_interaction(rr_handle h, const float* query_li, const float* 
   const int D = c.li_dim, Hc = c.ce_hidden, Ic = c.ce_intermediate;
   const float* cli = context_li + (size_t)pair_begin * Lc * D;
   const float* cm = context_mask + (size_t)pair_begin * Lc;
+  // segments: one (n pairs of Lc context tokens) for the plain forward.  Seg.S = context tokens per pair, Seg.r0 = first
+  // context row, Seg.rt0 = first row of the concatenated [query | context] sequence.
+  std::vector<Seg> segs;
+  if (packed) {
+    size_t p0 = 0, c0 = 0, rt0 = 0;
+    for (const auto& g : *packed) {
+      segs.push_back(Seg{g.first, g.second, Lq + g.second, p0, c0, rt0});
+      p0 += (size_t)g.first;
+      c0 += (size_t)g.first * g.second;
+      rt0 += (size_t)g.first * (Lq + g.second);
+    }
+  } else {
+    segs.push_back(Seg{n, Lc, T, 0, 0, 0});
+  }
+  const Seg& last = segs.back();
+  const int C = (int)(last.r0 + (size_t)last.n * last.S), RT = (int)(last.rt0 + (size_t)last.n * last.T);
 
-  RR_RUN(m, st, RR_K_EMBED, 0.0, 8.0 * n * T,
-         rr_launch_interaction_bias(query_mask, cm, n, Lq, Lc, pair_begin, K, w.ce_bias, w.text_bias, w.li32, st));
+  for (const Seg& g : segs)
+    RR_RUN(m, st, RR_K_EMBED, 0.0, 8.0 * g.n * g.T,
+           rr_launch_interaction_bias(query_mask, cm + g.r0, g.n, Lq, g.S, pair_begin + (int)g.p0, K, w.ce_bias + g.rt0,
+                                      w.text_bias + g.p0 * Lq, w.li32 + g.r0, st));
   // operands in 16 bits, query rows broadcast to the K pairs of the query (repeat_interleave, :128-129)
-  RR_RUN(m, st, RR_K_TAIL, 0.0, 6.0 * n * Lq * D,
-         rr_launch_li_normalize(query_li, nullptr, 0, n, Lq, D, T, 0, pair_begin, K, 0, w.li16, m->dt, 0, nullptr, 1 << 30, 0, st));
-  RR_RUN(m, st, RR_K_TAIL, 0.0, 6.0 * n * Lc * D,
-         rr_launch_li_normalize(cli, nullptr, 0, n, Lc, D, T, Lq, 0, 1, 0, w.li16, m->dt, 0, nullptr, 1 << 30, 0, st));
+  for (const Seg& g : segs) {
+    RR_RUN(m, st, RR_K_TAIL, 0.0, 6.0 * g.n * Lq * D,
+           rr_launch_li_normalize(query_li, nullptr, 0, g.n, Lq, D, g.T, 0, pair_begin + (int)g.p0, K, 0, w.li16 + g.rt0 * D, m->dt, 0,
+                                  nullptr, 1 << 30, 0, st));
+    RR_RUN(m, st, RR_K_TAIL, 0.0, 6.0 * g.n * g.S * D,
+           rr_launch_li_normalize(cli + g.r0 * D, nullptr, 0, g.n, g.S, D, g.T, Lq, 0, 1, 0, w.li16 + g.rt0 * D, m->dt, 0, nullptr,
+                                  1 << 30, 0, st));
+  }
   m->tap_li = w.li16;
-  m->tap_li_elems = (size_t)n * T * D;
+  m->tap_li_elems = (size_t)RT * D;
 
   if (c.model_kind == RR_MODEL_INTERACTION) {
     const float* adj = nullptr;
     int adj_ld = 0;
-    if (preflmr_scores) {   // interaction_rerank_model.py:131-142: scores [N, Lc, Lq] over the tokens [query | context]
+    if (preflmr_scores && packed) {   // scores stay [n, Lc, Lq] (padded context axis: the normalisers); bias per segment
+      RR_TRY(fusion_bias_packed(m, st, segs, preflmr_scores, Lc, Lq, 0, fusion_multiplier));
+      adj = m->adj;
+    } else if (preflmr_scores) {   // interaction_rerank_model.py:131-142: scores [N, Lc, Lq] over the tokens [query | context]
       adj_ld = (T + 63) / 64 * 64;
       const size_t need_adj = (size_t)n * T * adj_ld * sizeof(float);
       RR_TRY(ensure_adj(m, need_adj, st));
@@ -1946,9 +2016,8 @@ static int forward_interaction(rr_handle h, const float* query_li, const float* 
              rr_launch_fusion_adj(preflmr_scores, Lc, Lq, Lc, fusion_multiplier, pair_begin, n, m->adj, adj_ld, st, 0));
       adj = m->adj;
     }
-    const std::vector<Seg> one{Seg{n, T, T, 0, 0, 0}};
-    RR_TRY(run_cross_encoder(m, st, w, one, adj, adj_ld));
-    RR_TRY(run_heads(m, st, w, one, Bq, K, pair_begin, full, labels, logits_out, logits2_out, loss_out, scores_out,
+    RR_TRY(run_cross_encoder(m, st, w, segs, adj, adj_ld, -1, packed ? T : 0));
+    RR_TRY(run_heads(m, st, w, segs, Bq, K, pair_begin, full, labels, logits_out, logits2_out, loss_out, scores_out,
                      order_out));
     return range_guard_exit(m, st);
   }
@@ -1956,22 +2025,31 @@ static int forward_interaction(rr_handle h, const float* query_li, const float* 
 
   // ---- MORES: hidden = Linear(query) [n*Lq, Hc] (no embeddings, no LayerNorm), doc = Linear(context) [n*Lc, Hc]
   // gather the two token groups out of the concatenated 16-bit buffer into contiguous GEMM operands
-  RR_RUN(m, st, RR_K_TAIL, 0.0, 4.0 * n * Lq * D, rr_launch_gather_rows(w.li16, w.a16, n, Lq, T, D * 2, 0, 1, 0, st));
+  // (packed: the query side keeps its n * Lq rows, the doc side holds the C rows that exist)
+  for (const Seg& g : segs)
+    RR_RUN(m, st, RR_K_TAIL, 0.0, 4.0 * g.n * Lq * D,
+           rr_launch_gather_rows(w.li16 + g.rt0 * D, w.a16 + g.p0 * Lq * D, g.n, Lq, g.T, D * 2, 0, 1, 0, st));
   RR_GEMM(m, st, w.a16, D, m->w_cemap, m->b_cemap, nullptr, 0, w.h32, Hc, n * Lq, Hc, D, EPI_BIAS_F32, 4.0);
   RR_RUN(m, st, RR_K_TAIL, 0.0, 6.0 * n * Lq * Hc, rr_launch_f32_to_bf16(w.h32, w.h16, (size_t)n * Lq * Hc, m->dt, st));
-  RR_RUN(m, st, RR_K_TAIL, 0.0, 4.0 * n * Lc * D,
-         rr_launch_gather_rows((const char*)w.li16 + (size_t)Lq * D * 2, w.ctx, n, Lc, T, D * 2, 0, 1, 0, st));
-  RR_GEMM(m, st, w.ctx, D, m->w_cemap, m->b_cemap, nullptr, 0, w.enc16, Hc, n * Lc, Hc, D, EPI_BIAS_BF16, 2.0);
+  for (const Seg& g : segs)
+    RR_RUN(m, st, RR_K_TAIL, 0.0, 4.0 * g.n * g.S * D,
+           rr_launch_gather_rows((const char*)w.li16 + ((size_t)g.rt0 + Lq) * D * 2, w.ctx + g.r0 * D, g.n, g.S, g.T, D * 2, 0, 1, 0,
+                                 st));
+  RR_GEMM(m, st, w.ctx, D, m->w_cemap, m->b_cemap, nullptr, 0, w.enc16, Hc, C, Hc, D, EPI_BIAS_BF16, 2.0);
+  // cross-attention per segment (Tk = its context length) under the padded call's schedule (its grid: n pairs x Lq rows)
+  const long x_sched = packed ? (((long)n * c.ce_heads + 7) / 8) * 8 * ((Lq + 127) / 128) : 0;
   (void)nq;
   for (int l = 0; l < c.ce_layers; ++l) {
     const LayerW& L = m->ce_layers[l];
     const int rq = n * Lq;
     // cross-attention first (MORES_BertLayer.forward, mores_model.py:31-41): queries from the query tokens, keys/values from doc
     RR_GEMM(m, st, w.h16, Hc, L.wq_c, L.bq_c, nullptr, 0, w.q_c, Hc, rq, Hc, Hc, EPI_BIAS_BF16, 2.0);
-    RR_GEMM(m, st, w.enc16, Hc, L.wkv_c, L.bkv_c, nullptr, 0, w.kv_c, 2 * Hc, n * Lc, 2 * Hc, Hc, EPI_BIAS_BF16, 2.0);
-    RR_RUN(m, st, RR_K_ATTENTION, 4.0 * n * (double)Lq * Lc * Hc, 2.0 * n * (2.0 * Lq + 2.0 * Lc) * Hc,
-           rr_launch_attention(w.q_c, Hc, 1, 0, w.kv_c, w.kv_c + Hc, 2 * Hc, w.li32, n, c.ce_heads, Lq, Lc, w.ctx, Hc,
-                               m->dt, st, nullptr, 0, 0, opt_of(m, RR_OPT_ATTN_FIXED_REF)));
+    RR_GEMM(m, st, w.enc16, Hc, L.wkv_c, L.bkv_c, nullptr, 0, w.kv_c, 2 * Hc, C, 2 * Hc, Hc, EPI_BIAS_BF16, 2.0);
+    for (const Seg& g : segs)
+      RR_RUN(m, st, RR_K_ATTENTION, 4.0 * g.n * (double)Lq * g.S * Hc, 2.0 * g.n * (2.0 * Lq + 2.0 * g.S) * Hc,
+             rr_launch_attention(w.q_c + g.p0 * Lq * Hc, Hc, 1, 0, w.kv_c + g.r0 * 2 * Hc, w.kv_c + g.r0 * 2 * Hc + Hc, 2 * Hc,
+                                 w.li32 + g.r0, g.n, c.ce_heads, Lq, g.S, w.ctx + g.p0 * Lq * Hc, Hc, m->dt, st, nullptr, 0, x_sched,
+                                 opt_of(m, RR_OPT_ATTN_FIXED_REF)));
     RR_GEMM(m, st, w.ctx, Hc, L.wo_c, L.bo_c, w.h32, Hc, w.pre, Hc, rq, Hc, Hc, EPI_BIAS_RESID_F32, 4.0);
     RR_RUN(m, st, RR_K_LAYERNORM, 0.0, 10.0 * rq * Hc,
            rr_launch_layernorm(w.pre, L.lncg, L.lncb, c.ln_eps, rq, Hc, w.a32, w.a16, m->dt, st));
@@ -1995,6 +2073,87 @@ static int forward_interaction(rr_handle h, const float* query_li, const float* 
   RR_TRY(run_heads(m, st, w, one, Bq, K, pair_begin, full, labels, logits_out, logits2_out, loss_out, scores_out,
                    order_out));
   return range_guard_exit(m, st);
+}
+
+// Packed segment tables of rr_forward_joint_packed / rr_forward_interaction_packed (include/rerank_mi355.h): 1..64 non-empty
+// segments of lengths in (min_len, padded_len]
+static int packed_segments(rr_model* m, const char* what, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len,
+                           int padded_len, int min_len, int extra_rows, std::vector<std::pair<int, int>>* out) {
+  if (!seg_pairs || !seg_len) return fail(m, RR_ERR_BAD_ARG, "%s: null segment tables", what);
+  if (n_segments <= 0 || n_segments > 64) return fail(m, RR_ERR_BAD_SHAPE, "%s: %d segments (1..64)", what, n_segments);
+  long long pairs = 0, rows = 0;
+  for (int i = 0; i < n_segments; ++i) {
+    if (seg_pairs[i] <= 0 || seg_len[i] <= min_len || seg_len[i] > padded_len)
+      return fail(m, RR_ERR_BAD_SHAPE, "%s: segment %d holds %d pairs of length %d (lengths in (%d, %d])", what, i, seg_pairs[i],
+                  seg_len[i], min_len, padded_len);
+    out->emplace_back(seg_pairs[i], seg_len[i]);
+    pairs += seg_pairs[i];
+    rows += (long long)seg_pairs[i] * (seg_len[i] + extra_rows);
+  }
+  if (pairs > (1 << 24) || rows > (1LL << 30)) return fail(m, RR_ERR_BAD_SHAPE, "%s: %lld pairs / %lld rows", what, pairs, rows);
+  return RR_OK;
+}
+
+// Packed RerankModel forward: see include/rerank_mi355.h.
+static int rr_forward_joint_packed_impl(rr_handle h, const int64_t* joint_input_ids, const int64_t* joint_attention_mask,
+                                        const float* image_cls, const float* image_patches, const float* preflmr_scores,
+                                        float fusion_multiplier, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len,
+                                        int padded_seq_len, int query_len, int64_t instruction_token_id, float* logits_out,
+                                        float* logits2_out, void* hip_stream) {
+  if (!h) return RR_ERR_BAD_ARG;
+  rr_model* m = h;
+  std::vector<std::pair<int, int>> segs;
+  const int P = m->cfg.prefix_len + m->cfg.n_patches;
+  RR_TRY(packed_segments(m, "rr_forward_joint_packed", n_segments, seg_pairs, seg_len, padded_seq_len, query_len < 0 ? 0 : query_len,
+                         P, &segs));
+  int n = 0;
+  for (const auto& g : segs) n += g.first;
+  return forward_full(h, joint_input_ids, joint_attention_mask, nullptr, image_cls, image_patches, n, 1, padded_seq_len, nullptr, 0,
+                      n, logits_out, logits2_out, nullptr, nullptr, nullptr, hip_stream, 1, query_len, (long long)instruction_token_id,
+                      preflmr_scores, fusion_multiplier, &segs);
+}
+
+// Packed InteractionRerankModel forward (NORMAL and MORES): see include/rerank_mi355.h.
+static int rr_forward_interaction_packed_impl(rr_handle h, const float* query_li, const float* context_li, const float* query_mask,
+                                              const float* context_mask, const float* preflmr_scores, float fusion_multiplier,
+                                              int n_segments, const int32_t* seg_pairs, const int32_t* seg_len,
+                                              int padded_context_len, int Lq, float* logits_out, float* logits2_out,
+                                              void* hip_stream) {
+  if (!h) return RR_ERR_BAD_ARG;
+  rr_model* m = h;
+  std::vector<std::pair<int, int>> segs;
+  RR_TRY(packed_segments(m, "rr_forward_interaction_packed", n_segments, seg_pairs, seg_len, padded_context_len, 0, Lq < 0 ? 0 : Lq,
+                         &segs));
+  int n = 0;
+  for (const auto& g : segs) n += g.first;
+  return forward_interaction(h, query_li, context_li, query_mask, context_mask, n, 1, Lq, padded_context_len, nullptr, 0, n,
+                             logits_out, logits2_out, nullptr, nullptr, nullptr, hip_stream, preflmr_scores, fusion_multiplier,
+                             &segs);
+}
+
+// rr_head with RerankModel.forward's loss: loss_fn(logits, logits) (rerank_model.py:328), as rr_forward_joint runs it
+static int rr_head_joint_impl(rr_handle h, const float* logits, const float* logits2, int Bq, int K, float* loss_out,
+                              float* scores_out, int32_t* order_out, void* hip_stream) {
+  if (!h || !logits) return fail(h, RR_ERR_BAD_ARG, "rr_head_joint: null argument");
+  if (Bq <= 0 || K <= 0) return fail(h, RR_ERR_BAD_SHAPE, "rr_head_joint: Bq=%d K=%d", Bq, K);
+  if (K > 4096) return fail(h, RR_ERR_UNSUPPORTED, "rr_head_joint: K=%d > 4096", K);
+  const rr_config& c = h->cfg;
+  if (c.model_kind != RR_MODEL_FULL_CONTEXT) return fail(h, RR_ERR_BAD_ARG, "rr_head_joint on an interaction model");
+  if (c.loss_kind == RR_LOSS_2H_BCE && !logits2) return fail(h, RR_ERR_BAD_ARG, "rr_head_joint: 2H_BCE needs logits2 (first head)");
+  if (c.loss_kind == RR_LOSS_NEGATIVE_SAMPLING && loss_out)
+    return fail(h, RR_ERR_UNSUPPORTED, "RerankModel with negative_sampling loss is not covered (no reference config)");
+  hipStream_t st = (hipStream_t)hip_stream;
+  RR_HIP(h, hipSetDevice(c.device));
+  Work w;
+  const size_t need = layout(c, 1, Bq, 8, false, nullptr, &w);
+  RR_TRY(ensure_ws(h, need, st));
+  layout(c, 1, Bq, 8, false, h->ws, &w);
+  const int has_pw = !std::isnan(c.pos_weight);
+  const bool two = c.loss_kind == RR_LOSS_2H_BCE;
+  RR_RUN(h, st, RR_K_HEAD, 0.0, 12.0 * Bq * K,
+         rr_launch_head(logits, two ? logits2 : nullptr, logits, Bq, K, two ? 3 : c.loss_kind, has_pw ? c.pos_weight : 1.0f, has_pw,
+                        scores_out, order_out, loss_out, w.part_l, w.part_w, st));
+  return RR_OK;
 }
 
 static int rr_forward_interaction_impl(rr_handle h, const float* query_li, const float* context_li, const float* query_mask,
@@ -2332,6 +2491,15 @@ int rr_forward(rr_handle h, const int64_t* input_ids, const int64_t* attention_m
 }
 int rr_forward_packed(rr_handle h, const int64_t* input_ids, const int64_t* attention_mask, const int64_t* token_type_ids, const float* image_cls, const float* image_patches, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int padded_seq_len, float* logits_out, float* logits2_out, void* hip_stream) {
   return guarded(h, [&]() -> int { return rr_forward_packed_impl(h, input_ids, attention_mask, token_type_ids, image_cls, image_patches, n_segments, seg_pairs, seg_len, padded_seq_len, logits_out, logits2_out, hip_stream); });
+}
+int rr_forward_joint_packed(rr_handle h, const int64_t* joint_input_ids, const int64_t* joint_attention_mask, const float* image_cls, const float* image_patches, const float* preflmr_scores, float fusion_multiplier, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int padded_seq_len, int query_len, int64_t instruction_token_id, float* logits_out, float* logits2_out, void* hip_stream) {
+  return guarded(h, [&]() -> int { return rr_forward_joint_packed_impl(h, joint_input_ids, joint_attention_mask, image_cls, image_patches, preflmr_scores, fusion_multiplier, n_segments, seg_pairs, seg_len, padded_seq_len, query_len, instruction_token_id, logits_out, logits2_out, hip_stream); });
+}
+int rr_forward_interaction_packed(rr_handle h, const float* query_li, const float* context_li, const float* query_mask, const float* context_mask, const float* preflmr_scores, float fusion_multiplier, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int padded_context_len, int Lq, float* logits_out, float* logits2_out, void* hip_stream) {
+  return guarded(h, [&]() -> int { return rr_forward_interaction_packed_impl(h, query_li, context_li, query_mask, context_mask, preflmr_scores, fusion_multiplier, n_segments, seg_pairs, seg_len, padded_context_len, Lq, logits_out, logits2_out, hip_stream); });
+}
+int rr_head_joint(rr_handle h, const float* logits, const float* logits2, int Bq, int K, float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream) {
+  return guarded(h, [&]() -> int { return rr_head_joint_impl(h, logits, logits2, Bq, K, loss_out, scores_out, order_out, hip_stream); });
 }
 int rr_forward_joint(rr_handle h, const int64_t* joint_input_ids, const int64_t* joint_attention_mask, const float* image_cls, const float* image_patches, int Bq, int K, int S, int query_len, int64_t instruction_token_id, int pair_begin, int pair_end, float* logits_out, float* logits2_out, float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream) {
   return guarded(h, [&]() -> int { return rr_forward_joint_impl(h, joint_input_ids, joint_attention_mask, image_cls, image_patches, Bq, K, S, query_len, instruction_token_id, pair_begin, pair_end, logits_out, logits2_out, loss_out, scores_out, order_out, hip_stream); });

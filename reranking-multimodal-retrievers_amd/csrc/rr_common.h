@@ -406,6 +406,12 @@ hipError_t rr_launch_attention_segs(const bf16_t* q, int q_stride, const bf16_t*
 // dense_bias: optional additive bias [B][Tq][dense_ld] (dense_ld a multiple of 64 >= Tk, zero padded), PreFLMR fusion
 hipError_t rr_launch_fusion_adj(const float* scores, int S, int Tq, int Tc, float mult, int pair0, int n, float* adj, int ld,
                                 hipStream_t st, int row0 = 2);
+// the same for a packed call, ONE launch: nseg (<= 64) segments of seg_n[s] pairs (HOST arrays) in the packed order, whose
+// sequences end after seg_tk[s] of the Tc context tokens; the softmax normalisers still run over all Tc.  adj holds the
+// segments one after the other, segment s as [seg_n[s]][Tq + seg_tk[s]][round_up(Tq + seg_tk[s], 64)]
+#define RR_FUSION_MAX_SEGS 64
+hipError_t rr_launch_fusion_adj_segs(const float* scores, int S, int Tq, int Tc, float mult, int nseg, const int* seg_n,
+                                     const int* seg_tk, float* adj, hipStream_t st, int row0);
 
 // CLIP ViT front end: im2col of the stride = kernel patch convolution, and [class | patches] + position -> pre_layrnorm
 hipError_t rr_launch_vit_im2col(const float* px, bf16_t* out, int B, int IS, int ps, int Kp, int dt, hipStream_t st);

@@ -20,7 +20,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import _lib as L
-from .pair_inputs import group_pairs_by_length
+from .pair_inputs import group_pairs_by_length, pack_fusion_scores, pack_rows, pair_lengths, scatter_packed
 
 
 class RerankOutput(dict):
@@ -531,6 +531,112 @@ class RerankEngine:
                                                     L.ptr(order), stream), self.h, "rr_forward_interaction")
         return dict(logits=logits, logits2=logits2, loss=loss, scores=scores, order=order)
 
+    def forward_joint_packed(self, joint_input_ids: torch.Tensor, joint_attention_mask: torch.Tensor, Bq: int, K: int,
+                             query_len: int, image_cls: torch.Tensor, image_patches: torch.Tensor,
+                             instruction_token_id: Optional[int] = None, want_scores: bool = False, want_order: bool = False,
+                             want_loss: bool = True, preflmr_scores: Optional[torch.Tensor] = None,
+                             fusion_multiplier: float = 1.0, granule: int = 16, lengths: Optional[Sequence[int]] = None,
+                             segment_cost_rows: int = 0):
+        """`forward_joint` over PACKED rows (rr_forward_joint_packed): the pairs are grouped by the length of their joint
+        sequence (1 + last non-pad position of the joint ids / mask) rounded up to `granule`, at least query_len + 1 and the
+        mapping network's cross-attention window, and laid out group after group, so that the text encoder and the cross
+        encoder compute only the rows that exist.  `preflmr_scores` [N, S, query_len + image tokens] as forward_joint takes
+        it; its context rows go over padded (the reference normalises over the padded context axis).  The head runs on the
+        scattered logits (rr_head_joint: the reference's loss_fn(logits, logits), rerank_model.py:328).  `lengths`: the pairs'
+        joint lengths as the host knows them (no device -> host copy).  The sharded path and pair_range slices are not
+        packed.  Returns the dict of forward_joint plus `packed_rows`, `packed_segments`."""
+        dev = self.device
+        N, S = joint_input_ids.shape
+        assert N == Bq * K and granule > 0
+        if image_cls is None or image_patches is None:
+            raise NotImplementedError("text_only is not implemented for this model")        # rerank_model.py:184-185
+        ql = int(query_len)
+        f32 = dict(device=dev, dtype=torch.float32)
+        ids, am = joint_input_ids.to(dev).contiguous(), joint_attention_mask.to(dev).contiguous()
+        floor = max(ql + 1, min(S, int(self.arch.get("cross_attn_len", 32))))
+        if lengths is None:                                            # derived on the device: one device -> host copy
+            lengths = pair_lengths(ids, am).cpu().numpy()
+        order_h, seg_n, seg_len = group_pairs_by_length(lengths, S, granule, floor, segment_cost_rows)
+        assert len(order_h) == N, "one length per pair"
+        order = torch.from_numpy(order_h).to(dev, non_blocking=True)
+        ids_p, am_p = pack_rows(ids, order, seg_n, seg_len), pack_rows(am, order, seg_n, seg_len)
+        q = torch.div(order, K, rounding_mode="floor")                 # image features per pair: a segment mixes queries
+        cls_p = image_cls.to(**f32).index_select(0, q).contiguous()
+        pat_p = image_patches.to(**f32).index_select(0, q).contiguous()
+        ps = None
+        if preflmr_scores is not None:
+            P = self.arch["prefix_len"] + self.arch["n_patches"]
+            if tuple(preflmr_scores.shape) != (N, S, ql + P):                                  # rerank_model.py:280-284
+                raise AssertionError(f"preflmr_scores must be [{N}, {S}, {ql + P}], got {tuple(preflmr_scores.shape)}")
+            ps = pack_fusion_scores(preflmr_scores.to(**f32), order, 2, S - ql)
+        lp, lp2 = torch.empty(N, **f32), torch.empty(N, **f32)
+        sn, sl = (C.c_int32 * len(seg_n))(*seg_n), (C.c_int32 * len(seg_n))(*seg_len)
+        instr = -1 if instruction_token_id is None else int(instruction_token_id)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        L.check(self.lib.rr_forward_joint_packed(self.h, L.ptr(ids_p), L.ptr(am_p), L.ptr(cls_p), L.ptr(pat_p), L.ptr(ps),
+                                                 float(fusion_multiplier), len(seg_n), sn, sl, S, ql, instr, L.ptr(lp),
+                                                 L.ptr(lp2), stream), self.h, "rr_forward_joint_packed")
+        logits, logits2 = scatter_packed(lp, order), scatter_packed(lp2, order)
+        two = self.arch["loss_fn"] == "2H_BCE"
+        loss = torch.empty((), **f32) if want_loss else None
+        scores = torch.empty(N, **f32) if want_scores else None
+        order_out = torch.empty((Bq, K), dtype=torch.int32, device=dev) if want_order else None
+        L.check(self.lib.rr_head_joint(self.h, L.ptr(logits), L.ptr(logits2 if two else None), Bq, K, L.ptr(loss), L.ptr(scores),
+                                       L.ptr(order_out), stream), self.h, "rr_head_joint")
+        return dict(logits=logits, logits2=logits2, loss=loss, scores=scores, order=order_out,
+                    packed_rows=sum(n * s for n, s in zip(seg_n, seg_len)), packed_segments=len(seg_n))
+
+    def forward_interaction_packed(self, query_li: torch.Tensor, context_li: torch.Tensor, query_mask: torch.Tensor,
+                                   context_mask: torch.Tensor, Bq: int, K: int, labels: Optional[torch.Tensor] = None,
+                                   want_scores: bool = False, want_order: bool = False, want_loss: bool = True,
+                                   preflmr_scores: Optional[torch.Tensor] = None, fusion_multiplier: float = 1.0,
+                                   granule: int = 16, lengths: Optional[Sequence[int]] = None, segment_cost_rows: int = 0):
+        """`forward_interaction` over PACKED rows (rr_forward_interaction_packed, NORMAL and MORES): the pairs are grouped by
+        their context length (1 + last non-zero position of `context_mask`) rounded up to `granule`; NORMAL computes the
+        cross-encoder rows [query | context] that exist, MORES the doc-side rows.  `preflmr_scores` [N, Lc, Lq] goes over
+        padded along the context axis (the reference's normalisers run over it).  `lengths`: the context lengths as the host
+        knows them (no device -> host copy).  The sharded path and pair_range slices are not packed.  Returns the dict of
+        forward_interaction plus `packed_rows` (context rows computed), `packed_segments`."""
+        dev = self.device
+        N = context_li.shape[0]
+        assert N == Bq * K and query_li.shape[0] == Bq and granule > 0, \
+            f"{tuple(query_li.shape)}, {tuple(context_li.shape)}, {K - 1}"        # interaction_rerank_model.py:123
+        Lq, Lc = query_li.shape[1], context_li.shape[1]
+        f32 = dict(device=dev, dtype=torch.float32)
+        cm = context_mask.reshape(N, Lc).to(**f32).contiguous()
+        if lengths is None:                                            # derived on the device: one device -> host copy
+            lengths = pair_lengths(cm).cpu().numpy()
+        order_h, seg_n, seg_len = group_pairs_by_length(lengths, Lc, granule, 1, segment_cost_rows)
+        assert len(order_h) == N, "one length per pair"
+        order = torch.from_numpy(order_h).to(dev, non_blocking=True)
+        q = torch.div(order, K, rounding_mode="floor")                 # query tensors per pair
+        q_p = query_li.to(**f32).index_select(0, q).contiguous()
+        qm_p = query_mask.reshape(Bq, Lq).to(**f32).index_select(0, q).contiguous()
+        c_p = pack_rows(context_li.to(**f32), order, seg_n, seg_len)
+        cm_p = pack_rows(cm, order, seg_n, seg_len)
+        ps = None
+        if preflmr_scores is not None:
+            if tuple(preflmr_scores.shape) != (N, Lc, Lq):
+                raise AssertionError(f"preflmr_scores must be [{N}, {Lc}, {Lq}], got {tuple(preflmr_scores.shape)}")
+            ps = pack_fusion_scores(preflmr_scores.to(**f32), order)
+        lp, lp2 = torch.empty(N, **f32), torch.empty(N, **f32)
+        sn, sl = (C.c_int32 * len(seg_n))(*seg_n), (C.c_int32 * len(seg_n))(*seg_len)
+        L.check(self.lib.rr_forward_interaction_packed(self.h, L.ptr(q_p), L.ptr(c_p), L.ptr(qm_p), L.ptr(cm_p), L.ptr(ps),
+                                                       float(fusion_multiplier), len(seg_n), sn, sl, Lc, Lq, L.ptr(lp),
+                                                       L.ptr(lp2), torch.cuda.current_stream(dev).cuda_stream),
+                self.h, "rr_forward_interaction_packed")
+        logits, logits2 = scatter_packed(lp, order), scatter_packed(lp2, order)
+        two = self.arch["loss_fn"] == "2H_BCE"
+        if labels is not None:
+            assert labels.numel() == N
+        out = self.head(logits, logits2 if two else None, labels, Bq, K, want_scores=want_scores, want_order=want_order)
+        out["logits"], out["logits2"] = logits, logits2
+        if not want_loss:
+            out["loss"] = None
+        out["packed_rows"] = sum(n * s for n, s in zip(seg_n, seg_len))
+        out["packed_segments"] = len(seg_n)
+        return out
+
     def head(self, logits: torch.Tensor, logits2: Optional[torch.Tensor], labels: Optional[torch.Tensor], Bq: int,
              K: int, want_scores: bool = False, want_order: bool = True):
         """Scoring head on complete logits (after the cross-rank all-gather)."""
@@ -586,8 +692,8 @@ class RerankEngine:
                 packed: bool = False):
         """Allocate everything a forward of at most this shape needs (rr_reserve) on the current stream: afterwards the
         forward neither allocates nor synchronises (a precondition for capturing it into a hipGraph).  `packed`: for
-        forward_ids_packed / forward_ids_bucketed, whose image features are per PAIR (n_queries = n_pairs, as
-        include/rerank_mi355.h documents for rr_forward_packed)."""
+        forward_ids_packed / forward_ids_bucketed / forward_joint_packed / forward_interaction_packed, whose per-query
+        tensors are per PAIR (n_queries = n_pairs, as include/rerank_mi355.h documents for the packed calls)."""
         if packed:
             n_queries = n_pairs
         L.check(self.lib.rr_reserve(self.h, int(n_pairs), int(n_queries), int(len_a), int(len_b), int(with_fusion),
@@ -613,6 +719,9 @@ class FullContextRerankModel(torch.nn.Module):
       `text_only`       – build without the vision weights (`text_only` module of the reference configs)
       `native_tokenizer`– True: assemble the pair inputs with the library's multi-threaded C++ WordPiece tokenizer
                           (rr_tok_prepare_pairs) built from `tokenizer`'s vocabulary instead of calling `tokenizer`
+      `packed_rows`     – True: `forward_ids` and the text `forward` run over packed rows (RerankEngine.forward_ids_packed; the
+                          text call hands the tokenizer's pair lengths over, no device -> host copy).  Default False: padded.
+                          Calls with `pair_range` (the sharded path) stay padded.
     """
 
     def __init__(self, config, state_dict: Optional[Dict[str, torch.Tensor]] = None, device=None):
@@ -634,6 +743,7 @@ class FullContextRerankModel(torch.nn.Module):
             self.native_tokenizer = NativePairTokenizer(self.query_tokenizer,
                                                         do_lower_case=getattr(self.query_tokenizer, "do_lower_case", True))
         self.image_feature_fn = _get(config, "image_feature_fn", None)
+        self.packed_rows = bool(_get(config, "packed_rows", False))
         self.context_vision_encoder = _FrozenStub()
         if state_dict is not None:
             self.engine.load_state_dict(state_dict)
@@ -657,8 +767,16 @@ class FullContextRerankModel(torch.nn.Module):
             labels_t = torch.tensor(labels, dtype=torch.float32, device=self.engine.device)
         else:
             labels_t = None
-        r = self.engine.forward_ids(input_ids, attention_mask, token_type_ids, Bq, K, image_cls, image_patches,
-                                    labels_t, **kw)
+        if self.packed_rows and kw.get("pair_range") is None:     # config `packed_rows`: the same logits over packed rows
+            kw.pop("pair_range", None)
+            want_loss = kw.pop("want_loss", True)
+            r = self.engine.forward_ids_packed(input_ids, attention_mask, token_type_ids, Bq, K, image_cls, image_patches,
+                                               labels_t, **kw)
+            if not want_loss:
+                r["loss"] = None
+        else:
+            r = self.engine.forward_ids(input_ids, attention_mask, token_type_ids, Bq, K, image_cls, image_patches,
+                                        labels_t, **kw)
         logits = r["logits"]
         logits = logits.view(Bq, K) if arch["loss_fn"] == "negative_sampling" else logits.view(N, 1)
         out = RerankOutput(loss=r["loss"], logits=logits)
@@ -696,14 +814,19 @@ class FullContextRerankModel(torch.nn.Module):
             else:
                 raise NotImplementedError("query_pixel_values given but neither config.vision_encoder nor "
                                           "config.image_feature_fn (CLIP ViT) is set")
+        kw = {}
+        if self.packed_rows:              # the tokenizer's output is host memory: the pair lengths cost no device -> host copy
+            kw["lengths"] = pair_lengths(enc["input_ids"], enc["attention_mask"]).numpy()
         return self.forward_ids(enc["input_ids"].to(dev), enc["attention_mask"].to(dev),
                                 enc["token_type_ids"].to(dev), num_negative_examples, cls, patches,
-                                labels if labels else None)
+                                labels if labels else None, **kw)
 
 
 class InteractionRerankModel(torch.nn.Module):
     """Drop-in for the reference's `InteractionRerankModel` (interaction_rerank_model.py:86-166), inference only:
-    `config.interaction_type` "MORES" selects the MORES stack (mores_model.py), anything else the CrossEncoder."""
+    `config.interaction_type` "MORES" selects the MORES stack (mores_model.py), anything else the CrossEncoder.
+    Optional config key `packed_rows` (default False): `forward` runs over packed rows (RerankEngine.forward_interaction_packed;
+    pass `lengths=` to spare the device -> host copy of the context lengths).  Calls with `pair_range` stay padded."""
 
     def __init__(self, config, state_dict: Optional[Dict[str, torch.Tensor]] = None, device=None):
         super().__init__()
@@ -711,6 +834,7 @@ class InteractionRerankModel(torch.nn.Module):
         kind = "mores" if _get(config, "interaction_type", "NORMAL") == "MORES" else "interaction"
         arch = make_arch(config, model_kind=kind, has_vision=0)
         self.engine = RerankEngine(arch, device)
+        self.packed_rows = bool(_get(config, "packed_rows", False))
         if state_dict is not None:
             self.engine.load_state_dict(state_dict)
 
@@ -730,9 +854,15 @@ class InteractionRerankModel(torch.nn.Module):
             if arch["loss_fn"] == "negative_sampling":
                 raise AssertionError("Labels should not be provided for negative sampling loss function")
             labels_t = torch.tensor(labels, dtype=torch.float32, device=self.engine.device)
-        r = self.engine.forward_interaction(query_late_interaction, context_late_interaction, query_mask, context_mask,
-                                            Bq, K, labels_t, preflmr_scores=preflmr_scores,
-                                            fusion_multiplier=float(fusion_multiplier), **kw)
+        if self.packed_rows and kw.get("pair_range") is None:     # config `packed_rows`: the same logits over packed rows
+            kw.pop("pair_range", None)
+            r = self.engine.forward_interaction_packed(query_late_interaction, context_late_interaction, query_mask,
+                                                       context_mask, Bq, K, labels_t, preflmr_scores=preflmr_scores,
+                                                       fusion_multiplier=float(fusion_multiplier), **kw)
+        else:
+            r = self.engine.forward_interaction(query_late_interaction, context_late_interaction, query_mask, context_mask,
+                                                Bq, K, labels_t, preflmr_scores=preflmr_scores,
+                                                fusion_multiplier=float(fusion_multiplier), **kw)
         logits = r["logits"]
         logits = logits.view(Bq, K) if arch["loss_fn"] == "negative_sampling" else logits.view(N, 1)
         out = RerankOutput(loss=r["loss"], logits=logits)
@@ -745,7 +875,9 @@ class InteractionRerankModel(torch.nn.Module):
 class RerankModel(torch.nn.Module):
     """Drop-in for the reference's `RerankModel` (rerank_model.py:76-331; the "softmax"/2-head variant), inference
     only.  Extra optional config keys: `arch`, `image_feature_fn` (pixel_values -> (cls, patches)),
-    `instruction_token_id` (id of `mask_instruction_token`, rerank_model.py:161-169; None = no instruction masking)."""
+    `instruction_token_id` (id of `mask_instruction_token`, rerank_model.py:161-169; None = no instruction masking),
+    `packed_rows` (default False: `forward` runs over packed rows, RerankEngine.forward_joint_packed; pass `lengths=` with the
+    joint sequences' lengths to spare the device -> host copy; calls with `pair_range` stay padded)."""
 
     def __init__(self, config, state_dict: Optional[Dict[str, torch.Tensor]] = None, device=None):
         super().__init__()
@@ -753,6 +885,7 @@ class RerankModel(torch.nn.Module):
         self.engine = RerankEngine(make_arch(config), device)
         self.image_feature_fn = _get(config, "image_feature_fn", None)
         self.instruction_token_id = _get(config, "instruction_token_id", None)
+        self.packed_rows = bool(_get(config, "packed_rows", False))
         self.context_vision_encoder = _FrozenStub()
         if state_dict is not None:
             self.engine.load_state_dict(state_dict)
@@ -789,8 +922,13 @@ class RerankModel(torch.nn.Module):
             else:
                 raise NotImplementedError("query_pixel_values given but neither config.vision_encoder nor "
                                           "config.image_feature_fn (CLIP ViT) is set")
-        r = self.engine.forward_joint(joint_ids, joint_am, Bq, K, ql, cls, patches, self.instruction_token_id,
-                                      preflmr_scores=preflmr_scores, fusion_multiplier=float(fusion_multiplier), **kw)
+        if self.packed_rows and kw.get("pair_range") is None:     # config `packed_rows`: the same logits over packed rows
+            kw.pop("pair_range", None)
+            r = self.engine.forward_joint_packed(joint_ids, joint_am, Bq, K, ql, cls, patches, self.instruction_token_id,
+                                                 preflmr_scores=preflmr_scores, fusion_multiplier=float(fusion_multiplier), **kw)
+        else:
+            r = self.engine.forward_joint(joint_ids, joint_am, Bq, K, ql, cls, patches, self.instruction_token_id,
+                                          preflmr_scores=preflmr_scores, fusion_multiplier=float(fusion_multiplier), **kw)
         out = RerankOutput(loss=r["loss"], logits=r["logits"].view(N, 1))
         for k in ("scores", "order", "logits2"):
             if r.get(k) is not None:

@@ -152,3 +152,39 @@ def group_pairs_by_length(lengths, padded_len: int, granule: int, min_len: int =
         segs.reverse()
         cnt, szs = [pre[j] - pre[i] for i, j in segs], [szs[j - 1] for i, j in segs]
     return order, cnt, szs
+
+
+def pair_lengths(*rows) -> torch.Tensor:
+    """Length of every pair for the packed forwards: 1 + index of the last non-zero entry over the union of the given [N, S]
+    tensors (ids / attention masks of the full-context and joint sequences, the context mask of the interaction rerankers),
+    at least 1.  Stays on the tensors' device."""
+    used = None
+    for t in rows:
+        nz = t.reshape(t.shape[0], -1) != 0
+        used = nz if used is None else used | nz
+    cols = torch.arange(1, used.shape[1] + 1, device=used.device)
+    return (used * cols).amax(1).clamp_(min=1)
+
+
+def pack_rows(t: torch.Tensor, order: torch.Tensor, seg_n, seg_len) -> torch.Tensor:
+    """Packed layout of a per-pair tensor t [N, S, ...] for the rr_forward_*_packed calls: segment after segment, inside a
+    segment pair after pair (`order`, as group_pairs_by_length returns it), the first seg_len[i] positions of every pair:
+    [sum_i seg_n[i] * seg_len[i], ...].  Index plumbing only (index_select + slicing)."""
+    parts, o = [], 0
+    for n, sl in zip(seg_n, seg_len):
+        parts.append(t.index_select(0, order[o: o + n])[:, :sl].reshape(n * sl, *t.shape[2:]))
+        o += n
+    return torch.cat(parts).contiguous()
+
+
+def scatter_packed(values: torch.Tensor, order: torch.Tensor) -> torch.Tensor:
+    """Inverse of the packed pair order: out[order[i]] = values[i] (logits come back from the packed calls in packed order)."""
+    return torch.empty_like(values).index_copy_(0, order, values)
+
+
+def pack_fusion_scores(scores: torch.Tensor, order: torch.Tensor, row0: int = 0, rows: int = -1) -> torch.Tensor:
+    """PreFLMR fusion scores of a packed call: rows row0 .. row0 + rows of every pair's context axis (the joint sequence's context
+    tokens sit at score rows 2 .. 2 + S - query_len, rerank_model.py:276-284; the interaction scores [N, Lc, Lq] are all context)
+    in packed pair order — still PADDED along that axis: the reference's softmax over the context tokens runs over all of it."""
+    rows = scores.shape[1] - row0 if rows < 0 else rows
+    return scores[:, row0:row0 + rows].index_select(0, order).contiguous()

@@ -1116,13 +1116,103 @@ int ensure_adj(rr_model* m, size_t bytes, hipStream_t st) {
   return RR_OK;
 }
 
+// One forward call as an exported entry point hands it over (include/rerank_mi355.h); forward_full and forward_interaction
+// take it.  FAM_INTERACTION is NORMAL or MORES, after the handle's model_kind.
+enum Family { FAM_FULL, FAM_JOINT, FAM_INTERACTION };
+struct Request {
+  Family family = FAM_FULL;
+  // full / joint: token ids, attention mask, token types [pairs, len] and the per-query image features
+  const int64_t *ids = nullptr, *mask = nullptr, *token_types = nullptr;
+  const float *image_cls = nullptr, *image_patches = nullptr;
+  // interaction: late-interaction tensors query_li [Bq, Lq, D], context_li [N, Lc, D] and their 0/1 masks
+  const float *query_li = nullptr, *context_li = nullptr, *query_mask = nullptr, *context_mask = nullptr;
+  int Bq = 0, K = 0;
+  int len = 0;                 // full / joint: S, the row length (packed: the padded one); interaction: Lc, the context length
+  int q_len = 0;               // joint: query tokens at the head of the joint sequence; interaction: Lq
+  long long instruction_token = -1;
+  const float* labels = nullptr;
+  int pair_begin = 0, pair_end = 0;
+  float *logits = nullptr, *logits2 = nullptr, *loss = nullptr, *scores = nullptr;
+  int32_t* order = nullptr;
+  hipStream_t stream = nullptr;
+  const float* fusion_scores = nullptr;   // PreFLMR attention fusion (joint / NORMAL interaction)
+  float fusion_mult = 1.0f;
+  bool packed = false;                    // rr_forward_*_packed: the segment table (pairs, length per pair)
+  int n_segments = 0;
+  const int32_t *seg_pairs = nullptr, *seg_len = nullptr;
+};
+
+// The rows of a forward: the segment list (one segment for a padded or length-bucketed call) and what the cross-encoder needs
+// to know about it.
+struct RowPlan {
+  std::vector<Seg> segs;
+  int n = 0;                   // pairs
+  bool packed = false;         // the call came as a segment table: the text stack runs per segment
+  bool ce_segs = false;        // the cross-encoder runs per segment (run_layer's SegView list)
+  int vis_pos0 = -1;           // first cross-encoder position of the vision tokens; -1: plain positions 0 .. T-1
+  int sched_T = 0;             // rows per pair the cross-encoder's attention schedule assumes
+};
+
+// `len` rows per pair of the call (packed: the padded length) plus `extra` cross-encoder rows (vision tokens P; interaction:
+// query tokens Lq).  bucket_of > 0: a full-context call of a shorter length bucket (rr_set_padded_seq_len), whose vision
+// tokens keep the positions behind the padded text.
+RowPlan plan_rows(Family fam, int n, int len, int extra, const std::vector<std::pair<int, int>>& table, int bucket_of) {
+  RowPlan p;
+  p.n = n;
+  p.packed = !table.empty();
+  size_t p0 = 0, r0 = 0, rt0 = 0;
+  for (const auto& g : table) {
+    p.segs.push_back(Seg{g.first, g.second, g.second + extra, p0, r0, rt0});
+    p0 += (size_t)g.first;
+    r0 += (size_t)g.first * g.second;
+    rt0 += (size_t)g.first * (g.second + extra);
+  }
+  if (!p.packed) p.segs.push_back(Seg{n, len, len + extra, 0, 0, 0});
+  const bool full = fam == FAM_FULL;      // (joint: [query | image | context] is padded at its end, no position moves)
+  p.vis_pos0 = !full ? -1 : p.packed ? len : bucket_of > 0 ? bucket_of : -1;
+  // a full-context packed call of ONE segment runs its cross-encoder as a bucketed call does, on the schedule of its own rows
+  p.ce_segs = p.packed && !(full && p.segs.size() == 1);
+  p.sched_T = p.ce_segs ? len + extra : p.segs.back().T;   // (per segment: the padded call's rows per pair)
+  return p;
+}
+
+// The scoring head over complete logits [Bq, K] (rr_launch_head).  joint: RerankModel's loss_fn(logits, logits)
+// (rerank_model.py:328) — the logits are their own targets, and 2H_BCE takes loss kind 3.
+int launch_head(rr_model* m, hipStream_t st, const Work& w, const float* logits, const float* logits2, const float* labels, int Bq,
+                int K, bool joint, float* loss, float* scores, int32_t* order) {
+  const rr_config& c = m->cfg;
+  const bool two = c.loss_kind == RR_LOSS_2H_BCE;
+  const int has_pw = !std::isnan(c.pos_weight);
+  RR_RUN(m, st, RR_K_HEAD, 0.0, 12.0 * Bq * K,
+         rr_launch_head(logits, two ? logits2 : nullptr, joint ? logits : labels, Bq, K, (joint && two) ? 3 : c.loss_kind,
+                        has_pw ? c.pos_weight : 1.0f, has_pw, scores, order, loss, w.part_l, w.part_w, st));
+  return RR_OK;
+}
+
+// The head and pair-slice part of a request (both forwards, rr_head, rr_head_joint): loss / scores / order need every pair,
+// and what the scoring head reads must be there when it runs.
+int check_head(rr_model* m, const char* what, int Bq, int K, int pair_begin, long long pair_end, const float* labels,
+               const float* logits2, const float* loss, const float* scores, const int32_t* order, bool joint) {
+  const rr_config& c = m->cfg;
+  const long long N = (long long)Bq * K;
+  if (pair_begin < 0 || pair_end > N || pair_begin >= pair_end)
+    return fail(m, RR_ERR_BAD_SHAPE, "%s: pair slice [%d,%lld) outside [0,%lld)", what, pair_begin, pair_end, N);
+  const bool full = pair_begin == 0 && pair_end == N, head = loss || scores || order;
+  if (c.loss_kind == RR_LOSS_NEGATIVE_SAMPLING && labels)
+    return fail(m, RR_ERR_BAD_ARG, "Labels should not be provided for negative sampling loss function");
+  if (!full && head) return fail(m, RR_ERR_BAD_ARG, "loss/scores/order need the full pair range; use rr_head after gathering logits");
+  if (c.loss_kind == RR_LOSS_2H_BCE && head && !logits2) return fail(m, RR_ERR_BAD_ARG, "%s: 2H_BCE head needs logits2 (first head)", what);
+  if (K > 4096 && head) return fail(m, RR_ERR_UNSUPPORTED, "%s: K=%d > 4096", what, K);
+  if (joint && c.loss_kind == RR_LOSS_NEGATIVE_SAMPLING && loss)
+    return fail(m, RR_ERR_UNSUPPORTED, "RerankModel with negative_sampling loss is not covered (no reference config)");
+  return RR_OK;
+}
+
 // CLS heads + (when this call covers every pair) the scoring head.  classifier1 -> "logits", classifier2 ->
 // "logits_secondary" (utils.py:105-108); for 2H_BCE the ranked logit is the second head (rerank_model.py:589-590).
-int run_heads(rr_model* m, hipStream_t st, Work& w, const std::vector<Seg>& segs, int Bq, int K, int pair_begin, bool full,
-              const float* labels, float* logits_out, float* logits2_out, float* loss_out, float* scores_out,
-              int32_t* order_out, bool logits_as_targets = false) {
+int run_heads(rr_model* m, hipStream_t st, Work& w, const std::vector<Seg>& segs, const Request& r) {
   const rr_config& c = m->cfg;
-  const int Hc = c.ce_hidden, N = Bq * K;
+  const int Hc = c.ce_hidden;
   std::vector<Seg> one;
   if (m->cls_rows) {      // the cross-encoder's last layer ran on the CLS rows only (run_cross_encoder): n contiguous rows
     int n = 0;
@@ -1130,8 +1220,8 @@ int run_heads(rr_model* m, hipStream_t st, Work& w, const std::vector<Seg>& segs
     one.push_back(Seg{n, 1, 1, 0, 0, 0});
   }
   for (const Seg& g : (m->cls_rows ? one : segs)) {
-    float* out_a = logits_out + pair_begin + g.p0;
-    float* out_b = (logits2_out ? logits2_out + pair_begin : w.l2) + g.p0;
+    float* out_a = r.logits + r.pair_begin + g.p0;
+    float* out_b = (r.logits2 ? r.logits2 + r.pair_begin : w.l2) + g.p0;
     const float* h = m->cls_rows ? m->cls_rows : w.h32 + g.rt0 * Hc;
     if (c.loss_kind == RR_LOSS_2H_BCE) {
       RR_RUN(m, st, RR_K_HEAD, 4.0 * g.n * Hc, 8.0 * g.n * Hc,
@@ -1141,25 +1231,19 @@ int run_heads(rr_model* m, hipStream_t st, Work& w, const std::vector<Seg>& segs
              rr_launch_cls_heads(h, g.T, Hc, g.n, m->cls1_w, m->cls1_b, m->cls2_w, m->cls2_b, out_a, out_b, st));
     }
   }
-  if (full && (loss_out || scores_out || order_out)) {
-    const int has_pw = !std::isnan(c.pos_weight);
-    RR_RUN(m, st, RR_K_HEAD, 0.0, 12.0 * N,
-           rr_launch_head(logits_out, c.loss_kind == RR_LOSS_2H_BCE ? logits2_out : nullptr, labels, Bq, K,
-                          (logits_as_targets && c.loss_kind == RR_LOSS_2H_BCE) ? 3 : c.loss_kind,
-                          has_pw ? c.pos_weight : 1.0f, has_pw, scores_out, order_out, loss_out, w.part_l, w.part_w, st));
-  }
+  if (r.pair_begin == 0 && r.pair_end == r.Bq * r.K && (r.loss || r.scores || r.order))
+    return launch_head(m, st, w, r.logits, r.logits2, r.labels, r.Bq, r.K, r.family == FAM_JOINT, r.loss, r.scores, r.order);
   return RR_OK;
 }
 
 // CrossEncoder over AttentionFusionBertModel (utils.py:85-108, attention_fusion.py:61-160): Linear(D -> Hc) ->
 // embeddings(inputs_embeds) -> Lc layers.  Input: w.li16 [n*T, D], w.ce_bias [n, T]; output: w.h32 [n*T, Hc].
-// `segs`: one entry for the plain forward.  vis_pos0 >= 0: the vision tokens of every pair take the positions from vis_pos0 on
-// (length-bucketed / packed calls: behind the PADDED text), -1: plain positions 0 .. T-1.
-// pad_T > 0: the padded call's rows per pair (packed joint / interaction calls, whose cross-encoder positions do not move;
-// the full-context packed call derives it from vis_pos0).  Packed with `adj`: the bias is laid out per segment (run_layer).
-int run_cross_encoder(rr_model* m, hipStream_t st, Work& w, const std::vector<Seg>& segs, const float* adj = nullptr,
-                      int adj_ld = 0, int vis_pos0 = -1, int pad_T = 0) {
+// The rows, the vision tokens' positions and the attention schedule come from the plan (plan_rows).  Per segment with `adj`:
+// the bias is laid out per segment (run_layer).
+int run_cross_encoder(rr_model* m, hipStream_t st, Work& w, const RowPlan& plan, const float* adj, int adj_ld) {
   const rr_config& c = m->cfg;
+  const std::vector<Seg>& segs = plan.segs;
+  const int vis_pos0 = plan.vis_pos0;
   const int D = c.li_dim, Hc = c.ce_hidden, Ic = c.ce_intermediate;
   const Seg& last = segs.back();
   const int RT = (int)(last.rt0 + (size_t)last.n * last.T);
@@ -1175,7 +1259,6 @@ int run_cross_encoder(rr_model* m, hipStream_t st, Work& w, const std::vector<Se
                                  vis_pos0 >= 0 ? vis_pos0 : 0, cls_only ? 1 : 0));
     view.push_back(SegView{g.n, g.T, g.rt0});
   }
-  const bool packed = segs.size() > 1 || pad_T > 0;
   m->cls_rows = nullptr;
   if (cls_only) {
     // Only the CLS row of every pair leaves the cross-encoder (the classifiers read hidden state [:, 0], utils.py:105-108):
@@ -1227,11 +1310,10 @@ int run_cross_encoder(rr_model* m, hipStream_t st, Work& w, const std::vector<Se
     ResidSrc rs{w.h32, nullptr, nullptr, nullptr};
     int folded = OP_NORMALISED;
     for (int l = 0; l < c.ce_layers; ++l)
-      RR_TRY(run_layer(m, st, m->ce_layers[l], n, packed ? (pad_T > 0 ? pad_T : vis_pos0 + (last.T - last.S)) : last.T,   // (packed: the padded call's rows per pair, for the attention schedule)
-                       Hc, c.ce_heads, Ic, c.ln_eps, w.ce_bias, w, rs, folded,
+      RR_TRY(run_layer(m, st, m->ce_layers[l], n, plan.sched_T, Hc, c.ce_heads, Ic, c.ln_eps, w.ce_bias, w, rs, folded,
                        l == c.ce_layers - 1, true,          // the CLS heads read the fp32 rows of the last layer
                        adj, adj_ld,                         // attention fusion: the same bias in every layer
-                       packed ? &view : nullptr));
+                       plan.ce_segs ? &view : nullptr));
   }
   m->tap_ce = w.h32;
   m->tap_ce_elems = (size_t)RT * Hc;
@@ -1573,31 +1655,24 @@ static int rr_encode_image_impl(rr_handle h, const float* pixel_values, int B, f
   return RR_OK;
 }
 
-static int rr_head_impl(rr_handle h, const float* logits, const float* logits2, const float* labels, int Bq, int K,
-            float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream) {
-  if (!h || !logits) return fail(h, RR_ERR_BAD_ARG, "rr_head: null argument");
-  if (Bq <= 0 || K <= 0) return fail(h, RR_ERR_BAD_SHAPE, "rr_head: Bq=%d K=%d", Bq, K);
-  if (K > 4096) return fail(h, RR_ERR_UNSUPPORTED, "rr_head: K=%d > 4096", K);
+// rr_head / rr_head_joint: the scoring head on gathered logits (joint: with RerankModel.forward's loss, as rr_forward_joint
+// runs it)
+static int head_call(rr_handle h, const char* what, bool joint, const float* logits, const float* logits2, const float* labels,
+                     int Bq, int K, float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream) {
+  if (!h || !logits) return fail(h, RR_ERR_BAD_ARG, "%s: null argument", what);
+  if (Bq <= 0 || K <= 0) return fail(h, RR_ERR_BAD_SHAPE, "%s: Bq=%d K=%d", what, Bq, K);
   const rr_config& c = h->cfg;
-  if (c.loss_kind == RR_LOSS_NEGATIVE_SAMPLING && labels)
-    return fail(h, RR_ERR_BAD_ARG, "Labels should not be provided for negative sampling loss function");
-  if (c.loss_kind == RR_LOSS_2H_BCE && !logits2) return fail(h, RR_ERR_BAD_ARG, "rr_head: 2H_BCE needs logits2 (first head)");
+  if (joint && c.model_kind != RR_MODEL_FULL_CONTEXT) return fail(h, RR_ERR_BAD_ARG, "rr_head_joint on an interaction model");
+  RR_TRY(check_head(h, what, Bq, K, 0, (long long)Bq * K, labels, logits2, loss_out, scores_out, order_out, joint));
   hipStream_t st = (hipStream_t)hip_stream;
   RR_HIP(h, hipSetDevice(c.device));
   Work w;
   const size_t need = layout(c, 1, Bq, 8, false, nullptr, &w);
   RR_TRY(ensure_ws(h, need, st));
   layout(c, 1, Bq, 8, false, h->ws, &w);
-  const int has_pw = !std::isnan(c.pos_weight);
-  RR_RUN(h, st, RR_K_HEAD, 0.0, 12.0 * Bq * K,
-         rr_launch_head(logits, logits2, labels, Bq, K, c.loss_kind, has_pw ? c.pos_weight : 1.0f, has_pw, scores_out,
-                        order_out, loss_out, w.part_l, w.part_w, st));
-  return RR_OK;
+  return launch_head(h, st, w, logits, logits2, labels, Bq, K, joint, loss_out, scores_out, order_out);
 }
 
-// joint != 0: RerankModel.forward semantics (rerank_model.py:171-331) on the pre-assembled joint sequence:
-// token types all 0, query_mask with instruction masking, cross-encoder order [query | image | context], and the
-// reference's `loss_fn(logits, logits)` quirk (:328).
 // Sticky range error (include/rerank_mi355.h, rr_activation_range_flag): look at what the PREVIOUS forwards left in the pinned
 // word (no synchronisation: a copy still in flight simply reports one call later), refuse to go on once it is raised.
 static int range_guard_enter(rr_model* m) {
@@ -1618,57 +1693,94 @@ static int range_guard_exit(rr_model* m, hipStream_t st) {
   return RR_OK;
 }
 
-// Attention-fusion bias of a packed call into m->adj, one launch: scores [n][Tc][Tq] (the context rows, packed pair order, padded
-// context axis), segment g's pairs end after g.S - s_off context tokens (joint: g.S - q_len; interaction: g.S), so its rows
-// are g.T = Tq + that; layout per segment as run_layer reads it: [g.n][g.T][round_up(g.T, 64)]
-static int fusion_bias_packed(rr_model* m, hipStream_t st, const std::vector<Seg>& segs, const float* scores, int Tc, int Tq, int s_off,
-                              float mult) {
+// Attention-fusion bias of a forward into m->adj from scores over the Tq + Tc tokens of every pair.  Padded call: scores
+// [N][Tc + s_off][Tq], context rows from row0 on, of pairs pair_begin.., bias [n][T][*adj_ld = round_up(T, 64)]
+// (rr_launch_fusion_adj).  Packed call: scores [n][Tc][Tq] (the context rows, packed pair order, padded context axis), segment
+// g's pairs end after g.S - s_off context tokens (joint: g.S - q_len; interaction: g.S), so its rows are g.T = Tq + that; one
+// launch, layout per segment as run_layer reads it: [g.n][g.T][round_up(g.T, 64)] (rr_launch_fusion_adj_segs, *adj_ld = 0).
+static int fusion_bias(rr_model* m, hipStream_t st, const RowPlan& plan, const float* scores, int Tq, int Tc, int s_off, int row0,
+                       float mult, int pair_begin, int* adj_ld) {
+  if (!plan.packed) {
+    const int T = Tq + Tc, rows = Tc + s_off, n = plan.n;
+    *adj_ld = (T + 63) / 64 * 64;
+    const size_t need = (size_t)n * T * *adj_ld * sizeof(float);
+    RR_TRY(ensure_adj(m, need, st));
+    RR_RUN(m, st, RR_K_TAIL, 0.0, 4.0 * n * (double)rows * Tq + (double)need,
+           rr_launch_fusion_adj(scores, rows, Tq, Tc, mult, pair_begin, n, m->adj, *adj_ld, st, row0));
+    return RR_OK;
+  }
   size_t need = 0;
   double rd = 0.0;
   std::vector<int> sn, tk;
-  for (const Seg& g : segs) {
+  for (const Seg& g : plan.segs) {
     if (g.T != Tq + g.S - s_off) return fail(m, RR_ERR_BAD_ARG, "internal: fusion bias rows %d != %d + %d", g.T, Tq, g.S - s_off);
     need += (size_t)g.n * g.T * ((g.T + 63) / 64 * 64) * sizeof(float);
     rd += 4.0 * g.n * (double)Tc * Tq;
     sn.push_back(g.n);
     tk.push_back(g.S - s_off);
   }
+  *adj_ld = 0;
   RR_TRY(ensure_adj(m, need, st));
   RR_RUN(m, st, RR_K_TAIL, 0.0, rd + (double)need,
-         rr_launch_fusion_adj_segs(scores, Tc, Tq, Tc, mult, (int)segs.size(), sn.data(), tk.data(), m->adj, st, 0));
+         rr_launch_fusion_adj_segs(scores, Tc, Tq, Tc, mult, (int)plan.segs.size(), sn.data(), tk.data(), m->adj, st, 0));
   return RR_OK;
 }
 
-static int forward_full(rr_handle h, const int64_t* input_ids, const int64_t* attention_mask,
-                        const int64_t* token_type_ids, const float* image_cls, const float* image_patches, int Bq, int K,
-                        int S, const float* labels, int pair_begin, int pair_end, float* logits_out,
-                        float* logits2_out, float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream,
-                        int joint, int q_len, long long instruction_token, const float* preflmr_scores = nullptr,
-                        float fusion_multiplier = 1.0f, const std::vector<std::pair<int, int>>* packed = nullptr) {
-  // `packed` (rr_forward_packed): segments (pairs, rows per pair); the token arrays then hold the segments' pairs back to back
-  // at THEIR row length, Bq = number of pairs, K = 1 (image features per pair), S = the padded length the reference would use
+// Segment table of a packed call (rr_forward_*_packed, include/rerank_mi355.h): 1..64 non-empty segments of lengths in
+// (min_len, r.len]; the call then covers all its pairs, one per query (Bq = pairs, K = 1).
+static int packed_segments(rr_model* m, const char* what, Request& r, int min_len, int extra_rows,
+                           std::vector<std::pair<int, int>>* out) {
+  if (!r.seg_pairs || !r.seg_len) return fail(m, RR_ERR_BAD_ARG, "%s: null segment tables", what);
+  if (r.n_segments <= 0 || r.n_segments > 64) return fail(m, RR_ERR_BAD_SHAPE, "%s: %d segments (1..64)", what, r.n_segments);
+  long long pairs = 0, rows = 0;
+  for (int i = 0; i < r.n_segments; ++i) {
+    if (r.seg_pairs[i] <= 0 || r.seg_len[i] <= min_len || r.seg_len[i] > r.len)
+      return fail(m, RR_ERR_BAD_SHAPE, "%s: segment %d holds %d pairs of length %d (lengths in (%d, %d])", what, i, r.seg_pairs[i],
+                  r.seg_len[i], min_len, r.len);
+    out->emplace_back(r.seg_pairs[i], r.seg_len[i]);
+    pairs += r.seg_pairs[i];
+    rows += (long long)r.seg_pairs[i] * (r.seg_len[i] + extra_rows);
+  }
+  if (pairs > (1 << 24) || rows > (1LL << 30)) return fail(m, RR_ERR_BAD_SHAPE, "%s: %lld pairs / %lld rows", what, pairs, rows);
+  r.Bq = r.pair_end = (int)pairs;
+  r.K = 1;
+  r.pair_begin = 0;
+  return RR_OK;
+}
+
+// FullContextRerankModel.forward (rerank_model.py:523-591) on the tokenised pairs.  FAM_JOINT: RerankModel.forward semantics
+// (rerank_model.py:171-331) on the pre-assembled joint sequence: token types all 0, query_mask with instruction masking,
+// cross-encoder order [query | image | context], and the reference's `loss_fn(logits, logits)` quirk (:328).
+// Packed: the token arrays hold the segments' pairs back to back at THEIR row length, image features per pair, r.len = the
+// padded length the reference would use.
+static int forward_full(rr_handle h, Request r) {
   if (!h) return RR_ERR_BAD_ARG;
   rr_model* m = h;
   const rr_config& c = m->cfg;
+  const bool joint = r.family == FAM_JOINT;
+  const bool vision = r.image_cls != nullptr || r.image_patches != nullptr;
+  const int P = vision ? c.prefix_len + c.n_patches : 0;
+  std::vector<std::pair<int, int>> table;
+  if (r.packed)
+    RR_TRY(packed_segments(m, joint ? "rr_forward_joint_packed" : "rr_forward_packed", r, joint ? std::max(r.q_len, 0) : 0,
+                           joint ? c.prefix_len + c.n_patches : P, &table));
   if (c.model_kind != RR_MODEL_FULL_CONTEXT) return fail(m, RR_ERR_BAD_ARG, "rr_forward on an interaction model; use rr_forward_interaction");
   if (!m->finalized) return fail(m, RR_ERR_BAD_ARG, "rr_forward before rr_finalize_weights");
   RR_TRY(range_guard_enter(m));
-  if (!input_ids || !attention_mask || !logits_out) return fail(m, RR_ERR_BAD_ARG, "rr_forward: null input_ids/attention_mask/logits_out");
+  if (!r.ids || !r.mask || !r.logits) return fail(m, RR_ERR_BAD_ARG, "rr_forward: null input_ids/attention_mask/logits_out");
+  const int Bq = r.Bq, K = r.K, S = r.len, q_len = r.q_len, pair_begin = r.pair_begin;
   if (Bq <= 0 || K <= 0 || S <= 0) return fail(m, RR_ERR_BAD_SHAPE, "rr_forward: Bq=%d K=%d S=%d", Bq, K, S);
-  const int N = Bq * K;
-  if (pair_begin < 0 || pair_end > N || pair_begin >= pair_end)
-    return fail(m, RR_ERR_BAD_SHAPE, "rr_forward: pair slice [%d,%d) outside [0,%d)", pair_begin, pair_end, N);
+  RR_TRY(check_head(m, "rr_forward", Bq, K, pair_begin, r.pair_end, r.labels, r.logits2, r.loss, r.scores, r.order, joint));
   if (S > c.max_pos) return fail(m, RR_ERR_BAD_SHAPE, "seq_len %d exceeds max_position_embeddings %d", S, c.max_pos);
-  const bool vision = image_cls != nullptr || image_patches != nullptr;
-  if (vision && !(image_cls && image_patches)) return fail(m, RR_ERR_BAD_ARG, "image_cls and image_patches must be given together");
+  if (vision && !(r.image_cls && r.image_patches)) return fail(m, RR_ERR_BAD_ARG, "image_cls and image_patches must be given together");
   if (vision && !c.has_vision) return fail(m, RR_ERR_UNSUPPORTED, "image features passed to a text_only model");
-  const int P = vision ? c.prefix_len + c.n_patches : 0, T = S + P;
+  const int T = S + P;
   if (T > c.ce_max_pos)
     return fail(m, RR_ERR_BAD_SHAPE, "cross-encoder length %d exceeds cross_encoder_max_position_embeddings %d", T, c.ce_max_pos);
   // length-bucketed forward (rr_set_padded_seq_len): S is this call's (shorter) row length, the cross-encoder positions of the
   // vision tokens are those behind the padded text
-  int vis_pos0 = -1;
-  if (m->padded_S > 0 && !joint && !packed && S != m->padded_S) {
+  int bucket_of = 0;
+  if (m->padded_S > 0 && !joint && !r.packed && S != m->padded_S) {
     if (S > m->padded_S) return fail(m, RR_ERR_BAD_SHAPE, "seq_len %d exceeds the padded length %d set by rr_set_padded_seq_len", S, m->padded_S);
     if (m->padded_S + P > c.ce_max_pos)
       return fail(m, RR_ERR_BAD_SHAPE, "padded cross-encoder length %d exceeds cross_encoder_max_position_embeddings %d", m->padded_S + P, c.ce_max_pos);
@@ -1677,68 +1789,41 @@ static int forward_full(rr_handle h, const int64_t* input_ids, const int64_t* at
     if (vision && S < (m->padded_S < c.cross_attn_len ? m->padded_S : c.cross_attn_len))
       return fail(m, RR_ERR_BAD_SHAPE, "bucketed seq_len %d is below the %d text rows the vision mapping network attends to", S,
                   m->padded_S < c.cross_attn_len ? m->padded_S : c.cross_attn_len);
-    vis_pos0 = m->padded_S;
+    bucket_of = m->padded_S;
   }
-  if (packed) {
-    if (K != 1) return fail(m, RR_ERR_BAD_ARG, "internal: packed forward is per pair");
-    if (!joint) vis_pos0 = S;     // (joint: [query | image | context] is padded at its end, no position moves)
-  }
-  const bool full = pair_begin == 0 && pair_end == N;
-  if (c.loss_kind == RR_LOSS_NEGATIVE_SAMPLING && labels)
-    return fail(m, RR_ERR_BAD_ARG, "Labels should not be provided for negative sampling loss function");
-  if (!full && (loss_out || scores_out || order_out))
-    return fail(m, RR_ERR_BAD_ARG, "loss/scores/order need the full pair range; use rr_head after gathering logits");
-  if (c.loss_kind == RR_LOSS_2H_BCE && full && (loss_out || scores_out) && !logits2_out)
-    return fail(m, RR_ERR_BAD_ARG, "2H_BCE head needs logits2_out");
-  if (K > 4096 && (loss_out || scores_out || order_out)) return fail(m, RR_ERR_UNSUPPORTED, "K=%d > 4096", K);
   if (joint) {
     if (!vision) return fail(m, RR_ERR_UNSUPPORTED, "text_only is not implemented for this model");   // rerank_model.py:184-185
     if (q_len <= 0 || q_len >= S) return fail(m, RR_ERR_BAD_SHAPE, "query length %d outside (0,%d)", q_len, S);
-    if (c.loss_kind == RR_LOSS_NEGATIVE_SAMPLING && loss_out)
-      return fail(m, RR_ERR_UNSUPPORTED, "RerankModel with negative_sampling loss is not covered (no reference config)");
   }
 
-  hipStream_t st = (hipStream_t)hip_stream;
+  hipStream_t st = r.stream;
   RR_HIP(m, hipSetDevice(c.device));
-  const int n = pair_end - pair_begin;
-  const int q_lo = pair_begin / K, q_hi = (pair_end - 1) / K, nq = q_hi - q_lo + 1;   // queries touched by the slice
+  const int n = r.pair_end - pair_begin;
+  const int q_lo = pair_begin / K, q_hi = (r.pair_end - 1) / K, nq = q_hi - q_lo + 1;   // queries touched by the slice
   Work w;
   const size_t need = layout(c, n, Bq, S, vision, nullptr, &w);
   RR_TRY(ensure_ws(m, need, st));
   layout(c, n, Bq, S, vision, m->ws, &w);
   m->last_stream = st;
 
-  const int Hd = c.hidden, I = c.intermediate, D = c.li_dim, Hc = c.ce_hidden, Ic = c.ce_intermediate;
-  (void)Hc; (void)Ic;
-  const int64_t* ids = input_ids + (size_t)pair_begin * S;
-  const int64_t* am = attention_mask + (size_t)pair_begin * S;
-  const int64_t* tts = token_type_ids ? token_type_ids + (size_t)pair_begin * S : nullptr;
-  // segments: one (n pairs of S rows) for the plain forward
-  std::vector<Seg> segs;
+  const int Hd = c.hidden, I = c.intermediate, D = c.li_dim;
+  const int64_t* ids = r.ids + (size_t)pair_begin * S;
+  const int64_t* am = r.mask + (size_t)pair_begin * S;
+  const int64_t* tts = r.token_types ? r.token_types + (size_t)pair_begin * S : nullptr;
+  const RowPlan plan = plan_rows(r.family, n, S, P, table, bucket_of);
+  const std::vector<Seg>& segs = plan.segs;
   std::vector<SegView> text_view;
-  if (packed) {
-    size_t p0 = 0, r0 = 0, rt0 = 0;
-    for (const auto& g : *packed) {
-      segs.push_back(Seg{g.first, g.second, g.second + P, p0, r0, rt0});
-      p0 += (size_t)g.first;
-      r0 += (size_t)g.first * g.second;
-      rt0 += (size_t)g.first * (g.second + P);
-    }
-    for (const Seg& g : segs) text_view.push_back(SegView{g.n, g.S, g.r0});
-  } else {
-    segs.push_back(Seg{n, S, T, 0, 0, 0});
-  }
+  for (const Seg& g : segs) text_view.push_back(SegView{g.n, g.S, g.r0});
   const int R = (int)(segs.back().r0 + (size_t)segs.back().n * segs.back().S);       // text rows of the call
   const int RT = (int)(segs.back().rt0 + (size_t)segs.back().n * segs.back().T);     // cross-encoder rows
-  const std::vector<SegView>* tv = packed ? &text_view : nullptr;
+  const std::vector<SegView>* tv = plan.packed ? &text_view : nullptr;
 
   // ---- masks -> additive key bias (text: tokenizer mask; cross encoder: id != 0, vision = 1)
   const int txt_split = joint ? q_len : (1 << 30), txt_shift = joint ? P : 0;   // [query | image | context] reorder
-  const int vis_off = joint ? q_len : S;                                           // where the image tokens go
   if (joint) {
     for (const Seg& g : segs)
       RR_RUN(m, st, RR_K_EMBED, 0.0, 24.0 * g.n * g.S + 4.0 * g.n * g.T,
-             rr_launch_joint_masks(ids + g.r0, am + g.r0, g.n, g.S, P, q_len, instruction_token, w.text_bias + g.r0,
+             rr_launch_joint_masks(ids + g.r0, am + g.r0, g.n, g.S, P, q_len, r.instruction_token, w.text_bias + g.r0,
                                    w.li_mask + g.r0, w.ce_bias + g.rt0, st));
   } else {
     for (const Seg& g : segs)
@@ -1777,15 +1862,16 @@ static int forward_full(rr_handle h, const int64_t* input_ids, const int64_t* at
 
   if (vision) {
     const int np = c.n_patches, PL = c.prefix_len, Vh = c.vision_hidden, mid = D * PL / 2, outd = D * PL;
-    const float* cls = image_cls + (size_t)q_lo * Vh;
-    const float* pat = image_patches + (size_t)q_lo * np * Vh;
+    auto vis_at = [&](const Seg& g) { return joint ? q_len : g.S; };   // where a pair's image tokens go: behind its query / its text
+    const float* cls = r.image_cls + (size_t)q_lo * Vh;
+    const float* pat = r.image_patches + (size_t)q_lo * np * Vh;
     // prefix MLP (per query): Linear -> Tanh -> Linear -> view [PL, D]
     RR_RUN(m, st, RR_K_TAIL, 0.0, 6.0 * nq * Vh, rr_launch_f32_to_bf16(cls, w.cls16, (size_t)nq * Vh, m->dt, st));
     RR_GEMM(m, st, w.cls16, Vh, m->w_vp0, m->b_vp0, nullptr, 0, w.vp_mid16, mid, nq, mid, Vh, EPI_BIAS_TANH_BF16, 2.0);
     RR_GEMM(m, st, w.vp_mid16, mid, m->w_vp2, m->b_vp2, nullptr, 0, w.vp_out32, outd, nq, outd, mid, EPI_BIAS_F32, 4.0);
     for (const Seg& g : segs)           // (packed: per pair, K = 1 -> pair p0 + i reads prefix p0 + i)
       RR_RUN(m, st, RR_K_TAIL, 0.0, 6.0 * g.n * PL * D,
-             rr_launch_li_normalize(w.vp_out32, nullptr, 0, g.n, PL, D, g.T, (packed && !joint) ? g.S : vis_off, pair_begin + (int)g.p0, K,
+             rr_launch_li_normalize(w.vp_out32, nullptr, 0, g.n, PL, D, g.T, vis_at(g), pair_begin + (int)g.p0, K,
                                     q_lo, w.li16 + g.rt0 * D, m->dt, 1, nullptr, 1 << 30, 0, st));
     // mapping network: input linear + self-attention block depend on the image only => per query
     RR_RUN(m, st, RR_K_TAIL, 0.0, 6.0 * nq * np * Vh, rr_launch_f32_to_bf16(pat, w.pat16, (size_t)nq * np * Vh, m->dt, st));
@@ -1793,7 +1879,7 @@ static int forward_full(rr_handle h, const int64_t* input_ids, const int64_t* at
     RR_RUN(m, st, RR_K_TAIL, 0.0, 6.0 * nq * np * Hd, rr_launch_f32_to_bf16(w.t32, w.t16, (size_t)nq * np * Hd, m->dt, st));
     int ca = S < c.cross_attn_len ? S : c.cross_attn_len;
     for (const Seg& g : segs) ca = g.S < ca ? g.S : ca;
-    if (packed && ca != (S < c.cross_attn_len ? S : c.cross_attn_len))
+    if (plan.packed && ca != (S < c.cross_attn_len ? S : c.cross_attn_len))
       return fail(m, RR_ERR_BAD_SHAPE, "packed segment shorter than the %d rows the mapping network's cross-attention reads", c.cross_attn_len);
     // pair-specific text states the cross-attention reads: first `ca` rows of every pair (rerank_model.py:438-442)
     for (const Seg& g : segs)
@@ -1842,7 +1928,7 @@ static int forward_full(rr_handle h, const int64_t* input_ids, const int64_t* at
     RR_GEMM(m, st, w.m16, Hd, m->w_mout, m->b_mout, nullptr, 0, w.mo32, D, n * np, D, Hd, EPI_BIAS_F32, 4.0);
     for (const Seg& g : segs)
       RR_RUN(m, st, RR_K_TAIL, 0.0, 6.0 * g.n * np * D,
-             rr_launch_li_normalize(w.mo32 + g.p0 * np * D, nullptr, 0, g.n, np, D, g.T, ((packed && !joint) ? g.S : vis_off) + PL, 0, 1, 0,
+             rr_launch_li_normalize(w.mo32 + g.p0 * np * D, nullptr, 0, g.n, np, D, g.T, vis_at(g) + PL, 0, 1, 0,
                                     w.li16 + g.rt0 * D, m->dt, 1, nullptr, 1 << 30, 0, st));
   }
   m->tap_li = w.li16;
@@ -1850,150 +1936,67 @@ static int forward_full(rr_handle h, const int64_t* input_ids, const int64_t* at
 
   const float* adj = nullptr;
   int adj_ld = 0;
-  if (preflmr_scores) {   // rerank_model.py:276-319: scores [N, S, q_len + P] -> additive bias [n, T, ld]
+  if (r.fusion_scores) {   // rerank_model.py:276-319: scores [N, S, q_len + P] (packed: the context rows) -> additive bias
     if (!joint) return fail(m, RR_ERR_BAD_ARG, "attention fusion belongs to the joint (RerankModel) forward");
-    if (packed) {         // scores [n, S - q_len, q_len + P] (the context rows only); the bias segment after segment
-      RR_TRY(fusion_bias_packed(m, st, segs, preflmr_scores, S - q_len, q_len + P, q_len, fusion_multiplier));
-    } else {
-      adj_ld = (T + 63) / 64 * 64;
-      const size_t need_adj = (size_t)n * T * adj_ld * sizeof(float);
-      RR_TRY(ensure_adj(m, need_adj, st));
-      RR_RUN(m, st, RR_K_TAIL, 0.0, 4.0 * n * (double)S * (q_len + P) + (double)need_adj,
-             rr_launch_fusion_adj(preflmr_scores, S, q_len + P, S - q_len, fusion_multiplier, pair_begin, n, m->adj, adj_ld, st));
-    }
+    RR_TRY(fusion_bias(m, st, plan, r.fusion_scores, q_len + P, S - q_len, q_len, 2, r.fusion_mult, pair_begin, &adj_ld));
     adj = m->adj;
   }
-  RR_TRY(run_cross_encoder(m, st, w, segs, adj, adj_ld, vis_pos0, (packed && joint) ? T : 0));
-  RR_TRY(run_heads(m, st, w, segs, Bq, K, pair_begin, full, joint ? logits_out : labels, logits_out, logits2_out,
-                   loss_out, scores_out, order_out, joint != 0));
+  RR_TRY(run_cross_encoder(m, st, w, plan, adj, adj_ld));
+  RR_TRY(run_heads(m, st, w, segs, r));
   return range_guard_exit(m, st);
-}
-
-static int rr_forward_impl(rr_handle h, const int64_t* input_ids, const int64_t* attention_mask, const int64_t* token_type_ids,
-               const float* image_cls, const float* image_patches, int Bq, int K, int S, const float* labels,
-               int pair_begin, int pair_end, float* logits_out, float* logits2_out, float* loss_out,
-               float* scores_out, int32_t* order_out, void* hip_stream) {
-  return forward_full(h, input_ids, attention_mask, token_type_ids, image_cls, image_patches, Bq, K, S, labels,
-                      pair_begin, pair_end, logits_out, logits2_out, loss_out, scores_out, order_out, hip_stream, 0, 0,
-                      -1);
-}
-
-// Packed (variable-length) FullContextRerankModel forward: see include/rerank_mi355.h.
-static int rr_forward_packed_impl(rr_handle h, const int64_t* input_ids, const int64_t* attention_mask, const int64_t* token_type_ids,
-                                  const float* image_cls, const float* image_patches, int n_segments, const int32_t* seg_pairs,
-                                  const int32_t* seg_len, int padded_seq_len, float* logits_out, float* logits2_out,
-                                  void* hip_stream) {
-  if (!h) return RR_ERR_BAD_ARG;
-  rr_model* m = h;
-  if (!seg_pairs || !seg_len) return fail(m, RR_ERR_BAD_ARG, "rr_forward_packed: null segment tables");
-  if (n_segments <= 0 || n_segments > 64) return fail(m, RR_ERR_BAD_SHAPE, "rr_forward_packed: %d segments (1..64)", n_segments);
-  std::vector<std::pair<int, int>> segs;
-  long long pairs = 0, rows = 0;
-  const int P = (image_cls || image_patches) ? m->cfg.prefix_len + m->cfg.n_patches : 0;
-  for (int i = 0; i < n_segments; ++i) {
-    if (seg_pairs[i] <= 0 || seg_len[i] <= 0 || seg_len[i] > padded_seq_len)
-      return fail(m, RR_ERR_BAD_SHAPE, "rr_forward_packed: segment %d holds %d pairs of %d rows (padded length %d)", i, seg_pairs[i],
-                  seg_len[i], padded_seq_len);
-    segs.emplace_back(seg_pairs[i], seg_len[i]);
-    pairs += seg_pairs[i];
-    rows += (long long)seg_pairs[i] * (seg_len[i] + P);
-  }
-  if (pairs > (1 << 24) || rows > (1LL << 30)) return fail(m, RR_ERR_BAD_SHAPE, "rr_forward_packed: %lld pairs / %lld rows", pairs, rows);
-  const int n = (int)pairs;
-  return forward_full(h, input_ids, attention_mask, token_type_ids, image_cls, image_patches, n, 1, padded_seq_len, nullptr, 0, n,
-                      logits_out, logits2_out, nullptr, nullptr, nullptr, hip_stream, 0, 0, -1, nullptr, 1.0f, &segs);
-}
-
-static int rr_forward_joint_impl(rr_handle h, const int64_t* joint_input_ids, const int64_t* joint_attention_mask,
-                     const float* image_cls, const float* image_patches, int Bq, int K, int S, int query_len,
-                     int64_t instruction_token_id, int pair_begin, int pair_end, float* logits_out,
-                     float* logits2_out, float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream) {
-  return forward_full(h, joint_input_ids, joint_attention_mask, nullptr, image_cls, image_patches, Bq, K, S, nullptr,
-                      pair_begin, pair_end, logits_out, logits2_out, loss_out, scores_out, order_out, hip_stream, 1,
-                      query_len, (long long)instruction_token_id);
-}
-
-static int rr_forward_joint_fusion_impl(rr_handle h, const int64_t* joint_input_ids, const int64_t* joint_attention_mask,
-                            const float* image_cls, const float* image_patches, const float* preflmr_scores,
-                            float fusion_multiplier, int Bq, int K, int S, int query_len, int64_t instruction_token_id,
-                            int pair_begin, int pair_end, float* logits_out, float* logits2_out, float* loss_out,
-                            float* scores_out, int32_t* order_out, void* hip_stream) {
-  if (h && !preflmr_scores) return fail(h, RR_ERR_BAD_ARG, "rr_forward_joint_fusion: preflmr_scores is null (use rr_forward_joint)");
-  return forward_full(h, joint_input_ids, joint_attention_mask, nullptr, image_cls, image_patches, Bq, K, S, nullptr,
-                      pair_begin, pair_end, logits_out, logits2_out, loss_out, scores_out, order_out, hip_stream, 1,
-                      query_len, (long long)instruction_token_id, preflmr_scores, fusion_multiplier);
 }
 
 /* InteractionRerankModel.forward (interaction_rerank_model.py:110-166) from the retriever's late-interaction
  * tensors.  NORMAL: cat(query, context) -> Linear -> CrossEncoder; MORES (mores_model.py:21-94): Lc layers of
  * cross-attention(query -> doc) -> self-attention -> FFN over the query tokens. */
-static int forward_interaction(rr_handle h, const float* query_li, const float* context_li, const float* query_mask,
-                               const float* context_mask, int Bq, int K, int Lq, int Lc, const float* labels,
-                               int pair_begin, int pair_end, float* logits_out, float* logits2_out, float* loss_out,
-                               float* scores_out, int32_t* order_out, void* hip_stream, const float* preflmr_scores,
-                               float fusion_multiplier, const std::vector<std::pair<int, int>>* packed = nullptr) {
-  // `packed` (rr_forward_interaction_packed): segments (pairs, context tokens per pair); context_li / context_mask then hold the
-  // segments' pairs back to back at THEIR context length, query_li / query_mask one entry per pair, Bq = pairs, K = 1, Lc = the
-  // padded context length
+static int forward_interaction(rr_handle h, Request r) {
+  // packed: context_li / context_mask hold the segments' pairs back to back at THEIR context length, query_li / query_mask one
+  // entry per pair, r.len = the padded context length
   if (!h) return RR_ERR_BAD_ARG;
   rr_model* m = h;
   const rr_config& c = m->cfg;
+  const int Lq = r.q_len;
+  std::vector<std::pair<int, int>> table;
+  if (r.packed) RR_TRY(packed_segments(m, "rr_forward_interaction_packed", r, 0, Lq < 0 ? 0 : Lq, &table));
   if (c.model_kind == RR_MODEL_FULL_CONTEXT) return fail(m, RR_ERR_BAD_ARG, "rr_forward_interaction on a full-context model");
   if (!m->finalized) return fail(m, RR_ERR_BAD_ARG, "rr_forward_interaction before rr_finalize_weights");
   RR_TRY(range_guard_enter(m));
-  if (!query_li || !context_li || !query_mask || !context_mask || !logits_out)
+  if (!r.query_li || !r.context_li || !r.query_mask || !r.context_mask || !r.logits)
     return fail(m, RR_ERR_BAD_ARG, "rr_forward_interaction: null tensor");
+  const int Bq = r.Bq, K = r.K, Lc = r.len, pair_begin = r.pair_begin;
   if (Bq <= 0 || K <= 0 || Lq <= 0 || Lc <= 0) return fail(m, RR_ERR_BAD_SHAPE, "Bq=%d K=%d Lq=%d Lc=%d", Bq, K, Lq, Lc);
-  const int N = Bq * K, T = Lq + Lc;
-  if (pair_begin < 0 || pair_end > N || pair_begin >= pair_end)
-    return fail(m, RR_ERR_BAD_SHAPE, "pair slice [%d,%d) outside [0,%d)", pair_begin, pair_end, N);
+  const int T = Lq + Lc;
+  RR_TRY(check_head(m, "rr_forward_interaction", Bq, K, pair_begin, r.pair_end, r.labels, r.logits2, r.loss, r.scores, r.order,
+                    false));
   if (c.model_kind == RR_MODEL_INTERACTION && T > c.ce_max_pos)
     return fail(m, RR_ERR_BAD_SHAPE, "sequence %d exceeds cross_encoder_max_position_embeddings %d", T, c.ce_max_pos);
-  const bool full = pair_begin == 0 && pair_end == N;
-  if (c.loss_kind == RR_LOSS_NEGATIVE_SAMPLING && labels)
-    return fail(m, RR_ERR_BAD_ARG, "Labels should not be provided for negative sampling loss function");
-  if (!full && (loss_out || scores_out || order_out))
-    return fail(m, RR_ERR_BAD_ARG, "loss/scores/order need the full pair range; use rr_head after gathering logits");
-  if (c.loss_kind == RR_LOSS_2H_BCE && full && (loss_out || scores_out) && !logits2_out)
-    return fail(m, RR_ERR_BAD_ARG, "2H_BCE head needs logits2_out");
-  if (K > 4096 && (loss_out || scores_out || order_out)) return fail(m, RR_ERR_UNSUPPORTED, "K=%d > 4096", K);
 
-  hipStream_t st = (hipStream_t)hip_stream;
+  hipStream_t st = r.stream;
   RR_HIP(m, hipSetDevice(c.device));
-  const int n = pair_end - pair_begin, q_lo = pair_begin / K, nq = (pair_end - 1) / K - q_lo + 1;
+  const int n = r.pair_end - pair_begin;
   Work w{};
   const size_t need = layout_interaction(c, n, Bq, Lq, Lc, nullptr, &w);
   RR_TRY(ensure_ws(m, need, st));
   layout_interaction(c, n, Bq, Lq, Lc, m->ws, &w);
   m->last_stream = st;
   const int D = c.li_dim, Hc = c.ce_hidden, Ic = c.ce_intermediate;
-  const float* cli = context_li + (size_t)pair_begin * Lc * D;
-  const float* cm = context_mask + (size_t)pair_begin * Lc;
-  // segments: one (n pairs of Lc context tokens) for the plain forward.  Seg.S = context tokens per pair, Seg.r0 = first
-  // context row, Seg.rt0 = first row of the concatenated [query | context] sequence.
-  std::vector<Seg> segs;
-  if (packed) {
-    size_t p0 = 0, c0 = 0, rt0 = 0;
-    for (const auto& g : *packed) {
-      segs.push_back(Seg{g.first, g.second, Lq + g.second, p0, c0, rt0});
-      p0 += (size_t)g.first;
-      c0 += (size_t)g.first * g.second;
-      rt0 += (size_t)g.first * (Lq + g.second);
-    }
-  } else {
-    segs.push_back(Seg{n, Lc, T, 0, 0, 0});
-  }
+  const float* cli = r.context_li + (size_t)pair_begin * Lc * D;
+  const float* cm = r.context_mask + (size_t)pair_begin * Lc;
+  // segments: Seg.S = context tokens per pair, Seg.r0 = first context row, Seg.rt0 = first row of the concatenated
+  // [query | context] sequence
+  const RowPlan plan = plan_rows(FAM_INTERACTION, n, Lc, Lq, table, 0);
+  const std::vector<Seg>& segs = plan.segs;
   const Seg& last = segs.back();
   const int C = (int)(last.r0 + (size_t)last.n * last.S), RT = (int)(last.rt0 + (size_t)last.n * last.T);
 
   for (const Seg& g : segs)
     RR_RUN(m, st, RR_K_EMBED, 0.0, 8.0 * g.n * g.T,
-           rr_launch_interaction_bias(query_mask, cm + g.r0, g.n, Lq, g.S, pair_begin + (int)g.p0, K, w.ce_bias + g.rt0,
+           rr_launch_interaction_bias(r.query_mask, cm + g.r0, g.n, Lq, g.S, pair_begin + (int)g.p0, K, w.ce_bias + g.rt0,
                                       w.text_bias + g.p0 * Lq, w.li32 + g.r0, st));
   // operands in 16 bits, query rows broadcast to the K pairs of the query (repeat_interleave, :128-129)
   for (const Seg& g : segs) {
     RR_RUN(m, st, RR_K_TAIL, 0.0, 6.0 * g.n * Lq * D,
-           rr_launch_li_normalize(query_li, nullptr, 0, g.n, Lq, D, g.T, 0, pair_begin + (int)g.p0, K, 0, w.li16 + g.rt0 * D, m->dt, 0,
+           rr_launch_li_normalize(r.query_li, nullptr, 0, g.n, Lq, D, g.T, 0, pair_begin + (int)g.p0, K, 0, w.li16 + g.rt0 * D, m->dt, 0,
                                   nullptr, 1 << 30, 0, st));
     RR_RUN(m, st, RR_K_TAIL, 0.0, 6.0 * g.n * g.S * D,
            rr_launch_li_normalize(cli + g.r0 * D, nullptr, 0, g.n, g.S, D, g.T, Lq, 0, 1, 0, w.li16 + g.rt0 * D, m->dt, 0, nullptr,
@@ -2005,23 +2008,17 @@ static int forward_interaction(rr_handle h, const float* query_li, const float* 
   if (c.model_kind == RR_MODEL_INTERACTION) {
     const float* adj = nullptr;
     int adj_ld = 0;
-    if (preflmr_scores && packed) {   // scores stay [n, Lc, Lq] (padded context axis: the normalisers); bias per segment
-      RR_TRY(fusion_bias_packed(m, st, segs, preflmr_scores, Lc, Lq, 0, fusion_multiplier));
-      adj = m->adj;
-    } else if (preflmr_scores) {   // interaction_rerank_model.py:131-142: scores [N, Lc, Lq] over the tokens [query | context]
-      adj_ld = (T + 63) / 64 * 64;
-      const size_t need_adj = (size_t)n * T * adj_ld * sizeof(float);
-      RR_TRY(ensure_adj(m, need_adj, st));
-      RR_RUN(m, st, RR_K_TAIL, 0.0, 4.0 * n * (double)Lc * Lq + (double)need_adj,
-             rr_launch_fusion_adj(preflmr_scores, Lc, Lq, Lc, fusion_multiplier, pair_begin, n, m->adj, adj_ld, st, 0));
+    // interaction_rerank_model.py:131-142: scores [N, Lc, Lq] over the tokens [query | context] (packed: the context axis stays
+    // padded, the reference's normalisers run over it)
+    if (r.fusion_scores) {
+      RR_TRY(fusion_bias(m, st, plan, r.fusion_scores, Lq, Lc, 0, 0, r.fusion_mult, pair_begin, &adj_ld));
       adj = m->adj;
     }
-    RR_TRY(run_cross_encoder(m, st, w, segs, adj, adj_ld, -1, packed ? T : 0));
-    RR_TRY(run_heads(m, st, w, segs, Bq, K, pair_begin, full, labels, logits_out, logits2_out, loss_out, scores_out,
-                     order_out));
+    RR_TRY(run_cross_encoder(m, st, w, plan, adj, adj_ld));
+    RR_TRY(run_heads(m, st, w, segs, r));
     return range_guard_exit(m, st);
   }
-  if (preflmr_scores) return fail(m, RR_ERR_UNSUPPORTED, "Attention adj is not implemented for MORES");   // mores_model.py:72-73
+  if (r.fusion_scores) return fail(m, RR_ERR_UNSUPPORTED, "Attention adj is not implemented for MORES");   // mores_model.py:72-73
 
   // ---- MORES: hidden = Linear(query) [n*Lq, Hc] (no embeddings, no LayerNorm), doc = Linear(context) [n*Lc, Hc]
   // gather the two token groups out of the concatenated 16-bit buffer into contiguous GEMM operands
@@ -2037,8 +2034,7 @@ static int forward_interaction(rr_handle h, const float* query_li, const float* 
                                  st));
   RR_GEMM(m, st, w.ctx, D, m->w_cemap, m->b_cemap, nullptr, 0, w.enc16, Hc, C, Hc, D, EPI_BIAS_BF16, 2.0);
   // cross-attention per segment (Tk = its context length) under the padded call's schedule (its grid: n pairs x Lq rows)
-  const long x_sched = packed ? (((long)n * c.ce_heads + 7) / 8) * 8 * ((Lq + 127) / 128) : 0;
-  (void)nq;
+  const long x_sched = plan.packed ? (((long)n * c.ce_heads + 7) / 8) * 8 * ((Lq + 127) / 128) : 0;
   for (int l = 0; l < c.ce_layers; ++l) {
     const LayerW& L = m->ce_layers[l];
     const int rq = n * Lq;
@@ -2070,109 +2066,8 @@ static int forward_interaction(rr_handle h, const float* query_li, const float* 
   m->tap_ce = w.h32;
   m->tap_ce_elems = (size_t)n * Lq * Hc;
   const std::vector<Seg> one{Seg{n, Lq, Lq, 0, 0, 0}};
-  RR_TRY(run_heads(m, st, w, one, Bq, K, pair_begin, full, labels, logits_out, logits2_out, loss_out, scores_out,
-                   order_out));
+  RR_TRY(run_heads(m, st, w, one, r));
   return range_guard_exit(m, st);
-}
-
-// Packed segment tables of rr_forward_joint_packed / rr_forward_interaction_packed (include/rerank_mi355.h): 1..64 non-empty
-// segments of lengths in (min_len, padded_len]
-static int packed_segments(rr_model* m, const char* what, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len,
-                           int padded_len, int min_len, int extra_rows, std::vector<std::pair<int, int>>* out) {
-  if (!seg_pairs || !seg_len) return fail(m, RR_ERR_BAD_ARG, "%s: null segment tables", what);
-  if (n_segments <= 0 || n_segments > 64) return fail(m, RR_ERR_BAD_SHAPE, "%s: %d segments (1..64)", what, n_segments);
-  long long pairs = 0, rows = 0;
-  for (int i = 0; i < n_segments; ++i) {
-    if (seg_pairs[i] <= 0 || seg_len[i] <= min_len || seg_len[i] > padded_len)
-      return fail(m, RR_ERR_BAD_SHAPE, "%s: segment %d holds %d pairs of length %d (lengths in (%d, %d])", what, i, seg_pairs[i],
-                  seg_len[i], min_len, padded_len);
-    out->emplace_back(seg_pairs[i], seg_len[i]);
-    pairs += seg_pairs[i];
-    rows += (long long)seg_pairs[i] * (seg_len[i] + extra_rows);
-  }
-  if (pairs > (1 << 24) || rows > (1LL << 30)) return fail(m, RR_ERR_BAD_SHAPE, "%s: %lld pairs / %lld rows", what, pairs, rows);
-  return RR_OK;
-}
-
-// Packed RerankModel forward: see include/rerank_mi355.h.
-static int rr_forward_joint_packed_impl(rr_handle h, const int64_t* joint_input_ids, const int64_t* joint_attention_mask,
-                                        const float* image_cls, const float* image_patches, const float* preflmr_scores,
-                                        float fusion_multiplier, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len,
-                                        int padded_seq_len, int query_len, int64_t instruction_token_id, float* logits_out,
-                                        float* logits2_out, void* hip_stream) {
-  if (!h) return RR_ERR_BAD_ARG;
-  rr_model* m = h;
-  std::vector<std::pair<int, int>> segs;
-  const int P = m->cfg.prefix_len + m->cfg.n_patches;
-  RR_TRY(packed_segments(m, "rr_forward_joint_packed", n_segments, seg_pairs, seg_len, padded_seq_len, query_len < 0 ? 0 : query_len,
-                         P, &segs));
-  int n = 0;
-  for (const auto& g : segs) n += g.first;
-  return forward_full(h, joint_input_ids, joint_attention_mask, nullptr, image_cls, image_patches, n, 1, padded_seq_len, nullptr, 0,
-                      n, logits_out, logits2_out, nullptr, nullptr, nullptr, hip_stream, 1, query_len, (long long)instruction_token_id,
-                      preflmr_scores, fusion_multiplier, &segs);
-}
-
-// Packed InteractionRerankModel forward (NORMAL and MORES): see include/rerank_mi355.h.
-static int rr_forward_interaction_packed_impl(rr_handle h, const float* query_li, const float* context_li, const float* query_mask,
-                                              const float* context_mask, const float* preflmr_scores, float fusion_multiplier,
-                                              int n_segments, const int32_t* seg_pairs, const int32_t* seg_len,
-                                              int padded_context_len, int Lq, float* logits_out, float* logits2_out,
-                                              void* hip_stream) {
-  if (!h) return RR_ERR_BAD_ARG;
-  rr_model* m = h;
-  std::vector<std::pair<int, int>> segs;
-  RR_TRY(packed_segments(m, "rr_forward_interaction_packed", n_segments, seg_pairs, seg_len, padded_context_len, 0, Lq < 0 ? 0 : Lq,
-                         &segs));
-  int n = 0;
-  for (const auto& g : segs) n += g.first;
-  return forward_interaction(h, query_li, context_li, query_mask, context_mask, n, 1, Lq, padded_context_len, nullptr, 0, n,
-                             logits_out, logits2_out, nullptr, nullptr, nullptr, hip_stream, preflmr_scores, fusion_multiplier,
-                             &segs);
-}
-
-// rr_head with RerankModel.forward's loss: loss_fn(logits, logits) (rerank_model.py:328), as rr_forward_joint runs it
-static int rr_head_joint_impl(rr_handle h, const float* logits, const float* logits2, int Bq, int K, float* loss_out,
-                              float* scores_out, int32_t* order_out, void* hip_stream) {
-  if (!h || !logits) return fail(h, RR_ERR_BAD_ARG, "rr_head_joint: null argument");
-  if (Bq <= 0 || K <= 0) return fail(h, RR_ERR_BAD_SHAPE, "rr_head_joint: Bq=%d K=%d", Bq, K);
-  if (K > 4096) return fail(h, RR_ERR_UNSUPPORTED, "rr_head_joint: K=%d > 4096", K);
-  const rr_config& c = h->cfg;
-  if (c.model_kind != RR_MODEL_FULL_CONTEXT) return fail(h, RR_ERR_BAD_ARG, "rr_head_joint on an interaction model");
-  if (c.loss_kind == RR_LOSS_2H_BCE && !logits2) return fail(h, RR_ERR_BAD_ARG, "rr_head_joint: 2H_BCE needs logits2 (first head)");
-  if (c.loss_kind == RR_LOSS_NEGATIVE_SAMPLING && loss_out)
-    return fail(h, RR_ERR_UNSUPPORTED, "RerankModel with negative_sampling loss is not covered (no reference config)");
-  hipStream_t st = (hipStream_t)hip_stream;
-  RR_HIP(h, hipSetDevice(c.device));
-  Work w;
-  const size_t need = layout(c, 1, Bq, 8, false, nullptr, &w);
-  RR_TRY(ensure_ws(h, need, st));
-  layout(c, 1, Bq, 8, false, h->ws, &w);
-  const int has_pw = !std::isnan(c.pos_weight);
-  const bool two = c.loss_kind == RR_LOSS_2H_BCE;
-  RR_RUN(h, st, RR_K_HEAD, 0.0, 12.0 * Bq * K,
-         rr_launch_head(logits, two ? logits2 : nullptr, logits, Bq, K, two ? 3 : c.loss_kind, has_pw ? c.pos_weight : 1.0f, has_pw,
-                        scores_out, order_out, loss_out, w.part_l, w.part_w, st));
-  return RR_OK;
-}
-
-static int rr_forward_interaction_impl(rr_handle h, const float* query_li, const float* context_li, const float* query_mask,
-                           const float* context_mask, int Bq, int K, int Lq, int Lc, const float* labels,
-                           int pair_begin, int pair_end, float* logits_out, float* logits2_out, float* loss_out,
-                           float* scores_out, int32_t* order_out, void* hip_stream) {
-  return forward_interaction(h, query_li, context_li, query_mask, context_mask, Bq, K, Lq, Lc, labels, pair_begin, pair_end,
-                             logits_out, logits2_out, loss_out, scores_out, order_out, hip_stream, nullptr, 1.0f);
-}
-
-static int rr_forward_interaction_fusion_impl(rr_handle h, const float* query_li, const float* context_li, const float* query_mask,
-                                  const float* context_mask, const float* preflmr_scores, float fusion_multiplier, int Bq,
-                                  int K, int Lq, int Lc, const float* labels, int pair_begin, int pair_end,
-                                  float* logits_out, float* logits2_out, float* loss_out, float* scores_out,
-                                  int32_t* order_out, void* hip_stream) {
-  if (h && !preflmr_scores) return fail(h, RR_ERR_BAD_ARG, "rr_forward_interaction_fusion: preflmr_scores is null");
-  return forward_interaction(h, query_li, context_li, query_mask, context_mask, Bq, K, Lq, Lc, labels, pair_begin, pair_end,
-                             logits_out, logits2_out, loss_out, scores_out, order_out, hip_stream, preflmr_scores,
-                             fusion_multiplier);
 }
 
 static int64_t rr_debug_read_impl(rr_handle h, const char* name, float* host_out, int64_t max_elems) {
@@ -2483,35 +2378,91 @@ int rr_finalize_weights(rr_handle h) {
 int rr_encode_image(rr_handle h, const float* pixel_values, int B, float* image_cls_out, float* image_patches_out, void* hip_stream) {
   return guarded(h, [&]() -> int { return rr_encode_image_impl(h, pixel_values, B, image_cls_out, image_patches_out, hip_stream); });
 }
+// the forwards: the arguments into one Request (forward_full / forward_interaction)
 int rr_head(rr_handle h, const float* logits, const float* logits2, const float* labels, int Bq, int K, float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream) {
-  return guarded(h, [&]() -> int { return rr_head_impl(h, logits, logits2, labels, Bq, K, loss_out, scores_out, order_out, hip_stream); });
-}
-int rr_forward(rr_handle h, const int64_t* input_ids, const int64_t* attention_mask, const int64_t* token_type_ids, const float* image_cls, const float* image_patches, int Bq, int K, int S, const float* labels, int pair_begin, int pair_end, float* logits_out, float* logits2_out, float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream) {
-  return guarded(h, [&]() -> int { return rr_forward_impl(h, input_ids, attention_mask, token_type_ids, image_cls, image_patches, Bq, K, S, labels, pair_begin, pair_end, logits_out, logits2_out, loss_out, scores_out, order_out, hip_stream); });
-}
-int rr_forward_packed(rr_handle h, const int64_t* input_ids, const int64_t* attention_mask, const int64_t* token_type_ids, const float* image_cls, const float* image_patches, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int padded_seq_len, float* logits_out, float* logits2_out, void* hip_stream) {
-  return guarded(h, [&]() -> int { return rr_forward_packed_impl(h, input_ids, attention_mask, token_type_ids, image_cls, image_patches, n_segments, seg_pairs, seg_len, padded_seq_len, logits_out, logits2_out, hip_stream); });
-}
-int rr_forward_joint_packed(rr_handle h, const int64_t* joint_input_ids, const int64_t* joint_attention_mask, const float* image_cls, const float* image_patches, const float* preflmr_scores, float fusion_multiplier, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int padded_seq_len, int query_len, int64_t instruction_token_id, float* logits_out, float* logits2_out, void* hip_stream) {
-  return guarded(h, [&]() -> int { return rr_forward_joint_packed_impl(h, joint_input_ids, joint_attention_mask, image_cls, image_patches, preflmr_scores, fusion_multiplier, n_segments, seg_pairs, seg_len, padded_seq_len, query_len, instruction_token_id, logits_out, logits2_out, hip_stream); });
-}
-int rr_forward_interaction_packed(rr_handle h, const float* query_li, const float* context_li, const float* query_mask, const float* context_mask, const float* preflmr_scores, float fusion_multiplier, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int padded_context_len, int Lq, float* logits_out, float* logits2_out, void* hip_stream) {
-  return guarded(h, [&]() -> int { return rr_forward_interaction_packed_impl(h, query_li, context_li, query_mask, context_mask, preflmr_scores, fusion_multiplier, n_segments, seg_pairs, seg_len, padded_context_len, Lq, logits_out, logits2_out, hip_stream); });
+  return guarded(h, [&]() -> int { return head_call(h, "rr_head", false, logits, logits2, labels, Bq, K, loss_out, scores_out, order_out, hip_stream); });
 }
 int rr_head_joint(rr_handle h, const float* logits, const float* logits2, int Bq, int K, float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream) {
-  return guarded(h, [&]() -> int { return rr_head_joint_impl(h, logits, logits2, Bq, K, loss_out, scores_out, order_out, hip_stream); });
+  return guarded(h, [&]() -> int { return head_call(h, "rr_head_joint", true, logits, logits2, nullptr, Bq, K, loss_out, scores_out, order_out, hip_stream); });
+}
+int rr_forward(rr_handle h, const int64_t* input_ids, const int64_t* attention_mask, const int64_t* token_type_ids, const float* image_cls, const float* image_patches, int Bq, int K, int S, const float* labels, int pair_begin, int pair_end, float* logits_out, float* logits2_out, float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream) {
+  return guarded(h, [&]() -> int {
+    Request r;
+    r.ids = input_ids; r.mask = attention_mask; r.token_types = token_type_ids; r.image_cls = image_cls; r.image_patches = image_patches;
+    r.Bq = Bq; r.K = K; r.len = S; r.labels = labels; r.pair_begin = pair_begin; r.pair_end = pair_end;
+    r.logits = logits_out; r.logits2 = logits2_out; r.loss = loss_out; r.scores = scores_out; r.order = order_out; r.stream = (hipStream_t)hip_stream;
+    return forward_full(h, r);
+  });
+}
+int rr_forward_packed(rr_handle h, const int64_t* input_ids, const int64_t* attention_mask, const int64_t* token_type_ids, const float* image_cls, const float* image_patches, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int padded_seq_len, float* logits_out, float* logits2_out, void* hip_stream) {
+  return guarded(h, [&]() -> int {
+    Request r;
+    r.ids = input_ids; r.mask = attention_mask; r.token_types = token_type_ids; r.image_cls = image_cls; r.image_patches = image_patches;
+    r.packed = true; r.n_segments = n_segments; r.seg_pairs = seg_pairs; r.seg_len = seg_len; r.len = padded_seq_len;
+    r.logits = logits_out; r.logits2 = logits2_out; r.stream = (hipStream_t)hip_stream;
+    return forward_full(h, r);
+  });
 }
 int rr_forward_joint(rr_handle h, const int64_t* joint_input_ids, const int64_t* joint_attention_mask, const float* image_cls, const float* image_patches, int Bq, int K, int S, int query_len, int64_t instruction_token_id, int pair_begin, int pair_end, float* logits_out, float* logits2_out, float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream) {
-  return guarded(h, [&]() -> int { return rr_forward_joint_impl(h, joint_input_ids, joint_attention_mask, image_cls, image_patches, Bq, K, S, query_len, instruction_token_id, pair_begin, pair_end, logits_out, logits2_out, loss_out, scores_out, order_out, hip_stream); });
+  return guarded(h, [&]() -> int {
+    Request r;
+    r.family = FAM_JOINT; r.ids = joint_input_ids; r.mask = joint_attention_mask; r.image_cls = image_cls; r.image_patches = image_patches;
+    r.Bq = Bq; r.K = K; r.len = S; r.q_len = query_len; r.instruction_token = instruction_token_id; r.pair_begin = pair_begin; r.pair_end = pair_end;
+    r.logits = logits_out; r.logits2 = logits2_out; r.loss = loss_out; r.scores = scores_out; r.order = order_out; r.stream = (hipStream_t)hip_stream;
+    return forward_full(h, r);
+  });
 }
 int rr_forward_joint_fusion(rr_handle h, const int64_t* joint_input_ids, const int64_t* joint_attention_mask, const float* image_cls, const float* image_patches, const float* preflmr_scores, float fusion_multiplier, int Bq, int K, int S, int query_len, int64_t instruction_token_id, int pair_begin, int pair_end, float* logits_out, float* logits2_out, float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream) {
-  return guarded(h, [&]() -> int { return rr_forward_joint_fusion_impl(h, joint_input_ids, joint_attention_mask, image_cls, image_patches, preflmr_scores, fusion_multiplier, Bq, K, S, query_len, instruction_token_id, pair_begin, pair_end, logits_out, logits2_out, loss_out, scores_out, order_out, hip_stream); });
+  return guarded(h, [&]() -> int {
+    if (h && !preflmr_scores) return fail(h, RR_ERR_BAD_ARG, "rr_forward_joint_fusion: preflmr_scores is null (use rr_forward_joint)");
+    Request r;
+    r.family = FAM_JOINT; r.ids = joint_input_ids; r.mask = joint_attention_mask; r.image_cls = image_cls; r.image_patches = image_patches;
+    r.fusion_scores = preflmr_scores; r.fusion_mult = fusion_multiplier;
+    r.Bq = Bq; r.K = K; r.len = S; r.q_len = query_len; r.instruction_token = instruction_token_id; r.pair_begin = pair_begin; r.pair_end = pair_end;
+    r.logits = logits_out; r.logits2 = logits2_out; r.loss = loss_out; r.scores = scores_out; r.order = order_out; r.stream = (hipStream_t)hip_stream;
+    return forward_full(h, r);
+  });
+}
+int rr_forward_joint_packed(rr_handle h, const int64_t* joint_input_ids, const int64_t* joint_attention_mask, const float* image_cls, const float* image_patches, const float* preflmr_scores, float fusion_multiplier, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int padded_seq_len, int query_len, int64_t instruction_token_id, float* logits_out, float* logits2_out, void* hip_stream) {
+  return guarded(h, [&]() -> int {
+    Request r;
+    r.family = FAM_JOINT; r.ids = joint_input_ids; r.mask = joint_attention_mask; r.image_cls = image_cls; r.image_patches = image_patches;
+    r.fusion_scores = preflmr_scores; r.fusion_mult = fusion_multiplier;
+    r.packed = true; r.n_segments = n_segments; r.seg_pairs = seg_pairs; r.seg_len = seg_len; r.len = padded_seq_len;
+    r.q_len = query_len; r.instruction_token = instruction_token_id;
+    r.logits = logits_out; r.logits2 = logits2_out; r.stream = (hipStream_t)hip_stream;
+    return forward_full(h, r);
+  });
 }
 int rr_forward_interaction(rr_handle h, const float* query_li, const float* context_li, const float* query_mask, const float* context_mask, int Bq, int K, int Lq, int Lc, const float* labels, int pair_begin, int pair_end, float* logits_out, float* logits2_out, float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream) {
-  return guarded(h, [&]() -> int { return rr_forward_interaction_impl(h, query_li, context_li, query_mask, context_mask, Bq, K, Lq, Lc, labels, pair_begin, pair_end, logits_out, logits2_out, loss_out, scores_out, order_out, hip_stream); });
+  return guarded(h, [&]() -> int {
+    Request r;
+    r.family = FAM_INTERACTION; r.query_li = query_li; r.context_li = context_li; r.query_mask = query_mask; r.context_mask = context_mask;
+    r.Bq = Bq; r.K = K; r.q_len = Lq; r.len = Lc; r.labels = labels; r.pair_begin = pair_begin; r.pair_end = pair_end;
+    r.logits = logits_out; r.logits2 = logits2_out; r.loss = loss_out; r.scores = scores_out; r.order = order_out; r.stream = (hipStream_t)hip_stream;
+    return forward_interaction(h, r);
+  });
 }
 int rr_forward_interaction_fusion(rr_handle h, const float* query_li, const float* context_li, const float* query_mask, const float* context_mask, const float* preflmr_scores, float fusion_multiplier, int Bq, int K, int Lq, int Lc, const float* labels, int pair_begin, int pair_end, float* logits_out, float* logits2_out, float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream) {
-  return guarded(h, [&]() -> int { return rr_forward_interaction_fusion_impl(h, query_li, context_li, query_mask, context_mask, preflmr_scores, fusion_multiplier, Bq, K, Lq, Lc, labels, pair_begin, pair_end, logits_out, logits2_out, loss_out, scores_out, order_out, hip_stream); });
+  return guarded(h, [&]() -> int {
+    if (h && !preflmr_scores) return fail(h, RR_ERR_BAD_ARG, "rr_forward_interaction_fusion: preflmr_scores is null");
+    Request r;
+    r.family = FAM_INTERACTION; r.query_li = query_li; r.context_li = context_li; r.query_mask = query_mask; r.context_mask = context_mask;
+    r.fusion_scores = preflmr_scores; r.fusion_mult = fusion_multiplier;
+    r.Bq = Bq; r.K = K; r.q_len = Lq; r.len = Lc; r.labels = labels; r.pair_begin = pair_begin; r.pair_end = pair_end;
+    r.logits = logits_out; r.logits2 = logits2_out; r.loss = loss_out; r.scores = scores_out; r.order = order_out; r.stream = (hipStream_t)hip_stream;
+    return forward_interaction(h, r);
+  });
+}
+int rr_forward_interaction_packed(rr_handle h, const float* query_li, const float* context_li, const float* query_mask, const float* context_mask, const float* preflmr_scores, float fusion_multiplier, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int padded_context_len, int Lq, float* logits_out, float* logits2_out, void* hip_stream) {
+  return guarded(h, [&]() -> int {
+    Request r;
+    r.family = FAM_INTERACTION; r.query_li = query_li; r.context_li = context_li; r.query_mask = query_mask; r.context_mask = context_mask;
+    r.fusion_scores = preflmr_scores; r.fusion_mult = fusion_multiplier;
+    r.packed = true; r.n_segments = n_segments; r.seg_pairs = seg_pairs; r.seg_len = seg_len; r.len = padded_context_len; r.q_len = Lq;
+    r.logits = logits_out; r.logits2 = logits2_out; r.stream = (hipStream_t)hip_stream;
+    return forward_interaction(h, r);
+  });
 }
 int rr_get_profile(rr_handle h, rr_profile* out, int reset) {
   return guarded(h, [&]() -> int { return rr_get_profile_impl(h, out, reset); });

@@ -183,6 +183,11 @@ def synthetic_state_dict(a: dict, seed: int = 0, hf_init: bool = True, gain: flo
     return w
 
 
+def _ptrs(out: dict) -> list:
+    """The output pointers of a forward / head call, in the C ABI's order (absent outputs are null)."""
+    return [L.ptr(out[k]) for k in ("logits", "logits2", "loss", "scores", "order") if k in out]
+
+
 class RerankEngine:
     """Owns one `rr_handle` (one model replica on one GPU)."""
 
@@ -291,19 +296,11 @@ class RerankEngine:
             image_patches = image_patches.to(device=dev, dtype=torch.float32).contiguous()
             if image_cls.shape[0] != Bq or image_patches.shape[0] != Bq:
                 raise AssertionError("image features must be per query: [Bq, ...]")
-        pb, pe = (0, N) if pair_range is None else (int(pair_range[0]), int(pair_range[1]))
-        full = pb == 0 and pe == N
-        logits = torch.empty(N, dtype=torch.float32, device=dev)
-        logits2 = torch.empty(N, dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev) if (full and want_loss) else None
-        scores = torch.empty(N, dtype=torch.float32, device=dev) if (full and want_scores) else None
-        order = torch.empty((Bq, K), dtype=torch.int32, device=dev) if (full and want_order) else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        pb, pe, out = self._outputs(Bq, K, pair_range, want_loss, want_scores, want_order)
         L.check(self.lib.rr_forward(self.h, L.ptr(input_ids), L.ptr(attention_mask), L.ptr(token_type_ids),
-                                    L.ptr(image_cls), L.ptr(image_patches), Bq, K, S, L.ptr(labels), pb, pe,
-                                    L.ptr(logits), L.ptr(logits2), L.ptr(loss), L.ptr(scores), L.ptr(order),
-                                    stream), self.h, "rr_forward")
-        return dict(logits=logits, logits2=logits2, loss=loss, scores=scores, order=order)
+                                    L.ptr(image_cls), L.ptr(image_patches), Bq, K, S, L.ptr(labels), pb, pe, *_ptrs(out),
+                                    self._stream()), self.h, "rr_forward")
+        return out
 
     def forward_ids_bucketed(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, token_type_ids: Optional[torch.Tensor],
                              Bq: int, K: int, image_cls: Optional[torch.Tensor] = None,
@@ -326,9 +323,7 @@ class RerankEngine:
         dev = self.device
         N, S = input_ids.shape
         assert N == Bq * K
-        cols = torch.arange(1, S + 1, device=dev)
-        used = (input_ids != 0) | (attention_mask != 0)
-        lens = (used * cols).amax(1)                                   # 1 + index of the last non-pad position
+        lens = pair_lengths(input_ids, attention_mask)                 # 1 + index of the last non-pad position
         # with vision tokens the mapping network attends to the first cross_attn_len text rows: no bucket below that (the
         # library refuses it: RR_ERR_BAD_SHAPE)
         floor = min(S, int(self.arch.get("cross_attn_len", 32))) if image_cls is not None else 1
@@ -369,7 +364,7 @@ class RerankEngine:
                            Bq: int, K: int, image_cls: Optional[torch.Tensor] = None,
                            image_patches: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
                            granule: int = 16, want_scores: bool = False, want_order: bool = False,
-                           lengths: Optional[Sequence[int]] = None, segment_cost_rows: int = 0):
+                           lengths: Optional[Sequence[int]] = None, segment_cost_rows: int = 0, want_loss: bool = True):
         """The same result as `forward_ids` on right-padded pairs, computed over PACKED rows (rr_forward_packed): the pairs are
         grouped by their length rounded up to a multiple of `granule` and laid out group after group, so that every GEMM /
         LayerNorm pass of a layer runs once over the rows that exist — the reference pads every pair to
@@ -382,46 +377,22 @@ class RerankEngine:
         derived on the device and the group counts cost one device -> host copy per call, which drains the stream between
         two forwards.  `segment_cost_rows`: merge neighbouring lengths where a segment's fixed launches cost more than the rows
         the merge pads (pair_inputs.group_pairs_by_length).  Returns the dict of forward_ids plus `packed_rows`, `packed_segments`."""
-        dev = self.device
         N, S = input_ids.shape
-        assert N == Bq * K and granule > 0
+        assert N == Bq * K
         floor = int(self.arch.get("cross_attn_len", 32)) if image_cls is not None else 1   # the mapping network's cross-attention window
-        if lengths is None:                                            # derived on the device: one device -> host copy
-            cols = torch.arange(1, S + 1, device=dev)
-            lengths = (((input_ids != 0) | (attention_mask != 0)) * cols).amax(1).cpu().numpy()
-        order_h, seg_n, seg_len = group_pairs_by_length(lengths, S, granule, floor, segment_cost_rows)
-        assert len(order_h) == N, "one length per pair"
-        order = torch.from_numpy(order_h).to(dev, non_blocking=True)
-        parts = [[], [], []]
-        o = 0
-        for n, sb in zip(seg_n, seg_len):
-            idx = order[o: o + n]
-            o += n
-            for dst, t in zip(parts, (input_ids, attention_mask, token_type_ids)):
-                if t is not None:
-                    dst.append(t.index_select(0, idx)[:, :sb].reshape(-1))
-        ids_p, am_p = torch.cat(parts[0]), torch.cat(parts[1])
-        tt_p = torch.cat(parts[2]) if token_type_ids is not None else None
-        cls_p = pat_p = None
-        if image_cls is not None:                                       # per pair: a group mixes candidates of several queries
-            q = torch.div(order, K, rounding_mode="floor")
-            cls_p = image_cls.index_select(0, q).float().contiguous()
-            pat_p = image_patches.index_select(0, q).float().contiguous()
-        two = self.arch["loss_fn"] == "2H_BCE"
-        lp = torch.empty(N, dtype=torch.float32, device=dev)
-        lp2 = torch.empty(N, dtype=torch.float32, device=dev) if two else None
-        sn = (C.c_int32 * len(seg_n))(*seg_n)
-        sl = (C.c_int32 * len(seg_n))(*seg_len)
-        L.check(self.lib.rr_forward_packed(self.h, L.ptr(ids_p), L.ptr(am_p), L.ptr(tt_p), L.ptr(cls_p), L.ptr(pat_p), len(seg_n),
-                                           sn, sl, S, L.ptr(lp), L.ptr(lp2), torch.cuda.current_stream(dev).cuda_stream),
-                self.h, "rr_forward_packed")
-        logits = torch.empty_like(lp).index_copy_(0, order, lp)
-        logits2 = torch.empty_like(lp).index_copy_(0, order, lp2) if two else torch.empty(N, dtype=torch.float32, device=dev)
-        out = self.head(logits, logits2 if two else None, labels, Bq, K, want_scores=want_scores, want_order=want_order)
-        out["logits"], out["logits2"] = logits, logits2
-        out["packed_rows"] = sum(n * s for n, s in zip(seg_n, seg_len))
-        out["packed_segments"] = len(seg_n)
-        return out
+
+        def launch(order, seg_n, seg_len, sn, sl, lp, lp2):
+            ids_p, am_p = pack_rows(input_ids, order, seg_n, seg_len), pack_rows(attention_mask, order, seg_n, seg_len)
+            tt_p = pack_rows(token_type_ids, order, seg_n, seg_len) if token_type_ids is not None else None
+            cls_p = pat_p = None
+            if image_cls is not None:                                   # per pair: a group mixes candidates of several queries
+                q = torch.div(order, K, rounding_mode="floor")
+                cls_p = image_cls.index_select(0, q).float().contiguous()
+                pat_p = image_patches.index_select(0, q).float().contiguous()
+            L.check(self.lib.rr_forward_packed(self.h, L.ptr(ids_p), L.ptr(am_p), L.ptr(tt_p), L.ptr(cls_p), L.ptr(pat_p), len(seg_n),
+                                               sn, sl, S, L.ptr(lp), L.ptr(lp2), self._stream()), self.h, "rr_forward_packed")
+        return self._packed(launch, (input_ids, attention_mask), lengths, S, floor, granule, segment_cost_rows, Bq, K, labels,
+                            want_loss, want_scores, want_order)
 
     def activation_range_exceeded(self, reset: bool = True) -> bool:
         """True when, since the last reset, a pre-LayerNorm residual row came within a factor 2 of the fp16 range (or was
@@ -463,30 +434,22 @@ class RerankEngine:
         cls = patches = None
         if image_cls is not None:
             cls, patches = image_cls.to(**f32).contiguous(), image_patches.to(**f32).contiguous()
-        pb, pe = (0, N) if pair_range is None else (int(pair_range[0]), int(pair_range[1]))
-        full = pb == 0 and pe == N
-        logits, logits2 = torch.empty(N, **f32), torch.empty(N, **f32)
-        loss = torch.empty((), **f32) if (full and want_loss) else None
-        scores = torch.empty(N, **f32) if (full and want_scores) else None
-        order = torch.empty((Bq, K), dtype=torch.int32, device=dev) if (full and want_order) else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        pb, pe, out = self._outputs(Bq, K, pair_range, want_loss, want_scores, want_order)
+        stream = self._stream()
         instr = -1 if instruction_token_id is None else int(instruction_token_id)
+        ids, am = L.ptr(joint_input_ids.contiguous()), L.ptr(joint_attention_mask.contiguous())
         if preflmr_scores is not None:
             P = self.arch["prefix_len"] + self.arch["n_patches"]
             ps = preflmr_scores.to(**f32).contiguous()
             if tuple(ps.shape) != (N, S, int(query_len) + P):                                   # rerank_model.py:280-284
                 raise AssertionError(f"preflmr_scores must be [{N}, {S}, {int(query_len) + P}], got {tuple(ps.shape)}")
-            L.check(self.lib.rr_forward_joint_fusion(self.h, L.ptr(joint_input_ids.contiguous()),
-                                                     L.ptr(joint_attention_mask.contiguous()), L.ptr(cls), L.ptr(patches),
-                                                     L.ptr(ps), float(fusion_multiplier), Bq, K, S, int(query_len), instr, pb,
-                                                     pe, L.ptr(logits), L.ptr(logits2), L.ptr(loss), L.ptr(scores),
-                                                     L.ptr(order), stream), self.h, "rr_forward_joint_fusion")
+            L.check(self.lib.rr_forward_joint_fusion(self.h, ids, am, L.ptr(cls), L.ptr(patches), L.ptr(ps), float(fusion_multiplier),
+                                                     Bq, K, S, int(query_len), instr, pb, pe, *_ptrs(out), stream),
+                    self.h, "rr_forward_joint_fusion")
         else:
-            L.check(self.lib.rr_forward_joint(self.h, L.ptr(joint_input_ids.contiguous()),
-                                              L.ptr(joint_attention_mask.contiguous()), L.ptr(cls), L.ptr(patches), Bq, K, S,
-                                              int(query_len), instr, pb, pe, L.ptr(logits), L.ptr(logits2), L.ptr(loss),
-                                              L.ptr(scores), L.ptr(order), stream), self.h, "rr_forward_joint")
-        return dict(logits=logits, logits2=logits2, loss=loss, scores=scores, order=order)
+            L.check(self.lib.rr_forward_joint(self.h, ids, am, L.ptr(cls), L.ptr(patches), Bq, K, S, int(query_len), instr, pb, pe,
+                                              *_ptrs(out), stream), self.h, "rr_forward_joint")
+        return out
 
     def forward_interaction(self, query_li: torch.Tensor, context_li: torch.Tensor, query_mask: torch.Tensor,
                             context_mask: torch.Tensor, Bq: int, K: int, labels: Optional[torch.Tensor] = None,
@@ -507,29 +470,20 @@ class RerankEngine:
         if labels is not None:
             assert labels.numel() == N
             labels = labels.to(**f32).contiguous()
-        pb, pe = (0, N) if pair_range is None else (int(pair_range[0]), int(pair_range[1]))
-        full = pb == 0 and pe == N
-        logits = torch.empty(N, **f32)
-        logits2 = torch.empty(N, **f32)
-        loss = torch.empty((), **f32) if (full and want_loss) else None
-        scores = torch.empty(N, **f32) if (full and want_scores) else None
-        order = torch.empty((Bq, K), dtype=torch.int32, device=dev) if (full and want_order) else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        pb, pe, out = self._outputs(Bq, K, pair_range, want_loss, want_scores, want_order)
+        stream = self._stream()
+        tensors = L.ptr(query_li), L.ptr(context_li), L.ptr(query_mask), L.ptr(context_mask)
         if preflmr_scores is not None:
             ps = preflmr_scores.to(**f32).contiguous()
             if tuple(ps.shape) != (N, Lc, Lq):
                 raise AssertionError(f"preflmr_scores must be [{N}, {Lc}, {Lq}], got {tuple(ps.shape)}")
-            L.check(self.lib.rr_forward_interaction_fusion(self.h, L.ptr(query_li), L.ptr(context_li), L.ptr(query_mask),
-                                                           L.ptr(context_mask), L.ptr(ps), float(fusion_multiplier), Bq, K,
-                                                           Lq, Lc, L.ptr(labels), pb, pe, L.ptr(logits), L.ptr(logits2),
-                                                           L.ptr(loss), L.ptr(scores), L.ptr(order), stream),
+            L.check(self.lib.rr_forward_interaction_fusion(self.h, *tensors, L.ptr(ps), float(fusion_multiplier), Bq, K, Lq, Lc,
+                                                           L.ptr(labels), pb, pe, *_ptrs(out), stream),
                     self.h, "rr_forward_interaction_fusion")
         else:
-            L.check(self.lib.rr_forward_interaction(self.h, L.ptr(query_li), L.ptr(context_li), L.ptr(query_mask),
-                                                    L.ptr(context_mask), Bq, K, Lq, Lc, L.ptr(labels), pb, pe,
-                                                    L.ptr(logits), L.ptr(logits2), L.ptr(loss), L.ptr(scores),
-                                                    L.ptr(order), stream), self.h, "rr_forward_interaction")
-        return dict(logits=logits, logits2=logits2, loss=loss, scores=scores, order=order)
+            L.check(self.lib.rr_forward_interaction(self.h, *tensors, Bq, K, Lq, Lc, L.ptr(labels), pb, pe, *_ptrs(out), stream),
+                    self.h, "rr_forward_interaction")
+        return out
 
     def forward_joint_packed(self, joint_input_ids: torch.Tensor, joint_attention_mask: torch.Tensor, Bq: int, K: int,
                              query_len: int, image_cls: torch.Tensor, image_patches: torch.Tensor,
@@ -547,44 +501,30 @@ class RerankEngine:
         packed.  Returns the dict of forward_joint plus `packed_rows`, `packed_segments`."""
         dev = self.device
         N, S = joint_input_ids.shape
-        assert N == Bq * K and granule > 0
+        assert N == Bq * K
         if image_cls is None or image_patches is None:
             raise NotImplementedError("text_only is not implemented for this model")        # rerank_model.py:184-185
         ql = int(query_len)
         f32 = dict(device=dev, dtype=torch.float32)
         ids, am = joint_input_ids.to(dev).contiguous(), joint_attention_mask.to(dev).contiguous()
         floor = max(ql + 1, min(S, int(self.arch.get("cross_attn_len", 32))))
-        if lengths is None:                                            # derived on the device: one device -> host copy
-            lengths = pair_lengths(ids, am).cpu().numpy()
-        order_h, seg_n, seg_len = group_pairs_by_length(lengths, S, granule, floor, segment_cost_rows)
-        assert len(order_h) == N, "one length per pair"
-        order = torch.from_numpy(order_h).to(dev, non_blocking=True)
-        ids_p, am_p = pack_rows(ids, order, seg_n, seg_len), pack_rows(am, order, seg_n, seg_len)
-        q = torch.div(order, K, rounding_mode="floor")                 # image features per pair: a segment mixes queries
-        cls_p = image_cls.to(**f32).index_select(0, q).contiguous()
-        pat_p = image_patches.to(**f32).index_select(0, q).contiguous()
-        ps = None
         if preflmr_scores is not None:
             P = self.arch["prefix_len"] + self.arch["n_patches"]
             if tuple(preflmr_scores.shape) != (N, S, ql + P):                                  # rerank_model.py:280-284
                 raise AssertionError(f"preflmr_scores must be [{N}, {S}, {ql + P}], got {tuple(preflmr_scores.shape)}")
-            ps = pack_fusion_scores(preflmr_scores.to(**f32), order, 2, S - ql)
-        lp, lp2 = torch.empty(N, **f32), torch.empty(N, **f32)
-        sn, sl = (C.c_int32 * len(seg_n))(*seg_n), (C.c_int32 * len(seg_n))(*seg_len)
         instr = -1 if instruction_token_id is None else int(instruction_token_id)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        L.check(self.lib.rr_forward_joint_packed(self.h, L.ptr(ids_p), L.ptr(am_p), L.ptr(cls_p), L.ptr(pat_p), L.ptr(ps),
-                                                 float(fusion_multiplier), len(seg_n), sn, sl, S, ql, instr, L.ptr(lp),
-                                                 L.ptr(lp2), stream), self.h, "rr_forward_joint_packed")
-        logits, logits2 = scatter_packed(lp, order), scatter_packed(lp2, order)
-        two = self.arch["loss_fn"] == "2H_BCE"
-        loss = torch.empty((), **f32) if want_loss else None
-        scores = torch.empty(N, **f32) if want_scores else None
-        order_out = torch.empty((Bq, K), dtype=torch.int32, device=dev) if want_order else None
-        L.check(self.lib.rr_head_joint(self.h, L.ptr(logits), L.ptr(logits2 if two else None), Bq, K, L.ptr(loss), L.ptr(scores),
-                                       L.ptr(order_out), stream), self.h, "rr_head_joint")
-        return dict(logits=logits, logits2=logits2, loss=loss, scores=scores, order=order_out,
-                    packed_rows=sum(n * s for n, s in zip(seg_n, seg_len)), packed_segments=len(seg_n))
+
+        def launch(order, seg_n, seg_len, sn, sl, lp, lp2):
+            ids_p, am_p = pack_rows(ids, order, seg_n, seg_len), pack_rows(am, order, seg_n, seg_len)
+            q = torch.div(order, K, rounding_mode="floor")             # image features per pair: a segment mixes queries
+            cls_p = image_cls.to(**f32).index_select(0, q).contiguous()
+            pat_p = image_patches.to(**f32).index_select(0, q).contiguous()
+            ps = None if preflmr_scores is None else pack_fusion_scores(preflmr_scores.to(**f32), order, 2, S - ql)
+            L.check(self.lib.rr_forward_joint_packed(self.h, L.ptr(ids_p), L.ptr(am_p), L.ptr(cls_p), L.ptr(pat_p), L.ptr(ps),
+                                                     float(fusion_multiplier), len(seg_n), sn, sl, S, ql, instr, L.ptr(lp),
+                                                     L.ptr(lp2), self._stream()), self.h, "rr_forward_joint_packed")
+        return self._packed(launch, (ids, am), lengths, S, floor, granule, segment_cost_rows, Bq, K, None, want_loss, want_scores,
+                            want_order, joint=True)
 
     def forward_interaction_packed(self, query_li: torch.Tensor, context_li: torch.Tensor, query_mask: torch.Tensor,
                                    context_mask: torch.Tensor, Bq: int, K: int, labels: Optional[torch.Tensor] = None,
@@ -599,57 +539,87 @@ class RerankEngine:
         forward_interaction plus `packed_rows` (context rows computed), `packed_segments`."""
         dev = self.device
         N = context_li.shape[0]
-        assert N == Bq * K and query_li.shape[0] == Bq and granule > 0, \
+        assert N == Bq * K and query_li.shape[0] == Bq, \
             f"{tuple(query_li.shape)}, {tuple(context_li.shape)}, {K - 1}"        # interaction_rerank_model.py:123
         Lq, Lc = query_li.shape[1], context_li.shape[1]
         f32 = dict(device=dev, dtype=torch.float32)
         cm = context_mask.reshape(N, Lc).to(**f32).contiguous()
-        if lengths is None:                                            # derived on the device: one device -> host copy
-            lengths = pair_lengths(cm).cpu().numpy()
-        order_h, seg_n, seg_len = group_pairs_by_length(lengths, Lc, granule, 1, segment_cost_rows)
-        assert len(order_h) == N, "one length per pair"
-        order = torch.from_numpy(order_h).to(dev, non_blocking=True)
-        q = torch.div(order, K, rounding_mode="floor")                 # query tensors per pair
-        q_p = query_li.to(**f32).index_select(0, q).contiguous()
-        qm_p = query_mask.reshape(Bq, Lq).to(**f32).index_select(0, q).contiguous()
-        c_p = pack_rows(context_li.to(**f32), order, seg_n, seg_len)
-        cm_p = pack_rows(cm, order, seg_n, seg_len)
-        ps = None
-        if preflmr_scores is not None:
-            if tuple(preflmr_scores.shape) != (N, Lc, Lq):
-                raise AssertionError(f"preflmr_scores must be [{N}, {Lc}, {Lq}], got {tuple(preflmr_scores.shape)}")
-            ps = pack_fusion_scores(preflmr_scores.to(**f32), order)
-        lp, lp2 = torch.empty(N, **f32), torch.empty(N, **f32)
-        sn, sl = (C.c_int32 * len(seg_n))(*seg_n), (C.c_int32 * len(seg_n))(*seg_len)
-        L.check(self.lib.rr_forward_interaction_packed(self.h, L.ptr(q_p), L.ptr(c_p), L.ptr(qm_p), L.ptr(cm_p), L.ptr(ps),
-                                                       float(fusion_multiplier), len(seg_n), sn, sl, Lc, Lq, L.ptr(lp),
-                                                       L.ptr(lp2), torch.cuda.current_stream(dev).cuda_stream),
-                self.h, "rr_forward_interaction_packed")
-        logits, logits2 = scatter_packed(lp, order), scatter_packed(lp2, order)
-        two = self.arch["loss_fn"] == "2H_BCE"
-        if labels is not None:
-            assert labels.numel() == N
-        out = self.head(logits, logits2 if two else None, labels, Bq, K, want_scores=want_scores, want_order=want_order)
-        out["logits"], out["logits2"] = logits, logits2
-        if not want_loss:
-            out["loss"] = None
-        out["packed_rows"] = sum(n * s for n, s in zip(seg_n, seg_len))
-        out["packed_segments"] = len(seg_n)
-        return out
+        if preflmr_scores is not None and tuple(preflmr_scores.shape) != (N, Lc, Lq):
+            raise AssertionError(f"preflmr_scores must be [{N}, {Lc}, {Lq}], got {tuple(preflmr_scores.shape)}")
+
+        def launch(order, seg_n, seg_len, sn, sl, lp, lp2):
+            q = torch.div(order, K, rounding_mode="floor")             # query tensors per pair
+            q_p = query_li.to(**f32).index_select(0, q).contiguous()
+            qm_p = query_mask.reshape(Bq, Lq).to(**f32).index_select(0, q).contiguous()
+            c_p = pack_rows(context_li.to(**f32), order, seg_n, seg_len)
+            cm_p = pack_rows(cm, order, seg_n, seg_len)
+            ps = None if preflmr_scores is None else pack_fusion_scores(preflmr_scores.to(**f32), order)
+            L.check(self.lib.rr_forward_interaction_packed(self.h, L.ptr(q_p), L.ptr(c_p), L.ptr(qm_p), L.ptr(cm_p), L.ptr(ps),
+                                                           float(fusion_multiplier), len(seg_n), sn, sl, Lc, Lq, L.ptr(lp),
+                                                           L.ptr(lp2), self._stream()), self.h, "rr_forward_interaction_packed")
+        return self._packed(launch, (cm,), lengths, Lc, 1, granule, segment_cost_rows, Bq, K, labels, want_loss, want_scores,
+                            want_order)
 
     def head(self, logits: torch.Tensor, logits2: Optional[torch.Tensor], labels: Optional[torch.Tensor], Bq: int,
-             K: int, want_scores: bool = False, want_order: bool = True):
-        """Scoring head on complete logits (after the cross-rank all-gather)."""
-        dev = self.device
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        scores = torch.empty(Bq * K, dtype=torch.float32, device=dev) if want_scores else None
-        order = torch.empty((Bq, K), dtype=torch.int32, device=dev) if want_order else None
+             K: int, want_scores: bool = False, want_order: bool = True, want_loss: bool = True, joint: bool = False):
+        """Scoring head on complete logits (after the cross-rank all-gather).  `joint`: RerankModel's loss, the reference's
+        loss_fn(logits, logits) (rr_head_joint, rerank_model.py:328; no labels)."""
+        out = self._head_outputs(Bq, K, want_loss, want_scores, want_order)
+        if joint:
+            L.check(self.lib.rr_head_joint(self.h, L.ptr(logits), L.ptr(logits2), Bq, K, *_ptrs(out), self._stream()),
+                    self.h, "rr_head_joint")
+            return out
         if labels is not None:
-            labels = labels.to(device=dev, dtype=torch.float32).contiguous()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        L.check(self.lib.rr_head(self.h, L.ptr(logits), L.ptr(logits2), L.ptr(labels), Bq, K, L.ptr(loss),
-                                 L.ptr(scores), L.ptr(order), stream), self.h, "rr_head")
-        return dict(loss=loss, scores=scores, order=order)
+            labels = labels.to(device=self.device, dtype=torch.float32).contiguous()
+        L.check(self.lib.rr_head(self.h, L.ptr(logits), L.ptr(logits2), L.ptr(labels), Bq, K, *_ptrs(out), self._stream()),
+                self.h, "rr_head")
+        return out
+
+    # ---- plumbing shared by the forwards
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _head_outputs(self, Bq: int, K: int, want_loss: bool, want_scores: bool, want_order: bool) -> dict:
+        dev = self.device
+        return dict(loss=torch.empty((), dtype=torch.float32, device=dev) if want_loss else None,
+                    scores=torch.empty(Bq * K, dtype=torch.float32, device=dev) if want_scores else None,
+                    order=torch.empty((Bq, K), dtype=torch.int32, device=dev) if want_order else None)
+
+    def _outputs(self, Bq: int, K: int, pair_range, want_loss: bool, want_scores: bool, want_order: bool):
+        """(pair_begin, pair_end, outputs) of a padded forward: logits / logits2 [N] always, loss / scores / order when the call
+        covers every pair and they are wanted."""
+        N = Bq * K
+        pb, pe = (0, N) if pair_range is None else (int(pair_range[0]), int(pair_range[1]))
+        full = pb == 0 and pe == N
+        out = dict(logits=torch.empty(N, dtype=torch.float32, device=self.device),
+                   logits2=torch.empty(N, dtype=torch.float32, device=self.device))
+        out.update(self._head_outputs(Bq, K, full and want_loss, full and want_scores, full and want_order))
+        return pb, pe, out
+
+    def _packed(self, launch, rows, lengths, padded_len: int, floor: int, granule: int, segment_cost_rows: int, Bq: int, K: int,
+                labels, want_loss: bool, want_scores: bool, want_order: bool, joint: bool = False) -> dict:
+        """What the packed forwards share: the pairs' lengths (`lengths` from the host, else derived from the [N, padded_len]
+        tensors `rows` on the device: one device -> host copy) -> segments (group_pairs_by_length) -> the pair order on the
+        device -> the ctypes segment tables -> `launch(order, seg_n, seg_len, seg_pairs, seg_lens, logits, logits2)`, which
+        packs its inputs and makes the call -> the logits scattered back to pair order -> the scoring head over them."""
+        N = Bq * K
+        assert granule > 0
+        if labels is not None:
+            assert labels.numel() == N
+        if lengths is None:
+            lengths = pair_lengths(*rows).cpu().numpy()
+        order_h, seg_n, seg_len = group_pairs_by_length(lengths, padded_len, granule, floor, segment_cost_rows)
+        assert len(order_h) == N, "one length per pair"
+        order = torch.from_numpy(order_h).to(self.device, non_blocking=True)
+        lp, lp2 = (torch.empty(N, dtype=torch.float32, device=self.device) for _ in range(2))
+        launch(order, seg_n, seg_len, (C.c_int32 * len(seg_n))(*seg_n), (C.c_int32 * len(seg_n))(*seg_len), lp, lp2)
+        logits, logits2 = scatter_packed(lp, order), scatter_packed(lp2, order)
+        two = self.arch["loss_fn"] == "2H_BCE"
+        out = self.head(logits, logits2 if two else None, labels, Bq, K, want_scores=want_scores, want_order=want_order,
+                        want_loss=want_loss, joint=joint)
+        out.update(logits=logits, logits2=logits2, packed_rows=sum(n * s for n, s in zip(seg_n, seg_len)),
+                   packed_segments=len(seg_n))
+        return out
 
     # ---- debugging / profiling ------------------------------------------------------------------
     def set_debug(self, on: bool):
@@ -705,7 +675,42 @@ class _FrozenStub(torch.nn.Module):
     freeze them (Reranker_base_executor.py:204-207).  The CLIP ViT is upstream of this path."""
 
 
-class FullContextRerankModel(torch.nn.Module):
+class _DropIn(torch.nn.Module):
+    """What the drop-in classes share: the engine's weights, the labels, the packed-or-padded routing and the output."""
+
+    def load_state_dict(self, state_dict, strict: bool = False, prefix: str = ""):  # type: ignore[override]
+        return self.engine.load_state_dict(state_dict, strict=strict, prefix=prefix)
+
+    def _labels(self, labels: Optional[List[float]], N: int) -> Optional[torch.Tensor]:
+        """A labels list as an fp32 device tensor (utils.py:232-233, rerank_model.py:528-529)."""
+        if labels is None:
+            return None
+        assert isinstance(labels, list), "Labels must be a list"
+        if self.engine.arch["loss_fn"] == "negative_sampling":
+            raise AssertionError("Labels should not be provided for negative sampling loss function")
+        assert len(labels) == N
+        return torch.tensor(labels, dtype=torch.float32, device=self.engine.device)
+
+    def _route(self, padded, packed, kw: dict):
+        """Config `packed_rows`: the same logits over packed rows; calls with `pair_range` (the sharded path) stay padded."""
+        if self.packed_rows and kw.get("pair_range") is None:
+            kw.pop("pair_range", None)
+            return packed
+        return padded
+
+    @staticmethod
+    def _output(r: dict, logits: torch.Tensor) -> RerankOutput:
+        out = RerankOutput(loss=r["loss"], logits=logits)
+        for k in ("scores", "order", "logits2"):
+            if r.get(k) is not None:
+                out[k] = r[k]
+        return out
+
+    def _ranked_logits(self, r: dict, Bq: int, K: int) -> torch.Tensor:
+        return r["logits"].view(Bq, K) if self.engine.arch["loss_fn"] == "negative_sampling" else r["logits"].view(Bq * K, 1)
+
+
+class FullContextRerankModel(_DropIn):
     """Drop-in for the reference's `FullContextRerankModel` (rerank_model.py:515-591), inference only.
 
     `config` is the reference `reranker_config` (EasyDict/dict).  Extra, optional keys:
@@ -748,9 +753,6 @@ class FullContextRerankModel(torch.nn.Module):
         if state_dict is not None:
             self.engine.load_state_dict(state_dict)
 
-    def load_state_dict(self, state_dict, strict: bool = False, prefix: str = ""):  # type: ignore[override]
-        return self.engine.load_state_dict(state_dict, strict=strict, prefix=prefix)
-
     # tensor fast path (synthetic benchmarks, pre-tokenised callers)
     def forward_ids(self, input_ids, attention_mask, token_type_ids, num_negative_examples: int,
                     image_cls=None, image_patches=None, labels: Optional[List[float]] = None, **kw) -> RerankOutput:
@@ -758,32 +760,10 @@ class FullContextRerankModel(torch.nn.Module):
         N = input_ids.shape[0]
         assert N % K == 0, "expanded batch size must be batch_size * (num_negative_examples + 1)"
         Bq = N // K
-        arch = self.engine.arch
-        if labels is not None:
-            assert isinstance(labels, list), "Labels must be a list"                       # utils.py:232
-            if arch["loss_fn"] == "negative_sampling":
-                raise AssertionError("Labels should not be provided for negative sampling loss function")
-            assert len(labels) == N                                                        # rerank_model.py:528-529
-            labels_t = torch.tensor(labels, dtype=torch.float32, device=self.engine.device)
-        else:
-            labels_t = None
-        if self.packed_rows and kw.get("pair_range") is None:     # config `packed_rows`: the same logits over packed rows
-            kw.pop("pair_range", None)
-            want_loss = kw.pop("want_loss", True)
-            r = self.engine.forward_ids_packed(input_ids, attention_mask, token_type_ids, Bq, K, image_cls, image_patches,
-                                               labels_t, **kw)
-            if not want_loss:
-                r["loss"] = None
-        else:
-            r = self.engine.forward_ids(input_ids, attention_mask, token_type_ids, Bq, K, image_cls, image_patches,
-                                        labels_t, **kw)
-        logits = r["logits"]
-        logits = logits.view(Bq, K) if arch["loss_fn"] == "negative_sampling" else logits.view(N, 1)
-        out = RerankOutput(loss=r["loss"], logits=logits)
-        for k in ("scores", "order", "logits2"):
-            if r.get(k) is not None:
-                out[k] = r[k]
-        return out
+        eng = self.engine
+        r = self._route(eng.forward_ids, eng.forward_ids_packed, kw)(input_ids, attention_mask, token_type_ids, Bq, K, image_cls,
+                                                                     image_patches, self._labels(labels, N), **kw)
+        return self._output(r, self._ranked_logits(r, Bq, K))
 
     def forward(self, query_text_sequences, query_pixel_values, context_text_sequences, num_negative_examples,
                 labels=None) -> RerankOutput:
@@ -822,7 +802,7 @@ class FullContextRerankModel(torch.nn.Module):
                                 labels if labels else None, **kw)
 
 
-class InteractionRerankModel(torch.nn.Module):
+class InteractionRerankModel(_DropIn):
     """Drop-in for the reference's `InteractionRerankModel` (interaction_rerank_model.py:86-166), inference only:
     `config.interaction_type` "MORES" selects the MORES stack (mores_model.py), anything else the CrossEncoder.
     Optional config key `packed_rows` (default False): `forward` runs over packed rows (RerankEngine.forward_interaction_packed;
@@ -838,41 +818,20 @@ class InteractionRerankModel(torch.nn.Module):
         if state_dict is not None:
             self.engine.load_state_dict(state_dict)
 
-    def load_state_dict(self, state_dict, strict: bool = False, prefix: str = ""):  # type: ignore[override]
-        return self.engine.load_state_dict(state_dict, strict=strict, prefix=prefix)
-
     def forward(self, query_late_interaction, context_late_interaction, num_negative_examples, query_mask,
                 context_mask, preflmr_scores=None, fusion_multiplier=1, labels=None, **kw) -> RerankOutput:
         K = num_negative_examples + 1
         Bq = query_late_interaction.size(0)
         N = context_late_interaction.size(0)
         assert Bq * K == N, f"{query_late_interaction.shape}, {context_late_interaction.shape}, {num_negative_examples}"
-        arch = self.engine.arch
-        labels_t = None
-        if labels is not None:
-            assert isinstance(labels, list), "Labels must be a list"
-            if arch["loss_fn"] == "negative_sampling":
-                raise AssertionError("Labels should not be provided for negative sampling loss function")
-            labels_t = torch.tensor(labels, dtype=torch.float32, device=self.engine.device)
-        if self.packed_rows and kw.get("pair_range") is None:     # config `packed_rows`: the same logits over packed rows
-            kw.pop("pair_range", None)
-            r = self.engine.forward_interaction_packed(query_late_interaction, context_late_interaction, query_mask,
-                                                       context_mask, Bq, K, labels_t, preflmr_scores=preflmr_scores,
-                                                       fusion_multiplier=float(fusion_multiplier), **kw)
-        else:
-            r = self.engine.forward_interaction(query_late_interaction, context_late_interaction, query_mask, context_mask,
-                                                Bq, K, labels_t, preflmr_scores=preflmr_scores,
-                                                fusion_multiplier=float(fusion_multiplier), **kw)
-        logits = r["logits"]
-        logits = logits.view(Bq, K) if arch["loss_fn"] == "negative_sampling" else logits.view(N, 1)
-        out = RerankOutput(loss=r["loss"], logits=logits)
-        for k in ("scores", "order", "logits2"):
-            if r.get(k) is not None:
-                out[k] = r[k]
-        return out
+        eng = self.engine
+        r = self._route(eng.forward_interaction, eng.forward_interaction_packed, kw)(
+            query_late_interaction, context_late_interaction, query_mask, context_mask, Bq, K, self._labels(labels, N),
+            preflmr_scores=preflmr_scores, fusion_multiplier=float(fusion_multiplier), **kw)
+        return self._output(r, self._ranked_logits(r, Bq, K))
 
 
-class RerankModel(torch.nn.Module):
+class RerankModel(_DropIn):
     """Drop-in for the reference's `RerankModel` (rerank_model.py:76-331; the "softmax"/2-head variant), inference
     only.  Extra optional config keys: `arch`, `image_feature_fn` (pixel_values -> (cls, patches)),
     `instruction_token_id` (id of `mask_instruction_token`, rerank_model.py:161-169; None = no instruction masking),
@@ -889,9 +848,6 @@ class RerankModel(torch.nn.Module):
         self.context_vision_encoder = _FrozenStub()
         if state_dict is not None:
             self.engine.load_state_dict(state_dict)
-
-    def load_state_dict(self, state_dict, strict: bool = False, prefix: str = ""):  # type: ignore[override]
-        return self.engine.load_state_dict(state_dict, strict=strict, prefix=prefix)
 
     def forward(self, query_input_ids, query_attention_mask, query_pixel_values, context_input_ids,
                 context_attention_mask, num_negative_examples, preflmr_scores=None, fusion_multiplier=1, labels=None,
@@ -922,15 +878,8 @@ class RerankModel(torch.nn.Module):
             else:
                 raise NotImplementedError("query_pixel_values given but neither config.vision_encoder nor "
                                           "config.image_feature_fn (CLIP ViT) is set")
-        if self.packed_rows and kw.get("pair_range") is None:     # config `packed_rows`: the same logits over packed rows
-            kw.pop("pair_range", None)
-            r = self.engine.forward_joint_packed(joint_ids, joint_am, Bq, K, ql, cls, patches, self.instruction_token_id,
-                                                 preflmr_scores=preflmr_scores, fusion_multiplier=float(fusion_multiplier), **kw)
-        else:
-            r = self.engine.forward_joint(joint_ids, joint_am, Bq, K, ql, cls, patches, self.instruction_token_id,
-                                          preflmr_scores=preflmr_scores, fusion_multiplier=float(fusion_multiplier), **kw)
-        out = RerankOutput(loss=r["loss"], logits=r["logits"].view(N, 1))
-        for k in ("scores", "order", "logits2"):
-            if r.get(k) is not None:
-                out[k] = r[k]
-        return out
+        eng = self.engine
+        r = self._route(eng.forward_joint, eng.forward_joint_packed, kw)(
+            joint_ids, joint_am, Bq, K, ql, cls, patches, self.instruction_token_id, preflmr_scores=preflmr_scores,
+            fusion_multiplier=float(fusion_multiplier), **kw)
+        return self._output(r, r["logits"].view(N, 1))

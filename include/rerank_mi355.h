@@ -274,6 +274,21 @@ int rr_forward_packed(rr_handle h, const int64_t* input_ids, const int64_t* atte
                       const float* image_cls, const float* image_patches, int n_segments, const int32_t* seg_pairs,
                       const int32_t* seg_len, int padded_seq_len, float* logits_out, float* logits2_out, void* hip_stream);
 
+/* rr_assemble_pairs: the token inputs of rr_forward_packed built on the device from rr_tok_prepare_compact's output, instead of
+ * uploading padded int64 rows.  pool: DEVICE int32 [pool_len]; desc: HOST int32 [n_pairs, 4] (query offset, la, context
+ * offset, lb) in pair order; order: HOST int32 [n_pairs], the packed pair order (pair order[i] is the i-th packed pair);
+ * n_segments / seg_pairs / seg_len: HOST segment table as rr_forward_packed takes it (1..64 segments, sum seg_pairs = n_pairs).
+ * Writes input_ids / attention_mask / token_type_ids (DEVICE int64, sum_s seg_pairs[s] * seg_len[s] entries, segment after
+ * segment, pair after pair; token_type_ids may be NULL): [CLS] q[:la] [SEP] c[:lb] [SEP] with mask 1, type 1 on c[:lb] and the
+ * closing [SEP], then pad_id with mask 0 and type 0 — rr_tok_prepare_pairs' row of the pair, cut to its segment's length.  The
+ * padded [N, S] layout is one segment of length S with the identity order.  Every descriptor is checked on the host BEFORE
+ * anything is enqueued (non-negative lengths and offsets, both runs inside the pool, la + lb + 3 <= its segment's length, order a
+ * permutation): any violation returns RR_ERR_BAD_SHAPE and writes nothing.  The library stages the descriptors to the device
+ * itself (desc and order may be reused when the call returns).  Enqueued on hip_stream; not capturable into a graph. */
+int rr_assemble_pairs(rr_handle h, const int32_t* pool, int64_t pool_len, const int32_t* desc, int n_pairs, const int32_t* order,
+                      int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int64_t cls_id, int64_t sep_id,
+                      int64_t pad_id, int64_t* input_ids, int64_t* attention_mask, int64_t* token_type_ids, void* hip_stream);
+
 /* rr_forward: one pass of the hot path over N = Bq*K (query,candidate) pairs.
  *   input_ids, attention_mask, token_type_ids : DEVICE int64 [N,S] row-major, query-major pair order
  *       (prepare_full_context_inputs, utils.py:129-167).  attention_mask masks keys in the text
@@ -437,6 +452,15 @@ int rr_tok_decode(rr_tokenizer_handle h, const int32_t* ids, int n, char* out, i
 int rr_tok_prepare_pairs(rr_tokenizer_handle h, const char* const* queries, int n_queries, const char* const* contexts,
                          int docs_per_query, int max_query_length, int max_context_length, int max_length, int n_threads,
                          int64_t* input_ids, int64_t* attention_mask, int64_t* token_type_ids);
+/* The same pairs in COMPACT form, for rr_assemble_pairs: identical round trips, budgets and LONGEST_FIRST truncation, no
+ * padded rows.  pool (int32, pool_capacity entries) receives every query's round-tripped ids once (query order), followed by
+ * every pair's kept context ids c[:lb] (pair order); desc (int32 [N, 4]) receives per pair (query offset, la, context offset,
+ * lb), offsets into pool: pair p is [CLS] q[:la] [SEP] c[:lb] [SEP], la + lb + 3 <= max_length tokens, exactly the non-pad
+ * part of rr_tok_prepare_pairs' row p.  *pool_needed = the entries the pool needs; when that exceeds pool_capacity the call
+ * returns RR_ERR_BAD_SHAPE and writes neither pool nor desc (grow the buffer and call again).  n_threads as rr_tok_prepare_pairs. */
+int rr_tok_prepare_compact(rr_tokenizer_handle h, const char* const* queries, int n_queries, const char* const* contexts,
+                           int docs_per_query, int max_query_length, int max_context_length, int max_length, int n_threads,
+                           int32_t* pool, int64_t pool_capacity, int64_t* pool_needed, int32_t* desc);
 
 /* Profiling: when on, rr_forward brackets every kernel launch with HIP events on the work
  * stream; rr_get_profile synchronises, accumulates and returns the per-class totals. */

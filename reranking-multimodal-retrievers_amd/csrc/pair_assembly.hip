@@ -1,0 +1,43 @@
+// Pair-input assembly on the device (rr_assemble_pairs, include/rerank_mi355.h): the int64 input_ids / attention_mask /
+// token_type_ids rows rr_forward_packed reads, expanded from the compact token pool of rr_tok_prepare_compact.  The row of a
+// pair is what rr_tok_prepare_pairs writes (csrc/pair_tokenizer.cpp): [CLS] q[:la] [SEP] c[:lb] [SEP], mask 1 on those
+// la + lb + 3 tokens, type 1 on c[:lb] and the closing [SEP], then [PAD] / mask 0 / type 0 up to the segment's length.
+// Memory only: one workgroup per packed pair, the query's ids are read by all K pairs of the query (from L2), every store is a
+// coalesced 8-byte run.  The host has checked every descriptor against the pool and its segment before the launch; the bound
+// test on the pool index below keeps a bad descriptor from ever reading outside it all the same.
+#include "rr_common.h"
+
+namespace {
+
+__global__ __launch_bounds__(256) void assemble_pairs_kernel(const int32_t* __restrict__ pool, long long pool_len,
+                                                             const rr_asm_pair* __restrict__ pairs, long long cls, long long sep,
+                                                             long long pad, int64_t* __restrict__ ids, int64_t* __restrict__ am,
+                                                             int64_t* __restrict__ tt) {
+  const rr_asm_pair d = pairs[blockIdx.x];
+  const int q_end = 1 + d.la, c_beg = q_end + 1, c_end = c_beg + d.lb;
+  const size_t base = (size_t)(unsigned)d.row0;
+  for (int j = threadIdx.x; j < d.len; j += blockDim.x) {
+    long long id = pad, src = -1;
+    int64_t m = 1, t = 0;
+    if (j == 0) id = cls;
+    else if (j < q_end) src = (long long)d.qoff + (j - 1);
+    else if (j == q_end) id = sep;
+    else if (j < c_end) { src = (long long)d.coff + (j - c_beg); t = 1; }
+    else if (j == c_end) { id = sep; t = 1; }
+    else m = 0;
+    if (src >= 0) id = src < pool_len ? (long long)pool[src] : pad;
+    ids[base + j] = id;
+    am[base + j] = m;
+    if (tt) tt[base + j] = t;
+  }
+}
+
+}  // namespace
+
+hipError_t rr_launch_assemble_pairs(const int32_t* pool, long long pool_len, const rr_asm_pair* pairs, int n_pairs, long long cls,
+                                    long long sep, long long pad, int64_t* ids, int64_t* am, int64_t* tt, hipStream_t st) {
+  if (n_pairs <= 0 || pool_len < 0 || !pairs || !ids || !am) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(assemble_pairs_kernel, dim3((unsigned)n_pairs), dim3(256), 0, st, pool, pool_len, pairs, cls, sep, pad, ids,
+                     am, tt);
+  return hipGetLastError();
+}

@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <condition_variable>
 #include <cstring>
 #include <exception>
@@ -469,6 +470,90 @@ int rr_tok_prepare_pairs(rr_tokenizer_handle h, const char* const* queries, int 
     h->pool.run(n_threads, worker);
     return RR_OK;
   
+  } catch (const std::bad_alloc&) {
+    return RR_ERR_OOM;
+  } catch (...) {
+    return RR_ERR_BAD_ARG;   // no C++ exception crosses the C ABI
+  }
+}
+
+// Compact form of rr_tok_prepare_pairs (include/rerank_mi355.h): the same round trips, budgets and LONGEST_FIRST cut, but no
+// padded rows: every query's round-tripped ids once, then every context's kept ids c[:lb], into one int32 pool, and one
+// (query offset, la, context offset, lb) descriptor per pair.  rr_assemble_pairs expands them on the device.
+int rr_tok_prepare_compact(rr_tokenizer_handle h, const char* const* queries, int n_queries, const char* const* contexts,
+                           int docs_per_query, int max_query_length, int max_context_length, int max_length, int n_threads,
+                           int32_t* pool, int64_t pool_capacity, int64_t* pool_needed, int32_t* desc) {
+  try {
+    if (!h || !queries || !contexts || !desc || !pool_needed || pool_capacity < 0 || (!pool && pool_capacity)) return RR_ERR_BAD_ARG;
+    *pool_needed = 0;
+    if (n_queries <= 0 || docs_per_query <= 0 || max_query_length < 0 || max_context_length < 0 || max_length < 3)
+      return RR_ERR_BAD_SHAPE;
+    const size_t N = (size_t)n_queries * docs_per_query;
+    for (int i = 0; i < n_queries; ++i) if (!queries[i]) return RR_ERR_BAD_ARG;
+    for (size_t i = 0; i < N; ++i) if (!contexts[i]) return RR_ERR_BAD_ARG;
+    if (n_threads <= 0) n_threads = (int)std::max(1u, std::thread::hardware_concurrency());
+    n_threads = (int)std::min<size_t>((size_t)n_threads, N);
+
+    // queries: as rr_tok_prepare_pairs step 1
+    std::vector<std::vector<int32_t>> qids((size_t)n_queries);
+    {
+      std::vector<int32_t> ids;
+      std::string txt;
+      for (int i = 0; i < n_queries; ++i) {
+        h->encode(queries[i], strlen(queries[i]), ids);
+        if ((int)ids.size() > max_query_length) ids.resize(max_query_length);
+        h->decode(ids.data(), ids.size(), txt);
+        h->encode(txt.data(), txt.size(), qids[(size_t)i]);
+      }
+    }
+    // contexts: round trip and LONGEST_FIRST lengths per pair, kept ids only
+    std::vector<std::vector<int32_t>> cids(N);
+    std::vector<int32_t> la(N), lb(N);
+    std::atomic<size_t> next{0};
+    auto worker = [&]() {
+      std::vector<int32_t> ids;
+      std::string txt;
+      for (;;) {
+        const size_t p = next.fetch_add(1);
+        if (p >= N) break;
+        h->encode(contexts[p], strlen(contexts[p]), ids);
+        if ((int)ids.size() > max_context_length) ids.resize(max_context_length);
+        h->decode(ids.data(), ids.size(), txt);
+        std::vector<int32_t>& c = cids[p];
+        h->encode(txt.data(), txt.size(), c);
+        size_t a = qids[p / (size_t)docs_per_query].size(), b = c.size();
+        while (a + b + 3 > (size_t)max_length) { if (a > b) --a; else --b; }
+        c.resize(b);
+        la[p] = (int32_t)a;
+        lb[p] = (int32_t)b;
+      }
+    };
+    h->pool.run(n_threads, worker);
+
+    int64_t need = 0;
+    for (const auto& q : qids) need += (int64_t)q.size();
+    for (const auto& c : cids) need += (int64_t)c.size();
+    *pool_needed = need;
+    if (need > INT32_MAX) return RR_ERR_BAD_SHAPE;           // descriptor offsets are int32
+    if (need > pool_capacity) return RR_ERR_BAD_SHAPE;
+    int64_t o = 0;
+    std::vector<int32_t> qoff((size_t)n_queries);
+    for (int i = 0; i < n_queries; ++i) {
+      qoff[(size_t)i] = (int32_t)o;
+      std::copy(qids[(size_t)i].begin(), qids[(size_t)i].end(), pool + o);
+      o += (int64_t)qids[(size_t)i].size();
+    }
+    for (size_t p = 0; p < N; ++p) {
+      int32_t* d = desc + 4 * p;
+      d[0] = qoff[p / (size_t)docs_per_query];
+      d[1] = la[p];
+      d[2] = (int32_t)o;
+      d[3] = lb[p];
+      std::copy(cids[p].begin(), cids[p].end(), pool + o);
+      o += (int64_t)cids[p].size();
+    }
+    return RR_OK;
+
   } catch (const std::bad_alloc&) {
     return RR_ERR_OOM;
   } catch (...) {

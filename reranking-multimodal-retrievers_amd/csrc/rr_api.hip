@@ -7,6 +7,7 @@
 #include "../../include/rerank_mi355_diag.h"   // product ABI (rerank_mi355.h) + the diagnostic entry points
 #include "rr_common.h"
 
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -252,6 +253,12 @@ struct rr_model {
   int prof_chain = -1;
   hipStream_t prof_chain_st = nullptr;
   rr_profile prof{};
+
+  // rr_assemble_pairs: two staging slots for the checked descriptors (pinned host -> device), used in turn.  `done` is recorded
+  // behind the assembly launch that read the slot: the slot is refilled only after it completed.
+  struct AsmSlot { rr_asm_pair* host = nullptr; rr_asm_pair* dev = nullptr; int cap = 0; hipEvent_t done = nullptr; };
+  AsmSlot asm_slot[2];
+  int asm_next = 0;
 };
 
 namespace {
@@ -1445,6 +1452,11 @@ static int rr_destroy_impl(rr_handle h) {
   if (h->tap_text) (void)hipFree(h->tap_text);
   if (h->adj) (void)hipFree(h->adj);
   for (auto& e : h->ev_pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
+  for (auto& a : h->asm_slot) {
+    if (a.host) (void)hipHostFree(a.host);
+    if (a.dev) (void)hipFree(a.dev);
+    if (a.done) (void)hipEventDestroy(a.done);
+  }
   delete h;
   return RR_OK;
 }
@@ -1745,6 +1757,72 @@ static int packed_segments(rr_model* m, const char* what, Request& r, int min_le
   r.Bq = r.pair_end = (int)pairs;
   r.K = 1;
   r.pair_begin = 0;
+  return RR_OK;
+}
+
+// rr_assemble_pairs (include/rerank_mi355.h): every check on the host first, then one staged upload and one launch.
+static int rr_assemble_pairs_impl(rr_handle h, const int32_t* pool, int64_t pool_len, const int32_t* desc, int n_pairs,
+                                  const int32_t* order, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len,
+                                  int64_t cls_id, int64_t sep_id, int64_t pad_id, int64_t* input_ids, int64_t* attention_mask,
+                                  int64_t* token_type_ids, void* hip_stream) {
+  const char* what = "rr_assemble_pairs";
+  if (!h) return RR_ERR_BAD_ARG;
+  rr_model* m = h;
+  if (!desc || !order || !seg_pairs || !seg_len || !input_ids || !attention_mask || (!pool && pool_len > 0))
+    return fail(m, RR_ERR_BAD_ARG, "%s: null argument", what);
+  if (pool_len < 0 || n_pairs <= 0 || n_segments <= 0 || n_segments > 64)
+    return fail(m, RR_ERR_BAD_SHAPE, "%s: pool_len=%lld, %d pairs, %d segments (1..64)", what, (long long)pool_len, n_pairs,
+                n_segments);
+  long long pairs = 0, rows = 0;
+  for (int s = 0; s < n_segments; ++s) {
+    if (seg_pairs[s] <= 0 || seg_len[s] < 3)
+      return fail(m, RR_ERR_BAD_SHAPE, "%s: segment %d holds %d pairs of length %d", what, s, seg_pairs[s], seg_len[s]);
+    pairs += seg_pairs[s];
+    rows += (long long)seg_pairs[s] * seg_len[s];
+  }
+  if (pairs != n_pairs || rows > INT32_MAX)
+    return fail(m, RR_ERR_BAD_SHAPE, "%s: the segments hold %lld pairs (%lld rows), the call has %d", what, pairs, rows, n_pairs);
+  std::vector<char> seen((size_t)n_pairs, 0);
+  for (int i = 0; i < n_pairs; ++i) {
+    const int32_t p = order[i];
+    if (p < 0 || p >= n_pairs || seen[(size_t)p]) return fail(m, RR_ERR_BAD_SHAPE, "%s: order is not a permutation (entry %d = %d)", what, i, p);
+    seen[(size_t)p] = 1;
+  }
+  std::vector<rr_asm_pair> staged((size_t)n_pairs);
+  int i = 0;
+  long long row0 = 0;
+  for (int s = 0; s < n_segments; ++s)
+    for (int k = 0; k < seg_pairs[s]; ++k, ++i, row0 += seg_len[s]) {
+      const int32_t* d = desc + 4 * (size_t)order[i];
+      if (d[0] < 0 || d[1] < 0 || d[2] < 0 || d[3] < 0 || (long long)d[0] + d[1] > pool_len || (long long)d[2] + d[3] > pool_len ||
+          (long long)d[1] + d[3] + 3 > seg_len[s])
+        return fail(m, RR_ERR_BAD_SHAPE, "%s: pair %d (query offset %d, la %d, context offset %d, lb %d) does not fit a pool of %lld "
+                    "ids and its segment's length %d", what, order[i], d[0], d[1], d[2], d[3], (long long)pool_len, seg_len[s]);
+      staged[(size_t)i] = rr_asm_pair{d[0], d[1], d[2], d[3], seg_len[s], (int32_t)row0, 0, 0};
+    }
+  hipStream_t st = (hipStream_t)hip_stream;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return fail(m, RR_ERR_BAD_ARG, "%s cannot be captured into a graph (it stages its descriptors from the host)", what);
+  RR_HIP(m, hipSetDevice(m->cfg.device));
+  rr_model::AsmSlot& a = m->asm_slot[m->asm_next];
+  if (!a.done) RR_HIP(m, hipEventCreateWithFlags(&a.done, hipEventDisableTiming));
+  else RR_HIP(m, hipEventSynchronize(a.done));      // the last upload from this slot, and the launch that read it, are done
+  if (a.cap < n_pairs) {
+    if (a.host) { RR_HIP(m, hipHostFree(a.host)); a.host = nullptr; }
+    if (a.dev) { RR_HIP(m, hipFree(a.dev)); a.dev = nullptr; }
+    a.cap = 0;
+    const int cap = std::max(n_pairs, 1024);
+    RR_HIP(m, hipHostMalloc((void**)&a.host, (size_t)cap * sizeof(rr_asm_pair), hipHostMallocDefault));
+    RR_HIP(m, hipMalloc((void**)&a.dev, (size_t)cap * sizeof(rr_asm_pair)));
+    a.cap = cap;
+  }
+  memcpy(a.host, staged.data(), staged.size() * sizeof(rr_asm_pair));
+  RR_HIP(m, hipMemcpyAsync(a.dev, a.host, staged.size() * sizeof(rr_asm_pair), hipMemcpyHostToDevice, st));
+  RR_RUN(m, st, RR_K_EMBED, 0.0, (double)rows * (token_type_ids ? 24.0 : 16.0) + 4.0 * (double)rows,
+         rr_launch_assemble_pairs(pool, pool_len, a.dev, n_pairs, cls_id, sep_id, pad_id, input_ids, attention_mask, token_type_ids, st));
+  RR_HIP(m, hipEventRecord(a.done, st));
+  m->asm_next ^= 1;
   return RR_OK;
 }
 
@@ -2401,6 +2479,12 @@ int rr_forward_packed(rr_handle h, const int64_t* input_ids, const int64_t* atte
     r.packed = true; r.n_segments = n_segments; r.seg_pairs = seg_pairs; r.seg_len = seg_len; r.len = padded_seq_len;
     r.logits = logits_out; r.logits2 = logits2_out; r.stream = (hipStream_t)hip_stream;
     return forward_full(h, r);
+  });
+}
+int rr_assemble_pairs(rr_handle h, const int32_t* pool, int64_t pool_len, const int32_t* desc, int n_pairs, const int32_t* order, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int64_t cls_id, int64_t sep_id, int64_t pad_id, int64_t* input_ids, int64_t* attention_mask, int64_t* token_type_ids, void* hip_stream) {
+  return guarded(h, [&]() -> int {
+    return rr_assemble_pairs_impl(h, pool, pool_len, desc, n_pairs, order, n_segments, seg_pairs, seg_len, cls_id, sep_id, pad_id,
+                                  input_ids, attention_mask, token_type_ids, hip_stream);
   });
 }
 int rr_forward_joint(rr_handle h, const int64_t* joint_input_ids, const int64_t* joint_attention_mask, const float* image_cls, const float* image_patches, int Bq, int K, int S, int query_len, int64_t instruction_token_id, int pair_begin, int pair_end, float* logits_out, float* logits2_out, float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream) {

@@ -420,3 +420,9 @@ hipError_t rr_launch_vit_embed_ln(const float* patches, const float* cls_emb, co
 
 hipError_t rr_launch_layernorm(const float* x, const float* gamma, const float* beta, float eps,
                                int rows, int cols, float* out_f32, bf16_t* out_bf16, int dt, hipStream_t st);
+
+// rr_assemble_pairs: one packed pair as the host stages it (descriptor checked against pool and segment; row0 = its first entry
+// in the packed rows, len = its segment's length)
+struct rr_asm_pair { int32_t qoff, la, coff, lb, len, row0, unused0, unused1; };
+hipError_t rr_launch_assemble_pairs(const int32_t* pool, long long pool_len, const rr_asm_pair* pairs, int n_pairs, long long cls,
+                                    long long sep, long long pad, int64_t* ids, int64_t* am, int64_t* tt, hipStream_t st);

@@ -394,6 +394,62 @@ class RerankEngine:
         return self._packed(launch, (input_ids, attention_mask), lengths, S, floor, granule, segment_cost_rows, Bq, K, labels,
                             want_loss, want_scores, want_order)
 
+    def assemble_pairs(self, pool: torch.Tensor, desc, order, seg_n: Sequence[int], seg_len: Sequence[int], special_ids: Sequence[int],
+                       with_token_types: bool = True):
+        """rr_assemble_pairs: the packed int64 (input_ids, attention_mask, token_type_ids) rows of rr_forward_packed, built on the
+        device from the compact tokens of NativePairTokenizer.prepare_compact.  `pool`: int32 device tensor; `desc`: host int32
+        [N, 4] (query offset, la, context offset, lb); `order`: host pair order; `seg_n` / `seg_len`: the segment table
+        (group_pairs_by_length); `special_ids`: (cls, sep, pad).  The padded [N, S] rows are order = arange(N), seg_n = [N],
+        seg_len = [S].  A descriptor outside the pool or longer than its segment raises ValueError before anything is written."""
+        import numpy as np
+        dev = self.device
+        if pool.dtype != torch.int32 or pool.device != dev or not pool.is_contiguous():
+            raise ValueError("pool must be a contiguous int32 tensor on the model device")
+        desc = np.ascontiguousarray(desc, dtype=np.int32)
+        order = np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
+        if desc.ndim != 2 or desc.shape[1] != 4 or desc.shape[0] != order.shape[0]:
+            raise ValueError("desc must be [N, 4] with one order entry per pair")
+        rows = sum(int(n) * int(l) for n, l in zip(seg_n, seg_len))
+        ids, am = (torch.empty(rows, dtype=torch.int64, device=dev) for _ in range(2))
+        tt = torch.empty(rows, dtype=torch.int64, device=dev) if with_token_types else None
+        cls_id, sep_id, pad_id = (int(x) for x in special_ids)
+        rc = self.lib.rr_assemble_pairs(self.h, L.ptr(pool), pool.numel(), desc.ctypes.data, desc.shape[0], order.ctypes.data,
+                                        len(seg_n), (C.c_int32 * len(seg_n))(*seg_n), (C.c_int32 * len(seg_n))(*seg_len), cls_id,
+                                        sep_id, pad_id, L.ptr(ids), L.ptr(am), L.ptr(tt), self._stream())
+        if rc == L.RR_ERR_BAD_SHAPE:        # a bad descriptor is a bad argument of this call, not an expanded-batch mismatch
+            raise ValueError(f"rr_assemble_pairs: {self.lib.rr_last_error(self.h).decode()}")
+        L.check(rc, self.h, "rr_assemble_pairs")
+        return ids, am, tt
+
+    def forward_tokens_packed(self, pool: torch.Tensor, desc, Bq: int, K: int, image_cls: Optional[torch.Tensor] = None,
+                              image_patches: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
+                              granule: int = 16, segment_cost_rows: int = 0, want_scores: bool = False, want_order: bool = False,
+                              want_loss: bool = True, padded_len: int = 512, special_ids: Sequence[int] = (101, 102, 0)):
+        """forward_ids_packed from COMPACT tokens (NativePairTokenizer.prepare_compact): the pool on the device, the
+        descriptors on the host, the rows assembled on the device by rr_assemble_pairs where forward_ids_packed packs padded
+        rows with pack_rows.  `padded_len` is the length the padded call would use (max_decoder_source_length), `special_ids`
+        the tokenizer's (cls, sep, pad).  Same grouping, image features per pair, scatter and head as forward_ids_packed, so
+        the same logits: bit for bit for text-only models.  Returns the dict of forward_ids_packed."""
+        import numpy as np
+        desc = np.ascontiguousarray(desc, dtype=np.int32)
+        N = Bq * K
+        assert desc.shape == (N, 4), f"expanded batch {Bq}*{K} != {desc.shape[0]}"
+        lengths = desc[:, 1].astype(np.int64) + desc[:, 3] + 3
+        floor = int(self.arch.get("cross_attn_len", 32)) if image_cls is not None else 1
+
+        def launch(order, seg_n, seg_len, sn, sl, lp, lp2, order_h):
+            ids_p, am_p, tt_p = self.assemble_pairs(pool, desc, order_h, seg_n, seg_len, special_ids)
+            cls_p = pat_p = None
+            if image_cls is not None:                                   # per pair: a group mixes candidates of several queries
+                q = torch.div(order, K, rounding_mode="floor")
+                cls_p = image_cls.index_select(0, q).float().contiguous()
+                pat_p = image_patches.index_select(0, q).float().contiguous()
+            L.check(self.lib.rr_forward_packed(self.h, L.ptr(ids_p), L.ptr(am_p), L.ptr(tt_p), L.ptr(cls_p), L.ptr(pat_p), len(seg_n),
+                                               sn, sl, int(padded_len), L.ptr(lp), L.ptr(lp2), self._stream()), self.h,
+                    "rr_forward_packed")
+        return self._packed(launch, (), lengths, int(padded_len), floor, granule, segment_cost_rows, Bq, K, labels, want_loss,
+                            want_scores, want_order, host_order=True)
+
     def activation_range_exceeded(self, reset: bool = True) -> bool:
         """True when, since the last reset, a pre-LayerNorm residual row came within a factor 2 of the fp16 range (or was
         not finite) — rr_activation_range_flag; synchronises the current stream, so call it once per batch group, not per
@@ -597,11 +653,12 @@ class RerankEngine:
         return pb, pe, out
 
     def _packed(self, launch, rows, lengths, padded_len: int, floor: int, granule: int, segment_cost_rows: int, Bq: int, K: int,
-                labels, want_loss: bool, want_scores: bool, want_order: bool, joint: bool = False) -> dict:
+                labels, want_loss: bool, want_scores: bool, want_order: bool, joint: bool = False, host_order: bool = False) -> dict:
         """What the packed forwards share: the pairs' lengths (`lengths` from the host, else derived from the [N, padded_len]
         tensors `rows` on the device: one device -> host copy) -> segments (group_pairs_by_length) -> the pair order on the
-        device -> the ctypes segment tables -> `launch(order, seg_n, seg_len, seg_pairs, seg_lens, logits, logits2)`, which
-        packs its inputs and makes the call -> the logits scattered back to pair order -> the scoring head over them."""
+        device -> the ctypes segment tables -> `launch(order, seg_n, seg_len, seg_pairs, seg_lens, logits, logits2)` (with
+        `host_order`, the host pair order as one more argument), which packs its inputs and makes the call -> the logits
+        scattered back to pair order -> the scoring head over them."""
         N = Bq * K
         assert granule > 0
         if labels is not None:
@@ -612,7 +669,8 @@ class RerankEngine:
         assert len(order_h) == N, "one length per pair"
         order = torch.from_numpy(order_h).to(self.device, non_blocking=True)
         lp, lp2 = (torch.empty(N, dtype=torch.float32, device=self.device) for _ in range(2))
-        launch(order, seg_n, seg_len, (C.c_int32 * len(seg_n))(*seg_n), (C.c_int32 * len(seg_n))(*seg_len), lp, lp2)
+        launch(order, seg_n, seg_len, (C.c_int32 * len(seg_n))(*seg_n), (C.c_int32 * len(seg_n))(*seg_len), lp, lp2,
+               *((order_h,) if host_order else ()))
         logits, logits2 = scatter_packed(lp, order), scatter_packed(lp2, order)
         two = self.arch["loss_fn"] == "2H_BCE"
         out = self.head(logits, logits2 if two else None, labels, Bq, K, want_scores=want_scores, want_order=want_order,

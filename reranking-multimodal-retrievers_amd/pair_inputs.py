@@ -9,7 +9,7 @@ environment has no vocab file, so tests use a small locally generated WordPiece 
 """
 from __future__ import annotations
 
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import torch
 
@@ -108,6 +108,58 @@ class NativePairTokenizer:
         if rc != 0:
             raise ValueError(f"rr_tok_prepare_pairs failed ({rc})")
         return {"input_ids": out[0], "attention_mask": out[1], "token_type_ids": out[2]}
+
+
+    @property
+    def special_ids(self):
+        """(cls, sep, pad) ids of the vocabulary (a repeated token keeps its last index, as rr_tok_create)."""
+        idx = {t: i for i, t in enumerate(self.vocab)}
+        return idx["[CLS]"], idx["[SEP]"], idx["[PAD]"]
+
+    def prepare_compact(self, query_text_sequences: List[str], context_text_sequences: List[str], max_query_length: int,
+                        max_context_length: int, max_decoder_source_length: int, docs_per_query: int,
+                        out: Optional[torch.Tensor] = None, pin_memory: bool = True):
+        """rr_tok_prepare_compact: the pairs of `prepare_full_context_inputs` without padded rows.  Returns (pool, desc,
+        lengths): `pool` an int32 host tensor (a view of `out` when it is large enough, else of a new buffer, pinned when
+        `pin_memory`) with every query's round-tripped ids once, then every pair's kept context ids; `desc` an int32 numpy
+        [N, 4] of (query offset, la, context offset, lb); `lengths` the int64 numpy token counts la + lb + 3, which is
+        what `pair_lengths` gives for the padded rows.  All host values: grouping needs no device -> host copy."""
+        import numpy as np
+        C = self._C
+        nq = len(query_text_sequences)
+        N = nq * docs_per_query
+        assert N == len(context_text_sequences), "expanded batch size must be batch_size * docs_per_query"   # :527
+        q = (C.c_char_p * nq)(*[t.encode("utf-8", "replace") for t in query_text_sequences])
+        c = (C.c_char_p * N)(*[t.encode("utf-8", "replace") for t in context_text_sequences])
+        desc = np.empty((N, 4), dtype=np.int32)
+        need = C.c_int64(0)
+        threads = self.n_threads if self.n_threads > 0 else host_threads()
+        buf = out if out is not None else torch.empty(nq * 2 * max(1, max_query_length) + N * max_decoder_source_length,
+                                                      dtype=torch.int32, pin_memory=pin_memory)
+        for _ in range(2):
+            assert buf.dtype == torch.int32 and buf.is_contiguous()
+            rc = self.lib.rr_tok_prepare_compact(self.h, q, nq, c, docs_per_query, max_query_length, max_context_length,
+                                                 max_decoder_source_length, threads, buf.data_ptr(), buf.numel(), C.byref(need),
+                                                 desc.ctypes.data)
+            if rc == 0:
+                lengths = desc[:, 1].astype(np.int64) + desc[:, 3] + 3
+                return buf[:need.value], desc, lengths
+            if rc != self._L.RR_ERR_BAD_SHAPE or need.value <= buf.numel():
+                break
+            buf = torch.empty(need.value + need.value // 4, dtype=torch.int32, pin_memory=pin_memory)   # grow, tokenise again
+        raise ValueError(f"rr_tok_prepare_compact failed ({rc}, pool needs {need.value})")
+
+
+def host_threads() -> int:
+    """CPU threads for host-side tokenisation: the CPUs this process may run on (not os.cpu_count(), the machine's), capped by
+    OMP_NUM_THREADS when that is set."""
+    import os
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        cap = int(os.environ.get("OMP_NUM_THREADS", "0"))
+    except ValueError:
+        cap = 0
+    return max(1, min(n, cap) if cap > 0 else n)
 
 
 def group_pairs_by_length(lengths, padded_len: int, granule: int, min_len: int = 1, segment_cost_rows: int = 0):

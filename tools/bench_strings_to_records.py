@@ -1,0 +1,179 @@
+"""Strings -> prediction records on one MI355X: rerank_dataset_pipelined against the serial loop and the device-bound rate.
+
+c3 shape: bert-base text encoder, one cross-encoder layer, K = 100 candidates, 8 queries per batch, fp16 operands, packed rows
+(granule 16), one vision line (81 vision tokens: 32 prefix + 49 patches from pixel values through the in-library CLIP ViT-B/32)
+and one text-only line.  Contexts are synthetic WordPiece text built as tools/bench_tokenizer.py builds it, with pair lengths
+spread over U[64, 512] tokens (the bench's realistic regime).  Three modes, each over the same queries after a warm-up:
+  resident_inputs        padded ids and pixels already on the device; per batch the ViT, forward_ids_packed with the host
+                         lengths (the same segments as the string modes), the head and non-blocking copies of logits and order
+                         into pinned memory; one synchronisation at the end.  The device-bound rate.
+  serial_from_strings    evaluate.rerank_dataset driving FullContextRerankModel.forward (native_tokenizer, packed_rows).
+  pipelined_from_strings pipeline.rerank_dataset_pipelined.
+Prints one JSON line.  Usage: python tools/bench_strings_to_records.py [--queries 64] [--warmup 16]"""
+import argparse
+import json
+import os
+import random
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+import rmr_amd  # noqa: E402
+from rmr_amd.pair_inputs import NativePairTokenizer, host_threads  # noqa: E402
+from rmr_amd.ranking import rank_descending_stable  # noqa: E402
+
+
+class VocabTokenizer:
+    """The smallest object FullContextRerankModel's native tokenizer needs: an id-ordered vocabulary."""
+
+    do_lower_case = True
+
+    def __init__(self, vocab):
+        self._v = {t: i for i, t in enumerate(vocab)}
+
+    def get_vocab(self):
+        return dict(self._v)
+
+
+def make_corpus(n_queries, K, seed=0):
+    rng = random.Random(seed)
+    syll = ["ka", "to", "mi", "ra", "ne", "so", "lu", "vi", "en", "or", "th", "st", "ing", "ed", "er", "al", "pre", "con"]
+    words = sorted({"".join(rng.choice(syll) for _ in range(rng.randint(1, 3))) for _ in range(4000)})
+    vocab = ["[PAD]"] + [f"[unused{i}]" for i in range(99)] + ["[UNK]", "[CLS]", "[SEP]", "[MASK]"] + words + \
+        ["##" + s for s in syll] + list(".,?!'-")
+    text = lambda n: " ".join(rng.choice(words) + rng.choice(["", "", "", ",", "."]) for _ in range(n))
+    tok = NativePairTokenizer(vocab, n_threads=1)
+    sample = [text(200) for _ in range(20)]
+    per_word = sum(len(tok.encode(s)) for s in sample) / (200.0 * len(sample))      # tokens per word of this generator
+    queries = []
+    for i in range(n_queries):
+        q = text(12) + "?"
+        ql = len(tok.encode(q))
+        docs = []
+        for k in range(K):
+            target = rng.randint(64, 512)                                             # pair length, [CLS] q [SEP] c [SEP]
+            docs.append({"passage_id": f"p{i}_{k}", "content": text(max(0, round((target - ql - 3) / per_word)))})
+        queries.append({"question_id": f"q{i}", "question": q, "retrieved_docs": docs,
+                        "pos_item_ids": [docs[j]["passage_id"] for j in rng.sample(range(K), 3)], "neg_item_ids": []})
+    return vocab, queries
+
+
+def build_model(vocab, vision, dev):
+    conf = dict(cross_encoder_num_hidden_layers=1, cross_encoder_max_position_embeddings=750, loss_fn="BCE", pos_weight=None,
+                max_query_length=32, max_decoder_source_length=512, compute_dtype="fp16", vision_encoder=vision,
+                text_only=not vision, tokenizer=VocabTokenizer(vocab), native_tokenizer=True, packed_rows=True)
+    arch = rmr_amd.make_arch(conf)
+    if not vision:
+        arch["has_vision"] = 0
+    sd = rmr_amd.synthetic_state_dict(arch, seed=0, hf_init=True)
+    m = rmr_amd.FullContextRerankModel(conf, state_dict=sd, device=dev)
+    m.native_tokenizer.n_threads = host_threads()      # both string modes: the CPUs this process may use, not the machine's
+    return m
+
+
+def labels_of(batch):
+    return [1.0 if d["passage_id"] in q["pos_item_ids"] else 0.0 for q in batch for d in q["retrieved_docs"]]
+
+
+def serial_forward(m, K):
+    def fwd(batch):
+        px = torch.stack([q["pixel_values"] for q in batch]) if "pixel_values" in batch[0] else None
+        r = m([q["question"] for q in batch], px, [d["content"] for q in batch for d in q["retrieved_docs"]], K - 1,
+              labels=labels_of(batch))
+        logits = r.logits.view(len(batch), K).tolist()
+        return {"logits": logits, "order": [rank_descending_stable(x) for x in logits], "loss": r.loss.item()}
+    return fwd
+
+
+def resident(m, batches, K):
+    """Inputs tokenised and uploaded beforehand; the timed part only queues device work and pinned read-backs."""
+    tok, eng = m.native_tokenizer, m.engine
+    prepared = []
+    for b in batches:
+        enc = tok.prepare_full_context_inputs([q["question"] for q in b], [d["content"] for q in b for d in q["retrieved_docs"]],
+                                              m.max_query_length, m.max_context_length, m.max_decoder_source_length, K)
+        lengths = (((enc["input_ids"] != 0) | (enc["attention_mask"] != 0)) * torch.arange(1, enc["input_ids"].shape[1] + 1)).amax(1)
+        px = torch.stack([q["pixel_values"] for q in b]).to(eng.device) if "pixel_values" in b[0] else None
+        prepared.append(([enc[k].to(eng.device) for k in ("input_ids", "attention_mask", "token_type_ids")], lengths.numpy(), px,
+                         torch.tensor(labels_of(b), device=eng.device), len(b)))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    keep = []
+    for (ids, am, tt), lengths, px, labels, n in prepared:
+        cls = pat = None
+        if px is not None:
+            cls, pat = eng.encode_image(px)
+        r = eng.forward_ids_packed(ids, am, tt, n, K, cls, pat, labels, want_order=True, lengths=lengths)
+        lh = torch.empty((n, K), dtype=torch.float32, pin_memory=True).copy_(r["logits"].view(n, K), non_blocking=True)
+        oh = torch.empty((n, K), dtype=torch.int32, pin_memory=True).copy_(r["order"], non_blocking=True)
+        keep.append((r, lh, oh))
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def run_line(vocab, queries, vision, args, dev):
+    K, B = args.K, args.batch
+    m = build_model(vocab, vision, dev)
+    if vision:
+        g = torch.Generator().manual_seed(3)
+        for q in queries:
+            q["pixel_values"] = 1.2 * torch.randn(3, 224, 224, generator=g)
+    else:
+        for q in queries:
+            q.pop("pixel_values", None)
+    warm, timed = queries[:args.warmup], queries[args.warmup:]
+    Ks = [1, 5, 10, K]
+    # warm-up of every mode (kernels, workspaces, pinned pools, tokenizer worker threads)
+    rmr_amd.rerank_dataset(warm, serial_forward(m, K), B, Ks, docs_to_rerank=K)
+    rmr_amd.rerank_dataset_pipelined(warm, m, B, Ks, docs_to_rerank=K)
+    resident(m, [warm[i:i + B] for i in range(0, len(warm), B)], K)
+    nb = -(-len(timed) // B)
+    out = {}
+    t = resident(m, [timed[i:i + B] for i in range(0, len(timed), B)], K)
+    out["resident_inputs"] = dict(queries_per_s=round(len(timed) / t, 2), ms_per_batch=round(t * 1e3 / nb, 3))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ser = rmr_amd.rerank_dataset(timed, serial_forward(m, K), B, Ks, docs_to_rerank=K)
+    t = time.perf_counter() - t0
+    out["serial_from_strings"] = dict(queries_per_s=round(len(timed) / t, 2), ms_per_batch=round(t * 1e3 / nb, 3))
+    stats = {}
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    pip = rmr_amd.rerank_dataset_pipelined(timed, m, B, Ks, docs_to_rerank=K, stats=stats)
+    t = time.perf_counter() - t0
+    out["pipelined_from_strings"] = dict(queries_per_s=round(len(timed) / t, 2), ms_per_batch=round(t * 1e3 / nb, 3),
+                                         host_tokenise_ms_per_batch=round(stats["tokenise_ms"] / stats["batches"], 3),
+                                         host_records_ms_per_batch=round(stats["records_ms"] / stats["batches"], 3))
+    out["pipelined_over_resident"] = round(out["pipelined_from_strings"]["queries_per_s"] / out["resident_inputs"]["queries_per_s"], 4)
+    out["serial_over_resident"] = round(out["serial_from_strings"]["queries_per_s"] / out["resident_inputs"]["queries_per_s"], 4)
+    out["records_identical"] = json.dumps(ser["output"]) == json.dumps(pip["output"])
+    out["metrics_identical"] = ser["metrics"] == pip["metrics"]
+    lens = [min(512, 3 + len(m.native_tokenizer.encode(q["question"])) + len(m.native_tokenizer.encode(d["content"])))
+            for q in timed[:2] for d in q["retrieved_docs"]]
+    out["mean_pair_tokens_sample"] = round(sum(lens) / len(lens), 1)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--queries", type=int, default=64, help="timed queries per mode (after the warm-up)")
+    ap.add_argument("--warmup", type=int, default=16)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--K", type=int, default=100)
+    ap.add_argument("--lines", default="vision,text_only")
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    vocab, queries = make_corpus(args.warmup + args.queries, args.K)
+    res = {"tool": "bench_strings_to_records", "shape": f"c3 bert-base, K={args.K}, {args.batch} queries/batch, fp16, packed rows "
+           "granule 16, pair lengths U[64, 512]", "queries_timed": args.queries, "host_threads": host_threads(),
+           "gpu": torch.cuda.get_device_name(dev)}
+    for line in args.lines.split(","):
+        res[line] = run_line(vocab, queries, line == "vision", args, dev)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

@@ -24,9 +24,13 @@ exchanged with one RCCL all_gather_into_tensor, the head runs on every rank.  Ra
 Timing: W warm-up steps, then K steps between (barrier + device synchronize) fences, max over ranks -> `value`.  Inside
 the timed region every step is also bracketed by HIP events on the work stream (-> median / p10 / p90 of the per-step
 device time) and the library brackets every kernel launch with HIP events (-> per-class device time, the roofline of
-the GEMM); `--no-profile` switches the per-launch events off.  At N = 1 the end-to-end window the reference times
-(Reranker_base_executor.py:898-939: H2D ids -> forward -> D2H logits/order for ONE query) and the CPU baseline follow,
-outside the timed region.
+the GEMM); `--no-profile` switches the per-launch events off.
+
+A plain run stops there: set up, warm up, time, `--dump-outputs`, print the line.  `--full` adds the measurements that
+take runs of their own, all outside the timed region: with `--weights-gain` one counted step of the attention fallback
+before it; at N = 1 after it the reference's 'Rerank time' window (H2D ids -> forward -> D2H logits/order for ONE
+query), the step with every cross-encoder row computed, the other 16-bit operand type and the CPU baseline (`--no-e2e`,
+`--no-alt-dtype`, `--no-cpu-baseline` leave one out).
 
 `--dump-outputs DIR` (rank 0): what the last timed step returned (logits, scores, order, loss, ...) as DIR/<name>.npy, right
 after the timed loop; inputs and weights are seeded, so two builds run with the same arguments can be compared array for array.
@@ -66,16 +70,20 @@ def parse_args(argv=None):
     ap.add_argument("--encoder", default=None, choices=["bert-base", "bert-large"], help="deprecated alias: bert-large = --workload c5")
     ap.add_argument("--regime", default="full", choices=["full", "realistic"])
     ap.add_argument("--fp8", action="store_true", help="c5: e4m3 operands for the QKV and FFN-up GEMMs (DESIGN.md §fp8)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need (see the module docstring): the end-to-end window, the all-rows "
+                         "step, the other operand type and the CPU baseline at N = 1, the attention redo count with --weights-gain")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-pairs", type=int, default=100, help="pairs of the CPU-baseline sample (one query of K = 100)")
     ap.add_argument("--no-profile", action="store_true", help="do not record per-launch HIP events")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end per-query window (N = 1)")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the end-to-end per-query window (N = 1)")
     ap.add_argument("--compute-dtype", default="fp16", choices=["bf16", "fp16"],
                     help="16-bit MFMA operand type of the timed run.  Default fp16: the mode whose logits are within 1e-3 of the "
                          "fp32 reference forward on every golden (same MFMA rate as bf16, 3 more mantissa bits; accumulation, "
                          "residual stream, LayerNorm, softmax stay fp32).  bf16 (what the reference's autocast uses) drifts "
                          "2e-3..1e-2 from fp32 in ANY implementation, the reference's own included (tests/golden/autocast.npz)")
-    ap.add_argument("--no-alt-dtype", action="store_true", help="skip the extra timing of the other operand type (N=1 only)")
+    ap.add_argument("--no-alt-dtype", action="store_true",
+                    help="--full: skip the extra timings of the other operand type and of the all-rows step (N=1 only)")
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="N > 1 ranks time-share cuda:0 and exchange over gloo: exercises the spawn / shard / gather / head "
                          "path with the real engine on a one-GPU box; the line is marked, it is NOT a scaling measurement")
@@ -94,8 +102,8 @@ def parse_args(argv=None):
                          "(rows one segment is worth; 0 = one segment per distinct length)")
     ap.add_argument("--weights-gain", type=float, default=1.0,
                     help="std multiplier of the Linear matrices of the synthetic weights (1 = HF init: near-uniform attention; 2.5 = the "
-                         "peaked-attention regime of tests/golden c3_sep).  The line then also reports how many attention workgroups "
-                         "the fixed-reference schedule had to recompute online (`attention_redo`)")
+                         "peaked-attention regime of tests/golden c3_sep).  With --full the line then also reports how many attention "
+                         "workgroups the fixed-reference schedule had to recompute online (`attention_redo`)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--tuning", action="append", default=[], metavar="KEY=INT",
@@ -463,7 +471,7 @@ def main():
         torch.cuda.synchronize(dev)
         assert torch.equal(ref["logits"], gout["logits"]), "graph replay differs from the eager step"
     redo = None
-    if args.weights_gain != 1.0:      # one untimed step with the redo counters on: how often the fixed-reference attention falls back
+    if args.full and args.weights_gain != 1.0:   # one untimed step with the redo counters on: how often the fixed-reference attention falls back
         cnt = torch.zeros(2, dtype=torch.int64, device=dev)
         rmr_amd._lib.load().rr_set_attn_redo_stats(cnt.data_ptr())
         step()
@@ -524,7 +532,7 @@ def main():
                        "cross_encoder_last_layer": "all layers run; in the cross-encoder's (single, last) layer K/V are projected for every row and the "
                                                    "query / attention-output / LayerNorm / FFN work is done for the CLS row of each pair only - "
                                                    "the only row the classifiers read (utils.py:105-108); logits equal the all-rows computation up "
-                                                   "to rounding; all_cross_encoder_rows_mode = the same step with every row computed",
+                                                   "to rounding; all_cross_encoder_rows_mode (--full) = the same step with every row computed",
                        **({"launch": "the step is ONE captured HIP graph, replayed"} if args.graph else {}),
                        "weights": "seeded random init (HF init), fp32 master -> 16-bit MFMA operands"
                                   + (f"; Linear matrices widened x{args.weights_gain} (peaked attention)" if args.weights_gain != 1.0 else "")},
@@ -594,7 +602,7 @@ def main():
             res["executed_tflops_per_gpu"] = exe / dt / 1e12
             res["executed_frac_of_bf16_peak"] = exe / dt / 1e12 / PEAK_BF16_TFLOPS
             res["executed_gflop_per_pair"] = exe / max(1, (N // world) * args.steps) / 1e9
-        if world == 1 and not args.no_e2e:
+        if args.full and world == 1 and not args.no_e2e:
             # the window the reference prints as "Rerank time" (Reranker_base_executor.py:898-939), for ONE query of K
             # candidates: host ids -> device, forward, logits/order back to the host (the sort runs on the device)
             h_ids, h_am, h_tt = (x[:K].cpu().pin_memory() for x in (ids, am, tt))
@@ -615,7 +623,7 @@ def main():
                                               "window": "pinned host ids/masks/features -> HBM, rr_forward (K pairs, device-side "
                                                         "stable top-K), logits + order -> host; the reference's 'Rerank time' "
                                                         "window (1.40 s per query published for monoPreFLMR-B on its GPU)"}
-        if world == 1 and not args.no_alt_dtype and not args.bucketed and not args.packed:
+        if args.full and world == 1 and not args.no_alt_dtype and not args.bucketed and not args.packed:
             # The library computes the cross-encoder's last layer behind its K / V projection for the CLS rows only (the classifiers
             # read hidden state [:, 0]; same logits up to rounding).  The same step with every row of that layer computed, as the
             # reference does, is reported beside the headline (rr_set_option "ce_cls_only" 0).
@@ -632,7 +640,7 @@ def main():
                                                       "note": "the last cross-encoder layer computed for all rows (handle option ce_cls_only = 0)"}
             finally:
                 eng.set_option("ce_cls_only", -1)
-        if world == 1 and not args.no_alt_dtype and not args.fp8:
+        if args.full and world == 1 and not args.no_alt_dtype and not args.fp8:
             # the same kernels with the other 16-bit operand type
             alt = "bf16" if args.compute_dtype == "fp16" else "fp16"
             del eng
@@ -649,7 +657,7 @@ def main():
             res[alt + "_operand_mode"] = {"value": N * args.steps / (time.perf_counter() - t1), "unit": "pairs/s",
                                           "note": res["parity"][alt]}
             del eng2
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(arch, sd, S, vision, args.cpu_pairs)
             res["gpu_over_cpu"] = pairs_per_s / res["cpu_baseline"]["value"]
         print(json.dumps(res))

@@ -51,6 +51,32 @@ int rr_op_gemm_ln_resid_f32(const uint16_t* A, const uint16_t* W, const float* b
 int rr_op_attention_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int q_stride, int kv_stride,
                          const float* key_bias, int B, int heads, int Tq, int Tk, int q_batch_div, uint16_t* out,
                          int out_stride, void* hip_stream);
+/* rr_op_attention_bf16 with every launch form the forwards use (rr_op_attention_bf16 is this call with q_batch_off 0, no dense
+ * bias, schedule_blocks 0 and fixed_mode -1).  q row (b,t): q + (((b + q_batch_off) / q_batch_div) * Tq + t) * q_stride + head*64.
+ * dense_bias: f32 [B][Tq][dense_ld] added to the scores in the natural-log domain (attention fusion; dense_ld a multiple of 64,
+ * >= Tk; it always runs the online form), or NULL.  schedule_blocks > 0: the grid size that picks the schedule (a packed forward
+ * passes its padded call's grid); 0 = this call's own grid.  fixed_mode 0..3: the schedule ("attn_fixed_ref" values), -1 = the
+ * process-wide switch. */
+int rr_op_attention_ex(const uint16_t* q, const uint16_t* k, const uint16_t* v, int q_stride, int kv_stride,
+                       const float* key_bias, int B, int heads, int Tq, int Tk, int q_batch_div, int q_batch_off, uint16_t* out,
+                       int out_stride, const float* dense_bias, int dense_ld, int64_t schedule_blocks, int fixed_mode,
+                       void* hip_stream);
+/* Self-attention over the segments of a packed layer (Tq = Tk = seg_len[s]): segment s holds seg_n[s] sequences whose rows lie
+ * back to back from row seg_row0[s] of q / k / v / out (row r at q + r * q_stride, ...); key_bias is one f32 per row, or NULL.
+ * One fixed-reference launch (and its redo launch) for all segments when the schedule is the fixed-reference one and nseg <= 64,
+ * else one rr_op_attention_ex per segment.  seg_* are HOST arrays. */
+int rr_op_attention_segs(const uint16_t* q, int q_stride, const uint16_t* k, const uint16_t* v, int kv_stride,
+                         const float* key_bias, int heads, int nseg, const int* seg_n, const int* seg_len, const int64_t* seg_row0,
+                         uint16_t* out, int out_stride, int64_t schedule_blocks, int fixed_mode, void* hip_stream);
+/* Attention-fusion bias builders.  scores f32 [*][S][Tq]; the Tc context rows of pair p start at row row0 of its scores.
+ * rr_op_fusion_adj: pairs pair0 .. pair0 + n - 1 -> adj [n][Tq + Tc][ld] (ld a multiple of 64, >= Tq + Tc; columns
+ * [Tq + Tc, ld) written as 0).  rr_op_fusion_adj_segs: nseg <= 64 segments of seg_n[s] pairs (HOST arrays) whose sequences end
+ * after seg_tk[s] <= Tc context tokens, normalised over all Tc; segment s as [seg_n[s]][Tq + seg_tk[s]][round_up(Tq + seg_tk[s],
+ * 64)], the segments back to back. */
+int rr_op_fusion_adj(const float* scores, int S, int Tq, int Tc, float mult, int pair0, int n, float* adj, int ld, int row0,
+                     void* hip_stream);
+int rr_op_fusion_adj_segs(const float* scores, int S, int Tq, int Tc, float mult, int nseg, const int* seg_n, const int* seg_tk,
+                          float* adj, int row0, void* hip_stream);
 /* Tuning hooks (tools/bench_gemm.py). rr_set_gemm_variant forces a kernel / tile configuration: 0..3 = gemm_kernel_s
  * {128x128x2st, 128x128x4st, 256x256x2st, 256x128x3st} with the direct epilogue, 10 = 256x256x2st with the LDS-staged
  * epilogue, 11 / 12 = gemm_kernel_h (half-tile ring) with the direct / LDS-staged epilogue, 13 = its diagnostic timeline

@@ -91,6 +91,12 @@ _SIGS = {
     "rr_op_gemm_resid_f32": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rr_op_attention_bf16": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, _P, C.c_int, _P]),
+    "rr_op_attention_ex": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     _P, C.c_int, _P, C.c_int, C.c_int64, C.c_int, _P]),
+    "rr_op_attention_segs": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int64,
+                                       C.c_int, _P]),
+    "rr_op_fusion_adj": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),
+    "rr_op_fusion_adj_segs": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P, _P, _P, C.c_int, _P]),
     "rr_set_gemm_variant": (C.c_int, [C.c_int]),
     "rr_set_op_dtype": (C.c_int, [C.c_int]),
     "rr_op_quantize_fp8": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -2354,12 +2354,39 @@ static int rr_op_gemm_resid_f32_impl(const uint16_t* A, const uint16_t* W, const
   return e == hipSuccess ? RR_OK : (e == hipErrorInvalidValue ? RR_ERR_BAD_SHAPE : RR_ERR_HIP);
 }
 
-static int rr_op_attention_bf16_impl(const uint16_t* q, const uint16_t* k, const uint16_t* v, int q_stride, int kv_stride,
-                         const float* key_bias, int B, int heads, int Tq, int Tk, int q_batch_div, uint16_t* out,
-                         int out_stride, void* hip_stream) {
+static int rr_op_attention_ex_impl(const uint16_t* q, const uint16_t* k, const uint16_t* v, int q_stride, int kv_stride,
+                                   const float* key_bias, int B, int heads, int Tq, int Tk, int q_batch_div, int q_batch_off,
+                                   uint16_t* out, int out_stride, const float* dense_bias, int dense_ld, int64_t schedule_blocks,
+                                   int fixed_mode, void* hip_stream) {
   if (!q || !k || !v || !out) return RR_ERR_BAD_ARG;
-  hipError_t e = rr_launch_attention(q, q_stride, q_batch_div, 0, k, v, kv_stride, key_bias, B, heads, Tq, Tk, out,
-                                     out_stride, g_op_dt, (hipStream_t)hip_stream);
+  hipError_t e = rr_launch_attention(q, q_stride, q_batch_div, q_batch_off, k, v, kv_stride, key_bias, B, heads, Tq, Tk, out,
+                                     out_stride, g_op_dt, (hipStream_t)hip_stream, dense_bias, dense_ld, (long)schedule_blocks,
+                                     fixed_mode);
+  return e == hipSuccess ? RR_OK : (e == hipErrorInvalidValue ? RR_ERR_BAD_SHAPE : RR_ERR_HIP);
+}
+
+static int rr_op_attention_segs_impl(const uint16_t* q, int q_stride, const uint16_t* k, const uint16_t* v, int kv_stride,
+                                     const float* key_bias, int heads, int nseg, const int* seg_n, const int* seg_len,
+                                     const int64_t* seg_row0, uint16_t* out, int out_stride, int64_t schedule_blocks, int fixed_mode,
+                                     void* hip_stream) {
+  if (!q || !k || !v || !out || !seg_n || !seg_len || !seg_row0 || nseg <= 0) return RR_ERR_BAD_ARG;
+  const std::vector<long long> row0(seg_row0, seg_row0 + nseg);
+  hipError_t e = rr_launch_attention_segs(q, q_stride, k, v, kv_stride, key_bias, heads, nseg, seg_n, seg_len, row0.data(), out,
+                                          out_stride, g_op_dt, (hipStream_t)hip_stream, (long)schedule_blocks, fixed_mode);
+  return e == hipSuccess ? RR_OK : (e == hipErrorInvalidValue ? RR_ERR_BAD_SHAPE : RR_ERR_HIP);
+}
+
+static int rr_op_fusion_adj_impl(const float* scores, int S, int Tq, int Tc, float mult, int pair0, int n, float* adj, int ld,
+                                 int row0, void* hip_stream) {
+  if (!scores || !adj) return RR_ERR_BAD_ARG;
+  hipError_t e = rr_launch_fusion_adj(scores, S, Tq, Tc, mult, pair0, n, adj, ld, (hipStream_t)hip_stream, row0);
+  return e == hipSuccess ? RR_OK : (e == hipErrorInvalidValue ? RR_ERR_BAD_SHAPE : RR_ERR_HIP);
+}
+
+static int rr_op_fusion_adj_segs_impl(const float* scores, int S, int Tq, int Tc, float mult, int nseg, const int* seg_n,
+                                      const int* seg_tk, float* adj, int row0, void* hip_stream) {
+  if (!scores || !adj || !seg_n || !seg_tk) return RR_ERR_BAD_ARG;
+  hipError_t e = rr_launch_fusion_adj_segs(scores, S, Tq, Tc, mult, nseg, seg_n, seg_tk, adj, (hipStream_t)hip_stream, row0);
   return e == hipSuccess ? RR_OK : (e == hipErrorInvalidValue ? RR_ERR_BAD_SHAPE : RR_ERR_HIP);
 }
 
@@ -2567,7 +2594,19 @@ int rr_op_gemm_resid_f32(const uint16_t* A, const uint16_t* W, const float* bias
   return guarded(nullptr, [&]() -> int { return rr_op_gemm_resid_f32_impl(A, W, bias, resid, M, N, Kd, out, hip_stream); });
 }
 int rr_op_attention_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int q_stride, int kv_stride, const float* key_bias, int B, int heads, int Tq, int Tk, int q_batch_div, uint16_t* out, int out_stride, void* hip_stream) {
-  return guarded(nullptr, [&]() -> int { return rr_op_attention_bf16_impl(q, k, v, q_stride, kv_stride, key_bias, B, heads, Tq, Tk, q_batch_div, out, out_stride, hip_stream); });
+  return guarded(nullptr, [&]() -> int { return rr_op_attention_ex_impl(q, k, v, q_stride, kv_stride, key_bias, B, heads, Tq, Tk, q_batch_div, 0, out, out_stride, nullptr, 0, 0, -1, hip_stream); });
+}
+int rr_op_attention_ex(const uint16_t* q, const uint16_t* k, const uint16_t* v, int q_stride, int kv_stride, const float* key_bias, int B, int heads, int Tq, int Tk, int q_batch_div, int q_batch_off, uint16_t* out, int out_stride, const float* dense_bias, int dense_ld, int64_t schedule_blocks, int fixed_mode, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_attention_ex_impl(q, k, v, q_stride, kv_stride, key_bias, B, heads, Tq, Tk, q_batch_div, q_batch_off, out, out_stride, dense_bias, dense_ld, schedule_blocks, fixed_mode, hip_stream); });
+}
+int rr_op_attention_segs(const uint16_t* q, int q_stride, const uint16_t* k, const uint16_t* v, int kv_stride, const float* key_bias, int heads, int nseg, const int* seg_n, const int* seg_len, const int64_t* seg_row0, uint16_t* out, int out_stride, int64_t schedule_blocks, int fixed_mode, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_attention_segs_impl(q, q_stride, k, v, kv_stride, key_bias, heads, nseg, seg_n, seg_len, seg_row0, out, out_stride, schedule_blocks, fixed_mode, hip_stream); });
+}
+int rr_op_fusion_adj(const float* scores, int S, int Tq, int Tc, float mult, int pair0, int n, float* adj, int ld, int row0, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_fusion_adj_impl(scores, S, Tq, Tc, mult, pair0, n, adj, ld, row0, hip_stream); });
+}
+int rr_op_fusion_adj_segs(const float* scores, int S, int Tq, int Tc, float mult, int nseg, const int* seg_n, const int* seg_tk, float* adj, int row0, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_fusion_adj_segs_impl(scores, S, Tq, Tc, mult, nseg, seg_n, seg_tk, adj, row0, hip_stream); });
 }
 int rr_op_gemm_ln_resid_f32(const uint16_t* A, const uint16_t* W, const float* bias, const float* x, const float* stats, const float* gamma, const float* beta, int M, int N, int Kd, float* out, void* hip_stream) {
   return guarded(nullptr, [&]() -> int { return rr_op_gemm_ln_resid_f32_impl(A, W, bias, x, stats, gamma, beta, M, N, Kd, out, hip_stream); });

@@ -1,5 +1,6 @@
 """Shared test helpers: golden loading, oracle<->engine config mapping."""
 import ast
+import math
 import os
 import sys
 
@@ -155,3 +156,43 @@ def record_margin(key, **metrics):
             json.dump(data, f, indent=1, sort_keys=True)
     except Exception:      # noqa: BLE001 — bookkeeping only
         pass
+
+
+def _query_rows(q, B, qdiv, qoff):
+    """q [Bq, Tq, H] -> the query rows each of the B sequences reads: q[(b + qoff) // qdiv] (rr_launch_attention)."""
+    return q[(torch.arange(B, device=q.device) + qoff) // qdiv]
+
+
+def attn_ref(q, k, v, bias, heads, qdiv=1, qoff=0, dense=None):
+    """Exact softmax attention in float64 on the kernel's (16-bit) inputs.  q arrives pre-scaled by log2(e)/sqrt(64), so the
+    natural-log scores are (q . k) ln 2; `bias` [B, Tk] is the additive key bias in that log2 domain (0 / -1e30), `dense`
+    [B, Tq, Tk] the attention-fusion bias in the natural domain.  -1e30 absorbs every finite score in float64 as finfo.min does
+    in the reference's float32: a sequence without a valid key attends uniformly to all Tk keys."""
+    B, Tk, Tq = k.shape[0], k.shape[1], q.shape[1]
+    qh = _query_rows(q.double(), B, qdiv, qoff).view(B, Tq, heads, 64).transpose(1, 2)
+    kh = k.double().view(B, Tk, heads, 64).transpose(1, 2)
+    vh = v.double().view(B, Tk, heads, 64).transpose(1, 2)
+    s = (qh @ kh.transpose(-1, -2)) * math.log(2.0)
+    if dense is not None:
+        s = s + dense.to(s.device, torch.float64)[:, None]
+    if bias is not None:
+        s = s + bias.to(s.device, torch.float64)[:, None, None, :] * math.log(2.0)
+    return (torch.softmax(s, -1) @ vh).transpose(1, 2).reshape(B, Tq, heads * 64)
+
+
+def attn_emulation(q, k, v, bias, heads, qdiv=1, qoff=0, dense=None):
+    """The device's rounding points (oracle.multi_head_attention_bf16 at the operand type of q: 16-bit Q, K, V and P, fp32
+    scores and row sums) on the same inputs and biases as attn_ref, the output rounded to that type, returned as float64.  The
+    biases enter as the float32 mask the oracle expects: -1e30 absorbs the fusion bias there as finfo.min does."""
+    dt, dev = q.dtype, k.device
+    B = k.shape[0]
+    qq = (_query_rows(q.double(), B, qdiv, qoff) / O._QSCALE).float()      # the oracle scales q itself
+    mask = None
+    if bias is not None:
+        mask = (bias.to(dev, torch.float64) * math.log(2.0))[:, None, None, :]
+    if dense is not None:
+        d = dense.to(dev, torch.float64)[:, None]
+        mask = d if mask is None else mask + d
+    with O.device_rounding(dt):
+        out = O.multi_head_attention_bf16(qq, k.float(), v.float(), heads, None if mask is None else mask.float())
+    return out.to(dt).double()

@@ -5,6 +5,8 @@ import math
 import pytest
 import torch
 
+from helpers import attn_ref
+
 pytestmark = pytest.mark.gpu
 
 
@@ -82,19 +84,6 @@ def test_gemm_rejects_bad_shapes(lib):
     assert lib.rr_op_gemm_bf16(A.data_ptr(), A.data_ptr(), 0, 8, 8, 96, 2, out.data_ptr(), _stream()) == -2   # K % 64
 
 
-def _attn_ref(q, k, v, bias, heads, qdiv=1):
-    B, Tk = k.shape[0], k.shape[1]
-    Tq = q.shape[1]
-    qq = q.float().repeat_interleave(qdiv, 0)[:B]
-    qh = qq.view(B, Tq, heads, 64).transpose(1, 2)
-    kh = k.float().view(B, Tk, heads, 64).transpose(1, 2)
-    vh = v.float().view(B, Tk, heads, 64).transpose(1, 2)
-    s = (qh @ kh.transpose(-1, -2)) * math.log(2.0)   # q arrives pre-scaled by log2(e)/sqrt(dh): the kernel's exponentials are base 2
-    if bias is not None:
-        s = s + bias[:, None, None, :]
-    return (torch.softmax(s, -1) @ vh).transpose(1, 2).reshape(B, Tq, heads * 64)
-
-
 @pytest.mark.parametrize("B,heads,Tq,Tk,masked", [(2, 2, 64, 64, False), (3, 12, 128, 128, True), (2, 12, 512, 512, True),
                                                    (2, 2, 593, 593, True), (4, 12, 49, 49, False), (6, 12, 49, 32, False),
                                                    (1, 1, 1, 1, False), (2, 3, 70, 130, True)])
@@ -116,7 +105,7 @@ def test_attention(lib, B, heads, Tq, Tk, masked):
                                   B, heads, Tq, Tk, 1, out.data_ptr(), H, _stream())
     assert rc == 0
     torch.cuda.synchronize()
-    ref = _attn_ref(q, k, v, bias, heads)
+    ref = attn_ref(q, k, v, bias, heads)
     got = out.float()
     assert torch.isfinite(got).all()
     assert (got - ref).abs().max().item() < 2e-2       # bf16 P and bf16 output on |O| <~ 1
@@ -135,7 +124,7 @@ def test_attention_fused_qkv_layout_and_query_broadcast(lib):
     assert rc == 0
     torch.cuda.synchronize()
     x = qkv.view(B, T, 3 * H)
-    ref = _attn_ref(x[..., :H], x[..., H:2 * H], x[..., 2 * H:], None, heads)
+    ref = attn_ref(x[..., :H], x[..., H:2 * H], x[..., 2 * H:], None, heads)
     assert (out.float() - ref).abs().max().item() < 2e-2
     # q_batch_div: 2 queries, each shared by 3 pairs
     q = torch.randn(2, 49, H, generator=g).bfloat16().cuda()
@@ -145,8 +134,20 @@ def test_attention_fused_qkv_layout_and_query_broadcast(lib):
     assert lib.rr_op_attention_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), H, H, 0, 6, heads, 49, 32, 3,
                                     out.data_ptr(), H, _stream()) == 0
     torch.cuda.synchronize()
-    ref = _attn_ref(q, k, v, None, heads, qdiv=3)
+    ref = attn_ref(q, k, v, None, heads, qdiv=3)
     assert (out.float() - ref).abs().max().item() < 2e-2
+    # q_batch_off (rr_op_attention_ex, the per-query cross-attention of a pair slice): pairs [2, 5) start inside query 0's pairs
+    # and read q[(b + 2) / 3]; their rows are the unsliced call's rows bit for bit, on the online and the fixed-reference schedule
+    for sched, mode in ((0, 0), (4096, 1), (4096, 2)):
+        full = torch.empty(6, 49, H, dtype=torch.bfloat16, device="cuda")
+        assert lib.rr_op_attention_ex(q.data_ptr(), k.data_ptr(), v.data_ptr(), H, H, 0, 6, heads, 49, 32, 3, 0, full.data_ptr(), H,
+                                      0, 0, sched, mode, _stream()) == 0
+        part = torch.full((3, 49, H), float("nan"), dtype=torch.bfloat16, device="cuda")
+        assert lib.rr_op_attention_ex(q.data_ptr(), k[2:].data_ptr(), v[2:].data_ptr(), H, H, 0, 3, heads, 49, 32, 3, 2,
+                                      part.data_ptr(), H, 0, 0, sched, mode, _stream()) == 0
+        torch.cuda.synchronize()
+        assert torch.equal(part, full[2:5]), (sched, mode)
+        assert (part.float() - attn_ref(q, k[2:5], v[2:5], None, heads, qdiv=3, qoff=2)).abs().max().item() < 2e-2
 
 
 def test_attention_all_masked_row_is_uniform(lib):
@@ -164,7 +165,7 @@ def test_attention_all_masked_row_is_uniform(lib):
     torch.cuda.synchronize()
     want = v[1].float().mean(0, keepdim=True).expand(T, 64)
     assert (out[1].float() - want).abs().max().item() < 1e-2
-    ref0 = _attn_ref(q[:1], k[:1], v[:1], None, 1)
+    ref0 = attn_ref(q[:1], k[:1], v[:1], None, 1)
     assert (out[0].float() - ref0[0]).abs().max().item() < 2e-2
 
 
@@ -182,7 +183,7 @@ def test_attention_online_softmax_rescale(lib):
     assert lib.rr_op_attention_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), 64, 64, 0, B, heads, T, T, 1,
                                     out.data_ptr(), 64, _stream()) == 0
     torch.cuda.synchronize()
-    ref = _attn_ref(q, k, v, None, 1)
+    ref = attn_ref(q, k, v, None, 1)
     assert (out.float() - ref).abs().max().item() < 3e-2
 
 
@@ -229,7 +230,7 @@ def _fixed_reference_cases(lib, t16, mode):
     bias[3, :] = -1e30                                                              # (d) no valid key
     bias[4:, 300:] = -1e30
     q, k, v, bias = q.to(t16).cuda(), k.to(t16).cuda(), v.to(t16).cuda(), bias.cuda()
-    ref = _attn_ref(q, k, v, bias, heads)
+    ref = attn_ref(q, k, v, bias, heads)
     try:
         assert lib.rr_set_tuning(b"attn_fixed_ref", mode) == 0
         got = _run_attn(lib, q, k, v, bias, heads)
@@ -284,7 +285,7 @@ def test_attention_fixed_reference_forms_are_bitwise_equal(lib):
     finally:
         lib.rr_set_tuning(b"attn_fixed_ref", -1)
     assert torch.equal(outs[0], outs[1])
-    assert (outs[0] - _attn_ref(q, k, v, bias, heads)).abs().max().item() < 3e-2
+    assert (outs[0] - attn_ref(q, k, v, bias, heads)).abs().max().item() < 3e-2
 
 
 @pytest.mark.parametrize("Tk", [1100, 2100])
@@ -309,7 +310,7 @@ def test_attention_long_key_sequences_reload_the_bias_chunk(lib, Tk):
     finally:
         lib.rr_set_tuning(b"attn_fixed_ref", -1)
     assert torch.equal(outs[1], outs[2])                        # the two fixed-reference forms agree bit for bit
-    ref = _attn_ref(q, k, v, bias, heads)
+    ref = attn_ref(q, k, v, bias, heads)
     for o in outs:
         assert (o - ref).abs().max().item() < 3e-2
 
@@ -448,7 +449,7 @@ def test_fp16_operand_ops(lib):
         assert lib.rr_op_attention_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), H, H, bias.data_ptr(), B, heads, T, T,
                                         1, o.data_ptr(), H, _stream()) == 0
         torch.cuda.synchronize()
-        ref = _attn_ref(q, k, v, bias, heads)
+        ref = attn_ref(q, k, v, bias, heads)
         assert (o.float() - ref).abs().max().item() < 3e-3
         x = torch.randn(9, 768, generator=g).cuda()
         gm, bt = torch.ones(768).cuda(), torch.zeros(768).cuda()

@@ -186,6 +186,62 @@ int rr_set_gemm_stagger(int unit);   /* diagnostic codes of the 16-bit GEMM kern
 int rr_op_layernorm(const float* x, const float* gamma, const float* beta, float eps, int rows, int cols,
                     float* out_f32, uint16_t* out_bf16, void* hip_stream);
 
+/* The row and glue kernels of the forwards, stand-alone (each passes straight through to its launcher; the forwards call the
+ * launchers directly).  All pointers DEVICE; every 16-bit output is in the operand type of rr_set_op_dtype.  Row kernels run one
+ * wave per row: cols (D) a multiple of 4, at most 2048.  Buffers the kernel reads or writes with 16-byte (8-byte: 16-bit rows,
+ * float2 statistics) accesses must be aligned to that.  What the host can check is checked before the launch: a NULL that is
+ * not optional or a misaligned buffer gives RR_ERR_BAD_ARG, a size or shape the kernel cannot take RR_ERR_BAD_SHAPE; neither
+ * launches anything. */
+/* BertEmbeddings: row r = (word[ids[r]] + type[tts[r]]) + pos[r % S] -> LayerNorm; ids clamped to [0, vocab), token types to
+ * [0, type_vocab); tts NULL = type 0.  Both outputs required. */
+int rr_op_embed_ln(const int64_t* ids, const int64_t* tts, const float* word, const float* pos, const float* type,
+                   const float* gamma, const float* beta, float eps, int rows, int S, int cols, int vocab, int type_vocab,
+                   float* out_f32, uint16_t* out16, void* hip_stream);
+/* Cross-encoder embeddings: row r (t = r % T) = (x[r] + type0) + pos[p(t)] -> LayerNorm, p(t) = t for t < s_text, else
+ * vis_pos0 + t - s_text; s_text < 0 or > T: plain positions.  cls32 != 0: out_f32 written for the rows t == 0 only (out16 for
+ * every row).  Both outputs required. */
+int rr_op_ce_embed_ln(const float* x, const float* pos, const float* type0, const float* gamma, const float* beta, float eps,
+                      int rows, int T, int cols, float* out_f32, uint16_t* out16, int s_text, int vis_pos0, int cls32,
+                      void* hip_stream);
+/* Late-interaction rows: destination row (p, j < rows_per_batch) = src row ((p + pair_off) / bdiv - src_batch_off, j) times its
+ * mask, L2-normalised (F.normalize, eps 1e-12) when normalize != 0, cast to 16 bits into dst [n_pairs][T][D] at row
+ * t_off + j + (j >= split ? shift : 0).  Mask: maskf[p * rows_per_batch + j] if maskf, else (ids[p * ids_stride + j] != 0) if
+ * ids, else 1. */
+int rr_op_li_normalize(const float* src, const int64_t* ids, int ids_stride, int n_pairs, int rows_per_batch, int D, int T,
+                       int t_off, int pair_off, int bdiv, int src_batch_off, uint16_t* dst, int normalize, const float* maskf,
+                       int split, int shift, void* hip_stream);
+/* Key-padding biases (0 / -1e30): text_bias [n][S] from am != 0; ce_bias [n][T] from ids != 0 for t < S, 0 for t >= S. */
+int rr_op_key_bias(const int64_t* ids, const int64_t* am, int n, int S, int T, float* text_bias, float* ce_bias, void* hip_stream);
+/* RerankModel masks: text_bias [n][S] from am; li_mask [n][S] = instruction query mask (id != 0 and (s > sep or s < 2), sep =
+ * first position of instruction_token clamped to >= 1; instruction_token < 0: id != 0); ce_bias [n][S + P] = that mask as a bias,
+ * reordered to [query (q_len) | P zeros | rest]. */
+int rr_op_joint_masks(const int64_t* ids, const int64_t* am, int n, int S, int P, int q_len, int64_t instruction_token,
+                      float* text_bias, float* li_mask, float* ce_bias, void* hip_stream);
+/* Interaction rerankers' biases from 0/1 masks: pair p's query mask is qmask row (p + pair_off) / K; cat_bias [n][Lq + Lc],
+ * q_bias [n][Lq], c_bias [n][Lc], each optional. */
+int rr_op_interaction_bias(const float* qmask, const float* cmask, int n, int Lq, int Lc, int pair_off, int K, float* cat_bias,
+                           float* q_bias, float* c_bias, void* hip_stream);
+/* CLIP patch im2col: px f32 [B][3][IS][IS] -> out [B * (IS / ps)^2][Kp], columns (c, ky, kx), zeros in [3 ps^2, Kp). */
+int rr_op_vit_im2col(const float* px, uint16_t* out, int B, int IS, int ps, int Kp, void* hip_stream);
+/* [cls_emb ; patches] + pos -> LayerNorm (fp32 only): row r = b * T + t; t = 0 takes cls_emb, t > 0 patch row b * (T - 1) + t - 1. */
+int rr_op_vit_embed_ln(const float* patches, const float* cls_emb, const float* pos, const float* gamma, const float* beta,
+                       float eps, int rows, int T, int cols, float* out_f32, void* hip_stream);
+/* f32 [n] -> 16 bits, round to nearest even; n a multiple of 4. */
+int rr_op_cast16(const float* x, uint16_t* y, int64_t n, void* hip_stream);
+/* Row gather / broadcast of row_bytes-byte rows (a multiple of 16): dst row (p, j < rows_take) = src row
+ * ((p + batch_off) / bdiv - src_batch_off) * src_rows_per_batch + j. */
+int rr_op_gather_rows(const void* src, void* dst, int n_dst_batches, int rows_take, int src_rows_per_batch, int row_bytes,
+                      int batch_off, int bdiv, int src_batch_off, void* hip_stream);
+/* Classifier heads on the CLS rows: out1[p] = <h32[p * T], w1> + b1[0]; out2 (optional, then b2 too) likewise with w2 / b2.
+ * w2 is read even when out2 is NULL. */
+int rr_op_cls_heads(const float* h32, int T, int cols, int n_pairs, const float* w1, const float* b1, const float* w2,
+                    const float* b2, float* out1, float* out2, void* hip_stream);
+/* Merge per-128-column-group (mean, M2) partials [rows][nparts] (nparts = ceil(cols / 128), the last group cols - 128 (nparts - 1)
+ * wide) into stats [rows] = (mean, 1 / sqrt(M2 / cols + eps)).  range_flag (optional int): OR-ed with 1 by every row whose sum of
+ * squares is not below range_ss (NaN included). */
+int rr_op_ln_finalize(const float* part, int nparts, int cols, float eps, int rows, float* stats, int* range_flag, float range_ss,
+                      void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,20 @@ _SIGS = {
     "rr_set_gemm_stamps": (C.c_int, [_P]),
     "rr_set_gemm_stagger": (C.c_int, [C.c_int]),
     "rr_op_layernorm": (C.c_int, [_P, _P, _P, C.c_float, C.c_int, C.c_int, _P, _P, _P]),
+    "rr_op_embed_ln": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "rr_op_ce_embed_ln": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int,
+                                    _P]),
+    "rr_op_li_normalize": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P,
+                                     C.c_int, _P, C.c_int, C.c_int, _P]),
+    "rr_op_key_bias": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "rr_op_joint_masks": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P]),
+    "rr_op_interaction_bias": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "rr_op_vit_im2col": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "rr_op_vit_embed_ln": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "rr_op_cast16": (C.c_int, [_P, _P, C.c_int64, _P]),
+    "rr_op_gather_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "rr_op_cls_heads": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "rr_op_ln_finalize": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_int, _P, _P, C.c_float, _P]),
 }
 EXPORTED = sorted(_SIGS)
 

@@ -2466,6 +2466,110 @@ static int rr_op_layernorm_impl(const float* x, const float* gamma, const float*
   return e == hipSuccess ? RR_OK : (e == hipErrorInvalidValue ? RR_ERR_BAD_SHAPE : RR_ERR_HIP);
 }
 
+// ---- row and glue kernels of elementwise.hip, stand-alone.  Several launchers validate nothing, and several kernels add a row
+// offset to an output pointer before testing it; these checks stand in front of them, and a failed one launches nothing.
+static bool op_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+static bool op_row_cols(int cols) { return cols > 0 && (cols & 3) == 0 && cols <= 2048; }   // one wave per row, MAX_V4 = 8
+static int op_status(hipError_t e) { return e == hipSuccess ? RR_OK : (e == hipErrorInvalidValue ? RR_ERR_BAD_SHAPE : RR_ERR_HIP); }
+
+static int rr_op_embed_ln_impl(const int64_t* ids, const int64_t* tts, const float* word, const float* pos, const float* type,
+                               const float* gamma, const float* beta, float eps, int rows, int S, int cols, int vocab,
+                               int type_vocab, float* out_f32, uint16_t* out16, void* hip_stream) {
+  if (!ids || !word || !pos || !type || !gamma || !beta || !out_f32 || !out16) return RR_ERR_BAD_ARG;
+  for (const void* p : {(const void*)word, (const void*)pos, (const void*)type, (const void*)gamma, (const void*)beta,
+                        (const void*)out_f32})
+    if (!op_aligned(p, 16)) return RR_ERR_BAD_ARG;
+  if (!op_aligned(out16, 8)) return RR_ERR_BAD_ARG;
+  if (rows <= 0 || S <= 0 || vocab <= 0 || type_vocab <= 0 || !op_row_cols(cols)) return RR_ERR_BAD_SHAPE;
+  return op_status(rr_launch_embed_ln(ids, tts, word, pos, type, gamma, beta, eps, rows, S, cols, vocab, type_vocab, out_f32, out16,
+                                      g_op_dt, (hipStream_t)hip_stream));
+}
+static int rr_op_ce_embed_ln_impl(const float* x, const float* pos, const float* type0, const float* gamma, const float* beta,
+                                  float eps, int rows, int T, int cols, float* out_f32, uint16_t* out16, int s_text, int vis_pos0,
+                                  int cls32, void* hip_stream) {
+  if (!x || !pos || !type0 || !gamma || !beta || !out_f32 || !out16) return RR_ERR_BAD_ARG;
+  for (const void* p : {(const void*)x, (const void*)pos, (const void*)type0, (const void*)gamma, (const void*)beta,
+                        (const void*)out_f32})
+    if (!op_aligned(p, 16)) return RR_ERR_BAD_ARG;
+  if (!op_aligned(out16, 8)) return RR_ERR_BAD_ARG;
+  if (rows <= 0 || T <= 0 || vis_pos0 < 0 || !op_row_cols(cols)) return RR_ERR_BAD_SHAPE;
+  return op_status(rr_launch_ce_embed_ln(x, pos, type0, gamma, beta, eps, rows, T, cols, out_f32, out16, g_op_dt,
+                                         (hipStream_t)hip_stream, s_text, vis_pos0, cls32));
+}
+static int rr_op_li_normalize_impl(const float* src, const int64_t* ids, int ids_stride, int n_pairs, int rows_per_batch, int D,
+                                   int T, int t_off, int pair_off, int bdiv, int src_batch_off, uint16_t* dst, int normalize,
+                                   const float* maskf, int split, int shift, void* hip_stream) {
+  if (!src || !dst || !op_aligned(src, 16) || !op_aligned(dst, 8)) return RR_ERR_BAD_ARG;
+  if (n_pairs <= 0 || rows_per_batch <= 0 || !op_row_cols(D) || T <= 0 || bdiv <= 0 || t_off < 0 || pair_off < 0 ||
+      src_batch_off < 0 || pair_off / bdiv < src_batch_off || split < 0 || shift < 0 || (ids && ids_stride < rows_per_batch))
+    return RR_ERR_BAD_SHAPE;
+  const int j = rows_per_batch - 1;                       // the last destination row of a pair lies inside its T rows
+  if ((long long)t_off + j + (j >= split ? shift : 0) >= T) return RR_ERR_BAD_SHAPE;
+  return op_status(rr_launch_li_normalize(src, ids, ids_stride, n_pairs, rows_per_batch, D, T, t_off, pair_off, bdiv, src_batch_off,
+                                          dst, g_op_dt, normalize, maskf, split, shift, (hipStream_t)hip_stream));
+}
+static int rr_op_key_bias_impl(const int64_t* ids, const int64_t* am, int n, int S, int T, float* text_bias, float* ce_bias,
+                               void* hip_stream) {
+  if (!ids || !am || !text_bias || !ce_bias) return RR_ERR_BAD_ARG;
+  if (n <= 0 || S <= 0 || T < S || (long long)n * T > INT_MAX) return RR_ERR_BAD_SHAPE;
+  return op_status(rr_launch_key_bias(ids, am, n, S, T, text_bias, ce_bias, (hipStream_t)hip_stream));
+}
+static int rr_op_joint_masks_impl(const int64_t* ids, const int64_t* am, int n, int S, int P, int q_len, int64_t instruction_token,
+                                  float* text_bias, float* li_mask, float* ce_bias, void* hip_stream) {
+  if (!ids || !am || !text_bias || !li_mask || !ce_bias) return RR_ERR_BAD_ARG;
+  if (n <= 0 || S <= 0 || P < 0 || q_len < 0 || q_len > S) return RR_ERR_BAD_SHAPE;
+  return op_status(rr_launch_joint_masks(ids, am, n, S, P, q_len, (long long)instruction_token, text_bias, li_mask, ce_bias,
+                                         (hipStream_t)hip_stream));
+}
+static int rr_op_interaction_bias_impl(const float* qmask, const float* cmask, int n, int Lq, int Lc, int pair_off, int K,
+                                       float* cat_bias, float* q_bias, float* c_bias, void* hip_stream) {
+  if (!qmask || !cmask) return RR_ERR_BAD_ARG;
+  if (n <= 0 || Lq <= 0 || Lc <= 0 || K <= 0 || pair_off < 0 || (long long)n * (Lq + Lc) > INT_MAX) return RR_ERR_BAD_SHAPE;
+  return op_status(rr_launch_interaction_bias(qmask, cmask, n, Lq, Lc, pair_off, K, cat_bias, q_bias, c_bias,
+                                              (hipStream_t)hip_stream));
+}
+static int rr_op_vit_im2col_impl(const float* px, uint16_t* out, int B, int IS, int ps, int Kp, void* hip_stream) {
+  if (!px || !out) return RR_ERR_BAD_ARG;
+  if (B <= 0 || ps <= 0 || IS < ps || Kp < 3 * ps * ps) return RR_ERR_BAD_SHAPE;
+  return op_status(rr_launch_vit_im2col(px, out, B, IS, ps, Kp, g_op_dt, (hipStream_t)hip_stream));
+}
+static int rr_op_vit_embed_ln_impl(const float* patches, const float* cls_emb, const float* pos, const float* gamma, const float* beta,
+                                   float eps, int rows, int T, int cols, float* out_f32, void* hip_stream) {
+  if (!patches || !cls_emb || !pos || !gamma || !beta || !out_f32) return RR_ERR_BAD_ARG;
+  for (const void* p : {(const void*)patches, (const void*)cls_emb, (const void*)pos, (const void*)gamma, (const void*)beta,
+                        (const void*)out_f32})
+    if (!op_aligned(p, 16)) return RR_ERR_BAD_ARG;
+  if (rows <= 0 || T <= 0 || !op_row_cols(cols)) return RR_ERR_BAD_SHAPE;
+  return op_status(rr_launch_vit_embed_ln(patches, cls_emb, pos, gamma, beta, eps, rows, T, cols, out_f32, (hipStream_t)hip_stream));
+}
+static int rr_op_cast16_impl(const float* x, uint16_t* y, int64_t n, void* hip_stream) {
+  if (!x || !y || !op_aligned(x, 16) || !op_aligned(y, 8)) return RR_ERR_BAD_ARG;
+  if (n <= 0 || (n & 3)) return RR_ERR_BAD_SHAPE;
+  return op_status(rr_launch_f32_to_bf16(x, y, (size_t)n, g_op_dt, (hipStream_t)hip_stream));
+}
+static int rr_op_gather_rows_impl(const void* src, void* dst, int n_dst_batches, int rows_take, int src_rows_per_batch, int row_bytes,
+                                  int batch_off, int bdiv, int src_batch_off, void* hip_stream) {
+  if (!src || !dst || !op_aligned(src, 16) || !op_aligned(dst, 16)) return RR_ERR_BAD_ARG;
+  if (n_dst_batches <= 0 || rows_take <= 0 || src_rows_per_batch < rows_take || row_bytes <= 0 || (row_bytes & 15) || bdiv <= 0 ||
+      batch_off < 0 || src_batch_off < 0 || batch_off / bdiv < src_batch_off)
+    return RR_ERR_BAD_SHAPE;
+  return op_status(rr_launch_gather_rows(src, dst, n_dst_batches, rows_take, src_rows_per_batch, row_bytes, batch_off, bdiv,
+                                         src_batch_off, (hipStream_t)hip_stream));
+}
+static int rr_op_cls_heads_impl(const float* h32, int T, int cols, int n_pairs, const float* w1, const float* b1, const float* w2,
+                                const float* b2, float* out1, float* out2, void* hip_stream) {
+  if (!h32 || !w1 || !b1 || !w2 || !out1 || (out2 && !b2)) return RR_ERR_BAD_ARG;
+  if (!op_aligned(h32, 16) || !op_aligned(w1, 16) || !op_aligned(w2, 16)) return RR_ERR_BAD_ARG;
+  if (T <= 0 || n_pairs <= 0 || cols <= 0 || (cols & 3)) return RR_ERR_BAD_SHAPE;
+  return op_status(rr_launch_cls_heads(h32, T, cols, n_pairs, w1, b1, w2, b2, out1, out2, (hipStream_t)hip_stream));
+}
+static int rr_op_ln_finalize_impl(const float* part, int nparts, int cols, float eps, int rows, float* stats, int* range_flag,
+                                  float range_ss, void* hip_stream) {
+  if (!part || !stats || !op_aligned(part, 8) || !op_aligned(stats, 8)) return RR_ERR_BAD_ARG;
+  if (rows <= 0 || cols <= 0 || nparts != (cols + 127) / 128) return RR_ERR_BAD_SHAPE;
+  return op_status(rr_launch_ln_finalize(part, nparts, cols, eps, rows, stats, (hipStream_t)hip_stream, range_flag, range_ss));
+}
+
 
 // ---- the exported entry points: bodies above, run through guarded() so that no C++ exception crosses the ABI
 int rr_create(const rr_config* cfg, rr_handle* out) {
@@ -2702,6 +2806,53 @@ int64_t rr_workspace_bytes(rr_handle h, int n_pairs, int seq_len) {
 }
 int64_t rr_debug_read(rr_handle h, const char* name, float* host_out, int64_t max_elems) {
   return guarded<int64_t>(h, [&]() -> int64_t { return rr_debug_read_impl(h, name, host_out, max_elems); });
+}
+int rr_op_embed_ln(const int64_t* ids, const int64_t* tts, const float* word, const float* pos, const float* type, const float* gamma,
+                   const float* beta, float eps, int rows, int S, int cols, int vocab, int type_vocab, float* out_f32, uint16_t* out16,
+                   void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_embed_ln_impl(ids, tts, word, pos, type, gamma, beta, eps, rows, S, cols, vocab, type_vocab, out_f32, out16, hip_stream); });
+}
+int rr_op_ce_embed_ln(const float* x, const float* pos, const float* type0, const float* gamma, const float* beta, float eps, int rows,
+                      int T, int cols, float* out_f32, uint16_t* out16, int s_text, int vis_pos0, int cls32, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_ce_embed_ln_impl(x, pos, type0, gamma, beta, eps, rows, T, cols, out_f32, out16, s_text, vis_pos0, cls32, hip_stream); });
+}
+int rr_op_li_normalize(const float* src, const int64_t* ids, int ids_stride, int n_pairs, int rows_per_batch, int D, int T, int t_off,
+                       int pair_off, int bdiv, int src_batch_off, uint16_t* dst, int normalize, const float* maskf, int split, int shift,
+                       void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_li_normalize_impl(src, ids, ids_stride, n_pairs, rows_per_batch, D, T, t_off, pair_off, bdiv, src_batch_off, dst, normalize, maskf, split, shift, hip_stream); });
+}
+int rr_op_key_bias(const int64_t* ids, const int64_t* am, int n, int S, int T, float* text_bias, float* ce_bias, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_key_bias_impl(ids, am, n, S, T, text_bias, ce_bias, hip_stream); });
+}
+int rr_op_joint_masks(const int64_t* ids, const int64_t* am, int n, int S, int P, int q_len, int64_t instruction_token, float* text_bias,
+                      float* li_mask, float* ce_bias, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_joint_masks_impl(ids, am, n, S, P, q_len, instruction_token, text_bias, li_mask, ce_bias, hip_stream); });
+}
+int rr_op_interaction_bias(const float* qmask, const float* cmask, int n, int Lq, int Lc, int pair_off, int K, float* cat_bias,
+                           float* q_bias, float* c_bias, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_interaction_bias_impl(qmask, cmask, n, Lq, Lc, pair_off, K, cat_bias, q_bias, c_bias, hip_stream); });
+}
+int rr_op_vit_im2col(const float* px, uint16_t* out, int B, int IS, int ps, int Kp, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_vit_im2col_impl(px, out, B, IS, ps, Kp, hip_stream); });
+}
+int rr_op_vit_embed_ln(const float* patches, const float* cls_emb, const float* pos, const float* gamma, const float* beta, float eps,
+                       int rows, int T, int cols, float* out_f32, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_vit_embed_ln_impl(patches, cls_emb, pos, gamma, beta, eps, rows, T, cols, out_f32, hip_stream); });
+}
+int rr_op_cast16(const float* x, uint16_t* y, int64_t n, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_cast16_impl(x, y, n, hip_stream); });
+}
+int rr_op_gather_rows(const void* src, void* dst, int n_dst_batches, int rows_take, int src_rows_per_batch, int row_bytes, int batch_off,
+                      int bdiv, int src_batch_off, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_gather_rows_impl(src, dst, n_dst_batches, rows_take, src_rows_per_batch, row_bytes, batch_off, bdiv, src_batch_off, hip_stream); });
+}
+int rr_op_cls_heads(const float* h32, int T, int cols, int n_pairs, const float* w1, const float* b1, const float* w2, const float* b2,
+                    float* out1, float* out2, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_cls_heads_impl(h32, T, cols, n_pairs, w1, b1, w2, b2, out1, out2, hip_stream); });
+}
+int rr_op_ln_finalize(const float* part, int nparts, int cols, float eps, int rows, float* stats, int* range_flag, float range_ss,
+                      void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_ln_finalize_impl(part, nparts, cols, eps, rows, stats, range_flag, range_ss, hip_stream); });
 }
 
 }  // extern "C"

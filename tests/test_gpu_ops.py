@@ -403,7 +403,8 @@ def test_production_split_epilogue_is_bit_exact(lib, dt, K, lo8):
         lib.rr_set_tuning(b"resid_lo8", -1)
 
 
-@pytest.mark.parametrize("rows,cols", [(1, 128), (7, 768), (1000, 768), (33, 1024), (5, 64)])
+@pytest.mark.parametrize("rows,cols", [(1, 128), (7, 768), (1000, 768), (33, 1024), (5, 64),
+                                       (5, 4), (9, 260), (4097, 2044), (13, 2048)])    # MAX_V4 edges: 1 and 65 float4s, 511 and 512
 def test_layernorm(lib, rows, cols):
     g = torch.Generator().manual_seed(rows + cols)
     x = (torch.randn(rows, cols, generator=g) * 3 + 0.5).cuda()
@@ -417,6 +418,18 @@ def test_layernorm(lib, rows, cols):
     ref = torch.nn.functional.layer_norm(x, (cols,), gamma, beta, 1e-12)
     assert torch.allclose(o32, ref, atol=2e-6, rtol=1e-5)
     assert torch.equal(o16, o32.bfloat16())
+    # the fp16 operand type: the same fp32 rows, rounded to fp16 bit for bit
+    assert lib.rr_set_op_dtype(1) == 0
+    try:
+        h32 = torch.empty_like(x)
+        h16 = torch.empty(rows, cols, dtype=torch.float16, device="cuda")
+        assert lib.rr_op_layernorm(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), 1e-12, rows, cols, h32.data_ptr(),
+                                   h16.data_ptr(), _stream()) == 0
+        torch.cuda.synchronize()
+    finally:
+        lib.rr_set_op_dtype(0)
+    assert torch.equal(h32, o32)
+    assert torch.equal(h16.view(torch.int16), o32.half().view(torch.int16))
 
 
 def test_fp16_operand_ops(lib):

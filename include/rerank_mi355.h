@@ -289,6 +289,25 @@ int rr_assemble_pairs(rr_handle h, const int32_t* pool, int64_t pool_len, const 
                       int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int64_t cls_id, int64_t sep_id,
                       int64_t pad_id, int64_t* input_ids, int64_t* attention_mask, int64_t* token_type_ids, void* hip_stream);
 
+/* rr_assemble_joint: the joint rows of rr_forward_joint_packed built on the device from compact tokens, instead of the
+ * reference's cat(query_input_ids, context_input_ids[:, 2 : 2 - query_len]) over padded rows (RerankModel.forward,
+ * rerank_model.py:191-222, on tokenize_retrieved_docs' [N, 512] output, Reranker_base_executor.py:1056-1066).
+ * pool: DEVICE int32 [pool_len], holding every query's query_len ids followed by its query_len attention-mask values (as the
+ * dataset gives them), and the context runs of rr_tok_prepare_contexts_compact; desc: HOST int32 [n_pairs, 3] (query offset,
+ * context offset, m) in pair order: the query's ids at pool[qoff .. qoff + query_len), its mask behind them, the context's
+ * t[0:m] at pool[coff .. coff + m); order / n_segments / seg_pairs / seg_len as rr_assemble_pairs takes them.  Writes
+ * joint_input_ids / joint_attention_mask (DEVICE int64, sum_s seg_pairs[s] * seg_len[s] entries, packed as rr_forward_joint_packed
+ * reads them): q_ids | the first padded_seq_len - query_len entries of t[0:m] [SEP] [PAD]..., mask q_mask | 1 ... 1 | 0 ..., cut
+ * to the segment's length.  A pair's real length is query_len + min(m + 1, padded_seq_len - query_len) (a passage that fills
+ * its window loses the [SEP], as in the reference).  Checked on the host BEFORE anything is enqueued: 0 < query_len <
+ * padded_seq_len, every seg_len in (query_len, padded_seq_len] and at least min(padded_seq_len, cross_attn_len) (the
+ * preconditions of rr_forward_joint_packed), order a permutation, non-negative offsets and m, the query's 2 * query_len values
+ * and the context run inside the pool, every pair's real length within its segment's; any violation returns RR_ERR_BAD_SHAPE and
+ * writes nothing.  The library stages the descriptors itself; enqueued on hip_stream; not capturable into a graph. */
+int rr_assemble_joint(rr_handle h, const int32_t* pool, int64_t pool_len, const int32_t* desc, int n_pairs, const int32_t* order,
+                      int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int query_len, int padded_seq_len,
+                      int64_t sep_id, int64_t pad_id, int64_t* joint_input_ids, int64_t* joint_attention_mask, void* hip_stream);
+
 /* rr_forward: one pass of the hot path over N = Bq*K (query,candidate) pairs.
  *   input_ids, attention_mask, token_type_ids : DEVICE int64 [N,S] row-major, query-major pair order
  *       (prepare_full_context_inputs, utils.py:129-167).  attention_mask masks keys in the text
@@ -461,6 +480,17 @@ int rr_tok_prepare_pairs(rr_tokenizer_handle h, const char* const* queries, int 
 int rr_tok_prepare_compact(rr_tokenizer_handle h, const char* const* queries, int n_queries, const char* const* contexts,
                            int docs_per_query, int max_query_length, int max_context_length, int max_length, int n_threads,
                            int32_t* pool, int64_t pool_capacity, int64_t* pool_needed, int32_t* desc);
+/* Context-encoder tokenisation in COMPACT form, for rr_assemble_joint; replaces FLMRContextEncoderTokenizer.__call__
+ * (tokenization_flmr.py:120-150: ". " + text, padding="max_length", truncation=True, ids[:, 1] = [unused1]) as
+ * tokenize_retrieved_docs calls it (Reranker_base_executor.py:1056-1066).  Writes each context's t[0:min(len(t), max_tokens)],
+ * t = encode(text) without special tokens, once into pool (int32, pool_capacity entries, context order), and offsets[i] /
+ * lengths[i] (int32 [n_contexts]); with max_tokens = max_length - 3 the reference's row is [CLS] [unused1] t[0:m] [SEP] [PAD]...
+ * (the "." of the prefix is always a token of its own).  *pool_needed = the entries the pool needs; when that exceeds
+ * pool_capacity the call returns RR_ERR_BAD_SHAPE and writes neither pool, offsets nor lengths.  n_threads as
+ * rr_tok_prepare_pairs. */
+int rr_tok_prepare_contexts_compact(rr_tokenizer_handle h, const char* const* contexts, int n_contexts, int max_tokens,
+                                    int n_threads, int32_t* pool, int64_t pool_capacity, int64_t* pool_needed, int32_t* offsets,
+                                    int32_t* lengths);
 
 /* Profiling: when on, rr_forward brackets every kernel launch with HIP events on the work
  * stream; rr_get_profile synchronises, accumulates and returns the per-class totals. */

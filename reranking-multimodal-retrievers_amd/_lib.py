@@ -66,6 +66,8 @@ _SIGS = {
     "rr_forward_packed": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
     "rr_assemble_pairs": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P,
                                     _P]),
+    "rr_assemble_joint": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P,
+                                    _P]),
     "rr_forward_joint_packed": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_float, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int64,
                                           _P, _P, _P]),
     "rr_forward_interaction_packed": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_float, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P,
@@ -122,6 +124,8 @@ _SIGS = {
                                        C.c_int, C.c_int, _P, _P, _P]),
     "rr_tok_prepare_compact": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64), _P]),
+    "rr_tok_prepare_contexts_compact": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _P, C.c_int64,
+                                                  C.POINTER(C.c_int64), _P, _P]),
     "rr_op_layernorm_stats": (C.c_int, [_P, _P, _P, C.c_float, C.c_int, C.c_int, _P, _P, _P, _P]),
     "rr_op_gemm_ln_resid_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rr_op_gemm_resid_lnprep": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, _P]),

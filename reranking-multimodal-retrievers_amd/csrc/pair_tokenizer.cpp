@@ -561,4 +561,56 @@ int rr_tok_prepare_compact(rr_tokenizer_handle h, const char* const* queries, in
   }
 }
 
+// Context-encoder tokenisation in compact form (include/rerank_mi355.h): the ids t[0:min(len, max_tokens)] of every context,
+// where t is the WordPiece encoding of the text, written once into an int32 pool, with a per-context offset and length.  The
+// reference's FLMRContextEncoderTokenizer (tokenization_flmr.py:120-150) encodes ". " + text and overwrites the "." with the
+// [D] marker: BasicTokenizer's whitespace and punctuation splits make that "." a token of its own in front of t, so the row
+// it pads is [CLS] [D] t[0:m] [SEP], m = min(len(t), max_length - 3).  rr_assemble_joint builds the joint rows from the pool.
+int rr_tok_prepare_contexts_compact(rr_tokenizer_handle h, const char* const* contexts, int n_contexts, int max_tokens,
+                                    int n_threads, int32_t* pool, int64_t pool_capacity, int64_t* pool_needed, int32_t* offsets,
+                                    int32_t* lengths) {
+  try {
+    if (!h || !contexts || !offsets || !lengths || !pool_needed || pool_capacity < 0 || (!pool && pool_capacity))
+      return RR_ERR_BAD_ARG;
+    *pool_needed = 0;
+    if (n_contexts <= 0 || max_tokens < 0) return RR_ERR_BAD_SHAPE;
+    const size_t N = (size_t)n_contexts;
+    for (size_t i = 0; i < N; ++i) if (!contexts[i]) return RR_ERR_BAD_ARG;
+    if (n_threads <= 0) n_threads = (int)std::max(1u, std::thread::hardware_concurrency());
+    n_threads = (int)std::min<size_t>((size_t)n_threads, N);
+
+    std::vector<std::vector<int32_t>> cids(N);
+    std::atomic<size_t> next{0};
+    auto worker = [&]() {
+      for (;;) {
+        const size_t p = next.fetch_add(1);
+        if (p >= N) break;
+        std::vector<int32_t>& c = cids[p];
+        h->encode(contexts[p], strlen(contexts[p]), c);
+        if ((int64_t)c.size() > max_tokens) c.resize((size_t)max_tokens);
+      }
+    };
+    h->pool.run(n_threads, worker);
+
+    int64_t need = 0;
+    for (const auto& c : cids) need += (int64_t)c.size();
+    *pool_needed = need;
+    if (need > INT32_MAX) return RR_ERR_BAD_SHAPE;           // offsets are int32
+    if (need > pool_capacity) return RR_ERR_BAD_SHAPE;
+    int64_t o = 0;
+    for (size_t p = 0; p < N; ++p) {
+      offsets[p] = (int32_t)o;
+      lengths[p] = (int32_t)cids[p].size();
+      std::copy(cids[p].begin(), cids[p].end(), pool + o);
+      o += (int64_t)cids[p].size();
+    }
+    return RR_OK;
+
+  } catch (const std::bad_alloc&) {
+    return RR_ERR_OOM;
+  } catch (...) {
+    return RR_ERR_BAD_ARG;   // no C++ exception crosses the C ABI
+  }
+}
+
 }  // extern "C"

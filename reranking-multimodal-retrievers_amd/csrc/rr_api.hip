@@ -254,9 +254,9 @@ struct rr_model {
   hipStream_t prof_chain_st = nullptr;
   rr_profile prof{};
 
-  // rr_assemble_pairs: two staging slots for the checked descriptors (pinned host -> device), used in turn.  `done` is recorded
-  // behind the assembly launch that read the slot: the slot is refilled only after it completed.
-  struct AsmSlot { rr_asm_pair* host = nullptr; rr_asm_pair* dev = nullptr; int cap = 0; hipEvent_t done = nullptr; };
+  // rr_assemble_pairs / rr_assemble_joint: two staging slots for the checked descriptors (pinned host -> device), used in turn.
+  // `done` is recorded behind the assembly launch that read the slot: the slot is refilled only after it completed.
+  struct AsmSlot { void* host = nullptr; void* dev = nullptr; size_t cap = 0; hipEvent_t done = nullptr; };
   AsmSlot asm_slot[2];
   int asm_next = 0;
 };
@@ -1760,6 +1760,38 @@ static int packed_segments(rr_model* m, const char* what, Request& r, int min_le
   return RR_OK;
 }
 
+// The descriptor upload of rr_assemble_pairs / rr_assemble_joint: `bytes` of checked host descriptors into the next staging
+// slot (pinned), once the launch that last read that slot has completed, and an async copy to its device half on `st`.
+// asm_done records the slot's event behind the launch that reads it and hands the next call the other slot.
+static int asm_stage(rr_model* m, const char* what, const void* data, size_t bytes, hipStream_t st, void** dev) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return fail(m, RR_ERR_BAD_ARG, "%s cannot be captured into a graph (it stages its descriptors from the host)", what);
+  RR_HIP(m, hipSetDevice(m->cfg.device));
+  rr_model::AsmSlot& a = m->asm_slot[m->asm_next];
+  if (!a.done) RR_HIP(m, hipEventCreateWithFlags(&a.done, hipEventDisableTiming));
+  else RR_HIP(m, hipEventSynchronize(a.done));      // the last upload from this slot, and the launch that read it, are done
+  if (a.cap < bytes) {
+    if (a.host) { RR_HIP(m, hipHostFree(a.host)); a.host = nullptr; }
+    if (a.dev) { RR_HIP(m, hipFree(a.dev)); a.dev = nullptr; }
+    a.cap = 0;
+    const size_t cap = std::max(bytes, (size_t)1024 * sizeof(rr_asm_pair));
+    RR_HIP(m, hipHostMalloc(&a.host, cap, hipHostMallocDefault));
+    RR_HIP(m, hipMalloc(&a.dev, cap));
+    a.cap = cap;
+  }
+  memcpy(a.host, data, bytes);
+  RR_HIP(m, hipMemcpyAsync(a.dev, a.host, bytes, hipMemcpyHostToDevice, st));
+  *dev = a.dev;
+  return RR_OK;
+}
+
+static int asm_done(rr_model* m, hipStream_t st) {
+  RR_HIP(m, hipEventRecord(m->asm_slot[m->asm_next].done, st));
+  m->asm_next ^= 1;
+  return RR_OK;
+}
+
 // rr_assemble_pairs (include/rerank_mi355.h): every check on the host first, then one staged upload and one launch.
 static int rr_assemble_pairs_impl(rr_handle h, const int32_t* pool, int64_t pool_len, const int32_t* desc, int n_pairs,
                                   const int32_t* order, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len,
@@ -1801,29 +1833,66 @@ static int rr_assemble_pairs_impl(rr_handle h, const int32_t* pool, int64_t pool
       staged[(size_t)i] = rr_asm_pair{d[0], d[1], d[2], d[3], seg_len[s], (int32_t)row0, 0, 0};
     }
   hipStream_t st = (hipStream_t)hip_stream;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-    return fail(m, RR_ERR_BAD_ARG, "%s cannot be captured into a graph (it stages its descriptors from the host)", what);
-  RR_HIP(m, hipSetDevice(m->cfg.device));
-  rr_model::AsmSlot& a = m->asm_slot[m->asm_next];
-  if (!a.done) RR_HIP(m, hipEventCreateWithFlags(&a.done, hipEventDisableTiming));
-  else RR_HIP(m, hipEventSynchronize(a.done));      // the last upload from this slot, and the launch that read it, are done
-  if (a.cap < n_pairs) {
-    if (a.host) { RR_HIP(m, hipHostFree(a.host)); a.host = nullptr; }
-    if (a.dev) { RR_HIP(m, hipFree(a.dev)); a.dev = nullptr; }
-    a.cap = 0;
-    const int cap = std::max(n_pairs, 1024);
-    RR_HIP(m, hipHostMalloc((void**)&a.host, (size_t)cap * sizeof(rr_asm_pair), hipHostMallocDefault));
-    RR_HIP(m, hipMalloc((void**)&a.dev, (size_t)cap * sizeof(rr_asm_pair)));
-    a.cap = cap;
-  }
-  memcpy(a.host, staged.data(), staged.size() * sizeof(rr_asm_pair));
-  RR_HIP(m, hipMemcpyAsync(a.dev, a.host, staged.size() * sizeof(rr_asm_pair), hipMemcpyHostToDevice, st));
+  void* dev = nullptr;
+  RR_TRY(asm_stage(m, what, staged.data(), staged.size() * sizeof(rr_asm_pair), st, &dev));
   RR_RUN(m, st, RR_K_EMBED, 0.0, (double)rows * (token_type_ids ? 24.0 : 16.0) + 4.0 * (double)rows,
-         rr_launch_assemble_pairs(pool, pool_len, a.dev, n_pairs, cls_id, sep_id, pad_id, input_ids, attention_mask, token_type_ids, st));
-  RR_HIP(m, hipEventRecord(a.done, st));
-  m->asm_next ^= 1;
-  return RR_OK;
+         rr_launch_assemble_pairs(pool, pool_len, (const rr_asm_pair*)dev, n_pairs, cls_id, sep_id, pad_id, input_ids, attention_mask,
+                                  token_type_ids, st));
+  return asm_done(m, st);
+}
+
+// rr_assemble_joint (include/rerank_mi355.h): the joint family's rows, checked and staged as rr_assemble_pairs does.
+static int rr_assemble_joint_impl(rr_handle h, const int32_t* pool, int64_t pool_len, const int32_t* desc, int n_pairs,
+                                  const int32_t* order, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int query_len,
+                                  int padded_seq_len, int64_t sep_id, int64_t pad_id, int64_t* joint_input_ids,
+                                  int64_t* joint_attention_mask, void* hip_stream) {
+  const char* what = "rr_assemble_joint";
+  if (!h) return RR_ERR_BAD_ARG;
+  rr_model* m = h;
+  if (!desc || !order || !seg_pairs || !seg_len || !joint_input_ids || !joint_attention_mask || (!pool && pool_len > 0))
+    return fail(m, RR_ERR_BAD_ARG, "%s: null argument", what);
+  const int ql = query_len, S = padded_seq_len;
+  if (pool_len < 0 || n_pairs <= 0 || n_segments <= 0 || n_segments > 64 || ql <= 0 || S <= ql)
+    return fail(m, RR_ERR_BAD_SHAPE, "%s: pool_len=%lld, %d pairs, %d segments (1..64), query_len %d, padded length %d", what,
+                (long long)pool_len, n_pairs, n_segments, ql, S);
+  const int floor_len = std::min(S, m->cfg.cross_attn_len);   // the mapping network's cross-attention window
+  long long pairs = 0, rows = 0;
+  for (int s = 0; s < n_segments; ++s) {
+    if (seg_pairs[s] <= 0 || seg_len[s] <= ql || seg_len[s] < floor_len || seg_len[s] > S)
+      return fail(m, RR_ERR_BAD_SHAPE, "%s: segment %d holds %d pairs of length %d (lengths in (%d, %d], at least %d)", what, s,
+                  seg_pairs[s], seg_len[s], ql, S, floor_len);
+    pairs += seg_pairs[s];
+    rows += (long long)seg_pairs[s] * seg_len[s];
+  }
+  if (pairs != n_pairs || rows > INT32_MAX)
+    return fail(m, RR_ERR_BAD_SHAPE, "%s: the segments hold %lld pairs (%lld rows), the call has %d", what, pairs, rows, n_pairs);
+  std::vector<char> seen((size_t)n_pairs, 0);
+  for (int i = 0; i < n_pairs; ++i) {
+    const int32_t p = order[i];
+    if (p < 0 || p >= n_pairs || seen[(size_t)p]) return fail(m, RR_ERR_BAD_SHAPE, "%s: order is not a permutation (entry %d = %d)", what, i, p);
+    seen[(size_t)p] = 1;
+  }
+  const int ctx_w = S - ql;
+  std::vector<rr_asm_joint> staged((size_t)n_pairs);
+  int i = 0;
+  long long row0 = 0;
+  for (int s = 0; s < n_segments; ++s)
+    for (int k = 0; k < seg_pairs[s]; ++k, ++i, row0 += seg_len[s]) {
+      const int32_t* d = desc + 3 * (size_t)order[i];
+      const long long real = (long long)ql + std::min((long long)d[2] + 1, (long long)ctx_w);
+      if (d[0] < 0 || d[1] < 0 || d[2] < 0 || (long long)d[0] + 2LL * ql > pool_len || (long long)d[1] + d[2] > pool_len ||
+          real > seg_len[s])
+        return fail(m, RR_ERR_BAD_SHAPE, "%s: pair %d (query offset %d, context offset %d, m %d) does not fit a pool of %lld ids and "
+                    "its segment's length %d", what, order[i], d[0], d[1], d[2], (long long)pool_len, seg_len[s]);
+      staged[(size_t)i] = rr_asm_joint{d[0], ql, d[1], d[2], ctx_w, seg_len[s], (int32_t)row0, 0};
+    }
+  hipStream_t st = (hipStream_t)hip_stream;
+  void* dev = nullptr;
+  RR_TRY(asm_stage(m, what, staged.data(), staged.size() * sizeof(rr_asm_joint), st, &dev));
+  RR_RUN(m, st, RR_K_EMBED, 0.0, (double)rows * 16.0 + 8.0 * (double)rows,
+         rr_launch_assemble_joint(pool, pool_len, (const rr_asm_joint*)dev, n_pairs, sep_id, pad_id, joint_input_ids,
+                                  joint_attention_mask, st));
+  return asm_done(m, st);
 }
 
 // FullContextRerankModel.forward (rerank_model.py:523-591) on the tokenised pairs.  FAM_JOINT: RerankModel.forward semantics
@@ -2616,6 +2685,12 @@ int rr_assemble_pairs(rr_handle h, const int32_t* pool, int64_t pool_len, const 
   return guarded(h, [&]() -> int {
     return rr_assemble_pairs_impl(h, pool, pool_len, desc, n_pairs, order, n_segments, seg_pairs, seg_len, cls_id, sep_id, pad_id,
                                   input_ids, attention_mask, token_type_ids, hip_stream);
+  });
+}
+int rr_assemble_joint(rr_handle h, const int32_t* pool, int64_t pool_len, const int32_t* desc, int n_pairs, const int32_t* order, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int query_len, int padded_seq_len, int64_t sep_id, int64_t pad_id, int64_t* joint_input_ids, int64_t* joint_attention_mask, void* hip_stream) {
+  return guarded(h, [&]() -> int {
+    return rr_assemble_joint_impl(h, pool, pool_len, desc, n_pairs, order, n_segments, seg_pairs, seg_len, query_len, padded_seq_len,
+                                  sep_id, pad_id, joint_input_ids, joint_attention_mask, hip_stream);
   });
 }
 int rr_forward_joint(rr_handle h, const int64_t* joint_input_ids, const int64_t* joint_attention_mask, const float* image_cls, const float* image_patches, int Bq, int K, int S, int query_len, int64_t instruction_token_id, int pair_begin, int pair_end, float* logits_out, float* logits2_out, float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream) {

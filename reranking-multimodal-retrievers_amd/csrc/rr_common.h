@@ -426,3 +426,10 @@ hipError_t rr_launch_layernorm(const float* x, const float* gamma, const float* 
 struct rr_asm_pair { int32_t qoff, la, coff, lb, len, row0, unused0, unused1; };
 hipError_t rr_launch_assemble_pairs(const int32_t* pool, long long pool_len, const rr_asm_pair* pairs, int n_pairs, long long cls,
                                     long long sep, long long pad, int64_t* ids, int64_t* am, int64_t* tt, hipStream_t st);
+
+// rr_assemble_joint: one packed pair of the joint family as the host stages it (descriptor checked against pool and segment;
+// the query's ql ids then its ql mask values at qoff, the context run t[0:m] at coff, ctx_w = padded length - ql the context
+// window of the joint row, row0 = its first entry in the packed rows, len = its segment's length)
+struct rr_asm_joint { int32_t qoff, ql, coff, m, ctx_w, len, row0, unused0; };
+hipError_t rr_launch_assemble_joint(const int32_t* pool, long long pool_len, const rr_asm_joint* pairs, int n_pairs, long long sep,
+                                    long long pad, int64_t* ids, int64_t* am, hipStream_t st);

@@ -450,6 +450,70 @@ class RerankEngine:
         return self._packed(launch, (), lengths, int(padded_len), floor, granule, segment_cost_rows, Bq, K, labels, want_loss,
                             want_scores, want_order, host_order=True)
 
+    def assemble_joint(self, pool: torch.Tensor, desc, order, seg_n: Sequence[int], seg_len: Sequence[int], query_len: int,
+                       padded_len: int, special_ids: Sequence[int]):
+        """rr_assemble_joint: the packed int64 (joint_input_ids, joint_attention_mask) rows of rr_forward_joint_packed, built on
+        the device from compact tokens.  `pool`: int32 device tensor holding every query's `query_len` ids then its
+        `query_len` mask values, and the context runs of NativePairTokenizer.prepare_contexts_compact; `desc`: host int32
+        [N, 3] (query offset, context offset, m); `order` / `seg_n` / `seg_len`: the packed order and segment table;
+        `padded_len`: the padded joint length (max_decoder_source_length); `special_ids`: the tokenizer's (cls, sep, pad).
+        Row of a pair: q_ids | the first padded_len - query_len entries of t[0:m] [SEP] [PAD]..., mask q_mask | 1 | 0, cut to its
+        segment.  A descriptor outside the pool or longer than its segment, or a segment table rr_forward_joint_packed would
+        refuse, raises ValueError before anything is written."""
+        import numpy as np
+        dev = self.device
+        if pool.dtype != torch.int32 or pool.device != dev or not pool.is_contiguous():
+            raise ValueError("pool must be a contiguous int32 tensor on the model device")
+        desc = np.ascontiguousarray(desc, dtype=np.int32)
+        order = np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
+        if desc.ndim != 2 or desc.shape[1] != 3 or desc.shape[0] != order.shape[0]:
+            raise ValueError("desc must be [N, 3] with one order entry per pair")
+        rows = sum(int(n) * int(l) for n, l in zip(seg_n, seg_len))
+        ids, am = (torch.empty(rows, dtype=torch.int64, device=dev) for _ in range(2))
+        _, sep_id, pad_id = (int(x) for x in special_ids)
+        rc = self.lib.rr_assemble_joint(self.h, L.ptr(pool), pool.numel(), desc.ctypes.data, desc.shape[0], order.ctypes.data,
+                                        len(seg_n), (C.c_int32 * len(seg_n))(*seg_n), (C.c_int32 * len(seg_n))(*seg_len),
+                                        int(query_len), int(padded_len), sep_id, pad_id, L.ptr(ids), L.ptr(am), self._stream())
+        if rc == L.RR_ERR_BAD_SHAPE:        # a bad descriptor is a bad argument of this call, not an expanded-batch mismatch
+            raise ValueError(f"rr_assemble_joint: {self.lib.rr_last_error(self.h).decode()}")
+        L.check(rc, self.h, "rr_assemble_joint")
+        return ids, am
+
+    def forward_joint_tokens_packed(self, pool: torch.Tensor, desc, Bq: int, K: int, query_len: int, image_cls: torch.Tensor,
+                                    image_patches: torch.Tensor, instruction_token_id: Optional[int] = None, granule: int = 16,
+                                    segment_cost_rows: int = 0, want_scores: bool = False, want_order: bool = False,
+                                    want_loss: bool = True, padded_len: int = 512, special_ids: Sequence[int] = (101, 102, 0)):
+        """forward_joint_packed from COMPACT tokens (see assemble_joint): the pool on the device, the descriptors on the host,
+        the joint rows assembled on the device where forward_joint_packed packs padded rows with pack_rows.  `image_cls` /
+        `image_patches` are PER QUERY ([Bq, ...]: the ViT runs once per query) and expanded per pair in packed order on the
+        device.  A pair's length is query_len + min(m + 1, padded_len - query_len), what forward_joint_packed derives from the
+        padded rows, so the grouping, the rows and the logits are those of forward_joint_packed on the same inputs, bit for
+        bit.  The head is rr_head_joint (loss_fn(logits, logits), rerank_model.py:328).  Returns the dict of
+        forward_joint_packed."""
+        import numpy as np
+        if image_cls is None or image_patches is None:
+            raise NotImplementedError("text_only is not implemented for this model")        # rerank_model.py:184-185
+        desc = np.ascontiguousarray(desc, dtype=np.int32)
+        N, ql, S = Bq * K, int(query_len), int(padded_len)
+        assert desc.shape == (N, 3), f"expanded batch {Bq}*{K} != {desc.shape[0]}"
+        if image_cls.shape[0] != Bq or image_patches.shape[0] != Bq:
+            raise AssertionError("image features must be per query: [Bq, ...]")
+        lengths = ql + np.minimum(desc[:, 2].astype(np.int64) + 1, S - ql)
+        floor = max(ql + 1, min(S, int(self.arch.get("cross_attn_len", 32))))
+        f32 = dict(device=self.device, dtype=torch.float32)
+        instr = -1 if instruction_token_id is None else int(instruction_token_id)
+
+        def launch(order, seg_n, seg_len, sn, sl, lp, lp2, order_h):
+            ids_p, am_p = self.assemble_joint(pool, desc, order_h, seg_n, seg_len, ql, S, special_ids)
+            q = torch.div(order, K, rounding_mode="floor")             # image features per pair: a segment mixes queries
+            cls_p = image_cls.to(**f32).index_select(0, q).contiguous()
+            pat_p = image_patches.to(**f32).index_select(0, q).contiguous()
+            L.check(self.lib.rr_forward_joint_packed(self.h, L.ptr(ids_p), L.ptr(am_p), L.ptr(cls_p), L.ptr(pat_p), None, 1.0,
+                                                     len(seg_n), sn, sl, S, ql, instr, L.ptr(lp), L.ptr(lp2), self._stream()),
+                    self.h, "rr_forward_joint_packed")
+        return self._packed(launch, (), lengths, S, floor, granule, segment_cost_rows, Bq, K, None, want_loss, want_scores,
+                            want_order, joint=True, host_order=True)
+
     def activation_range_exceeded(self, reset: bool = True) -> bool:
         """True when, since the last reset, a pre-LayerNorm residual row came within a factor 2 of the fp16 range (or was
         not finite) — rr_activation_range_flag; synchronises the current stream, so call it once per batch group, not per
@@ -894,7 +958,10 @@ class RerankModel(_DropIn):
     only.  Extra optional config keys: `arch`, `image_feature_fn` (pixel_values -> (cls, patches)),
     `instruction_token_id` (id of `mask_instruction_token`, rerank_model.py:161-169; None = no instruction masking),
     `packed_rows` (default False: `forward` runs over packed rows, RerankEngine.forward_joint_packed; pass `lengths=` with the
-    joint sequences' lengths to spare the device -> host copy; calls with `pair_range` stay padded)."""
+    joint sequences' lengths to spare the device -> host copy; calls with `pair_range` stay padded), `decoder_tokenizer` (the
+    executor's context tokenizer, an HF-style BERT tokenizer: the vocabulary of `native_tokenizer`, which
+    rerank_dataset_pipelined tokenises the retrieved passages with) and `max_decoder_source_length` (the context rows'
+    padded length; must equal the text encoder's max_pos, as `forward` asserts)."""
 
     def __init__(self, config, state_dict: Optional[Dict[str, torch.Tensor]] = None, device=None):
         super().__init__()
@@ -903,6 +970,15 @@ class RerankModel(_DropIn):
         self.image_feature_fn = _get(config, "image_feature_fn", None)
         self.instruction_token_id = _get(config, "instruction_token_id", None)
         self.packed_rows = bool(_get(config, "packed_rows", False))
+        self.max_decoder_source_length = int(_get(config, "max_decoder_source_length", self.engine.arch["max_pos"]))
+        assert self.max_decoder_source_length == self.engine.arch["max_pos"], \
+            f"max_decoder_source_length {self.max_decoder_source_length} != max_pos {self.engine.arch['max_pos']}"   # :202
+        self.decoder_tokenizer = _get(config, "decoder_tokenizer", None)
+        self.native_tokenizer = None
+        if self.decoder_tokenizer is not None:
+            from .pair_inputs import NativePairTokenizer
+            self.native_tokenizer = NativePairTokenizer(self.decoder_tokenizer,
+                                                        do_lower_case=getattr(self.decoder_tokenizer, "do_lower_case", True))
         self.context_vision_encoder = _FrozenStub()
         if state_dict is not None:
             self.engine.load_state_dict(state_dict)

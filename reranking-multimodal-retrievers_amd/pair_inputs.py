@@ -149,6 +149,44 @@ class NativePairTokenizer:
             buf = torch.empty(need.value + need.value // 4, dtype=torch.int32, pin_memory=pin_memory)   # grow, tokenise again
         raise ValueError(f"rr_tok_prepare_compact failed ({rc}, pool needs {need.value})")
 
+    def prepare_contexts_compact(self, context_text_sequences: List[str], max_tokens: int, out: Optional[torch.Tensor] = None,
+                                 pin_memory: bool = True):
+        """rr_tok_prepare_contexts_compact: the context encoder's tokens (FLMRContextEncoderTokenizer, see
+        flmr_context_inputs) without padded rows.  Returns (pool, offsets, lengths): `pool` an int32 host tensor (a view of
+        `out` when it is large enough, else of a new buffer, pinned when `pin_memory`) holding every context's
+        t[0:min(len(t), max_tokens)] once, in context order; `offsets` / `lengths` int32 numpy [n] into it.  With max_tokens =
+        max_length - 3 the reference's padded row of context i is [CLS] [unused1] t[0:lengths[i]] [SEP] [PAD]..."""
+        import numpy as np
+        C = self._C
+        n = len(context_text_sequences)
+        c = (C.c_char_p * n)(*[t.encode("utf-8", "replace") for t in context_text_sequences])
+        offsets, lengths = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        need = C.c_int64(0)
+        threads = self.n_threads if self.n_threads > 0 else host_threads()
+        buf = out if out is not None else torch.empty(max(1, n * int(max_tokens)), dtype=torch.int32, pin_memory=pin_memory)
+        for _ in range(2):
+            assert buf.dtype == torch.int32 and buf.is_contiguous()
+            rc = self.lib.rr_tok_prepare_contexts_compact(self.h, c, n, int(max_tokens), threads, buf.data_ptr(), buf.numel(),
+                                                          C.byref(need), offsets.ctypes.data, lengths.ctypes.data)
+            if rc == 0:
+                return buf[:need.value], offsets, lengths
+            if rc != self._L.RR_ERR_BAD_SHAPE or need.value <= buf.numel():
+                break
+            buf = torch.empty(need.value + need.value // 4, dtype=torch.int32, pin_memory=pin_memory)   # grow, tokenise again
+        raise ValueError(f"rr_tok_prepare_contexts_compact failed ({rc}, pool needs {need.value})")
+
+
+def flmr_context_inputs(context_text_sequences: List[str], tokenizer, max_length: int = 512) -> Dict[str, torch.Tensor]:
+    """What the reference executor's `tokenize_retrieved_docs` (Reranker_base_executor.py:1056-1066) gets from its
+    `decoder_tokenizer`, FLMRContextEncoderTokenizer.__call__ (tokenization_flmr.py:120-150), on any HF-style BERT tokenizer:
+    ". " + text, padded and truncated to `max_length`, then ids[:, 1] = [unused1] (the [D] marker).  int64 [N, max_length]
+    input_ids / attention_mask: the serial path's context inputs of RerankModel.forward."""
+    enc = tokenizer([". " + t for t in context_text_sequences], padding="max_length", max_length=max_length, truncation=True,
+                    return_tensors="pt")
+    ids, mask = enc["input_ids"].to(torch.int64), enc["attention_mask"].to(torch.int64)
+    ids[:, 1] = tokenizer.convert_tokens_to_ids("[unused1]")
+    return {"input_ids": ids, "attention_mask": mask}
+
 
 def host_threads() -> int:
     """CPU threads for host-side tokenisation: the CPUs this process may run on (not os.cpu_count(), the machine's), capped by

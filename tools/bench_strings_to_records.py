@@ -9,13 +9,20 @@ spread over U[64, 512] tokens (the bench's realistic regime).  Three modes, each
                          into pinned memory; one synchronisation at the end.  The device-bound rate.
   serial_from_strings    evaluate.rerank_dataset driving FullContextRerankModel.forward (native_tokenizer, packed_rows).
   pipelined_from_strings pipeline.rerank_dataset_pipelined.
-Prints one JSON line.  Usage: python tools/bench_strings_to_records.py [--queries 64] [--warmup 16]"""
+--family joint measures the two-head RerankModel instead (the reference's monoPreFLMR-B_pointwise_softmax: loss 2H_BCE, the
+same bert-base / one-layer geometry, ViT from pixels), one line "joint": the queries carry the dataset's query ids and mask
+(32 entries) and the passages' joint lengths query_len + min(m + 1, 512 - query_len) spread over U[64, 512]; resident_inputs
+runs forward_joint_packed on padded joint rows already on the device, serial_from_strings drives RerankModel.forward (packed
+rows) with the passages tokenised and padded per batch, pipelined_from_strings is rerank_dataset_pipelined (JointStages).
+Prints one JSON line.  Usage: python tools/bench_strings_to_records.py [--queries 64] [--warmup 16] [--family joint]"""
 import argparse
 import json
 import os
 import random
 import sys
 import time
+
+import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
@@ -37,7 +44,7 @@ class VocabTokenizer:
         return dict(self._v)
 
 
-def make_corpus(n_queries, K, seed=0):
+def make_corpus(n_queries, K, seed=0, joint_query_len=0):
     rng = random.Random(seed)
     syll = ["ka", "to", "mi", "ra", "ne", "so", "lu", "vi", "en", "or", "th", "st", "ing", "ed", "er", "al", "pre", "con"]
     words = sorted({"".join(rng.choice(syll) for _ in range(rng.randint(1, 3))) for _ in range(4000)})
@@ -54,9 +61,15 @@ def make_corpus(n_queries, K, seed=0):
         docs = []
         for k in range(K):
             target = rng.randint(64, 512)                                             # pair length, [CLS] q [SEP] c [SEP]
-            docs.append({"passage_id": f"p{i}_{k}", "content": text(max(0, round((target - ql - 3) / per_word)))})
+            overhead = joint_query_len + 1 if joint_query_len else ql + 3             # joint: q_ids (padded) t [SEP]
+            docs.append({"passage_id": f"p{i}_{k}", "content": text(max(0, round((target - overhead) / per_word)))})
         queries.append({"question_id": f"q{i}", "question": q, "retrieved_docs": docs,
                         "pos_item_ids": [docs[j]["passage_id"] for j in rng.sample(range(K), 3)], "neg_item_ids": []})
+        if joint_query_len:                               # the dataset's query tokens: [CLS] q [SEP], padded to max_query_length
+            ids = [vocab.index("[CLS]")] + tok.encode(q)[:joint_query_len - 2] + [vocab.index("[SEP]")]
+            pad = joint_query_len - len(ids)
+            queries[-1]["query_input_ids"] = torch.tensor(ids + [0] * pad)
+            queries[-1]["query_attention_mask"] = torch.tensor([1] * len(ids) + [0] * pad)
     return vocab, queries
 
 
@@ -156,6 +169,108 @@ def run_line(vocab, queries, vision, args, dev):
     return out
 
 
+# ---- the joint family (RerankModel) ------------------------------------------------------------------------------------
+
+def build_joint_model(vocab, dev):
+    conf = dict(cross_encoder_num_hidden_layers=1, cross_encoder_max_position_embeddings=750, loss_fn="2H_BCE", pos_weight=None,
+                max_decoder_source_length=512, compute_dtype="fp16", vision_encoder=True, decoder_tokenizer=VocabTokenizer(vocab),
+                packed_rows=True)
+    sd = rmr_amd.synthetic_state_dict(rmr_amd.make_arch(conf), seed=0, hf_init=True)
+    m = rmr_amd.RerankModel(conf, state_dict=sd, device=dev)
+    m.native_tokenizer.n_threads = host_threads()
+    return m
+
+
+def padded_contexts(m, texts):
+    """tokenize_retrieved_docs' padded rows ([CLS] [unused1] t [SEP] [PAD]..., int64 [N, 512]) from the native tokenizer."""
+    tok, S = m.native_tokenizer, m.max_decoder_source_length
+    cls, sep, pad = tok.special_ids
+    d_marker = tok.vocab.index("[unused1]")
+    pool, off, ln = tok.prepare_contexts_compact(texts, S - 3, pin_memory=False)
+    pool = pool.numpy()
+    ids = np.full((len(texts), S), pad, dtype=np.int64)
+    am = np.zeros((len(texts), S), dtype=np.int64)
+    for i, (o, n) in enumerate(zip(off.tolist(), ln.tolist())):
+        ids[i, 0], ids[i, 1], ids[i, 2:2 + n], ids[i, 2 + n] = cls, d_marker, pool[o:o + n], sep
+        am[i, :n + 3] = 1
+    return torch.from_numpy(ids), torch.from_numpy(am)
+
+
+def joint_serial_forward(m, K):
+    def fwd(batch):
+        c_ids, c_am = padded_contexts(m, [d["content"] for q in batch for d in q["retrieved_docs"]])
+        r = m(torch.stack([q["query_input_ids"] for q in batch]), torch.stack([q["query_attention_mask"] for q in batch]),
+              torch.stack([q["pixel_values"] for q in batch]), c_ids, c_am, K - 1)
+        logits = r.logits.view(len(batch), K).tolist()
+        return {"logits": logits, "order": [rank_descending_stable(x) for x in logits], "loss": r.loss.item()}
+    return fwd
+
+
+def joint_resident(m, batches, K):
+    """Padded joint rows, their host lengths and the pixels on the device beforehand; the timed part queues the ViT,
+    forward_joint_packed, the head and the pinned read-backs."""
+    eng, dev = m.engine, m.engine.device
+    prepared = []
+    for b in batches:
+        q_ids = torch.stack([q["query_input_ids"] for q in b])
+        q_am = torch.stack([q["query_attention_mask"] for q in b])
+        ql = q_ids.shape[1]
+        c_ids, c_am = padded_contexts(m, [d["content"] for q in b for d in q["retrieved_docs"]])
+        ids = torch.cat([q_ids.repeat_interleave(K, 0), c_ids[:, 2:2 - ql]], 1)
+        am = torch.cat([q_am.repeat_interleave(K, 0), c_am[:, 2:2 - ql]], 1)
+        lengths = (((ids != 0) | (am != 0)) * torch.arange(1, ids.shape[1] + 1)).amax(1)
+        prepared.append((ids.to(dev), am.to(dev), lengths.numpy(), torch.stack([q["pixel_values"] for q in b]).to(dev), ql, len(b)))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    keep = []
+    for ids, am, lengths, px, ql, n in prepared:
+        cls, pat = eng.encode_image(px)
+        r = eng.forward_joint_packed(ids, am, n, K, ql, cls, pat, None, want_order=True, lengths=lengths)
+        lh = torch.empty((n, K), dtype=torch.float32, pin_memory=True).copy_(r["logits"].view(n, K), non_blocking=True)
+        oh = torch.empty((n, K), dtype=torch.int32, pin_memory=True).copy_(r["order"], non_blocking=True)
+        keep.append((r, lh, oh))
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def run_joint_line(vocab, queries, args, dev):
+    K, B = args.K, args.batch
+    m = build_joint_model(vocab, dev)
+    g = torch.Generator().manual_seed(3)
+    for q in queries:
+        q["pixel_values"] = 1.2 * torch.randn(3, 224, 224, generator=g)
+    warm, timed = queries[:args.warmup], queries[args.warmup:]
+    Ks = [1, 5, 10, K]
+    rmr_amd.rerank_dataset(warm, joint_serial_forward(m, K), B, Ks, docs_to_rerank=K)
+    rmr_amd.rerank_dataset_pipelined(warm, m, B, Ks, docs_to_rerank=K)
+    joint_resident(m, [warm[i:i + B] for i in range(0, len(warm), B)], K)
+    nb = -(-len(timed) // B)
+    out = {}
+    t = joint_resident(m, [timed[i:i + B] for i in range(0, len(timed), B)], K)
+    out["resident_inputs"] = dict(queries_per_s=round(len(timed) / t, 2), ms_per_batch=round(t * 1e3 / nb, 3))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ser = rmr_amd.rerank_dataset(timed, joint_serial_forward(m, K), B, Ks, docs_to_rerank=K)
+    t = time.perf_counter() - t0
+    out["serial_from_strings"] = dict(queries_per_s=round(len(timed) / t, 2), ms_per_batch=round(t * 1e3 / nb, 3))
+    stats = {}
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    pip = rmr_amd.rerank_dataset_pipelined(timed, m, B, Ks, docs_to_rerank=K, stats=stats)
+    t = time.perf_counter() - t0
+    out["pipelined_from_strings"] = dict(queries_per_s=round(len(timed) / t, 2), ms_per_batch=round(t * 1e3 / nb, 3),
+                                         host_tokenise_ms_per_batch=round(stats["tokenise_ms"] / stats["batches"], 3),
+                                         host_records_ms_per_batch=round(stats["records_ms"] / stats["batches"], 3))
+    out["pipelined_over_resident"] = round(out["pipelined_from_strings"]["queries_per_s"] / out["resident_inputs"]["queries_per_s"], 4)
+    out["serial_over_resident"] = round(out["serial_from_strings"]["queries_per_s"] / out["resident_inputs"]["queries_per_s"], 4)
+    out["records_identical"] = json.dumps(ser["output"]) == json.dumps(pip["output"])
+    out["metrics_identical"] = ser["metrics"] == pip["metrics"]
+    ql = int(timed[0]["query_input_ids"].numel())
+    lens = [ql + min(len(m.native_tokenizer.encode(d["content"])) + 1, 512 - ql) for q in timed[:2] for d in q["retrieved_docs"]]
+    out["mean_pair_tokens_sample"] = round(sum(lens) / len(lens), 1)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--queries", type=int, default=64, help="timed queries per mode (after the warm-up)")
@@ -163,9 +278,19 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--K", type=int, default=100)
     ap.add_argument("--lines", default="vision,text_only")
+    ap.add_argument("--family", choices=["full_context", "joint"], default="full_context",
+                    help="full_context: FullContextRerankModel (--lines); joint: the two-head RerankModel, one line")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
+    if args.family == "joint":
+        vocab, queries = make_corpus(args.warmup + args.queries, args.K, joint_query_len=32)
+        res = {"tool": "bench_strings_to_records", "family": "joint", "shape": f"c3 bert-base, RerankModel 2H_BCE, K={args.K}, "
+               f"{args.batch} queries/batch, fp16, packed joint rows granule 16, query_len 32, joint lengths U[64, 512], ViT from "
+               "pixels", "queries_timed": args.queries, "host_threads": host_threads(), "gpu": torch.cuda.get_device_name(dev),
+               "joint": run_joint_line(vocab, queries, args, dev)}
+        print(json.dumps(res))
+        return
     vocab, queries = make_corpus(args.warmup + args.queries, args.K)
     res = {"tool": "bench_strings_to_records", "shape": f"c3 bert-base, K={args.K}, {args.batch} queries/batch, fp16, packed rows "
            "granule 16, pair lengths U[64, 512]", "queries_timed": args.queries, "host_threads": host_threads(),

@@ -451,6 +451,37 @@ int rr_forward_interaction_packed(rr_handle h, const float* query_li, const floa
 int rr_head_joint(rr_handle h, const float* logits, const float* logits2, int Bq, int K, float* loss_out, float* scores_out,
                   int32_t* order_out, void* hip_stream);
 
+/* rr_head_lists: rr_head / rr_head_joint over a LIST LAYOUT: n_lists lists, list q holding k_q >= 1 candidates (at most 4096,
+ * as K of rr_head), pairs stored list after list, N = sum k_q.  The reference reranks one query per forward and takes whatever
+ * its retriever returned for it (src/executors/Reranker_base_executor.py:807-976), so lists of unequal length work there query
+ * by query; this is the head that lets several of them share one forward here.  No reference counterpart as one call.
+ * (Python: RerankEngine.head_lists.)
+ *   list_offsets : HOST int32 [n_lists + 1], offsets[q] = k_0 + ... + k_{q-1}, offsets[n_lists] = N.  Checked before anything
+ *       is enqueued: offsets[0] == 0 and strictly ascending (no empty list), else RR_ERR_BAD_SHAPE; a list above 4096
+ *       RR_ERR_UNSUPPORTED, as rr_head answers K > 4096.  A refused call writes nothing.  May be reused when the call returns.
+ *   logits / logits2 : DEVICE float32 [N] (logits2: the first head, 2H_BCE only, as for rr_head).
+ *   gather : DEVICE int32 [N] or NULL.  Pair p's logits are read at logits[gather[p]] (and logits2[gather[p]]); NULL = p.  With
+ *       the inverse of a packed forward's pair order the head consumes the logits in packed order, without the scatter in
+ *       between.  Must hold indices in [0, N); the array is on the device and is not checked.
+ *   labels : DEVICE float32 [N] in pair order (never gathered) or NULL = the first candidate of EVERY list is the positive
+ *       (src/models/rerank/utils.py:239-243, per list).  joint = 1 ignores it.
+ *   joint : 0 = rr_head's loss; 1 = rr_head_joint's (the logits are their own targets, read through the same gather).
+ *   loss_out : DEVICE float32 scalar or NULL.  The per-list partial sums and weights reduced in list order, as rr_head reduces
+ *       its per-query partials: BCE kinds and the joint loss = the mean over all N pairs (what the reference's loss function
+ *       returns for the concatenated logits), negative_sampling = the mean over lists of CE(target = the list's first
+ *       candidate) (the mean of what the reference computes query by query), weighted 2H_BCE = weight-normalised over all pairs.
+ *   list_loss_out : DEVICE float32 [n_lists] or NULL: list q's own loss, what rr_head returns for that list alone (Bq = 1).
+ *   scores_out : DEVICE float32 [N] or NULL, pair order.  order_out : DEVICE int32 [N] or NULL: list q's descending, retrieval-
+ *       order-stable rank at order_out[offsets[q] .. offsets[q + 1]), as indices LOCAL to the list (0 .. k_q - 1).
+ * With offsets = [0, K, 2K, ...], gather = NULL, loss_out, scores_out and order_out hold rr_head's (joint = 1: rr_head_joint's)
+ * bits for (Bq, K): the same arithmetic in the same order (tests/test_gpu_lists.py).  Every combination rr_head / rr_head_joint
+ * reject is rejected in the same way (labels with negative_sampling, 2H_BCE without logits2, joint on an interaction handle,
+ * joint with negative_sampling and a loss).  The library stages the offsets itself, through the slots rr_assemble_pairs uses;
+ * enqueued on hip_stream; NOT capturable into a graph (RR_ERR_BAD_ARG under stream capture). */
+int rr_head_lists(rr_handle h, const float* logits, const float* logits2, const float* labels, int n_lists,
+                  const int32_t* list_offsets, const int32_t* gather, int joint, float* loss_out, float* list_loss_out,
+                  float* scores_out, int32_t* order_out, void* hip_stream);
+
 /* ---- Host-side pair-input assembly (no GPU involved): WordPiece tokenisation of the (query, candidate) texts into the
  * int64 [N, S] tensors rr_forward takes.  Replaces prepare_full_context_inputs (src/models/rerank/utils.py:129-167) and
  * the BertTokenizer encode / decode / batch_encode_plus calls under it (transformers 4.38.2 slow tokenizer semantics).

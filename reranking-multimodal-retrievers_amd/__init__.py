@@ -10,7 +10,7 @@ Importing the package does not need a GPU; constructing a model does (no CPU fal
 from ._lib import EXPORTED, LIB_PATH  # noqa: F401
 from .model import (FullContextRerankModel, InteractionRerankModel, RerankModel, RerankEngine, RerankOutput, make_arch,  # noqa: F401
                     synthetic_state_dict, weight_spec)
-from .sharding import shard_range, ShardedReranker  # noqa: F401
+from .sharding import shard_range, ShardedReranker, sharded_forward_lists  # noqa: F401
 from .ranking import rank_descending_stable, recall_precision_at_k  # noqa: F401
 from .evaluate import build_records, compute_rerank_scores, rerank_dataset  # noqa: F401
 from .pipeline import rerank_dataset_pipelined  # noqa: F401

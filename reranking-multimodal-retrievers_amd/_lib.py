@@ -85,6 +85,7 @@ _SIGS = {
                                                 C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "rr_head": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "rr_head_joint": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "rr_head_lists": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "rr_debug_read": (C.c_int64, [_P, C.c_char_p, _P, C.c_int64]),
     "rr_set_debug": (C.c_int, [_P, C.c_int]),
     "rr_set_profiling": (C.c_int, [_P, C.c_int]),

@@ -43,6 +43,8 @@ hipError_t rr_launch_cls_heads(const float*, int, int, int, const float*, const 
                                float*, float*, hipStream_t);
 hipError_t rr_launch_head(const float*, const float*, const float*, int, int, int, float, int, float*, int32_t*,
                           float*, float*, float*, hipStream_t);
+hipError_t rr_launch_head_lists(const float*, const float*, const float*, int, const int32_t*, const int32_t*, int, int, int,
+                                float, int, float*, int32_t*, float*, float*, float*, float*, hipStream_t);
 hipError_t rr_attention_reserve(int B, int heads, int Tq, hipStream_t st);
 
 namespace {
@@ -1685,6 +1687,51 @@ static int head_call(rr_handle h, const char* what, bool joint, const float* log
   return launch_head(h, st, w, logits, logits2, labels, Bq, K, joint, loss_out, scores_out, order_out);
 }
 
+static int asm_stage(rr_model* m, const char* what, const void* data, size_t bytes, hipStream_t st, void** dev);
+static int asm_done(rr_model* m, hipStream_t st);
+
+// rr_head_lists (include/rerank_mi355.h): the scoring head over lists of unequal length.  Every check on the host first; then
+// the offsets go up through the staging slots of rr_assemble_pairs, with the per-list partials behind them in the same block:
+// [offsets: n_lists + 1 | part_loss: n_lists | part_w: n_lists], so nothing here is sized by a query count of the workspace.
+// Sharing the two slots means that this call waits, on the host, for the launch that read its slot two staged calls ago: in
+// the pipelined loop (assemble, head, assemble, head, ...) that is the previous batch's head, i.e. the host runs at most one
+// batch ahead of the device, which is what that loop does anyway (profiles/strings_to_records_lists_ragged.json.log).
+static int head_lists_call(rr_handle h, const float* logits, const float* logits2, const float* labels, int n_lists,
+                           const int32_t* off, const int32_t* gather, int joint, float* loss_out, float* list_loss_out,
+                           float* scores_out, int32_t* order_out, void* hip_stream) {
+  const char* what = "rr_head_lists";
+  if (!h) return RR_ERR_BAD_ARG;
+  if (!logits || !off) return fail(h, RR_ERR_BAD_ARG, "%s: null argument", what);
+  if (n_lists <= 0 || n_lists > (1 << 24)) return fail(h, RR_ERR_BAD_SHAPE, "%s: %d lists", what, n_lists);
+  if (off[0] != 0) return fail(h, RR_ERR_BAD_SHAPE, "%s: list_offsets[0] = %d, not 0", what, off[0]);
+  int longest = 0;
+  for (int q = 0; q < n_lists; ++q) {
+    if (off[q + 1] <= off[q])
+      return fail(h, RR_ERR_BAD_SHAPE, "%s: list %d is empty or descending (offsets %d, %d)", what, q, off[q], off[q + 1]);
+    longest = std::max(longest, off[q + 1] - off[q]);
+  }
+  const rr_config& c = h->cfg;
+  if (joint && c.model_kind != RR_MODEL_FULL_CONTEXT) return fail(h, RR_ERR_BAD_ARG, "%s: joint = 1 on an interaction model", what);
+  const float* loss_any = loss_out ? loss_out : list_loss_out;
+  RR_TRY(check_head(h, what, 1, longest, 0, longest, labels, logits2, loss_any, scores_out, order_out, joint != 0));
+  const int N = off[n_lists];
+  hipStream_t st = (hipStream_t)hip_stream;
+  std::vector<int32_t> staged((size_t)3 * n_lists + 1, 0);
+  std::copy(off, off + n_lists + 1, staged.begin());
+  void* dev = nullptr;
+  RR_TRY(asm_stage(h, what, staged.data(), staged.size() * sizeof(int32_t), st, &dev));
+  const int32_t* off_d = (const int32_t*)dev;
+  float* part_l = (float*)(off_d + n_lists + 1);
+  float* part_w = part_l + n_lists;
+  const bool two = c.loss_kind == RR_LOSS_2H_BCE;
+  const int has_pw = !std::isnan(c.pos_weight);
+  RR_RUN(h, st, RR_K_HEAD, 0.0, 12.0 * N,
+         rr_launch_head_lists(logits, two ? logits2 : nullptr, joint ? nullptr : labels, joint != 0, off_d, gather, n_lists, N,
+                              (joint && two) ? 3 : c.loss_kind, has_pw ? c.pos_weight : 1.0f, has_pw, scores_out, order_out,
+                              loss_out, list_loss_out, part_l, part_w, st));
+  return asm_done(h, st);
+}
+
 // Sticky range error (include/rerank_mi355.h, rr_activation_range_flag): look at what the PREVIOUS forwards left in the pinned
 // word (no synchronisation: a copy still in flight simply reports one call later), refuse to go on once it is raised.
 static int range_guard_enter(rr_model* m) {
@@ -2659,6 +2706,9 @@ int rr_encode_image(rr_handle h, const float* pixel_values, int B, float* image_
 // the forwards: the arguments into one Request (forward_full / forward_interaction)
 int rr_head(rr_handle h, const float* logits, const float* logits2, const float* labels, int Bq, int K, float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream) {
   return guarded(h, [&]() -> int { return head_call(h, "rr_head", false, logits, logits2, labels, Bq, K, loss_out, scores_out, order_out, hip_stream); });
+}
+int rr_head_lists(rr_handle h, const float* logits, const float* logits2, const float* labels, int n_lists, const int32_t* list_offsets, const int32_t* gather, int joint, float* loss_out, float* list_loss_out, float* scores_out, int32_t* order_out, void* hip_stream) {
+  return guarded(h, [&]() -> int { return head_lists_call(h, logits, logits2, labels, n_lists, list_offsets, gather, joint, loss_out, list_loss_out, scores_out, order_out, hip_stream); });
 }
 int rr_head_joint(rr_handle h, const float* logits, const float* logits2, int Bq, int K, float* loss_out, float* scores_out, int32_t* order_out, void* hip_stream) {
   return guarded(h, [&]() -> int { return head_call(h, "rr_head_joint", true, logits, logits2, nullptr, Bq, K, loss_out, scores_out, order_out, hip_stream); });

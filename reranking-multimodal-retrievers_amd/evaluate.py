@@ -22,11 +22,14 @@ from typing import Callable, Dict, Iterable, List, Optional, Sequence
 from .ranking import recall_precision_at_k
 
 
-def build_records(queries: Sequence[dict], logits, order, loss: float) -> List[dict]:
+def build_records(queries: Sequence[dict], logits, order, loss) -> List[dict]:
     """One reference-schema record per query.  `queries[i]` = {"question_id", "retrieved_docs": [{"passage_id",
     "content"}, ...] (retrieval order), "pos_item_ids", optional "neg_item_ids"/"question"/"answers"/"gold_answer"}.
-    `logits[i][k]` is the score of retrieved doc k, `order[i]` its descending stable rank (device or host)."""
+    `logits[i][k]` is the score of retrieved doc k, `order[i]` its descending stable rank (device or host); the rows may
+    differ in length (ragged batches).  `loss`: the batch's loss, recorded for every query, or one loss per query."""
     out = []
+    per_query = None if isinstance(loss, (int, float)) else [float(x) for x in loss]
+    assert per_query is None or len(per_query) == len(queries), "one loss per query"
     for qi, q in enumerate(queries):
         docs = q["retrieved_docs"]
         row = [float(x) for x in logits[qi]]
@@ -40,7 +43,7 @@ def build_records(queries: Sequence[dict], logits, order, loss: float) -> List[d
                                          for d in docs],
             "pos_item_ids": list(q["pos_item_ids"]),
             "neg_item_ids": list(q.get("neg_item_ids", [])),
-            "loss": float(loss),
+            "loss": float(loss) if per_query is None else per_query[qi],
         }
         for k in ("answers", "gold_answer", "question"):
             if q.get(k) is not None:
@@ -64,11 +67,36 @@ def compute_rerank_scores(records: Sequence[dict], Ks: Sequence[int], field: str
     return res
 
 
+def cut_lists(queries: Iterable[dict], most: Optional[int]):
+    """The queries of a ragged loop: a list longer than `most` is cut to it (a shallow copy; the caller's dict is untouched)."""
+    for q in queries:
+        docs = q["retrieved_docs"]
+        assert len(docs) >= 1, f"query {q.get('question_id')}: no retrieved docs"
+        yield dict(q, retrieved_docs=docs[:most]) if most is not None and len(docs) > most else q
+
+
+def split_lists(flat, sizes: Sequence[int]) -> List[list]:
+    """A flat per-pair sequence as one row per list."""
+    out, o = [], 0
+    for k in sizes:
+        out.append(list(flat[o:o + k]))
+        o += k
+    assert o == len(flat), "the list sizes do not cover the flat values"
+    return out
+
+
 def rerank_dataset(queries: Iterable[dict], forward_batch: Callable[[List[dict]], dict], batch_queries: int,
-                   Ks: Sequence[int], docs_to_rerank: Optional[int] = None, out_path: Optional[str] = None) -> dict:
+                   Ks: Sequence[int], docs_to_rerank: Optional[int] = None, out_path: Optional[str] = None,
+                   ragged: bool = False) -> dict:
     """The evaluate_outputs loop (Reranker_base_executor.py:785-1030), `batch_queries` queries per forward.
     Returns {"metrics": {...}, "output": [records]}; optionally writes the reference's
-    `{..}_predictions_rank_{r}.json` payload (`{"output": [...]}`, :1113-1126)."""
+    `{..}_predictions_rank_{r}.json` payload (`{"output": [...]}`, :1113-1126).
+    `ragged`: a batch is the next `batch_queries` queries whatever the lengths of their retrieved lists; `docs_to_rerank`
+    (if given) is the most a list may hold and longer lists are cut to it.  `forward_batch` then returns `logits` and `order`
+    either as one row per query or flat over the batch's pairs (order local to each list), and `loss` as one value per query
+    (`list_loss`) or a scalar: each record carries its own list's loss, as the reference's one-query loop records it."""
+    if ragged:
+        queries = cut_lists(queries, docs_to_rerank)
     if docs_to_rerank is not None:
         assert docs_to_rerank == max(Ks), "The number of retrieved documents must be equal to the maximum K."   # :806-808
     records: List[dict] = []
@@ -80,6 +108,19 @@ def rerank_dataset(queries: Iterable[dict], forward_batch: Callable[[List[dict]]
         r = forward_batch(batch)
         logits = r["logits"].tolist() if hasattr(r["logits"], "tolist") else r["logits"]
         order = r["order"].tolist() if hasattr(r["order"], "tolist") else r["order"]
+        if ragged:
+            sizes = [len(q["retrieved_docs"]) for q in batch]
+            rows = len(logits) == len(batch) and all(isinstance(x, (list, tuple)) for x in logits) and \
+                [len(x) for x in logits] == sizes
+            if not rows:                                                                     # flat over the batch's pairs
+                logits = split_lists([x[0] if isinstance(x, (list, tuple)) else x for x in logits], sizes)   # [N, 1] or [N]
+            if not isinstance(order[0], (list, tuple)):
+                order = split_lists(order, sizes)
+            loss = r["list_loss"] if r.get("list_loss") is not None else r["loss"]
+            loss = loss.tolist() if hasattr(loss, "tolist") else loss
+            records.extend(build_records(batch, logits, order, loss))
+            batch.clear()
+            return
         records.extend(build_records(batch, logits, order, float(r["loss"])))
         batch.clear()
 

@@ -364,7 +364,8 @@ class RerankEngine:
                            Bq: int, K: int, image_cls: Optional[torch.Tensor] = None,
                            image_patches: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
                            granule: int = 16, want_scores: bool = False, want_order: bool = False,
-                           lengths: Optional[Sequence[int]] = None, segment_cost_rows: int = 0, want_loss: bool = True):
+                           lengths: Optional[Sequence[int]] = None, segment_cost_rows: int = 0, want_loss: bool = True,
+                           list_sizes: Optional[Sequence[int]] = None, pair_lists=None):
         """The same result as `forward_ids` on right-padded pairs, computed over PACKED rows (rr_forward_packed): the pairs are
         grouped by their length rounded up to a multiple of `granule` and laid out group after group, so that every GEMM /
         LayerNorm pass of a layer runs once over the rows that exist — the reference pads every pair to
@@ -376,9 +377,11 @@ class RerankEngine:
         the HOST knows them from the tokenizer (pair_inputs.prepare_full_context_inputs keeps them); without it they are
         derived on the device and the group counts cost one device -> host copy per call, which drains the stream between
         two forwards.  `segment_cost_rows`: merge neighbouring lengths where a segment's fixed launches cost more than the rows
-        the merge pads (pair_inputs.group_pairs_by_length).  Returns the dict of forward_ids plus `packed_rows`, `packed_segments`."""
+        the merge pads (pair_inputs.group_pairs_by_length).  `list_sizes` / `pair_lists` in place of (Bq, K) (pass None for both):
+        lists of unequal length, or a slice of them (see `_packed`).  Returns the dict of forward_ids plus `packed_rows`,
+        `packed_segments`."""
         N, S = input_ids.shape
-        assert N == Bq * K
+        Bq, K, pair_query = self._layout(N, Bq, K, list_sizes, pair_lists)
         floor = int(self.arch.get("cross_attn_len", 32)) if image_cls is not None else 1   # the mapping network's cross-attention window
 
         def launch(order, seg_n, seg_len, sn, sl, lp, lp2):
@@ -386,13 +389,13 @@ class RerankEngine:
             tt_p = pack_rows(token_type_ids, order, seg_n, seg_len) if token_type_ids is not None else None
             cls_p = pat_p = None
             if image_cls is not None:                                   # per pair: a group mixes candidates of several queries
-                q = torch.div(order, K, rounding_mode="floor")
+                q = pair_query(order)
                 cls_p = image_cls.index_select(0, q).float().contiguous()
                 pat_p = image_patches.index_select(0, q).float().contiguous()
             L.check(self.lib.rr_forward_packed(self.h, L.ptr(ids_p), L.ptr(am_p), L.ptr(tt_p), L.ptr(cls_p), L.ptr(pat_p), len(seg_n),
                                                sn, sl, S, L.ptr(lp), L.ptr(lp2), self._stream()), self.h, "rr_forward_packed")
         return self._packed(launch, (input_ids, attention_mask), lengths, S, floor, granule, segment_cost_rows, Bq, K, labels,
-                            want_loss, want_scores, want_order)
+                            want_loss, want_scores, want_order, list_sizes=list_sizes, pair_lists=pair_lists, n_pairs=N)
 
     def assemble_pairs(self, pool: torch.Tensor, desc, order, seg_n: Sequence[int], seg_len: Sequence[int], special_ids: Sequence[int],
                        with_token_types: bool = True):
@@ -424,7 +427,8 @@ class RerankEngine:
     def forward_tokens_packed(self, pool: torch.Tensor, desc, Bq: int, K: int, image_cls: Optional[torch.Tensor] = None,
                               image_patches: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
                               granule: int = 16, segment_cost_rows: int = 0, want_scores: bool = False, want_order: bool = False,
-                              want_loss: bool = True, padded_len: int = 512, special_ids: Sequence[int] = (101, 102, 0)):
+                              want_loss: bool = True, padded_len: int = 512, special_ids: Sequence[int] = (101, 102, 0),
+                              list_sizes: Optional[Sequence[int]] = None):
         """forward_ids_packed from COMPACT tokens (NativePairTokenizer.prepare_compact): the pool on the device, the
         descriptors on the host, the rows assembled on the device by rr_assemble_pairs where forward_ids_packed packs padded
         rows with pack_rows.  `padded_len` is the length the padded call would use (max_decoder_source_length), `special_ids`
@@ -432,8 +436,9 @@ class RerankEngine:
         the same logits: bit for bit for text-only models.  Returns the dict of forward_ids_packed."""
         import numpy as np
         desc = np.ascontiguousarray(desc, dtype=np.int32)
-        N = Bq * K
+        N = Bq * K if list_sizes is None else int(sum(list_sizes))
         assert desc.shape == (N, 4), f"expanded batch {Bq}*{K} != {desc.shape[0]}"
+        Bq, K, pair_query = self._layout(N, Bq, K, list_sizes, None)
         lengths = desc[:, 1].astype(np.int64) + desc[:, 3] + 3
         floor = int(self.arch.get("cross_attn_len", 32)) if image_cls is not None else 1
 
@@ -441,14 +446,14 @@ class RerankEngine:
             ids_p, am_p, tt_p = self.assemble_pairs(pool, desc, order_h, seg_n, seg_len, special_ids)
             cls_p = pat_p = None
             if image_cls is not None:                                   # per pair: a group mixes candidates of several queries
-                q = torch.div(order, K, rounding_mode="floor")
+                q = pair_query(order)
                 cls_p = image_cls.index_select(0, q).float().contiguous()
                 pat_p = image_patches.index_select(0, q).float().contiguous()
             L.check(self.lib.rr_forward_packed(self.h, L.ptr(ids_p), L.ptr(am_p), L.ptr(tt_p), L.ptr(cls_p), L.ptr(pat_p), len(seg_n),
                                                sn, sl, int(padded_len), L.ptr(lp), L.ptr(lp2), self._stream()), self.h,
                     "rr_forward_packed")
         return self._packed(launch, (), lengths, int(padded_len), floor, granule, segment_cost_rows, Bq, K, labels, want_loss,
-                            want_scores, want_order, host_order=True)
+                            want_scores, want_order, host_order=True, list_sizes=list_sizes, n_pairs=N)
 
     def assemble_joint(self, pool: torch.Tensor, desc, order, seg_n: Sequence[int], seg_len: Sequence[int], query_len: int,
                        padded_len: int, special_ids: Sequence[int]):
@@ -482,7 +487,8 @@ class RerankEngine:
     def forward_joint_tokens_packed(self, pool: torch.Tensor, desc, Bq: int, K: int, query_len: int, image_cls: torch.Tensor,
                                     image_patches: torch.Tensor, instruction_token_id: Optional[int] = None, granule: int = 16,
                                     segment_cost_rows: int = 0, want_scores: bool = False, want_order: bool = False,
-                                    want_loss: bool = True, padded_len: int = 512, special_ids: Sequence[int] = (101, 102, 0)):
+                                    want_loss: bool = True, padded_len: int = 512, special_ids: Sequence[int] = (101, 102, 0),
+                                    list_sizes: Optional[Sequence[int]] = None):
         """forward_joint_packed from COMPACT tokens (see assemble_joint): the pool on the device, the descriptors on the host,
         the joint rows assembled on the device where forward_joint_packed packs padded rows with pack_rows.  `image_cls` /
         `image_patches` are PER QUERY ([Bq, ...]: the ViT runs once per query) and expanded per pair in packed order on the
@@ -494,8 +500,9 @@ class RerankEngine:
         if image_cls is None or image_patches is None:
             raise NotImplementedError("text_only is not implemented for this model")        # rerank_model.py:184-185
         desc = np.ascontiguousarray(desc, dtype=np.int32)
-        N, ql, S = Bq * K, int(query_len), int(padded_len)
+        N, ql, S = (Bq * K if list_sizes is None else int(sum(list_sizes))), int(query_len), int(padded_len)
         assert desc.shape == (N, 3), f"expanded batch {Bq}*{K} != {desc.shape[0]}"
+        Bq, K, pair_query = self._layout(N, Bq, K, list_sizes, None)
         if image_cls.shape[0] != Bq or image_patches.shape[0] != Bq:
             raise AssertionError("image features must be per query: [Bq, ...]")
         lengths = ql + np.minimum(desc[:, 2].astype(np.int64) + 1, S - ql)
@@ -505,14 +512,14 @@ class RerankEngine:
 
         def launch(order, seg_n, seg_len, sn, sl, lp, lp2, order_h):
             ids_p, am_p = self.assemble_joint(pool, desc, order_h, seg_n, seg_len, ql, S, special_ids)
-            q = torch.div(order, K, rounding_mode="floor")             # image features per pair: a segment mixes queries
+            q = pair_query(order)                                     # image features per pair: a segment mixes queries
             cls_p = image_cls.to(**f32).index_select(0, q).contiguous()
             pat_p = image_patches.to(**f32).index_select(0, q).contiguous()
             L.check(self.lib.rr_forward_joint_packed(self.h, L.ptr(ids_p), L.ptr(am_p), L.ptr(cls_p), L.ptr(pat_p), None, 1.0,
                                                      len(seg_n), sn, sl, S, ql, instr, L.ptr(lp), L.ptr(lp2), self._stream()),
                     self.h, "rr_forward_joint_packed")
         return self._packed(launch, (), lengths, S, floor, granule, segment_cost_rows, Bq, K, None, want_loss, want_scores,
-                            want_order, joint=True, host_order=True)
+                            want_order, joint=True, host_order=True, list_sizes=list_sizes, n_pairs=N)
 
     def activation_range_exceeded(self, reset: bool = True) -> bool:
         """True when, since the last reset, a pre-LayerNorm residual row came within a factor 2 of the fp16 range (or was
@@ -610,7 +617,7 @@ class RerankEngine:
                              instruction_token_id: Optional[int] = None, want_scores: bool = False, want_order: bool = False,
                              want_loss: bool = True, preflmr_scores: Optional[torch.Tensor] = None,
                              fusion_multiplier: float = 1.0, granule: int = 16, lengths: Optional[Sequence[int]] = None,
-                             segment_cost_rows: int = 0):
+                             segment_cost_rows: int = 0, list_sizes: Optional[Sequence[int]] = None, pair_lists=None):
         """`forward_joint` over PACKED rows (rr_forward_joint_packed): the pairs are grouped by the length of their joint
         sequence (1 + last non-pad position of the joint ids / mask) rounded up to `granule`, at least query_len + 1 and the
         mapping network's cross-attention window, and laid out group after group, so that the text encoder and the cross
@@ -621,7 +628,7 @@ class RerankEngine:
         packed.  Returns the dict of forward_joint plus `packed_rows`, `packed_segments`."""
         dev = self.device
         N, S = joint_input_ids.shape
-        assert N == Bq * K
+        Bq, K, pair_query = self._layout(N, Bq, K, list_sizes, pair_lists)
         if image_cls is None or image_patches is None:
             raise NotImplementedError("text_only is not implemented for this model")        # rerank_model.py:184-185
         ql = int(query_len)
@@ -636,7 +643,7 @@ class RerankEngine:
 
         def launch(order, seg_n, seg_len, sn, sl, lp, lp2):
             ids_p, am_p = pack_rows(ids, order, seg_n, seg_len), pack_rows(am, order, seg_n, seg_len)
-            q = torch.div(order, K, rounding_mode="floor")             # image features per pair: a segment mixes queries
+            q = pair_query(order)                                     # image features per pair: a segment mixes queries
             cls_p = image_cls.to(**f32).index_select(0, q).contiguous()
             pat_p = image_patches.to(**f32).index_select(0, q).contiguous()
             ps = None if preflmr_scores is None else pack_fusion_scores(preflmr_scores.to(**f32), order, 2, S - ql)
@@ -644,13 +651,14 @@ class RerankEngine:
                                                      float(fusion_multiplier), len(seg_n), sn, sl, S, ql, instr, L.ptr(lp),
                                                      L.ptr(lp2), self._stream()), self.h, "rr_forward_joint_packed")
         return self._packed(launch, (ids, am), lengths, S, floor, granule, segment_cost_rows, Bq, K, None, want_loss, want_scores,
-                            want_order, joint=True)
+                            want_order, joint=True, list_sizes=list_sizes, pair_lists=pair_lists, n_pairs=N)
 
     def forward_interaction_packed(self, query_li: torch.Tensor, context_li: torch.Tensor, query_mask: torch.Tensor,
                                    context_mask: torch.Tensor, Bq: int, K: int, labels: Optional[torch.Tensor] = None,
                                    want_scores: bool = False, want_order: bool = False, want_loss: bool = True,
                                    preflmr_scores: Optional[torch.Tensor] = None, fusion_multiplier: float = 1.0,
-                                   granule: int = 16, lengths: Optional[Sequence[int]] = None, segment_cost_rows: int = 0):
+                                   granule: int = 16, lengths: Optional[Sequence[int]] = None, segment_cost_rows: int = 0,
+                                   list_sizes: Optional[Sequence[int]] = None, pair_lists=None):
         """`forward_interaction` over PACKED rows (rr_forward_interaction_packed, NORMAL and MORES): the pairs are grouped by
         their context length (1 + last non-zero position of `context_mask`) rounded up to `granule`; NORMAL computes the
         cross-encoder rows [query | context] that exist, MORES the doc-side rows.  `preflmr_scores` [N, Lc, Lq] goes over
@@ -659,8 +667,12 @@ class RerankEngine:
         forward_interaction plus `packed_rows` (context rows computed), `packed_segments`."""
         dev = self.device
         N = context_li.shape[0]
-        assert N == Bq * K and query_li.shape[0] == Bq, \
-            f"{tuple(query_li.shape)}, {tuple(context_li.shape)}, {K - 1}"        # interaction_rerank_model.py:123
+        if list_sizes is None and pair_lists is None:
+            assert N == Bq * K and query_li.shape[0] == Bq, \
+                f"{tuple(query_li.shape)}, {tuple(context_li.shape)}, {K - 1}"        # interaction_rerank_model.py:123
+        Bq, K, pair_query = self._layout(N, Bq, K, list_sizes, pair_lists)
+        if list_sizes is not None:
+            assert query_li.shape[0] == Bq, f"{tuple(query_li.shape)}: one query per list, {Bq} lists"
         Lq, Lc = query_li.shape[1], context_li.shape[1]
         f32 = dict(device=dev, dtype=torch.float32)
         cm = context_mask.reshape(N, Lc).to(**f32).contiguous()
@@ -668,9 +680,9 @@ class RerankEngine:
             raise AssertionError(f"preflmr_scores must be [{N}, {Lc}, {Lq}], got {tuple(preflmr_scores.shape)}")
 
         def launch(order, seg_n, seg_len, sn, sl, lp, lp2):
-            q = torch.div(order, K, rounding_mode="floor")             # query tensors per pair
+            q = pair_query(order)                                     # query tensors per pair
             q_p = query_li.to(**f32).index_select(0, q).contiguous()
-            qm_p = query_mask.reshape(Bq, Lq).to(**f32).index_select(0, q).contiguous()
+            qm_p = query_mask.reshape(-1, Lq).to(**f32).index_select(0, q).contiguous()
             c_p = pack_rows(context_li.to(**f32), order, seg_n, seg_len)
             cm_p = pack_rows(cm, order, seg_n, seg_len)
             ps = None if preflmr_scores is None else pack_fusion_scores(preflmr_scores.to(**f32), order)
@@ -678,7 +690,7 @@ class RerankEngine:
                                                            float(fusion_multiplier), len(seg_n), sn, sl, Lc, Lq, L.ptr(lp),
                                                            L.ptr(lp2), self._stream()), self.h, "rr_forward_interaction_packed")
         return self._packed(launch, (cm,), lengths, Lc, 1, granule, segment_cost_rows, Bq, K, labels, want_loss, want_scores,
-                            want_order)
+                            want_order, list_sizes=list_sizes, pair_lists=pair_lists, n_pairs=N)
 
     def head(self, logits: torch.Tensor, logits2: Optional[torch.Tensor], labels: Optional[torch.Tensor], Bq: int,
              K: int, want_scores: bool = False, want_order: bool = True, want_loss: bool = True, joint: bool = False):
@@ -693,6 +705,37 @@ class RerankEngine:
             labels = labels.to(device=self.device, dtype=torch.float32).contiguous()
         L.check(self.lib.rr_head(self.h, L.ptr(logits), L.ptr(logits2), L.ptr(labels), Bq, K, *_ptrs(out), self._stream()),
                 self.h, "rr_head")
+        return out
+
+    def head_lists(self, logits: torch.Tensor, logits2: Optional[torch.Tensor], labels: Optional[torch.Tensor],
+                   list_sizes: Sequence[int], want_scores: bool = False, want_order: bool = True, want_loss: bool = True,
+                   gather: Optional[torch.Tensor] = None, joint: bool = False):
+        """The scoring head over lists of unequal length (rr_head_lists): list q holds list_sizes[q] >= 1 candidates (at most
+        4096), the pairs stored list after list.  `logits` / `logits2` [N] on the device; `gather` (int32 [N] on the device):
+        pair p's logits are read at logits[gather[p]], which lets a packed forward's logits be consumed in packed order;
+        `labels` [N] in pair order (None: the first candidate of every list is the positive); `joint`: RerankModel's loss
+        (rr_head_joint's).  Returns loss (scalar), list_loss [n_lists] (each list's own loss, what `head` gives for it alone),
+        scores [N] and order [N] int32 (each list's descending stable rank, as indices local to the list), as wanted.  An empty
+        list raises AssertionError, a list above 4096 NotImplementedError."""
+        import numpy as np
+        sizes = np.asarray(list_sizes, dtype=np.int64).reshape(-1)
+        off = np.zeros(sizes.size + 1, dtype=np.int32)
+        np.cumsum(sizes, out=off[1:])
+        N, dev = int(sizes.sum()), self.device
+        assert logits.numel() == N, f"{logits.numel()} logits for lists of {N} candidates"
+        if labels is not None:
+            labels = labels.to(device=dev, dtype=torch.float32).contiguous()
+            assert labels.numel() == N
+        if gather is not None:
+            assert gather.dtype == torch.int32 and gather.numel() == N and gather.device == dev
+        out = dict(loss=torch.empty((), dtype=torch.float32, device=dev) if want_loss else None,
+                   list_loss=torch.empty(sizes.size, dtype=torch.float32, device=dev) if want_loss else None,
+                   scores=torch.empty(N, dtype=torch.float32, device=dev) if want_scores else None,
+                   order=torch.empty(N, dtype=torch.int32, device=dev) if want_order else None)
+        L.check(self.lib.rr_head_lists(self.h, L.ptr(logits), L.ptr(logits2), None if joint else L.ptr(labels), int(sizes.size),
+                                       off.ctypes.data, L.ptr(gather), int(joint),
+                                       *[L.ptr(out[k]) for k in ("loss", "list_loss", "scores", "order")], self._stream()),
+                self.h, "rr_head_lists")
         return out
 
     # ---- plumbing shared by the forwards
@@ -716,14 +759,34 @@ class RerankEngine:
         out.update(self._head_outputs(Bq, K, full and want_loss, full and want_scores, full and want_order))
         return pb, pe, out
 
+    def _layout(self, N: int, Bq, K, list_sizes, pair_lists):
+        """(Bq, K, pair_query) of a packed forward.  Uniform: pair p belongs to query p // K.  `list_sizes`: lists of unequal
+        length, pair p belongs to the list that holds it (K is None from here on).  `pair_lists` (sharded slices): the list
+        index of each of the call's N pairs, given.  pair_query(order) is the device int64 query index of the pairs `order`."""
+        if list_sizes is None and pair_lists is None:
+            assert N == Bq * K
+            return Bq, K, lambda order: torch.div(order, K, rounding_mode="floor")
+        if pair_lists is None:
+            sizes = torch.as_tensor(list_sizes, dtype=torch.int64).reshape(-1)
+            assert sizes.numel() > 0 and int(sizes.min()) >= 1 and int(sizes.sum()) == N, \
+                f"list_sizes {sizes.tolist()} do not partition {N} pairs into non-empty lists"
+            pair_lists = torch.repeat_interleave(torch.arange(sizes.numel()), sizes)
+        table = torch.as_tensor(pair_lists, dtype=torch.int64).reshape(-1).to(self.device, non_blocking=True)
+        assert table.numel() == N, "one list index per pair"
+        return (None if list_sizes is None else len(list_sizes)), None, lambda order: table.index_select(0, order.long())
+
     def _packed(self, launch, rows, lengths, padded_len: int, floor: int, granule: int, segment_cost_rows: int, Bq: int, K: int,
-                labels, want_loss: bool, want_scores: bool, want_order: bool, joint: bool = False, host_order: bool = False) -> dict:
+                labels, want_loss: bool, want_scores: bool, want_order: bool, joint: bool = False, host_order: bool = False,
+                list_sizes=None, pair_lists=None, n_pairs: Optional[int] = None) -> dict:
         """What the packed forwards share: the pairs' lengths (`lengths` from the host, else derived from the [N, padded_len]
         tensors `rows` on the device: one device -> host copy) -> segments (group_pairs_by_length) -> the pair order on the
         device -> the ctypes segment tables -> `launch(order, seg_n, seg_len, seg_pairs, seg_lens, logits, logits2)` (with
         `host_order`, the host pair order as one more argument), which packs its inputs and makes the call -> the logits
-        scattered back to pair order -> the scoring head over them."""
-        N = Bq * K
+        scattered back to pair order -> the scoring head over them.
+        `list_sizes` in place of (Bq, K): lists of unequal length; the head is rr_head_lists over the PACKED logits with the
+        packed order's inverse as its gather, and the result also holds `list_loss`; `order` is flat [N], local to each list.
+        `pair_lists` without `list_sizes` (a rank's slice of a sharded batch): logits only, no head."""
+        N = Bq * K if n_pairs is None else n_pairs
         assert granule > 0
         if labels is not None:
             assert labels.numel() == N
@@ -737,8 +800,16 @@ class RerankEngine:
                *((order_h,) if host_order else ()))
         logits, logits2 = scatter_packed(lp, order), scatter_packed(lp2, order)
         two = self.arch["loss_fn"] == "2H_BCE"
-        out = self.head(logits, logits2 if two else None, labels, Bq, K, want_scores=want_scores, want_order=want_order,
-                        want_loss=want_loss, joint=joint)
+        if list_sizes is not None:
+            inverse = torch.empty(N, dtype=torch.int32, device=self.device)
+            inverse[order] = torch.arange(N, dtype=torch.int32, device=self.device)
+            out = self.head_lists(lp, lp2 if two else None, labels, list_sizes, want_scores=want_scores, want_order=want_order,
+                                  want_loss=want_loss, gather=inverse, joint=joint)
+        elif pair_lists is not None:
+            out = {}
+        else:
+            out = self.head(logits, logits2 if two else None, labels, Bq, K, want_scores=want_scores, want_order=want_order,
+                            want_loss=want_loss, joint=joint)
         out.update(logits=logits, logits2=logits2, packed_rows=sum(n * s for n, s in zip(seg_n, seg_len)),
                    packed_segments=len(seg_n))
         return out
@@ -823,10 +894,26 @@ class _DropIn(torch.nn.Module):
     @staticmethod
     def _output(r: dict, logits: torch.Tensor) -> RerankOutput:
         out = RerankOutput(loss=r["loss"], logits=logits)
-        for k in ("scores", "order", "logits2"):
+        for k in ("scores", "order", "logits2", "list_loss"):
             if r.get(k) is not None:
                 out[k] = r[k]
         return out
+
+    def _lists(self, candidates_per_query, N: int, kw: dict) -> List[int]:
+        """The list layout of a call with `candidates_per_query` (no such keyword in the reference, which reranks one query per
+        forward and so never meets two list lengths in one batch): packed rows only, the sizes partition the N contexts."""
+        if not self.packed_rows or kw.get("pair_range") is not None:
+            raise ValueError("candidates_per_query needs config.packed_rows = True (and no pair_range): lists of unequal length "
+                             "go through the packed forwards only")
+        sizes = [int(k) for k in candidates_per_query]
+        assert sizes and min(sizes) >= 1 and sum(sizes) == N, \
+            f"candidates_per_query {sizes} must be positive and sum to the {N} contexts"
+        kw.pop("pair_range", None)
+        kw.setdefault("want_order", True)
+        return sizes
+
+    def _flat_logits(self, r: dict) -> torch.Tensor:
+        return r["logits"] if self.engine.arch["loss_fn"] == "negative_sampling" else r["logits"].view(-1, 1)
 
     def _ranked_logits(self, r: dict, Bq: int, K: int) -> torch.Tensor:
         return r["logits"].view(Bq, K) if self.engine.arch["loss_fn"] == "negative_sampling" else r["logits"].view(Bq * K, 1)
@@ -849,6 +936,12 @@ class FullContextRerankModel(_DropIn):
       `packed_rows`     – True: `forward_ids` and the text `forward` run over packed rows (RerankEngine.forward_ids_packed; the
                           text call hands the tokenizer's pair lengths over, no device -> host copy).  Default False: padded.
                           Calls with `pair_range` (the sharded path) stay padded.
+
+    `forward` / `forward_ids` take an optional keyword `candidates_per_query` (a sequence of ints whose sum is the number of
+    contexts): query i owns the next candidates_per_query[i] contexts, `num_negative_examples` is not read, `.logits` is flat
+    ([N, 1] for the pointwise losses as today, [N] for negative_sampling) and the output carries `order` ([N] int32, each
+    query's rank as indices local to its list) and `list_loss` (each query's own loss).  It needs `packed_rows`.  The reference
+    has no such keyword: it reranks one query per forward (Reranker_base_executor.py:807-976).
     """
 
     def __init__(self, config, state_dict: Optional[Dict[str, torch.Tensor]] = None, device=None):
@@ -877,9 +970,15 @@ class FullContextRerankModel(_DropIn):
 
     # tensor fast path (synthetic benchmarks, pre-tokenised callers)
     def forward_ids(self, input_ids, attention_mask, token_type_ids, num_negative_examples: int,
-                    image_cls=None, image_patches=None, labels: Optional[List[float]] = None, **kw) -> RerankOutput:
-        K = num_negative_examples + 1
+                    image_cls=None, image_patches=None, labels: Optional[List[float]] = None, candidates_per_query=None,
+                    **kw) -> RerankOutput:
         N = input_ids.shape[0]
+        if candidates_per_query is not None:
+            sizes = self._lists(candidates_per_query, N, kw)
+            r = self.engine.forward_ids_packed(input_ids, attention_mask, token_type_ids, None, None, image_cls, image_patches,
+                                               self._labels(labels, N), list_sizes=sizes, **kw)
+            return self._output(r, self._flat_logits(r))
+        K = num_negative_examples + 1
         assert N % K == 0, "expanded batch size must be batch_size * (num_negative_examples + 1)"
         Bq = N // K
         eng = self.engine
@@ -888,10 +987,16 @@ class FullContextRerankModel(_DropIn):
         return self._output(r, self._ranked_logits(r, Bq, K))
 
     def forward(self, query_text_sequences, query_pixel_values, context_text_sequences, num_negative_examples,
-                labels=None) -> RerankOutput:
+                labels=None, candidates_per_query=None) -> RerankOutput:
         text_only = query_pixel_values is None
         batch_size = len(query_text_sequences)
-        expanded = batch_size * (num_negative_examples + 1)
+        pair_queries = query_text_sequences
+        if candidates_per_query is not None:          # every pair names its query: the tokenizers take one count per call
+            sizes = self._lists(candidates_per_query, len(context_text_sequences), {})
+            assert len(sizes) == batch_size, "one candidates_per_query entry per query"
+            pair_queries = [q for q, k in zip(query_text_sequences, sizes) for _ in range(k)]
+            num_negative_examples = 0
+        expanded = len(pair_queries) * (num_negative_examples + 1)
         assert expanded == len(context_text_sequences)                                     # rerank_model.py:527
         if labels:
             assert len(labels) == expanded
@@ -899,11 +1004,11 @@ class FullContextRerankModel(_DropIn):
             raise RuntimeError("text call signature needs config.tokenizer (an HF-style BERT tokenizer)")
         if self.native_tokenizer is not None:
             enc = self.native_tokenizer.prepare_full_context_inputs(
-                list(query_text_sequences), list(context_text_sequences), self.max_query_length, self.max_context_length,
+                list(pair_queries), list(context_text_sequences), self.max_query_length, self.max_context_length,
                 self.max_decoder_source_length, num_negative_examples + 1, pin_memory=True)
         else:
             from .pair_inputs import prepare_full_context_inputs
-            enc = prepare_full_context_inputs(query_text_sequences, context_text_sequences, self.query_tokenizer,
+            enc = prepare_full_context_inputs(pair_queries, context_text_sequences, self.query_tokenizer,
                                               self.max_query_length, self.max_context_length,
                                               self.max_decoder_source_length, num_negative_examples + 1)
         dev = self.engine.device
@@ -921,14 +1026,16 @@ class FullContextRerankModel(_DropIn):
             kw["lengths"] = pair_lengths(enc["input_ids"], enc["attention_mask"]).numpy()
         return self.forward_ids(enc["input_ids"].to(dev), enc["attention_mask"].to(dev),
                                 enc["token_type_ids"].to(dev), num_negative_examples, cls, patches,
-                                labels if labels else None, **kw)
+                                labels if labels else None, candidates_per_query=candidates_per_query, **kw)
 
 
 class InteractionRerankModel(_DropIn):
     """Drop-in for the reference's `InteractionRerankModel` (interaction_rerank_model.py:86-166), inference only:
     `config.interaction_type` "MORES" selects the MORES stack (mores_model.py), anything else the CrossEncoder.
     Optional config key `packed_rows` (default False): `forward` runs over packed rows (RerankEngine.forward_interaction_packed;
-    pass `lengths=` to spare the device -> host copy of the context lengths).  Calls with `pair_range` stay padded."""
+    pass `lengths=` to spare the device -> host copy of the context lengths).  Calls with `pair_range` stay padded.
+    `forward` takes the optional keyword `candidates_per_query` of FullContextRerankModel (lists of unequal length; needs
+    `packed_rows`; no reference counterpart)."""
 
     def __init__(self, config, state_dict: Optional[Dict[str, torch.Tensor]] = None, device=None):
         super().__init__()
@@ -941,10 +1048,17 @@ class InteractionRerankModel(_DropIn):
             self.engine.load_state_dict(state_dict)
 
     def forward(self, query_late_interaction, context_late_interaction, num_negative_examples, query_mask,
-                context_mask, preflmr_scores=None, fusion_multiplier=1, labels=None, **kw) -> RerankOutput:
-        K = num_negative_examples + 1
+                context_mask, preflmr_scores=None, fusion_multiplier=1, labels=None, candidates_per_query=None,
+                **kw) -> RerankOutput:
         Bq = query_late_interaction.size(0)
         N = context_late_interaction.size(0)
+        if candidates_per_query is not None:
+            sizes = self._lists(candidates_per_query, N, kw)
+            r = self.engine.forward_interaction_packed(
+                query_late_interaction, context_late_interaction, query_mask, context_mask, None, None, self._labels(labels, N),
+                preflmr_scores=preflmr_scores, fusion_multiplier=float(fusion_multiplier), list_sizes=sizes, **kw)
+            return self._output(r, self._flat_logits(r))
+        K = num_negative_examples + 1
         assert Bq * K == N, f"{query_late_interaction.shape}, {context_late_interaction.shape}, {num_negative_examples}"
         eng = self.engine
         r = self._route(eng.forward_interaction, eng.forward_interaction_packed, kw)(
@@ -961,7 +1075,8 @@ class RerankModel(_DropIn):
     joint sequences' lengths to spare the device -> host copy; calls with `pair_range` stay padded), `decoder_tokenizer` (the
     executor's context tokenizer, an HF-style BERT tokenizer: the vocabulary of `native_tokenizer`, which
     rerank_dataset_pipelined tokenises the retrieved passages with) and `max_decoder_source_length` (the context rows'
-    padded length; must equal the text encoder's max_pos, as `forward` asserts)."""
+    padded length; must equal the text encoder's max_pos, as `forward` asserts).  `forward` takes the optional keyword
+    `candidates_per_query` of FullContextRerankModel (lists of unequal length; needs `packed_rows`; no reference counterpart)."""
 
     def __init__(self, config, state_dict: Optional[Dict[str, torch.Tensor]] = None, device=None):
         super().__init__()
@@ -985,12 +1100,17 @@ class RerankModel(_DropIn):
 
     def forward(self, query_input_ids, query_attention_mask, query_pixel_values, context_input_ids,
                 context_attention_mask, num_negative_examples, preflmr_scores=None, fusion_multiplier=1, labels=None,
-                image_features=None, **kw) -> RerankOutput:
+                image_features=None, candidates_per_query=None, **kw) -> RerankOutput:
         if query_pixel_values is None and image_features is None:
             raise NotImplementedError("text_only is not implemented for this model")        # rerank_model.py:184-185
         K = num_negative_examples + 1
         Bq = query_input_ids.size(0)
-        N = Bq * K
+        sizes = None
+        if candidates_per_query is not None:
+            sizes = self._lists(candidates_per_query, context_input_ids.size(0), kw)
+            assert len(sizes) == Bq, "one candidates_per_query entry per query"
+            K = torch.tensor(sizes, device=self.engine.device)                              # repeats per query
+        N = Bq * K if sizes is None else sum(sizes)
         assert N == context_input_ids.size(0)                                               # :188
         if labels:
             assert len(labels) == N                                                         # :189-190
@@ -1013,6 +1133,11 @@ class RerankModel(_DropIn):
                 raise NotImplementedError("query_pixel_values given but neither config.vision_encoder nor "
                                           "config.image_feature_fn (CLIP ViT) is set")
         eng = self.engine
+        if sizes is not None:
+            r = eng.forward_joint_packed(joint_ids, joint_am, None, None, ql, cls, patches, self.instruction_token_id,
+                                         preflmr_scores=preflmr_scores, fusion_multiplier=float(fusion_multiplier),
+                                         list_sizes=sizes, **kw)
+            return self._output(r, r["logits"].view(N, 1))
         r = self._route(eng.forward_joint, eng.forward_joint_packed, kw)(
             joint_ids, joint_am, Bq, K, ql, cls, patches, self.instruction_token_id, preflmr_scores=preflmr_scores,
             fusion_multiplier=float(fusion_multiplier), **kw)

@@ -33,18 +33,20 @@ import threading
 import time
 from typing import Iterable, List, Optional, Sequence
 
-from .evaluate import build_records, compute_rerank_scores
+from .evaluate import build_records, compute_rerank_scores, cut_lists, split_lists
 
 
 class DeviceStages:
     """The device side of rerank_dataset_pipelined for a `FullContextRerankModel` (native tokenizer, packed rows)."""
 
-    def __init__(self, model, batch_queries: int, K: int, first_query: dict):
+    def __init__(self, model, batch_queries: int, K: int, first_query: dict, ragged: bool = False):
+        """`ragged`: K is the most a query's list may hold (the pinned slots are sized for batch_queries * K pairs), a batch's
+        lists may differ in length, and the host buffers are flat over the batch's pairs, beside the list sizes."""
         import torch
         from .pair_inputs import NativePairTokenizer
         self.torch = torch
         self.model, self.engine = model, model.engine
-        self.K, self.batch_queries = int(K), int(batch_queries)
+        self.K, self.batch_queries, self.ragged = int(K), int(batch_queries), bool(ragged)
         tok = model.native_tokenizer
         if tok is None:
             if model.query_tokenizer is None:
@@ -72,12 +74,16 @@ class DeviceStages:
         contexts, labels = [], []
         for q in batch:
             docs = q["retrieved_docs"]
-            assert len(docs) == K, f"query {q.get('question_id')}: {len(docs)} retrieved docs, the loop reranks {K}"
+            if self.ragged:
+                assert 1 <= len(docs) <= K, f"query {q.get('question_id')}: {len(docs)} retrieved docs, the slots hold 1..{K}"
+            else:
+                assert len(docs) == K, f"query {q.get('question_id')}: {len(docs)} retrieved docs, the loop reranks {K}"
             contexts += [d["content"] for d in docs]
             if self.pointwise:                       # Reranker_base_executor.py:830-833
                 pos = q["pos_item_ids"]
                 labels += [1.0 if d["passage_id"] in pos else 0.0 for d in docs]
         n = len(batch)
+        sizes = [len(q["retrieved_docs"]) for q in batch] if self.ragged else None
         has_px = [q.get("pixel_values") is not None for q in batch]
         assert all(has_px) or not any(has_px), "every query of a batch carries pixel_values, or none does"
         pixels = None
@@ -88,11 +94,34 @@ class DeviceStages:
                         out=pixels)
         lab = None
         if self.pointwise:
-            lab = slot["labels"][:n * K]
+            lab = slot["labels"][:len(labels)]
             lab.copy_(torch.tensor(labels, dtype=torch.float32))
+        if sizes is not None:
+            pool, desc = self._prepare_lists(batch, contexts, sizes, slot["pool"])
+            return dict(n=n, pool=pool, desc=desc, labels=lab, pixels=pixels, sizes=sizes)
         pool, desc, _ = self.tok.prepare_compact([q["question"] for q in batch], contexts, m.max_query_length, m.max_context_length,
                                                  m.max_decoder_source_length, K, out=slot["pool"], pin_memory=False)
         return dict(n=n, pool=pool, desc=desc, labels=lab, pixels=pixels)
+
+    def _prepare_lists(self, batch: List[dict], contexts: List[str], sizes: List[int], out):
+        """prepare_compact for lists of unequal length: the tokenizer takes one candidate count per call, so every query is
+        tokenised with its own list into the next part of the slot's pool, and its descriptors are moved to that part."""
+        import numpy as np
+        torch, m = self.torch, self.model
+        descs, pools, used, o, in_place = [], [], 0, 0, True
+        for q, k in zip(batch, sizes):
+            pool, desc, _ = self.tok.prepare_compact([q["question"]], contexts[o:o + k], m.max_query_length, m.max_context_length,
+                                                     m.max_decoder_source_length, k, out=out[used:], pin_memory=False)
+            in_place = in_place and pool.numel() > 0 and pool.data_ptr() == out[used:].data_ptr()
+            desc = desc.copy()
+            desc[:, 0] += used
+            desc[:, 2] += used
+            descs.append(desc)
+            pools.append(pool)
+            used += pool.numel()
+            o += k
+        pool = out[:used] if in_place else torch.cat(pools)      # (a pool the tokenizer had to grow is not in the slot)
+        return pool, np.concatenate(descs)
 
     def submit(self, batch: List[dict], item: dict) -> dict:
         torch, eng, m, dev = self.torch, self.engine, self.model, self.device
@@ -117,35 +146,60 @@ class DeviceStages:
             else:
                 raise NotImplementedError("pixel_values given but neither config.vision_encoder nor config.image_feature_fn "
                                           "(CLIP ViT) is set")
-        r = eng.forward_tokens_packed(pool_d, item["desc"], n, K, cls, patches, labels_d, want_order=True,
-                                      padded_len=m.max_decoder_source_length, special_ids=self.special)
-        host = dict(logits=torch.empty((n, K), dtype=torch.float32, pin_memory=True),
-                    order=torch.empty((n, K), dtype=torch.int32, pin_memory=True),
-                    loss=torch.empty((), dtype=torch.float32, pin_memory=True))
-        host["logits"].copy_(r["logits"].view(n, K), non_blocking=True)
+        if self.ragged:
+            r = eng.forward_tokens_packed(pool_d, item["desc"], None, None, cls, patches, labels_d, want_order=True,
+                                          padded_len=m.max_decoder_source_length, special_ids=self.special,
+                                          list_sizes=item["sizes"])
+        else:
+            r = eng.forward_tokens_packed(pool_d, item["desc"], n, K, cls, patches, labels_d, want_order=True,
+                                          padded_len=m.max_decoder_source_length, special_ids=self.special)
+        host, done = self._read_back(r, n, item.get("sizes"), cs)
+        # the batch's device buffers stay referenced here until `done` has been waited for
+        return dict(uploaded=uploaded, done=done, host=host, keep=(up, cls, patches, r), sizes=item.get("sizes"))
+
+    def _read_back(self, r: dict, n: int, sizes, cs):
+        """Non-blocking copies of a batch's logits, order and loss into pinned memory, and the event behind them.  Uniform:
+        [n, K] logits and order, the batch loss.  Ragged: flat [N] logits and order, one loss per list."""
+        torch, K = self.torch, self.K
+        if sizes is None:
+            host = dict(logits=torch.empty((n, K), dtype=torch.float32, pin_memory=True),
+                        order=torch.empty((n, K), dtype=torch.int32, pin_memory=True),
+                        loss=torch.empty((), dtype=torch.float32, pin_memory=True))
+            host["logits"].copy_(r["logits"].view(n, K), non_blocking=True)
+            host["loss"].copy_(r["loss"], non_blocking=True)
+        else:
+            N = sum(sizes)
+            host = dict(logits=torch.empty(N, dtype=torch.float32, pin_memory=True),
+                        order=torch.empty(N, dtype=torch.int32, pin_memory=True),
+                        loss=torch.empty(n, dtype=torch.float32, pin_memory=True))
+            host["logits"].copy_(r["logits"], non_blocking=True)
+            host["loss"].copy_(r["list_loss"], non_blocking=True)
         host["order"].copy_(r["order"], non_blocking=True)
-        host["loss"].copy_(r["loss"], non_blocking=True)
         done = torch.cuda.Event()
         done.record(cs)
-        # the batch's device buffers stay referenced here until `done` has been waited for
-        return dict(uploaded=uploaded, done=done, host=host, keep=(up, cls, patches, r))
+        return host, done
 
     def release(self, pending: dict) -> None:
         pending["uploaded"].synchronize()
 
     def collect(self, pending: dict):
         pending["done"].synchronize()
-        h = pending["host"]
-        out = h["logits"].tolist(), h["order"].tolist(), float(h["loss"])
+        h, sizes = pending["host"], pending.get("sizes")
+        if sizes is None:
+            out = h["logits"].tolist(), h["order"].tolist(), float(h["loss"])
+        else:                                           # one row per list, one loss per list
+            out = split_lists(h["logits"].tolist(), sizes), split_lists(h["order"].tolist(), sizes), h["loss"].tolist()
         pending.clear()
         return out
 
 
-def joint_compact_batch(tok, batch: List[dict], contexts: List[str], K: int, query_len: int, padded_len: int, out=None):
+def joint_compact_batch(tok, batch: List[dict], contexts: List[str], K: int, query_len: int, padded_len: int, out=None,
+                        sizes: Optional[Sequence[int]] = None):
     """Host side of JointStages.prepare: the compact inputs of rr_assemble_joint for one batch.  Returns (pool, desc): `pool`
     an int32 host tensor (a view of `out` when it is large enough) with every query's `query_len` ids then its `query_len` mask
     values (query order), then every context's t[0:m], m <= padded_len - 3 (tok.prepare_contexts_compact, pair order); `desc`
-    an int32 numpy [len(batch) * K, 3] of (query offset, context offset, m)."""
+    an int32 numpy [len(batch) * K, 3] of (query offset, context offset, m).  `sizes`: the queries' list lengths in place of one K
+    (desc then has sum(sizes) rows)."""
     import numpy as np
     import torch
     n, ql = len(batch), int(query_len)
@@ -165,8 +219,10 @@ def joint_compact_batch(tok, batch: List[dict], contexts: List[str], K: int, que
         pool = pool.pin_memory() if out.is_pinned() else pool
     else:
         pool = out[:base + cpool.numel()]
-    desc = np.empty((n * K, 3), dtype=np.int32)
-    desc[:, 0] = (np.arange(n * K) // K) * 2 * ql
+    owner = np.arange(n * K) // K if sizes is None else np.repeat(np.arange(n), np.asarray(sizes, dtype=np.int64))
+    assert owner.size == len(contexts), "one context per pair"
+    desc = np.empty((owner.size, 3), dtype=np.int32)
+    desc[:, 0] = owner * 2 * ql
     desc[:, 1] = off + base
     desc[:, 2] = ln
     return pool, desc
@@ -175,12 +231,12 @@ def joint_compact_batch(tok, batch: List[dict], contexts: List[str], K: int, que
 class JointStages(DeviceStages):
     """The device side of rerank_dataset_pipelined for a `RerankModel` (native context tokenizer, packed joint rows)."""
 
-    def __init__(self, model, batch_queries: int, K: int, first_query: dict):
+    def __init__(self, model, batch_queries: int, K: int, first_query: dict, ragged: bool = False):
         import torch
         from .pair_inputs import NativePairTokenizer
         self.torch = torch
         self.model, self.engine = model, model.engine
-        self.K, self.batch_queries = int(K), int(batch_queries)
+        self.K, self.batch_queries, self.ragged = int(K), int(batch_queries), bool(ragged)
         tok = model.native_tokenizer
         if tok is None:
             if model.decoder_tokenizer is None:
@@ -208,16 +264,20 @@ class JointStages(DeviceStages):
         contexts = []
         for q in batch:
             docs = q["retrieved_docs"]
-            assert len(docs) == K, f"query {q.get('question_id')}: {len(docs)} retrieved docs, the loop reranks {K}"
+            if self.ragged:
+                assert 1 <= len(docs) <= K, f"query {q.get('question_id')}: {len(docs)} retrieved docs, the slots hold 1..{K}"
+            else:
+                assert len(docs) == K, f"query {q.get('question_id')}: {len(docs)} retrieved docs, the loop reranks {K}"
             contexts += [d["content"] for d in docs]
         n = len(batch)
+        sizes = [len(q["retrieved_docs"]) for q in batch] if self.ragged else None
         if any(q.get("pixel_values") is None for q in batch):
             raise NotImplementedError("text_only is not implemented for this model")        # rerank_model.py:184-185
         assert slot["pixels"] is not None, "pixel_values appear after a first query without them"
         pixels = slot["pixels"][:n]
         torch.stack([torch.as_tensor(q["pixel_values"], dtype=torch.float32).reshape(self.pixel_shape) for q in batch], out=pixels)
-        pool, desc = joint_compact_batch(self.tok, batch, contexts, K, ql, self.S, out=slot["pool"])
-        return dict(n=n, pool=pool, desc=desc, pixels=pixels)
+        pool, desc = joint_compact_batch(self.tok, batch, contexts, K, ql, self.S, out=slot["pool"], sizes=sizes)
+        return dict(n=n, pool=pool, desc=desc, pixels=pixels, sizes=sizes)
 
     def submit(self, batch: List[dict], item: dict) -> dict:
         torch, eng, m, dev = self.torch, self.engine, self.model, self.device
@@ -240,23 +300,21 @@ class JointStages(DeviceStages):
         else:
             raise NotImplementedError("query_pixel_values given but neither config.vision_encoder nor config.image_feature_fn "
                                       "(CLIP ViT) is set")
-        r = eng.forward_joint_tokens_packed(pool_d, item["desc"], n, K, self.ql, cls, patches, m.instruction_token_id,
-                                            want_order=True, padded_len=self.S, special_ids=self.special)
-        host = dict(logits=torch.empty((n, K), dtype=torch.float32, pin_memory=True),
-                    order=torch.empty((n, K), dtype=torch.int32, pin_memory=True),
-                    loss=torch.empty((), dtype=torch.float32, pin_memory=True))
-        host["logits"].copy_(r["logits"].view(n, K), non_blocking=True)
-        host["order"].copy_(r["order"], non_blocking=True)
-        host["loss"].copy_(r["loss"], non_blocking=True)
-        done = torch.cuda.Event()
-        done.record(cs)
+        if self.ragged:
+            r = eng.forward_joint_tokens_packed(pool_d, item["desc"], None, None, self.ql, cls, patches, m.instruction_token_id,
+                                                want_order=True, padded_len=self.S, special_ids=self.special,
+                                                list_sizes=item["sizes"])
+        else:
+            r = eng.forward_joint_tokens_packed(pool_d, item["desc"], n, K, self.ql, cls, patches, m.instruction_token_id,
+                                                want_order=True, padded_len=self.S, special_ids=self.special)
+        host, done = self._read_back(r, n, item.get("sizes"), cs)
         # the batch's device buffers stay referenced here until `done` has been waited for
-        return dict(uploaded=uploaded, done=done, host=host, keep=(up, cls, patches, r))
+        return dict(uploaded=uploaded, done=done, host=host, keep=(up, cls, patches, r), sizes=item.get("sizes"))
 
 
 def rerank_dataset_pipelined(queries: Iterable[dict], model, batch_queries: int, Ks: Sequence[int],
                              docs_to_rerank: Optional[int] = None, out_path: Optional[str] = None, stages=None,
-                             stats: Optional[dict] = None) -> dict:
+                             stats: Optional[dict] = None, ragged: bool = False) -> dict:
     """`evaluate.rerank_dataset` for a `FullContextRerankModel` or a `RerankModel`, from strings, pipelined (module
     docstring).  A query dict has the fields rerank_dataset reads and, for a FullContextRerankModel, "question" (the query
     text) and optionally "pixel_values" [3, 224, 224] (the model's image path); labels follow the reference executor: 1 where
@@ -266,7 +324,13 @@ def rerank_dataset_pipelined(queries: Iterable[dict], model, batch_queries: int,
     K = docs_to_rerank, else the first query's retrieved-doc count; a query with another count raises AssertionError.
     Returns {"metrics", "output"} and writes `out_path` as rerank_dataset does.  `stages`: the device side (default
     JointStages(model, ...) for a RerankModel, else DeviceStages(model, ...)).  `stats`, when given, receives batches, tokenise_ms (producer time in `prepare`) and
-    records_ms (calling-thread time building records)."""
+    records_ms (calling-thread time building records).
+    `ragged`: a batch is the next `batch_queries` queries whatever the lengths of their retrieved lists (1 or more docs each);
+    `docs_to_rerank`, if given, is the most a list may hold and longer lists are cut to it, else the longest list sizes the
+    pinned slots (the queries are then read once before the loop starts); `collect` returns one row of logits and of order
+    per query and one loss per query, so each record carries its own list's loss, as the reference's one-query loop does."""
+    if ragged:
+        queries = cut_lists(queries, docs_to_rerank)
     if docs_to_rerank is not None:
         assert docs_to_rerank == max(Ks), "The number of retrieved documents must be equal to the maximum K."   # :806-808
     records: List[dict] = []
@@ -277,7 +341,14 @@ def rerank_dataset_pipelined(queries: Iterable[dict], model, batch_queries: int,
         if stages is None:
             K = docs_to_rerank if docs_to_rerank is not None else len(first["retrieved_docs"])
             from .model import RerankModel
-            stages = (JointStages if isinstance(model, RerankModel) else DeviceStages)(model, batch_queries, K, first)
+            kind = JointStages if isinstance(model, RerankModel) else DeviceStages
+            if ragged:
+                if docs_to_rerank is None:           # the longest list sizes the slots
+                    rest = list(it)
+                    K, it = max(len(q["retrieved_docs"]) for q in [first] + rest), iter(rest)
+                stages = kind(model, batch_queries, K, first, ragged=True)
+            else:
+                stages = kind(model, batch_queries, K, first)
         _run(itertools.chain([first], it), stages, batch_queries, records, st)
     if stats is not None:
         stats.update(st)

@@ -233,3 +233,43 @@ def sharded_forward(engine, input_ids, attention_mask, token_type_ids, Bq: int, 
         return torch.zeros(n, dtype=torch.float32, device=input_ids.device)
 
     return ShardedReranker(encode, head, group, two_heads=two_heads, empty=empty, defer_status=defer_status)(N)
+
+
+def sharded_forward_lists(engine, input_ids, attention_mask, token_type_ids, list_sizes, image_cls=None, image_patches=None,
+                          labels: Optional[torch.Tensor] = None, group=None, want_scores=False, defer_status: bool = False,
+                          lengths=None, **packed_kw):
+    """`sharded_forward` for lists of unequal length: query q owns list_sizes[q] >= 1 of the N = sum(list_sizes) pairs, stored
+    list after list.  The pair slices are cut as there (`shard_range` over N, so a list may straddle ranks); a rank encodes its
+    slice over PACKED rows, logits only (`engine.forward_ids_packed(..., pair_lists=...)`: the per-query image features are
+    picked per pair through the pair-to-list index), and after the one all-gather every rank runs `engine.head_lists` on the
+    full logits.  `lengths`: the N pairs' token counts as the host knows them (spares each rank a device -> host copy);
+    `packed_kw`: granule / segment_cost_rows of the packed forward.  Status words, the deferred mode and the collective errors
+    are ShardedReranker's.  Returns head_lists' dict (loss, list_loss, order flat and local to each list, scores) plus
+    `logits` (/ `logits2`)."""
+    sizes = [int(k) for k in list_sizes]
+    assert sizes and min(sizes) >= 1, "every list holds at least one candidate"
+    N = sum(sizes)
+    assert input_ids.shape[0] == N, f"{input_ids.shape[0]} pairs for lists of {N} candidates"
+    two_heads = engine.arch["loss_fn"] == "2H_BCE"
+    pair_lists = torch.repeat_interleave(torch.arange(len(sizes)), torch.tensor(sizes))
+
+    def encode(b, e):
+        if e <= b:                       # more ranks than pairs: this rank contributes an empty slice
+            z = torch.empty(0, dtype=torch.float32, device=input_ids.device)
+            return z, (z if two_heads else None)
+        r = engine.forward_ids_packed(input_ids[b:e], attention_mask[b:e], None if token_type_ids is None else token_type_ids[b:e],
+                                      None, None, image_cls, image_patches, None, pair_lists=pair_lists[b:e],
+                                      lengths=None if lengths is None else lengths[b:e], want_loss=False, **packed_kw)
+        return r["logits"], (r["logits2"] if two_heads else None)
+
+    def head(l1, l2):
+        out = engine.head_lists(l1, l2, labels, sizes, want_scores=want_scores, want_order=True)
+        out["logits"] = l1.clone()       # the gathered vectors are views of the exchange buffers (see sharded_forward)
+        if l2 is not None:
+            out["logits2"] = l2.clone()
+        return out
+
+    def empty(n):
+        return torch.zeros(n, dtype=torch.float32, device=input_ids.device)
+
+    return ShardedReranker(encode, head, group, two_heads=two_heads, empty=empty, defer_status=defer_status)(N)

@@ -14,7 +14,11 @@ same bert-base / one-layer geometry, ViT from pixels), one line "joint": the que
 (32 entries) and the passages' joint lengths query_len + min(m + 1, 512 - query_len) spread over U[64, 512]; resident_inputs
 runs forward_joint_packed on padded joint rows already on the device, serial_from_strings drives RerankModel.forward (packed
 rows) with the passages tokenised and padded per batch, pipelined_from_strings is rerank_dataset_pipelined (JointStages).
-Prints one JSON line.  Usage: python tools/bench_strings_to_records.py [--queries 64] [--warmup 16] [--family joint]"""
+--ragged LO:HI (full_context family): the lists' lengths are drawn uniformly from [LO, HI] (seeded) and the batches go through
+rerank_dataset_pipelined(ragged=True); each line then holds, for the same model in the same process, the pipelined rate over
+uniform lists of K candidates and over the ragged lists, both as pairs/s (LO + HI = 2 K gives the same expected pairs per batch).
+Prints one JSON line.  Usage: python tools/bench_strings_to_records.py [--queries 64] [--warmup 16] [--family joint]
+[--ragged 1:199]"""
 import argparse
 import json
 import os
@@ -156,7 +160,8 @@ def run_line(vocab, queries, vision, args, dev):
     t0 = time.perf_counter()
     pip = rmr_amd.rerank_dataset_pipelined(timed, m, B, Ks, docs_to_rerank=K, stats=stats)
     t = time.perf_counter() - t0
-    out["pipelined_from_strings"] = dict(queries_per_s=round(len(timed) / t, 2), ms_per_batch=round(t * 1e3 / nb, 3),
+    out["pipelined_from_strings"] = dict(queries_per_s=round(len(timed) / t, 2), pairs_per_s=round(len(timed) * K / t, 1),
+                                         ms_per_batch=round(t * 1e3 / nb, 3),
                                          host_tokenise_ms_per_batch=round(stats["tokenise_ms"] / stats["batches"], 3),
                                          host_records_ms_per_batch=round(stats["records_ms"] / stats["batches"], 3))
     out["pipelined_over_resident"] = round(out["pipelined_from_strings"]["queries_per_s"] / out["resident_inputs"]["queries_per_s"], 4)
@@ -167,6 +172,56 @@ def run_line(vocab, queries, vision, args, dev):
             for q in timed[:2] for d in q["retrieved_docs"]]
     out["mean_pair_tokens_sample"] = round(sum(lens) / len(lens), 1)
     return out
+
+
+def run_ragged_line(vocab, queries, ragged_queries, vision, args, dev):
+    """Pipelined strings -> records over uniform lists (K each) and over ragged lists, same model, alternating, twice each."""
+    K, B = args.K, args.batch
+    m = build_model(vocab, vision, dev)
+    g = torch.Generator().manual_seed(3)
+    for q, r in zip(queries, ragged_queries):
+        if vision:
+            q["pixel_values"] = r["pixel_values"] = 1.2 * torch.randn(3, 224, 224, generator=g)
+        else:
+            q.pop("pixel_values", None)
+            r.pop("pixel_values", None)
+    hi = max(len(q["retrieved_docs"]) for q in ragged_queries)
+    Ks = [1, 5, 10]
+
+    def timed(qs, ragged):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        stats = {}
+        if ragged:
+            rmr_amd.rerank_dataset_pipelined(qs, m, B, Ks + [hi], docs_to_rerank=hi, stats=stats, ragged=True)
+        else:
+            rmr_amd.rerank_dataset_pipelined(qs, m, B, Ks + [K], docs_to_rerank=K, stats=stats)
+        t = time.perf_counter() - t0
+        pairs = sum(len(q["retrieved_docs"]) for q in qs)
+        return dict(pairs=pairs, pairs_per_s=round(pairs / t, 1), queries_per_s=round(len(qs) / t, 2),
+                    ms_per_batch=round(t * 1e3 / stats["batches"], 3),
+                    host_tokenise_ms_per_batch=round(stats["tokenise_ms"] / stats["batches"], 3))
+    w = args.warmup
+    timed(queries[:w], False)
+    timed(ragged_queries[:w], True)
+    out = {"uniform": [], "ragged": []}
+    for _ in range(2):
+        out["uniform"].append(timed(queries[w:], False))
+        out["ragged"].append(timed(ragged_queries[w:], True))
+    out["uniform_pairs_per_s"] = max(r["pairs_per_s"] for r in out["uniform"])
+    out["ragged_pairs_per_s"] = max(r["pairs_per_s"] for r in out["ragged"])
+    out["ragged_over_uniform"] = round(out["ragged_pairs_per_s"] / out["uniform_pairs_per_s"], 4)
+    return out
+
+
+def ragged_corpus(n_queries, lo, hi, seed=0):
+    """make_corpus with hi candidates per query, each list then cut to a length drawn from U[lo, hi] (its own seeded stream)."""
+    vocab, queries = make_corpus(n_queries, hi, seed)
+    rng = random.Random(seed + 1)
+    for q in queries:
+        q["retrieved_docs"] = q["retrieved_docs"][:rng.randint(lo, hi)]
+        q["pos_item_ids"] = [q["retrieved_docs"][0]["passage_id"]]
+    return vocab, queries
 
 
 # ---- the joint family (RerankModel) ------------------------------------------------------------------------------------
@@ -280,6 +335,8 @@ def main():
     ap.add_argument("--lines", default="vision,text_only")
     ap.add_argument("--family", choices=["full_context", "joint"], default="full_context",
                     help="full_context: FullContextRerankModel (--lines); joint: the two-head RerankModel, one line")
+    ap.add_argument("--ragged", default=None, metavar="LO:HI",
+                    help="list lengths drawn uniformly from [LO, HI]: pipelined pairs/s over ragged lists beside uniform lists of K")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
@@ -289,6 +346,18 @@ def main():
                f"{args.batch} queries/batch, fp16, packed joint rows granule 16, query_len 32, joint lengths U[64, 512], ViT from "
                "pixels", "queries_timed": args.queries, "host_threads": host_threads(), "gpu": torch.cuda.get_device_name(dev),
                "joint": run_joint_line(vocab, queries, args, dev)}
+        print(json.dumps(res))
+        return
+    if args.ragged:
+        lo, hi = (int(x) for x in args.ragged.split(":"))
+        assert 1 <= lo <= hi
+        vocab, queries = make_corpus(args.warmup + args.queries, args.K)           # the same vocabulary: same seed, same words
+        _, ragged_queries = ragged_corpus(args.warmup + args.queries, lo, hi)
+        res = {"tool": "bench_strings_to_records", "mode": "ragged", "shape": f"c3 bert-base, {args.batch} queries/batch, fp16, "
+               f"packed rows granule 16, pair lengths U[64, 512]; uniform lists K={args.K} against list lengths U[{lo}, {hi}]",
+               "queries_timed": args.queries, "host_threads": host_threads(), "gpu": torch.cuda.get_device_name(dev)}
+        for line in args.lines.split(","):
+            res[line] = run_ragged_line(vocab, queries, ragged_queries, line == "vision", args, dev)
         print(json.dumps(res))
         return
     vocab, queries = make_corpus(args.warmup + args.queries, args.K)

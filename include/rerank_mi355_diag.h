@@ -142,7 +142,8 @@ int rr_op_gemm_lnfold(const uint16_t* A_raw, const uint16_t* W_folded, const flo
                       int M, int N, int Kd, int epilogue, void* out, void* hip_stream);
 /* LayerNorm whose output is an fp8 GEMM operand: out8[row] = e4m3(LN(x[row]) / row_scale[row]), row_scale = row amax / 448,
  * stats (may be NULL) = (mean, rstd).  rr_util_quantize_rows_e4m3 is the HOST routine the weight packer uses (per output
- * channel = per row of W [rows, cols]): usable without a GPU. */
+ * channel = per row of W [rows, cols]): usable without a GPU.  A row that holds a NaN or an inf gets the scale NaN (the scale
+ * multiplies the whole output column in the GEMM epilogue); rr_util_quantize_rows_i8 likewise. */
 int rr_op_layernorm_q8(const float* x, const float* gamma, const float* beta, float eps, int rows, int cols, uint8_t* out8,
                        float* row_scale, float* stats, void* hip_stream);
 int rr_util_quantize_rows_e4m3(const float* w_host, int rows, int cols, uint8_t* out_host, float* scales_host);

@@ -41,6 +41,8 @@ template <int N>
 __device__ __forceinline__ void wait_vmcnt8() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 __device__ __forceinline__ float gelu13(float x) { return gelu_erf_fast(x); }   // rr_common.h (the name is historical)
+// clamp to the e4m3 range that keeps a NaN: med3 alone returns min3 = -448 for a NaN operand, an ordinary code
+__device__ __forceinline__ float sat448(float v) { return v != v ? v : __builtin_amdgcn_fmed3f(v, -448.f, 448.f); }
 
 __device__ __forceinline__ i32x4 lo16(const i32x8& f) { return i32x4{f[0], f[1], f[2], f[3]}; }
 __device__ __forceinline__ i32x4 hi16(const i32x8& f) { return i32x4{f[4], f[5], f[6], f[7]}; }
@@ -469,10 +471,8 @@ __global__ __launch_bounds__(512) void gemm_kernel_hp8(const uint8_t* __restrict
                         v2 = fmaf(acc[q][mb][4 * rg + 2], r_ * cw.z, bv.z), v3 = fmaf(acc[q][mb][4 * rg + 3], r_ * cw.w, bv.w);
             const f32x2 g0 = gelu_erf_fast2(f32x2{v0, v1}), g1 = gelu_erf_fast2(f32x2{v2, v3});
             int w8 = 0;                                       // (saturating: |gelu| * out_mul beyond 448 clamps)
-            w8 = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(g0.x * x.out_mul, -448.f, 448.f),
-                                                 __builtin_amdgcn_fmed3f(g0.y * x.out_mul, -448.f, 448.f), w8, false);
-            w8 = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(g1.x * x.out_mul, -448.f, 448.f),
-                                                 __builtin_amdgcn_fmed3f(g1.y * x.out_mul, -448.f, 448.f), w8, true);
+            w8 = __builtin_amdgcn_cvt_pk_fp8_f32(sat448(g0.x * x.out_mul), sat448(g0.y * x.out_mul), w8, false);
+            w8 = __builtin_amdgcn_cvt_pk_fp8_f32(sat448(g1.x * x.out_mul), sat448(g1.y * x.out_mul), w8, true);
             const int r = wr * 64 + mb * 32 + (lane & 31);
             *(uint32_t*)(stg + r * PITCH + (cn ^ (((r >> 3) & 3) << 2))) = (uint32_t)w8;
           }

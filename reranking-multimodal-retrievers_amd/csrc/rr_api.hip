@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <cstring>
 #include <exception>
+#include <limits>
 #include <map>
 #include <new>
 #include <string>
@@ -109,25 +110,28 @@ uint8_t host_f2e4m3(float f) {
   if (e > 8 || (e == 8 && m > 6)) return sign | 0x7e;
   return sign | (uint8_t)(((e + 7) << 3) | m);
 }
-// rows of W [rows, cols] -> e4m3 with one scale per row (amax / 448; a zero row gets scale 1)
+// rows of W [rows, cols] -> e4m3 with one scale per row (amax / 448; a zero row gets scale 1; a row that holds a NaN or an inf
+// gets the scale NaN — the scale multiplies the whole output column in the GEMM epilogue — and codes without meaning)
 void host_quantize_rows(const float* W, size_t rows, size_t cols, uint8_t* out, float* scales) {
   for (size_t r = 0; r < rows; ++r) {
     float amax = 0.f;
-    for (size_t k = 0; k < cols; ++k) amax = fmaxf(amax, fabsf(W[r * cols + k]));
+    bool finite = true;                                         // fmaxf drops a NaN and the clamp below turns one into -448
+    for (size_t k = 0; k < cols; ++k) { amax = fmaxf(amax, fabsf(W[r * cols + k])); finite = finite && std::isfinite(W[r * cols + k]); }
     const float sc = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f, inv = 1.0f / sc;
-    scales[r] = sc;
+    scales[r] = finite ? sc : std::numeric_limits<float>::quiet_NaN();   // a NaN / inf in the row: the whole output column is NaN
     for (size_t k = 0; k < cols; ++k) out[r * cols + k] = host_f2e4m3(fminf(fmaxf(W[r * cols + k] * inv, -448.0f), 448.0f));
   }
 }
 
 // rows of W [rows, cols] -> int8 codes with one scale per row (amax / 127; a zero row gets scale 1): round to nearest even,
-// clamped to +-127 (the code range stays symmetric, -128 never occurs)
+// clamped to +-127 (the code range stays symmetric, -128 never occurs); a row that holds a NaN or an inf gets the scale NaN
 void host_quantize_rows_i8(const float* W, size_t rows, size_t cols, int8_t* out, float* scales) {
   for (size_t r = 0; r < rows; ++r) {
     float amax = 0.f;
-    for (size_t k = 0; k < cols; ++k) amax = fmaxf(amax, fabsf(W[r * cols + k]));
+    bool finite = true;                                         // fmaxf drops a NaN and the clamp below turns one into -127
+    for (size_t k = 0; k < cols; ++k) { amax = fmaxf(amax, fabsf(W[r * cols + k])); finite = finite && std::isfinite(W[r * cols + k]); }
     const float sc = amax > 0.f ? amax * (1.0f / 127.0f) : 1.0f, inv = 1.0f / sc;
-    scales[r] = sc;
+    scales[r] = finite ? sc : std::numeric_limits<float>::quiet_NaN();   // a NaN / inf in the row: the whole output column is NaN
     for (size_t k = 0; k < cols; ++k) out[r * cols + k] = (int8_t)nearbyintf(fminf(fmaxf(W[r * cols + k] * inv, -127.0f), 127.0f));
   }
 }

@@ -188,6 +188,9 @@ __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
 // wherever |gelu| >= 1e-3 — two FMAs per value fewer than the degree-7 fit of rounds 2-4 (4.8e-7 / 3.4e-5; RR_GELU_DEGREE 7 keeps
 // it for A/B runs), still two to three orders below the 16-bit rounding of the output (fp16: 4.9e-4 relative).
 // Beyond |x| = 5.7 the neglected term is below 6e-8.
+// NaN in, NaN out: max(x, 0) is formed as x - min(x, 0) — min drops a NaN (IEEE minNum), the subtraction brings it back — where
+// med3(x, 0, +inf) returned 0 for a NaN and, with z = min(|NaN|, 5.7) = 5.7, made gelu(NaN) = -1e-8: a NaN in an FFN-up weight or
+// bias became an ordinary column and never reached the range guard (tests/test_gpu_nonfinite.py).  +inf -> +inf, -inf -> NaN.
 #ifndef RR_GELU_DEGREE
 #define RR_GELU_DEGREE 5
 #endif
@@ -210,11 +213,11 @@ __device__ __forceinline__ float gelu_erf_fast(float x) {
   p = fmaf(p, z, -1.150787830e+00f);
   p = fmaf(p, z, -1.000037670e+00f);
 #endif
-  return fmaf(-z, __builtin_amdgcn_exp2f(p), __builtin_amdgcn_fmed3f(x, 0.0f, __builtin_huge_valf()));   // med3(x, 0, +inf) = max(x, 0)
+  return fmaf(-z, __builtin_amdgcn_exp2f(p), x - fminf(x, 0.0f));   // x - min(x, 0) = max(x, 0), exact for every finite x; NaN stays NaN
 }
 
 // The same function on two values with the Horner chain as v_pk_fma_f32 (two fp32 lanes per instruction at the full VALU
-// rate: 8 packed multiply-adds for the pair instead of 16 scalar ones; |x|, min, exp2 and med3 have no packed form).
+// rate: 8 packed multiply-adds for the pair instead of 16 scalar ones; |x|, min, exp2 and max(x, 0) stay scalar).
 // Every packed operand is VALU-produced (z from v_min, p from the previous packed op, coefficients from SGPR pairs), so the
 // stale-lane hazard of packed-f32 ops behind a vmcnt release (DESIGN.md "Numerics") cannot arise here; each lane's result
 // is the same IEEE fma chain as gelu_erf_fast, bit for bit.
@@ -242,7 +245,7 @@ __device__ __forceinline__ f32x2 gelu_erf_fast2(f32x2 x) {
   p = __builtin_elementwise_fma(p, z, f32x2{-1.000037670e+00f, -1.000037670e+00f});
 #endif
   const f32x2 e = {__builtin_amdgcn_exp2f(p.x), __builtin_amdgcn_exp2f(p.y)};
-  const f32x2 m = {__builtin_amdgcn_fmed3f(x.x, 0.0f, __builtin_huge_valf()), __builtin_amdgcn_fmed3f(x.y, 0.0f, __builtin_huge_valf())};
+  const f32x2 m = {x.x - fminf(x.x, 0.0f), x.y - fminf(x.y, 0.0f)};   // as gelu_erf_fast; scalar: the build admits no packed add
   return __builtin_elementwise_fma(-z, e, m);
 }
 

@@ -141,3 +141,33 @@ def test_host_row_quantiser_matches_torch_e4m3():
     want = (W * (1.0 / want_s)[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8)
     same = (out == want) | ((out & 0x7f) == 0) & ((want & 0x7f) == 0)     # +0 / -0 both encode zero
     assert same.all(), f"{int((~same).sum())} codes differ"
+
+
+def test_host_row_quantiser_e4m3_gives_a_row_with_a_nan_or_inf_a_non_finite_scale():
+    """The e4m3 sibling of tests/test_int8_cpu.py test_a_nan_or_inf_in_a_weight_row_makes_its_scale_non_finite: the row maximum
+    (fmaxf) dropped a NaN and the clamp turned it into -448 under a finite scale.  Now the row's scale is NaN; rows without a
+    NaN / inf pack bit for bit as before."""
+    import torch
+    from rmr_amd import _lib
+    lib = _lib.load()
+
+    def quant(W):
+        out = torch.empty(W.shape, dtype=torch.uint8)
+        sc = torch.empty(W.shape[0])
+        assert lib.rr_util_quantize_rows_e4m3(W.contiguous().data_ptr(), W.shape[0], W.shape[1], out.data_ptr(), sc.data_ptr()) == 0
+        return out, sc
+
+    out, sc = quant(torch.tensor([[0.5, float("nan"), -0.25, 0.1], [0.5, 0.25, -0.25, 0.1]]))
+    assert not torch.isfinite(sc[0]) and sc[1].item() == (torch.tensor(0.5) * (1.0 / 448.0)).item()
+    assert out[1].view(torch.float8_e4m3fn).float().tolist() == [448.0, 224.0, -224.0, 88.0]
+    g = torch.Generator().manual_seed(9)
+    W = torch.randn(64, 256, generator=g) * torch.logspace(-3, 1, 64)[:, None]
+    bad = W.clone()
+    bad[3, 0], bad[10, 255], bad[20, 7], bad[33, 100], bad[33, 101] = float("nan"), float("nan"), float("inf"), float("-inf"), float("nan")
+    rows = torch.tensor([3, 10, 20, 33])
+    keep = torch.ones(64, dtype=torch.bool)
+    keep[rows] = False
+    o0, s0 = quant(W)
+    o1, s1 = quant(bad)
+    assert not torch.isfinite(s1[rows]).any()
+    assert torch.equal(s1[keep].view(torch.int32), s0[keep].view(torch.int32)) and torch.equal(o1[keep], o0[keep])

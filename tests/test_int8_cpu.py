@@ -114,3 +114,27 @@ def test_quantiser_edge_cases():
     # the emulation rounds ties to even too
     qe, _ = quant_rows_i8(torch.from_numpy(row)[None, :])
     assert qe[0].tolist() == [127, 2, 4, -2, 0, 2, 0, -127]
+
+
+def test_a_nan_or_inf_in_a_weight_row_makes_its_scale_non_finite():
+    """fmaxf drops a NaN from the row maximum and fminf(fmaxf(v, -127), 127) turns one into -127: the row (0.5, NaN, -0.25, 0.1)
+    used to pack as scale 0.5 / 127, codes 127, -127, -64, 25 — the most negative code under a finite scale.  The scale multiplies
+    the whole output column in the GEMM epilogue, so a row that holds a NaN or an inf gets a NaN scale (the column is then
+    non-finite and the range guard sees it); every other row packs exactly as before."""
+    q, sc = _lib_quant(np.array([[0.5, np.nan, -0.25, 0.1], [0.5, 0.25, -0.25, 0.1]], dtype=np.float32))
+    assert not np.isfinite(sc[0]) and sc[1] == np.float32(0.5) * np.float32(1.0 / 127.0)
+    assert q[1].tolist() == [127, 64, -64, 25]
+    g = np.random.default_rng(9)
+    W = (g.standard_normal((64, 256)) * g.uniform(0.01, 3.0, (64, 1))).astype(np.float32)
+    bad = W.copy()
+    bad[3, 0], bad[10, 255], bad[20, 7], bad[33, 100], bad[33, 101] = np.nan, np.nan, np.inf, -np.inf, np.nan
+    rows = [3, 10, 20, 33]
+    q0, s0 = _lib_quant(W)
+    q1, s1 = _lib_quant(bad)
+    assert not np.isfinite(s1[rows]).any()
+    keep = np.setdiff1d(np.arange(64), rows)
+    np.testing.assert_array_equal(s1[keep].view(np.int32), s0[keep].view(np.int32))      # bit for bit
+    np.testing.assert_array_equal(q1[keep], q0[keep])
+    qe, se = quant_rows_i8(torch.from_numpy(W))
+    np.testing.assert_array_equal(s1[keep], se.numpy().reshape(-1)[keep])
+    np.testing.assert_array_equal(q1[keep].astype(np.float32), qe.numpy()[keep])

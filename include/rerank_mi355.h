@@ -327,6 +327,8 @@ int rr_assemble_joint(rr_handle h, const int32_t* pool, int64_t pool_len, const 
  *       (multi-GPU sharding; 0,N = everything).  Only that slice of logits_out is written; the head
  *       (loss/scores/order) is computed by rr_head after the caller has all-gathered logits.
  *       With the full range the head runs inside rr_forward.
+ * A call (or slice) of more than 2^30 rows — pairs x (seq_len + vision tokens) — returns RR_ERR_BAD_SHAPE before anything is
+ * allocated or launched (row counts are 32-bit inside a forward); rr_reserve and the interaction / packed forwards likewise.
  */
 int rr_forward(rr_handle h, const int64_t* input_ids, const int64_t* attention_mask,
                const int64_t* token_type_ids, const float* image_cls, const float* image_patches,

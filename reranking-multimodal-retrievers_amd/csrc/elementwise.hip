@@ -611,6 +611,7 @@ hipError_t rr_launch_li_normalize(const float* src, const int64_t* ids, int ids_
                                   int src_batch_off, bf16_t* dst, int dt, int normalize, const float* maskf, int split,
                                   int shift, hipStream_t st) {
   if (n_pairs <= 0 || rows_per_batch <= 0 || (D & 3) || D > 64 * 4 * MAX_V4 || bdiv <= 0) return hipErrorInvalidValue;
+  if ((long long)n_pairs * rows_per_batch > 0x7fffffffLL) return hipErrorInvalidValue;      // the kernel's row index is an int
   const int rows = n_pairs * rows_per_batch;
   hipLaunchKernelGGL(li_normalize_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, src, ids, ids_stride, n_pairs,
                      rows_per_batch, D, T, t_off, pair_off, bdiv, src_batch_off, dst, dt, normalize, maskf, split, shift);
@@ -619,6 +620,7 @@ hipError_t rr_launch_li_normalize(const float* src, const int64_t* ids, int ids_
 
 hipError_t rr_launch_key_bias(const int64_t* ids, const int64_t* am, int n, int S, int T, float* text_bias,
                               float* ce_bias, hipStream_t st) {
+  if (n <= 0 || T <= 0 || (long long)n * T > 0x7fffffffLL) return hipErrorInvalidValue;      // the kernel's element index is an int
   const int total = n * T;
   hipLaunchKernelGGL(key_bias_kernel, dim3((total + 255) / 256), dim3(256), 0, st, ids, am, n, S, T, text_bias,
                      ce_bias);
@@ -679,6 +681,7 @@ hipError_t rr_launch_joint_masks(const int64_t* ids, const int64_t* am, int n, i
 
 hipError_t rr_launch_interaction_bias(const float* qmask, const float* cmask, int n, int Lq, int Lc, int pair_off, int K,
                                       float* cat_bias, float* q_bias, float* c_bias, hipStream_t st) {
+  if (n <= 0 || Lq + Lc <= 0 || (long long)n * (Lq + Lc) > 0x7fffffffLL) return hipErrorInvalidValue;
   const int total = n * (Lq + Lc);
   hipLaunchKernelGGL(interaction_bias_kernel, dim3((total + 255) / 256), dim3(256), 0, st, qmask, cmask, n, Lq, Lc,
                      pair_off, K, cat_bias, q_bias, c_bias);

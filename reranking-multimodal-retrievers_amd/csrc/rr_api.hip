@@ -1221,6 +1221,15 @@ int check_head(rr_model* m, const char* what, int Bq, int K, int pair_begin, lon
   return RR_OK;
 }
 
+// Row counts travel as int through the layer chain (run_layer's `rows`, the row kernels' grids and their n * T products): a call
+// whose n pairs of T rows do not fit is refused here, before anything is allocated or launched.  2^30 rows is the limit of the
+// packed calls too (packed_segments); the workspace of that many rows is beyond any card (audit: tests/test_gpu_large_index.py).
+constexpr long long RR_MAX_ROWS = 1LL << 30;
+int check_rows(rr_model* m, const char* what, long long n, int T) {
+  if (n * (long long)T > RR_MAX_ROWS) return fail(m, RR_ERR_BAD_SHAPE, "%s: %lld pairs of %d rows exceed %lld rows per call", what, n, T, RR_MAX_ROWS);
+  return RR_OK;
+}
+
 // CLS heads + (when this call covers every pair) the scoring head.  classifier1 -> "logits", classifier2 ->
 // "logits_secondary" (utils.py:105-108); for 2H_BCE the ranked logit is the second head (rerank_model.py:589-590).
 int run_heads(rr_model* m, hipStream_t st, Work& w, const std::vector<Seg>& segs, const Request& r) {
@@ -1608,6 +1617,8 @@ static int rr_reserve_impl(rr_handle h, int n_pairs, int n_queries, int len_a, i
   const rr_config& c = m->cfg;
   if (n_pairs <= 0 || n_queries <= 0 || len_a <= 0) return fail(m, RR_ERR_BAD_SHAPE, "rr_reserve: n_pairs=%d n_queries=%d len=%d", n_pairs, n_queries, len_a);
   hipStream_t st = (hipStream_t)hip_stream;
+  RR_TRY(check_rows(m, "rr_reserve", n_pairs,
+                    c.model_kind == RR_MODEL_FULL_CONTEXT ? len_a + (c.has_vision ? c.prefix_len + c.n_patches : 0) : len_a + (len_b > 0 ? len_b : 0)));
   RR_HIP(m, hipSetDevice(c.device));
   Work w{};
   size_t need;
@@ -1975,6 +1986,7 @@ static int forward_full(rr_handle h, Request r) {
   const int T = S + P;
   if (T > c.ce_max_pos)
     return fail(m, RR_ERR_BAD_SHAPE, "cross-encoder length %d exceeds cross_encoder_max_position_embeddings %d", T, c.ce_max_pos);
+  RR_TRY(check_rows(m, "rr_forward", (long long)r.pair_end - pair_begin, T));
   // length-bucketed forward (rr_set_padded_seq_len): S is this call's (shorter) row length, the cross-encoder positions of the
   // vision tokens are those behind the padded text
   int bucket_of = 0;
@@ -2168,6 +2180,7 @@ static int forward_interaction(rr_handle h, Request r) {
                     false));
   if (c.model_kind == RR_MODEL_INTERACTION && T > c.ce_max_pos)
     return fail(m, RR_ERR_BAD_SHAPE, "sequence %d exceeds cross_encoder_max_position_embeddings %d", T, c.ce_max_pos);
+  RR_TRY(check_rows(m, "rr_forward_interaction", (long long)r.pair_end - pair_begin, T));
 
   hipStream_t st = r.stream;
   RR_HIP(m, hipSetDevice(c.device));

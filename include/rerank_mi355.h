@@ -161,7 +161,10 @@ int64_t rr_workspace_bytes(rr_handle h, int n_pairs, int seq_len);
  * handle, an outgrown block is retired until rr_destroy instead of freed, and the attention redo-flag buffers are never
  * freed; such a replay computes in the old blocks it was captured with (and overlaps nothing the handle still uses).  What
  * a replay does NOT survive: rr_destroy of the handle.  The module's constructor-time analogue in the reference: none
- * (PyTorch's caching allocator). */
+ * (PyTorch's caching allocator).
+ * with_fusion: 0 = no attention fusion, 1 = the fusion bias, 2 = the bias and, on a NORMAL interaction handle, the score block
+ * [n_pairs, Lc, Lq] that rr_forward_interaction_fusion_li / rr_forward_interaction_packed_fusion_li compute into (on other
+ * handles 2 means 1: their scores stay with the caller, rr_li_scores). */
 int rr_reserve(rr_handle h, int n_pairs, int n_queries, int len_a, int len_b, int with_fusion, void* hip_stream);
 
 /* Length-bucketed execution (SURVEY.md "Variable length"; the reference pads every pair to max_decoder_source_length,
@@ -393,6 +396,38 @@ int rr_forward_interaction_fusion(rr_handle h, const float* query_li, const floa
                                   float* logits_out, float* logits2_out, float* loss_out, float* scores_out,
                                   int32_t* order_out, void* hip_stream);
 
+/* rr_li_scores: the retriever's own score of every pair and the matrix behind it, on the device, from the late-interaction
+ * tensors rr_forward_interaction takes.  Replaces colbert_score (src/models/flmr/models/flmr/flmr_utils.py:22-48, reached through
+ * FLMRModelForRetrieval.score, modeling_flmr.py:932-936,1601-1602), whose second return value the executor hands to the
+ * rerankers as retrieval_results.scores_raw -> preflmr_scores (Reranker_base_executor.py:877-891).  Any model kind: the joint
+ * family calls it with Lq = query_len + prefix_len + n_patches and Lc = S and passes the result to rr_forward_joint_fusion.
+ *   query_li [Bq, Lq, li_dim], context_li [N, Lc, li_dim], context_mask [N, Lc] (any 0/1 pattern) : DEVICE float32, N = Bq * K;
+ *       query_li / context_li 16-byte aligned (RR_ERR_BAD_ARG).  No query mask: the reference sums over every query token.
+ *   scores_out : DEVICE float32 [N, Lc, Lq] or NULL.  scores[p][c][j] = dot(context_li[p][c], query_li[p / K][j]) in exact
+ *       float32 (one fmaf chain over li_dim per entry, the same chain whatever the slice or shape), and -9999.0f on every row c
+ *       with context_mask[p][c] == 0, whatever that row's embedding holds (the reference assigns, NaN / inf included).
+ *   maxsim_out : DEVICE float32 [N] or NULL.  maxsim[p] = sum over j of max over c of scores[p][c][j], columns added in
+ *       ascending order by one thread: the same bits on every run, with and without scores_out.  A NaN in an unmasked row makes
+ *       its pair's maxsim NaN (torch.max semantics); a fully masked pair gives -9999 * Lq.
+ *   pair_begin / pair_end : only rows [pair_begin, pair_end) of the outputs are written.  K = 1 is the per-pair form.
+ * At least one output (RR_ERR_BAD_ARG); null inputs RR_ERR_BAD_ARG; non-positive sizes or a slice outside [0, Bq * K)
+ * RR_ERR_BAD_SHAPE; all before anything is enqueued.  Without scores_out nothing of size [N, Lc, Lq] is written anywhere.
+ * Allocates nothing, capturable into a graph.  Python: RerankEngine.li_scores. */
+int rr_li_scores(rr_handle h, const float* query_li, const float* context_li, const float* context_mask, int Bq, int K, int Lq,
+                 int Lc, int pair_begin, int pair_end, float* scores_out, float* maxsim_out, void* hip_stream);
+
+/* rr_forward_interaction_fusion_li: rr_forward_interaction_fusion without preflmr_scores: the scores of the slice are computed
+ * from query_li / context_li / context_mask as rr_li_scores computes them (flmr_utils.py:22-48) into a block of the handle
+ * ([n, Lc, Lq]; rr_reserve with_fusion = 2 covers it), and the forward continues as rr_forward_interaction_fusion does on that
+ * block: logits bit for bit those of rr_forward_interaction_fusion(preflmr_scores = rr_li_scores(...)).
+ *   maxsim_out : DEVICE float32 [N] or NULL: the retriever's MaxSim of the pairs of the slice (only those are written).
+ * MORES handles: RR_ERR_UNSUPPORTED (mores_model.py:72-73), before anything is enqueued.
+ * Python: RerankEngine.forward_interaction(fusion_from_li=True). */
+int rr_forward_interaction_fusion_li(rr_handle h, const float* query_li, const float* context_li, const float* query_mask,
+                                     const float* context_mask, float fusion_multiplier, int Bq, int K, int Lq, int Lc,
+                                     const float* labels, int pair_begin, int pair_end, float* logits_out, float* logits2_out,
+                                     float* loss_out, float* scores_out, int32_t* order_out, float* maxsim_out, void* hip_stream);
+
 /* rr_head: scoring head + loss + top-K order over complete logits [Bq*K] (after the RCCL
  * all-gather of per-rank slices).  Same semantics as the tail of rr_forward. */
 int rr_head(rr_handle h, const float* logits, const float* logits2, const float* labels, int Bq, int K,
@@ -446,6 +481,16 @@ int rr_forward_interaction_packed(rr_handle h, const float* query_li, const floa
                                   const float* context_mask, const float* preflmr_scores, float fusion_multiplier,
                                   int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int padded_context_len,
                                   int Lq, float* logits_out, float* logits2_out, void* hip_stream);
+/* rr_forward_interaction_packed_fusion_li: rr_forward_interaction_packed with the attention fusion computed from the packed
+ * tensors themselves (rr_forward_interaction_fusion_li; flmr_utils.py:22-48), so nothing padded is handed over any more: the
+ * positions of a pair beyond its seg_len[i] are pad positions, i.e. masked rows (-9999) of the padded score matrix the library
+ * builds in its own block [n, padded_context_len, Lq], and the bias is the one the padded call builds, bit for bit, normalisers
+ * over the padded axis included.  maxsim_out : DEVICE float32 [n] in packed pair order, or NULL.  NORMAL handles only (MORES:
+ * RR_ERR_UNSUPPORTED).  Python: RerankEngine.forward_interaction_packed(fusion_from_li=True). */
+int rr_forward_interaction_packed_fusion_li(rr_handle h, const float* query_li, const float* context_li, const float* query_mask,
+                                            const float* context_mask, float fusion_multiplier, int n_segments,
+                                            const int32_t* seg_pairs, const int32_t* seg_len, int padded_context_len, int Lq,
+                                            float* logits_out, float* logits2_out, float* maxsim_out, void* hip_stream);
 
 /* rr_head_joint: rr_head with the head RerankModel.forward runs (rr_forward_joint): `loss_fn(logits, logits)`
  * (rerank_model.py:328) — the labels are the logits themselves (2H_BCE: the two heads as class-probability targets).  The

@@ -83,6 +83,11 @@ _SIGS = {
                                          _P, _P, _P, _P, _P, _P]),
     "rr_forward_interaction_fusion": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P,
                                                 C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "rr_li_scores": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "rr_forward_interaction_fusion_li": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P,
+                                                   C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "rr_forward_interaction_packed_fusion_li": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, C.c_int, _P, _P, C.c_int, C.c_int, _P,
+                                                          _P, _P, _P]),
     "rr_head": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "rr_head_joint": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "rr_head_lists": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),

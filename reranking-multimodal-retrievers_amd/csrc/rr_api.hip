@@ -218,6 +218,9 @@ struct rr_model {
   // PreFLMR attention-fusion bias (grow-only, only when rr_forward_joint_fusion is used)
   float* adj = nullptr;
   size_t adj_cap = 0;
+  // late-interaction score block [n][Lc][Lq] of the *_fusion_li forwards (grow-only; rr_reserve with_fusion = 2)
+  float* li_sc = nullptr;
+  size_t li_sc_cap = 0;
   // CLIP ViT (optional)
   std::vector<LayerW> vit_layers;
   bf16_t* vit_wpatch = nullptr;                             // [Vh, Kp] patch convolution, zero-padded to Kp
@@ -1129,6 +1132,16 @@ int ensure_adj(rr_model* m, size_t bytes, hipStream_t st) {
   return RR_OK;
 }
 
+// grow-only score block of the *_fusion_li forwards [n][Lc][Lq] (what the caller of rr_forward_interaction_fusion holds itself)
+int ensure_li_scores(rr_model* m, size_t bytes, hipStream_t st) {
+  if (bytes <= m->li_sc_cap) return RR_OK;
+  RR_TRY(capture_guard(m, st, "the late-interaction score block"));
+  if (m->li_sc) { RR_TRY(release_block(m, m->li_sc, st)); m->li_sc = nullptr; m->li_sc_cap = 0; }
+  RR_HIP(m, hipMalloc((void**)&m->li_sc, bytes));
+  m->li_sc_cap = bytes;
+  return RR_OK;
+}
+
 // One forward call as an exported entry point hands it over (include/rerank_mi355.h); forward_full and forward_interaction
 // take it.  FAM_INTERACTION is NORMAL or MORES, after the handle's model_kind.
 enum Family { FAM_FULL, FAM_JOINT, FAM_INTERACTION };
@@ -1150,6 +1163,8 @@ struct Request {
   hipStream_t stream = nullptr;
   const float* fusion_scores = nullptr;   // PreFLMR attention fusion (joint / NORMAL interaction)
   float fusion_mult = 1.0f;
+  bool fusion_from_li = false;            // interaction: the fusion scores are computed from the call's own tensors (rr_li_scores)
+  float* maxsim = nullptr;                // ... and the retriever's MaxSim of every pair [N] goes here (optional)
   bool packed = false;                    // rr_forward_*_packed: the segment table (pairs, length per pair)
   int n_segments = 0;
   const int32_t *seg_pairs = nullptr, *seg_len = nullptr;
@@ -1466,6 +1481,7 @@ static int rr_destroy_impl(rr_handle h) {
   if (h->ws) (void)hipFree(h->ws);
   if (h->tap_text) (void)hipFree(h->tap_text);
   if (h->adj) (void)hipFree(h->adj);
+  if (h->li_sc) (void)hipFree(h->li_sc);
   for (auto& e : h->ev_pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   for (auto& a : h->asm_slot) {
     if (a.host) (void)hipHostFree(a.host);
@@ -1635,6 +1651,8 @@ static int rr_reserve_impl(rr_handle h, int n_pairs, int n_queries, int len_a, i
   RR_HIP(m, rr_attention_reserve(n_pairs, c.ce_heads, T, st));
   RR_TRY(ensure_ws(m, need, st));
   if (with_fusion) RR_TRY(ensure_adj(m, (size_t)n_pairs * T * ((T + 63) / 64 * 64) * sizeof(float), st));
+  if (with_fusion == 2 && c.model_kind == RR_MODEL_INTERACTION)      // the score block of rr_forward_interaction*_fusion_li
+    RR_TRY(ensure_li_scores(m, (size_t)n_pairs * len_b * len_a * sizeof(float), st));
   return RR_OK;
 }
 
@@ -2170,6 +2188,8 @@ static int forward_interaction(rr_handle h, Request r) {
   if (r.packed) RR_TRY(packed_segments(m, "rr_forward_interaction_packed", r, 0, Lq < 0 ? 0 : Lq, &table));
   if (c.model_kind == RR_MODEL_FULL_CONTEXT) return fail(m, RR_ERR_BAD_ARG, "rr_forward_interaction on a full-context model");
   if (!m->finalized) return fail(m, RR_ERR_BAD_ARG, "rr_forward_interaction before rr_finalize_weights");
+  if (r.fusion_from_li && c.model_kind == RR_MODEL_MORES)
+    return fail(m, RR_ERR_UNSUPPORTED, "Attention adj is not implemented for MORES");   // mores_model.py:72-73
   RR_TRY(range_guard_enter(m));
   if (!r.query_li || !r.context_li || !r.query_mask || !r.context_mask || !r.logits)
     return fail(m, RR_ERR_BAD_ARG, "rr_forward_interaction: null tensor");
@@ -2221,7 +2241,18 @@ static int forward_interaction(rr_handle h, Request r) {
     int adj_ld = 0;
     // interaction_rerank_model.py:131-142: scores [N, Lc, Lq] over the tokens [query | context] (packed: the context axis stays
     // padded, the reference's normalisers run over it)
-    if (r.fusion_scores) {
+    if (r.fusion_from_li) {
+      // the retriever's scores_raw of the slice (flmr_utils.py:22-48) into the handle's block [n][Lc][Lq], then as the padded
+      // call with explicit scores; a packed pair's rows beyond its segment are masked rows of the padded matrix
+      RR_TRY(ensure_li_scores(m, (size_t)n * Lc * Lq * sizeof(float), st));
+      float* ms = r.maxsim ? r.maxsim + pair_begin : nullptr;
+      for (const Seg& g : segs)
+        RR_RUN(m, st, RR_K_TAIL, 2.0 * g.n * (double)g.S * Lq * D, 4.0 * g.n * ((double)g.S * D + (double)Lc * Lq),
+               rr_launch_li_scores(r.query_li, cli + g.r0 * D, cm + g.r0, g.n, K, Lq, g.S, Lc, D, pair_begin + (int)g.p0,
+                                   m->li_sc + g.p0 * Lc * Lq, ms ? ms + g.p0 : nullptr, st));
+      RR_TRY(fusion_bias(m, st, plan, m->li_sc, Lq, Lc, 0, 0, r.fusion_mult, 0, &adj_ld));
+      adj = m->adj;
+    } else if (r.fusion_scores) {
       RR_TRY(fusion_bias(m, st, plan, r.fusion_scores, Lq, Lc, 0, 0, r.fusion_mult, pair_begin, &adj_ld));
       adj = m->adj;
     }
@@ -2279,6 +2310,33 @@ static int forward_interaction(rr_handle h, Request r) {
   const std::vector<Seg> one{Seg{n, Lq, Lq, 0, 0, 0}};
   RR_TRY(run_heads(m, st, w, one, r));
   return range_guard_exit(m, st);
+}
+
+// rr_li_scores (include/rerank_mi355.h): the stand-alone operator, any model kind; every check before anything is enqueued
+static int li_scores_call(rr_handle h, const float* query_li, const float* context_li, const float* context_mask, int Bq, int K,
+                          int Lq, int Lc, int pair_begin, int pair_end, float* scores_out, float* maxsim_out, void* hip_stream) {
+  const char* what = "rr_li_scores";
+  if (!h) return RR_ERR_BAD_ARG;
+  rr_model* m = h;
+  if (!query_li || !context_li || !context_mask) return fail(m, RR_ERR_BAD_ARG, "%s: null tensor", what);
+  if (!scores_out && !maxsim_out) return fail(m, RR_ERR_BAD_ARG, "%s: scores_out and maxsim_out are both null", what);
+  if (Bq <= 0 || K <= 0 || Lq <= 0 || Lc <= 0) return fail(m, RR_ERR_BAD_SHAPE, "%s: Bq=%d K=%d Lq=%d Lc=%d", what, Bq, K, Lq, Lc);
+  const long long N = (long long)Bq * K;
+  if (pair_begin < 0 || pair_end > N || pair_begin >= pair_end)
+    return fail(m, RR_ERR_BAD_SHAPE, "%s: pair slice [%d,%d) outside [0,%lld)", what, pair_begin, pair_end, N);
+  RR_TRY(check_rows(m, what, (long long)pair_end - pair_begin, Lc));
+  if ((((uintptr_t)query_li) | ((uintptr_t)context_li)) & 15)
+    return fail(m, RR_ERR_BAD_ARG, "%s: query_li / context_li must be 16-byte aligned", what);
+  const int D = m->cfg.li_dim, n = pair_end - pair_begin;
+  hipStream_t st = (hipStream_t)hip_stream;
+  RR_HIP(m, hipSetDevice(m->cfg.device));
+  m->last_stream = st;
+  const size_t b = (size_t)pair_begin;
+  RR_RUN(m, st, RR_K_TAIL, 2.0 * n * (double)Lc * Lq * D,
+         4.0 * n * ((double)Lc * D + (scores_out ? (double)Lc * Lq : 0.0)) + 4.0 * Bq * (double)Lq * D,
+         rr_launch_li_scores(query_li, context_li + b * Lc * D, context_mask + b * Lc, n, K, Lq, Lc, Lc, D, pair_begin,
+                             scores_out ? scores_out + b * Lc * Lq : nullptr, maxsim_out ? maxsim_out + b : nullptr, st));
+  return RR_OK;
 }
 
 static int64_t rr_debug_read_impl(rr_handle h, const char* name, float* host_out, int64_t max_elems) {
@@ -2820,6 +2878,29 @@ int rr_forward_interaction_packed(rr_handle h, const float* query_li, const floa
     r.logits = logits_out; r.logits2 = logits2_out; r.stream = (hipStream_t)hip_stream;
     return forward_interaction(h, r);
   });
+}
+int rr_forward_interaction_fusion_li(rr_handle h, const float* query_li, const float* context_li, const float* query_mask, const float* context_mask, float fusion_multiplier, int Bq, int K, int Lq, int Lc, const float* labels, int pair_begin, int pair_end, float* logits_out, float* logits2_out, float* loss_out, float* scores_out, int32_t* order_out, float* maxsim_out, void* hip_stream) {
+  return guarded(h, [&]() -> int {
+    Request r;
+    r.family = FAM_INTERACTION; r.query_li = query_li; r.context_li = context_li; r.query_mask = query_mask; r.context_mask = context_mask;
+    r.fusion_from_li = true; r.maxsim = maxsim_out; r.fusion_mult = fusion_multiplier;
+    r.Bq = Bq; r.K = K; r.q_len = Lq; r.len = Lc; r.labels = labels; r.pair_begin = pair_begin; r.pair_end = pair_end;
+    r.logits = logits_out; r.logits2 = logits2_out; r.loss = loss_out; r.scores = scores_out; r.order = order_out; r.stream = (hipStream_t)hip_stream;
+    return forward_interaction(h, r);
+  });
+}
+int rr_forward_interaction_packed_fusion_li(rr_handle h, const float* query_li, const float* context_li, const float* query_mask, const float* context_mask, float fusion_multiplier, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int padded_context_len, int Lq, float* logits_out, float* logits2_out, float* maxsim_out, void* hip_stream) {
+  return guarded(h, [&]() -> int {
+    Request r;
+    r.family = FAM_INTERACTION; r.query_li = query_li; r.context_li = context_li; r.query_mask = query_mask; r.context_mask = context_mask;
+    r.fusion_from_li = true; r.maxsim = maxsim_out; r.fusion_mult = fusion_multiplier;
+    r.packed = true; r.n_segments = n_segments; r.seg_pairs = seg_pairs; r.seg_len = seg_len; r.len = padded_context_len; r.q_len = Lq;
+    r.logits = logits_out; r.logits2 = logits2_out; r.stream = (hipStream_t)hip_stream;
+    return forward_interaction(h, r);
+  });
+}
+int rr_li_scores(rr_handle h, const float* query_li, const float* context_li, const float* context_mask, int Bq, int K, int Lq, int Lc, int pair_begin, int pair_end, float* scores_out, float* maxsim_out, void* hip_stream) {
+  return guarded(h, [&]() -> int { return li_scores_call(h, query_li, context_li, context_mask, Bq, K, Lq, Lc, pair_begin, pair_end, scores_out, maxsim_out, hip_stream); });
 }
 int rr_get_profile(rr_handle h, rr_profile* out, int reset) {
   return guarded(h, [&]() -> int { return rr_get_profile_impl(h, out, reset); });

@@ -415,6 +415,11 @@ hipError_t rr_launch_fusion_adj(const float* scores, int S, int Tq, int Tc, floa
 #define RR_FUSION_MAX_SEGS 64
 hipError_t rr_launch_fusion_adj_segs(const float* scores, int S, int Tq, int Tc, float mult, int nseg, const int* seg_n,
                                      const int* seg_tk, float* adj, hipStream_t st, int row0);
+// the retriever's late-interaction score matrix [n][Lc][Lq] (-9999 on masked rows and on rows Lc_in <= c < Lc) and MaxSim [n]
+// of n pairs from pair pair0 on, in exact f32 (li_scores.hip); context_li / context_mask hold Lc_in rows per pair; scores or
+// maxsim may be null
+hipError_t rr_launch_li_scores(const float* query_li, const float* context_li, const float* context_mask, int n, int K, int Lq,
+                               int Lc_in, int Lc, int D, int pair0, float* scores, float* maxsim, hipStream_t st);
 
 // CLIP ViT front end: im2col of the stride = kernel patch convolution, and [class | patches] + position -> pre_layrnorm
 hipError_t rr_launch_vit_im2col(const float* px, bf16_t* out, int B, int IS, int ps, int Kp, int dt, hipStream_t st);

@@ -551,12 +551,18 @@ class RerankEngine:
                       query_len: int, image_cls: torch.Tensor, image_patches: torch.Tensor,
                       instruction_token_id: Optional[int] = None, want_scores: bool = False, want_order: bool = False,
                       pair_range: Optional[Sequence[int]] = None, want_loss: bool = True,
-                      preflmr_scores: Optional[torch.Tensor] = None, fusion_multiplier: float = 1.0):
+                      preflmr_scores: Optional[torch.Tensor] = None, fusion_multiplier: float = 1.0,
+                      retriever_query_li: Optional[torch.Tensor] = None, retriever_context_li: Optional[torch.Tensor] = None,
+                      retriever_context_mask: Optional[torch.Tensor] = None):
         """RerankModel.forward semantics on the assembled joint sequence (see rr_forward_joint); `preflmr_scores`
-        [N, S, query_len + image tokens] switches the PreFLMR attention fusion on (rr_forward_joint_fusion)."""
+        [N, S, query_len + image tokens] switches the PreFLMR attention fusion on (rr_forward_joint_fusion).  In its place the
+        retriever's embeddings `retriever_query_li` [Bq, query_len + image tokens, D], `retriever_context_li` [N, S, D] and
+        `retriever_context_mask` [N, S] may be given: the scores are then computed on the device (li_scores)."""
         dev = self.device
         N, S = joint_input_ids.shape
         assert N == Bq * K
+        preflmr_scores = self._retriever_scores(preflmr_scores, retriever_query_li, retriever_context_li, retriever_context_mask,
+                                                Bq, K, pair_range)
         f32 = dict(device=dev, dtype=torch.float32)
         cls = patches = None
         if image_cls is not None:
@@ -582,9 +588,17 @@ class RerankEngine:
                             context_mask: torch.Tensor, Bq: int, K: int, labels: Optional[torch.Tensor] = None,
                             want_scores: bool = False, want_order: bool = False,
                             pair_range: Optional[Sequence[int]] = None, want_loss: bool = True,
-                            preflmr_scores: Optional[torch.Tensor] = None, fusion_multiplier: float = 1.0):
+                            preflmr_scores: Optional[torch.Tensor] = None, fusion_multiplier: float = 1.0,
+                            fusion_from_li: bool = False, want_maxsim: bool = False):
         """Interaction rerankers: late-interaction tensors [Bq,Lq,D] / [N,Lc,D] and 0/1 masks [Bq,Lq] / [N,Lc];
-        `preflmr_scores` [N, Lc, Lq] switches the attention fusion on (rr_forward_interaction_fusion)."""
+        `preflmr_scores` [N, Lc, Lq] switches the attention fusion on (rr_forward_interaction_fusion).  `fusion_from_li`: the
+        fusion scores are the retriever's own, computed inside the call from query_li / context_li / context_mask
+        (rr_forward_interaction_fusion_li; flmr_utils.py:22-48), `want_maxsim` adds the retriever's score of every pair of the
+        slice as `maxsim` [N]."""
+        if fusion_from_li and preflmr_scores is not None:
+            raise ValueError("fusion_from_li=True computes the scores itself: do not pass preflmr_scores as well")
+        if want_maxsim and not fusion_from_li:
+            raise ValueError("want_maxsim needs fusion_from_li=True (or call li_scores)")
         dev = self.device
         N = context_li.shape[0]
         assert N == Bq * K and query_li.shape[0] == Bq, \
@@ -600,7 +614,14 @@ class RerankEngine:
         pb, pe, out = self._outputs(Bq, K, pair_range, want_loss, want_scores, want_order)
         stream = self._stream()
         tensors = L.ptr(query_li), L.ptr(context_li), L.ptr(query_mask), L.ptr(context_mask)
-        if preflmr_scores is not None:
+        if fusion_from_li:
+            maxsim = torch.empty(N, **f32) if want_maxsim else None
+            L.check(self.lib.rr_forward_interaction_fusion_li(self.h, *tensors, float(fusion_multiplier), Bq, K, Lq, Lc,
+                                                              L.ptr(labels), pb, pe, *_ptrs(out), L.ptr(maxsim), stream),
+                    self.h, "rr_forward_interaction_fusion_li")
+            if want_maxsim:
+                out["maxsim"] = maxsim
+        elif preflmr_scores is not None:
             ps = preflmr_scores.to(**f32).contiguous()
             if tuple(ps.shape) != (N, Lc, Lq):
                 raise AssertionError(f"preflmr_scores must be [{N}, {Lc}, {Lq}], got {tuple(ps.shape)}")
@@ -617,7 +638,10 @@ class RerankEngine:
                              instruction_token_id: Optional[int] = None, want_scores: bool = False, want_order: bool = False,
                              want_loss: bool = True, preflmr_scores: Optional[torch.Tensor] = None,
                              fusion_multiplier: float = 1.0, granule: int = 16, lengths: Optional[Sequence[int]] = None,
-                             segment_cost_rows: int = 0, list_sizes: Optional[Sequence[int]] = None, pair_lists=None):
+                             segment_cost_rows: int = 0, list_sizes: Optional[Sequence[int]] = None, pair_lists=None,
+                             retriever_query_li: Optional[torch.Tensor] = None,
+                             retriever_context_li: Optional[torch.Tensor] = None,
+                             retriever_context_mask: Optional[torch.Tensor] = None):
         """`forward_joint` over PACKED rows (rr_forward_joint_packed): the pairs are grouped by the length of their joint
         sequence (1 + last non-pad position of the joint ids / mask) rounded up to `granule`, at least query_len + 1 and the
         mapping network's cross-attention window, and laid out group after group, so that the text encoder and the cross
@@ -625,10 +649,14 @@ class RerankEngine:
         it; its context rows go over padded (the reference normalises over the padded context axis).  The head runs on the
         scattered logits (rr_head_joint: the reference's loss_fn(logits, logits), rerank_model.py:328).  `lengths`: the pairs'
         joint lengths as the host knows them (no device -> host copy).  The sharded path and pair_range slices are not
-        packed.  Returns the dict of forward_joint plus `packed_rows`, `packed_segments`."""
+        packed.  `retriever_query_li` / `retriever_context_li` / `retriever_context_mask` in place of `preflmr_scores`, as
+        forward_joint takes them (one query row per list with `list_sizes`).  Returns the dict of forward_joint plus
+        `packed_rows`, `packed_segments`."""
         dev = self.device
         N, S = joint_input_ids.shape
         Bq, K, pair_query = self._layout(N, Bq, K, list_sizes, pair_lists)
+        preflmr_scores = self._retriever_scores(preflmr_scores, retriever_query_li, retriever_context_li, retriever_context_mask,
+                                                Bq, K, None, pair_query=pair_query, N=N)
         if image_cls is None or image_patches is None:
             raise NotImplementedError("text_only is not implemented for this model")        # rerank_model.py:184-185
         ql = int(query_len)
@@ -658,13 +686,20 @@ class RerankEngine:
                                    want_scores: bool = False, want_order: bool = False, want_loss: bool = True,
                                    preflmr_scores: Optional[torch.Tensor] = None, fusion_multiplier: float = 1.0,
                                    granule: int = 16, lengths: Optional[Sequence[int]] = None, segment_cost_rows: int = 0,
-                                   list_sizes: Optional[Sequence[int]] = None, pair_lists=None):
+                                   list_sizes: Optional[Sequence[int]] = None, pair_lists=None,
+                                   fusion_from_li: bool = False, want_maxsim: bool = False):
         """`forward_interaction` over PACKED rows (rr_forward_interaction_packed, NORMAL and MORES): the pairs are grouped by
         their context length (1 + last non-zero position of `context_mask`) rounded up to `granule`; NORMAL computes the
         cross-encoder rows [query | context] that exist, MORES the doc-side rows.  `preflmr_scores` [N, Lc, Lq] goes over
         padded along the context axis (the reference's normalisers run over it).  `lengths`: the context lengths as the host
         knows them (no device -> host copy).  The sharded path and pair_range slices are not packed.  Returns the dict of
-        forward_interaction plus `packed_rows` (context rows computed), `packed_segments`."""
+        forward_interaction plus `packed_rows` (context rows computed), `packed_segments`.  `fusion_from_li` / `want_maxsim` as
+        forward_interaction takes them (rr_forward_interaction_packed_fusion_li): nothing padded goes over, the positions beyond
+        a pair's segment count as masked rows of the score matrix."""
+        if fusion_from_li and preflmr_scores is not None:
+            raise ValueError("fusion_from_li=True computes the scores itself: do not pass preflmr_scores as well")
+        if want_maxsim and not fusion_from_li:
+            raise ValueError("want_maxsim needs fusion_from_li=True (or call li_scores)")
         dev = self.device
         N = context_li.shape[0]
         if list_sizes is None and pair_lists is None:
@@ -679,18 +714,69 @@ class RerankEngine:
         if preflmr_scores is not None and tuple(preflmr_scores.shape) != (N, Lc, Lq):
             raise AssertionError(f"preflmr_scores must be [{N}, {Lc}, {Lq}], got {tuple(preflmr_scores.shape)}")
 
+        extra = {}
+
         def launch(order, seg_n, seg_len, sn, sl, lp, lp2):
             q = pair_query(order)                                     # query tensors per pair
             q_p = query_li.to(**f32).index_select(0, q).contiguous()
             qm_p = query_mask.reshape(-1, Lq).to(**f32).index_select(0, q).contiguous()
             c_p = pack_rows(context_li.to(**f32), order, seg_n, seg_len)
             cm_p = pack_rows(cm, order, seg_n, seg_len)
+            if fusion_from_li:
+                mp = torch.empty(N, **f32) if want_maxsim else None
+                L.check(self.lib.rr_forward_interaction_packed_fusion_li(self.h, L.ptr(q_p), L.ptr(c_p), L.ptr(qm_p), L.ptr(cm_p),
+                                                                         float(fusion_multiplier), len(seg_n), sn, sl, Lc, Lq,
+                                                                         L.ptr(lp), L.ptr(lp2), L.ptr(mp), self._stream()),
+                        self.h, "rr_forward_interaction_packed_fusion_li")
+                if want_maxsim:
+                    extra["maxsim"] = scatter_packed(mp, order)
+                return
             ps = None if preflmr_scores is None else pack_fusion_scores(preflmr_scores.to(**f32), order)
             L.check(self.lib.rr_forward_interaction_packed(self.h, L.ptr(q_p), L.ptr(c_p), L.ptr(qm_p), L.ptr(cm_p), L.ptr(ps),
                                                            float(fusion_multiplier), len(seg_n), sn, sl, Lc, Lq, L.ptr(lp),
                                                            L.ptr(lp2), self._stream()), self.h, "rr_forward_interaction_packed")
-        return self._packed(launch, (cm,), lengths, Lc, 1, granule, segment_cost_rows, Bq, K, labels, want_loss, want_scores,
-                            want_order, list_sizes=list_sizes, pair_lists=pair_lists, n_pairs=N)
+        out = self._packed(launch, (cm,), lengths, Lc, 1, granule, segment_cost_rows, Bq, K, labels, want_loss, want_scores,
+                           want_order, list_sizes=list_sizes, pair_lists=pair_lists, n_pairs=N)
+        out.update(extra)
+        return out
+
+    def li_scores(self, query_li: torch.Tensor, context_li: torch.Tensor, context_mask: torch.Tensor, Bq: int, K: int,
+                  pair_range: Optional[Sequence[int]] = None, want_scores: bool = True, want_maxsim: bool = True) -> dict:
+        """The frozen retriever's score of every pair and the matrix behind it (rr_li_scores; colbert_score,
+        flmr_utils.py:22-48) from query_li [Bq, Lq, D], context_li [N, Lc, D] and the 0/1 context_mask [N, Lc], N = Bq * K:
+        `scores` [N, Lc, Lq] (context token x query token, -9999 on masked context rows: what the executor hands over as
+        retrieval_results.scores_raw) and `maxsim` [N], in exact float32.  With `pair_range` only that slice of the outputs is
+        written (the rest is uninitialised).  Engines of any model kind."""
+        if not (want_scores or want_maxsim):
+            raise ValueError("li_scores: want_scores or want_maxsim")
+        N = context_li.shape[0]
+        assert N == Bq * K and query_li.shape[0] == Bq, f"{tuple(query_li.shape)}, {tuple(context_li.shape)}, Bq={Bq} K={K}"
+        Lq, Lc, D = query_li.shape[1], context_li.shape[1], self.arch["li_dim"]
+        assert query_li.shape[2] == D and context_li.shape[2] == D, f"late-interaction dim {D}"
+        f32 = dict(device=self.device, dtype=torch.float32)
+        query_li, context_li = query_li.to(**f32).contiguous(), context_li.to(**f32).contiguous()
+        context_mask = context_mask.reshape(N, Lc).to(**f32).contiguous()
+        pb, pe = (0, N) if pair_range is None else (int(pair_range[0]), int(pair_range[1]))
+        out = dict(scores=torch.empty((N, Lc, Lq), **f32) if want_scores else None,
+                   maxsim=torch.empty(N, **f32) if want_maxsim else None)
+        L.check(self.lib.rr_li_scores(self.h, L.ptr(query_li), L.ptr(context_li), L.ptr(context_mask), Bq, K, Lq, Lc, pb, pe,
+                                      L.ptr(out["scores"]), L.ptr(out["maxsim"]), self._stream()), self.h, "rr_li_scores")
+        return {k: v for k, v in out.items() if v is not None}
+
+    def _retriever_scores(self, preflmr_scores, query_li, context_li, context_mask, Bq, K, pair_range, pair_query=None, N=None):
+        """`preflmr_scores` of a joint forward: as given, or from the retriever's embeddings (li_scores).  With a list layout
+        (K is None) the query rows are handed over per pair."""
+        given = [t is not None for t in (query_li, context_li, context_mask)]
+        if not any(given):
+            return preflmr_scores
+        if preflmr_scores is not None:
+            raise ValueError("give preflmr_scores or the retriever_*_li tensors, not both")
+        if not all(given):
+            raise ValueError("retriever_query_li, retriever_context_li and retriever_context_mask go together")
+        if K is None:
+            q = pair_query(torch.arange(N, device=self.device))
+            query_li, Bq, K = query_li.to(self.device).index_select(0, q), N, 1
+        return self.li_scores(query_li, context_li, context_mask, Bq, K, pair_range, want_maxsim=False)["scores"]
 
     def head(self, logits: torch.Tensor, logits2: Optional[torch.Tensor], labels: Optional[torch.Tensor], Bq: int,
              K: int, want_scores: bool = False, want_order: bool = True, want_loss: bool = True, joint: bool = False):
@@ -851,12 +937,13 @@ class RerankEngine:
         L.check(self.lib.rr_get_option(self.h, key.encode(), ctypes.byref(v)), self.h, "rr_get_option")
         return int(v.value)
 
-    def reserve(self, n_pairs: int, n_queries: int, len_a: int, len_b: int = 0, with_fusion: bool = False,
+    def reserve(self, n_pairs: int, n_queries: int, len_a: int, len_b: int = 0, with_fusion: int = 0,
                 packed: bool = False):
         """Allocate everything a forward of at most this shape needs (rr_reserve) on the current stream: afterwards the
         forward neither allocates nor synchronises (a precondition for capturing it into a hipGraph).  `packed`: for
         forward_ids_packed / forward_ids_bucketed / forward_joint_packed / forward_interaction_packed, whose per-query
-        tensors are per PAIR (n_queries = n_pairs, as include/rerank_mi355.h documents for the packed calls)."""
+        tensors are per PAIR (n_queries = n_pairs, as include/rerank_mi355.h documents for the packed calls).  `with_fusion`:
+        0 / False none, 1 / True the attention-fusion bias, 2 the bias and the score block of the `fusion_from_li` forwards."""
         if packed:
             n_queries = n_pairs
         L.check(self.lib.rr_reserve(self.h, int(n_pairs), int(n_queries), int(len_a), int(len_b), int(with_fusion),
@@ -894,7 +981,7 @@ class _DropIn(torch.nn.Module):
     @staticmethod
     def _output(r: dict, logits: torch.Tensor) -> RerankOutput:
         out = RerankOutput(loss=r["loss"], logits=logits)
-        for k in ("scores", "order", "logits2", "list_loss"):
+        for k in ("scores", "order", "logits2", "list_loss", "maxsim"):
             if r.get(k) is not None:
                 out[k] = r[k]
         return out
@@ -1035,7 +1122,9 @@ class InteractionRerankModel(_DropIn):
     Optional config key `packed_rows` (default False): `forward` runs over packed rows (RerankEngine.forward_interaction_packed;
     pass `lengths=` to spare the device -> host copy of the context lengths).  Calls with `pair_range` stay padded.
     `forward` takes the optional keyword `candidates_per_query` of FullContextRerankModel (lists of unequal length; needs
-    `packed_rows`; no reference counterpart)."""
+    `packed_rows`; no reference counterpart), and `fusion_from_li=True` in place of `preflmr_scores`: the attention fusion then
+    runs on the retriever's scores computed from the call's own late-interaction tensors (RerankEngine.li_scores; what the
+    executor passes as `retrieval_results.scores_raw`), `want_maxsim=True` adds them per pair as `maxsim`."""
 
     def __init__(self, config, state_dict: Optional[Dict[str, torch.Tensor]] = None, device=None):
         super().__init__()
@@ -1049,9 +1138,11 @@ class InteractionRerankModel(_DropIn):
 
     def forward(self, query_late_interaction, context_late_interaction, num_negative_examples, query_mask,
                 context_mask, preflmr_scores=None, fusion_multiplier=1, labels=None, candidates_per_query=None,
-                **kw) -> RerankOutput:
+                fusion_from_li=False, **kw) -> RerankOutput:
         Bq = query_late_interaction.size(0)
         N = context_late_interaction.size(0)
+        if fusion_from_li:                    # (without it the engine is called exactly as before)
+            kw["fusion_from_li"] = True
         if candidates_per_query is not None:
             sizes = self._lists(candidates_per_query, N, kw)
             r = self.engine.forward_interaction_packed(
@@ -1076,7 +1167,10 @@ class RerankModel(_DropIn):
     executor's context tokenizer, an HF-style BERT tokenizer: the vocabulary of `native_tokenizer`, which
     rerank_dataset_pipelined tokenises the retrieved passages with) and `max_decoder_source_length` (the context rows'
     padded length; must equal the text encoder's max_pos, as `forward` asserts).  `forward` takes the optional keyword
-    `candidates_per_query` of FullContextRerankModel (lists of unequal length; needs `packed_rows`; no reference counterpart)."""
+    `candidates_per_query` of FullContextRerankModel (lists of unequal length; needs `packed_rows`; no reference counterpart),
+    and, in place of `preflmr_scores`, the retriever's embeddings `retriever_query_li` [Bq, query_len + image tokens, D],
+    `retriever_context_li` [N, S, D] and `retriever_context_mask` [N, S]: the scores are computed on the device
+    (RerankEngine.li_scores); giving both raises ValueError."""
 
     def __init__(self, config, state_dict: Optional[Dict[str, torch.Tensor]] = None, device=None):
         super().__init__()

@@ -492,6 +492,70 @@ int rr_forward_interaction_packed_fusion_li(rr_handle h, const float* query_li, 
                                             const int32_t* seg_pairs, const int32_t* seg_len, int padded_context_len, int Lq,
                                             float* logits_out, float* logits2_out, float* maxsim_out, void* hip_stream);
 
+/* ---- Passage-embedding bank of the interaction rerankers.  They rerank from embeddings that already exist: the frozen retriever's
+ * context token embeddings, which the reference hands over in fp16 (`D = D.half()`, modeling_flmr.py:1554-1555).  A bank keeps
+ * them on the device in that form, each passage at its own length, so that a forward names passages by index instead of taking a
+ * padded float32 context_li [N, Lc, li_dim] per call.  Append-only: per passage rows [len, li_dim] as fp16, one mask byte per row,
+ * and a host-side table (first row as int64, length).  No reference counterpart (it recomputes or reloads the embeddings per batch).
+ * Python: rmr_amd.PassageBank, RerankEngine.create_bank / forward_interaction_bank.
+ *
+ * rr_bank_create: a bank of capacity_rows rows and at most max_passages passages on h's device with h's li_dim (a multiple of 8,
+ * at most 512: RR_ERR_UNSUPPORTED otherwise; interaction handles only).  Its lifetime is its own — rr_destroy(h) does not free it,
+ * rr_bank_destroy does (it synchronises the device) — and every handle of that device with the same li_dim may use it: one bank
+ * serves a NORMAL and a MORES handle.  RR_ERR_OOM when the device allocation fails (message: rr_last_error(h)).  A bank is not
+ * thread-safe, and the stream order is the caller's: a forward reads what the rr_bank_add calls enqueued before it on the same
+ * stream (or on a stream it has been ordered behind) wrote.
+ * rr_bank_clear forgets every passage (capacity kept; forwards still in flight must have completed).  rr_bank_info: passages held,
+ * rows used, row capacity (any pointer may be NULL).  rr_bank_last_error: the message of the last failed rr_bank_* call on b. */
+typedef struct rr_bank* rr_bank_handle;
+int rr_bank_create(rr_handle h, int64_t capacity_rows, int32_t max_passages, rr_bank_handle* out);
+int rr_bank_destroy(rr_bank_handle b);
+int rr_bank_clear(rr_bank_handle b);
+const char* rr_bank_last_error(rr_bank_handle b);
+int rr_bank_info(rr_bank_handle b, int32_t* passages_out, int64_t* rows_used_out, int64_t* capacity_rows_out);
+/* rr_bank_add: append n passages from the padded tensors a retriever produces.
+ *   context_li   : DEVICE [n, Lc, li_dim], float32 (dtype RR_F32) or fp16 bits (RR_F16), 16-byte aligned
+ *   context_mask : DEVICE float32 [n, Lc]
+ *   lengths      : HOST int32 [n], 1 <= lengths[i] <= Lc: passage i keeps rows 0 .. lengths[i] - 1 (everything behind its last
+ *                  unmasked token may go; a passage without an unmasked token has length 1)
+ * Values are rounded to fp16, round to nearest even — what .half() gives; fp16 input is copied.  The mask byte of a kept row is
+ * (mask != 0); rows at or beyond the length count as masked in every forward.  Interior zeros of the mask (punctuation on the
+ * retriever's skiplist) are kept and no position moves.  The passages get the dense indices *first_index_out .. + n - 1
+ * (first_index_out may be NULL).  The call appends all n passages or refuses before anything is enqueued and leaves the bank
+ * unchanged: RR_ERR_BAD_SHAPE for a length outside [1, Lc], RR_ERR_OOM when the rows or the passage slots do not suffice,
+ * RR_ERR_BAD_DTYPE for another dtype.  The library stages the (first row, length) table itself: enqueued on hip_stream, not
+ * capturable into a graph (RR_ERR_BAD_ARG under stream capture). */
+int rr_bank_add(rr_bank_handle b, const void* context_li, int dtype, const float* context_mask, const int32_t* lengths, int n, int Lc,
+                int32_t* first_index_out, void* hip_stream);
+/* rr_forward_interaction_bank: rr_forward_interaction_packed (fusion_from_li != 0: rr_forward_interaction_packed_fusion_li) with
+ * the context side taken from a bank.  NORMAL and MORES handles.
+ *   query_li [n_queries, Lq, li_dim], query_mask [n_queries, Lq] : DEVICE float32, per QUERY (query_li 16-byte aligned)
+ *   pair_passage, pair_query : HOST int32 [n], n = sum seg_pairs: the bank index and the query index of every pair, in the
+ *       PACKED pair order (segment after segment, pair after pair).  A passage may appear in any number of pairs.
+ *   n_segments / seg_pairs / seg_len / padded_context_len, logits_out / logits2_out / maxsim_out : as the packed calls take them
+ *       (maxsim_out only with fusion_from_li).
+ * One gather launch per segment writes the 16-bit [query | context] rows the cross encoder / the MORES stack consume (context
+ * rows fp16 -> float32 -> the handle's operand type, zero beyond the passage's length) and the float mask rows; the rest of the
+ * forward is the packed call's.  Without fusion nothing of size [n, Lc, li_dim] in float32 is written.  With fusion_from_li the
+ * gather also writes float32 copies of the call's query and context rows into a grow-only block of the handle, which the score
+ * kernel of rr_li_scores reads unchanged (cost: 4 bytes per element written and read again; the score block dominates it).
+ * Checked on the host BEFORE anything is enqueued, a refused call writes nothing: bank and handle on one device (RR_ERR_BAD_ARG)
+ * with one li_dim (RR_ERR_BAD_SHAPE); MORES with fusion_from_li (RR_ERR_UNSUPPORTED, mores_model.py:72-73); the segment table
+ * (1..64 non-empty segments, lengths in (0, padded_context_len]); every passage index inside the bank, every passage's length <=
+ * its segment's length, every query index inside n_queries (RR_ERR_BAD_SHAPE); and what rr_forward_interaction_packed checks.
+ * The library stages the per-pair descriptors itself, through the slots rr_assemble_pairs uses: NOT capturable into a graph
+ * (RR_ERR_BAD_ARG under stream capture).
+ * CONTRACT: logits (and maxsim_out) are bit for bit those of rr_forward_interaction_packed / _packed_fusion_li called with the
+ * same segment table and query_li[pair_query], query_mask[pair_query] per pair, context_li = float32(bank rows) (zero beyond a
+ * passage's length) and context_mask = the bank's mask bytes.  On an fp16 handle (compute_dtype 1) that is also, bit for bit,
+ * the call on the ORIGINAL float32 tensors: float32 -> fp16 happens once either way.  On a bf16 handle it is NOT: float32 -> fp16
+ * -> bf16 differs from float32 -> bf16 on 3.3 - 3.5 % of the elements of unit-scale embeddings (532 of 15 360 and 13 004 of
+ * 393 216 on the test fixtures; logits moved by 5e-5 .. 1e-3 there) — the reference's own fp16 hand-over rounds twice as well. */
+int rr_forward_interaction_bank(rr_handle h, rr_bank_handle b, const float* query_li, const float* query_mask, int n_queries, int Lq,
+                                const int32_t* pair_passage, const int32_t* pair_query, int n_segments, const int32_t* seg_pairs,
+                                const int32_t* seg_len, int padded_context_len, int fusion_from_li, float fusion_multiplier,
+                                float* logits_out, float* logits2_out, float* maxsim_out, void* hip_stream);
+
 /* rr_head_joint: rr_head with the head RerankModel.forward runs (rr_forward_joint): `loss_fn(logits, logits)`
  * (rerank_model.py:328) — the labels are the logits themselves (2H_BCE: the two heads as class-probability targets).  The
  * head of a packed joint call, after the scatter.  negative_sampling with loss_out: RR_ERR_UNSUPPORTED, as rr_forward_joint. */

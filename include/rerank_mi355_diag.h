@@ -242,6 +242,10 @@ int rr_op_cls_heads(const float* h32, int T, int cols, int n_pairs, const float*
  * squares is not below range_ss (NaN included). */
 int rr_op_ln_finalize(const float* part, int nparts, int cols, float eps, int rows, float* stats, int* range_flag, float range_ss,
                       void* hip_stream);
+/* Read one passage of a bank back to HOST memory: rows_out [len, li_dim] fp16 bits, mask_out [len] bytes (either may be NULL;
+ * both NULL = only the length), buffers of capacity_rows rows.  Synchronises hip_stream (the stream the rr_bank_add calls went to)
+ * and copies synchronously.  Returns the passage's length, or < 0 (RR_ERR_BAD_SHAPE: no such passage, buffers too small). */
+int rr_bank_read(rr_bank_handle b, int32_t index, uint16_t* rows_out, uint8_t* mask_out, int32_t capacity_rows, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,7 @@ Only what the hot path needs lives here: `csrc/` (HIP kernels + the C ABI of lib
 `_lib.py` (ctypes declarations), `model.py` (mirror of the reference's RerankerClass interface),
 `pair_inputs.py` (pair-input assembly), `sharding.py` (pair sharding + score all-gather across ranks), `evaluate.py` (batched executor-side rerank loop, the
 reference's prediction-record schema and Recall@K), `pipeline.py` (the same loop from strings, tokenisation and records
-overlapped with the device).
+overlapped with the device), `passage_bank.py` (the device-resident passage-embedding bank of the interaction rerankers).
 Importing the package does not need a GPU; constructing a model does (no CPU fallback exists).
 """
 from ._lib import EXPORTED, LIB_PATH  # noqa: F401
@@ -14,5 +14,6 @@ from .sharding import shard_range, ShardedReranker, sharded_forward_lists  # noq
 from .ranking import rank_descending_stable, recall_precision_at_k  # noqa: F401
 from .evaluate import build_records, compute_rerank_scores, rerank_dataset  # noqa: F401
 from .pipeline import rerank_dataset_pipelined  # noqa: F401
+from .passage_bank import BankTable, PassageBank, plan_bank_batch  # noqa: F401
 
 __version__ = "0.1.0"

@@ -88,6 +88,15 @@ _SIGS = {
                                                    C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "rr_forward_interaction_packed_fusion_li": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, C.c_int, _P, _P, C.c_int, C.c_int, _P,
                                                           _P, _P, _P]),
+    "rr_bank_create": (C.c_int, [_P, C.c_int64, C.c_int32, C.POINTER(_P)]),
+    "rr_bank_destroy": (C.c_int, [_P]),
+    "rr_bank_clear": (C.c_int, [_P]),
+    "rr_bank_last_error": (C.c_char_p, [_P]),
+    "rr_bank_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "rr_bank_add": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_int32), _P]),
+    "rr_bank_read": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P]),
+    "rr_forward_interaction_bank": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_float,
+                                              _P, _P, _P, _P]),
     "rr_head": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "rr_head_joint": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "rr_head_lists": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),

@@ -221,6 +221,10 @@ struct rr_model {
   // late-interaction score block [n][Lc][Lq] of the *_fusion_li forwards (grow-only; rr_reserve with_fusion = 2)
   float* li_sc = nullptr;
   size_t li_sc_cap = 0;
+  // what rr_forward_interaction_bank's gather writes beside the 16-bit rows (grow-only): the float mask rows of the call, and with
+  // fusion_from_li the float32 copies of its query / context rows that li_scores reads
+  char* bank_blk = nullptr;
+  size_t bank_blk_cap = 0;
   // CLIP ViT (optional)
   std::vector<LayerW> vit_layers;
   bf16_t* vit_wpatch = nullptr;                             // [Vh, Kp] patch convolution, zero-padded to Kp
@@ -268,6 +272,21 @@ struct rr_model {
   struct AsmSlot { void* host = nullptr; void* dev = nullptr; size_t cap = 0; hipEvent_t done = nullptr; };
   AsmSlot asm_slot[2];
   int asm_next = 0;
+};
+
+// rr_bank_* (include/rerank_mi355.h): an append-only device store of passages.  rows [capacity_rows][D] fp16 bits, one mask byte
+// per row, and the host table (first row, length) per passage.  Its own staging slots: rr_bank_add belongs to no handle.
+struct rr_bank {
+  int device = 0, D = 0;
+  int64_t cap_rows = 0, used_rows = 0;
+  int32_t max_passages = 0;
+  uint16_t* rows = nullptr;
+  uint8_t* mask = nullptr;
+  std::vector<int64_t> first;
+  std::vector<int32_t> len;
+  std::string err;
+  rr_model::AsmSlot slot[2];
+  int next = 0;
 };
 
 namespace {
@@ -1142,6 +1161,16 @@ int ensure_li_scores(rr_model* m, size_t bytes, hipStream_t st) {
   return RR_OK;
 }
 
+// grow-only block of rr_forward_interaction_bank (rr_model::bank_blk)
+int ensure_bank_blk(rr_model* m, size_t bytes, hipStream_t st) {
+  if (bytes <= m->bank_blk_cap) return RR_OK;
+  RR_TRY(capture_guard(m, st, "the bank forward's block"));
+  if (m->bank_blk) { RR_TRY(release_block(m, m->bank_blk, st)); m->bank_blk = nullptr; m->bank_blk_cap = 0; }
+  RR_HIP(m, hipMalloc((void**)&m->bank_blk, bytes));
+  m->bank_blk_cap = bytes;
+  return RR_OK;
+}
+
 // One forward call as an exported entry point hands it over (include/rerank_mi355.h); forward_full and forward_interaction
 // take it.  FAM_INTERACTION is NORMAL or MORES, after the handle's model_kind.
 enum Family { FAM_FULL, FAM_JOINT, FAM_INTERACTION };
@@ -1168,6 +1197,10 @@ struct Request {
   bool packed = false;                    // rr_forward_*_packed: the segment table (pairs, length per pair)
   int n_segments = 0;
   const int32_t *seg_pairs = nullptr, *seg_len = nullptr;
+  // rr_forward_interaction_bank: the context rows and masks come from `bank` through the checked per-pair descriptors (packed pair
+  // order); query_li / query_mask are per QUERY and the descriptors name each pair's query
+  const rr_bank* bank = nullptr;
+  const std::vector<rr_bank_pair>* bank_pairs = nullptr;
 };
 
 // The rows of a forward: the segment list (one segment for a padded or length-bucketed call) and what the cross-encoder needs
@@ -1482,6 +1515,7 @@ static int rr_destroy_impl(rr_handle h) {
   if (h->tap_text) (void)hipFree(h->tap_text);
   if (h->adj) (void)hipFree(h->adj);
   if (h->li_sc) (void)hipFree(h->li_sc);
+  if (h->bank_blk) (void)hipFree(h->bank_blk);
   for (auto& e : h->ev_pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   for (auto& a : h->asm_slot) {
     if (a.host) (void)hipHostFree(a.host);
@@ -1975,6 +2009,144 @@ static int rr_assemble_joint_impl(rr_handle h, const int32_t* pool, int64_t pool
   return asm_done(m, st);
 }
 
+// ---- rr_bank_* (include/rerank_mi355.h)
+static int bfail(rr_bank* b, int code, const char* fmt, ...) noexcept {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  if (b) { try { b->err = buf; } catch (...) {} }
+  return code;
+}
+#define RR_BHIP(b, call)                                                                                                  \
+  do {                                                                                                                    \
+    hipError_t e_ = (call);                                                                                               \
+    if (e_ != hipSuccess)                                                                                                 \
+      return bfail(b, e_ == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
+  } while (0)
+
+static void bank_free(rr_bank* b) {
+  if (b->rows) (void)hipFree(b->rows);
+  if (b->mask) (void)hipFree(b->mask);
+  for (auto& a : b->slot) {
+    if (a.host) (void)hipHostFree(a.host);
+    if (a.dev) (void)hipFree(a.dev);
+    if (a.done) (void)hipEventDestroy(a.done);
+  }
+  delete b;
+}
+
+static int rr_bank_create_impl(rr_handle h, int64_t capacity_rows, int32_t max_passages, rr_bank_handle* out) {
+  if (!h) return RR_ERR_BAD_ARG;
+  if (!out) return fail(h, RR_ERR_BAD_ARG, "rr_bank_create: null out");
+  *out = nullptr;
+  const int D = h->cfg.li_dim;
+  if (h->cfg.model_kind == RR_MODEL_FULL_CONTEXT) return fail(h, RR_ERR_BAD_ARG, "rr_bank_create on a full-context model");
+  if (D <= 0 || (D & 7) || D > 512) return fail(h, RR_ERR_UNSUPPORTED, "rr_bank_create: li_dim %d (a multiple of 8, at most 512)", D);
+  if (capacity_rows <= 0 || max_passages <= 0 || capacity_rows > (1LL << 40))
+    return fail(h, RR_ERR_BAD_SHAPE, "rr_bank_create: capacity_rows=%lld max_passages=%d", (long long)capacity_rows, max_passages);
+  RR_HIP(h, hipSetDevice(h->cfg.device));
+  rr_bank* b = new rr_bank();
+  b->device = h->cfg.device;
+  b->D = D;
+  b->cap_rows = capacity_rows;
+  b->max_passages = max_passages;
+  hipError_t e = hipMalloc((void**)&b->rows, (size_t)capacity_rows * D * sizeof(uint16_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&b->mask, (size_t)capacity_rows);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    bank_free(b);
+    return fail(h, e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP, "rr_bank_create: %lld rows of %d: %s", (long long)capacity_rows, D,
+                hipGetErrorString(e));
+  }
+  b->first.reserve((size_t)std::min<int64_t>(max_passages, 1 << 20));
+  b->len.reserve((size_t)std::min<int64_t>(max_passages, 1 << 20));
+  *out = b;
+  return RR_OK;
+}
+
+static int rr_bank_destroy_impl(rr_bank* b) {
+  if (!b) return RR_ERR_BAD_ARG;
+  (void)hipSetDevice(b->device);
+  (void)hipDeviceSynchronize();
+  bank_free(b);
+  return RR_OK;
+}
+
+// every check on the host first; then one staged upload of the (first row, length) slots and one launch
+static int rr_bank_add_impl(rr_bank* b, const void* context_li, int dtype, const float* context_mask, const int32_t* lengths, int n,
+                            int Lc, int32_t* first_index_out, void* hip_stream) {
+  const char* what = "rr_bank_add";
+  if (!b) return RR_ERR_BAD_ARG;
+  if (!context_li || !context_mask || !lengths) return bfail(b, RR_ERR_BAD_ARG, "%s: null argument", what);
+  if (dtype != RR_F32 && dtype != RR_F16) return bfail(b, RR_ERR_BAD_DTYPE, "%s: dtype %d (RR_F32 or RR_F16)", what, dtype);
+  if (((uintptr_t)context_li) & 15) return bfail(b, RR_ERR_BAD_ARG, "%s: context_li must be 16-byte aligned", what);
+  if (n <= 0 || Lc <= 0 || (long long)n * Lc > (1LL << 40)) return bfail(b, RR_ERR_BAD_SHAPE, "%s: n=%d Lc=%d", what, n, Lc);
+  int64_t rows = 0;
+  for (int i = 0; i < n; ++i) {
+    if (lengths[i] < 1 || lengths[i] > Lc)
+      return bfail(b, RR_ERR_BAD_SHAPE, "%s: passage %d has length %d (1..%d)", what, i, lengths[i], Lc);
+    rows += lengths[i];
+  }
+  const int64_t have = (int64_t)b->first.size();
+  if (have + n > b->max_passages)
+    return bfail(b, RR_ERR_OOM, "%s: %lld + %d passages exceed the bank's %d slots", what, (long long)have, n, b->max_passages);
+  if (b->used_rows + rows > b->cap_rows)
+    return bfail(b, RR_ERR_OOM, "%s: %lld + %lld rows exceed the bank's %lld", what, (long long)b->used_rows, (long long)rows,
+                 (long long)b->cap_rows);
+  hipStream_t st = (hipStream_t)hip_stream;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return bfail(b, RR_ERR_BAD_ARG, "%s cannot be captured into a graph (it stages its descriptors from the host)", what);
+  std::vector<rr_bank_slot> staged((size_t)n);
+  int64_t row = b->used_rows;
+  for (int i = 0; i < n; ++i) {
+    staged[(size_t)i] = rr_bank_slot{row, lengths[i], 0};
+    row += lengths[i];
+  }
+  RR_BHIP(b, hipSetDevice(b->device));
+  rr_model::AsmSlot& a = b->slot[b->next];
+  const size_t bytes = staged.size() * sizeof(rr_bank_slot);
+  if (!a.done) RR_BHIP(b, hipEventCreateWithFlags(&a.done, hipEventDisableTiming));
+  else RR_BHIP(b, hipEventSynchronize(a.done));      // the launch that last read this slot is done
+  if (a.cap < bytes) {
+    if (a.host) { RR_BHIP(b, hipHostFree(a.host)); a.host = nullptr; }
+    if (a.dev) { RR_BHIP(b, hipFree(a.dev)); a.dev = nullptr; }
+    a.cap = 0;
+    const size_t cap = std::max(bytes, (size_t)1024 * sizeof(rr_bank_slot));
+    RR_BHIP(b, hipHostMalloc(&a.host, cap, hipHostMallocDefault));
+    RR_BHIP(b, hipMalloc(&a.dev, cap));
+    a.cap = cap;
+  }
+  memcpy(a.host, staged.data(), bytes);
+  RR_BHIP(b, hipMemcpyAsync(a.dev, a.host, bytes, hipMemcpyHostToDevice, st));
+  RR_BHIP(b, rr_launch_bank_ingest(context_li, dtype == RR_F16, context_mask, (const rr_bank_slot*)a.dev, n, Lc, b->D, b->rows, b->mask, st));
+  RR_BHIP(b, hipEventRecord(a.done, st));
+  b->next ^= 1;
+  for (int i = 0; i < n; ++i) {
+    b->first.push_back(staged[(size_t)i].first_row);
+    b->len.push_back(lengths[i]);
+  }
+  b->used_rows = row;
+  if (first_index_out) *first_index_out = (int32_t)have;
+  return RR_OK;
+}
+
+static int rr_bank_read_impl(rr_bank* b, int32_t index, uint16_t* rows_out, uint8_t* mask_out, int32_t capacity_rows, void* hip_stream) {
+  if (!b) return RR_ERR_BAD_ARG;
+  if (index < 0 || (size_t)index >= b->first.size()) return bfail(b, RR_ERR_BAD_SHAPE, "rr_bank_read: passage %d of %zu", index, b->first.size());
+  const int32_t len = b->len[(size_t)index];
+  if (!rows_out && !mask_out) return len;
+  if (capacity_rows < len) return bfail(b, RR_ERR_BAD_SHAPE, "rr_bank_read: passage %d holds %d rows, the buffers %d", index, len, capacity_rows);
+  RR_BHIP(b, hipSetDevice(b->device));
+  RR_BHIP(b, hipStreamSynchronize((hipStream_t)hip_stream));
+  const int64_t r0 = b->first[(size_t)index];
+  if (rows_out) RR_BHIP(b, hipMemcpy(rows_out, b->rows + (size_t)r0 * b->D, (size_t)len * b->D * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  if (mask_out) RR_BHIP(b, hipMemcpy(mask_out, b->mask + r0, (size_t)len, hipMemcpyDeviceToHost));
+  return len;
+}
+
 // FullContextRerankModel.forward (rerank_model.py:523-591) on the tokenised pairs.  FAM_JOINT: RerankModel.forward semantics
 // (rerank_model.py:171-331) on the pre-assembled joint sequence: token types all 0, query_mask with instruction masking,
 // cross-encoder order [query | image | context], and the reference's `loss_fn(logits, logits)` quirk (:328).
@@ -2191,7 +2363,7 @@ static int forward_interaction(rr_handle h, Request r) {
   if (r.fusion_from_li && c.model_kind == RR_MODEL_MORES)
     return fail(m, RR_ERR_UNSUPPORTED, "Attention adj is not implemented for MORES");   // mores_model.py:72-73
   RR_TRY(range_guard_enter(m));
-  if (!r.query_li || !r.context_li || !r.query_mask || !r.context_mask || !r.logits)
+  if (!r.query_li || !r.query_mask || !r.logits || (!r.bank && (!r.context_li || !r.context_mask)))
     return fail(m, RR_ERR_BAD_ARG, "rr_forward_interaction: null tensor");
   const int Bq = r.Bq, K = r.K, Lc = r.len, pair_begin = r.pair_begin;
   if (Bq <= 0 || K <= 0 || Lq <= 0 || Lc <= 0) return fail(m, RR_ERR_BAD_SHAPE, "Bq=%d K=%d Lq=%d Lc=%d", Bq, K, Lq, Lc);
@@ -2211,8 +2383,9 @@ static int forward_interaction(rr_handle h, Request r) {
   layout_interaction(c, n, Bq, Lq, Lc, m->ws, &w);
   m->last_stream = st;
   const int D = c.li_dim, Hc = c.ce_hidden, Ic = c.ce_intermediate;
-  const float* cli = r.context_li + (size_t)pair_begin * Lc * D;
-  const float* cm = r.context_mask + (size_t)pair_begin * Lc;
+  const float* cli = r.bank ? nullptr : r.context_li + (size_t)pair_begin * Lc * D;
+  const float* cm = r.bank ? nullptr : r.context_mask + (size_t)pair_begin * Lc;
+  const float *qli = r.query_li, *qm = r.query_mask;
   // segments: Seg.S = context tokens per pair, Seg.r0 = first context row, Seg.rt0 = first row of the concatenated
   // [query | context] sequence
   const RowPlan plan = plan_rows(FAM_INTERACTION, n, Lc, Lq, table, 0);
@@ -2220,12 +2393,38 @@ static int forward_interaction(rr_handle h, Request r) {
   const Seg& last = segs.back();
   const int C = (int)(last.r0 + (size_t)last.n * last.S), RT = (int)(last.rt0 + (size_t)last.n * last.T);
 
+  if (r.bank) {
+    // the 16-bit [query | context] rows straight from the bank, one launch per segment, with the float mask rows the bias kernel
+    // reads (per pair, as the packed call takes them) and, for the attention fusion, float32 copies of the rows for li_scores
+    size_t off = 0;
+    auto take = [&off](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_cm = take((size_t)C * 4), o_qm = take((size_t)n * Lq * 4);
+    const size_t o_c32 = r.fusion_from_li ? take((size_t)C * D * 4) : 0, o_q32 = r.fusion_from_li ? take((size_t)n * Lq * D * 4) : 0;
+    RR_TRY(ensure_bank_blk(m, off, st));
+    float *cm_w = (float*)(m->bank_blk + o_cm), *qm_w = (float*)(m->bank_blk + o_qm);
+    float* c32 = r.fusion_from_li ? (float*)(m->bank_blk + o_c32) : nullptr;
+    float* q32 = r.fusion_from_li ? (float*)(m->bank_blk + o_q32) : nullptr;
+    void* dev = nullptr;
+    RR_TRY(asm_stage(m, "rr_forward_interaction_bank", r.bank_pairs->data(), r.bank_pairs->size() * sizeof(rr_bank_pair), st, &dev));
+    for (const Seg& g : segs)
+      RR_RUN(m, st, RR_K_TAIL, 0.0, (double)g.n * (Lq * D * (4.0 + 2.0 + (q32 ? 4.0 : 0.0)) + (double)g.S * D * (2.0 + 2.0 + (c32 ? 4.0 : 0.0))),
+             rr_launch_bank_gather((const rr_bank_pair*)dev + g.p0, g.n, Lq, g.S, D, r.query_li, r.query_mask, r.bank->rows,
+                                   r.bank->mask, w.li16 + g.rt0 * D, m->dt, qm_w + g.p0 * Lq, cm_w + g.r0,
+                                   q32 ? q32 + g.p0 * Lq * D : nullptr, c32 ? c32 + g.r0 * D : nullptr, st));
+    RR_TRY(asm_done(m, st));
+    cm = cm_w;
+    qm = qm_w;
+    cli = c32;
+    if (q32) qli = q32;
+  }
   for (const Seg& g : segs)
     RR_RUN(m, st, RR_K_EMBED, 0.0, 8.0 * g.n * g.T,
-           rr_launch_interaction_bias(r.query_mask, cm + g.r0, g.n, Lq, g.S, pair_begin + (int)g.p0, K, w.ce_bias + g.rt0,
+           rr_launch_interaction_bias(qm, cm + g.r0, g.n, Lq, g.S, pair_begin + (int)g.p0, K, w.ce_bias + g.rt0,
                                       w.text_bias + g.p0 * Lq, w.li32 + g.r0, st));
-  // operands in 16 bits, query rows broadcast to the K pairs of the query (repeat_interleave, :128-129)
-  for (const Seg& g : segs) {
+  // operands in 16 bits, query rows broadcast to the K pairs of the query (repeat_interleave, :128-129); a bank call's gather
+  // has written them
+  for (size_t s = 0; !r.bank && s < segs.size(); ++s) {
+    const Seg& g = segs[s];
     RR_RUN(m, st, RR_K_TAIL, 0.0, 6.0 * g.n * Lq * D,
            rr_launch_li_normalize(r.query_li, nullptr, 0, g.n, Lq, D, g.T, 0, pair_begin + (int)g.p0, K, 0, w.li16 + g.rt0 * D, m->dt, 0,
                                   nullptr, 1 << 30, 0, st));
@@ -2248,7 +2447,7 @@ static int forward_interaction(rr_handle h, Request r) {
       float* ms = r.maxsim ? r.maxsim + pair_begin : nullptr;
       for (const Seg& g : segs)
         RR_RUN(m, st, RR_K_TAIL, 2.0 * g.n * (double)g.S * Lq * D, 4.0 * g.n * ((double)g.S * D + (double)Lc * Lq),
-               rr_launch_li_scores(r.query_li, cli + g.r0 * D, cm + g.r0, g.n, K, Lq, g.S, Lc, D, pair_begin + (int)g.p0,
+               rr_launch_li_scores(qli, cli + g.r0 * D, cm + g.r0, g.n, K, Lq, g.S, Lc, D, pair_begin + (int)g.p0,
                                    m->li_sc + g.p0 * Lc * Lq, ms ? ms + g.p0 : nullptr, st));
       RR_TRY(fusion_bias(m, st, plan, m->li_sc, Lq, Lc, 0, 0, r.fusion_mult, 0, &adj_ld));
       adj = m->adj;
@@ -2310,6 +2509,61 @@ static int forward_interaction(rr_handle h, Request r) {
   const std::vector<Seg> one{Seg{n, Lq, Lq, 0, 0, 0}};
   RR_TRY(run_heads(m, st, w, one, r));
   return range_guard_exit(m, st);
+}
+
+// rr_forward_interaction_bank (include/rerank_mi355.h): everything about the bank, the segment table and the per-pair indices is
+// checked here, on the host; forward_interaction then checks what it checks for a packed call, stages the descriptors and runs.
+static int forward_interaction_bank(rr_handle h, rr_bank* b, const float* query_li, const float* query_mask, int n_queries, int Lq,
+                                    const int32_t* pair_passage, const int32_t* pair_query, int n_segments, const int32_t* seg_pairs,
+                                    const int32_t* seg_len, int padded_context_len, int fusion_from_li, float fusion_multiplier,
+                                    float* logits_out, float* logits2_out, float* maxsim_out, void* hip_stream) {
+  const char* what = "rr_forward_interaction_bank";
+  if (!h) return RR_ERR_BAD_ARG;
+  rr_model* m = h;
+  const rr_config& c = m->cfg;
+  if (!b || !query_li || !query_mask || !pair_passage || !pair_query || !seg_pairs || !seg_len || !logits_out)
+    return fail(m, RR_ERR_BAD_ARG, "%s: null argument", what);
+  if (c.model_kind == RR_MODEL_FULL_CONTEXT) return fail(m, RR_ERR_BAD_ARG, "%s on a full-context model", what);
+  if (b->device != c.device) return fail(m, RR_ERR_BAD_ARG, "%s: the bank lives on device %d, the handle on %d", what, b->device, c.device);
+  if (b->D != c.li_dim) return fail(m, RR_ERR_BAD_SHAPE, "%s: the bank holds rows of %d, the handle's li_dim is %d", what, b->D, c.li_dim);
+  if (fusion_from_li && c.model_kind == RR_MODEL_MORES)
+    return fail(m, RR_ERR_UNSUPPORTED, "Attention adj is not implemented for MORES");   // mores_model.py:72-73
+  if (maxsim_out && !fusion_from_li) return fail(m, RR_ERR_BAD_ARG, "%s: maxsim_out needs fusion_from_li", what);
+  if (((uintptr_t)query_li) & 15) return fail(m, RR_ERR_BAD_ARG, "%s: query_li must be 16-byte aligned", what);
+  hipStream_t st = (hipStream_t)hip_stream;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return fail(m, RR_ERR_BAD_ARG, "%s cannot be captured into a graph (it stages its descriptors from the host)", what);
+  if (n_queries <= 0 || Lq <= 0 || padded_context_len <= 0)
+    return fail(m, RR_ERR_BAD_SHAPE, "%s: n_queries=%d Lq=%d padded_context_len=%d", what, n_queries, Lq, padded_context_len);
+  if (n_segments <= 0 || n_segments > 64) return fail(m, RR_ERR_BAD_SHAPE, "%s: %d segments (1..64)", what, n_segments);
+  long long pairs = 0;
+  for (int s = 0; s < n_segments; ++s) {
+    if (seg_pairs[s] <= 0 || seg_len[s] <= 0 || seg_len[s] > padded_context_len)
+      return fail(m, RR_ERR_BAD_SHAPE, "%s: segment %d holds %d pairs of length %d (lengths in (0, %d])", what, s, seg_pairs[s], seg_len[s],
+                  padded_context_len);
+    pairs += seg_pairs[s];
+  }
+  if (pairs > (1 << 24)) return fail(m, RR_ERR_BAD_SHAPE, "%s: %lld pairs", what, pairs);
+  const long long held = (long long)b->first.size();
+  std::vector<rr_bank_pair> staged((size_t)pairs);
+  size_t i = 0;
+  for (int s = 0; s < n_segments; ++s)
+    for (int k = 0; k < seg_pairs[s]; ++k, ++i) {
+      const int32_t pi = pair_passage[i], qi = pair_query[i];
+      if (pi < 0 || pi >= held) return fail(m, RR_ERR_BAD_SHAPE, "%s: pair %zu names passage %d, the bank holds %lld", what, i, pi, held);
+      if (qi < 0 || qi >= n_queries) return fail(m, RR_ERR_BAD_SHAPE, "%s: pair %zu names query %d of %d", what, i, qi, n_queries);
+      if (b->len[(size_t)pi] > seg_len[s])
+        return fail(m, RR_ERR_BAD_SHAPE, "%s: pair %zu: passage %d holds %d rows, its segment %d", what, i, pi, b->len[(size_t)pi], seg_len[s]);
+      staged[i] = rr_bank_pair{b->first[(size_t)pi], b->len[(size_t)pi], qi};
+    }
+  Request r;
+  r.family = FAM_INTERACTION; r.query_li = query_li; r.query_mask = query_mask;
+  r.fusion_from_li = fusion_from_li != 0; r.maxsim = maxsim_out; r.fusion_mult = fusion_multiplier;
+  r.packed = true; r.n_segments = n_segments; r.seg_pairs = seg_pairs; r.seg_len = seg_len; r.len = padded_context_len; r.q_len = Lq;
+  r.logits = logits_out; r.logits2 = logits2_out; r.stream = st;
+  r.bank = b; r.bank_pairs = &staged;
+  return forward_interaction(h, r);
 }
 
 // rr_li_scores (include/rerank_mi355.h): the stand-alone operator, any model kind; every check before anything is enqueued
@@ -2898,6 +3152,34 @@ int rr_forward_interaction_packed_fusion_li(rr_handle h, const float* query_li, 
     r.logits = logits_out; r.logits2 = logits2_out; r.stream = (hipStream_t)hip_stream;
     return forward_interaction(h, r);
   });
+}
+int rr_bank_create(rr_handle h, int64_t capacity_rows, int32_t max_passages, rr_bank_handle* out) {
+  return guarded(h, [&]() -> int { return rr_bank_create_impl(h, capacity_rows, max_passages, out); });
+}
+int rr_bank_destroy(rr_bank_handle b) { return guarded(nullptr, [&]() -> int { return rr_bank_destroy_impl(b); }); }
+int rr_bank_clear(rr_bank_handle b) {
+  if (!b) return RR_ERR_BAD_ARG;
+  b->first.clear();
+  b->len.clear();
+  b->used_rows = 0;
+  return RR_OK;
+}
+const char* rr_bank_last_error(rr_bank_handle b) { return b ? b->err.c_str() : ""; }
+int rr_bank_info(rr_bank_handle b, int32_t* passages_out, int64_t* rows_used_out, int64_t* capacity_rows_out) {
+  if (!b) return RR_ERR_BAD_ARG;
+  if (passages_out) *passages_out = (int32_t)b->first.size();
+  if (rows_used_out) *rows_used_out = b->used_rows;
+  if (capacity_rows_out) *capacity_rows_out = b->cap_rows;
+  return RR_OK;
+}
+int rr_bank_add(rr_bank_handle b, const void* context_li, int dtype, const float* context_mask, const int32_t* lengths, int n, int Lc, int32_t* first_index_out, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_bank_add_impl(b, context_li, dtype, context_mask, lengths, n, Lc, first_index_out, hip_stream); });
+}
+int rr_bank_read(rr_bank_handle b, int32_t index, uint16_t* rows_out, uint8_t* mask_out, int32_t capacity_rows, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_bank_read_impl(b, index, rows_out, mask_out, capacity_rows, hip_stream); });
+}
+int rr_forward_interaction_bank(rr_handle h, rr_bank_handle b, const float* query_li, const float* query_mask, int n_queries, int Lq, const int32_t* pair_passage, const int32_t* pair_query, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int padded_context_len, int fusion_from_li, float fusion_multiplier, float* logits_out, float* logits2_out, float* maxsim_out, void* hip_stream) {
+  return guarded(h, [&]() -> int { return forward_interaction_bank(h, b, query_li, query_mask, n_queries, Lq, pair_passage, pair_query, n_segments, seg_pairs, seg_len, padded_context_len, fusion_from_li, fusion_multiplier, logits_out, logits2_out, maxsim_out, hip_stream); });
 }
 int rr_li_scores(rr_handle h, const float* query_li, const float* context_li, const float* context_mask, int Bq, int K, int Lq, int Lc, int pair_begin, int pair_end, float* scores_out, float* maxsim_out, void* hip_stream) {
   return guarded(h, [&]() -> int { return li_scores_call(h, query_li, context_li, context_mask, Bq, K, Lq, Lc, pair_begin, pair_end, scores_out, maxsim_out, hip_stream); });

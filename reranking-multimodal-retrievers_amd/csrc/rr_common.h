@@ -441,3 +441,14 @@ hipError_t rr_launch_assemble_pairs(const int32_t* pool, long long pool_len, con
 struct rr_asm_joint { int32_t qoff, ql, coff, m, ctx_w, len, row0, unused0; };
 hipError_t rr_launch_assemble_joint(const int32_t* pool, long long pool_len, const rr_asm_joint* pairs, int n_pairs, long long sep,
                                     long long pad, int64_t* ids, int64_t* am, hipStream_t st);
+
+// Passage bank (passage_bank.hip).  rr_bank_slot: one passage of an rr_bank_add as the host stages it (its first row in the bank,
+// its length).  rr_bank_pair: one packed pair of rr_forward_interaction_bank (the passage's first bank row and length, the pair's
+// query), checked against the bank, the segment and n_queries before it is staged.
+struct rr_bank_slot { int64_t first_row; int32_t len, unused0; };
+struct rr_bank_pair { int64_t first_row; int32_t len, query; };
+hipError_t rr_launch_bank_ingest(const void* src, int src_f16, const float* mask, const rr_bank_slot* slots, int n, int Lc, int D,
+                                 uint16_t* rows, uint8_t* mask_bytes, hipStream_t st);
+hipError_t rr_launch_bank_gather(const rr_bank_pair* pairs, int n, int Lq, int S, int D, const float* query_li,
+                                 const float* query_mask, const uint16_t* rows, const uint8_t* mask_bytes, bf16_t* li16, int dt,
+                                 float* qmask_out, float* cmask_out, float* q32_out, float* c32_out, hipStream_t st);

@@ -740,6 +740,67 @@ class RerankEngine:
         out.update(extra)
         return out
 
+    def create_bank(self, capacity_rows: int, max_passages: int):
+        """A device-resident passage-embedding bank (rr_bank_create; passage_bank.PassageBank) of `capacity_rows` token rows
+        and at most `max_passages` passages on this engine's device with its li_dim.  It outlives the engine and serves every
+        interaction engine of the device with the same li_dim (NORMAL and MORES)."""
+        from .passage_bank import PassageBank
+        return PassageBank(self, capacity_rows, max_passages)
+
+    def forward_interaction_bank(self, bank, query_li: torch.Tensor, query_mask: torch.Tensor, passage_ids, Bq: int, K: int,
+                                 labels: Optional[torch.Tensor] = None, list_sizes: Optional[Sequence[int]] = None,
+                                 granule: int = 16, segment_cost_rows: int = 0, fusion_from_li: bool = False,
+                                 fusion_multiplier: float = 1.0, want_maxsim: bool = False, want_scores: bool = False,
+                                 want_order: bool = False, want_loss: bool = True, pair_range=None,
+                                 padded_len: Optional[int] = None, plan: Optional[dict] = None):
+        """`forward_interaction_packed` with the context side named by passage id and read from `bank`
+        (rr_forward_interaction_bank, NORMAL and MORES): `query_li` [Bq, Lq, D] / `query_mask` [Bq, Lq] per query, `passage_ids`
+        the N = Bq * K candidates in pair order (`list_sizes` in place of (Bq, K), both None then: lists of unequal length).  The
+        context lengths come from the bank's host table, so nothing is copied from the device to group the pairs, nothing is
+        uploaded or packed for the context side, and a passage may serve any number of pairs.  `padded_len`: the context length
+        the padded call would use (the fusion normalisers, the attention schedule and NORMAL's position limit follow it);
+        default: the longest Lc an `add` of the bank has seen.  `plan`: passage_bank.plan_bank_batch's result for this call,
+        when the ids were looked up and grouped already (`passage_ids` is not read then).  An id the bank does not hold raises
+        KeyError naming it.  Logits: bit for bit those of forward_interaction_packed on float32(bank rows) and the bank's masks;
+        on an fp16 engine also those of the call on the original float32 tensors (include/rerank_mi355.h).  `pair_range` and
+        sharded slices are not covered.  Returns the dict of forward_interaction_packed."""
+        import numpy as np
+        from .passage_bank import plan_bank_batch
+        if pair_range is not None:
+            raise ValueError("forward_interaction_bank does not take pair_range: the sharded path and slices are not packed")
+        if want_maxsim and not fusion_from_li:
+            raise ValueError("want_maxsim needs fusion_from_li=True (or call li_scores)")
+        dev = self.device
+        Lc = int(bank.padded_len if padded_len is None else padded_len)
+        if plan is None:
+            plan = plan_bank_batch(bank.table, passage_ids, K if list_sizes is None else None, list_sizes, Lc, granule,
+                                   segment_cost_rows)
+        N = int(plan["indices"].size)
+        if list_sizes is None:
+            assert N == Bq * K and query_li.shape[0] == Bq, f"{tuple(query_li.shape)}, {N} passages, {K - 1}"
+        Bq, K, _ = self._layout(N, Bq, K, list_sizes, None)
+        assert query_li.shape[0] == Bq, f"{tuple(query_li.shape)}: one query per list, {Bq} lists"
+        Lq = query_li.shape[1]
+        f32 = dict(device=dev, dtype=torch.float32)
+        q = query_li.to(**f32).contiguous()
+        qm = query_mask.reshape(Bq, Lq).to(**f32).contiguous()
+        pp = np.ascontiguousarray(plan["pair_passage"], dtype=np.int32)
+        pq = np.ascontiguousarray(plan["pair_query"], dtype=np.int32)
+        extra = {}
+
+        def launch(order, seg_n, seg_len, sn, sl, lp, lp2):
+            mp = torch.empty(N, **f32) if want_maxsim else None
+            L.check(self.lib.rr_forward_interaction_bank(self.h, bank.h, L.ptr(q), L.ptr(qm), Bq, Lq, pp.ctypes.data, pq.ctypes.data,
+                                                         len(seg_n), sn, sl, Lc, int(bool(fusion_from_li)), float(fusion_multiplier),
+                                                         L.ptr(lp), L.ptr(lp2), L.ptr(mp), self._stream()),
+                    self.h, "rr_forward_interaction_bank")
+            if want_maxsim:
+                extra["maxsim"] = scatter_packed(mp, order)
+        out = self._packed(launch, (), plan["lengths"], Lc, 1, granule, segment_cost_rows, Bq, K, labels, want_loss, want_scores,
+                           want_order, list_sizes=list_sizes, n_pairs=N, grouping=(plan["order"], plan["seg_n"], plan["seg_len"]))
+        out.update(extra)
+        return out
+
     def li_scores(self, query_li: torch.Tensor, context_li: torch.Tensor, context_mask: torch.Tensor, Bq: int, K: int,
                   pair_range: Optional[Sequence[int]] = None, want_scores: bool = True, want_maxsim: bool = True) -> dict:
         """The frozen retriever's score of every pair and the matrix behind it (rr_li_scores; colbert_score,
@@ -863,7 +924,7 @@ class RerankEngine:
 
     def _packed(self, launch, rows, lengths, padded_len: int, floor: int, granule: int, segment_cost_rows: int, Bq: int, K: int,
                 labels, want_loss: bool, want_scores: bool, want_order: bool, joint: bool = False, host_order: bool = False,
-                list_sizes=None, pair_lists=None, n_pairs: Optional[int] = None) -> dict:
+                list_sizes=None, pair_lists=None, n_pairs: Optional[int] = None, grouping=None) -> dict:
         """What the packed forwards share: the pairs' lengths (`lengths` from the host, else derived from the [N, padded_len]
         tensors `rows` on the device: one device -> host copy) -> segments (group_pairs_by_length) -> the pair order on the
         device -> the ctypes segment tables -> `launch(order, seg_n, seg_len, seg_pairs, seg_lens, logits, logits2)` (with
@@ -871,14 +932,19 @@ class RerankEngine:
         scattered back to pair order -> the scoring head over them.
         `list_sizes` in place of (Bq, K): lists of unequal length; the head is rr_head_lists over the PACKED logits with the
         packed order's inverse as its gather, and the result also holds `list_loss`; `order` is flat [N], local to each list.
-        `pair_lists` without `list_sizes` (a rank's slice of a sharded batch): logits only, no head."""
+        `pair_lists` without `list_sizes` (a rank's slice of a sharded batch): logits only, no head.
+        `grouping`: (order, seg_pairs, seg_len) as group_pairs_by_length returned them for these lengths, when the caller has
+        grouped already (passage_bank.plan_bank_batch, on another thread); nothing is derived then."""
         N = Bq * K if n_pairs is None else n_pairs
         assert granule > 0
         if labels is not None:
             assert labels.numel() == N
-        if lengths is None:
-            lengths = pair_lengths(*rows).cpu().numpy()
-        order_h, seg_n, seg_len = group_pairs_by_length(lengths, padded_len, granule, floor, segment_cost_rows)
+        if grouping is not None:
+            order_h, seg_n, seg_len = grouping
+        else:
+            if lengths is None:
+                lengths = pair_lengths(*rows).cpu().numpy()
+            order_h, seg_n, seg_len = group_pairs_by_length(lengths, padded_len, granule, floor, segment_cost_rows)
         assert len(order_h) == N, "one length per pair"
         order = torch.from_numpy(order_h).to(self.device, non_blocking=True)
         lp, lp2 = (torch.empty(N, dtype=torch.float32, device=self.device) for _ in range(2))
@@ -1124,7 +1190,9 @@ class InteractionRerankModel(_DropIn):
     `forward` takes the optional keyword `candidates_per_query` of FullContextRerankModel (lists of unequal length; needs
     `packed_rows`; no reference counterpart), and `fusion_from_li=True` in place of `preflmr_scores`: the attention fusion then
     runs on the retriever's scores computed from the call's own late-interaction tensors (RerankEngine.li_scores; what the
-    executor passes as `retrieval_results.scores_raw`), `want_maxsim=True` adds them per pair as `maxsim`."""
+    executor passes as `retrieval_results.scores_raw`), `want_maxsim=True` adds them per pair as `maxsim`.
+    `create_bank` / `forward_passages`: the candidates' embeddings in a device-resident bank (passage_bank.PassageBank), named by
+    passage id per call; `rerank_dataset_pipelined` runs the executor's loop from it."""
 
     def __init__(self, config, state_dict: Optional[Dict[str, torch.Tensor]] = None, device=None):
         super().__init__()
@@ -1133,8 +1201,39 @@ class InteractionRerankModel(_DropIn):
         arch = make_arch(config, model_kind=kind, has_vision=0)
         self.engine = RerankEngine(arch, device)
         self.packed_rows = bool(_get(config, "packed_rows", False))
+        self.bank = None                      # create_bank / forward_passages
         if state_dict is not None:
             self.engine.load_state_dict(state_dict)
+
+    def create_bank(self, capacity_rows: int, max_passages: int):
+        """Give the model a passage-embedding bank (RerankEngine.create_bank) and return it; `bank` may also be assigned a bank
+        another model of the same device and li_dim created."""
+        self.bank = self.engine.create_bank(capacity_rows, max_passages)
+        return self.bank
+
+    def forward_passages(self, query_late_interaction, query_mask, passage_ids, num_negative_examples, labels=None,
+                         candidates_per_query=None, fusion_from_li=False, fusion_multiplier=1, **kw) -> RerankOutput:
+        """`forward` with the candidates named by passage id and their embeddings read from `self.bank`
+        (RerankEngine.forward_interaction_bank; always over packed rows): the output `forward` gives for the banked tensors.
+        `candidates_per_query` as `forward` takes it.  No reference counterpart (its executor recomputes the embeddings per
+        query, Reranker_base_executor.py:877-885)."""
+        if self.bank is None:
+            raise RuntimeError("forward_passages needs a bank: model.create_bank(capacity_rows, max_passages), then bank.add(...)")
+        Bq, N = query_late_interaction.size(0), len(passage_ids)
+        common = dict(fusion_from_li=bool(fusion_from_li), fusion_multiplier=float(fusion_multiplier), **kw)
+        if candidates_per_query is not None:
+            sizes = [int(k) for k in candidates_per_query]
+            assert sizes and min(sizes) >= 1 and sum(sizes) == N and len(sizes) == Bq, \
+                f"candidates_per_query {sizes} must be positive, one per query, and sum to the {N} passages"
+            common.setdefault("want_order", True)
+            r = self.engine.forward_interaction_bank(self.bank, query_late_interaction, query_mask, passage_ids, None, None,
+                                                     self._labels(labels, N), list_sizes=sizes, **common)
+            return self._output(r, self._flat_logits(r))
+        K = num_negative_examples + 1
+        assert Bq * K == N, f"{query_late_interaction.shape}, {N} passages, {num_negative_examples}"
+        r = self.engine.forward_interaction_bank(self.bank, query_late_interaction, query_mask, passage_ids, Bq, K,
+                                                 self._labels(labels, N), **common)
+        return self._output(r, self._ranked_logits(r, Bq, K))
 
     def forward(self, query_late_interaction, context_late_interaction, num_negative_examples, query_mask,
                 context_mask, preflmr_scores=None, fusion_multiplier=1, labels=None, candidates_per_query=None,

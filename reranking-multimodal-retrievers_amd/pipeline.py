@@ -16,7 +16,12 @@ tokens); rr_assemble_joint builds the joint rows on the device and RerankEngine.
 rr_forward_joint_packed and rr_head_joint.  Records and metrics are those of rerank_dataset driven by RerankModel.forward
 with `packed_rows` over the reference's padded inputs.
 
-The device side is a `stages` object (DeviceStages for a FullContextRerankModel, JointStages for a RerankModel) with
+For the interaction rerankers (NORMAL, MORES) InteractionStages runs the loop from the frozen retriever's embeddings: the query's
+late-interaction tensors travel with the query, the passages' are in the model's device-resident bank (passage_bank.PassageBank)
+and are named by id.  Records and metrics are those of rerank_dataset driven by InteractionRerankModel.forward_passages.
+
+The device side is a `stages` object (DeviceStages for a FullContextRerankModel, JointStages for a RerankModel,
+InteractionStages for an InteractionRerankModel) with
   new_slot() -> slot                     (calling thread; pinned host buffers)
   prepare(batch, slot) -> item           (producer thread; host work only)
   submit(batch, item) -> pending         (calling thread; enqueues everything, blocks on nothing)
@@ -312,6 +317,91 @@ class JointStages(DeviceStages):
         return dict(uploaded=uploaded, done=done, host=host, keep=(up, cls, patches, r), sizes=item.get("sizes"))
 
 
+class InteractionStages(DeviceStages):
+    """The device side of rerank_dataset_pipelined for an `InteractionRerankModel` with a passage bank (model.bank): a query
+    carries its own late-interaction tensors "query_late_interaction" [Lq, D] and "query_mask" [Lq] and names its candidates
+    by "passage_id"; their embeddings are in the bank.  The producer thread fills a pinned slot with the batch's query tensors,
+    looks the passages up (an id the bank does not hold raises KeyError naming it, which reaches the caller), groups the pairs
+    into segments (passage_bank.plan_bank_batch) and builds the labels; the calling thread uploads the slot and runs
+    RerankEngine.forward_interaction_bank.  `granule` / `segment_cost_rows` as that call takes them."""
+
+    def __init__(self, model, batch_queries: int, K: int, first_query: dict, ragged: bool = False, granule: int = 16,
+                 segment_cost_rows: int = 0):
+        import torch
+        self.torch = torch
+        self.model, self.engine = model, model.engine
+        if getattr(model, "bank", None) is None:
+            raise ValueError("rerank_dataset_pipelined needs model.bank (InteractionRerankModel.create_bank) for an interaction model")
+        self.bank = model.bank
+        self.K, self.batch_queries, self.ragged = int(K), int(batch_queries), bool(ragged)
+        self.granule, self.segment_cost_rows = int(granule), int(segment_cost_rows)
+        q = torch.as_tensor(first_query["query_late_interaction"])
+        assert q.dim() == 2 and q.shape[1] == self.bank.li_dim, f"query_late_interaction must be [Lq, {self.bank.li_dim}]"
+        self.Lq, self.D = int(q.shape[0]), int(q.shape[1])
+        self.pointwise = self.engine.arch["loss_fn"] != "negative_sampling"
+        self.device = self.engine.device
+        self.copy_stream = None                         # created by the first submit (the calling thread)
+
+    def new_slot(self, pin_memory: bool = True) -> dict:
+        torch, nq = self.torch, self.batch_queries
+        return dict(q=torch.empty((nq, self.Lq, self.D), dtype=torch.float32, pin_memory=pin_memory),
+                    qm=torch.empty((nq, self.Lq), dtype=torch.float32, pin_memory=pin_memory),
+                    labels=torch.empty(nq * self.K, dtype=torch.float32, pin_memory=pin_memory))
+
+    def prepare(self, batch: List[dict], slot: dict) -> dict:
+        from .passage_bank import plan_bank_batch
+        torch, K = self.torch, self.K
+        ids, labels = [], []
+        for q in batch:
+            docs = q["retrieved_docs"]
+            if self.ragged:
+                assert 1 <= len(docs) <= K, f"query {q.get('question_id')}: {len(docs)} retrieved docs, the slots hold 1..{K}"
+            else:
+                assert len(docs) == K, f"query {q.get('question_id')}: {len(docs)} retrieved docs, the loop reranks {K}"
+            ids += [d["passage_id"] for d in docs]
+            if self.pointwise:                       # Reranker_base_executor.py:829-832
+                pos = q["pos_item_ids"]
+                labels += [1.0 if d["passage_id"] in pos else 0.0 for d in docs]
+        n = len(batch)
+        sizes = [len(q["retrieved_docs"]) for q in batch] if self.ragged else None
+        qs, qms = slot["q"][:n], slot["qm"][:n]
+        for i, q in enumerate(batch):
+            qs[i].copy_(torch.as_tensor(q["query_late_interaction"], dtype=torch.float32).reshape(self.Lq, self.D))
+            qms[i].copy_(torch.as_tensor(q["query_mask"], dtype=torch.float32).reshape(self.Lq))
+        lab = None
+        if self.pointwise:
+            lab = slot["labels"][:len(labels)]
+            lab.copy_(torch.tensor(labels, dtype=torch.float32))
+        plan = plan_bank_batch(self.bank.table, ids, None if self.ragged else K, sizes, self.bank.padded_len, self.granule,
+                               self.segment_cost_rows)
+        return dict(n=n, q=qs, qm=qms, labels=lab, plan=plan, sizes=sizes)
+
+    def submit(self, batch: List[dict], item: dict) -> dict:
+        torch, eng, dev = self.torch, self.engine, self.device
+        n, K = item["n"], self.K
+        if self.copy_stream is None:
+            self.copy_stream = torch.cuda.Stream(dev)
+        cs = torch.cuda.current_stream(dev)
+        with torch.cuda.stream(self.copy_stream):       # allocated and filled on the copy stream, used on the compute stream
+            up = [torch.empty(t.shape, dtype=t.dtype, device=dev).copy_(t, non_blocking=True) if t is not None else None
+                  for t in (item["q"], item["qm"], item["labels"])]
+            uploaded = torch.cuda.Event()
+            uploaded.record(self.copy_stream)
+        cs.wait_event(uploaded)
+        for t in up:
+            if t is not None:
+                t.record_stream(cs)
+        q_d, qm_d, labels_d = up
+        kw = dict(want_order=True, granule=self.granule, segment_cost_rows=self.segment_cost_rows, plan=item["plan"])
+        if self.ragged:
+            r = eng.forward_interaction_bank(self.bank, q_d, qm_d, None, None, None, labels_d, list_sizes=item["sizes"], **kw)
+        else:
+            r = eng.forward_interaction_bank(self.bank, q_d, qm_d, None, n, K, labels_d, **kw)
+        host, done = self._read_back(r, n, item.get("sizes"), cs)
+        # the batch's device buffers stay referenced here until `done` has been waited for
+        return dict(uploaded=uploaded, done=done, host=host, keep=(up, r), sizes=item.get("sizes"))
+
+
 def rerank_dataset_pipelined(queries: Iterable[dict], model, batch_queries: int, Ks: Sequence[int],
                              docs_to_rerank: Optional[int] = None, out_path: Optional[str] = None, stages=None,
                              stats: Optional[dict] = None, ragged: bool = False) -> dict:
@@ -321,9 +411,12 @@ def rerank_dataset_pipelined(queries: Iterable[dict], model, batch_queries: int,
     a retrieved passage is in pos_item_ids for pointwise losses, none for negative_sampling.  For a RerankModel it has
     "query_input_ids" / "query_attention_mask" (max_query_length entries each, as the dataset gives them) and "pixel_values"
     (mandatory: a query without it raises NotImplementedError, as RerankModel.forward does); its loss reads no labels.
+    For an InteractionRerankModel with a passage bank (model.bank) it has "query_late_interaction" [Lq, D] and "query_mask" [Lq],
+    the retrieved passages are looked up in the bank by "passage_id" (KeyError for one it does not hold), labels as above.
     K = docs_to_rerank, else the first query's retrieved-doc count; a query with another count raises AssertionError.
     Returns {"metrics", "output"} and writes `out_path` as rerank_dataset does.  `stages`: the device side (default
-    JointStages(model, ...) for a RerankModel, else DeviceStages(model, ...)).  `stats`, when given, receives batches, tokenise_ms (producer time in `prepare`) and
+    JointStages(model, ...) for a RerankModel, InteractionStages(model, ...) for an InteractionRerankModel, else
+    DeviceStages(model, ...)).  `stats`, when given, receives batches, tokenise_ms (producer time in `prepare`) and
     records_ms (calling-thread time building records).
     `ragged`: a batch is the next `batch_queries` queries whatever the lengths of their retrieved lists (1 or more docs each);
     `docs_to_rerank`, if given, is the most a list may hold and longer lists are cut to it, else the longest list sizes the
@@ -340,8 +433,9 @@ def rerank_dataset_pipelined(queries: Iterable[dict], model, batch_queries: int,
     if first is not None:
         if stages is None:
             K = docs_to_rerank if docs_to_rerank is not None else len(first["retrieved_docs"])
-            from .model import RerankModel
-            kind = JointStages if isinstance(model, RerankModel) else DeviceStages
+            from .model import InteractionRerankModel, RerankModel
+            kind = JointStages if isinstance(model, RerankModel) else \
+                InteractionStages if isinstance(model, InteractionRerankModel) else DeviceStages
             if ragged:
                 if docs_to_rerank is None:           # the longest list sizes the slots
                     rest = list(it)

@@ -527,6 +527,54 @@ int rr_bank_info(rr_bank_handle b, int32_t* passages_out, int64_t* rows_used_out
  * capturable into a graph (RR_ERR_BAD_ARG under stream capture). */
 int rr_bank_add(rr_bank_handle b, const void* context_li, int dtype, const float* context_mask, const int32_t* lengths, int n, int Lc,
                 int32_t* first_index_out, void* hip_stream);
+/* ---- Compressed bank: the rows as a ColBERTv2 / PLAID index stores them (one int32 centroid code and li_dim * nbits / 8 bytes of
+ * bucketised residual per token, third_party/ColBERT/colbert/indexing/index_saver.py:33-46; every reference config builds its index
+ * with "nbits": 8), decoded on the device inside the gather of rr_forward_interaction_bank.  Replaces the reference's own native
+ * kernel on the retriever-to-reranker hand-over (third_party/ColBERT/colbert/indexing/codecs/decompress_residuals.cu) and the
+ * F.normalize behind it (codecs/residual.py:242-278).  Bytes per token at li_dim 128: 257 as fp16, 133 / 69 / 37 / 21 at nbits 8 /
+ * 4 / 2 / 1.  Nothing here compresses, searches or computes embeddings.
+ *
+ * THE DECODED ROW, for a row with code c, residual bytes r[0 .. D * nbits / 8), centroids [C, D] fp16 (the index stores them with
+ * .half(), residual.py:161) and float32 bucket weights w[2^nbits]:
+ *   element e lies in byte j = e / (8 / nbits), group g = e % (8 / nbits) counted from the MOST significant end;
+ *   x = (r[j] >> (8 - nbits * (g + 1))) & (2^nbits - 1); bucket = x with its nbits bits reversed (binarize writes the bucket's bit
+ *   0 first and np.packbits fills bytes MSB-first, residual.py:188-204; reversed_bit_map and decompression_lookup_table, :51-95,
+ *   undo exactly that);
+ *   s_e = float(centroid[c][e]) + w[bucket], one float32 add;
+ *   n = sqrtf(sum_e s_e^2) in float32, summed in ONE fixed order: per chunk of 8 consecutive elements an fmaf chain from zero,
+ *   element 0 first (q = fmaf(s_0, s_0, 0); q = fmaf(s_k, s_k, q), k = 1..7), then the D / 8 chunk sums added as a pairwise tree over
+ *   neighbours (q_0 + q_1, q_2 + q_3, ...; again on the results, until one is left);
+ *   y_e = fp16_rne(s_e / fmaxf(n, 1e-12f)), square root and divide correctly rounded.
+ * That is the reference's CPU branch (residual.py:264-275) followed by the .half() the bank applies to everything it keeps.  The
+ * gather rounds to fp16 FIRST and then converts fp16 -> float32 -> the handle's operand type as it does for an fp16 bank's rows:
+ * a compressed bank is bit for bit an fp16 bank that holds the decoded rows, on fp16 and bf16 handles and in the float32 copies of
+ * the attention fusion.  rr_util_plaid_decode_rows (rerank_mi355_diag.h) is this definition in host code.
+ *
+ * rr_bank_create_plaid: rr_bank_create for compressed rows.  nbits in {1, 2, 4, 8}; h's li_dim a power of two in [8, 512] and a
+ * multiple of 8 * nbits (the reference asserts that, residual.py:195): RR_ERR_UNSUPPORTED otherwise.
+ *   centroids_f16  : HOST [n_centroids, li_dim] fp16 bits (centroids.pt)
+ *   bucket_weights : HOST float32 [2^nbits]        (the second tensor of buckets.pt)
+ * Both are copied to the device before the call returns; per row of capacity the bank allocates the code, the residual bytes and
+ * the mask byte.  Everything rr_bank_create says about lifetime, sharing between handles and thread safety holds.
+ * rr_bank_add_plaid: append n passages, rows concatenated passage after passage as the index stores them, R = sum lengths.
+ *   codes     : HOST int32 [R]                       residuals : HOST uint8 [R, li_dim * nbits / 8]
+ *   mask      : HOST uint8 [R], or NULL = all ones (the ColBERT indexer has dropped the skiplist tokens already)
+ *   lengths   : HOST int32 [n], every length >= 1 (doclens)
+ * Checked on the host before anything is enqueued, a refused call leaves the bank unchanged: every length >= 1 and every code in
+ * [0, n_centroids) (RR_ERR_BAD_SHAPE), the row and the passage capacity (RR_ERR_OOM).  A LOAD-TIME call: it copies from the
+ * caller's host memory on hip_stream and synchronises that stream, so the host buffers may be reused when it returns; not
+ * capturable into a graph (RR_ERR_BAD_ARG under stream capture).
+ * rr_bank_format: nbits (0 for an fp16 bank), the number of centroids (0) and the device bytes one row takes (mask byte included);
+ * any pointer may be NULL.
+ * The two formats do not mix: rr_bank_add on a compressed bank and rr_bank_add_plaid on an fp16 bank return RR_ERR_UNSUPPORTED.
+ * rr_bank_clear / rr_bank_info / rr_bank_destroy / rr_bank_read and rr_forward_interaction_bank take either kind unchanged.
+ * Python: rmr_amd.PlaidCodec, RerankEngine.create_bank(codec=...), PassageBank.add_compressed / load_plaid_index,
+ * rmr_amd.read_plaid_index. */
+int rr_bank_create_plaid(rr_handle h, int64_t capacity_rows, int32_t max_passages, int nbits, int32_t n_centroids,
+                         const uint16_t* centroids_f16, const float* bucket_weights, rr_bank_handle* out);
+int rr_bank_add_plaid(rr_bank_handle b, const int32_t* codes, const uint8_t* residuals, const uint8_t* mask, const int32_t* lengths,
+                      int n, int32_t* first_index_out, void* hip_stream);
+int rr_bank_format(rr_bank_handle b, int32_t* nbits_out, int32_t* n_centroids_out, int64_t* bytes_per_row_out);
 /* rr_forward_interaction_bank: rr_forward_interaction_packed (fusion_from_li != 0: rr_forward_interaction_packed_fusion_li) with
  * the context side taken from a bank.  NORMAL and MORES handles.
  *   query_li [n_queries, Lq, li_dim], query_mask [n_queries, Lq] : DEVICE float32, per QUERY (query_li 16-byte aligned)
@@ -535,7 +583,8 @@ int rr_bank_add(rr_bank_handle b, const void* context_li, int dtype, const float
  *   n_segments / seg_pairs / seg_len / padded_context_len, logits_out / logits2_out / maxsim_out : as the packed calls take them
  *       (maxsim_out only with fusion_from_li).
  * One gather launch per segment writes the 16-bit [query | context] rows the cross encoder / the MORES stack consume (context
- * rows fp16 -> float32 -> the handle's operand type, zero beyond the passage's length) and the float mask rows; the rest of the
+ * rows fp16 -> float32 -> the handle's operand type, zero beyond the passage's length; the rows of a compressed bank decoded to
+ * fp16 first, see rr_bank_create_plaid) and the float mask rows; the rest of the
  * forward is the packed call's.  Without fusion nothing of size [n, Lc, li_dim] in float32 is written.  With fusion_from_li the
  * gather also writes float32 copies of the call's query and context rows into a grow-only block of the handle, which the score
  * kernel of rr_li_scores reads unchanged (cost: 4 bytes per element written and read again; the score block dominates it).

@@ -242,10 +242,25 @@ int rr_op_cls_heads(const float* h32, int T, int cols, int n_pairs, const float*
  * squares is not below range_ss (NaN included). */
 int rr_op_ln_finalize(const float* part, int nparts, int cols, float eps, int rows, float* stats, int* range_flag, float range_ss,
                       void* hip_stream);
-/* Read one passage of a bank back to HOST memory: rows_out [len, li_dim] fp16 bits, mask_out [len] bytes (either may be NULL;
+/* Read one passage of a bank back to HOST memory: rows_out [len, li_dim] fp16 bits (a compressed bank: the decoded rows), mask_out [len] bytes (either may be NULL;
  * both NULL = only the length), buffers of capacity_rows rows.  Synchronises hip_stream (the stream the rr_bank_add calls went to)
  * and copies synchronously.  Returns the passage's length, or < 0 (RR_ERR_BAD_SHAPE: no such passage, buffers too small). */
 int rr_bank_read(rr_bank_handle b, int32_t index, uint16_t* rows_out, uint8_t* mask_out, int32_t capacity_rows, void* hip_stream);
+/* PLAID residual decode (the decoded row: rerank_mi355.h, rr_bank_create_plaid; replaces codecs/decompress_residuals.cu and the
+ * F.normalize of third_party/ColBERT/colbert/indexing/codecs/residual.py:242-278 of the reference).
+ * rr_util_plaid_decode_rows: pure HOST code, usable without a GPU, in the summation order of the kernels: the bit-level definition
+ * the device is held to.  centroids_f16 [n_centroids, D] fp16 bits, bucket_weights float32 [2^nbits], codes int32 [n_rows],
+ * residuals uint8 [n_rows, D * nbits / 8] -> rows_out_f16 [n_rows, D] fp16 bits.  RR_ERR_UNSUPPORTED for an nbits / D the bank does
+ * not take, RR_ERR_BAD_SHAPE for a code outside [0, n_centroids).
+ * rr_op_plaid_decode_rows: the same over raw DEVICE pointers, rows [first_row, first_row + n_rows) of codes / residuals (64-bit
+ * row offsets) -> rows_out_f16 [n_rows, D]; the device function of the bank's gather, so its bits are the gather's.  residuals
+ * 8-byte aligned, centroids and the output 16-byte aligned.  A code outside [0, n_centroids) is clamped into it (nothing outside
+ * the table is read). */
+int rr_util_plaid_decode_rows(const uint16_t* centroids_f16, int32_t n_centroids, const float* bucket_weights, int nbits, int D,
+                              const int32_t* codes, const uint8_t* residuals, int64_t n_rows, uint16_t* rows_out_f16);
+int rr_op_plaid_decode_rows(const uint16_t* centroids_f16, int32_t n_centroids, const float* bucket_weights, int nbits, int D,
+                            const int32_t* codes, const uint8_t* residuals, int64_t first_row, int64_t n_rows,
+                            uint16_t* rows_out_f16, void* hip_stream);
 
 #ifdef __cplusplus
 }

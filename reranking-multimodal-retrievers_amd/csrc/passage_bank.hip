@@ -10,10 +10,32 @@
 //                       for fp16 handles, one rounding for bf16), zero rows beyond a passage's length; the float mask rows the
 //                       bias kernel reads; and, for the attention fusion only, float32 copies of the same rows for li_scores.
 //
-// Both are copy kernels: a lane moves 8 elements (one 16-byte fp16 chunk; 32 bytes of a float32 source as two 16-byte loads),
+//   bank_gather_plaid_kernel  bank_gather_kernel over a COMPRESSED bank (rr_bank_create_plaid): a context row is a ColBERTv2 /
+//                       PLAID residual code (one int32 centroid index and D * nbits / 8 bytes of bucketised residual, as
+//                       third_party/ColBERT/colbert/indexing/index_saver.py:33-46 of the reference writes them) and is decoded in
+//                       the gather by plaid_decode8: what the reference's decompress_residuals.cu + F.normalize do
+//                       (codecs/residual.py:242-278), then rounded to fp16 FIRST and converted fp16 -> float32 -> operand type as
+//                       the fp16 bank's rows are, so that a compressed bank is bit for bit an fp16 bank of its decoded rows.
+//   bank_decode_plaid_kernel  rows [first_row, first_row + n) decoded to fp16 by the same device function (rr_bank_read on a
+//                       compressed bank, rr_op_plaid_decode_rows).
+//   rr_plaid_decode_rows_host  the same arithmetic in host code (rr_util_plaid_decode_rows): the bit-level definition.
+//
+// THE DECODED ROW (one definition, plaid_bucket / plaid_sumsq8 / the pairwise tree / plaid_finish below, compiled for both sides):
+//   element e lies in residual byte e / (8 / nbits), group g = e % (8 / nbits) counted from the most significant end;
+//   x = (byte >> (8 - nbits * (g + 1))) & (2^nbits - 1); bucket = x with its nbits bits reversed (binarize writes bit 0 first and
+//   packbits fills bytes MSB-first, residual.py:188-204);  s_e = float(centroid[code][e]) + w[bucket], one float32 add;
+//   sum of squares in float32: per 8-element chunk q = fmaf(s_7, s_7, ... fmaf(s_1, s_1, fmaf(s_0, s_0, 0)) ...), then the D / 8
+//   chunk sums are added as a pairwise tree over neighbours (q_0 + q_1, q_2 + q_3, ... and again until one is left) — the
+//   butterfly of the lane group, whose lanes all end with the same bits because a float add commutes;
+//   n = sqrtf(sum), y_e = fp16_rne(s_e / fmaxf(n, 1e-12f)): correctly rounded square root and divide on both sides.
+//
+// All four are row kernels of one shape: a lane moves 8 elements (one 16-byte fp16 chunk; 32 bytes of a float32 source as two 16-byte loads),
 // a row takes D / 8 lanes, and a wave takes 64 / (D / 8) rows (4 at D = 128, 8 at D = 64) so that no lane idles at the
 // dimensions in use; four waves per 256-thread block as the row kernels of elementwise.hip.  Row offsets are 64-bit: a bank
-// passes 4 GiB (2^31 elements) at 16.8 M rows of D = 128.  No LDS, no scratch.
+// passes 4 GiB (2^31 elements) at 16.8 M rows of D = 128.  No LDS, no scratch.  The compressed kernels need D a power of two (the
+// lane group of a row is then a power of two and the butterfly stays inside it) and never leave before the butterfly: every lane
+// of a wave reaches it, loads and stores are predicated.  The bucket weights (at most 256 floats, 1 KiB) are read through the
+// vector cache: a block decodes 16 - 32 rows, and filling LDS per block would cost a barrier and as many bytes as the rows do.
 #include "rr_common.h"
 
 namespace {
@@ -102,6 +124,182 @@ __global__ __launch_bounds__(256) void bank_gather_kernel(const rr_bank_pair* __
   }
 }
 
+// ---- PLAID residual decode.  plaid_bucket: the bucket of element k (0..7) of a lane's chunk from its NBITS residual bytes
+// (r[b] = byte b of the chunk, in memory order).
+template <int NBITS>
+__host__ __device__ __forceinline__ uint32_t plaid_bucket(const uint8_t (&r)[NBITS], int k) {
+  constexpr int per = 8 / NBITS;                       // elements per byte
+  const int g = k % per;
+  const uint32_t x = ((uint32_t)r[k / per] >> (8 - NBITS * (g + 1))) & ((1u << NBITS) - 1u);
+  return __builtin_bitreverse32(x) >> (32 - NBITS);
+}
+// the sum of squares of one 8-element chunk: an explicit fmaf chain, element 0 first
+__host__ __device__ __forceinline__ float plaid_sumsq8(const float (&s)[8]) {
+  float q = fmaf(s[0], s[0], 0.f);
+#pragma unroll
+  for (int k = 1; k < 8; ++k) q = fmaf(s[k], s[k], q);
+  return q;
+}
+// float32 -> fp16 bits, round to nearest even, in host code (the device's conversion instruction rounds the same way)
+inline uint16_t plaid_f16_bits(float f) {
+  const uint32_t u = __builtin_bit_cast(uint32_t, f), sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
+  if (a >= 0x7f800000u) return (uint16_t)(sign | (a > 0x7f800000u ? 0x7e00u : 0x7c00u));
+  if (a >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                     // rounds to 65536 or beyond: inf
+  if (a < 0x33000001u) return (uint16_t)sign;                                  // at most 2^-25: zero (the tie goes to even)
+  const int e = (int)(a >> 23) - 127;
+  uint32_t m = (a & 0x7fffffu) | 0x800000u;
+  const int shift = e >= -14 ? 13 : 13 + (-14 - e);                            // subnormal halves lose more bits
+  const uint32_t keep = m >> shift, rest = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
+  uint32_t h = e >= -14 ? (((uint32_t)(e + 15) << 10) + (keep - 0x400u)) : keep;
+  if (rest > half || (rest == half && (h & 1u))) ++h;                           // a carry into the exponent is the right value
+  return (uint16_t)(sign | h);
+}
+// the divisor of the definition
+__host__ __device__ __forceinline__ float plaid_scale(float n) { return fmaxf(n, 1e-12f); }
+
+// one lane's chunk c8 of bank row `row`: s[0..8) = centroid + bucket weight.  code is clamped to [0, C): rr_bank_add_plaid has
+// checked it on the host, rr_op_plaid_decode_rows runs over raw pointers and must not read outside the table.
+template <int NBITS>
+__device__ __forceinline__ void plaid_load8(const int32_t* __restrict__ codes, const uint8_t* __restrict__ resid,
+                                            const uint16_t* __restrict__ centroids, const float* __restrict__ weights, int C,
+                                            long long row, int D, int c8, float (&s)[8]) {
+  const int code = min(max(codes[row], 0), C - 1);
+  const uint8_t* rp = resid + (size_t)row * ((size_t)D / 8 * NBITS) + (size_t)c8 * NBITS;
+  uint8_t r[NBITS];
+  if constexpr (NBITS == 1) {
+    r[0] = rp[0];
+  } else if constexpr (NBITS == 2) {
+    const uint32_t u = *(const uint16_t*)rp;
+    r[0] = (uint8_t)u; r[1] = (uint8_t)(u >> 8);
+  } else if constexpr (NBITS == 4) {
+    const uint32_t u = *(const uint32_t*)rp;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) r[b] = (uint8_t)(u >> (8 * b));
+  } else {
+    const uint2 u = *(const uint2*)rp;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) { r[b] = (uint8_t)(u.x >> (8 * b)); r[4 + b] = (uint8_t)(u.y >> (8 * b)); }
+  }
+  float cv[8];
+  load8<true>(centroids + (size_t)code * D, c8, cv);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) s[k] = cv[k] + weights[plaid_bucket<NBITS>(r, k)];
+}
+
+// s[0..8) of a lane (zeros where the lane decodes nothing) -> the decoded values as floats that hold fp16 values.  EVERY lane
+// of the wave calls this: the butterfly over the lpr lanes of a row (lpr a power of two, the group aligned to it) is cross-lane.
+__device__ __forceinline__ void plaid_finish8(float (&s)[8], int lpr) {
+  float q = plaid_sumsq8(s);
+  for (int o = 1; o < lpr; o <<= 1) q += __shfl_xor(q, o, 64);
+  const float d = plaid_scale(sqrtf(q));
+  uint32_t h[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) h[k] = pack2<1>(s[2 * k] / d, s[2 * k + 1] / d);      // fp16 FIRST, as the fp16 bank holds it
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float2 f = unpack2<1>(h[k]);
+    s[2 * k] = f.x; s[2 * k + 1] = f.y;
+  }
+}
+
+// bank_gather_kernel with the context rows decoded from a compressed bank; outputs as there
+template <int DT, int NBITS>
+__global__ __launch_bounds__(256) void bank_gather_plaid_kernel(const rr_bank_pair* __restrict__ pairs, int n, int Lq, int S, int D,
+                                                                int lpr, int rpw, const float* __restrict__ query_li,
+                                                                const float* __restrict__ query_mask, const int32_t* __restrict__ codes,
+                                                                const uint8_t* __restrict__ resid, const uint16_t* __restrict__ centroids,
+                                                                const float* __restrict__ weights, int C,
+                                                                const uint8_t* __restrict__ mask_bytes, bf16_t* __restrict__ li16,
+                                                                float* __restrict__ qmask_out, float* __restrict__ cmask_out,
+                                                                float* __restrict__ q32_out, float* __restrict__ c32_out) {
+  const int lane = threadIdx.x & 63, sub = lane / lpr, c8 = lane - sub * lpr;
+  const int T = Lq + S;
+  const long long r = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * rpw + sub;
+  const bool live = sub < rpw && r < (long long)n * T;
+  const long long rr = live ? r : 0;                   // a dead lane computes on row 0 and stores nothing
+  const int p = (int)(rr / T), t = (int)(rr - (long long)p * T);
+  const rr_bank_pair d = pairs[p];
+  const int j = t - Lq;
+  const bool ctx = live && j >= 0, in = ctx && j < d.len;
+  float s[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) s[k] = 0.f;
+  if (in) plaid_load8<NBITS>(codes, resid, centroids, weights, C, d.first_row + j, D, c8, s);
+  plaid_finish8(s, lpr);                               // all 64 lanes
+  float* f32 = nullptr;
+  if (live && !ctx) {
+    const size_t q = (size_t)d.query * Lq + t;
+    load8<false>(query_li + q * D, c8, s);
+    if (c8 == 0) qmask_out[(size_t)p * Lq + t] = query_mask[q];
+    if (q32_out) f32 = q32_out + ((size_t)p * Lq + t) * D;
+  } else if (ctx) {
+    if (c8 == 0) cmask_out[(size_t)p * S + j] = (in && mask_bytes[d.first_row + j]) ? 1.0f : 0.0f;
+    if (c32_out) f32 = c32_out + ((size_t)p * S + j) * D;
+  }
+  if (live)
+    ((uint4*)(li16 + (size_t)r * D))[c8] =
+        make_uint4(pack2<DT>(s[0], s[1]), pack2<DT>(s[2], s[3]), pack2<DT>(s[4], s[5]), pack2<DT>(s[6], s[7]));
+  if (f32) {
+    ((float4*)f32)[2 * c8] = make_float4(s[0], s[1], s[2], s[3]);
+    ((float4*)f32)[2 * c8 + 1] = make_float4(s[4], s[5], s[6], s[7]);
+  }
+}
+
+// rows [first_row, first_row + n) of a compressed store -> out [n][D] fp16 bits
+template <int NBITS>
+__global__ __launch_bounds__(256) void bank_decode_plaid_kernel(const int32_t* __restrict__ codes, const uint8_t* __restrict__ resid,
+                                                                const uint16_t* __restrict__ centroids,
+                                                                const float* __restrict__ weights, int C, long long first_row,
+                                                                long long n, int D, int lpr, int rpw, uint16_t* __restrict__ out) {
+  const int lane = threadIdx.x & 63, sub = lane / lpr, c8 = lane - sub * lpr;
+  const long long r = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * rpw + sub;
+  const bool live = sub < rpw && r < n;
+  float s[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) s[k] = 0.f;
+  if (live) plaid_load8<NBITS>(codes, resid, centroids, weights, C, first_row + r, D, c8, s);
+  plaid_finish8(s, lpr);                               // all 64 lanes
+  if (live)
+    ((uint4*)(out + (size_t)r * D))[c8] = make_uint4(pack2h(s[0], s[1]), pack2h(s[2], s[3]), pack2h(s[4], s[5]), pack2h(s[6], s[7]));
+}
+
+template <int NBITS>
+void plaid_decode_rows_host(const uint16_t* centroids, int C, const float* weights, int D, const int32_t* codes, const uint8_t* resid,
+                            long long n_rows, uint16_t* out) {
+  const int lpr = D / 8;
+  float s[512], q[64];
+  for (long long row = 0; row < n_rows; ++row) {
+    const uint16_t* crow = centroids + (size_t)codes[row] * D;
+    const uint8_t* rrow = resid + (size_t)row * ((size_t)D / 8 * NBITS);
+    for (int c8 = 0; c8 < lpr; ++c8) {
+      uint8_t r[NBITS];
+      for (int b = 0; b < NBITS; ++b) r[b] = rrow[c8 * NBITS + b];
+      float c[8];
+      for (int k = 0; k < 8; ++k) {
+        const uint16_t hb = crow[8 * c8 + k];                                   // fp16 bits -> float, exact
+        const uint32_t sign = (uint32_t)(hb & 0x8000u) << 16, e = (hb >> 10) & 31u, m = hb & 0x3ffu;
+        float v;
+        if (e == 0) v = (sign ? -1.f : 1.f) * ((float)m * 5.9604644775390625e-8f);   // subnormal or zero: m * 2^-24, exact
+        else if (e == 31) v = __builtin_bit_cast(float, sign | 0x7f800000u | (m << 13));
+        else v = __builtin_bit_cast(float, sign | ((e + 112u) << 23) | (m << 13));
+        c[k] = v + weights[plaid_bucket<NBITS>(r, k)];
+      }
+      for (int k = 0; k < 8; ++k) s[8 * c8 + k] = c[k];
+      q[c8] = plaid_sumsq8(c);
+    }
+    for (int w = lpr; w > 1; w >>= 1)
+      for (int i = 0; i < w / 2; ++i) q[i] = q[2 * i] + q[2 * i + 1];
+    const float d = plaid_scale(sqrtf(q[0]));
+    for (int e = 0; e < D; ++e) out[(size_t)row * D + e] = plaid_f16_bits(s[e] / d);
+  }
+}
+
+// what a compressed bank takes: nbits in {1, 2, 4, 8}, D a power of two in [8, 512] with D % (8 * nbits) == 0 (residual.py:195)
+bool plaid_shape(int nbits, int D) {
+  if (nbits != 1 && nbits != 2 && nbits != 4 && nbits != 8) return false;
+  return D >= 8 && D <= 512 && (D & (D - 1)) == 0 && D % (8 * nbits) == 0;
+}
+
 // lanes per row and rows per wave of a copy over rows of D elements (D % 8 == 0, D <= 512)
 bool row_shape(int D, int* lpr, int* rpw) {
   if (D <= 0 || (D & 7) || D > 512) return false;
@@ -150,4 +348,86 @@ hipError_t rr_launch_bank_gather(const rr_bank_pair* pairs, int n, int Lq, int S
     hipLaunchKernelGGL(bank_gather_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, st, pairs, n, Lq, S, D, lpr, rpw, query_li,
                        query_mask, rows, mask_bytes, li16, qmask_out, cmask_out, q32_out, c32_out);
   return hipGetLastError();
+}
+
+namespace {
+template <int DT>
+hipError_t gather_plaid_dt(int nbits, dim3 grid, hipStream_t st, const rr_bank_pair* pairs, int n, int Lq, int S, int D, int lpr, int rpw,
+                           const float* query_li, const float* query_mask, const int32_t* codes, const uint8_t* resid,
+                           const uint16_t* centroids, const float* weights, int C, const uint8_t* mask_bytes, bf16_t* li16,
+                           float* qmask_out, float* cmask_out, float* q32_out, float* c32_out) {
+#define RR_PLAID_GATHER(NB)                                                                                                          \
+  hipLaunchKernelGGL((bank_gather_plaid_kernel<DT, NB>), grid, dim3(256), 0, st, pairs, n, Lq, S, D, lpr, rpw, query_li, query_mask, \
+                     codes, resid, centroids, weights, C, mask_bytes, li16, qmask_out, cmask_out, q32_out, c32_out)
+  switch (nbits) {
+    case 1: RR_PLAID_GATHER(1); break;
+    case 2: RR_PLAID_GATHER(2); break;
+    case 4: RR_PLAID_GATHER(4); break;
+    case 8: RR_PLAID_GATHER(8); break;
+    default: return hipErrorInvalidValue;
+  }
+#undef RR_PLAID_GATHER
+  return hipGetLastError();
+}
+}  // namespace
+
+// rr_launch_bank_gather over a compressed bank: codes [rows] int32, resid [rows][D * nbits / 8], centroids [C][D] fp16 bits, weights
+// [2^nbits] float32, all on the device
+hipError_t rr_launch_bank_gather_plaid(const rr_bank_pair* pairs, int n, int Lq, int S, int D, const float* query_li,
+                                       const float* query_mask, int nbits, const int32_t* codes, const uint8_t* resid,
+                                       const uint16_t* centroids, const float* weights, int C, const uint8_t* mask_bytes, bf16_t* li16,
+                                       int dt, float* qmask_out, float* cmask_out, float* q32_out, float* c32_out, hipStream_t st) {
+  int lpr = 0, rpw = 0;
+  if (n <= 0 || Lq <= 0 || S <= 0 || !plaid_shape(nbits, D) || !row_shape(D, &lpr, &rpw) || C <= 0 || !pairs || !query_li || !query_mask ||
+      !codes || !resid || !centroids || !weights || !mask_bytes || !li16 || !qmask_out || !cmask_out || (!q32_out) != (!c32_out))
+    return hipErrorInvalidValue;
+  if ((((uintptr_t)query_li) | ((uintptr_t)centroids) | ((uintptr_t)li16) | ((uintptr_t)q32_out) | ((uintptr_t)c32_out)) & 15)
+    return hipErrorInvalidValue;
+  if ((((uintptr_t)resid) & 7) || (((uintptr_t)codes) & 3)) return hipErrorInvalidValue;      // a lane loads nbits <= 8 bytes at once
+  const long long n_rows = (long long)n * (Lq + S), per_block = 4LL * rpw, blocks = (n_rows + per_block - 1) / per_block;
+  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+  return dt ? gather_plaid_dt<1>(nbits, dim3((unsigned)blocks), st, pairs, n, Lq, S, D, lpr, rpw, query_li, query_mask, codes, resid,
+                                 centroids, weights, C, mask_bytes, li16, qmask_out, cmask_out, q32_out, c32_out)
+            : gather_plaid_dt<0>(nbits, dim3((unsigned)blocks), st, pairs, n, Lq, S, D, lpr, rpw, query_li, query_mask, codes, resid,
+                                 centroids, weights, C, mask_bytes, li16, qmask_out, cmask_out, q32_out, c32_out);
+}
+
+// rows [first_row, first_row + n_rows) of (codes, resid) decoded into out [n_rows][D] fp16 bits, all on the device
+hipError_t rr_launch_plaid_decode(const uint16_t* centroids, int C, const float* weights, int nbits, int D, const int32_t* codes,
+                                  const uint8_t* resid, long long first_row, long long n_rows, uint16_t* out, hipStream_t st) {
+  int lpr = 0, rpw = 0;
+  if (!plaid_shape(nbits, D) || !row_shape(D, &lpr, &rpw) || C <= 0 || first_row < 0 || n_rows <= 0 || !centroids || !weights || !codes ||
+      !resid || !out)
+    return hipErrorInvalidValue;
+  if (((((uintptr_t)centroids) | ((uintptr_t)out)) & 15) || (((uintptr_t)resid) & 7) || (((uintptr_t)codes) & 3)) return hipErrorInvalidValue;
+  const long long per_block = 4LL * rpw, blocks = (n_rows + per_block - 1) / per_block;
+  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+#define RR_PLAID_DECODE(NB)                                                                                                      \
+  hipLaunchKernelGGL(bank_decode_plaid_kernel<NB>, dim3((unsigned)blocks), dim3(256), 0, st, codes, resid, centroids, weights, C, \
+                     first_row, n_rows, D, lpr, rpw, out)
+  switch (nbits) {
+    case 1: RR_PLAID_DECODE(1); break;
+    case 2: RR_PLAID_DECODE(2); break;
+    case 4: RR_PLAID_DECODE(4); break;
+    default: RR_PLAID_DECODE(8); break;
+  }
+#undef RR_PLAID_DECODE
+  return hipGetLastError();
+}
+
+bool rr_plaid_shape_ok(int nbits, int D) { return plaid_shape(nbits, D); }
+
+// rr_util_plaid_decode_rows: host memory throughout; false when the shape is not one plaid_shape takes or a code lies outside [0, C)
+bool rr_plaid_decode_rows_host(const uint16_t* centroids, int C, const float* weights, int nbits, int D, const int32_t* codes,
+                               const uint8_t* resid, long long n_rows, uint16_t* out) {
+  if (!plaid_shape(nbits, D) || C <= 0) return false;
+  for (long long i = 0; i < n_rows; ++i)
+    if (codes[i] < 0 || codes[i] >= C) return false;
+  switch (nbits) {
+    case 1: plaid_decode_rows_host<1>(centroids, C, weights, D, codes, resid, n_rows, out); break;
+    case 2: plaid_decode_rows_host<2>(centroids, C, weights, D, codes, resid, n_rows, out); break;
+    case 4: plaid_decode_rows_host<4>(centroids, C, weights, D, codes, resid, n_rows, out); break;
+    default: plaid_decode_rows_host<8>(centroids, C, weights, D, codes, resid, n_rows, out); break;
+  }
+  return true;
 }

@@ -276,12 +276,20 @@ struct rr_model {
 
 // rr_bank_* (include/rerank_mi355.h): an append-only device store of passages.  rows [capacity_rows][D] fp16 bits, one mask byte
 // per row, and the host table (first row, length) per passage.  Its own staging slots: rr_bank_add belongs to no handle.
+// A compressed bank (rr_bank_create_plaid, nbits != 0) holds per row a centroid code and D * nbits / 8 residual bytes in place of
+// `rows`, and the codec's tables: centroids [n_centroids][D] fp16 bits, weights [2^nbits] float32.
 struct rr_bank {
   int device = 0, D = 0;
   int64_t cap_rows = 0, used_rows = 0;
   int32_t max_passages = 0;
   uint16_t* rows = nullptr;
   uint8_t* mask = nullptr;
+  int nbits = 0, n_centroids = 0;
+  int32_t* codes = nullptr;
+  uint8_t* resid = nullptr;
+  uint16_t* centroids = nullptr;
+  float* weights = nullptr;
+  size_t resid_row_bytes() const { return (size_t)D / 8 * (size_t)nbits; }
   std::vector<int64_t> first;
   std::vector<int32_t> len;
   std::string err;
@@ -2029,6 +2037,10 @@ static int bfail(rr_bank* b, int code, const char* fmt, ...) noexcept {
 static void bank_free(rr_bank* b) {
   if (b->rows) (void)hipFree(b->rows);
   if (b->mask) (void)hipFree(b->mask);
+  if (b->codes) (void)hipFree(b->codes);
+  if (b->resid) (void)hipFree(b->resid);
+  if (b->centroids) (void)hipFree(b->centroids);
+  if (b->weights) (void)hipFree(b->weights);
   for (auto& a : b->slot) {
     if (a.host) (void)hipHostFree(a.host);
     if (a.dev) (void)hipFree(a.dev);
@@ -2079,6 +2091,7 @@ static int rr_bank_add_impl(rr_bank* b, const void* context_li, int dtype, const
                             int Lc, int32_t* first_index_out, void* hip_stream) {
   const char* what = "rr_bank_add";
   if (!b) return RR_ERR_BAD_ARG;
+  if (b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on a compressed bank: it takes residual codes (rr_bank_add_plaid); nothing here compresses", what);
   if (!context_li || !context_mask || !lengths) return bfail(b, RR_ERR_BAD_ARG, "%s: null argument", what);
   if (dtype != RR_F32 && dtype != RR_F16) return bfail(b, RR_ERR_BAD_DTYPE, "%s: dtype %d (RR_F32 or RR_F16)", what, dtype);
   if (((uintptr_t)context_li) & 15) return bfail(b, RR_ERR_BAD_ARG, "%s: context_li must be 16-byte aligned", what);
@@ -2133,6 +2146,108 @@ static int rr_bank_add_impl(rr_bank* b, const void* context_li, int dtype, const
   return RR_OK;
 }
 
+// rr_bank_create_plaid: rr_bank_create with compressed rows and the codec's tables copied to the device
+static int rr_bank_create_plaid_impl(rr_handle h, int64_t capacity_rows, int32_t max_passages, int nbits, int32_t n_centroids,
+                                     const uint16_t* centroids_f16, const float* bucket_weights, rr_bank_handle* out) {
+  const char* what = "rr_bank_create_plaid";
+  if (!h) return RR_ERR_BAD_ARG;
+  if (!out) return fail(h, RR_ERR_BAD_ARG, "%s: null out", what);
+  *out = nullptr;
+  const int D = h->cfg.li_dim;
+  if (h->cfg.model_kind == RR_MODEL_FULL_CONTEXT) return fail(h, RR_ERR_BAD_ARG, "%s on a full-context model", what);
+  if (!centroids_f16 || !bucket_weights) return fail(h, RR_ERR_BAD_ARG, "%s: null table", what);
+  if (!rr_plaid_shape_ok(nbits, D))
+    return fail(h, RR_ERR_UNSUPPORTED, "%s: nbits %d, li_dim %d (nbits 1, 2, 4 or 8; li_dim a power of two in [8, 512], a multiple of 8 * nbits)",
+                what, nbits, D);
+  if (capacity_rows <= 0 || max_passages <= 0 || capacity_rows > (1LL << 40) || n_centroids <= 0 || n_centroids > (1 << 24))
+    return fail(h, RR_ERR_BAD_SHAPE, "%s: capacity_rows=%lld max_passages=%d n_centroids=%d", what, (long long)capacity_rows, max_passages,
+                n_centroids);
+  RR_HIP(h, hipSetDevice(h->cfg.device));
+  rr_bank* b = new rr_bank();
+  b->device = h->cfg.device;
+  b->D = D;
+  b->cap_rows = capacity_rows;
+  b->max_passages = max_passages;
+  b->nbits = nbits;
+  b->n_centroids = n_centroids;
+  const size_t cbytes = (size_t)n_centroids * D * sizeof(uint16_t), wbytes = ((size_t)1 << nbits) * sizeof(float);
+  hipError_t e = hipMalloc((void**)&b->codes, (size_t)capacity_rows * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&b->resid, (size_t)capacity_rows * b->resid_row_bytes());
+  if (e == hipSuccess) e = hipMalloc((void**)&b->mask, (size_t)capacity_rows);
+  if (e == hipSuccess) e = hipMalloc((void**)&b->centroids, cbytes);
+  if (e == hipSuccess) e = hipMalloc((void**)&b->weights, wbytes);
+  if (e == hipSuccess) e = hipMemcpy(b->centroids, centroids_f16, cbytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(b->weights, bucket_weights, wbytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    bank_free(b);
+    return fail(h, e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP, "%s: %lld rows of %d at %d bits, %d centroids: %s", what,
+                (long long)capacity_rows, D, nbits, n_centroids, hipGetErrorString(e));
+  }
+  b->first.reserve((size_t)std::min<int64_t>(max_passages, 1 << 20));
+  b->len.reserve((size_t)std::min<int64_t>(max_passages, 1 << 20));
+  *out = b;
+  return RR_OK;
+}
+
+// every check on the host first; then three copies (a fill for a NULL mask) and one synchronisation: a load-time call
+static int rr_bank_add_plaid_impl(rr_bank* b, const int32_t* codes, const uint8_t* residuals, const uint8_t* mask, const int32_t* lengths,
+                                  int n, int32_t* first_index_out, void* hip_stream) {
+  const char* what = "rr_bank_add_plaid";
+  if (!b) return RR_ERR_BAD_ARG;
+  if (!b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it takes embeddings (rr_bank_add)", what);
+  if (!codes || !residuals || !lengths) return bfail(b, RR_ERR_BAD_ARG, "%s: null argument", what);
+  if (n <= 0) return bfail(b, RR_ERR_BAD_SHAPE, "%s: n=%d", what, n);
+  int64_t rows = 0;
+  for (int i = 0; i < n; ++i) {
+    if (lengths[i] < 1) return bfail(b, RR_ERR_BAD_SHAPE, "%s: passage %d has length %d (at least 1)", what, i, lengths[i]);
+    rows += lengths[i];
+  }
+  const int64_t have = (int64_t)b->first.size();
+  if (have + n > b->max_passages)
+    return bfail(b, RR_ERR_OOM, "%s: %lld + %d passages exceed the bank's %d slots", what, (long long)have, n, b->max_passages);
+  if (b->used_rows + rows > b->cap_rows)
+    return bfail(b, RR_ERR_OOM, "%s: %lld + %lld rows exceed the bank's %lld", what, (long long)b->used_rows, (long long)rows,
+                 (long long)b->cap_rows);
+  for (int64_t i = 0; i < rows; ++i)               // behind the capacity check: rows is bounded by it here
+    if (codes[i] < 0 || codes[i] >= b->n_centroids)
+      return bfail(b, RR_ERR_BAD_SHAPE, "%s: row %lld has centroid code %d, the codec %d centroids", what, (long long)i, codes[i], b->n_centroids);
+  hipStream_t st = (hipStream_t)hip_stream;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return bfail(b, RR_ERR_BAD_ARG, "%s cannot be captured into a graph (it copies from host memory and synchronises)", what);
+  RR_BHIP(b, hipSetDevice(b->device));
+  const int64_t r0 = b->used_rows;
+  const size_t rb = b->resid_row_bytes();
+  RR_BHIP(b, hipMemcpyAsync(b->codes + r0, codes, (size_t)rows * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  RR_BHIP(b, hipMemcpyAsync(b->resid + (size_t)r0 * rb, residuals, (size_t)rows * rb, hipMemcpyHostToDevice, st));
+  if (mask) RR_BHIP(b, hipMemcpyAsync(b->mask + r0, mask, (size_t)rows, hipMemcpyHostToDevice, st));
+  else RR_BHIP(b, hipMemsetAsync(b->mask + r0, 1, (size_t)rows, st));
+  RR_BHIP(b, hipStreamSynchronize(st));            // the host buffers are the caller's again
+  int64_t row = r0;
+  for (int i = 0; i < n; ++i) {
+    b->first.push_back(row);
+    b->len.push_back(lengths[i]);
+    row += lengths[i];
+  }
+  b->used_rows = row;
+  if (first_index_out) *first_index_out = (int32_t)have;
+  return RR_OK;
+}
+
+static int rr_op_plaid_decode_rows_impl(const uint16_t* centroids_f16, int32_t n_centroids, const float* bucket_weights, int nbits, int D,
+                                        const int32_t* codes, const uint8_t* residuals, int64_t first_row, int64_t n_rows,
+                                        uint16_t* rows_out_f16, void* hip_stream) {
+  if (!centroids_f16 || !bucket_weights || !codes || !residuals || !rows_out_f16) return fail(nullptr, RR_ERR_BAD_ARG, "rr_op_plaid_decode_rows: null argument");
+  if (!rr_plaid_shape_ok(nbits, D)) return RR_ERR_UNSUPPORTED;
+  if (n_centroids <= 0 || first_row < 0 || n_rows <= 0 || first_row > (1LL << 40) || n_rows > (1LL << 40)) return RR_ERR_BAD_SHAPE;
+  if (((((uintptr_t)centroids_f16) | ((uintptr_t)rows_out_f16)) & 15) || (((uintptr_t)residuals) & 7) || (((uintptr_t)codes) & 3))
+    return RR_ERR_BAD_ARG;
+  const hipError_t e = rr_launch_plaid_decode(centroids_f16, n_centroids, bucket_weights, nbits, D, codes, residuals, first_row, n_rows,
+                                              rows_out_f16, (hipStream_t)hip_stream);
+  return e == hipSuccess ? RR_OK : RR_ERR_HIP;
+}
+
 static int rr_bank_read_impl(rr_bank* b, int32_t index, uint16_t* rows_out, uint8_t* mask_out, int32_t capacity_rows, void* hip_stream) {
   if (!b) return RR_ERR_BAD_ARG;
   if (index < 0 || (size_t)index >= b->first.size()) return bfail(b, RR_ERR_BAD_SHAPE, "rr_bank_read: passage %d of %zu", index, b->first.size());
@@ -2142,7 +2257,19 @@ static int rr_bank_read_impl(rr_bank* b, int32_t index, uint16_t* rows_out, uint
   RR_BHIP(b, hipSetDevice(b->device));
   RR_BHIP(b, hipStreamSynchronize((hipStream_t)hip_stream));
   const int64_t r0 = b->first[(size_t)index];
-  if (rows_out) RR_BHIP(b, hipMemcpy(rows_out, b->rows + (size_t)r0 * b->D, (size_t)len * b->D * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  if (rows_out && b->nbits) {                      // decoded by the kernel function the gather uses
+    const size_t bytes = (size_t)len * b->D * sizeof(uint16_t);
+    uint16_t* tmp = nullptr;
+    RR_BHIP(b, hipMalloc((void**)&tmp, bytes));
+    hipError_t e = rr_launch_plaid_decode(b->centroids, b->n_centroids, b->weights, b->nbits, b->D, b->codes, b->resid, r0, len, tmp,
+                                          (hipStream_t)hip_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)hip_stream);
+    if (e == hipSuccess) e = hipMemcpy(rows_out, tmp, bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(tmp);
+    RR_BHIP(b, e);
+  } else if (rows_out) {
+    RR_BHIP(b, hipMemcpy(rows_out, b->rows + (size_t)r0 * b->D, (size_t)len * b->D * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  }
   if (mask_out) RR_BHIP(b, hipMemcpy(mask_out, b->mask + r0, (size_t)len, hipMemcpyDeviceToHost));
   return len;
 }
@@ -2407,6 +2534,14 @@ static int forward_interaction(rr_handle h, Request r) {
     void* dev = nullptr;
     RR_TRY(asm_stage(m, "rr_forward_interaction_bank", r.bank_pairs->data(), r.bank_pairs->size() * sizeof(rr_bank_pair), st, &dev));
     for (const Seg& g : segs)
+      if (r.bank->nbits)       // compressed rows (code + residual bytes + the centroid chunk from L2) are decoded in the gather
+        RR_RUN(m, st, RR_K_TAIL, 0.0, (double)g.n * (Lq * D * (4.0 + 2.0 + (q32 ? 4.0 : 0.0)) +
+                                                    (double)g.S * (4.0 + D * (r.bank->nbits / 8.0 + 2.0 + 2.0 + (c32 ? 4.0 : 0.0)))),
+               rr_launch_bank_gather_plaid((const rr_bank_pair*)dev + g.p0, g.n, Lq, g.S, D, r.query_li, r.query_mask, r.bank->nbits,
+                                           r.bank->codes, r.bank->resid, r.bank->centroids, r.bank->weights, r.bank->n_centroids,
+                                           r.bank->mask, w.li16 + g.rt0 * D, m->dt, qm_w + g.p0 * Lq, cm_w + g.r0,
+                                           q32 ? q32 + g.p0 * Lq * D : nullptr, c32 ? c32 + g.r0 * D : nullptr, st));
+      else
       RR_RUN(m, st, RR_K_TAIL, 0.0, (double)g.n * (Lq * D * (4.0 + 2.0 + (q32 ? 4.0 : 0.0)) + (double)g.S * D * (2.0 + 2.0 + (c32 ? 4.0 : 0.0))),
              rr_launch_bank_gather((const rr_bank_pair*)dev + g.p0, g.n, Lq, g.S, D, r.query_li, r.query_mask, r.bank->rows,
                                    r.bank->mask, w.li16 + g.rt0 * D, m->dt, qm_w + g.p0 * Lq, cm_w + g.r0,
@@ -3174,6 +3309,30 @@ int rr_bank_info(rr_bank_handle b, int32_t* passages_out, int64_t* rows_used_out
 }
 int rr_bank_add(rr_bank_handle b, const void* context_li, int dtype, const float* context_mask, const int32_t* lengths, int n, int Lc, int32_t* first_index_out, void* hip_stream) {
   return guarded(nullptr, [&]() -> int { return rr_bank_add_impl(b, context_li, dtype, context_mask, lengths, n, Lc, first_index_out, hip_stream); });
+}
+int rr_bank_create_plaid(rr_handle h, int64_t capacity_rows, int32_t max_passages, int nbits, int32_t n_centroids, const uint16_t* centroids_f16, const float* bucket_weights, rr_bank_handle* out) {
+  return guarded(h, [&]() -> int { return rr_bank_create_plaid_impl(h, capacity_rows, max_passages, nbits, n_centroids, centroids_f16, bucket_weights, out); });
+}
+int rr_bank_add_plaid(rr_bank_handle b, const int32_t* codes, const uint8_t* residuals, const uint8_t* mask, const int32_t* lengths, int n, int32_t* first_index_out, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_bank_add_plaid_impl(b, codes, residuals, mask, lengths, n, first_index_out, hip_stream); });
+}
+int rr_bank_format(rr_bank_handle b, int32_t* nbits_out, int32_t* n_centroids_out, int64_t* bytes_per_row_out) {
+  if (!b) return RR_ERR_BAD_ARG;
+  if (nbits_out) *nbits_out = b->nbits;
+  if (n_centroids_out) *n_centroids_out = b->n_centroids;
+  if (bytes_per_row_out) *bytes_per_row_out = b->nbits ? (int64_t)(4 + b->resid_row_bytes() + 1) : (int64_t)b->D * 2 + 1;
+  return RR_OK;
+}
+int rr_util_plaid_decode_rows(const uint16_t* centroids_f16, int32_t n_centroids, const float* bucket_weights, int nbits, int D, const int32_t* codes, const uint8_t* residuals, int64_t n_rows, uint16_t* rows_out_f16) {
+  if (!centroids_f16 || !bucket_weights || !codes || !residuals || !rows_out_f16) return RR_ERR_BAD_ARG;
+  if (!rr_plaid_shape_ok(nbits, D)) return RR_ERR_UNSUPPORTED;
+  if (n_centroids <= 0 || n_rows < 0) return RR_ERR_BAD_SHAPE;
+  return guarded(nullptr, [&]() -> int {
+    return rr_plaid_decode_rows_host(centroids_f16, n_centroids, bucket_weights, nbits, D, codes, residuals, n_rows, rows_out_f16) ? RR_OK : RR_ERR_BAD_SHAPE;
+  });
+}
+int rr_op_plaid_decode_rows(const uint16_t* centroids_f16, int32_t n_centroids, const float* bucket_weights, int nbits, int D, const int32_t* codes, const uint8_t* residuals, int64_t first_row, int64_t n_rows, uint16_t* rows_out_f16, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_plaid_decode_rows_impl(centroids_f16, n_centroids, bucket_weights, nbits, D, codes, residuals, first_row, n_rows, rows_out_f16, hip_stream); });
 }
 int rr_bank_read(rr_bank_handle b, int32_t index, uint16_t* rows_out, uint8_t* mask_out, int32_t capacity_rows, void* hip_stream) {
   return guarded(nullptr, [&]() -> int { return rr_bank_read_impl(b, index, rows_out, mask_out, capacity_rows, hip_stream); });

@@ -452,3 +452,14 @@ hipError_t rr_launch_bank_ingest(const void* src, int src_f16, const float* mask
 hipError_t rr_launch_bank_gather(const rr_bank_pair* pairs, int n, int Lq, int S, int D, const float* query_li,
                                  const float* query_mask, const uint16_t* rows, const uint8_t* mask_bytes, bf16_t* li16, int dt,
                                  float* qmask_out, float* cmask_out, float* q32_out, float* c32_out, hipStream_t st);
+// compressed (PLAID residual) bank: the gather that decodes, the stand-alone decode of a row range, the shape rule and the host
+// decoder that defines the bits (passage_bank.hip)
+hipError_t rr_launch_bank_gather_plaid(const rr_bank_pair* pairs, int n, int Lq, int S, int D, const float* query_li,
+                                       const float* query_mask, int nbits, const int32_t* codes, const uint8_t* resid,
+                                       const uint16_t* centroids, const float* weights, int C, const uint8_t* mask_bytes, bf16_t* li16,
+                                       int dt, float* qmask_out, float* cmask_out, float* q32_out, float* c32_out, hipStream_t st);
+hipError_t rr_launch_plaid_decode(const uint16_t* centroids, int C, const float* weights, int nbits, int D, const int32_t* codes,
+                                  const uint8_t* resid, long long first_row, long long n_rows, uint16_t* out, hipStream_t st);
+bool rr_plaid_shape_ok(int nbits, int D);
+bool rr_plaid_decode_rows_host(const uint16_t* centroids, int C, const float* weights, int nbits, int D, const int32_t* codes,
+                               const uint8_t* resid, long long n_rows, uint16_t* out);

@@ -740,12 +740,14 @@ class RerankEngine:
         out.update(extra)
         return out
 
-    def create_bank(self, capacity_rows: int, max_passages: int):
+    def create_bank(self, capacity_rows: int, max_passages: int, codec=None):
         """A device-resident passage-embedding bank (rr_bank_create; passage_bank.PassageBank) of `capacity_rows` token rows
         and at most `max_passages` passages on this engine's device with its li_dim.  It outlives the engine and serves every
-        interaction engine of the device with the same li_dim (NORMAL and MORES)."""
+        interaction engine of the device with the same li_dim (NORMAL and MORES).  `codec` (passage_bank.PlaidCodec): a
+        compressed bank (rr_bank_create_plaid) that holds the residual codes of a ColBERTv2 / PLAID index and decodes them in the
+        forward; filled with add_compressed / load_plaid_index."""
         from .passage_bank import PassageBank
-        return PassageBank(self, capacity_rows, max_passages)
+        return PassageBank(self, capacity_rows, max_passages, codec)
 
     def forward_interaction_bank(self, bank, query_li: torch.Tensor, query_mask: torch.Tensor, passage_ids, Bq: int, K: int,
                                  labels: Optional[torch.Tensor] = None, list_sizes: Optional[Sequence[int]] = None,
@@ -1205,10 +1207,10 @@ class InteractionRerankModel(_DropIn):
         if state_dict is not None:
             self.engine.load_state_dict(state_dict)
 
-    def create_bank(self, capacity_rows: int, max_passages: int):
-        """Give the model a passage-embedding bank (RerankEngine.create_bank) and return it; `bank` may also be assigned a bank
+    def create_bank(self, capacity_rows: int, max_passages: int, codec=None):
+        """Give the model a passage-embedding bank (RerankEngine.create_bank; `codec`: a compressed one) and return it; `bank` may also be assigned a bank
         another model of the same device and li_dim created."""
-        self.bank = self.engine.create_bank(capacity_rows, max_passages)
+        self.bank = self.engine.create_bank(capacity_rows, max_passages, codec)
         return self.bank
 
     def forward_passages(self, query_late_interaction, query_mask, passage_ids, num_negative_examples, labels=None,

@@ -6,8 +6,13 @@ device in that form, every passage at its own length, under the caller's passage
 (RerankEngine.forward_interaction_bank, InteractionRerankModel.forward_passages, pipeline.InteractionStages) instead of
 uploading and packing a padded float32 [N, Lc, D] tensor per query.
 
-`BankTable` and `plan_bank_batch` are the host side (ids -> indices and lengths -> segments and the packed pair order): pure
-Python / numpy, usable and tested without a device.
+A bank created with a `PlaidCodec` is a COMPRESSED one: it holds the rows as a ColBERTv2 / PLAID index stores them (one int32
+centroid code and D * nbits / 8 residual bytes per token; third_party/ColBERT/colbert/indexing/codecs/residual.py of the reference)
+and decodes them on the device inside the forward's gather, bit for bit the fp16 bank of the decoded rows (the decoded row:
+include/rerank_mi355.h, rr_bank_create_plaid).  `read_plaid_index` reads such an index from disk with torch.load and json alone.
+
+`BankTable`, `plan_bank_batch`, `PlaidCodec` and `read_plaid_index` are the host side: pure Python / numpy / torch on the CPU,
+usable and tested without a device.
 """
 from __future__ import annotations
 
@@ -95,18 +100,127 @@ def plan_bank_batch(table: BankTable, passage_ids: Sequence, K: Optional[int], l
                 pair_passage=idx[order].astype(np.int32), pair_query=owner[order].astype(np.int32))
 
 
+PLAID_NBITS = (1, 2, 4, 8)
+
+
+def plaid_shape_ok(nbits: int, dim: int) -> bool:
+    """What a compressed bank takes: nbits 1, 2, 4 or 8; dim a power of two in [8, 512] and a multiple of 8 * nbits."""
+    return nbits in PLAID_NBITS and 8 <= dim <= 512 and dim & (dim - 1) == 0 and dim % (8 * nbits) == 0
+
+
+class PlaidCodec:
+    """The tables of a ColBERTv2 / PLAID residual codec, as an index stores them: `centroids` [C, D] (kept as fp16: the index
+    saves them with .half(), codecs/residual.py:161), `bucket_weights` [2^nbits] (kept as float32) and `nbits`.  A plain holder:
+    it validates shapes and dtypes (ValueError) and compresses nothing."""
+
+    def __init__(self, centroids, bucket_weights, nbits: int):
+        import torch
+        if not isinstance(nbits, int) or isinstance(nbits, bool) or nbits not in PLAID_NBITS:
+            raise ValueError(f"nbits {nbits!r}: 1, 2, 4 or 8")
+        centroids, bucket_weights = torch.as_tensor(centroids), torch.as_tensor(bucket_weights)
+        if centroids.dim() != 2 or centroids.shape[0] < 1 or not centroids.is_floating_point():
+            raise ValueError(f"centroids must be a floating-point [C, D] tensor, got {centroids.dtype} {tuple(centroids.shape)}")
+        dim = int(centroids.shape[1])
+        if not plaid_shape_ok(nbits, dim):
+            raise ValueError(f"dim {dim} at nbits {nbits}: a power of two in [8, 512] and a multiple of {8 * nbits}")
+        if not bucket_weights.is_floating_point() or tuple(bucket_weights.shape) != (1 << nbits,):
+            raise ValueError(f"bucket_weights must be {1 << nbits} floating-point values at nbits {nbits}, got {bucket_weights.dtype} "
+                             f"{tuple(bucket_weights.shape)}")
+        self.nbits, self.dim = nbits, dim
+        self.centroids = centroids.detach().to(device="cpu", dtype=torch.float16).contiguous()
+        self.bucket_weights = bucket_weights.detach().to(device="cpu", dtype=torch.float32).contiguous()
+
+    @property
+    def n_centroids(self) -> int:
+        return int(self.centroids.shape[0])
+
+    @property
+    def residual_bytes(self) -> int:
+        """Bytes of packed residual per row."""
+        return self.dim // 8 * self.nbits
+
+    def decode(self, codes, residuals):
+        """The decoded rows [R, D] float16 of `codes` [R] / `residuals` [R, residual_bytes] in host code
+        (rr_util_plaid_decode_rows: the bit-level definition the device is held to; no GPU needed)."""
+        import numpy as np
+        import torch
+        from . import _lib as L
+        lib = L.load()
+        codes = np.ascontiguousarray(np.asarray(codes).reshape(-1), dtype=np.int32)
+        res = np.ascontiguousarray(np.asarray(residuals), dtype=np.uint8).reshape(codes.size, self.residual_bytes)
+        out = torch.empty((codes.size, self.dim), dtype=torch.float16)
+        rc = lib.rr_util_plaid_decode_rows(self.centroids.data_ptr(), self.n_centroids, self.bucket_weights.data_ptr(), self.nbits,
+                                           self.dim, codes.ctypes.data, res.ctypes.data, codes.size, out.data_ptr())
+        if rc == L.RR_ERR_BAD_SHAPE:
+            raise ValueError(f"a centroid code lies outside [0, {self.n_centroids})")
+        L.check(rc, None, "rr_util_plaid_decode_rows")
+        return out
+
+
+def read_plaid_index(index_path: str):
+    """Read a ColBERTv2 / PLAID index directory as the reference's indexer writes it
+    (third_party/ColBERT/colbert/indexing/index_saver.py:33-46, collection_indexer.py): `metadata.json` (config.nbits, config.dim,
+    num_chunks), `centroids.pt`, `buckets.pt` = (cutoffs, weights), and per chunk i `{i}.codes.pt`, `{i}.residuals.pt`,
+    `doclens.{i}.json`.  torch.load and json only; nothing of colbert is imported.  Returns (PlaidCodec, chunks); `chunks` is a
+    generator of (first passage number, codes int32 [R], residuals uint8 [R, D * nbits / 8], doclens list) that loads one chunk at a
+    time.  The passage numbers run through the chunks in order, as the index numbers them."""
+    import json
+    import os
+
+    import torch
+
+    def load(name):
+        path = os.path.join(index_path, name)
+        try:
+            return torch.load(path, map_location="cpu", weights_only=True)
+        except TypeError:                                   # a torch without weights_only
+            return torch.load(path, map_location="cpu")
+
+    with open(os.path.join(index_path, "metadata.json")) as f:
+        meta = json.load(f)
+    nbits, dim, n_chunks = int(meta["config"]["nbits"]), int(meta["config"]["dim"]), int(meta["num_chunks"])
+    buckets = load("buckets.pt")
+    codec = PlaidCodec(load("centroids.pt"), buckets[1], nbits)
+    if codec.dim != dim:
+        raise ValueError(f"{index_path}: metadata.json says dim {dim}, centroids.pt holds rows of {codec.dim}")
+
+    def chunks():
+        first = 0
+        for i in range(n_chunks):
+            with open(os.path.join(index_path, f"doclens.{i}.json")) as f:
+                doclens = [int(x) for x in json.load(f)]
+            codes = load(f"{i}.codes.pt").to(torch.int32).reshape(-1).contiguous()
+            res = load(f"{i}.residuals.pt").to(torch.uint8).reshape(codes.numel(), codec.residual_bytes).contiguous()
+            if sum(doclens) != codes.numel():
+                raise ValueError(f"{index_path}: chunk {i} holds {codes.numel()} rows, its doclens sum to {sum(doclens)}")
+            yield first, codes, res, doclens
+            first += len(doclens)
+    return codec, chunks()
+
+
 class PassageBank:
-    """An append-only device store of passage token embeddings (fp16 rows, one mask byte per row) under the caller's ids.
+    """An append-only device store of passage token embeddings under the caller's ids: fp16 rows, or with a `codec` (PlaidCodec)
+    the residual codes of a ColBERTv2 / PLAID index, decoded on the device in every forward; one mask byte per row either way.
     Created by RerankEngine.create_bank; usable by every interaction engine of the same device and li_dim."""
 
-    def __init__(self, engine, capacity_rows: int, max_passages: int):
+    def __init__(self, engine, capacity_rows: int, max_passages: int, codec: Optional[PlaidCodec] = None):
         from . import _lib as L
         self._L, self.lib = L, engine.lib
         self.device, self.li_dim = engine.device, int(engine.arch["li_dim"])
         self.table = BankTable()
-        self.padded_len = 0                  # the longest Lc an add has seen: the default padded context length of a forward
+        self.padded_len = 0                  # the longest Lc (compressed: passage) an add has seen: a forward's default padded length
+        self.codec = codec
         h = C.c_void_p()
-        L.check(self.lib.rr_bank_create(engine.h, int(capacity_rows), int(max_passages), C.byref(h)), engine.h, "rr_bank_create")
+        if codec is None:
+            L.check(self.lib.rr_bank_create(engine.h, int(capacity_rows), int(max_passages), C.byref(h)), engine.h, "rr_bank_create")
+        else:
+            if not isinstance(codec, PlaidCodec):
+                raise TypeError(f"codec must be a PlaidCodec, got {type(codec).__name__}")
+            if codec.dim != self.li_dim:
+                raise ValueError(f"the codec's rows hold {codec.dim} values, the engine's li_dim is {self.li_dim}")
+            L.check(self.lib.rr_bank_create_plaid(engine.h, int(capacity_rows), int(max_passages), codec.nbits, codec.n_centroids,
+                                                  codec.centroids.data_ptr(), codec.bucket_weights.data_ptr(), C.byref(h)),
+                    engine.h, "rr_bank_create_plaid")
         self.h = h
 
     def __del__(self):
@@ -139,10 +253,22 @@ class PassageBank:
         return torch.cuda.current_stream(self.device).cuda_stream
 
     def info(self) -> dict:
-        """rr_bank_info: passages held, rows used, row capacity."""
+        """rr_bank_info: passages held, rows used, row capacity.  A compressed bank adds `nbits` and `bytes_per_row` (format());
+        an fp16 bank's dict is those three keys alone."""
         p, r, c = C.c_int32(0), C.c_int64(0), C.c_int64(0)
         self._check(self.lib.rr_bank_info(self.h, C.byref(p), C.byref(r), C.byref(c)), "rr_bank_info")
-        return dict(passages=int(p.value), rows_used=int(r.value), capacity_rows=int(c.value))
+        out = dict(passages=int(p.value), rows_used=int(r.value), capacity_rows=int(c.value))
+        if self.codec is not None:
+            f = self.format()
+            out.update(nbits=f["nbits"], bytes_per_row=f["bytes_per_row"])
+        return out
+
+    def format(self) -> dict:
+        """rr_bank_format, either kind of bank: nbits (0: an fp16 bank), the codec's centroids (0) and the device bytes one row
+        takes, mask byte included."""
+        nb, nc, bpr = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        self._check(self.lib.rr_bank_format(self.h, C.byref(nb), C.byref(nc), C.byref(bpr)), "rr_bank_format")
+        return dict(nbits=int(nb.value), n_centroids=int(nc.value), bytes_per_row=int(bpr.value))
 
     def add(self, passage_ids: Sequence, context_li, context_mask, lengths: Optional[Sequence[int]] = None) -> int:
         """Append the passages `passage_ids` from the padded tensors a retriever produces: `context_li` [n, Lc, D] (host or
@@ -155,6 +281,8 @@ class PassageBank:
         import torch
         from .pair_inputs import pair_lengths
         L = self._L
+        if self.codec is not None:
+            raise NotImplementedError("a compressed bank takes residual codes (add_compressed): nothing here compresses embeddings")
         ids = list(passage_ids)
         n = len(ids)
         if context_li.dim() != 3 or context_li.shape[0] != n or context_li.shape[2] != self.li_dim:
@@ -176,13 +304,84 @@ class PassageBank:
         self.padded_len = max(self.padded_len, Lc)
         return int(first.value)
 
+    def add_compressed(self, passage_ids: Sequence, codes, residuals, doclens: Sequence[int], mask=None) -> int:
+        """Append the passages `passage_ids` of a compressed bank from an index's own arrays (rr_bank_add_plaid): `codes` [R]
+        integer centroid codes and `residuals` [R, D * nbits / 8] uint8, the rows of the passages one after the other, R =
+        sum(doclens); `doclens` the rows of each passage; `mask` [R] (non-zero = a token that counts) or None = all ones — the
+        ColBERT indexer has dropped the skiplist tokens already.  Host tensors / arrays (a device tensor is copied back).  A
+        load-time call: it synchronises the current stream.  Returns the first of the dense indices.  An id added twice, a code
+        outside the codec's centroids, a length below 1 or arrays that do not fit the lengths raise ValueError, rows or passage
+        slots that do not suffice MemoryError, an fp16 bank NotImplementedError; the bank is unchanged then."""
+        import numpy as np
+        import torch
+
+        def host(x, dtype):
+            if torch.is_tensor(x):
+                x = x.detach().cpu().numpy()
+            return np.ascontiguousarray(np.asarray(x), dtype=dtype)
+        if self.codec is None:
+            raise NotImplementedError("add_compressed on an fp16 bank: create the bank with a codec (create_bank(..., codec=PlaidCodec(...)))")
+        ids = list(passage_ids)
+        n = len(ids)
+        ln = host(doclens, np.int64).reshape(-1)
+        if ln.size != n or n == 0:
+            raise ValueError(f"{ln.size} doclens for {n} passages")
+        if int(ln.min()) < 1 or int(ln.max()) > 2 ** 31 - 1:
+            raise ValueError(f"a passage of {int(ln.min() if ln.min() < 1 else ln.max())} rows")
+        R = int(ln.sum())
+        cd = host(codes, np.int64).reshape(-1)
+        if cd.size != R:
+            raise ValueError(f"{cd.size} codes for {R} rows (sum of doclens)")
+        if cd.size and (int(cd.min()) < 0 or int(cd.max()) >= self.codec.n_centroids):
+            raise ValueError(f"centroid codes span [{int(cd.min())}, {int(cd.max())}], the codec holds {self.codec.n_centroids} centroids")
+        rs = host(residuals, np.uint8)
+        if rs.shape != (R, self.codec.residual_bytes):
+            raise ValueError(f"residuals must be [{R}, {self.codec.residual_bytes}] uint8, got {rs.shape}")
+        mk = None
+        if mask is not None:
+            mk = (host(mask, np.float32).reshape(-1) != 0).astype(np.uint8)
+            if mk.size != R:
+                raise ValueError(f"{mk.size} mask values for {R} rows")
+        self.table.check_new(ids)
+        cd32, ln32 = cd.astype(np.int32), ln.astype(np.int32)
+        first = C.c_int32(-1)
+        self._check(self.lib.rr_bank_add_plaid(self.h, cd32.ctypes.data, rs.ctypes.data, mk.ctypes.data if mk is not None else None,
+                                               ln32.ctypes.data, n, C.byref(first), self._stream()), "rr_bank_add_plaid",
+                    bad_shape=ValueError)
+        self.table.append(ids, ln32.tolist(), int(first.value))
+        self.padded_len = max(self.padded_len, int(ln.max()))
+        return int(first.value)
+
+    def load_plaid_index(self, index_path: str, passage_ids: Optional[Sequence] = None) -> int:
+        """Fill a compressed bank from a ColBERTv2 / PLAID index directory (read_plaid_index), chunk by chunk through
+        add_compressed.  The bank's codec must hold the index's tables (create the bank with the codec read_plaid_index returns).
+        `passage_ids`: the caller's id of passage number i of the index at position i; default: the passage numbers themselves.
+        Returns the number of passages added."""
+        import torch
+        codec, chunks = read_plaid_index(index_path)
+        mine = self.codec
+        if mine is None:
+            raise NotImplementedError("load_plaid_index on an fp16 bank: create the bank with the index's codec")
+        if (mine.nbits, mine.dim) != (codec.nbits, codec.dim) or not torch.equal(mine.centroids, codec.centroids) \
+                or not torch.equal(mine.bucket_weights, codec.bucket_weights):
+            raise ValueError(f"{index_path}: the index's codec (nbits {codec.nbits}, dim {codec.dim}, {codec.n_centroids} centroids) is "
+                             "not the bank's")
+        added = 0
+        for first, codes, res, doclens in chunks:
+            ids = list(range(first, first + len(doclens))) if passage_ids is None else list(passage_ids[first:first + len(doclens)])
+            if len(ids) != len(doclens):
+                raise ValueError(f"{len(passage_ids)} passage ids for an index of more than {first + len(ids)} passages")
+            self.add_compressed(ids, codes, res, doclens)
+            added += len(doclens)
+        return added
+
     def lookup(self, passage_ids: Sequence):
         """(indices, lengths) of `passage_ids`; KeyError names an id the bank does not hold."""
         return self.table.lookup(passage_ids)
 
     def read(self, passage_id):
         """One passage back on the host (rr_bank_read; synchronises the current stream): (rows [len, D] float16, mask [len]
-        uint8)."""
+        uint8).  A compressed bank returns the decoded rows: what its forwards use."""
         import torch
         idx, lens = self.table.lookup([passage_id])
         n = int(lens[0])

@@ -605,6 +605,35 @@ int rr_forward_interaction_bank(rr_handle h, rr_bank_handle b, const float* quer
                                 const int32_t* seg_len, int padded_context_len, int fusion_from_li, float fusion_multiplier,
                                 float* logits_out, float* logits2_out, float* maxsim_out, void* hip_stream);
 
+/* rr_bank_li_scores: the retriever's own score of (query, passage) pairs straight from a bank: what colbert_score returns
+ * (flmr_utils.py:22-48), the [Lc, Lq] matrix and the MaxSim of every pair, i.e. rr_li_scores without the padded float32
+ * context_li.  Any interaction handle of the bank's device and li_dim, NORMAL or MORES, with or without weights loaded; either
+ * bank format.  li_dim must be a multiple of 16 (RR_ERR_UNSUPPORTED).
+ *   query_li [n_queries, Lq, li_dim] : DEVICE float32, per QUERY, 16-byte aligned.  No query mask: the reference sums over
+ *       every query token.
+ *   pair_passage, pair_query : HOST int32 [n_pairs]: the bank index and the query index of every pair, in any order; a passage
+ *       or a query may appear any number of times.
+ *   scores_out : DEVICE float32 [n_pairs, padded_context_len, Lq] or NULL; -9999 on masked rows and on the rows at or beyond
+ *       the passage's length (pad rows, which count once in the column maximum and cost no arithmetic).
+ *   maxsim_out : DEVICE float32 [n_pairs] or NULL.
+ * ONE launch over the pair list (one workgroup per pair), booked in the profile's `tail` class with
+ * 2 * sum(len) * Lq * li_dim FLOPs.  An fp16 bank's rows are converted to float32 in the load (exact); a compressed bank's rows
+ * are decoded tile by tile in LDS by the one definition of the decoded row (rr_bank_create_plaid), rounded to fp16 first: no
+ * buffer of rows x li_dim is written to global memory.  Nothing is allocated beyond the descriptor staging.
+ * Checked on the host BEFORE anything is enqueued, a refused call writes nothing: null handle, bank or inputs, both outputs
+ * null, a misaligned query_li, bank and handle on different devices, a full-context handle (RR_ERR_BAD_ARG); a different li_dim,
+ * non-positive sizes, a passage index outside the bank, a query index outside n_queries, a passage longer than
+ * padded_context_len (RR_ERR_BAD_SHAPE).  The descriptors are staged through the slots rr_assemble_pairs uses: NOT capturable
+ * into a graph (RR_ERR_BAD_ARG under stream capture).
+ * CONTRACT: scores_out and maxsim_out are bit for bit what rr_li_scores returns when called with K = 1, query_li[pair_query]
+ * per pair, context_li = float32(the bank's rows) zero-padded to padded_context_len and context_mask = the bank's mask bytes, 0
+ * beyond the length.  Hence a compressed bank gives the bits of an fp16 bank holding rr_bank_read's rows, MaxSim is the same
+ * with and without the score block and from run to run, and it equals the maxsim_out of
+ * rr_forward_interaction_bank(fusion_from_li = 1) for the same pairs. */
+int rr_bank_li_scores(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, const int32_t* pair_passage,
+                      const int32_t* pair_query, int n_pairs, int padded_context_len, float* scores_out, float* maxsim_out,
+                      void* hip_stream);
+
 /* rr_head_joint: rr_head with the head RerankModel.forward runs (rr_forward_joint): `loss_fn(logits, logits)`
  * (rerank_model.py:328) — the labels are the logits themselves (2H_BCE: the two heads as class-probability targets).  The
  * head of a packed joint call, after the scatter.  negative_sampling with loss_out: RR_ERR_UNSUPPORTED, as rr_forward_joint. */

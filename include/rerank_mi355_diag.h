@@ -171,7 +171,8 @@ int rr_set_gemm_variant(int variant);
  * percent of a tile period), "persistent_gemm" (1), "gemm_ring_min_tiles" (128: smallest problem, in 256 x 256 tiles, on the
  * persistent ring), "m_alternate" (1: consecutive large launches of the layer chain walk the rows in opposite directions, so that
  * a consumer starts on the rows its producer wrote last; results bit-identical either way),
- * "attn_prio" (1).  "resid_lo8": -1 (the built-in default) = by operand type (1 for fp16, 0 for bf16), 0 / 1 = for every handle that has not
+ * "attn_prio" (1), "li_lds_kb" (72; 16 .. 150: the LDS bytes per workgroup, in KiB, above which the score kernels of rr_li_scores /
+ * rr_bank_li_scores halve their column block; 72 keeps two workgroups per CU, 150 takes the widest block at one).  "resid_lo8": -1 (the built-in default) = by operand type (1 for fp16, 0 for bf16), 0 / 1 = for every handle that has not
  * pinned it; the environment variable RR_RESID_LO8 = 0 | 1, read once at load, replaces the built-in -1 (lets an unmodified test
  * run take either form).  Not thread-safe against running forwards; never needed on the product path. */
 int rr_set_tuning(const char* key, int value);
@@ -261,6 +262,20 @@ int rr_util_plaid_decode_rows(const uint16_t* centroids_f16, int32_t n_centroids
 int rr_op_plaid_decode_rows(const uint16_t* centroids_f16, int32_t n_centroids, const float* bucket_weights, int nbits, int D,
                             const int32_t* codes, const uint8_t* residuals, int64_t first_row, int64_t n_rows,
                             uint16_t* rows_out_f16, void* hip_stream);
+/* The score kernels of rr_li_scores and rr_bank_li_scores (rerank_mi355.h) over raw DEVICE pointers, at any D that is a multiple of
+ * 16: a handle's li_dim is a multiple of 64, so D = 16 (one step of the kernel's walk over D) and D = 32 are reachable here only.
+ * rr_op_li_scores: n pairs, query (pair index) / K; query_li [.., Lq, D], context_li [n, Lc, D], context_mask [n, Lc] float32;
+ * scores_out [n, Lc, Lq] / maxsim_out [n], either may be NULL.
+ * rr_op_bank_li_scores: pairs = DEVICE array [n_pairs] of {int64 first_row; int32 len; int32 query} (len <= padded_context_len;
+ * NOT checked against the buffers: the caller answers for them); nbits 0: rows_f16 [rows, D] fp16 bits (8-byte aligned); nbits 1,
+ * 2, 4, 8: codes / residuals / centroids_f16 / bucket_weights as rr_op_plaid_decode_rows takes them; mask_bytes [rows].
+ * query_li 16-byte aligned.  RR_ERR_UNSUPPORTED for a D or nbits the kernels do not take. */
+int rr_op_li_scores(const float* query_li, const float* context_li, const float* context_mask, int n, int K, int Lq, int Lc, int D,
+                    float* scores_out, float* maxsim_out, void* hip_stream);
+int rr_op_bank_li_scores(const float* query_li, int Lq, int D, const void* pairs, int n_pairs, int padded_context_len,
+                         const uint16_t* rows_f16, const uint8_t* mask_bytes, int nbits, const int32_t* codes, const uint8_t* residuals,
+                         const uint16_t* centroids_f16, const float* bucket_weights, int32_t n_centroids, float* scores_out,
+                         float* maxsim_out, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -100,8 +100,11 @@ _SIGS = {
     "rr_bank_format": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "rr_util_plaid_decode_rows": (C.c_int, [_P, C.c_int32, _P, C.c_int, C.c_int, _P, _P, C.c_int64, _P]),
     "rr_op_plaid_decode_rows": (C.c_int, [_P, C.c_int32, _P, C.c_int, C.c_int, _P, _P, C.c_int64, C.c_int64, _P, _P]),
+    "rr_op_li_scores": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "rr_op_bank_li_scores": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int32, _P, _P, _P]),
     "rr_forward_interaction_bank": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_float,
                                               _P, _P, _P, _P]),
+    "rr_bank_li_scores": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "rr_head": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "rr_head_joint": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "rr_head_lists": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),

@@ -18,8 +18,27 @@
 // per tile pass against 32 KB of L1: 0.33 ms, and requesting the context rows ahead changed nothing there.  What is left:
 // 800 workgroups on 512 slots run as two uneven rounds, and a workgroup stages its 64 KB before it computes.)
 // NaN: a column maximum keeps a NaN once it has seen one (torch.max does; fmaxf would drop it), masked rows never feed it.
+//
+// ONE KERNEL BODY, three sources of a context tile's operand (the lane (li, g) of a wave feeds row ct * 16 + li, elements
+// d + 4 g + e of it, to the matrix core; where those four floats come from is all that differs):
+//   li_src_f32    rr_li_scores and the forward's fusion: padded float32 rows [n][Lc_in][D] and a float mask, query (pair0 + p) / K;
+//   li_src_f16    rr_bank_li_scores on an fp16 bank: a pair list of rr_bank_pair {first_row, len, query} as the bank gathers take
+//                 it, four fp16 values (one 8-byte load, requested a step ahead like the float32 rows) from
+//                 rows + (first_row + c) * D with 64-bit offsets, converted to float32 (exact), the bank's mask bytes;
+//   li_src_plaid  the same on a compressed bank: before its matrix instructions a wave decodes its own 16-row tile with
+//                 plaid_load8 / plaid_finish8 (plaid_decode.h, THE decoded row) in passes of 64 / (D / 8) rows, every lane of the
+//                 wave reaching the butterfly, stores the fp16 values into a wave-private LDS tile [16][D + 8] behind the query
+//                 block (4 waves x 16 x (D + 8) x 2 bytes: 17 KB at D 128, 65 KB at D 512; the + 8 puts the 16 rows of a
+//                 ds_read_b64 4 banks apart) and reads its operand from there.  No barrier: the tile belongs to one wave, whose LDS
+//                 operations complete in order; wavefront-scope fences keep the compiler from moving the reads over the writes.
+//                 Nothing of rows x D goes to global memory.
+// A bank pair holds len rows; the rows len .. Lc - 1 are pad rows (-9999, once in the column maximum), and a tile that lies
+// wholly beyond the pair's rows runs no matrix instruction and no decode (its accumulators stay zero and every row of it is
+// masked; the float32 source takes the same path for Lc_in <= c < Lc).  The arithmetic of an entry is the same instruction
+// sequence on the same float32 values in all three, so the three agree bit for bit on equal rows.
 #include <atomic>
 
+#include "plaid_decode.h"      // plaid_load8 / plaid_finish8, pack2h
 #include "rr_common.h"
 
 namespace {
@@ -28,24 +47,113 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int LI_JT_MAX = 8;             // query tiles (16 columns) per column block: 1, 2, 4 or 8, after Lq
 constexpr float LI_MASKED = -9999.0f;
+constexpr int LI_TILE_PAD = 8;           // fp16 values behind a row of a decoded tile (li_src_plaid)
 
 __device__ __forceinline__ float nan_max(float m, float v) { return (v > m || v != v) ? v : m; }
 
-template <int LI_JT>
-__global__ __launch_bounds__(256) void li_scores_kernel(const float* __restrict__ query_li, const float* __restrict__ context_li,
-                                                        const float* __restrict__ context_mask, int K, int Lq, int Lc_in, int Lc,
-                                                        int D, int pair0, float* __restrict__ scores, float* __restrict__ maxsim) {
+// four fp16 values (8 bytes, global or LDS) as the float32 operand of one step
+__device__ __forceinline__ f32x4 half4(const uint16_t* p) {
+  const uint2 u = *(const uint2*)p;
+  const float2 a = unpack2<1>(u.x), b = unpack2<1>(u.y);
+  return f32x4{a.x, a.y, b.x, b.y};
+}
+
+// ---- the sources of a context tile's operand.  open(p, D): the pair's query, its rows and how many it holds; row(pr, c, g, ..):
+// the cursor of lane (li, g) on context row c (a row the pair holds), at(cur, d) its four floats of step d; keep(pr, row): the mask.
+struct li_src_f32 {
+  const float* context_li;
+  const float* context_mask;
+  int K, Lc_in, pair0;
+  static constexpr bool TILE = false;
+  struct pair_t { const float* rows; const float* mask; int len, query, out; };
+  typedef const float* cursor;
+  __device__ __forceinline__ pair_t open(int p, int D) const {
+    return pair_t{context_li + (size_t)p * Lc_in * D, context_mask + (size_t)p * Lc_in, Lc_in, (pair0 + p) / K, p};
+  }
+  __device__ __forceinline__ cursor row(const pair_t& pr, int c, int g, int D, int li, const uint16_t*) const {
+    return pr.rows + (size_t)c * D + 4 * g;
+  }
+  static __device__ __forceinline__ f32x4 at(cursor cur, int d) { return *(const f32x4*)(cur + d); }
+  __device__ __forceinline__ bool keep(const pair_t& pr, int row) const { return pr.mask[row] != 0.0f; }
+};
+
+struct li_src_f16 {
+  const rr_bank_pair* pairs;
+  const int32_t* slot;               // the output row of workgroup p, or null: p itself
+  const uint16_t* rows;
+  const uint8_t* mask_bytes;
+  static constexpr bool TILE = false;
+  struct pair_t { const uint16_t* rows; const uint8_t* mask; int len, query, out; };
+  typedef const uint16_t* cursor;
+  __device__ __forceinline__ pair_t open(int p, int D) const {
+    const rr_bank_pair d = pairs[p];
+    return pair_t{rows + (size_t)d.first_row * D, mask_bytes + d.first_row, d.len, d.query, slot ? slot[p] : p};
+  }
+  __device__ __forceinline__ cursor row(const pair_t& pr, int c, int g, int D, int li, const uint16_t*) const {
+    return pr.rows + (size_t)c * D + 4 * g;
+  }
+  static __device__ __forceinline__ f32x4 at(cursor cur, int d) { return half4(cur + d); }
+  __device__ __forceinline__ bool keep(const pair_t& pr, int row) const { return pr.mask[row] != 0; }
+};
+
+template <int NBITS>
+struct li_src_plaid {
+  const rr_bank_pair* pairs;
+  const int32_t* slot;
+  const int32_t* codes;
+  const uint8_t* resid;
+  const uint16_t* centroids;
+  const float* weights;
+  int C;
+  const uint8_t* mask_bytes;
+  static constexpr bool TILE = true;
+  struct pair_t { long long first_row; const uint8_t* mask; int len, query, out; };
+  typedef const uint16_t* cursor;
+  __device__ __forceinline__ pair_t open(int p, int D) const {
+    const rr_bank_pair d = pairs[p];
+    return pair_t{d.first_row, mask_bytes + d.first_row, d.len, d.query, slot ? slot[p] : p};
+  }
+  // the wave's tile ct decoded into `tile` [16][D + LI_TILE_PAD] fp16: passes of rpw rows, D / 8 lanes per row as the bank's row
+  // kernels; the pass loop is wave-uniform and EVERY lane reaches plaid_finish8 (its butterfly is cross-lane), loads and stores
+  // are predicated; rows the pair does not hold are not written (and never read: row() is asked for held rows only)
+  __device__ __forceinline__ void stage(const pair_t& pr, int ct, int D, int lane, uint16_t* tile) const {
+    const int lpr = D / 8, rpw = min(64 / lpr, 16), sub = lane / lpr, c8 = lane - sub * lpr;
+    for (int r0 = 0; r0 < 16; r0 += rpw) {
+      const int r = r0 + sub, c = ct * 16 + r;
+      const bool in = sub < rpw && c < pr.len;
+      float s[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) s[k] = 0.f;
+      if (in) plaid_load8<NBITS>(codes, resid, centroids, weights, C, pr.first_row + c, D, c8, s);
+      plaid_finish8(s, lpr);                               // all 64 lanes; s now holds fp16 values, packing them is exact
+      if (in)
+        *(uint4*)(tile + r * (D + LI_TILE_PAD) + 8 * c8) =
+            make_uint4(pack2h(s[0], s[1]), pack2h(s[2], s[3]), pack2h(s[4], s[5]), pack2h(s[6], s[7]));
+    }
+  }
+  __device__ __forceinline__ cursor row(const pair_t&, int, int g, int D, int li, const uint16_t* tile) const {
+    return tile + li * (D + LI_TILE_PAD) + 4 * g;
+  }
+  static __device__ __forceinline__ f32x4 at(cursor cur, int d) { return half4(cur + d); }
+  __device__ __forceinline__ bool keep(const pair_t& pr, int row) const { return pr.mask[row] != 0; }
+};
+
+template <int LI_JT, class SRC>
+__global__ __launch_bounds__(256) void li_scores_kernel(const float* __restrict__ query_li, const SRC src, int Lq, int Lc, int D,
+                                                        float* __restrict__ scores, float* __restrict__ maxsim) {
   constexpr int LI_JB = 16 * LI_JT;      // columns per block
-  extern __shared__ __attribute__((aligned(16))) float qblk[];      // [LI_JB][D + 4]: the block's query rows
-  const int ldq = D + 4;                 // row stride: the 16 rows of a tile start 4 banks apart (D is a multiple of 64)
+  extern __shared__ __attribute__((aligned(16))) float qblk[];      // [LI_JB][D + 4]: the block's query rows; TILE: the tiles behind
+  const int ldq = D + 4;                 // row stride: at a handle's D (a multiple of 64) the 16 rows of a tile start 4 banks
+                                         // apart; the operators' D = 16 / 32 / 48 give strides of 20 / 36 / 52 dwords (right, not tuned)
   __shared__ float colmax[4][LI_JB];
   __shared__ float blockmax[LI_JB];
   const int p = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = lane & 15, g = lane >> 4;
-  const float* Q = query_li + (size_t)((pair0 + p) / K) * Lq * D;
-  const float* Cx = context_li + (size_t)p * Lc_in * D;
-  const float* M = context_mask + (size_t)p * Lc_in;
-  float* out = scores ? scores + (size_t)p * Lc * Lq : nullptr;
+  const typename SRC::pair_t pr = src.open(p, D);
+  const int Lc_in = pr.len;              // the rows the pair holds; Lc_in .. Lc - 1 are written as masked rows
+  const float* Q = query_li + (size_t)pr.query * Lq * D;
+  uint16_t* tile = SRC::TILE ? (uint16_t*)(qblk + LI_JB * ldq) + wave * 16 * (D + LI_TILE_PAD) : nullptr;
+  float* out = scores ? scores + (size_t)pr.out * Lc * Lq : nullptr;
   const int c_tiles = (Lc + 15) / 16;
   float sum = 0.0f;                      // thread 0 only
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -65,33 +173,43 @@ __global__ __launch_bounds__(256) void li_scores_kernel(const float* __restrict_
     for (int ct = wave; ct < c_tiles; ct += 4) {
       const int c = ct * 16 + li;                           // the context row this lane feeds to the matrix core
       const bool c_ok = c < Lc_in;
-      const float* crow = Cx + (size_t)(c_ok ? c : 0) * D + 4 * g;
       f32x4 acc[LI_JT];
 #pragma unroll
       for (int t = 0; t < LI_JT; ++t) acc[t] = zero4;
-      const float* qrow = qblk + li * ldq + 4 * g;
-      f32x4 a = c_ok ? *(const f32x4*)crow : zero4;
-      for (int d = 0; d < D; d += 16) {
-        // the context rows come from HBM: those of step d + 16 are requested before the matrix instructions of step d issue
-        const f32x4 a_n = (c_ok && d + 16 < D) ? *(const f32x4*)(crow + d + 16) : zero4;
-        f32x4 b[LI_JT];
-#pragma unroll
-        for (int t = 0; t < LI_JT; ++t) b[t] = *(const f32x4*)(qrow + t * 16 * ldq + d);
-        // e outside, tiles inside: consecutive instructions write different accumulators (40 cycles dependent latency, 32 issue)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-#pragma unroll
-          for (int t = 0; t < LI_JT; ++t)
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b[t][e], acc[t], 0, 0, 0);
+      if (ct * 16 < Lc_in) {                                // wave-uniform: a tile beyond the pair's rows holds masked rows only
+        if constexpr (SRC::TILE) {
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // the reads of the last tile stay in front of these writes
+          src.stage(pr, ct, D, lane, tile);
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // lanes read what other lanes of the wave wrote
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
-        a = a_n;
+        const typename SRC::cursor crow = src.row(pr, c_ok ? c : 0, g, D, li, tile);
+        const float* qrow = qblk + li * ldq + 4 * g;
+        f32x4 a = c_ok ? SRC::at(crow, 0) : zero4;
+        for (int d = 0; d < D; d += 16) {
+          // the context rows come from HBM (a compressed bank's: from the wave's LDS tile): those of step d + 16 are requested
+          // before the matrix instructions of step d issue
+          const f32x4 a_n = (c_ok && d + 16 < D) ? SRC::at(crow, d + 16) : zero4;
+          f32x4 b[LI_JT];
+#pragma unroll
+          for (int t = 0; t < LI_JT; ++t) b[t] = *(const f32x4*)(qrow + t * 16 * ldq + d);
+          // e outside, tiles inside: consecutive instructions write different accumulators (40 cycles dependent latency, 32 issue)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+#pragma unroll
+            for (int t = 0; t < LI_JT; ++t)
+              acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b[t][e], acc[t], 0, 0, 0);
+          }
+          a = a_n;
+        }
       }
       // accumulator element r of this lane: row ct * 16 + 4 g + r, column j0 + t * 16 + li
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = ct * 16 + 4 * g + r;
         if (row >= Lc) continue;
-        const bool keep = row < Lc_in && M[row] != 0.0f;
+        const bool keep = row < Lc_in && src.keep(pr, row);
 #pragma unroll
         for (int t = 0; t < LI_JT; ++t) {
           const int j = j0 + t * 16 + li;
@@ -123,10 +241,54 @@ __global__ __launch_bounds__(256) void li_scores_kernel(const float* __restrict_
       }
     }
   }
-  if (maxsim && threadIdx.x == 0) maxsim[p] = sum;
+  if (maxsim && threadIdx.x == 0) maxsim[pr.out] = sum;
+}
+
+// rr_set_tuning("li_lds_kb"): the LDS bytes of a workgroup above which the column block is halved (72: two workgroups per CU)
+std::atomic<int> g_li_lds_kb{72};
+
+template <int JT, class SRC>
+hipError_t li_launch_jt(const float* query_li, const SRC& src, int n, int Lq, int Lc, int D, size_t lds, float* scores, float* maxsim,
+                        hipStream_t st) {
+  static std::atomic<unsigned long long> attr_set{0};   // per device ordinal (see gemm_bf16.hip ensure_lds_attr)
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (dev < 0 || dev >= 64 || !((attr_set.load(std::memory_order_acquire) >> dev) & 1ull)) {
+    e = hipFuncSetAttribute((const void*)li_scores_kernel<JT, SRC>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    if (e != hipSuccess) return e;
+    if (dev >= 0 && dev < 64) attr_set.fetch_or(1ull << dev, std::memory_order_release);
+  }
+  hipLaunchKernelGGL((li_scores_kernel<JT, SRC>), dim3((unsigned)n), dim3(256), lds, st, query_li, src, Lq, Lc, D, scores, maxsim);
+  return hipGetLastError();
+}
+
+// one workgroup per pair; tile_bytes: the decoded tiles of the four waves behind the query block (0 unless SRC::TILE)
+template <class SRC>
+hipError_t li_launch(const float* query_li, const SRC& src, int n, int Lq, int Lc, int D, size_t tile_bytes, float* scores,
+                     float* maxsim, hipStream_t st) {
+  // the narrowest column block that takes Lq in one pass (a tile without a column is matrix-core time), 128 columns beyond;
+  // halved while its query rows [16 JT][D + 4] and the decoded tiles would not leave room for two workgroups per CU (D above
+  // 128; a compressed bank at D = 128 already)
+  int jt = Lq <= 16 ? 1 : Lq <= 32 ? 2 : Lq <= 64 ? 4 : LI_JT_MAX;
+  auto lds_bytes = [&](int t) { return (size_t)16 * t * (D + 4) * sizeof(float) + tile_bytes; };
+  const size_t limit = (size_t)g_li_lds_kb.load(std::memory_order_relaxed) * 1024;
+  while (jt > 1 && lds_bytes(jt) > limit) jt /= 2;
+  const size_t lds = lds_bytes(jt);
+  if (lds > 150 * 1024) return hipErrorInvalidValue;
+  if (jt == 1) return li_launch_jt<1>(query_li, src, n, Lq, Lc, D, lds, scores, maxsim, st);
+  if (jt == 2) return li_launch_jt<2>(query_li, src, n, Lq, Lc, D, lds, scores, maxsim, st);
+  if (jt == 4) return li_launch_jt<4>(query_li, src, n, Lq, Lc, D, lds, scores, maxsim, st);
+  return li_launch_jt<LI_JT_MAX>(query_li, src, n, Lq, Lc, D, lds, scores, maxsim, st);
 }
 
 }  // namespace
+
+int rr_set_li_lds_kb(int kb) {
+  if (kb < 16 || kb > 150) return -1;
+  g_li_lds_kb.store(kb, std::memory_order_relaxed);
+  return 0;
+}
 
 // n pairs from pair pair0 of the query-major pair order on; context_li / context_mask / scores / maxsim point at the first of
 // them.  Lc_in rows per pair are read, Lc >= Lc_in rows per pair written (the rest as masked rows).  scores or maxsim may be null.
@@ -136,31 +298,39 @@ hipError_t rr_launch_li_scores(const float* query_li, const float* context_li, c
       !context_mask || (!scores && !maxsim))
     return hipErrorInvalidValue;
   if ((((uintptr_t)query_li) | ((uintptr_t)context_li)) & 15) return hipErrorInvalidValue;   // 16-byte row loads
-  // the narrowest column block that takes Lq in one pass (a tile without a column is matrix-core time), 128 columns beyond;
-  // halved while its query rows [16 JT][D + 4] would not leave room for two workgroups per CU (D above 128)
-  int jt = Lq <= 16 ? 1 : Lq <= 32 ? 2 : Lq <= 64 ? 4 : LI_JT_MAX;
-  auto lds_bytes = [&](int t) { return (size_t)16 * t * (D + 4) * sizeof(float); };
-  while (jt > 1 && lds_bytes(jt) > 72 * 1024) jt /= 2;
-  const size_t lds = lds_bytes(jt);
-  if (lds > 150 * 1024) return hipErrorInvalidValue;
-#define LI_LAUNCH(JT)                                                                                                          \
-  do {                                                                                                                         \
-    static std::atomic<unsigned long long> attr_set{0};   /* per device ordinal (see gemm_bf16.hip ensure_lds_attr) */        \
-    int dev = 0;                                                                                                               \
-    hipError_t e = hipGetDevice(&dev);                                                                                         \
-    if (e != hipSuccess) return e;                                                                                             \
-    if (dev < 0 || dev >= 64 || !((attr_set.load(std::memory_order_acquire) >> dev) & 1ull)) {                                 \
-      e = hipFuncSetAttribute((const void*)li_scores_kernel<JT>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);      \
-      if (e != hipSuccess) return e;                                                                                           \
-      if (dev >= 0 && dev < 64) attr_set.fetch_or(1ull << dev, std::memory_order_release);                                     \
-    }                                                                                                                          \
-    hipLaunchKernelGGL(li_scores_kernel<JT>, dim3((unsigned)n), dim3(256), lds, st, query_li, context_li, context_mask, K, Lq, \
-                       Lc_in, Lc, D, pair0, scores, maxsim);                                                                   \
-  } while (0)
-  if (jt == 1) LI_LAUNCH(1);
-  else if (jt == 2) LI_LAUNCH(2);
-  else if (jt == 4) LI_LAUNCH(4);
-  else LI_LAUNCH(LI_JT_MAX);
-#undef LI_LAUNCH
-  return hipGetLastError();
+  return li_launch(query_li, li_src_f32{context_li, context_mask, K, Lc_in, pair0}, n, Lq, Lc, D, 0, scores, maxsim, st);
+}
+
+// the same over a pair list and an fp16 bank: pairs [n] on the device, each checked on the host (first_row + len inside the bank,
+// len <= Lc, query inside query_li); scores [n][Lc][Lq], maxsim [n], either may be null.  slot [n] (device) or null: workgroup p
+// writes row slot[p] of the outputs, so that the host can start the longest passages first (one workgroup per pair: 800 pairs of
+// 64 .. 512 rows on 512 slots end 20 - 25 % sooner that way, profiles/bank_li_scores_bench_call_order.json.log) and the caller still
+// gets its own order; a permutation of 0 .. n - 1, checked by whoever builds it
+hipError_t rr_launch_bank_li_scores(const rr_bank_pair* pairs, const int32_t* slot, int n, int Lq, int Lc, int D, const float* query_li, const uint16_t* rows,
+                                    const uint8_t* mask_bytes, float* scores, float* maxsim, hipStream_t st) {
+  if (n <= 0 || Lq <= 0 || Lc <= 0 || D <= 0 || D % 16 || !pairs || !query_li || !rows || !mask_bytes || (!scores && !maxsim))
+    return hipErrorInvalidValue;
+  if ((((uintptr_t)query_li) & 15) || (((uintptr_t)rows) & 7)) return hipErrorInvalidValue;   // 16-byte query, 8-byte bank loads
+  return li_launch(query_li, li_src_f16{pairs, slot, rows, mask_bytes}, n, Lq, Lc, D, 0, scores, maxsim, st);
+}
+
+// ... and a compressed bank (tables as rr_launch_bank_gather_plaid takes them)
+hipError_t rr_launch_bank_li_scores_plaid(const rr_bank_pair* pairs, const int32_t* slot, int n, int Lq, int Lc, int D, const float* query_li, int nbits,
+                                          const int32_t* codes, const uint8_t* resid, const uint16_t* centroids, const float* weights,
+                                          int C, const uint8_t* mask_bytes, float* scores, float* maxsim, hipStream_t st) {
+  if (n <= 0 || Lq <= 0 || Lc <= 0 || D % 16 || !rr_plaid_shape_ok(nbits, D) || C <= 0 || !pairs || !query_li || !codes || !resid ||
+      !centroids || !weights || !mask_bytes || (!scores && !maxsim))
+    return hipErrorInvalidValue;
+  if (((((uintptr_t)query_li) | ((uintptr_t)centroids)) & 15) || (((uintptr_t)resid) & 7) || (((uintptr_t)codes) & 3))
+    return hipErrorInvalidValue;
+  const size_t tile_bytes = (size_t)4 * 16 * (D + LI_TILE_PAD) * sizeof(uint16_t);
+#define LI_PLAID(NB) \
+  return li_launch(query_li, li_src_plaid<NB>{pairs, slot, codes, resid, centroids, weights, C, mask_bytes}, n, Lq, Lc, D, tile_bytes, scores, maxsim, st)
+  switch (nbits) {
+    case 1: LI_PLAID(1);
+    case 2: LI_PLAID(2);
+    case 4: LI_PLAID(4);
+    default: LI_PLAID(8);
+  }
+#undef LI_PLAID
 }

@@ -20,7 +20,7 @@
 //                       compressed bank, rr_op_plaid_decode_rows).
 //   rr_plaid_decode_rows_host  the same arithmetic in host code (rr_util_plaid_decode_rows): the bit-level definition.
 //
-// THE DECODED ROW (one definition, plaid_bucket / plaid_sumsq8 / the pairwise tree / plaid_finish below, compiled for both sides):
+// THE DECODED ROW (one definition, plaid_bucket / plaid_sumsq8 / the pairwise tree / plaid_finish8 of plaid_decode.h, compiled for both sides):
 //   element e lies in residual byte e / (8 / nbits), group g = e % (8 / nbits) counted from the most significant end;
 //   x = (byte >> (8 - nbits * (g + 1))) & (2^nbits - 1); bucket = x with its nbits bits reversed (binarize writes bit 0 first and
 //   packbits fills bytes MSB-first, residual.py:188-204);  s_e = float(centroid[code][e]) + w[bucket], one float32 add;
@@ -36,24 +36,10 @@
 // lane group of a row is then a power of two and the butterfly stays inside it) and never leave before the butterfly: every lane
 // of a wave reaches it, loads and stores are predicated.  The bucket weights (at most 256 floats, 1 KiB) are read through the
 // vector cache: a block decodes 16 - 32 rows, and filling LDS per block would cost a barrier and as many bytes as the rows do.
+#include "plaid_decode.h"      // load8, plaid_bucket / plaid_sumsq8 / plaid_scale, plaid_load8, plaid_finish8
 #include "rr_common.h"
 
 namespace {
-
-__device__ __forceinline__ uint32_t pack2h(float lo, float hi) { return pack2<1>(lo, hi); }
-
-// 8 consecutive elements of a source row as floats; SRC_F16: the row holds fp16 bits
-template <bool SRC_F16>
-__device__ __forceinline__ void load8(const void* row, int c8, float (&v)[8]) {
-  if constexpr (SRC_F16) {
-    const uint4 u = ((const uint4*)row)[c8];
-    const float2 a = unpack2<1>(u.x), b = unpack2<1>(u.y), c = unpack2<1>(u.z), d = unpack2<1>(u.w);
-    v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y; v[4] = c.x; v[5] = c.y; v[6] = d.x; v[7] = d.y;
-  } else {
-    const float4 a = ((const float4*)row)[2 * c8], b = ((const float4*)row)[2 * c8 + 1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  }
-}
 
 // one lane group (lpr = D / 8 lanes) per SOURCE row (i, j) of the padded input; rows at or beyond the passage's length do nothing
 template <bool SRC_F16>
@@ -124,22 +110,6 @@ __global__ __launch_bounds__(256) void bank_gather_kernel(const rr_bank_pair* __
   }
 }
 
-// ---- PLAID residual decode.  plaid_bucket: the bucket of element k (0..7) of a lane's chunk from its NBITS residual bytes
-// (r[b] = byte b of the chunk, in memory order).
-template <int NBITS>
-__host__ __device__ __forceinline__ uint32_t plaid_bucket(const uint8_t (&r)[NBITS], int k) {
-  constexpr int per = 8 / NBITS;                       // elements per byte
-  const int g = k % per;
-  const uint32_t x = ((uint32_t)r[k / per] >> (8 - NBITS * (g + 1))) & ((1u << NBITS) - 1u);
-  return __builtin_bitreverse32(x) >> (32 - NBITS);
-}
-// the sum of squares of one 8-element chunk: an explicit fmaf chain, element 0 first
-__host__ __device__ __forceinline__ float plaid_sumsq8(const float (&s)[8]) {
-  float q = fmaf(s[0], s[0], 0.f);
-#pragma unroll
-  for (int k = 1; k < 8; ++k) q = fmaf(s[k], s[k], q);
-  return q;
-}
 // float32 -> fp16 bits, round to nearest even, in host code (the device's conversion instruction rounds the same way)
 inline uint16_t plaid_f16_bits(float f) {
   const uint32_t u = __builtin_bit_cast(uint32_t, f), sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
@@ -153,53 +123,6 @@ inline uint16_t plaid_f16_bits(float f) {
   uint32_t h = e >= -14 ? (((uint32_t)(e + 15) << 10) + (keep - 0x400u)) : keep;
   if (rest > half || (rest == half && (h & 1u))) ++h;                           // a carry into the exponent is the right value
   return (uint16_t)(sign | h);
-}
-// the divisor of the definition
-__host__ __device__ __forceinline__ float plaid_scale(float n) { return fmaxf(n, 1e-12f); }
-
-// one lane's chunk c8 of bank row `row`: s[0..8) = centroid + bucket weight.  code is clamped to [0, C): rr_bank_add_plaid has
-// checked it on the host, rr_op_plaid_decode_rows runs over raw pointers and must not read outside the table.
-template <int NBITS>
-__device__ __forceinline__ void plaid_load8(const int32_t* __restrict__ codes, const uint8_t* __restrict__ resid,
-                                            const uint16_t* __restrict__ centroids, const float* __restrict__ weights, int C,
-                                            long long row, int D, int c8, float (&s)[8]) {
-  const int code = min(max(codes[row], 0), C - 1);
-  const uint8_t* rp = resid + (size_t)row * ((size_t)D / 8 * NBITS) + (size_t)c8 * NBITS;
-  uint8_t r[NBITS];
-  if constexpr (NBITS == 1) {
-    r[0] = rp[0];
-  } else if constexpr (NBITS == 2) {
-    const uint32_t u = *(const uint16_t*)rp;
-    r[0] = (uint8_t)u; r[1] = (uint8_t)(u >> 8);
-  } else if constexpr (NBITS == 4) {
-    const uint32_t u = *(const uint32_t*)rp;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) r[b] = (uint8_t)(u >> (8 * b));
-  } else {
-    const uint2 u = *(const uint2*)rp;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) { r[b] = (uint8_t)(u.x >> (8 * b)); r[4 + b] = (uint8_t)(u.y >> (8 * b)); }
-  }
-  float cv[8];
-  load8<true>(centroids + (size_t)code * D, c8, cv);
-#pragma unroll
-  for (int k = 0; k < 8; ++k) s[k] = cv[k] + weights[plaid_bucket<NBITS>(r, k)];
-}
-
-// s[0..8) of a lane (zeros where the lane decodes nothing) -> the decoded values as floats that hold fp16 values.  EVERY lane
-// of the wave calls this: the butterfly over the lpr lanes of a row (lpr a power of two, the group aligned to it) is cross-lane.
-__device__ __forceinline__ void plaid_finish8(float (&s)[8], int lpr) {
-  float q = plaid_sumsq8(s);
-  for (int o = 1; o < lpr; o <<= 1) q += __shfl_xor(q, o, 64);
-  const float d = plaid_scale(sqrtf(q));
-  uint32_t h[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) h[k] = pack2<1>(s[2 * k] / d, s[2 * k + 1] / d);      // fp16 FIRST, as the fp16 bank holds it
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float2 f = unpack2<1>(h[k]);
-    s[2 * k] = f.x; s[2 * k + 1] = f.y;
-  }
 }
 
 // bank_gather_kernel with the context rows decoded from a compressed bank; outputs as there

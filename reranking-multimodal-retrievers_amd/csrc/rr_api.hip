@@ -2728,6 +2728,72 @@ static int li_scores_call(rr_handle h, const float* query_li, const float* conte
   return RR_OK;
 }
 
+// rr_bank_li_scores (include/rerank_mi355.h): every check on the host first, then one staged upload and one launch
+static int bank_li_scores_call(rr_handle h, rr_bank* b, const float* query_li, int n_queries, int Lq, const int32_t* pair_passage,
+                               const int32_t* pair_query, int n_pairs, int padded_context_len, float* scores_out, float* maxsim_out,
+                               void* hip_stream) {
+  const char* what = "rr_bank_li_scores";
+  if (!h) return RR_ERR_BAD_ARG;
+  rr_model* m = h;
+  const rr_config& c = m->cfg;
+  if (!b || !query_li || !pair_passage || !pair_query) return fail(m, RR_ERR_BAD_ARG, "%s: null argument", what);
+  if (!scores_out && !maxsim_out) return fail(m, RR_ERR_BAD_ARG, "%s: scores_out and maxsim_out are both null", what);
+  if (c.model_kind == RR_MODEL_FULL_CONTEXT) return fail(m, RR_ERR_BAD_ARG, "%s on a full-context model", what);
+  if (b->device != c.device) return fail(m, RR_ERR_BAD_ARG, "%s: the bank lives on device %d, the handle on %d", what, b->device, c.device);
+  if (b->D != c.li_dim) return fail(m, RR_ERR_BAD_SHAPE, "%s: the bank holds rows of %d, the handle's li_dim is %d", what, b->D, c.li_dim);
+  const int D = c.li_dim;
+  if (D % 16) return fail(m, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a multiple of 16)", what, D);
+  if (((uintptr_t)query_li) & 15) return fail(m, RR_ERR_BAD_ARG, "%s: query_li must be 16-byte aligned", what);
+  if (n_queries <= 0 || Lq <= 0 || n_pairs <= 0 || padded_context_len <= 0)
+    return fail(m, RR_ERR_BAD_SHAPE, "%s: n_queries=%d Lq=%d n_pairs=%d padded_context_len=%d", what, n_queries, Lq, n_pairs,
+                padded_context_len);
+  if (n_pairs > (1 << 24)) return fail(m, RR_ERR_BAD_SHAPE, "%s: %d pairs", what, n_pairs);
+  RR_TRY(check_rows(m, what, n_pairs, padded_context_len));
+  const long long held = (long long)b->first.size();
+  std::vector<rr_bank_pair> checked((size_t)n_pairs);
+  double rows = 0.0;
+  for (int i = 0; i < n_pairs; ++i) {
+    const int32_t pi = pair_passage[i], qi = pair_query[i];
+    if (pi < 0 || pi >= held) return fail(m, RR_ERR_BAD_SHAPE, "%s: pair %d names passage %d, the bank holds %lld", what, i, pi, held);
+    if (qi < 0 || qi >= n_queries) return fail(m, RR_ERR_BAD_SHAPE, "%s: pair %d names query %d of %d", what, i, qi, n_queries);
+    if (b->len[(size_t)pi] > padded_context_len)
+      return fail(m, RR_ERR_BAD_SHAPE, "%s: pair %d: passage %d holds %d rows, padded_context_len is %d", what, i, pi, b->len[(size_t)pi],
+                  padded_context_len);
+    checked[(size_t)i] = rr_bank_pair{b->first[(size_t)pi], b->len[(size_t)pi], qi};
+    rows += b->len[(size_t)pi];
+  }
+  // one workgroup per pair, dispatched in launch order: the longest passages go first (stable, so equal lengths keep call order)
+  // and every workgroup is told which output row is its pair's.  One upload: [n] descriptors in launch order, then [n] int32
+  // output rows.
+  std::vector<int32_t> order((size_t)n_pairs);
+  for (int i = 0; i < n_pairs; ++i) order[(size_t)i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return checked[(size_t)x].len > checked[(size_t)y].len; });
+  const size_t desc_bytes = (size_t)n_pairs * sizeof(rr_bank_pair);
+  std::vector<char> upload(desc_bytes + (size_t)n_pairs * sizeof(int32_t));
+  rr_bank_pair* up = (rr_bank_pair*)upload.data();
+  for (int i = 0; i < n_pairs; ++i) up[i] = checked[(size_t)order[(size_t)i]];
+  memcpy(upload.data() + desc_bytes, order.data(), (size_t)n_pairs * sizeof(int32_t));
+  hipStream_t st = (hipStream_t)hip_stream;
+  void* dev = nullptr;
+  RR_TRY(asm_stage(m, what, upload.data(), upload.size(), st, &dev));      // refuses a capturing stream
+  const int32_t* slot = (const int32_t*)((const char*)dev + desc_bytes);
+  m->last_stream = st;
+  // bytes: the rows that exist (a compressed row: its code, its residual bytes and the centroid row from L2), one mask byte per
+  // row, the query block per pair, the outputs; pad rows cost their -9999 in the score block only
+  const double row_bytes = b->nbits ? 4.0 + D * (b->nbits / 8.0 + 2.0) : 2.0 * D;
+  const double bytes = rows * (row_bytes + 1.0) + (double)n_pairs * (16.0 + 4.0 * Lq * D) +
+                       (scores_out ? 4.0 * n_pairs * (double)padded_context_len * Lq : 0.0) + (maxsim_out ? 4.0 * n_pairs : 0.0);
+  if (b->nbits)
+    RR_RUN(m, st, RR_K_TAIL, 2.0 * rows * Lq * D, bytes,
+           rr_launch_bank_li_scores_plaid((const rr_bank_pair*)dev, slot, n_pairs, Lq, padded_context_len, D, query_li, b->nbits, b->codes,
+                                          b->resid, b->centroids, b->weights, b->n_centroids, b->mask, scores_out, maxsim_out, st));
+  else
+    RR_RUN(m, st, RR_K_TAIL, 2.0 * rows * Lq * D, bytes,
+           rr_launch_bank_li_scores((const rr_bank_pair*)dev, slot, n_pairs, Lq, padded_context_len, D, query_li, b->rows, b->mask, scores_out,
+                                    maxsim_out, st));
+  return asm_done(m, st);
+}
+
 static int64_t rr_debug_read_impl(rr_handle h, const char* name, float* host_out, int64_t max_elems) {
   if (!h || !name || !host_out) return RR_ERR_BAD_ARG;
   if (hipSetDevice(h->cfg.device) != hipSuccess) return RR_ERR_HIP;
@@ -2843,6 +2909,7 @@ int rr_set_tuning(const char* key, int value) {
   if (!strcmp(key, "gemm_grid_cus")) { rr_set_gemm_grid_cus(value); return RR_OK; }
   if (!strcmp(key, "gemm_desync")) return rr_set_gemm_desync(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
   if (!strcmp(key, "m_alternate")) return rr_set_m_alternate(value);
+  if (!strcmp(key, "li_lds_kb")) return rr_set_li_lds_kb(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
   if (!strcmp(key, "attn_prio")) return rr_set_attn_prio(value);
   if (!strcmp(key, "attn_fixed_ref")) return rr_set_attn_fixed_ref(value);
   return RR_ERR_BAD_ARG;
@@ -3339,6 +3406,24 @@ int rr_bank_read(rr_bank_handle b, int32_t index, uint16_t* rows_out, uint8_t* m
 }
 int rr_forward_interaction_bank(rr_handle h, rr_bank_handle b, const float* query_li, const float* query_mask, int n_queries, int Lq, const int32_t* pair_passage, const int32_t* pair_query, int n_segments, const int32_t* seg_pairs, const int32_t* seg_len, int padded_context_len, int fusion_from_li, float fusion_multiplier, float* logits_out, float* logits2_out, float* maxsim_out, void* hip_stream) {
   return guarded(h, [&]() -> int { return forward_interaction_bank(h, b, query_li, query_mask, n_queries, Lq, pair_passage, pair_query, n_segments, seg_pairs, seg_len, padded_context_len, fusion_from_li, fusion_multiplier, logits_out, logits2_out, maxsim_out, hip_stream); });
+}
+int rr_bank_li_scores(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, const int32_t* pair_passage, const int32_t* pair_query, int n_pairs, int padded_context_len, float* scores_out, float* maxsim_out, void* hip_stream) {
+  return guarded(h, [&]() -> int { return bank_li_scores_call(h, b, query_li, n_queries, Lq, pair_passage, pair_query, n_pairs, padded_context_len, scores_out, maxsim_out, hip_stream); });
+}
+int rr_op_li_scores(const float* query_li, const float* context_li, const float* context_mask, int n, int K, int Lq, int Lc, int D, float* scores_out, float* maxsim_out, void* hip_stream) {
+  if (!query_li || !context_li || !context_mask || (!scores_out && !maxsim_out)) return RR_ERR_BAD_ARG;
+  if (D <= 0 || D % 16) return RR_ERR_UNSUPPORTED;
+  if (n <= 0 || K <= 0 || Lq <= 0 || Lc <= 0) return RR_ERR_BAD_SHAPE;
+  return rr_launch_li_scores(query_li, context_li, context_mask, n, K, Lq, Lc, Lc, D, 0, scores_out, maxsim_out, (hipStream_t)hip_stream) == hipSuccess ? RR_OK : RR_ERR_HIP;
+}
+int rr_op_bank_li_scores(const float* query_li, int Lq, int D, const void* pairs, int n_pairs, int padded_context_len, const uint16_t* rows_f16, const uint8_t* mask_bytes, int nbits, const int32_t* codes, const uint8_t* residuals, const uint16_t* centroids_f16, const float* bucket_weights, int32_t n_centroids, float* scores_out, float* maxsim_out, void* hip_stream) {
+  if (!query_li || !pairs || !mask_bytes || (!scores_out && !maxsim_out)) return RR_ERR_BAD_ARG;
+  if (nbits ? (!codes || !residuals || !centroids_f16 || !bucket_weights) : !rows_f16) return RR_ERR_BAD_ARG;
+  if (D <= 0 || D % 16 || (nbits && !rr_plaid_shape_ok(nbits, D))) return RR_ERR_UNSUPPORTED;
+  if (Lq <= 0 || n_pairs <= 0 || padded_context_len <= 0 || (nbits && n_centroids <= 0)) return RR_ERR_BAD_SHAPE;
+  const hipError_t e = nbits ? rr_launch_bank_li_scores_plaid((const rr_bank_pair*)pairs, nullptr, n_pairs, Lq, padded_context_len, D, query_li, nbits, codes, residuals, centroids_f16, bucket_weights, n_centroids, mask_bytes, scores_out, maxsim_out, (hipStream_t)hip_stream)
+                             : rr_launch_bank_li_scores((const rr_bank_pair*)pairs, nullptr, n_pairs, Lq, padded_context_len, D, query_li, rows_f16, mask_bytes, scores_out, maxsim_out, (hipStream_t)hip_stream);
+  return e == hipSuccess ? RR_OK : RR_ERR_HIP;
 }
 int rr_li_scores(rr_handle h, const float* query_li, const float* context_li, const float* context_mask, int Bq, int K, int Lq, int Lc, int pair_begin, int pair_end, float* scores_out, float* maxsim_out, void* hip_stream) {
   return guarded(h, [&]() -> int { return li_scores_call(h, query_li, context_li, context_mask, Bq, K, Lq, Lc, pair_begin, pair_end, scores_out, maxsim_out, hip_stream); });

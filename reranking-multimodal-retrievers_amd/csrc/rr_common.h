@@ -460,6 +460,15 @@ hipError_t rr_launch_bank_gather_plaid(const rr_bank_pair* pairs, int n, int Lq,
                                        int dt, float* qmask_out, float* cmask_out, float* q32_out, float* c32_out, hipStream_t st);
 hipError_t rr_launch_plaid_decode(const uint16_t* centroids, int C, const float* weights, int nbits, int D, const int32_t* codes,
                                   const uint8_t* resid, long long first_row, long long n_rows, uint16_t* out, hipStream_t st);
+int rr_set_li_lds_kb(int kb);      // rr_set_tuning("li_lds_kb"): 16 .. 150, -1 outside (li_scores.hip)
+// the score matrix [n][Lc][Lq] and MaxSim [n] of a pair list with the context rows read from a bank, fp16 or compressed: the
+// kernel of rr_launch_li_scores over another operand source, bit for bit its result on the same rows (li_scores.hip); slot [n] on
+// the device or null: the output row of workgroup p
+hipError_t rr_launch_bank_li_scores(const rr_bank_pair* pairs, const int32_t* slot, int n, int Lq, int Lc, int D, const float* query_li, const uint16_t* rows,
+                                    const uint8_t* mask_bytes, float* scores, float* maxsim, hipStream_t st);
+hipError_t rr_launch_bank_li_scores_plaid(const rr_bank_pair* pairs, const int32_t* slot, int n, int Lq, int Lc, int D, const float* query_li, int nbits,
+                                          const int32_t* codes, const uint8_t* resid, const uint16_t* centroids, const float* weights,
+                                          int C, const uint8_t* mask_bytes, float* scores, float* maxsim, hipStream_t st);
 bool rr_plaid_shape_ok(int nbits, int D);
 bool rr_plaid_decode_rows_host(const uint16_t* centroids, int C, const float* weights, int nbits, int D, const int32_t* codes,
                                const uint8_t* resid, long long n_rows, uint16_t* out);

@@ -803,6 +803,38 @@ class RerankEngine:
         out.update(extra)
         return out
 
+    def bank_li_scores(self, bank, query_li: torch.Tensor, passage_ids, pair_query=None, K: Optional[int] = None,
+                       list_sizes: Optional[Sequence[int]] = None, want_scores: bool = False, want_maxsim: bool = True,
+                       padded_len: Optional[int] = None) -> dict:
+        """`li_scores` with the context side named by passage id and read from `bank`, fp16 or compressed (rr_bank_li_scores;
+        colbert_score, flmr_utils.py:22-48): `maxsim` [n_pairs] and, with `want_scores`, `scores` [n_pairs, padded_len, Lq]
+        (-9999 on masked rows and beyond a passage's length), in exact float32, pair order.  `query_li` [n_queries, Lq, D];
+        the query of pair i is `pair_query[i]`, or i // K, or given by `list_sizes` (pairs of query 0 first, then query 1, ...),
+        as forward_interaction_bank lays pairs out; with none of the three and one query, every pair is that query's.
+        `padded_len`: default the longest passage of the call.  NORMAL and MORES engines, weights loaded or not.  Bit for bit
+        li_scores(K = 1) on float32(bank rows) and the bank's masks.  An id the bank does not hold raises KeyError naming it."""
+        import numpy as np
+        from .passage_bank import plan_bank_scores
+        if not (want_scores or want_maxsim):
+            raise ValueError("bank_li_scores: want_scores or want_maxsim")
+        D = self.arch["li_dim"]
+        assert query_li.dim() == 3 and query_li.shape[2] == D, f"query_li {tuple(query_li.shape)}: [n_queries, Lq, {D}]"
+        nq, Lq = int(query_li.shape[0]), int(query_li.shape[1])
+        if pair_query is None and K is None and list_sizes is None:
+            assert nq == 1, "bank_li_scores: pair_query, K or list_sizes says which query a pair belongs to"
+            K = len(passage_ids)
+        plan = plan_bank_scores(bank.table, passage_ids, nq, pair_query, K, list_sizes, padded_len)
+        N, Lc = int(plan["indices"].size), plan["padded_len"]
+        f32 = dict(device=self.device, dtype=torch.float32)
+        q = query_li.to(**f32).contiguous()
+        pp = np.ascontiguousarray(plan["pair_passage"], dtype=np.int32)
+        pq = np.ascontiguousarray(plan["pair_query"], dtype=np.int32)
+        out = dict(scores=torch.empty((N, Lc, Lq), **f32) if want_scores else None,
+                   maxsim=torch.empty(N, **f32) if want_maxsim else None)
+        L.check(self.lib.rr_bank_li_scores(self.h, bank.h, L.ptr(q), nq, Lq, pp.ctypes.data, pq.ctypes.data, N, Lc,
+                                           L.ptr(out["scores"]), L.ptr(out["maxsim"]), self._stream()), self.h, "rr_bank_li_scores")
+        return {k: v for k, v in out.items() if v is not None}
+
     def li_scores(self, query_li: torch.Tensor, context_li: torch.Tensor, context_mask: torch.Tensor, Bq: int, K: int,
                   pair_range: Optional[Sequence[int]] = None, want_scores: bool = True, want_maxsim: bool = True) -> dict:
         """The frozen retriever's score of every pair and the matrix behind it (rr_li_scores; colbert_score,
@@ -1194,7 +1226,7 @@ class InteractionRerankModel(_DropIn):
     runs on the retriever's scores computed from the call's own late-interaction tensors (RerankEngine.li_scores; what the
     executor passes as `retrieval_results.scores_raw`), `want_maxsim=True` adds them per pair as `maxsim`.
     `create_bank` / `forward_passages`: the candidates' embeddings in a device-resident bank (passage_bank.PassageBank), named by
-    passage id per call; `rerank_dataset_pipelined` runs the executor's loop from it."""
+    passage id per call; `retriever_scores`: the retriever's MaxSim / score matrix of such pairs from the bank; `rerank_dataset_pipelined` runs the executor's loop from it."""
 
     def __init__(self, config, state_dict: Optional[Dict[str, torch.Tensor]] = None, device=None):
         super().__init__()
@@ -1236,6 +1268,13 @@ class InteractionRerankModel(_DropIn):
         r = self.engine.forward_interaction_bank(self.bank, query_late_interaction, query_mask, passage_ids, Bq, K,
                                                  self._labels(labels, N), **common)
         return self._output(r, self._ranked_logits(r, Bq, K))
+
+    def retriever_scores(self, query_late_interaction, passage_ids, **kw) -> dict:
+        """The frozen retriever's score of (query, passage) pairs from `self.bank` (RerankEngine.bank_li_scores; colbert_score,
+        flmr_utils.py:22-48): {"maxsim"} and, with want_scores=True, {"scores"}.  NORMAL and MORES models."""
+        if self.bank is None:
+            raise RuntimeError("retriever_scores needs a bank: model.create_bank(capacity_rows, max_passages), then bank.add(...)")
+        return self.engine.bank_li_scores(self.bank, query_late_interaction, passage_ids, **kw)
 
     def forward(self, query_late_interaction, context_late_interaction, num_negative_examples, query_mask,
                 context_mask, preflmr_scores=None, fusion_multiplier=1, labels=None, candidates_per_query=None,

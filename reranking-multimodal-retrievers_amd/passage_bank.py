@@ -11,7 +11,10 @@ centroid code and D * nbits / 8 residual bytes per token; third_party/ColBERT/co
 and decodes them on the device inside the forward's gather, bit for bit the fp16 bank of the decoded rows (the decoded row:
 include/rerank_mi355.h, rr_bank_create_plaid).  `read_plaid_index` reads such an index from disk with torch.load and json alone.
 
-`BankTable`, `plan_bank_batch`, `PlaidCodec` and `read_plaid_index` are the host side: pure Python / numpy / torch on the CPU,
+`PassageBank.maxsim` / RerankEngine.bank_li_scores give the retriever's own score of (query, passage) pairs (MaxSim and the score
+matrix, rr_bank_li_scores) from either kind of bank, without a padded context tensor.
+
+`BankTable`, `plan_bank_batch`, `plan_bank_scores`, `PlaidCodec` and `read_plaid_index` are the host side: pure Python / numpy / torch on the CPU,
 usable and tested without a device.
 """
 from __future__ import annotations
@@ -98,6 +101,40 @@ def plan_bank_batch(table: BankTable, passage_ids: Sequence, K: Optional[int], l
     order, seg_n, seg_len = group_pairs_by_length(lens, int(padded_len), int(granule), 1, int(segment_cost_rows))
     return dict(indices=idx, lengths=lens, owner=owner, order=order, seg_n=seg_n, seg_len=seg_len,
                 pair_passage=idx[order].astype(np.int32), pair_query=owner[order].astype(np.int32))
+
+
+def plan_bank_scores(table: BankTable, passage_ids: Sequence, n_queries: int, pair_query=None, K: Optional[int] = None,
+                     list_sizes: Optional[Sequence[int]] = None, padded_len: Optional[int] = None) -> dict:
+    """Host side of one rr_bank_li_scores call.  `passage_ids`: the passages in pair order (any passage any number of times).
+    The query of every pair: `pair_query` explicitly (any order), or K pairs per query, or `list_sizes[q]` pairs for query q, as
+    plan_bank_batch lays pairs out; exactly one of the three.  `padded_len`: the context rows per pair of the score block,
+    default: the longest passage of the call.  Returns
+      indices, lengths         : bank index and length of every pair (int64)
+      pair_passage, pair_query : int32, pair order — what the C call takes
+      padded_len               : int.
+    The pairs are not reordered: the outputs come back in the caller's order.  An unknown id raises KeyError naming it."""
+    import numpy as np
+    idx, lens = table.lookup(passage_ids)
+    N = int(idx.size)
+    assert N >= 1, "no passages"
+    assert (pair_query is not None) + (K is not None) + (list_sizes is not None) == 1, "one of pair_query, K and list_sizes"
+    if pair_query is not None:
+        owner = np.asarray(pair_query, dtype=np.int64).reshape(-1)
+        assert owner.size == N, f"{owner.size} query indices for {N} passages"
+    elif list_sizes is not None:
+        sizes = np.asarray(list_sizes, dtype=np.int64).reshape(-1)
+        assert sizes.size > 0 and int(sizes.min()) >= 1 and int(sizes.sum()) == N, \
+            f"list_sizes {sizes.tolist()} do not partition {N} passages into non-empty lists"
+        owner = np.repeat(np.arange(sizes.size, dtype=np.int64), sizes)
+    else:
+        assert K >= 1 and N % K == 0, f"{N} passages are not lists of {K}"
+        owner = np.arange(N, dtype=np.int64) // K
+    assert int(owner.min()) >= 0 and int(owner.max()) < n_queries, \
+        f"the pairs name queries {int(owner.min())} .. {int(owner.max())}, query_li holds {n_queries}"
+    longest = int(lens.max())
+    Lc = longest if padded_len is None else int(padded_len)
+    assert longest <= Lc, f"a passage of {longest} rows exceeds the padded context length {Lc}"
+    return dict(indices=idx, lengths=lens, pair_passage=idx.astype(np.int32), pair_query=owner.astype(np.int32), padded_len=Lc)
 
 
 PLAID_NBITS = (1, 2, 4, 8)
@@ -391,6 +428,10 @@ class PassageBank:
         self._check(got, "rr_bank_read")
         assert got == n, f"the bank holds {got} rows for passage {passage_id!r}, the table {n}"
         return rows, mask
+
+    def maxsim(self, engine, query_li, passage_ids, **kw):
+        """The retriever's MaxSim [n_pairs] of the pairs (query, passage id) from this bank: engine.bank_li_scores(...)["maxsim"]."""
+        return engine.bank_li_scores(self, query_li, passage_ids, **kw)["maxsim"]
 
     def clear(self) -> None:
         """Forget every passage (rr_bank_clear; the capacity stays).  Forwards that read the bank must have completed."""

@@ -532,7 +532,8 @@ int rr_bank_add(rr_bank_handle b, const void* context_li, int dtype, const float
  * with "nbits": 8), decoded on the device inside the gather of rr_forward_interaction_bank.  Replaces the reference's own native
  * kernel on the retriever-to-reranker hand-over (third_party/ColBERT/colbert/indexing/codecs/decompress_residuals.cu) and the
  * F.normalize behind it (codecs/residual.py:242-278).  Bytes per token at li_dim 128: 257 as fp16, 133 / 69 / 37 / 21 at nbits 8 /
- * 4 / 2 / 1.  Nothing here compresses, searches or computes embeddings.
+ * 4 / 2 / 1.  Nothing here compresses or computes embeddings; rr_bank_search searches, exhaustively (no PLAID candidate
+ * generation or centroid pruning).
  *
  * THE DECODED ROW, for a row with code c, residual bytes r[0 .. D * nbits / 8), centroids [C, D] fp16 (the index stores them with
  * .half(), residual.py:161) and float32 bucket weights w[2^nbits]:
@@ -633,6 +634,41 @@ int rr_forward_interaction_bank(rr_handle h, rr_bank_handle b, const float* quer
 int rr_bank_li_scores(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, const int32_t* pair_passage,
                       const int32_t* pair_query, int n_pairs, int padded_context_len, float* scores_out, float* maxsim_out,
                       void* hip_stream);
+
+/* rr_bank_search: exact top-k MaxSim search over a range of a bank: the candidates a reranker starts from, taken from the bank
+ * itself.  The reference reads them from a file a separate PLAID search wrote (third_party/ColBERT/colbert/search/
+ * index_storage.py:86-98: candidate generation, two centroid-score pruning passes, exact MaxSim on the ndocs / 4 survivors, sort);
+ * here EVERY passage of the range is scored with what that last stage computes (colbert_score, flmr_utils.py:22-48) and the k best
+ * per query are returned, so no recall is lost to pruning.  Handles, bank formats and li_dim as rr_bank_li_scores takes them.
+ *   query_li [n_queries, Lq, li_dim] : DEVICE float32, 16-byte aligned; no query mask.  n_queries <= 65535.
+ *   first_passage, n_passages : the bank indices first_passage .. first_passage + n_passages - 1 are searched; n_passages = -1:
+ *       through the last passage.  (A rank can search its slice of a bank; merging the results of ranks is the caller's.)
+ *   indices_out : DEVICE int32 [n_queries, k], bank indices.   scores_out : DEVICE float32 [n_queries, k], or NULL.
+ *   k : 1 <= k <= min(n_passages, 1024).  A selection pass sorts slices of 4096 candidates in LDS (as rr_head's rank does) and
+ *       keeps k of each: with k <= 1024 every pass shrinks the list at least fourfold, so the passes end after
+ *       log4(n_passages / 4096) + 1 launches and the survivor buffers stay a quarter of the scores.  A larger k: RR_ERR_UNSUPPORTED.
+ * SCORE of a passage: bit for bit the maxsim_out of rr_bank_li_scores for that (query, passage) with padded_context_len = the
+ * passage's own length.  A larger padded_context_len adds rows of -9999 to every column maximum, which changes the value only
+ * if every unmasked score of a column is below -9999: impossible for unit rows (|score| <= 1), so for those the score is the
+ * maxsim_out at ANY padded_context_len.  A fully masked passage scores the sum of Lq times -9999.  A compressed bank gives the
+ * bits of the fp16 bank of its decoded rows.
+ * ORDER per query: that of torch.sort(scores, descending=True, stable=True) truncated to k: higher score first, equal scores
+ * (+0 == -0) by ascending bank index, NaN ahead of every number (NaNs among themselves by index); the same from run to run.
+ * Two kernels, booked in the profile's `tail` class: one scoring launch over (passage chunk, query) with 2 * sum(len) * Lq *
+ * li_dim FLOPs per query (a workgroup stages its query block once and walks a chunk of passages, a wave per passage), then the
+ * selection passes (no atomics).  One float per (query, passage) and the survivor indices live in a grow-only block of the
+ * handle: 4 * n_queries * n_passages * (1 + k / 2048) bytes.  The bank keeps a device copy of its passage table for this call (16 bytes per passage), brought up to
+ * date by the first search after an rr_bank_add / rr_bank_add_plaid / rr_bank_clear: THAT search uploads the new entries and
+ * synchronises hip_stream once.
+ * Checked on the host BEFORE anything is enqueued, a refused call writes nothing: null handle, bank, query_li or indices_out,
+ * misaligned pointers, bank and handle on different devices, a full-context handle (RR_ERR_BAD_ARG); a different li_dim,
+ * non-positive sizes, a range that is empty or not inside the bank, k < 1 or k > n_passages (RR_ERR_BAD_SHAPE).
+ * LIMITS: k <= 1024; not capturable into a graph (RR_ERR_BAD_ARG under stream capture: the call may upload the table and grow
+ * its block); one device (no merge across ranks: search ranges and merge the k-lists yourself); no candidate filter (every
+ * passage of the range competes; restrict by range only).  (Python: RerankEngine.bank_search, PassageBank.search,
+ * InteractionRerankModel.retrieve / retrieve_and_rerank.) */
+int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage,
+                   int32_t n_passages, int k, int32_t* indices_out, float* scores_out, void* hip_stream);
 
 /* rr_head_joint: rr_head with the head RerankModel.forward runs (rr_forward_joint): `loss_fn(logits, logits)`
  * (rerank_model.py:328) — the labels are the logits themselves (2H_BCE: the two heads as class-probability targets).  The

@@ -276,6 +276,21 @@ int rr_op_bank_li_scores(const float* query_li, int Lq, int D, const void* pairs
                          const uint16_t* rows_f16, const uint8_t* mask_bytes, int nbits, const int32_t* codes, const uint8_t* residuals,
                          const uint16_t* centroids_f16, const float* bucket_weights, int32_t n_centroids, float* scores_out,
                          float* maxsim_out, void* hip_stream);
+/* The kernels of rr_bank_search (rerank_mi355.h) over raw DEVICE pointers, at any D that is a multiple of 16 (D = 16 is reachable
+ * here only).  Both allocate their scratch per call and synchronise hip_stream before they free it.
+ * rr_op_bank_search: table = DEVICE array of {int64 first_row; int32 len; int32 unused}, 16-byte aligned, one entry per passage
+ * (NOT checked against the buffers: the caller answers for them); the passages first_passage .. first_passage + n_passages - 1 of
+ * it are searched; rows / mask / nbits / codes / residuals / tables as rr_op_bank_li_scores takes them; indices_out int32
+ * [n_queries, k] (table indices), scores_out float32 [n_queries, k] or NULL; 1 <= k <= min(n_passages, 1024).
+ * rr_op_topk_select: the selection alone: scores float32 [n_lists, n] -> the first k of every list in the order of
+ * torch.sort(descending=True, stable=True) (NaN first, ties by ascending index): indices_out int32 [n_lists, k], scores_out
+ * float32 [n_lists, k] or NULL; n_lists <= 65535.
+ * rr_set_tuning("search_chunk") (16; 4 .. 128): the passages one workgroup of the scoring kernel walks. */
+int rr_op_bank_search(const float* query_li, int n_queries, int Lq, int D, const void* table, int32_t first_passage,
+                      int32_t n_passages, int k, const uint16_t* rows_f16, const uint8_t* mask_bytes, int nbits, const int32_t* codes,
+                      const uint8_t* residuals, const uint16_t* centroids_f16, const float* bucket_weights, int32_t n_centroids,
+                      int32_t* indices_out, float* scores_out, void* hip_stream);
+int rr_op_topk_select(const float* scores, int n_lists, int n, int k, int32_t* indices_out, float* scores_out, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -105,6 +105,10 @@ _SIGS = {
     "rr_forward_interaction_bank": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_float,
                                               _P, _P, _P, _P]),
     "rr_bank_li_scores": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "rr_bank_search": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int, _P, _P, _P]),
+    "rr_op_bank_search": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int32, C.c_int32, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P,
+                                    C.c_int32, _P, _P, _P]),
+    "rr_op_topk_select": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "rr_head": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "rr_head_joint": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "rr_head_lists": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),

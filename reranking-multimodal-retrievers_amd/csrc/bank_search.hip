@@ -1,0 +1,300 @@
+// Exact top-k MaxSim search over a range of a passage bank (rr_bank_search, include/rerank_mi355.h): the score PLAID's last stage
+// computes (colbert_score, flmr_utils.py:22-48) for EVERY passage of the range, then the k best per query.  Two kernels.
+//
+// (a) bank_search_scores_kernel: one float per (query, passage), out[q][p] = the maxsim of li_scores_kernel (li_scores.hip) for
+//     that pair with padded_context_len = the passage's own length, bit for bit: the same operand sources (li_sources.h), the
+//     same v_mfma_f32_16x16x4_f32 chain per entry (D in ascending steps of 16, e = 0..3 inside a step), nan_max column maxima,
+//     and the columns summed 0, 1, ... Lq - 1 in sequence from 0.0f.  What differs is who does it.  A workgroup (4 waves) belongs
+//     to one query and one contiguous chunk of passages: it stages the query's column block in LDS once per chunk ([16 JT][D + 4]
+//     floats, 17 KB at Lq 32, D 128) where li_scores_kernel stages it once per pair, and a WAVE takes whole passages (passage
+//     wave, wave + 4, ... of the chunk), tile after tile.  So a column maximum never leaves the wave: the four lane groups g meet
+//     by two shuffles, the sixteen columns of a tile are read back lane by lane (constant-lane shuffles) into one sequential sum
+//     that every lane of the wave carries, and there is no barrier inside the passage loop.  A maximum is the same whichever order
+//     its rows arrive in (a NaN sticks; +0 / -0 cannot change a sum that starts at +0), so the wave-per-passage order of the rows
+//     gives li_scores_kernel's bits.  For Lq above one column block the workgroup walks its chunk once per block and the running
+//     sum of a passage waits in LDS (psum) between blocks: the sum stays ONE chain over all Lq columns.
+//     Chunking: chunks are short (16 passages, 4 per wave; rr_set_tuning("search_chunk")) and consecutive workgroups are the
+//     queries of one chunk (blockIdx = chunk * n_queries + query), so that a chunk's rows are read from HBM once and by the other
+//     queries from L2 / MALL.  The grid is static, so what passages of unequal length cost is the last round of workgroups: 100 000
+//     passages of 64 .. 180 rows are 6250 chunks per query on about 1536 resident workgroups (80 VGPRs at JT 2: 6 waves per SIMD),
+//     four rounds, and a workgroup that drew long passages delays the end by its own chunk only.  Measured on that bank at Lq 32
+//     (tools/bench_bank_search.py, profiles/bank_search_bench.json.log "search_ms" / "search_ms_at_chunk", ms per call): one
+//     query, fp16: 8 / 16 / 32 / 64 / 128 passages per chunk took 1.72 / 1.90 / 1.84 / 2.15 / 2.51, compressed 3.02 / 3.14 / 3.17 /
+//     3.42 / 3.81; 16 queries, fp16: 19.30 / 19.12 / 18.92 / 18.96 / 18.97, compressed 38.9 / 37.9 / 37.1 / 36.8 / 36.7.  Long
+//     chunks lose up to a third at one query (few rounds, an uneven last one) and gain 3 % at sixteen; 8, 16 and 32 lie within
+//     what two boxes differ by (a first run gave 1.76 / 1.74 / 2.05 at one query), and below 16 the 17 KB query block restaged
+//     per chunk shows at sixteen queries.  16 it is.  On the device alone the scoring launch takes 1.17 x the time of
+//     li_scores_kernel over the same pairs at one query on the fp16 bank (that launch gets its pairs longest first from the host
+//     and fills every slot with one pair), and 0.95 / 0.88 / 0.82 x compressed, at 16 queries fp16, and both: the call wins by
+//     what it no longer stages and sorts on the host.
+// (b) topk_select_kernel: each workgroup sorts a slice of at most 4096 (score, index) in LDS by ONE total order and keeps its
+//     first k (k <= 1024, so a pass is a strict reduction); passes repeat over the survivors until one slice is left.  The order
+//     is that of torch.sort(descending=True, stable=True): NaN ahead of every number, higher score first, equal scores (+0 == -0)
+//     by ascending index.  Score and index are packed into one 64-bit key (an order-preserving image of the float above, the
+//     complement of the index below), keys are distinct, so the bitonic network has one possible result: no atomics, nothing
+//     depends on scheduling.  Survivors travel as indices; a pass reads their scores again from the score row.
+#include <algorithm>
+#include <atomic>
+
+#include "li_sources.h"
+#include "rr_common.h"
+
+namespace {
+
+constexpr int BS_JT_MAX = 8;             // query tiles (16 columns) per column block
+constexpr int BS_CHUNK_MAX = 128;        // passages of a workgroup's chunk (psum)
+constexpr int SEL_SLICE = 4096;          // (score, index) entries one workgroup sorts
+constexpr int SEL_THREADS = 512;
+
+template <int JT, class SRC>
+__global__ __launch_bounds__(256) void bank_search_scores_kernel(const float* __restrict__ query_li, const SRC src,
+                                                                 const rr_bank_slot* __restrict__ table, int n, int nq, int chunk,
+                                                                 int Lq, int D, float* __restrict__ out) {
+  constexpr int JB = 16 * JT;            // columns per block
+  extern __shared__ __attribute__((aligned(16))) float qblk[];      // [JB][D + 4]: the block's query rows; TILE: the tiles behind
+  __shared__ float psum[BS_CHUNK_MAX];   // the running column sum of the chunk's passages between column blocks
+  const int ldq = D + 4;                 // as li_scores_kernel
+  const int q = blockIdx.x % nq, p0 = (blockIdx.x / nq) * chunk, pn = min(chunk, n - p0);
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int li = lane & 15, g = lane >> 4;
+  const float* Q = query_li + (size_t)q * Lq * D;
+  uint16_t* tile = SRC::TILE ? (uint16_t*)(qblk + JB * ldq) + wave * 16 * (D + LI_TILE_PAD) : nullptr;
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+
+  for (int j0 = 0; j0 < Lq; j0 += JB) {
+    __syncthreads();                     // every wave is done with the last block's query rows (and psum is written)
+    for (int i = threadIdx.x; i < JB * (D / 4); i += 256) {
+      const int row = i / (D / 4), col = (i - row * (D / 4)) * 4;
+      *(f32x4*)(qblk + row * ldq + col) = j0 + row < Lq ? *(const f32x4*)(Q + (size_t)(j0 + row) * D + col) : zero4;
+    }
+    __syncthreads();
+    const bool last = j0 + JB >= Lq;
+    for (int i = wave; i < pn; i += 4) {                      // a passage belongs to one wave
+      const rr_bank_slot sl = table[p0 + i];                  // the same entry in every lane: kept in scalar registers
+      const long long first_row = (long long)(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(sl.first_row >> 32)) << 32) |
+                                              (uint32_t)__builtin_amdgcn_readfirstlane((int)sl.first_row));
+      const typename SRC::pair_t pr = src.of(first_row, __builtin_amdgcn_readfirstlane(sl.len), q, 0, D);
+      const int len = pr.len, c_tiles = (len + 15) / 16;
+      float cmax[JT];
+#pragma unroll
+      for (int t = 0; t < JT; ++t) cmax[t] = -INFINITY;
+      for (int ct = 0; ct < c_tiles; ++ct) {
+        const int c = ct * 16 + li;                           // the context row this lane feeds to the matrix core
+        const bool c_ok = c < len;
+        f32x4 acc[JT];
+#pragma unroll
+        for (int t = 0; t < JT; ++t) acc[t] = zero4;
+        if constexpr (SRC::TILE) {
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // the reads of the last tile stay in front of these writes
+          src.stage(pr, ct, D, lane, tile);
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // lanes read what other lanes of the wave wrote
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+        const typename SRC::cursor crow = src.row(pr, c_ok ? c : 0, g, D, li, tile);
+        const float* qrow = qblk + li * ldq + 4 * g;
+        f32x4 a = c_ok ? SRC::at(crow, 0) : zero4;
+        for (int d = 0; d < D; d += 16) {
+          const f32x4 a_n = (c_ok && d + 16 < D) ? SRC::at(crow, d + 16) : zero4;      // requested a step ahead
+          f32x4 b[JT];
+#pragma unroll
+          for (int t = 0; t < JT; ++t) b[t] = *(const f32x4*)(qrow + t * 16 * ldq + d);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+#pragma unroll
+            for (int t = 0; t < JT; ++t)
+              acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b[t][e], acc[t], 0, 0, 0);
+          }
+          a = a_n;
+        }
+        // accumulator element r of this lane: row ct * 16 + 4 g + r, column j0 + t * 16 + li
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = ct * 16 + 4 * g + r;
+          if (row >= len) continue;
+          const bool keep = src.keep(pr, row);
+#pragma unroll
+          for (int t = 0; t < JT; ++t)
+            if (j0 + t * 16 + li < Lq) cmax[t] = nan_max(cmax[t], keep ? acc[t][r] : LI_MASKED);
+        }
+      }
+      float sum = j0 ? psum[i] : 0.0f;                        // every lane of the wave carries the same sum
+#pragma unroll
+      for (int t = 0; t < JT; ++t) {
+        float v = cmax[t];
+        v = nan_max(v, __shfl_xor(v, 16, 64));
+        v = nan_max(v, __shfl_xor(v, 32, 64));
+#pragma unroll
+        for (int l = 0; l < 16; ++l) {
+          const float x = __shfl(v, l, 64);
+          if (j0 + t * 16 + l < Lq) sum += x;                 // columns 0, 1, ... Lq - 1, one after the other
+        }
+      }
+      if (lane == 0) {
+        if (last) out[(size_t)q * n + p0 + i] = sum;
+        else psum[i] = sum;
+      }
+    }
+  }
+}
+
+// rr_set_tuning("search_chunk"): passages per workgroup of the scoring kernel
+std::atomic<int> g_search_chunk{16};
+
+template <int JT, class SRC>
+hipError_t search_launch_jt(const float* query_li, const SRC& src, const rr_bank_slot* table, int n, int nq, int Lq, int D, size_t lds,
+                            float* out, hipStream_t st) {
+  static std::atomic<unsigned long long> attr_set{0};   // per device ordinal (see gemm_bf16.hip ensure_lds_attr)
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (dev < 0 || dev >= 64 || !((attr_set.load(std::memory_order_acquire) >> dev) & 1ull)) {
+    e = hipFuncSetAttribute((const void*)bank_search_scores_kernel<JT, SRC>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    if (e != hipSuccess) return e;
+    if (dev >= 0 && dev < 64) attr_set.fetch_or(1ull << dev, std::memory_order_release);
+  }
+  const int chunk = g_search_chunk.load(std::memory_order_relaxed);
+  const long long blocks = ((long long)n + chunk - 1) / chunk * nq;
+  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((bank_search_scores_kernel<JT, SRC>), dim3((unsigned)blocks), dim3(256), lds, st, query_li, src, table, n, nq,
+                     chunk, Lq, D, out);
+  return hipGetLastError();
+}
+
+template <class SRC>
+hipError_t search_launch(const float* query_li, const SRC& src, const rr_bank_slot* table, int n, int nq, int Lq, int D,
+                         size_t tile_bytes, float* out, hipStream_t st) {
+  // the narrowest column block that takes Lq in one pass, 128 columns beyond; halved while the query rows and the decoded tiles
+  // would leave room for fewer than two workgroups per CU (any width gives the same bits: the sum is carried between blocks)
+  int jt = Lq <= 16 ? 1 : Lq <= 32 ? 2 : Lq <= 64 ? 4 : BS_JT_MAX;
+  auto lds_bytes = [&](int t) { return (size_t)16 * t * (D + 4) * sizeof(float) + tile_bytes; };
+  while (jt > 1 && lds_bytes(jt) > (size_t)72 * 1024) jt /= 2;
+  const size_t lds = lds_bytes(jt);
+  if (lds > 150 * 1024) return hipErrorInvalidValue;
+  if (jt == 1) return search_launch_jt<1>(query_li, src, table, n, nq, Lq, D, lds, out, st);
+  if (jt == 2) return search_launch_jt<2>(query_li, src, table, n, nq, Lq, D, lds, out, st);
+  if (jt == 4) return search_launch_jt<4>(query_li, src, table, n, nq, Lq, D, lds, out, st);
+  return search_launch_jt<BS_JT_MAX>(query_li, src, table, n, nq, Lq, D, lds, out, st);
+}
+
+// the order-preserving image of a score: NaN above +inf, -0 as +0, then the usual sign flip; never 0
+__device__ __forceinline__ uint32_t score_key(float s) {
+  if (s != s) return 0xffffffffu;
+  uint32_t u = __float_as_uint(s);
+  if (u == 0x80000000u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// One pass.  List `blockIdx.y`, slice `blockIdx.x` of its n_in entries: entry i is index idx_in[list][i] of the score row (idx_in
+// null: i itself).  The slice's first min(k, entries) in rank order go to idx_out[list * out_ld + slice * k ...]; the last pass
+// (one slice) writes `add` + index and, if asked, the scores.
+__global__ __launch_bounds__(SEL_THREADS) void topk_select_kernel(const float* __restrict__ scores, long long n, const int32_t* __restrict__ idx_in,
+                                                                  long long in_ld, int n_in, int k, int32_t* __restrict__ idx_out,
+                                                                  long long out_ld, int add, float* __restrict__ scores_out) {
+  __shared__ unsigned long long key[SEL_SLICE];
+  const int list = blockIdx.y, base = blockIdx.x * SEL_SLICE, cnt = min(SEL_SLICE, n_in - base), tid = threadIdx.x;
+  const float* row = scores + (size_t)list * n;
+  int n2 = 1;
+  while (n2 < cnt) n2 <<= 1;
+  for (int i = tid; i < n2; i += SEL_THREADS) {
+    unsigned long long kv = 0ull;                             // padding ranks behind every entry
+    if (i < cnt) {
+      const int idx = idx_in ? idx_in[(size_t)list * in_ld + base + i] : base + i;
+      kv = ((unsigned long long)score_key(row[idx]) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)idx);
+    }
+    key[i] = kv;
+  }
+  __syncthreads();
+  for (int kk = 2; kk <= n2; kk <<= 1) {
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < n2; i += SEL_THREADS) {
+        const int l = i ^ j;
+        if (l > i) {
+          const bool up = (i & kk) == 0;                      // a run in rank order (larger key first)
+          const unsigned long long a = key[i], b = key[l];
+          if (up ? a < b : a > b) { key[i] = b; key[l] = a; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  const int keep = min(k, cnt);
+  const bool final_pass = gridDim.x == 1;
+  for (int i = tid; i < keep; i += SEL_THREADS) {
+    const int idx = (int)(0xffffffffu - (uint32_t)key[i]);
+    if (final_pass) {
+      idx_out[(size_t)list * out_ld + i] = idx + add;
+      if (scores_out) scores_out[(size_t)list * out_ld + i] = row[idx];
+    } else {
+      idx_out[(size_t)list * out_ld + (size_t)blockIdx.x * k + i] = idx;
+    }
+  }
+}
+
+}  // namespace
+
+int rr_set_search_chunk(int passages) {
+  if (passages < 4 || passages > BS_CHUNK_MAX) return -1;
+  g_search_chunk.store(passages, std::memory_order_relaxed);
+  return 0;
+}
+
+// out [nq][n]: the MaxSim of every query against the passages table[0 .. n) (an fp16 bank)
+hipError_t rr_launch_bank_search_scores(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li, const uint16_t* rows,
+                                        const uint8_t* mask_bytes, float* out, hipStream_t st) {
+  if (n <= 0 || nq <= 0 || Lq <= 0 || D <= 0 || D % 16 || !table || !query_li || !rows || !mask_bytes || !out) return hipErrorInvalidValue;
+  if ((((uintptr_t)query_li) & 15) || (((uintptr_t)rows) & 7) || (((uintptr_t)table) & 15)) return hipErrorInvalidValue;
+  return search_launch(query_li, li_src_f16{nullptr, nullptr, rows, mask_bytes}, table, n, nq, Lq, D, 0, out, st);
+}
+
+// ... and a compressed bank (tables as rr_launch_bank_gather_plaid takes them)
+hipError_t rr_launch_bank_search_scores_plaid(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li, int nbits,
+                                              const int32_t* codes, const uint8_t* resid, const uint16_t* centroids, const float* weights,
+                                              int C, const uint8_t* mask_bytes, float* out, hipStream_t st) {
+  if (n <= 0 || nq <= 0 || Lq <= 0 || D % 16 || !rr_plaid_shape_ok(nbits, D) || C <= 0 || !table || !query_li || !codes || !resid ||
+      !centroids || !weights || !mask_bytes || !out)
+    return hipErrorInvalidValue;
+  if (((((uintptr_t)query_li) | ((uintptr_t)centroids) | ((uintptr_t)table)) & 15) || (((uintptr_t)resid) & 7) || (((uintptr_t)codes) & 3))
+    return hipErrorInvalidValue;
+  const size_t tile_bytes = (size_t)4 * 16 * (D + LI_TILE_PAD) * sizeof(uint16_t);
+#define BS_PLAID(NB) \
+  return search_launch(query_li, li_src_plaid<NB>{nullptr, nullptr, codes, resid, centroids, weights, C, mask_bytes}, table, n, nq, Lq, D, tile_bytes, out, st)
+  switch (nbits) {
+    case 1: BS_PLAID(1);
+    case 2: BS_PLAID(2);
+    case 4: BS_PLAID(4);
+    default: BS_PLAID(8);
+  }
+#undef BS_PLAID
+}
+
+// int32 entries of EACH of the two survivor buffers rr_launch_topk_select needs (0: one slice, none)
+size_t rr_topk_select_scratch(int n_lists, int n, int k) {
+  if (n <= SEL_SLICE) return 0;
+  return (size_t)n_lists * (size_t)((n + SEL_SLICE - 1) / SEL_SLICE) * (size_t)k;
+}
+
+// the first k of every list scores [n_lists][n] in rank order: indices_out [n_lists][k] (+ add), scores_out [n_lists][k] or null.
+// 1 <= k <= min(n, 1024); tmp_a / tmp_b: rr_topk_select_scratch entries each
+hipError_t rr_launch_topk_select(const float* scores, int n_lists, int n, int k, int add, int32_t* tmp_a, int32_t* tmp_b,
+                                 int32_t* indices_out, float* scores_out, hipStream_t st) {
+  if (!scores || !indices_out || n_lists <= 0 || n_lists > 65535 || n <= 0 || k < 1 || k > n || k > 1024) return hipErrorInvalidValue;
+  if (n > SEL_SLICE && (!tmp_a || !tmp_b)) return hipErrorInvalidValue;
+  const long long ld = (long long)((n + SEL_SLICE - 1) / SEL_SLICE) * k;      // row pitch of both survivor buffers
+  const int32_t* in = nullptr;
+  int32_t* bufs[2] = {tmp_a, tmp_b};
+  int n_in = n, pass = 0;
+  for (;;) {
+    const int slices = (n_in + SEL_SLICE - 1) / SEL_SLICE;
+    const bool final_pass = slices == 1;
+    int32_t* o = final_pass ? indices_out : bufs[pass & 1];
+    hipLaunchKernelGGL(topk_select_kernel, dim3((unsigned)slices, (unsigned)n_lists), dim3(SEL_THREADS), 0, st, scores, (long long)n, in, ld,
+                       n_in, k, o, final_pass ? (long long)k : ld, add, final_pass ? scores_out : nullptr);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || final_pass) return e;
+    // every slice but the last is full and leaves k; the last leaves what it holds, at most k: the survivors are contiguous
+    n_in = (slices - 1) * k + std::min(k, n_in - (slices - 1) * SEL_SLICE);
+    in = o;
+    ++pass;
+  }
+}

@@ -225,6 +225,9 @@ struct rr_model {
   // fusion_from_li the float32 copies of its query / context rows that li_scores reads
   char* bank_blk = nullptr;
   size_t bank_blk_cap = 0;
+  // rr_bank_search (grow-only): the score of every (query, passage) of the call, then the two survivor buffers of the selection
+  char* search_blk = nullptr;
+  size_t search_blk_cap = 0;
   // CLIP ViT (optional)
   std::vector<LayerW> vit_layers;
   bf16_t* vit_wpatch = nullptr;                             // [Vh, Kp] patch convolution, zero-padded to Kp
@@ -292,6 +295,10 @@ struct rr_bank {
   size_t resid_row_bytes() const { return (size_t)D / 8 * (size_t)nbits; }
   std::vector<int64_t> first;
   std::vector<int32_t> len;
+  // the device copy of (first, len) that rr_bank_search's kernel walks: 16 bytes per passage, allocated and brought up to date
+  // by the first search after an add (table_n passages of it are current); nothing else reads it
+  rr_bank_slot* table = nullptr;
+  size_t table_cap = 0, table_n = 0;
   std::string err;
   rr_model::AsmSlot slot[2];
   int next = 0;
@@ -1169,6 +1176,16 @@ int ensure_li_scores(rr_model* m, size_t bytes, hipStream_t st) {
   return RR_OK;
 }
 
+// grow-only block of rr_bank_search (rr_model::search_blk)
+int ensure_search_blk(rr_model* m, size_t bytes, hipStream_t st) {
+  if (bytes <= m->search_blk_cap) return RR_OK;
+  RR_TRY(capture_guard(m, st, "the bank search's block"));
+  if (m->search_blk) { RR_TRY(release_block(m, m->search_blk, st)); m->search_blk = nullptr; m->search_blk_cap = 0; }
+  RR_HIP(m, hipMalloc((void**)&m->search_blk, bytes));
+  m->search_blk_cap = bytes;
+  return RR_OK;
+}
+
 // grow-only block of rr_forward_interaction_bank (rr_model::bank_blk)
 int ensure_bank_blk(rr_model* m, size_t bytes, hipStream_t st) {
   if (bytes <= m->bank_blk_cap) return RR_OK;
@@ -1524,6 +1541,7 @@ static int rr_destroy_impl(rr_handle h) {
   if (h->adj) (void)hipFree(h->adj);
   if (h->li_sc) (void)hipFree(h->li_sc);
   if (h->bank_blk) (void)hipFree(h->bank_blk);
+  if (h->search_blk) (void)hipFree(h->search_blk);
   for (auto& e : h->ev_pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   for (auto& a : h->asm_slot) {
     if (a.host) (void)hipHostFree(a.host);
@@ -2041,6 +2059,7 @@ static void bank_free(rr_bank* b) {
   if (b->resid) (void)hipFree(b->resid);
   if (b->centroids) (void)hipFree(b->centroids);
   if (b->weights) (void)hipFree(b->weights);
+  if (b->table) (void)hipFree(b->table);
   for (auto& a : b->slot) {
     if (a.host) (void)hipHostFree(a.host);
     if (a.dev) (void)hipFree(a.dev);
@@ -2794,6 +2813,122 @@ static int bank_li_scores_call(rr_handle h, rr_bank* b, const float* query_li, i
   return asm_done(m, st);
 }
 
+// rr_bank_search (include/rerank_mi355.h): every check on the host first; then the bank's device table is brought up to date
+// (only after an add), one scoring launch over the range and the selection passes
+static int bank_search_call(rr_handle h, rr_bank* b, const float* query_li, int n_queries, int Lq, int32_t first_passage,
+                            int32_t n_passages, int k, int32_t* indices_out, float* scores_out, void* hip_stream) {
+  const char* what = "rr_bank_search";
+  if (!h) return RR_ERR_BAD_ARG;
+  rr_model* m = h;
+  const rr_config& c = m->cfg;
+  if (!b || !query_li || !indices_out) return fail(m, RR_ERR_BAD_ARG, "%s: null argument", what);
+  if (c.model_kind == RR_MODEL_FULL_CONTEXT) return fail(m, RR_ERR_BAD_ARG, "%s on a full-context model", what);
+  if (b->device != c.device) return fail(m, RR_ERR_BAD_ARG, "%s: the bank lives on device %d, the handle on %d", what, b->device, c.device);
+  if (b->D != c.li_dim) return fail(m, RR_ERR_BAD_SHAPE, "%s: the bank holds rows of %d, the handle's li_dim is %d", what, b->D, c.li_dim);
+  const int D = c.li_dim;
+  if (D % 16) return fail(m, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a multiple of 16)", what, D);
+  if (((uintptr_t)query_li) & 15) return fail(m, RR_ERR_BAD_ARG, "%s: query_li must be 16-byte aligned", what);
+  if ((((uintptr_t)indices_out) | ((uintptr_t)scores_out)) & 3) return fail(m, RR_ERR_BAD_ARG, "%s: misaligned output", what);
+  if (n_queries <= 0 || n_queries > 65535 || Lq <= 0)
+    return fail(m, RR_ERR_BAD_SHAPE, "%s: n_queries=%d (1..65535) Lq=%d", what, n_queries, Lq);
+  const long long held = (long long)b->first.size();
+  const long long n_ll = n_passages == -1 ? held - (long long)first_passage : (long long)n_passages;
+  if (first_passage < 0 || n_ll <= 0 || (long long)first_passage + n_ll > held)
+    return fail(m, RR_ERR_BAD_SHAPE, "%s: passages [%d, %d + %lld) of a bank that holds %lld", what, first_passage, first_passage, n_ll, held);
+  const int n = (int)n_ll;
+  if (k < 1 || k > n) return fail(m, RR_ERR_BAD_SHAPE, "%s: k=%d of %d passages", what, k, n);
+  if (k > 1024) return fail(m, RR_ERR_UNSUPPORTED, "%s: k=%d (at most 1024: a selection pass keeps k of 4096)", what, k);
+  hipStream_t st = (hipStream_t)hip_stream;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return fail(m, RR_ERR_BAD_ARG, "%s cannot be captured into a graph (it may upload the bank's passage table and grow its block)", what);
+  RR_HIP(m, hipSetDevice(c.device));
+  if (b->table_n < (size_t)held) {                  // the first search after an add
+    if (b->table_cap < (size_t)held) {
+      if (b->table) { RR_HIP(m, hipFree(b->table)); b->table = nullptr; }      // hipFree waits for whatever still reads it
+      b->table_cap = 0;
+      b->table_n = 0;
+      const size_t cap = std::min<size_t>((size_t)b->max_passages, std::max<size_t>((size_t)held * 2, 1024));
+      RR_HIP(m, hipMalloc((void**)&b->table, cap * sizeof(rr_bank_slot)));
+      b->table_cap = cap;
+    }
+    std::vector<rr_bank_slot> up((size_t)held - b->table_n);
+    for (size_t i = 0; i < up.size(); ++i) up[i] = rr_bank_slot{b->first[b->table_n + i], b->len[b->table_n + i], 0};
+    RR_HIP(m, hipMemcpyAsync(b->table + b->table_n, up.data(), up.size() * sizeof(rr_bank_slot), hipMemcpyHostToDevice, st));
+    RR_HIP(m, hipStreamSynchronize(st));            // `up` is pageable memory of this call
+    b->table_n = (size_t)held;
+  }
+  const size_t sc_bytes = (((size_t)n_queries * n * sizeof(float)) + 15) & ~(size_t)15;
+  const size_t tmp_bytes = ((rr_topk_select_scratch(n_queries, n, k) * sizeof(int32_t)) + 15) & ~(size_t)15;
+  RR_TRY(ensure_search_blk(m, sc_bytes + 2 * tmp_bytes, st));
+  float* sc = (float*)m->search_blk;
+  int32_t* tmp_a = tmp_bytes ? (int32_t*)(m->search_blk + sc_bytes) : nullptr;
+  int32_t* tmp_b = tmp_bytes ? (int32_t*)(m->search_blk + sc_bytes + tmp_bytes) : nullptr;
+  m->last_stream = st;
+  const size_t last = (size_t)first_passage + (size_t)n - 1;
+  const double rows = (double)(b->first[last] + b->len[last] - b->first[(size_t)first_passage]);      // passages lie back to back
+  const double row_bytes = b->nbits ? 4.0 + D * (b->nbits / 8.0 + 2.0) : 2.0 * D;
+  // bytes: the range's rows and mask bytes once (the queries of a chunk run side by side), the table, the query block per
+  // workgroup of 16 passages, one float per (query, passage)
+  const double bytes = rows * (row_bytes + 1.0) + 16.0 * n + (double)n_queries * (n / 16.0 + 1.0) * 4.0 * Lq * D + 4.0 * n_queries * (double)n;
+  const rr_bank_slot* table = b->table + first_passage;
+  if (b->nbits)
+    RR_RUN(m, st, RR_K_TAIL, 2.0 * n_queries * rows * Lq * D, bytes,
+           rr_launch_bank_search_scores_plaid(table, n, n_queries, Lq, D, query_li, b->nbits, b->codes, b->resid, b->centroids, b->weights,
+                                              b->n_centroids, b->mask, sc, st));
+  else
+    RR_RUN(m, st, RR_K_TAIL, 2.0 * n_queries * rows * Lq * D, bytes,
+           rr_launch_bank_search_scores(table, n, n_queries, Lq, D, query_li, b->rows, b->mask, sc, st));
+  RR_RUN(m, st, RR_K_TAIL, 0.0, 12.0 * n_queries * (double)n,
+         rr_launch_topk_select(sc, n_queries, n, k, first_passage, tmp_a, tmp_b, indices_out, scores_out, st));
+  return RR_OK;
+}
+
+// the scratch of the diagnostic search operators: allocated per call and freed behind a synchronisation of the stream
+static int op_select_with_scratch(const float* scores, int n_lists, int n, int k, int add, int32_t* indices_out, float* scores_out, hipStream_t st) {
+  const size_t entries = rr_topk_select_scratch(n_lists, n, k);
+  int32_t* tmp = nullptr;
+  if (entries && hipMalloc((void**)&tmp, 2 * entries * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); return RR_ERR_OOM; }
+  hipError_t e = rr_launch_topk_select(scores, n_lists, n, k, add, tmp, tmp ? tmp + entries : nullptr, indices_out, scores_out, st);
+  if (tmp) {
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2;
+    (void)hipFree(tmp);
+  }
+  return e == hipSuccess ? RR_OK : RR_ERR_HIP;
+}
+
+static int rr_op_topk_select_impl(const float* scores, int n_lists, int n, int k, int32_t* indices_out, float* scores_out, void* hip_stream) {
+  if (!scores || !indices_out) return RR_ERR_BAD_ARG;
+  if (n_lists <= 0 || n_lists > 65535 || n <= 0 || k < 1 || k > n) return RR_ERR_BAD_SHAPE;
+  if (k > 1024) return RR_ERR_UNSUPPORTED;
+  return op_select_with_scratch(scores, n_lists, n, k, 0, indices_out, scores_out, (hipStream_t)hip_stream);
+}
+
+static int rr_op_bank_search_impl(const float* query_li, int n_queries, int Lq, int D, const void* table, int32_t first_passage, int32_t n_passages,
+                                  int k, const uint16_t* rows_f16, const uint8_t* mask_bytes, int nbits, const int32_t* codes,
+                                  const uint8_t* residuals, const uint16_t* centroids_f16, const float* bucket_weights, int32_t n_centroids,
+                                  int32_t* indices_out, float* scores_out, void* hip_stream) {
+  if (!query_li || !table || !mask_bytes || !indices_out) return RR_ERR_BAD_ARG;
+  if (nbits ? (!codes || !residuals || !centroids_f16 || !bucket_weights) : !rows_f16) return RR_ERR_BAD_ARG;
+  if ((((uintptr_t)query_li) | ((uintptr_t)table)) & 15) return RR_ERR_BAD_ARG;
+  if (D <= 0 || D % 16 || (nbits && !rr_plaid_shape_ok(nbits, D))) return RR_ERR_UNSUPPORTED;
+  if (n_queries <= 0 || n_queries > 65535 || Lq <= 0 || first_passage < 0 || n_passages <= 0 || (nbits && n_centroids <= 0) || k < 1 || k > n_passages)
+    return RR_ERR_BAD_SHAPE;
+  if (k > 1024) return RR_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)hip_stream;
+  float* sc = nullptr;
+  if (hipMalloc((void**)&sc, (size_t)n_queries * n_passages * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return RR_ERR_OOM; }
+  const rr_bank_slot* t = (const rr_bank_slot*)table + first_passage;
+  const hipError_t e = nbits ? rr_launch_bank_search_scores_plaid(t, n_passages, n_queries, Lq, D, query_li, nbits, codes, residuals, centroids_f16,
+                                                                  bucket_weights, n_centroids, mask_bytes, sc, st)
+                             : rr_launch_bank_search_scores(t, n_passages, n_queries, Lq, D, query_li, rows_f16, mask_bytes, sc, st);
+  int rc = e == hipSuccess ? op_select_with_scratch(sc, n_queries, n_passages, k, first_passage, indices_out, scores_out, st) : RR_ERR_HIP;
+  if (hipStreamSynchronize(st) != hipSuccess && rc == RR_OK) rc = RR_ERR_HIP;
+  (void)hipFree(sc);
+  return rc;
+}
+
 static int64_t rr_debug_read_impl(rr_handle h, const char* name, float* host_out, int64_t max_elems) {
   if (!h || !name || !host_out) return RR_ERR_BAD_ARG;
   if (hipSetDevice(h->cfg.device) != hipSuccess) return RR_ERR_HIP;
@@ -2910,6 +3045,7 @@ int rr_set_tuning(const char* key, int value) {
   if (!strcmp(key, "gemm_desync")) return rr_set_gemm_desync(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
   if (!strcmp(key, "m_alternate")) return rr_set_m_alternate(value);
   if (!strcmp(key, "li_lds_kb")) return rr_set_li_lds_kb(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
+  if (!strcmp(key, "search_chunk")) return rr_set_search_chunk(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
   if (!strcmp(key, "attn_prio")) return rr_set_attn_prio(value);
   if (!strcmp(key, "attn_fixed_ref")) return rr_set_attn_fixed_ref(value);
   return RR_ERR_BAD_ARG;
@@ -3364,6 +3500,7 @@ int rr_bank_clear(rr_bank_handle b) {
   b->first.clear();
   b->len.clear();
   b->used_rows = 0;
+  b->table_n = 0;                 // the search's device table is rebuilt from the next passages
   return RR_OK;
 }
 const char* rr_bank_last_error(rr_bank_handle b) { return b ? b->err.c_str() : ""; }
@@ -3409,6 +3546,15 @@ int rr_forward_interaction_bank(rr_handle h, rr_bank_handle b, const float* quer
 }
 int rr_bank_li_scores(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, const int32_t* pair_passage, const int32_t* pair_query, int n_pairs, int padded_context_len, float* scores_out, float* maxsim_out, void* hip_stream) {
   return guarded(h, [&]() -> int { return bank_li_scores_call(h, b, query_li, n_queries, Lq, pair_passage, pair_query, n_pairs, padded_context_len, scores_out, maxsim_out, hip_stream); });
+}
+int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage, int32_t n_passages, int k, int32_t* indices_out, float* scores_out, void* hip_stream) {
+  return guarded(h, [&]() -> int { return bank_search_call(h, b, query_li, n_queries, Lq, first_passage, n_passages, k, indices_out, scores_out, hip_stream); });
+}
+int rr_op_bank_search(const float* query_li, int n_queries, int Lq, int D, const void* table, int32_t first_passage, int32_t n_passages, int k, const uint16_t* rows_f16, const uint8_t* mask_bytes, int nbits, const int32_t* codes, const uint8_t* residuals, const uint16_t* centroids_f16, const float* bucket_weights, int32_t n_centroids, int32_t* indices_out, float* scores_out, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_bank_search_impl(query_li, n_queries, Lq, D, table, first_passage, n_passages, k, rows_f16, mask_bytes, nbits, codes, residuals, centroids_f16, bucket_weights, n_centroids, indices_out, scores_out, hip_stream); });
+}
+int rr_op_topk_select(const float* scores, int n_lists, int n, int k, int32_t* indices_out, float* scores_out, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_topk_select_impl(scores, n_lists, n, k, indices_out, scores_out, hip_stream); });
 }
 int rr_op_li_scores(const float* query_li, const float* context_li, const float* context_mask, int n, int K, int Lq, int Lc, int D, float* scores_out, float* maxsim_out, void* hip_stream) {
   if (!query_li || !context_li || !context_mask || (!scores_out && !maxsim_out)) return RR_ERR_BAD_ARG;

@@ -469,6 +469,18 @@ hipError_t rr_launch_bank_li_scores(const rr_bank_pair* pairs, const int32_t* sl
 hipError_t rr_launch_bank_li_scores_plaid(const rr_bank_pair* pairs, const int32_t* slot, int n, int Lq, int Lc, int D, const float* query_li, int nbits,
                                           const int32_t* codes, const uint8_t* resid, const uint16_t* centroids, const float* weights,
                                           int C, const uint8_t* mask_bytes, float* scores, float* maxsim, hipStream_t st);
+// rr_bank_search (bank_search.hip): out [nq][n] = the MaxSim of every query against the passages table[0 .. n) (the bits of
+// rr_launch_bank_li_scores' maxsim at Lc = the passage's length), and the selection: the first k of every list in the order of a
+// stable descending sort (NaN first, ties by ascending index), indices + add; tmp_a / tmp_b hold rr_topk_select_scratch int32 each
+hipError_t rr_launch_bank_search_scores(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li, const uint16_t* rows,
+                                        const uint8_t* mask_bytes, float* out, hipStream_t st);
+hipError_t rr_launch_bank_search_scores_plaid(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li, int nbits,
+                                              const int32_t* codes, const uint8_t* resid, const uint16_t* centroids, const float* weights,
+                                              int C, const uint8_t* mask_bytes, float* out, hipStream_t st);
+size_t rr_topk_select_scratch(int n_lists, int n, int k);
+hipError_t rr_launch_topk_select(const float* scores, int n_lists, int n, int k, int add, int32_t* tmp_a, int32_t* tmp_b,
+                                 int32_t* indices_out, float* scores_out, hipStream_t st);
+int rr_set_search_chunk(int passages);      // rr_set_tuning("search_chunk"): 4 .. 128, -1 outside
 bool rr_plaid_shape_ok(int nbits, int D);
 bool rr_plaid_decode_rows_host(const uint16_t* centroids, int C, const float* weights, int nbits, int D, const int32_t* codes,
                                const uint8_t* resid, long long n_rows, uint16_t* out);

@@ -835,6 +835,36 @@ class RerankEngine:
                                            L.ptr(out["scores"]), L.ptr(out["maxsim"]), self._stream()), self.h, "rr_bank_li_scores")
         return {k: v for k, v in out.items() if v is not None}
 
+    def bank_search(self, bank, query_li: torch.Tensor, k: int, first: int = 0, count: Optional[int] = None) -> dict:
+        """Exact top-k MaxSim search over `bank`, fp16 or compressed (rr_bank_search): every passage of the dense index range
+        [first, first + count) (`count` None: through the last passage) is scored against every query of `query_li`
+        [n_queries, Lq, D] with the retriever's MaxSim (colbert_score, flmr_utils.py:22-48; bit for bit the `maxsim` of
+        bank_li_scores), and per query the k best are returned in the order of torch.sort(descending=True, stable=True):
+        {"indices": int32 [n_queries, k] dense bank indices, "scores": float32 [n_queries, k]}, both on the device.
+        1 <= k <= min(count, 1024) (ValueError / NotImplementedError).  NORMAL and MORES engines, weights loaded or not."""
+        D = self.arch["li_dim"]
+        if query_li.dim() != 3 or query_li.shape[2] != D:
+            raise ValueError(f"query_li {tuple(query_li.shape)}: [n_queries, Lq, {D}]")
+        held = len(bank)
+        first = int(first)
+        n = held - first if count is None else int(count)
+        if first < 0 or n < 1 or first + n > held:
+            raise ValueError(f"bank_search: passages [{first}, {first} + {n}) of a bank that holds {held}")
+        k = int(k)
+        if k < 1 or k > n:
+            raise ValueError(f"bank_search: k = {k} of {n} passages")
+        if k > 1024:
+            raise NotImplementedError(f"bank_search: k = {k} (at most 1024)")
+        nq, Lq = int(query_li.shape[0]), int(query_li.shape[1])
+        if nq < 1 or Lq < 1:
+            raise ValueError(f"query_li {tuple(query_li.shape)}: no query tokens")
+        q = query_li.to(device=self.device, dtype=torch.float32).contiguous()
+        out = dict(indices=torch.empty((nq, k), device=self.device, dtype=torch.int32),
+                   scores=torch.empty((nq, k), device=self.device, dtype=torch.float32))
+        L.check(self.lib.rr_bank_search(self.h, bank.h, L.ptr(q), nq, Lq, first, n, k, L.ptr(out["indices"]), L.ptr(out["scores"]),
+                                        self._stream()), self.h, "rr_bank_search")
+        return out
+
     def li_scores(self, query_li: torch.Tensor, context_li: torch.Tensor, context_mask: torch.Tensor, Bq: int, K: int,
                   pair_range: Optional[Sequence[int]] = None, want_scores: bool = True, want_maxsim: bool = True) -> dict:
         """The frozen retriever's score of every pair and the matrix behind it (rr_li_scores; colbert_score,
@@ -1275,6 +1305,20 @@ class InteractionRerankModel(_DropIn):
         if self.bank is None:
             raise RuntimeError("retriever_scores needs a bank: model.create_bank(capacity_rows, max_passages), then bank.add(...)")
         return self.engine.bank_li_scores(self.bank, query_late_interaction, passage_ids, **kw)
+
+    def retrieve(self, query_late_interaction, k: int, **kw):
+        """The k best passages of `self.bank` per query by the frozen retriever's MaxSim, every passage scored
+        (PassageBank.search): (passage_ids: one list per query, best first; scores float32 [n_queries, k] on the device)."""
+        if self.bank is None:
+            raise RuntimeError("retrieve needs a bank: model.create_bank(capacity_rows, max_passages), then bank.add(...)")
+        return self.bank.search(self.engine, query_late_interaction, k, **kw)
+
+    def retrieve_and_rerank(self, query_late_interaction, query_mask, k: int, **kw):
+        """`retrieve` then `forward_passages` on what it found, k candidates per query in retrieval order: (passage_ids, the
+        RerankOutput).  `kw` goes to forward_passages (labels default as there: candidate 0 of every query)."""
+        ids, _ = self.retrieve(query_late_interaction, k)
+        flat = [pid for row in ids for pid in row]
+        return ids, self.forward_passages(query_late_interaction, query_mask, flat, int(k) - 1, **kw)
 
     def forward(self, query_late_interaction, context_late_interaction, num_negative_examples, query_mask,
                 context_mask, preflmr_scores=None, fusion_multiplier=1, labels=None, candidates_per_query=None,

@@ -14,6 +14,9 @@ include/rerank_mi355.h, rr_bank_create_plaid).  `read_plaid_index` reads such an
 `PassageBank.maxsim` / RerankEngine.bank_li_scores give the retriever's own score of (query, passage) pairs (MaxSim and the score
 matrix, rr_bank_li_scores) from either kind of bank, without a padded context tensor.
 
+`PassageBank.search` / RerankEngine.bank_search give the k best passages of the bank (or of a range of it) per query by that
+score, exactly (rr_bank_search): every passage is scored, nothing is pruned.
+
 `BankTable`, `plan_bank_batch`, `plan_bank_scores`, `PlaidCodec` and `read_plaid_index` are the host side: pure Python / numpy / torch on the CPU,
 usable and tested without a device.
 """
@@ -26,11 +29,12 @@ from .pair_inputs import group_pairs_by_length
 
 
 class BankTable:
-    """The host table of a bank: passage id -> dense index, and every passage's length in rows."""
+    """The host table of a bank: passage id -> dense index, dense index -> passage id (`ids`), and every passage's length in rows."""
 
     def __init__(self):
         self.index_of: dict = {}
         self.lengths: list = []
+        self.ids: list = []
 
     def __len__(self) -> int:
         return len(self.lengths)
@@ -56,6 +60,7 @@ class BankTable:
             assert int(ln) >= 1, f"passage {pid!r}: length {ln}"
             self.index_of[pid] = len(self.lengths)
             self.lengths.append(int(ln))
+            self.ids.append(pid)
         return first
 
     def lookup(self, passage_ids: Sequence):
@@ -74,6 +79,7 @@ class BankTable:
     def clear(self) -> None:
         self.index_of.clear()
         self.lengths.clear()
+        self.ids.clear()
 
 
 def plan_bank_batch(table: BankTable, passage_ids: Sequence, K: Optional[int], list_sizes: Optional[Sequence[int]], padded_len: int,
@@ -432,6 +438,14 @@ class PassageBank:
     def maxsim(self, engine, query_li, passage_ids, **kw):
         """The retriever's MaxSim [n_pairs] of the pairs (query, passage id) from this bank: engine.bank_li_scores(...)["maxsim"]."""
         return engine.bank_li_scores(self, query_li, passage_ids, **kw)["maxsim"]
+
+    def search(self, engine, query_li, k: int, first: int = 0, count: Optional[int] = None):
+        """The k best passages per query by the retriever's MaxSim, every passage of the bank scored (engine.bank_search;
+        `first` / `count`: a range of dense indices).  Returns (passage_ids, scores): passage_ids[q] the ids of query q best
+        first, scores float32 [n_queries, k] on the device.  Copies the indices to the host (synchronises)."""
+        r = engine.bank_search(self, query_li, k, first=first, count=count)
+        ids = self.table.ids
+        return [[ids[j] for j in row] for row in r["indices"].tolist()], r["scores"]
 
     def clear(self) -> None:
         """Forget every passage (rr_bank_clear; the capacity stays).  Forwards that read the bank must have completed."""

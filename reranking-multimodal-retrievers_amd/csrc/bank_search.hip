@@ -33,6 +33,10 @@
 //     by ascending index.  Score and index are packed into one 64-bit key (an order-preserving image of the float above, the
 //     complement of the index below), keys are distinct, so the bitonic network has one possible result: no atomics, nothing
 //     depends on scheduling.  Survivors travel as indices; a pass reads their scores again from the score row.
+// LAUNCHERS: rr_launch_bank_search_scores takes an rr_bank_view (rr_common.h), fp16 or compressed, and rr_launch_topk_select.  The
+// operand sources, the view-to-source dispatch (li_with_bank_source), the once-per-device LDS attribute (li_lds_attr) and the width
+// of the column block (li_pick_jt, here with a fixed 72 KB) live in li_sources.h, shared with li_scores.hip; the tile step is
+// written out in both kernel bodies (see li_scores.hip's header).
 #include <algorithm>
 #include <atomic>
 
@@ -144,15 +148,9 @@ std::atomic<int> g_search_chunk{16};
 template <int JT, class SRC>
 hipError_t search_launch_jt(const float* query_li, const SRC& src, const rr_bank_slot* table, int n, int nq, int Lq, int D, size_t lds,
                             float* out, hipStream_t st) {
-  static std::atomic<unsigned long long> attr_set{0};   // per device ordinal (see gemm_bf16.hip ensure_lds_attr)
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  static std::atomic<unsigned long long> attr_set{0};
+  const hipError_t e = li_lds_attr((const void*)bank_search_scores_kernel<JT, SRC>, attr_set);
   if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64 || !((attr_set.load(std::memory_order_acquire) >> dev) & 1ull)) {
-    e = hipFuncSetAttribute((const void*)bank_search_scores_kernel<JT, SRC>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) attr_set.fetch_or(1ull << dev, std::memory_order_release);
-  }
   const int chunk = g_search_chunk.load(std::memory_order_relaxed);
   const long long blocks = ((long long)n + chunk - 1) / chunk * nq;
   if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
@@ -164,13 +162,10 @@ hipError_t search_launch_jt(const float* query_li, const SRC& src, const rr_bank
 template <class SRC>
 hipError_t search_launch(const float* query_li, const SRC& src, const rr_bank_slot* table, int n, int nq, int Lq, int D,
                          size_t tile_bytes, float* out, hipStream_t st) {
-  // the narrowest column block that takes Lq in one pass, 128 columns beyond; halved while the query rows and the decoded tiles
-  // would leave room for fewer than two workgroups per CU (any width gives the same bits: the sum is carried between blocks)
-  int jt = Lq <= 16 ? 1 : Lq <= 32 ? 2 : Lq <= 64 ? 4 : BS_JT_MAX;
-  auto lds_bytes = [&](int t) { return (size_t)16 * t * (D + 4) * sizeof(float) + tile_bytes; };
-  while (jt > 1 && lds_bytes(jt) > (size_t)72 * 1024) jt /= 2;
-  const size_t lds = lds_bytes(jt);
-  if (lds > 150 * 1024) return hipErrorInvalidValue;
+  // the column block is halved above a fixed 72 KB (any width gives the same bits: the sum is carried between blocks)
+  size_t lds = 0;
+  const int jt = li_pick_jt(Lq, D, tile_bytes, (size_t)72 * 1024, &lds);
+  if (jt == 0) return hipErrorInvalidValue;
   if (jt == 1) return search_launch_jt<1>(query_li, src, table, n, nq, Lq, D, lds, out, st);
   if (jt == 2) return search_launch_jt<2>(query_li, src, table, n, nq, Lq, D, lds, out, st);
   if (jt == 4) return search_launch_jt<4>(query_li, src, table, n, nq, Lq, D, lds, out, st);
@@ -239,33 +234,13 @@ int rr_set_search_chunk(int passages) {
   return 0;
 }
 
-// out [nq][n]: the MaxSim of every query against the passages table[0 .. n) (an fp16 bank)
-hipError_t rr_launch_bank_search_scores(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li, const uint16_t* rows,
-                                        const uint8_t* mask_bytes, float* out, hipStream_t st) {
-  if (n <= 0 || nq <= 0 || Lq <= 0 || D <= 0 || D % 16 || !table || !query_li || !rows || !mask_bytes || !out) return hipErrorInvalidValue;
-  if ((((uintptr_t)query_li) & 15) || (((uintptr_t)rows) & 7) || (((uintptr_t)table) & 15)) return hipErrorInvalidValue;
-  return search_launch(query_li, li_src_f16{nullptr, nullptr, rows, mask_bytes}, table, n, nq, Lq, D, 0, out, st);
-}
-
-// ... and a compressed bank (tables as rr_launch_bank_gather_plaid takes them)
-hipError_t rr_launch_bank_search_scores_plaid(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li, int nbits,
-                                              const int32_t* codes, const uint8_t* resid, const uint16_t* centroids, const float* weights,
-                                              int C, const uint8_t* mask_bytes, float* out, hipStream_t st) {
-  if (n <= 0 || nq <= 0 || Lq <= 0 || D % 16 || !rr_plaid_shape_ok(nbits, D) || C <= 0 || !table || !query_li || !codes || !resid ||
-      !centroids || !weights || !mask_bytes || !out)
-    return hipErrorInvalidValue;
-  if (((((uintptr_t)query_li) | ((uintptr_t)centroids) | ((uintptr_t)table)) & 15) || (((uintptr_t)resid) & 7) || (((uintptr_t)codes) & 3))
-    return hipErrorInvalidValue;
-  const size_t tile_bytes = (size_t)4 * 16 * (D + LI_TILE_PAD) * sizeof(uint16_t);
-#define BS_PLAID(NB) \
-  return search_launch(query_li, li_src_plaid<NB>{nullptr, nullptr, codes, resid, centroids, weights, C, mask_bytes}, table, n, nq, Lq, D, tile_bytes, out, st)
-  switch (nbits) {
-    case 1: BS_PLAID(1);
-    case 2: BS_PLAID(2);
-    case 4: BS_PLAID(4);
-    default: BS_PLAID(8);
-  }
-#undef BS_PLAID
+// out [nq][n]: the MaxSim of every query against the passages table[0 .. n) of a bank, fp16 or compressed (li_with_bank_source)
+hipError_t rr_launch_bank_search_scores(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
+                                        const rr_bank_view& bank, float* out, hipStream_t st) {
+  if (n <= 0 || nq <= 0 || Lq <= 0 || !table || !query_li || !out || ((((uintptr_t)query_li) | ((uintptr_t)table)) & 15)) return hipErrorInvalidValue;
+  return li_with_bank_source(nullptr, nullptr, bank, D, [&](const auto& src, size_t tile_bytes) {
+    return search_launch(query_li, src, table, n, nq, Lq, D, tile_bytes, out, st);
+  });
 }
 
 // int32 entries of EACH of the two survivor buffers rr_launch_topk_select needs (0: one slice, none)

@@ -36,9 +36,12 @@
 // wholly beyond the pair's rows runs no matrix instruction and no decode (its accumulators stay zero and every row of it is
 // masked; the float32 source takes the same path for Lc_in <= c < Lc).  The arithmetic of an entry is the same instruction
 // sequence on the same float32 values in all three, so the three agree bit for bit on equal rows.
-#include <atomic>
-
-#include "li_sources.h"    // f32x4, nan_max, half4, li_src_f16, li_src_plaid (shared with bank_search.hip)
+// LAUNCHERS: rr_launch_li_scores (li_src_f32) and rr_launch_bank_li_scores, which takes an rr_bank_view (rr_common.h) and leaves the
+// choice between li_src_f16 and li_src_plaid<nbits> to li_with_bank_source.  That helper, the two bank sources, the once-per-device
+// LDS attribute (li_lds_attr) and the width of the column block (li_pick_jt, here under the li_lds_kb tunable) live in li_sources.h,
+// shared with bank_search.hip.  The tile step (stage, cursor, look-ahead load, the e-outer / t-inner matrix loop) is written out in
+// both kernel bodies: as a shared __forceinline__ function it compiled to a different instruction stream in every instantiation.
+#include "li_sources.h"    // f32x4, nan_max, half4, li_src_f16, li_src_plaid, li_with_bank_source, li_lds_attr, li_pick_jt
 #include "rr_common.h"
 
 namespace {
@@ -176,32 +179,21 @@ std::atomic<int> g_li_lds_kb{72};
 template <int JT, class SRC>
 hipError_t li_launch_jt(const float* query_li, const SRC& src, int n, int Lq, int Lc, int D, size_t lds, float* scores, float* maxsim,
                         hipStream_t st) {
-  static std::atomic<unsigned long long> attr_set{0};   // per device ordinal (see gemm_bf16.hip ensure_lds_attr)
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  static std::atomic<unsigned long long> attr_set{0};
+  const hipError_t e = li_lds_attr((const void*)li_scores_kernel<JT, SRC>, attr_set);
   if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64 || !((attr_set.load(std::memory_order_acquire) >> dev) & 1ull)) {
-    e = hipFuncSetAttribute((const void*)li_scores_kernel<JT, SRC>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) attr_set.fetch_or(1ull << dev, std::memory_order_release);
-  }
   hipLaunchKernelGGL((li_scores_kernel<JT, SRC>), dim3((unsigned)n), dim3(256), lds, st, query_li, src, Lq, Lc, D, scores, maxsim);
   return hipGetLastError();
 }
 
-// one workgroup per pair; tile_bytes: the decoded tiles of the four waves behind the query block (0 unless SRC::TILE)
+// one workgroup per pair; tile_bytes: the decoded tiles of the four waves behind the query block (0 unless SRC::TILE).  The
+// column block is halved above li_lds_kb (D above 128; a compressed bank at D = 128 already)
 template <class SRC>
 hipError_t li_launch(const float* query_li, const SRC& src, int n, int Lq, int Lc, int D, size_t tile_bytes, float* scores,
                      float* maxsim, hipStream_t st) {
-  // the narrowest column block that takes Lq in one pass (a tile without a column is matrix-core time), 128 columns beyond;
-  // halved while its query rows [16 JT][D + 4] and the decoded tiles would not leave room for two workgroups per CU (D above
-  // 128; a compressed bank at D = 128 already)
-  int jt = Lq <= 16 ? 1 : Lq <= 32 ? 2 : Lq <= 64 ? 4 : LI_JT_MAX;
-  auto lds_bytes = [&](int t) { return (size_t)16 * t * (D + 4) * sizeof(float) + tile_bytes; };
-  const size_t limit = (size_t)g_li_lds_kb.load(std::memory_order_relaxed) * 1024;
-  while (jt > 1 && lds_bytes(jt) > limit) jt /= 2;
-  const size_t lds = lds_bytes(jt);
-  if (lds > 150 * 1024) return hipErrorInvalidValue;
+  size_t lds = 0;
+  const int jt = li_pick_jt(Lq, D, tile_bytes, (size_t)g_li_lds_kb.load(std::memory_order_relaxed) * 1024, &lds);
+  if (jt == 0) return hipErrorInvalidValue;
   if (jt == 1) return li_launch_jt<1>(query_li, src, n, Lq, Lc, D, lds, scores, maxsim, st);
   if (jt == 2) return li_launch_jt<2>(query_li, src, n, Lq, Lc, D, lds, scores, maxsim, st);
   if (jt == 4) return li_launch_jt<4>(query_li, src, n, Lq, Lc, D, lds, scores, maxsim, st);
@@ -227,36 +219,16 @@ hipError_t rr_launch_li_scores(const float* query_li, const float* context_li, c
   return li_launch(query_li, li_src_f32{context_li, context_mask, K, Lc_in, pair0}, n, Lq, Lc, D, 0, scores, maxsim, st);
 }
 
-// the same over a pair list and an fp16 bank: pairs [n] on the device, each checked on the host (first_row + len inside the bank,
-// len <= Lc, query inside query_li); scores [n][Lc][Lq], maxsim [n], either may be null.  slot [n] (device) or null: workgroup p
-// writes row slot[p] of the outputs, so that the host can start the longest passages first (one workgroup per pair: 800 pairs of
-// 64 .. 512 rows on 512 slots end 20 - 25 % sooner that way, profiles/bank_li_scores_bench_call_order.json.log) and the caller still
-// gets its own order; a permutation of 0 .. n - 1, checked by whoever builds it
-hipError_t rr_launch_bank_li_scores(const rr_bank_pair* pairs, const int32_t* slot, int n, int Lq, int Lc, int D, const float* query_li, const uint16_t* rows,
-                                    const uint8_t* mask_bytes, float* scores, float* maxsim, hipStream_t st) {
-  if (n <= 0 || Lq <= 0 || Lc <= 0 || D <= 0 || D % 16 || !pairs || !query_li || !rows || !mask_bytes || (!scores && !maxsim))
-    return hipErrorInvalidValue;
-  if ((((uintptr_t)query_li) & 15) || (((uintptr_t)rows) & 7)) return hipErrorInvalidValue;   // 16-byte query, 8-byte bank loads
-  return li_launch(query_li, li_src_f16{pairs, slot, rows, mask_bytes}, n, Lq, Lc, D, 0, scores, maxsim, st);
-}
-
-// ... and a compressed bank (tables as rr_launch_bank_gather_plaid takes them)
-hipError_t rr_launch_bank_li_scores_plaid(const rr_bank_pair* pairs, const int32_t* slot, int n, int Lq, int Lc, int D, const float* query_li, int nbits,
-                                          const int32_t* codes, const uint8_t* resid, const uint16_t* centroids, const float* weights,
-                                          int C, const uint8_t* mask_bytes, float* scores, float* maxsim, hipStream_t st) {
-  if (n <= 0 || Lq <= 0 || Lc <= 0 || D % 16 || !rr_plaid_shape_ok(nbits, D) || C <= 0 || !pairs || !query_li || !codes || !resid ||
-      !centroids || !weights || !mask_bytes || (!scores && !maxsim))
-    return hipErrorInvalidValue;
-  if (((((uintptr_t)query_li) | ((uintptr_t)centroids)) & 15) || (((uintptr_t)resid) & 7) || (((uintptr_t)codes) & 3))
-    return hipErrorInvalidValue;
-  const size_t tile_bytes = (size_t)4 * 16 * (D + LI_TILE_PAD) * sizeof(uint16_t);
-#define LI_PLAID(NB) \
-  return li_launch(query_li, li_src_plaid<NB>{pairs, slot, codes, resid, centroids, weights, C, mask_bytes}, n, Lq, Lc, D, tile_bytes, scores, maxsim, st)
-  switch (nbits) {
-    case 1: LI_PLAID(1);
-    case 2: LI_PLAID(2);
-    case 4: LI_PLAID(4);
-    default: LI_PLAID(8);
-  }
-#undef LI_PLAID
+// the same over a pair list and a bank, fp16 or compressed (li_with_bank_source, li_sources.h): pairs [n] on the device, each
+// checked on the host (first_row + len inside the bank, len <= Lc, query inside query_li); scores [n][Lc][Lq], maxsim [n], either may
+// be null.  slot [n] (device) or null: workgroup p writes row slot[p] of the outputs, so that the host can start the longest
+// passages first (one workgroup per pair: 800 pairs of 64 .. 512 rows on 512 slots end 20 - 25 % sooner that way,
+// profiles/bank_li_scores_bench_call_order.json.log) and the caller still gets its own order; a permutation of 0 .. n - 1, checked
+// by whoever builds it
+hipError_t rr_launch_bank_li_scores(const rr_bank_pair* pairs, const int32_t* slot, int n, int Lq, int Lc, int D, const float* query_li,
+                                    const rr_bank_view& bank, float* scores, float* maxsim, hipStream_t st) {
+  if (n <= 0 || Lq <= 0 || Lc <= 0 || !pairs || !query_li || (!scores && !maxsim) || (((uintptr_t)query_li) & 15)) return hipErrorInvalidValue;
+  return li_with_bank_source(pairs, slot, bank, D, [&](const auto& src, size_t tile_bytes) {
+    return li_launch(query_li, src, n, Lq, Lc, D, tile_bytes, scores, maxsim, st);
+  });
 }

@@ -1,9 +1,17 @@
 // The bank-side operand sources of the late-interaction score kernels, shared by li_scores.hip (one workgroup per pair,
 // rr_bank_li_scores) and bank_search.hip (one wave per passage, rr_bank_search): where the four floats a lane feeds to one
 // v_mfma_f32_16x16x4_f32 step come from.  One definition, so that both kernels run the same instruction sequence on the same
-// float32 values (li_scores.hip's header comment describes the sources).
+// float32 values (li_scores.hip's header comment describes the sources).  The rest of what the two kernels share lives here too:
+//   li_with_bank_source an rr_bank_view as the source a kernel template takes (li_src_f16 or li_src_plaid<NBITS>), with the checks
+//                       of each kind: the one place the two launchers (rr_launch_bank_li_scores, rr_launch_bank_search_scores)
+//                       decide between fp16 and compressed;
+//   li_lds_attr / li_pick_jt   the launch rule: the dynamic-LDS attribute once per device, the width of the column block.
+// The tile step of the two kernels is NOT here: moved into one __forceinline__ function it changed the instruction stream of every
+// instantiation of both kernels (same registers, LDS and instruction counts within 3, another schedule), so each body keeps its copy.
 #pragma once
-#include "plaid_decode.h"      // plaid_load8 / plaid_finish8, pack2h
+#include <atomic>
+
+#include "plaid_decode.h"      // plaid_load8 / plaid_finish8, pack2h, plaid_with_nbits, plaid_tables_ok
 #include "rr_common.h"
 
 namespace {
@@ -91,5 +99,47 @@ struct li_src_plaid {
   static __device__ __forceinline__ f32x4 at(cursor cur, int d) { return half4(cur + d); }
   __device__ __forceinline__ bool keep(const pair_t& pr, int row) const { return pr.mask[row] != 0; }
 };
+
+// f(source, tile_bytes) over the rows of `bank`; tile_bytes: the decoded tiles of the four waves behind the query block (0 for
+// fp16 rows).  16-byte query loads are the caller's check; here: 8-byte loads of fp16 rows, plaid_tables_ok of compressed ones.
+template <class F>
+hipError_t li_with_bank_source(const rr_bank_pair* pairs, const int32_t* slot, const rr_bank_view& bank, int D, F&& f) {
+  if (D <= 0 || D % 16 || !bank.mask) return hipErrorInvalidValue;
+  if (!bank.nbits) {
+    if (!bank.rows || (((uintptr_t)bank.rows) & 7)) return hipErrorInvalidValue;
+    return f(li_src_f16{pairs, slot, bank.rows, bank.mask}, (size_t)0);
+  }
+  if (!plaid_tables_ok(bank, D)) return hipErrorInvalidValue;
+  const size_t tile_bytes = (size_t)4 * 16 * (D + LI_TILE_PAD) * sizeof(uint16_t);
+  return plaid_with_nbits(bank.nbits, [&](auto nb) {
+    return f(li_src_plaid<decltype(nb)::value>{pairs, slot, bank.codes, bank.resid, bank.centroids, bank.weights, bank.n_centroids, bank.mask},
+             tile_bytes);
+  });
+}
+
+// up to 150 KB of dynamic LDS for `kernel`, asked for once per device ordinal (attr_set: one word per kernel instantiation; see
+// gemm_bf16.hip ensure_lds_attr)
+inline hipError_t li_lds_attr(const void* kernel, std::atomic<unsigned long long>& attr_set) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (dev < 0 || dev >= 64 || !((attr_set.load(std::memory_order_acquire) >> dev) & 1ull)) {
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    if (e != hipSuccess) return e;
+    if (dev >= 0 && dev < 64) attr_set.fetch_or(1ull << dev, std::memory_order_release);
+  }
+  return hipSuccess;
+}
+
+// the query tiles (16 columns) of a column block: the narrowest block that takes Lq in one pass (a tile without a column is
+// matrix-core time), 128 columns beyond; halved while its query rows [16 JT][D + 4] and the decoded tiles exceed `limit` bytes (room
+// for two workgroups per CU at 72 KB).  *lds: the dynamic LDS of the launch; 0 when even that exceeds what a workgroup can have
+inline int li_pick_jt(int Lq, int D, size_t tile_bytes, size_t limit, size_t* lds) {
+  int jt = Lq <= 16 ? 1 : Lq <= 32 ? 2 : Lq <= 64 ? 4 : 8;
+  auto lds_bytes = [&](int t) { return (size_t)16 * t * (D + 4) * sizeof(float) + tile_bytes; };
+  while (jt > 1 && lds_bytes(jt) > limit) jt /= 2;
+  *lds = lds_bytes(jt);
+  return *lds > 150 * 1024 ? 0 : jt;
+}
 
 }  // namespace

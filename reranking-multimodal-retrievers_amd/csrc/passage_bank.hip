@@ -13,12 +13,15 @@
 //   bank_gather_plaid_kernel  bank_gather_kernel over a COMPRESSED bank (rr_bank_create_plaid): a context row is a ColBERTv2 /
 //                       PLAID residual code (one int32 centroid index and D * nbits / 8 bytes of bucketised residual, as
 //                       third_party/ColBERT/colbert/indexing/index_saver.py:33-46 of the reference writes them) and is decoded in
-//                       the gather by plaid_decode8: what the reference's decompress_residuals.cu + F.normalize do
+//                       the gather by plaid_load8 / plaid_finish8: what the reference's decompress_residuals.cu + F.normalize do
 //                       (codecs/residual.py:242-278), then rounded to fp16 FIRST and converted fp16 -> float32 -> operand type as
 //                       the fp16 bank's rows are, so that a compressed bank is bit for bit an fp16 bank of its decoded rows.
 //   bank_decode_plaid_kernel  rows [first_row, first_row + n) decoded to fp16 by the same device function (rr_bank_read on a
 //                       compressed bank, rr_op_plaid_decode_rows).
 //   rr_plaid_decode_rows_host  the same arithmetic in host code (rr_util_plaid_decode_rows): the bit-level definition.
+// LAUNCHERS: rr_launch_bank_ingest, rr_launch_bank_gather and rr_launch_plaid_decode.  The last two take an rr_bank_view
+// (rr_common.h); the gather picks its kernel by the view's nbits.  A runtime nbits becomes a template argument in one place,
+// plaid_with_nbits (plaid_decode.h), which the host decoder uses too; plaid_tables_ok there is the check of a compressed view.
 //
 // THE DECODED ROW (one definition, plaid_bucket / plaid_sumsq8 / the pairwise tree / plaid_finish8 of plaid_decode.h, compiled for both sides):
 //   element e lies in residual byte e / (8 / nbits), group g = e % (8 / nbits) counted from the most significant end;
@@ -252,89 +255,47 @@ hipError_t rr_launch_bank_ingest(const void* src, int src_f16, const float* mask
 }
 
 // one segment (n pairs, S context rows each) of rr_forward_interaction_bank: li16 [n][Lq + S][D] in the operand type dt,
-// qmask_out [n][Lq], cmask_out [n][S]; q32_out [n][Lq][D] / c32_out [n][S][D] float32 or both null (no attention fusion)
+// qmask_out [n][Lq], cmask_out [n][S]; q32_out [n][Lq][D] / c32_out [n][S][D] float32 or both null (no attention fusion).  The
+// context rows come from `bank`: bank_gather_kernel on fp16 rows, bank_gather_plaid_kernel on a compressed bank's tables
 hipError_t rr_launch_bank_gather(const rr_bank_pair* pairs, int n, int Lq, int S, int D, const float* query_li,
-                                 const float* query_mask, const uint16_t* rows, const uint8_t* mask_bytes, bf16_t* li16, int dt,
-                                 float* qmask_out, float* cmask_out, float* q32_out, float* c32_out, hipStream_t st) {
+                                 const float* query_mask, const rr_bank_view& bank, bf16_t* li16, int dt, float* qmask_out,
+                                 float* cmask_out, float* q32_out, float* c32_out, hipStream_t st) {
   int lpr = 0, rpw = 0;
-  if (n <= 0 || Lq <= 0 || S <= 0 || !row_shape(D, &lpr, &rpw) || !pairs || !query_li || !query_mask || !rows || !mask_bytes ||
-      !li16 || !qmask_out || !cmask_out || (!q32_out) != (!c32_out))
+  if (n <= 0 || Lq <= 0 || S <= 0 || !row_shape(D, &lpr, &rpw) || !pairs || !query_li || !query_mask || !bank.mask || !li16 ||
+      !qmask_out || !cmask_out || (!q32_out) != (!c32_out))
     return hipErrorInvalidValue;
-  if ((((uintptr_t)query_li) | ((uintptr_t)rows) | ((uintptr_t)li16) | ((uintptr_t)q32_out) | ((uintptr_t)c32_out)) & 15)
-    return hipErrorInvalidValue;
+  if ((((uintptr_t)query_li) | ((uintptr_t)li16) | ((uintptr_t)q32_out) | ((uintptr_t)c32_out)) & 15) return hipErrorInvalidValue;
+  if (bank.nbits ? !plaid_tables_ok(bank, D) : (!bank.rows || (((uintptr_t)bank.rows) & 15))) return hipErrorInvalidValue;
   const long long n_rows = (long long)n * (Lq + S), per_block = 4LL * rpw, blocks = (n_rows + per_block - 1) / per_block;
   if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  if (dt)
-    hipLaunchKernelGGL(bank_gather_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, pairs, n, Lq, S, D, lpr, rpw, query_li,
-                       query_mask, rows, mask_bytes, li16, qmask_out, cmask_out, q32_out, c32_out);
-  else
-    hipLaunchKernelGGL(bank_gather_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, st, pairs, n, Lq, S, D, lpr, rpw, query_li,
-                       query_mask, rows, mask_bytes, li16, qmask_out, cmask_out, q32_out, c32_out);
+  // the two kernels take the same arguments but for where a context row comes from (src)
+  auto run = [&](auto kernel, auto... src) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, pairs, n, Lq, S, D, lpr, rpw, query_li, query_mask, src...,
+                       bank.mask, li16, qmask_out, cmask_out, q32_out, c32_out);
+  };
+  auto plaid = [&](auto dtc) {
+    plaid_with_nbits(bank.nbits, [&](auto nb) {
+      run(bank_gather_plaid_kernel<decltype(dtc)::value, decltype(nb)::value>, bank.codes, bank.resid, bank.centroids, bank.weights,
+          bank.n_centroids);
+    });
+  };
+  if (!bank.nbits) run(dt ? bank_gather_kernel<1> : bank_gather_kernel<0>, bank.rows);
+  else if (dt) plaid(std::integral_constant<int, 1>{});
+  else plaid(std::integral_constant<int, 0>{});
   return hipGetLastError();
 }
 
-namespace {
-template <int DT>
-hipError_t gather_plaid_dt(int nbits, dim3 grid, hipStream_t st, const rr_bank_pair* pairs, int n, int Lq, int S, int D, int lpr, int rpw,
-                           const float* query_li, const float* query_mask, const int32_t* codes, const uint8_t* resid,
-                           const uint16_t* centroids, const float* weights, int C, const uint8_t* mask_bytes, bf16_t* li16,
-                           float* qmask_out, float* cmask_out, float* q32_out, float* c32_out) {
-#define RR_PLAID_GATHER(NB)                                                                                                          \
-  hipLaunchKernelGGL((bank_gather_plaid_kernel<DT, NB>), grid, dim3(256), 0, st, pairs, n, Lq, S, D, lpr, rpw, query_li, query_mask, \
-                     codes, resid, centroids, weights, C, mask_bytes, li16, qmask_out, cmask_out, q32_out, c32_out)
-  switch (nbits) {
-    case 1: RR_PLAID_GATHER(1); break;
-    case 2: RR_PLAID_GATHER(2); break;
-    case 4: RR_PLAID_GATHER(4); break;
-    case 8: RR_PLAID_GATHER(8); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef RR_PLAID_GATHER
-  return hipGetLastError();
-}
-}  // namespace
-
-// rr_launch_bank_gather over a compressed bank: codes [rows] int32, resid [rows][D * nbits / 8], centroids [C][D] fp16 bits, weights
-// [2^nbits] float32, all on the device
-hipError_t rr_launch_bank_gather_plaid(const rr_bank_pair* pairs, int n, int Lq, int S, int D, const float* query_li,
-                                       const float* query_mask, int nbits, const int32_t* codes, const uint8_t* resid,
-                                       const uint16_t* centroids, const float* weights, int C, const uint8_t* mask_bytes, bf16_t* li16,
-                                       int dt, float* qmask_out, float* cmask_out, float* q32_out, float* c32_out, hipStream_t st) {
+// rows [first_row, first_row + n_rows) of a compressed bank's (codes, resid) decoded into out [n_rows][D] fp16 bits, all on the device
+hipError_t rr_launch_plaid_decode(const rr_bank_view& bank, int D, long long first_row, long long n_rows, uint16_t* out, hipStream_t st) {
   int lpr = 0, rpw = 0;
-  if (n <= 0 || Lq <= 0 || S <= 0 || !plaid_shape(nbits, D) || !row_shape(D, &lpr, &rpw) || C <= 0 || !pairs || !query_li || !query_mask ||
-      !codes || !resid || !centroids || !weights || !mask_bytes || !li16 || !qmask_out || !cmask_out || (!q32_out) != (!c32_out))
+  if (!plaid_tables_ok(bank, D) || !row_shape(D, &lpr, &rpw) || first_row < 0 || n_rows <= 0 || !out || (((uintptr_t)out) & 15))
     return hipErrorInvalidValue;
-  if ((((uintptr_t)query_li) | ((uintptr_t)centroids) | ((uintptr_t)li16) | ((uintptr_t)q32_out) | ((uintptr_t)c32_out)) & 15)
-    return hipErrorInvalidValue;
-  if ((((uintptr_t)resid) & 7) || (((uintptr_t)codes) & 3)) return hipErrorInvalidValue;      // a lane loads nbits <= 8 bytes at once
-  const long long n_rows = (long long)n * (Lq + S), per_block = 4LL * rpw, blocks = (n_rows + per_block - 1) / per_block;
-  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  return dt ? gather_plaid_dt<1>(nbits, dim3((unsigned)blocks), st, pairs, n, Lq, S, D, lpr, rpw, query_li, query_mask, codes, resid,
-                                 centroids, weights, C, mask_bytes, li16, qmask_out, cmask_out, q32_out, c32_out)
-            : gather_plaid_dt<0>(nbits, dim3((unsigned)blocks), st, pairs, n, Lq, S, D, lpr, rpw, query_li, query_mask, codes, resid,
-                                 centroids, weights, C, mask_bytes, li16, qmask_out, cmask_out, q32_out, c32_out);
-}
-
-// rows [first_row, first_row + n_rows) of (codes, resid) decoded into out [n_rows][D] fp16 bits, all on the device
-hipError_t rr_launch_plaid_decode(const uint16_t* centroids, int C, const float* weights, int nbits, int D, const int32_t* codes,
-                                  const uint8_t* resid, long long first_row, long long n_rows, uint16_t* out, hipStream_t st) {
-  int lpr = 0, rpw = 0;
-  if (!plaid_shape(nbits, D) || !row_shape(D, &lpr, &rpw) || C <= 0 || first_row < 0 || n_rows <= 0 || !centroids || !weights || !codes ||
-      !resid || !out)
-    return hipErrorInvalidValue;
-  if (((((uintptr_t)centroids) | ((uintptr_t)out)) & 15) || (((uintptr_t)resid) & 7) || (((uintptr_t)codes) & 3)) return hipErrorInvalidValue;
   const long long per_block = 4LL * rpw, blocks = (n_rows + per_block - 1) / per_block;
   if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-#define RR_PLAID_DECODE(NB)                                                                                                      \
-  hipLaunchKernelGGL(bank_decode_plaid_kernel<NB>, dim3((unsigned)blocks), dim3(256), 0, st, codes, resid, centroids, weights, C, \
-                     first_row, n_rows, D, lpr, rpw, out)
-  switch (nbits) {
-    case 1: RR_PLAID_DECODE(1); break;
-    case 2: RR_PLAID_DECODE(2); break;
-    case 4: RR_PLAID_DECODE(4); break;
-    default: RR_PLAID_DECODE(8); break;
-  }
-#undef RR_PLAID_DECODE
+  plaid_with_nbits(bank.nbits, [&](auto nb) {
+    hipLaunchKernelGGL(bank_decode_plaid_kernel<decltype(nb)::value>, dim3((unsigned)blocks), dim3(256), 0, st, bank.codes, bank.resid,
+                       bank.centroids, bank.weights, bank.n_centroids, first_row, n_rows, D, lpr, rpw, out);
+  });
   return hipGetLastError();
 }
 
@@ -346,11 +307,8 @@ bool rr_plaid_decode_rows_host(const uint16_t* centroids, int C, const float* we
   if (!plaid_shape(nbits, D) || C <= 0) return false;
   for (long long i = 0; i < n_rows; ++i)
     if (codes[i] < 0 || codes[i] >= C) return false;
-  switch (nbits) {
-    case 1: plaid_decode_rows_host<1>(centroids, C, weights, D, codes, resid, n_rows, out); break;
-    case 2: plaid_decode_rows_host<2>(centroids, C, weights, D, codes, resid, n_rows, out); break;
-    case 4: plaid_decode_rows_host<4>(centroids, C, weights, D, codes, resid, n_rows, out); break;
-    default: plaid_decode_rows_host<8>(centroids, C, weights, D, codes, resid, n_rows, out); break;
-  }
+  plaid_with_nbits(nbits, [&](auto nb) {
+    plaid_decode_rows_host<decltype(nb)::value>(centroids, C, weights, D, codes, resid, n_rows, out);
+  });
   return true;
 }

@@ -1,13 +1,33 @@
 // Row loaders and the PLAID residual decode of the passage bank, shared by the row kernels (passage_bank.hip) and the score
 // kernel that reads its context rows from a bank (li_scores.hip).  THE DECODED ROW is defined in passage_bank.hip's header
 // comment; plaid_bucket / plaid_sumsq8 / plaid_scale are compiled for both sides, plaid_load8 / plaid_finish8 are the one
-// device definition every kernel decodes with.
+// device definition every kernel decodes with.  plaid_with_nbits is the one place a runtime nbits becomes a template argument,
+// plaid_tables_ok what every launcher checks of a compressed rr_bank_view.
 #pragma once
+#include <type_traits>
+
 #include "rr_common.h"
 
 namespace {
 
 __device__ __forceinline__ uint32_t pack2h(float lo, float hi) { return pack2<1>(lo, hi); }
+
+// f(std::integral_constant<int, NBITS>) for nbits = 1, 2, 4 or 8 (rr_plaid_shape_ok has checked it; anything else takes 8)
+template <class F>
+inline auto plaid_with_nbits(int nbits, F&& f) {
+  switch (nbits) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    default: return f(std::integral_constant<int, 8>{});
+  }
+}
+
+// the tables of a compressed bank as a kernel reads them: 16-byte centroid chunks, nbits <= 8 residual bytes at once, int32 codes
+inline bool plaid_tables_ok(const rr_bank_view& v, int D) {
+  return rr_plaid_shape_ok(v.nbits, D) && v.n_centroids > 0 && v.codes && v.resid && v.centroids && v.weights &&
+         !(((uintptr_t)v.centroids) & 15) && !(((uintptr_t)v.resid) & 7) && !(((uintptr_t)v.codes) & 3);
+}
 
 // 8 consecutive elements of a source row as floats; SRC_F16: the row holds fp16 bits
 template <bool SRC_F16>

@@ -303,6 +303,10 @@ struct rr_bank {
   rr_model::AsmSlot slot[2];
   int next = 0;
 };
+// the one place an rr_bank becomes the row source the launchers take (rr_common.h)
+static rr_bank_view bank_view(const rr_bank* b) {
+  return rr_bank_view{b->nbits, b->n_centroids, b->rows, b->codes, b->resid, b->centroids, b->weights, b->mask};
+}
 
 namespace {
 
@@ -805,19 +809,17 @@ size_t layout(const rr_config& c, int n, int Bq, int S, bool vision, char* base,
 // kernel nodes: once a capture has been SEEN on this handle (pinned_blocks; every forward looks), an outgrown
 // block is not freed but retired until rr_destroy, so that replaying such a graph after a later, larger forward stays
 // valid (it computes in the old block).
-int capture_guard(rr_model* m, hipStream_t st, const char* what) {
+// capture_guard: RR_ERR_BAD_ARG when `st` is being captured, with the caller's sentence about `what` (CAP_*; null: no message).
+const char* const CAP_GROWS = "%s would have to grow during stream capture; call rr_reserve for the largest shape before capturing";
+const char* const CAP_STAGES = "%s cannot be captured into a graph (it stages its descriptors from the host)";
+int capture_guard(rr_model* m, hipStream_t st, const char* sentence, const char* what) {
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
-    m->pinned_blocks = true;
-    return fail(m, RR_ERR_BAD_ARG, "%s would have to grow during stream capture; call rr_reserve for the largest shape "
-                                   "before capturing", what);
-  }
-  return RR_OK;
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs == hipStreamCaptureStatusNone) return RR_OK;
+  return sentence ? fail(m, RR_ERR_BAD_ARG, sentence, what) : RR_ERR_BAD_ARG;
 }
 // every forward notes a capture in progress, also when nothing has to grow
 void note_capture(rr_model* m, hipStream_t st) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (!m->pinned_blocks && hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) m->pinned_blocks = true;
+  if (!m->pinned_blocks && capture_guard(m, st, nullptr, nullptr) != RR_OK) m->pinned_blocks = true;
 }
 int release_block(rr_model* m, void* p, hipStream_t st) {
   if (!p) return RR_OK;
@@ -826,19 +828,27 @@ int release_block(rr_model* m, void* p, hipStream_t st) {
   else RR_HIP(m, hipFree(p));
   return RR_OK;
 }
+// a grow-only device block of the handle (ws, adj, li_sc, search_blk, bank_blk); `what` names it in the refusal
+template <class T>
+int ensure_block(rr_model* m, T*& ptr, size_t& cap, size_t bytes, hipStream_t st, const char* what) {
+  if (bytes <= cap) return RR_OK;
+  if (const int rc = capture_guard(m, st, CAP_GROWS, what)) {
+    m->pinned_blocks = true;
+    return rc;
+  }
+  if (ptr) {
+    RR_TRY(release_block(m, ptr, st));
+    ptr = nullptr;
+    cap = 0;
+  }
+  RR_HIP(m, hipMalloc((void**)&ptr, bytes));
+  cap = bytes;
+  return RR_OK;
+}
 
 int ensure_ws(rr_model* m, size_t bytes, hipStream_t st) {
   note_capture(m, st);
-  if (bytes <= m->ws_cap) return RR_OK;
-  RR_TRY(capture_guard(m, st, "the workspace"));
-  if (m->ws) {
-    RR_TRY(release_block(m, m->ws, st));
-    m->ws = nullptr;
-    m->ws_cap = 0;
-  }
-  RR_HIP(m, hipMalloc((void**)&m->ws, bytes));
-  m->ws_cap = bytes;
-  return RR_OK;
+  return ensure_block(m, m->ws, m->ws_cap, bytes, st, "the workspace");
 }
 
 double gemm_flops(double M, double N, double K) { return 2.0 * M * N * K; }
@@ -1153,46 +1163,6 @@ int run_layer(rr_model* m, hipStream_t st, const LayerW& L, int batch, int Tseq,
                                    w.stats_b, m->dt, st));
   rs = ResidSrc{w.pre2, w.stats_b, L.ln2g, L.ln2b};
   in_kind = OP_NORMALISED;
-  return RR_OK;
-}
-
-// grow-only buffer of the attention-fusion bias [n][T][ld]
-int ensure_adj(rr_model* m, size_t bytes, hipStream_t st) {
-  if (bytes <= m->adj_cap) return RR_OK;
-  RR_TRY(capture_guard(m, st, "the attention-fusion bias buffer"));
-  if (m->adj) { RR_TRY(release_block(m, m->adj, st)); m->adj = nullptr; m->adj_cap = 0; }
-  RR_HIP(m, hipMalloc((void**)&m->adj, bytes));
-  m->adj_cap = bytes;
-  return RR_OK;
-}
-
-// grow-only score block of the *_fusion_li forwards [n][Lc][Lq] (what the caller of rr_forward_interaction_fusion holds itself)
-int ensure_li_scores(rr_model* m, size_t bytes, hipStream_t st) {
-  if (bytes <= m->li_sc_cap) return RR_OK;
-  RR_TRY(capture_guard(m, st, "the late-interaction score block"));
-  if (m->li_sc) { RR_TRY(release_block(m, m->li_sc, st)); m->li_sc = nullptr; m->li_sc_cap = 0; }
-  RR_HIP(m, hipMalloc((void**)&m->li_sc, bytes));
-  m->li_sc_cap = bytes;
-  return RR_OK;
-}
-
-// grow-only block of rr_bank_search (rr_model::search_blk)
-int ensure_search_blk(rr_model* m, size_t bytes, hipStream_t st) {
-  if (bytes <= m->search_blk_cap) return RR_OK;
-  RR_TRY(capture_guard(m, st, "the bank search's block"));
-  if (m->search_blk) { RR_TRY(release_block(m, m->search_blk, st)); m->search_blk = nullptr; m->search_blk_cap = 0; }
-  RR_HIP(m, hipMalloc((void**)&m->search_blk, bytes));
-  m->search_blk_cap = bytes;
-  return RR_OK;
-}
-
-// grow-only block of rr_forward_interaction_bank (rr_model::bank_blk)
-int ensure_bank_blk(rr_model* m, size_t bytes, hipStream_t st) {
-  if (bytes <= m->bank_blk_cap) return RR_OK;
-  RR_TRY(capture_guard(m, st, "the bank forward's block"));
-  if (m->bank_blk) { RR_TRY(release_block(m, m->bank_blk, st)); m->bank_blk = nullptr; m->bank_blk_cap = 0; }
-  RR_HIP(m, hipMalloc((void**)&m->bank_blk, bytes));
-  m->bank_blk_cap = bytes;
   return RR_OK;
 }
 
@@ -1710,9 +1680,9 @@ static int rr_reserve_impl(rr_handle h, int n_pairs, int n_queries, int len_a, i
   }
   RR_HIP(m, rr_attention_reserve(n_pairs, c.ce_heads, T, st));
   RR_TRY(ensure_ws(m, need, st));
-  if (with_fusion) RR_TRY(ensure_adj(m, (size_t)n_pairs * T * ((T + 63) / 64 * 64) * sizeof(float), st));
+  if (with_fusion) RR_TRY(ensure_block(m, m->adj, m->adj_cap, (size_t)n_pairs * T * ((T + 63) / 64 * 64) * sizeof(float), st, "the attention-fusion bias buffer"));
   if (with_fusion == 2 && c.model_kind == RR_MODEL_INTERACTION)      // the score block of rr_forward_interaction*_fusion_li
-    RR_TRY(ensure_li_scores(m, (size_t)n_pairs * len_b * len_a * sizeof(float), st));
+    RR_TRY(ensure_block(m, m->li_sc, m->li_sc_cap, (size_t)n_pairs * len_b * len_a * sizeof(float), st, "the late-interaction score block"));
   return RR_OK;
 }
 
@@ -1856,7 +1826,7 @@ static int fusion_bias(rr_model* m, hipStream_t st, const RowPlan& plan, const f
     const int T = Tq + Tc, rows = Tc + s_off, n = plan.n;
     *adj_ld = (T + 63) / 64 * 64;
     const size_t need = (size_t)n * T * *adj_ld * sizeof(float);
-    RR_TRY(ensure_adj(m, need, st));
+    RR_TRY(ensure_block(m, m->adj, m->adj_cap, need, st, "the attention-fusion bias buffer"));
     RR_RUN(m, st, RR_K_TAIL, 0.0, 4.0 * n * (double)rows * Tq + (double)need,
            rr_launch_fusion_adj(scores, rows, Tq, Tc, mult, pair_begin, n, m->adj, *adj_ld, st, row0));
     return RR_OK;
@@ -1872,7 +1842,7 @@ static int fusion_bias(rr_model* m, hipStream_t st, const RowPlan& plan, const f
     tk.push_back(g.S - s_off);
   }
   *adj_ld = 0;
-  RR_TRY(ensure_adj(m, need, st));
+  RR_TRY(ensure_block(m, m->adj, m->adj_cap, need, st, "the attention-fusion bias buffer"));
   RR_RUN(m, st, RR_K_TAIL, 0.0, rd + (double)need,
          rr_launch_fusion_adj_segs(scores, Tc, Tq, Tc, mult, (int)plan.segs.size(), sn.data(), tk.data(), m->adj, st, 0));
   return RR_OK;
@@ -1900,28 +1870,32 @@ static int packed_segments(rr_model* m, const char* what, Request& r, int min_le
   return RR_OK;
 }
 
-// The descriptor upload of rr_assemble_pairs / rr_assemble_joint: `bytes` of checked host descriptors into the next staging
-// slot (pinned), once the launch that last read that slot has completed, and an async copy to its device half on `st`.
-// asm_done records the slot's event behind the launch that reads it and hands the next call the other slot.
-static int asm_stage(rr_model* m, const char* what, const void* data, size_t bytes, hipStream_t st, void** dev) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-    return fail(m, RR_ERR_BAD_ARG, "%s cannot be captured into a graph (it stages its descriptors from the host)", what);
-  RR_HIP(m, hipSetDevice(m->cfg.device));
-  rr_model::AsmSlot& a = m->asm_slot[m->asm_next];
-  if (!a.done) RR_HIP(m, hipEventCreateWithFlags(&a.done, hipEventDisableTiming));
-  else RR_HIP(m, hipEventSynchronize(a.done));      // the last upload from this slot, and the launch that read it, are done
+// One staged upload: `bytes` of checked host descriptors into a staging slot (pinned host half, device half, at least min_cap
+// bytes each), once the launch that last read that slot has completed (its event), and an async copy to the device half on `st`.
+// The handle's slot pair (asm_stage) and a bank's (rr_bank_add) both go through here.
+static hipError_t stage_slot(rr_model::AsmSlot& a, const void* data, size_t bytes, size_t min_cap, hipStream_t st) {
+  hipError_t e = a.done ? hipEventSynchronize(a.done) : hipEventCreateWithFlags(&a.done, hipEventDisableTiming);
+  if (e != hipSuccess) return e;
   if (a.cap < bytes) {
-    if (a.host) { RR_HIP(m, hipHostFree(a.host)); a.host = nullptr; }
-    if (a.dev) { RR_HIP(m, hipFree(a.dev)); a.dev = nullptr; }
+    if (a.host) { if ((e = hipHostFree(a.host)) != hipSuccess) return e; a.host = nullptr; }
+    if (a.dev) { if ((e = hipFree(a.dev)) != hipSuccess) return e; a.dev = nullptr; }
     a.cap = 0;
-    const size_t cap = std::max(bytes, (size_t)1024 * sizeof(rr_asm_pair));
-    RR_HIP(m, hipHostMalloc(&a.host, cap, hipHostMallocDefault));
-    RR_HIP(m, hipMalloc(&a.dev, cap));
+    const size_t cap = std::max(bytes, min_cap);
+    if ((e = hipHostMalloc(&a.host, cap, hipHostMallocDefault)) != hipSuccess) return e;
+    if ((e = hipMalloc(&a.dev, cap)) != hipSuccess) return e;
     a.cap = cap;
   }
   memcpy(a.host, data, bytes);
-  RR_HIP(m, hipMemcpyAsync(a.dev, a.host, bytes, hipMemcpyHostToDevice, st));
+  return hipMemcpyAsync(a.dev, a.host, bytes, hipMemcpyHostToDevice, st);
+}
+
+// The descriptor upload of rr_assemble_pairs / rr_assemble_joint and of the bank calls of a handle: into the next of the handle's
+// two slots.  asm_done records the slot's event behind the launch that reads it and hands the next call the other slot.
+static int asm_stage(rr_model* m, const char* what, const void* data, size_t bytes, hipStream_t st, void** dev) {
+  RR_TRY(capture_guard(m, st, CAP_STAGES, what));
+  RR_HIP(m, hipSetDevice(m->cfg.device));
+  rr_model::AsmSlot& a = m->asm_slot[m->asm_next];
+  RR_HIP(m, stage_slot(a, data, bytes, (size_t)1024 * sizeof(rr_asm_pair), st));
   *dev = a.dev;
   return RR_OK;
 }
@@ -2052,6 +2026,13 @@ static int bfail(rr_bank* b, int code, const char* fmt, ...) noexcept {
       return bfail(b, e_ == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
   } while (0)
 
+// capture_guard for the calls that report through the bank
+static int bank_capture_guard(rr_bank* b, hipStream_t st, const char* sentence, const char* what) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs == hipStreamCaptureStatusNone) return RR_OK;
+  return bfail(b, RR_ERR_BAD_ARG, sentence, what);
+}
+
 static void bank_free(rr_bank* b) {
   if (b->rows) (void)hipFree(b->rows);
   if (b->mask) (void)hipFree(b->mask);
@@ -2068,6 +2049,43 @@ static void bank_free(rr_bank* b) {
   delete b;
 }
 
+// what rr_bank_create and rr_bank_create_plaid do behind their own argument checks: the bank of the handle's device and li_dim with
+// its device stores (nbits == 0: fp16 rows; else codes, residual bytes and the codec's tables copied from the host)
+static hipError_t bank_new(rr_handle h, int64_t capacity_rows, int32_t max_passages, int nbits, int32_t n_centroids,
+                           const uint16_t* centroids_f16, const float* bucket_weights, rr_bank_handle* out) {
+  rr_bank* b = new rr_bank();
+  b->device = h->cfg.device;
+  b->D = h->cfg.li_dim;
+  b->cap_rows = capacity_rows;
+  b->max_passages = max_passages;
+  b->nbits = nbits;
+  b->n_centroids = n_centroids;
+  const size_t cbytes = (size_t)n_centroids * b->D * sizeof(uint16_t), wbytes = ((size_t)1 << nbits) * sizeof(float);
+  hipError_t e;
+  if (nbits) {
+    e = hipMalloc((void**)&b->codes, (size_t)capacity_rows * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->resid, (size_t)capacity_rows * b->resid_row_bytes());
+  } else {
+    e = hipMalloc((void**)&b->rows, (size_t)capacity_rows * b->D * sizeof(uint16_t));
+  }
+  if (e == hipSuccess) e = hipMalloc((void**)&b->mask, (size_t)capacity_rows);
+  if (nbits) {
+    if (e == hipSuccess) e = hipMalloc((void**)&b->centroids, cbytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&b->weights, wbytes);
+    if (e == hipSuccess) e = hipMemcpy(b->centroids, centroids_f16, cbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(b->weights, bucket_weights, wbytes, hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    bank_free(b);
+    return e;
+  }
+  b->first.reserve((size_t)std::min<int64_t>(max_passages, 1 << 20));
+  b->len.reserve((size_t)std::min<int64_t>(max_passages, 1 << 20));
+  *out = b;
+  return hipSuccess;
+}
+
 static int rr_bank_create_impl(rr_handle h, int64_t capacity_rows, int32_t max_passages, rr_bank_handle* out) {
   if (!h) return RR_ERR_BAD_ARG;
   if (!out) return fail(h, RR_ERR_BAD_ARG, "rr_bank_create: null out");
@@ -2078,22 +2096,10 @@ static int rr_bank_create_impl(rr_handle h, int64_t capacity_rows, int32_t max_p
   if (capacity_rows <= 0 || max_passages <= 0 || capacity_rows > (1LL << 40))
     return fail(h, RR_ERR_BAD_SHAPE, "rr_bank_create: capacity_rows=%lld max_passages=%d", (long long)capacity_rows, max_passages);
   RR_HIP(h, hipSetDevice(h->cfg.device));
-  rr_bank* b = new rr_bank();
-  b->device = h->cfg.device;
-  b->D = D;
-  b->cap_rows = capacity_rows;
-  b->max_passages = max_passages;
-  hipError_t e = hipMalloc((void**)&b->rows, (size_t)capacity_rows * D * sizeof(uint16_t));
-  if (e == hipSuccess) e = hipMalloc((void**)&b->mask, (size_t)capacity_rows);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    bank_free(b);
+  const hipError_t e = bank_new(h, capacity_rows, max_passages, 0, 0, nullptr, nullptr, out);
+  if (e != hipSuccess)
     return fail(h, e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP, "rr_bank_create: %lld rows of %d: %s", (long long)capacity_rows, D,
                 hipGetErrorString(e));
-  }
-  b->first.reserve((size_t)std::min<int64_t>(max_passages, 1 << 20));
-  b->len.reserve((size_t)std::min<int64_t>(max_passages, 1 << 20));
-  *out = b;
   return RR_OK;
 }
 
@@ -2103,6 +2109,34 @@ static int rr_bank_destroy_impl(rr_bank* b) {
   (void)hipDeviceSynchronize();
   bank_free(b);
   return RR_OK;
+}
+
+// Admission of n passages, shared by both kinds of add: every length in 1 .. max_len (0: no upper bound), *rows their sum, and
+// the bank's slot and row limits.
+static int bank_admit(rr_bank* b, const char* what, const int32_t* lengths, int n, int max_len, int64_t* rows) {
+  *rows = 0;
+  for (int i = 0; i < n; ++i) {
+    if (lengths[i] < 1 || (max_len && lengths[i] > max_len))
+      return max_len ? bfail(b, RR_ERR_BAD_SHAPE, "%s: passage %d has length %d (1..%d)", what, i, lengths[i], max_len)
+                     : bfail(b, RR_ERR_BAD_SHAPE, "%s: passage %d has length %d (at least 1)", what, i, lengths[i]);
+    *rows += lengths[i];
+  }
+  const int64_t have = (int64_t)b->first.size();
+  if (have + n > b->max_passages)
+    return bfail(b, RR_ERR_OOM, "%s: %lld + %d passages exceed the bank's %d slots", what, (long long)have, n, b->max_passages);
+  if (b->used_rows + *rows > b->cap_rows)
+    return bfail(b, RR_ERR_OOM, "%s: %lld + %lld rows exceed the bank's %lld", what, (long long)b->used_rows, (long long)*rows,
+                 (long long)b->cap_rows);
+  return RR_OK;
+}
+// ... and once their rows are on their way: the admitted passages appended to the host table, back to back from used_rows on
+static void bank_append(rr_bank* b, const int32_t* lengths, int n, int32_t* first_index_out) {
+  if (first_index_out) *first_index_out = (int32_t)b->first.size();
+  for (int i = 0; i < n; ++i) {
+    b->first.push_back(b->used_rows);
+    b->len.push_back(lengths[i]);
+    b->used_rows += lengths[i];
+  }
 }
 
 // every check on the host first; then one staged upload of the (first row, length) slots and one launch
@@ -2116,21 +2150,9 @@ static int rr_bank_add_impl(rr_bank* b, const void* context_li, int dtype, const
   if (((uintptr_t)context_li) & 15) return bfail(b, RR_ERR_BAD_ARG, "%s: context_li must be 16-byte aligned", what);
   if (n <= 0 || Lc <= 0 || (long long)n * Lc > (1LL << 40)) return bfail(b, RR_ERR_BAD_SHAPE, "%s: n=%d Lc=%d", what, n, Lc);
   int64_t rows = 0;
-  for (int i = 0; i < n; ++i) {
-    if (lengths[i] < 1 || lengths[i] > Lc)
-      return bfail(b, RR_ERR_BAD_SHAPE, "%s: passage %d has length %d (1..%d)", what, i, lengths[i], Lc);
-    rows += lengths[i];
-  }
-  const int64_t have = (int64_t)b->first.size();
-  if (have + n > b->max_passages)
-    return bfail(b, RR_ERR_OOM, "%s: %lld + %d passages exceed the bank's %d slots", what, (long long)have, n, b->max_passages);
-  if (b->used_rows + rows > b->cap_rows)
-    return bfail(b, RR_ERR_OOM, "%s: %lld + %lld rows exceed the bank's %lld", what, (long long)b->used_rows, (long long)rows,
-                 (long long)b->cap_rows);
+  RR_TRY(bank_admit(b, what, lengths, n, Lc, &rows));
   hipStream_t st = (hipStream_t)hip_stream;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-    return bfail(b, RR_ERR_BAD_ARG, "%s cannot be captured into a graph (it stages its descriptors from the host)", what);
+  RR_TRY(bank_capture_guard(b, st, CAP_STAGES, what));
   std::vector<rr_bank_slot> staged((size_t)n);
   int64_t row = b->used_rows;
   for (int i = 0; i < n; ++i) {
@@ -2139,29 +2161,11 @@ static int rr_bank_add_impl(rr_bank* b, const void* context_li, int dtype, const
   }
   RR_BHIP(b, hipSetDevice(b->device));
   rr_model::AsmSlot& a = b->slot[b->next];
-  const size_t bytes = staged.size() * sizeof(rr_bank_slot);
-  if (!a.done) RR_BHIP(b, hipEventCreateWithFlags(&a.done, hipEventDisableTiming));
-  else RR_BHIP(b, hipEventSynchronize(a.done));      // the launch that last read this slot is done
-  if (a.cap < bytes) {
-    if (a.host) { RR_BHIP(b, hipHostFree(a.host)); a.host = nullptr; }
-    if (a.dev) { RR_BHIP(b, hipFree(a.dev)); a.dev = nullptr; }
-    a.cap = 0;
-    const size_t cap = std::max(bytes, (size_t)1024 * sizeof(rr_bank_slot));
-    RR_BHIP(b, hipHostMalloc(&a.host, cap, hipHostMallocDefault));
-    RR_BHIP(b, hipMalloc(&a.dev, cap));
-    a.cap = cap;
-  }
-  memcpy(a.host, staged.data(), bytes);
-  RR_BHIP(b, hipMemcpyAsync(a.dev, a.host, bytes, hipMemcpyHostToDevice, st));
+  RR_BHIP(b, stage_slot(a, staged.data(), staged.size() * sizeof(rr_bank_slot), (size_t)1024 * sizeof(rr_bank_slot), st));
   RR_BHIP(b, rr_launch_bank_ingest(context_li, dtype == RR_F16, context_mask, (const rr_bank_slot*)a.dev, n, Lc, b->D, b->rows, b->mask, st));
   RR_BHIP(b, hipEventRecord(a.done, st));
   b->next ^= 1;
-  for (int i = 0; i < n; ++i) {
-    b->first.push_back(staged[(size_t)i].first_row);
-    b->len.push_back(lengths[i]);
-  }
-  b->used_rows = row;
-  if (first_index_out) *first_index_out = (int32_t)have;
+  bank_append(b, lengths, n, first_index_out);
   return RR_OK;
 }
 
@@ -2182,30 +2186,10 @@ static int rr_bank_create_plaid_impl(rr_handle h, int64_t capacity_rows, int32_t
     return fail(h, RR_ERR_BAD_SHAPE, "%s: capacity_rows=%lld max_passages=%d n_centroids=%d", what, (long long)capacity_rows, max_passages,
                 n_centroids);
   RR_HIP(h, hipSetDevice(h->cfg.device));
-  rr_bank* b = new rr_bank();
-  b->device = h->cfg.device;
-  b->D = D;
-  b->cap_rows = capacity_rows;
-  b->max_passages = max_passages;
-  b->nbits = nbits;
-  b->n_centroids = n_centroids;
-  const size_t cbytes = (size_t)n_centroids * D * sizeof(uint16_t), wbytes = ((size_t)1 << nbits) * sizeof(float);
-  hipError_t e = hipMalloc((void**)&b->codes, (size_t)capacity_rows * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc((void**)&b->resid, (size_t)capacity_rows * b->resid_row_bytes());
-  if (e == hipSuccess) e = hipMalloc((void**)&b->mask, (size_t)capacity_rows);
-  if (e == hipSuccess) e = hipMalloc((void**)&b->centroids, cbytes);
-  if (e == hipSuccess) e = hipMalloc((void**)&b->weights, wbytes);
-  if (e == hipSuccess) e = hipMemcpy(b->centroids, centroids_f16, cbytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(b->weights, bucket_weights, wbytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    bank_free(b);
+  const hipError_t e = bank_new(h, capacity_rows, max_passages, nbits, n_centroids, centroids_f16, bucket_weights, out);
+  if (e != hipSuccess)
     return fail(h, e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP, "%s: %lld rows of %d at %d bits, %d centroids: %s", what,
                 (long long)capacity_rows, D, nbits, n_centroids, hipGetErrorString(e));
-  }
-  b->first.reserve((size_t)std::min<int64_t>(max_passages, 1 << 20));
-  b->len.reserve((size_t)std::min<int64_t>(max_passages, 1 << 20));
-  *out = b;
   return RR_OK;
 }
 
@@ -2218,23 +2202,12 @@ static int rr_bank_add_plaid_impl(rr_bank* b, const int32_t* codes, const uint8_
   if (!codes || !residuals || !lengths) return bfail(b, RR_ERR_BAD_ARG, "%s: null argument", what);
   if (n <= 0) return bfail(b, RR_ERR_BAD_SHAPE, "%s: n=%d", what, n);
   int64_t rows = 0;
-  for (int i = 0; i < n; ++i) {
-    if (lengths[i] < 1) return bfail(b, RR_ERR_BAD_SHAPE, "%s: passage %d has length %d (at least 1)", what, i, lengths[i]);
-    rows += lengths[i];
-  }
-  const int64_t have = (int64_t)b->first.size();
-  if (have + n > b->max_passages)
-    return bfail(b, RR_ERR_OOM, "%s: %lld + %d passages exceed the bank's %d slots", what, (long long)have, n, b->max_passages);
-  if (b->used_rows + rows > b->cap_rows)
-    return bfail(b, RR_ERR_OOM, "%s: %lld + %lld rows exceed the bank's %lld", what, (long long)b->used_rows, (long long)rows,
-                 (long long)b->cap_rows);
+  RR_TRY(bank_admit(b, what, lengths, n, 0, &rows));
   for (int64_t i = 0; i < rows; ++i)               // behind the capacity check: rows is bounded by it here
     if (codes[i] < 0 || codes[i] >= b->n_centroids)
       return bfail(b, RR_ERR_BAD_SHAPE, "%s: row %lld has centroid code %d, the codec %d centroids", what, (long long)i, codes[i], b->n_centroids);
   hipStream_t st = (hipStream_t)hip_stream;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-    return bfail(b, RR_ERR_BAD_ARG, "%s cannot be captured into a graph (it copies from host memory and synchronises)", what);
+  RR_TRY(bank_capture_guard(b, st, "%s cannot be captured into a graph (it copies from host memory and synchronises)", what));
   RR_BHIP(b, hipSetDevice(b->device));
   const int64_t r0 = b->used_rows;
   const size_t rb = b->resid_row_bytes();
@@ -2243,14 +2216,7 @@ static int rr_bank_add_plaid_impl(rr_bank* b, const int32_t* codes, const uint8_
   if (mask) RR_BHIP(b, hipMemcpyAsync(b->mask + r0, mask, (size_t)rows, hipMemcpyHostToDevice, st));
   else RR_BHIP(b, hipMemsetAsync(b->mask + r0, 1, (size_t)rows, st));
   RR_BHIP(b, hipStreamSynchronize(st));            // the host buffers are the caller's again
-  int64_t row = r0;
-  for (int i = 0; i < n; ++i) {
-    b->first.push_back(row);
-    b->len.push_back(lengths[i]);
-    row += lengths[i];
-  }
-  b->used_rows = row;
-  if (first_index_out) *first_index_out = (int32_t)have;
+  bank_append(b, lengths, n, first_index_out);
   return RR_OK;
 }
 
@@ -2262,8 +2228,8 @@ static int rr_op_plaid_decode_rows_impl(const uint16_t* centroids_f16, int32_t n
   if (n_centroids <= 0 || first_row < 0 || n_rows <= 0 || first_row > (1LL << 40) || n_rows > (1LL << 40)) return RR_ERR_BAD_SHAPE;
   if (((((uintptr_t)centroids_f16) | ((uintptr_t)rows_out_f16)) & 15) || (((uintptr_t)residuals) & 7) || (((uintptr_t)codes) & 3))
     return RR_ERR_BAD_ARG;
-  const hipError_t e = rr_launch_plaid_decode(centroids_f16, n_centroids, bucket_weights, nbits, D, codes, residuals, first_row, n_rows,
-                                              rows_out_f16, (hipStream_t)hip_stream);
+  const rr_bank_view bank{nbits, n_centroids, nullptr, codes, residuals, centroids_f16, bucket_weights, nullptr};
+  const hipError_t e = rr_launch_plaid_decode(bank, D, first_row, n_rows, rows_out_f16, (hipStream_t)hip_stream);
   return e == hipSuccess ? RR_OK : RR_ERR_HIP;
 }
 
@@ -2280,8 +2246,7 @@ static int rr_bank_read_impl(rr_bank* b, int32_t index, uint16_t* rows_out, uint
     const size_t bytes = (size_t)len * b->D * sizeof(uint16_t);
     uint16_t* tmp = nullptr;
     RR_BHIP(b, hipMalloc((void**)&tmp, bytes));
-    hipError_t e = rr_launch_plaid_decode(b->centroids, b->n_centroids, b->weights, b->nbits, b->D, b->codes, b->resid, r0, len, tmp,
-                                          (hipStream_t)hip_stream);
+    hipError_t e = rr_launch_plaid_decode(bank_view(b), b->D, r0, len, tmp, (hipStream_t)hip_stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)hip_stream);
     if (e == hipSuccess) e = hipMemcpy(rows_out, tmp, bytes, hipMemcpyDeviceToHost);
     (void)hipFree(tmp);
@@ -2546,25 +2511,19 @@ static int forward_interaction(rr_handle h, Request r) {
     auto take = [&off](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
     const size_t o_cm = take((size_t)C * 4), o_qm = take((size_t)n * Lq * 4);
     const size_t o_c32 = r.fusion_from_li ? take((size_t)C * D * 4) : 0, o_q32 = r.fusion_from_li ? take((size_t)n * Lq * D * 4) : 0;
-    RR_TRY(ensure_bank_blk(m, off, st));
+    RR_TRY(ensure_block(m, m->bank_blk, m->bank_blk_cap, off, st, "the bank forward's block"));
     float *cm_w = (float*)(m->bank_blk + o_cm), *qm_w = (float*)(m->bank_blk + o_qm);
     float* c32 = r.fusion_from_li ? (float*)(m->bank_blk + o_c32) : nullptr;
     float* q32 = r.fusion_from_li ? (float*)(m->bank_blk + o_q32) : nullptr;
     void* dev = nullptr;
     RR_TRY(asm_stage(m, "rr_forward_interaction_bank", r.bank_pairs->data(), r.bank_pairs->size() * sizeof(rr_bank_pair), st, &dev));
+    // bytes of a context row: what the bank's row costs (compressed rows are decoded in the gather), its 16-bit copy, its float32 copy
+    const rr_bank_view bank = bank_view(r.bank);
+    const double ctx_row = rr_bank_row_bytes(bank, D) + D * (2.0 + (c32 ? 4.0 : 0.0));
     for (const Seg& g : segs)
-      if (r.bank->nbits)       // compressed rows (code + residual bytes + the centroid chunk from L2) are decoded in the gather
-        RR_RUN(m, st, RR_K_TAIL, 0.0, (double)g.n * (Lq * D * (4.0 + 2.0 + (q32 ? 4.0 : 0.0)) +
-                                                    (double)g.S * (4.0 + D * (r.bank->nbits / 8.0 + 2.0 + 2.0 + (c32 ? 4.0 : 0.0)))),
-               rr_launch_bank_gather_plaid((const rr_bank_pair*)dev + g.p0, g.n, Lq, g.S, D, r.query_li, r.query_mask, r.bank->nbits,
-                                           r.bank->codes, r.bank->resid, r.bank->centroids, r.bank->weights, r.bank->n_centroids,
-                                           r.bank->mask, w.li16 + g.rt0 * D, m->dt, qm_w + g.p0 * Lq, cm_w + g.r0,
-                                           q32 ? q32 + g.p0 * Lq * D : nullptr, c32 ? c32 + g.r0 * D : nullptr, st));
-      else
-      RR_RUN(m, st, RR_K_TAIL, 0.0, (double)g.n * (Lq * D * (4.0 + 2.0 + (q32 ? 4.0 : 0.0)) + (double)g.S * D * (2.0 + 2.0 + (c32 ? 4.0 : 0.0))),
-             rr_launch_bank_gather((const rr_bank_pair*)dev + g.p0, g.n, Lq, g.S, D, r.query_li, r.query_mask, r.bank->rows,
-                                   r.bank->mask, w.li16 + g.rt0 * D, m->dt, qm_w + g.p0 * Lq, cm_w + g.r0,
-                                   q32 ? q32 + g.p0 * Lq * D : nullptr, c32 ? c32 + g.r0 * D : nullptr, st));
+      RR_RUN(m, st, RR_K_TAIL, 0.0, (double)g.n * (Lq * D * (4.0 + 2.0 + (q32 ? 4.0 : 0.0)) + (double)g.S * ctx_row),
+             rr_launch_bank_gather((const rr_bank_pair*)dev + g.p0, g.n, Lq, g.S, D, r.query_li, r.query_mask, bank, w.li16 + g.rt0 * D, m->dt,
+                                   qm_w + g.p0 * Lq, cm_w + g.r0, q32 ? q32 + g.p0 * Lq * D : nullptr, c32 ? c32 + g.r0 * D : nullptr, st));
     RR_TRY(asm_done(m, st));
     cm = cm_w;
     qm = qm_w;
@@ -2597,7 +2556,7 @@ static int forward_interaction(rr_handle h, Request r) {
     if (r.fusion_from_li) {
       // the retriever's scores_raw of the slice (flmr_utils.py:22-48) into the handle's block [n][Lc][Lq], then as the padded
       // call with explicit scores; a packed pair's rows beyond its segment are masked rows of the padded matrix
-      RR_TRY(ensure_li_scores(m, (size_t)n * Lc * Lq * sizeof(float), st));
+      RR_TRY(ensure_block(m, m->li_sc, m->li_sc_cap, (size_t)n * Lc * Lq * sizeof(float), st, "the late-interaction score block"));
       float* ms = r.maxsim ? r.maxsim + pair_begin : nullptr;
       for (const Seg& g : segs)
         RR_RUN(m, st, RR_K_TAIL, 2.0 * g.n * (double)g.S * Lq * D, 4.0 * g.n * ((double)g.S * D + (double)Lc * Lq),
@@ -2665,6 +2624,27 @@ static int forward_interaction(rr_handle h, Request r) {
   return range_guard_exit(m, st);
 }
 
+// What every call that reads a bank through a handle asks first: an interaction model, bank and handle on one device, rows of li_dim.
+static int bank_usable(rr_model* m, const char* what, const rr_bank* b) {
+  const rr_config& c = m->cfg;
+  if (c.model_kind == RR_MODEL_FULL_CONTEXT) return fail(m, RR_ERR_BAD_ARG, "%s on a full-context model", what);
+  if (b->device != c.device) return fail(m, RR_ERR_BAD_ARG, "%s: the bank lives on device %d, the handle on %d", what, b->device, c.device);
+  if (b->D != c.li_dim) return fail(m, RR_ERR_BAD_SHAPE, "%s: the bank holds rows of %d, the handle's li_dim is %d", what, b->D, c.li_dim);
+  return RR_OK;
+}
+// Pair i of a call, (passage pi of the bank, query qi of n_queries), as the checked descriptor the kernels take.  The passage must
+// fit `limit` rows; limit_is: how the caller's message names that limit.  Inlined: it runs once per pair of every call.
+__attribute__((always_inline)) static inline int bank_checked_pair(rr_model* m, const char* what, const rr_bank* b, long long i, int32_t pi, int32_t qi, int n_queries,
+                                    int limit, const char* limit_is, rr_bank_pair* out) {
+  const long long held = (long long)b->first.size();
+  if (pi < 0 || pi >= held) return fail(m, RR_ERR_BAD_SHAPE, "%s: pair %lld names passage %d, the bank holds %lld", what, i, pi, held);
+  if (qi < 0 || qi >= n_queries) return fail(m, RR_ERR_BAD_SHAPE, "%s: pair %lld names query %d of %d", what, i, qi, n_queries);
+  const int32_t len = b->len[(size_t)pi];
+  if (len > limit) return fail(m, RR_ERR_BAD_SHAPE, "%s: pair %lld: passage %d holds %d rows, %s %d", what, i, pi, len, limit_is, limit);
+  *out = rr_bank_pair{b->first[(size_t)pi], len, qi};
+  return RR_OK;
+}
+
 // rr_forward_interaction_bank (include/rerank_mi355.h): everything about the bank, the segment table and the per-pair indices is
 // checked here, on the host; forward_interaction then checks what it checks for a packed call, stages the descriptors and runs.
 static int forward_interaction_bank(rr_handle h, rr_bank* b, const float* query_li, const float* query_mask, int n_queries, int Lq,
@@ -2677,17 +2657,13 @@ static int forward_interaction_bank(rr_handle h, rr_bank* b, const float* query_
   const rr_config& c = m->cfg;
   if (!b || !query_li || !query_mask || !pair_passage || !pair_query || !seg_pairs || !seg_len || !logits_out)
     return fail(m, RR_ERR_BAD_ARG, "%s: null argument", what);
-  if (c.model_kind == RR_MODEL_FULL_CONTEXT) return fail(m, RR_ERR_BAD_ARG, "%s on a full-context model", what);
-  if (b->device != c.device) return fail(m, RR_ERR_BAD_ARG, "%s: the bank lives on device %d, the handle on %d", what, b->device, c.device);
-  if (b->D != c.li_dim) return fail(m, RR_ERR_BAD_SHAPE, "%s: the bank holds rows of %d, the handle's li_dim is %d", what, b->D, c.li_dim);
+  RR_TRY(bank_usable(m, what, b));
   if (fusion_from_li && c.model_kind == RR_MODEL_MORES)
     return fail(m, RR_ERR_UNSUPPORTED, "Attention adj is not implemented for MORES");   // mores_model.py:72-73
   if (maxsim_out && !fusion_from_li) return fail(m, RR_ERR_BAD_ARG, "%s: maxsim_out needs fusion_from_li", what);
   if (((uintptr_t)query_li) & 15) return fail(m, RR_ERR_BAD_ARG, "%s: query_li must be 16-byte aligned", what);
   hipStream_t st = (hipStream_t)hip_stream;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-    return fail(m, RR_ERR_BAD_ARG, "%s cannot be captured into a graph (it stages its descriptors from the host)", what);
+  RR_TRY(capture_guard(m, st, CAP_STAGES, what));
   if (n_queries <= 0 || Lq <= 0 || padded_context_len <= 0)
     return fail(m, RR_ERR_BAD_SHAPE, "%s: n_queries=%d Lq=%d padded_context_len=%d", what, n_queries, Lq, padded_context_len);
   if (n_segments <= 0 || n_segments > 64) return fail(m, RR_ERR_BAD_SHAPE, "%s: %d segments (1..64)", what, n_segments);
@@ -2699,18 +2675,11 @@ static int forward_interaction_bank(rr_handle h, rr_bank* b, const float* query_
     pairs += seg_pairs[s];
   }
   if (pairs > (1 << 24)) return fail(m, RR_ERR_BAD_SHAPE, "%s: %lld pairs", what, pairs);
-  const long long held = (long long)b->first.size();
   std::vector<rr_bank_pair> staged((size_t)pairs);
   size_t i = 0;
   for (int s = 0; s < n_segments; ++s)
-    for (int k = 0; k < seg_pairs[s]; ++k, ++i) {
-      const int32_t pi = pair_passage[i], qi = pair_query[i];
-      if (pi < 0 || pi >= held) return fail(m, RR_ERR_BAD_SHAPE, "%s: pair %zu names passage %d, the bank holds %lld", what, i, pi, held);
-      if (qi < 0 || qi >= n_queries) return fail(m, RR_ERR_BAD_SHAPE, "%s: pair %zu names query %d of %d", what, i, qi, n_queries);
-      if (b->len[(size_t)pi] > seg_len[s])
-        return fail(m, RR_ERR_BAD_SHAPE, "%s: pair %zu: passage %d holds %d rows, its segment %d", what, i, pi, b->len[(size_t)pi], seg_len[s]);
-      staged[i] = rr_bank_pair{b->first[(size_t)pi], b->len[(size_t)pi], qi};
-    }
+    for (int k = 0; k < seg_pairs[s]; ++k, ++i)
+      RR_TRY(bank_checked_pair(m, what, b, (long long)i, pair_passage[i], pair_query[i], n_queries, seg_len[s], "its segment", &staged[i]));
   Request r;
   r.family = FAM_INTERACTION; r.query_li = query_li; r.query_mask = query_mask;
   r.fusion_from_li = fusion_from_li != 0; r.maxsim = maxsim_out; r.fusion_mult = fusion_multiplier;
@@ -2757,9 +2726,7 @@ static int bank_li_scores_call(rr_handle h, rr_bank* b, const float* query_li, i
   const rr_config& c = m->cfg;
   if (!b || !query_li || !pair_passage || !pair_query) return fail(m, RR_ERR_BAD_ARG, "%s: null argument", what);
   if (!scores_out && !maxsim_out) return fail(m, RR_ERR_BAD_ARG, "%s: scores_out and maxsim_out are both null", what);
-  if (c.model_kind == RR_MODEL_FULL_CONTEXT) return fail(m, RR_ERR_BAD_ARG, "%s on a full-context model", what);
-  if (b->device != c.device) return fail(m, RR_ERR_BAD_ARG, "%s: the bank lives on device %d, the handle on %d", what, b->device, c.device);
-  if (b->D != c.li_dim) return fail(m, RR_ERR_BAD_SHAPE, "%s: the bank holds rows of %d, the handle's li_dim is %d", what, b->D, c.li_dim);
+  RR_TRY(bank_usable(m, what, b));
   const int D = c.li_dim;
   if (D % 16) return fail(m, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a multiple of 16)", what, D);
   if (((uintptr_t)query_li) & 15) return fail(m, RR_ERR_BAD_ARG, "%s: query_li must be 16-byte aligned", what);
@@ -2768,18 +2735,12 @@ static int bank_li_scores_call(rr_handle h, rr_bank* b, const float* query_li, i
                 padded_context_len);
   if (n_pairs > (1 << 24)) return fail(m, RR_ERR_BAD_SHAPE, "%s: %d pairs", what, n_pairs);
   RR_TRY(check_rows(m, what, n_pairs, padded_context_len));
-  const long long held = (long long)b->first.size();
   std::vector<rr_bank_pair> checked((size_t)n_pairs);
   double rows = 0.0;
   for (int i = 0; i < n_pairs; ++i) {
-    const int32_t pi = pair_passage[i], qi = pair_query[i];
-    if (pi < 0 || pi >= held) return fail(m, RR_ERR_BAD_SHAPE, "%s: pair %d names passage %d, the bank holds %lld", what, i, pi, held);
-    if (qi < 0 || qi >= n_queries) return fail(m, RR_ERR_BAD_SHAPE, "%s: pair %d names query %d of %d", what, i, qi, n_queries);
-    if (b->len[(size_t)pi] > padded_context_len)
-      return fail(m, RR_ERR_BAD_SHAPE, "%s: pair %d: passage %d holds %d rows, padded_context_len is %d", what, i, pi, b->len[(size_t)pi],
-                  padded_context_len);
-    checked[(size_t)i] = rr_bank_pair{b->first[(size_t)pi], b->len[(size_t)pi], qi};
-    rows += b->len[(size_t)pi];
+    RR_TRY(bank_checked_pair(m, what, b, i, pair_passage[i], pair_query[i], n_queries, padded_context_len, "padded_context_len is",
+                             &checked[(size_t)i]));
+    rows += checked[(size_t)i].len;
   }
   // one workgroup per pair, dispatched in launch order: the longest passages go first (stable, so equal lengths keep call order)
   // and every workgroup is told which output row is its pair's.  One upload: [n] descriptors in launch order, then [n] int32
@@ -2799,17 +2760,11 @@ static int bank_li_scores_call(rr_handle h, rr_bank* b, const float* query_li, i
   m->last_stream = st;
   // bytes: the rows that exist (a compressed row: its code, its residual bytes and the centroid row from L2), one mask byte per
   // row, the query block per pair, the outputs; pad rows cost their -9999 in the score block only
-  const double row_bytes = b->nbits ? 4.0 + D * (b->nbits / 8.0 + 2.0) : 2.0 * D;
-  const double bytes = rows * (row_bytes + 1.0) + (double)n_pairs * (16.0 + 4.0 * Lq * D) +
+  const rr_bank_view bank = bank_view(b);
+  const double bytes = rows * (rr_bank_row_bytes(bank, D) + 1.0) + (double)n_pairs * (16.0 + 4.0 * Lq * D) +
                        (scores_out ? 4.0 * n_pairs * (double)padded_context_len * Lq : 0.0) + (maxsim_out ? 4.0 * n_pairs : 0.0);
-  if (b->nbits)
-    RR_RUN(m, st, RR_K_TAIL, 2.0 * rows * Lq * D, bytes,
-           rr_launch_bank_li_scores_plaid((const rr_bank_pair*)dev, slot, n_pairs, Lq, padded_context_len, D, query_li, b->nbits, b->codes,
-                                          b->resid, b->centroids, b->weights, b->n_centroids, b->mask, scores_out, maxsim_out, st));
-  else
-    RR_RUN(m, st, RR_K_TAIL, 2.0 * rows * Lq * D, bytes,
-           rr_launch_bank_li_scores((const rr_bank_pair*)dev, slot, n_pairs, Lq, padded_context_len, D, query_li, b->rows, b->mask, scores_out,
-                                    maxsim_out, st));
+  RR_RUN(m, st, RR_K_TAIL, 2.0 * rows * Lq * D, bytes,
+         rr_launch_bank_li_scores((const rr_bank_pair*)dev, slot, n_pairs, Lq, padded_context_len, D, query_li, bank, scores_out, maxsim_out, st));
   return asm_done(m, st);
 }
 
@@ -2822,9 +2777,7 @@ static int bank_search_call(rr_handle h, rr_bank* b, const float* query_li, int 
   rr_model* m = h;
   const rr_config& c = m->cfg;
   if (!b || !query_li || !indices_out) return fail(m, RR_ERR_BAD_ARG, "%s: null argument", what);
-  if (c.model_kind == RR_MODEL_FULL_CONTEXT) return fail(m, RR_ERR_BAD_ARG, "%s on a full-context model", what);
-  if (b->device != c.device) return fail(m, RR_ERR_BAD_ARG, "%s: the bank lives on device %d, the handle on %d", what, b->device, c.device);
-  if (b->D != c.li_dim) return fail(m, RR_ERR_BAD_SHAPE, "%s: the bank holds rows of %d, the handle's li_dim is %d", what, b->D, c.li_dim);
+  RR_TRY(bank_usable(m, what, b));
   const int D = c.li_dim;
   if (D % 16) return fail(m, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a multiple of 16)", what, D);
   if (((uintptr_t)query_li) & 15) return fail(m, RR_ERR_BAD_ARG, "%s: query_li must be 16-byte aligned", what);
@@ -2839,9 +2792,7 @@ static int bank_search_call(rr_handle h, rr_bank* b, const float* query_li, int 
   if (k < 1 || k > n) return fail(m, RR_ERR_BAD_SHAPE, "%s: k=%d of %d passages", what, k, n);
   if (k > 1024) return fail(m, RR_ERR_UNSUPPORTED, "%s: k=%d (at most 1024: a selection pass keeps k of 4096)", what, k);
   hipStream_t st = (hipStream_t)hip_stream;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-    return fail(m, RR_ERR_BAD_ARG, "%s cannot be captured into a graph (it may upload the bank's passage table and grow its block)", what);
+  RR_TRY(capture_guard(m, st, "%s cannot be captured into a graph (it may upload the bank's passage table and grow its block)", what));
   RR_HIP(m, hipSetDevice(c.device));
   if (b->table_n < (size_t)held) {                  // the first search after an add
     if (b->table_cap < (size_t)held) {
@@ -2860,25 +2811,19 @@ static int bank_search_call(rr_handle h, rr_bank* b, const float* query_li, int 
   }
   const size_t sc_bytes = (((size_t)n_queries * n * sizeof(float)) + 15) & ~(size_t)15;
   const size_t tmp_bytes = ((rr_topk_select_scratch(n_queries, n, k) * sizeof(int32_t)) + 15) & ~(size_t)15;
-  RR_TRY(ensure_search_blk(m, sc_bytes + 2 * tmp_bytes, st));
+  RR_TRY(ensure_block(m, m->search_blk, m->search_blk_cap, sc_bytes + 2 * tmp_bytes, st, "the bank search's block"));
   float* sc = (float*)m->search_blk;
   int32_t* tmp_a = tmp_bytes ? (int32_t*)(m->search_blk + sc_bytes) : nullptr;
   int32_t* tmp_b = tmp_bytes ? (int32_t*)(m->search_blk + sc_bytes + tmp_bytes) : nullptr;
   m->last_stream = st;
   const size_t last = (size_t)first_passage + (size_t)n - 1;
   const double rows = (double)(b->first[last] + b->len[last] - b->first[(size_t)first_passage]);      // passages lie back to back
-  const double row_bytes = b->nbits ? 4.0 + D * (b->nbits / 8.0 + 2.0) : 2.0 * D;
+  const rr_bank_view bank = bank_view(b);
   // bytes: the range's rows and mask bytes once (the queries of a chunk run side by side), the table, the query block per
   // workgroup of 16 passages, one float per (query, passage)
-  const double bytes = rows * (row_bytes + 1.0) + 16.0 * n + (double)n_queries * (n / 16.0 + 1.0) * 4.0 * Lq * D + 4.0 * n_queries * (double)n;
-  const rr_bank_slot* table = b->table + first_passage;
-  if (b->nbits)
-    RR_RUN(m, st, RR_K_TAIL, 2.0 * n_queries * rows * Lq * D, bytes,
-           rr_launch_bank_search_scores_plaid(table, n, n_queries, Lq, D, query_li, b->nbits, b->codes, b->resid, b->centroids, b->weights,
-                                              b->n_centroids, b->mask, sc, st));
-  else
-    RR_RUN(m, st, RR_K_TAIL, 2.0 * n_queries * rows * Lq * D, bytes,
-           rr_launch_bank_search_scores(table, n, n_queries, Lq, D, query_li, b->rows, b->mask, sc, st));
+  const double bytes = rows * (rr_bank_row_bytes(bank, D) + 1.0) + 16.0 * n + (double)n_queries * (n / 16.0 + 1.0) * 4.0 * Lq * D + 4.0 * n_queries * (double)n;
+  RR_RUN(m, st, RR_K_TAIL, 2.0 * n_queries * rows * Lq * D, bytes,
+         rr_launch_bank_search_scores(b->table + first_passage, n, n_queries, Lq, D, query_li, bank, sc, st));
   RR_RUN(m, st, RR_K_TAIL, 0.0, 12.0 * n_queries * (double)n,
          rr_launch_topk_select(sc, n_queries, n, k, first_passage, tmp_a, tmp_b, indices_out, scores_out, st));
   return RR_OK;
@@ -2920,9 +2865,8 @@ static int rr_op_bank_search_impl(const float* query_li, int n_queries, int Lq, 
   float* sc = nullptr;
   if (hipMalloc((void**)&sc, (size_t)n_queries * n_passages * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return RR_ERR_OOM; }
   const rr_bank_slot* t = (const rr_bank_slot*)table + first_passage;
-  const hipError_t e = nbits ? rr_launch_bank_search_scores_plaid(t, n_passages, n_queries, Lq, D, query_li, nbits, codes, residuals, centroids_f16,
-                                                                  bucket_weights, n_centroids, mask_bytes, sc, st)
-                             : rr_launch_bank_search_scores(t, n_passages, n_queries, Lq, D, query_li, rows_f16, mask_bytes, sc, st);
+  const rr_bank_view bank{nbits, n_centroids, rows_f16, codes, residuals, centroids_f16, bucket_weights, mask_bytes};
+  const hipError_t e = rr_launch_bank_search_scores(t, n_passages, n_queries, Lq, D, query_li, bank, sc, st);
   int rc = e == hipSuccess ? op_select_with_scratch(sc, n_queries, n_passages, k, first_passage, indices_out, scores_out, st) : RR_ERR_HIP;
   if (hipStreamSynchronize(st) != hipSuccess && rc == RR_OK) rc = RR_ERR_HIP;
   (void)hipFree(sc);
@@ -3567,8 +3511,8 @@ int rr_op_bank_li_scores(const float* query_li, int Lq, int D, const void* pairs
   if (nbits ? (!codes || !residuals || !centroids_f16 || !bucket_weights) : !rows_f16) return RR_ERR_BAD_ARG;
   if (D <= 0 || D % 16 || (nbits && !rr_plaid_shape_ok(nbits, D))) return RR_ERR_UNSUPPORTED;
   if (Lq <= 0 || n_pairs <= 0 || padded_context_len <= 0 || (nbits && n_centroids <= 0)) return RR_ERR_BAD_SHAPE;
-  const hipError_t e = nbits ? rr_launch_bank_li_scores_plaid((const rr_bank_pair*)pairs, nullptr, n_pairs, Lq, padded_context_len, D, query_li, nbits, codes, residuals, centroids_f16, bucket_weights, n_centroids, mask_bytes, scores_out, maxsim_out, (hipStream_t)hip_stream)
-                             : rr_launch_bank_li_scores((const rr_bank_pair*)pairs, nullptr, n_pairs, Lq, padded_context_len, D, query_li, rows_f16, mask_bytes, scores_out, maxsim_out, (hipStream_t)hip_stream);
+  const rr_bank_view bank{nbits, n_centroids, rows_f16, codes, residuals, centroids_f16, bucket_weights, mask_bytes};
+  const hipError_t e = rr_launch_bank_li_scores((const rr_bank_pair*)pairs, nullptr, n_pairs, Lq, padded_context_len, D, query_li, bank, scores_out, maxsim_out, (hipStream_t)hip_stream);
   return e == hipSuccess ? RR_OK : RR_ERR_HIP;
 }
 int rr_li_scores(rr_handle h, const float* query_li, const float* context_li, const float* context_mask, int Bq, int K, int Lq, int Lc, int pair_begin, int pair_end, float* scores_out, float* maxsim_out, void* hip_stream) {

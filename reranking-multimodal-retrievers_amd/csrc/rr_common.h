@@ -449,34 +449,38 @@ struct rr_bank_slot { int64_t first_row; int32_t len, unused0; };
 struct rr_bank_pair { int64_t first_row; int32_t len, query; };
 hipError_t rr_launch_bank_ingest(const void* src, int src_f16, const float* mask, const rr_bank_slot* slots, int n, int Lc, int D,
                                  uint16_t* rows, uint8_t* mask_bytes, hipStream_t st);
+// The context rows of a bank as the launchers take them, fp16 or compressed (PLAID residual codes): nbits == 0: `rows` [.][D] fp16
+// bits; else codes [.] int32, resid [.][D * nbits / 8], centroids [n_centroids][D] fp16 bits, weights [2^nbits] float32.  mask:
+// one byte per row.  All on the device.  rr_api.hip builds it from an rr_bank (bank_view), the diagnostic operators from their
+// loose pointers; every launcher below decides between the two kinds inside.
+struct rr_bank_view {
+  int nbits, n_centroids;
+  const uint16_t* rows;
+  const int32_t* codes;
+  const uint8_t* resid;
+  const uint16_t* centroids;
+  const float* weights;
+  const uint8_t* mask;
+};
+// the bytes one context row costs a kernel that reads it (a compressed row: its code, its residual bytes and the centroid row from L2)
+inline double rr_bank_row_bytes(const rr_bank_view& v, int D) { return v.nbits ? 4.0 + D * (v.nbits / 8.0 + 2.0) : 2.0 * D; }
+// one segment of rr_forward_interaction_bank; a compressed bank's rows are decoded in the gather (passage_bank.hip)
 hipError_t rr_launch_bank_gather(const rr_bank_pair* pairs, int n, int Lq, int S, int D, const float* query_li,
-                                 const float* query_mask, const uint16_t* rows, const uint8_t* mask_bytes, bf16_t* li16, int dt,
-                                 float* qmask_out, float* cmask_out, float* q32_out, float* c32_out, hipStream_t st);
-// compressed (PLAID residual) bank: the gather that decodes, the stand-alone decode of a row range, the shape rule and the host
-// decoder that defines the bits (passage_bank.hip)
-hipError_t rr_launch_bank_gather_plaid(const rr_bank_pair* pairs, int n, int Lq, int S, int D, const float* query_li,
-                                       const float* query_mask, int nbits, const int32_t* codes, const uint8_t* resid,
-                                       const uint16_t* centroids, const float* weights, int C, const uint8_t* mask_bytes, bf16_t* li16,
-                                       int dt, float* qmask_out, float* cmask_out, float* q32_out, float* c32_out, hipStream_t st);
-hipError_t rr_launch_plaid_decode(const uint16_t* centroids, int C, const float* weights, int nbits, int D, const int32_t* codes,
-                                  const uint8_t* resid, long long first_row, long long n_rows, uint16_t* out, hipStream_t st);
+                                 const float* query_mask, const rr_bank_view& bank, bf16_t* li16, int dt, float* qmask_out,
+                                 float* cmask_out, float* q32_out, float* c32_out, hipStream_t st);
+// compressed bank: the stand-alone decode of a row range (rows and mask of the view unused)
+hipError_t rr_launch_plaid_decode(const rr_bank_view& bank, int D, long long first_row, long long n_rows, uint16_t* out, hipStream_t st);
 int rr_set_li_lds_kb(int kb);      // rr_set_tuning("li_lds_kb"): 16 .. 150, -1 outside (li_scores.hip)
-// the score matrix [n][Lc][Lq] and MaxSim [n] of a pair list with the context rows read from a bank, fp16 or compressed: the
-// kernel of rr_launch_li_scores over another operand source, bit for bit its result on the same rows (li_scores.hip); slot [n] on
-// the device or null: the output row of workgroup p
-hipError_t rr_launch_bank_li_scores(const rr_bank_pair* pairs, const int32_t* slot, int n, int Lq, int Lc, int D, const float* query_li, const uint16_t* rows,
-                                    const uint8_t* mask_bytes, float* scores, float* maxsim, hipStream_t st);
-hipError_t rr_launch_bank_li_scores_plaid(const rr_bank_pair* pairs, const int32_t* slot, int n, int Lq, int Lc, int D, const float* query_li, int nbits,
-                                          const int32_t* codes, const uint8_t* resid, const uint16_t* centroids, const float* weights,
-                                          int C, const uint8_t* mask_bytes, float* scores, float* maxsim, hipStream_t st);
+// the score matrix [n][Lc][Lq] and MaxSim [n] of a pair list with the context rows read from a bank: the kernel of
+// rr_launch_li_scores over another operand source, bit for bit its result on the same rows (li_scores.hip); slot [n] on the device
+// or null: the output row of workgroup p
+hipError_t rr_launch_bank_li_scores(const rr_bank_pair* pairs, const int32_t* slot, int n, int Lq, int Lc, int D, const float* query_li,
+                                    const rr_bank_view& bank, float* scores, float* maxsim, hipStream_t st);
 // rr_bank_search (bank_search.hip): out [nq][n] = the MaxSim of every query against the passages table[0 .. n) (the bits of
 // rr_launch_bank_li_scores' maxsim at Lc = the passage's length), and the selection: the first k of every list in the order of a
 // stable descending sort (NaN first, ties by ascending index), indices + add; tmp_a / tmp_b hold rr_topk_select_scratch int32 each
-hipError_t rr_launch_bank_search_scores(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li, const uint16_t* rows,
-                                        const uint8_t* mask_bytes, float* out, hipStream_t st);
-hipError_t rr_launch_bank_search_scores_plaid(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li, int nbits,
-                                              const int32_t* codes, const uint8_t* resid, const uint16_t* centroids, const float* weights,
-                                              int C, const uint8_t* mask_bytes, float* out, hipStream_t st);
+hipError_t rr_launch_bank_search_scores(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
+                                        const rr_bank_view& bank, float* out, hipStream_t st);
 size_t rr_topk_select_scratch(int n_lists, int n, int k);
 hipError_t rr_launch_topk_select(const float* scores, int n_lists, int n, int k, int add, int32_t* tmp_a, int32_t* tmp_b,
                                  int32_t* indices_out, float* scores_out, hipStream_t st);

@@ -532,8 +532,8 @@ int rr_bank_add(rr_bank_handle b, const void* context_li, int dtype, const float
  * with "nbits": 8), decoded on the device inside the gather of rr_forward_interaction_bank.  Replaces the reference's own native
  * kernel on the retriever-to-reranker hand-over (third_party/ColBERT/colbert/indexing/codecs/decompress_residuals.cu) and the
  * F.normalize behind it (codecs/residual.py:242-278).  Bytes per token at li_dim 128: 257 as fp16, 133 / 69 / 37 / 21 at nbits 8 /
- * 4 / 2 / 1.  Nothing here compresses or computes embeddings; rr_bank_search searches, exhaustively (no PLAID candidate
- * generation or centroid pruning).
+ * 4 / 2 / 1.  Nothing here compresses or computes embeddings; rr_bank_search searches exhaustively;
+ * rr_bank_search_plaid runs PLAID's candidate generation and centroid pruning over the codes a compressed bank holds.
  *
  * THE DECODED ROW, for a row with code c, residual bytes r[0 .. D * nbits / 8), centroids [C, D] fp16 (the index stores them with
  * .half(), residual.py:161) and float32 bucket weights w[2^nbits]:
@@ -664,11 +664,57 @@ int rr_bank_li_scores(rr_handle h, rr_bank_handle b, const float* query_li, int 
  * misaligned pointers, bank and handle on different devices, a full-context handle (RR_ERR_BAD_ARG); a different li_dim,
  * non-positive sizes, a range that is empty or not inside the bank, k < 1 or k > n_passages (RR_ERR_BAD_SHAPE).
  * LIMITS: k <= 1024; not capturable into a graph (RR_ERR_BAD_ARG under stream capture: the call may upload the table and grow
- * its block); one device (no merge across ranks: search ranges and merge the k-lists yourself); no candidate filter (every
- * passage of the range competes; restrict by range only).  (Python: RerankEngine.bank_search, PassageBank.search,
+ * its block); one device (no merge across ranks: search ranges and merge the k-lists yourself); every passage of the range competes (restrict
+ * by range, or prune by centroid with rr_bank_search_plaid; no caller-supplied candidate filter).  (Python: RerankEngine.bank_search, PassageBank.search,
  * InteractionRerankModel.retrieve / retrieve_and_rerank.) */
 int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage,
                    int32_t n_passages, int k, int32_t* indices_out, float* scores_out, void* hip_stream);
+
+/* rr_bank_search_plaid: PLAID's staged, centroid-pruned top-k search over a range of a COMPRESSED bank (the reference:
+ * third_party/ColBERT/colbert/search/index_storage.py:86-184, candidate_generation.py, filter_pids.cpp), from what the bank holds
+ * already: a centroid code per row, the fp16 centroid table, the passage table.  No IVF is built or loaded: the candidate set the
+ * reference reads from its IVF (per centroid the passages holding a token with that code: _build_ivf, indexing/
+ * collection_indexer.py:393-431, sorts the embedding ids by code and counts them per centroid; optimize_ivf, indexing/utils.py:8-48,
+ * maps every embedding id to its passage and keeps the unique passages of each centroid) comes from one scan over the codes of
+ * the range.  An fp16 bank: RR_ERR_UNSUPPORTED.  Handles, li_dim, query_li,
+ * first_passage / n_passages, alignment, device checks and the graph-capture refusal exactly as rr_bank_search has them.
+ *   Lq_coarse : 1 <= Lq_coarse <= Lq (RR_ERR_BAD_SHAPE): stages 0-2 use the first Lq_coarse query tokens, the exact stage all Lq
+ *       (the reference cuts the query to query_maxlen for the approximate stages, index_storage.py:77).
+ *   ncells    : 1 <= ncells <= n_centroids (RR_ERR_BAD_SHAPE), at most 16 (RR_ERR_UNSUPPORTED).
+ *   ndocs     : 4 <= ndocs (RR_ERR_BAD_SHAPE) <= 1024 (RR_ERR_UNSUPPORTED: the k <= 1024 of the selection kernel).
+ *   k         : 1 <= k <= min(ndocs / 4, n_passages) (RR_ERR_BAD_SHAPE).   n_centroids <= 262144 (RR_ERR_UNSUPPORTED).
+ *   indices_out int32 [n_queries, k], scores_out float32 [n_queries, k] or NULL, counts_out int32 [n_queries] (required): DEVICE.
+ * Per query, over the passages of the range.  "Order" is rr_bank_search's one total order: NaN first, then higher score, then
+ * ascending bank index for equal scores.  -inf is the "absent" mark throughout: a passage whose score at some stage is a genuine
+ * -inf counts as absent from that stage on.  Masked rows contribute nothing at any stage.
+ *   STAGE 0, centroid scores: S[c][j], c < n_centroids, j < Lq_coarse, float32: bit for bit the scores_out entry rr_li_scores gives
+ *     for a context row equal to float32(centroid c) against query column j (its kernel runs over the centroid table cut into
+ *     pseudo-passages of 64).  The reference's GPU branch does this product in fp16, its CPU branch in float32: float32 here.
+ *   CELLS: for each of the Lq_coarse columns the first ncells centroids of that column in order (get_cells,
+ *     candidate_generation.py:12-20, ties made definite); the cell set of the query is their union.
+ *   CANDIDATES: a passage is a candidate iff at least one of its unmasked rows has a code in the cell set.
+ *   STAGE 1: keep[c] = (max_j S[c][j] >= centroid_score_threshold; a row of S holding a NaN is not kept).  A candidate scores
+ *     A1 = sum_j max(-9999, max over its unmasked rows r with keep[code_r] of S[code_r][j]), columns summed 0, 1, ... Lq_coarse - 1
+ *     in sequence from 0.0f in float32 (the reference's CPU definition, filter_pids.cpp:27-66; a NaN sticks in a maximum).  A
+ *     candidate without a kept code scores Lq_coarse * -9999.  The first min(ndocs, candidates) candidates in order survive.
+ *   STAGE 2: A2, the same sum with every keep true; the first min(ndocs / 4, survivors) in order survive.
+ *   STAGE 3: the survivors are scored with all Lq columns: bit for bit the score rr_bank_search returns for (query, passage).
+ *   OUTPUT: the first k in order; counts_out[q] = the number of real entries, entries behind it hold index -1 and score -inf.
+ * PROPERTY: with ncells = n_centroids every passage with an unmasked row is a candidate; if also ndocs / 4 >= n_passages, the
+ * result is rr_bank_search's, bit for bit (where no exact score is -inf).  The same bytes from run to run: no global atomics,
+ * nothing depends on scheduling.
+ * Eight launches and the selection passes (csrc/bank_search_plaid.hip), booked in the profile's `tail` class: stage 0 with 2 *
+ * n_queries * ceil64(n_centroids) * Lq * li_dim FLOPs, stage 3 with 2 * n_queries * min(ndocs / 4, n) * (mean rows per passage of
+ * the range) * Lq * li_dim (the survivors are counted on the device only: an upper bound).  Scratch in the grow-only block
+ * rr_bank_search uses, each term rounded up to 16 bytes, Cp = ceil64(n_centroids), W = ceil(n_centroids / 32), k1 = min(ndocs, n),
+ * k2 = min(ndocs / 4, n): 4 nq Cp Lq + 16 nq Cp / 64 + Cp + 4 nq Lq_coarse ncells + 8 nq W + 8 nq n + 4 nq (k1 + k2 + 1)
+ * + 8 * (n > 4096 ? nq ceil(n / 4096) k1 : 0) bytes.
+ * Checked on the host BEFORE anything is enqueued; a refused call writes nothing.  Not capturable into a graph (RR_ERR_BAD_ARG).
+ * Out of scope: ndocs > 1024, an IVF, merging across ranks, a caller-supplied filter, fp16 banks.  (Python:
+ * RerankEngine.bank_search_plaid, PlaidSearch with PassageBank.search / InteractionRerankModel.retrieve / retrieve_and_rerank.) */
+int rr_bank_search_plaid(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse,
+                         int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k,
+                         int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream);
 
 /* rr_head_joint: rr_head with the head RerankModel.forward runs (rr_forward_joint): `loss_fn(logits, logits)`
  * (rerank_model.py:328) — the labels are the logits themselves (2H_BCE: the two heads as class-probability targets).  The

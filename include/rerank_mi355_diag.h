@@ -292,6 +292,31 @@ int rr_op_bank_search(const float* query_li, int n_queries, int Lq, int D, const
                       int32_t* indices_out, float* scores_out, void* hip_stream);
 int rr_op_topk_select(const float* scores, int n_lists, int n, int k, int32_t* indices_out, float* scores_out, void* hip_stream);
 
+/* rr_bank_search_plaid (rerank_mi355.h) from the inside.
+ * rr_op_bank_search_plaid: the stages over raw DEVICE pointers, as rr_op_bank_search takes a compressed bank's (table, mask, codes,
+ * residuals, tables; codes are clamped into [0, n_centroids)); allocates its scratch per call and synchronises hip_stream.
+ * rr_bank_search_plaid_tap: one intermediate of the handle's LAST rr_bank_search_plaid call, copied to HOST memory (synchronises
+ * the call's stream); valid until the next search of either kind on the handle.  Returns the bytes written or < 0.  Names:
+ *   "S" float32 [n_queries, n_centroids, Lq_coarse];  "cells" / "keep" uint8 [n_queries, n_centroids] (1: in the cell set / kept);
+ *   "a1" float32 [n_queries, n_passages]: A1 of every passage of the range, -inf for a non-candidate;
+ *   "list1" int32 [n_queries, min(ndocs, n_passages)]: the stage-1 survivors in order, range-relative, -1 behind them;
+ *   "list2" int32 [n_queries, min(ndocs / 4, n_passages)]: the stage-2 survivors likewise.
+ * rr_util_plaid_prune: cells, candidates, stage 1 and stage 2 of ONE query in pure HOST code, usable without a GPU: the written-
+ * down definition the device is held to.  S float32 [n_centroids, Lq_coarse]; codes int32 / mask uint8 (NULL: all ones) over the
+ * rows of the n_passages passages back to back, lengths int32 [n_passages].  Outputs, each optional: cells_out uint8
+ * [n_centroids], a1_out / a2_out float32 [n_passages] (-inf: no candidate), list1_out int32 [min(ndocs, n_passages)] with its
+ * length in n1_out, list2_out int32 [min(ndocs / 4, n_passages)] with n2_out.  RR_ERR_BAD_SHAPE for a code outside the table.
+ * rr_set_tuning("plaid_stop_after") (7; 0 .. 7): the last stage a call runs (timing by difference; below 7 nothing is output). */
+int rr_op_bank_search_plaid(const float* query_li, int n_queries, int Lq, int Lq_coarse, int D, const void* table, int32_t first_passage,
+                            int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k, const uint8_t* mask_bytes,
+                            int nbits, const int32_t* codes, const uint8_t* residuals, const uint16_t* centroids_f16,
+                            const float* bucket_weights, int32_t n_centroids, int32_t* indices_out, float* scores_out,
+                            int32_t* counts_out, void* hip_stream);
+int64_t rr_bank_search_plaid_tap(rr_handle h, const char* name, void* host_out, int64_t max_bytes);
+int rr_util_plaid_prune(const float* S, int32_t n_centroids, int Lq_coarse, const int32_t* codes, const uint8_t* mask,
+                        const int32_t* lengths, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs,
+                        uint8_t* cells_out, float* a1_out, float* a2_out, int32_t* list1_out, int32_t* n1_out, int32_t* list2_out,
+                        int32_t* n2_out);
 #ifdef __cplusplus
 }
 #endif

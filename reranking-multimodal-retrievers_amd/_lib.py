@@ -109,6 +109,13 @@ _SIGS = {
     "rr_op_bank_search": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int32, C.c_int32, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P,
                                     C.c_int32, _P, _P, _P]),
     "rr_op_topk_select": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "rr_bank_search_plaid": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int, C.c_float, C.c_int, C.c_int,
+                                       _P, _P, _P, _P]),
+    "rr_op_bank_search_plaid": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int32, C.c_int32, C.c_int, C.c_float, C.c_int,
+                                          C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    "rr_bank_search_plaid_tap": (C.c_int64, [_P, C.c_char_p, _P, C.c_int64]),
+    "rr_util_plaid_prune": (C.c_int, [_P, C.c_int32, C.c_int, _P, _P, _P, C.c_int32, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P, _P,
+                                      _P, _P]),
     "rr_head": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "rr_head_joint": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "rr_head_lists": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),

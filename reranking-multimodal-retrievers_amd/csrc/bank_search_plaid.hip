@@ -1,0 +1,545 @@
+// PLAID-pruned top-k search over a range of a COMPRESSED passage bank (rr_bank_search_plaid, include/rerank_mi355.h): the staged
+// search of the reference (third_party/ColBERT/colbert/search/index_storage.py:86-184, candidate_generation.py) with every tie made
+// definite, from what a compressed bank already holds: one int32 centroid code per row, the fp16 centroid table, the passage table.
+// No IVF: the candidate set comes from one scan over the codes of the range.  The stages of a call, one launch each unless noted:
+//   0  S [nq][Cp][Lq] float32, S[q][c][j] = <float32(centroid c), query q column j>: li_scores_kernel (li_scores.hip) over the
+//      centroid table taken as an fp16 bank of pseudo-passages of 64 centroids (Cp = C rounded up to 64; a prep launch writes the
+//      pair list and the all-ones mask), so an entry has the bits rr_li_scores gives.  All Lq columns are computed (the kernel
+//      finds query q at q * Lq * D); the stages below read the first Lq_coarse of a row.
+//   1  plaid_cells_kernel: a workgroup per (query, column) takes the first ncells centroids of the column in rank order (NaN first,
+//      higher score, lower index), one block-wide maximum per cell over 64-bit (score image, ~index) keys: keys are distinct, so
+//      the result does not depend on scheduling.
+//   2  plaid_bitmaps_kernel: per query the cell set and keep[c] = (max_j S[c][j] >= threshold; a NaN in the row: false) as bitmaps
+//      of C bits.  A workgroup owns 256 centroids: the cell bits meet in LDS (ds_or), keep bits by ballot; no global atomics.
+//   3  plaid_scan_kernel, the hot path: a workgroup belongs to one query and 64 consecutive passages, holds the query's two
+//      bitmaps in LDS (C / 4 bytes) and a WAVE takes whole passages.  Lanes load 64 codes and mask bytes per step and test them
+//      against the cell bitmap; a ballot decides candidacy.  A non-candidate costs its codes and mask bytes and writes -inf.  A
+//      candidate walks its unmasked rows: lane j owns column j, one row of S per code is one coalesced read (Lq_coarse * 4 bytes),
+//      the column maxima with (A1) and without (A2) the keep test are kept side by side, and the columns are summed 0, 1, ...
+//      Lq_coarse - 1 in sequence from 0.0f by constant-lane shuffles, a chain every lane carries.  Above 64 columns the passage
+//      is walked once per block of 64 and the chain goes on.  A1 and A2 go to two dense rows [nq][n].
+//   4  rr_launch_topk_select (bank_search.hip, unchanged) over the A1 row: the first min(ndocs, n) per query; ties by bank index.
+//   5  plaid_list_select_kernel: stage-1 survivors (A1 != -inf) ordered by A2, the first ndocs / 4 kept, with their count.
+//   6  plaid_exact_list_kernel: the tile loop of bank_search_scores_kernel (same operand source, same matrix-core chain per entry,
+//      same column sum: the bits of rr_bank_search), a workgroup's passages taken from the stage-2 list of its query, one per
+//      wave; the exact score overwrites the passage's entry of the A2 row.
+//   7  plaid_list_select_kernel again: by exact score, the first k; -1 / -inf behind the count, and the count.
+// -inf is the "absent" mark of every row and list: an entry that holds it at some stage is not a survivor of that stage.
+// rr_plaid_prune_host restates cells, candidates, stage 1 and stage 2 in host code: the written-down definition.
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstring>
+#include <type_traits>
+#include <vector>
+
+#include "li_sources.h"
+#include "rr_common.h"
+
+namespace {
+
+constexpr int PS_CHUNK = 64;             // passages per workgroup of the scan (16 per wave)
+constexpr int PL_CHUNK = 4;              // passages per workgroup of the list-driven exact kernel (one per wave)
+constexpr int PL_JT_MAX = 8;
+constexpr int LIST_MAX = 1024;           // entries plaid_list_select_kernel sorts (ndocs)
+constexpr int PSEUDO = 64;               // centroids per pseudo-passage of stage 0
+
+// the order-preserving image of a score (bank_search.hip score_key): NaN above +inf, -0 as +0; never 0
+__device__ __host__ __forceinline__ uint32_t plaid_score_key(float s) {
+  if (s != s) return 0xffffffffu;
+  uint32_t u;
+  memcpy(&u, &s, 4);
+  if (u == 0x80000000u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __host__ __forceinline__ unsigned long long plaid_key(float s, uint32_t idx) {
+  return ((unsigned long long)plaid_score_key(s) << 32) | (unsigned long long)(0xffffffffu - idx);
+}
+
+__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int m) {
+  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// stage 0 prep: the pair list of the pseudo-passages ((query, block of 64 centroids), query-major) and the all-ones mask bytes
+__global__ __launch_bounds__(256) void plaid_prep_kernel(rr_bank_pair* pairs, int blocks, int nq, int C, uint8_t* ones, int Cp) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < blocks * nq) {
+    const int q = i / blocks, b = i - q * blocks;
+    pairs[i] = rr_bank_pair{(int64_t)b * PSEUDO, min(PSEUDO, C - b * PSEUDO), q};
+  }
+  if (i < Cp) ones[i] = 1;
+}
+
+__global__ __launch_bounds__(256) void plaid_cells_kernel(const float* __restrict__ S, long long s_q, int s_ld, int C, int Lqc, int ncells,
+                                                          int32_t* __restrict__ cells) {
+  __shared__ unsigned long long wbest[2][4];
+  const int q = blockIdx.x / Lqc, j = blockIdx.x - q * Lqc, tid = threadIdx.x;
+  const float* col = S + (size_t)q * s_q + j;
+  unsigned long long prev = 0ull;
+  for (int r = 0; r < ncells; ++r) {
+    unsigned long long best = 0ull;                           // below every key
+    for (int c = tid; c < C; c += 256) {
+      const unsigned long long key = plaid_key(col[(size_t)c * s_ld], (uint32_t)c);
+      if ((r == 0 || key < prev) && key > best) best = key;
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+      const unsigned long long o = shfl_xor_u64(best, m);
+      if (o > best) best = o;
+    }
+    if ((tid & 63) == 0) wbest[r & 1][tid >> 6] = best;
+    __syncthreads();                                          // (the buffers alternate: one barrier per cell)
+    prev = max(max(wbest[r & 1][0], wbest[r & 1][1]), max(wbest[r & 1][2], wbest[r & 1][3]));
+    if (tid == 0) cells[((size_t)q * Lqc + j) * ncells + r] = (int32_t)(0xffffffffu - (uint32_t)prev);
+  }
+}
+
+__global__ __launch_bounds__(256) void plaid_bitmaps_kernel(const float* __restrict__ S, long long s_q, int s_ld, int C, int Lqc, int ncells,
+                                                            float thr, const int32_t* __restrict__ cells, int W,
+                                                            uint32_t* __restrict__ cellbits, uint32_t* __restrict__ keepbits) {
+  __shared__ uint32_t cb[8], kb[8];
+  const int q = blockIdx.y, tid = threadIdx.x, c = blockIdx.x * 256 + tid;
+  if (tid < 8) cb[tid] = 0u;
+  __syncthreads();
+  const int32_t* cl = cells + (size_t)q * Lqc * ncells;
+  for (int i = tid; i < Lqc * ncells; i += 256) {
+    const int cc = cl[i];
+    if ((cc >> 8) == (int)blockIdx.x) atomicOr(&cb[(cc & 255) >> 5], 1u << (cc & 31));      // LDS; an OR has one result
+  }
+  bool keep = false;
+  if (c < C) {
+    const float* row = S + (size_t)q * s_q + (size_t)c * s_ld;
+    float m = -INFINITY;
+    for (int j = 0; j < Lqc; ++j) m = nan_max(m, row[j]);
+    keep = m >= thr;
+  }
+  const unsigned long long b = __ballot(keep);
+  if ((tid & 63) == 0) {
+    kb[(tid >> 6) * 2] = (uint32_t)b;
+    kb[(tid >> 6) * 2 + 1] = (uint32_t)(b >> 32);
+  }
+  __syncthreads();
+  if (tid < 8 && blockIdx.x * 8 + tid < W) {
+    cellbits[(size_t)q * W + blockIdx.x * 8 + tid] = cb[tid];
+    keepbits[(size_t)q * W + blockIdx.x * 8 + tid] = kb[tid];
+  }
+}
+
+__device__ __forceinline__ long long uniform_i64(int64_t v) {
+  return (long long)(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+                     (uint32_t)__builtin_amdgcn_readfirstlane((int)v));
+}
+
+__global__ __launch_bounds__(256) void plaid_scan_kernel(const float* __restrict__ S, long long s_q, int s_ld, int C, int Lqc,
+                                                         const uint32_t* __restrict__ cellbits, const uint32_t* __restrict__ keepbits, int W,
+                                                         const int32_t* __restrict__ codes, const uint8_t* __restrict__ mask,
+                                                         const rr_bank_slot* __restrict__ table, int n, int nq, float* __restrict__ a1,
+                                                         float* __restrict__ a2) {
+  extern __shared__ uint32_t bits[];     // [W] cell set, [W] keep
+  const int q = blockIdx.x % nq, p0 = (blockIdx.x / nq) * PS_CHUNK, pn = min(PS_CHUNK, n - p0);
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int i = threadIdx.x; i < W; i += 256) {
+    bits[i] = cellbits[(size_t)q * W + i];
+    bits[W + i] = keepbits[(size_t)q * W + i];
+  }
+  __syncthreads();
+  const float* Sq = S + (size_t)q * s_q;
+  for (int i = wave; i < pn; i += 4) {                        // a passage belongs to one wave
+    const rr_bank_slot sl = table[p0 + i];
+    const long long first_row = uniform_i64(sl.first_row);
+    const int len = __builtin_amdgcn_readfirstlane(sl.len);
+    bool cand = false;
+    for (int base = 0; base < len && !cand; base += 64) {
+      const int r = base + lane;
+      bool hit = false;
+      if (r < len && mask[first_row + r]) {
+        const int c = min(max(codes[first_row + r], 0), C - 1);
+        hit = (bits[c >> 5] >> (c & 31)) & 1u;
+      }
+      cand = __ballot(hit) != 0ull;
+    }
+    float s1 = -INFINITY, s2 = -INFINITY;
+    if (cand) {                                               // wave-uniform
+      s1 = 0.0f;
+      s2 = 0.0f;
+      for (int j0 = 0; j0 < Lqc; j0 += 64) {
+        const int j = j0 + lane;
+        const bool j_ok = j < Lqc;
+        float m1 = LI_MASKED, m2 = LI_MASKED;
+        for (int base = 0; base < len; base += 64) {
+          const int r = base + lane;
+          int code = 0, mk = 0;
+          if (r < len) {
+            code = min(max(codes[first_row + r], 0), C - 1);
+            mk = mask[first_row + r];
+          }
+          const int cnt = min(64, len - base);
+          for (int t = 0; t < cnt; ++t) {
+            if (!__builtin_amdgcn_readlane(mk, t)) continue;  // a masked row contributes nothing
+            const int c = __builtin_amdgcn_readlane(code, t);
+            const bool kept = (bits[W + (c >> 5)] >> (c & 31)) & 1u;
+            const float v = j_ok ? Sq[(size_t)c * s_ld + j] : LI_MASKED;
+            m2 = nan_max(m2, v);
+            if (kept) m1 = nan_max(m1, v);
+          }
+        }
+        const int cols = min(64, Lqc - j0);
+        for (int l = 0; l < cols; ++l) {                      // columns 0, 1, ... Lq_coarse - 1, one after the other
+          s1 += __shfl(m1, l, 64);
+          s2 += __shfl(m2, l, 64);
+        }
+      }
+    }
+    if (lane == 0) {
+      a1[(size_t)q * n + p0 + i] = s1;
+      a2[(size_t)q * n + p0 + i] = s2;
+    }
+  }
+}
+
+// One workgroup per query: the entries list_in[q][0 .. cnt) (cnt = cnt_in[q], or n_in) whose score (and whose entry of valid_row, if
+// given) is not -inf, in rank order by scores[q][entry]; the first `keep` go to list_out[q] (+ add) and scores_out[q], -1 / -inf
+// behind them up to `keep`, their number to cnt_out[q].  cnt <= 1024.
+__global__ __launch_bounds__(256) void plaid_list_select_kernel(const float* __restrict__ scores, const float* __restrict__ valid_row, long long n,
+                                                                const int32_t* __restrict__ list_in, int in_ld, const int32_t* __restrict__ cnt_in,
+                                                                int n_in, int keep, int32_t* __restrict__ list_out, int out_ld,
+                                                                int32_t* __restrict__ cnt_out, int add, float* __restrict__ scores_out) {
+  __shared__ unsigned long long key[LIST_MAX];
+  __shared__ int valid;
+  const int q = blockIdx.x, tid = threadIdx.x;
+  const int cnt = min(cnt_in ? cnt_in[q] : n_in, LIST_MAX);
+  const float* row = scores + (size_t)q * n;
+  int n2 = 2;
+  while (n2 < cnt) n2 <<= 1;
+  if (tid == 0) valid = 0;
+  for (int i = tid; i < n2; i += 256) {
+    unsigned long long kv = 0ull;                             // absent: behind every entry
+    if (i < cnt) {
+      const int idx = list_in[(size_t)q * in_ld + i];
+      const float s = row[idx];
+      if (s != -INFINITY && (!valid_row || valid_row[(size_t)q * n + idx] != -INFINITY)) kv = plaid_key(s, (uint32_t)idx);
+    }
+    key[i] = kv;
+  }
+  __syncthreads();
+  for (int kk = 2; kk <= n2; kk <<= 1) {
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < n2; i += 256) {
+        const int l = i ^ j;
+        if (l > i) {
+          const bool up = (i & kk) == 0;
+          const unsigned long long a = key[i], b = key[l];
+          if (up ? a < b : a > b) { key[i] = b; key[l] = a; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (int i = tid; i < n2; i += 256)
+    if (key[i] != 0ull && (i == n2 - 1 || key[i + 1] == 0ull)) valid = i + 1;      // one thread at most
+  __syncthreads();
+  const int kept = min(keep, valid);
+  for (int i = tid; i < keep; i += 256) {
+    int32_t o = -1;
+    float s = -INFINITY;
+    if (i < kept) {
+      const int idx = (int)(0xffffffffu - (uint32_t)key[i]);
+      o = idx + add;
+      s = row[idx];
+    }
+    list_out[(size_t)q * out_ld + i] = o;
+    if (scores_out) scores_out[(size_t)q * out_ld + i] = s;
+  }
+  if (tid == 0) cnt_out[q] = kept;
+}
+
+// bank_search_scores_kernel's passage loop (bank_search.hip) with the passages of a workgroup taken from list[q][p0 .. p0 + 4) and
+// the score written to the passage's entry of the dense row out[q][.].  The tile step is that kernel's, written out (li_sources.h).
+template <int JT, class SRC>
+__global__ __launch_bounds__(256) void plaid_exact_list_kernel(const float* __restrict__ query_li, const SRC src,
+                                                               const rr_bank_slot* __restrict__ table, int n, int nq,
+                                                               const int32_t* __restrict__ list, int list_ld, const int32_t* __restrict__ cnt,
+                                                               int Lq, int D, float* __restrict__ out) {
+  constexpr int JB = 16 * JT;
+  extern __shared__ __attribute__((aligned(16))) float qblk[];
+  __shared__ float psum[PL_CHUNK];
+  const int ldq = D + 4;
+  const int q = blockIdx.x % nq, p0 = (blockIdx.x / nq) * PL_CHUNK;
+  const int have = cnt[q];
+  if (p0 >= have) return;                                     // the whole workgroup
+  const int pn = min(PL_CHUNK, have - p0);
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int li = lane & 15, g = lane >> 4;
+  const float* Q = query_li + (size_t)q * Lq * D;
+  uint16_t* tile = SRC::TILE ? (uint16_t*)(qblk + JB * ldq) + wave * 16 * (D + LI_TILE_PAD) : nullptr;
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+
+  for (int j0 = 0; j0 < Lq; j0 += JB) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < JB * (D / 4); i += 256) {
+      const int row = i / (D / 4), col = (i - row * (D / 4)) * 4;
+      *(f32x4*)(qblk + row * ldq + col) = j0 + row < Lq ? *(const f32x4*)(Q + (size_t)(j0 + row) * D + col) : zero4;
+    }
+    __syncthreads();
+    const bool last = j0 + JB >= Lq;
+    for (int i = wave; i < pn; i += 4) {
+      const int pi = min(max(__builtin_amdgcn_readfirstlane(list[(size_t)q * list_ld + p0 + i]), 0), n - 1);
+      const rr_bank_slot sl = table[pi];
+      const long long first_row = uniform_i64(sl.first_row);
+      const typename SRC::pair_t pr = src.of(first_row, __builtin_amdgcn_readfirstlane(sl.len), q, 0, D);
+      const int len = pr.len, c_tiles = (len + 15) / 16;
+      float cmax[JT];
+#pragma unroll
+      for (int t = 0; t < JT; ++t) cmax[t] = -INFINITY;
+      for (int ct = 0; ct < c_tiles; ++ct) {
+        const int c = ct * 16 + li;
+        const bool c_ok = c < len;
+        f32x4 acc[JT];
+#pragma unroll
+        for (int t = 0; t < JT; ++t) acc[t] = zero4;
+        if constexpr (SRC::TILE) {
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          src.stage(pr, ct, D, lane, tile);
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+        const typename SRC::cursor crow = src.row(pr, c_ok ? c : 0, g, D, li, tile);
+        const float* qrow = qblk + li * ldq + 4 * g;
+        f32x4 a = c_ok ? SRC::at(crow, 0) : zero4;
+        for (int d = 0; d < D; d += 16) {
+          const f32x4 a_n = (c_ok && d + 16 < D) ? SRC::at(crow, d + 16) : zero4;
+          f32x4 b[JT];
+#pragma unroll
+          for (int t = 0; t < JT; ++t) b[t] = *(const f32x4*)(qrow + t * 16 * ldq + d);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+#pragma unroll
+            for (int t = 0; t < JT; ++t)
+              acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b[t][e], acc[t], 0, 0, 0);
+          }
+          a = a_n;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = ct * 16 + 4 * g + r;
+          if (row >= len) continue;
+          const bool keep = src.keep(pr, row);
+#pragma unroll
+          for (int t = 0; t < JT; ++t)
+            if (j0 + t * 16 + li < Lq) cmax[t] = nan_max(cmax[t], keep ? acc[t][r] : LI_MASKED);
+        }
+      }
+      float sum = j0 ? psum[i] : 0.0f;
+#pragma unroll
+      for (int t = 0; t < JT; ++t) {
+        float v = cmax[t];
+        v = nan_max(v, __shfl_xor(v, 16, 64));
+        v = nan_max(v, __shfl_xor(v, 32, 64));
+#pragma unroll
+        for (int l = 0; l < 16; ++l) {
+          const float x = __shfl(v, l, 64);
+          if (j0 + t * 16 + l < Lq) sum += x;
+        }
+      }
+      if (lane == 0) {
+        if (last) out[(size_t)q * n + pi] = sum;
+        else psum[i] = sum;
+      }
+    }
+  }
+}
+
+template <int JT, class SRC>
+hipError_t exact_launch_jt(const rr_plaid_search_args& a, const SRC& src, const int32_t* list, int list_ld, const int32_t* cnt, size_t lds,
+                           float* out, hipStream_t st) {
+  static std::atomic<unsigned long long> attr_set{0};
+  const hipError_t e = li_lds_attr((const void*)plaid_exact_list_kernel<JT, SRC>, attr_set);
+  if (e != hipSuccess) return e;
+  const long long blocks = (long long)((list_ld + PL_CHUNK - 1) / PL_CHUNK) * a.nq;
+  hipLaunchKernelGGL((plaid_exact_list_kernel<JT, SRC>), dim3((unsigned)blocks), dim3(256), lds, st, a.query_li, src, a.table, a.n, a.nq,
+                     list, list_ld, cnt, a.Lq, a.D, out);
+  return hipGetLastError();
+}
+
+hipError_t exact_launch(const rr_plaid_search_args& a, const int32_t* list, int list_ld, const int32_t* cnt, float* out, hipStream_t st) {
+  return li_with_bank_source(nullptr, nullptr, a.bank, a.D, [&](const auto& src, size_t tile_bytes) -> hipError_t {
+    using SRC = std::decay_t<decltype(src)>;
+    if constexpr (!SRC::TILE) {
+      return hipErrorInvalidValue;                            // compressed banks only
+    } else {
+      size_t lds = 0;
+      const int jt = li_pick_jt(a.Lq, a.D, tile_bytes, (size_t)72 * 1024, &lds);
+      if (jt == 0) return hipErrorInvalidValue;
+      if (jt == 1) return exact_launch_jt<1>(a, src, list, list_ld, cnt, lds, out, st);
+      if (jt == 2) return exact_launch_jt<2>(a, src, list, list_ld, cnt, lds, out, st);
+      if (jt == 4) return exact_launch_jt<4>(a, src, list, list_ld, cnt, lds, out, st);
+      return exact_launch_jt<PL_JT_MAX>(a, src, list, list_ld, cnt, lds, out, st);
+    }
+  });
+}
+
+size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// the order of the lists on the host: NaN first, higher score, lower index
+bool ranks_before(float sa, int ia, float sb, int ib) { return plaid_key(sa, (uint32_t)ia) > plaid_key(sb, (uint32_t)ib); }
+float host_nan_max(float m, float v) { return (v > m || v != v) ? v : m; }
+
+}  // namespace
+
+bool rr_plaid_search_shape_ok(int n_centroids, int ndocs) { return n_centroids >= 1 && n_centroids <= RR_PLAID_SEARCH_MAX_CENTROIDS && ndocs <= LIST_MAX; }
+
+rr_plaid_search_layout rr_plaid_search_plan(int nq, int n, int C, int Lq, int Lqc, int ncells, int ndocs, int k) {
+  rr_plaid_search_layout l{};
+  l.Cp = (C + PSEUDO - 1) / PSEUDO * PSEUDO;
+  l.W = (C + 31) / 32;
+  l.k1 = std::min(ndocs, n);
+  l.k2 = std::min(ndocs / 4, n);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off += up16(bytes); return o; };
+  l.S = take((size_t)nq * l.Cp * Lq * sizeof(float));
+  l.pairs = take((size_t)nq * (l.Cp / PSEUDO) * sizeof(rr_bank_pair));
+  l.ones = take((size_t)l.Cp);
+  l.cells = take((size_t)nq * Lqc * ncells * sizeof(int32_t));
+  l.cellbits = take((size_t)nq * l.W * sizeof(uint32_t));
+  l.keepbits = take((size_t)nq * l.W * sizeof(uint32_t));
+  l.a1 = take((size_t)nq * n * sizeof(float));
+  l.a2 = take((size_t)nq * n * sizeof(float));
+  l.list1 = take((size_t)nq * l.k1 * sizeof(int32_t));
+  l.list2 = take((size_t)nq * l.k2 * sizeof(int32_t));
+  l.cnt2 = take((size_t)nq * sizeof(int32_t));
+  l.tmp_entries = rr_topk_select_scratch(nq, n, l.k1);
+  l.tmp_a = take(l.tmp_entries * sizeof(int32_t));
+  l.tmp_b = take(l.tmp_entries * sizeof(int32_t));
+  l.total = off;
+  (void)k;
+  return l;
+}
+
+hipError_t rr_launch_plaid_search_stage(int stage, const rr_plaid_search_args& a, const rr_plaid_search_layout& l, hipStream_t st) {
+  const int C = a.bank.n_centroids;
+  if (!a.scratch || !a.query_li || !a.table || !a.bank.nbits || !a.bank.codes || !a.bank.mask || !a.bank.centroids || C < 1 ||
+      C > RR_PLAID_SEARCH_MAX_CENTROIDS || a.nq < 1 || a.n < 1 || a.Lqc < 1 || a.Lqc > a.Lq || a.ncells < 1 || a.ncells > std::min(C, 16) ||
+      a.ndocs < 4 || a.ndocs > LIST_MAX || a.k < 1 || a.k > l.k2 || !a.indices_out || !a.counts_out)
+    return hipErrorInvalidValue;
+  float* S = (float*)(a.scratch + l.S);
+  const long long s_q = (long long)l.Cp * a.Lq;
+  rr_bank_pair* pairs = (rr_bank_pair*)(a.scratch + l.pairs);
+  uint8_t* ones = (uint8_t*)(a.scratch + l.ones);
+  int32_t* cells = (int32_t*)(a.scratch + l.cells);
+  uint32_t* cellbits = (uint32_t*)(a.scratch + l.cellbits);
+  uint32_t* keepbits = (uint32_t*)(a.scratch + l.keepbits);
+  float* a1 = (float*)(a.scratch + l.a1);
+  float* a2 = (float*)(a.scratch + l.a2);
+  int32_t* list1 = (int32_t*)(a.scratch + l.list1);
+  int32_t* list2 = (int32_t*)(a.scratch + l.list2);
+  int32_t* cnt2 = (int32_t*)(a.scratch + l.cnt2);
+  switch (stage) {
+    case 0: {
+      const int blocks = l.Cp / PSEUDO, items = std::max(blocks * a.nq, l.Cp);
+      hipLaunchKernelGGL(plaid_prep_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, pairs, blocks, a.nq, C, ones, l.Cp);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return e;
+      const rr_bank_view cent{0, 0, a.bank.centroids, nullptr, nullptr, nullptr, nullptr, ones};
+      return rr_launch_bank_li_scores(pairs, nullptr, blocks * a.nq, a.Lq, PSEUDO, a.D, a.query_li, cent, S, nullptr, st);
+    }
+    case 1:
+      hipLaunchKernelGGL(plaid_cells_kernel, dim3((unsigned)(a.nq * a.Lqc)), dim3(256), 0, st, S, s_q, a.Lq, C, a.Lqc, a.ncells, cells);
+      return hipGetLastError();
+    case 2:
+      hipLaunchKernelGGL(plaid_bitmaps_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)a.nq), dim3(256), 0, st, S, s_q, a.Lq, C, a.Lqc,
+                         a.ncells, a.thr, cells, l.W, cellbits, keepbits);
+      return hipGetLastError();
+    case 3: {
+      const long long blocks = ((long long)a.n + PS_CHUNK - 1) / PS_CHUNK * a.nq;
+      if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+      hipLaunchKernelGGL(plaid_scan_kernel, dim3((unsigned)blocks), dim3(256), (size_t)2 * l.W * sizeof(uint32_t), st, S, s_q, a.Lq, C, a.Lqc,
+                         cellbits, keepbits, l.W, a.bank.codes, a.bank.mask, a.table, a.n, a.nq, a1, a2);
+      return hipGetLastError();
+    }
+    case 4:
+      return rr_launch_topk_select(a1, a.nq, a.n, l.k1, 0, l.tmp_entries ? (int32_t*)(a.scratch + l.tmp_a) : nullptr,
+                                   l.tmp_entries ? (int32_t*)(a.scratch + l.tmp_b) : nullptr, list1, nullptr, st);
+    case 5:
+      hipLaunchKernelGGL(plaid_list_select_kernel, dim3((unsigned)a.nq), dim3(256), 0, st, a2, a1, (long long)a.n, list1, l.k1, nullptr, l.k1,
+                         std::min(a.ndocs / 4, l.k2), list2, l.k2, cnt2, 0, nullptr);
+      return hipGetLastError();
+    case 6:
+      return exact_launch(a, list2, l.k2, cnt2, a2, st);
+    case 7:
+      hipLaunchKernelGGL(plaid_list_select_kernel, dim3((unsigned)a.nq), dim3(256), 0, st, a2, nullptr, (long long)a.n, list2, l.k2, cnt2, 0,
+                         a.k, a.indices_out, a.k, a.counts_out, a.first, a.scores_out);
+      return hipGetLastError();
+  }
+  return hipErrorInvalidValue;
+}
+
+// Cells, candidates, stage 1 and stage 2 of ONE query on the host, from a given S (rr_util_plaid_prune, rerank_mi355_diag.h).
+// Passages lie back to back in codes / mask.  Returns false for a code outside [0, C).
+bool rr_plaid_prune_host(const float* S, int C, int Lqc, int s_ld, const int32_t* codes, const uint8_t* mask, const int32_t* lengths,
+                         int n, int ncells, float thr, int ndocs, uint8_t* cells_out, float* a1_out, float* a2_out, int32_t* list1_out,
+                         int32_t* n1_out, int32_t* list2_out, int32_t* n2_out) {
+  std::vector<uint8_t> cell((size_t)C, 0), keep((size_t)C, 0);
+  std::vector<int> order((size_t)C);
+  for (int j = 0; j < Lqc; ++j) {
+    for (int c = 0; c < C; ++c) order[(size_t)c] = c;
+    std::partial_sort(order.begin(), order.begin() + ncells, order.end(),
+                      [&](int x, int y) { return ranks_before(S[(size_t)x * s_ld + j], x, S[(size_t)y * s_ld + j], y); });
+    for (int r = 0; r < ncells; ++r) cell[(size_t)order[(size_t)r]] = 1;
+  }
+  for (int c = 0; c < C; ++c) {
+    float m = -INFINITY;
+    for (int j = 0; j < Lqc; ++j) m = host_nan_max(m, S[(size_t)c * s_ld + j]);
+    keep[(size_t)c] = m >= thr;
+  }
+  if (cells_out) memcpy(cells_out, cell.data(), (size_t)C);
+  std::vector<float> a1((size_t)n), a2((size_t)n);
+  size_t row0 = 0;
+  for (int p = 0; p < n; ++p) {
+    const int len = lengths[p];
+    bool cand = false;
+    for (int r = 0; r < len; ++r) {
+      const int c = codes[row0 + r];
+      if (c < 0 || c >= C) return false;
+      if ((!mask || mask[row0 + r]) && cell[(size_t)c]) cand = true;
+    }
+    float s1 = -INFINITY, s2 = -INFINITY;
+    if (cand) {
+      s1 = 0.0f;
+      s2 = 0.0f;
+      for (int j = 0; j < Lqc; ++j) {
+        float m1 = -9999.0f, m2 = -9999.0f;
+        for (int r = 0; r < len; ++r) {
+          if (mask && !mask[row0 + r]) continue;
+          const int c = codes[row0 + r];
+          const float v = S[(size_t)c * s_ld + j];
+          m2 = host_nan_max(m2, v);
+          if (keep[(size_t)c]) m1 = host_nan_max(m1, v);
+        }
+        s1 += m1;
+        s2 += m2;
+      }
+    }
+    a1[(size_t)p] = s1;
+    a2[(size_t)p] = s2;
+    row0 += (size_t)len;
+  }
+  if (a1_out) memcpy(a1_out, a1.data(), (size_t)n * sizeof(float));
+  if (a2_out) memcpy(a2_out, a2.data(), (size_t)n * sizeof(float));
+  std::vector<int> l1;
+  for (int p = 0; p < n; ++p)
+    if (a1[(size_t)p] != -INFINITY) l1.push_back(p);
+  std::sort(l1.begin(), l1.end(), [&](int x, int y) { return ranks_before(a1[(size_t)x], x, a1[(size_t)y], y); });
+  if ((int)l1.size() > ndocs) l1.resize((size_t)ndocs);
+  std::vector<int> l2;
+  for (int p : l1)
+    if (a2[(size_t)p] != -INFINITY) l2.push_back(p);
+  std::sort(l2.begin(), l2.end(), [&](int x, int y) { return ranks_before(a2[(size_t)x], x, a2[(size_t)y], y); });
+  if ((int)l2.size() > ndocs / 4) l2.resize((size_t)(ndocs / 4));
+  if (n1_out) *n1_out = (int32_t)l1.size();
+  if (n2_out) *n2_out = (int32_t)l2.size();
+  if (list1_out) for (size_t i = 0; i < l1.size(); ++i) list1_out[i] = l1[i];
+  if (list2_out) for (size_t i = 0; i < l2.size(); ++i) list2_out[i] = l2[i];
+  return true;
+}

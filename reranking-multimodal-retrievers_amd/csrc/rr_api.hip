@@ -228,6 +228,10 @@ struct rr_model {
   // rr_bank_search (grow-only): the score of every (query, passage) of the call, then the two survivor buffers of the selection
   char* search_blk = nullptr;
   size_t search_blk_cap = 0;
+  // rr_bank_search_plaid shares that block; what its LAST call left there (rr_bank_search_plaid_tap), until the next search
+  rr_plaid_search_args plaid_last{};
+  rr_plaid_search_layout plaid_last_layout{};
+  bool plaid_last_ok = false;
   // CLIP ViT (optional)
   std::vector<LayerW> vit_layers;
   bf16_t* vit_wpatch = nullptr;                             // [Vh, Kp] patch convolution, zero-padded to Kp
@@ -2768,6 +2772,27 @@ static int bank_li_scores_call(rr_handle h, rr_bank* b, const float* query_li, i
   return asm_done(m, st);
 }
 
+// the bank's device copy of its passage table, brought up to date (only after an add): what every search does first
+static int bank_table_current(rr_model* m, rr_bank* b, hipStream_t st) {
+  const long long held = (long long)b->first.size();
+  if (b->table_n < (size_t)held) {                  // the first search after an add
+    if (b->table_cap < (size_t)held) {
+      if (b->table) { RR_HIP(m, hipFree(b->table)); b->table = nullptr; }      // hipFree waits for whatever still reads it
+      b->table_cap = 0;
+      b->table_n = 0;
+      const size_t cap = std::min<size_t>((size_t)b->max_passages, std::max<size_t>((size_t)held * 2, 1024));
+      RR_HIP(m, hipMalloc((void**)&b->table, cap * sizeof(rr_bank_slot)));
+      b->table_cap = cap;
+    }
+    std::vector<rr_bank_slot> up((size_t)held - b->table_n);
+    for (size_t i = 0; i < up.size(); ++i) up[i] = rr_bank_slot{b->first[b->table_n + i], b->len[b->table_n + i], 0};
+    RR_HIP(m, hipMemcpyAsync(b->table + b->table_n, up.data(), up.size() * sizeof(rr_bank_slot), hipMemcpyHostToDevice, st));
+    RR_HIP(m, hipStreamSynchronize(st));            // `up` is pageable memory of this call
+    b->table_n = (size_t)held;
+  }
+  return RR_OK;
+}
+
 // rr_bank_search (include/rerank_mi355.h): every check on the host first; then the bank's device table is brought up to date
 // (only after an add), one scoring launch over the range and the selection passes
 static int bank_search_call(rr_handle h, rr_bank* b, const float* query_li, int n_queries, int Lq, int32_t first_passage,
@@ -2794,24 +2819,11 @@ static int bank_search_call(rr_handle h, rr_bank* b, const float* query_li, int 
   hipStream_t st = (hipStream_t)hip_stream;
   RR_TRY(capture_guard(m, st, "%s cannot be captured into a graph (it may upload the bank's passage table and grow its block)", what));
   RR_HIP(m, hipSetDevice(c.device));
-  if (b->table_n < (size_t)held) {                  // the first search after an add
-    if (b->table_cap < (size_t)held) {
-      if (b->table) { RR_HIP(m, hipFree(b->table)); b->table = nullptr; }      // hipFree waits for whatever still reads it
-      b->table_cap = 0;
-      b->table_n = 0;
-      const size_t cap = std::min<size_t>((size_t)b->max_passages, std::max<size_t>((size_t)held * 2, 1024));
-      RR_HIP(m, hipMalloc((void**)&b->table, cap * sizeof(rr_bank_slot)));
-      b->table_cap = cap;
-    }
-    std::vector<rr_bank_slot> up((size_t)held - b->table_n);
-    for (size_t i = 0; i < up.size(); ++i) up[i] = rr_bank_slot{b->first[b->table_n + i], b->len[b->table_n + i], 0};
-    RR_HIP(m, hipMemcpyAsync(b->table + b->table_n, up.data(), up.size() * sizeof(rr_bank_slot), hipMemcpyHostToDevice, st));
-    RR_HIP(m, hipStreamSynchronize(st));            // `up` is pageable memory of this call
-    b->table_n = (size_t)held;
-  }
+  RR_TRY(bank_table_current(m, b, st));
   const size_t sc_bytes = (((size_t)n_queries * n * sizeof(float)) + 15) & ~(size_t)15;
   const size_t tmp_bytes = ((rr_topk_select_scratch(n_queries, n, k) * sizeof(int32_t)) + 15) & ~(size_t)15;
   RR_TRY(ensure_block(m, m->search_blk, m->search_blk_cap, sc_bytes + 2 * tmp_bytes, st, "the bank search's block"));
+  m->plaid_last_ok = false;                         // the block no longer holds a pruned search's intermediates
   float* sc = (float*)m->search_blk;
   int32_t* tmp_a = tmp_bytes ? (int32_t*)(m->search_blk + sc_bytes) : nullptr;
   int32_t* tmp_b = tmp_bytes ? (int32_t*)(m->search_blk + sc_bytes + tmp_bytes) : nullptr;
@@ -2871,6 +2883,173 @@ static int rr_op_bank_search_impl(const float* query_li, int n_queries, int Lq, 
   if (hipStreamSynchronize(st) != hipSuccess && rc == RR_OK) rc = RR_ERR_HIP;
   (void)hipFree(sc);
   return rc;
+}
+
+// rr_set_tuning("plaid_stop_after"): the last stage an rr_bank_search_plaid call runs (7: all; below it the outputs are not
+// written): tools/bench_bank_search_plaid.py times the stages by difference
+static int g_plaid_stop_after = RR_PLAID_SEARCH_STAGES - 1;      // a diagnostic switch, set between calls (as g_op_dt)
+
+// what rr_bank_search_plaid and rr_op_bank_search_plaid refuse alike, in the order the header gives; msg: the sentence for the handle
+static int plaid_search_limits(int n_centroids, int n, int Lq, int Lq_coarse, int ncells, int ndocs, int k, const char** msg) {
+  *msg = "";
+  if (Lq_coarse < 1 || Lq_coarse > Lq) { *msg = "1 <= Lq_coarse <= Lq"; return RR_ERR_BAD_SHAPE; }
+  if (ncells < 1 || ncells > n_centroids) { *msg = "1 <= ncells <= n_centroids"; return RR_ERR_BAD_SHAPE; }
+  if (ncells > 16) { *msg = "ncells at most 16"; return RR_ERR_UNSUPPORTED; }
+  if (ndocs < 4) { *msg = "ndocs at least 4"; return RR_ERR_BAD_SHAPE; }
+  if (ndocs > 1024) { *msg = "ndocs at most 1024 (the selection kernel keeps at most 1024 of a slice)"; return RR_ERR_UNSUPPORTED; }
+  if (k < 1 || k > std::min(ndocs / 4, n)) { *msg = "1 <= k <= min(ndocs / 4, n_passages)"; return RR_ERR_BAD_SHAPE; }
+  if (n_centroids > RR_PLAID_SEARCH_MAX_CENTROIDS) { *msg = "more than 262144 centroids"; return RR_ERR_UNSUPPORTED; }
+  return RR_OK;
+}
+
+// rr_bank_search_plaid (include/rerank_mi355.h): every check on the host first; then the table as rr_bank_search brings it up to
+// date, the block, and the eight stages of bank_search_plaid.hip, each booked on its own
+static int bank_search_plaid_call(rr_handle h, rr_bank* b, const float* query_li, int n_queries, int Lq, int Lq_coarse, int32_t first_passage,
+                                  int32_t n_passages, int ncells, float threshold, int ndocs, int k, int32_t* indices_out, float* scores_out,
+                                  int32_t* counts_out, void* hip_stream) {
+  const char* what = "rr_bank_search_plaid";
+  if (!h) return RR_ERR_BAD_ARG;
+  rr_model* m = h;
+  const rr_config& c = m->cfg;
+  if (!b || !query_li || !indices_out || !counts_out) return fail(m, RR_ERR_BAD_ARG, "%s: null argument", what);
+  RR_TRY(bank_usable(m, what, b));
+  if (!b->nbits) return fail(m, RR_ERR_UNSUPPORTED, "%s: an fp16 bank (compressed banks only: the stages read the centroid codes)", what);
+  const int D = c.li_dim;
+  if (D % 16) return fail(m, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a multiple of 16)", what, D);
+  if (((uintptr_t)query_li) & 15) return fail(m, RR_ERR_BAD_ARG, "%s: query_li must be 16-byte aligned", what);
+  if ((((uintptr_t)indices_out) | ((uintptr_t)scores_out) | ((uintptr_t)counts_out)) & 3) return fail(m, RR_ERR_BAD_ARG, "%s: misaligned output", what);
+  if (n_queries <= 0 || n_queries > 65535 || Lq <= 0)
+    return fail(m, RR_ERR_BAD_SHAPE, "%s: n_queries=%d (1..65535) Lq=%d", what, n_queries, Lq);
+  const long long held = (long long)b->first.size();
+  const long long n_ll = n_passages == -1 ? held - (long long)first_passage : (long long)n_passages;
+  if (first_passage < 0 || n_ll <= 0 || (long long)first_passage + n_ll > held)
+    return fail(m, RR_ERR_BAD_SHAPE, "%s: passages [%d, %d + %lld) of a bank that holds %lld", what, first_passage, first_passage, n_ll, held);
+  const int n = (int)n_ll;
+  const char* msg;
+  if (const int rc = plaid_search_limits(b->n_centroids, n, Lq, Lq_coarse, ncells, ndocs, k, &msg))
+    return fail(m, rc, "%s: %s (Lq=%d Lq_coarse=%d ncells=%d ndocs=%d k=%d, %d passages, %d centroids)", what, msg, Lq, Lq_coarse, ncells, ndocs, k,
+                n, b->n_centroids);
+  hipStream_t st = (hipStream_t)hip_stream;
+  RR_TRY(capture_guard(m, st, "%s cannot be captured into a graph (it may upload the bank's passage table and grow its block)", what));
+  RR_HIP(m, hipSetDevice(c.device));
+  RR_TRY(bank_table_current(m, b, st));
+  const rr_plaid_search_layout l = rr_plaid_search_plan(n_queries, n, b->n_centroids, Lq, Lq_coarse, ncells, ndocs, k);
+  m->plaid_last_ok = false;
+  RR_TRY(ensure_block(m, m->search_blk, m->search_blk_cap, l.total, st, "the bank search's block"));
+  m->last_stream = st;
+  const rr_plaid_search_args a{n_queries, n, first_passage, Lq, Lq_coarse, D, ncells, ndocs, k, threshold, query_li, b->table + first_passage,
+                               bank_view(b), m->search_blk, indices_out, scores_out, counts_out};
+  const size_t last = (size_t)first_passage + (size_t)n - 1;
+  const double rows = (double)(b->first[last] + b->len[last] - b->first[(size_t)first_passage]);
+  const double nq = n_queries, C = l.Cp, SLq = 4.0 * Lq_coarse;
+  // FLOPs: stage 0 exactly; stage 6 for ndocs / 4 survivors of the range's mean length (their number is known on the device only:
+  // an upper bound).  Bytes: what a stage must read and write once; the scan's candidates add a row of S per unmasked row.
+  const double flops[RR_PLAID_SEARCH_STAGES] = {2.0 * nq * C * Lq * D, 0, 0, 0, 0, 0, 2.0 * nq * l.k2 * (rows / n) * Lq * D, 0};
+  const double bytes[RR_PLAID_SEARCH_STAGES] = {2.0 * C * D + nq * (4.0 * Lq * D + 4.0 * C * Lq), nq * C * SLq * std::min(ncells, 2), nq * C * SLq,
+                                                5.0 * rows + 16.0 * n + 8.0 * nq * n, 12.0 * nq * n, 16.0 * nq * l.k1,
+                                                nq * l.k2 * (rows / n) * (rr_bank_row_bytes(a.bank, D) + 1.0), 16.0 * nq * l.k2};
+  const int stop = g_plaid_stop_after;
+  for (int s = 0; s < RR_PLAID_SEARCH_STAGES && s <= stop; ++s)
+    RR_RUN(m, st, RR_K_TAIL, flops[s], bytes[s], rr_launch_plaid_search_stage(s, a, l, st));
+  m->plaid_last = a;
+  m->plaid_last_layout = l;
+  m->plaid_last_ok = true;
+  return RR_OK;
+}
+
+// rr_bank_search_plaid_tap (include/rerank_mi355_diag.h): one intermediate of the handle's last pruned search, copied to the host
+static int64_t bank_search_plaid_tap(rr_handle h, const char* name, void* host_out, int64_t max_bytes) {
+  if (!h || !name || !host_out) return RR_ERR_BAD_ARG;
+  rr_model* m = h;
+  if (!m->plaid_last_ok) return fail(m, RR_ERR_BAD_ARG, "rr_bank_search_plaid_tap: no rr_bank_search_plaid call since the last search of this handle");
+  const rr_plaid_search_args& a = m->plaid_last;
+  const rr_plaid_search_layout& l = m->plaid_last_layout;
+  const int C = a.bank.n_centroids;
+  if (hipSetDevice(m->cfg.device) != hipSuccess || hipStreamSynchronize(m->last_stream) != hipSuccess) return fail(m, RR_ERR_HIP, "stream sync failed");
+  const std::string nm = name;
+  auto fetch = [&](size_t off, size_t bytes, void* dst) { return hipMemcpy(dst, a.scratch + off, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+  auto room = [&](size_t bytes) { return (int64_t)bytes <= max_bytes; };
+  if (nm == "S") {                       // float32 [nq][C][Lq_coarse]
+    const size_t out = (size_t)a.nq * C * a.Lqc * 4;
+    if (!room(out)) return fail(m, RR_ERR_BAD_SHAPE, "buffer too small");
+    std::vector<float> t((size_t)a.nq * l.Cp * a.Lq);
+    if (!fetch(l.S, t.size() * 4, t.data())) return RR_ERR_HIP;
+    float* o = (float*)host_out;
+    for (int q = 0; q < a.nq; ++q)
+      for (int cc = 0; cc < C; ++cc)
+        memcpy(o + ((size_t)q * C + cc) * a.Lqc, t.data() + ((size_t)q * l.Cp + cc) * a.Lq, (size_t)a.Lqc * 4);
+    return (int64_t)out;
+  }
+  if (nm == "cells" || nm == "keep") {   // uint8 [nq][C]
+    const size_t out = (size_t)a.nq * C;
+    if (!room(out)) return fail(m, RR_ERR_BAD_SHAPE, "buffer too small");
+    std::vector<uint32_t> t((size_t)a.nq * l.W);
+    if (!fetch(nm == "cells" ? l.cellbits : l.keepbits, t.size() * 4, t.data())) return RR_ERR_HIP;
+    uint8_t* o = (uint8_t*)host_out;
+    for (int q = 0; q < a.nq; ++q)
+      for (int cc = 0; cc < C; ++cc) o[(size_t)q * C + cc] = (t[(size_t)q * l.W + (cc >> 5)] >> (cc & 31)) & 1u;
+    return (int64_t)out;
+  }
+  if (nm == "a1") {                      // float32 [nq][n]
+    const size_t out = (size_t)a.nq * a.n * 4;
+    if (!room(out)) return fail(m, RR_ERR_BAD_SHAPE, "buffer too small");
+    return fetch(l.a1, out, host_out) ? (int64_t)out : (int64_t)RR_ERR_HIP;
+  }
+  if (nm == "list1") {                   // int32 [nq][min(ndocs, n)], range-relative; -1 where the entry is no candidate
+    const size_t out = (size_t)a.nq * l.k1 * 4;
+    if (!room(out)) return fail(m, RR_ERR_BAD_SHAPE, "buffer too small");
+    std::vector<float> a1((size_t)a.nq * a.n);
+    if (!fetch(l.list1, out, host_out) || !fetch(l.a1, a1.size() * 4, a1.data())) return RR_ERR_HIP;
+    int32_t* o = (int32_t*)host_out;
+    for (int q = 0; q < a.nq; ++q)
+      for (int i = 0; i < l.k1; ++i) {
+        int32_t& e = o[(size_t)q * l.k1 + i];
+        if (e < 0 || e >= a.n || a1[(size_t)q * a.n + e] == -INFINITY) e = -1;
+      }
+    return (int64_t)out;
+  }
+  if (nm == "list2") {                   // int32 [nq][min(ndocs / 4, n)], range-relative; -1 behind the survivors
+    const size_t out = (size_t)a.nq * l.k2 * 4;
+    if (!room(out)) return fail(m, RR_ERR_BAD_SHAPE, "buffer too small");
+    return fetch(l.list2, out, host_out) ? (int64_t)out : (int64_t)RR_ERR_HIP;
+  }
+  return fail(m, RR_ERR_BAD_ARG, "unknown tap %s", name);
+}
+
+static int rr_op_bank_search_plaid_impl(const float* query_li, int n_queries, int Lq, int Lq_coarse, int D, const void* table, int32_t first_passage,
+                                        int32_t n_passages, int ncells, float threshold, int ndocs, int k, const uint8_t* mask_bytes, int nbits,
+                                        const int32_t* codes, const uint8_t* residuals, const uint16_t* centroids_f16, const float* bucket_weights,
+                                        int32_t n_centroids, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream) {
+  if (!query_li || !table || !mask_bytes || !indices_out || !counts_out || !codes || !residuals || !centroids_f16 || !bucket_weights) return RR_ERR_BAD_ARG;
+  if ((((uintptr_t)query_li) | ((uintptr_t)table)) & 15) return RR_ERR_BAD_ARG;
+  if (!nbits || D <= 0 || D % 16 || !rr_plaid_shape_ok(nbits, D)) return RR_ERR_UNSUPPORTED;
+  if (n_queries <= 0 || n_queries > 65535 || Lq <= 0 || first_passage < 0 || n_passages <= 0 || n_centroids <= 0) return RR_ERR_BAD_SHAPE;
+  const char* msg;
+  if (const int rc = plaid_search_limits(n_centroids, n_passages, Lq, Lq_coarse, ncells, ndocs, k, &msg)) return rc;
+  hipStream_t st = (hipStream_t)hip_stream;
+  const rr_plaid_search_layout l = rr_plaid_search_plan(n_queries, n_passages, n_centroids, Lq, Lq_coarse, ncells, ndocs, k);
+  char* blk = nullptr;
+  if (hipMalloc((void**)&blk, l.total) != hipSuccess) { (void)hipGetLastError(); return RR_ERR_OOM; }
+  const rr_bank_view bank{nbits, n_centroids, nullptr, codes, residuals, centroids_f16, bucket_weights, mask_bytes};
+  const rr_plaid_search_args a{n_queries, n_passages, first_passage, Lq, Lq_coarse, D, ncells, ndocs, k, threshold, query_li,
+                               (const rr_bank_slot*)table + first_passage, bank, blk, indices_out, scores_out, counts_out};
+  int rc = RR_OK;
+  for (int s = 0; s < RR_PLAID_SEARCH_STAGES && rc == RR_OK; ++s)
+    if (rr_launch_plaid_search_stage(s, a, l, st) != hipSuccess) rc = RR_ERR_HIP;
+  if (hipStreamSynchronize(st) != hipSuccess && rc == RR_OK) rc = RR_ERR_HIP;
+  (void)hipFree(blk);
+  return rc;
+}
+
+static int rr_util_plaid_prune_impl(const float* S, int32_t n_centroids, int Lq_coarse, const int32_t* codes, const uint8_t* mask, const int32_t* lengths,
+                                    int32_t n_passages, int ncells, float threshold, int ndocs, uint8_t* cells_out, float* a1_out, float* a2_out,
+                                    int32_t* list1_out, int32_t* n1_out, int32_t* list2_out, int32_t* n2_out) {
+  if (!S || !codes || !lengths) return RR_ERR_BAD_ARG;
+  if (n_centroids < 1 || Lq_coarse < 1 || n_passages < 1 || ncells < 1 || ncells > n_centroids || ndocs < 4) return RR_ERR_BAD_SHAPE;
+  for (int p = 0; p < n_passages; ++p)
+    if (lengths[p] < 1) return RR_ERR_BAD_SHAPE;
+  return rr_plaid_prune_host(S, n_centroids, Lq_coarse, Lq_coarse, codes, mask, lengths, n_passages, ncells, threshold, ndocs, cells_out, a1_out,
+                             a2_out, list1_out, n1_out, list2_out, n2_out) ? RR_OK : RR_ERR_BAD_SHAPE;
 }
 
 static int64_t rr_debug_read_impl(rr_handle h, const char* name, float* host_out, int64_t max_elems) {
@@ -2990,6 +3169,11 @@ int rr_set_tuning(const char* key, int value) {
   if (!strcmp(key, "m_alternate")) return rr_set_m_alternate(value);
   if (!strcmp(key, "li_lds_kb")) return rr_set_li_lds_kb(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
   if (!strcmp(key, "search_chunk")) return rr_set_search_chunk(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
+  if (!strcmp(key, "plaid_stop_after")) {
+    if (value < 0 || value >= RR_PLAID_SEARCH_STAGES) return RR_ERR_BAD_ARG;
+    g_plaid_stop_after = value;
+    return RR_OK;
+  }
   if (!strcmp(key, "attn_prio")) return rr_set_attn_prio(value);
   if (!strcmp(key, "attn_fixed_ref")) return rr_set_attn_fixed_ref(value);
   return RR_ERR_BAD_ARG;
@@ -3493,6 +3677,18 @@ int rr_bank_li_scores(rr_handle h, rr_bank_handle b, const float* query_li, int 
 }
 int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage, int32_t n_passages, int k, int32_t* indices_out, float* scores_out, void* hip_stream) {
   return guarded(h, [&]() -> int { return bank_search_call(h, b, query_li, n_queries, Lq, first_passage, n_passages, k, indices_out, scores_out, hip_stream); });
+}
+int rr_bank_search_plaid(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse, int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream) {
+  return guarded(h, [&]() -> int { return bank_search_plaid_call(h, b, query_li, n_queries, Lq, Lq_coarse, first_passage, n_passages, ncells, centroid_score_threshold, ndocs, k, indices_out, scores_out, counts_out, hip_stream); });
+}
+int64_t rr_bank_search_plaid_tap(rr_handle h, const char* name, void* host_out, int64_t max_bytes) {
+  return guarded<int64_t>(h, [&]() -> int64_t { return bank_search_plaid_tap(h, name, host_out, max_bytes); });
+}
+int rr_op_bank_search_plaid(const float* query_li, int n_queries, int Lq, int Lq_coarse, int D, const void* table, int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k, const uint8_t* mask_bytes, int nbits, const int32_t* codes, const uint8_t* residuals, const uint16_t* centroids_f16, const float* bucket_weights, int32_t n_centroids, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_bank_search_plaid_impl(query_li, n_queries, Lq, Lq_coarse, D, table, first_passage, n_passages, ncells, centroid_score_threshold, ndocs, k, mask_bytes, nbits, codes, residuals, centroids_f16, bucket_weights, n_centroids, indices_out, scores_out, counts_out, hip_stream); });
+}
+int rr_util_plaid_prune(const float* S, int32_t n_centroids, int Lq_coarse, const int32_t* codes, const uint8_t* mask, const int32_t* lengths, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, uint8_t* cells_out, float* a1_out, float* a2_out, int32_t* list1_out, int32_t* n1_out, int32_t* list2_out, int32_t* n2_out) {
+  return guarded(nullptr, [&]() -> int { return rr_util_plaid_prune_impl(S, n_centroids, Lq_coarse, codes, mask, lengths, n_passages, ncells, centroid_score_threshold, ndocs, cells_out, a1_out, a2_out, list1_out, n1_out, list2_out, n2_out); });
 }
 int rr_op_bank_search(const float* query_li, int n_queries, int Lq, int D, const void* table, int32_t first_passage, int32_t n_passages, int k, const uint16_t* rows_f16, const uint8_t* mask_bytes, int nbits, const int32_t* codes, const uint8_t* residuals, const uint16_t* centroids_f16, const float* bucket_weights, int32_t n_centroids, int32_t* indices_out, float* scores_out, void* hip_stream) {
   return guarded(nullptr, [&]() -> int { return rr_op_bank_search_impl(query_li, n_queries, Lq, D, table, first_passage, n_passages, k, rows_f16, mask_bytes, nbits, codes, residuals, centroids_f16, bucket_weights, n_centroids, indices_out, scores_out, hip_stream); });

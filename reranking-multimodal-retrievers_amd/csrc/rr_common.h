@@ -485,6 +485,32 @@ size_t rr_topk_select_scratch(int n_lists, int n, int k);
 hipError_t rr_launch_topk_select(const float* scores, int n_lists, int n, int k, int add, int32_t* tmp_a, int32_t* tmp_b,
                                  int32_t* indices_out, float* scores_out, hipStream_t st);
 int rr_set_search_chunk(int passages);      // rr_set_tuning("search_chunk"): 4 .. 128, -1 outside
+// rr_bank_search_plaid (bank_search_plaid.hip): the staged, centroid-pruned search over a compressed bank.  The arguments of a call
+// as its eight stages take them (table: the first passage of the range; indices + first), where the intermediates of the call lie
+// in `scratch` (byte offsets, 16-byte aligned; rr_plaid_search_plan), and one launcher per stage so that a caller can book each.
+constexpr int RR_PLAID_SEARCH_STAGES = 8;
+constexpr int RR_PLAID_SEARCH_MAX_CENTROIDS = 1 << 18;      // two bitmaps of a query in the scan's LDS: 64 KB
+struct rr_plaid_search_args {
+  int nq, n, first, Lq, Lqc, D, ncells, ndocs, k;
+  float thr;
+  const float* query_li;
+  const rr_bank_slot* table;
+  rr_bank_view bank;
+  char* scratch;
+  int32_t* indices_out;
+  float* scores_out;
+  int32_t* counts_out;
+};
+struct rr_plaid_search_layout {
+  int Cp, W, k1, k2;          // centroids rounded up to 64; words of a bitmap; entries of a stage-1 / stage-2 list
+  size_t S, pairs, ones, cells, cellbits, keepbits, a1, a2, list1, list2, cnt2, tmp_a, tmp_b, tmp_entries, total;
+};
+bool rr_plaid_search_shape_ok(int n_centroids, int ndocs);
+rr_plaid_search_layout rr_plaid_search_plan(int nq, int n, int C, int Lq, int Lqc, int ncells, int ndocs, int k);
+hipError_t rr_launch_plaid_search_stage(int stage, const rr_plaid_search_args& a, const rr_plaid_search_layout& l, hipStream_t st);
+bool rr_plaid_prune_host(const float* S, int C, int Lqc, int s_ld, const int32_t* codes, const uint8_t* mask, const int32_t* lengths,
+                         int n, int ncells, float thr, int ndocs, uint8_t* cells_out, float* a1_out, float* a2_out, int32_t* list1_out,
+                         int32_t* n1_out, int32_t* list2_out, int32_t* n2_out);
 bool rr_plaid_shape_ok(int nbits, int D);
 bool rr_plaid_decode_rows_host(const uint16_t* centroids, int C, const float* weights, int nbits, int D, const int32_t* codes,
                                const uint8_t* resid, long long n_rows, uint16_t* out);

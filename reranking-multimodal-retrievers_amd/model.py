@@ -865,6 +865,67 @@ class RerankEngine:
                                         self._stream()), self.h, "rr_bank_search")
         return out
 
+    def bank_search_plaid(self, bank, query_li: torch.Tensor, k: int, *, ncells: int, centroid_score_threshold: float, ndocs: int,
+                          coarse_tokens: Optional[int] = None, first: int = 0, count: Optional[int] = None) -> dict:
+        """PLAID's pruned top-k search over a COMPRESSED `bank` (rr_bank_search_plaid; the reference's
+        colbert/search/index_storage.py:86-184): per query the cells of the first `coarse_tokens` query tokens (None: all) give
+        the candidates, two centroid-only passes keep `ndocs` and then ndocs // 4 of them, and the survivors get the exact MaxSim
+        of bank_search.  {"indices": int32 [n_queries, k] dense bank indices, -1 behind the count; "scores": float32
+        [n_queries, k], -inf there; "counts": int32 [n_queries]}, on the device.  1 <= ncells <= min(centroids, 16),
+        4 <= ndocs <= 1024, 1 <= k <= min(ndocs // 4, count) (ValueError / NotImplementedError before the library)."""
+        D = self.arch["li_dim"]
+        if query_li.dim() != 3 or query_li.shape[2] != D:
+            raise ValueError(f"query_li {tuple(query_li.shape)}: [n_queries, Lq, {D}]")
+        codec = getattr(bank, "codec", None)
+        if codec is None:
+            raise NotImplementedError("bank_search_plaid: an fp16 bank (the pruned search reads the centroid codes of a compressed bank)")
+        held = len(bank)
+        first = int(first)
+        n = held - first if count is None else int(count)
+        if first < 0 or n < 1 or first + n > held:
+            raise ValueError(f"bank_search_plaid: passages [{first}, {first} + {n}) of a bank that holds {held}")
+        nq, Lq = int(query_li.shape[0]), int(query_li.shape[1])
+        if nq < 1 or Lq < 1:
+            raise ValueError(f"query_li {tuple(query_li.shape)}: no query tokens")
+        Lqc = Lq if coarse_tokens is None else int(coarse_tokens)
+        if Lqc < 1 or Lqc > Lq:
+            raise ValueError(f"bank_search_plaid: coarse_tokens = {Lqc} of {Lq} query tokens")
+        ncells, ndocs, k = int(ncells), int(ndocs), int(k)
+        if ncells < 1 or ncells > codec.n_centroids:
+            raise ValueError(f"bank_search_plaid: ncells = {ncells} of {codec.n_centroids} centroids")
+        if ncells > 16:
+            raise NotImplementedError(f"bank_search_plaid: ncells = {ncells} (at most 16)")
+        if ndocs < 4:
+            raise ValueError(f"bank_search_plaid: ndocs = {ndocs} (at least 4)")
+        if ndocs > 1024:
+            raise NotImplementedError(f"bank_search_plaid: ndocs = {ndocs} (at most 1024)")
+        if k < 1 or k > min(ndocs // 4, n):
+            raise ValueError(f"bank_search_plaid: k = {k} of ndocs // 4 = {ndocs // 4} survivors and {n} passages")
+        q = query_li.to(device=self.device, dtype=torch.float32).contiguous()
+        out = dict(indices=torch.empty((nq, k), device=self.device, dtype=torch.int32),
+                   scores=torch.empty((nq, k), device=self.device, dtype=torch.float32),
+                   counts=torch.empty((nq,), device=self.device, dtype=torch.int32))
+        L.check(self.lib.rr_bank_search_plaid(self.h, bank.h, L.ptr(q), nq, Lq, Lqc, first, n, ncells, float(centroid_score_threshold), ndocs, k,
+                                              L.ptr(out["indices"]), L.ptr(out["scores"]), L.ptr(out["counts"]), self._stream()),
+                self.h, "rr_bank_search_plaid")
+        return out
+
+    def bank_search_plaid_tap(self, name: str):
+        """One intermediate of this engine's last bank_search_plaid call as a numpy array (rr_bank_search_plaid_tap,
+        include/rerank_mi355_diag.h): "S", "cells", "keep", "a1", "list1", "list2".  Flat; the caller knows the shape."""
+        import numpy as np
+        dt = {"S": np.float32, "a1": np.float32, "cells": np.uint8, "keep": np.uint8, "list1": np.int32, "list2": np.int32}[name]
+        cap = 1 << 20
+        while True:
+            buf = np.empty(cap, dtype=np.uint8)
+            got = int(self.lib.rr_bank_search_plaid_tap(self.h, name.encode(), buf.ctypes.data, cap))
+            if got == L.RR_ERR_BAD_SHAPE and cap < (1 << 34):
+                cap *= 8
+                continue
+            if got < 0:
+                L.check(got, self.h, "rr_bank_search_plaid_tap")
+            return buf[:got].view(dt).copy()
+
     def li_scores(self, query_li: torch.Tensor, context_li: torch.Tensor, context_mask: torch.Tensor, Bq: int, K: int,
                   pair_range: Optional[Sequence[int]] = None, want_scores: bool = True, want_maxsim: bool = True) -> dict:
         """The frozen retriever's score of every pair and the matrix behind it (rr_li_scores; colbert_score,
@@ -1306,19 +1367,31 @@ class InteractionRerankModel(_DropIn):
             raise RuntimeError("retriever_scores needs a bank: model.create_bank(capacity_rows, max_passages), then bank.add(...)")
         return self.engine.bank_li_scores(self.bank, query_late_interaction, passage_ids, **kw)
 
-    def retrieve(self, query_late_interaction, k: int, **kw):
+    def retrieve(self, query_late_interaction, k: int, plaid=None, **kw):
         """The k best passages of `self.bank` per query by the frozen retriever's MaxSim, every passage scored
-        (PassageBank.search): (passage_ids: one list per query, best first; scores float32 [n_queries, k] on the device)."""
+        (PassageBank.search): (passage_ids: one list per query, best first; scores float32 [n_queries, k] on the device).
+        `plaid` (a PlaidSearch): PLAID's pruned search over a compressed bank instead; a query's list may then be shorter than k."""
         if self.bank is None:
             raise RuntimeError("retrieve needs a bank: model.create_bank(capacity_rows, max_passages), then bank.add(...)")
+        if plaid is not None:
+            kw["plaid"] = plaid
         return self.bank.search(self.engine, query_late_interaction, k, **kw)
 
-    def retrieve_and_rerank(self, query_late_interaction, query_mask, k: int, **kw):
+    def retrieve_and_rerank(self, query_late_interaction, query_mask, k: int, plaid=None, **kw):
         """`retrieve` then `forward_passages` on what it found, k candidates per query in retrieval order: (passage_ids, the
-        RerankOutput).  `kw` goes to forward_passages (labels default as there: candidate 0 of every query)."""
-        ids, _ = self.retrieve(query_late_interaction, k)
+        RerankOutput).  `kw` goes to forward_passages (labels default as there: candidate 0 of every query).  With `plaid` the
+        lists may be of unequal length: they go to forward_passages as candidates_per_query; a query that found no candidate
+        raises ValueError."""
+        if plaid is None:
+            ids, _ = self.retrieve(query_late_interaction, k)
+            flat = [pid for row in ids for pid in row]
+            return ids, self.forward_passages(query_late_interaction, query_mask, flat, int(k) - 1, **kw)
+        ids, _ = self.retrieve(query_late_interaction, k, plaid=plaid)
+        sizes = [len(row) for row in ids]
+        if min(sizes) < 1:
+            raise ValueError(f"retrieve_and_rerank: query {sizes.index(0)} found no candidate under {plaid!r}")
         flat = [pid for row in ids for pid in row]
-        return ids, self.forward_passages(query_late_interaction, query_mask, flat, int(k) - 1, **kw)
+        return ids, self.forward_passages(query_late_interaction, query_mask, flat, int(k) - 1, candidates_per_query=sizes, **kw)
 
     def forward(self, query_late_interaction, context_late_interaction, num_negative_examples, query_mask,
                 context_mask, preflmr_scores=None, fusion_multiplier=1, labels=None, candidates_per_query=None,

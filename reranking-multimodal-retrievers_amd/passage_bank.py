@@ -15,7 +15,9 @@ include/rerank_mi355.h, rr_bank_create_plaid).  `read_plaid_index` reads such an
 matrix, rr_bank_li_scores) from either kind of bank, without a padded context tensor.
 
 `PassageBank.search` / RerankEngine.bank_search give the k best passages of the bank (or of a range of it) per query by that
-score, exactly (rr_bank_search): every passage is scored, nothing is pruned.
+score, exactly (rr_bank_search): every passage is scored, nothing is pruned.  With a `PlaidSearch` the same calls run PLAID's
+staged search over a compressed bank (rr_bank_search_plaid, RerankEngine.bank_search_plaid): candidates by centroid, two
+centroid-only pruning passes, exact MaxSim on the survivors.
 
 `BankTable`, `plan_bank_batch`, `plan_bank_scores`, `PlaidCodec` and `read_plaid_index` are the host side: pure Python / numpy / torch on the CPU,
 usable and tested without a device.
@@ -26,6 +28,33 @@ import ctypes as C
 from typing import Optional, Sequence
 
 from .pair_inputs import group_pairs_by_length
+
+
+class PlaidSearch:
+    """The parameters of PLAID's pruned search (rr_bank_search_plaid): `ncells` centroids per query token open the candidate set,
+    centroids whose best score is below `centroid_score_threshold` do not count in the first pruning pass, `ndocs` candidates
+    survive it and ndocs // 4 the second; `coarse_tokens`: the leading query tokens the approximate stages use (None: all)."""
+
+    def __init__(self, ncells: int, centroid_score_threshold: float, ndocs: int, coarse_tokens: Optional[int] = None):
+        self.ncells, self.centroid_score_threshold, self.ndocs = int(ncells), float(centroid_score_threshold), int(ndocs)
+        self.coarse_tokens = None if coarse_tokens is None else int(coarse_tokens)
+
+    @classmethod
+    def defaults(cls, k: int, coarse_tokens: Optional[int] = None) -> "PlaidSearch":
+        """The reference's parameters by k (third_party/ColBERT/colbert/searcher.py:97-122): k <= 100: ncells 2, threshold 0.45,
+        ndocs 1024 (its k <= 10 branch sets the same three).  Its k > 100 defaults need ndocs = max(4 k, 4096), above what the
+        search takes: NotImplementedError."""
+        k = int(k)
+        if k < 1:
+            raise ValueError(f"PlaidSearch.defaults: k = {k}")
+        if k <= 100:
+            return cls(2, 0.45, 1024, coarse_tokens)
+        raise NotImplementedError(f"PlaidSearch.defaults: k = {k}: the reference's defaults above k = 100 (ncells 4, threshold 0.4, "
+                                  f"ndocs {max(4 * k, 4096)}) need ndocs above 1024, the most the pruned search takes")
+
+    def __repr__(self) -> str:
+        return (f"PlaidSearch(ncells={self.ncells}, centroid_score_threshold={self.centroid_score_threshold}, ndocs={self.ndocs}, "
+                f"coarse_tokens={self.coarse_tokens})")
 
 
 class BankTable:
@@ -439,13 +468,20 @@ class PassageBank:
         """The retriever's MaxSim [n_pairs] of the pairs (query, passage id) from this bank: engine.bank_li_scores(...)["maxsim"]."""
         return engine.bank_li_scores(self, query_li, passage_ids, **kw)["maxsim"]
 
-    def search(self, engine, query_li, k: int, first: int = 0, count: Optional[int] = None):
+    def search(self, engine, query_li, k: int, first: int = 0, count: Optional[int] = None, plaid: Optional[PlaidSearch] = None):
         """The k best passages per query by the retriever's MaxSim, every passage of the bank scored (engine.bank_search;
         `first` / `count`: a range of dense indices).  Returns (passage_ids, scores): passage_ids[q] the ids of query q best
-        first, scores float32 [n_queries, k] on the device.  Copies the indices to the host (synchronises)."""
-        r = engine.bank_search(self, query_li, k, first=first, count=count)
+        first, scores float32 [n_queries, k] on the device.  Copies the indices to the host (synchronises).
+        With `plaid` (a PlaidSearch; compressed banks) the pruned search runs instead (engine.bank_search_plaid): passage_ids[q]
+        has its true length, at most k (a query may find fewer candidates, or none), and scores holds -inf behind it."""
         ids = self.table.ids
-        return [[ids[j] for j in row] for row in r["indices"].tolist()], r["scores"]
+        if plaid is None:
+            r = engine.bank_search(self, query_li, k, first=first, count=count)
+            return [[ids[j] for j in row] for row in r["indices"].tolist()], r["scores"]
+        r = engine.bank_search_plaid(self, query_li, k, ncells=plaid.ncells, centroid_score_threshold=plaid.centroid_score_threshold,
+                                     ndocs=plaid.ndocs, coarse_tokens=plaid.coarse_tokens, first=first, count=count)
+        counts = r["counts"].tolist()
+        return [[ids[j] for j in row[:c]] for row, c in zip(r["indices"].tolist(), counts)], r["scores"]
 
     def clear(self) -> None:
         """Forget every passage (rr_bank_clear; the capacity stays).  Forwards that read the bank must have completed."""

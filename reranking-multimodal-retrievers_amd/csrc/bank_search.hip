@@ -27,20 +27,25 @@
 //     li_scores_kernel over the same pairs at one query on the fp16 bank (that launch gets its pairs longest first from the host
 //     and fills every slot with one pair), and 0.95 / 0.88 / 0.82 x compressed, at 16 queries fp16, and both: the call wins by
 //     what it no longer stages and sorts on the host.
+//     WHICH passages a workgroup owns is a template parameter (PICK): pick_range, the chunk above, for rr_bank_search; pick_list,
+//     four entries of a per-query list with a count, one per wave, for stage 6 of rr_bank_search_plaid (bank_search_plaid.hip),
+//     whose scores are therefore these bits.  The range form compiles to the instructions it had before the picker existed.
 // (b) topk_select_kernel: each workgroup sorts a slice of at most 4096 (score, index) in LDS by ONE total order and keeps its
 //     first k (k <= 1024, so a pass is a strict reduction); passes repeat over the survivors until one slice is left.  The order
-//     is that of torch.sort(descending=True, stable=True): NaN ahead of every number, higher score first, equal scores (+0 == -0)
-//     by ascending index.  Score and index are packed into one 64-bit key (an order-preserving image of the float above, the
-//     complement of the index below), keys are distinct, so the bitonic network has one possible result: no atomics, nothing
-//     depends on scheduling.  Survivors travel as indices; a pass reads their scores again from the score row.
-// LAUNCHERS: rr_launch_bank_search_scores takes an rr_bank_view (rr_common.h), fp16 or compressed, and rr_launch_topk_select.  The
-// operand sources, the view-to-source dispatch (li_with_bank_source), the once-per-device LDS attribute (li_lds_attr) and the width
-// of the column block (li_pick_jt, here with a fixed 72 KB) live in li_sources.h, shared with li_scores.hip; the tile step is
-// written out in both kernel bodies (see li_scores.hip's header).
+//     and its 64-bit key are rank_order.h's, shared with the pruned search: keys are distinct, so the bitonic network (written out
+//     here and in plaid_list_select_kernel, see rank_order.h) has one possible result.  Survivors travel as indices; a pass reads
+//     their scores again from the score row.
+// LAUNCHERS: rr_launch_bank_search_scores and rr_launch_bank_search_scores_listed take an rr_bank_view (rr_common.h), fp16 or
+// compressed (the listed form: compressed only), and rr_launch_topk_select.  The operand sources, the view-to-source dispatch
+// (li_with_bank_source), the once-per-device LDS attribute (li_lds_attr) and the width of the column block (li_pick_jt, here with a
+// fixed 72 KB) live in li_sources.h, shared with li_scores.hip; the tile step is written out in this kernel body and in
+// li_scores_kernel's (see li_scores.hip's header).
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 #include "li_sources.h"
+#include "rank_order.h"
 #include "rr_common.h"
 
 namespace {
@@ -50,15 +55,45 @@ constexpr int BS_CHUNK_MAX = 128;        // passages of a workgroup's chunk (psu
 constexpr int SEL_SLICE = 4096;          // (score, index) entries one workgroup sorts
 constexpr int SEL_THREADS = 512;
 
-template <int JT, class SRC>
+// Which passages a workgroup of the scoring kernel owns, and where their scores go (PICK).  at(q, p0, i, n): the table entry of
+// the workgroup's passage i; slot(row, p0, i, pi): its place in `out`, row = q * n.
+// pick_range: `chunk` consecutive passages of the range; out is the dense [nq][n].
+struct pick_range {
+  int chunk;
+  static constexpr int PSUM = BS_CHUNK_MAX;
+  static constexpr bool LISTED = false;
+  __device__ __forceinline__ int first(int c) const { return c * chunk; }
+  __device__ __forceinline__ int count(int, int p0, int n) const { return min(chunk, n - p0); }
+  __device__ __forceinline__ int at(int, int p0, int i, int) const { return p0 + i; }
+  __device__ __forceinline__ size_t slot(size_t row, int p0, int i, int) const { return row + p0 + i; }
+};
+// pick_list: four entries, one per wave, of the first cnt[q] of list[q][0 .. list_ld) (an entry outside [0, n) is clamped); a score
+// goes to its passage's entry of the dense row out[q][.].  A workgroup behind the count has nothing to do.
+struct pick_list {
+  const int32_t* list;
+  int list_ld;
+  const int32_t* cnt;
+  static constexpr int PSUM = 4;
+  static constexpr bool LISTED = true;
+  __device__ __forceinline__ int first(int c) const { return c * 4; }
+  __device__ __forceinline__ int count(int q, int p0, int) const { return min(4, cnt[q] - p0); }
+  __device__ __forceinline__ int at(int q, int p0, int i, int n) const {
+    return min(max(__builtin_amdgcn_readfirstlane(list[(size_t)q * list_ld + p0 + i]), 0), n - 1);
+  }
+  __device__ __forceinline__ size_t slot(size_t row, int, int, int pi) const { return row + pi; }
+};
+
+template <int JT, class SRC, class PICK>
 __global__ __launch_bounds__(256) void bank_search_scores_kernel(const float* __restrict__ query_li, const SRC src,
-                                                                 const rr_bank_slot* __restrict__ table, int n, int nq, int chunk,
+                                                                 const rr_bank_slot* __restrict__ table, int n, int nq, const PICK pick,
                                                                  int Lq, int D, float* __restrict__ out) {
   constexpr int JB = 16 * JT;            // columns per block
   extern __shared__ __attribute__((aligned(16))) float qblk[];      // [JB][D + 4]: the block's query rows; TILE: the tiles behind
-  __shared__ float psum[BS_CHUNK_MAX];   // the running column sum of the chunk's passages between column blocks
+  __shared__ float psum[PICK::PSUM];     // the running column sum of the workgroup's passages between column blocks
   const int ldq = D + 4;                 // as li_scores_kernel
-  const int q = blockIdx.x % nq, p0 = (blockIdx.x / nq) * chunk, pn = min(chunk, n - p0);
+  const int q = blockIdx.x % nq, p0 = pick.first(blockIdx.x / nq), pn = pick.count(q, p0, n);
+  if constexpr (PICK::LISTED)
+    if (pn <= 0) return;                 // the whole workgroup
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int li = lane & 15, g = lane >> 4;
   const float* Q = query_li + (size_t)q * Lq * D;
@@ -74,10 +109,9 @@ __global__ __launch_bounds__(256) void bank_search_scores_kernel(const float* __
     __syncthreads();
     const bool last = j0 + JB >= Lq;
     for (int i = wave; i < pn; i += 4) {                      // a passage belongs to one wave
-      const rr_bank_slot sl = table[p0 + i];                  // the same entry in every lane: kept in scalar registers
-      const long long first_row = (long long)(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(sl.first_row >> 32)) << 32) |
-                                              (uint32_t)__builtin_amdgcn_readfirstlane((int)sl.first_row));
-      const typename SRC::pair_t pr = src.of(first_row, __builtin_amdgcn_readfirstlane(sl.len), q, 0, D);
+      const int pi = pick.at(q, p0, i, n);
+      const rr_bank_slot sl = table[pi];                      // the same entry in every lane: kept in scalar registers
+      const typename SRC::pair_t pr = src.of(uniform_i64(sl.first_row), __builtin_amdgcn_readfirstlane(sl.len), q, 0, D);
       const int len = pr.len, c_tiles = (len + 15) / 16;
       float cmax[JT];
 #pragma unroll
@@ -135,7 +169,7 @@ __global__ __launch_bounds__(256) void bank_search_scores_kernel(const float* __
         }
       }
       if (lane == 0) {
-        if (last) out[(size_t)q * n + p0 + i] = sum;
+        if (last) out[pick.slot((size_t)q * n, p0, i, pi)] = sum;
         else psum[i] = sum;
       }
     }
@@ -145,39 +179,35 @@ __global__ __launch_bounds__(256) void bank_search_scores_kernel(const float* __
 // rr_set_tuning("search_chunk"): passages per workgroup of the scoring kernel
 std::atomic<int> g_search_chunk{16};
 
-template <int JT, class SRC>
-hipError_t search_launch_jt(const float* query_li, const SRC& src, const rr_bank_slot* table, int n, int nq, int Lq, int D, size_t lds,
-                            float* out, hipStream_t st) {
+// one launch of `chunks` workgroups per query; the width of the column block is decided here for both pickers
+template <int JT, class SRC, class PICK>
+hipError_t search_launch_jt(const float* query_li, const SRC& src, const rr_bank_slot* table, int n, int nq, long long chunks, const PICK& pick,
+                            int Lq, int D, size_t lds, float* out, hipStream_t st) {
   static std::atomic<unsigned long long> attr_set{0};
-  const hipError_t e = li_lds_attr((const void*)bank_search_scores_kernel<JT, SRC>, attr_set);
+  const hipError_t e = li_lds_attr((const void*)bank_search_scores_kernel<JT, SRC, PICK>, attr_set);
   if (e != hipSuccess) return e;
-  const int chunk = g_search_chunk.load(std::memory_order_relaxed);
-  const long long blocks = ((long long)n + chunk - 1) / chunk * nq;
+  const long long blocks = chunks * nq;
   if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((bank_search_scores_kernel<JT, SRC>), dim3((unsigned)blocks), dim3(256), lds, st, query_li, src, table, n, nq,
-                     chunk, Lq, D, out);
+  hipLaunchKernelGGL((bank_search_scores_kernel<JT, SRC, PICK>), dim3((unsigned)blocks), dim3(256), lds, st, query_li, src, table, n, nq,
+                     pick, Lq, D, out);
   return hipGetLastError();
 }
 
-template <class SRC>
-hipError_t search_launch(const float* query_li, const SRC& src, const rr_bank_slot* table, int n, int nq, int Lq, int D,
-                         size_t tile_bytes, float* out, hipStream_t st) {
+template <class SRC, class PICK>
+hipError_t search_launch(const float* query_li, const SRC& src, const rr_bank_slot* table, int n, int nq, long long chunks, const PICK& pick,
+                         int Lq, int D, size_t tile_bytes, float* out, hipStream_t st) {
   // the column block is halved above a fixed 72 KB (any width gives the same bits: the sum is carried between blocks)
   size_t lds = 0;
   const int jt = li_pick_jt(Lq, D, tile_bytes, (size_t)72 * 1024, &lds);
   if (jt == 0) return hipErrorInvalidValue;
-  if (jt == 1) return search_launch_jt<1>(query_li, src, table, n, nq, Lq, D, lds, out, st);
-  if (jt == 2) return search_launch_jt<2>(query_li, src, table, n, nq, Lq, D, lds, out, st);
-  if (jt == 4) return search_launch_jt<4>(query_li, src, table, n, nq, Lq, D, lds, out, st);
-  return search_launch_jt<BS_JT_MAX>(query_li, src, table, n, nq, Lq, D, lds, out, st);
+  if (jt == 1) return search_launch_jt<1>(query_li, src, table, n, nq, chunks, pick, Lq, D, lds, out, st);
+  if (jt == 2) return search_launch_jt<2>(query_li, src, table, n, nq, chunks, pick, Lq, D, lds, out, st);
+  if (jt == 4) return search_launch_jt<4>(query_li, src, table, n, nq, chunks, pick, Lq, D, lds, out, st);
+  return search_launch_jt<BS_JT_MAX>(query_li, src, table, n, nq, chunks, pick, Lq, D, lds, out, st);
 }
 
-// the order-preserving image of a score: NaN above +inf, -0 as +0, then the usual sign flip; never 0
-__device__ __forceinline__ uint32_t score_key(float s) {
-  if (s != s) return 0xffffffffu;
-  uint32_t u = __float_as_uint(s);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+bool scores_args_ok(const rr_bank_slot* table, int n, int nq, int Lq, const float* query_li, const float* out) {
+  return n > 0 && nq > 0 && Lq > 0 && table && query_li && out && !((((uintptr_t)query_li) | ((uintptr_t)table)) & 15);
 }
 
 // One pass.  List `blockIdx.y`, slice `blockIdx.x` of its n_in entries: entry i is index idx_in[list][i] of the score row (idx_in
@@ -195,7 +225,7 @@ __global__ __launch_bounds__(SEL_THREADS) void topk_select_kernel(const float* _
     unsigned long long kv = 0ull;                             // padding ranks behind every entry
     if (i < cnt) {
       const int idx = idx_in ? idx_in[(size_t)list * in_ld + base + i] : base + i;
-      kv = ((unsigned long long)score_key(row[idx]) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)idx);
+      kv = rank_key(row[idx], (uint32_t)idx);
     }
     key[i] = kv;
   }
@@ -216,7 +246,7 @@ __global__ __launch_bounds__(SEL_THREADS) void topk_select_kernel(const float* _
   const int keep = min(k, cnt);
   const bool final_pass = gridDim.x == 1;
   for (int i = tid; i < keep; i += SEL_THREADS) {
-    const int idx = (int)(0xffffffffu - (uint32_t)key[i]);
+    const int idx = (int)rank_key_index(key[i]);
     if (final_pass) {
       idx_out[(size_t)list * out_ld + i] = idx + add;
       if (scores_out) scores_out[(size_t)list * out_ld + i] = row[idx];
@@ -237,9 +267,24 @@ int rr_set_search_chunk(int passages) {
 // out [nq][n]: the MaxSim of every query against the passages table[0 .. n) of a bank, fp16 or compressed (li_with_bank_source)
 hipError_t rr_launch_bank_search_scores(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
                                         const rr_bank_view& bank, float* out, hipStream_t st) {
-  if (n <= 0 || nq <= 0 || Lq <= 0 || !table || !query_li || !out || ((((uintptr_t)query_li) | ((uintptr_t)table)) & 15)) return hipErrorInvalidValue;
+  if (!scores_args_ok(table, n, nq, Lq, query_li, out)) return hipErrorInvalidValue;
+  const int chunk = g_search_chunk.load(std::memory_order_relaxed);
   return li_with_bank_source(nullptr, nullptr, bank, D, [&](const auto& src, size_t tile_bytes) {
-    return search_launch(query_li, src, table, n, nq, Lq, D, tile_bytes, out, st);
+    return search_launch(query_li, src, table, n, nq, ((long long)n + chunk - 1) / chunk, pick_range{chunk}, Lq, D, tile_bytes, out, st);
+  });
+}
+
+// the same MaxSim for the passages list[q][0 .. cnt[q]) (entries of table[0 .. n), cnt[q] <= list_ld) of every query q, written to
+// out[q][entry] of the dense [nq][n]; the rest of `out` is left as it is.  Compressed banks only (the pruned search is the caller)
+hipError_t rr_launch_bank_search_scores_listed(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
+                                               const rr_bank_view& bank, const int32_t* list, int list_ld, const int32_t* cnt, float* out,
+                                               hipStream_t st) {
+  if (!scores_args_ok(table, n, nq, Lq, query_li, out) || !list || !cnt || list_ld <= 0) return hipErrorInvalidValue;
+  return li_with_bank_source(nullptr, nullptr, bank, D, [&](const auto& src, size_t tile_bytes) -> hipError_t {
+    if constexpr (!std::decay_t<decltype(src)>::TILE)
+      return hipErrorInvalidValue;
+    else
+      return search_launch(query_li, src, table, n, nq, (list_ld + 3) / 4, pick_list{list, list_ld, cnt}, Lq, D, tile_bytes, out, st);
   });
 }
 

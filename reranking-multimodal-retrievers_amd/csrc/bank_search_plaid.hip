@@ -7,7 +7,7 @@
 //      pair list and the all-ones mask), so an entry has the bits rr_li_scores gives.  All Lq columns are computed (the kernel
 //      finds query q at q * Lq * D); the stages below read the first Lq_coarse of a row.
 //   1  plaid_cells_kernel: a workgroup per (query, column) takes the first ncells centroids of the column in rank order (NaN first,
-//      higher score, lower index), one block-wide maximum per cell over 64-bit (score image, ~index) keys: keys are distinct, so
+//      higher score, lower index), one block-wide maximum per cell over the 64-bit keys of rank_order.h: keys are distinct, so
 //      the result does not depend on scheduling.
 //   2  plaid_bitmaps_kernel: per query the cell set and keep[c] = (max_j S[c][j] >= threshold; a NaN in the row: false) as bitmaps
 //      of C bits.  A workgroup owns 256 centroids: the cell bits meet in LDS (ds_or), keep bits by ballot; no global atomics.
@@ -20,41 +20,28 @@
 //      is walked once per block of 64 and the chain goes on.  A1 and A2 go to two dense rows [nq][n].
 //   4  rr_launch_topk_select (bank_search.hip, unchanged) over the A1 row: the first min(ndocs, n) per query; ties by bank index.
 //   5  plaid_list_select_kernel: stage-1 survivors (A1 != -inf) ordered by A2, the first ndocs / 4 kept, with their count.
-//   6  plaid_exact_list_kernel: the tile loop of bank_search_scores_kernel (same operand source, same matrix-core chain per entry,
-//      same column sum: the bits of rr_bank_search), a workgroup's passages taken from the stage-2 list of its query, one per
-//      wave; the exact score overwrites the passage's entry of the A2 row.
+//   6  rr_launch_bank_search_scores_listed (bank_search.hip): bank_search_scores_kernel itself, the kernel of rr_bank_search, with
+//      a workgroup's passages picked from the stage-2 list of its query, one per wave (pick_list); the exact score overwrites
+//      the passage's entry of the A2 row.
 //   7  plaid_list_select_kernel again: by exact score, the first k; -1 / -inf behind the count, and the count.
 // -inf is the "absent" mark of every row and list: an entry that holds it at some stage is not a survivor of that stage.
-// rr_plaid_prune_host restates cells, candidates, stage 1 and stage 2 in host code: the written-down definition.
+// The rank order of every list (NaN first, higher score, lower index) and its 64-bit key are those of rr_bank_search: rank_order.h
+// (the bitonic network over keys is written out in plaid_list_select_kernel as in topk_select_kernel; rank_order.h says why).
+// rr_plaid_prune_host restates cells, candidates, stage 1 and stage 2 in host code over the same key: the written-down definition.
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstring>
-#include <type_traits>
 #include <vector>
 
 #include "li_sources.h"
+#include "rank_order.h"
 #include "rr_common.h"
 
 namespace {
 
 constexpr int PS_CHUNK = 64;             // passages per workgroup of the scan (16 per wave)
-constexpr int PL_CHUNK = 4;              // passages per workgroup of the list-driven exact kernel (one per wave)
-constexpr int PL_JT_MAX = 8;
 constexpr int LIST_MAX = 1024;           // entries plaid_list_select_kernel sorts (ndocs)
 constexpr int PSEUDO = 64;               // centroids per pseudo-passage of stage 0
-
-// the order-preserving image of a score (bank_search.hip score_key): NaN above +inf, -0 as +0; never 0
-__device__ __host__ __forceinline__ uint32_t plaid_score_key(float s) {
-  if (s != s) return 0xffffffffu;
-  uint32_t u;
-  memcpy(&u, &s, 4);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __host__ __forceinline__ unsigned long long plaid_key(float s, uint32_t idx) {
-  return ((unsigned long long)plaid_score_key(s) << 32) | (unsigned long long)(0xffffffffu - idx);
-}
 
 __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int m) {
   const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
@@ -80,7 +67,7 @@ __global__ __launch_bounds__(256) void plaid_cells_kernel(const float* __restric
   for (int r = 0; r < ncells; ++r) {
     unsigned long long best = 0ull;                           // below every key
     for (int c = tid; c < C; c += 256) {
-      const unsigned long long key = plaid_key(col[(size_t)c * s_ld], (uint32_t)c);
+      const unsigned long long key = rank_key(col[(size_t)c * s_ld], (uint32_t)c);
       if ((r == 0 || key < prev) && key > best) best = key;
     }
 #pragma unroll
@@ -91,7 +78,7 @@ __global__ __launch_bounds__(256) void plaid_cells_kernel(const float* __restric
     if ((tid & 63) == 0) wbest[r & 1][tid >> 6] = best;
     __syncthreads();                                          // (the buffers alternate: one barrier per cell)
     prev = max(max(wbest[r & 1][0], wbest[r & 1][1]), max(wbest[r & 1][2], wbest[r & 1][3]));
-    if (tid == 0) cells[((size_t)q * Lqc + j) * ncells + r] = (int32_t)(0xffffffffu - (uint32_t)prev);
+    if (tid == 0) cells[((size_t)q * Lqc + j) * ncells + r] = (int32_t)rank_key_index(prev);
   }
 }
 
@@ -124,11 +111,6 @@ __global__ __launch_bounds__(256) void plaid_bitmaps_kernel(const float* __restr
     cellbits[(size_t)q * W + blockIdx.x * 8 + tid] = cb[tid];
     keepbits[(size_t)q * W + blockIdx.x * 8 + tid] = kb[tid];
   }
-}
-
-__device__ __forceinline__ long long uniform_i64(int64_t v) {
-  return (long long)(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
-                     (uint32_t)__builtin_amdgcn_readfirstlane((int)v));
 }
 
 __global__ __launch_bounds__(256) void plaid_scan_kernel(const float* __restrict__ S, long long s_q, int s_ld, int C, int Lqc,
@@ -218,7 +200,7 @@ __global__ __launch_bounds__(256) void plaid_list_select_kernel(const float* __r
     if (i < cnt) {
       const int idx = list_in[(size_t)q * in_ld + i];
       const float s = row[idx];
-      if (s != -INFINITY && (!valid_row || valid_row[(size_t)q * n + idx] != -INFINITY)) kv = plaid_key(s, (uint32_t)idx);
+      if (s != -INFINITY && (!valid_row || valid_row[(size_t)q * n + idx] != -INFINITY)) kv = rank_key(s, (uint32_t)idx);
     }
     key[i] = kv;
   }
@@ -228,7 +210,7 @@ __global__ __launch_bounds__(256) void plaid_list_select_kernel(const float* __r
       for (int i = tid; i < n2; i += 256) {
         const int l = i ^ j;
         if (l > i) {
-          const bool up = (i & kk) == 0;
+          const bool up = (i & kk) == 0;                      // a run in rank order (larger key first)
           const unsigned long long a = key[i], b = key[l];
           if (up ? a < b : a > b) { key[i] = b; key[l] = a; }
         }
@@ -244,7 +226,7 @@ __global__ __launch_bounds__(256) void plaid_list_select_kernel(const float* __r
     int32_t o = -1;
     float s = -INFINITY;
     if (i < kept) {
-      const int idx = (int)(0xffffffffu - (uint32_t)key[i]);
+      const int idx = (int)rank_key_index(key[i]);
       o = idx + add;
       s = row[idx];
     }
@@ -254,143 +236,15 @@ __global__ __launch_bounds__(256) void plaid_list_select_kernel(const float* __r
   if (tid == 0) cnt_out[q] = kept;
 }
 
-// bank_search_scores_kernel's passage loop (bank_search.hip) with the passages of a workgroup taken from list[q][p0 .. p0 + 4) and
-// the score written to the passage's entry of the dense row out[q][.].  The tile step is that kernel's, written out (li_sources.h).
-template <int JT, class SRC>
-__global__ __launch_bounds__(256) void plaid_exact_list_kernel(const float* __restrict__ query_li, const SRC src,
-                                                               const rr_bank_slot* __restrict__ table, int n, int nq,
-                                                               const int32_t* __restrict__ list, int list_ld, const int32_t* __restrict__ cnt,
-                                                               int Lq, int D, float* __restrict__ out) {
-  constexpr int JB = 16 * JT;
-  extern __shared__ __attribute__((aligned(16))) float qblk[];
-  __shared__ float psum[PL_CHUNK];
-  const int ldq = D + 4;
-  const int q = blockIdx.x % nq, p0 = (blockIdx.x / nq) * PL_CHUNK;
-  const int have = cnt[q];
-  if (p0 >= have) return;                                     // the whole workgroup
-  const int pn = min(PL_CHUNK, have - p0);
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int li = lane & 15, g = lane >> 4;
-  const float* Q = query_li + (size_t)q * Lq * D;
-  uint16_t* tile = SRC::TILE ? (uint16_t*)(qblk + JB * ldq) + wave * 16 * (D + LI_TILE_PAD) : nullptr;
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-
-  for (int j0 = 0; j0 < Lq; j0 += JB) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < JB * (D / 4); i += 256) {
-      const int row = i / (D / 4), col = (i - row * (D / 4)) * 4;
-      *(f32x4*)(qblk + row * ldq + col) = j0 + row < Lq ? *(const f32x4*)(Q + (size_t)(j0 + row) * D + col) : zero4;
-    }
-    __syncthreads();
-    const bool last = j0 + JB >= Lq;
-    for (int i = wave; i < pn; i += 4) {
-      const int pi = min(max(__builtin_amdgcn_readfirstlane(list[(size_t)q * list_ld + p0 + i]), 0), n - 1);
-      const rr_bank_slot sl = table[pi];
-      const long long first_row = uniform_i64(sl.first_row);
-      const typename SRC::pair_t pr = src.of(first_row, __builtin_amdgcn_readfirstlane(sl.len), q, 0, D);
-      const int len = pr.len, c_tiles = (len + 15) / 16;
-      float cmax[JT];
-#pragma unroll
-      for (int t = 0; t < JT; ++t) cmax[t] = -INFINITY;
-      for (int ct = 0; ct < c_tiles; ++ct) {
-        const int c = ct * 16 + li;
-        const bool c_ok = c < len;
-        f32x4 acc[JT];
-#pragma unroll
-        for (int t = 0; t < JT; ++t) acc[t] = zero4;
-        if constexpr (SRC::TILE) {
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          src.stage(pr, ct, D, lane, tile);
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-        const typename SRC::cursor crow = src.row(pr, c_ok ? c : 0, g, D, li, tile);
-        const float* qrow = qblk + li * ldq + 4 * g;
-        f32x4 a = c_ok ? SRC::at(crow, 0) : zero4;
-        for (int d = 0; d < D; d += 16) {
-          const f32x4 a_n = (c_ok && d + 16 < D) ? SRC::at(crow, d + 16) : zero4;
-          f32x4 b[JT];
-#pragma unroll
-          for (int t = 0; t < JT; ++t) b[t] = *(const f32x4*)(qrow + t * 16 * ldq + d);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-#pragma unroll
-            for (int t = 0; t < JT; ++t)
-              acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b[t][e], acc[t], 0, 0, 0);
-          }
-          a = a_n;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = ct * 16 + 4 * g + r;
-          if (row >= len) continue;
-          const bool keep = src.keep(pr, row);
-#pragma unroll
-          for (int t = 0; t < JT; ++t)
-            if (j0 + t * 16 + li < Lq) cmax[t] = nan_max(cmax[t], keep ? acc[t][r] : LI_MASKED);
-        }
-      }
-      float sum = j0 ? psum[i] : 0.0f;
-#pragma unroll
-      for (int t = 0; t < JT; ++t) {
-        float v = cmax[t];
-        v = nan_max(v, __shfl_xor(v, 16, 64));
-        v = nan_max(v, __shfl_xor(v, 32, 64));
-#pragma unroll
-        for (int l = 0; l < 16; ++l) {
-          const float x = __shfl(v, l, 64);
-          if (j0 + t * 16 + l < Lq) sum += x;
-        }
-      }
-      if (lane == 0) {
-        if (last) out[(size_t)q * n + pi] = sum;
-        else psum[i] = sum;
-      }
-    }
-  }
-}
-
-template <int JT, class SRC>
-hipError_t exact_launch_jt(const rr_plaid_search_args& a, const SRC& src, const int32_t* list, int list_ld, const int32_t* cnt, size_t lds,
-                           float* out, hipStream_t st) {
-  static std::atomic<unsigned long long> attr_set{0};
-  const hipError_t e = li_lds_attr((const void*)plaid_exact_list_kernel<JT, SRC>, attr_set);
-  if (e != hipSuccess) return e;
-  const long long blocks = (long long)((list_ld + PL_CHUNK - 1) / PL_CHUNK) * a.nq;
-  hipLaunchKernelGGL((plaid_exact_list_kernel<JT, SRC>), dim3((unsigned)blocks), dim3(256), lds, st, a.query_li, src, a.table, a.n, a.nq,
-                     list, list_ld, cnt, a.Lq, a.D, out);
-  return hipGetLastError();
-}
-
-hipError_t exact_launch(const rr_plaid_search_args& a, const int32_t* list, int list_ld, const int32_t* cnt, float* out, hipStream_t st) {
-  return li_with_bank_source(nullptr, nullptr, a.bank, a.D, [&](const auto& src, size_t tile_bytes) -> hipError_t {
-    using SRC = std::decay_t<decltype(src)>;
-    if constexpr (!SRC::TILE) {
-      return hipErrorInvalidValue;                            // compressed banks only
-    } else {
-      size_t lds = 0;
-      const int jt = li_pick_jt(a.Lq, a.D, tile_bytes, (size_t)72 * 1024, &lds);
-      if (jt == 0) return hipErrorInvalidValue;
-      if (jt == 1) return exact_launch_jt<1>(a, src, list, list_ld, cnt, lds, out, st);
-      if (jt == 2) return exact_launch_jt<2>(a, src, list, list_ld, cnt, lds, out, st);
-      if (jt == 4) return exact_launch_jt<4>(a, src, list, list_ld, cnt, lds, out, st);
-      return exact_launch_jt<PL_JT_MAX>(a, src, list, list_ld, cnt, lds, out, st);
-    }
-  });
-}
-
 size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 // the order of the lists on the host: NaN first, higher score, lower index
-bool ranks_before(float sa, int ia, float sb, int ib) { return plaid_key(sa, (uint32_t)ia) > plaid_key(sb, (uint32_t)ib); }
+bool ranks_before(float sa, int ia, float sb, int ib) { return rank_key(sa, (uint32_t)ia) > rank_key(sb, (uint32_t)ib); }
 float host_nan_max(float m, float v) { return (v > m || v != v) ? v : m; }
 
 }  // namespace
 
-bool rr_plaid_search_shape_ok(int n_centroids, int ndocs) { return n_centroids >= 1 && n_centroids <= RR_PLAID_SEARCH_MAX_CENTROIDS && ndocs <= LIST_MAX; }
-
-rr_plaid_search_layout rr_plaid_search_plan(int nq, int n, int C, int Lq, int Lqc, int ncells, int ndocs, int k) {
+rr_plaid_search_layout rr_plaid_search_plan(int nq, int n, int C, int Lq, int Lqc, int ncells, int ndocs) {
   rr_plaid_search_layout l{};
   l.Cp = (C + PSEUDO - 1) / PSEUDO * PSEUDO;
   l.W = (C + 31) / 32;
@@ -413,7 +267,6 @@ rr_plaid_search_layout rr_plaid_search_plan(int nq, int n, int C, int Lq, int Lq
   l.tmp_a = take(l.tmp_entries * sizeof(int32_t));
   l.tmp_b = take(l.tmp_entries * sizeof(int32_t));
   l.total = off;
-  (void)k;
   return l;
 }
 
@@ -466,7 +319,7 @@ hipError_t rr_launch_plaid_search_stage(int stage, const rr_plaid_search_args& a
                          std::min(a.ndocs / 4, l.k2), list2, l.k2, cnt2, 0, nullptr);
       return hipGetLastError();
     case 6:
-      return exact_launch(a, list2, l.k2, cnt2, a2, st);
+      return rr_launch_bank_search_scores_listed(a.table, a.n, a.nq, a.Lq, a.D, a.query_li, a.bank, list2, l.k2, cnt2, a2, st);
     case 7:
       hipLaunchKernelGGL(plaid_list_select_kernel, dim3((unsigned)a.nq), dim3(256), 0, st, a2, nullptr, (long long)a.n, list2, l.k2, cnt2, 0,
                          a.k, a.indices_out, a.k, a.counts_out, a.first, a.scores_out);

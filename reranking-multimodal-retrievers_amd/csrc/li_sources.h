@@ -1,10 +1,10 @@
 // The bank-side operand sources of the late-interaction score kernels, shared by li_scores.hip (one workgroup per pair,
-// rr_bank_li_scores) and bank_search.hip (one wave per passage, rr_bank_search): where the four floats a lane feeds to one
-// v_mfma_f32_16x16x4_f32 step come from.  One definition, so that both kernels run the same instruction sequence on the same
-// float32 values (li_scores.hip's header comment describes the sources).  The rest of what the two kernels share lives here too:
+// rr_bank_li_scores) and bank_search.hip (one wave per passage, rr_bank_search and stage 6 of rr_bank_search_plaid): where the
+// four floats a lane feeds to one v_mfma_f32_16x16x4_f32 step come from.  One definition, so that both kernels run the same
+// instruction sequence on the same float32 values (li_scores.hip's header comment describes the sources).  The rest of what the two kernels share lives here too:
 //   li_with_bank_source an rr_bank_view as the source a kernel template takes (li_src_f16 or li_src_plaid<NBITS>), with the checks
-//                       of each kind: the one place the two launchers (rr_launch_bank_li_scores, rr_launch_bank_search_scores)
-//                       decide between fp16 and compressed;
+//                       of each kind: the one place the launchers (rr_launch_bank_li_scores, rr_launch_bank_search_scores and
+//                       its _listed form) decide between fp16 and compressed;
 //   li_lds_attr / li_pick_jt   the launch rule: the dynamic-LDS attribute once per device, the width of the column block.
 // The tile step of the two kernels is NOT here: moved into one __forceinline__ function it changed the instruction stream of every
 // instantiation of both kernels (same registers, LDS and instruction counts within 3, another schedule), so each body keeps its copy.

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <cstring>
 #include <exception>
+#include <functional>
 #include <limits>
 #include <map>
 #include <new>
@@ -2793,33 +2794,48 @@ static int bank_table_current(rr_model* m, rr_bank* b, hipStream_t st) {
   return RR_OK;
 }
 
-// rr_bank_search (include/rerank_mi355.h): every check on the host first; then the bank's device table is brought up to date
-// (only after an add), one scoring launch over the range and the selection passes
+// What rr_bank_search and rr_bank_search_plaid (`pruned`: compressed banks only, counts_out) do alike before their first launch: the
+// shared checks, the range resolved into (first_passage, *n), then `limits(n)`, the call's own refusals, where they have always stood;
+// the device, the bank's table brought up to date, and *rows: the rows of the range (passages lie back to back), for the profile
+static int bank_search_begin(rr_model* m, const char* what, bool pruned, rr_bank* b, const float* query_li, int n_queries, int Lq,
+                             int32_t first_passage, int32_t n_passages, const int32_t* indices_out, const float* scores_out,
+                             const int32_t* counts_out, hipStream_t st, int* n, double* rows, const std::function<int(int)>& limits) {
+  if (!b || !query_li || !indices_out || (pruned && !counts_out)) return fail(m, RR_ERR_BAD_ARG, "%s: null argument", what);
+  RR_TRY(bank_usable(m, what, b));
+  if (pruned && !b->nbits) return fail(m, RR_ERR_UNSUPPORTED, "%s: an fp16 bank (compressed banks only: the stages read the centroid codes)", what);
+  if (m->cfg.li_dim % 16) return fail(m, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a multiple of 16)", what, m->cfg.li_dim);
+  if (((uintptr_t)query_li) & 15) return fail(m, RR_ERR_BAD_ARG, "%s: query_li must be 16-byte aligned", what);
+  if ((((uintptr_t)indices_out) | ((uintptr_t)scores_out) | ((uintptr_t)counts_out)) & 3) return fail(m, RR_ERR_BAD_ARG, "%s: misaligned output", what);
+  if (n_queries <= 0 || n_queries > 65535 || Lq <= 0) return fail(m, RR_ERR_BAD_SHAPE, "%s: n_queries=%d (1..65535) Lq=%d", what, n_queries, Lq);
+  const long long held = (long long)b->first.size(), n_ll = n_passages == -1 ? held - (long long)first_passage : (long long)n_passages;
+  if (first_passage < 0 || n_ll <= 0 || (long long)first_passage + n_ll > held)
+    return fail(m, RR_ERR_BAD_SHAPE, "%s: passages [%d, %d + %lld) of a bank that holds %lld", what, first_passage, first_passage, n_ll, held);
+  *n = (int)n_ll;
+  RR_TRY(limits(*n));
+  RR_TRY(capture_guard(m, st, "%s cannot be captured into a graph (it may upload the bank's passage table and grow its block)", what));
+  RR_HIP(m, hipSetDevice(m->cfg.device));
+  RR_TRY(bank_table_current(m, b, st));
+  const size_t last = (size_t)first_passage + (size_t)*n - 1;
+  *rows = (double)(b->first[last] + b->len[last] - b->first[(size_t)first_passage]);
+  return RR_OK;
+}
+
+// rr_bank_search (include/rerank_mi355.h): one scoring launch over the range and the selection passes
 static int bank_search_call(rr_handle h, rr_bank* b, const float* query_li, int n_queries, int Lq, int32_t first_passage,
                             int32_t n_passages, int k, int32_t* indices_out, float* scores_out, void* hip_stream) {
   const char* what = "rr_bank_search";
   if (!h) return RR_ERR_BAD_ARG;
   rr_model* m = h;
-  const rr_config& c = m->cfg;
-  if (!b || !query_li || !indices_out) return fail(m, RR_ERR_BAD_ARG, "%s: null argument", what);
-  RR_TRY(bank_usable(m, what, b));
-  const int D = c.li_dim;
-  if (D % 16) return fail(m, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a multiple of 16)", what, D);
-  if (((uintptr_t)query_li) & 15) return fail(m, RR_ERR_BAD_ARG, "%s: query_li must be 16-byte aligned", what);
-  if ((((uintptr_t)indices_out) | ((uintptr_t)scores_out)) & 3) return fail(m, RR_ERR_BAD_ARG, "%s: misaligned output", what);
-  if (n_queries <= 0 || n_queries > 65535 || Lq <= 0)
-    return fail(m, RR_ERR_BAD_SHAPE, "%s: n_queries=%d (1..65535) Lq=%d", what, n_queries, Lq);
-  const long long held = (long long)b->first.size();
-  const long long n_ll = n_passages == -1 ? held - (long long)first_passage : (long long)n_passages;
-  if (first_passage < 0 || n_ll <= 0 || (long long)first_passage + n_ll > held)
-    return fail(m, RR_ERR_BAD_SHAPE, "%s: passages [%d, %d + %lld) of a bank that holds %lld", what, first_passage, first_passage, n_ll, held);
-  const int n = (int)n_ll;
-  if (k < 1 || k > n) return fail(m, RR_ERR_BAD_SHAPE, "%s: k=%d of %d passages", what, k, n);
-  if (k > 1024) return fail(m, RR_ERR_UNSUPPORTED, "%s: k=%d (at most 1024: a selection pass keeps k of 4096)", what, k);
   hipStream_t st = (hipStream_t)hip_stream;
-  RR_TRY(capture_guard(m, st, "%s cannot be captured into a graph (it may upload the bank's passage table and grow its block)", what));
-  RR_HIP(m, hipSetDevice(c.device));
-  RR_TRY(bank_table_current(m, b, st));
+  int n = 0;
+  double rows = 0.0;
+  RR_TRY(bank_search_begin(m, what, false, b, query_li, n_queries, Lq, first_passage, n_passages, indices_out, scores_out, nullptr, st, &n, &rows,
+                           [&](int np) {
+                             if (k < 1 || k > np) return fail(m, RR_ERR_BAD_SHAPE, "%s: k=%d of %d passages", what, k, np);
+                             if (k > 1024) return fail(m, RR_ERR_UNSUPPORTED, "%s: k=%d (at most 1024: a selection pass keeps k of 4096)", what, k);
+                             return (int)RR_OK;
+                           }));
+  const int D = m->cfg.li_dim;
   const size_t sc_bytes = (((size_t)n_queries * n * sizeof(float)) + 15) & ~(size_t)15;
   const size_t tmp_bytes = ((rr_topk_select_scratch(n_queries, n, k) * sizeof(int32_t)) + 15) & ~(size_t)15;
   RR_TRY(ensure_block(m, m->search_blk, m->search_blk_cap, sc_bytes + 2 * tmp_bytes, st, "the bank search's block"));
@@ -2828,8 +2844,6 @@ static int bank_search_call(rr_handle h, rr_bank* b, const float* query_li, int 
   int32_t* tmp_a = tmp_bytes ? (int32_t*)(m->search_blk + sc_bytes) : nullptr;
   int32_t* tmp_b = tmp_bytes ? (int32_t*)(m->search_blk + sc_bytes + tmp_bytes) : nullptr;
   m->last_stream = st;
-  const size_t last = (size_t)first_passage + (size_t)n - 1;
-  const double rows = (double)(b->first[last] + b->len[last] - b->first[(size_t)first_passage]);      // passages lie back to back
   const rr_bank_view bank = bank_view(b);
   // bytes: the range's rows and mask bytes once (the queries of a chunk run side by side), the table, the query block per
   // workgroup of 16 passages, one float per (query, passage)
@@ -2902,45 +2916,30 @@ static int plaid_search_limits(int n_centroids, int n, int Lq, int Lq_coarse, in
   return RR_OK;
 }
 
-// rr_bank_search_plaid (include/rerank_mi355.h): every check on the host first; then the table as rr_bank_search brings it up to
-// date, the block, and the eight stages of bank_search_plaid.hip, each booked on its own
+// rr_bank_search_plaid (include/rerank_mi355.h): the block, and the eight stages of bank_search_plaid.hip, each booked on its own
 static int bank_search_plaid_call(rr_handle h, rr_bank* b, const float* query_li, int n_queries, int Lq, int Lq_coarse, int32_t first_passage,
                                   int32_t n_passages, int ncells, float threshold, int ndocs, int k, int32_t* indices_out, float* scores_out,
                                   int32_t* counts_out, void* hip_stream) {
   const char* what = "rr_bank_search_plaid";
   if (!h) return RR_ERR_BAD_ARG;
   rr_model* m = h;
-  const rr_config& c = m->cfg;
-  if (!b || !query_li || !indices_out || !counts_out) return fail(m, RR_ERR_BAD_ARG, "%s: null argument", what);
-  RR_TRY(bank_usable(m, what, b));
-  if (!b->nbits) return fail(m, RR_ERR_UNSUPPORTED, "%s: an fp16 bank (compressed banks only: the stages read the centroid codes)", what);
-  const int D = c.li_dim;
-  if (D % 16) return fail(m, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a multiple of 16)", what, D);
-  if (((uintptr_t)query_li) & 15) return fail(m, RR_ERR_BAD_ARG, "%s: query_li must be 16-byte aligned", what);
-  if ((((uintptr_t)indices_out) | ((uintptr_t)scores_out) | ((uintptr_t)counts_out)) & 3) return fail(m, RR_ERR_BAD_ARG, "%s: misaligned output", what);
-  if (n_queries <= 0 || n_queries > 65535 || Lq <= 0)
-    return fail(m, RR_ERR_BAD_SHAPE, "%s: n_queries=%d (1..65535) Lq=%d", what, n_queries, Lq);
-  const long long held = (long long)b->first.size();
-  const long long n_ll = n_passages == -1 ? held - (long long)first_passage : (long long)n_passages;
-  if (first_passage < 0 || n_ll <= 0 || (long long)first_passage + n_ll > held)
-    return fail(m, RR_ERR_BAD_SHAPE, "%s: passages [%d, %d + %lld) of a bank that holds %lld", what, first_passage, first_passage, n_ll, held);
-  const int n = (int)n_ll;
-  const char* msg;
-  if (const int rc = plaid_search_limits(b->n_centroids, n, Lq, Lq_coarse, ncells, ndocs, k, &msg))
-    return fail(m, rc, "%s: %s (Lq=%d Lq_coarse=%d ncells=%d ndocs=%d k=%d, %d passages, %d centroids)", what, msg, Lq, Lq_coarse, ncells, ndocs, k,
-                n, b->n_centroids);
   hipStream_t st = (hipStream_t)hip_stream;
-  RR_TRY(capture_guard(m, st, "%s cannot be captured into a graph (it may upload the bank's passage table and grow its block)", what));
-  RR_HIP(m, hipSetDevice(c.device));
-  RR_TRY(bank_table_current(m, b, st));
-  const rr_plaid_search_layout l = rr_plaid_search_plan(n_queries, n, b->n_centroids, Lq, Lq_coarse, ncells, ndocs, k);
+  int n = 0;
+  double rows = 0.0;
+  RR_TRY(bank_search_begin(m, what, true, b, query_li, n_queries, Lq, first_passage, n_passages, indices_out, scores_out, counts_out, st, &n, &rows,
+                           [&](int np) {
+                             const char* msg;
+                             const int rc = plaid_search_limits(b->n_centroids, np, Lq, Lq_coarse, ncells, ndocs, k, &msg);
+                             return rc ? fail(m, rc, "%s: %s (Lq=%d Lq_coarse=%d ncells=%d ndocs=%d k=%d, %d passages, %d centroids)", what, msg, Lq,
+                                              Lq_coarse, ncells, ndocs, k, np, b->n_centroids) : (int)RR_OK;
+                           }));
+  const int D = m->cfg.li_dim;
+  const rr_plaid_search_layout l = rr_plaid_search_plan(n_queries, n, b->n_centroids, Lq, Lq_coarse, ncells, ndocs);
   m->plaid_last_ok = false;
   RR_TRY(ensure_block(m, m->search_blk, m->search_blk_cap, l.total, st, "the bank search's block"));
   m->last_stream = st;
   const rr_plaid_search_args a{n_queries, n, first_passage, Lq, Lq_coarse, D, ncells, ndocs, k, threshold, query_li, b->table + first_passage,
                                bank_view(b), m->search_blk, indices_out, scores_out, counts_out};
-  const size_t last = (size_t)first_passage + (size_t)n - 1;
-  const double rows = (double)(b->first[last] + b->len[last] - b->first[(size_t)first_passage]);
   const double nq = n_queries, C = l.Cp, SLq = 4.0 * Lq_coarse;
   // FLOPs: stage 0 exactly; stage 6 for ndocs / 4 survivors of the range's mean length (their number is known on the device only:
   // an upper bound).  Bytes: what a stage must read and write once; the scan's candidates add a row of S per unmasked row.
@@ -3027,7 +3026,7 @@ static int rr_op_bank_search_plaid_impl(const float* query_li, int n_queries, in
   const char* msg;
   if (const int rc = plaid_search_limits(n_centroids, n_passages, Lq, Lq_coarse, ncells, ndocs, k, &msg)) return rc;
   hipStream_t st = (hipStream_t)hip_stream;
-  const rr_plaid_search_layout l = rr_plaid_search_plan(n_queries, n_passages, n_centroids, Lq, Lq_coarse, ncells, ndocs, k);
+  const rr_plaid_search_layout l = rr_plaid_search_plan(n_queries, n_passages, n_centroids, Lq, Lq_coarse, ncells, ndocs);
   char* blk = nullptr;
   if (hipMalloc((void**)&blk, l.total) != hipSuccess) { (void)hipGetLastError(); return RR_ERR_OOM; }
   const rr_bank_view bank{nbits, n_centroids, nullptr, codes, residuals, centroids_f16, bucket_weights, mask_bytes};

@@ -481,6 +481,11 @@ hipError_t rr_launch_bank_li_scores(const rr_bank_pair* pairs, const int32_t* sl
 // stable descending sort (NaN first, ties by ascending index), indices + add; tmp_a / tmp_b hold rr_topk_select_scratch int32 each
 hipError_t rr_launch_bank_search_scores(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
                                         const rr_bank_view& bank, float* out, hipStream_t st);
+// the same for the passages list[q][0 .. cnt[q]) of every query (cnt[q] <= list_ld; entries of table[0 .. n)), written to the
+// passage's entry of the dense out [nq][n]; compressed banks only
+hipError_t rr_launch_bank_search_scores_listed(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
+                                               const rr_bank_view& bank, const int32_t* list, int list_ld, const int32_t* cnt, float* out,
+                                               hipStream_t st);
 size_t rr_topk_select_scratch(int n_lists, int n, int k);
 hipError_t rr_launch_topk_select(const float* scores, int n_lists, int n, int k, int add, int32_t* tmp_a, int32_t* tmp_b,
                                  int32_t* indices_out, float* scores_out, hipStream_t st);
@@ -505,8 +510,7 @@ struct rr_plaid_search_layout {
   int Cp, W, k1, k2;          // centroids rounded up to 64; words of a bitmap; entries of a stage-1 / stage-2 list
   size_t S, pairs, ones, cells, cellbits, keepbits, a1, a2, list1, list2, cnt2, tmp_a, tmp_b, tmp_entries, total;
 };
-bool rr_plaid_search_shape_ok(int n_centroids, int ndocs);
-rr_plaid_search_layout rr_plaid_search_plan(int nq, int n, int C, int Lq, int Lqc, int ncells, int ndocs, int k);
+rr_plaid_search_layout rr_plaid_search_plan(int nq, int n, int C, int Lq, int Lqc, int ncells, int ndocs);
 hipError_t rr_launch_plaid_search_stage(int stage, const rr_plaid_search_args& a, const rr_plaid_search_layout& l, hipStream_t st);
 bool rr_plaid_prune_host(const float* S, int C, int Lqc, int s_ld, const int32_t* codes, const uint8_t* mask, const int32_t* lengths,
                          int n, int ncells, float thr, int ndocs, uint8_t* cells_out, float* a1_out, float* a2_out, int32_t* list1_out,

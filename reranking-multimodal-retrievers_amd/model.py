@@ -188,6 +188,25 @@ def _ptrs(out: dict) -> list:
     return [L.ptr(out[k]) for k in ("logits", "logits2", "loss", "scores", "order") if k in out]
 
 
+def _bank_search_args(eng, name: str, bank, query_li: torch.Tensor, first: int, count: Optional[int], compressed_only: bool = False):
+    """What RerankEngine.bank_search and bank_search_plaid (`name`) check and prepare alike: (first, n, n_queries, Lq, the queries
+    as contiguous float32 on the engine's device)."""
+    D = eng.arch["li_dim"]
+    if query_li.dim() != 3 or query_li.shape[2] != D:
+        raise ValueError(f"query_li {tuple(query_li.shape)}: [n_queries, Lq, {D}]")
+    if compressed_only and getattr(bank, "codec", None) is None:
+        raise NotImplementedError(f"{name}: an fp16 bank (the pruned search reads the centroid codes of a compressed bank)")
+    held = len(bank)
+    first = int(first)
+    n = held - first if count is None else int(count)
+    if first < 0 or n < 1 or first + n > held:
+        raise ValueError(f"{name}: passages [{first}, {first} + {n}) of a bank that holds {held}")
+    nq, Lq = int(query_li.shape[0]), int(query_li.shape[1])
+    if nq < 1 or Lq < 1:
+        raise ValueError(f"query_li {tuple(query_li.shape)}: no query tokens")
+    return first, n, nq, Lq, query_li.to(device=eng.device, dtype=torch.float32).contiguous()
+
+
 class RerankEngine:
     """Owns one `rr_handle` (one model replica on one GPU)."""
 
@@ -842,23 +861,12 @@ class RerankEngine:
         bank_li_scores), and per query the k best are returned in the order of torch.sort(descending=True, stable=True):
         {"indices": int32 [n_queries, k] dense bank indices, "scores": float32 [n_queries, k]}, both on the device.
         1 <= k <= min(count, 1024) (ValueError / NotImplementedError).  NORMAL and MORES engines, weights loaded or not."""
-        D = self.arch["li_dim"]
-        if query_li.dim() != 3 or query_li.shape[2] != D:
-            raise ValueError(f"query_li {tuple(query_li.shape)}: [n_queries, Lq, {D}]")
-        held = len(bank)
-        first = int(first)
-        n = held - first if count is None else int(count)
-        if first < 0 or n < 1 or first + n > held:
-            raise ValueError(f"bank_search: passages [{first}, {first} + {n}) of a bank that holds {held}")
+        first, n, nq, Lq, q = _bank_search_args(self, "bank_search", bank, query_li, first, count)
         k = int(k)
         if k < 1 or k > n:
             raise ValueError(f"bank_search: k = {k} of {n} passages")
         if k > 1024:
             raise NotImplementedError(f"bank_search: k = {k} (at most 1024)")
-        nq, Lq = int(query_li.shape[0]), int(query_li.shape[1])
-        if nq < 1 or Lq < 1:
-            raise ValueError(f"query_li {tuple(query_li.shape)}: no query tokens")
-        q = query_li.to(device=self.device, dtype=torch.float32).contiguous()
         out = dict(indices=torch.empty((nq, k), device=self.device, dtype=torch.int32),
                    scores=torch.empty((nq, k), device=self.device, dtype=torch.float32))
         L.check(self.lib.rr_bank_search(self.h, bank.h, L.ptr(q), nq, Lq, first, n, k, L.ptr(out["indices"]), L.ptr(out["scores"]),
@@ -873,20 +881,8 @@ class RerankEngine:
         of bank_search.  {"indices": int32 [n_queries, k] dense bank indices, -1 behind the count; "scores": float32
         [n_queries, k], -inf there; "counts": int32 [n_queries]}, on the device.  1 <= ncells <= min(centroids, 16),
         4 <= ndocs <= 1024, 1 <= k <= min(ndocs // 4, count) (ValueError / NotImplementedError before the library)."""
-        D = self.arch["li_dim"]
-        if query_li.dim() != 3 or query_li.shape[2] != D:
-            raise ValueError(f"query_li {tuple(query_li.shape)}: [n_queries, Lq, {D}]")
-        codec = getattr(bank, "codec", None)
-        if codec is None:
-            raise NotImplementedError("bank_search_plaid: an fp16 bank (the pruned search reads the centroid codes of a compressed bank)")
-        held = len(bank)
-        first = int(first)
-        n = held - first if count is None else int(count)
-        if first < 0 or n < 1 or first + n > held:
-            raise ValueError(f"bank_search_plaid: passages [{first}, {first} + {n}) of a bank that holds {held}")
-        nq, Lq = int(query_li.shape[0]), int(query_li.shape[1])
-        if nq < 1 or Lq < 1:
-            raise ValueError(f"query_li {tuple(query_li.shape)}: no query tokens")
+        first, n, nq, Lq, q = _bank_search_args(self, "bank_search_plaid", bank, query_li, first, count, compressed_only=True)
+        codec = bank.codec
         Lqc = Lq if coarse_tokens is None else int(coarse_tokens)
         if Lqc < 1 or Lqc > Lq:
             raise ValueError(f"bank_search_plaid: coarse_tokens = {Lqc} of {Lq} query tokens")
@@ -901,7 +897,6 @@ class RerankEngine:
             raise NotImplementedError(f"bank_search_plaid: ndocs = {ndocs} (at most 1024)")
         if k < 1 or k > min(ndocs // 4, n):
             raise ValueError(f"bank_search_plaid: k = {k} of ndocs // 4 = {ndocs // 4} survivors and {n} passages")
-        q = query_li.to(device=self.device, dtype=torch.float32).contiguous()
         out = dict(indices=torch.empty((nq, k), device=self.device, dtype=torch.int32),
                    scores=torch.empty((nq, k), device=self.device, dtype=torch.float32),
                    counts=torch.empty((nq,), device=self.device, dtype=torch.int32))

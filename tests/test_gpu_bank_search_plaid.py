@@ -205,6 +205,40 @@ def test_every_centroid_a_cell_and_no_cut_equals_bank_search(k):
     assert got["counts"].tolist() == [k, k]
 
 
+@pytest.mark.parametrize("D,nbits,Lq", [(16, 1, 40), (16, 2, 70), (64, 8, 40), (64, 4, 200)])
+def test_listed_scores_at_one_bit_and_the_64_column_block_equal_bank_search(D, nbits, Lq):
+    """The list-driven form of the scoring kernel where no other test takes it: nbits 1, the block of 64 columns (Lq 40), 128
+    columns in one block and in two.  41 passages: the last workgroup of the list holds one.  Every centroid a cell, no cut.  A
+    handle takes li_dim in multiples of 64, so both searches run through their handle-free operators (rr_op_bank_search_plaid,
+    rr_op_bank_search: the launchers of the two calls over the same rows), as the D = 16 cases of test_gpu_bank_search.py do."""
+    from rmr_amd import _lib as L
+    from test_gpu_bank_search import _table_dev
+    lib, st = L.load(), torch.cuda.current_stream().cuda_stream
+    C, P, nq = 16, 41, 2
+    codec = _codec(D, nbits, C)
+    lens = [LEN_CYCLE[i % len(LEN_CYCLE)] for i in range(P - 1)] + [1]
+    codes, res = _topic_rows(codec, lens, seed=Lq)
+    masks = [torch.ones(ln, dtype=torch.uint8) for ln in lens]
+    for m in masks[::2]:
+        m[2::3] = 0                                               # interior masked rows; every passage keeps an unmasked row
+    keep = (torch.cat(masks).cuda(), codes.cuda(), res.cuda(), codec.centroids.cuda(), codec.bucket_weights.cuda())
+    mask_p, comp = L.ptr(keep[0]), (nbits, *(L.ptr(t) for t in keep[1:]), C)
+    table = _table_dev(lens)
+    q = _near_queries(codec, nq, Lq, seed=5)
+    for first, n in ((0, P), (1, P - 2)):
+        k = n
+        wi, gi = (torch.full((nq, k), IPOISON, device="cuda", dtype=torch.int32) for _ in range(2))
+        ws, gs = (torch.full((nq, k), POISON, device="cuda") for _ in range(2))
+        gc = torch.full((nq,), IPOISON, device="cuda", dtype=torch.int32)
+        assert lib.rr_op_bank_search(L.ptr(q), nq, Lq, D, L.ptr(table), first, n, k, None, mask_p, *comp, L.ptr(wi), L.ptr(ws), st) == 0
+        assert lib.rr_op_bank_search_plaid(L.ptr(q), nq, Lq, Lq, D, L.ptr(table), first, n, C, 0.45, 1024, k, mask_p, *comp, L.ptr(gi),
+                                           L.ptr(gs), L.ptr(gc), st) == 0
+        torch.cuda.synchronize()
+        assert sorted(wi[0].tolist()) == list(range(first, first + n))
+        assert torch.equal(gi, wi) and torch.equal(gs, ws), f"first {first} n {n}"
+        assert gc.tolist() == [k, k]
+
+
 # ---- 3. short lists ----------------------------------------------------------------------------------------------------------------
 def test_short_and_empty_lists_and_nothing_else_written():
     from rmr_amd import _lib as L

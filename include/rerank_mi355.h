@@ -532,7 +532,8 @@ int rr_bank_add(rr_bank_handle b, const void* context_li, int dtype, const float
  * with "nbits": 8), decoded on the device inside the gather of rr_forward_interaction_bank.  Replaces the reference's own native
  * kernel on the retriever-to-reranker hand-over (third_party/ColBERT/colbert/indexing/codecs/decompress_residuals.cu) and the
  * F.normalize behind it (codecs/residual.py:242-278).  Bytes per token at li_dim 128: 257 as fp16, 133 / 69 / 37 / 21 at nbits 8 /
- * 4 / 2 / 1.  Nothing here compresses or computes embeddings; rr_bank_search searches exhaustively;
+ * 4 / 2 / 1.  Nothing here computes embeddings or trains a codec (k-means, quantiles); rr_bank_add_compress compresses embeddings
+ * that are on the device against the codec's tables; rr_bank_search searches exhaustively;
  * rr_bank_search_plaid runs PLAID's candidate generation and centroid pruning over the codes a compressed bank holds.
  *
  * THE DECODED ROW, for a row with code c, residual bytes r[0 .. D * nbits / 8), centroids [C, D] fp16 (the index stores them with
@@ -576,6 +577,43 @@ int rr_bank_create_plaid(rr_handle h, int64_t capacity_rows, int32_t max_passage
 int rr_bank_add_plaid(rr_bank_handle b, const int32_t* codes, const uint8_t* residuals, const uint8_t* mask, const int32_t* lengths,
                       int n, int32_t* first_index_out, void* hip_stream);
 int rr_bank_format(rr_bank_handle b, int32_t* nbits_out, int32_t* n_centroids_out, int64_t* bytes_per_row_out);
+/* ---- Compressing embeddings into a compressed bank on the device: what the reference's indexer does with
+ * ResidualCodec.compress (third_party/ColBERT/colbert/indexing/codecs/residual.py:169-221, CPU branch), from the padded tensors a
+ * retriever produces, without the [centroids x rows] score matrix that code materialises and without a host round trip.
+ *
+ * THE COMPRESSED ROW, for one kept row with input values v[0 .. D), centroids [C, D] fp16 and cutoffs[0 .. 2^nbits - 1):
+ *   1. x_e = fp16_rne(v_e): what .half() gives, what rr_bank_add stores and what the reference's indexer is handed; fp16 input
+ *      is taken as is.  Everything below uses float32(x_e).
+ *   2. S[c], the score against centroid c, is the float32 fmaf chain rr_li_scores computes for the context row float32(centroid c)
+ *      against the query column x: acc = fmaf(a_d, b_d, acc) from 0, d in the order t outer (steps of 16), e in 0..3, g in 0..3,
+ *      d = 16 t + 4 g + e (one v_mfma_f32_16x16x4_f32 after another).  Bit for bit the scores_out entry of rr_op_li_scores, and
+ *      stage 0 of rr_bank_search_plaid, for that (centroid, column).
+ *   3. code = the centroid with the largest rank key of (S[c], c), the order of the bank searches: a NaN score wins, otherwise the
+ *      highest score, and on equal scores (+0 == -0) the LOWEST centroid index.  Deterministic from run to run and independent of
+ *      how the centroid range is divided among waves and workgroups (no atomics).
+ *   4. r_e = float32(x_e) - float32(centroid[code][e]), one float32 subtraction; bucket_e = the number of cutoffs strictly below
+ *      r_e.  Every comparison with a NaN is false: a NaN residual has bucket 0 (torch.bucketize places a NaN differently; no
+ *      index holds one).
+ *   5. Packing is the inverse of THE DECODED ROW above: element e goes to byte e / (8 / nbits), group e % (8 / nbits) counted from
+ *      the most significant end, the bucket's nbits bits reversed.
+ *   6. Mask and positions exactly as rr_bank_add: a passage keeps rows 0 .. len - 1, the mask byte is (mask != 0), interior masked
+ *      rows are kept and compressed like any other row, no position moves.
+ * rr_util_plaid_compress_rows (rerank_mi355_diag.h) is this definition in host code.
+ *
+ * rr_bank_set_plaid_cutoffs: the codec's bucket cutoffs (the FIRST tensor of buckets.pt), HOST float32 [2^nbits - 1], copied to the
+ * device before the call returns.  RR_ERR_UNSUPPORTED on an fp16 bank, RR_ERR_BAD_SHAPE for a NaN or a decreasing sequence (equal
+ * neighbours are allowed).  May be called again (it then synchronises the device); the new cutoffs apply to later adds only.
+ * rr_bank_add_compress: rr_bank_add for a compressed bank: the same arguments with the same meaning, alignment, admission rules,
+ * staging and graph-capture refusal.  On success all n passages are appended; a refused call leaves the bank unchanged, and
+ * every refusal comes from the host before anything is enqueued: RR_ERR_UNSUPPORTED on an fp16 bank (use rr_bank_add), without
+ * cutoffs, and for an li_dim that is not a multiple of 16 (the matrix-core step; li_dim 8, which a compressed bank otherwise
+ * takes, is out); the rest as rr_bank_add.  It enqueues on hip_stream and does not synchronise, except when the bank's scratch
+ * (8 bytes per kept row of the call, times 1 + the number of centroid splits; grow-only) has to grow: then it synchronises the
+ * device once.  Two adds of one bank in flight on different streams would share that scratch: order them.
+ * rr_bank_add on a compressed bank still refuses.  Python: PlaidCodec(bucket_cutoffs=...), PassageBank.add_compress. */
+int rr_bank_set_plaid_cutoffs(rr_bank_handle b, const float* cutoffs_host);
+int rr_bank_add_compress(rr_bank_handle b, const void* context_li, int dtype, const float* context_mask, const int32_t* lengths, int n,
+                         int Lc, int32_t* first_index_out, void* hip_stream);
 /* rr_forward_interaction_bank: rr_forward_interaction_packed (fusion_from_li != 0: rr_forward_interaction_packed_fusion_li) with
  * the context side taken from a bank.  NORMAL and MORES handles.
  *   query_li [n_queries, Lq, li_dim], query_mask [n_queries, Lq] : DEVICE float32, per QUERY (query_li 16-byte aligned)

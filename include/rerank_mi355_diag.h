@@ -262,6 +262,30 @@ int rr_util_plaid_decode_rows(const uint16_t* centroids_f16, int32_t n_centroids
 int rr_op_plaid_decode_rows(const uint16_t* centroids_f16, int32_t n_centroids, const float* bucket_weights, int nbits, int D,
                             const int32_t* codes, const uint8_t* residuals, int64_t first_row, int64_t n_rows,
                             uint16_t* rows_out_f16, void* hip_stream);
+/* PLAID residual compression (the compressed row: rerank_mi355.h, rr_bank_add_compress; the reference's ResidualCodec.compress,
+ * codecs/residual.py:169-221).
+ * rr_util_plaid_compress_rows: pure HOST code, usable without a GPU: the definition, the score chain written as explicit fmaf in
+ * the stated order.  rows [n_rows, D] float32 (dtype RR_F32) or fp16 bits (RR_F16), centroids_f16 [n_centroids, D] fp16 bits,
+ * cutoffs float32 [2^nbits - 1] -> codes_out int32 [n_rows], residuals_out uint8 [n_rows, D * nbits / 8].  D a multiple of 16 in
+ * [16, 512] and of 8 * nbits, nbits 1, 2, 4 or 8: RR_ERR_UNSUPPORTED otherwise.
+ * rr_op_plaid_compress_rows: the two kernels of rr_bank_add_compress over raw DEVICE pointers, without a handle, at the same
+ * shapes (D = 16, 32, 48, ... that no handle takes included).  rows, centroids 16-byte aligned, residuals_out 8-byte aligned;
+ * cutoffs must not decrease (not checked: the bucket is found by binary search).  It allocates its scratch for the call and
+ * synchronises hip_stream before it returns.
+ * rr_set_tuning("compress_chunk") (0; or a multiple of 16 in [16, 2^24]): the centroids of one split of the assignment kernel; 0
+ * lets the launch choose (enough splits for about four workgroups per CU, at least 256 centroids each).  The codes do not depend on it.
+ * rr_set_tuning("compress_stop_after") (1; 0 or 1): 0 ends a call behind the assignment kernel (timing by difference; codes, bytes
+ * and mask bytes are then not written).
+ * rr_bank_read_plaid: the STORED form of one passage of a compressed bank, the raw twin of rr_bank_read: codes_out int32 [len],
+ * residuals_out uint8 [len, li_dim * nbits / 8], mask_out [len] in HOST memory (any may be NULL; all NULL = only the length),
+ * buffers of capacity_rows rows.  Synchronises hip_stream and copies synchronously.  Returns the length or < 0
+ * (RR_ERR_UNSUPPORTED on an fp16 bank). */
+int rr_util_plaid_compress_rows(const void* rows, int dtype, int64_t n_rows, int D, const uint16_t* centroids_f16, int32_t n_centroids,
+                                const float* cutoffs, int nbits, int32_t* codes_out, uint8_t* residuals_out);
+int rr_op_plaid_compress_rows(const void* rows, int dtype, int64_t n_rows, int D, const uint16_t* centroids_f16, int32_t n_centroids,
+                              const float* cutoffs, int nbits, int32_t* codes_out, uint8_t* residuals_out, void* hip_stream);
+int rr_bank_read_plaid(rr_bank_handle b, int32_t index, int32_t* codes_out, uint8_t* residuals_out, uint8_t* mask_out,
+                       int32_t capacity_rows, void* hip_stream);
 /* The score kernels of rr_li_scores and rr_bank_li_scores (rerank_mi355.h) over raw DEVICE pointers, at any D that is a multiple of
  * 16: a handle's li_dim is a multiple of 64, so D = 16 (one step of the kernel's walk over D) and D = 32 are reachable here only.
  * rr_op_li_scores: n pairs, query (pair index) / K; query_li [.., Lq, D], context_li [n, Lc, D], context_mask [n, Lc] float32;

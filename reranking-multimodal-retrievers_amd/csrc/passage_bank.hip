@@ -19,6 +19,8 @@
 //   bank_decode_plaid_kernel  rows [first_row, first_row + n) decoded to fp16 by the same device function (rr_bank_read on a
 //                       compressed bank, rr_op_plaid_decode_rows).
 //   rr_plaid_decode_rows_host  the same arithmetic in host code (rr_util_plaid_decode_rows): the bit-level definition.
+//   rr_plaid_compress_rows_host  the other direction in host code (rr_util_plaid_compress_rows): the definition bank_compress.hip's
+//                       kernels are held to.
 // LAUNCHERS: rr_launch_bank_ingest, rr_launch_bank_gather and rr_launch_plaid_decode.  The last two take an rr_bank_view
 // (rr_common.h); the gather picks its kernel by the view's nbits.  A runtime nbits becomes a template argument in one place,
 // plaid_with_nbits (plaid_decode.h), which the host decoder uses too; plaid_tables_ok there is the check of a compressed view.
@@ -39,7 +41,11 @@
 // lane group of a row is then a power of two and the butterfly stays inside it) and never leave before the butterfly: every lane
 // of a wave reaches it, loads and stores are predicated.  The bucket weights (at most 256 floats, 1 KiB) are read through the
 // vector cache: a block decodes 16 - 32 rows, and filling LDS per block would cost a barrier and as many bytes as the rows do.
+#include <cmath>
+#include <vector>
+
 #include "plaid_decode.h"      // load8, plaid_bucket / plaid_sumsq8 / plaid_scale, plaid_load8, plaid_finish8
+#include "rank_order.h"        // rank_key: the host definition of the compressed row picks its code by it
 #include "rr_common.h"
 
 namespace {
@@ -310,5 +316,58 @@ bool rr_plaid_decode_rows_host(const uint16_t* centroids, int C, const float* we
   plaid_with_nbits(nbits, [&](auto nb) {
     plaid_decode_rows_host<decltype(nb)::value>(centroids, C, weights, D, codes, resid, n_rows, out);
   });
+  return true;
+}
+
+namespace {
+
+// fp16 bits -> float, exact (host)
+inline float plaid_f16_value(uint16_t hb) {
+  const uint32_t sign = (uint32_t)(hb & 0x8000u) << 16, e = (hb >> 10) & 31u, m = hb & 0x3ffu;
+  if (e == 0) return (sign ? -1.f : 1.f) * ((float)m * 5.9604644775390625e-8f);
+  if (e == 31) return __builtin_bit_cast(float, sign | 0x7f800000u | (m << 13));
+  return __builtin_bit_cast(float, sign | ((e + 112u) << 23) | (m << 13));
+}
+
+}  // namespace
+
+// rr_util_plaid_compress_rows: THE COMPRESSED ROW (include/rerank_mi355.h, rr_bank_add_compress) in host code, the score chain as
+// explicit fmaf in the order of the matrix core (t outer in steps of 16, e, then g; d = 16 t + 4 g + e); false for a shape
+// rr_plaid_compress_shape_ok does not take.  Host memory throughout.
+bool rr_plaid_compress_rows_host(const void* rows, int rows_f16, long long n_rows, int D, const uint16_t* centroids, int C,
+                                 const float* cutoffs, int nbits, int32_t* codes_out, uint8_t* resid_out) {
+  if (!rr_plaid_compress_shape_ok(nbits, D) || C <= 0 || n_rows < 0) return false;
+  std::vector<float> cf((size_t)C * D), x((size_t)D);
+  for (size_t i = 0; i < cf.size(); ++i) cf[i] = plaid_f16_value(centroids[i]);
+  const int n_cut = (1 << nbits) - 1;
+  const size_t rb = (size_t)D / 8 * nbits;
+  for (long long row = 0; row < n_rows; ++row) {
+    for (int e = 0; e < D; ++e)
+      x[(size_t)e] = plaid_f16_value(rows_f16 ? ((const uint16_t*)rows)[(size_t)row * D + e]
+                                              : plaid_f16_bits(((const float*)rows)[(size_t)row * D + e]));
+    unsigned long long best = 0;
+    for (int c = 0; c < C; ++c) {
+      const float* a = cf.data() + (size_t)c * D;
+      float acc = 0.f;
+      for (int t = 0; t < D; t += 16)
+        for (int e = 0; e < 4; ++e)
+          for (int g = 0; g < 4; ++g) acc = fmaf(a[t + 4 * g + e], x[(size_t)(t + 4 * g + e)], acc);
+      const unsigned long long key = rank_key(acc, (uint32_t)c);
+      if (key > best) best = key;
+    }
+    const int code = (int)rank_key_index(best);
+    codes_out[row] = code;
+    uint8_t* out = resid_out + (size_t)row * rb;
+    for (size_t i = 0; i < rb; ++i) out[i] = 0;
+    for (int e = 0; e < D; ++e) {
+      const float res = x[(size_t)e] - cf[(size_t)code * D + e];
+      int bucket = 0;
+      for (int j = 0; j < n_cut; ++j) bucket += cutoffs[j] < res ? 1 : 0;
+      for (int j = 0; j < nbits; ++j) {
+        const size_t p = (size_t)e * nbits + j;            // np.packbits: bit j of the bucket, bit 0 first, bytes from the top
+        out[p >> 3] |= (uint8_t)(((bucket >> j) & 1) << (7 - (p & 7)));
+      }
+    }
+  }
   return true;
 }

@@ -304,6 +304,12 @@ struct rr_bank {
   // by the first search after an add (table_n passages of it are current); nothing else reads it
   rr_bank_slot* table = nullptr;
   size_t table_cap = 0, table_n = 0;
+  // rr_bank_add_compress: the codec's bucket cutoffs [2^nbits - 1] on the device (rr_bank_set_plaid_cutoffs; null until then) and
+  // the grow-only scratch of a call (row map and the splits' rank keys, rr_compress_plan)
+  float* cutoffs = nullptr;
+  bool has_cutoffs = false;
+  char* cscratch = nullptr;
+  size_t cscratch_cap = 0;
   std::string err;
   rr_model::AsmSlot slot[2];
   int next = 0;
@@ -2046,6 +2052,8 @@ static void bank_free(rr_bank* b) {
   if (b->centroids) (void)hipFree(b->centroids);
   if (b->weights) (void)hipFree(b->weights);
   if (b->table) (void)hipFree(b->table);
+  if (b->cutoffs) (void)hipFree(b->cutoffs);
+  if (b->cscratch) (void)hipFree(b->cscratch);
   for (auto& a : b->slot) {
     if (a.host) (void)hipHostFree(a.host);
     if (a.dev) (void)hipFree(a.dev);
@@ -2223,6 +2231,116 @@ static int rr_bank_add_plaid_impl(rr_bank* b, const int32_t* codes, const uint8_
   RR_BHIP(b, hipStreamSynchronize(st));            // the host buffers are the caller's again
   bank_append(b, lengths, n, first_index_out);
   return RR_OK;
+}
+
+// rr_bank_set_plaid_cutoffs (include/rerank_mi355.h): validated on the host, then copied; a load-time call
+static int rr_bank_set_plaid_cutoffs_impl(rr_bank* b, const float* cutoffs_host) {
+  const char* what = "rr_bank_set_plaid_cutoffs";
+  if (!b) return RR_ERR_BAD_ARG;
+  if (!b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it holds embeddings as they are (rr_bank_add)", what);
+  if (!cutoffs_host) return bfail(b, RR_ERR_BAD_ARG, "%s: null argument", what);
+  const int n = (1 << b->nbits) - 1;
+  for (int i = 0; i < n; ++i) {
+    if (cutoffs_host[i] != cutoffs_host[i]) return bfail(b, RR_ERR_BAD_SHAPE, "%s: cutoff %d is NaN", what, i);
+    if (i && cutoffs_host[i] < cutoffs_host[i - 1])
+      return bfail(b, RR_ERR_BAD_SHAPE, "%s: cutoff %d (%g) lies below cutoff %d (%g): the sequence must not decrease", what, i,
+                   (double)cutoffs_host[i], i - 1, (double)cutoffs_host[i - 1]);
+  }
+  RR_BHIP(b, hipSetDevice(b->device));
+  if (!b->cutoffs) RR_BHIP(b, hipMalloc((void**)&b->cutoffs, 256 * sizeof(float)));
+  else RR_BHIP(b, hipDeviceSynchronize());         // adds already enqueued keep the cutoffs they were given
+  RR_BHIP(b, hipMemcpy(b->cutoffs, cutoffs_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  b->has_cutoffs = true;
+  return RR_OK;
+}
+
+// rr_bank_add_compress: rr_bank_add's checks and staging, then the kernels of bank_compress.hip into the bank's codes, residual
+// bytes and mask bytes.  Everything that can refuse comes before the first enqueue.
+static int rr_bank_add_compress_impl(rr_bank* b, const void* context_li, int dtype, const float* context_mask, const int32_t* lengths,
+                                     int n, int Lc, int32_t* first_index_out, void* hip_stream) {
+  const char* what = "rr_bank_add_compress";
+  if (!b) return RR_ERR_BAD_ARG;
+  if (!b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it keeps embeddings as fp16 rows (rr_bank_add)", what);
+  if (!b->has_cutoffs) return bfail(b, RR_ERR_UNSUPPORTED, "%s: the bank has no bucket cutoffs (rr_bank_set_plaid_cutoffs)", what);
+  if (b->D % 16) return bfail(b, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a multiple of 16: the matrix-core step of the centroid search)", what, b->D);
+  if (!context_li || !context_mask || !lengths) return bfail(b, RR_ERR_BAD_ARG, "%s: null argument", what);
+  if (dtype != RR_F32 && dtype != RR_F16) return bfail(b, RR_ERR_BAD_DTYPE, "%s: dtype %d (RR_F32 or RR_F16)", what, dtype);
+  if (((uintptr_t)context_li) & 15) return bfail(b, RR_ERR_BAD_ARG, "%s: context_li must be 16-byte aligned", what);
+  if (n <= 0 || Lc <= 0 || (long long)n * Lc > (1LL << 40)) return bfail(b, RR_ERR_BAD_SHAPE, "%s: n=%d Lc=%d", what, n, Lc);
+  int64_t rows = 0;
+  RR_TRY(bank_admit(b, what, lengths, n, Lc, &rows));
+  hipStream_t st = (hipStream_t)hip_stream;
+  RR_TRY(bank_capture_guard(b, st, CAP_STAGES, what));
+  const rr_compress_plan pl = rr_plaid_compress_plan(rows, b->n_centroids, b->D);
+  if (pl.jt == 0)
+    return bfail(b, RR_ERR_BAD_SHAPE, "%s: %lld rows against %d centroids at the compress_chunk in force do not fit a launch", what,
+                 (long long)rows, b->n_centroids);
+  RR_BHIP(b, hipSetDevice(b->device));
+  if (b->cscratch_cap < pl.total) {                // grow-only; calls still in flight read the old block
+    RR_BHIP(b, hipDeviceSynchronize());
+    if (b->cscratch) { RR_BHIP(b, hipFree(b->cscratch)); b->cscratch = nullptr; b->cscratch_cap = 0; }
+    RR_BHIP(b, hipMalloc((void**)&b->cscratch, pl.total));
+    b->cscratch_cap = pl.total;
+  }
+  std::vector<rr_bank_slot> staged((size_t)n);
+  int64_t row = b->used_rows;
+  for (int i = 0; i < n; ++i) {
+    staged[(size_t)i] = rr_bank_slot{row, lengths[i], 0};
+    row += lengths[i];
+  }
+  rr_model::AsmSlot& a = b->slot[b->next];
+  RR_BHIP(b, stage_slot(a, staged.data(), staged.size() * sizeof(rr_bank_slot), (size_t)1024 * sizeof(rr_bank_slot), st));
+  const int64_t r0 = b->used_rows;
+  RR_BHIP(b, rr_launch_plaid_compress(context_li, dtype == RR_F16, context_mask, (const rr_bank_slot*)a.dev, n, Lc, r0, rows, b->D, b->nbits,
+                                      b->centroids, b->n_centroids, b->cutoffs, b->cscratch, pl, b->codes + r0,
+                                      b->resid + (size_t)r0 * b->resid_row_bytes(), b->mask + r0, st));
+  RR_BHIP(b, hipEventRecord(a.done, st));
+  b->next ^= 1;
+  bank_append(b, lengths, n, first_index_out);
+  return RR_OK;
+}
+
+// rr_op_plaid_compress_rows (include/rerank_mi355_diag.h): the kernels over loose device pointers; its scratch lives for the call
+static int rr_op_plaid_compress_rows_impl(const void* rows, int dtype, int64_t n_rows, int D, const uint16_t* centroids_f16, int32_t n_centroids,
+                                          const float* cutoffs, int nbits, int32_t* codes_out, uint8_t* residuals_out, void* hip_stream) {
+  if (!rows || !centroids_f16 || !cutoffs || !codes_out || !residuals_out) return RR_ERR_BAD_ARG;
+  if (dtype != RR_F32 && dtype != RR_F16) return RR_ERR_BAD_DTYPE;
+  if (!rr_plaid_compress_shape_ok(nbits, D)) return RR_ERR_UNSUPPORTED;
+  if (n_rows <= 0 || n_rows > (1LL << 31) || n_centroids <= 0 || n_centroids > (1 << 24)) return RR_ERR_BAD_SHAPE;
+  if (((((uintptr_t)rows) | ((uintptr_t)centroids_f16)) & 15) || (((uintptr_t)residuals_out) & 7) || (((uintptr_t)codes_out) & 3) ||
+      (((uintptr_t)cutoffs) & 3))
+    return RR_ERR_BAD_ARG;
+  const rr_compress_plan pl = rr_plaid_compress_plan(n_rows, n_centroids, D);
+  if (pl.jt == 0) return RR_ERR_BAD_SHAPE;
+  hipStream_t st = (hipStream_t)hip_stream;
+  char* scratch = nullptr;
+  hipError_t e = hipMalloc((void**)&scratch, pl.total);
+  if (e != hipSuccess) return e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP;
+  e = rr_launch_plaid_compress(rows, dtype == RR_F16, nullptr, nullptr, 0, 0, 0, n_rows, D, nbits, centroids_f16, n_centroids, cutoffs, scratch,
+                               pl, codes_out, residuals_out, nullptr, st);
+  const hipError_t e2 = hipStreamSynchronize(st);
+  (void)hipFree(scratch);
+  return e == hipSuccess && e2 == hipSuccess ? RR_OK : RR_ERR_HIP;
+}
+
+// rr_bank_read_plaid: the stored form of one passage of a compressed bank, copied to the host
+static int rr_bank_read_plaid_impl(rr_bank* b, int32_t index, int32_t* codes_out, uint8_t* resid_out, uint8_t* mask_out, int32_t capacity_rows,
+                                   void* hip_stream) {
+  const char* what = "rr_bank_read_plaid";
+  if (!b) return RR_ERR_BAD_ARG;
+  if (!b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it holds no codes (rr_bank_read)", what);
+  if (index < 0 || (size_t)index >= b->first.size()) return bfail(b, RR_ERR_BAD_SHAPE, "%s: passage %d of %zu", what, index, b->first.size());
+  const int32_t len = b->len[(size_t)index];
+  if (!codes_out && !resid_out && !mask_out) return len;
+  if (capacity_rows < len) return bfail(b, RR_ERR_BAD_SHAPE, "%s: passage %d holds %d rows, the buffers %d", what, index, len, capacity_rows);
+  RR_BHIP(b, hipSetDevice(b->device));
+  RR_BHIP(b, hipStreamSynchronize((hipStream_t)hip_stream));
+  const int64_t r0 = b->first[(size_t)index];
+  const size_t rb = b->resid_row_bytes();
+  if (codes_out) RR_BHIP(b, hipMemcpy(codes_out, b->codes + r0, (size_t)len * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (resid_out) RR_BHIP(b, hipMemcpy(resid_out, b->resid + (size_t)r0 * rb, (size_t)len * rb, hipMemcpyDeviceToHost));
+  if (mask_out) RR_BHIP(b, hipMemcpy(mask_out, b->mask + r0, (size_t)len, hipMemcpyDeviceToHost));
+  return len;
 }
 
 static int rr_op_plaid_decode_rows_impl(const uint16_t* centroids_f16, int32_t n_centroids, const float* bucket_weights, int nbits, int D,
@@ -3168,6 +3286,8 @@ int rr_set_tuning(const char* key, int value) {
   if (!strcmp(key, "m_alternate")) return rr_set_m_alternate(value);
   if (!strcmp(key, "li_lds_kb")) return rr_set_li_lds_kb(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
   if (!strcmp(key, "search_chunk")) return rr_set_search_chunk(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
+  if (!strcmp(key, "compress_chunk")) return rr_set_compress_chunk(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
+  if (!strcmp(key, "compress_stop_after")) return rr_set_compress_stop_after(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
   if (!strcmp(key, "plaid_stop_after")) {
     if (value < 0 || value >= RR_PLAID_SEARCH_STAGES) return RR_ERR_BAD_ARG;
     g_plaid_stop_after = value;
@@ -3646,6 +3766,27 @@ int rr_bank_create_plaid(rr_handle h, int64_t capacity_rows, int32_t max_passage
 }
 int rr_bank_add_plaid(rr_bank_handle b, const int32_t* codes, const uint8_t* residuals, const uint8_t* mask, const int32_t* lengths, int n, int32_t* first_index_out, void* hip_stream) {
   return guarded(nullptr, [&]() -> int { return rr_bank_add_plaid_impl(b, codes, residuals, mask, lengths, n, first_index_out, hip_stream); });
+}
+int rr_bank_set_plaid_cutoffs(rr_bank_handle b, const float* cutoffs_host) {
+  return guarded(nullptr, [&]() -> int { return rr_bank_set_plaid_cutoffs_impl(b, cutoffs_host); });
+}
+int rr_bank_add_compress(rr_bank_handle b, const void* context_li, int dtype, const float* context_mask, const int32_t* lengths, int n, int Lc, int32_t* first_index_out, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_bank_add_compress_impl(b, context_li, dtype, context_mask, lengths, n, Lc, first_index_out, hip_stream); });
+}
+int rr_util_plaid_compress_rows(const void* rows, int dtype, int64_t n_rows, int D, const uint16_t* centroids_f16, int32_t n_centroids, const float* cutoffs, int nbits, int32_t* codes_out, uint8_t* residuals_out) {
+  if (!rows || !centroids_f16 || !cutoffs || !codes_out || !residuals_out) return RR_ERR_BAD_ARG;
+  if (dtype != RR_F32 && dtype != RR_F16) return RR_ERR_BAD_DTYPE;
+  if (!rr_plaid_compress_shape_ok(nbits, D)) return RR_ERR_UNSUPPORTED;
+  if (n_centroids <= 0 || n_centroids > (1 << 24) || n_rows < 0) return RR_ERR_BAD_SHAPE;
+  return guarded(nullptr, [&]() -> int {
+    return rr_plaid_compress_rows_host(rows, dtype == RR_F16, n_rows, D, centroids_f16, n_centroids, cutoffs, nbits, codes_out, residuals_out) ? RR_OK : RR_ERR_BAD_SHAPE;
+  });
+}
+int rr_op_plaid_compress_rows(const void* rows, int dtype, int64_t n_rows, int D, const uint16_t* centroids_f16, int32_t n_centroids, const float* cutoffs, int nbits, int32_t* codes_out, uint8_t* residuals_out, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_plaid_compress_rows_impl(rows, dtype, n_rows, D, centroids_f16, n_centroids, cutoffs, nbits, codes_out, residuals_out, hip_stream); });
+}
+int rr_bank_read_plaid(rr_bank_handle b, int32_t index, int32_t* codes_out, uint8_t* residuals_out, uint8_t* mask_out, int32_t capacity_rows, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_bank_read_plaid_impl(b, index, codes_out, residuals_out, mask_out, capacity_rows, hip_stream); });
 }
 int rr_bank_format(rr_bank_handle b, int32_t* nbits_out, int32_t* n_centroids_out, int64_t* bytes_per_row_out) {
   if (!b) return RR_ERR_BAD_ARG;

@@ -516,5 +516,19 @@ bool rr_plaid_prune_host(const float* S, int C, int Lqc, int s_ld, const int32_t
                          int n, int ncells, float thr, int ndocs, uint8_t* cells_out, float* a1_out, float* a2_out, int32_t* list1_out,
                          int32_t* n1_out, int32_t* list2_out, int32_t* n2_out);
 bool rr_plaid_shape_ok(int nbits, int D);
+// rr_bank_add_compress / rr_op_plaid_compress_rows (bank_compress.hip): embeddings -> (code, packed residual bytes).  The launch
+// shape of a call and where its intermediates lie in `scratch` (16-byte aligned, `total` bytes): map [R] int64 (bank calls),
+// keys [splits][R] 64-bit rank keys.  jt == 0: a shape the kernels do not take.
+struct rr_compress_plan { int jt, row_blocks, splits, chunk; size_t lds, map_off, keys_off, total; };
+bool rr_plaid_compress_shape_ok(int nbits, int D);
+int rr_set_compress_chunk(int centroids);      // rr_set_tuning("compress_chunk"): 0 (chosen per launch) or a multiple of 16 in [16, 2^24], -1 outside
+int rr_set_compress_stop_after(int stage);     // rr_set_tuning("compress_stop_after"): 1 (all) or 0 (the assignment kernel only), -1 outside
+rr_compress_plan rr_plaid_compress_plan(long long R, int C, int D);
+hipError_t rr_launch_plaid_compress(const void* src, int src_f16, const float* mask, const rr_bank_slot* slots, int n, int Lc, long long base,
+                                    long long R, int D, int nbits, const uint16_t* centroids, int C, const float* cutoffs, char* scratch,
+                                    const rr_compress_plan& pl, int32_t* codes, uint8_t* resid, uint8_t* mask_bytes, hipStream_t st);
+// rr_util_plaid_compress_rows: the definition in host code (passage_bank.hip, beside the host decoder)
+bool rr_plaid_compress_rows_host(const void* rows, int rows_f16, long long n_rows, int D, const uint16_t* centroids, int C,
+                                 const float* cutoffs, int nbits, int32_t* codes_out, uint8_t* resid_out);
 bool rr_plaid_decode_rows_host(const uint16_t* centroids, int C, const float* weights, int nbits, int D, const int32_t* codes,
                                const uint8_t* resid, long long n_rows, uint16_t* out);

@@ -764,7 +764,8 @@ class RerankEngine:
         and at most `max_passages` passages on this engine's device with its li_dim.  It outlives the engine and serves every
         interaction engine of the device with the same li_dim (NORMAL and MORES).  `codec` (passage_bank.PlaidCodec): a
         compressed bank (rr_bank_create_plaid) that holds the residual codes of a ColBERTv2 / PLAID index and decodes them in the
-        forward; filled with add_compressed / load_plaid_index."""
+        forward; filled with add_compressed / load_plaid_index, or, when the codec carries its bucket cutoffs (they are set on the
+        bank here, rr_bank_set_plaid_cutoffs), from embeddings on the device with add_compress."""
         from .passage_bank import PassageBank
         return PassageBank(self, capacity_rows, max_passages, codec)
 

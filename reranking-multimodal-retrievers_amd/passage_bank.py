@@ -19,6 +19,9 @@ score, exactly (rr_bank_search): every passage is scored, nothing is pruned.  Wi
 staged search over a compressed bank (rr_bank_search_plaid, RerankEngine.bank_search_plaid): candidates by centroid, two
 centroid-only pruning passes, exact MaxSim on the survivors.
 
+`PassageBank.add_compress` fills a compressed bank from embeddings that are on the device (rr_bank_add_compress): nearest centroid
+on the matrix core and residual bucketising in two kernels, the codec's cutoffs given as `PlaidCodec(bucket_cutoffs=...)`.
+
 `BankTable`, `plan_bank_batch`, `plan_bank_scores`, `PlaidCodec` and `read_plaid_index` are the host side: pure Python / numpy / torch on the CPU,
 usable and tested without a device.
 """
@@ -182,10 +185,12 @@ def plaid_shape_ok(nbits: int, dim: int) -> bool:
 
 class PlaidCodec:
     """The tables of a ColBERTv2 / PLAID residual codec, as an index stores them: `centroids` [C, D] (kept as fp16: the index
-    saves them with .half(), codecs/residual.py:161), `bucket_weights` [2^nbits] (kept as float32) and `nbits`.  A plain holder:
-    it validates shapes and dtypes (ValueError) and compresses nothing."""
+    saves them with .half(), codecs/residual.py:161), `bucket_weights` [2^nbits] (kept as float32) and `nbits`; optionally
+    `bucket_cutoffs` [2^nbits - 1] (the first tensor of buckets.pt, kept as float32), which compressing needs and decoding does
+    not.  It validates shapes, dtypes and the cutoffs (ValueError: wrong count, a NaN, a decreasing sequence); `decode` and
+    `compress` run the host definitions of the library."""
 
-    def __init__(self, centroids, bucket_weights, nbits: int):
+    def __init__(self, centroids, bucket_weights, nbits: int, *, bucket_cutoffs=None):
         import torch
         if not isinstance(nbits, int) or isinstance(nbits, bool) or nbits not in PLAID_NBITS:
             raise ValueError(f"nbits {nbits!r}: 1, 2, 4 or 8")
@@ -201,6 +206,18 @@ class PlaidCodec:
         self.nbits, self.dim = nbits, dim
         self.centroids = centroids.detach().to(device="cpu", dtype=torch.float16).contiguous()
         self.bucket_weights = bucket_weights.detach().to(device="cpu", dtype=torch.float32).contiguous()
+        self.bucket_cutoffs = None
+        if bucket_cutoffs is not None:
+            cut = torch.as_tensor(bucket_cutoffs)
+            if not cut.is_floating_point() or tuple(cut.shape) != ((1 << nbits) - 1,):
+                raise ValueError(f"bucket_cutoffs must be {(1 << nbits) - 1} floating-point values at nbits {nbits}, got {cut.dtype} "
+                                 f"{tuple(cut.shape)}")
+            cut = cut.detach().to(device="cpu", dtype=torch.float32).contiguous()
+            if bool(torch.isnan(cut).any()):
+                raise ValueError("bucket_cutoffs hold a NaN")
+            if cut.numel() > 1 and bool((cut[1:] < cut[:-1]).any()):
+                raise ValueError("bucket_cutoffs decrease: a bucket is the number of cutoffs below a residual")
+            self.bucket_cutoffs = cut
 
     @property
     def n_centroids(self) -> int:
@@ -228,6 +245,28 @@ class PlaidCodec:
         L.check(rc, None, "rr_util_plaid_decode_rows")
         return out
 
+    def compress(self, rows):
+        """(codes int32 [R], residuals uint8 [R, residual_bytes]) of `rows` [R, D] (float32 or float16; anything else goes through
+        float32) in host code (rr_util_plaid_compress_rows: the compressed row of include/rerank_mi355.h, the definition the
+        device is held to; no GPU needed).  Needs `bucket_cutoffs`; dim must be a multiple of 16."""
+        import torch
+        from . import _lib as L
+        lib = L.load()
+        if self.bucket_cutoffs is None:
+            raise ValueError("compress needs the codec's bucket_cutoffs (PlaidCodec(..., bucket_cutoffs=...))")
+        rows = torch.as_tensor(rows)
+        if rows.dim() != 2 or rows.shape[1] != self.dim:
+            raise ValueError(f"rows must be [R, {self.dim}], got {tuple(rows.shape)}")
+        dt = rows.dtype if rows.dtype in (torch.float32, torch.float16) else torch.float32
+        rows = rows.detach().to(device="cpu", dtype=dt).contiguous()
+        R = int(rows.shape[0])
+        codes = torch.empty(R, dtype=torch.int32)
+        res = torch.empty((R, self.residual_bytes), dtype=torch.uint8)
+        L.check(lib.rr_util_plaid_compress_rows(rows.data_ptr(), L.RR_F16 if dt == torch.float16 else L.RR_F32, R, self.dim,
+                                                self.centroids.data_ptr(), self.n_centroids, self.bucket_cutoffs.data_ptr(), self.nbits,
+                                                codes.data_ptr(), res.data_ptr()), None, "rr_util_plaid_compress_rows")
+        return codes, res
+
 
 def read_plaid_index(index_path: str):
     """Read a ColBERTv2 / PLAID index directory as the reference's indexer writes it
@@ -235,7 +274,8 @@ def read_plaid_index(index_path: str):
     num_chunks), `centroids.pt`, `buckets.pt` = (cutoffs, weights), and per chunk i `{i}.codes.pt`, `{i}.residuals.pt`,
     `doclens.{i}.json`.  torch.load and json only; nothing of colbert is imported.  Returns (PlaidCodec, chunks); `chunks` is a
     generator of (first passage number, codes int32 [R], residuals uint8 [R, D * nbits / 8], doclens list) that loads one chunk at a
-    time.  The passage numbers run through the chunks in order, as the index numbers them."""
+    time.  The passage numbers run through the chunks in order, as the index numbers them.  The codec keeps the index's cutoffs, so a
+    bank created with it can also compress new embeddings (PassageBank.add_compress)."""
     import json
     import os
 
@@ -252,7 +292,7 @@ def read_plaid_index(index_path: str):
         meta = json.load(f)
     nbits, dim, n_chunks = int(meta["config"]["nbits"]), int(meta["config"]["dim"]), int(meta["num_chunks"])
     buckets = load("buckets.pt")
-    codec = PlaidCodec(load("centroids.pt"), buckets[1], nbits)
+    codec = PlaidCodec(load("centroids.pt"), buckets[1], nbits, bucket_cutoffs=buckets[0])
     if codec.dim != dim:
         raise ValueError(f"{index_path}: metadata.json says dim {dim}, centroids.pt holds rows of {codec.dim}")
 
@@ -294,6 +334,9 @@ class PassageBank:
                                                   codec.centroids.data_ptr(), codec.bucket_weights.data_ptr(), C.byref(h)),
                     engine.h, "rr_bank_create_plaid")
         self.h = h
+        if codec is not None and codec.bucket_cutoffs is not None:
+            self._check(self.lib.rr_bank_set_plaid_cutoffs(h, codec.bucket_cutoffs.data_ptr()), "rr_bank_set_plaid_cutoffs",
+                        bad_shape=ValueError)
 
     def __del__(self):
         self.close()
@@ -372,6 +415,39 @@ class PassageBank:
         first = C.c_int32(-1)
         self._check(self.lib.rr_bank_add(self.h, L.ptr(li), L.RR_F16 if dt == torch.float16 else L.RR_F32, L.ptr(cm), ln.ctypes.data,
                                          n, Lc, C.byref(first), self._stream()), "rr_bank_add", bad_shape=ValueError)
+        self.table.append(ids, ln.tolist(), int(first.value))
+        self.padded_len = max(self.padded_len, Lc)
+        return int(first.value)
+
+    def add_compress(self, passage_ids: Sequence, context_li, context_mask, lengths: Optional[Sequence[int]] = None) -> int:
+        """`add` for a compressed bank (rr_bank_add_compress): the padded tensors a retriever produces are compressed on the
+        device against the codec's centroids and cutoffs and appended as codes and residual bytes — the compressed row of
+        include/rerank_mi355.h, what the reference's indexer computes from `context_li.half()`.  Arguments, return value and
+        errors as `add`; an fp16 bank, a codec without cutoffs and an li_dim that is no multiple of 16 raise NotImplementedError."""
+        import numpy as np
+        import torch
+        from .pair_inputs import pair_lengths
+        L = self._L
+        if self.codec is None:
+            raise NotImplementedError("add_compress on an fp16 bank: it keeps embeddings as they are (add)")
+        ids = list(passage_ids)
+        n = len(ids)
+        if context_li.dim() != 3 or context_li.shape[0] != n or context_li.shape[2] != self.li_dim:
+            raise ValueError(f"context_li must be [{n}, Lc, {self.li_dim}], got {tuple(context_li.shape)}")
+        Lc = int(context_li.shape[1])
+        self.table.check_new(ids)
+        dt = context_li.dtype if context_li.dtype in (torch.float32, torch.float16) else torch.float32
+        li = context_li.to(device=self.device, dtype=dt).contiguous()
+        cm = context_mask.reshape(n, Lc).to(device=self.device, dtype=torch.float32).contiguous()
+        if lengths is None:
+            lengths = pair_lengths(cm).cpu().numpy()
+        ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1), dtype=np.int32)
+        if ln.size != n:
+            raise ValueError(f"{ln.size} lengths for {n} passages")
+        first = C.c_int32(-1)
+        self._check(self.lib.rr_bank_add_compress(self.h, L.ptr(li), L.RR_F16 if dt == torch.float16 else L.RR_F32, L.ptr(cm),
+                                                  ln.ctypes.data, n, Lc, C.byref(first), self._stream()), "rr_bank_add_compress",
+                    bad_shape=ValueError)
         self.table.append(ids, ln.tolist(), int(first.value))
         self.padded_len = max(self.padded_len, Lc)
         return int(first.value)
@@ -463,6 +539,22 @@ class PassageBank:
         self._check(got, "rr_bank_read")
         assert got == n, f"the bank holds {got} rows for passage {passage_id!r}, the table {n}"
         return rows, mask
+
+    def read_compressed(self, passage_id):
+        """One passage of a compressed bank back on the host as it is stored (rr_bank_read_plaid; synchronises the current
+        stream): (codes int32 [len], residuals uint8 [len, D * nbits / 8], mask uint8 [len])."""
+        import torch
+        if self.codec is None:
+            raise NotImplementedError("read_compressed on an fp16 bank: it holds no codes (read)")
+        idx, lens = self.table.lookup([passage_id])
+        n = int(lens[0])
+        codes = torch.empty(n, dtype=torch.int32)
+        res = torch.empty((n, self.codec.residual_bytes), dtype=torch.uint8)
+        mask = torch.empty(n, dtype=torch.uint8)
+        got = self.lib.rr_bank_read_plaid(self.h, int(idx[0]), codes.data_ptr(), res.data_ptr(), mask.data_ptr(), n, self._stream())
+        self._check(got, "rr_bank_read_plaid")
+        assert got == n, f"the bank holds {got} rows for passage {passage_id!r}, the table {n}"
+        return codes, res, mask
 
     def maxsim(self, engine, query_li, passage_ids, **kw):
         """The retriever's MaxSim [n_pairs] of the pairs (query, passage id) from this bank: engine.bank_li_scores(...)["maxsim"]."""

@@ -280,30 +280,31 @@ rr_compress_plan rr_plaid_compress_plan(long long R, int C, int D) {
   return pl;
 }
 
-// The kernels over R rows.  slots != null: a bank call, the rows are the kept rows of the padded source [n][Lc][D] (slots[i] =
-// (first destination row, length) on the device, `base` the first destination row of the call), mask [n][Lc] float32, mask_bytes
-// written; slots == null: src holds the R rows back to back, no mask.  codes / resid / mask_bytes point at the call's first row.
-hipError_t rr_launch_plaid_compress(const void* src, int src_f16, const float* mask, const rr_bank_slot* slots, int n, int Lc, long long base,
-                                    long long R, int D, int nbits, const uint16_t* centroids, int C, const float* cutoffs, char* scratch,
-                                    const rr_compress_plan& pl, int32_t* codes, uint8_t* resid, uint8_t* mask_bytes, hipStream_t st) {
+// The kernels over R rows.  in.slots != null: a bank call, the rows are the kept rows of the padded source `in` (rr_common.h; `base`
+// the first destination row of the call), mask_bytes written; in.slots == null: in.src holds the R rows back to back, no mask.
+// codes / resid / mask_bytes point at the call's first row.
+hipError_t rr_launch_plaid_compress(const rr_padded_rows& in, long long base, long long R, int D, int nbits, const uint16_t* centroids, int C,
+                                    const float* cutoffs, char* scratch, const rr_compress_plan& pl, int32_t* codes, uint8_t* resid,
+                                    uint8_t* mask_bytes, hipStream_t st) {
+  const void* src = in.src;
   if (!src || !centroids || !cutoffs || !scratch || !codes || !resid || R <= 0 || pl.jt == 0 || !rr_plaid_compress_shape_ok(nbits, D) ||
       C <= 0)
     return hipErrorInvalidValue;
-  if (slots && (!mask || !mask_bytes || n <= 0 || Lc <= 0)) return hipErrorInvalidValue;
+  if (in.slots && (!in.mask || !mask_bytes || in.n <= 0 || in.Lc <= 0)) return hipErrorInvalidValue;
   // 16-byte row chunks of the source and the centroids, 8-byte keys and residual stores
   if (((((uintptr_t)src) | ((uintptr_t)centroids) | ((uintptr_t)scratch)) & 15) || (((uintptr_t)resid) & 7) || (((uintptr_t)codes) & 3))
     return hipErrorInvalidValue;
-  long long* map = slots ? (long long*)(scratch + pl.map_off) : nullptr;
+  long long* map = in.slots ? (long long*)(scratch + pl.map_off) : nullptr;
   unsigned long long* keys = (unsigned long long*)(scratch + pl.keys_off);
-  if (slots) {
-    const long long n_src = (long long)n * Lc, blocks = (n_src + 255) / 256;
+  if (in.slots) {
+    const long long n_src = (long long)in.n * in.Lc, blocks = (n_src + 255) / 256;
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(compress_map_kernel, dim3((unsigned)blocks), dim3(256), 0, st, slots, n_src, Lc, base, map);
+    hipLaunchKernelGGL(compress_map_kernel, dim3((unsigned)blocks), dim3(256), 0, st, in.slots, n_src, in.Lc, base, map);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  hipError_t e = src_f16 ? assign_pick<true>(src, map, R, D, centroids, C, pl, keys, st)
-                         : assign_pick<false>(src, map, R, D, centroids, C, pl, keys, st);
+  hipError_t e = in.src_f16 ? assign_pick<true>(src, map, R, D, centroids, C, pl, keys, st)
+                            : assign_pick<false>(src, map, R, D, centroids, C, pl, keys, st);
   if (e != hipSuccess) return e;
   if (g_compress_stop_after.load(std::memory_order_relaxed) == 0) return hipSuccess;
   const int lpr = D / 8, rpw = 64 / lpr;
@@ -311,11 +312,11 @@ hipError_t rr_launch_plaid_compress(const void* src, int src_f16, const float* m
   if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
   plaid_with_nbits(nbits, [&](auto nb) {
     constexpr int NB = decltype(nb)::value;
-    if (src_f16)
-      hipLaunchKernelGGL((compress_residual_kernel<NB, true>), dim3((unsigned)blocks), dim3(256), 0, st, src, map, mask, R, D, lpr, rpw,
+    if (in.src_f16)
+      hipLaunchKernelGGL((compress_residual_kernel<NB, true>), dim3((unsigned)blocks), dim3(256), 0, st, src, map, in.mask, R, D, lpr, rpw,
                          centroids, C, cutoffs, keys, pl.splits, codes, resid, mask_bytes);
     else
-      hipLaunchKernelGGL((compress_residual_kernel<NB, false>), dim3((unsigned)blocks), dim3(256), 0, st, src, map, mask, R, D, lpr, rpw,
+      hipLaunchKernelGGL((compress_residual_kernel<NB, false>), dim3((unsigned)blocks), dim3(256), 0, st, src, map, in.mask, R, D, lpr, rpw,
                          centroids, C, cutoffs, keys, pl.splits, codes, resid, mask_bytes);
   });
   return hipGetLastError();

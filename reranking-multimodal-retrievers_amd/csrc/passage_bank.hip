@@ -242,20 +242,19 @@ bool row_shape(int D, int* lpr, int* rpw) {
 
 }  // namespace
 
-// n passages of the padded source [n, Lc, D] (src_f16: fp16 bits, else float32) and mask [n, Lc] into the bank's rows / mask
-// bytes; slots[i] = (first destination row, length) on the device.  The caller has checked the rows against the capacity.
-hipError_t rr_launch_bank_ingest(const void* src, int src_f16, const float* mask, const rr_bank_slot* slots, int n, int Lc, int D,
-                                 uint16_t* rows, uint8_t* mask_bytes, hipStream_t st) {
+// the n passages of the padded source `in` (rr_common.h) into the bank's rows / mask bytes.  The caller has checked the rows against
+// the capacity.
+hipError_t rr_launch_bank_ingest(const rr_padded_rows& in, int D, uint16_t* rows, uint8_t* mask_bytes, hipStream_t st) {
   int lpr = 0, rpw = 0;
-  if (n <= 0 || Lc <= 0 || !row_shape(D, &lpr, &rpw) || !src || !mask || !slots || !rows || !mask_bytes) return hipErrorInvalidValue;
-  if ((((uintptr_t)src) | ((uintptr_t)rows)) & 15) return hipErrorInvalidValue;       // 16-byte row chunks
-  const long long n_rows = (long long)n * Lc, per_block = 4LL * rpw, blocks = (n_rows + per_block - 1) / per_block;
+  if (in.n <= 0 || in.Lc <= 0 || !row_shape(D, &lpr, &rpw) || !in.src || !in.mask || !in.slots || !rows || !mask_bytes) return hipErrorInvalidValue;
+  if ((((uintptr_t)in.src) | ((uintptr_t)rows)) & 15) return hipErrorInvalidValue;    // 16-byte row chunks
+  const long long n_rows = (long long)in.n * in.Lc, per_block = 4LL * rpw, blocks = (n_rows + per_block - 1) / per_block;
   if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  if (src_f16)
-    hipLaunchKernelGGL(bank_ingest_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, src, mask, slots, n_rows, Lc, D, lpr, rpw,
+  if (in.src_f16)
+    hipLaunchKernelGGL(bank_ingest_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, in.src, in.mask, in.slots, n_rows, in.Lc, D, lpr, rpw,
                        rows, mask_bytes);
   else
-    hipLaunchKernelGGL(bank_ingest_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, src, mask, slots, n_rows, Lc, D, lpr, rpw,
+    hipLaunchKernelGGL(bank_ingest_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, in.src, in.mask, in.slots, n_rows, in.Lc, D, lpr, rpw,
                        rows, mask_bytes);
   return hipGetLastError();
 }

@@ -2099,21 +2099,40 @@ static hipError_t bank_new(rr_handle h, int64_t capacity_rows, int32_t max_passa
   return hipSuccess;
 }
 
-static int rr_bank_create_impl(rr_handle h, int64_t capacity_rows, int32_t max_passages, rr_bank_handle* out) {
+// rr_bank_create and rr_bank_create_plaid (`plaid`: compressed rows and the codec's tables copied to the device): the checks, each
+// call's own between the model kind and the capacity, then the device and bank_new
+static int bank_create(rr_handle h, const char* what, bool plaid, int64_t capacity_rows, int32_t max_passages, int nbits, int32_t n_centroids,
+                       const uint16_t* centroids_f16, const float* bucket_weights, rr_bank_handle* out) {
   if (!h) return RR_ERR_BAD_ARG;
-  if (!out) return fail(h, RR_ERR_BAD_ARG, "rr_bank_create: null out");
+  if (!out) return fail(h, RR_ERR_BAD_ARG, "%s: null out", what);
   *out = nullptr;
   const int D = h->cfg.li_dim;
-  if (h->cfg.model_kind == RR_MODEL_FULL_CONTEXT) return fail(h, RR_ERR_BAD_ARG, "rr_bank_create on a full-context model");
-  if (D <= 0 || (D & 7) || D > 512) return fail(h, RR_ERR_UNSUPPORTED, "rr_bank_create: li_dim %d (a multiple of 8, at most 512)", D);
-  if (capacity_rows <= 0 || max_passages <= 0 || capacity_rows > (1LL << 40))
-    return fail(h, RR_ERR_BAD_SHAPE, "rr_bank_create: capacity_rows=%lld max_passages=%d", (long long)capacity_rows, max_passages);
+  if (h->cfg.model_kind == RR_MODEL_FULL_CONTEXT) return fail(h, RR_ERR_BAD_ARG, "%s on a full-context model", what);
+  if (plaid && (!centroids_f16 || !bucket_weights)) return fail(h, RR_ERR_BAD_ARG, "%s: null table", what);
+  if (plaid && !rr_plaid_shape_ok(nbits, D))
+    return fail(h, RR_ERR_UNSUPPORTED, "%s: nbits %d, li_dim %d (nbits 1, 2, 4 or 8; li_dim a power of two in [8, 512], a multiple of 8 * nbits)",
+                what, nbits, D);
+  if (!plaid && (D <= 0 || (D & 7) || D > 512)) return fail(h, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a multiple of 8, at most 512)", what, D);
+  if (capacity_rows <= 0 || max_passages <= 0 || capacity_rows > (1LL << 40) || (plaid && (n_centroids <= 0 || n_centroids > (1 << 24))))
+    return plaid ? fail(h, RR_ERR_BAD_SHAPE, "%s: capacity_rows=%lld max_passages=%d n_centroids=%d", what, (long long)capacity_rows, max_passages,
+                        n_centroids)
+                 : fail(h, RR_ERR_BAD_SHAPE, "%s: capacity_rows=%lld max_passages=%d", what, (long long)capacity_rows, max_passages);
   RR_HIP(h, hipSetDevice(h->cfg.device));
-  const hipError_t e = bank_new(h, capacity_rows, max_passages, 0, 0, nullptr, nullptr, out);
-  if (e != hipSuccess)
-    return fail(h, e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP, "rr_bank_create: %lld rows of %d: %s", (long long)capacity_rows, D,
-                hipGetErrorString(e));
-  return RR_OK;
+  const hipError_t e = bank_new(h, capacity_rows, max_passages, nbits, n_centroids, centroids_f16, bucket_weights, out);
+  if (e == hipSuccess) return RR_OK;
+  const int rc = e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP;
+  return plaid ? fail(h, rc, "%s: %lld rows of %d at %d bits, %d centroids: %s", what, (long long)capacity_rows, D, nbits, n_centroids,
+                      hipGetErrorString(e))
+               : fail(h, rc, "%s: %lld rows of %d: %s", what, (long long)capacity_rows, D, hipGetErrorString(e));
+}
+
+static int rr_bank_create_impl(rr_handle h, int64_t capacity_rows, int32_t max_passages, rr_bank_handle* out) {
+  return bank_create(h, "rr_bank_create", false, capacity_rows, max_passages, 0, 0, nullptr, nullptr, out);
+}
+
+static int rr_bank_create_plaid_impl(rr_handle h, int64_t capacity_rows, int32_t max_passages, int nbits, int32_t n_centroids,
+                                     const uint16_t* centroids_f16, const float* bucket_weights, rr_bank_handle* out) {
+  return bank_create(h, "rr_bank_create_plaid", true, capacity_rows, max_passages, nbits, n_centroids, centroids_f16, bucket_weights, out);
 }
 
 static int rr_bank_destroy_impl(rr_bank* b) {
@@ -2152,12 +2171,12 @@ static void bank_append(rr_bank* b, const int32_t* lengths, int n, int32_t* firs
   }
 }
 
-// every check on the host first; then one staged upload of the (first row, length) slots and one launch
-static int rr_bank_add_impl(rr_bank* b, const void* context_li, int dtype, const float* context_mask, const int32_t* lengths, int n,
-                            int Lc, int32_t* first_index_out, void* hip_stream) {
-  const char* what = "rr_bank_add";
-  if (!b) return RR_ERR_BAD_ARG;
-  if (b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on a compressed bank: it takes residual codes (rr_bank_add_plaid); nothing here compresses", what);
+// What rr_bank_add and rr_bank_add_compress (a compressed bank) do behind their own refusals.  Every check on the host first, so
+// that everything that can refuse comes before the first enqueue; then one staged upload of the (first row, length) slots and the
+// launch: the ingest kernel into the fp16 rows, or the kernels of bank_compress.hip (their scratch grown first) into the codes and
+// residual bytes; mask bytes either way.
+static int bank_add_padded(rr_bank* b, const char* what, const void* context_li, int dtype, const float* context_mask, const int32_t* lengths,
+                           int n, int Lc, int32_t* first_index_out, void* hip_stream) {
   if (!context_li || !context_mask || !lengths) return bfail(b, RR_ERR_BAD_ARG, "%s: null argument", what);
   if (dtype != RR_F32 && dtype != RR_F16) return bfail(b, RR_ERR_BAD_DTYPE, "%s: dtype %d (RR_F32 or RR_F16)", what, dtype);
   if (((uintptr_t)context_li) & 15) return bfail(b, RR_ERR_BAD_ARG, "%s: context_li must be 16-byte aligned", what);
@@ -2166,44 +2185,44 @@ static int rr_bank_add_impl(rr_bank* b, const void* context_li, int dtype, const
   RR_TRY(bank_admit(b, what, lengths, n, Lc, &rows));
   hipStream_t st = (hipStream_t)hip_stream;
   RR_TRY(bank_capture_guard(b, st, CAP_STAGES, what));
+  const rr_compress_plan pl = b->nbits ? rr_plaid_compress_plan(rows, b->n_centroids, b->D) : rr_compress_plan{};
+  if (b->nbits && pl.jt == 0)
+    return bfail(b, RR_ERR_BAD_SHAPE, "%s: %lld rows against %d centroids at the compress_chunk in force do not fit a launch", what,
+                 (long long)rows, b->n_centroids);
+  RR_BHIP(b, hipSetDevice(b->device));
+  if (b->cscratch_cap < pl.total) {                // grow-only; calls still in flight read the old block (an fp16 bank's plan: 0 bytes)
+    RR_BHIP(b, hipDeviceSynchronize());
+    if (b->cscratch) { RR_BHIP(b, hipFree(b->cscratch)); b->cscratch = nullptr; b->cscratch_cap = 0; }
+    RR_BHIP(b, hipMalloc((void**)&b->cscratch, pl.total));
+    b->cscratch_cap = pl.total;
+  }
+  const int64_t r0 = b->used_rows;
   std::vector<rr_bank_slot> staged((size_t)n);
-  int64_t row = b->used_rows;
+  int64_t row = r0;
   for (int i = 0; i < n; ++i) {
     staged[(size_t)i] = rr_bank_slot{row, lengths[i], 0};
     row += lengths[i];
   }
-  RR_BHIP(b, hipSetDevice(b->device));
   rr_model::AsmSlot& a = b->slot[b->next];
   RR_BHIP(b, stage_slot(a, staged.data(), staged.size() * sizeof(rr_bank_slot), (size_t)1024 * sizeof(rr_bank_slot), st));
-  RR_BHIP(b, rr_launch_bank_ingest(context_li, dtype == RR_F16, context_mask, (const rr_bank_slot*)a.dev, n, Lc, b->D, b->rows, b->mask, st));
+  const rr_padded_rows in{context_li, dtype == RR_F16, context_mask, (const rr_bank_slot*)a.dev, n, Lc};
+  if (b->nbits)
+    RR_BHIP(b, rr_launch_plaid_compress(in, r0, rows, b->D, b->nbits, b->centroids, b->n_centroids, b->cutoffs, b->cscratch, pl, b->codes + r0,
+                                        b->resid + (size_t)r0 * b->resid_row_bytes(), b->mask + r0, st));
+  else
+    RR_BHIP(b, rr_launch_bank_ingest(in, b->D, b->rows, b->mask, st));
   RR_BHIP(b, hipEventRecord(a.done, st));
   b->next ^= 1;
   bank_append(b, lengths, n, first_index_out);
   return RR_OK;
 }
 
-// rr_bank_create_plaid: rr_bank_create with compressed rows and the codec's tables copied to the device
-static int rr_bank_create_plaid_impl(rr_handle h, int64_t capacity_rows, int32_t max_passages, int nbits, int32_t n_centroids,
-                                     const uint16_t* centroids_f16, const float* bucket_weights, rr_bank_handle* out) {
-  const char* what = "rr_bank_create_plaid";
-  if (!h) return RR_ERR_BAD_ARG;
-  if (!out) return fail(h, RR_ERR_BAD_ARG, "%s: null out", what);
-  *out = nullptr;
-  const int D = h->cfg.li_dim;
-  if (h->cfg.model_kind == RR_MODEL_FULL_CONTEXT) return fail(h, RR_ERR_BAD_ARG, "%s on a full-context model", what);
-  if (!centroids_f16 || !bucket_weights) return fail(h, RR_ERR_BAD_ARG, "%s: null table", what);
-  if (!rr_plaid_shape_ok(nbits, D))
-    return fail(h, RR_ERR_UNSUPPORTED, "%s: nbits %d, li_dim %d (nbits 1, 2, 4 or 8; li_dim a power of two in [8, 512], a multiple of 8 * nbits)",
-                what, nbits, D);
-  if (capacity_rows <= 0 || max_passages <= 0 || capacity_rows > (1LL << 40) || n_centroids <= 0 || n_centroids > (1 << 24))
-    return fail(h, RR_ERR_BAD_SHAPE, "%s: capacity_rows=%lld max_passages=%d n_centroids=%d", what, (long long)capacity_rows, max_passages,
-                n_centroids);
-  RR_HIP(h, hipSetDevice(h->cfg.device));
-  const hipError_t e = bank_new(h, capacity_rows, max_passages, nbits, n_centroids, centroids_f16, bucket_weights, out);
-  if (e != hipSuccess)
-    return fail(h, e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP, "%s: %lld rows of %d at %d bits, %d centroids: %s", what,
-                (long long)capacity_rows, D, nbits, n_centroids, hipGetErrorString(e));
-  return RR_OK;
+static int rr_bank_add_impl(rr_bank* b, const void* context_li, int dtype, const float* context_mask, const int32_t* lengths, int n,
+                            int Lc, int32_t* first_index_out, void* hip_stream) {
+  const char* what = "rr_bank_add";
+  if (!b) return RR_ERR_BAD_ARG;
+  if (b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on a compressed bank: it takes residual codes (rr_bank_add_plaid); nothing here compresses", what);
+  return bank_add_padded(b, what, context_li, dtype, context_mask, lengths, n, Lc, first_index_out, hip_stream);
 }
 
 // every check on the host first; then three copies (a fill for a NULL mask) and one synchronisation: a load-time call
@@ -2254,8 +2273,7 @@ static int rr_bank_set_plaid_cutoffs_impl(rr_bank* b, const float* cutoffs_host)
   return RR_OK;
 }
 
-// rr_bank_add_compress: rr_bank_add's checks and staging, then the kernels of bank_compress.hip into the bank's codes, residual
-// bytes and mask bytes.  Everything that can refuse comes before the first enqueue.
+// rr_bank_add_compress: what a bank must be to compress, then rr_bank_add's body
 static int rr_bank_add_compress_impl(rr_bank* b, const void* context_li, int dtype, const float* context_mask, const int32_t* lengths,
                                      int n, int Lc, int32_t* first_index_out, void* hip_stream) {
   const char* what = "rr_bank_add_compress";
@@ -2263,41 +2281,7 @@ static int rr_bank_add_compress_impl(rr_bank* b, const void* context_li, int dty
   if (!b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it keeps embeddings as fp16 rows (rr_bank_add)", what);
   if (!b->has_cutoffs) return bfail(b, RR_ERR_UNSUPPORTED, "%s: the bank has no bucket cutoffs (rr_bank_set_plaid_cutoffs)", what);
   if (b->D % 16) return bfail(b, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a multiple of 16: the matrix-core step of the centroid search)", what, b->D);
-  if (!context_li || !context_mask || !lengths) return bfail(b, RR_ERR_BAD_ARG, "%s: null argument", what);
-  if (dtype != RR_F32 && dtype != RR_F16) return bfail(b, RR_ERR_BAD_DTYPE, "%s: dtype %d (RR_F32 or RR_F16)", what, dtype);
-  if (((uintptr_t)context_li) & 15) return bfail(b, RR_ERR_BAD_ARG, "%s: context_li must be 16-byte aligned", what);
-  if (n <= 0 || Lc <= 0 || (long long)n * Lc > (1LL << 40)) return bfail(b, RR_ERR_BAD_SHAPE, "%s: n=%d Lc=%d", what, n, Lc);
-  int64_t rows = 0;
-  RR_TRY(bank_admit(b, what, lengths, n, Lc, &rows));
-  hipStream_t st = (hipStream_t)hip_stream;
-  RR_TRY(bank_capture_guard(b, st, CAP_STAGES, what));
-  const rr_compress_plan pl = rr_plaid_compress_plan(rows, b->n_centroids, b->D);
-  if (pl.jt == 0)
-    return bfail(b, RR_ERR_BAD_SHAPE, "%s: %lld rows against %d centroids at the compress_chunk in force do not fit a launch", what,
-                 (long long)rows, b->n_centroids);
-  RR_BHIP(b, hipSetDevice(b->device));
-  if (b->cscratch_cap < pl.total) {                // grow-only; calls still in flight read the old block
-    RR_BHIP(b, hipDeviceSynchronize());
-    if (b->cscratch) { RR_BHIP(b, hipFree(b->cscratch)); b->cscratch = nullptr; b->cscratch_cap = 0; }
-    RR_BHIP(b, hipMalloc((void**)&b->cscratch, pl.total));
-    b->cscratch_cap = pl.total;
-  }
-  std::vector<rr_bank_slot> staged((size_t)n);
-  int64_t row = b->used_rows;
-  for (int i = 0; i < n; ++i) {
-    staged[(size_t)i] = rr_bank_slot{row, lengths[i], 0};
-    row += lengths[i];
-  }
-  rr_model::AsmSlot& a = b->slot[b->next];
-  RR_BHIP(b, stage_slot(a, staged.data(), staged.size() * sizeof(rr_bank_slot), (size_t)1024 * sizeof(rr_bank_slot), st));
-  const int64_t r0 = b->used_rows;
-  RR_BHIP(b, rr_launch_plaid_compress(context_li, dtype == RR_F16, context_mask, (const rr_bank_slot*)a.dev, n, Lc, r0, rows, b->D, b->nbits,
-                                      b->centroids, b->n_centroids, b->cutoffs, b->cscratch, pl, b->codes + r0,
-                                      b->resid + (size_t)r0 * b->resid_row_bytes(), b->mask + r0, st));
-  RR_BHIP(b, hipEventRecord(a.done, st));
-  b->next ^= 1;
-  bank_append(b, lengths, n, first_index_out);
-  return RR_OK;
+  return bank_add_padded(b, what, context_li, dtype, context_mask, lengths, n, Lc, first_index_out, hip_stream);
 }
 
 // rr_op_plaid_compress_rows (include/rerank_mi355_diag.h): the kernels over loose device pointers; its scratch lives for the call
@@ -2316,31 +2300,11 @@ static int rr_op_plaid_compress_rows_impl(const void* rows, int dtype, int64_t n
   char* scratch = nullptr;
   hipError_t e = hipMalloc((void**)&scratch, pl.total);
   if (e != hipSuccess) return e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP;
-  e = rr_launch_plaid_compress(rows, dtype == RR_F16, nullptr, nullptr, 0, 0, 0, n_rows, D, nbits, centroids_f16, n_centroids, cutoffs, scratch,
-                               pl, codes_out, residuals_out, nullptr, st);
+  e = rr_launch_plaid_compress(rr_padded_rows{rows, dtype == RR_F16, nullptr, nullptr, 0, 0}, 0, n_rows, D, nbits, centroids_f16, n_centroids,
+                               cutoffs, scratch, pl, codes_out, residuals_out, nullptr, st);
   const hipError_t e2 = hipStreamSynchronize(st);
   (void)hipFree(scratch);
   return e == hipSuccess && e2 == hipSuccess ? RR_OK : RR_ERR_HIP;
-}
-
-// rr_bank_read_plaid: the stored form of one passage of a compressed bank, copied to the host
-static int rr_bank_read_plaid_impl(rr_bank* b, int32_t index, int32_t* codes_out, uint8_t* resid_out, uint8_t* mask_out, int32_t capacity_rows,
-                                   void* hip_stream) {
-  const char* what = "rr_bank_read_plaid";
-  if (!b) return RR_ERR_BAD_ARG;
-  if (!b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it holds no codes (rr_bank_read)", what);
-  if (index < 0 || (size_t)index >= b->first.size()) return bfail(b, RR_ERR_BAD_SHAPE, "%s: passage %d of %zu", what, index, b->first.size());
-  const int32_t len = b->len[(size_t)index];
-  if (!codes_out && !resid_out && !mask_out) return len;
-  if (capacity_rows < len) return bfail(b, RR_ERR_BAD_SHAPE, "%s: passage %d holds %d rows, the buffers %d", what, index, len, capacity_rows);
-  RR_BHIP(b, hipSetDevice(b->device));
-  RR_BHIP(b, hipStreamSynchronize((hipStream_t)hip_stream));
-  const int64_t r0 = b->first[(size_t)index];
-  const size_t rb = b->resid_row_bytes();
-  if (codes_out) RR_BHIP(b, hipMemcpy(codes_out, b->codes + r0, (size_t)len * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (resid_out) RR_BHIP(b, hipMemcpy(resid_out, b->resid + (size_t)r0 * rb, (size_t)len * rb, hipMemcpyDeviceToHost));
-  if (mask_out) RR_BHIP(b, hipMemcpy(mask_out, b->mask + r0, (size_t)len, hipMemcpyDeviceToHost));
-  return len;
 }
 
 static int rr_op_plaid_decode_rows_impl(const uint16_t* centroids_f16, int32_t n_centroids, const float* bucket_weights, int nbits, int D,
@@ -2356,15 +2320,18 @@ static int rr_op_plaid_decode_rows_impl(const uint16_t* centroids_f16, int32_t n
   return e == hipSuccess ? RR_OK : RR_ERR_HIP;
 }
 
-static int rr_bank_read_impl(rr_bank* b, int32_t index, uint16_t* rows_out, uint8_t* mask_out, int32_t capacity_rows, void* hip_stream) {
-  if (!b) return RR_ERR_BAD_ARG;
-  if (index < 0 || (size_t)index >= b->first.size()) return bfail(b, RR_ERR_BAD_SHAPE, "rr_bank_read: passage %d of %zu", index, b->first.size());
+// rr_bank_read (rows_out, mask_out) and rr_bank_read_plaid (codes_out, resid_out, mask_out) behind their own refusals: one passage
+// copied to the host.  All outputs null: its length alone, nothing synchronised.
+static int bank_read(rr_bank* b, const char* what, int32_t index, uint16_t* rows_out, int32_t* codes_out, uint8_t* resid_out, uint8_t* mask_out,
+                     int32_t capacity_rows, void* hip_stream) {
+  if (index < 0 || (size_t)index >= b->first.size()) return bfail(b, RR_ERR_BAD_SHAPE, "%s: passage %d of %zu", what, index, b->first.size());
   const int32_t len = b->len[(size_t)index];
-  if (!rows_out && !mask_out) return len;
-  if (capacity_rows < len) return bfail(b, RR_ERR_BAD_SHAPE, "rr_bank_read: passage %d holds %d rows, the buffers %d", index, len, capacity_rows);
+  if (!rows_out && !codes_out && !resid_out && !mask_out) return len;
+  if (capacity_rows < len) return bfail(b, RR_ERR_BAD_SHAPE, "%s: passage %d holds %d rows, the buffers %d", what, index, len, capacity_rows);
   RR_BHIP(b, hipSetDevice(b->device));
   RR_BHIP(b, hipStreamSynchronize((hipStream_t)hip_stream));
   const int64_t r0 = b->first[(size_t)index];
+  const size_t rb = b->resid_row_bytes();
   if (rows_out && b->nbits) {                      // decoded by the kernel function the gather uses
     const size_t bytes = (size_t)len * b->D * sizeof(uint16_t);
     uint16_t* tmp = nullptr;
@@ -2377,8 +2344,24 @@ static int rr_bank_read_impl(rr_bank* b, int32_t index, uint16_t* rows_out, uint
   } else if (rows_out) {
     RR_BHIP(b, hipMemcpy(rows_out, b->rows + (size_t)r0 * b->D, (size_t)len * b->D * sizeof(uint16_t), hipMemcpyDeviceToHost));
   }
+  if (codes_out) RR_BHIP(b, hipMemcpy(codes_out, b->codes + r0, (size_t)len * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (resid_out) RR_BHIP(b, hipMemcpy(resid_out, b->resid + (size_t)r0 * rb, (size_t)len * rb, hipMemcpyDeviceToHost));
   if (mask_out) RR_BHIP(b, hipMemcpy(mask_out, b->mask + r0, (size_t)len, hipMemcpyDeviceToHost));
   return len;
+}
+
+static int rr_bank_read_impl(rr_bank* b, int32_t index, uint16_t* rows_out, uint8_t* mask_out, int32_t capacity_rows, void* hip_stream) {
+  if (!b) return RR_ERR_BAD_ARG;
+  return bank_read(b, "rr_bank_read", index, rows_out, nullptr, nullptr, mask_out, capacity_rows, hip_stream);
+}
+
+// rr_bank_read_plaid: the stored form of one passage of a compressed bank
+static int rr_bank_read_plaid_impl(rr_bank* b, int32_t index, int32_t* codes_out, uint8_t* resid_out, uint8_t* mask_out, int32_t capacity_rows,
+                                   void* hip_stream) {
+  const char* what = "rr_bank_read_plaid";
+  if (!b) return RR_ERR_BAD_ARG;
+  if (!b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it holds no codes (rr_bank_read)", what);
+  return bank_read(b, what, index, nullptr, codes_out, resid_out, mask_out, capacity_rows, hip_stream);
 }
 
 // FullContextRerankModel.forward (rerank_model.py:523-591) on the tokenised pairs.  FAM_JOINT: RerankModel.forward semantics

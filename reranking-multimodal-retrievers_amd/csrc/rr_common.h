@@ -447,8 +447,11 @@ hipError_t rr_launch_assemble_joint(const int32_t* pool, long long pool_len, con
 // query), checked against the bank, the segment and n_queries before it is staged.
 struct rr_bank_slot { int64_t first_row; int32_t len, unused0; };
 struct rr_bank_pair { int64_t first_row; int32_t len, query; };
-hipError_t rr_launch_bank_ingest(const void* src, int src_f16, const float* mask, const rr_bank_slot* slots, int n, int Lc, int D,
-                                 uint16_t* rows, uint8_t* mask_bytes, hipStream_t st);
+// The padded source of an add as both launchers that take one read it: src [n][Lc][D] (src_f16: fp16 bits, else float32), mask
+// [n][Lc] float32, slots[i] = (first destination row, length) on the device.  slots == null (rr_launch_plaid_compress alone): src
+// holds its rows back to back, no mask, n and Lc unused.
+struct rr_padded_rows { const void* src; int src_f16; const float* mask; const rr_bank_slot* slots; int n, Lc; };
+hipError_t rr_launch_bank_ingest(const rr_padded_rows& in, int D, uint16_t* rows, uint8_t* mask_bytes, hipStream_t st);
 // The context rows of a bank as the launchers take them, fp16 or compressed (PLAID residual codes): nbits == 0: `rows` [.][D] fp16
 // bits; else codes [.] int32, resid [.][D * nbits / 8], centroids [n_centroids][D] fp16 bits, weights [2^nbits] float32.  mask:
 // one byte per row.  All on the device.  rr_api.hip builds it from an rr_bank (bank_view), the diagnostic operators from their
@@ -524,9 +527,9 @@ bool rr_plaid_compress_shape_ok(int nbits, int D);
 int rr_set_compress_chunk(int centroids);      // rr_set_tuning("compress_chunk"): 0 (chosen per launch) or a multiple of 16 in [16, 2^24], -1 outside
 int rr_set_compress_stop_after(int stage);     // rr_set_tuning("compress_stop_after"): 1 (all) or 0 (the assignment kernel only), -1 outside
 rr_compress_plan rr_plaid_compress_plan(long long R, int C, int D);
-hipError_t rr_launch_plaid_compress(const void* src, int src_f16, const float* mask, const rr_bank_slot* slots, int n, int Lc, long long base,
-                                    long long R, int D, int nbits, const uint16_t* centroids, int C, const float* cutoffs, char* scratch,
-                                    const rr_compress_plan& pl, int32_t* codes, uint8_t* resid, uint8_t* mask_bytes, hipStream_t st);
+hipError_t rr_launch_plaid_compress(const rr_padded_rows& in, long long base, long long R, int D, int nbits, const uint16_t* centroids, int C,
+                                    const float* cutoffs, char* scratch, const rr_compress_plan& pl, int32_t* codes, uint8_t* resid,
+                                    uint8_t* mask_bytes, hipStream_t st);
 // rr_util_plaid_compress_rows: the definition in host code (passage_bank.hip, beside the host decoder)
 bool rr_plaid_compress_rows_host(const void* rows, int rows_f16, long long n_rows, int D, const uint16_t* centroids, int C,
                                  const float* cutoffs, int nbits, int32_t* codes_out, uint8_t* resid_out);

@@ -392,44 +392,26 @@ class PassageBank:
         its last unmasked token, at least 1) as the host knows them; without it they are derived on the device and copied once.
         Returns the first of the n dense indices.  An id added twice raises ValueError, a length outside [1, Lc] ValueError,
         rows or passage slots that do not suffice MemoryError; the bank is unchanged then."""
-        import numpy as np
-        import torch
-        from .pair_inputs import pair_lengths
-        L = self._L
         if self.codec is not None:
             raise NotImplementedError("a compressed bank takes residual codes (add_compressed): nothing here compresses embeddings")
-        ids = list(passage_ids)
-        n = len(ids)
-        if context_li.dim() != 3 or context_li.shape[0] != n or context_li.shape[2] != self.li_dim:
-            raise ValueError(f"context_li must be [{n}, Lc, {self.li_dim}], got {tuple(context_li.shape)}")
-        Lc = int(context_li.shape[1])
-        self.table.check_new(ids)
-        dt = context_li.dtype if context_li.dtype in (torch.float32, torch.float16) else torch.float32
-        li = context_li.to(device=self.device, dtype=dt).contiguous()
-        cm = context_mask.reshape(n, Lc).to(device=self.device, dtype=torch.float32).contiguous()
-        if lengths is None:
-            lengths = pair_lengths(cm).cpu().numpy()
-        ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1), dtype=np.int32)
-        if ln.size != n:
-            raise ValueError(f"{ln.size} lengths for {n} passages")
-        first = C.c_int32(-1)
-        self._check(self.lib.rr_bank_add(self.h, L.ptr(li), L.RR_F16 if dt == torch.float16 else L.RR_F32, L.ptr(cm), ln.ctypes.data,
-                                         n, Lc, C.byref(first), self._stream()), "rr_bank_add", bad_shape=ValueError)
-        self.table.append(ids, ln.tolist(), int(first.value))
-        self.padded_len = max(self.padded_len, Lc)
-        return int(first.value)
+        return self._add_padded("rr_bank_add", passage_ids, context_li, context_mask, lengths)
 
     def add_compress(self, passage_ids: Sequence, context_li, context_mask, lengths: Optional[Sequence[int]] = None) -> int:
         """`add` for a compressed bank (rr_bank_add_compress): the padded tensors a retriever produces are compressed on the
         device against the codec's centroids and cutoffs and appended as codes and residual bytes — the compressed row of
         include/rerank_mi355.h, what the reference's indexer computes from `context_li.half()`.  Arguments, return value and
         errors as `add`; an fp16 bank, a codec without cutoffs and an li_dim that is no multiple of 16 raise NotImplementedError."""
+        if self.codec is None:
+            raise NotImplementedError("add_compress on an fp16 bank: it keeps embeddings as they are (add)")
+        return self._add_padded("rr_bank_add_compress", passage_ids, context_li, context_mask, lengths)
+
+    def _add_padded(self, entry_name: str, passage_ids, context_li, context_mask, lengths) -> int:
+        """`add` and `add_compress` behind their own refusals: the padded tensors brought to the device as the entry point
+        `entry_name` (rr_bank_add / rr_bank_add_compress) takes them, the call, the ids appended to the table."""
         import numpy as np
         import torch
         from .pair_inputs import pair_lengths
         L = self._L
-        if self.codec is None:
-            raise NotImplementedError("add_compress on an fp16 bank: it keeps embeddings as they are (add)")
         ids = list(passage_ids)
         n = len(ids)
         if context_li.dim() != 3 or context_li.shape[0] != n or context_li.shape[2] != self.li_dim:
@@ -445,9 +427,8 @@ class PassageBank:
         if ln.size != n:
             raise ValueError(f"{ln.size} lengths for {n} passages")
         first = C.c_int32(-1)
-        self._check(self.lib.rr_bank_add_compress(self.h, L.ptr(li), L.RR_F16 if dt == torch.float16 else L.RR_F32, L.ptr(cm),
-                                                  ln.ctypes.data, n, Lc, C.byref(first), self._stream()), "rr_bank_add_compress",
-                    bad_shape=ValueError)
+        self._check(getattr(self.lib, entry_name)(self.h, L.ptr(li), L.RR_F16 if dt == torch.float16 else L.RR_F32, L.ptr(cm), ln.ctypes.data,
+                                                  n, Lc, C.byref(first), self._stream()), entry_name, bad_shape=ValueError)
         self.table.append(ids, ln.tolist(), int(first.value))
         self.padded_len = max(self.padded_len, Lc)
         return int(first.value)
@@ -531,14 +512,7 @@ class PassageBank:
         """One passage back on the host (rr_bank_read; synchronises the current stream): (rows [len, D] float16, mask [len]
         uint8).  A compressed bank returns the decoded rows: what its forwards use."""
         import torch
-        idx, lens = self.table.lookup([passage_id])
-        n = int(lens[0])
-        rows = torch.empty((n, self.li_dim), dtype=torch.float16)
-        mask = torch.empty(n, dtype=torch.uint8)
-        got = self.lib.rr_bank_read(self.h, int(idx[0]), rows.data_ptr(), mask.data_ptr(), n, self._stream())
-        self._check(got, "rr_bank_read")
-        assert got == n, f"the bank holds {got} rows for passage {passage_id!r}, the table {n}"
-        return rows, mask
+        return self._read("rr_bank_read", passage_id, ((self.li_dim,), torch.float16), ((), torch.uint8))
 
     def read_compressed(self, passage_id):
         """One passage of a compressed bank back on the host as it is stored (rr_bank_read_plaid; synchronises the current
@@ -546,15 +520,18 @@ class PassageBank:
         import torch
         if self.codec is None:
             raise NotImplementedError("read_compressed on an fp16 bank: it holds no codes (read)")
+        return self._read("rr_bank_read_plaid", passage_id, ((), torch.int32), ((self.codec.residual_bytes,), torch.uint8), ((), torch.uint8))
+
+    def _read(self, entry_name: str, passage_id, *outputs):
+        """`read` and `read_compressed`: host tensors [len, *shape] of `outputs` = (shape, dtype), ..., filled by `entry_name`."""
+        import torch
         idx, lens = self.table.lookup([passage_id])
         n = int(lens[0])
-        codes = torch.empty(n, dtype=torch.int32)
-        res = torch.empty((n, self.codec.residual_bytes), dtype=torch.uint8)
-        mask = torch.empty(n, dtype=torch.uint8)
-        got = self.lib.rr_bank_read_plaid(self.h, int(idx[0]), codes.data_ptr(), res.data_ptr(), mask.data_ptr(), n, self._stream())
-        self._check(got, "rr_bank_read_plaid")
+        outs = tuple(torch.empty((n, *shape), dtype=dt) for shape, dt in outputs)
+        got = getattr(self.lib, entry_name)(self.h, int(idx[0]), *(o.data_ptr() for o in outs), n, self._stream())
+        self._check(got, entry_name)
         assert got == n, f"the bank holds {got} rows for passage {passage_id!r}, the table {n}"
-        return codes, res, mask
+        return outs
 
     def maxsim(self, engine, query_li, passage_ids, **kw):
         """The retriever's MaxSim [n_pairs] of the pairs (query, passage id) from this bank: engine.bank_li_scores(...)["maxsim"]."""

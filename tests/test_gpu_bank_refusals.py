@@ -1,10 +1,14 @@
 """GPU: the full text of the refusals that the bank entry points share — rr_forward_interaction_bank, rr_bank_li_scores,
-rr_bank_search, rr_bank_add and rr_bank_add_plaid (include/rerank_mi355.h).
+rr_bank_search, rr_bank_add, rr_bank_add_plaid and rr_bank_add_compress — and of those of rr_bank_create, rr_bank_create_plaid,
+rr_bank_read, rr_bank_read_plaid and rr_bank_set_plaid_cutoffs (include/rerank_mi355.h).
 
 The other bank suites sample these messages by substring; here the return code and the COMPLETE rr_last_error /
 rr_bank_last_error string of each is pinned, written out by hand from the format strings of csrc/rr_api.hip, on an fp16 bank and
 on an nbits = 2 bank of three passages (2, 5 and 3 rows) with Lq = 4.  Every call is refused on the host before anything is
-enqueued: an output buffer a call was handed keeps its sentinel, a bank keeps its contents."""
+enqueued: an output buffer a call was handed keeps its sentinel, a bank keeps its contents.
+
+Not pinned: rr_bank_add_compress's "li_dim %d (a multiple of 16 ...)" refusal.  It needs a compressed bank of li_dim 8, the only
+li_dim a codec takes that is no multiple of 16, and rr_create takes no li_dim that is not a multiple of 64."""
 import ctypes as C
 
 import numpy as np
@@ -21,6 +25,7 @@ ROWS, CAP_ROWS, SLOTS = sum(LENS), sum(LENS) + 2, len(LENS) + 1      # two rows 
 NQ, LQ, LC = 2, 4, 5
 POISON, IPOISON = -12345.0, -77
 PP, PQ = [0, 1, 2], [0, 1, 1]
+CUTOFFS = [-0.05, 0.0, 0.05]
 FIB, BLS, SEARCH = "rr_forward_interaction_bank", "rr_bank_li_scores", "rr_bank_search"
 
 
@@ -38,9 +43,12 @@ class _Setup:
         ids = [f"p{i}" for i in range(len(LENS))]
         self.fp16 = self.eng.create_bank(CAP_ROWS, SLOTS)
         self.fp16.add(ids, li, cm, lengths=LENS)
-        codec = _codec(D, 2)
+        from rmr_amd import PlaidCodec
+        bare = self.codec = _codec(D, 2)                                # no cutoffs
+        codec = PlaidCodec(bare.centroids, bare.bucket_weights, 2, bucket_cutoffs=torch.tensor(CUTOFFS))
         self.codes, self.res = _rows(codec, ROWS, seed=9)
         self.plaid = self.eng.create_bank(CAP_ROWS, SLOTS, codec=codec)
+        self.bare = self.eng.create_bank(CAP_ROWS, SLOTS, codec=bare)   # a compressed bank that cannot compress: empty
         self.plaid.add_compressed(ids, self.codes, self.res, LENS)
         self.other = wide.create_bank(8, 2)                             # a second engine's bank: rows of 128
         # one spare row behind the queries, so that the pointer 4 bytes on still points into the tensor
@@ -87,10 +95,15 @@ class _Setup:
             self.eng.h, bank.h, self.q.data_ptr() if q_ptr is None else q_ptr, NQ, LQ, 0, -1, 2, self.top_i.data_ptr(),
             self.top_s.data_ptr(), self.stream())
 
-    def add(self, bank, lengths, first):
+    # rr_bank_add / rr_bank_add_compress (`entry`) on the padded device tensors; li, dtype, cm, ln, n: what a case hands over instead
+    def add(self, bank, lengths, first, entry="rr_bank_add", **over):
         ln = np.asarray(lengths, dtype=np.int32)
-        return self.eng.lib.rr_bank_add(bank.h, self.add_li.data_ptr(), self.L.RR_F32, self.add_cm.data_ptr(), ln.ctypes.data, len(ln), LC,
-                                        C.byref(first), self.stream())
+        a = dict(li=self.add_li.data_ptr(), dtype=self.L.RR_F32, cm=self.add_cm.data_ptr(), ln=ln.ctypes.data, n=len(ln))
+        a.update(over)
+        return getattr(self.eng.lib, entry)(bank.h, a["li"], a["dtype"], a["cm"], a["ln"], a["n"], LC, C.byref(first), self.stream())
+
+    def add_compress(self, bank, lengths, first, **over):
+        return self.add(bank, lengths, first, entry="rr_bank_add_compress", **over)
 
     def add_plaid(self, bank, lengths, first):
         ln = np.asarray(lengths, dtype=np.int32)
@@ -106,7 +119,8 @@ class _Setup:
 
     def banks_unchanged(self):
         want = dict(passages=len(LENS), rows_used=ROWS, capacity_rows=CAP_ROWS)
-        return all({k: b.info()[k] for k in want} == want and len(b) == len(LENS) for b in (self.fp16, self.plaid))
+        held = all({k: b.info()[k] for k in want} == want and len(b) == len(LENS) for b in (self.fp16, self.plaid))
+        return held and self.bare.info()["passages"] == 0 and self.bare.info()["rows_used"] == 0
 
 
 @pytest.fixture(scope="module")
@@ -157,6 +171,138 @@ def test_add_admission_and_the_wrong_kind_of_bank(s):
     assert first.value == -7 and s.banks_unchanged()
 
 
+def test_the_padded_adds_refuse_alike(s):
+    """rr_bank_add and rr_bank_add_compress, each on its own kind of bank, in the order they refuse: the wrong kind of bank (and for
+    the compressing add a codec without cutoffs), a null argument, the dtype, the alignment, n / Lc, a length, the slots, the rows."""
+    L = s.L
+    first = C.c_int32(-7)
+    for what, add, bank in (("rr_bank_add", s.add, s.fp16), ("rr_bank_add_compress", s.add_compress, s.plaid)):
+        for null in ("li", "cm", "ln"):
+            assert add(bank, [1], first, **{null: None}) == L.RR_ERR_BAD_ARG
+            assert s.bank_err(bank) == f"{what}: null argument"
+        assert add(bank, [1], first, dtype=L.RR_BF16) == L.RR_ERR_BAD_DTYPE
+        assert s.bank_err(bank) == f"{what}: dtype 1 (RR_F32 or RR_F16)"
+        assert add(bank, [1], first, dtype=7) == L.RR_ERR_BAD_DTYPE
+        assert s.bank_err(bank) == f"{what}: dtype 7 (RR_F32 or RR_F16)"
+        assert add(bank, [1], first, li=s.add_li.data_ptr() + 4) == L.RR_ERR_BAD_ARG
+        assert s.bank_err(bank) == f"{what}: context_li must be 16-byte aligned"
+        assert add(bank, [1], first, n=0) == L.RR_ERR_BAD_SHAPE
+        assert s.bank_err(bank) == f"{what}: n=0 Lc=5"
+        assert add(bank, [1, 0], first) == L.RR_ERR_BAD_SHAPE
+        assert s.bank_err(bank) == f"{what}: passage 1 has length 0 (1..5)"
+        assert add(bank, [6], first) == L.RR_ERR_BAD_SHAPE               # Lc is 5
+        assert s.bank_err(bank) == f"{what}: passage 0 has length 6 (1..5)"
+        assert add(bank, [1, 1], first) == L.RR_ERR_OOM                  # two passages, one slot is free
+        assert s.bank_err(bank) == f"{what}: 3 + 2 passages exceed the bank's 4 slots"
+        assert add(bank, [3], first) == L.RR_ERR_OOM                     # three rows, two are free
+        assert s.bank_err(bank) == f"{what}: 10 + 3 rows exceed the bank's 12"
+        # the kind of bank is asked before anything else: here with a null argument, a dtype and an n that would be refused too
+        wrong = s.plaid if bank is s.fp16 else s.fp16
+        assert add(wrong, [1], first, li=None, dtype=7, n=0) == L.RR_ERR_UNSUPPORTED
+        assert s.bank_err(wrong) == ("rr_bank_add on a compressed bank: it takes residual codes (rr_bank_add_plaid); nothing here compresses"
+                                     if bank is s.fp16 else
+                                     "rr_bank_add_compress on an fp16 bank: it keeps embeddings as fp16 rows (rr_bank_add)")
+    assert s.add_compress(s.bare, [1], first, li=None) == L.RR_ERR_UNSUPPORTED        # the cutoffs are asked before the arguments
+    assert s.bank_err(s.bare) == "rr_bank_add_compress: the bank has no bucket cutoffs (rr_bank_set_plaid_cutoffs)"
+    assert first.value == -7 and s.banks_unchanged()
+
+
+def test_create_refusals(s):
+    """rr_bank_create and rr_bank_create_plaid report through the handle; a refused call leaves *out null."""
+    L, lib = s.L, s.eng.lib
+    full = type(s.eng)(dict(s.eng.arch, model_kind="full_context"))      # no weights: a handle is all the call asks for
+    cen, w = s.codec.centroids.data_ptr(), s.codec.bucket_weights.data_ptr()
+    NC = s.codec.n_centroids
+
+    def plain(h, cap, slots, out):
+        return lib.rr_bank_create(h, cap, slots, out)
+
+    def plaid(h, cap, slots, out, nbits=2, nc=NC, cen=cen, w=w):
+        return lib.rr_bank_create_plaid(h, cap, slots, nbits, nc, cen, w, out)
+
+    def err(h):
+        return lib.rr_last_error(h).decode()
+    for what, create, tail in (("rr_bank_create", plain, ""), ("rr_bank_create_plaid", plaid, f" n_centroids={NC}")):
+        out = C.c_void_p(0xdead0)
+        assert create(s.eng.h, 8, 4, None) == L.RR_ERR_BAD_ARG
+        assert err(s.eng.h) == f"{what}: null out"
+        assert create(full.h, 8, 4, C.byref(out)) == L.RR_ERR_BAD_ARG
+        assert err(full.h) == f"{what} on a full-context model" and out.value is None
+        for cap, slots in ((0, 4), (-1, 4), (8, 0), ((1 << 40) + 1, 4)):
+            out = C.c_void_p(0xdead0)
+            assert create(s.eng.h, cap, slots, C.byref(out)) == L.RR_ERR_BAD_SHAPE
+            assert err(s.eng.h) == f"{what}: capacity_rows={cap} max_passages={slots}{tail}" and out.value is None
+    out = C.c_void_p(0xdead0)
+    what = "rr_bank_create_plaid"
+    for null in (dict(cen=None), dict(w=None)):
+        assert plaid(s.eng.h, 8, 4, C.byref(out), nbits=3, nc=0, **null) == L.RR_ERR_BAD_ARG    # before the shape and the counts
+        assert err(s.eng.h) == f"{what}: null table"
+    assert plaid(s.eng.h, 0, 4, C.byref(out), nbits=3) == L.RR_ERR_UNSUPPORTED                  # before the capacity
+    assert err(s.eng.h) == f"{what}: nbits 3, li_dim 64 (nbits 1, 2, 4 or 8; li_dim a power of two in [8, 512], a multiple of 8 * nbits)"
+    assert plaid(s.eng.h, 8, 4, C.byref(out), nbits=16) == L.RR_ERR_UNSUPPORTED                 # 64 is no multiple of 8 * 16
+    assert err(s.eng.h) == f"{what}: nbits 16, li_dim 64 (nbits 1, 2, 4 or 8; li_dim a power of two in [8, 512], a multiple of 8 * nbits)"
+    for nc in (0, -3, (1 << 24) + 1):
+        assert plaid(s.eng.h, 8, 4, C.byref(out), nc=nc) == L.RR_ERR_BAD_SHAPE
+        assert err(s.eng.h) == f"{what}: capacity_rows=8 max_passages=4 n_centroids={nc}"
+    assert out.value is None and s.banks_unchanged()
+
+
+def test_read_refusals_and_the_length_only_call(s):
+    L, lib = s.L, s.eng.lib
+    D = s.D
+    rows = torch.full((LC, D), 7.0, dtype=torch.float16)
+    codes = torch.full((LC,), IPOISON, dtype=torch.int32)
+    res = torch.full((LC, s.codec.residual_bytes), 0xA5, dtype=torch.uint8)
+    mask = torch.full((LC,), 0xA5, dtype=torch.uint8)
+
+    def read(bank, index, cap, outs=True):
+        return lib.rr_bank_read(bank.h, index, rows.data_ptr() if outs else None, mask.data_ptr() if outs else None, cap, s.stream())
+
+    def read_plaid(bank, index, cap, outs=True):
+        return lib.rr_bank_read_plaid(bank.h, index, codes.data_ptr() if outs else None, res.data_ptr() if outs else None,
+                                      mask.data_ptr() if outs else None, cap, s.stream())
+    for what, call, banks in (("rr_bank_read", read, (s.fp16, s.plaid)), ("rr_bank_read_plaid", read_plaid, (s.plaid,))):
+        for bank in banks:
+            for index in (3, -1):
+                assert call(bank, index, LC) == L.RR_ERR_BAD_SHAPE
+                assert s.bank_err(bank) == f"{what}: passage {index} of 3"
+                assert call(bank, index, 0, outs=False) == L.RR_ERR_BAD_SHAPE          # the index comes before the length-only answer
+                assert s.bank_err(bank) == f"{what}: passage {index} of 3"
+            assert call(bank, 1, 4) == L.RR_ERR_BAD_SHAPE                              # passage 1 holds 5 rows
+            assert s.bank_err(bank) == f"{what}: passage 1 holds 5 rows, the buffers 4"
+            assert [call(bank, i, 0, outs=False) for i in range(3)] == LENS            # all outputs null: the length, whatever the capacity
+    assert read_plaid(s.fp16, 1, LC) == L.RR_ERR_UNSUPPORTED
+    assert s.bank_err(s.fp16) == "rr_bank_read_plaid on an fp16 bank: it holds no codes (rr_bank_read)"
+    assert read_plaid(s.fp16, 7, 0, outs=False) == L.RR_ERR_UNSUPPORTED                # the kind of bank comes before the index
+    assert s.bank_err(s.fp16) == "rr_bank_read_plaid on an fp16 bank: it holds no codes (rr_bank_read)"
+    assert bool((rows == 7.0).all()) and bool((codes == IPOISON).all()) and bool((res == 0xA5).all()) and bool((mask == 0xA5).all())
+    assert s.banks_unchanged()
+
+
+def test_cutoffs_refusals(s):
+    L, lib = s.L, s.eng.lib
+    what = "rr_bank_set_plaid_cutoffs"
+
+    def put(bank, values):
+        v = np.asarray(values, dtype=np.float32)
+        return lib.rr_bank_set_plaid_cutoffs(bank.h, v.ctypes.data if values is not None else None)
+    assert put(s.fp16, None) == L.RR_ERR_UNSUPPORTED                                   # the kind of bank comes before the argument
+    assert s.bank_err(s.fp16) == f"{what} on an fp16 bank: it holds embeddings as they are (rr_bank_add)"
+    for bank in (s.plaid, s.bare):
+        assert put(bank, None) == L.RR_ERR_BAD_ARG
+        assert s.bank_err(bank) == f"{what}: null argument"
+        assert put(bank, [0.0, float("nan"), -1.0]) == L.RR_ERR_BAD_SHAPE
+        assert s.bank_err(bank) == f"{what}: cutoff 1 is NaN"
+        assert put(bank, [-0.5, 0.25, 0.125]) == L.RR_ERR_BAD_SHAPE
+        assert s.bank_err(bank) == f"{what}: cutoff 2 (0.125) lies below cutoff 1 (0.25): the sequence must not decrease"
+        assert put(bank, [0.5, -1.0, 2.0]) == L.RR_ERR_BAD_SHAPE
+        assert s.bank_err(bank) == f"{what}: cutoff 1 (-1) lies below cutoff 0 (0.5): the sequence must not decrease"
+    first = C.c_int32(-7)
+    assert s.add_compress(s.bare, [1], first) == L.RR_ERR_UNSUPPORTED                  # a refused table is no table
+    assert s.bank_err(s.bare) == "rr_bank_add_compress: the bank has no bucket cutoffs (rr_bank_set_plaid_cutoffs)"
+    assert first.value == -7 and s.banks_unchanged()
+
+
 def test_a_capturing_stream(s):
     """Every call that stages, uploads or copies from the host refuses a stream that is being captured, in its own words; nothing
     but the probe enters the graph, and the same calls are taken once the capture is over."""
@@ -169,6 +315,7 @@ def test_a_capturing_stream(s):
         want[kind, SEARCH] = f"{SEARCH} cannot be captured into a graph (it may upload the bank's passage table and grow its block)"
     want["fp16", "add"] = f"rr_bank_add {staged}"
     want["nbits2", "add"] = "rr_bank_add_plaid cannot be captured into a graph (it copies from host memory and synchronises)"
+    want["nbits2", "add_compress"] = f"rr_bank_add_compress {staged}"
     got = {}
     first = C.c_int32(-7)
     probe = torch.zeros(1, device="cuda")
@@ -189,6 +336,8 @@ def test_a_capturing_stream(s):
                     got[kind, what] = (call(bank), s.err())
                 add = s.add if kind == "fp16" else s.add_plaid
                 got[kind, "add"] = (add(bank, [1], first), s.bank_err(bank))
+                if kind == "nbits2":
+                    got[kind, "add_compress"] = (s.add_compress(bank, [1], first), s.bank_err(bank))
         graph.replay()
         torch.cuda.synchronize()
     assert got == {k: (L.RR_ERR_BAD_ARG, v) for k, v in want.items()}

@@ -341,3 +341,75 @@ def test_refused_calls_leave_the_bank_unchanged():
     c, r, mk = bank.read_compressed("x")
     want = codec.compress(y[0, :5].cpu())
     assert torch.equal(c, want[0]) and torch.equal(r, want[1]) and mk.tolist() == [1] * 5
+
+
+# ---- 8. what rr_bank_add and rr_bank_add_compress share: admission, the two staging slots, the append ---------------------------------
+def _bank_pair(eng, cap_rows, slots):
+    """An fp16 bank and an nbits = 2 bank of 32 centroids (li_dim 64) of the same capacity."""
+    from rmr_amd import PlaidCodec
+    cen, cut, _ = _tables(64, 2, 32)
+    codec = PlaidCodec(cen, torch.tensor([-0.06, -0.02, 0.02, 0.06]), 2, bucket_cutoffs=cut)
+    return codec, eng.create_bank(cap_rows, slots), eng.create_bank(cap_rows, slots, codec=codec)
+
+
+def _holds(plain, bank, codec, pid, x, m, ln):
+    """Passage `pid` is rows 0 .. ln - 1 of the padded x [Lc, D] / m [Lc] (host): `x.half()` and (m != 0) in the fp16 bank, the host
+    definition's codes and bytes of the same rows in the compressed one."""
+    want_mask = (m[:ln] != 0).to(torch.uint8)
+    rows, mask = plain.read(pid)
+    assert rows.shape == (ln, x.shape[1]) and torch.equal(rows.view(torch.int16), x[:ln].half().view(torch.int16)), pid
+    assert torch.equal(mask, want_mask), pid
+    codes, res = _host(x[:ln].contiguous(), codec.centroids, codec.bucket_cutoffs, codec.nbits)
+    gc, gr, gm = bank.read_compressed(pid)
+    assert torch.equal(gc, codes) and torch.equal(gr, res) and torch.equal(gm, want_mask), pid
+
+
+def test_three_adds_back_to_back_reuse_a_staging_slot():
+    """A bank stages its (first row, length) slots through two buffers taking turns: the third add is the first that overwrites one,
+    and must wait for the first add's launch.  Device tensors and host lengths: nothing synchronises between the calls."""
+    eng, _ = _engine("int_tiny")
+    D, Lc = int(eng.arch["li_dim"]), 5
+    assert D == 64
+    calls = ([5, 2], [1, 4], [3, 3])
+    total = sum(map(sum, calls))
+    codec, plain, bank = _bank_pair(eng, total + 1, 2 * len(calls) + 1)
+    gen = torch.Generator().manual_seed(61)
+    host, dev = [], []
+    for k, lens in enumerate(calls):
+        x = torch.nn.functional.normalize(torch.randn(2, Lc, D, generator=gen), dim=-1)
+        x = x.half() if k == 1 else x                                    # an fp16 source between two float32 ones
+        m = (torch.arange(Lc)[None, :] < torch.tensor(lens)[:, None]).float()
+        i = max(range(2), key=lambda j: lens[j])
+        m[i, 1] = 0.0                                                    # one interior zero, in the longer passage
+        host.append((x, m))
+        dev.append((x.cuda(), m.cuda()))
+    torch.cuda.synchronize()
+    for b, add in ((plain, plain.add), (bank, bank.add_compress)):
+        for k, lens in enumerate(calls):
+            assert add([f"{k}/0", f"{k}/1"], *dev[k], lengths=lens) == 2 * k
+        assert b.info()["passages"] == 2 * len(calls) and b.info()["rows_used"] == total and b.padded_len == Lc
+    for k, lens in enumerate(calls):
+        for i, ln in enumerate(lens):
+            _holds(plain, bank, codec, f"{k}/{i}", host[k][0][i], host[k][1][i], ln)
+
+
+def test_one_add_of_more_passages_than_a_staging_slot_starts_with():
+    """1025 passages of one row: one descriptor more than the 1024 a staging slot starts with.  Two small adds first give both slots
+    that size, so that the slot grows inside the call."""
+    eng, _ = _engine("int_tiny")
+    D, n = int(eng.arch["li_dim"]), 1025
+    codec, plain, bank = _bank_pair(eng, n, n)
+    gen = torch.Generator().manual_seed(62)
+    x = torch.nn.functional.normalize(torch.randn(n, 1, D, generator=gen), dim=-1)
+    m = torch.ones(n, 1)
+    m[1023] = 0.0                                                        # no unmasked token: still one row, its mask byte 0
+    xd, md = x.cuda(), m.cuda()
+    ids = list(range(n))
+    for b, add in ((plain, plain.add), (bank, bank.add_compress)):
+        for warm in ("a", "b"):
+            add([warm], xd[:1], md[:1], lengths=[1])
+        b.clear()
+        assert add(ids, xd, md, lengths=[1] * n) == 0
+        assert b.info()["passages"] == n and b.info()["rows_used"] == n and len(b) == n
+    for i in (0, 1023, 1024):
+        _holds(plain, bank, codec, i, x[i], m[i], 1)

@@ -9,6 +9,8 @@ Rows are centroids plus a small residual, renormalised, handed over as fp16 (wha
   composed       on the kept rows, as the reference's ResidualCodec.compress does it on a GPU: float32 `centroids @ rows.T` in
                  chunks of (1 << 29) // centroids rows with `.max(0)`, the float32 residual, torch.bucketize, the bit packing by
                  shifts and a weighted sum, then PassageBank.add_compressed through the host.
+  add_fp16       PassageBank.add (rr_bank_add) of the same tensors into an fp16 bank of the same capacity, timed the same way in
+                 rounds of its own.
 
 Wall-clock ms per call (median of `--iters` calls, the two taking turns, `--rounds` times; the bank is cleared between calls), the
 device time of add_compress between two events, the same with rr_set_tuning("compress_stop_after") = 0: the row map and the
@@ -63,6 +65,7 @@ def main():
     weights = resid.quantile((torch.arange(0, nb) + 0.5) / nb).float()
     codec = rmr_amd.PlaidCodec(cen, weights, nbits, bucket_cutoffs=cutoffs)
     bank = eng.create_bank(R, P, codec=codec)
+    plain = eng.create_bank(R, P)
     ids = list(range(P))
     cen32, cut_d = cen.float(), cutoffs.to(dev)
     shifts = torch.arange(nbits, device=dev, dtype=torch.int32)
@@ -72,6 +75,10 @@ def main():
     def fused():
         bank.clear()
         bank.add_compress(ids, li, cm, lengths=lens)
+
+    def add_fp16():
+        plain.clear()
+        plain.add(ids, li, cm, lengths=lens)
 
     def composed():
         bank.clear()
@@ -109,10 +116,12 @@ def main():
             t.append(a.elapsed_time(b))
         return statistics.median(t)
 
-    per = dict(add_compress=[], composed=[])
+    per = dict(add_compress=[], composed=[], add_fp16=[])
     for _ in range(args.rounds):
         for key, x in zip(("add_compress", "composed"), wall([fused, composed])):
             per[key].append(round(statistics.median(x), 3))
+    for _ in range(args.rounds):
+        per["add_fp16"].append(round(statistics.median(wall([add_fp16])[0]), 3))
     mid = {k: statistics.median(v) for k, v in per.items()}
     composed()
     want_codes, want_res = last["codes"], last["res"]
@@ -137,7 +146,7 @@ def main():
     res = dict(device=torch.cuda.get_device_name(0), passages=P, Lc=Lc, lengths=[64, Lc], rows=R, D=D, nbits=nbits, centroids=Cn,
                iters=args.iters, warmup=args.warmup, rounds=args.rounds, round_medians_ms=per,
                add_compress_ms=round(mid["add_compress"], 3), composed_ms=round(mid["composed"], 3),
-               add_compress_over_composed=round(mid["add_compress"] / mid["composed"], 4),
+               add_compress_over_composed=round(mid["add_compress"] / mid["composed"], 4), add_fp16_ms=round(mid["add_fp16"], 3),
                add_compress_device_ms=round(call_dev, 3), assign_kernel_ms=round(assign_dev, 3),
                assign_tflops=round(flop / (assign_dev * 1e-3) / 1e12, 2), f32_matrix_core_tflops=155, li_scores_kernel_tflops=54,
                compared_rows=rows_cmp, codes_equal=same_code, rows_equal_where_codes_equal=same_rows)

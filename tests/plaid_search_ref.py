@@ -1,7 +1,8 @@
 """The contract of rr_bank_search_plaid (include/rerank_mi355.h) restated in numpy from a given S: cells, candidates, the two
 centroid-only pruning stages and the final cut.  Written from the definition: float32 scalars, maxima in which a NaN sticks,
 columns summed one after the other from 0.0f, and ONE order everywhere: NaN first, then higher score, then lower index
-(+0 == -0).  -inf marks "absent".  Helper of tests/test_plaid_search_cpu.py and tests/test_gpu_bank_search_plaid.py."""
+(+0 == -0).  -inf marks "absent".  Helper of tests/test_plaid_search_cpu.py, tests/test_gpu_bank_search_plaid.py
+and tests/plaid_exact_cases.py."""
 import numpy as np
 
 MASKED = np.float32(-9999.0)

@@ -532,7 +532,8 @@ int rr_bank_add(rr_bank_handle b, const void* context_li, int dtype, const float
  * with "nbits": 8), decoded on the device inside the gather of rr_forward_interaction_bank.  Replaces the reference's own native
  * kernel on the retriever-to-reranker hand-over (third_party/ColBERT/colbert/indexing/codecs/decompress_residuals.cu) and the
  * F.normalize behind it (codecs/residual.py:242-278).  Bytes per token at li_dim 128: 257 as fp16, 133 / 69 / 37 / 21 at nbits 8 /
- * 4 / 2 / 1.  Nothing here computes embeddings or trains a codec (k-means, quantiles); rr_bank_add_compress compresses embeddings
+ * 4 / 2 / 1.  Nothing here computes embeddings; rr_plaid_kmeans and rr_plaid_residuals (below) train the codec's tables from
+ * embeddings on the device; rr_bank_add_compress compresses embeddings
  * that are on the device against the codec's tables; rr_bank_search searches exhaustively;
  * rr_bank_search_plaid runs PLAID's candidate generation and centroid pruning over the codes a compressed bank holds.
  *
@@ -614,6 +615,57 @@ int rr_bank_format(rr_bank_handle b, int32_t* nbits_out, int32_t* n_centroids_ou
 int rr_bank_set_plaid_cutoffs(rr_bank_handle b, const float* cutoffs_host);
 int rr_bank_add_compress(rr_bank_handle b, const void* context_li, int dtype, const float* context_mask, const int32_t* lengths, int n,
                          int Lc, int32_t* first_index_out, void* hip_stream);
+/* ---- Training a PLAID codec on the device: the centroid table by k-means and the residuals the bucket statistics are taken
+ * from.  Replaces, in third_party/ColBERT/colbert/indexing/collection_indexer.py of the reference, train (:211-228),
+ * _concatenate_and_split_sample (:230-261), _train_kmeans (:263-293), _compute_avg_residual (:295-319) and compute_faiss_kmeans
+ * (:452-465).  faiss's random generator and its cluster-splitting rule cannot be reproduced, so the definition is this library's
+ * own; Lloyd's algorithm with L2 distance is what faiss runs.
+ *
+ * THE TRAINED CENTROIDS.  Inputs: rows [R, D] float32 or fp16, C distinct initial row indices init_rows in [0, R), niters >= 0, a
+ * 64-bit seed.
+ *   1. Rounding.  x = fp16_rne(row), as in THE COMPRESSED ROW step 1.  Everything below uses float32(x).
+ *   2. Initial table.  T [C, D] of fp16 values: T[c] = x[init_rows[c]].
+ *   3. Bias.  h[c] = -0.5f * q(c), q(c) the float32 sum of squares of float32(T[c][e]) summed in the fixed order of THE DECODED
+ *      ROW's norm: per chunk of 8 an fmaf chain from zero, then the pairwise tree over neighbours.
+ *   4. Per iteration i = 0 .. niters - 1:
+ *      Assignment.  S[c] is the fmaf chain of THE COMPRESSED ROW step 2; S'[c] = S[c] + h[c], one float32 add; code[r] is the
+ *        centroid with the largest rank key of (S'[c], c): the nearest centroid in L2, equal scores going to the lowest index.
+ *      Sum.  n[c] is the number of rows with code c, A[c][e] the int64 sum over those rows of fix(x[r][e]), fix(v) = clamp(v,
+ *        -256, 256) * 2^24 as an integer (exact: every fp16 value is a multiple of 2^-24), fix(NaN) = 0.  Integer addition has
+ *        one result in any order, so the sum is made with 64-bit vector atomics and stays deterministic.  R <= 2^30 keeps it
+ *        inside int64; more rows return RR_ERR_UNSUPPORTED.
+ *      Update, for n[c] > 0.  T[c][e] = fp16_rne(float32(double(A[c][e]) / double(n[c] * 2^24))): the int64 -> double
+ *        conversion, the double division and double -> float32 each round to nearest even.
+ *      Empty cluster, n[c] == 0.  T[c] = x[rho]: z = seed ^ ((uint64(i) << 32) | c); z += 0x9E3779B97F4A7C15;
+ *        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^= z >> 31; rho = z mod R.  Each
+ *        cluster computes this on the device by itself: no scan and no host round trip.
+ *      Bias again.  h is recomputed from the new T.
+ *      Statistics.  stats[i][0] = the number of rows whose code differs from the previous iteration's (in iteration 0: R);
+ *        stats[i][1] = the number of clusters re-seeded.
+ *   5. Output.  centroids_out[c][e] = fp16_rne(float32(T[c][e]) / fmaxf(norm, 1e-12f)), the norm as in THE DECODED ROW.
+ *      counts = n of the last assignment, all zero when niters == 0.
+ * D must be a power of two in [16, 512]: the matrix-core step needs a multiple of 16, and the pairwise tree of the norm is
+ * defined for a power of two (what rr_bank_create_plaid takes anyway).
+ * rr_util_plaid_kmeans (rerank_mi355_diag.h) is this definition in host code; the device equals it bit for bit, from run to run
+ * and however the centroid range is split.
+ *
+ * rr_plaid_kmeans: D is h's li_dim.  rows [n_rows, D] (dtype RR_F32 or RR_F16, 16-byte aligned) and all outputs are DEVICE
+ * pointers: centroids_f16_out [n_centroids, D] fp16 bits (16-byte aligned), counts_out int32 [n_centroids] or NULL, stats_out int32
+ * [niters, 2] or NULL.  init_rows_host: HOST int32 [n_centroids].  Every refusal comes from the host before anything is enqueued,
+ * with a message in rr_last_error: RR_ERR_BAD_DTYPE for another dtype, RR_ERR_UNSUPPORTED for the li_dim and for n_rows > 2^30,
+ * RR_ERR_BAD_ARG for a null or misaligned pointer, for rows on another device than the handle's and under stream capture,
+ * RR_ERR_BAD_SHAPE for n_centroids < 1 or > n_rows, niters < 0 and an initial index out of range or named twice.  The call
+ * synchronises hip_stream once at the start (init_rows staged; the handle's grow-only training block grown) and not again: the
+ * iterations are enqueued back to back.  Two training calls of one handle in flight on different streams would share that block:
+ * order them.
+ * rr_plaid_residuals: THE COMPRESSED ROW steps 1 - 4 without the buckets, of n_rows DEVICE rows against a finished table
+ * centroids_f16 [n_centroids, D] (DEVICE, 16-byte aligned; no bias): codes_out int32 [n_rows] and residuals_out float32 [n_rows, D]
+ * (r_e of step 4; 16-byte aligned), both DEVICE.  Refusals as above; it does not synchronise unless the block has to grow.
+ * Python: rmr_amd.PlaidCodec.train / PlaidCodec.save, rmr_amd.plaid_num_partitions. */
+int rr_plaid_kmeans(rr_handle h, const void* rows, int dtype, int64_t n_rows, const int32_t* init_rows_host, int32_t n_centroids,
+                    int niters, uint64_t seed, uint16_t* centroids_f16_out, int32_t* counts_out, int32_t* stats_out, void* hip_stream);
+int rr_plaid_residuals(rr_handle h, const void* rows, int dtype, int64_t n_rows, const uint16_t* centroids_f16, int32_t n_centroids,
+                       int32_t* codes_out, float* residuals_out, void* hip_stream);
 /* rr_forward_interaction_bank: rr_forward_interaction_packed (fusion_from_li != 0: rr_forward_interaction_packed_fusion_li) with
  * the context side taken from a bank.  NORMAL and MORES handles.
  *   query_li [n_queries, Lq, li_dim], query_mask [n_queries, Lq] : DEVICE float32, per QUERY (query_li 16-byte aligned)

@@ -286,6 +286,23 @@ int rr_op_plaid_compress_rows(const void* rows, int dtype, int64_t n_rows, int D
                               const float* cutoffs, int nbits, int32_t* codes_out, uint8_t* residuals_out, void* hip_stream);
 int rr_bank_read_plaid(rr_bank_handle b, int32_t index, int32_t* codes_out, uint8_t* residuals_out, uint8_t* mask_out,
                        int32_t capacity_rows, void* hip_stream);
+/* PLAID codec training (THE TRAINED CENTROIDS: rerank_mi355.h, rr_plaid_kmeans).
+ * rr_util_plaid_kmeans: pure HOST code, usable without a GPU: the definition, every step in the stated order.  rows [n_rows, D]
+ * float32 (RR_F32) or fp16 bits (RR_F16), init_rows int32 [n_centroids] -> centroids_f16_out [n_centroids, D] fp16 bits, counts_out
+ * int32 [n_centroids] or NULL, stats_out int32 [niters, 2] or NULL.  The codes of rr_plaid_kmeans: RR_ERR_BAD_DTYPE,
+ * RR_ERR_UNSUPPORTED (D not a power of two in [16, 512]; n_rows > 2^30), RR_ERR_BAD_SHAPE (n_centroids outside [1, n_rows],
+ * niters < 0, an initial index out of range or named twice).
+ * rr_op_plaid_kmeans / rr_op_plaid_residuals: rr_plaid_kmeans / rr_plaid_residuals over raw DEVICE pointers without a handle, D given
+ * (D = 16 and 32, which no handle takes, are reachable here only): the same kernels, checks and codes, no message.  They allocate
+ * their scratch for the call and synchronise hip_stream before they return.
+ * rr_set_tuning("kmeans_stop_after") (2; 0, 1 or 2): 0 ends every iteration of rr_plaid_kmeans behind the assignment kernel, 1
+ * behind the accumulation (timing by difference; the outputs are then meaningless). */
+int rr_util_plaid_kmeans(const void* rows, int dtype, int64_t n_rows, int D, const int32_t* init_rows, int32_t n_centroids, int niters,
+                         uint64_t seed, uint16_t* centroids_f16_out, int32_t* counts_out, int32_t* stats_out);
+int rr_op_plaid_kmeans(const void* rows, int dtype, int64_t n_rows, int D, const int32_t* init_rows_host, int32_t n_centroids, int niters,
+                       uint64_t seed, uint16_t* centroids_f16_out, int32_t* counts_out, int32_t* stats_out, void* hip_stream);
+int rr_op_plaid_residuals(const void* rows, int dtype, int64_t n_rows, int D, const uint16_t* centroids_f16, int32_t n_centroids,
+                          int32_t* codes_out, float* residuals_out, void* hip_stream);
 /* The score kernels of rr_li_scores and rr_bank_li_scores (rerank_mi355.h) over raw DEVICE pointers, at any D that is a multiple of
  * 16: a handle's li_dim is a multiple of 64, so D = 16 (one step of the kernel's walk over D) and D = 32 are reachable here only.
  * rr_op_li_scores: n pairs, query (pair index) / K; query_li [.., Lq, D], context_li [n, Lc, D], context_mask [n, Lc] float32;

@@ -119,21 +119,6 @@ __global__ __launch_bounds__(256) void bank_gather_kernel(const rr_bank_pair* __
   }
 }
 
-// float32 -> fp16 bits, round to nearest even, in host code (the device's conversion instruction rounds the same way)
-inline uint16_t plaid_f16_bits(float f) {
-  const uint32_t u = __builtin_bit_cast(uint32_t, f), sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
-  if (a >= 0x7f800000u) return (uint16_t)(sign | (a > 0x7f800000u ? 0x7e00u : 0x7c00u));
-  if (a >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                     // rounds to 65536 or beyond: inf
-  if (a < 0x33000001u) return (uint16_t)sign;                                  // at most 2^-25: zero (the tie goes to even)
-  const int e = (int)(a >> 23) - 127;
-  uint32_t m = (a & 0x7fffffu) | 0x800000u;
-  const int shift = e >= -14 ? 13 : 13 + (-14 - e);                            // subnormal halves lose more bits
-  const uint32_t keep = m >> shift, rest = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
-  uint32_t h = e >= -14 ? (((uint32_t)(e + 15) << 10) + (keep - 0x400u)) : keep;
-  if (rest > half || (rest == half && (h & 1u))) ++h;                           // a carry into the exponent is the right value
-  return (uint16_t)(sign | h);
-}
-
 // bank_gather_kernel with the context rows decoded from a compressed bank; outputs as there
 template <int DT, int NBITS>
 __global__ __launch_bounds__(256) void bank_gather_plaid_kernel(const rr_bank_pair* __restrict__ pairs, int n, int Lq, int S, int D,
@@ -317,18 +302,6 @@ bool rr_plaid_decode_rows_host(const uint16_t* centroids, int C, const float* we
   });
   return true;
 }
-
-namespace {
-
-// fp16 bits -> float, exact (host)
-inline float plaid_f16_value(uint16_t hb) {
-  const uint32_t sign = (uint32_t)(hb & 0x8000u) << 16, e = (hb >> 10) & 31u, m = hb & 0x3ffu;
-  if (e == 0) return (sign ? -1.f : 1.f) * ((float)m * 5.9604644775390625e-8f);
-  if (e == 31) return __builtin_bit_cast(float, sign | 0x7f800000u | (m << 13));
-  return __builtin_bit_cast(float, sign | ((e + 112u) << 23) | (m << 13));
-}
-
-}  // namespace
 
 // rr_util_plaid_compress_rows: THE COMPRESSED ROW (include/rerank_mi355.h, rr_bank_add_compress) in host code, the score chain as
 // explicit fmaf in the order of the matrix core (t outer in steps of 16, e, then g; d = 16 t + 4 g + e); false for a shape

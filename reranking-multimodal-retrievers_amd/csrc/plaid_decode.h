@@ -2,7 +2,8 @@
 // kernel that reads its context rows from a bank (li_scores.hip).  THE DECODED ROW is defined in passage_bank.hip's header
 // comment; plaid_bucket / plaid_sumsq8 / plaid_scale are compiled for both sides, plaid_load8 / plaid_finish8 are the one
 // device definition every kernel decodes with.  plaid_with_nbits is the one place a runtime nbits becomes a template argument,
-// plaid_tables_ok what every launcher checks of a compressed rr_bank_view.
+// plaid_tables_ok what every launcher checks of a compressed rr_bank_view, plaid_f16_bits / plaid_f16_value the fp16 conversions of
+// the host definitions (passage_bank.hip, plaid_train.hip).
 #pragma once
 #include <type_traits>
 
@@ -27,6 +28,29 @@ inline auto plaid_with_nbits(int nbits, F&& f) {
 inline bool plaid_tables_ok(const rr_bank_view& v, int D) {
   return rr_plaid_shape_ok(v.nbits, D) && v.n_centroids > 0 && v.codes && v.resid && v.centroids && v.weights &&
          !(((uintptr_t)v.centroids) & 15) && !(((uintptr_t)v.resid) & 7) && !(((uintptr_t)v.codes) & 3);
+}
+
+// float32 -> fp16 bits, round to nearest even, in host code (the device's conversion instruction rounds the same way)
+inline uint16_t plaid_f16_bits(float f) {
+  const uint32_t u = __builtin_bit_cast(uint32_t, f), sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
+  if (a >= 0x7f800000u) return (uint16_t)(sign | (a > 0x7f800000u ? 0x7e00u : 0x7c00u));
+  if (a >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                     // rounds to 65536 or beyond: inf
+  if (a < 0x33000001u) return (uint16_t)sign;                                  // at most 2^-25: zero (the tie goes to even)
+  const int e = (int)(a >> 23) - 127;
+  uint32_t m = (a & 0x7fffffu) | 0x800000u;
+  const int shift = e >= -14 ? 13 : 13 + (-14 - e);                            // subnormal halves lose more bits
+  const uint32_t keep = m >> shift, rest = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
+  uint32_t h = e >= -14 ? (((uint32_t)(e + 15) << 10) + (keep - 0x400u)) : keep;
+  if (rest > half || (rest == half && (h & 1u))) ++h;                           // a carry into the exponent is the right value
+  return (uint16_t)(sign | h);
+}
+
+// fp16 bits -> float, exact (host)
+inline float plaid_f16_value(uint16_t hb) {
+  const uint32_t sign = (uint32_t)(hb & 0x8000u) << 16, e = (hb >> 10) & 31u, m = hb & 0x3ffu;
+  if (e == 0) return (sign ? -1.f : 1.f) * ((float)m * 5.9604644775390625e-8f);
+  if (e == 31) return __builtin_bit_cast(float, sign | 0x7f800000u | (m << 13));
+  return __builtin_bit_cast(float, sign | ((e + 112u) << 23) | (m << 13));
 }
 
 // 8 consecutive elements of a source row as floats; SRC_F16: the row holds fp16 bits

@@ -229,6 +229,9 @@ struct rr_model {
   // rr_bank_search (grow-only): the score of every (query, passage) of the call, then the two survivor buffers of the selection
   char* search_blk = nullptr;
   size_t search_blk_cap = 0;
+  // rr_plaid_kmeans / rr_plaid_residuals (grow-only): the table, the sums and the assignment's keys of a call (rr_kmeans_plan)
+  char* train_blk = nullptr;
+  size_t train_blk_cap = 0;
   // rr_bank_search_plaid shares that block; what its LAST call left there (rr_bank_search_plaid_tap), until the next search
   rr_plaid_search_args plaid_last{};
   rr_plaid_search_layout plaid_last_layout{};
@@ -1523,6 +1526,7 @@ static int rr_destroy_impl(rr_handle h) {
   if (h->li_sc) (void)hipFree(h->li_sc);
   if (h->bank_blk) (void)hipFree(h->bank_blk);
   if (h->search_blk) (void)hipFree(h->search_blk);
+  if (h->train_blk) (void)hipFree(h->train_blk);
   for (auto& e : h->ev_pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   for (auto& a : h->asm_slot) {
     if (a.host) (void)hipHostFree(a.host);
@@ -2305,6 +2309,107 @@ static int rr_op_plaid_compress_rows_impl(const void* rows, int dtype, int64_t n
   const hipError_t e2 = hipStreamSynchronize(st);
   (void)hipFree(scratch);
   return e == hipSuccess && e2 == hipSuccess ? RR_OK : RR_ERR_HIP;
+}
+
+// What rr_plaid_kmeans and rr_plaid_residuals check of their rows alike, in the order the bank entries refuse
+static int plaid_train_rows_ok(rr_model* m, const char* what, int D, const void* rows, int dtype, int64_t n_rows, int32_t n_centroids) {
+  if (dtype != RR_F32 && dtype != RR_F16) return fail(m, RR_ERR_BAD_DTYPE, "%s: dtype %d (RR_F32 or RR_F16)", what, dtype);
+  if (!rr_plaid_train_shape_ok(D))
+    return fail(m, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a power of two in [16, 512]: the matrix-core step and the tree of the norm)", what, D);
+  if (((uintptr_t)rows) & 15) return fail(m, RR_ERR_BAD_ARG, "%s: rows must be 16-byte aligned", what);
+  if (n_rows > (1LL << 30))
+    return fail(m, RR_ERR_UNSUPPORTED, "%s: %lld rows (at most 2^30: the fixed-point sums stay inside 64 bits)", what, (long long)n_rows);
+  if (n_rows < 1) return fail(m, RR_ERR_BAD_SHAPE, "%s: n_rows=%lld", what, (long long)n_rows);
+  if (n_centroids < 1 || n_centroids > n_rows)
+    return fail(m, RR_ERR_BAD_SHAPE, "%s: %d centroids of %lld rows (1 .. n_rows)", what, n_centroids, (long long)n_rows);
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, rows) != hipSuccess) {
+    (void)hipGetLastError();                       // not a pointer the runtime knows: the caller answers for it
+  } else if (m && at.type == hipMemoryTypeDevice && at.device != m->cfg.device) {
+    return fail(m, RR_ERR_BAD_ARG, "%s: rows live on device %d, the handle on %d", what, at.device, m->cfg.device);
+  }
+  return RR_OK;
+}
+
+// the scratch of a training call: the handle's grow-only block, or without a handle (the diagnostic operators) a block of its own,
+// released behind a synchronisation by plaid_train_done
+static int plaid_train_scratch(rr_model* m, size_t bytes, hipStream_t st, char** out) {
+  if (m) {
+    RR_HIP(m, hipSetDevice(m->cfg.device));
+    RR_TRY(ensure_block(m, m->train_blk, m->train_blk_cap, bytes, st, "the codec training's block"));
+    *out = m->train_blk;
+    return RR_OK;
+  }
+  RR_HIP(m, hipMalloc((void**)out, bytes));
+  return RR_OK;
+}
+static int plaid_train_done(rr_model* m, char* scratch, hipStream_t st, int rc) {
+  if (m) return rc;
+  const hipError_t e = hipStreamSynchronize(st);
+  (void)hipFree(scratch);
+  return rc != RR_OK ? rc : e == hipSuccess ? RR_OK : RR_ERR_HIP;
+}
+
+// rr_plaid_kmeans (include/rerank_mi355.h, THE TRAINED CENTROIDS): every refusal on the host, one synchronisation behind the staging
+// of init_rows, then the kernels of plaid_train.hip back to back
+static int rr_plaid_kmeans_impl(rr_model* m, const char* what, int D, const void* rows, int dtype, int64_t n_rows, const int32_t* init_rows_host, int32_t n_centroids,
+                                int niters, uint64_t seed, uint16_t* centroids_f16_out, int32_t* counts_out, int32_t* stats_out,
+                                void* hip_stream) {
+  if (!rows || !init_rows_host || !centroids_f16_out) return fail(m, RR_ERR_BAD_ARG, "%s: null argument", what);
+  RR_TRY(plaid_train_rows_ok(m, what, D, rows, dtype, n_rows, n_centroids));
+  if ((((uintptr_t)centroids_f16_out) & 15) || ((((uintptr_t)counts_out) | ((uintptr_t)stats_out)) & 3))
+    return fail(m, RR_ERR_BAD_ARG, "%s: centroids_f16_out must be 16-byte aligned, counts_out and stats_out 4-byte", what);
+  if (niters < 0) return fail(m, RR_ERR_BAD_SHAPE, "%s: niters=%d", what, niters);
+  {
+    std::vector<int32_t> sorted(init_rows_host, init_rows_host + n_centroids);
+    std::sort(sorted.begin(), sorted.end());
+    if (sorted.front() < 0 || sorted.back() >= n_rows)
+      return fail(m, RR_ERR_BAD_SHAPE, "%s: an initial row index outside [0, %lld)", what, (long long)n_rows);
+    for (size_t i = 1; i < sorted.size(); ++i)
+      if (sorted[i] == sorted[i - 1]) return fail(m, RR_ERR_BAD_SHAPE, "%s: initial row %d is named twice", what, sorted[i]);
+  }
+  const rr_kmeans_plan pl = rr_plaid_kmeans_plan(n_rows, n_centroids, D, niters);
+  if (pl.assign.jt == 0)
+    return fail(m, RR_ERR_BAD_SHAPE, "%s: %lld rows against %d centroids at the compress_chunk in force do not fit a launch", what,
+                (long long)n_rows, n_centroids);
+  hipStream_t st = (hipStream_t)hip_stream;
+  RR_TRY(capture_guard(m, st, CAP_STAGES, what));
+  char* scratch = nullptr;
+  RR_TRY(plaid_train_scratch(m, pl.total, st, &scratch));
+  auto run = [&]() -> int {
+    RR_HIP(m, hipMemcpyAsync(scratch + pl.init_off, init_rows_host, (size_t)n_centroids * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    RR_HIP(m, hipStreamSynchronize(st));           // the caller's init_rows are its own again; nothing below synchronises
+    RR_HIP(m, rr_launch_plaid_kmeans(rows, dtype == RR_F16, n_rows, D, n_centroids, niters, (unsigned long long)seed, scratch, pl,
+                                     centroids_f16_out, counts_out, stats_out, st));
+    return RR_OK;
+  };
+  return plaid_train_done(m, scratch, st, run());
+}
+
+// rr_plaid_residuals: codes and float32 residuals of device rows against a finished table
+static int rr_plaid_residuals_impl(rr_model* m, const char* what, int D, const void* rows, int dtype, int64_t n_rows, const uint16_t* centroids_f16, int32_t n_centroids,
+                                   int32_t* codes_out, float* residuals_out, void* hip_stream) {
+  if (!rows || !centroids_f16 || !codes_out || !residuals_out) return fail(m, RR_ERR_BAD_ARG, "%s: null argument", what);
+  if (dtype != RR_F32 && dtype != RR_F16) return fail(m, RR_ERR_BAD_DTYPE, "%s: dtype %d (RR_F32 or RR_F16)", what, dtype);
+  if (!rr_plaid_train_shape_ok(D))
+    return fail(m, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a power of two in [16, 512]: the matrix-core step and the tree of the norm)", what, D);
+  if (((((uintptr_t)rows) | ((uintptr_t)centroids_f16) | ((uintptr_t)residuals_out)) & 15) || (((uintptr_t)codes_out) & 3))
+    return fail(m, RR_ERR_BAD_ARG, "%s: rows, centroids_f16 and residuals_out must be 16-byte aligned, codes_out 4-byte", what);
+  if (n_rows < 1 || n_rows > (1LL << 31) || n_centroids < 1)
+    return fail(m, RR_ERR_BAD_SHAPE, "%s: n_rows=%lld n_centroids=%d", what, (long long)n_rows, n_centroids);
+  const rr_compress_plan pl = rr_plaid_compress_plan(n_rows, n_centroids, D);
+  if (pl.jt == 0)
+    return fail(m, RR_ERR_BAD_SHAPE, "%s: %lld rows against %d centroids at the compress_chunk in force do not fit a launch", what,
+                (long long)n_rows, n_centroids);
+  hipStream_t st = (hipStream_t)hip_stream;
+  RR_TRY(capture_guard(m, st, "%s cannot be captured into a graph (it may grow the handle's training block)", what));
+  char* scratch = nullptr;
+  RR_TRY(plaid_train_scratch(m, pl.total, st, &scratch));
+  auto run = [&]() -> int {
+    RR_HIP(m, rr_launch_plaid_residuals(rows, dtype == RR_F16, n_rows, D, centroids_f16, n_centroids, scratch, pl, codes_out, residuals_out, st));
+    return RR_OK;
+  };
+  return plaid_train_done(m, scratch, st, run());
 }
 
 static int rr_op_plaid_decode_rows_impl(const uint16_t* centroids_f16, int32_t n_centroids, const float* bucket_weights, int nbits, int D,
@@ -3271,6 +3376,7 @@ int rr_set_tuning(const char* key, int value) {
   if (!strcmp(key, "search_chunk")) return rr_set_search_chunk(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
   if (!strcmp(key, "compress_chunk")) return rr_set_compress_chunk(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
   if (!strcmp(key, "compress_stop_after")) return rr_set_compress_stop_after(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
+  if (!strcmp(key, "kmeans_stop_after")) return rr_set_kmeans_stop_after(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
   if (!strcmp(key, "plaid_stop_after")) {
     if (value < 0 || value >= RR_PLAID_SEARCH_STAGES) return RR_ERR_BAD_ARG;
     g_plaid_stop_after = value;
@@ -3763,6 +3869,32 @@ int rr_util_plaid_compress_rows(const void* rows, int dtype, int64_t n_rows, int
   if (n_centroids <= 0 || n_centroids > (1 << 24) || n_rows < 0) return RR_ERR_BAD_SHAPE;
   return guarded(nullptr, [&]() -> int {
     return rr_plaid_compress_rows_host(rows, dtype == RR_F16, n_rows, D, centroids_f16, n_centroids, cutoffs, nbits, codes_out, residuals_out) ? RR_OK : RR_ERR_BAD_SHAPE;
+  });
+}
+int rr_plaid_kmeans(rr_handle h, const void* rows, int dtype, int64_t n_rows, const int32_t* init_rows_host, int32_t n_centroids, int niters, uint64_t seed, uint16_t* centroids_f16_out, int32_t* counts_out, int32_t* stats_out, void* hip_stream) {
+  return guarded(h, [&]() -> int { return h ? rr_plaid_kmeans_impl(h, "rr_plaid_kmeans", h->cfg.li_dim, rows, dtype, n_rows, init_rows_host, n_centroids, niters, seed, centroids_f16_out, counts_out, stats_out, hip_stream) : RR_ERR_BAD_ARG; });
+}
+int rr_op_plaid_kmeans(const void* rows, int dtype, int64_t n_rows, int D, const int32_t* init_rows_host, int32_t n_centroids, int niters, uint64_t seed, uint16_t* centroids_f16_out, int32_t* counts_out, int32_t* stats_out, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_plaid_kmeans_impl(nullptr, "rr_op_plaid_kmeans", D, rows, dtype, n_rows, init_rows_host, n_centroids, niters, seed, centroids_f16_out, counts_out, stats_out, hip_stream); });
+}
+int rr_op_plaid_residuals(const void* rows, int dtype, int64_t n_rows, int D, const uint16_t* centroids_f16, int32_t n_centroids, int32_t* codes_out, float* residuals_out, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_plaid_residuals_impl(nullptr, "rr_op_plaid_residuals", D, rows, dtype, n_rows, centroids_f16, n_centroids, codes_out, residuals_out, hip_stream); });
+}
+int rr_plaid_residuals(rr_handle h, const void* rows, int dtype, int64_t n_rows, const uint16_t* centroids_f16, int32_t n_centroids, int32_t* codes_out, float* residuals_out, void* hip_stream) {
+  return guarded(h, [&]() -> int { return h ? rr_plaid_residuals_impl(h, "rr_plaid_residuals", h->cfg.li_dim, rows, dtype, n_rows, centroids_f16, n_centroids, codes_out, residuals_out, hip_stream) : RR_ERR_BAD_ARG; });
+}
+int rr_util_plaid_kmeans(const void* rows, int dtype, int64_t n_rows, int D, const int32_t* init_rows, int32_t n_centroids, int niters, uint64_t seed, uint16_t* centroids_f16_out, int32_t* counts_out, int32_t* stats_out) {
+  return guarded(nullptr, [&]() -> int {
+    if (!rows || !init_rows || !centroids_f16_out) return RR_ERR_BAD_ARG;
+    if (dtype != RR_F32 && dtype != RR_F16) return RR_ERR_BAD_DTYPE;
+    if (!rr_plaid_train_shape_ok(D) || n_rows > (1LL << 30)) return RR_ERR_UNSUPPORTED;
+    if (n_rows < 1 || n_centroids < 1 || n_centroids > n_rows || niters < 0) return RR_ERR_BAD_SHAPE;
+    std::vector<int32_t> sorted(init_rows, init_rows + n_centroids);
+    std::sort(sorted.begin(), sorted.end());
+    if (sorted.front() < 0 || sorted.back() >= n_rows) return RR_ERR_BAD_SHAPE;
+    for (size_t i = 1; i < sorted.size(); ++i)
+      if (sorted[i] == sorted[i - 1]) return RR_ERR_BAD_SHAPE;
+    return rr_plaid_kmeans_host(rows, dtype == RR_F16, n_rows, D, init_rows, n_centroids, niters, (unsigned long long)seed, centroids_f16_out, counts_out, stats_out) ? RR_OK : RR_ERR_BAD_SHAPE;
   });
 }
 int rr_op_plaid_compress_rows(const void* rows, int dtype, int64_t n_rows, int D, const uint16_t* centroids_f16, int32_t n_centroids, const float* cutoffs, int nbits, int32_t* codes_out, uint8_t* residuals_out, void* hip_stream) {

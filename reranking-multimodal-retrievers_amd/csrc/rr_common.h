@@ -535,3 +535,20 @@ bool rr_plaid_compress_rows_host(const void* rows, int rows_f16, long long n_row
                                  const float* cutoffs, int nbits, int32_t* codes_out, uint8_t* resid_out);
 bool rr_plaid_decode_rows_host(const uint16_t* centroids, int C, const float* weights, int nbits, int D, const int32_t* codes,
                                const uint8_t* resid, long long n_rows, uint16_t* out);
+// rr_plaid_kmeans / rr_plaid_residuals (plaid_train.hip): codec training.  Where the intermediates of a k-means call lie in its
+// `scratch` (16-byte aligned, `total` bytes): init_rows [C] int32 (staged by the caller), T [C][D] fp16 table, h [C up to 16] float32
+// bias, A [C][D] int64 sums, n [C] counts, codes [R] int32 of the previous iteration, stats (when the caller wants none), the
+// assignment's keys [splits][R].  assign: the launch shape of the assignment (rr_plaid_compress_plan); assign.jt == 0: a shape the
+// kernels do not take.
+struct rr_kmeans_plan { rr_compress_plan assign; size_t init_off, T_off, h_off, A_off, n_off, codes_off, stats_off, keys_off, total; };
+bool rr_plaid_train_shape_ok(int D);           // D a power of two in [16, 512]
+int rr_set_kmeans_stop_after(int stage);       // rr_set_tuning("kmeans_stop_after"): 2 (all), 1 (assignment + accumulation), 0 (assignment), -1 outside
+rr_kmeans_plan rr_plaid_kmeans_plan(long long R, int C, int D, int niters);
+hipError_t rr_launch_plaid_kmeans(const void* rows, int rows_f16, long long R, int D, int C, int niters, unsigned long long seed,
+                                  char* scratch, const rr_kmeans_plan& pl, uint16_t* centroids_out, int32_t* counts_out,
+                                  int32_t* stats_out, hipStream_t st);
+hipError_t rr_launch_plaid_residuals(const void* rows, int rows_f16, long long R, int D, const uint16_t* centroids, int C, char* scratch,
+                                     const rr_compress_plan& pl, int32_t* codes_out, float* resid_out, hipStream_t st);
+// rr_util_plaid_kmeans: the definition in host code
+bool rr_plaid_kmeans_host(const void* rows, int rows_f16, long long R, int D, const int32_t* init_rows, int C, int niters,
+                          unsigned long long seed, uint16_t* centroids_out, int32_t* counts_out, int32_t* stats_out);

@@ -22,6 +22,10 @@ centroid-only pruning passes, exact MaxSim on the survivors.
 `PassageBank.add_compress` fills a compressed bank from embeddings that are on the device (rr_bank_add_compress): nearest centroid
 on the matrix core and residual bucketising in two kernels, the codec's cutoffs given as `PlaidCodec(bucket_cutoffs=...)`.
 
+`PlaidCodec.train` makes the codec itself from embeddings on the device (rr_plaid_kmeans, rr_plaid_residuals): k-means centroids by
+Lloyd's iteration with an exact fixed-point sum, bucket cutoffs and weights from held-out residuals; `PlaidCodec.save` writes it as an
+index stores it.  With it a compressed bank is built from a retriever's embeddings with nothing but this library.
+
 `BankTable`, `plan_bank_batch`, `plan_bank_scores`, `PlaidCodec` and `read_plaid_index` are the host side: pure Python / numpy / torch on the CPU,
 usable and tested without a device.
 """
@@ -207,6 +211,8 @@ class PlaidCodec:
         self.centroids = centroids.detach().to(device="cpu", dtype=torch.float16).contiguous()
         self.bucket_weights = bucket_weights.detach().to(device="cpu", dtype=torch.float32).contiguous()
         self.bucket_cutoffs = None
+        self.avg_residual = None             # PlaidCodec.train: the mean absolute held-out residual, and how the training went
+        self.train_stats = None
         if bucket_cutoffs is not None:
             cut = torch.as_tensor(bucket_cutoffs)
             if not cut.is_floating_point() or tuple(cut.shape) != ((1 << nbits) - 1,):
@@ -266,6 +272,111 @@ class PlaidCodec:
                                                 self.centroids.data_ptr(), self.n_centroids, self.bucket_cutoffs.data_ptr(), self.nbits,
                                                 codes.data_ptr(), res.data_ptr()), None, "rr_util_plaid_compress_rows")
         return codes, res
+
+    QUANTILE_MAX_ELEMENTS = 1 << 24          # what torch.quantile takes
+
+    @staticmethod
+    def bucket_statistics(residuals, nbits: int):
+        """(bucket_cutoffs [2^nbits - 1], bucket_weights [2^nbits], avg_residual scalar) of held-out `residuals` [H, D] float32, on
+        the device the tensor lives on: the mean absolute residual and the two `quantile` calls of the reference's
+        _compute_avg_residual (third_party/ColBERT/colbert/indexing/collection_indexer.py:305-319), operation for operation.
+        ValueError for an empty block and for more elements than torch.quantile takes."""
+        import torch
+        if residuals.dim() != 2 or residuals.numel() == 0:
+            raise ValueError(f"the held-out block is empty: {tuple(residuals.shape)}")
+        if residuals.numel() > PlaidCodec.QUANTILE_MAX_ELEMENTS:
+            raise ValueError(f"the held-out block holds {residuals.numel()} elements, torch.quantile takes at most "
+                             f"{PlaidCodec.QUANTILE_MAX_ELEMENTS}: lower heldout_max")
+        avg_residual = torch.abs(residuals).mean(dim=0).cpu()
+        num_options = 2 ** nbits
+        quantiles = torch.arange(0, num_options, device=residuals.device) * (1 / num_options)
+        cutoffs_q, weights_q = quantiles[1:], quantiles + (0.5 / num_options)
+        cutoffs = residuals.float().quantile(cutoffs_q)
+        weights = residuals.float().quantile(weights_q)
+        return cutoffs.cpu(), weights.cpu(), avg_residual.mean()
+
+    @classmethod
+    def train(cls, engine, embeddings, nbits: int, n_centroids: Optional[int] = None, *, niters: int = 20, seed: int = 123,
+              max_points_per_centroid: int = 256, heldout_fraction: float = 0.05, heldout_max: int = 50_000) -> "PlaidCodec":
+        """Train a codec from `embeddings` [N, D] (a device tensor, float32 or float16; D the engine's li_dim) with nothing but this
+        library: what the reference's indexer does with faiss k-means and _compute_avg_residual (collection_indexer.py:211-319,
+        452-465).  The rows are shuffled with a CPU torch.randperm seeded with `seed`; the last int(min(heldout_fraction * N,
+        heldout_max)) of them are held out, as the reference splits them; at most max_points_per_centroid * C of the rest train
+        (faiss's default); the first C training rows are the initial centroids of rr_plaid_kmeans (THE TRAINED CENTROIDS,
+        include/rerank_mi355.h; `niters` Lloyd iterations, empty clusters re-seeded from `seed`).  The held-out rows' residuals
+        (rr_plaid_residuals) give avg_residual and the bucket cutoffs and weights by `bucket_statistics`, on the device.
+        n_centroids None: plaid_num_partitions(N).
+        The residuals are taken against the fp16 table, the one the index stores and add_compress uses; the reference's CPU branch
+        subtracts the unrounded float32 table (its GPU branch the .half() one, as here).
+        Returns a PlaidCodec with cutoffs; `.avg_residual` (float) and `.train_stats` (dict: n_train, n_heldout, counts int32 [C],
+        stats int32 [niters, 2] = (rows that changed code, clusters re-seeded) per iteration).  ValueError when the held-out block
+        is empty or holds more elements than torch.quantile takes."""
+        import torch
+        from . import _lib as L
+        if embeddings.dim() != 2 or not embeddings.is_cuda:
+            raise ValueError(f"embeddings must be a device tensor [N, D], got {embeddings.device} {tuple(embeddings.shape)}")
+        N, D = int(embeddings.shape[0]), int(embeddings.shape[1])
+        if D != int(engine.arch["li_dim"]):
+            raise ValueError(f"embeddings hold rows of {D}, the engine's li_dim is {int(engine.arch['li_dim'])}")
+        if not isinstance(nbits, int) or isinstance(nbits, bool) or nbits not in PLAID_NBITS:
+            raise ValueError(f"nbits {nbits!r}: 1, 2, 4 or 8")
+        Cn = plaid_num_partitions(N) if n_centroids is None else int(n_centroids)
+        n_held = int(min(heldout_fraction * N, heldout_max))
+        if n_held < 1:
+            raise ValueError(f"the held-out block is empty: {N} rows at heldout_fraction {heldout_fraction}, heldout_max {heldout_max}")
+        if n_held * D > cls.QUANTILE_MAX_ELEMENTS:
+            raise ValueError(f"the held-out block holds {n_held * D} elements, torch.quantile takes at most {cls.QUANTILE_MAX_ELEMENTS}: "
+                             "lower heldout_max")
+        n_train = min(N - n_held, int(max_points_per_centroid) * Cn)
+        if Cn < 1 or Cn > n_train:
+            raise ValueError(f"{Cn} centroids of {n_train} training rows")
+        dt = embeddings.dtype if embeddings.dtype in (torch.float32, torch.float16) else torch.float32
+        perm = torch.randperm(N, generator=torch.Generator().manual_seed(int(seed))).to(embeddings.device)
+        shuffled = embeddings.to(dt)[perm]
+        train = shuffled[:n_train].contiguous()
+        held = shuffled[N - n_held:].contiguous()
+        del shuffled
+        lib, dev = engine.lib, embeddings.device
+        rdt = L.RR_F16 if dt == torch.float16 else L.RR_F32
+        st = torch.cuda.current_stream(dev).cuda_stream
+        init = torch.arange(Cn, dtype=torch.int32)
+        cen = torch.empty((Cn, D), dtype=torch.float16, device=dev)
+        counts = torch.empty(Cn, dtype=torch.int32, device=dev)
+        stats = torch.zeros((max(int(niters), 1), 2), dtype=torch.int32, device=dev)
+        L.check(lib.rr_plaid_kmeans(engine.h, L.ptr(train), rdt, n_train, init.data_ptr(), Cn, int(niters), int(seed) & ((1 << 64) - 1),
+                                    L.ptr(cen), L.ptr(counts), L.ptr(stats), st), engine.h, "rr_plaid_kmeans")
+        codes = torch.empty(n_held, dtype=torch.int32, device=dev)
+        resid = torch.empty((n_held, D), dtype=torch.float32, device=dev)
+        L.check(lib.rr_plaid_residuals(engine.h, L.ptr(held), rdt, n_held, L.ptr(cen), Cn, L.ptr(codes), L.ptr(resid), st), engine.h,
+                "rr_plaid_residuals")
+        cutoffs, weights, avg = cls.bucket_statistics(resid, nbits)
+        codec = cls(cen.cpu(), weights, nbits, bucket_cutoffs=cutoffs)
+        codec.avg_residual = float(avg)
+        codec.train_stats = dict(n_train=n_train, n_heldout=n_held, counts=counts.cpu(), stats=stats[:int(niters)].cpu())
+        return codec
+
+    def save(self, path: str) -> None:
+        """Write the codec into the directory `path` as the reference's indexer does (codecs/residual.py:154-167): `centroids.pt`
+        (fp16) and `buckets.pt` = (cutoffs, weights), the files read_plaid_index reads, and `avg_residual.pt` (the scalar a trained
+        codec carries, 0 otherwise), which it does not read.  Needs `bucket_cutoffs`."""
+        import os
+
+        import torch
+        if self.bucket_cutoffs is None:
+            raise ValueError("save needs the codec's bucket_cutoffs: buckets.pt holds (cutoffs, weights)")
+        os.makedirs(path, exist_ok=True)
+        torch.save(self.centroids, os.path.join(path, "centroids.pt"))
+        torch.save((self.bucket_cutoffs, self.bucket_weights), os.path.join(path, "buckets.pt"))
+        torch.save(torch.tensor(float(self.avg_residual or 0.0)), os.path.join(path, "avg_residual.pt"))
+
+
+def plaid_num_partitions(n_embeddings) -> int:
+    """The number of centroids the reference's indexer picks for n_embeddings token embeddings: 2^floor(log2(16 sqrt(n)))
+    (third_party/ColBERT/colbert/indexing/collection_indexer.py:98)."""
+    import numpy as np
+    if not n_embeddings >= 1:
+        raise ValueError(f"n_embeddings = {n_embeddings}")
+    return int(2 ** np.floor(np.log2(16 * np.sqrt(n_embeddings))))
 
 
 def read_plaid_index(index_path: str):

@@ -762,7 +762,8 @@ int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_q
 
 /* rr_bank_search_plaid: PLAID's staged, centroid-pruned top-k search over a range of a COMPRESSED bank (the reference:
  * third_party/ColBERT/colbert/search/index_storage.py:86-184, candidate_generation.py, filter_pids.cpp), from what the bank holds
- * already: a centroid code per row, the fp16 centroid table, the passage table.  No IVF is built or loaded: the candidate set the
+ * already: a centroid code per row, the fp16 centroid table, the passage table.  This entry reads no IVF (rr_bank_search_plaid_ivf
+ * below does, with the same result): the candidate set the
  * reference reads from its IVF (per centroid the passages holding a token with that code: _build_ivf, indexing/
  * collection_indexer.py:393-431, sorts the embedding ids by code and counts them per centroid; optimize_ivf, indexing/utils.py:8-48,
  * maps every embedding id to its passage and keeps the unique passages of each centroid) comes from one scan over the codes of
@@ -800,11 +801,62 @@ int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_q
  * k2 = min(ndocs / 4, n): 4 nq Cp Lq + 16 nq Cp / 64 + Cp + 4 nq Lq_coarse ncells + 8 nq W + 8 nq n + 4 nq (k1 + k2 + 1)
  * + 8 * (n > 4096 ? nq ceil(n / 4096) k1 : 0) bytes.
  * Checked on the host BEFORE anything is enqueued; a refused call writes nothing.  Not capturable into a graph (RR_ERR_BAD_ARG).
- * Out of scope: ndocs > 1024, an IVF, merging across ranks, a caller-supplied filter, fp16 banks.  (Python:
+ * Out of scope: ndocs > 1024, merging across ranks, a caller-supplied filter, fp16 banks; candidates from an IVF:
+ * rr_bank_build_ivf / rr_bank_search_plaid_ivf below.  (Python:
  * RerankEngine.bank_search_plaid, PlaidSearch with PassageBank.search / InteractionRerankModel.retrieve / retrieve_and_rerank.) */
 int rr_bank_search_plaid(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse,
                          int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k,
                          int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream);
+
+/* THE INVERTED FILE of a compressed bank, and the pruned search that takes its candidates from it.
+ * DEFINITION.  The file covers the passages 0 .. P-1 the bank held when it was built.  With C = n_centroids, list[c], c < C, is the
+ * set of passages that have at least one UNMASKED row r with clamp(code_r, 0, C-1) == c (the clamp of rr_bank_search_plaid's
+ * scan), in ascending bank index, every passage once per list.  Stored as offsets int64 [C + 1] (offsets[0] = 0, list[c] =
+ * pids[offsets[c] .. offsets[c + 1])) and pids int32 [offsets[C]].  This is the content of the reference's ivf.pid.pt, (ivf,
+ * ivf_lengths) with ivf_lengths the differences of offsets (_build_ivf, third_party/ColBERT/colbert/indexing/
+ * collection_indexer.py:393-431; optimize_ivf, indexing/utils.py:8-48), with one difference: masked rows do not count (the
+ * reference's indexer has dropped them before it builds).  The same bytes from run to run.  In host code: rr_util_plaid_ivf
+ * (rerank_mi355_diag.h).
+ * rr_bank_build_ivf builds, or rebuilds, the file over EVERY passage now in the bank, on the device (csrc/bank_ivf.hip: first
+ * occurrences of a code per passage counted with 32-bit vector atomics, an exclusive scan, a fill through per-centroid cursors,
+ * then every list sorted: in LDS up to 4096 entries, through a bitmap of P bits above).  A load-time call: it allocates
+ * (8 (C + 1) + 4 postings bytes kept; 16 P + 4 C + P / 8 bytes for the call), reads the postings total and the longest list back
+ * and synchronises hip_stream; not capturable into a graph (RR_ERR_BAD_ARG).  An fp16 bank: RR_ERR_UNSUPPORTED; an empty bank:
+ * RR_ERR_BAD_SHAPE; a failed allocation: RR_ERR_OOM with the bank unchanged: a previous file survives a failed rebuild.
+ * LIFETIME: rr_bank_clear drops the file; passages added after a build leave it valid for its prefix 0 .. P-1 (build again to
+ * cover them; there is no incremental update); rr_bank_destroy frees it.
+ * rr_bank_ivf_info: passages_covered (0: no file), the postings total and the longest list; any pointer may be NULL.
+ * rr_bank_ivf_read copies offsets [C + 1] and pids [postings] to HOST buffers (either may be NULL) and synchronises hip_stream;
+ * RR_ERR_BAD_ARG without a file.  Errors of the three: rr_bank_last_error.  Loading a foreign ivf.pid.pt is out of scope.
+ *
+ * rr_bank_search_plaid_ivf takes exactly the arguments of rr_bank_search_plaid.  CONTRACT: indices_out, scores_out and counts_out
+ * are bit for bit those of rr_bank_search_plaid with the same arguments, the -1 / -inf behind the count included; its checks, its
+ * refusals and the graph-capture refusal are those of rr_bank_search_plaid, in the same order.  One refusal more, behind the
+ * others: RR_ERR_UNSUPPORTED when the bank has no inverted file, or when [first_passage, first_passage + n_passages) reaches
+ * beyond passages_covered; rr_last_error says to call rr_bank_build_ivf.
+ * Stages 0 - 2 (centroid scores, cells, bitmaps) are rr_bank_search_plaid's.  Its scan and its selection over the dense rows are
+ * replaced: CANDIDATES: per query a bitmap over the passages of the range; every distinct cell of the query ORs in the passages of
+ * its list that lie in the range (a set: no order enters), and the bitmap is compacted into an ASCENDING candidate list [nq][cap]
+ * with a count, cap = max(1, min(n_passages, Lq_coarse * ncells * longest_list)).  A place in that list follows bank-index order,
+ * so the tie rule of the order (lower index first) holds for places.  SCORES: A1 and A2 of the listed candidates, a wave per
+ * candidate, by the arithmetic of the scan (one device function under both kernels), into compact rows [nq][cap], -inf behind
+ * the count.  SELECTION: the selection passes of rr_bank_search over the compact A1 row; the later stages address places of the
+ * compact rows and the last one maps a place back to its bank index.  Nothing depends on scheduling.
+ * The bitmap pass writes, sets and reads n_passages / 8 bytes per query, and a candidate costs the scan's 5 bytes per row; the
+ * scan it replaces reads 5 bytes per row of the whole range per call.  Scratch in the grow-only block rr_bank_search uses, each
+ * term rounded up to 16 bytes, Cp, W, k2 as above, k1 = min(ndocs, cap), Wn = ceil(n / 32): 4 nq Cp Lq + 16 nq Cp / 64 + Cp
+ * + 4 nq Lq_coarse ncells + 8 nq W + 4 nq Wn + 12 nq cap + 4 nq (k1 + k2 + 2) + 8 * (cap > 4096 ? nq ceil(cap / 4096) k1 : 0)
+ * bytes: with cap <= n never more than rr_bank_search_plaid's but for the bitmap and the candidate list (8 nq n against
+ * 4 nq (n / 32 + 3 cap)).  Ten launches, a memset and the selection passes, booked in the profile's `tail` class.
+ * LIMITS: those of rr_bank_search_plaid (ndocs <= 1024, one device, compressed banks); rr_bank_search_plaid_tap does not cover
+ * this entry.  (Python: RerankEngine.bank_build_ivf / bank_search_plaid_ivf, PassageBank.build_ivf / ivf / save_ivf,
+ * PlaidSearch(..., ivf=True).) */
+int rr_bank_build_ivf(rr_bank_handle b, void* hip_stream);
+int rr_bank_ivf_info(rr_bank_handle b, int32_t* passages_covered_out, int64_t* postings_out, int32_t* longest_list_out);
+int rr_bank_ivf_read(rr_bank_handle b, int64_t* offsets_host_out, int32_t* pids_host_out, void* hip_stream);
+int rr_bank_search_plaid_ivf(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse,
+                             int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k,
+                             int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream);
 
 /* rr_head_joint: rr_head with the head RerankModel.forward runs (rr_forward_joint): `loss_fn(logits, logits)`
  * (rerank_model.py:328) — the labels are the logits themselves (2H_BCE: the two heads as class-probability targets).  The

@@ -347,7 +347,14 @@ int rr_op_topk_select(const float* scores, int n_lists, int n, int k, int32_t* i
  * rows of the n_passages passages back to back, lengths int32 [n_passages].  Outputs, each optional: cells_out uint8
  * [n_centroids], a1_out / a2_out float32 [n_passages] (-inf: no candidate), list1_out int32 [min(ndocs, n_passages)] with its
  * length in n1_out, list2_out int32 [min(ndocs / 4, n_passages)] with n2_out.  RR_ERR_BAD_SHAPE for a code outside the table.
- * rr_set_tuning("plaid_stop_after") (7; 0 .. 7): the last stage a call runs (timing by difference; below 7 nothing is output). */
+ * rr_set_tuning("plaid_stop_after") (7; 0 .. 7): the last stage a call runs (timing by difference; below 7 nothing is output).
+ * rr_set_tuning("plaid_ivf_stop_after") (8; 0 .. 8): the same for rr_bank_search_plaid_ivf: 0 - 2 as above, 3 candidates, 4 the
+ * listed A1 / A2, 5 the selection of ndocs, 6 the selection of ndocs / 4, 7 the exact scores, 8 the output.
+ * rr_util_plaid_ivf: THE INVERTED FILE (rerank_mi355.h) in pure HOST code, usable without a GPU: the written-down definition
+ * rr_bank_build_ivf is held to.  codes int32 / mask uint8 (NULL: all ones) over the rows of the n_passages passages back to back,
+ * lengths int32 [n_passages] (each >= 1); codes are clamped into [0, n_centroids).  offsets_out int64 [n_centroids + 1] is always
+ * written and *postings_out (or NULL) gets offsets_out[n_centroids]; pids_out (or NULL, to size it first) holds room for
+ * pids_capacity entries: RR_ERR_BAD_SHAPE, with pids_out untouched, when the postings do not fit. */
 int rr_op_bank_search_plaid(const float* query_li, int n_queries, int Lq, int Lq_coarse, int D, const void* table, int32_t first_passage,
                             int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k, const uint8_t* mask_bytes,
                             int nbits, const int32_t* codes, const uint8_t* residuals, const uint16_t* centroids_f16,
@@ -358,6 +365,8 @@ int rr_util_plaid_prune(const float* S, int32_t n_centroids, int Lq_coarse, cons
                         const int32_t* lengths, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs,
                         uint8_t* cells_out, float* a1_out, float* a2_out, int32_t* list1_out, int32_t* n1_out, int32_t* list2_out,
                         int32_t* n2_out);
+int rr_util_plaid_ivf(const int32_t* codes, const uint8_t* mask, const int32_t* lengths, int32_t n_passages, int32_t n_centroids,
+                      int64_t* offsets_out, int32_t* pids_out, int64_t pids_capacity, int64_t* postings_out);
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,364 @@
+// The inverted file of a compressed passage bank (rr_bank_build_ivf, include/rerank_mi355.h, "THE INVERTED FILE"): per centroid the
+// sorted unique passages with an unmasked row of that code, what the reference keeps as ivf.pid.pt (_build_ivf, third_party/ColBERT/
+// colbert/indexing/collection_indexer.py:393-431; optimize_ivf, indexing/utils.py:8-48), built from the codes the bank holds; and
+// the candidate step of rr_bank_search_plaid_ivf, which reads it (candidate_generation.py).
+// BUILD, rr_ivf_build (a load-time call: it allocates and synchronises):
+//   (a) ivf_mark_kernel<false>: a WAVE per passage.  Lanes load 64 codes per step (masked: -1) and a row is a FIRST OCCURRENCE iff
+//       no earlier unmasked row of the passage has its code: the rows of the same step are compared lane by lane (readlane, the
+//       step stays in registers), the rows of earlier steps are loaded again step by step and compared the same way, so a passage
+//       of any length takes no LDS.  A first occurrence adds 1 to its centroid's count (32-bit vector atomic on integers: one
+//       result in any order).
+//   (b) ivf_scan_kernel: one workgroup, the exclusive scan of the counts into int64 offsets [C + 1], the postings total and the
+//       longest list, which the host reads back to size `pids` and the search's scratch.
+//   (c) ivf_mark_kernel<true>: the same walk; a first occurrence takes a place in its list through the centroid's atomic cursor.
+//       WHICH place depends on scheduling; (d) removes that.
+//   (d) ivf_sort_kernel: a workgroup per list of 2 .. 4096 entries sorts it ascending in LDS (a bitonic network over distinct
+//       integers: one result).  A longer list is rebuilt: its passages set their bits in a bitmap of P bits (atomicOr: a set has
+//       no order) and ivf_compact_kernel writes the set bits out in ascending order.
+// SEARCH, rr_launch_ivf_candidates: per query a bitmap over the passages of the range is cleared, ivf_candidates_kernel (a
+// workgroup per (query, cell entry); an entry that repeats an earlier one of its query ends at once) ORs in the passages of the
+// cell's list that lie inside the range (found by two binary searches: the list is sorted), and ivf_compact_kernel turns every
+// bitmap into the ascending candidate list [nq][cap] with its count and writes -inf behind the count into the two compact score
+// rows.  Sets and sorted lists only: nothing depends on scheduling.
+// ivf_compact_kernel: ONE workgroup of 1024 per bitmap walks it 1024 words a time: a popcount per word, an inclusive scan over the
+// workgroup (wave shuffles, the sixteen wave totals through LDS), and every thread writes the bits of its word from its place on.
+// rr_ivf_host restates the definition in host code (rr_util_plaid_ivf).
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "rank_order.h"
+#include "rr_common.h"
+
+namespace {
+
+constexpr int IVF_SORT_MAX = 4096;       // entries ivf_sort_kernel sorts in LDS
+constexpr int IVF_COMPACT_THREADS = 1024;
+
+__device__ __forceinline__ long long shfl_up_i64(long long v, int d) {
+  const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_up((int)(uint32_t)((unsigned long long)v >> 32), d, 64);
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(256) void ivf_mark_kernel(const int32_t* __restrict__ codes, const uint8_t* __restrict__ mask,
+                                                       const rr_bank_slot* __restrict__ table, int P, int C, uint32_t* __restrict__ counts,
+                                                       const int64_t* __restrict__ offsets, int32_t* __restrict__ pids) {
+  const int lane = threadIdx.x & 63;
+  const long long pl = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (pl >= P) return;                                        // the whole wave
+  const int p = __builtin_amdgcn_readfirstlane((int)pl);
+  const rr_bank_slot sl = table[p];
+  const long long first_row = uniform_i64(sl.first_row);
+  const int len = __builtin_amdgcn_readfirstlane(sl.len);
+  for (int base = 0; base < len; base += 64) {
+    const int r = base + lane;
+    int code = -1;                                            // masked, or behind the end: no occurrence
+    if (r < len && mask[first_row + r]) code = min(max(codes[first_row + r], 0), C - 1);
+    bool first = code >= 0;
+    for (int eb = 0; eb < base; eb += 64) {                   // the steps before this one: 64 rows each, all inside the passage
+      int ec = -1;
+      if (mask[first_row + eb + lane]) ec = min(max(codes[first_row + eb + lane], 0), C - 1);
+      for (int t = 0; t < 64; ++t)
+        if (__builtin_amdgcn_readlane(ec, t) == code) first = false;      // (-1 meets -1 only where first is false already)
+    }
+    const int cnt = min(64, len - base);
+    for (int t = 0; t < cnt; ++t)
+      if (__builtin_amdgcn_readlane(code, t) == code && t < lane) first = false;
+    if (first) {
+      const uint32_t pos = atomicAdd(&counts[code], 1u);
+      if constexpr (FILL) {
+        const int64_t o = offsets[code];
+        if ((int64_t)pos < offsets[code + 1] - o) pids[o + pos] = p;
+      }
+    }
+  }
+}
+
+// info[0]: the postings total, info[1]: the longest list
+__global__ __launch_bounds__(1024) void ivf_scan_kernel(const uint32_t* __restrict__ counts, int C, int64_t* __restrict__ offsets,
+                                                        int64_t* __restrict__ info) {
+  __shared__ long long wsum[16];
+  __shared__ uint32_t wmax[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long per = ((long long)C + 1023) / 1024;
+  const int c0 = tid * per < C ? (int)(tid * per) : C, c1 = c0 + per < C ? (int)(c0 + per) : C;
+  long long s = 0;
+  uint32_t mx = 0;
+  for (int c = c0; c < c1; ++c) {
+    s += counts[c];
+    mx = max(mx, counts[c]);
+  }
+  long long incl = s;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const long long o = shfl_up_i64(incl, d);
+    if (lane >= d) incl += o;
+  }
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, m, 64));
+  if (lane == 63) wsum[wave] = incl;
+  if (lane == 0) wmax[wave] = mx;
+  __syncthreads();
+  long long run = incl - s;
+  for (int w = 0; w < wave; ++w) run += wsum[w];
+  for (int c = c0; c < c1; ++c) {
+    offsets[c] = run;
+    run += counts[c];
+  }
+  if (tid == 1023) {                                          // the last thread ends at the total
+    offsets[C] = run;
+    info[0] = run;
+  }
+  if (tid == 0) {
+    uint32_t m = 0;
+    for (int w = 0; w < 16; ++w) m = max(m, wmax[w]);
+    info[1] = m;
+  }
+}
+
+__global__ __launch_bounds__(256) void ivf_sort_kernel(const int64_t* __restrict__ offsets, int32_t* __restrict__ pids) {
+  __shared__ uint32_t key[IVF_SORT_MAX];
+  const int64_t o = offsets[blockIdx.x], cnt64 = offsets[blockIdx.x + 1] - o;
+  if (cnt64 < 2 || cnt64 > IVF_SORT_MAX) return;              // the whole workgroup
+  const int cnt = (int)cnt64, tid = threadIdx.x;
+  int n2 = 2;
+  while (n2 < cnt) n2 <<= 1;
+  for (int i = tid; i < n2; i += 256) key[i] = i < cnt ? (uint32_t)pids[o + i] : 0xffffffffu;      // padding behind every passage
+  __syncthreads();
+  for (int kk = 2; kk <= n2; kk <<= 1) {
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < n2; i += 256) {
+        const int l = i ^ j;
+        if (l > i) {
+          const bool up = (i & kk) == 0;                      // an ascending run
+          const uint32_t a = key[i], b = key[l];
+          if (up ? a > b : a < b) { key[i] = b; key[l] = a; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (int i = tid; i < cnt; i += 256) pids[o + i] = (int32_t)key[i];
+}
+
+// the passages list[0 .. cnt) as bits of bm (bit pid - first; a passage outside [first, first + n) sets none)
+__global__ __launch_bounds__(256) void ivf_list_bits_kernel(const int32_t* __restrict__ list, long long cnt, int first, int n,
+                                                            uint32_t* __restrict__ bm) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < cnt; i += (long long)gridDim.x * 256) {
+    const long long r = (long long)list[i] - first;
+    if (r >= 0 && r < n) atomicOr(&bm[r >> 5], 1u << (r & 31));
+  }
+}
+
+__device__ __forceinline__ long long ivf_lower_bound(const int32_t* __restrict__ pids, long long lo, long long hi, long long v) {
+  while (lo < hi) {                                           // the first entry of the sorted pids[lo .. hi) that is >= v
+    const long long mid = lo + ((hi - lo) >> 1);
+    if (pids[mid] < v) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// workgroup (e, q): cell entry e of query q (cells [nq][E]); the passages of its list inside [first, first + n) set their bits
+__global__ __launch_bounds__(256) void ivf_candidates_kernel(const int32_t* __restrict__ cells, int E, int C, const int64_t* __restrict__ offsets,
+                                                             const int32_t* __restrict__ pids, int first, int n, uint32_t* __restrict__ bm,
+                                                             int Wn) {
+  const int e = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
+  const int32_t* cl = cells + (size_t)q * E;
+  const int c = min(max(cl[e], 0), C - 1);
+  bool dup = false;
+  for (int i = tid; i < e; i += 256)
+    if (min(max(cl[i], 0), C - 1) == c) dup = true;
+  if (__syncthreads_or(dup)) return;                          // an earlier entry of the query walks this list
+  const long long a = ivf_lower_bound(pids, offsets[c], offsets[c + 1], first);
+  const long long b = ivf_lower_bound(pids, a, offsets[c + 1], (long long)first + n);
+  uint32_t* row = bm + (size_t)q * Wn;
+  for (long long i = a + tid; i < b; i += 256) {
+    const long long r = (long long)pids[i] - first;
+    if (r >= 0 && r < n) atomicOr(&row[r >> 5], 1u << (r & 31));      // an OR has one result
+  }
+}
+
+// Workgroup q: the set bits of bm[q][0 .. Wn) in ascending order, bit + add, to out[q * out_ld ...] (at most cap of them), their
+// number to cnt_out[q]; fill_a / fill_b (or null) [nq][cap] get -inf behind the count.
+__global__ __launch_bounds__(IVF_COMPACT_THREADS) void ivf_compact_kernel(const uint32_t* __restrict__ bm, int Wn, int32_t* __restrict__ out,
+                                                                          long long out_ld, int cap, int32_t* __restrict__ cnt_out, int add,
+                                                                          float* __restrict__ fill_a, float* __restrict__ fill_b) {
+  __shared__ int wtot[2][16];
+  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t* row = bm + (size_t)q * Wn;
+  int32_t* o = out + (size_t)q * out_ld;
+  long long base = 0;
+  int round = 0;
+  for (int w0 = 0; w0 < Wn; w0 += IVF_COMPACT_THREADS, round ^= 1) {
+    const int w = w0 + tid;
+    uint32_t word = w < Wn ? row[w] : 0u;
+    const int pc = __popc(word);
+    int incl = pc;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int x = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += x;
+    }
+    if (lane == 63) wtot[round][wave] = incl;
+    __syncthreads();                                          // (the buffers alternate: one barrier per round)
+    long long pos = base + incl - pc;
+    int tot = 0;
+    for (int i = 0; i < 16; ++i) {
+      if (i < wave) pos += wtot[round][i];
+      tot += wtot[round][i];
+    }
+    while (word) {
+      const int b = __ffs(word) - 1;
+      word &= word - 1;
+      if (pos < cap) o[pos] = w * 32 + b + add;
+      ++pos;
+    }
+    base += tot;
+  }
+  const int cnt = base < cap ? (int)base : cap;
+  if (tid == 0) cnt_out[q] = cnt;
+  if (fill_a)
+    for (int i = cnt + tid; i < cap; i += IVF_COMPACT_THREADS) {
+      fill_a[(size_t)q * cap + i] = -INFINITY;
+      fill_b[(size_t)q * cap + i] = -INFINITY;
+    }
+}
+
+}  // namespace
+
+void rr_ivf_free(rr_ivf* f) {
+  if (f->offsets) (void)hipFree(f->offsets);
+  if (f->pids) (void)hipFree(f->pids);
+  *f = rr_ivf{};
+}
+
+// The inverted file over the P passages (first[i], len[i]) of a compressed bank (host table), into *out (which must be empty).  On
+// a failure nothing is left allocated and *out stays empty; hipErrorOutOfMemory: an allocation failed.  Synchronises `st`.
+hipError_t rr_ivf_build(const rr_bank_view& bank, const int64_t* first, const int32_t* len, int P, hipStream_t st, rr_ivf* out) {
+  const int C = bank.n_centroids;
+  if (!bank.nbits || !bank.codes || !bank.mask || C < 1 || P < 1 || !first || !len || out->offsets || out->pids) return hipErrorInvalidValue;
+  const size_t Wn = ((size_t)P + 31) / 32;
+  rr_bank_slot* table = nullptr;
+  uint32_t* counts = nullptr;
+  int64_t* info = nullptr;
+  uint32_t* bm = nullptr;
+  rr_ivf f{};
+  hipError_t e = hipSuccess;
+  auto ok = [&](hipError_t x) { if (e == hipSuccess && x != hipSuccess) e = x; return e == hipSuccess; };
+  std::vector<rr_bank_slot> slots((size_t)P);
+  for (int i = 0; i < P; ++i) slots[(size_t)i] = rr_bank_slot{first[i], len[i], 0};
+  int64_t host_info[2] = {0, 0};
+  const unsigned mark_blocks = (unsigned)(((long long)P + 3) / 4);
+  if (ok(hipMalloc((void**)&table, (size_t)P * sizeof(rr_bank_slot))) && ok(hipMalloc((void**)&counts, (size_t)C * sizeof(uint32_t))) &&
+      ok(hipMalloc((void**)&info, 2 * sizeof(int64_t))) && ok(hipMalloc((void**)&f.offsets, ((size_t)C + 1) * sizeof(int64_t))) &&
+      ok(hipMemcpyAsync(table, slots.data(), slots.size() * sizeof(rr_bank_slot), hipMemcpyHostToDevice, st)) &&
+      ok(hipMemsetAsync(counts, 0, (size_t)C * sizeof(uint32_t), st))) {
+    hipLaunchKernelGGL(ivf_mark_kernel<false>, dim3(mark_blocks), dim3(256), 0, st, bank.codes, bank.mask, table, P, C, counts, nullptr, nullptr);
+    hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), dim3(1024), 0, st, counts, C, f.offsets, info);
+    ok(hipGetLastError());
+    ok(hipMemcpyAsync(host_info, info, sizeof host_info, hipMemcpyDeviceToHost, st));
+    ok(hipStreamSynchronize(st));                             // `slots` and host_info are pageable memory of this call
+  }
+  if (e == hipSuccess) {
+    f.passages = P;
+    f.postings = host_info[0];
+    f.longest = (int32_t)host_info[1];
+    if (f.postings < 0 || f.longest < 0 || f.longest > P) e = hipErrorUnknown;
+  }
+  if (e == hipSuccess && ok(hipMalloc((void**)&f.pids, (size_t)std::max<int64_t>(f.postings, 1) * sizeof(int32_t))) &&
+      ok(hipMemsetAsync(counts, 0, (size_t)C * sizeof(uint32_t), st))) {
+    hipLaunchKernelGGL(ivf_mark_kernel<true>, dim3(mark_blocks), dim3(256), 0, st, bank.codes, bank.mask, table, P, C, counts, f.offsets, f.pids);
+    hipLaunchKernelGGL(ivf_sort_kernel, dim3((unsigned)C), dim3(256), 0, st, f.offsets, f.pids);
+    ok(hipGetLastError());
+  }
+  if (e == hipSuccess && f.longest > IVF_SORT_MAX) {          // the lists one LDS slice does not hold, one after the other
+    std::vector<int64_t> off((size_t)C + 1);
+    int32_t* cnt_dev = (int32_t*)info;                        // the compaction's count: not needed again
+    if (ok(hipMalloc((void**)&bm, Wn * sizeof(uint32_t))) &&
+        ok(hipMemcpyAsync(off.data(), f.offsets, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st)) && ok(hipStreamSynchronize(st))) {
+      for (int c = 0; c < C && e == hipSuccess; ++c) {
+        const int64_t cnt = off[(size_t)c + 1] - off[(size_t)c];
+        if (cnt <= IVF_SORT_MAX) continue;
+        if (!ok(hipMemsetAsync(bm, 0, Wn * sizeof(uint32_t), st))) break;
+        const unsigned blocks = (unsigned)std::min<int64_t>((cnt + 255) / 256, 4096);
+        hipLaunchKernelGGL(ivf_list_bits_kernel, dim3(blocks), dim3(256), 0, st, f.pids + off[(size_t)c], (long long)cnt, 0, P, bm);
+        hipLaunchKernelGGL(ivf_compact_kernel, dim3(1), dim3(IVF_COMPACT_THREADS), 0, st, bm, (int)Wn, f.pids + off[(size_t)c], 0LL, (int)cnt,
+                           cnt_dev, 0, nullptr, nullptr);
+        ok(hipGetLastError());
+      }
+    }
+  }
+  const hipError_t es = hipStreamSynchronize(st);             // before the scratch goes
+  ok(es);
+  if (e != hipSuccess) (void)hipGetLastError();
+  if (table) (void)hipFree(table);
+  if (counts) (void)hipFree(counts);
+  if (info) (void)hipFree(info);
+  if (bm) (void)hipFree(bm);
+  if (e != hipSuccess) {
+    rr_ivf_free(&f);
+    return e;
+  }
+  *out = f;
+  return hipSuccess;
+}
+
+// stage 3 of rr_bank_search_plaid_ivf: cand [nq][cap] ascending range-relative candidates of every query, ccnt [nq] their numbers,
+// -inf behind them in a1 / a2 [nq][cap]; bm [nq][Wn] scratch, Wn = ceil(n / 32); cells [nq][E] from stage 1
+hipError_t rr_launch_ivf_candidates(const rr_ivf& f, int C, const int32_t* cells, int E, int nq, int first, int n, uint32_t* bm, int Wn,
+                                    int32_t* cand, int cap, int32_t* ccnt, float* a1, float* a2, hipStream_t st) {
+  if (!f.offsets || !f.pids || !cells || !bm || !cand || !ccnt || !a1 || !a2 || C < 1 || E < 1 || nq < 1 || nq > 65535 || first < 0 || n < 1 ||
+      (long long)first + n > f.passages || Wn != (n + 31) / 32 || cap < 1 || cap > n)
+    return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(bm, 0, (size_t)nq * Wn * sizeof(uint32_t), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(ivf_candidates_kernel, dim3((unsigned)E, (unsigned)nq), dim3(256), 0, st, cells, E, C, f.offsets, f.pids, first, n, bm, Wn);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(ivf_compact_kernel, dim3((unsigned)nq), dim3(IVF_COMPACT_THREADS), 0, st, bm, Wn, cand, (long long)cap, cap, ccnt, 0, a1, a2);
+  return hipGetLastError();
+}
+
+hipError_t rr_ivf_read(const rr_ivf& f, int C, int64_t* offsets_host, int32_t* pids_host, hipStream_t st) {
+  hipError_t e = hipSuccess;
+  if (offsets_host) e = hipMemcpyAsync(offsets_host, f.offsets, ((size_t)C + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && pids_host && f.postings > 0)
+    e = hipMemcpyAsync(pids_host, f.pids, (size_t)f.postings * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  return e != hipSuccess ? e : es;
+}
+
+// THE INVERTED FILE in host code (rr_util_plaid_ivf, rerank_mi355_diag.h).  Passages lie back to back in codes / mask.  offsets_out
+// [C + 1] is always written; pids_out (or null) holds room for pids_capacity entries.  Returns the postings total.
+int64_t rr_ivf_host(const int32_t* codes, const uint8_t* mask, const int32_t* lengths, int n, int C, int64_t* offsets_out, int32_t* pids_out,
+                    int64_t pids_capacity) {
+  std::vector<int64_t> count((size_t)C, 0);
+  std::vector<int32_t> last((size_t)C, -1);                   // the last passage counted for a centroid: passages come in ascending order
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass == 1) {
+      int64_t run = 0;
+      for (int c = 0; c < C; ++c) {
+        offsets_out[c] = run;
+        run += count[(size_t)c];
+        count[(size_t)c] = 0;
+        last[(size_t)c] = -1;
+      }
+      offsets_out[C] = run;
+      if (!pids_out || run > pids_capacity) return run;
+    }
+    size_t row = 0;
+    for (int p = 0; p < n; ++p) {
+      for (int r = 0; r < lengths[p]; ++r, ++row) {
+        if (mask && !mask[row]) continue;
+        const int c = std::min(std::max(codes[row], 0), C - 1);
+        if (last[(size_t)c] == p) continue;
+        last[(size_t)c] = p;
+        if (pass == 1) pids_out[offsets_out[c] + count[(size_t)c]] = p;
+        ++count[(size_t)c];
+      }
+    }
+  }
+  return offsets_out[C];
+}

@@ -29,7 +29,9 @@
 //     what it no longer stages and sorts on the host.
 //     WHICH passages a workgroup owns is a template parameter (PICK): pick_range, the chunk above, for rr_bank_search; pick_list,
 //     four entries of a per-query list with a count, one per wave, for stage 6 of rr_bank_search_plaid (bank_search_plaid.hip),
-//     whose scores are therefore these bits.  The range form compiles to the instructions it had before the picker existed.
+//     whose scores are therefore these bits; pick_via, pick_list through the candidate list of rr_bank_search_plaid_ivf (a list
+//     entry is a place in that list, and the score goes to that place of a compact row).  The range form compiles to the
+//     instructions it had before the picker existed.
 // (b) topk_select_kernel: each workgroup sorts a slice of at most 4096 (score, index) in LDS by ONE total order and keeps its
 //     first k (k <= 1024, so a pass is a strict reduction); passes repeat over the survivors until one slice is left.  The order
 //     and its 64-bit key are rank_order.h's, shared with the pruned search: keys are distinct, so the bitonic network (written out
@@ -56,7 +58,7 @@ constexpr int SEL_SLICE = 4096;          // (score, index) entries one workgroup
 constexpr int SEL_THREADS = 512;
 
 // Which passages a workgroup of the scoring kernel owns, and where their scores go (PICK).  at(q, p0, i, n): the table entry of
-// the workgroup's passage i; slot(row, p0, i, pi): its place in `out`, row = q * n.
+// the workgroup's passage i; slot(q, n, p0, i, pi): its place in `out`.
 // pick_range: `chunk` consecutive passages of the range; out is the dense [nq][n].
 struct pick_range {
   int chunk;
@@ -65,7 +67,7 @@ struct pick_range {
   __device__ __forceinline__ int first(int c) const { return c * chunk; }
   __device__ __forceinline__ int count(int, int p0, int n) const { return min(chunk, n - p0); }
   __device__ __forceinline__ int at(int, int p0, int i, int) const { return p0 + i; }
-  __device__ __forceinline__ size_t slot(size_t row, int p0, int i, int) const { return row + p0 + i; }
+  __device__ __forceinline__ size_t slot(int q, int n, int p0, int i, int) const { return (size_t)q * n + p0 + i; }
 };
 // pick_list: four entries, one per wave, of the first cnt[q] of list[q][0 .. list_ld) (an entry outside [0, n) is clamped); a score
 // goes to its passage's entry of the dense row out[q][.].  A workgroup behind the count has nothing to do.
@@ -80,7 +82,27 @@ struct pick_list {
   __device__ __forceinline__ int at(int q, int p0, int i, int n) const {
     return min(max(__builtin_amdgcn_readfirstlane(list[(size_t)q * list_ld + p0 + i]), 0), n - 1);
   }
-  __device__ __forceinline__ size_t slot(size_t row, int, int, int pi) const { return row + pi; }
+  __device__ __forceinline__ size_t slot(int q, int n, int, int, int pi) const { return (size_t)q * n + pi; }
+};
+// pick_via: pick_list through a candidate list: a list entry is a PLACE of cand[q][0 .. cap) (clamped), the passage is the entry of
+// cand there (clamped into [0, n)), and the score goes to that place of the compact row out[q][0 .. cap).
+struct pick_via {
+  const int32_t* list;
+  int list_ld;
+  const int32_t* cnt;
+  const int32_t* cand;
+  int cap;
+  static constexpr int PSUM = 4;
+  static constexpr bool LISTED = true;
+  __device__ __forceinline__ int first(int c) const { return c * 4; }
+  __device__ __forceinline__ int count(int q, int p0, int) const { return min(4, cnt[q] - p0); }
+  __device__ __forceinline__ int place(int q, int p0, int i) const {
+    return min(max(__builtin_amdgcn_readfirstlane(list[(size_t)q * list_ld + p0 + i]), 0), cap - 1);
+  }
+  __device__ __forceinline__ int at(int q, int p0, int i, int n) const {
+    return min(max(__builtin_amdgcn_readfirstlane(cand[(size_t)q * cap + place(q, p0, i)]), 0), n - 1);
+  }
+  __device__ __forceinline__ size_t slot(int q, int, int p0, int i, int) const { return (size_t)q * cap + place(q, p0, i); }
 };
 
 template <int JT, class SRC, class PICK>
@@ -169,7 +191,7 @@ __global__ __launch_bounds__(256) void bank_search_scores_kernel(const float* __
         }
       }
       if (lane == 0) {
-        if (last) out[pick.slot((size_t)q * n, p0, i, pi)] = sum;
+        if (last) out[pick.slot(q, n, p0, i, pi)] = sum;
         else psum[i] = sum;
       }
     }
@@ -285,6 +307,18 @@ hipError_t rr_launch_bank_search_scores_listed(const rr_bank_slot* table, int n,
       return hipErrorInvalidValue;
     else
       return search_launch(query_li, src, table, n, nq, (list_ld + 3) / 4, pick_list{list, list_ld, cnt}, Lq, D, tile_bytes, out, st);
+  });
+}
+
+hipError_t rr_launch_bank_search_scores_via(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
+                                            const rr_bank_view& bank, const int32_t* list, int list_ld, const int32_t* cnt,
+                                            const int32_t* cand, int cap, float* out, hipStream_t st) {
+  if (!scores_args_ok(table, n, nq, Lq, query_li, out) || !list || !cnt || list_ld <= 0 || !cand || cap <= 0) return hipErrorInvalidValue;
+  return li_with_bank_source(nullptr, nullptr, bank, D, [&](const auto& src, size_t tile_bytes) -> hipError_t {
+    if constexpr (!std::decay_t<decltype(src)>::TILE)
+      return hipErrorInvalidValue;
+    else
+      return search_launch(query_li, src, table, n, nq, (list_ld + 3) / 4, pick_via{list, list_ld, cnt, cand, cap}, Lq, D, tile_bytes, out, st);
   });
 }
 

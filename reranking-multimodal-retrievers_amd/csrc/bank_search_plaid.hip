@@ -28,6 +28,13 @@
 // The rank order of every list (NaN first, higher score, lower index) and its 64-bit key are those of rr_bank_search: rank_order.h
 // (the bitonic network over keys is written out in plaid_list_select_kernel as in topk_select_kernel; rank_order.h says why).
 // rr_plaid_prune_host restates cells, candidates, stage 1 and stage 2 in host code over the same key: the written-down definition.
+// rr_bank_search_plaid_ivf (rr_launch_plaid_ivf_search_stage) keeps stages 0 - 2 and takes the candidates from the bank's inverted
+// file in place of the scan: 3 the candidate lists (bank_ivf.hip: a bitmap per query set from the lists of its cells, compacted in
+// ascending order, cap entries a query), 4 plaid_score_listed_kernel: A1 / A2 of the listed candidates into compact rows [nq][cap]
+// by plaid_a1_a2, the device function the scan computes them with, 5 rr_launch_topk_select over the compact A1 row, 6 - 8 the
+// stages 5 - 7 above over the compact rows: a list entry is a PLACE in the candidate list (places follow bank-index order, so the
+// tie rule holds), stage 7 finds the passage of a place through the list (pick_via, bank_search.hip) and stage 8 maps places back.
+// rr_launch_plaid_search_stage keeps its eight launches; its scan kernel compiles to the instructions it had before plaid_a1_a2.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -113,6 +120,44 @@ __global__ __launch_bounds__(256) void plaid_bitmaps_kernel(const float* __restr
   }
 }
 
+// A1 (s1) and A2 (s2) of ONE candidate passage, by the whole wave (every lane ends with both): lane j owns column j, one row of S per
+// unmasked row of the passage, the column maxima with and without the keep test (keep: the query's keep bitmap in LDS) side by
+// side, the columns summed 0, 1, ... Lq_coarse - 1 in sequence from 0.0f.  The one body under plaid_scan_kernel and
+// plaid_score_listed_kernel, so that both give the same bits.
+__device__ __forceinline__ void plaid_a1_a2(const float* __restrict__ Sq, int s_ld, int C, int Lqc, const uint32_t* keep,
+                                            const int32_t* __restrict__ codes, const uint8_t* __restrict__ mask, long long first_row, int len,
+                                            int lane, float& s1, float& s2) {
+  s1 = 0.0f;
+  s2 = 0.0f;
+  for (int j0 = 0; j0 < Lqc; j0 += 64) {
+    const int j = j0 + lane;
+    const bool j_ok = j < Lqc;
+    float m1 = LI_MASKED, m2 = LI_MASKED;
+    for (int base = 0; base < len; base += 64) {
+      const int r = base + lane;
+      int code = 0, mk = 0;
+      if (r < len) {
+        code = min(max(codes[first_row + r], 0), C - 1);
+        mk = mask[first_row + r];
+      }
+      const int cnt = min(64, len - base);
+      for (int t = 0; t < cnt; ++t) {
+        if (!__builtin_amdgcn_readlane(mk, t)) continue;      // a masked row contributes nothing
+        const int c = __builtin_amdgcn_readlane(code, t);
+        const bool kept = (keep[c >> 5] >> (c & 31)) & 1u;
+        const float v = j_ok ? Sq[(size_t)c * s_ld + j] : LI_MASKED;
+        m2 = nan_max(m2, v);
+        if (kept) m1 = nan_max(m1, v);
+      }
+    }
+    const int cols = min(64, Lqc - j0);
+    for (int l = 0; l < cols; ++l) {                          // columns 0, 1, ... Lq_coarse - 1, one after the other
+      s1 += __shfl(m1, l, 64);
+      s2 += __shfl(m2, l, 64);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void plaid_scan_kernel(const float* __restrict__ S, long long s_q, int s_ld, int C, int Lqc,
                                                          const uint32_t* __restrict__ cellbits, const uint32_t* __restrict__ keepbits, int W,
                                                          const int32_t* __restrict__ codes, const uint8_t* __restrict__ mask,
@@ -142,37 +187,7 @@ __global__ __launch_bounds__(256) void plaid_scan_kernel(const float* __restrict
       cand = __ballot(hit) != 0ull;
     }
     float s1 = -INFINITY, s2 = -INFINITY;
-    if (cand) {                                               // wave-uniform
-      s1 = 0.0f;
-      s2 = 0.0f;
-      for (int j0 = 0; j0 < Lqc; j0 += 64) {
-        const int j = j0 + lane;
-        const bool j_ok = j < Lqc;
-        float m1 = LI_MASKED, m2 = LI_MASKED;
-        for (int base = 0; base < len; base += 64) {
-          const int r = base + lane;
-          int code = 0, mk = 0;
-          if (r < len) {
-            code = min(max(codes[first_row + r], 0), C - 1);
-            mk = mask[first_row + r];
-          }
-          const int cnt = min(64, len - base);
-          for (int t = 0; t < cnt; ++t) {
-            if (!__builtin_amdgcn_readlane(mk, t)) continue;  // a masked row contributes nothing
-            const int c = __builtin_amdgcn_readlane(code, t);
-            const bool kept = (bits[W + (c >> 5)] >> (c & 31)) & 1u;
-            const float v = j_ok ? Sq[(size_t)c * s_ld + j] : LI_MASKED;
-            m2 = nan_max(m2, v);
-            if (kept) m1 = nan_max(m1, v);
-          }
-        }
-        const int cols = min(64, Lqc - j0);
-        for (int l = 0; l < cols; ++l) {                      // columns 0, 1, ... Lq_coarse - 1, one after the other
-          s1 += __shfl(m1, l, 64);
-          s2 += __shfl(m2, l, 64);
-        }
-      }
-    }
+    if (cand) plaid_a1_a2(Sq, s_ld, C, Lqc, bits + W, codes, mask, first_row, len, lane, s1, s2);      // wave-uniform
     if (lane == 0) {
       a1[(size_t)q * n + p0 + i] = s1;
       a2[(size_t)q * n + p0 + i] = s2;
@@ -180,13 +195,44 @@ __global__ __launch_bounds__(256) void plaid_scan_kernel(const float* __restrict
   }
 }
 
+// Stage 4 of rr_bank_search_plaid_ivf: A1 and A2 (plaid_a1_a2, the arithmetic of the scan) of the LISTED candidates of a query:
+// entry i < min(cnt[q], cap) of cand[q][0 .. cap) (range-relative, clamped into [0, n)) goes to a1 / a2 [q][i] of the compact rows
+// [nq][cap]; the entries behind the count are written by the candidate step.  A workgroup belongs to one query (blockIdx % nq), holds
+// its keep bitmap in LDS and takes four entries a round, one per wave, `groups` workgroups of a query striding over its list; a
+// workgroup whose first round lies behind the count ends before it loads anything.
+__global__ __launch_bounds__(256) void plaid_score_listed_kernel(const float* __restrict__ S, long long s_q, int s_ld, int C, int Lqc,
+                                                                 const uint32_t* __restrict__ keepbits, int W, const int32_t* __restrict__ codes,
+                                                                 const uint8_t* __restrict__ mask, const rr_bank_slot* __restrict__ table, int n,
+                                                                 int nq, int groups, const int32_t* __restrict__ cand, int cap,
+                                                                 const int32_t* __restrict__ cnt, float* __restrict__ a1, float* __restrict__ a2) {
+  extern __shared__ uint32_t bits[];     // [W] keep
+  const int q = blockIdx.x % nq, g = blockIdx.x / nq, have = min(cnt[q], cap);
+  if (g * 4 >= have) return;             // the whole workgroup
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int i = threadIdx.x; i < W; i += 256) bits[i] = keepbits[(size_t)q * W + i];
+  __syncthreads();
+  const float* Sq = S + (size_t)q * s_q;
+  for (int i = g * 4 + wave; i < have; i += groups * 4) {     // a candidate belongs to one wave
+    const int p = min(max(__builtin_amdgcn_readfirstlane(cand[(size_t)q * cap + i]), 0), n - 1);
+    const rr_bank_slot sl = table[p];
+    float s1, s2;
+    plaid_a1_a2(Sq, s_ld, C, Lqc, bits, codes, mask, uniform_i64(sl.first_row), __builtin_amdgcn_readfirstlane(sl.len), lane, s1, s2);
+    if (lane == 0) {
+      a1[(size_t)q * cap + i] = s1;
+      a2[(size_t)q * cap + i] = s2;
+    }
+  }
+}
+
 // One workgroup per query: the entries list_in[q][0 .. cnt) (cnt = cnt_in[q], or n_in) whose score (and whose entry of valid_row, if
 // given) is not -inf, in rank order by scores[q][entry]; the first `keep` go to list_out[q] (+ add) and scores_out[q], -1 / -inf
-// behind them up to `keep`, their number to cnt_out[q].  cnt <= 1024.
+// behind them up to `keep`, their number to cnt_out[q].  cnt <= 1024.  map (or null) [.][n]: list_out gets map[q][entry] in place of
+// the entry (rr_bank_search_plaid_ivf: an entry is a place in the query's candidate list, the output its passage).
 __global__ __launch_bounds__(256) void plaid_list_select_kernel(const float* __restrict__ scores, const float* __restrict__ valid_row, long long n,
                                                                 const int32_t* __restrict__ list_in, int in_ld, const int32_t* __restrict__ cnt_in,
                                                                 int n_in, int keep, int32_t* __restrict__ list_out, int out_ld,
-                                                                int32_t* __restrict__ cnt_out, int add, float* __restrict__ scores_out) {
+                                                                int32_t* __restrict__ cnt_out, int add, float* __restrict__ scores_out,
+                                                                const int32_t* __restrict__ map) {
   __shared__ unsigned long long key[LIST_MAX];
   __shared__ int valid;
   const int q = blockIdx.x, tid = threadIdx.x;
@@ -227,7 +273,7 @@ __global__ __launch_bounds__(256) void plaid_list_select_kernel(const float* __r
     float s = -INFINITY;
     if (i < kept) {
       const int idx = (int)rank_key_index(key[i]);
-      o = idx + add;
+      o = (map ? map[(size_t)q * n + idx] : idx) + add;
       s = row[idx];
     }
     list_out[(size_t)q * out_ld + i] = o;
@@ -316,13 +362,92 @@ hipError_t rr_launch_plaid_search_stage(int stage, const rr_plaid_search_args& a
                                    l.tmp_entries ? (int32_t*)(a.scratch + l.tmp_b) : nullptr, list1, nullptr, st);
     case 5:
       hipLaunchKernelGGL(plaid_list_select_kernel, dim3((unsigned)a.nq), dim3(256), 0, st, a2, a1, (long long)a.n, list1, l.k1, nullptr, l.k1,
-                         std::min(a.ndocs / 4, l.k2), list2, l.k2, cnt2, 0, nullptr);
+                         std::min(a.ndocs / 4, l.k2), list2, l.k2, cnt2, 0, nullptr, nullptr);
       return hipGetLastError();
     case 6:
       return rr_launch_bank_search_scores_listed(a.table, a.n, a.nq, a.Lq, a.D, a.query_li, a.bank, list2, l.k2, cnt2, a2, st);
     case 7:
       hipLaunchKernelGGL(plaid_list_select_kernel, dim3((unsigned)a.nq), dim3(256), 0, st, a2, nullptr, (long long)a.n, list2, l.k2, cnt2, 0,
-                         a.k, a.indices_out, a.k, a.counts_out, a.first, a.scores_out);
+                         a.k, a.indices_out, a.k, a.counts_out, a.first, a.scores_out, nullptr);
+      return hipGetLastError();
+  }
+  return hipErrorInvalidValue;
+}
+
+// rr_bank_search_plaid_ivf: the block of a call.  cap, the entries of a candidate list and of a compact score row: a query has
+// Lq_coarse * ncells cell entries and a list holds at most `longest` passages, and never more than the range.
+rr_plaid_search_layout rr_plaid_ivf_search_plan(int nq, int n, int C, int Lq, int Lqc, int ncells, int ndocs, int longest) {
+  rr_plaid_search_layout l{};
+  l.Cp = (C + PSEUDO - 1) / PSEUDO * PSEUDO;
+  l.W = (C + 31) / 32;
+  l.cap = (int)std::max<long long>(1, std::min<long long>(n, (long long)Lqc * ncells * longest));
+  l.Wn = (n + 31) / 32;
+  l.k1 = std::min(ndocs, l.cap);
+  l.k2 = std::min(ndocs / 4, n);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off += up16(bytes); return o; };
+  l.S = take((size_t)nq * l.Cp * Lq * sizeof(float));
+  l.pairs = take((size_t)nq * (l.Cp / PSEUDO) * sizeof(rr_bank_pair));
+  l.ones = take((size_t)l.Cp);
+  l.cells = take((size_t)nq * Lqc * ncells * sizeof(int32_t));
+  l.cellbits = take((size_t)nq * l.W * sizeof(uint32_t));
+  l.keepbits = take((size_t)nq * l.W * sizeof(uint32_t));
+  l.bm = take((size_t)nq * l.Wn * sizeof(uint32_t));
+  l.cand = take((size_t)nq * l.cap * sizeof(int32_t));
+  l.ccnt = take((size_t)nq * sizeof(int32_t));
+  l.a1 = take((size_t)nq * l.cap * sizeof(float));
+  l.a2 = take((size_t)nq * l.cap * sizeof(float));
+  l.list1 = take((size_t)nq * l.k1 * sizeof(int32_t));
+  l.list2 = take((size_t)nq * l.k2 * sizeof(int32_t));
+  l.cnt2 = take((size_t)nq * sizeof(int32_t));
+  l.tmp_entries = rr_topk_select_scratch(nq, l.cap, l.k1);
+  l.tmp_a = take(l.tmp_entries * sizeof(int32_t));
+  l.tmp_b = take(l.tmp_entries * sizeof(int32_t));
+  l.total = off;
+  return l;
+}
+
+hipError_t rr_launch_plaid_ivf_search_stage(int stage, const rr_plaid_search_args& a, const rr_plaid_search_layout& l, hipStream_t st) {
+  if (stage >= 0 && stage < 3) return rr_launch_plaid_search_stage(stage, a, l, st);      // (which checks the arguments)
+  const int C = a.bank.n_centroids;
+  if (!a.scratch || !a.query_li || !a.table || !a.bank.nbits || !a.bank.codes || !a.bank.mask || C < 1 || C > RR_PLAID_SEARCH_MAX_CENTROIDS ||
+      a.nq < 1 || a.n < 1 || a.Lqc < 1 || a.Lqc > a.Lq || a.ncells < 1 || a.ncells > std::min(C, 16) || a.ndocs < 4 || a.ndocs > LIST_MAX ||
+      a.k < 1 || a.k > l.k2 || !a.indices_out || !a.counts_out || l.cap < 1 || l.cap > a.n || l.k1 < 1 || l.k1 > l.cap || !a.ivf.offsets ||
+      !a.ivf.pids || (long long)a.first + a.n > a.ivf.passages)
+    return hipErrorInvalidValue;
+  float* S = (float*)(a.scratch + l.S);
+  const long long s_q = (long long)l.Cp * a.Lq;
+  int32_t* cells = (int32_t*)(a.scratch + l.cells);
+  uint32_t* keepbits = (uint32_t*)(a.scratch + l.keepbits);
+  int32_t* cand = (int32_t*)(a.scratch + l.cand);
+  int32_t* ccnt = (int32_t*)(a.scratch + l.ccnt);
+  float* a1 = (float*)(a.scratch + l.a1);
+  float* a2 = (float*)(a.scratch + l.a2);
+  int32_t* list1 = (int32_t*)(a.scratch + l.list1);
+  int32_t* list2 = (int32_t*)(a.scratch + l.list2);
+  int32_t* cnt2 = (int32_t*)(a.scratch + l.cnt2);
+  switch (stage) {
+    case 3:
+      return rr_launch_ivf_candidates(a.ivf, C, cells, a.Lqc * a.ncells, a.nq, a.first, a.n, (uint32_t*)(a.scratch + l.bm), l.Wn, cand, l.cap,
+                                      ccnt, a1, a2, st);
+    case 4: {
+      const int groups = std::min((l.cap + 3) / 4, 2048);     // workgroups of a query; they stride over its list
+      hipLaunchKernelGGL(plaid_score_listed_kernel, dim3((unsigned)((long long)groups * a.nq)), dim3(256), (size_t)l.W * sizeof(uint32_t), st,
+                         S, s_q, a.Lq, C, a.Lqc, keepbits, l.W, a.bank.codes, a.bank.mask, a.table, a.n, a.nq, groups, cand, l.cap, ccnt, a1, a2);
+      return hipGetLastError();
+    }
+    case 5:
+      return rr_launch_topk_select(a1, a.nq, l.cap, l.k1, 0, l.tmp_entries ? (int32_t*)(a.scratch + l.tmp_a) : nullptr,
+                                   l.tmp_entries ? (int32_t*)(a.scratch + l.tmp_b) : nullptr, list1, nullptr, st);
+    case 6:
+      hipLaunchKernelGGL(plaid_list_select_kernel, dim3((unsigned)a.nq), dim3(256), 0, st, a2, a1, (long long)l.cap, list1, l.k1, nullptr, l.k1,
+                         std::min(a.ndocs / 4, l.k2), list2, l.k2, cnt2, 0, nullptr, nullptr);
+      return hipGetLastError();
+    case 7:
+      return rr_launch_bank_search_scores_via(a.table, a.n, a.nq, a.Lq, a.D, a.query_li, a.bank, list2, l.k2, cnt2, cand, l.cap, a2, st);
+    case 8:
+      hipLaunchKernelGGL(plaid_list_select_kernel, dim3((unsigned)a.nq), dim3(256), 0, st, a2, nullptr, (long long)l.cap, list2, l.k2, cnt2, 0,
+                         a.k, a.indices_out, a.k, a.counts_out, a.first, a.scores_out, cand);
       return hipGetLastError();
   }
   return hipErrorInvalidValue;

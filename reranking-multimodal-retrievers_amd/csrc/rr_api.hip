@@ -313,6 +313,8 @@ struct rr_bank {
   bool has_cutoffs = false;
   char* cscratch = nullptr;
   size_t cscratch_cap = 0;
+  // rr_bank_build_ivf: the inverted file over the first ivf.passages passages (0: none); rr_bank_clear drops it
+  rr_ivf ivf{};
   std::string err;
   rr_model::AsmSlot slot[2];
   int next = 0;
@@ -2058,6 +2060,7 @@ static void bank_free(rr_bank* b) {
   if (b->table) (void)hipFree(b->table);
   if (b->cutoffs) (void)hipFree(b->cutoffs);
   if (b->cscratch) (void)hipFree(b->cscratch);
+  rr_ivf_free(&b->ivf);
   for (auto& a : b->slot) {
     if (a.host) (void)hipHostFree(a.host);
     if (a.dev) (void)hipFree(a.dev);
@@ -2467,6 +2470,58 @@ static int rr_bank_read_plaid_impl(rr_bank* b, int32_t index, int32_t* codes_out
   if (!b) return RR_ERR_BAD_ARG;
   if (!b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it holds no codes (rr_bank_read)", what);
   return bank_read(b, what, index, nullptr, codes_out, resid_out, mask_out, capacity_rows, hip_stream);
+}
+
+// rr_bank_build_ivf (include/rerank_mi355.h): the file is built beside the one the bank holds and takes its place only when complete
+static int rr_bank_build_ivf_impl(rr_bank* b, void* hip_stream) {
+  const char* what = "rr_bank_build_ivf";
+  if (!b) return RR_ERR_BAD_ARG;
+  if (!b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it holds no codes", what);
+  const long long held = (long long)b->first.size();
+  if (held < 1) return bfail(b, RR_ERR_BAD_SHAPE, "%s: the bank holds no passage", what);
+  hipStream_t st = (hipStream_t)hip_stream;
+  RR_TRY(bank_capture_guard(b, st, "%s cannot be captured into a graph (it allocates and synchronises)", what));
+  RR_BHIP(b, hipSetDevice(b->device));
+  rr_ivf f{};
+  const hipError_t e = rr_ivf_build(bank_view(b), b->first.data(), b->len.data(), (int)held, st, &f);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return bfail(b, e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP, "%s: %lld passages, %d centroids: %s (the bank is unchanged)", what, held,
+                 b->n_centroids, hipGetErrorString(e));
+  }
+  rr_ivf_free(&b->ivf);                             // hipFree waits for a search that still reads the previous file
+  b->ivf = f;
+  return RR_OK;
+}
+
+static int rr_bank_ivf_info_impl(rr_bank* b, int32_t* passages_covered_out, int64_t* postings_out, int32_t* longest_list_out) {
+  if (!b) return RR_ERR_BAD_ARG;
+  if (passages_covered_out) *passages_covered_out = b->ivf.passages;
+  if (postings_out) *postings_out = b->ivf.postings;
+  if (longest_list_out) *longest_list_out = b->ivf.longest;
+  return RR_OK;
+}
+
+static int rr_bank_ivf_read_impl(rr_bank* b, int64_t* offsets_host_out, int32_t* pids_host_out, void* hip_stream) {
+  const char* what = "rr_bank_ivf_read";
+  if (!b) return RR_ERR_BAD_ARG;
+  if (!b->ivf.passages) return bfail(b, RR_ERR_BAD_ARG, "%s: the bank has no inverted file (rr_bank_build_ivf)", what);
+  hipStream_t st = (hipStream_t)hip_stream;
+  RR_TRY(bank_capture_guard(b, st, "%s cannot be captured into a graph (it synchronises)", what));
+  RR_BHIP(b, hipSetDevice(b->device));
+  RR_BHIP(b, rr_ivf_read(b->ivf, b->n_centroids, offsets_host_out, pids_host_out, st));
+  return RR_OK;
+}
+
+static int rr_util_plaid_ivf_impl(const int32_t* codes, const uint8_t* mask, const int32_t* lengths, int32_t n_passages, int32_t n_centroids,
+                                  int64_t* offsets_out, int32_t* pids_out, int64_t pids_capacity, int64_t* postings_out) {
+  if (!codes || !lengths || !offsets_out) return RR_ERR_BAD_ARG;
+  if (n_passages < 1 || n_centroids < 1 || (pids_out && pids_capacity < 0)) return RR_ERR_BAD_SHAPE;
+  for (int p = 0; p < n_passages; ++p)
+    if (lengths[p] < 1) return RR_ERR_BAD_SHAPE;
+  const int64_t total = rr_ivf_host(codes, mask, lengths, n_passages, n_centroids, offsets_out, pids_out, pids_out ? pids_capacity : 0);
+  if (postings_out) *postings_out = total;
+  return pids_out && total > pids_capacity ? RR_ERR_BAD_SHAPE : RR_OK;
 }
 
 // FullContextRerankModel.forward (rerank_model.py:523-591) on the tokenised pairs.  FAM_JOINT: RerankModel.forward semantics
@@ -3108,6 +3163,8 @@ static int rr_op_bank_search_impl(const float* query_li, int n_queries, int Lq, 
 // rr_set_tuning("plaid_stop_after"): the last stage an rr_bank_search_plaid call runs (7: all; below it the outputs are not
 // written): tools/bench_bank_search_plaid.py times the stages by difference
 static int g_plaid_stop_after = RR_PLAID_SEARCH_STAGES - 1;      // a diagnostic switch, set between calls (as g_op_dt)
+// rr_set_tuning("plaid_ivf_stop_after"): the same for rr_bank_search_plaid_ivf (8: all)
+static int g_plaid_ivf_stop_after = RR_PLAID_IVF_SEARCH_STAGES - 1;
 
 // what rr_bank_search_plaid and rr_op_bank_search_plaid refuse alike, in the order the header gives; msg: the sentence for the handle
 static int plaid_search_limits(int n_centroids, int n, int Lq, int Lq_coarse, int ncells, int ndocs, int k, const char** msg) {
@@ -3122,11 +3179,12 @@ static int plaid_search_limits(int n_centroids, int n, int Lq, int Lq_coarse, in
   return RR_OK;
 }
 
-// rr_bank_search_plaid (include/rerank_mi355.h): the block, and the eight stages of bank_search_plaid.hip, each booked on its own
-static int bank_search_plaid_call(rr_handle h, rr_bank* b, const float* query_li, int n_queries, int Lq, int Lq_coarse, int32_t first_passage,
-                                  int32_t n_passages, int ncells, float threshold, int ndocs, int k, int32_t* indices_out, float* scores_out,
-                                  int32_t* counts_out, void* hip_stream) {
-  const char* what = "rr_bank_search_plaid";
+// rr_bank_search_plaid (include/rerank_mi355.h): the block, and the eight stages of bank_search_plaid.hip, each booked on its own.
+// ivf: rr_bank_search_plaid_ivf, the same checks, one more refusal, and the nine stages that read the bank's inverted file
+static int bank_search_plaid_call(rr_handle h, bool ivf, rr_bank* b, const float* query_li, int n_queries, int Lq, int Lq_coarse,
+                                  int32_t first_passage, int32_t n_passages, int ncells, float threshold, int ndocs, int k, int32_t* indices_out,
+                                  float* scores_out, int32_t* counts_out, void* hip_stream) {
+  const char* what = ivf ? "rr_bank_search_plaid_ivf" : "rr_bank_search_plaid";
   if (!h) return RR_ERR_BAD_ARG;
   rr_model* m = h;
   hipStream_t st = (hipStream_t)hip_stream;
@@ -3136,17 +3194,40 @@ static int bank_search_plaid_call(rr_handle h, rr_bank* b, const float* query_li
                            [&](int np) {
                              const char* msg;
                              const int rc = plaid_search_limits(b->n_centroids, np, Lq, Lq_coarse, ncells, ndocs, k, &msg);
-                             return rc ? fail(m, rc, "%s: %s (Lq=%d Lq_coarse=%d ncells=%d ndocs=%d k=%d, %d passages, %d centroids)", what, msg, Lq,
-                                              Lq_coarse, ncells, ndocs, k, np, b->n_centroids) : (int)RR_OK;
+                             if (rc)
+                               return fail(m, rc, "%s: %s (Lq=%d Lq_coarse=%d ncells=%d ndocs=%d k=%d, %d passages, %d centroids)", what, msg, Lq,
+                                           Lq_coarse, ncells, ndocs, k, np, b->n_centroids);
+                             if (ivf && !b->ivf.passages)
+                               return fail(m, RR_ERR_UNSUPPORTED, "%s: the bank has no inverted file: call rr_bank_build_ivf first", what);
+                             if (ivf && (long long)first_passage + np > b->ivf.passages)
+                               return fail(m, RR_ERR_UNSUPPORTED, "%s: passages [%d, %d + %d) reach beyond the %d the inverted file covers: call "
+                                           "rr_bank_build_ivf again", what, first_passage, first_passage, np, b->ivf.passages);
+                             return (int)RR_OK;
                            }));
   const int D = m->cfg.li_dim;
-  const rr_plaid_search_layout l = rr_plaid_search_plan(n_queries, n, b->n_centroids, Lq, Lq_coarse, ncells, ndocs);
+  const rr_plaid_search_layout l = ivf ? rr_plaid_ivf_search_plan(n_queries, n, b->n_centroids, Lq, Lq_coarse, ncells, ndocs, b->ivf.longest)
+                                       : rr_plaid_search_plan(n_queries, n, b->n_centroids, Lq, Lq_coarse, ncells, ndocs);
   m->plaid_last_ok = false;
   RR_TRY(ensure_block(m, m->search_blk, m->search_blk_cap, l.total, st, "the bank search's block"));
   m->last_stream = st;
   const rr_plaid_search_args a{n_queries, n, first_passage, Lq, Lq_coarse, D, ncells, ndocs, k, threshold, query_li, b->table + first_passage,
-                               bank_view(b), m->search_blk, indices_out, scores_out, counts_out};
+                               bank_view(b), m->search_blk, indices_out, scores_out, counts_out, ivf ? b->ivf : rr_ivf{}};
   const double nq = n_queries, C = l.Cp, SLq = 4.0 * Lq_coarse;
+  if (ivf) {
+    // Bytes: the candidate step clears, sets and reads a bitmap of the range per query and writes the lists and the -inf behind
+    // them (the postings it reads are known on the device only); the listed scores read about 5 bytes per row of a candidate
+    // (at most cap of them: an upper bound); the selection reads the compact row.
+    const double cap = l.cap;
+    const double flops[RR_PLAID_IVF_SEARCH_STAGES] = {2.0 * nq * C * Lq * D, 0, 0, 0, 0, 0, 0, 2.0 * nq * l.k2 * (rows / n) * Lq * D, 0};
+    const double bytes[RR_PLAID_IVF_SEARCH_STAGES] = {2.0 * C * D + nq * (4.0 * Lq * D + 4.0 * C * Lq), nq * C * SLq * std::min(ncells, 2), nq * C * SLq,
+                                                      nq * (n / 8.0 * 3.0 + 12.0 * cap), nq * cap * (5.0 * (rows / n) + 28.0), 12.0 * nq * cap,
+                                                      16.0 * nq * l.k1, nq * l.k2 * (rows / n) * (rr_bank_row_bytes(a.bank, D) + 1.0),
+                                                      16.0 * nq * l.k2};
+    const int stop = g_plaid_ivf_stop_after;
+    for (int s = 0; s < RR_PLAID_IVF_SEARCH_STAGES && s <= stop; ++s)
+      RR_RUN(m, st, RR_K_TAIL, flops[s], bytes[s], rr_launch_plaid_ivf_search_stage(s, a, l, st));
+    return RR_OK;                                   // (no tap: plaid_last_ok stays false)
+  }
   // FLOPs: stage 0 exactly; stage 6 for ndocs / 4 survivors of the range's mean length (their number is known on the device only:
   // an upper bound).  Bytes: what a stage must read and write once; the scan's candidates add a row of S per unmasked row.
   const double flops[RR_PLAID_SEARCH_STAGES] = {2.0 * nq * C * Lq * D, 0, 0, 0, 0, 0, 2.0 * nq * l.k2 * (rows / n) * Lq * D, 0};
@@ -3380,6 +3461,11 @@ int rr_set_tuning(const char* key, int value) {
   if (!strcmp(key, "plaid_stop_after")) {
     if (value < 0 || value >= RR_PLAID_SEARCH_STAGES) return RR_ERR_BAD_ARG;
     g_plaid_stop_after = value;
+    return RR_OK;
+  }
+  if (!strcmp(key, "plaid_ivf_stop_after")) {
+    if (value < 0 || value >= RR_PLAID_IVF_SEARCH_STAGES) return RR_ERR_BAD_ARG;
+    g_plaid_ivf_stop_after = value;
     return RR_OK;
   }
   if (!strcmp(key, "attn_prio")) return rr_set_attn_prio(value);
@@ -3837,6 +3923,10 @@ int rr_bank_clear(rr_bank_handle b) {
   b->len.clear();
   b->used_rows = 0;
   b->table_n = 0;                 // the search's device table is rebuilt from the next passages
+  if (b->ivf.passages) {          // the inverted file names passages that are gone (hipFree waits for what still reads it)
+    (void)hipSetDevice(b->device);
+    rr_ivf_free(&b->ivf);
+  }
   return RR_OK;
 }
 const char* rr_bank_last_error(rr_bank_handle b) { return b ? b->err.c_str() : ""; }
@@ -3934,7 +4024,20 @@ int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_q
   return guarded(h, [&]() -> int { return bank_search_call(h, b, query_li, n_queries, Lq, first_passage, n_passages, k, indices_out, scores_out, hip_stream); });
 }
 int rr_bank_search_plaid(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse, int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream) {
-  return guarded(h, [&]() -> int { return bank_search_plaid_call(h, b, query_li, n_queries, Lq, Lq_coarse, first_passage, n_passages, ncells, centroid_score_threshold, ndocs, k, indices_out, scores_out, counts_out, hip_stream); });
+  return guarded(h, [&]() -> int { return bank_search_plaid_call(h, false, b, query_li, n_queries, Lq, Lq_coarse, first_passage, n_passages, ncells, centroid_score_threshold, ndocs, k, indices_out, scores_out, counts_out, hip_stream); });
+}
+int rr_bank_search_plaid_ivf(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse, int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream) {
+  return guarded(h, [&]() -> int { return bank_search_plaid_call(h, true, b, query_li, n_queries, Lq, Lq_coarse, first_passage, n_passages, ncells, centroid_score_threshold, ndocs, k, indices_out, scores_out, counts_out, hip_stream); });
+}
+int rr_bank_build_ivf(rr_bank_handle b, void* hip_stream) { return guarded(nullptr, [&]() -> int { return rr_bank_build_ivf_impl(b, hip_stream); }); }
+int rr_bank_ivf_info(rr_bank_handle b, int32_t* passages_covered_out, int64_t* postings_out, int32_t* longest_list_out) {
+  return guarded(nullptr, [&]() -> int { return rr_bank_ivf_info_impl(b, passages_covered_out, postings_out, longest_list_out); });
+}
+int rr_bank_ivf_read(rr_bank_handle b, int64_t* offsets_host_out, int32_t* pids_host_out, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_bank_ivf_read_impl(b, offsets_host_out, pids_host_out, hip_stream); });
+}
+int rr_util_plaid_ivf(const int32_t* codes, const uint8_t* mask, const int32_t* lengths, int32_t n_passages, int32_t n_centroids, int64_t* offsets_out, int32_t* pids_out, int64_t pids_capacity, int64_t* postings_out) {
+  return guarded(nullptr, [&]() -> int { return rr_util_plaid_ivf_impl(codes, mask, lengths, n_passages, n_centroids, offsets_out, pids_out, pids_capacity, postings_out); });
 }
 int64_t rr_bank_search_plaid_tap(rr_handle h, const char* name, void* host_out, int64_t max_bytes) {
   return guarded<int64_t>(h, [&]() -> int64_t { return bank_search_plaid_tap(h, name, host_out, max_bytes); });

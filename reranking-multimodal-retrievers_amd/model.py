@@ -207,6 +207,34 @@ def _bank_search_args(eng, name: str, bank, query_li: torch.Tensor, first: int, 
     return first, n, nq, Lq, query_li.to(device=eng.device, dtype=torch.float32).contiguous()
 
 
+def _bank_search_plaid(eng, entry: str, bank, query_li: torch.Tensor, k: int, *, ncells: int, centroid_score_threshold: float, ndocs: int,
+                       coarse_tokens: Optional[int] = None, first: int = 0, count: Optional[int] = None) -> dict:
+    """RerankEngine.bank_search_plaid and bank_search_plaid_ivf: the checks before the library, the outputs, the call of `entry`."""
+    first, n, nq, Lq, q = _bank_search_args(eng, "bank_search_plaid", bank, query_li, first, count, compressed_only=True)
+    codec = bank.codec
+    Lqc = Lq if coarse_tokens is None else int(coarse_tokens)
+    if Lqc < 1 or Lqc > Lq:
+        raise ValueError(f"bank_search_plaid: coarse_tokens = {Lqc} of {Lq} query tokens")
+    ncells, ndocs, k = int(ncells), int(ndocs), int(k)
+    if ncells < 1 or ncells > codec.n_centroids:
+        raise ValueError(f"bank_search_plaid: ncells = {ncells} of {codec.n_centroids} centroids")
+    if ncells > 16:
+        raise NotImplementedError(f"bank_search_plaid: ncells = {ncells} (at most 16)")
+    if ndocs < 4:
+        raise ValueError(f"bank_search_plaid: ndocs = {ndocs} (at least 4)")
+    if ndocs > 1024:
+        raise NotImplementedError(f"bank_search_plaid: ndocs = {ndocs} (at most 1024)")
+    if k < 1 or k > min(ndocs // 4, n):
+        raise ValueError(f"bank_search_plaid: k = {k} of ndocs // 4 = {ndocs // 4} survivors and {n} passages")
+    out = dict(indices=torch.empty((nq, k), device=eng.device, dtype=torch.int32),
+               scores=torch.empty((nq, k), device=eng.device, dtype=torch.float32),
+               counts=torch.empty((nq,), device=eng.device, dtype=torch.int32))
+    L.check(getattr(eng.lib, entry)(eng.h, bank.h, L.ptr(q), nq, Lq, Lqc, first, n, ncells, float(centroid_score_threshold), ndocs, k,
+                                     L.ptr(out["indices"]), L.ptr(out["scores"]), L.ptr(out["counts"]), eng._stream()),
+            eng.h, entry)
+    return out
+
+
 class RerankEngine:
     """Owns one `rr_handle` (one model replica on one GPU)."""
 
@@ -874,6 +902,19 @@ class RerankEngine:
                                         self._stream()), self.h, "rr_bank_search")
         return out
 
+    def bank_build_ivf(self, bank) -> dict:
+        """Build, or rebuild, the inverted file of a COMPRESSED `bank` over every passage it holds now (rr_bank_build_ivf; per
+        centroid the sorted unique passages with an unmasked token of that code, the reference's ivf.pid.pt).  A load-time call
+        on this engine's current stream: it allocates and synchronises.  Returns bank.ivf_info()."""
+        return bank.build_ivf()
+
+    def bank_search_plaid_ivf(self, bank, query_li: torch.Tensor, k: int, **kw) -> dict:
+        """bank_search_plaid with the candidates taken from the bank's inverted file (rr_bank_search_plaid_ivf): the same
+        arguments, the same checks and bit for bit the same result; the work of a query follows the lists of its cells, not the
+        rows of the range.  NotImplementedError when the bank has no file or the range reaches beyond the passages it covers
+        (bank_build_ivf)."""
+        return _bank_search_plaid(self, "rr_bank_search_plaid_ivf", bank, query_li, k, **kw)
+
     def bank_search_plaid(self, bank, query_li: torch.Tensor, k: int, *, ncells: int, centroid_score_threshold: float, ndocs: int,
                           coarse_tokens: Optional[int] = None, first: int = 0, count: Optional[int] = None) -> dict:
         """PLAID's pruned top-k search over a COMPRESSED `bank` (rr_bank_search_plaid; the reference's
@@ -882,29 +923,8 @@ class RerankEngine:
         of bank_search.  {"indices": int32 [n_queries, k] dense bank indices, -1 behind the count; "scores": float32
         [n_queries, k], -inf there; "counts": int32 [n_queries]}, on the device.  1 <= ncells <= min(centroids, 16),
         4 <= ndocs <= 1024, 1 <= k <= min(ndocs // 4, count) (ValueError / NotImplementedError before the library)."""
-        first, n, nq, Lq, q = _bank_search_args(self, "bank_search_plaid", bank, query_li, first, count, compressed_only=True)
-        codec = bank.codec
-        Lqc = Lq if coarse_tokens is None else int(coarse_tokens)
-        if Lqc < 1 or Lqc > Lq:
-            raise ValueError(f"bank_search_plaid: coarse_tokens = {Lqc} of {Lq} query tokens")
-        ncells, ndocs, k = int(ncells), int(ndocs), int(k)
-        if ncells < 1 or ncells > codec.n_centroids:
-            raise ValueError(f"bank_search_plaid: ncells = {ncells} of {codec.n_centroids} centroids")
-        if ncells > 16:
-            raise NotImplementedError(f"bank_search_plaid: ncells = {ncells} (at most 16)")
-        if ndocs < 4:
-            raise ValueError(f"bank_search_plaid: ndocs = {ndocs} (at least 4)")
-        if ndocs > 1024:
-            raise NotImplementedError(f"bank_search_plaid: ndocs = {ndocs} (at most 1024)")
-        if k < 1 or k > min(ndocs // 4, n):
-            raise ValueError(f"bank_search_plaid: k = {k} of ndocs // 4 = {ndocs // 4} survivors and {n} passages")
-        out = dict(indices=torch.empty((nq, k), device=self.device, dtype=torch.int32),
-                   scores=torch.empty((nq, k), device=self.device, dtype=torch.float32),
-                   counts=torch.empty((nq,), device=self.device, dtype=torch.int32))
-        L.check(self.lib.rr_bank_search_plaid(self.h, bank.h, L.ptr(q), nq, Lq, Lqc, first, n, ncells, float(centroid_score_threshold), ndocs, k,
-                                              L.ptr(out["indices"]), L.ptr(out["scores"]), L.ptr(out["counts"]), self._stream()),
-                self.h, "rr_bank_search_plaid")
-        return out
+        return _bank_search_plaid(self, "rr_bank_search_plaid", bank, query_li, k, ncells=ncells, centroid_score_threshold=centroid_score_threshold,
+                                  ndocs=ndocs, coarse_tokens=coarse_tokens, first=first, count=count)
 
     def bank_search_plaid_tap(self, name: str):
         """One intermediate of this engine's last bank_search_plaid call as a numpy array (rr_bank_search_plaid_tap,

@@ -17,7 +17,10 @@ matrix, rr_bank_li_scores) from either kind of bank, without a padded context te
 `PassageBank.search` / RerankEngine.bank_search give the k best passages of the bank (or of a range of it) per query by that
 score, exactly (rr_bank_search): every passage is scored, nothing is pruned.  With a `PlaidSearch` the same calls run PLAID's
 staged search over a compressed bank (rr_bank_search_plaid, RerankEngine.bank_search_plaid): candidates by centroid, two
-centroid-only pruning passes, exact MaxSim on the survivors.
+centroid-only pruning passes, exact MaxSim on the survivors.  `PassageBank.build_ivf` builds the bank's inverted file on the
+device (rr_bank_build_ivf: per centroid the sorted unique passages holding a token of that code, the reference's ivf.pid.pt;
+`ivf` / `save_ivf` read and write it), and `PlaidSearch(..., ivf=True)` takes the candidates from it (rr_bank_search_plaid_ivf):
+the same result, with work that follows the lists of the query's cells instead of the rows of the bank.
 
 `PassageBank.add_compress` fills a compressed bank from embeddings that are on the device (rr_bank_add_compress): nearest centroid
 on the matrix core and residual bucketising in two kernels, the codec's cutoffs given as `PlaidCodec(bucket_cutoffs=...)`.
@@ -40,14 +43,17 @@ from .pair_inputs import group_pairs_by_length
 class PlaidSearch:
     """The parameters of PLAID's pruned search (rr_bank_search_plaid): `ncells` centroids per query token open the candidate set,
     centroids whose best score is below `centroid_score_threshold` do not count in the first pruning pass, `ndocs` candidates
-    survive it and ndocs // 4 the second; `coarse_tokens`: the leading query tokens the approximate stages use (None: all)."""
+    survive it and ndocs // 4 the second; `coarse_tokens`: the leading query tokens the approximate stages use (None: all).
+    `ivf`: take the candidates from the bank's inverted file (rr_bank_search_plaid_ivf; PassageBank.build_ivf first): the same
+    result, bit for bit, with work that follows the lists of the query's cells instead of the rows of the bank."""
 
-    def __init__(self, ncells: int, centroid_score_threshold: float, ndocs: int, coarse_tokens: Optional[int] = None):
+    def __init__(self, ncells: int, centroid_score_threshold: float, ndocs: int, coarse_tokens: Optional[int] = None, ivf: bool = False):
         self.ncells, self.centroid_score_threshold, self.ndocs = int(ncells), float(centroid_score_threshold), int(ndocs)
         self.coarse_tokens = None if coarse_tokens is None else int(coarse_tokens)
+        self.ivf = bool(ivf)
 
     @classmethod
-    def defaults(cls, k: int, coarse_tokens: Optional[int] = None) -> "PlaidSearch":
+    def defaults(cls, k: int, coarse_tokens: Optional[int] = None, ivf: bool = False) -> "PlaidSearch":
         """The reference's parameters by k (third_party/ColBERT/colbert/searcher.py:97-122): k <= 100: ncells 2, threshold 0.45,
         ndocs 1024 (its k <= 10 branch sets the same three).  Its k > 100 defaults need ndocs = max(4 k, 4096), above what the
         search takes: NotImplementedError."""
@@ -55,13 +61,13 @@ class PlaidSearch:
         if k < 1:
             raise ValueError(f"PlaidSearch.defaults: k = {k}")
         if k <= 100:
-            return cls(2, 0.45, 1024, coarse_tokens)
+            return cls(2, 0.45, 1024, coarse_tokens, ivf)
         raise NotImplementedError(f"PlaidSearch.defaults: k = {k}: the reference's defaults above k = 100 (ncells 4, threshold 0.4, "
                                   f"ndocs {max(4 * k, 4096)}) need ndocs above 1024, the most the pruned search takes")
 
     def __repr__(self) -> str:
         return (f"PlaidSearch(ncells={self.ncells}, centroid_score_threshold={self.centroid_score_threshold}, ndocs={self.ndocs}, "
-                f"coarse_tokens={self.coarse_tokens})")
+                f"coarse_tokens={self.coarse_tokens}" + (", ivf=True)" if self.ivf else ")"))
 
 
 class BankTable:
@@ -653,17 +659,60 @@ class PassageBank:
         `first` / `count`: a range of dense indices).  Returns (passage_ids, scores): passage_ids[q] the ids of query q best
         first, scores float32 [n_queries, k] on the device.  Copies the indices to the host (synchronises).
         With `plaid` (a PlaidSearch; compressed banks) the pruned search runs instead (engine.bank_search_plaid): passage_ids[q]
-        has its true length, at most k (a query may find fewer candidates, or none), and scores holds -inf behind it."""
+        has its true length, at most k (a query may find fewer candidates, or none), and scores holds -inf behind it.  A
+        PlaidSearch with ivf=True takes the candidates from the inverted file (build_ivf first): the same result."""
         ids = self.table.ids
         if plaid is None:
             r = engine.bank_search(self, query_li, k, first=first, count=count)
             return [[ids[j] for j in row] for row in r["indices"].tolist()], r["scores"]
-        r = engine.bank_search_plaid(self, query_li, k, ncells=plaid.ncells, centroid_score_threshold=plaid.centroid_score_threshold,
-                                     ndocs=plaid.ndocs, coarse_tokens=plaid.coarse_tokens, first=first, count=count)
+        entry = engine.bank_search_plaid_ivf if getattr(plaid, "ivf", False) else engine.bank_search_plaid
+        r = entry(self, query_li, k, ncells=plaid.ncells, centroid_score_threshold=plaid.centroid_score_threshold, ndocs=plaid.ndocs,
+                  coarse_tokens=plaid.coarse_tokens, first=first, count=count)
         counts = r["counts"].tolist()
         return [[ids[j] for j in row[:c]] for row, c in zip(r["indices"].tolist(), counts)], r["scores"]
 
+    def build_ivf(self) -> dict:
+        """Build, or rebuild, the inverted file over every passage the bank holds now (rr_bank_build_ivf): per centroid the sorted
+        unique passages (dense indices) with an unmasked token of that code.  On the device; a load-time call that allocates and
+        synchronises the current stream.  Passages added later are not covered until the next build; `clear` drops the file.
+        Returns ivf_info().  An fp16 bank raises NotImplementedError, a failed allocation MemoryError with the previous file kept."""
+        if self.codec is None:
+            raise NotImplementedError("build_ivf on an fp16 bank: it holds no centroid codes")
+        self._check(self.lib.rr_bank_build_ivf(self.h, self._stream()), "rr_bank_build_ivf", bad_shape=ValueError)
+        return self.ivf_info()
+
+    def ivf_info(self) -> dict:
+        """rr_bank_ivf_info: passages_covered (0: no inverted file), postings (entries of all lists), longest_list."""
+        p, n, m = C.c_int32(0), C.c_int64(0), C.c_int32(0)
+        self._check(self.lib.rr_bank_ivf_info(self.h, C.byref(p), C.byref(n), C.byref(m)), "rr_bank_ivf_info")
+        return dict(passages_covered=int(p.value), postings=int(n.value), longest_list=int(m.value))
+
+    def ivf(self):
+        """The inverted file on the host (rr_bank_ivf_read; synchronises the current stream) as the reference's ivf.pid.pt holds
+        it: (pids int32 [postings], lengths int64 [n_centroids]); list c is pids[sum(lengths[:c]) : sum(lengths[:c + 1])], dense
+        bank indices in ascending order.  ValueError without a file (build_ivf)."""
+        import torch
+        info = self.ivf_info()
+        if not info["passages_covered"]:
+            raise ValueError("ivf: the bank has no inverted file (build_ivf)")
+        offsets = torch.empty(self.codec.n_centroids + 1, dtype=torch.int64)
+        pids = torch.empty(info["postings"], dtype=torch.int32)
+        self._check(self.lib.rr_bank_ivf_read(self.h, offsets.data_ptr(), pids.data_ptr() if pids.numel() else None, self._stream()),
+                    "rr_bank_ivf_read")
+        return pids, offsets[1:] - offsets[:-1]
+
+    def save_ivf(self, path: str) -> str:
+        """Write the inverted file as `path`/ivf.pid.pt, torch.save((ivf, ivf_lengths)) as the reference's indexer does
+        (optimize_ivf, colbert/indexing/utils.py:8-48), beside what PlaidCodec.save writes.  The pids are dense bank indices: they
+        are the reference's passage numbers when the bank was filled in the index's order.  Returns the file's path."""
+        import os
+        import torch
+        os.makedirs(path, exist_ok=True)
+        out = os.path.join(path, "ivf.pid.pt")
+        torch.save(self.ivf(), out)
+        return out
+
     def clear(self) -> None:
-        """Forget every passage (rr_bank_clear; the capacity stays).  Forwards that read the bank must have completed."""
+        """Forget every passage (rr_bank_clear; the capacity stays; the inverted file goes).  Forwards that read the bank must have completed."""
         self._check(self.lib.rr_bank_clear(self.h), "rr_bank_clear")
         self.table.clear()

@@ -16,7 +16,9 @@ Wall-clock ms per call (median of `--iters` calls, the two taking turns, `--roun
 device time of add_compress between two events, the same with rr_set_tuning("compress_stop_after") = 0: the row map and the
 assignment kernel alone, and that kernel's TFLOP/s (2 * rows * centroids * li_dim) beside the 155 the f32 matrix core gives and
 the 54 li_scores_kernel reaches.  The two paths' codes are compared on the first passages (the composed path sums in another
-order: rows whose two best centroids lie within rounding of each other may differ).  One JSON line to stdout and to --out."""
+order: rows whose two best centroids lie within rounding of each other may differ).  For scale beside the compress time: the
+build of the bank's inverted file over the passages just compressed (PassageBank.build_ivf, rr_bank_build_ivf: the median of three
+builds, synchronisation included).  One JSON line to stdout and to --out."""
 import argparse
 import json
 import os
@@ -136,6 +138,12 @@ def main():
         same_rows += int((eq & (r == want_res[o:o + lens[i]]).all(1)).sum())
         rows_cmp += lens[i]
         o += lens[i]
+    ivf_ms = []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ivf = bank.build_ivf()                             # synchronises
+        ivf_ms.append((time.perf_counter() - t0) * 1e3)
     call_dev = device_ms(fused)
     L.check(lib.rr_set_tuning(b"compress_stop_after", 0), None, "rr_set_tuning")
     try:
@@ -149,7 +157,8 @@ def main():
                add_compress_over_composed=round(mid["add_compress"] / mid["composed"], 4), add_fp16_ms=round(mid["add_fp16"], 3),
                add_compress_device_ms=round(call_dev, 3), assign_kernel_ms=round(assign_dev, 3),
                assign_tflops=round(flop / (assign_dev * 1e-3) / 1e12, 2), f32_matrix_core_tflops=155, li_scores_kernel_tflops=54,
-               compared_rows=rows_cmp, codes_equal=same_code, rows_equal_where_codes_equal=same_rows)
+               compared_rows=rows_cmp, codes_equal=same_code, rows_equal_where_codes_equal=same_rows,
+               ivf_build_ms=round(statistics.median(ivf_ms), 3), ivf_postings=ivf["postings"], ivf_longest_list=ivf["longest_list"])
     line = json.dumps(res)
     out = args.out if os.path.isabs(args.out) else os.path.join(ROOT, args.out)
     os.makedirs(os.path.dirname(out), exist_ok=True)

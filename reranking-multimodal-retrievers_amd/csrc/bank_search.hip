@@ -28,20 +28,20 @@
 //     and fills every slot with one pair), and 0.95 / 0.88 / 0.82 x compressed, at 16 queries fp16, and both: the call wins by
 //     what it no longer stages and sorts on the host.
 //     WHICH passages a workgroup owns is a template parameter (PICK): pick_range, the chunk above, for rr_bank_search; pick_list,
-//     four entries of a per-query list with a count, one per wave, for stage 6 of rr_bank_search_plaid (bank_search_plaid.hip),
-//     whose scores are therefore these bits; pick_via, pick_list through the candidate list of rr_bank_search_plaid_ivf (a list
-//     entry is a place in that list, and the score goes to that place of a compact row).  The range form compiles to the
-//     instructions it had before the picker existed.
+//     four entries of a per-query list with a count, one per wave, for the exact scores of rr_bank_search_plaid's tail
+//     (bank_search_plaid.hip), which are therefore these bits; pick_via, pick_list through the candidate list of
+//     rr_bank_search_plaid_ivf (a list entry is a place in that list, and the score goes to that place of a compact row).  The
+//     range form compiles to the instructions it had before the picker existed.
 // (b) topk_select_kernel: each workgroup sorts a slice of at most 4096 (score, index) in LDS by ONE total order and keeps its
 //     first k (k <= 1024, so a pass is a strict reduction); passes repeat over the survivors until one slice is left.  The order
 //     and its 64-bit key are rank_order.h's, shared with the pruned search: keys are distinct, so the bitonic network (written out
 //     here and in plaid_list_select_kernel, see rank_order.h) has one possible result.  Survivors travel as indices; a pass reads
 //     their scores again from the score row.
 // LAUNCHERS: rr_launch_bank_search_scores and rr_launch_bank_search_scores_listed take an rr_bank_view (rr_common.h), fp16 or
-// compressed (the listed form: compressed only), and rr_launch_topk_select.  The operand sources, the view-to-source dispatch
-// (li_with_bank_source), the once-per-device LDS attribute (li_lds_attr) and the width of the column block (li_pick_jt, here with a
-// fixed 72 KB) live in li_sources.h, shared with li_scores.hip; the tile step is written out in this kernel body and in
-// li_scores_kernel's (see li_scores.hip's header).
+// compressed (the listed form: compressed only; pick_list or, given a candidate list, pick_via), and rr_launch_topk_select.  The
+// operand sources, the view-to-source dispatch (li_with_bank_source), the once-per-device LDS attribute (li_lds_attr) and the
+// width of the column block (li_pick_jt, here with a fixed 72 KB) live in li_sources.h, shared with li_scores.hip; the tile step
+// is written out in this kernel body and in li_scores_kernel's (see li_scores.hip's header).
 #include <algorithm>
 #include <atomic>
 #include <type_traits>
@@ -297,29 +297,22 @@ hipError_t rr_launch_bank_search_scores(const rr_bank_slot* table, int n, int nq
 }
 
 // the same MaxSim for the passages list[q][0 .. cnt[q]) (entries of table[0 .. n), cnt[q] <= list_ld) of every query q, written to
-// out[q][entry] of the dense [nq][n]; the rest of `out` is left as it is.  Compressed banks only (the pruned search is the caller)
+// out[q][entry] of the dense [nq][n]; the rest of `out` is left as it is.  Compressed banks only (the pruned search is the caller).
+// cand / cap null / 0: pick_list.  Given: pick_via, a list entry is a place in cand [nq][cap] and out the compact [nq][cap].
 hipError_t rr_launch_bank_search_scores_listed(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
-                                               const rr_bank_view& bank, const int32_t* list, int list_ld, const int32_t* cnt, float* out,
-                                               hipStream_t st) {
-  if (!scores_args_ok(table, n, nq, Lq, query_li, out) || !list || !cnt || list_ld <= 0) return hipErrorInvalidValue;
-  return li_with_bank_source(nullptr, nullptr, bank, D, [&](const auto& src, size_t tile_bytes) -> hipError_t {
-    if constexpr (!std::decay_t<decltype(src)>::TILE)
-      return hipErrorInvalidValue;
-    else
-      return search_launch(query_li, src, table, n, nq, (list_ld + 3) / 4, pick_list{list, list_ld, cnt}, Lq, D, tile_bytes, out, st);
-  });
-}
-
-hipError_t rr_launch_bank_search_scores_via(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
-                                            const rr_bank_view& bank, const int32_t* list, int list_ld, const int32_t* cnt,
-                                            const int32_t* cand, int cap, float* out, hipStream_t st) {
-  if (!scores_args_ok(table, n, nq, Lq, query_li, out) || !list || !cnt || list_ld <= 0 || !cand || cap <= 0) return hipErrorInvalidValue;
-  return li_with_bank_source(nullptr, nullptr, bank, D, [&](const auto& src, size_t tile_bytes) -> hipError_t {
-    if constexpr (!std::decay_t<decltype(src)>::TILE)
-      return hipErrorInvalidValue;
-    else
-      return search_launch(query_li, src, table, n, nq, (list_ld + 3) / 4, pick_via{list, list_ld, cnt, cand, cap}, Lq, D, tile_bytes, out, st);
-  });
+                                               const rr_bank_view& bank, const int32_t* list, int list_ld, const int32_t* cnt,
+                                               const int32_t* cand, int cap, float* out, hipStream_t st) {
+  if (!scores_args_ok(table, n, nq, Lq, query_li, out) || !list || !cnt || list_ld <= 0 || (cand ? cap <= 0 : cap != 0))
+    return hipErrorInvalidValue;
+  auto with = [&](const auto& pick) {    // (a dispatch per picker: the kernels stay in the order the object had them in)
+    return li_with_bank_source(nullptr, nullptr, bank, D, [&](const auto& src, size_t tile_bytes) -> hipError_t {
+      if constexpr (!std::decay_t<decltype(src)>::TILE)
+        return hipErrorInvalidValue;
+      else
+        return search_launch(query_li, src, table, n, nq, (list_ld + 3) / 4, pick, Lq, D, tile_bytes, out, st);
+    });
+  };
+  return !cand ? with(pick_list{list, list_ld, cnt}) : with(pick_via{list, list_ld, cnt, cand, cap});
 }
 
 // int32 entries of EACH of the two survivor buffers rr_launch_topk_select needs (0: one slice, none)

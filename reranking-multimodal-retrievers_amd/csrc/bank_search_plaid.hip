@@ -1,7 +1,12 @@
 // PLAID-pruned top-k search over a range of a COMPRESSED passage bank (rr_bank_search_plaid, include/rerank_mi355.h): the staged
 // search of the reference (third_party/ColBERT/colbert/search/index_storage.py:86-184, candidate_generation.py) with every tie made
 // definite, from what a compressed bank already holds: one int32 centroid code per row, the fp16 centroid table, the passage table.
-// No IVF: the candidate set comes from one scan over the codes of the range.  The stages of a call, one launch each unless noted:
+// Two forms, one plan (rr_plaid_search_plan) and one stage driver (rr_launch_plaid_search_stage): rr_bank_search_plaid takes the
+// candidate set from one scan over the codes of the range, rr_bank_search_plaid_ivf from the bank's inverted file.  A call is a
+// HEAD of three stages, a CANDIDATE STEP of one stage (scan) or two (inverted file) that leaves A1 and A2 in two rows of `pitch`
+// entries a query, and a TAIL of four stages over those rows; a caller sees the stages numbered in sequence, 0 - 7 or 0 - 8.  One
+// launch each unless noted.
+// HEAD
 //   0  S [nq][Cp][Lq] float32, S[q][c][j] = <float32(centroid c), query q column j>: li_scores_kernel (li_scores.hip) over the
 //      centroid table taken as an fp16 bank of pseudo-passages of 64 centroids (Cp = C rounded up to 64; a prep launch writes the
 //      pair list and the all-ones mask), so an entry has the bits rr_li_scores gives.  All Lq columns are computed (the kernel
@@ -11,30 +16,31 @@
 //      the result does not depend on scheduling.
 //   2  plaid_bitmaps_kernel: per query the cell set and keep[c] = (max_j S[c][j] >= threshold; a NaN in the row: false) as bitmaps
 //      of C bits.  A workgroup owns 256 centroids: the cell bits meet in LDS (ds_or), keep bits by ballot; no global atomics.
-//   3  plaid_scan_kernel, the hot path: a workgroup belongs to one query and 64 consecutive passages, holds the query's two
+// CANDIDATE STEP, scan form (stage 3; pitch = n, an entry of a row is a passage of the range)
+//   plaid_scan_kernel, the hot path: a workgroup belongs to one query and 64 consecutive passages, holds the query's two
 //      bitmaps in LDS (C / 4 bytes) and a WAVE takes whole passages.  Lanes load 64 codes and mask bytes per step and test them
 //      against the cell bitmap; a ballot decides candidacy.  A non-candidate costs its codes and mask bytes and writes -inf.  A
 //      candidate walks its unmasked rows: lane j owns column j, one row of S per code is one coalesced read (Lq_coarse * 4 bytes),
 //      the column maxima with (A1) and without (A2) the keep test are kept side by side, and the columns are summed 0, 1, ...
 //      Lq_coarse - 1 in sequence from 0.0f by constant-lane shuffles, a chain every lane carries.  Above 64 columns the passage
-//      is walked once per block of 64 and the chain goes on.  A1 and A2 go to two dense rows [nq][n].
-//   4  rr_launch_topk_select (bank_search.hip, unchanged) over the A1 row: the first min(ndocs, n) per query; ties by bank index.
-//   5  plaid_list_select_kernel: stage-1 survivors (A1 != -inf) ordered by A2, the first ndocs / 4 kept, with their count.
-//   6  rr_launch_bank_search_scores_listed (bank_search.hip): bank_search_scores_kernel itself, the kernel of rr_bank_search, with
-//      a workgroup's passages picked from the stage-2 list of its query, one per wave (pick_list); the exact score overwrites
-//      the passage's entry of the A2 row.
-//   7  plaid_list_select_kernel again: by exact score, the first k; -1 / -inf behind the count, and the count.
+//      is walked once per block of 64 and the chain goes on (plaid_a1_a2).  A1 and A2 go to two dense rows [nq][n].
+// CANDIDATE STEP, inverted-file form (stages 3 and 4; pitch = cap, an entry of a row is a PLACE in the query's candidate list)
+//   rr_launch_ivf_candidates (bank_ivf.hip): a bitmap per query set from the lists of its cells and compacted in ascending order
+//      into cand [nq][cap] with its count; places follow bank-index order, so the tie rule holds.
+//   plaid_score_listed_kernel: A1 / A2 of the listed candidates into compact rows [nq][cap] by plaid_a1_a2, the device function the
+//      scan computes them with.
+// TAIL (stages 4 - 7, or 5 - 8), over the rows [nq][pitch] and via = the candidate lists (inverted file) or null (scan)
+//   rr_launch_topk_select (bank_search.hip) over the A1 row: the first min(ndocs, pitch) per query; ties by index.
+//   plaid_list_select_kernel: stage-1 survivors (A1 != -inf) ordered by A2, the first ndocs / 4 kept, with their count.
+//   rr_launch_bank_search_scores_listed (bank_search.hip): bank_search_scores_kernel itself, the kernel of rr_bank_search, with
+//      a workgroup's passages picked from the stage-2 list of its query, one per wave: the entry itself (pick_list), or the
+//      passage at that place of via (pick_via); the exact score overwrites the entry's place of the A2 row.
+//   plaid_list_select_kernel again: by exact score, the first k, mapped through via back to passages; -1 / -inf behind the count,
+//      and the count.
 // -inf is the "absent" mark of every row and list: an entry that holds it at some stage is not a survivor of that stage.
 // The rank order of every list (NaN first, higher score, lower index) and its 64-bit key are those of rr_bank_search: rank_order.h
 // (the bitonic network over keys is written out in plaid_list_select_kernel as in topk_select_kernel; rank_order.h says why).
 // rr_plaid_prune_host restates cells, candidates, stage 1 and stage 2 in host code over the same key: the written-down definition.
-// rr_bank_search_plaid_ivf (rr_launch_plaid_ivf_search_stage) keeps stages 0 - 2 and takes the candidates from the bank's inverted
-// file in place of the scan: 3 the candidate lists (bank_ivf.hip: a bitmap per query set from the lists of its cells, compacted in
-// ascending order, cap entries a query), 4 plaid_score_listed_kernel: A1 / A2 of the listed candidates into compact rows [nq][cap]
-// by plaid_a1_a2, the device function the scan computes them with, 5 rr_launch_topk_select over the compact A1 row, 6 - 8 the
-// stages 5 - 7 above over the compact rows: a list entry is a PLACE in the candidate list (places follow bank-index order, so the
-// tie rule holds), stage 7 finds the passage of a place through the list (pick_via, bank_search.hip) and stage 8 maps places back.
-// rr_launch_plaid_search_stage keeps its eight launches; its scan kernel compiles to the instructions it had before plaid_a1_a2.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -290,11 +296,21 @@ float host_nan_max(float m, float v) { return (v > m || v != v) ? v : m; }
 
 }  // namespace
 
-rr_plaid_search_layout rr_plaid_search_plan(int nq, int n, int C, int Lq, int Lqc, int ncells, int ndocs) {
+// The block of a call.  longest == 0: the scan form, score rows of n entries.  longest > 0, the longest list of the bank's inverted
+// file: the inverted-file form, with the bitmaps, the candidate lists and their counts, and score rows of cap entries: a query has
+// Lq_coarse * ncells cell entries and a list holds at most `longest` passages, and never more than the range.
+rr_plaid_search_layout rr_plaid_search_plan(int nq, int n, int C, int Lq, int Lqc, int ncells, int ndocs, int longest) {
   rr_plaid_search_layout l{};
+  const bool ivf = longest > 0;
+  l.stages = ivf ? RR_PLAID_IVF_SEARCH_STAGES : RR_PLAID_SEARCH_STAGES;
   l.Cp = (C + PSEUDO - 1) / PSEUDO * PSEUDO;
   l.W = (C + 31) / 32;
-  l.k1 = std::min(ndocs, n);
+  if (ivf) {
+    l.cap = (int)std::max<long long>(1, std::min<long long>(n, (long long)Lqc * ncells * longest));
+    l.Wn = (n + 31) / 32;
+  }
+  l.pitch = ivf ? l.cap : n;
+  l.k1 = std::min(ndocs, l.pitch);
   l.k2 = std::min(ndocs / 4, n);
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t o = off; off += up16(bytes); return o; };
@@ -304,24 +320,37 @@ rr_plaid_search_layout rr_plaid_search_plan(int nq, int n, int C, int Lq, int Lq
   l.cells = take((size_t)nq * Lqc * ncells * sizeof(int32_t));
   l.cellbits = take((size_t)nq * l.W * sizeof(uint32_t));
   l.keepbits = take((size_t)nq * l.W * sizeof(uint32_t));
-  l.a1 = take((size_t)nq * n * sizeof(float));
-  l.a2 = take((size_t)nq * n * sizeof(float));
+  if (ivf) {
+    l.bm = take((size_t)nq * l.Wn * sizeof(uint32_t));
+    l.cand = take((size_t)nq * l.cap * sizeof(int32_t));
+    l.ccnt = take((size_t)nq * sizeof(int32_t));
+  }
+  l.a1 = take((size_t)nq * l.pitch * sizeof(float));
+  l.a2 = take((size_t)nq * l.pitch * sizeof(float));
   l.list1 = take((size_t)nq * l.k1 * sizeof(int32_t));
   l.list2 = take((size_t)nq * l.k2 * sizeof(int32_t));
   l.cnt2 = take((size_t)nq * sizeof(int32_t));
-  l.tmp_entries = rr_topk_select_scratch(nq, n, l.k1);
+  l.tmp_entries = rr_topk_select_scratch(nq, l.pitch, l.k1);
   l.tmp_a = take(l.tmp_entries * sizeof(int32_t));
   l.tmp_b = take(l.tmp_entries * sizeof(int32_t));
   l.total = off;
   return l;
 }
 
+// Stage `stage` of l.stages.  The candidate step takes one stage number in the scan form and two in the inverted-file form; the
+// tail's four follow it.
 hipError_t rr_launch_plaid_search_stage(int stage, const rr_plaid_search_args& a, const rr_plaid_search_layout& l, hipStream_t st) {
   const int C = a.bank.n_centroids;
+  const bool ivf = l.stages == RR_PLAID_IVF_SEARCH_STAGES;
   if (!a.scratch || !a.query_li || !a.table || !a.bank.nbits || !a.bank.codes || !a.bank.mask || !a.bank.centroids || C < 1 ||
       C > RR_PLAID_SEARCH_MAX_CENTROIDS || a.nq < 1 || a.n < 1 || a.Lqc < 1 || a.Lqc > a.Lq || a.ncells < 1 || a.ncells > std::min(C, 16) ||
-      a.ndocs < 4 || a.ndocs > LIST_MAX || a.k < 1 || a.k > l.k2 || !a.indices_out || !a.counts_out)
+      a.ndocs < 4 || a.ndocs > LIST_MAX || a.k < 1 || a.k > l.k2 || !a.indices_out || !a.counts_out ||
+      (l.stages != RR_PLAID_SEARCH_STAGES && !ivf) || l.pitch != (ivf ? l.cap : a.n) || l.k1 < 1 || l.k1 > l.pitch ||
+      (ivf && (l.cap < 1 || l.cap > a.n || !a.ivf.offsets || !a.ivf.pids || (long long)a.first + a.n > a.ivf.passages)))
     return hipErrorInvalidValue;
+  // the steps of both forms in one sequence; a stage number skips the candidate steps of the other form
+  enum { SCORES, CELLS, BITMAPS, SCAN, IVF_LISTS, IVF_SCORES, SELECT_NDOCS, SELECT_QUARTER, EXACT, SELECT_K };
+  const int step = stage < 0 || stage >= l.stages ? -1 : stage < SCAN ? stage : ivf ? stage + 1 : stage == SCAN ? SCAN : stage + 2;
   float* S = (float*)(a.scratch + l.S);
   const long long s_q = (long long)l.Cp * a.Lq;
   rr_bank_pair* pairs = (rr_bank_pair*)(a.scratch + l.pairs);
@@ -334,8 +363,10 @@ hipError_t rr_launch_plaid_search_stage(int stage, const rr_plaid_search_args& a
   int32_t* list1 = (int32_t*)(a.scratch + l.list1);
   int32_t* list2 = (int32_t*)(a.scratch + l.list2);
   int32_t* cnt2 = (int32_t*)(a.scratch + l.cnt2);
-  switch (stage) {
-    case 0: {
+  int32_t* cand = ivf ? (int32_t*)(a.scratch + l.cand) : nullptr;      // the tail's via: a place in a row -> its passage
+  int32_t* ccnt = ivf ? (int32_t*)(a.scratch + l.ccnt) : nullptr;
+  switch (step) {
+    case SCORES: {
       const int blocks = l.Cp / PSEUDO, items = std::max(blocks * a.nq, l.Cp);
       hipLaunchKernelGGL(plaid_prep_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, pairs, blocks, a.nq, C, ones, l.Cp);
       const hipError_t e = hipGetLastError();
@@ -343,110 +374,40 @@ hipError_t rr_launch_plaid_search_stage(int stage, const rr_plaid_search_args& a
       const rr_bank_view cent{0, 0, a.bank.centroids, nullptr, nullptr, nullptr, nullptr, ones};
       return rr_launch_bank_li_scores(pairs, nullptr, blocks * a.nq, a.Lq, PSEUDO, a.D, a.query_li, cent, S, nullptr, st);
     }
-    case 1:
+    case CELLS:
       hipLaunchKernelGGL(plaid_cells_kernel, dim3((unsigned)(a.nq * a.Lqc)), dim3(256), 0, st, S, s_q, a.Lq, C, a.Lqc, a.ncells, cells);
       return hipGetLastError();
-    case 2:
+    case BITMAPS:
       hipLaunchKernelGGL(plaid_bitmaps_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)a.nq), dim3(256), 0, st, S, s_q, a.Lq, C, a.Lqc,
                          a.ncells, a.thr, cells, l.W, cellbits, keepbits);
       return hipGetLastError();
-    case 3: {
+    case SCAN: {
       const long long blocks = ((long long)a.n + PS_CHUNK - 1) / PS_CHUNK * a.nq;
       if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
       hipLaunchKernelGGL(plaid_scan_kernel, dim3((unsigned)blocks), dim3(256), (size_t)2 * l.W * sizeof(uint32_t), st, S, s_q, a.Lq, C, a.Lqc,
                          cellbits, keepbits, l.W, a.bank.codes, a.bank.mask, a.table, a.n, a.nq, a1, a2);
       return hipGetLastError();
     }
-    case 4:
-      return rr_launch_topk_select(a1, a.nq, a.n, l.k1, 0, l.tmp_entries ? (int32_t*)(a.scratch + l.tmp_a) : nullptr,
-                                   l.tmp_entries ? (int32_t*)(a.scratch + l.tmp_b) : nullptr, list1, nullptr, st);
-    case 5:
-      hipLaunchKernelGGL(plaid_list_select_kernel, dim3((unsigned)a.nq), dim3(256), 0, st, a2, a1, (long long)a.n, list1, l.k1, nullptr, l.k1,
-                         std::min(a.ndocs / 4, l.k2), list2, l.k2, cnt2, 0, nullptr, nullptr);
-      return hipGetLastError();
-    case 6:
-      return rr_launch_bank_search_scores_listed(a.table, a.n, a.nq, a.Lq, a.D, a.query_li, a.bank, list2, l.k2, cnt2, a2, st);
-    case 7:
-      hipLaunchKernelGGL(plaid_list_select_kernel, dim3((unsigned)a.nq), dim3(256), 0, st, a2, nullptr, (long long)a.n, list2, l.k2, cnt2, 0,
-                         a.k, a.indices_out, a.k, a.counts_out, a.first, a.scores_out, nullptr);
-      return hipGetLastError();
-  }
-  return hipErrorInvalidValue;
-}
-
-// rr_bank_search_plaid_ivf: the block of a call.  cap, the entries of a candidate list and of a compact score row: a query has
-// Lq_coarse * ncells cell entries and a list holds at most `longest` passages, and never more than the range.
-rr_plaid_search_layout rr_plaid_ivf_search_plan(int nq, int n, int C, int Lq, int Lqc, int ncells, int ndocs, int longest) {
-  rr_plaid_search_layout l{};
-  l.Cp = (C + PSEUDO - 1) / PSEUDO * PSEUDO;
-  l.W = (C + 31) / 32;
-  l.cap = (int)std::max<long long>(1, std::min<long long>(n, (long long)Lqc * ncells * longest));
-  l.Wn = (n + 31) / 32;
-  l.k1 = std::min(ndocs, l.cap);
-  l.k2 = std::min(ndocs / 4, n);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += up16(bytes); return o; };
-  l.S = take((size_t)nq * l.Cp * Lq * sizeof(float));
-  l.pairs = take((size_t)nq * (l.Cp / PSEUDO) * sizeof(rr_bank_pair));
-  l.ones = take((size_t)l.Cp);
-  l.cells = take((size_t)nq * Lqc * ncells * sizeof(int32_t));
-  l.cellbits = take((size_t)nq * l.W * sizeof(uint32_t));
-  l.keepbits = take((size_t)nq * l.W * sizeof(uint32_t));
-  l.bm = take((size_t)nq * l.Wn * sizeof(uint32_t));
-  l.cand = take((size_t)nq * l.cap * sizeof(int32_t));
-  l.ccnt = take((size_t)nq * sizeof(int32_t));
-  l.a1 = take((size_t)nq * l.cap * sizeof(float));
-  l.a2 = take((size_t)nq * l.cap * sizeof(float));
-  l.list1 = take((size_t)nq * l.k1 * sizeof(int32_t));
-  l.list2 = take((size_t)nq * l.k2 * sizeof(int32_t));
-  l.cnt2 = take((size_t)nq * sizeof(int32_t));
-  l.tmp_entries = rr_topk_select_scratch(nq, l.cap, l.k1);
-  l.tmp_a = take(l.tmp_entries * sizeof(int32_t));
-  l.tmp_b = take(l.tmp_entries * sizeof(int32_t));
-  l.total = off;
-  return l;
-}
-
-hipError_t rr_launch_plaid_ivf_search_stage(int stage, const rr_plaid_search_args& a, const rr_plaid_search_layout& l, hipStream_t st) {
-  if (stage >= 0 && stage < 3) return rr_launch_plaid_search_stage(stage, a, l, st);      // (which checks the arguments)
-  const int C = a.bank.n_centroids;
-  if (!a.scratch || !a.query_li || !a.table || !a.bank.nbits || !a.bank.codes || !a.bank.mask || C < 1 || C > RR_PLAID_SEARCH_MAX_CENTROIDS ||
-      a.nq < 1 || a.n < 1 || a.Lqc < 1 || a.Lqc > a.Lq || a.ncells < 1 || a.ncells > std::min(C, 16) || a.ndocs < 4 || a.ndocs > LIST_MAX ||
-      a.k < 1 || a.k > l.k2 || !a.indices_out || !a.counts_out || l.cap < 1 || l.cap > a.n || l.k1 < 1 || l.k1 > l.cap || !a.ivf.offsets ||
-      !a.ivf.pids || (long long)a.first + a.n > a.ivf.passages)
-    return hipErrorInvalidValue;
-  float* S = (float*)(a.scratch + l.S);
-  const long long s_q = (long long)l.Cp * a.Lq;
-  int32_t* cells = (int32_t*)(a.scratch + l.cells);
-  uint32_t* keepbits = (uint32_t*)(a.scratch + l.keepbits);
-  int32_t* cand = (int32_t*)(a.scratch + l.cand);
-  int32_t* ccnt = (int32_t*)(a.scratch + l.ccnt);
-  float* a1 = (float*)(a.scratch + l.a1);
-  float* a2 = (float*)(a.scratch + l.a2);
-  int32_t* list1 = (int32_t*)(a.scratch + l.list1);
-  int32_t* list2 = (int32_t*)(a.scratch + l.list2);
-  int32_t* cnt2 = (int32_t*)(a.scratch + l.cnt2);
-  switch (stage) {
-    case 3:
+    case IVF_LISTS:
       return rr_launch_ivf_candidates(a.ivf, C, cells, a.Lqc * a.ncells, a.nq, a.first, a.n, (uint32_t*)(a.scratch + l.bm), l.Wn, cand, l.cap,
                                       ccnt, a1, a2, st);
-    case 4: {
+    case IVF_SCORES: {
       const int groups = std::min((l.cap + 3) / 4, 2048);     // workgroups of a query; they stride over its list
       hipLaunchKernelGGL(plaid_score_listed_kernel, dim3((unsigned)((long long)groups * a.nq)), dim3(256), (size_t)l.W * sizeof(uint32_t), st,
                          S, s_q, a.Lq, C, a.Lqc, keepbits, l.W, a.bank.codes, a.bank.mask, a.table, a.n, a.nq, groups, cand, l.cap, ccnt, a1, a2);
       return hipGetLastError();
     }
-    case 5:
-      return rr_launch_topk_select(a1, a.nq, l.cap, l.k1, 0, l.tmp_entries ? (int32_t*)(a.scratch + l.tmp_a) : nullptr,
+    case SELECT_NDOCS:
+      return rr_launch_topk_select(a1, a.nq, l.pitch, l.k1, 0, l.tmp_entries ? (int32_t*)(a.scratch + l.tmp_a) : nullptr,
                                    l.tmp_entries ? (int32_t*)(a.scratch + l.tmp_b) : nullptr, list1, nullptr, st);
-    case 6:
-      hipLaunchKernelGGL(plaid_list_select_kernel, dim3((unsigned)a.nq), dim3(256), 0, st, a2, a1, (long long)l.cap, list1, l.k1, nullptr, l.k1,
+    case SELECT_QUARTER:
+      hipLaunchKernelGGL(plaid_list_select_kernel, dim3((unsigned)a.nq), dim3(256), 0, st, a2, a1, (long long)l.pitch, list1, l.k1, nullptr, l.k1,
                          std::min(a.ndocs / 4, l.k2), list2, l.k2, cnt2, 0, nullptr, nullptr);
       return hipGetLastError();
-    case 7:
-      return rr_launch_bank_search_scores_via(a.table, a.n, a.nq, a.Lq, a.D, a.query_li, a.bank, list2, l.k2, cnt2, cand, l.cap, a2, st);
-    case 8:
-      hipLaunchKernelGGL(plaid_list_select_kernel, dim3((unsigned)a.nq), dim3(256), 0, st, a2, nullptr, (long long)l.cap, list2, l.k2, cnt2, 0,
+    case EXACT:
+      return rr_launch_bank_search_scores_listed(a.table, a.n, a.nq, a.Lq, a.D, a.query_li, a.bank, list2, l.k2, cnt2, cand, l.cap, a2, st);
+    case SELECT_K:
+      hipLaunchKernelGGL(plaid_list_select_kernel, dim3((unsigned)a.nq), dim3(256), 0, st, a2, nullptr, (long long)l.pitch, list2, l.k2, cnt2, 0,
                          a.k, a.indices_out, a.k, a.counts_out, a.first, a.scores_out, cand);
       return hipGetLastError();
   }

@@ -3160,11 +3160,16 @@ static int rr_op_bank_search_impl(const float* query_li, int n_queries, int Lq, 
   return rc;
 }
 
-// rr_set_tuning("plaid_stop_after"): the last stage an rr_bank_search_plaid call runs (7: all; below it the outputs are not
-// written): tools/bench_bank_search_plaid.py times the stages by difference
-static int g_plaid_stop_after = RR_PLAID_SEARCH_STAGES - 1;      // a diagnostic switch, set between calls (as g_op_dt)
-// rr_set_tuning("plaid_ivf_stop_after"): the same for rr_bank_search_plaid_ivf (8: all)
-static int g_plaid_ivf_stop_after = RR_PLAID_IVF_SEARCH_STAGES - 1;
+// rr_set_tuning("plaid_stop_after") [0] and ("plaid_ivf_stop_after") [1]: the last stage an rr_bank_search_plaid call (7: all) and
+// an rr_bank_search_plaid_ivf call (8: all) runs; below it the outputs are not written: tools/bench_bank_search_plaid.py times the
+// stages by difference.  Diagnostic switches, set between calls (as g_op_dt).
+static const int g_plaid_stages[2] = {RR_PLAID_SEARCH_STAGES, RR_PLAID_IVF_SEARCH_STAGES};
+static int g_plaid_stop_after[2] = {RR_PLAID_SEARCH_STAGES - 1, RR_PLAID_IVF_SEARCH_STAGES - 1};
+static int set_plaid_stop_after(bool ivf, int value) {
+  if (value < 0 || value >= g_plaid_stages[ivf]) return RR_ERR_BAD_ARG;
+  g_plaid_stop_after[ivf] = value;
+  return RR_OK;
+}
 
 // what rr_bank_search_plaid and rr_op_bank_search_plaid refuse alike, in the order the header gives; msg: the sentence for the handle
 static int plaid_search_limits(int n_centroids, int n, int Lq, int Lq_coarse, int ncells, int ndocs, int k, const char** msg) {
@@ -3179,8 +3184,36 @@ static int plaid_search_limits(int n_centroids, int n, int Lq, int Lq_coarse, in
   return RR_OK;
 }
 
-// rr_bank_search_plaid (include/rerank_mi355.h): the block, and the eight stages of bank_search_plaid.hip, each booked on its own.
-// ivf: rr_bank_search_plaid_ivf, the same checks, one more refusal, and the nine stages that read the bank's inverted file
+// What the stages of a pruned search (bank_search_plaid.hip) are booked with: flops / bytes [l.stages]; rows: the rows of the range.
+// FLOPs: stage 0 exactly; the exact scores for ndocs / 4 survivors of the range's mean length (their number is known on the device
+// only: an upper bound).  Bytes: what a stage must read and write once.
+static void plaid_search_costs(const rr_plaid_search_args& a, const rr_plaid_search_layout& l, double rows, double* flops, double* bytes) {
+  const int n = a.n, Lq = a.Lq, D = a.D;
+  const double nq = a.nq, C = l.Cp, SLq = 4.0 * a.Lqc, cap = l.cap, pitch = l.pitch;
+  std::fill(flops, flops + l.stages, 0.0);
+  flops[0] = 2.0 * nq * C * Lq * D;
+  bytes[0] = 2.0 * C * D + nq * (4.0 * Lq * D + 4.0 * C * Lq);
+  bytes[1] = nq * C * SLq * std::min(a.ncells, 2);
+  bytes[2] = nq * C * SLq;
+  int s = 3;
+  if (l.stages == RR_PLAID_IVF_SEARCH_STAGES) {
+    // the candidate step clears, sets and reads a bitmap of the range per query and writes the lists and the -inf behind them (the
+    // postings it reads are known on the device only); the listed scores read about 5 bytes per row of a candidate (at most cap of
+    // them: an upper bound)
+    bytes[s++] = nq * (n / 8.0 * 3.0 + 12.0 * cap);
+    bytes[s++] = nq * cap * (5.0 * (rows / n) + 28.0);
+  } else {
+    bytes[s++] = 5.0 * rows + 16.0 * n + 8.0 * nq * n;      // the scan's candidates add a row of S per unmasked row
+  }
+  bytes[s++] = 12.0 * nq * pitch;                            // the selection reads the A1 row
+  bytes[s++] = 16.0 * nq * l.k1;
+  flops[s] = 2.0 * nq * l.k2 * (rows / n) * Lq * D;
+  bytes[s++] = nq * l.k2 * (rows / n) * (rr_bank_row_bytes(a.bank, D) + 1.0);
+  bytes[s++] = 16.0 * nq * l.k2;
+}
+
+// rr_bank_search_plaid (include/rerank_mi355.h): the block, and the stages of bank_search_plaid.hip, each booked on its own.
+// ivf: rr_bank_search_plaid_ivf, the same checks, one more refusal, and the plan that reads the bank's inverted file
 static int bank_search_plaid_call(rr_handle h, bool ivf, rr_bank* b, const float* query_li, int n_queries, int Lq, int Lq_coarse,
                                   int32_t first_passage, int32_t n_passages, int ncells, float threshold, int ndocs, int k, int32_t* indices_out,
                                   float* scores_out, int32_t* counts_out, void* hip_stream) {
@@ -3205,38 +3238,20 @@ static int bank_search_plaid_call(rr_handle h, bool ivf, rr_bank* b, const float
                              return (int)RR_OK;
                            }));
   const int D = m->cfg.li_dim;
-  const rr_plaid_search_layout l = ivf ? rr_plaid_ivf_search_plan(n_queries, n, b->n_centroids, Lq, Lq_coarse, ncells, ndocs, b->ivf.longest)
-                                       : rr_plaid_search_plan(n_queries, n, b->n_centroids, Lq, Lq_coarse, ncells, ndocs);
+  // (a file none of whose lists has an entry still takes the inverted-file form: its rows are one entry wide at the least)
+  const rr_plaid_search_layout l = rr_plaid_search_plan(n_queries, n, b->n_centroids, Lq, Lq_coarse, ncells, ndocs,
+                                                        ivf ? std::max(b->ivf.longest, 1) : 0);
   m->plaid_last_ok = false;
   RR_TRY(ensure_block(m, m->search_blk, m->search_blk_cap, l.total, st, "the bank search's block"));
   m->last_stream = st;
   const rr_plaid_search_args a{n_queries, n, first_passage, Lq, Lq_coarse, D, ncells, ndocs, k, threshold, query_li, b->table + first_passage,
                                bank_view(b), m->search_blk, indices_out, scores_out, counts_out, ivf ? b->ivf : rr_ivf{}};
-  const double nq = n_queries, C = l.Cp, SLq = 4.0 * Lq_coarse;
-  if (ivf) {
-    // Bytes: the candidate step clears, sets and reads a bitmap of the range per query and writes the lists and the -inf behind
-    // them (the postings it reads are known on the device only); the listed scores read about 5 bytes per row of a candidate
-    // (at most cap of them: an upper bound); the selection reads the compact row.
-    const double cap = l.cap;
-    const double flops[RR_PLAID_IVF_SEARCH_STAGES] = {2.0 * nq * C * Lq * D, 0, 0, 0, 0, 0, 0, 2.0 * nq * l.k2 * (rows / n) * Lq * D, 0};
-    const double bytes[RR_PLAID_IVF_SEARCH_STAGES] = {2.0 * C * D + nq * (4.0 * Lq * D + 4.0 * C * Lq), nq * C * SLq * std::min(ncells, 2), nq * C * SLq,
-                                                      nq * (n / 8.0 * 3.0 + 12.0 * cap), nq * cap * (5.0 * (rows / n) + 28.0), 12.0 * nq * cap,
-                                                      16.0 * nq * l.k1, nq * l.k2 * (rows / n) * (rr_bank_row_bytes(a.bank, D) + 1.0),
-                                                      16.0 * nq * l.k2};
-    const int stop = g_plaid_ivf_stop_after;
-    for (int s = 0; s < RR_PLAID_IVF_SEARCH_STAGES && s <= stop; ++s)
-      RR_RUN(m, st, RR_K_TAIL, flops[s], bytes[s], rr_launch_plaid_ivf_search_stage(s, a, l, st));
-    return RR_OK;                                   // (no tap: plaid_last_ok stays false)
-  }
-  // FLOPs: stage 0 exactly; stage 6 for ndocs / 4 survivors of the range's mean length (their number is known on the device only:
-  // an upper bound).  Bytes: what a stage must read and write once; the scan's candidates add a row of S per unmasked row.
-  const double flops[RR_PLAID_SEARCH_STAGES] = {2.0 * nq * C * Lq * D, 0, 0, 0, 0, 0, 2.0 * nq * l.k2 * (rows / n) * Lq * D, 0};
-  const double bytes[RR_PLAID_SEARCH_STAGES] = {2.0 * C * D + nq * (4.0 * Lq * D + 4.0 * C * Lq), nq * C * SLq * std::min(ncells, 2), nq * C * SLq,
-                                                5.0 * rows + 16.0 * n + 8.0 * nq * n, 12.0 * nq * n, 16.0 * nq * l.k1,
-                                                nq * l.k2 * (rows / n) * (rr_bank_row_bytes(a.bank, D) + 1.0), 16.0 * nq * l.k2};
-  const int stop = g_plaid_stop_after;
-  for (int s = 0; s < RR_PLAID_SEARCH_STAGES && s <= stop; ++s)
+  double flops[RR_PLAID_IVF_SEARCH_STAGES], bytes[RR_PLAID_IVF_SEARCH_STAGES];
+  plaid_search_costs(a, l, rows, flops, bytes);
+  const int stop = g_plaid_stop_after[ivf];
+  for (int s = 0; s < l.stages && s <= stop; ++s)
     RR_RUN(m, st, RR_K_TAIL, flops[s], bytes[s], rr_launch_plaid_search_stage(s, a, l, st));
+  if (ivf) return RR_OK;                            // (no tap: plaid_last_ok stays false)
   m->plaid_last = a;
   m->plaid_last_layout = l;
   m->plaid_last_ok = true;
@@ -3313,14 +3328,14 @@ static int rr_op_bank_search_plaid_impl(const float* query_li, int n_queries, in
   const char* msg;
   if (const int rc = plaid_search_limits(n_centroids, n_passages, Lq, Lq_coarse, ncells, ndocs, k, &msg)) return rc;
   hipStream_t st = (hipStream_t)hip_stream;
-  const rr_plaid_search_layout l = rr_plaid_search_plan(n_queries, n_passages, n_centroids, Lq, Lq_coarse, ncells, ndocs);
+  const rr_plaid_search_layout l = rr_plaid_search_plan(n_queries, n_passages, n_centroids, Lq, Lq_coarse, ncells, ndocs, 0);
   char* blk = nullptr;
   if (hipMalloc((void**)&blk, l.total) != hipSuccess) { (void)hipGetLastError(); return RR_ERR_OOM; }
   const rr_bank_view bank{nbits, n_centroids, nullptr, codes, residuals, centroids_f16, bucket_weights, mask_bytes};
   const rr_plaid_search_args a{n_queries, n_passages, first_passage, Lq, Lq_coarse, D, ncells, ndocs, k, threshold, query_li,
                                (const rr_bank_slot*)table + first_passage, bank, blk, indices_out, scores_out, counts_out};
   int rc = RR_OK;
-  for (int s = 0; s < RR_PLAID_SEARCH_STAGES && rc == RR_OK; ++s)
+  for (int s = 0; s < l.stages && rc == RR_OK; ++s)
     if (rr_launch_plaid_search_stage(s, a, l, st) != hipSuccess) rc = RR_ERR_HIP;
   if (hipStreamSynchronize(st) != hipSuccess && rc == RR_OK) rc = RR_ERR_HIP;
   (void)hipFree(blk);
@@ -3458,16 +3473,8 @@ int rr_set_tuning(const char* key, int value) {
   if (!strcmp(key, "compress_chunk")) return rr_set_compress_chunk(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
   if (!strcmp(key, "compress_stop_after")) return rr_set_compress_stop_after(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
   if (!strcmp(key, "kmeans_stop_after")) return rr_set_kmeans_stop_after(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
-  if (!strcmp(key, "plaid_stop_after")) {
-    if (value < 0 || value >= RR_PLAID_SEARCH_STAGES) return RR_ERR_BAD_ARG;
-    g_plaid_stop_after = value;
-    return RR_OK;
-  }
-  if (!strcmp(key, "plaid_ivf_stop_after")) {
-    if (value < 0 || value >= RR_PLAID_IVF_SEARCH_STAGES) return RR_ERR_BAD_ARG;
-    g_plaid_ivf_stop_after = value;
-    return RR_OK;
-  }
+  if (!strcmp(key, "plaid_stop_after")) return set_plaid_stop_after(false, value);
+  if (!strcmp(key, "plaid_ivf_stop_after")) return set_plaid_stop_after(true, value);
   if (!strcmp(key, "attn_prio")) return rr_set_attn_prio(value);
   if (!strcmp(key, "attn_fixed_ref")) return rr_set_attn_fixed_ref(value);
   return RR_ERR_BAD_ARG;

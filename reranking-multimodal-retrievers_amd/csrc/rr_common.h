@@ -485,15 +485,12 @@ hipError_t rr_launch_bank_li_scores(const rr_bank_pair* pairs, const int32_t* sl
 hipError_t rr_launch_bank_search_scores(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
                                         const rr_bank_view& bank, float* out, hipStream_t st);
 // the same for the passages list[q][0 .. cnt[q]) of every query (cnt[q] <= list_ld; entries of table[0 .. n)), written to the
-// passage's entry of the dense out [nq][n]; compressed banks only
+// passage's entry of the dense out [nq][n]; compressed banks only.  With cand (cap > 0; or null and 0) for the passages
+// cand[q][list[q][i]], i < cnt[q]: a list entry is a PLACE in the query's candidate list cand [nq][cap] (entries of table[0 .. n)),
+// and the score goes to that place of the compact out [nq][cap] (rr_bank_search_plaid_ivf)
 hipError_t rr_launch_bank_search_scores_listed(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
-                                               const rr_bank_view& bank, const int32_t* list, int list_ld, const int32_t* cnt, float* out,
-                                               hipStream_t st);
-// ... and for the passages cand[q][list[q][i]], i < cnt[q]: a list entry is a PLACE in the query's candidate list cand [nq][cap]
-// (entries of table[0 .. n)), and the score goes to that place of the compact out [nq][cap] (rr_bank_search_plaid_ivf)
-hipError_t rr_launch_bank_search_scores_via(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
-                                            const rr_bank_view& bank, const int32_t* list, int list_ld, const int32_t* cnt,
-                                            const int32_t* cand, int cap, float* out, hipStream_t st);
+                                               const rr_bank_view& bank, const int32_t* list, int list_ld, const int32_t* cnt,
+                                               const int32_t* cand, int cap, float* out, hipStream_t st);
 size_t rr_topk_select_scratch(int n_lists, int n, int k);
 hipError_t rr_launch_topk_select(const float* scores, int n_lists, int n, int k, int add, int32_t* tmp_a, int32_t* tmp_b,
                                  int32_t* indices_out, float* scores_out, hipStream_t st);
@@ -514,10 +511,15 @@ int64_t rr_ivf_host(const int32_t* codes, const uint8_t* mask, const int32_t* le
 // [nq][cap]; bm [nq][Wn], Wn = ceil(n / 32): scratch
 hipError_t rr_launch_ivf_candidates(const rr_ivf& f, int C, const int32_t* cells, int E, int nq, int first, int n, uint32_t* bm, int Wn,
                                     int32_t* cand, int cap, int32_t* ccnt, float* a1, float* a2, hipStream_t st);
-// rr_bank_search_plaid (bank_search_plaid.hip): the staged, centroid-pruned search over a compressed bank.  The arguments of a call
-// as its eight stages take them (table: the first passage of the range; indices + first), where the intermediates of the call lie
-// in `scratch` (byte offsets, 16-byte aligned; rr_plaid_search_plan), and one launcher per stage so that a caller can book each.
+// rr_bank_search_plaid and rr_bank_search_plaid_ivf (bank_search_plaid.hip): the staged, centroid-pruned search over a compressed
+// bank.  The arguments of a call as its stages take them (table: the first passage of the range; indices + first), where the
+// intermediates of the call lie in `scratch` (byte offsets, 16-byte aligned; rr_plaid_search_plan), and one launcher that runs one
+// stage so that a caller can book each.  Eight stages with the candidates from a scan of the range: 0 - 2 the head, 3 the scan,
+// 4 - 7 the tail.  Nine from the bank's inverted file: 0 - 2 the head, 3 the candidate lists (bank_ivf.hip), 4 A1 / A2 of the listed
+// candidates into compact rows [nq][cap], 5 - 8 the tail over the compact rows, its last stage mapping a place in the candidate
+// list back to its passage.
 constexpr int RR_PLAID_SEARCH_STAGES = 8;
+constexpr int RR_PLAID_IVF_SEARCH_STAGES = 9;
 constexpr int RR_PLAID_SEARCH_MAX_CENTROIDS = 1 << 18;      // two bitmaps of a query in the scan's LDS: 64 KB
 struct rr_plaid_search_args {
   int nq, n, first, Lq, Lqc, D, ncells, ndocs, k;
@@ -532,21 +534,18 @@ struct rr_plaid_search_args {
   rr_ivf ivf;                 // rr_bank_search_plaid_ivf alone: the bank's inverted file
 };
 struct rr_plaid_search_layout {
+  int stages;                 // RR_PLAID_SEARCH_STAGES or RR_PLAID_IVF_SEARCH_STAGES: which form the plan is for
   int Cp, W, k1, k2;          // centroids rounded up to 64; words of a bitmap; entries of a stage-1 / stage-2 list
+  int pitch;                  // entries of a query's row of a1 / a2: n, or cap
   size_t S, pairs, ones, cells, cellbits, keepbits, a1, a2, list1, list2, cnt2, tmp_a, tmp_b, tmp_entries, total;
-  // rr_bank_search_plaid_ivf alone (rr_plaid_ivf_search_plan): entries of a candidate list and of a compact score row; words of a
-  // query's bitmap over the range; the bitmaps, the candidate lists and their counts
+  // the inverted-file form alone (0 in the scan form): entries of a candidate list and of a compact score row; words of a query's
+  // bitmap over the range; the bitmaps, the candidate lists and their counts
   int cap, Wn;
   size_t bm, cand, ccnt;
 };
-rr_plaid_search_layout rr_plaid_search_plan(int nq, int n, int C, int Lq, int Lqc, int ncells, int ndocs);
+// longest: 0 for the scan form, the longest list of the bank's inverted file (> 0) for the inverted-file form
+rr_plaid_search_layout rr_plaid_search_plan(int nq, int n, int C, int Lq, int Lqc, int ncells, int ndocs, int longest);
 hipError_t rr_launch_plaid_search_stage(int stage, const rr_plaid_search_args& a, const rr_plaid_search_layout& l, hipStream_t st);
-// rr_bank_search_plaid_ivf: nine stages.  0 - 2 are those above; 3 candidates (bank_ivf.hip), 4 A1 / A2 of the listed candidates
-// into compact rows [nq][cap], 5 the selection over the compact A1 row, 6 - 8 are 5 - 7 above over the compact rows, the last one
-// mapping a place in the candidate list back to its passage.  longest: the longest list of the file.
-constexpr int RR_PLAID_IVF_SEARCH_STAGES = 9;
-rr_plaid_search_layout rr_plaid_ivf_search_plan(int nq, int n, int C, int Lq, int Lqc, int ncells, int ndocs, int longest);
-hipError_t rr_launch_plaid_ivf_search_stage(int stage, const rr_plaid_search_args& a, const rr_plaid_search_layout& l, hipStream_t st);
 bool rr_plaid_prune_host(const float* S, int C, int Lqc, int s_ld, const int32_t* codes, const uint8_t* mask, const int32_t* lengths,
                          int n, int ncells, float thr, int ndocs, uint8_t* cells_out, float* a1_out, float* a2_out, int32_t* list1_out,
                          int32_t* n1_out, int32_t* list2_out, int32_t* n2_out);

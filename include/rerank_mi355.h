@@ -755,7 +755,7 @@ int rr_bank_li_scores(rr_handle h, rr_bank_handle b, const float* query_li, int 
  * non-positive sizes, a range that is empty or not inside the bank, k < 1 or k > n_passages (RR_ERR_BAD_SHAPE).
  * LIMITS: k <= 1024; not capturable into a graph (RR_ERR_BAD_ARG under stream capture: the call may upload the table and grow
  * its block); one device (no merge across ranks: search ranges and merge the k-lists yourself); every passage of the range competes (restrict
- * by range, or prune by centroid with rr_bank_search_plaid; no caller-supplied candidate filter).  (Python: RerankEngine.bank_search, PassageBank.search,
+ * by range, by a candidate filter with rr_bank_search_filtered below, or prune by centroid with rr_bank_search_plaid).  (Python: RerankEngine.bank_search, PassageBank.search,
  * InteractionRerankModel.retrieve / retrieve_and_rerank.) */
 int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage,
                    int32_t n_passages, int k, int32_t* indices_out, float* scores_out, void* hip_stream);
@@ -801,8 +801,8 @@ int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_q
  * k2 = min(ndocs / 4, n): 4 nq Cp Lq + 16 nq Cp / 64 + Cp + 4 nq Lq_coarse ncells + 8 nq W + 8 nq n + 4 nq (k1 + k2 + 1)
  * + 8 * (n > 4096 ? nq ceil(n / 4096) k1 : 0) bytes.
  * Checked on the host BEFORE anything is enqueued; a refused call writes nothing.  Not capturable into a graph (RR_ERR_BAD_ARG).
- * Out of scope: ndocs > 1024, merging across ranks, a caller-supplied filter, fp16 banks; candidates from an IVF:
- * rr_bank_build_ivf / rr_bank_search_plaid_ivf below.  (Python:
+ * Out of scope: ndocs > 1024, merging across ranks, fp16 banks.  A caller-supplied candidate filter: rr_bank_search_plaid_filtered
+ * below; candidates from an IVF: rr_bank_build_ivf / rr_bank_search_plaid_ivf below.  (Python:
  * RerankEngine.bank_search_plaid, PlaidSearch with PassageBank.search / InteractionRerankModel.retrieve / retrieve_and_rerank.) */
 int rr_bank_search_plaid(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse,
                          int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k,
@@ -849,7 +849,7 @@ int rr_bank_search_plaid(rr_handle h, rr_bank_handle b, const float* query_li, i
  * bytes: with cap <= n never more than rr_bank_search_plaid's but for the bitmap and the candidate list (8 nq n against
  * 4 nq (n / 32 + 3 cap)).  Ten launches, a memset and the selection passes, booked in the profile's `tail` class.
  * LIMITS: those of rr_bank_search_plaid (ndocs <= 1024, one device, compressed banks); rr_bank_search_plaid_tap does not cover
- * this entry.  (Python: RerankEngine.bank_build_ivf / bank_search_plaid_ivf, PassageBank.build_ivf / ivf / save_ivf,
+ * this entry.  Under a candidate filter: rr_bank_search_plaid_ivf_filtered below.  (Python: RerankEngine.bank_build_ivf / bank_search_plaid_ivf, PassageBank.build_ivf / ivf / save_ivf,
  * PlaidSearch(..., ivf=True).) */
 int rr_bank_build_ivf(rr_bank_handle b, void* hip_stream);
 int rr_bank_ivf_info(rr_bank_handle b, int32_t* passages_covered_out, int64_t* postings_out, int32_t* longest_list_out);
@@ -857,6 +857,75 @@ int rr_bank_ivf_read(rr_bank_handle b, int64_t* offsets_host_out, int32_t* pids_
 int rr_bank_search_plaid_ivf(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse,
                              int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k,
                              int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream);
+
+/* CANDIDATE FILTERS: the three searches restricted to a caller's set of passages per query (the reference: filter_fn of
+ * Searcher.search / search_all / dense_search, third_party/ColBERT/colbert/searcher.py:68-134, applied by IndexScorer.rank between
+ * candidate generation and the pruning stages, colbert/search/index_storage.py:86-93).  A passage outside the set is never a
+ * candidate and costs no scoring work.
+ * THE FILTER: filter_bits, DEVICE uint32 [filter_rows][filter_ld], 4-byte aligned.  Bit (i & 31) of word (i >> 5) of a row stands
+ * for bank index i: ABSOLUTE, not relative to the range, so one filter serves any range and a rank searching its slice does not
+ * shift it.  filter_rows is 1 (one set for every query) or n_queries (row q for query q); anything else: RR_ERR_BAD_SHAPE.
+ * filter_ld >= ceil((first_passage + n_passages) / 32), else RR_ERR_BAD_SHAPE.  A NULL or misaligned filter_bits: RR_ERR_BAD_ARG
+ * (the unfiltered entries exist for "no filter").  Bits of indices outside [first_passage, first_passage + n_passages) are never
+ * consulted, set bits beyond the bank's passage count in the last word included.  The filter is read by the kernels of the call:
+ * it must stay unchanged until the call has completed on hip_stream.
+ * Each entry keeps the checks, refusals, check order, graph-capture refusal and the "a refused call writes nothing" rule of its
+ * unfiltered entry (its name in rr_last_error aside); the filter checks above come behind that entry's other refusals.
+ *
+ * rr_bank_search_filtered: rr_bank_search over the passages of the range whose bit is set.  A competitor's score is bit for bit
+ * rr_bank_search's, the order rr_bank_search's one order.  -inf means absent, as in the pruned search: a competitor whose exact
+ * score is a genuine -inf counts as absent.  counts_out int32 [n_queries] (DEVICE, required; NULL: RR_ERR_BAD_ARG) gets the number
+ * of real entries of a query, at most k; behind it indices_out holds -1 and scores_out -inf.  1 <= k <= min(n_passages, 1024) as
+ * rr_bank_search has it; k may exceed the number of allowed passages.  PROPERTY: with every bit of the range set, indices_out and
+ * scores_out are rr_bank_search's and every count is k (where no score is -inf).
+ * The scoring kernel of rr_bank_search with one more picker (csrc/bank_search.hip): a workgroup none of whose chunk's passages is
+ * allowed writes its -inf entries and ends before it stages its query block; a wave whose passage has a clear bit writes -inf,
+ * reads no row of the bank and issues no matrix instruction; the bit is a scalar load.  Then rr_bank_search's selection passes over
+ * the dense row, unchanged, and one pass of the pruned search's list kernel over their k survivors, which drops the absent, writes
+ * the tail and counts.  The block grows by 4 n_queries k bytes over rr_bank_search's.
+ * LIMIT: the selection still walks the dense row of n_passages scores per query, however few bits are set, and there is no
+ * list-driven exact form: for a filter of a few thousand passages rr_bank_li_scores over the explicit pair list and a top-k of its
+ * maxsim_out remains the cheaper route.
+ *
+ * rr_bank_search_plaid_filtered: rr_bank_search_plaid with CANDIDATES read as: the passage's bit is set AND at least one of its
+ * unmasked rows has a code in the cell set.  Stages 0 to 3 and OUTPUT are otherwise word for word rr_bank_search_plaid's.
+ * PROPERTY A: with every bit of the range set, the result is the bytes of rr_bank_search_plaid.  PROPERTY B: the result is the
+ * bytes of rr_bank_search_plaid on a bank that differs only in that every row of a filtered-out passage is masked; with a filter
+ * row per query this holds query by query.  The scan decides a clear bit before it reads the passage's table entry, codes or mask
+ * bytes: a filtered-out passage costs one bit and its two -inf, not 5 bytes per row.  No scratch beyond rr_bank_search_plaid's;
+ * rr_bank_search_plaid_tap covers this entry.
+ *
+ * rr_bank_search_plaid_ivf_filtered: the bytes of rr_bank_search_plaid_filtered, with the candidates from the bank's inverted
+ * file; the one refusal rr_bank_search_plaid_ivf adds stands in the same place, in front of the filter checks.  The per-query
+ * bitmap of the candidate step is ANDed with the filter's bits of the range as it is compacted (a range that does not start at a
+ * multiple of 32 takes a bitmap word's bits from two filter words); cap and the layout of the block stay rr_bank_search_plaid_ivf's.
+ *
+ * rr_bank_filter_fill writes a filter for bank `b` from HOST index lists: row r of filter_bits (DEVICE uint32 [rows][filter_ld],
+ * 4-byte aligned) gets the bank indices indices_host[offsets_host[r] .. offsets_host[r + 1]), offsets_host int64 [rows + 1] from
+ * 0, ascending; duplicates are allowed, a row may be empty.  exclude == 0: exactly those bits are set.  exclude != 0: every bit
+ * 0 .. passages - 1 is set except those (passages: what the bank holds now).  Bits at or beyond `passages`, up to filter_ld words,
+ * are zero in both modes.  An index outside [0, passages), offsets that do not start at 0 or descend, rows outside 1 .. 65535, an
+ * empty bank or filter_ld < ceil(passages / 32): RR_ERR_BAD_SHAPE, and nothing is written; NULL or misaligned pointers, a
+ * capturing stream: RR_ERR_BAD_ARG.  The lists are staged as rr_bank_add stages its descriptors (the bank's pinned slot pair, one
+ * asynchronous copy) and one kernel writes the bits (csrc/bank_ivf.hip: a workgroup per row fills its words, then clears or sets
+ * the listed bits with 32-bit vector atomicAnd / atomicOr; an AND or an OR has one result, so the bytes do not depend on
+ * scheduling).  Errors: rr_bank_last_error.  In host code: rr_util_bank_filter_bits (rerank_mi355_diag.h).  A filter describes
+ * the bank it was filled for: passages added later have clear bits under exclude == 0 and under exclude != 0 alike.
+ * (Python: RerankEngine.bank_search_filtered / bank_search_plaid_filtered / bank_search_plaid_ivf_filtered, PassageBank.filter,
+ * PassageBank.search(filter=), InteractionRerankModel.retrieve / retrieve_and_rerank(allowed=, excluded=, filter=).) */
+int rr_bank_search_filtered(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage,
+                            int32_t n_passages, int k, const uint32_t* filter_bits, int filter_rows, int64_t filter_ld,
+                            int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream);
+int rr_bank_search_plaid_filtered(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse,
+                                  int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k,
+                                  const uint32_t* filter_bits, int filter_rows, int64_t filter_ld, int32_t* indices_out,
+                                  float* scores_out, int32_t* counts_out, void* hip_stream);
+int rr_bank_search_plaid_ivf_filtered(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse,
+                                      int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs,
+                                      int k, const uint32_t* filter_bits, int filter_rows, int64_t filter_ld, int32_t* indices_out,
+                                      float* scores_out, int32_t* counts_out, void* hip_stream);
+int rr_bank_filter_fill(rr_bank_handle b, const int32_t* indices_host, const int64_t* offsets_host, int rows, int exclude,
+                        uint32_t* filter_bits, int64_t filter_ld, void* hip_stream);
 
 /* rr_head_joint: rr_head with the head RerankModel.forward runs (rr_forward_joint): `loss_fn(logits, logits)`
  * (rerank_model.py:328) — the labels are the logits themselves (2H_BCE: the two heads as class-probability targets).  The

@@ -354,7 +354,13 @@ int rr_op_topk_select(const float* scores, int n_lists, int n, int k, int32_t* i
  * rr_bank_build_ivf is held to.  codes int32 / mask uint8 (NULL: all ones) over the rows of the n_passages passages back to back,
  * lengths int32 [n_passages] (each >= 1); codes are clamped into [0, n_centroids).  offsets_out int64 [n_centroids + 1] is always
  * written and *postings_out (or NULL) gets offsets_out[n_centroids]; pids_out (or NULL, to size it first) holds room for
- * pids_capacity entries: RR_ERR_BAD_SHAPE, with pids_out untouched, when the postings do not fit. */
+ * pids_capacity entries: RR_ERR_BAD_SHAPE, with pids_out untouched, when the postings do not fit.
+ * rr_bank_search_plaid_tap covers rr_bank_search_plaid_filtered as it covers rr_bank_search_plaid ("a1": -inf for a passage the
+ * filter removed as for any other non-candidate).
+ * rr_util_bank_filter_bits: the bitmap rr_bank_filter_fill (rerank_mi355.h, "CANDIDATE FILTERS") writes, in pure HOST code, usable
+ * without a GPU: bits_out uint32 [rows][filter_ld] in host memory for a bank of `passages` passages, from indices int32 and offsets
+ * int64 [rows + 1] as that call takes them.  RR_ERR_BAD_SHAPE, with bits_out untouched, for an index outside [0, passages), offsets
+ * that do not start at 0 or descend, passages < 1, rows < 1 or filter_ld < ceil(passages / 32). */
 int rr_op_bank_search_plaid(const float* query_li, int n_queries, int Lq, int Lq_coarse, int D, const void* table, int32_t first_passage,
                             int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k, const uint8_t* mask_bytes,
                             int nbits, const int32_t* codes, const uint8_t* residuals, const uint16_t* centroids_f16,
@@ -367,6 +373,8 @@ int rr_util_plaid_prune(const float* S, int32_t n_centroids, int Lq_coarse, cons
                         int32_t* n2_out);
 int rr_util_plaid_ivf(const int32_t* codes, const uint8_t* mask, const int32_t* lengths, int32_t n_passages, int32_t n_centroids,
                       int64_t* offsets_out, int32_t* pids_out, int64_t pids_capacity, int64_t* postings_out);
+int rr_util_bank_filter_bits(const int32_t* indices, const int64_t* offsets, int rows, int exclude, int32_t passages,
+                             uint32_t* bits_out, int64_t filter_ld);
 #ifdef __cplusplus
 }
 #endif

@@ -19,7 +19,13 @@
 // workgroup per (query, cell entry); an entry that repeats an earlier one of its query ends at once) ORs in the passages of the
 // cell's list that lie inside the range (found by two binary searches: the list is sorted), and ivf_compact_kernel turns every
 // bitmap into the ascending candidate list [nq][cap] with its count and writes -inf behind the count into the two compact score
-// rows.  Sets and sorted lists only: nothing depends on scheduling.
+// rows.  Sets and sorted lists only: nothing depends on scheduling.  Under a caller's filter (rr_bank_search_plaid_ivf_filtered)
+// the compaction ANDs every word it reads with the filter's bits of those passages: the filter is indexed by bank index and the
+// bitmap starts at the range's first passage, so a word takes its bits from two filter words when that is no multiple of 32
+// (rr_passage_filter::range_word).  No launch more.
+// rr_launch_filter_fill (rr_bank_filter_fill): filter_fill_kernel, a workgroup per row, writes the row's words (zeros, or ones below
+// the passage count), meets at a barrier and then clears or sets the bits of the row's list with vector atomicAnd / atomicOr: an AND
+// or an OR has one result.  rr_filter_bits_host restates it (rr_util_bank_filter_bits).
 // ivf_compact_kernel: ONE workgroup of 1024 per bitmap walks it 1024 words a time: a popcount per word, an inclusive scan over the
 // workgroup (wave shuffles, the sixteen wave totals through LDS), and every thread writes the bits of its word from its place on.
 // rr_ivf_host restates the definition in host code (rr_util_plaid_ivf).
@@ -181,10 +187,12 @@ __global__ __launch_bounds__(256) void ivf_candidates_kernel(const int32_t* __re
 }
 
 // Workgroup q: the set bits of bm[q][0 .. Wn) in ascending order, bit + add, to out[q * out_ld ...] (at most cap of them), their
-// number to cnt_out[q]; fill_a / fill_b (or null) [nq][cap] get -inf behind the count.
+// number to cnt_out[q]; fill_a / fill_b (or null) [nq][cap] get -inf behind the count.  filter.bits given: a word is ANDed with the
+// filter's bits of its passages (n: the passages of the range) as it is read.
 __global__ __launch_bounds__(IVF_COMPACT_THREADS) void ivf_compact_kernel(const uint32_t* __restrict__ bm, int Wn, int32_t* __restrict__ out,
                                                                           long long out_ld, int cap, int32_t* __restrict__ cnt_out, int add,
-                                                                          float* __restrict__ fill_a, float* __restrict__ fill_b) {
+                                                                          float* __restrict__ fill_a, float* __restrict__ fill_b,
+                                                                          const rr_passage_filter filter, int n) {
   __shared__ int wtot[2][16];
   const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t* row = bm + (size_t)q * Wn;
@@ -194,6 +202,7 @@ __global__ __launch_bounds__(IVF_COMPACT_THREADS) void ivf_compact_kernel(const 
   for (int w0 = 0; w0 < Wn; w0 += IVF_COMPACT_THREADS, round ^= 1) {
     const int w = w0 + tid;
     uint32_t word = w < Wn ? row[w] : 0u;
+    if (filter.bits && word) word &= filter.range_word(q, w, n);
     const int pc = __popc(word);
     int incl = pc;
 #pragma unroll
@@ -226,7 +235,54 @@ __global__ __launch_bounds__(IVF_COMPACT_THREADS) void ivf_compact_kernel(const 
     }
 }
 
+// Workgroup r: row r of bits [rows][ld] from the indices[offsets[r] .. offsets[r + 1]) (inside [0, passages): checked on the host)
+__global__ __launch_bounds__(1024) void filter_fill_kernel(const int64_t* __restrict__ offsets, const int32_t* __restrict__ indices, int exclude,
+                                                           int passages, uint32_t* __restrict__ bits, long long ld) {
+  uint32_t* row = bits + (size_t)blockIdx.x * ld;
+  for (long long w = threadIdx.x; w < ld; w += 1024) {
+    uint32_t v = 0u;
+    if (exclude && w * 32 < passages) v = passages - w * 32 >= 32 ? 0xffffffffu : (1u << (passages - w * 32)) - 1u;
+    row[w] = v;
+  }
+  __syncthreads();                                            // the row is this workgroup's alone
+  for (int64_t i = offsets[blockIdx.x] + threadIdx.x; i < offsets[blockIdx.x + 1]; i += 1024) {
+    const int p = indices[i];
+    if (p < 0 || p >= passages) continue;
+    if (exclude) atomicAnd(&row[p >> 5], ~(1u << (p & 31)));
+    else atomicOr(&row[p >> 5], 1u << (p & 31));
+  }
+}
+
 }  // namespace
+
+hipError_t rr_launch_filter_fill(const int64_t* offsets, const int32_t* indices, int rows, int exclude, int passages, uint32_t* bits,
+                                 long long ld, hipStream_t st) {
+  if (!offsets || !indices || !bits || rows < 1 || passages < 1 || ld < ((long long)passages + 31) / 32) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(filter_fill_kernel, dim3((unsigned)rows), dim3(1024), 0, st, offsets, indices, exclude, passages, bits, ld);
+  return hipGetLastError();
+}
+
+bool rr_filter_bits_host(const int32_t* indices, const int64_t* offsets, int rows, int exclude, int passages, uint32_t* bits, long long ld) {
+  if (rows < 1 || passages < 1 || ld < ((long long)passages + 31) / 32 || offsets[0] != 0) return false;
+  for (int r = 0; r < rows; ++r)
+    if (offsets[r + 1] < offsets[r]) return false;
+  for (int64_t i = 0; i < offsets[rows]; ++i)
+    if (indices[i] < 0 || indices[i] >= passages) return false;
+  for (int r = 0; r < rows; ++r) {
+    uint32_t* row = bits + (size_t)r * ld;
+    for (long long w = 0; w < ld; ++w) {
+      uint32_t v = 0u;
+      if (exclude && w * 32 < passages) v = passages - w * 32 >= 32 ? 0xffffffffu : (1u << (passages - w * 32)) - 1u;
+      row[w] = v;
+    }
+    for (int64_t i = offsets[r]; i < offsets[r + 1]; ++i) {
+      const int p = indices[i];
+      if (exclude) row[p >> 5] &= ~(1u << (p & 31));
+      else row[p >> 5] |= 1u << (p & 31);
+    }
+  }
+  return true;
+}
 
 void rr_ivf_free(rr_ivf* f) {
   if (f->offsets) (void)hipFree(f->offsets);
@@ -285,7 +341,7 @@ hipError_t rr_ivf_build(const rr_bank_view& bank, const int64_t* first, const in
         const unsigned blocks = (unsigned)std::min<int64_t>((cnt + 255) / 256, 4096);
         hipLaunchKernelGGL(ivf_list_bits_kernel, dim3(blocks), dim3(256), 0, st, f.pids + off[(size_t)c], (long long)cnt, 0, P, bm);
         hipLaunchKernelGGL(ivf_compact_kernel, dim3(1), dim3(IVF_COMPACT_THREADS), 0, st, bm, (int)Wn, f.pids + off[(size_t)c], 0LL, (int)cnt,
-                           cnt_dev, 0, nullptr, nullptr);
+                           cnt_dev, 0, nullptr, nullptr, rr_passage_filter{}, P);
         ok(hipGetLastError());
       }
     }
@@ -308,7 +364,10 @@ hipError_t rr_ivf_build(const rr_bank_view& bank, const int64_t* first, const in
 // stage 3 of rr_bank_search_plaid_ivf: cand [nq][cap] ascending range-relative candidates of every query, ccnt [nq] their numbers,
 // -inf behind them in a1 / a2 [nq][cap]; bm [nq][Wn] scratch, Wn = ceil(n / 32); cells [nq][E] from stage 1
 hipError_t rr_launch_ivf_candidates(const rr_ivf& f, int C, const int32_t* cells, int E, int nq, int first, int n, uint32_t* bm, int Wn,
-                                    int32_t* cand, int cap, int32_t* ccnt, float* a1, float* a2, hipStream_t st) {
+                                    int32_t* cand, int cap, int32_t* ccnt, float* a1, float* a2, const rr_passage_filter& filter,
+                                    hipStream_t st) {
+  if (filter.bits && ((filter.rows != 1 && filter.rows != nq) || filter.first != first || filter.ld < ((long long)first + n + 31) / 32))
+    return hipErrorInvalidValue;
   if (!f.offsets || !f.pids || !cells || !bm || !cand || !ccnt || !a1 || !a2 || C < 1 || E < 1 || nq < 1 || nq > 65535 || first < 0 || n < 1 ||
       (long long)first + n > f.passages || Wn != (n + 31) / 32 || cap < 1 || cap > n)
     return hipErrorInvalidValue;
@@ -317,7 +376,8 @@ hipError_t rr_launch_ivf_candidates(const rr_ivf& f, int C, const int32_t* cells
   hipLaunchKernelGGL(ivf_candidates_kernel, dim3((unsigned)E, (unsigned)nq), dim3(256), 0, st, cells, E, C, f.offsets, f.pids, first, n, bm, Wn);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(ivf_compact_kernel, dim3((unsigned)nq), dim3(IVF_COMPACT_THREADS), 0, st, bm, Wn, cand, (long long)cap, cap, ccnt, 0, a1, a2);
+  hipLaunchKernelGGL(ivf_compact_kernel, dim3((unsigned)nq), dim3(IVF_COMPACT_THREADS), 0, st, bm, Wn, cand, (long long)cap, cap, ccnt, 0, a1, a2,
+                     filter, n);
   return hipGetLastError();
 }
 

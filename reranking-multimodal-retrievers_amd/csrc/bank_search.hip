@@ -31,7 +31,11 @@
 //     four entries of a per-query list with a count, one per wave, for the exact scores of rr_bank_search_plaid's tail
 //     (bank_search_plaid.hip), which are therefore these bits; pick_via, pick_list through the candidate list of
 //     rr_bank_search_plaid_ivf (a list entry is a place in that list, and the score goes to that place of a compact row).  The
-//     range form compiles to the instructions it had before the picker existed.
+//     range form compiles to the instructions it had before the picker existed.  pick_range_bits is pick_range under a caller's
+//     filter (rr_bank_search_filtered): a workgroup whose chunk has no set bit writes its -inf entries and ends before it stages
+//     the query block, and a wave whose passage has a clear bit writes -inf, reads no row and issues no matrix instruction.  The
+//     bit is read wave-uniformly (a scalar load of the word).  The selection (b) runs over the dense row as it is, then one
+//     plaid_list_select_kernel pass over its k survivors drops the -inf and writes the tail and the count.
 // (b) topk_select_kernel: each workgroup sorts a slice of at most 4096 (score, index) in LDS by ONE total order and keeps its
 //     first k (k <= 1024, so a pass is a strict reduction); passes repeat over the survivors until one slice is left.  The order
 //     and its 64-bit key are rank_order.h's, shared with the pruned search: keys are distinct, so the bitonic network (written out
@@ -64,10 +68,29 @@ struct pick_range {
   int chunk;
   static constexpr int PSUM = BS_CHUNK_MAX;
   static constexpr bool LISTED = false;
+  static constexpr bool FILTERED = false;
   __device__ __forceinline__ int first(int c) const { return c * chunk; }
   __device__ __forceinline__ int count(int, int p0, int n) const { return min(chunk, n - p0); }
   __device__ __forceinline__ int at(int, int p0, int i, int) const { return p0 + i; }
   __device__ __forceinline__ size_t slot(int q, int n, int p0, int i, int) const { return (size_t)q * n + p0 + i; }
+};
+// pick_range_bits: pick_range under a filter.  allowed(q, p0, i): the bit of the workgroup's passage i; any(q, p0, pn): whether one
+// of its pn passages has its bit set (the words of the chunk, at most five, their ends cut to the chunk).
+struct pick_range_bits : pick_range {
+  rr_passage_filter f;
+  static constexpr bool FILTERED = true;
+  __device__ __forceinline__ bool allowed(int q, int p0, int i) const { return f.allowed(q, p0 + i); }
+  __device__ __forceinline__ bool any(int q, int p0, int pn) const {
+    const int a = f.first + p0, b = a + pn - 1;               // the chunk's first and last bank index
+    uint32_t seen = 0u;
+    for (int w = a >> 5; w <= (b >> 5); ++w) {
+      uint32_t m = 0xffffffffu;
+      if (w == (a >> 5)) m &= 0xffffffffu << (a & 31);
+      if (w == (b >> 5)) m &= 0xffffffffu >> (31 - (b & 31));
+      seen |= f.word(q, w) & m;
+    }
+    return seen != 0u;
+  }
 };
 // pick_list: four entries, one per wave, of the first cnt[q] of list[q][0 .. list_ld) (an entry outside [0, n) is clamped); a score
 // goes to its passage's entry of the dense row out[q][.].  A workgroup behind the count has nothing to do.
@@ -77,6 +100,7 @@ struct pick_list {
   const int32_t* cnt;
   static constexpr int PSUM = 4;
   static constexpr bool LISTED = true;
+  static constexpr bool FILTERED = false;
   __device__ __forceinline__ int first(int c) const { return c * 4; }
   __device__ __forceinline__ int count(int q, int p0, int) const { return min(4, cnt[q] - p0); }
   __device__ __forceinline__ int at(int q, int p0, int i, int n) const {
@@ -94,6 +118,7 @@ struct pick_via {
   int cap;
   static constexpr int PSUM = 4;
   static constexpr bool LISTED = true;
+  static constexpr bool FILTERED = false;
   __device__ __forceinline__ int first(int c) const { return c * 4; }
   __device__ __forceinline__ int count(int q, int p0, int) const { return min(4, cnt[q] - p0); }
   __device__ __forceinline__ int place(int q, int p0, int i) const {
@@ -116,6 +141,11 @@ __global__ __launch_bounds__(256) void bank_search_scores_kernel(const float* __
   const int q = blockIdx.x % nq, p0 = pick.first(blockIdx.x / nq), pn = pick.count(q, p0, n);
   if constexpr (PICK::LISTED)
     if (pn <= 0) return;                 // the whole workgroup
+  if constexpr (PICK::FILTERED)
+    if (!pick.any(q, p0, pn)) {          // the whole workgroup: no passage of the chunk is allowed
+      for (int i = threadIdx.x; i < pn; i += 256) out[pick.slot(q, n, p0, i, 0)] = -INFINITY;
+      return;
+    }
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int li = lane & 15, g = lane >> 4;
   const float* Q = query_li + (size_t)q * Lq * D;
@@ -131,6 +161,11 @@ __global__ __launch_bounds__(256) void bank_search_scores_kernel(const float* __
     __syncthreads();
     const bool last = j0 + JB >= Lq;
     for (int i = wave; i < pn; i += 4) {                      // a passage belongs to one wave
+      if constexpr (PICK::FILTERED)
+        if (!pick.allowed(q, p0, i)) {                        // wave-uniform: the passage is not read
+          if (last && lane == 0) out[pick.slot(q, n, p0, i, 0)] = -INFINITY;
+          continue;
+        }
       const int pi = pick.at(q, p0, i, n);
       const rr_bank_slot sl = table[pi];                      // the same entry in every lane: kept in scalar registers
       const typename SRC::pair_t pr = src.of(uniform_i64(sl.first_row), __builtin_amdgcn_readfirstlane(sl.len), q, 0, D);
@@ -286,14 +321,20 @@ int rr_set_search_chunk(int passages) {
   return 0;
 }
 
-// out [nq][n]: the MaxSim of every query against the passages table[0 .. n) of a bank, fp16 or compressed (li_with_bank_source)
+// out [nq][n]: the MaxSim of every query against the passages table[0 .. n) of a bank, fp16 or compressed (li_with_bank_source);
+// under a filter (filter.bits given) -inf for a passage whose bit is clear
 hipError_t rr_launch_bank_search_scores(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
-                                        const rr_bank_view& bank, float* out, hipStream_t st) {
+                                        const rr_bank_view& bank, const rr_passage_filter& filter, float* out, hipStream_t st) {
   if (!scores_args_ok(table, n, nq, Lq, query_li, out)) return hipErrorInvalidValue;
+  if (filter.bits && ((filter.rows != 1 && filter.rows != nq) || filter.first < 0 || filter.ld < ((long long)filter.first + n + 31) / 32))
+    return hipErrorInvalidValue;
   const int chunk = g_search_chunk.load(std::memory_order_relaxed);
-  return li_with_bank_source(nullptr, nullptr, bank, D, [&](const auto& src, size_t tile_bytes) {
-    return search_launch(query_li, src, table, n, nq, ((long long)n + chunk - 1) / chunk, pick_range{chunk}, Lq, D, tile_bytes, out, st);
-  });
+  auto with = [&](const auto& pick) {    // (a dispatch per picker, as below)
+    return li_with_bank_source(nullptr, nullptr, bank, D, [&](const auto& src, size_t tile_bytes) {
+      return search_launch(query_li, src, table, n, nq, ((long long)n + chunk - 1) / chunk, pick, Lq, D, tile_bytes, out, st);
+    });
+  };
+  return !filter.bits ? with(pick_range{chunk}) : with(pick_range_bits{{chunk}, filter});
 }
 
 // the same MaxSim for the passages list[q][0 .. cnt[q]) (entries of table[0 .. n), cnt[q] <= list_ld) of every query q, written to

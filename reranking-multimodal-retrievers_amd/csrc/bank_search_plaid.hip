@@ -20,6 +20,8 @@
 //   plaid_scan_kernel, the hot path: a workgroup belongs to one query and 64 consecutive passages, holds the query's two
 //      bitmaps in LDS (C / 4 bytes) and a WAVE takes whole passages.  Lanes load 64 codes and mask bytes per step and test them
 //      against the cell bitmap; a ballot decides candidacy.  A non-candidate costs its codes and mask bytes and writes -inf.  A
+//      Under a caller's filter (FILTERED, rr_bank_search_plaid_filtered) a passage whose bit is clear is no candidate, decided
+//      before its table entry, codes or mask bytes are read: it costs one bit (a scalar load of the word) and its two -inf.  A
 //      candidate walks its unmasked rows: lane j owns column j, one row of S per code is one coalesced read (Lq_coarse * 4 bytes),
 //      the column maxima with (A1) and without (A2) the keep test are kept side by side, and the columns are summed 0, 1, ...
 //      Lq_coarse - 1 in sequence from 0.0f by constant-lane shuffles, a chain every lane carries.  Above 64 columns the passage
@@ -164,11 +166,12 @@ __device__ __forceinline__ void plaid_a1_a2(const float* __restrict__ Sq, int s_
   }
 }
 
+template <bool FILTERED>
 __global__ __launch_bounds__(256) void plaid_scan_kernel(const float* __restrict__ S, long long s_q, int s_ld, int C, int Lqc,
                                                          const uint32_t* __restrict__ cellbits, const uint32_t* __restrict__ keepbits, int W,
                                                          const int32_t* __restrict__ codes, const uint8_t* __restrict__ mask,
                                                          const rr_bank_slot* __restrict__ table, int n, int nq, float* __restrict__ a1,
-                                                         float* __restrict__ a2) {
+                                                         float* __restrict__ a2, const rr_passage_filter filter) {
   extern __shared__ uint32_t bits[];     // [W] cell set, [W] keep
   const int q = blockIdx.x % nq, p0 = (blockIdx.x / nq) * PS_CHUNK, pn = min(PS_CHUNK, n - p0);
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -179,6 +182,14 @@ __global__ __launch_bounds__(256) void plaid_scan_kernel(const float* __restrict
   __syncthreads();
   const float* Sq = S + (size_t)q * s_q;
   for (int i = wave; i < pn; i += 4) {                        // a passage belongs to one wave
+    if constexpr (FILTERED)
+      if (!filter.allowed(q, p0 + i)) {                       // wave-uniform: no candidate, and nothing of the passage is read
+        if (lane == 0) {
+          a1[(size_t)q * n + p0 + i] = -INFINITY;
+          a2[(size_t)q * n + p0 + i] = -INFINITY;
+        }
+        continue;
+      }
     const rr_bank_slot sl = table[p0 + i];
     const long long first_row = uniform_i64(sl.first_row);
     const int len = __builtin_amdgcn_readfirstlane(sl.len);
@@ -296,6 +307,14 @@ float host_nan_max(float m, float v) { return (v > m || v != v) ? v : m; }
 
 }  // namespace
 
+hipError_t rr_launch_list_select(const float* scores, long long n, int nq, const int32_t* list_in, int n_in, int keep, int32_t* list_out,
+                                 int32_t* cnt_out, int add, float* scores_out, hipStream_t st) {
+  if (!scores || !list_in || !list_out || !cnt_out || nq < 1 || n_in < 1 || n_in > LIST_MAX || keep < 1 || keep > n_in) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(plaid_list_select_kernel, dim3((unsigned)nq), dim3(256), 0, st, scores, nullptr, n, list_in, n_in, nullptr, n_in, keep, list_out,
+                     keep, cnt_out, add, scores_out, nullptr);
+  return hipGetLastError();
+}
+
 // The block of a call.  longest == 0: the scan form, score rows of n entries.  longest > 0, the longest list of the bank's inverted
 // file: the inverted-file form, with the bitmaps, the candidate lists and their counts, and score rows of cap entries: a query has
 // Lq_coarse * ncells cell entries and a list holds at most `longest` passages, and never more than the range.
@@ -346,7 +365,9 @@ hipError_t rr_launch_plaid_search_stage(int stage, const rr_plaid_search_args& a
       C > RR_PLAID_SEARCH_MAX_CENTROIDS || a.nq < 1 || a.n < 1 || a.Lqc < 1 || a.Lqc > a.Lq || a.ncells < 1 || a.ncells > std::min(C, 16) ||
       a.ndocs < 4 || a.ndocs > LIST_MAX || a.k < 1 || a.k > l.k2 || !a.indices_out || !a.counts_out ||
       (l.stages != RR_PLAID_SEARCH_STAGES && !ivf) || l.pitch != (ivf ? l.cap : a.n) || l.k1 < 1 || l.k1 > l.pitch ||
-      (ivf && (l.cap < 1 || l.cap > a.n || !a.ivf.offsets || !a.ivf.pids || (long long)a.first + a.n > a.ivf.passages)))
+      (ivf && (l.cap < 1 || l.cap > a.n || !a.ivf.offsets || !a.ivf.pids || (long long)a.first + a.n > a.ivf.passages)) ||
+      (a.filter.bits && ((a.filter.rows != 1 && a.filter.rows != a.nq) || a.filter.first != a.first ||
+                         a.filter.ld < ((long long)a.first + a.n + 31) / 32)))
     return hipErrorInvalidValue;
   // the steps of both forms in one sequence; a stage number skips the candidate steps of the other form
   enum { SCORES, CELLS, BITMAPS, SCAN, IVF_LISTS, IVF_SCORES, SELECT_NDOCS, SELECT_QUARTER, EXACT, SELECT_K };
@@ -384,13 +405,17 @@ hipError_t rr_launch_plaid_search_stage(int stage, const rr_plaid_search_args& a
     case SCAN: {
       const long long blocks = ((long long)a.n + PS_CHUNK - 1) / PS_CHUNK * a.nq;
       if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-      hipLaunchKernelGGL(plaid_scan_kernel, dim3((unsigned)blocks), dim3(256), (size_t)2 * l.W * sizeof(uint32_t), st, S, s_q, a.Lq, C, a.Lqc,
-                         cellbits, keepbits, l.W, a.bank.codes, a.bank.mask, a.table, a.n, a.nq, a1, a2);
+      if (a.filter.bits)
+        hipLaunchKernelGGL(plaid_scan_kernel<true>, dim3((unsigned)blocks), dim3(256), (size_t)2 * l.W * sizeof(uint32_t), st, S, s_q, a.Lq, C,
+                           a.Lqc, cellbits, keepbits, l.W, a.bank.codes, a.bank.mask, a.table, a.n, a.nq, a1, a2, a.filter);
+      else
+        hipLaunchKernelGGL(plaid_scan_kernel<false>, dim3((unsigned)blocks), dim3(256), (size_t)2 * l.W * sizeof(uint32_t), st, S, s_q, a.Lq, C,
+                           a.Lqc, cellbits, keepbits, l.W, a.bank.codes, a.bank.mask, a.table, a.n, a.nq, a1, a2, rr_passage_filter{});
       return hipGetLastError();
     }
     case IVF_LISTS:
       return rr_launch_ivf_candidates(a.ivf, C, cells, a.Lqc * a.ncells, a.nq, a.first, a.n, (uint32_t*)(a.scratch + l.bm), l.Wn, cand, l.cap,
-                                      ccnt, a1, a2, st);
+                                      ccnt, a1, a2, a.filter, st);
     case IVF_SCORES: {
       const int groups = std::min((l.cap + 3) / 4, 2048);     // workgroups of a query; they stride over its list
       hipLaunchKernelGGL(plaid_score_listed_kernel, dim3((unsigned)((long long)groups * a.nq)), dim3(256), (size_t)l.W * sizeof(uint32_t), st,

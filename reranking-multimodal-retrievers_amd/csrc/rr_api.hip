@@ -2513,6 +2513,51 @@ static int rr_bank_ivf_read_impl(rr_bank* b, int64_t* offsets_host_out, int32_t*
   return RR_OK;
 }
 
+// rr_bank_filter_fill (include/rerank_mi355.h): the lists checked on the host, staged through the bank's slot pair as an add stages
+// its descriptors ([rows + 1] int64 offsets, then the int32 indices), one launch
+static int rr_bank_filter_fill_impl(rr_bank* b, const int32_t* indices_host, const int64_t* offsets_host, int rows, int exclude,
+                                    uint32_t* filter_bits, int64_t filter_ld, void* hip_stream) {
+  const char* what = "rr_bank_filter_fill";
+  if (!b) return RR_ERR_BAD_ARG;
+  if (!offsets_host || !filter_bits || (((uintptr_t)filter_bits) & 3)) return bfail(b, RR_ERR_BAD_ARG, "%s: null or misaligned argument", what);
+  const long long held = (long long)b->first.size();
+  if (rows < 1 || rows > 65535) return bfail(b, RR_ERR_BAD_SHAPE, "%s: rows=%d (1..65535)", what, rows);
+  if (held < 1) return bfail(b, RR_ERR_BAD_SHAPE, "%s: the bank holds no passage", what);
+  if (filter_ld < (held + 31) / 32)
+    return bfail(b, RR_ERR_BAD_SHAPE, "%s: filter_ld=%lld words, %lld passages take %lld", what, (long long)filter_ld, held, (held + 31) / 32);
+  if (offsets_host[0] != 0) return bfail(b, RR_ERR_BAD_SHAPE, "%s: offsets[0]=%lld", what, (long long)offsets_host[0]);
+  for (int r = 0; r < rows; ++r)
+    if (offsets_host[r + 1] < offsets_host[r]) return bfail(b, RR_ERR_BAD_SHAPE, "%s: offsets descend at row %d", what, r);
+  const int64_t total = offsets_host[rows];
+  if (total > 0 && !indices_host) return bfail(b, RR_ERR_BAD_ARG, "%s: null indices", what);
+  if (total > ((int64_t)1 << 30)) return bfail(b, RR_ERR_BAD_SHAPE, "%s: %lld indices", what, (long long)total);
+  for (int64_t i = 0; i < total; ++i)
+    if (indices_host[i] < 0 || indices_host[i] >= held)
+      return bfail(b, RR_ERR_BAD_SHAPE, "%s: entry %lld names passage %d, the bank holds %lld", what, (long long)i, indices_host[i], held);
+  hipStream_t st = (hipStream_t)hip_stream;
+  RR_TRY(bank_capture_guard(b, st, "%s cannot be captured into a graph (it stages the lists)", what));
+  RR_BHIP(b, hipSetDevice(b->device));
+  const size_t off_bytes = ((size_t)rows + 1) * sizeof(int64_t);
+  std::vector<char> upload(off_bytes + (size_t)total * sizeof(int32_t));
+  memcpy(upload.data(), offsets_host, off_bytes);
+  if (total) memcpy(upload.data() + off_bytes, indices_host, (size_t)total * sizeof(int32_t));
+  rr_model::AsmSlot& a = b->slot[b->next];
+  RR_BHIP(b, stage_slot(a, upload.data(), upload.size(), (size_t)1024 * sizeof(rr_bank_slot), st));
+  RR_BHIP(b, rr_launch_filter_fill((const int64_t*)a.dev, (const int32_t*)((const char*)a.dev + off_bytes), rows, exclude != 0, (int)held,
+                                   filter_bits, (long long)filter_ld, st));
+  RR_BHIP(b, hipEventRecord(a.done, st));
+  b->next ^= 1;
+  return RR_OK;
+}
+
+static int rr_util_bank_filter_bits_impl(const int32_t* indices, const int64_t* offsets, int rows, int exclude, int32_t passages,
+                                         uint32_t* bits_out, int64_t filter_ld) {
+  if (!offsets || !bits_out) return RR_ERR_BAD_ARG;
+  if (rows < 1 || passages < 1) return RR_ERR_BAD_SHAPE;
+  if (offsets[0] == 0 && offsets[rows] > 0 && !indices) return RR_ERR_BAD_ARG;
+  return rr_filter_bits_host(indices, offsets, rows, exclude != 0, passages, bits_out, (long long)filter_ld) ? RR_OK : RR_ERR_BAD_SHAPE;
+}
+
 static int rr_util_plaid_ivf_impl(const int32_t* codes, const uint8_t* mask, const int32_t* lengths, int32_t n_passages, int32_t n_centroids,
                                   int64_t* offsets_out, int32_t* pids_out, int64_t pids_capacity, int64_t* postings_out) {
   if (!codes || !lengths || !offsets_out) return RR_ERR_BAD_ARG;
@@ -3055,13 +3100,14 @@ static int bank_table_current(rr_model* m, rr_bank* b, hipStream_t st) {
   return RR_OK;
 }
 
-// What rr_bank_search and rr_bank_search_plaid (`pruned`: compressed banks only, counts_out) do alike before their first launch: the
+// What rr_bank_search and rr_bank_search_plaid (`pruned`: compressed banks only; `counted`: counts_out is required, as in the pruned and
+// the filtered entries, and null with the other null arguments) do alike before their first launch: the
 // shared checks, the range resolved into (first_passage, *n), then `limits(n)`, the call's own refusals, where they have always stood;
 // the device, the bank's table brought up to date, and *rows: the rows of the range (passages lie back to back), for the profile
-static int bank_search_begin(rr_model* m, const char* what, bool pruned, rr_bank* b, const float* query_li, int n_queries, int Lq,
+static int bank_search_begin(rr_model* m, const char* what, bool pruned, bool counted, rr_bank* b, const float* query_li, int n_queries, int Lq,
                              int32_t first_passage, int32_t n_passages, const int32_t* indices_out, const float* scores_out,
                              const int32_t* counts_out, hipStream_t st, int* n, double* rows, const std::function<int(int)>& limits) {
-  if (!b || !query_li || !indices_out || (pruned && !counts_out)) return fail(m, RR_ERR_BAD_ARG, "%s: null argument", what);
+  if (!b || !query_li || !indices_out || (counted && !counts_out)) return fail(m, RR_ERR_BAD_ARG, "%s: null argument", what);
   RR_TRY(bank_usable(m, what, b));
   if (pruned && !b->nbits) return fail(m, RR_ERR_UNSUPPORTED, "%s: an fp16 bank (compressed banks only: the stages read the centroid codes)", what);
   if (m->cfg.li_dim % 16) return fail(m, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a multiple of 16)", what, m->cfg.li_dim);
@@ -3081,25 +3127,42 @@ static int bank_search_begin(rr_model* m, const char* what, bool pruned, rr_bank
   return RR_OK;
 }
 
-// rr_bank_search (include/rerank_mi355.h): one scoring launch over the range and the selection passes
+// A caller's filter as the three filtered searches (`what`) check it, behind their other refusals ("CANDIDATE FILTERS",
+// include/rerank_mi355.h); np: the passages of the resolved range
+struct FilterArg { const uint32_t* bits; int rows; int64_t ld; };
+static int bank_filter_check(rr_model* m, const char* what, const FilterArg& f, int n_queries, int32_t first_passage, int np) {
+  if (!f.bits) return fail(m, RR_ERR_BAD_ARG, "%s: null filter_bits (the unfiltered entry takes no filter)", what);
+  if (((uintptr_t)f.bits) & 3) return fail(m, RR_ERR_BAD_ARG, "%s: misaligned filter_bits", what);
+  if (f.rows != 1 && f.rows != n_queries) return fail(m, RR_ERR_BAD_SHAPE, "%s: filter_rows=%d (1 or n_queries=%d)", what, f.rows, n_queries);
+  const long long need = ((long long)first_passage + np + 31) / 32;
+  if (f.ld < need)
+    return fail(m, RR_ERR_BAD_SHAPE, "%s: filter_ld=%lld words, passages [%d, %d + %d) take %lld", what, (long long)f.ld, first_passage,
+                first_passage, np, need);
+  return RR_OK;
+}
+
+// rr_bank_search (include/rerank_mi355.h): one scoring launch over the range and the selection passes.  filter (or null):
+// rr_bank_search_filtered, the scores under the filter, the same selection, then one list pass that drops the absent and counts
 static int bank_search_call(rr_handle h, rr_bank* b, const float* query_li, int n_queries, int Lq, int32_t first_passage,
-                            int32_t n_passages, int k, int32_t* indices_out, float* scores_out, void* hip_stream) {
-  const char* what = "rr_bank_search";
+                            int32_t n_passages, int k, const FilterArg* filter, int32_t* indices_out, float* scores_out,
+                            int32_t* counts_out, void* hip_stream) {
+  const char* what = filter ? "rr_bank_search_filtered" : "rr_bank_search";
   if (!h) return RR_ERR_BAD_ARG;
   rr_model* m = h;
   hipStream_t st = (hipStream_t)hip_stream;
   int n = 0;
   double rows = 0.0;
-  RR_TRY(bank_search_begin(m, what, false, b, query_li, n_queries, Lq, first_passage, n_passages, indices_out, scores_out, nullptr, st, &n, &rows,
-                           [&](int np) {
+  RR_TRY(bank_search_begin(m, what, false, filter != nullptr, b, query_li, n_queries, Lq, first_passage, n_passages, indices_out, scores_out, counts_out, st, &n,
+                           &rows, [&](int np) {
                              if (k < 1 || k > np) return fail(m, RR_ERR_BAD_SHAPE, "%s: k=%d of %d passages", what, k, np);
                              if (k > 1024) return fail(m, RR_ERR_UNSUPPORTED, "%s: k=%d (at most 1024: a selection pass keeps k of 4096)", what, k);
-                             return (int)RR_OK;
+                             return filter ? bank_filter_check(m, what, *filter, n_queries, first_passage, np) : (int)RR_OK;
                            }));
   const int D = m->cfg.li_dim;
   const size_t sc_bytes = (((size_t)n_queries * n * sizeof(float)) + 15) & ~(size_t)15;
   const size_t tmp_bytes = ((rr_topk_select_scratch(n_queries, n, k) * sizeof(int32_t)) + 15) & ~(size_t)15;
-  RR_TRY(ensure_block(m, m->search_blk, m->search_blk_cap, sc_bytes + 2 * tmp_bytes, st, "the bank search's block"));
+  const size_t top_bytes = filter ? (((size_t)n_queries * k * sizeof(int32_t)) + 15) & ~(size_t)15 : 0;      // the selection's k, before the list pass
+  RR_TRY(ensure_block(m, m->search_blk, m->search_blk_cap, sc_bytes + 2 * tmp_bytes + top_bytes, st, "the bank search's block"));
   m->plaid_last_ok = false;                         // the block no longer holds a pruned search's intermediates
   float* sc = (float*)m->search_blk;
   int32_t* tmp_a = tmp_bytes ? (int32_t*)(m->search_blk + sc_bytes) : nullptr;
@@ -3110,9 +3173,18 @@ static int bank_search_call(rr_handle h, rr_bank* b, const float* query_li, int 
   // workgroup of 16 passages, one float per (query, passage)
   const double bytes = rows * (rr_bank_row_bytes(bank, D) + 1.0) + 16.0 * n + (double)n_queries * (n / 16.0 + 1.0) * 4.0 * Lq * D + 4.0 * n_queries * (double)n;
   RR_RUN(m, st, RR_K_TAIL, 2.0 * n_queries * rows * Lq * D, bytes,
-         rr_launch_bank_search_scores(b->table + first_passage, n, n_queries, Lq, D, query_li, bank, sc, st));
-  RR_RUN(m, st, RR_K_TAIL, 0.0, 12.0 * n_queries * (double)n,
-         rr_launch_topk_select(sc, n_queries, n, k, first_passage, tmp_a, tmp_b, indices_out, scores_out, st));
+         rr_launch_bank_search_scores(b->table + first_passage, n, n_queries, Lq, D, query_li, bank,
+                                      filter ? rr_passage_filter{filter->bits, filter->rows, (long long)filter->ld, first_passage} : rr_passage_filter{},
+                                      sc, st));
+  if (!filter) {
+    RR_RUN(m, st, RR_K_TAIL, 0.0, 12.0 * n_queries * (double)n,
+           rr_launch_topk_select(sc, n_queries, n, k, first_passage, tmp_a, tmp_b, indices_out, scores_out, st));
+    return RR_OK;
+  }
+  int32_t* top = (int32_t*)(m->search_blk + sc_bytes + 2 * tmp_bytes);
+  RR_RUN(m, st, RR_K_TAIL, 0.0, 12.0 * n_queries * (double)n, rr_launch_topk_select(sc, n_queries, n, k, 0, tmp_a, tmp_b, top, nullptr, st));
+  RR_RUN(m, st, RR_K_TAIL, 0.0, 16.0 * n_queries * (double)k,
+         rr_launch_list_select(sc, (long long)n, n_queries, top, k, k, indices_out, counts_out, first_passage, scores_out, st));
   return RR_OK;
 }
 
@@ -3153,7 +3225,7 @@ static int rr_op_bank_search_impl(const float* query_li, int n_queries, int Lq, 
   if (hipMalloc((void**)&sc, (size_t)n_queries * n_passages * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return RR_ERR_OOM; }
   const rr_bank_slot* t = (const rr_bank_slot*)table + first_passage;
   const rr_bank_view bank{nbits, n_centroids, rows_f16, codes, residuals, centroids_f16, bucket_weights, mask_bytes};
-  const hipError_t e = rr_launch_bank_search_scores(t, n_passages, n_queries, Lq, D, query_li, bank, sc, st);
+  const hipError_t e = rr_launch_bank_search_scores(t, n_passages, n_queries, Lq, D, query_li, bank, rr_passage_filter{}, sc, st);
   int rc = e == hipSuccess ? op_select_with_scratch(sc, n_queries, n_passages, k, first_passage, indices_out, scores_out, st) : RR_ERR_HIP;
   if (hipStreamSynchronize(st) != hipSuccess && rc == RR_OK) rc = RR_ERR_HIP;
   (void)hipFree(sc);
@@ -3215,15 +3287,16 @@ static void plaid_search_costs(const rr_plaid_search_args& a, const rr_plaid_sea
 // rr_bank_search_plaid (include/rerank_mi355.h): the block, and the stages of bank_search_plaid.hip, each booked on its own.
 // ivf: rr_bank_search_plaid_ivf, the same checks, one more refusal, and the plan that reads the bank's inverted file
 static int bank_search_plaid_call(rr_handle h, bool ivf, rr_bank* b, const float* query_li, int n_queries, int Lq, int Lq_coarse,
-                                  int32_t first_passage, int32_t n_passages, int ncells, float threshold, int ndocs, int k, int32_t* indices_out,
-                                  float* scores_out, int32_t* counts_out, void* hip_stream) {
-  const char* what = ivf ? "rr_bank_search_plaid_ivf" : "rr_bank_search_plaid";
+                                  int32_t first_passage, int32_t n_passages, int ncells, float threshold, int ndocs, int k,
+                                  const FilterArg* filter, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream) {
+  const char* what = filter ? (ivf ? "rr_bank_search_plaid_ivf_filtered" : "rr_bank_search_plaid_filtered")
+                            : (ivf ? "rr_bank_search_plaid_ivf" : "rr_bank_search_plaid");
   if (!h) return RR_ERR_BAD_ARG;
   rr_model* m = h;
   hipStream_t st = (hipStream_t)hip_stream;
   int n = 0;
   double rows = 0.0;
-  RR_TRY(bank_search_begin(m, what, true, b, query_li, n_queries, Lq, first_passage, n_passages, indices_out, scores_out, counts_out, st, &n, &rows,
+  RR_TRY(bank_search_begin(m, what, true, true, b, query_li, n_queries, Lq, first_passage, n_passages, indices_out, scores_out, counts_out, st, &n, &rows,
                            [&](int np) {
                              const char* msg;
                              const int rc = plaid_search_limits(b->n_centroids, np, Lq, Lq_coarse, ncells, ndocs, k, &msg);
@@ -3235,7 +3308,7 @@ static int bank_search_plaid_call(rr_handle h, bool ivf, rr_bank* b, const float
                              if (ivf && (long long)first_passage + np > b->ivf.passages)
                                return fail(m, RR_ERR_UNSUPPORTED, "%s: passages [%d, %d + %d) reach beyond the %d the inverted file covers: call "
                                            "rr_bank_build_ivf again", what, first_passage, first_passage, np, b->ivf.passages);
-                             return (int)RR_OK;
+                             return filter ? bank_filter_check(m, what, *filter, n_queries, first_passage, np) : (int)RR_OK;
                            }));
   const int D = m->cfg.li_dim;
   // (a file none of whose lists has an entry still takes the inverted-file form: its rows are one entry wide at the least)
@@ -3245,7 +3318,8 @@ static int bank_search_plaid_call(rr_handle h, bool ivf, rr_bank* b, const float
   RR_TRY(ensure_block(m, m->search_blk, m->search_blk_cap, l.total, st, "the bank search's block"));
   m->last_stream = st;
   const rr_plaid_search_args a{n_queries, n, first_passage, Lq, Lq_coarse, D, ncells, ndocs, k, threshold, query_li, b->table + first_passage,
-                               bank_view(b), m->search_blk, indices_out, scores_out, counts_out, ivf ? b->ivf : rr_ivf{}};
+                               bank_view(b), m->search_blk, indices_out, scores_out, counts_out, ivf ? b->ivf : rr_ivf{},
+                               filter ? rr_passage_filter{filter->bits, filter->rows, (long long)filter->ld, first_passage} : rr_passage_filter{}};
   double flops[RR_PLAID_IVF_SEARCH_STAGES], bytes[RR_PLAID_IVF_SEARCH_STAGES];
   plaid_search_costs(a, l, rows, flops, bytes);
   const int stop = g_plaid_stop_after[ivf];
@@ -4028,13 +4102,25 @@ int rr_bank_li_scores(rr_handle h, rr_bank_handle b, const float* query_li, int 
   return guarded(h, [&]() -> int { return bank_li_scores_call(h, b, query_li, n_queries, Lq, pair_passage, pair_query, n_pairs, padded_context_len, scores_out, maxsim_out, hip_stream); });
 }
 int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage, int32_t n_passages, int k, int32_t* indices_out, float* scores_out, void* hip_stream) {
-  return guarded(h, [&]() -> int { return bank_search_call(h, b, query_li, n_queries, Lq, first_passage, n_passages, k, indices_out, scores_out, hip_stream); });
+  return guarded(h, [&]() -> int { return bank_search_call(h, b, query_li, n_queries, Lq, first_passage, n_passages, k, nullptr, indices_out, scores_out, nullptr, hip_stream); });
+}
+int rr_bank_search_filtered(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage, int32_t n_passages, int k, const uint32_t* filter_bits, int filter_rows, int64_t filter_ld, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream) {
+  const FilterArg f{filter_bits, filter_rows, filter_ld};
+  return guarded(h, [&]() -> int { return bank_search_call(h, b, query_li, n_queries, Lq, first_passage, n_passages, k, &f, indices_out, scores_out, counts_out, hip_stream); });
+}
+int rr_bank_search_plaid_filtered(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse, int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k, const uint32_t* filter_bits, int filter_rows, int64_t filter_ld, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream) {
+  const FilterArg f{filter_bits, filter_rows, filter_ld};
+  return guarded(h, [&]() -> int { return bank_search_plaid_call(h, false, b, query_li, n_queries, Lq, Lq_coarse, first_passage, n_passages, ncells, centroid_score_threshold, ndocs, k, &f, indices_out, scores_out, counts_out, hip_stream); });
+}
+int rr_bank_search_plaid_ivf_filtered(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse, int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k, const uint32_t* filter_bits, int filter_rows, int64_t filter_ld, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream) {
+  const FilterArg f{filter_bits, filter_rows, filter_ld};
+  return guarded(h, [&]() -> int { return bank_search_plaid_call(h, true, b, query_li, n_queries, Lq, Lq_coarse, first_passage, n_passages, ncells, centroid_score_threshold, ndocs, k, &f, indices_out, scores_out, counts_out, hip_stream); });
 }
 int rr_bank_search_plaid(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse, int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream) {
-  return guarded(h, [&]() -> int { return bank_search_plaid_call(h, false, b, query_li, n_queries, Lq, Lq_coarse, first_passage, n_passages, ncells, centroid_score_threshold, ndocs, k, indices_out, scores_out, counts_out, hip_stream); });
+  return guarded(h, [&]() -> int { return bank_search_plaid_call(h, false, b, query_li, n_queries, Lq, Lq_coarse, first_passage, n_passages, ncells, centroid_score_threshold, ndocs, k, nullptr, indices_out, scores_out, counts_out, hip_stream); });
 }
 int rr_bank_search_plaid_ivf(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse, int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream) {
-  return guarded(h, [&]() -> int { return bank_search_plaid_call(h, true, b, query_li, n_queries, Lq, Lq_coarse, first_passage, n_passages, ncells, centroid_score_threshold, ndocs, k, indices_out, scores_out, counts_out, hip_stream); });
+  return guarded(h, [&]() -> int { return bank_search_plaid_call(h, true, b, query_li, n_queries, Lq, Lq_coarse, first_passage, n_passages, ncells, centroid_score_threshold, ndocs, k, nullptr, indices_out, scores_out, counts_out, hip_stream); });
 }
 int rr_bank_build_ivf(rr_bank_handle b, void* hip_stream) { return guarded(nullptr, [&]() -> int { return rr_bank_build_ivf_impl(b, hip_stream); }); }
 int rr_bank_ivf_info(rr_bank_handle b, int32_t* passages_covered_out, int64_t* postings_out, int32_t* longest_list_out) {
@@ -4042,6 +4128,12 @@ int rr_bank_ivf_info(rr_bank_handle b, int32_t* passages_covered_out, int64_t* p
 }
 int rr_bank_ivf_read(rr_bank_handle b, int64_t* offsets_host_out, int32_t* pids_host_out, void* hip_stream) {
   return guarded(nullptr, [&]() -> int { return rr_bank_ivf_read_impl(b, offsets_host_out, pids_host_out, hip_stream); });
+}
+int rr_bank_filter_fill(rr_bank_handle b, const int32_t* indices_host, const int64_t* offsets_host, int rows, int exclude, uint32_t* filter_bits, int64_t filter_ld, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_bank_filter_fill_impl(b, indices_host, offsets_host, rows, exclude, filter_bits, filter_ld, hip_stream); });
+}
+int rr_util_bank_filter_bits(const int32_t* indices, const int64_t* offsets, int rows, int exclude, int32_t passages, uint32_t* bits_out, int64_t filter_ld) {
+  return guarded(nullptr, [&]() -> int { return rr_util_bank_filter_bits_impl(indices, offsets, rows, exclude, passages, bits_out, filter_ld); });
 }
 int rr_util_plaid_ivf(const int32_t* codes, const uint8_t* mask, const int32_t* lengths, int32_t n_passages, int32_t n_centroids, int64_t* offsets_out, int32_t* pids_out, int64_t pids_capacity, int64_t* postings_out) {
   return guarded(nullptr, [&]() -> int { return rr_util_plaid_ivf_impl(codes, mask, lengths, n_passages, n_centroids, offsets_out, pids_out, pids_capacity, postings_out); });

@@ -479,11 +479,36 @@ int rr_set_li_lds_kb(int kb);      // rr_set_tuning("li_lds_kb"): 16 .. 150, -1 
 // or null: the output row of workgroup p
 hipError_t rr_launch_bank_li_scores(const rr_bank_pair* pairs, const int32_t* slot, int n, int Lq, int Lc, int D, const float* query_li,
                                     const rr_bank_view& bank, float* scores, float* maxsim, hipStream_t st);
+// A caller's candidate filter as the three filtered searches take it ("CANDIDATE FILTERS", include/rerank_mi355.h): bits [rows][ld]
+// uint32 on the device, bit (i & 31) of word (i >> 5) of a row = the ABSOLUTE bank index i; rows 1 (every query) or n_queries;
+// `first`: the bank index of the range's first passage.  bits == null: no filter.  word(q, w) and allowed(q, p) (p range-relative)
+// are asked with wave-uniform arguments, so the word is a scalar load.
+struct rr_passage_filter {
+  const uint32_t* bits;
+  int rows;
+  long long ld;
+  int first;
+  __device__ __forceinline__ uint32_t word(int q, int w) const { return bits[(size_t)(rows == 1 ? 0 : q) * ld + w]; }
+  __device__ __forceinline__ bool allowed(int q, int p) const {
+    const int i = first + p;
+    return (word(q, i >> 5) >> (i & 31)) & 1u;
+  }
+  // the filter bits of the range-relative passages 32 w .. 32 w + 31 of a range of n: a range that does not start at a multiple of
+  // 32 takes them from two words of the row (a funnel shift); no word behind the range's last is read
+  __device__ __forceinline__ uint32_t range_word(int q, int w, int n) const {
+    const long long i = (long long)first + (long long)w * 32;
+    const int fw = (int)(i >> 5), sh = (int)(i & 31);
+    const uint32_t lo = word(q, fw);
+    const uint32_t hi = (sh && ((long long)fw + 1) * 32 < (long long)first + n) ? word(q, fw + 1) : 0u;
+    return (uint32_t)((((unsigned long long)hi << 32) | lo) >> sh);
+  }
+};
 // rr_bank_search (bank_search.hip): out [nq][n] = the MaxSim of every query against the passages table[0 .. n) (the bits of
 // rr_launch_bank_li_scores' maxsim at Lc = the passage's length), and the selection: the first k of every list in the order of a
 // stable descending sort (NaN first, ties by ascending index), indices + add; tmp_a / tmp_b hold rr_topk_select_scratch int32 each
+// filter.bits given (rr_bank_search_filtered): a passage whose bit is clear gets -inf and is not read
 hipError_t rr_launch_bank_search_scores(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
-                                        const rr_bank_view& bank, float* out, hipStream_t st);
+                                        const rr_bank_view& bank, const rr_passage_filter& filter, float* out, hipStream_t st);
 // the same for the passages list[q][0 .. cnt[q]) of every query (cnt[q] <= list_ld; entries of table[0 .. n)), written to the
 // passage's entry of the dense out [nq][n]; compressed banks only.  With cand (cap > 0; or null and 0) for the passages
 // cand[q][list[q][i]], i < cnt[q]: a list entry is a PLACE in the query's candidate list cand [nq][cap] (entries of table[0 .. n)),
@@ -491,6 +516,18 @@ hipError_t rr_launch_bank_search_scores(const rr_bank_slot* table, int n, int nq
 hipError_t rr_launch_bank_search_scores_listed(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
                                                const rr_bank_view& bank, const int32_t* list, int list_ld, const int32_t* cnt,
                                                const int32_t* cand, int cap, float* out, hipStream_t st);
+// the passages 0 .. cnt - 1 of a row from list / offsets as a bitmap (rr_bank_filter_fill; bank_ivf.hip): staged [rows + 1] int64
+// offsets and the int32 indices behind them, both on the device; bits [rows][ld].  exclude: every bit below `passages` but those.
+hipError_t rr_launch_filter_fill(const int64_t* offsets, const int32_t* indices, int rows, int exclude, int passages, uint32_t* bits,
+                                 long long ld, hipStream_t st);
+// the definition in host code (rr_util_bank_filter_bits); false, with nothing written, for an index outside [0, passages), offsets
+// that do not ascend from 0 or ld < ceil(passages / 32)
+bool rr_filter_bits_host(const int32_t* indices, const int64_t* offsets, int rows, int exclude, int passages, uint32_t* bits, long long ld);
+// One workgroup per list (plaid_list_select_kernel, bank_search_plaid.hip): the entries list_in[q][0 .. n_in) whose score in
+// scores [nq][n] is not -inf, in rank order; the first `keep` (n_in <= 1024) to list_out [nq][keep] (+ add) and scores_out (or null),
+// -1 / -inf behind them, their number to cnt_out [nq].  The last step of rr_bank_search_filtered.
+hipError_t rr_launch_list_select(const float* scores, long long n, int nq, const int32_t* list_in, int n_in, int keep, int32_t* list_out,
+                                 int32_t* cnt_out, int add, float* scores_out, hipStream_t st);
 size_t rr_topk_select_scratch(int n_lists, int n, int k);
 hipError_t rr_launch_topk_select(const float* scores, int n_lists, int n, int k, int add, int32_t* tmp_a, int32_t* tmp_b,
                                  int32_t* indices_out, float* scores_out, hipStream_t st);
@@ -509,8 +546,10 @@ int64_t rr_ivf_host(const int32_t* codes, const uint8_t* mask, const int32_t* le
 // the candidate step of rr_bank_search_plaid_ivf: per query the passages of [first, first + n) in the lists of its cells
 // (cells [nq][E]) as an ascending range-relative list cand [nq][cap] with its count ccnt [nq]; -inf behind the count in a1 / a2
 // [nq][cap]; bm [nq][Wn], Wn = ceil(n / 32): scratch
+// filter.bits given: the bitmap is ANDed with the filter's bits of the range as it is compacted
 hipError_t rr_launch_ivf_candidates(const rr_ivf& f, int C, const int32_t* cells, int E, int nq, int first, int n, uint32_t* bm, int Wn,
-                                    int32_t* cand, int cap, int32_t* ccnt, float* a1, float* a2, hipStream_t st);
+                                    int32_t* cand, int cap, int32_t* ccnt, float* a1, float* a2, const rr_passage_filter& filter,
+                                    hipStream_t st);
 // rr_bank_search_plaid and rr_bank_search_plaid_ivf (bank_search_plaid.hip): the staged, centroid-pruned search over a compressed
 // bank.  The arguments of a call as its stages take them (table: the first passage of the range; indices + first), where the
 // intermediates of the call lie in `scratch` (byte offsets, 16-byte aligned; rr_plaid_search_plan), and one launcher that runs one
@@ -532,6 +571,7 @@ struct rr_plaid_search_args {
   float* scores_out;
   int32_t* counts_out;
   rr_ivf ivf;                 // rr_bank_search_plaid_ivf alone: the bank's inverted file
+  rr_passage_filter filter;   // the filtered entries alone (bits null: none): a passage whose bit is clear is no candidate
 };
 struct rr_plaid_search_layout {
   int stages;                 // RR_PLAID_SEARCH_STAGES or RR_PLAID_IVF_SEARCH_STAGES: which form the plan is for

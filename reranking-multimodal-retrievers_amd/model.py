@@ -207,9 +207,22 @@ def _bank_search_args(eng, name: str, bank, query_li: torch.Tensor, first: int, 
     return first, n, nq, Lq, query_li.to(device=eng.device, dtype=torch.float32).contiguous()
 
 
+def _bank_filter_args(name: str, filter, nq: int, first: int, n: int) -> list:
+    """The three filter arguments of a filtered search (bits, rows, words per row) from a BankFilter, checked against the call:
+    one row or one per query, built for at least the passages of the range (ValueError)."""
+    rows, ld = int(filter.bits.shape[0]), int(filter.bits.shape[1])
+    if rows not in (1, nq):
+        raise ValueError(f"{name}: a filter of {rows} rows for {nq} queries (1, or one per query)")
+    if filter.passages < first + n or ld * 32 < first + n:
+        raise ValueError(f"{name}: the filter was built for {filter.passages} passages, the range ends at {first + n}: build it again "
+                         "(PassageBank.filter)")
+    return [L.ptr(filter.bits), rows, ld]
+
+
 def _bank_search_plaid(eng, entry: str, bank, query_li: torch.Tensor, k: int, *, ncells: int, centroid_score_threshold: float, ndocs: int,
-                       coarse_tokens: Optional[int] = None, first: int = 0, count: Optional[int] = None) -> dict:
-    """RerankEngine.bank_search_plaid and bank_search_plaid_ivf: the checks before the library, the outputs, the call of `entry`."""
+                       coarse_tokens: Optional[int] = None, first: int = 0, count: Optional[int] = None, filter=None) -> dict:
+    """RerankEngine.bank_search_plaid and bank_search_plaid_ivf, and their filtered entries (`filter`: a BankFilter): the checks
+    before the library, the outputs, the call of `entry`."""
     first, n, nq, Lq, q = _bank_search_args(eng, "bank_search_plaid", bank, query_li, first, count, compressed_only=True)
     codec = bank.codec
     Lqc = Lq if coarse_tokens is None else int(coarse_tokens)
@@ -229,8 +242,9 @@ def _bank_search_plaid(eng, entry: str, bank, query_li: torch.Tensor, k: int, *,
     out = dict(indices=torch.empty((nq, k), device=eng.device, dtype=torch.int32),
                scores=torch.empty((nq, k), device=eng.device, dtype=torch.float32),
                counts=torch.empty((nq,), device=eng.device, dtype=torch.int32))
+    fargs = [] if filter is None else _bank_filter_args("bank_search_plaid", filter, nq, first, n)
     L.check(getattr(eng.lib, entry)(eng.h, bank.h, L.ptr(q), nq, Lq, Lqc, first, n, ncells, float(centroid_score_threshold), ndocs, k,
-                                     L.ptr(out["indices"]), L.ptr(out["scores"]), L.ptr(out["counts"]), eng._stream()),
+                                     *fargs, L.ptr(out["indices"]), L.ptr(out["scores"]), L.ptr(out["counts"]), eng._stream()),
             eng.h, entry)
     return out
 
@@ -902,6 +916,38 @@ class RerankEngine:
                                         self._stream()), self.h, "rr_bank_search")
         return out
 
+    def bank_search_filtered(self, bank, query_li: torch.Tensor, k: int, filter, first: int = 0, count: Optional[int] = None) -> dict:
+        """bank_search over the passages of the range that `filter` (a BankFilter, PassageBank.filter: one set for every query,
+        or one per query) allows (rr_bank_search_filtered): a passage outside the set is not scored.  {"indices": int32
+        [n_queries, k] dense bank indices, -1 behind the count; "scores": float32 [n_queries, k], -inf there; "counts": int32
+        [n_queries]}, on the device; k may exceed the number of allowed passages.  With every passage allowed: bank_search's
+        result.  The selection still walks one score per passage of the range: for a filter of a few thousand passages
+        bank_li_scores over those pairs and torch.topk is the cheaper route."""
+        first, n, nq, Lq, q = _bank_search_args(self, "bank_search_filtered", bank, query_li, first, count)
+        k = int(k)
+        if k < 1 or k > n:
+            raise ValueError(f"bank_search_filtered: k = {k} of {n} passages")
+        if k > 1024:
+            raise NotImplementedError(f"bank_search_filtered: k = {k} (at most 1024)")
+        fargs = _bank_filter_args("bank_search_filtered", filter, nq, first, n)
+        out = dict(indices=torch.empty((nq, k), device=self.device, dtype=torch.int32),
+                   scores=torch.empty((nq, k), device=self.device, dtype=torch.float32),
+                   counts=torch.empty((nq,), device=self.device, dtype=torch.int32))
+        L.check(self.lib.rr_bank_search_filtered(self.h, bank.h, L.ptr(q), nq, Lq, first, n, k, *fargs, L.ptr(out["indices"]),
+                                                 L.ptr(out["scores"]), L.ptr(out["counts"]), self._stream()), self.h, "rr_bank_search_filtered")
+        return out
+
+    def bank_search_plaid_filtered(self, bank, query_li: torch.Tensor, k: int, filter, **kw) -> dict:
+        """bank_search_plaid with the candidates restricted to what `filter` (a BankFilter) allows (rr_bank_search_plaid_filtered):
+        the result of bank_search_plaid on a bank whose filtered-out passages are fully masked.  The arguments and the outputs of
+        bank_search_plaid."""
+        return _bank_search_plaid(self, "rr_bank_search_plaid_filtered", bank, query_li, k, filter=filter, **kw)
+
+    def bank_search_plaid_ivf_filtered(self, bank, query_li: torch.Tensor, k: int, filter, **kw) -> dict:
+        """bank_search_plaid_filtered with the candidates from the bank's inverted file (rr_bank_search_plaid_ivf_filtered): bit
+        for bit the same result."""
+        return _bank_search_plaid(self, "rr_bank_search_plaid_ivf_filtered", bank, query_li, k, filter=filter, **kw)
+
     def bank_build_ivf(self, bank) -> dict:
         """Build, or rebuild, the inverted file of a COMPRESSED `bank` over every passage it holds now (rr_bank_build_ivf; per
         centroid the sorted unique passages with an unmasked token of that code, the reference's ivf.pid.pt).  A load-time call
@@ -1383,29 +1429,40 @@ class InteractionRerankModel(_DropIn):
             raise RuntimeError("retriever_scores needs a bank: model.create_bank(capacity_rows, max_passages), then bank.add(...)")
         return self.engine.bank_li_scores(self.bank, query_late_interaction, passage_ids, **kw)
 
-    def retrieve(self, query_late_interaction, k: int, plaid=None, **kw):
+    def retrieve(self, query_late_interaction, k: int, plaid=None, allowed=None, excluded=None, filter=None, **kw):
         """The k best passages of `self.bank` per query by the frozen retriever's MaxSim, every passage scored
         (PassageBank.search): (passage_ids: one list per query, best first; scores float32 [n_queries, k] on the device).
-        `plaid` (a PlaidSearch): PLAID's pruned search over a compressed bank instead; a query's list may then be shorter than k."""
+        `plaid` (a PlaidSearch): PLAID's pruned search over a compressed bank instead; a query's list may then be shorter than k.
+        `allowed` / `excluded` (passage ids: a flat sequence for every query, or a list of lists, one per query), or `filter` (a
+        BankFilter built by bank.filter): only the allowed passages compete (the reference's filter_fn); one of the three at most.
+        A query's list then has its true length, at most k."""
         if self.bank is None:
             raise RuntimeError("retrieve needs a bank: model.create_bank(capacity_rows, max_passages), then bank.add(...)")
         if plaid is not None:
             kw["plaid"] = plaid
+        if allowed is not None or excluded is not None:
+            if filter is not None:
+                raise ValueError("retrieve: give allowed / excluded or a filter built from them, not both")
+            filter = self.bank.filter(allowed=allowed, excluded=excluded)
+        if filter is not None:
+            kw["filter"] = filter
         return self.bank.search(self.engine, query_late_interaction, k, **kw)
 
-    def retrieve_and_rerank(self, query_late_interaction, query_mask, k: int, plaid=None, **kw):
+    def retrieve_and_rerank(self, query_late_interaction, query_mask, k: int, plaid=None, allowed=None, excluded=None, filter=None, **kw):
         """`retrieve` then `forward_passages` on what it found, k candidates per query in retrieval order: (passage_ids, the
-        RerankOutput).  `kw` goes to forward_passages (labels default as there: candidate 0 of every query).  With `plaid` the
-        lists may be of unequal length: they go to forward_passages as candidates_per_query; a query that found no candidate
-        raises ValueError."""
-        if plaid is None:
+        RerankOutput).  `kw` goes to forward_passages (labels default as there: candidate 0 of every query).  With `plaid`, or
+        under `allowed` / `excluded` / `filter` (as retrieve takes them), the lists may be of unequal length: they go to
+        forward_passages as candidates_per_query; a query that found no candidate raises ValueError."""
+        filtered = allowed is not None or excluded is not None or filter is not None
+        if plaid is None and not filtered:
             ids, _ = self.retrieve(query_late_interaction, k)
             flat = [pid for row in ids for pid in row]
             return ids, self.forward_passages(query_late_interaction, query_mask, flat, int(k) - 1, **kw)
-        ids, _ = self.retrieve(query_late_interaction, k, plaid=plaid)
+        ids, _ = self.retrieve(query_late_interaction, k, plaid=plaid, allowed=allowed, excluded=excluded, filter=filter)
         sizes = [len(row) for row in ids]
         if min(sizes) < 1:
-            raise ValueError(f"retrieve_and_rerank: query {sizes.index(0)} found no candidate under {plaid!r}")
+            under = " and ".join((["its filter"] if filtered else []) + ([repr(plaid)] if plaid is not None else []))
+            raise ValueError(f"retrieve_and_rerank: query {sizes.index(0)} found no candidate under {under}")
         flat = [pid for row in ids for pid in row]
         return ids, self.forward_passages(query_late_interaction, query_mask, flat, int(k) - 1, candidates_per_query=sizes, **kw)
 

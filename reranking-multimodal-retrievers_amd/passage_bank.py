@@ -20,7 +20,10 @@ staged search over a compressed bank (rr_bank_search_plaid, RerankEngine.bank_se
 centroid-only pruning passes, exact MaxSim on the survivors.  `PassageBank.build_ivf` builds the bank's inverted file on the
 device (rr_bank_build_ivf: per centroid the sorted unique passages holding a token of that code, the reference's ivf.pid.pt;
 `ivf` / `save_ivf` read and write it), and `PlaidSearch(..., ivf=True)` takes the candidates from it (rr_bank_search_plaid_ivf):
-the same result, with work that follows the lists of the query's cells instead of the rows of the bank.
+the same result, with work that follows the lists of the query's cells instead of the rows of the bank.  `PassageBank.filter`
+makes a candidate filter (a `BankFilter`: a device bitmap over the bank's passages, one set for every query or one per query,
+rr_bank_filter_fill) and `search(..., filter=)` restricts any of the three searches to it (rr_bank_search_filtered,
+rr_bank_search_plaid_filtered, rr_bank_search_plaid_ivf_filtered): the reference's filter_fn.
 
 `PassageBank.add_compress` fills a compressed bank from embeddings that are on the device (rr_bank_add_compress): nearest centroid
 on the matrix core and residual bucketising in two kernels, the codec's cutoffs given as `PlaidCodec(bucket_cutoffs=...)`.
@@ -68,6 +71,18 @@ class PlaidSearch:
     def __repr__(self) -> str:
         return (f"PlaidSearch(ncells={self.ncells}, centroid_score_threshold={self.centroid_score_threshold}, ndocs={self.ndocs}, "
                 f"coarse_tokens={self.coarse_tokens}" + (", ivf=True)" if self.ivf else ")"))
+
+
+class BankFilter:
+    """A candidate filter of the bank searches (PassageBank.filter; "CANDIDATE FILTERS", include/rerank_mi355.h): `bits`, the device
+    bitmap int32 [rows, ld] (bit i & 31 of word i >> 5 of a row: dense bank index i), `rows` (1: one set for every query; else one
+    row per query) and `passages`, the passage count of the bank when it was built: passages added later are not allowed by it."""
+
+    def __init__(self, bits, rows: int, passages: int):
+        self.bits, self.rows, self.passages = bits, int(rows), int(passages)
+
+    def __repr__(self) -> str:
+        return f"BankFilter(rows={self.rows}, passages={self.passages})"
 
 
 class BankTable:
@@ -654,14 +669,66 @@ class PassageBank:
         """The retriever's MaxSim [n_pairs] of the pairs (query, passage id) from this bank: engine.bank_li_scores(...)["maxsim"]."""
         return engine.bank_li_scores(self, query_li, passage_ids, **kw)["maxsim"]
 
-    def search(self, engine, query_li, k: int, first: int = 0, count: Optional[int] = None, plaid: Optional[PlaidSearch] = None):
+    def filter_lists(self, allowed=None, excluded=None):
+        """The host half of `filter`: (indices int32 [total], offsets int64 [rows + 1], exclude) as rr_bank_filter_fill takes them.
+        Exactly one of `allowed` / `excluded` is given (ValueError).  A flat sequence of passage ids is one row; a sequence whose
+        elements are all lists (or arrays) is one row per query (a tuple is an id, never a row).  Ids go through the table: a
+        KeyError names an id the bank does not hold."""
+        import numpy as np
+        if (allowed is None) == (excluded is None):
+            raise ValueError("filter: give exactly one of allowed / excluded")
+        given = allowed if allowed is not None else excluded
+        given = given.tolist() if hasattr(given, "tolist") else list(given)
+        nested = len(given) > 0 and all(isinstance(r, list) or (hasattr(r, "tolist") and getattr(r, "ndim", 0) > 0) for r in given)
+        rows = [r.tolist() if hasattr(r, "tolist") else list(r) for r in given] if nested else [given]
+        offsets = np.zeros(len(rows) + 1, dtype=np.int64)
+        for i, r in enumerate(rows):
+            offsets[i + 1] = offsets[i] + len(r)
+        flat = [pid for r in rows for pid in r]
+        indices = self.table.lookup(flat)[0].astype(np.int32) if flat else np.zeros(0, dtype=np.int32)
+        return np.ascontiguousarray(indices), offsets, excluded is not None
+
+    def filter(self, allowed=None, excluded=None) -> BankFilter:
+        """A candidate filter for `search` over the passages the bank holds now: the passages `allowed`, or every passage but
+        those `excluded` (exactly one of the two; passage ids, as filter_lists takes them: a flat sequence is one set for every
+        query, a list of lists one set per query).  The bitmap is written on the device (rr_bank_filter_fill) on the current
+        stream.  Build it again after an add: a filter knows the passage count it was built for."""
+        import torch
+        indices, offsets, exclude = self.filter_lists(allowed, excluded)
+        passages, rows = len(self.table), len(offsets) - 1
+        if passages < 1:
+            raise ValueError("filter: the bank holds no passage")
+        ld = (passages + 31) // 32
+        bits = torch.empty((rows, ld), device=self.device, dtype=torch.int32)
+        self._check(self.lib.rr_bank_filter_fill(self.h, indices.ctypes.data if indices.size else None, offsets.ctypes.data, rows, int(exclude),
+                                                 bits.data_ptr(), ld, self._stream()), "rr_bank_filter_fill", bad_shape=ValueError)
+        return BankFilter(bits, rows, passages)
+
+    def search(self, engine, query_li, k: int, first: int = 0, count: Optional[int] = None, plaid: Optional[PlaidSearch] = None,
+               filter: Optional[BankFilter] = None):
         """The k best passages per query by the retriever's MaxSim, every passage of the bank scored (engine.bank_search;
         `first` / `count`: a range of dense indices).  Returns (passage_ids, scores): passage_ids[q] the ids of query q best
         first, scores float32 [n_queries, k] on the device.  Copies the indices to the host (synchronises).
         With `plaid` (a PlaidSearch; compressed banks) the pruned search runs instead (engine.bank_search_plaid): passage_ids[q]
         has its true length, at most k (a query may find fewer candidates, or none), and scores holds -inf behind it.  A
-        PlaidSearch with ivf=True takes the candidates from the inverted file (build_ivf first): the same result."""
+        PlaidSearch with ivf=True takes the candidates from the inverted file (build_ivf first): the same result.
+        With `filter` (a BankFilter, `filter`) only the passages it allows compete, in the exact and in the pruned search
+        (engine.bank_search_filtered / bank_search_plaid_filtered / bank_search_plaid_ivf_filtered): passage_ids[q] has its true
+        length on the exact path too.  A filter built for fewer passages than the range ends at raises ValueError."""
         ids = self.table.ids
+        if filter is not None:
+            end = len(self.table) if count is None else int(first) + int(count)
+            if filter.passages < end:
+                raise ValueError(f"search: the filter was built for {filter.passages} passages, the range ends at {end}: build it again "
+                                 "(PassageBank.filter)")
+            if plaid is None:
+                r = engine.bank_search_filtered(self, query_li, k, filter, first=first, count=count)
+            else:
+                entry = engine.bank_search_plaid_ivf_filtered if getattr(plaid, "ivf", False) else engine.bank_search_plaid_filtered
+                r = entry(self, query_li, k, filter, ncells=plaid.ncells, centroid_score_threshold=plaid.centroid_score_threshold,
+                          ndocs=plaid.ndocs, coarse_tokens=plaid.coarse_tokens, first=first, count=count)
+            counts = r["counts"].tolist()
+            return [[ids[j] for j in row[:c]] for row, c in zip(r["indices"].tolist(), counts)], r["scores"]
         if plaid is None:
             r = engine.bank_search(self, query_li, k, first=first, count=count)
             return [[ids[j] for j in row] for row in r["indices"].tolist()], r["scores"]

@@ -827,7 +827,17 @@ int rr_bank_search_plaid(rr_handle h, rr_bank_handle b, const float* query_li, i
  * cover them; there is no incremental update); rr_bank_destroy frees it.
  * rr_bank_ivf_info: passages_covered (0: no file), the postings total and the longest list; any pointer may be NULL.
  * rr_bank_ivf_read copies offsets [C + 1] and pids [postings] to HOST buffers (either may be NULL) and synchronises hip_stream;
- * RR_ERR_BAD_ARG without a file.  Errors of the three: rr_bank_last_error.  Loading a foreign ivf.pid.pt is out of scope.
+ * RR_ERR_BAD_ARG without a file.  Errors of these calls: rr_bank_last_error.
+ * rr_bank_load_ivf takes a file from HOST arrays instead of building it: offsets_host int64 [C + 1] and pids_host int32
+ * [offsets_host[C]] (an ivf.pid.pt read back, its ivf_lengths summed into offsets; PassageBank.load_ivf does that).  The loaded file
+ * covers EVERY passage the bank holds now; longest_list and postings come from the offsets.  Checked on the host before anything is
+ * allocated, RR_ERR_BAD_SHAPE with the first offending list named in rr_bank_last_error: offsets_host[0] != 0, an offset below its
+ * predecessor, a pid outside [0, passages held), a list that does not ascend strictly.  An fp16 bank: RR_ERR_UNSUPPORTED; an empty
+ * bank: RR_ERR_BAD_SHAPE; under stream capture: RR_ERR_BAD_ARG; a failed allocation: RR_ERR_OOM.  verify != 0: the file is also
+ * compared, byte for byte, with a fresh build over the bank (rr_bank_build_ivf's kernels into a temporary, read back): a difference
+ * is RR_ERR_BAD_SHAPE.  That is the guard against the file of ANOTHER index, which passes the checks above and would change search
+ * results silently; verify == 0 trusts the caller and costs the upload alone.  After every refusal and failure the bank keeps the
+ * file it had.  A load-time call: it allocates and synchronises hip_stream.
  *
  * rr_bank_search_plaid_ivf takes exactly the arguments of rr_bank_search_plaid.  CONTRACT: indices_out, scores_out and counts_out
  * are bit for bit those of rr_bank_search_plaid with the same arguments, the -1 / -inf behind the count included; its checks, its
@@ -849,11 +859,39 @@ int rr_bank_search_plaid(rr_handle h, rr_bank_handle b, const float* query_li, i
  * bytes: with cap <= n never more than rr_bank_search_plaid's but for the bitmap and the candidate list (8 nq n against
  * 4 nq (n / 32 + 3 cap)).  Ten launches, a memset and the selection passes, booked in the profile's `tail` class.
  * LIMITS: those of rr_bank_search_plaid (ndocs <= 1024, one device, compressed banks); rr_bank_search_plaid_tap does not cover
- * this entry.  Under a candidate filter: rr_bank_search_plaid_ivf_filtered below.  (Python: RerankEngine.bank_build_ivf / bank_search_plaid_ivf, PassageBank.build_ivf / ivf / save_ivf,
+ * this entry.  Under a candidate filter: rr_bank_search_plaid_ivf_filtered below.  (Python: RerankEngine.bank_build_ivf / bank_search_plaid_ivf, PassageBank.build_ivf / ivf / save_ivf / load_ivf,
  * PlaidSearch(..., ivf=True).) */
 int rr_bank_build_ivf(rr_bank_handle b, void* hip_stream);
 int rr_bank_ivf_info(rr_bank_handle b, int32_t* passages_covered_out, int64_t* postings_out, int32_t* longest_list_out);
 int rr_bank_ivf_read(rr_bank_handle b, int64_t* offsets_host_out, int32_t* pids_host_out, void* hip_stream);
+int rr_bank_load_ivf(rr_bank_handle b, const int64_t* offsets_host, const int32_t* pids_host, int verify, void* hip_stream);
+
+/* rr_bank_export_plaid: a range of a COMPRESSED bank as a ColBERTv2 / PLAID index stores it, written on the device: the way back to
+ * disk of what rr_bank_add_plaid / rr_bank_add_compress put in (Python: PassageBank.export_compressed / save_plaid_index).
+ * DEFINITION.  For the passages first_passage .. first_passage + n_passages - 1 in bank order, the UNMASKED rows of each passage
+ * (mask byte != 0), in row order, back to back:
+ *   codes_out        : DEVICE int32 [R], 4-byte aligned.
+ *   residuals_out    : DEVICE uint8 [R, li_dim * nbits / 8], aligned to min(16, li_dim * nbits / 8) bytes.
+ *   doclens_host_out : HOST int32 [n_passages]: the unmasked rows of passage i; it may be 0.
+ *   *rows_host_out   : HOST: R, the sum of the doclens.
+ * These are the bytes the reference's indexer would have stored for the passages: it drops the skiplist tokens before it compresses
+ * (third_party/ColBERT/colbert/indexing/index_saver.py:70-90, collection_encoder.py), so MASKED ROWS DO NOT TRAVEL.  A bank loaded
+ * from the export (rr_bank_add_plaid with the doclens, no mask) gives the same MaxSim, the same search results and the same inverted
+ * file, bit for bit; it is NOT a snapshot of the bank: the codes and bytes under masked rows, and the positions of the kept rows
+ * inside their passage, are gone.  A passage of doclen 0 cannot be added again (rr_bank_add_plaid refuses it).
+ * SIZING CALL: codes_out and residuals_out both NULL: only doclens_host_out and *rows_host_out are written.
+ * REFUSALS, every one from the host, writing nothing: exactly one of codes_out / residuals_out NULL, a NULL doclens_host_out or
+ * rows_host_out, a misaligned output, a capturing stream (RR_ERR_BAD_ARG); an fp16 bank (RR_ERR_UNSUPPORTED); n_passages < 1 or a
+ * range that is not inside the bank (RR_ERR_BAD_SHAPE); both outputs given and capacity_rows < R (RR_ERR_BAD_SHAPE, decided after
+ * the count and before any row is moved; rr_bank_last_error names R).
+ * Three kernels (csrc/bank_export.hip), no global atomics, the same bytes from run to run: a count (a wave per passage, 64 mask
+ * bytes a step, ballot and popcount), the exclusive scan of the doclens into 64-bit row offsets (the scan of the inverted file's
+ * counts), and the move (a wave per passage; the ballot ranks the kept rows of a step, whose residual bytes go out as one contiguous
+ * run in 16-byte accesses).  Every row and byte offset is 64-bit.  The kernels walk the bank's device passage table, brought up to
+ * date as the first search after an add does.  A save-time call, like rr_bank_build_ivf: it allocates 12 n_passages + 24 bytes for
+ * the call and synchronises hip_stream, because it reads R back.  Errors: rr_bank_last_error. */
+int rr_bank_export_plaid(rr_bank_handle b, int32_t first_passage, int32_t n_passages, int32_t* doclens_host_out, int32_t* codes_out,
+                         uint8_t* residuals_out, int64_t capacity_rows, int64_t* rows_host_out, void* hip_stream);
 int rr_bank_search_plaid_ivf(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse,
                              int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k,
                              int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream);

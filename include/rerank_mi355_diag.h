@@ -367,6 +367,17 @@ int rr_op_bank_search_plaid(const float* query_li, int n_queries, int Lq, int Lq
                             const float* bucket_weights, int32_t n_centroids, int32_t* indices_out, float* scores_out,
                             int32_t* counts_out, void* hip_stream);
 int64_t rr_bank_search_plaid_tap(rr_handle h, const char* name, void* host_out, int64_t max_bytes);
+/* rr_op_bank_export_plaid: the kernels of rr_bank_export_plaid (rerank_mi355.h) over raw DEVICE pointers, without a handle, so that
+ * the row size and the table layout can be varied: table as rr_op_bank_search takes it (passages in any order, with gaps; NOT checked
+ * against the buffers), the passages first_passage .. first_passage + n_passages - 1 of it; mask_bytes / codes / residuals the row
+ * arrays, resid_row_bytes a power of two in [1, 512] (RR_ERR_UNSUPPORTED otherwise); residuals and residuals_out aligned to
+ * min(16, resid_row_bytes).  doclens_out int32 [n_passages] and offsets_out int64 [n_passages + 1] (or NULL) on the DEVICE:
+ * offsets_out[n_passages] = R.  codes_out int32 [R] / residuals_out uint8 [R, resid_row_bytes] with room for capacity_rows rows;
+ * both NULL: a sizing call.  capacity_rows < R: RR_ERR_BAD_SHAPE with NO output written, doclens_out and offsets_out included.
+ * Allocates its block per call and synchronises hip_stream. */
+int rr_op_bank_export_plaid(const void* table, int32_t first_passage, int32_t n_passages, const uint8_t* mask_bytes, const int32_t* codes,
+                            const uint8_t* residuals, int resid_row_bytes, int32_t* doclens_out, int64_t* offsets_out, int32_t* codes_out,
+                            uint8_t* residuals_out, int64_t capacity_rows, void* hip_stream);
 int rr_util_plaid_prune(const float* S, int32_t n_centroids, int Lq_coarse, const int32_t* codes, const uint8_t* mask,
                         const int32_t* lengths, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs,
                         uint8_t* cells_out, float* a1_out, float* a2_out, int32_t* list1_out, int32_t* n1_out, int32_t* list2_out,

@@ -136,6 +136,9 @@ _SIGS = {
     "rr_bank_build_ivf": (C.c_int, [_P, _P]),
     "rr_bank_ivf_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "rr_bank_ivf_read": (C.c_int, [_P, _P, _P, _P]),
+    "rr_bank_load_ivf": (C.c_int, [_P, _P, _P, C.c_int, _P]),
+    "rr_bank_export_plaid": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64), _P]),
+    "rr_op_bank_export_plaid": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int64, _P]),
     "rr_util_plaid_ivf": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "rr_util_plaid_prune": (C.c_int, [_P, C.c_int32, C.c_int, _P, _P, _P, C.c_int32, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P, _P,
                                       _P, _P]),

@@ -284,6 +284,14 @@ bool rr_filter_bits_host(const int32_t* indices, const int64_t* offsets, int row
   return true;
 }
 
+// ivf_scan_kernel for another caller (the export of a bank, bank_export.hip): the exclusive scan of counts [n] into offsets [n + 1],
+// info[0] their total, info[1] the largest
+hipError_t rr_launch_count_scan(const uint32_t* counts, int n, int64_t* offsets, int64_t* info, hipStream_t st) {
+  if (!counts || !offsets || !info || n < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), dim3(1024), 0, st, counts, n, offsets, info);
+  return hipGetLastError();
+}
+
 void rr_ivf_free(rr_ivf* f) {
   if (f->offsets) (void)hipFree(f->offsets);
   if (f->pids) (void)hipFree(f->pids);
@@ -379,6 +387,29 @@ hipError_t rr_launch_ivf_candidates(const rr_ivf& f, int C, const int32_t* cells
   hipLaunchKernelGGL(ivf_compact_kernel, dim3((unsigned)nq), dim3(IVF_COMPACT_THREADS), 0, st, bm, Wn, cand, (long long)cap, cap, ccnt, 0, a1, a2,
                      filter, n);
   return hipGetLastError();
+}
+
+// rr_bank_load_ivf: an EMPTY *out from host arrays that rr_ivf_check_host (ivf_check.h) has passed: offsets [C + 1], pids
+// [offsets[C]], over P passages, `longest` its longest list.  On a failure nothing is left allocated.  Synchronises `st`.
+hipError_t rr_ivf_load(const int64_t* offsets_host, const int32_t* pids_host, int C, int P, int32_t longest, hipStream_t st, rr_ivf* out) {
+  if (!offsets_host || C < 1 || P < 1 || out->offsets || out->pids || (offsets_host[C] > 0 && !pids_host)) return hipErrorInvalidValue;
+  rr_ivf f{};
+  f.passages = P;
+  f.postings = offsets_host[C];
+  f.longest = longest;
+  hipError_t e = hipMalloc((void**)&f.offsets, ((size_t)C + 1) * sizeof(int64_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&f.pids, (size_t)std::max<int64_t>(f.postings, 1) * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMemcpyAsync(f.offsets, offsets_host, ((size_t)C + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && f.postings > 0) e = hipMemcpyAsync(f.pids, pids_host, (size_t)f.postings * sizeof(int32_t), hipMemcpyHostToDevice, st);
+  const hipError_t es = hipStreamSynchronize(st);             // the host arrays are the caller's again
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    rr_ivf_free(&f);
+    return e;
+  }
+  *out = f;
+  return hipSuccess;
 }
 
 hipError_t rr_ivf_read(const rr_ivf& f, int C, int64_t* offsets_host, int32_t* pids_host, hipStream_t st) {

@@ -6,6 +6,7 @@
 // -> utils.py:228-254 (head); everything runs on the device, there is no CPU fallback.
 #include "../../include/rerank_mi355_diag.h"   // product ABI (rerank_mi355.h) + the diagnostic entry points
 #include "rr_common.h"
+#include "ivf_check.h"
 
 #include <climits>
 #include <cmath>
@@ -3416,6 +3417,116 @@ static int rr_op_bank_search_plaid_impl(const float* query_li, int n_queries, in
   return rc;
 }
 
+// rr_bank_export_plaid (include/rerank_mi355.h): every refusal on the host; the count, the scan and the move over the bank's device
+// passage table (csrc/bank_export.hip)
+static int rr_bank_export_plaid_impl(rr_bank* b, int32_t first_passage, int32_t n_passages, int32_t* doclens_host_out, int32_t* codes_out,
+                                     uint8_t* residuals_out, int64_t capacity_rows, int64_t* rows_host_out, void* hip_stream) {
+  const char* what = "rr_bank_export_plaid";
+  if (!b) return RR_ERR_BAD_ARG;
+  if (!doclens_host_out || !rows_host_out) return bfail(b, RR_ERR_BAD_ARG, "%s: null doclens_host_out or rows_host_out", what);
+  if ((codes_out == nullptr) != (residuals_out == nullptr))
+    return bfail(b, RR_ERR_BAD_ARG, "%s: codes_out and residuals_out are given together, or both NULL (a sizing call)", what);
+  if (!b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it holds no codes", what);
+  const long long held = (long long)b->first.size();
+  if (n_passages < 1 || first_passage < 0 || (long long)first_passage + n_passages > held)
+    return bfail(b, RR_ERR_BAD_SHAPE, "%s: passages [%d, %d + %d) of a bank that holds %lld", what, first_passage, first_passage, n_passages, held);
+  const int rb = (int)b->resid_row_bytes();
+  if (codes_out && ((((uintptr_t)codes_out) & 3) || (((uintptr_t)residuals_out) & (uintptr_t)(std::min(rb, 16) - 1))))
+    return bfail(b, RR_ERR_BAD_ARG, "%s: codes_out must be 4-byte aligned, residuals_out %d-byte", what, std::min(rb, 16));
+  if (codes_out && capacity_rows < 0) return bfail(b, RR_ERR_BAD_SHAPE, "%s: capacity_rows=%lld", what, (long long)capacity_rows);
+  hipStream_t st = (hipStream_t)hip_stream;
+  RR_TRY(bank_capture_guard(b, st, "%s cannot be captured into a graph (it allocates and synchronises)", what));
+  RR_BHIP(b, hipSetDevice(b->device));
+  if (const int rc = bank_table_current(nullptr, b, st)) return bfail(b, rc, "%s: the bank's device passage table could not be brought up to date", what);
+  int64_t R = 0;
+  const hipError_t e = rr_export_plaid(b->table + first_passage, n_passages, b->mask, b->codes, b->resid, rb, doclens_host_out, nullptr, nullptr,
+                                       codes_out, residuals_out, capacity_rows, &R, st);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return bfail(b, e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP, "%s: %d passages: %s", what, n_passages, hipGetErrorString(e));
+  }
+  if (codes_out && capacity_rows < R)
+    return bfail(b, RR_ERR_BAD_SHAPE, "%s: the passages hold %lld unmasked rows, the buffers %lld (nothing was written)", what, (long long)R,
+                 (long long)capacity_rows);
+  *rows_host_out = R;
+  return RR_OK;
+}
+
+static int rr_op_bank_export_plaid_impl(const void* table, int32_t first_passage, int32_t n_passages, const uint8_t* mask_bytes, const int32_t* codes,
+                                        const uint8_t* residuals, int resid_row_bytes, int32_t* doclens_out, int64_t* offsets_out,
+                                        int32_t* codes_out, uint8_t* residuals_out, int64_t capacity_rows, void* hip_stream) {
+  if (!table || !mask_bytes || !doclens_out || (codes_out == nullptr) != (residuals_out == nullptr)) return RR_ERR_BAD_ARG;
+  if (codes_out && (!codes || !residuals)) return RR_ERR_BAD_ARG;
+  if (!rr_export_row_bytes_ok(resid_row_bytes)) return RR_ERR_UNSUPPORTED;
+  const uintptr_t ra = (uintptr_t)(std::min(resid_row_bytes, 16) - 1);
+  if ((((uintptr_t)table) & 15) || ((((uintptr_t)doclens_out) | ((uintptr_t)codes) | ((uintptr_t)codes_out)) & 3) || (((uintptr_t)offsets_out) & 7) ||
+      ((((uintptr_t)residuals) | ((uintptr_t)residuals_out)) & ra))
+    return RR_ERR_BAD_ARG;
+  if (first_passage < 0 || n_passages < 1 || (codes_out && capacity_rows < 0)) return RR_ERR_BAD_SHAPE;
+  hipStream_t st = (hipStream_t)hip_stream;
+  int64_t R = 0;
+  const hipError_t e = rr_export_plaid((const rr_bank_slot*)table + first_passage, n_passages, mask_bytes, codes, residuals, resid_row_bytes, nullptr,
+                                       doclens_out, offsets_out, codes_out, residuals_out, capacity_rows, &R, st);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP;
+  }
+  return codes_out && capacity_rows < R ? RR_ERR_BAD_SHAPE : RR_OK;
+}
+
+// rr_bank_load_ivf (include/rerank_mi355.h): the caller's file checked on the host (ivf_check.h), uploaded beside the one the bank holds,
+// with `verify` compared with a fresh build, and put in its place only then
+static int rr_bank_load_ivf_impl(rr_bank* b, const int64_t* offsets_host, const int32_t* pids_host, int verify, void* hip_stream) {
+  const char* what = "rr_bank_load_ivf";
+  if (!b) return RR_ERR_BAD_ARG;
+  if (!offsets_host) return bfail(b, RR_ERR_BAD_ARG, "%s: null offsets", what);
+  if (!b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it holds no codes", what);
+  const long long held = (long long)b->first.size();
+  if (held < 1) return bfail(b, RR_ERR_BAD_SHAPE, "%s: the bank holds no passage", what);
+  const int C = b->n_centroids;
+  if (offsets_host[0] == 0 && offsets_host[C] > 0 && !pids_host) return bfail(b, RR_ERR_BAD_ARG, "%s: null pids", what);
+  int64_t longest = 0;
+  int list = 0;
+  char why[160];
+  if (!rr_ivf_check_host(offsets_host, pids_host, C, held, &longest, &list, why, sizeof why))
+    return bfail(b, RR_ERR_BAD_SHAPE, "%s: list %d: %s (the bank is unchanged)", what, list, why);
+  hipStream_t st = (hipStream_t)hip_stream;
+  RR_TRY(bank_capture_guard(b, st, "%s cannot be captured into a graph (it allocates and synchronises)", what));
+  RR_BHIP(b, hipSetDevice(b->device));
+  rr_ivf f{}, g{};
+  hipError_t e = rr_ivf_load(offsets_host, pids_host, C, (int)held, (int32_t)longest, st, &f);
+  bool same = true;
+  if (e == hipSuccess && verify) {                  // the guard against a file of another index: a fresh build must give these bytes
+    e = rr_ivf_build(bank_view(b), b->first.data(), b->len.data(), (int)held, st, &g);
+    if (e == hipSuccess) {
+      same = g.postings == f.postings && g.longest == f.longest;
+      if (same) {
+        std::vector<int64_t> off((size_t)C + 1);
+        std::vector<int32_t> pid((size_t)std::max<int64_t>(g.postings, 1));
+        e = rr_ivf_read(g, C, off.data(), pid.data(), st);
+        if (e == hipSuccess)
+          same = !memcmp(off.data(), offsets_host, off.size() * sizeof(int64_t)) &&
+                 (g.postings == 0 || !memcmp(pid.data(), pids_host, (size_t)g.postings * sizeof(int32_t)));
+      }
+    }
+    rr_ivf_free(&g);
+  }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    rr_ivf_free(&f);
+    return bfail(b, e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP, "%s: %lld passages, %d centroids: %s (the bank is unchanged)", what, held, C,
+                 hipGetErrorString(e));
+  }
+  if (!same) {
+    rr_ivf_free(&f);
+    return bfail(b, RR_ERR_BAD_SHAPE, "%s: the file is not the inverted file of the %lld passages this bank holds (a file of another index? "
+                 "the bank is unchanged)", what, held);
+  }
+  rr_ivf_free(&b->ivf);                             // hipFree waits for a search that still reads the previous file
+  b->ivf = f;
+  return RR_OK;
+}
+
 static int rr_util_plaid_prune_impl(const float* S, int32_t n_centroids, int Lq_coarse, const int32_t* codes, const uint8_t* mask, const int32_t* lengths,
                                     int32_t n_passages, int ncells, float threshold, int ndocs, uint8_t* cells_out, float* a1_out, float* a2_out,
                                     int32_t* list1_out, int32_t* n1_out, int32_t* list2_out, int32_t* n2_out) {
@@ -4125,6 +4236,15 @@ int rr_bank_search_plaid_ivf(rr_handle h, rr_bank_handle b, const float* query_l
 int rr_bank_build_ivf(rr_bank_handle b, void* hip_stream) { return guarded(nullptr, [&]() -> int { return rr_bank_build_ivf_impl(b, hip_stream); }); }
 int rr_bank_ivf_info(rr_bank_handle b, int32_t* passages_covered_out, int64_t* postings_out, int32_t* longest_list_out) {
   return guarded(nullptr, [&]() -> int { return rr_bank_ivf_info_impl(b, passages_covered_out, postings_out, longest_list_out); });
+}
+int rr_bank_load_ivf(rr_bank_handle b, const int64_t* offsets_host, const int32_t* pids_host, int verify, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_bank_load_ivf_impl(b, offsets_host, pids_host, verify, hip_stream); });
+}
+int rr_bank_export_plaid(rr_bank_handle b, int32_t first_passage, int32_t n_passages, int32_t* doclens_host_out, int32_t* codes_out, uint8_t* residuals_out, int64_t capacity_rows, int64_t* rows_host_out, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_bank_export_plaid_impl(b, first_passage, n_passages, doclens_host_out, codes_out, residuals_out, capacity_rows, rows_host_out, hip_stream); });
+}
+int rr_op_bank_export_plaid(const void* table, int32_t first_passage, int32_t n_passages, const uint8_t* mask_bytes, const int32_t* codes, const uint8_t* residuals, int resid_row_bytes, int32_t* doclens_out, int64_t* offsets_out, int32_t* codes_out, uint8_t* residuals_out, int64_t capacity_rows, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return rr_op_bank_export_plaid_impl(table, first_passage, n_passages, mask_bytes, codes, residuals, resid_row_bytes, doclens_out, offsets_out, codes_out, residuals_out, capacity_rows, hip_stream); });
 }
 int rr_bank_ivf_read(rr_bank_handle b, int64_t* offsets_host_out, int32_t* pids_host_out, void* hip_stream) {
   return guarded(nullptr, [&]() -> int { return rr_bank_ivf_read_impl(b, offsets_host_out, pids_host_out, hip_stream); });

@@ -543,6 +543,19 @@ void rr_ivf_free(rr_ivf* f);
 hipError_t rr_ivf_read(const rr_ivf& f, int C, int64_t* offsets_host, int32_t* pids_host, hipStream_t st);
 int64_t rr_ivf_host(const int32_t* codes, const uint8_t* mask, const int32_t* lengths, int n, int C, int64_t* offsets_out, int32_t* pids_out,
                     int64_t pids_capacity);
+// rr_bank_load_ivf: an EMPTY file filled from host arrays that rr_ivf_check_host (ivf_check.h) has passed (allocates, synchronises st)
+hipError_t rr_ivf_load(const int64_t* offsets_host, const int32_t* pids_host, int C, int P, int32_t longest, hipStream_t st, rr_ivf* out);
+// the scan of the inverted file's counts for another caller: offsets [n + 1] from counts [n], info[0] the total, info[1] the largest
+hipError_t rr_launch_count_scan(const uint32_t* counts, int n, int64_t* offsets, int64_t* info, hipStream_t st);
+// rr_bank_export_plaid / rr_op_bank_export_plaid (bank_export.hip): the unmasked rows of the passages table[0 .. n) back to back, a
+// code and rb residual bytes each (rb a power of two in [1, 512]; resid and resid_out aligned to min(rb, 16)).  rr_export_plaid
+// counts, scans, reads the row total back into *rows_out and moves: codes_out / resid_out both null is a sizing call; both given
+// with capacity_rows < *rows_out writes NOTHING and still returns hipSuccess (the caller compares).  doclens_host [n], doclens_dev
+// [n], offsets_dev int64 [n + 1]: each optional.  Allocates its block for the call and synchronises st.
+bool rr_export_row_bytes_ok(int rb);
+hipError_t rr_export_plaid(const rr_bank_slot* table, int n, const uint8_t* mask, const int32_t* codes, const uint8_t* resid, int rb,
+                           int32_t* doclens_host, int32_t* doclens_dev, int64_t* offsets_dev, int32_t* codes_out, uint8_t* resid_out,
+                           int64_t capacity_rows, int64_t* rows_out, hipStream_t st);
 // the candidate step of rr_bank_search_plaid_ivf: per query the passages of [first, first + n) in the lists of its cells
 // (cells [nq][E]) as an ascending range-relative list cand [nq][cap] with its count ccnt [nq]; -inf behind the count in a1 / a2
 // [nq][cap]; bm [nq][Wn], Wn = ceil(n / 32): scratch

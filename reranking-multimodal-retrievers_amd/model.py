@@ -954,6 +954,17 @@ class RerankEngine:
         on this engine's current stream: it allocates and synchronises.  Returns bank.ivf_info()."""
         return bank.build_ivf()
 
+    def bank_export_plaid(self, bank, first: int = 0, count: Optional[int] = None):
+        """A range of a COMPRESSED `bank` as an index stores it, on the device (rr_bank_export_plaid): (codes int32 [R], residuals
+        uint8 [R, li_dim * nbits / 8], doclens list), the unmasked rows of every passage back to back: bank.export_compressed.  A
+        save-time call on this engine's current stream: it synchronises."""
+        return bank.export_compressed(first, count)
+
+    def bank_load_ivf(self, bank, path_or_pair, verify: bool = True) -> dict:
+        """Take the inverted file of a COMPRESSED `bank` from an ivf.pid.pt (a path, or the pair it holds) instead of building it
+        (rr_bank_load_ivf), verified against a fresh build unless verify=False: bank.load_ivf.  Returns bank.ivf_info()."""
+        return bank.load_ivf(path_or_pair, verify=verify)
+
     def bank_search_plaid_ivf(self, bank, query_li: torch.Tensor, k: int, **kw) -> dict:
         """bank_search_plaid with the candidates taken from the bank's inverted file (rr_bank_search_plaid_ivf): the same
         arguments, the same checks and bit for bit the same result; the work of a query follows the lists of its cells, not the

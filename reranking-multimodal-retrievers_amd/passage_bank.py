@@ -32,8 +32,13 @@ on the matrix core and residual bucketising in two kernels, the codec's cutoffs 
 Lloyd's iteration with an exact fixed-point sum, bucket cutoffs and weights from held-out residuals; `PlaidCodec.save` writes it as an
 index stores it.  With it a compressed bank is built from a retriever's embeddings with nothing but this library.
 
-`BankTable`, `plan_bank_batch`, `plan_bank_scores`, `PlaidCodec` and `read_plaid_index` are the host side: pure Python / numpy / torch on the CPU,
-usable and tested without a device.
+`PassageBank.save_plaid_index` writes a compressed bank as the index directory the reference's indexer writes and its Searcher opens
+(`write_plaid_index`: chunk files, codec, metadata.json, ivf.pid.pt), the rows taken off the device by rr_bank_export_plaid
+(`export_compressed`: the unmasked rows of a range back to back, compacted by a kernel); `load_plaid_index(..., ivf=True)` brings the
+directory back with its inverted file (`load_ivf`, rr_bank_load_ivf) instead of rebuilding it.
+
+`BankTable`, `plan_bank_batch`, `plan_bank_scores`, `PlaidCodec`, `read_plaid_index` and `write_plaid_index` are the host side: pure Python /
+numpy / torch on the CPU, usable and tested without a device.
 """
 from __future__ import annotations
 
@@ -442,6 +447,85 @@ def read_plaid_index(index_path: str):
     return codec, chunks()
 
 
+def write_ivf(path: str, ivf) -> str:
+    """Write `ivf` = (pids int32 [postings], lengths int64 [n_centroids]) as `path`/ivf.pid.pt, torch.save((ivf, ivf_lengths)) as the
+    reference's indexer does (optimize_ivf, colbert/indexing/utils.py:8-48).  Returns the file's path."""
+    import os
+
+    import torch
+    pids, lengths = ivf
+    pids = torch.as_tensor(pids).detach().to(device="cpu", dtype=torch.int32).reshape(-1).contiguous()
+    lengths = torch.as_tensor(lengths).detach().to(device="cpu", dtype=torch.int64).reshape(-1).contiguous()
+    if int(lengths.sum()) != pids.numel() or (lengths.numel() and int(lengths.min()) < 0):
+        raise ValueError(f"write_ivf: {pids.numel()} pids for lists of {int(lengths.sum())} entries in all")
+    os.makedirs(path, exist_ok=True)
+    out = os.path.join(path, "ivf.pid.pt")
+    torch.save((pids, lengths), out)
+    return out
+
+
+def write_plaid_index(index_path: str, codec: "PlaidCodec", chunks, *, ivf=None, config: Optional[dict] = None, passage_ids=None) -> dict:
+    """Write a ColBERTv2 / PLAID index directory: what the reference's indexer writes and what its loader reads
+    (third_party/ColBERT/colbert/indexing/index_saver.py:79-90, collection_indexer.py:366-449, search/index_loader.py,
+    indexing/codecs/residual_embeddings.py:26-95), and what read_plaid_index reads.  torch and json only; nothing of colbert is
+    imported.  `chunks` yields (codes int32 [R_i], residuals uint8 [R_i, D * nbits / 8], doclens) per chunk, passages in index order.
+    Written: per chunk i `{i}.codes.pt`, `{i}.residuals.pt`, `doclens.{i}.json` (a list of ints) and `{i}.metadata.json`
+    ({"passage_offset", "num_passages", "num_embeddings", "embedding_offset"}); the codec's three files (PlaidCodec.save);
+    `metadata.json` = {"config": {"dim", "nbits", **config}, "num_chunks", "num_partitions" (the centroid count), "num_embeddings",
+    "avg_doclen"}; `ivf.pid.pt` (write_ivf) when `ivf` = (pids, lengths) is given; `passage_ids.json` when `passage_ids` is given and
+    every id is an int or a str (anything else does not survive json: the file is left out).  No plan.json: only a resumed indexing
+    run reads it.  Returns metadata.json's dict.
+    ValueError, before anything is written: a codec without cutoffs (PlaidCodec.save's).  ValueError at the chunk it concerns: doclens
+    that do not sum to the chunk's rows or hold a value below 1, residuals that are not [R_i, the codec's residual_bytes], an empty
+    chunk; no chunk at all; `passage_ids` of another count than the passages."""
+    import json
+    import os
+
+    import torch
+    if not isinstance(codec, PlaidCodec):
+        raise TypeError(f"codec must be a PlaidCodec, got {type(codec).__name__}")
+    if codec.bucket_cutoffs is None:
+        raise ValueError("save needs the codec's bucket_cutoffs: buckets.pt holds (cutoffs, weights)")
+    os.makedirs(index_path, exist_ok=True)
+    codec.save(index_path)
+    n_chunks = passages = embeddings = 0
+    for codes, res, doclens in chunks:
+        i = n_chunks
+        codes = torch.as_tensor(codes).detach().to(device="cpu", dtype=torch.int32).reshape(-1).contiguous()
+        res = torch.as_tensor(res).detach().to(device="cpu")
+        doclens = [int(x) for x in doclens]
+        R = int(codes.numel())
+        if not doclens or min(doclens) < 1 or sum(doclens) != R:
+            raise ValueError(f"write_plaid_index: chunk {i} holds {R} rows, its {len(doclens)} doclens (each at least 1) sum to {sum(doclens)}")
+        if res.dtype != torch.uint8 or tuple(res.shape) != (R, codec.residual_bytes):
+            raise ValueError(f"write_plaid_index: chunk {i}: residuals must be uint8 [{R}, {codec.residual_bytes}], got {res.dtype} "
+                             f"{tuple(res.shape)}")
+        torch.save(codes, os.path.join(index_path, f"{i}.codes.pt"))
+        torch.save(res.contiguous(), os.path.join(index_path, f"{i}.residuals.pt"))
+        with open(os.path.join(index_path, f"doclens.{i}.json"), "w") as f:
+            json.dump(doclens, f)
+        with open(os.path.join(index_path, f"{i}.metadata.json"), "w") as f:
+            f.write(json.dumps({"passage_offset": passages, "num_passages": len(doclens), "num_embeddings": R,
+                                "embedding_offset": embeddings}, indent=4) + "\n")
+        n_chunks, passages, embeddings = n_chunks + 1, passages + len(doclens), embeddings + R
+    if n_chunks == 0:
+        raise ValueError("write_plaid_index: no chunk")
+    if passage_ids is not None:
+        ids = list(passage_ids)
+        if len(ids) != passages:
+            raise ValueError(f"write_plaid_index: {len(ids)} passage ids for {passages} passages")
+        if all(isinstance(x, (int, str)) and not isinstance(x, bool) for x in ids):
+            with open(os.path.join(index_path, "passage_ids.json"), "w") as f:
+                json.dump(ids, f)
+    if ivf is not None:
+        write_ivf(index_path, ivf)
+    meta = {"config": {"dim": codec.dim, "nbits": codec.nbits, **(config or {})}, "num_chunks": n_chunks,
+            "num_partitions": codec.n_centroids, "num_embeddings": embeddings, "avg_doclen": embeddings / passages}
+    with open(os.path.join(index_path, "metadata.json"), "w") as f:
+        f.write(json.dumps(meta, indent=4) + "\n")
+    return meta
+
+
 class PassageBank:
     """An append-only device store of passage token embeddings under the caller's ids: fp16 rows, or with a `codec` (PlaidCodec)
     the residual codes of a ColBERTv2 / PLAID index, decoded on the device in every forward; one mask byte per row either way.
@@ -613,11 +697,17 @@ class PassageBank:
         self.padded_len = max(self.padded_len, int(ln.max()))
         return int(first.value)
 
-    def load_plaid_index(self, index_path: str, passage_ids: Optional[Sequence] = None) -> int:
+    def load_plaid_index(self, index_path: str, passage_ids: Optional[Sequence] = None, ivf: bool = False) -> int:
         """Fill a compressed bank from a ColBERTv2 / PLAID index directory (read_plaid_index), chunk by chunk through
         add_compressed.  The bank's codec must hold the index's tables (create the bank with the codec read_plaid_index returns).
-        `passage_ids`: the caller's id of passage number i of the index at position i; default: the passage numbers themselves.
+        `passage_ids`: the caller's id of passage number i of the index at position i; default: the ids of the directory's
+        passage_ids.json when it has one (save_plaid_index writes it), else the passage numbers themselves.
+        `ivf`: also load the directory's ivf.pid.pt (load_ivf, verified against the bank) instead of leaving the inverted file to a
+        build_ivf; the file numbers passages as the index does, so the bank must be empty before the call (ValueError).
         Returns the number of passages added."""
+        import json
+        import os
+
         import torch
         codec, chunks = read_plaid_index(index_path)
         mine = self.codec
@@ -627,6 +717,13 @@ class PassageBank:
                 or not torch.equal(mine.bucket_weights, codec.bucket_weights):
             raise ValueError(f"{index_path}: the index's codec (nbits {codec.nbits}, dim {codec.dim}, {codec.n_centroids} centroids) is "
                              "not the bank's")
+        if ivf and len(self.table):
+            raise ValueError(f"load_plaid_index(ivf=True): the bank holds {len(self.table)} passages already; ivf.pid.pt numbers "
+                             "passages from 0 (build_ivf after the load instead)")
+        ids_file = os.path.join(index_path, "passage_ids.json")
+        if passage_ids is None and os.path.exists(ids_file):
+            with open(ids_file) as f:
+                passage_ids = json.load(f)
         added = 0
         for first, codes, res, doclens in chunks:
             ids = list(range(first, first + len(doclens))) if passage_ids is None else list(passage_ids[first:first + len(doclens)])
@@ -634,7 +731,85 @@ class PassageBank:
                 raise ValueError(f"{len(passage_ids)} passage ids for an index of more than {first + len(ids)} passages")
             self.add_compressed(ids, codes, res, doclens)
             added += len(doclens)
+        if ivf:
+            self.load_ivf(index_path)
         return added
+
+    def export_compressed(self, first: int = 0, count: Optional[int] = None):
+        """The passages first .. first + count - 1 (dense indices; None: through the last) as an index stores them, on the device
+        (rr_bank_export_plaid): (codes int32 [R], residuals uint8 [R, D * nbits / 8], doclens list): the UNMASKED rows of every
+        passage back to back, doclens[i] of passage first + i (0 for a passage with no unmasked row).  Masked rows do not travel:
+        a bank filled from the result scores and searches like this one, but it is no snapshot of the masked rows.  One sizing
+        call, an allocation of exactly R rows, one export call; it synchronises the current stream.  An fp16 bank raises
+        NotImplementedError, a range outside the bank ValueError."""
+        first, n = int(first), (len(self.table) - int(first) if count is None else int(count))
+        doclens, R = self._export_sizes(first, n)
+        codes, res = self._export_rows(first, n, R)
+        return codes, res, doclens
+
+    def _export_sizes(self, first: int, n: int):
+        """The sizing call of rr_bank_export_plaid: (doclens list, R)."""
+        import numpy as np
+        if self.codec is None:
+            raise NotImplementedError("export_compressed on an fp16 bank: it holds no codes")
+        doclens = np.empty(max(n, 1), dtype=np.int32)
+        R = C.c_int64(-1)
+        self._check(self.lib.rr_bank_export_plaid(self.h, first, n, doclens.ctypes.data, None, None, 0, C.byref(R), self._stream()),
+                    "rr_bank_export_plaid", bad_shape=ValueError)
+        return doclens[:n].tolist(), int(R.value)
+
+    def _export_rows(self, first: int, n: int, R: int):
+        """The export call of rr_bank_export_plaid into tensors of exactly R rows (from _export_sizes): (codes, residuals)."""
+        import numpy as np
+        import torch
+        codes = torch.empty(R, device=self.device, dtype=torch.int32)
+        res = torch.empty((R, self.codec.residual_bytes), device=self.device, dtype=torch.uint8)
+        if R:
+            doclens = np.empty(n, dtype=np.int32)
+            got = C.c_int64(-1)
+            self._check(self.lib.rr_bank_export_plaid(self.h, first, n, doclens.ctypes.data, codes.data_ptr(), res.data_ptr(), R, C.byref(got),
+                                                      self._stream()), "rr_bank_export_plaid", bad_shape=ValueError)
+            assert int(got.value) == R, f"the export moved {int(got.value)} rows, the sizing call counted {R}"
+        return codes, res
+
+    def save_plaid_index(self, index_path: str, chunk_passages: int = 25000, ivf: bool = True, config: Optional[dict] = None) -> dict:
+        """Write the bank as a ColBERTv2 / PLAID index directory (write_plaid_index) that read_plaid_index / load_plaid_index and the
+        reference's loader open: the bank walked in chunks of `chunk_passages` passages (the reference's chunk size:
+        collection_indexer.py's min(25000, ...)), each exported on the device (rr_bank_export_plaid) and copied to the host; the
+        codec; metadata.json ({"dim", "nbits", **config} as its config); the passage ids as passage_ids.json when they are ints or
+        strs; with `ivf` the bank's inverted file as ivf.pid.pt, built first when the bank has none or it covers fewer passages than
+        the bank holds.  The index holds the unmasked rows only, as the reference's indexer would have stored the passages.
+        Every sizing call runs before the first file is written: a bank with a passage that has no unmasked row cannot be
+        represented (an index's doclens are at least 1) and raises ValueError naming up to eight ids, with nothing written.  An
+        fp16 bank raises NotImplementedError, a codec without cutoffs PlaidCodec.save's ValueError, an empty bank ValueError.
+        Returns metadata.json's dict."""
+        if self.codec is None:
+            raise NotImplementedError("save_plaid_index on an fp16 bank: it holds no codes")
+        if self.codec.bucket_cutoffs is None:
+            raise ValueError("save needs the codec's bucket_cutoffs: buckets.pt holds (cutoffs, weights)")
+        P, step = len(self.table), int(chunk_passages)
+        if P < 1 or step < 1:
+            raise ValueError(f"save_plaid_index: {P} passages in chunks of {step}")
+        plan, empty = [], []
+        for first in range(0, P, step):
+            n = min(step, P - first)
+            doclens, R = self._export_sizes(first, n)
+            empty += [self.table.ids[first + i] for i, d in enumerate(doclens) if d < 1]
+            plan.append((first, n, doclens, R))
+        if empty:
+            raise ValueError(f"save_plaid_index: {len(empty)} passages have no unmasked row, which an index cannot hold (doclens are at "
+                             f"least 1): {', '.join(repr(x) for x in empty[:8])}{' ...' if len(empty) > 8 else ''}")
+        pair = None
+        if ivf:
+            if self.ivf_info()["passages_covered"] < P:
+                self.build_ivf()
+            pair = self.ivf()
+
+        def chunks():
+            for first, n, doclens, R in plan:
+                codes, res = self._export_rows(first, n, R)
+                yield codes.cpu(), res.cpu(), doclens
+        return write_plaid_index(index_path, self.codec, chunks(), ivf=pair, config=config, passage_ids=self.table.ids)
 
     def lookup(self, passage_ids: Sequence):
         """(indices, lengths) of `passage_ids`; KeyError names an id the bank does not hold."""
@@ -772,12 +947,41 @@ class PassageBank:
         """Write the inverted file as `path`/ivf.pid.pt, torch.save((ivf, ivf_lengths)) as the reference's indexer does
         (optimize_ivf, colbert/indexing/utils.py:8-48), beside what PlaidCodec.save writes.  The pids are dense bank indices: they
         are the reference's passage numbers when the bank was filled in the index's order.  Returns the file's path."""
+        return write_ivf(path, self.ivf())
+
+    def load_ivf(self, path_or_pair, verify: bool = True) -> dict:
+        """Take the inverted file from an ivf.pid.pt instead of building it (rr_bank_load_ivf): `path_or_pair` is the file, the
+        index directory that holds it, or the pair (pids int32 [postings], lengths [n_centroids]) itself; the lengths are summed
+        into offsets here.  The file must cover every passage the bank holds now under its dense indices (an index loaded into an
+        empty bank in the index's order).  The library checks it on the host (offsets from 0 that do not decrease, pids inside
+        the bank, every list strictly ascending) and, with `verify`, compares it with a fresh build over the bank, which is what
+        catches the file of another index; verify=False trusts the caller and costs the upload alone.  ValueError for a file that
+        fails a check or the comparison, with the previous file kept; an fp16 bank raises NotImplementedError.  A load-time call:
+        it allocates and synchronises the current stream.  Returns ivf_info()."""
         import os
+
         import torch
-        os.makedirs(path, exist_ok=True)
-        out = os.path.join(path, "ivf.pid.pt")
-        torch.save(self.ivf(), out)
-        return out
+        if self.codec is None:
+            raise NotImplementedError("load_ivf on an fp16 bank: it holds no centroid codes")
+        pair = path_or_pair
+        if isinstance(pair, (str, os.PathLike)):
+            path = os.path.join(pair, "ivf.pid.pt") if os.path.isdir(pair) else os.fspath(pair)
+            try:
+                pair = torch.load(path, map_location="cpu", weights_only=True)
+            except TypeError:                                   # a torch without weights_only
+                pair = torch.load(path, map_location="cpu")
+        pids, lengths = pair
+        pids = torch.as_tensor(pids).detach().to(device="cpu", dtype=torch.int32).reshape(-1).contiguous()
+        lengths = torch.as_tensor(lengths).detach().to(device="cpu", dtype=torch.int64).reshape(-1)
+        if lengths.numel() != self.codec.n_centroids:
+            raise ValueError(f"load_ivf: {lengths.numel()} lists, the codec holds {self.codec.n_centroids} centroids")
+        offsets = torch.zeros(lengths.numel() + 1, dtype=torch.int64)
+        offsets[1:] = torch.cumsum(lengths, 0)
+        if int(offsets[-1]) != pids.numel():
+            raise ValueError(f"load_ivf: {pids.numel()} pids for lists of {int(offsets[-1])} entries in all")
+        self._check(self.lib.rr_bank_load_ivf(self.h, offsets.data_ptr(), pids.data_ptr() if pids.numel() else None, int(bool(verify)),
+                                              self._stream()), "rr_bank_load_ivf", bad_shape=ValueError)
+        return self.ivf_info()
 
     def clear(self) -> None:
         """Forget every passage (rr_bank_clear; the capacity stays; the inverted file goes).  Forwards that read the bank must have completed."""

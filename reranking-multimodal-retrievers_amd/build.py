@@ -13,12 +13,13 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librerank_mi355.so")
-SOURCES = ["rr_api.hip", "gemm_bf16.hip", "gemm_fp8.hip", "attention_bf16.hip", "elementwise.hip", "head.hip", "pair_assembly.hip", "li_scores.hip", "passage_bank.hip", "bank_search.hip", "bank_search_plaid.hip", "bank_compress.hip", "plaid_train.hip", "bank_ivf.hip", "bank_export.hip",
+SOURCES = ["rr_api.hip", "bank_api.hip", "gemm_bf16.hip", "gemm_fp8.hip", "attention_bf16.hip", "elementwise.hip", "head.hip", "pair_assembly.hip", "li_scores.hip", "passage_bank.hip", "bank_search.hip", "bank_search_plaid.hip", "bank_compress.hip", "plaid_train.hip", "bank_ivf.hip", "bank_export.hip",
            "pair_tokenizer.cpp"]
 HEADERS = [os.path.join(CSRC, "rr_common.h"), os.path.join(os.path.dirname(HERE), "include", "rerank_mi355.h"),
            os.path.join(os.path.dirname(HERE), "include", "rerank_mi355_diag.h"),
            os.path.join(CSRC, "unicode_tables.h"), os.path.join(CSRC, "plaid_decode.h"), os.path.join(CSRC, "li_sources.h"),
-           os.path.join(CSRC, "rank_order.h"), os.path.join(CSRC, "plaid_assign.h"), os.path.join(CSRC, "ivf_check.h")]
+           os.path.join(CSRC, "rank_order.h"), os.path.join(CSRC, "plaid_assign.h"), os.path.join(CSRC, "ivf_check.h"),
+           os.path.join(CSRC, "rr_api_internal.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-slp-vectorize: no compiler-formed v_pk_*_f32.  Root cause of the corruption it was added for (round 2, ISA and
 # measurements in profiles/r02_slp_hazard_isa.txt, tools/slp_hazard_probe.py): with SLP on, the LayerNorm-residual

@@ -454,7 +454,7 @@ struct rr_padded_rows { const void* src; int src_f16; const float* mask; const r
 hipError_t rr_launch_bank_ingest(const rr_padded_rows& in, int D, uint16_t* rows, uint8_t* mask_bytes, hipStream_t st);
 // The context rows of a bank as the launchers take them, fp16 or compressed (PLAID residual codes): nbits == 0: `rows` [.][D] fp16
 // bits; else codes [.] int32, resid [.][D * nbits / 8], centroids [n_centroids][D] fp16 bits, weights [2^nbits] float32.  mask:
-// one byte per row.  All on the device.  rr_api.hip builds it from an rr_bank (bank_view), the diagnostic operators from their
+// one byte per row.  All on the device.  bank_api.hip builds it from an rr_bank (bank_view), the diagnostic operators from their
 // loose pointers; every launcher below decides between the two kinds inside.
 struct rr_bank_view {
   int nbits, n_centroids;

@@ -3,7 +3,7 @@ rr_bank_search, rr_bank_add, rr_bank_add_plaid and rr_bank_add_compress — and 
 rr_bank_read, rr_bank_read_plaid and rr_bank_set_plaid_cutoffs (include/rerank_mi355.h).
 
 The other bank suites sample these messages by substring; here the return code and the COMPLETE rr_last_error /
-rr_bank_last_error string of each is pinned, written out by hand from the format strings of csrc/rr_api.hip, on an fp16 bank and
+rr_bank_last_error string of each is pinned, written out by hand from the format strings of csrc/bank_api.hip, on an fp16 bank and
 on an nbits = 2 bank of three passages (2, 5 and 3 rows) with Lq = 4.  Every call is refused on the host before anything is
 enqueued: an output buffer a call was handed keeps its sentinel, a bank keeps its contents.
 

@@ -1,6 +1,6 @@
 """GPU: the two stop-after switches of the pruned bank search (rr_set_tuning "plaid_stop_after" for rr_bank_search_plaid,
 "plaid_ivf_stop_after" for rr_bank_search_plaid_ivf) and what a call books per stage, on the one plan, stage driver and cost routine
-both forms share (csrc/bank_search_plaid.hip, csrc/rr_api.hip).
+both forms share (csrc/bank_search_plaid.hip, csrc/bank_api.hip).
 
 For each form and each legal stop value, on poisoned outputs: the call returns RR_OK; below the last stage the outputs are still
 poison, bit for bit; at the last stage they equal, bit for bit, the outputs of a call made before any switch was touched.  A value

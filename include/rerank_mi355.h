@@ -732,7 +732,7 @@ int rr_bank_li_scores(rr_handle h, rr_bank_handle b, const float* query_li, int 
  * per query are returned, so no recall is lost to pruning.  Handles, bank formats and li_dim as rr_bank_li_scores takes them.
  *   query_li [n_queries, Lq, li_dim] : DEVICE float32, 16-byte aligned; no query mask.  n_queries <= 65535.
  *   first_passage, n_passages : the bank indices first_passage .. first_passage + n_passages - 1 are searched; n_passages = -1:
- *       through the last passage.  (A rank can search its slice of a bank; merging the results of ranks is the caller's.)
+ *       through the last passage.  (A rank can search its slice of a bank; rr_bank_merge_topk merges the results of ranks.)
  *   indices_out : DEVICE int32 [n_queries, k], bank indices.   scores_out : DEVICE float32 [n_queries, k], or NULL.
  *   k : 1 <= k <= min(n_passages, 1024).  A selection pass sorts slices of 4096 candidates in LDS (as rr_head's rank does) and
  *       keeps k of each: with k <= 1024 every pass shrinks the list at least fourfold, so the passes end after
@@ -754,7 +754,7 @@ int rr_bank_li_scores(rr_handle h, rr_bank_handle b, const float* query_li, int 
  * misaligned pointers, bank and handle on different devices, a full-context handle (RR_ERR_BAD_ARG); a different li_dim,
  * non-positive sizes, a range that is empty or not inside the bank, k < 1 or k > n_passages (RR_ERR_BAD_SHAPE).
  * LIMITS: k <= 1024; not capturable into a graph (RR_ERR_BAD_ARG under stream capture: the call may upload the table and grow
- * its block); one device (no merge across ranks: search ranges and merge the k-lists yourself); every passage of the range competes (restrict
+ * its block); one device per call (a bank split over ranks or banks: search each part and merge the k-lists with rr_bank_merge_topk below); every passage of the range competes (restrict
  * by range, by a candidate filter with rr_bank_search_filtered below, or prune by centroid with rr_bank_search_plaid).  (Python: RerankEngine.bank_search, PassageBank.search,
  * InteractionRerankModel.retrieve / retrieve_and_rerank.) */
 int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage,
@@ -801,7 +801,7 @@ int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_q
  * k2 = min(ndocs / 4, n): 4 nq Cp Lq + 16 nq Cp / 64 + Cp + 4 nq Lq_coarse ncells + 8 nq W + 8 nq n + 4 nq (k1 + k2 + 1)
  * + 8 * (n > 4096 ? nq ceil(n / 4096) k1 : 0) bytes.
  * Checked on the host BEFORE anything is enqueued; a refused call writes nothing.  Not capturable into a graph (RR_ERR_BAD_ARG).
- * Out of scope: ndocs > 1024, merging across ranks, fp16 banks.  A caller-supplied candidate filter: rr_bank_search_plaid_filtered
+ * Out of scope: ndocs > 1024, fp16 banks.  A bank split over ranks: the per-part results merged by rr_bank_merge_topk below (which DEFINES the sharded pruned search).  A caller-supplied candidate filter: rr_bank_search_plaid_filtered
  * below; candidates from an IVF: rr_bank_build_ivf / rr_bank_search_plaid_ivf below.  (Python:
  * RerankEngine.bank_search_plaid, PlaidSearch with PassageBank.search / InteractionRerankModel.retrieve / retrieve_and_rerank.) */
 int rr_bank_search_plaid(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse,
@@ -858,7 +858,7 @@ int rr_bank_search_plaid(rr_handle h, rr_bank_handle b, const float* query_li, i
  * + 4 nq Lq_coarse ncells + 8 nq W + 4 nq Wn + 12 nq cap + 4 nq (k1 + k2 + 2) + 8 * (cap > 4096 ? nq ceil(cap / 4096) k1 : 0)
  * bytes: with cap <= n never more than rr_bank_search_plaid's but for the bitmap and the candidate list (8 nq n against
  * 4 nq (n / 32 + 3 cap)).  Ten launches, a memset and the selection passes, booked in the profile's `tail` class.
- * LIMITS: those of rr_bank_search_plaid (ndocs <= 1024, one device, compressed banks); rr_bank_search_plaid_tap does not cover
+ * LIMITS: those of rr_bank_search_plaid (ndocs <= 1024, one device per call with rr_bank_merge_topk behind it for a split bank, compressed banks); rr_bank_search_plaid_tap does not cover
  * this entry.  Under a candidate filter: rr_bank_search_plaid_ivf_filtered below.  (Python: RerankEngine.bank_build_ivf / bank_search_plaid_ivf, PassageBank.build_ivf / ivf / save_ivf / load_ivf,
  * PlaidSearch(..., ivf=True).) */
 int rr_bank_build_ivf(rr_bank_handle b, void* hip_stream);
@@ -964,6 +964,60 @@ int rr_bank_search_plaid_ivf_filtered(rr_handle h, rr_bank_handle b, const float
                                       float* scores_out, int32_t* counts_out, void* hip_stream);
 int rr_bank_filter_fill(rr_bank_handle b, const int32_t* indices_host, const int64_t* offsets_host, int rows, int exclude,
                         uint32_t* filter_bits, int64_t filter_ld, void* hip_stream);
+
+/* rr_bank_merge_topk: the k-lists of P parts of a corpus (the banks of P ranks, several banks of one process, or ranges of one
+ * bank) merged into one list over GLOBAL indices, on the device.  What a bank split over ranks needs behind its searches.
+ * THE MERGED LIST.
+ * Inputs:
+ *   P = n_parts, 1 <= P <= 64.   nq = n_queries, 1 <= nq <= 65535.
+ *   Per part p and query q a list of k_in entries:
+ *     indices_in[p][q][i] : int32, LOCAL indices of part p.
+ *     scores_in[p][q][i]  : float32.
+ *     counts_in[p][q]     : int32, or counts_in NULL: every list holds k_in entries.
+ *   part_offsets_host : HOST int32 [P + 1].  Part p stands for the global indices part_offsets[p] .. part_offsets[p + 1] - 1.
+ * Rules:
+ *   - Entry (p, q, i) is REAL iff i < clamp(counts_in[p][q], 0, k_in) and 0 <= indices_in[p][q][i] < part_offsets[p + 1] -
+ *     part_offsets[p].  Its global index is g = part_offsets[p] + indices_in[p][q][i].
+ *   - The score takes part as it is: NaN, +-inf and -0 included.  Inside the count, -inf is a number like any other.
+ *   - Nothing is assumed about the order of the incoming lists.
+ *   - Per query, the real entries of all parts are ordered by the one rank order of the searches on (score, g): NaN first, higher
+ *     score, equal scores (+0 == -0) by ascending g (rank_key(score, g) of csrc/rank_order.h, a larger key first).
+ *   - The first min(k, real entries) are written to indices_out[q][.] (the global index g), scores_out[q][.] (or NULL: the bits of
+ *     the entry's score, a -0 and a NaN's payload included) and parts_out[q][.] (or NULL: the part p the entry came from).
+ *     counts_out[q] (required) gets their number.  Behind the count the rows hold -1 / -inf / -1 up to k.
+ *   - A local index listed twice within a part appears twice.  Entries that agree in part, index and rank of the score (two +-0,
+ *     two NaNs) keep the order they have in their list: the order of a STABLE sort of the entries taken part by part.
+ *   - 1 <= k <= k_in.  The global top k is contained in the union of the per-part top k_in only for k <= k_in, and the call
+ *     promises exactly that.
+ * PROPERTY.  Let part p hold the rr_bank_search result, with k_in >= k, of a bank holding the passages part_offsets[p] .. of a
+ * corpus in corpus order.  Then the merged list is, byte for byte, rr_bank_search with k over one bank holding the whole corpus.
+ * The same holds for the ranges [first, first + n) of one bank, each list made local again (index - first).  It holds for
+ * rr_bank_search_filtered, with counts.  It holds for rr_bank_search_plaid* with ncells = n_centroids and ndocs / 4 >= every
+ * part's size.  IN GENERAL a sharded PLAID search is DEFINED as the merge of the per-part PLAID searches with the same
+ * parameters; it is NOT the PLAID search of the union, because each part keeps its own ndocs survivors.  A part with fewer than k
+ * passages is searched with its own size as k and padded, with its count saying so.
+ * Arrays: every in and out array is DEVICE, 4-byte aligned.  part_stride is the distance in 4-byte words from part p to part p + 1,
+ * the same for indices_in and scores_in, >= n_queries * k_in; count_stride likewise for counts_in, >= n_queries.  So the block an
+ * all-gather delivers serves directly, [P][ indices | score bits | counts | ... ], as three base pointers into one buffer.  No
+ * further layout is imposed.  indices_out / scores_out / parts_out [n_queries, k], counts_out [n_queries].
+ * One kernel (csrc/bank_merge.hip), one workgroup per query, booked in the profile's `tail` class: the 64-bit keys of the P * k_in
+ * entries, padded with key 0 to the next power of two, are sorted in LDS by the bitonic network and the first k leave; a winner's
+ * part is found by a search of g in part_offsets, which travels as a kernel argument.  No global atomics, nothing depends on
+ * scheduling: the same bytes from run to run.  Nothing is allocated, nothing staged; the handle's search block is not touched.
+ * REFUSALS, every one from the host before anything is enqueued; a refused call writes nothing; the sentence: rr_last_error(h).
+ *   RR_ERR_BAD_ARG     : a NULL handle, indices_in, scores_in, part_offsets_host, indices_out or counts_out; a misaligned
+ *                        pointer; a full-context handle; a capturing stream (as every bank search refuses them).
+ *   RR_ERR_BAD_SHAPE   : n_parts, n_queries, k_in or k non-positive; k > k_in; a stride below its minimum; part_offsets_host[0] < 0
+ *                        or a descending offset (an empty part is allowed).
+ *   RR_ERR_UNSUPPORTED : n_parts > 64; n_queries > 65535; n_parts * k_in > 8192 (8 ranks of the largest k the searches take: 64 KB
+ *                        of keys).
+ * LIMITS: the parts' lists must already be on this device (the collective is the caller's: Python sharding.ShardedBank does it with
+ * one all-gather); int32 global indices, so a corpus of at most 2^31 - 1 passages.  In host code: rr_util_bank_merge_topk
+ * (rerank_mi355_diag.h).  (Python: RerankEngine.bank_merge_topk, passage_bank.search_banks, sharding.ShardedBank /
+ * exchange_bank_results / sharded_retrieve_and_rerank.) */
+int rr_bank_merge_topk(rr_handle h, const int32_t* indices_in, const float* scores_in, const int32_t* counts_in, int64_t part_stride,
+                       int64_t count_stride, int n_parts, const int32_t* part_offsets_host, int n_queries, int k_in, int k,
+                       int32_t* indices_out, float* scores_out, int32_t* counts_out, int32_t* parts_out, void* hip_stream);
 
 /* rr_head_joint: rr_head with the head RerankModel.forward runs (rr_forward_joint): `loss_fn(logits, logits)`
  * (rerank_model.py:328) — the labels are the logits themselves (2H_BCE: the two heads as class-probability targets).  The

@@ -386,6 +386,18 @@ int rr_util_plaid_ivf(const int32_t* codes, const uint8_t* mask, const int32_t* 
                       int64_t* offsets_out, int32_t* pids_out, int64_t pids_capacity, int64_t* postings_out);
 int rr_util_bank_filter_bits(const int32_t* indices, const int64_t* offsets, int rows, int exclude, int32_t passages,
                              uint32_t* bits_out, int64_t filter_ld);
+/* rr_op_bank_merge_topk: the kernel of rr_bank_merge_topk (rerank_mi355.h, "THE MERGED LIST") over raw DEVICE pointers, without a
+ * handle: the same arguments, the same refusals in the same order (a capturing stream included; no handle, so no sentence and no
+ * profile).
+ * rr_util_bank_merge_topk: THE MERGED LIST in pure HOST code, usable without a GPU: the written-down definition the kernel is held to
+ * (the real entries of a query taken part by part, sorted stably by the rank key).  The same arguments over HOST arrays, the same
+ * checks and refusals; a refused call writes nothing. */
+int rr_op_bank_merge_topk(const int32_t* indices_in, const float* scores_in, const int32_t* counts_in, int64_t part_stride,
+                          int64_t count_stride, int n_parts, const int32_t* part_offsets_host, int n_queries, int k_in, int k,
+                          int32_t* indices_out, float* scores_out, int32_t* counts_out, int32_t* parts_out, void* hip_stream);
+int rr_util_bank_merge_topk(const int32_t* indices_in, const float* scores_in, const int32_t* counts_in, int64_t part_stride,
+                            int64_t count_stride, int n_parts, const int32_t* part_offsets, int n_queries, int k_in, int k,
+                            int32_t* indices_out, float* scores_out, int32_t* counts_out, int32_t* parts_out);
 #ifdef __cplusplus
 }
 #endif

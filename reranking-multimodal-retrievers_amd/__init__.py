@@ -10,11 +10,12 @@ Importing the package does not need a GPU; constructing a model does (no CPU fal
 from ._lib import EXPORTED, LIB_PATH  # noqa: F401
 from .model import (FullContextRerankModel, InteractionRerankModel, RerankModel, RerankEngine, RerankOutput, make_arch,  # noqa: F401
                     synthetic_state_dict, weight_spec)
-from .sharding import shard_range, ShardedReranker, sharded_forward_lists  # noqa: F401
+from .sharding import (ShardedBank, ShardedReranker, combine_owned, exchange_bank_results, rerank_owned, shard_range,  # noqa: F401
+                       sharded_forward_lists, sharded_retrieve_and_rerank)
 from .ranking import rank_descending_stable, recall_precision_at_k  # noqa: F401
 from .evaluate import build_records, compute_rerank_scores, rerank_dataset  # noqa: F401
 from .pipeline import rerank_dataset_pipelined  # noqa: F401
 from .passage_bank import (BankFilter, BankTable, PassageBank, PlaidCodec, PlaidSearch, plaid_num_partitions, plan_bank_batch,  # noqa: F401
-                           plan_bank_scores, read_plaid_index, write_ivf, write_plaid_index)
+                           plan_bank_scores, read_plaid_index, search_bank_part, search_banks, write_ivf, write_plaid_index)
 
 __version__ = "0.1.0"

@@ -1099,6 +1099,72 @@ int rr_util_plaid_prune(const float* S, int32_t n_centroids, int Lq_coarse, cons
   });
 }
 
+// rr_bank_merge_topk (include/rerank_mi355.h, THE MERGED LIST): every refusal on the host, then one launch; nothing is allocated and
+// the handle's search block is not touched
+static int bank_merge_call(rr_handle h, const int32_t* indices_in, const float* scores_in, const int32_t* counts_in, int64_t part_stride,
+                           int64_t count_stride, int n_parts, const int32_t* part_offsets_host, int n_queries, int k_in, int k,
+                           int32_t* indices_out, float* scores_out, int32_t* counts_out, int32_t* parts_out, void* hip_stream) {
+  const char* what = "rr_bank_merge_topk";
+  if (!h) return RR_ERR_BAD_ARG;
+  rr_model* m = h;
+  if (m->cfg.model_kind == RR_MODEL_FULL_CONTEXT) return fail(m, RR_ERR_BAD_ARG, "%s on a full-context model", what);
+  char msg[256];
+  if (const int rc = rr_merge_check(indices_in, scores_in, counts_in, part_stride, count_stride, n_parts, part_offsets_host, n_queries, k_in, k,
+                                    indices_out, scores_out, counts_out, parts_out, msg, sizeof msg))
+    return fail(m, rc, "%s: %s", what, msg);
+  hipStream_t st = (hipStream_t)hip_stream;
+  RR_TRY(capture_guard(m, st, "%s cannot be captured into a graph (no bank search can, and it reads what they wrote)", what));
+  RR_HIP(m, hipSetDevice(m->cfg.device));
+  m->last_stream = st;
+  // bytes: every entry's index and score, the counts, the rows that leave
+  const double bytes = 8.0 * n_parts * (double)n_queries * k_in + 4.0 * n_parts * (double)n_queries + 12.0 * n_queries * (double)k;
+  RR_RUN(m, st, RR_K_TAIL, 0.0, bytes,
+         rr_launch_bank_merge(indices_in, scores_in, counts_in, part_stride, count_stride, n_parts, part_offsets_host, n_queries, k_in, k,
+                              indices_out, scores_out, counts_out, parts_out, st));
+  return RR_OK;
+}
+
+int rr_bank_merge_topk(rr_handle h, const int32_t* indices_in, const float* scores_in, const int32_t* counts_in, int64_t part_stride,
+                       int64_t count_stride, int n_parts, const int32_t* part_offsets_host, int n_queries, int k_in, int k,
+                       int32_t* indices_out, float* scores_out, int32_t* counts_out, int32_t* parts_out, void* hip_stream) {
+  return guarded(h, [&]() -> int {
+    return bank_merge_call(h, indices_in, scores_in, counts_in, part_stride, count_stride, n_parts, part_offsets_host, n_queries, k_in, k,
+                           indices_out, scores_out, counts_out, parts_out, hip_stream);
+  });
+}
+
+// rr_op_bank_merge_topk (include/rerank_mi355_diag.h): the same launch over raw device pointers, without a handle
+int rr_op_bank_merge_topk(const int32_t* indices_in, const float* scores_in, const int32_t* counts_in, int64_t part_stride, int64_t count_stride,
+                          int n_parts, const int32_t* part_offsets_host, int n_queries, int k_in, int k, int32_t* indices_out,
+                          float* scores_out, int32_t* counts_out, int32_t* parts_out, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int {
+    char msg[256];
+    if (const int rc = rr_merge_check(indices_in, scores_in, counts_in, part_stride, count_stride, n_parts, part_offsets_host, n_queries, k_in,
+                                      k, indices_out, scores_out, counts_out, parts_out, msg, sizeof msg))
+      return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    RR_TRY(capture_guard(nullptr, st, "%s cannot be captured into a graph", "rr_op_bank_merge_topk"));
+    const hipError_t e = rr_launch_bank_merge(indices_in, scores_in, counts_in, part_stride, count_stride, n_parts, part_offsets_host, n_queries,
+                                              k_in, k, indices_out, scores_out, counts_out, parts_out, st);
+    return e == hipSuccess ? RR_OK : RR_ERR_HIP;
+  });
+}
+
+// rr_util_bank_merge_topk: THE MERGED LIST in pure host code over host arrays, behind the same refusals
+int rr_util_bank_merge_topk(const int32_t* indices_in, const float* scores_in, const int32_t* counts_in, int64_t part_stride, int64_t count_stride,
+                            int n_parts, const int32_t* part_offsets, int n_queries, int k_in, int k, int32_t* indices_out, float* scores_out,
+                            int32_t* counts_out, int32_t* parts_out) {
+  return guarded(nullptr, [&]() -> int {
+    char msg[256];
+    if (const int rc = rr_merge_check(indices_in, scores_in, counts_in, part_stride, count_stride, n_parts, part_offsets, n_queries, k_in, k,
+                                      indices_out, scores_out, counts_out, parts_out, msg, sizeof msg))
+      return rc;
+    rr_bank_merge_host(indices_in, scores_in, counts_in, part_stride, count_stride, n_parts, part_offsets, n_queries, k_in, k, indices_out,
+                       scores_out, counts_out, parts_out);
+    return RR_OK;
+  });
+}
+
 // ---- the entry points that share a body above (run through guarded(): no C++ exception crosses the ABI), and the small ones
 int rr_bank_clear(rr_bank_handle b) {
   if (!b) return RR_ERR_BAD_ARG;

@@ -532,6 +532,21 @@ size_t rr_topk_select_scratch(int n_lists, int n, int k);
 hipError_t rr_launch_topk_select(const float* scores, int n_lists, int n, int k, int add, int32_t* tmp_a, int32_t* tmp_b,
                                  int32_t* indices_out, float* scores_out, hipStream_t st);
 int rr_set_search_chunk(int passages);      // rr_set_tuning("search_chunk"): 4 .. 128, -1 outside
+// rr_bank_merge_topk (bank_merge.hip; "THE MERGED LIST", include/rerank_mi355.h): per-part k-lists over local indices into one list
+// over global indices, one workgroup per query.  rr_merge_check: what the three entry points refuse alike before anything is read
+// or written (RR_OK, or the status with its sentence in msg); rr_launch_bank_merge and rr_bank_merge_host (the definition in host
+// code) take arguments it has passed.
+constexpr int RR_MERGE_MAX_PARTS = 64;
+constexpr int RR_MERGE_MAX_ENTRIES = 8192;  // n_parts * k_in: 64 KB of keys
+int rr_merge_check(const void* indices_in, const void* scores_in, const void* counts_in, long long part_stride, long long count_stride,
+                   int n_parts, const int32_t* part_offsets, int n_queries, int k_in, int k, const void* indices_out, const void* scores_out,
+                   const void* counts_out, const void* parts_out, char* msg, size_t msg_len);
+hipError_t rr_launch_bank_merge(const int32_t* indices_in, const float* scores_in, const int32_t* counts_in, long long part_stride,
+                                long long count_stride, int n_parts, const int32_t* part_offsets_host, int n_queries, int k_in, int k,
+                                int32_t* indices_out, float* scores_out, int32_t* counts_out, int32_t* parts_out, hipStream_t st);
+void rr_bank_merge_host(const int32_t* indices_in, const float* scores_in, const int32_t* counts_in, long long part_stride,
+                        long long count_stride, int n_parts, const int32_t* part_offsets, int n_queries, int k_in, int k,
+                        int32_t* indices_out, float* scores_out, int32_t* counts_out, int32_t* parts_out);
 // The inverted file of a compressed bank (bank_ivf.hip; "THE INVERTED FILE", include/rerank_mi355.h): offsets [n_centroids + 1] and
 // pids [postings] on the device, the passages it covers and its longest list.  rr_ivf_build fills an EMPTY one over the host table
 // (first, len) of P passages (it allocates and synchronises st; hipErrorOutOfMemory: an allocation failed, nothing is kept);

@@ -983,6 +983,52 @@ class RerankEngine:
         return _bank_search_plaid(self, "rr_bank_search_plaid", bank, query_li, k, ncells=ncells, centroid_score_threshold=centroid_score_threshold,
                                   ndocs=ndocs, coarse_tokens=coarse_tokens, first=first, count=count)
 
+    def bank_merge_topk(self, indices: torch.Tensor, scores: torch.Tensor, counts: Optional[torch.Tensor], part_offsets, k: int, *,
+                        part_stride: Optional[int] = None, count_stride: Optional[int] = None, want_parts: bool = False) -> dict:
+        """The k-lists of P parts merged into one list over global indices (rr_bank_merge_topk, "THE MERGED LIST" in
+        include/rerank_mi355.h): `indices` int32 / `scores` float32 [P, n_queries, k_in] of LOCAL indices per part, `counts` int32
+        [P, n_queries] or None (every list is full), all on this engine's device; `part_offsets` the P + 1 host offsets of the
+        parts in the global index space.  With `part_stride` / `count_stride` (in 4-byte words) the three tensors may be views
+        into one gathered block whose parts lie further apart than their lists: only their first element's address and their
+        shapes are read then.  Per query the first k real entries in the one rank order of the searches over (score, global
+        index): {"indices": int32 [n_queries, k] global, -1 behind the count; "scores": float32 [n_queries, k], -inf there;
+        "counts": int32 [n_queries]; with `want_parts` "parts": int32 [n_queries, k], the part an entry came from}.  Merging the
+        bank_search results of the parts of a corpus gives, byte for byte, bank_search over the whole corpus.  1 <= k <= k_in,
+        P <= 64, P * k_in <= 8192 (AssertionError / NotImplementedError from the library)."""
+        import numpy as np
+        if indices.dim() != 3 or scores.shape != indices.shape:
+            raise ValueError(f"bank_merge_topk: indices {tuple(indices.shape)} and scores {tuple(scores.shape)}: both [parts, n_queries, k_in]")
+        if indices.dtype != torch.int32 or scores.dtype != torch.float32 or (counts is not None and counts.dtype != torch.int32):
+            raise ValueError("bank_merge_topk: indices and counts are int32, scores float32")
+        P, nq, k_in = (int(x) for x in indices.shape)
+        if counts is not None and tuple(counts.shape) != (P, nq):
+            raise ValueError(f"bank_merge_topk: counts {tuple(counts.shape)}: [{P}, {nq}]")
+        for t in (indices, scores, counts):
+            if t is not None and t.device != self.device:
+                raise ValueError(f"bank_merge_topk: a tensor on {t.device}, the engine on {self.device}")
+        off = np.ascontiguousarray(np.asarray(part_offsets, dtype=np.int64).reshape(-1))
+        if off.size != P + 1 or (off.size and (off.min() < -(1 << 31) or off.max() >= (1 << 31))):
+            raise ValueError(f"bank_merge_topk: part_offsets holds {off.size} int32 offsets for {P} parts ({P + 1})")
+        off = off.astype(np.int32)
+        if part_stride is None:
+            indices, scores = indices.contiguous(), scores.contiguous()
+            part_stride = nq * k_in
+        if count_stride is None:
+            counts = None if counts is None else counts.contiguous()
+            count_stride = nq
+        k = int(k)
+        if k < 1 or k > k_in:
+            raise AssertionError(f"bank_merge_topk: k = {k} of lists of {k_in}")
+        out = dict(indices=torch.empty((nq, k), device=self.device, dtype=torch.int32),
+                   scores=torch.empty((nq, k), device=self.device, dtype=torch.float32),
+                   counts=torch.empty((nq,), device=self.device, dtype=torch.int32),
+                   parts=torch.empty((nq, k), device=self.device, dtype=torch.int32) if want_parts else None)
+        L.check(self.lib.rr_bank_merge_topk(self.h, indices.data_ptr(), scores.data_ptr(), 0 if counts is None else counts.data_ptr(),
+                                            int(part_stride), int(count_stride), P, off.ctypes.data, nq, k_in, k, L.ptr(out["indices"]),
+                                            L.ptr(out["scores"]), L.ptr(out["counts"]), L.ptr(out["parts"]), self._stream()),
+                self.h, "rr_bank_merge_topk")
+        return {n: v for n, v in out.items() if v is not None}
+
     def bank_search_plaid_tap(self, name: str):
         """One intermediate of this engine's last bank_search_plaid call as a numpy array (rr_bank_search_plaid_tap,
         include/rerank_mi355_diag.h): "S", "cells", "keep", "a1", "list1", "list2".  Flat; the caller knows the shape."""

@@ -37,6 +37,9 @@ index stores it.  With it a compressed bank is built from a retriever's embeddin
 (`export_compressed`: the unmasked rows of a range back to back, compacted by a kernel); `load_plaid_index(..., ivf=True)` brings the
 directory back with its inverted file (`load_ivf`, rr_bank_load_ivf) instead of rebuilding it.
 
+`search_banks` searches several banks of one process as one (every bank searched, the k-lists merged on the device over global
+indices by rr_bank_merge_topk); a bank split over RANKS is sharding.ShardedBank.
+
 `BankTable`, `plan_bank_batch`, `plan_bank_scores`, `PlaidCodec`, `read_plaid_index` and `write_plaid_index` are the host side: pure Python /
 numpy / torch on the CPU, usable and tested without a device.
 """
@@ -987,3 +990,67 @@ class PassageBank:
         """Forget every passage (rr_bank_clear; the capacity stays; the inverted file goes).  Forwards that read the bank must have completed."""
         self._check(self.lib.rr_bank_clear(self.h), "rr_bank_clear")
         self.table.clear()
+
+
+def search_bank_part(engine, bank, query_li, k: int, plaid: Optional[PlaidSearch] = None, filter: Optional[BankFilter] = None) -> dict:
+    """One part's list for RerankEngine.bank_merge_topk: the search of `bank` (the exact one, or with `plaid` / `filter` what
+    PassageBank.search runs for them) with k_local = min(k, len(bank)), as {"indices": int32 [n_queries, k] dense indices of
+    THIS bank, "scores": float32 [n_queries, k], "counts": int32 [n_queries]} on the device.  Behind k_local the rows hold -1 /
+    -inf; an exact search, which returns no counts, gets k_local as its count; an empty bank contributes count 0 and no search
+    call."""
+    import torch
+    nq, k, dev = int(query_li.shape[0]), int(k), engine.device
+    k_local = min(k, len(bank))
+    out = dict(indices=torch.full((nq, k), -1, device=dev, dtype=torch.int32),
+               scores=torch.full((nq, k), float("-inf"), device=dev, dtype=torch.float32),
+               counts=torch.zeros((nq,), device=dev, dtype=torch.int32))
+    if k_local < 1:
+        return out
+    if plaid is not None:
+        kw = dict(ncells=plaid.ncells, centroid_score_threshold=plaid.centroid_score_threshold, ndocs=plaid.ndocs,
+                  coarse_tokens=plaid.coarse_tokens)
+        ivf = getattr(plaid, "ivf", False)
+        if filter is None:
+            r = (engine.bank_search_plaid_ivf if ivf else engine.bank_search_plaid)(bank, query_li, k_local, **kw)
+        else:
+            r = (engine.bank_search_plaid_ivf_filtered if ivf else engine.bank_search_plaid_filtered)(bank, query_li, k_local, filter, **kw)
+    elif filter is not None:
+        r = engine.bank_search_filtered(bank, query_li, k_local, filter)
+    else:
+        r = engine.bank_search(bank, query_li, k_local)
+    if k_local == k and "counts" in r:
+        return r
+    out["indices"][:, :k_local] = r["indices"]
+    out["scores"][:, :k_local] = r["scores"]
+    if "counts" in r:
+        out["counts"] = r["counts"]
+    else:
+        out["counts"].fill_(k_local)
+    return out
+
+
+def search_banks(engine, banks: Sequence, query_li, k: int, plaid: Optional[PlaidSearch] = None, filters: Optional[Sequence] = None):
+    """PassageBank.search over several banks held by one process (a corpus loaded bank by bank, an fp16 bank beside a compressed
+    one of the same li_dim) as over one bank holding their passages in the order of `banks`: every bank is searched
+    (search_bank_part: `plaid` for each, `filters[i]` a BankFilter of bank i or None), the lists are merged on the device
+    (RerankEngine.bank_merge_topk, rr_bank_merge_topk) and the ids come from each bank's table.  Returns (passage_ids, scores,
+    counts): passage_ids[q] the ids of query q best first, at its true length (at most k); scores float32 [n_queries, k] on the
+    device, -inf behind the count; counts int32 [n_queries] on the device.  With the exact search this is, byte for byte, the
+    search of the one bank; with `plaid` it is by definition the merge of the per-bank pruned searches (each bank keeps its own
+    ndocs).  Copies the merged indices to the host (synchronises).  At most 64 banks, len(banks) * k <= 8192."""
+    import numpy as np
+    import torch
+    banks = list(banks)
+    if not banks:
+        raise ValueError("search_banks: no bank")
+    if filters is not None and len(filters) != len(banks):
+        raise ValueError(f"search_banks: {len(filters)} filters for {len(banks)} banks (one each, or None)")
+    offsets = np.zeros(len(banks) + 1, dtype=np.int64)
+    np.cumsum([len(b) for b in banks], out=offsets[1:])
+    parts = [search_bank_part(engine, b, query_li, k, plaid, None if filters is None else filters[i]) for i, b in enumerate(banks)]
+    r = engine.bank_merge_topk(torch.stack([p["indices"] for p in parts]), torch.stack([p["scores"] for p in parts]),
+                               torch.stack([p["counts"] for p in parts]), offsets, k, want_parts=True)
+    counts = r["counts"].tolist()
+    ids = [[banks[p].table.ids[g - int(offsets[p])] for g, p in zip(row[:c], prow[:c])]
+           for row, prow, c in zip(r["indices"].tolist(), r["parts"].tolist(), counts)]
+    return ids, r["scores"], r["counts"]

@@ -273,3 +273,250 @@ def sharded_forward_lists(engine, input_ids, attention_mask, token_type_ids, lis
         return torch.zeros(n, dtype=torch.float32, device=input_ids.device)
 
     return ShardedReranker(encode, head, group, two_heads=two_heads, empty=empty, defer_status=defer_status)(N)
+
+
+# ---- a passage bank split over ranks ------------------------------------------------------------------------------------------------
+# A bank cannot be replicated like weights.  Every rank holds the passages of its slice of the corpus in a bank of its own (rank
+# r's passages are the global indices part_offsets[r] .. part_offsets[r + 1] - 1), the QUERIES are the caller's to replicate (every
+# rank calls with the same query tensors), every rank searches its bank, the k-lists travel with ONE all-gather and are merged on
+# every rank by rr_bank_merge_topk (include/rerank_mi355.h, THE MERGED LIST): with the exact search the result is, byte for byte,
+# the search of one bank holding the whole corpus; with a PlaidSearch it is BY DEFINITION the merge of the per-rank pruned searches
+# (each rank keeps its own ndocs).  The merged winners are then reranked where their embeddings live (sharded_retrieve_and_rerank):
+# the owner of a passage computes its logit, no embedding travels, and nothing balances that work between ranks: a query whose
+# winners all live on one rank is that rank's to rerank alone.  Errors are collective as described at the top of the module.
+# RCCL with more than one rank has never executed in this project's tests: this path rests on the gloo tests
+# (tests/test_sharding_bank_gloo.py) and on in-process GPU tests that run the "ranks" one after another (tests/test_gpu_bank_merge.py).
+class _BlockPlan:
+    """Preallocated buffers of one (device, dtype, world, block length) exchange of equal blocks; the last word of a block is its
+    rank's status.  A search's block is int32 [nq * k indices | nq * k score bits | nq counts | status word], a rerank's float32
+    [heads * nq * k logits | status word]."""
+
+    def __init__(self, device, dtype, world: int, blk: int):
+        self.world, self.blk = world, blk
+        self.send = torch.zeros(blk, dtype=dtype, device=device)
+        self.recv = torch.empty(world * blk, dtype=dtype, device=device)
+        self.host = None
+
+
+_BLOCK_PLANS = None
+
+
+def _block_plan(device, dtype, world, blk, group=None) -> _BlockPlan:
+    from collections import OrderedDict
+    global _BLOCK_PLANS
+    if _BLOCK_PLANS is None:
+        _BLOCK_PLANS = OrderedDict()
+    key = (str(device), dtype, world, blk, id(group) if group is not None else 0)
+    p = _BLOCK_PLANS.get(key)
+    if p is None:
+        p = _BLOCK_PLANS[key] = _BlockPlan(device, dtype, world, blk)
+        while len(_BLOCK_PLANS) > _MAX_PLANS:
+            _BLOCK_PLANS.popitem(last=False)
+    else:
+        _BLOCK_PLANS.move_to_end(key)
+    return p
+
+
+def _all_gather(recv: torch.Tensor, send: torch.Tensor, plan, group) -> None:
+    """One all_gather_into_tensor; under gloo, device tensors are staged through pinned host memory (plan.host), as gather_logits
+    does for the one-GPU rehearsal."""
+    if send.is_cuda and dist.get_backend(group) == "gloo":
+        if plan.host is None:
+            plan.host = (torch.empty_like(send, device="cpu").pin_memory(), torch.empty_like(recv, device="cpu").pin_memory())
+        plan.host[0].copy_(send)
+        dist.all_gather_into_tensor(plan.host[1], plan.host[0], group=group)
+        recv.copy_(plan.host[1])
+    else:
+        dist.all_gather_into_tensor(recv, send, group=group)
+
+
+def exchange_bank_results(local, part_offsets, k: int, group=None, merge: Optional[Callable] = None, engine=None,
+                          n_queries: Optional[int] = None, device=None) -> dict:
+    """The k-lists of every rank's bank search merged into the global list, on every rank alike.  `local`: this rank's
+    {"indices" int32 [nq, k] LOCAL bank indices, "scores" float32 [nq, k], "counts" int32 [nq]} (passage_bank.search_bank_part),
+    or a callable that returns it (the local search: then `n_queries`, and `device` unless `engine` is given, say what a rank
+    whose search raised sends).  `part_offsets`: the world + 1 host offsets of the ranks' banks (ShardedBank.refresh).  ONE
+    all_gather_into_tensor of an int32 block per rank; the merge then reads the received block in place, through strides:
+    `merge`(indices, scores, counts, part_offsets, k, part_stride=, count_stride=, want_parts=True), default
+    `engine`.bank_merge_topk.  Returns its dict {"indices" global, "scores", "counts", "parts"} plus "part_offsets".
+    A rank whose local search raised still takes part, with counts 0 and its status word set; every rank raises after the
+    exchange: that rank its own exception, the others ShardPeerError."""
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    own, status = None, STATUS_OK
+    if callable(local):
+        try:
+            local = local()
+        except Exception as ex:      # noqa: BLE001 — the exchange must still happen on this rank
+            own, status, local = ex, (STATUS_RANGE if isinstance(ex, OverflowError) else STATUS_ERROR), None
+    k = int(k)
+    if local is not None:
+        nq, device = int(local["indices"].shape[0]), local["indices"].device
+        assert tuple(local["indices"].shape) == (nq, k) == tuple(local["scores"].shape) and local["counts"].numel() == nq, \
+            f"a rank's lists are [n_queries, {k}] with one count per query"
+    else:
+        if n_queries is None or (device is None and engine is None):
+            raise own
+        nq, device = int(n_queries), (engine.device if device is None else device)
+    w = nq * k
+    p = _block_plan(device, torch.int32, world, 2 * w + nq + 1, group)
+    if local is not None:
+        p.send[:w].copy_(local["indices"].reshape(-1))
+        p.send[w:2 * w].copy_(local["scores"].reshape(-1).view(torch.int32))
+        p.send[2 * w:2 * w + nq].copy_(local["counts"].reshape(-1))
+    else:
+        p.send[2 * w:2 * w + nq].zero_()
+    p.send[p.blk - 1] = status
+    _all_gather(p.recv, p.send, p, group)
+    blocks = p.recv.view(world, p.blk)
+    _raise_collectively(blocks[:, p.blk - 1].tolist(), rank, own)      # one host read of `world` words per search
+    if merge is None:
+        if engine is None:
+            raise ValueError("exchange_bank_results: give the engine whose bank_merge_topk merges, or a merge function")
+        merge = engine.bank_merge_topk
+    out = merge(blocks[:, :w].unflatten(1, (nq, k)), blocks[:, w:2 * w].view(torch.float32).unflatten(1, (nq, k)),
+                blocks[:, 2 * w:2 * w + nq], part_offsets, k, part_stride=p.blk, count_stride=p.blk, want_parts=True)
+    out["part_offsets"] = [int(x) for x in part_offsets]
+    return out
+
+
+class ShardedBank:
+    """This rank's PassageBank as one part of a corpus split over the ranks of `group`, rank after rank in corpus order.
+    `refresh()` is a load-time collective: it all-gathers every rank's passage count into `part_offsets` and the passage ids
+    (all_gather_object) into the global id table `ids`; call it again after adds.  `search` is the local search plus the
+    exchange.  The queries are the caller's to replicate: every rank passes the same `query_li`."""
+
+    def __init__(self, bank, group=None):
+        self.bank, self.group = bank, group
+        self.part_offsets = None
+        self.ids = None
+
+    def refresh(self) -> None:
+        world = dist.get_world_size(self.group)
+        counts = [None] * world
+        dist.all_gather_object(counts, len(self.bank), group=self.group)
+        tables = [None] * world
+        dist.all_gather_object(tables, list(self.bank.table.ids), group=self.group)
+        assert [len(t) for t in tables] == counts
+        self.part_offsets = [0]
+        for c in counts:
+            self.part_offsets.append(self.part_offsets[-1] + int(c))
+        if self.part_offsets[-1] >= 1 << 31:
+            raise OverflowError(f"ShardedBank: {self.part_offsets[-1]} passages (global indices are int32)")
+        self.ids = [pid for t in tables for pid in t]
+
+    def search_merged(self, engine, query_li, k: int, plaid=None, filter=None, merge: Optional[Callable] = None) -> dict:
+        """The merged result on the device, as exchange_bank_results returns it (global indices, scores, counts, parts)."""
+        from .passage_bank import search_bank_part
+        if self.part_offsets is None:
+            raise RuntimeError("ShardedBank: call refresh() (on every rank) before the first search, and again after adds")
+        rank = dist.get_rank(self.group)
+        if self.part_offsets[rank + 1] - self.part_offsets[rank] != len(self.bank):
+            raise RuntimeError("ShardedBank: the bank has changed since refresh(): call it again on every rank")
+        return exchange_bank_results(lambda: search_bank_part(engine, self.bank, query_li, k, plaid, filter), self.part_offsets, k,
+                                     self.group, merge=merge, engine=engine, n_queries=int(query_li.shape[0]))
+
+    def search(self, engine, query_li, k: int, plaid=None, filter=None):
+        """The k best passages of the WHOLE corpus per query: this rank searches its bank with k_local = min(k, len(bank))
+        (the exact search, or with `plaid` / `filter`, a BankFilter of THIS rank's bank, what PassageBank.search runs for
+        them), one all-gather, the merge.  Returns (passage_ids: per query the ids best first, at their true length; scores
+        float32 [n_queries, k] on the device; counts int32 [n_queries]; parts int32 [n_queries, k]: the rank that holds each
+        winner), the same on every rank.  Copies the merged indices to the host (synchronises)."""
+        r = self.search_merged(engine, query_li, k, plaid, filter)
+        ids = [[self.ids[g] for g in row[:c]] for row, c in zip(r["indices"].tolist(), r["counts"].tolist())]
+        return ids, r["scores"], r["counts"], r["parts"]
+
+
+def _rerank_heads(model) -> int:
+    return 2 if model.engine.arch["loss_fn"] == "2H_BCE" else 1
+
+
+def rerank_owned(model, bank, merged: dict, part: int, query_late_interaction, query_mask, **kw) -> torch.Tensor:
+    """The logits of the merged winners that live in `bank`, part `part` of the corpus: a zeroed float32 [heads * nq * k] buffer
+    (heads: 2 for 2H_BCE) with the logit of every winner whose part is `part` at its merged position q * k + i (the second head
+    behind the first).  One engine.forward_interaction_bank over those winners, lists of unequal length per query; a part that
+    owns none runs no forward.  `merged`: exchange_bank_results' dict.  Process-free: a test runs the parts one after another."""
+    parts, idx = merged["parts"], merged["indices"]
+    nq, k = int(parts.shape[0]), int(parts.shape[1])
+    heads = _rerank_heads(model)
+    buf = torch.zeros(heads * nq * k, dtype=torch.float32, device=idx.device)
+    mine = (parts == int(part)).reshape(-1)
+    pos = mine.nonzero().reshape(-1)                                    # merged positions, query after query
+    if pos.numel() == 0:
+        return buf
+    local = (idx.reshape(-1)[pos] - int(merged["part_offsets"][part])).tolist()
+    per_query = torch.bincount(torch.div(pos, k, rounding_mode="floor"), minlength=nq).tolist()
+    sel = [q for q, n in enumerate(per_query) if n]
+    ids = [bank.table.ids[j] for j in local]
+    sel_t = torch.tensor(sel, device=query_late_interaction.device)
+    r = model.engine.forward_interaction_bank(bank, query_late_interaction.index_select(0, sel_t),
+                                              query_mask.reshape(nq, -1).index_select(0, sel_t.to(query_mask.device)), ids, None, None,
+                                              None, list_sizes=[per_query[q] for q in sel], want_loss=False, want_order=True, **kw)
+    buf[pos] = r["logits"]
+    if heads == 2:
+        buf[pos + nq * k] = r["logits2"]
+    return buf
+
+
+def combine_owned(buffers: torch.Tensor, parts: torch.Tensor) -> torch.Tensor:
+    """buffers [n_parts, heads * nq * k] (rerank_owned's, part after part), parts int32 [nq, k] -> [heads, nq * k]: every merged
+    position taken from its owner's buffer with one torch.gather whose index is computed from `parts` on the device.  No sum: the
+    bits, -0 included, arrive unchanged.  A position behind a query's count (part -1) reads part 0's zero."""
+    n = parts.numel()
+    heads = int(buffers.shape[1]) // n
+    assert heads * n == buffers.shape[1], f"buffers {tuple(buffers.shape)} for {n} merged positions"
+    owner = parts.reshape(1, 1, n).clamp(min=0).to(torch.int64).expand(1, heads, n)
+    return torch.gather(buffers.unflatten(1, (heads, n)), 0, owner).view(heads, n)
+
+
+def head_over_merged(model, logits: torch.Tensor, counts, k: int, labels=None, **kw):
+    """The scoring head over the merged lists: `logits` [heads, nq * k] (combine_owned), list q the first counts[q] positions of
+    row q.  Returns the model's RerankOutput (logits list after list, order local to each list)."""
+    sizes = [int(c) for c in counts]
+    if min(sizes) < 1:
+        raise ValueError(f"query {sizes.index(min(sizes))} found no candidate")
+    dev = logits.device
+    gather = torch.cat([torch.arange(c, dtype=torch.int32) + q * k for q, c in enumerate(sizes)]).to(dev)
+    l1 = logits[0].contiguous()
+    l2 = logits[1].contiguous() if logits.shape[0] == 2 else None
+    N = sum(sizes)
+    kw.setdefault("want_order", True)
+    r = model.engine.head_lists(l1, l2, model._labels(labels, N), sizes, gather=gather, **kw)
+    r["logits"] = l1.index_select(0, gather.long())
+    if l2 is not None:
+        r["logits2"] = l2.index_select(0, gather.long())
+    return model._output(r, model._flat_logits(r))
+
+
+def sharded_retrieve_and_rerank(model, shard: ShardedBank, query_late_interaction, query_mask, k: int, plaid=None, filter=None,
+                                labels=None, **kw):
+    """InteractionRerankModel.retrieve_and_rerank over a bank split over ranks: (passage_ids, RerankOutput), the same on every
+    rank.  1. shard.search (local search, one all-gather, the merge).  2. every rank runs forward_interaction_bank over the merged
+    winners whose part is its own (rerank_owned).  3. / 4. the zeroed [heads * nq * k] buffers travel with one all-gather.
+    5. every position is taken from its owner's block (combine_owned).  6. the head runs over the merged lists with
+    list_sizes = counts, redundantly on every rank, as sharded_forward_lists does.  A query that found no candidate raises
+    ValueError on every rank, as retrieve_and_rerank does; an exception inside one rank's forward is collective (ShardPeerError
+    on the others).  The owner computes: nothing balances the rerank work between ranks.  `kw`: granule / segment_cost_rows /
+    fusion_from_li ... of forward_interaction_bank."""
+    eng, group = model.engine, shard.group
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    merged = shard.search_merged(eng, query_late_interaction, k, plaid, filter)
+    counts = merged["counts"].tolist()
+    if min(counts) < 1:
+        raise ValueError(f"sharded_retrieve_and_rerank: query {counts.index(min(counts))} found no candidate")
+    nq, k = int(merged["parts"].shape[0]), int(k)
+    heads = _rerank_heads(model)
+    own, status = None, STATUS_OK
+    try:
+        buf = rerank_owned(model, shard.bank, merged, rank, query_late_interaction, query_mask, **kw)
+    except Exception as ex:      # noqa: BLE001 — the exchange must still happen on this rank
+        own, status = ex, (STATUS_RANGE if isinstance(ex, OverflowError) else STATUS_ERROR)
+        buf = torch.zeros(heads * nq * k, dtype=torch.float32, device=merged["parts"].device)
+    p = _block_plan(buf.device, torch.float32, world, heads * nq * k + 1, group)
+    p.send[:buf.numel()].copy_(buf)
+    p.send[p.blk - 1] = float(status)
+    _all_gather(p.recv, p.send, p, group)
+    blocks = p.recv.view(world, p.blk)
+    _raise_collectively(blocks[:, p.blk - 1].tolist(), rank, own)
+    logits = combine_owned(blocks[:, :heads * nq * k], merged["parts"])
+    ids = [[shard.ids[g] for g in row[:c]] for row, c in zip(merged["indices"].tolist(), counts)]
+    return ids, head_over_merged(model, logits, counts, k, labels=labels)

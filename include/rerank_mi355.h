@@ -495,8 +495,9 @@ int rr_forward_interaction_packed_fusion_li(rr_handle h, const float* query_li, 
 /* ---- Passage-embedding bank of the interaction rerankers.  They rerank from embeddings that already exist: the frozen retriever's
  * context token embeddings, which the reference hands over in fp16 (`D = D.half()`, modeling_flmr.py:1554-1555).  A bank keeps
  * them on the device in that form, each passage at its own length, so that a forward names passages by index instead of taking a
- * padded float32 context_li [N, Lc, li_dim] per call.  Append-only: per passage rows [len, li_dim] as fp16, one mask byte per row,
- * and a host-side table (first row as int64, length).  No reference counterpart (it recomputes or reloads the embeddings per batch).
+ * padded float32 context_li [N, Lc, li_dim] per call.  Passages are appended, and removed in place (rr_bank_remove, REMOVING
+ * PASSAGES below); the rows always lie back to back: per passage rows [len, li_dim] as fp16, one mask byte per row, and a host-side
+ * table (first row as int64, length).  No reference counterpart (it recomputes or reloads the embeddings per batch).
  * Python: rmr_amd.PassageBank, RerankEngine.create_bank / forward_interaction_bank.
  *
  * rr_bank_create: a bank of capacity_rows rows and at most max_passages passages on h's device with h's li_dim (a multiple of 8,
@@ -824,7 +825,8 @@ int rr_bank_search_plaid(rr_handle h, rr_bank_handle b, const float* query_li, i
  * and synchronises hip_stream; not capturable into a graph (RR_ERR_BAD_ARG).  An fp16 bank: RR_ERR_UNSUPPORTED; an empty bank:
  * RR_ERR_BAD_SHAPE; a failed allocation: RR_ERR_OOM with the bank unchanged: a previous file survives a failed rebuild.
  * LIFETIME: rr_bank_clear drops the file; passages added after a build leave it valid for its prefix 0 .. P-1 (build again to
- * cover them; there is no incremental update); rr_bank_destroy frees it.
+ * cover them; there is no incremental update); rr_bank_remove leaves the bank with the file over the survivors of that prefix,
+ * rebuilt by this builder when one of them went; rr_bank_destroy frees it.
  * rr_bank_ivf_info: passages_covered (0: no file), the postings total and the longest list; any pointer may be NULL.
  * rr_bank_ivf_read copies offsets [C + 1] and pids [postings] to HOST buffers (either may be NULL) and synchronises hip_stream;
  * RR_ERR_BAD_ARG without a file.  Errors of these calls: rr_bank_last_error.
@@ -865,6 +867,40 @@ int rr_bank_build_ivf(rr_bank_handle b, void* hip_stream);
 int rr_bank_ivf_info(rr_bank_handle b, int32_t* passages_covered_out, int64_t* postings_out, int32_t* longest_list_out);
 int rr_bank_ivf_read(rr_bank_handle b, int64_t* offsets_host_out, int32_t* pids_host_out, void* hip_stream);
 int rr_bank_load_ivf(rr_bank_handle b, const int64_t* offsets_host, const int32_t* pids_host, int verify, void* hip_stream);
+
+/* REMOVING PASSAGES.  rr_bank_remove drops n passages of either kind of bank and compacts what remains, on the device.
+ *   indices_host       : HOST int32 [n]: the dense indices to drop, in any order, distinct, each in [0, passages held).
+ *   new_index_host_out : HOST int32 [passages held before the call], or NULL: old dense index -> new dense index, -1 for a removed
+ *                        passage.
+ * CONTRACT: afterwards the bank is indistinguishable from a fresh bank filled with the survivors in their original order.  The
+ * survivors keep their relative order and are renumbered 0 .. passages - n - 1; rows_used shrinks by the removed rows; rows and
+ * passage slots are free for later adds.  Every array the bank holds (fp16 rows, mask bytes, codes, residual bytes) equals the
+ * fresh bank's over [0, rows_used), to the bit, so every rr_bank_read*, rr_bank_li_scores, rr_forward_interaction_bank,
+ * rr_bank_search* and rr_bank_export_plaid result does.  n == 0: RR_OK, nothing changes, the map is the identity.  Removing every
+ * passage leaves the state of rr_bank_clear.
+ * THE INVERTED FILE: a bank that holds a file over its first P passages holds afterwards the file over the survivors among those P
+ * (a prefix of the new bank), built by rr_bank_build_ivf's builder and so with the bytes a fresh build gives; with no survivor
+ * among them the file is dropped; with no removed passage among them it stays as it is.
+ * A LOAD-TIME CALL, like rr_bank_build_ivf: it allocates a staging block (at most 256 MiB, and 32 bytes per run of surviving rows and window),
+ * enqueues on hip_stream and synchronises it before it returns; not capturable into a graph.  Work on OTHER streams that reads the
+ * bank must have completed, as for rr_bank_clear.  A bank is still not thread-safe: in particular, no removal while another thread
+ * looks passages up (the producer thread of a pipelined rerank loop).  Filters built before the call (rr_bank_filter_fill) name the
+ * old indices: build them again.  The search's device table is invalidated from the first moved passage on; the next search
+ * uploads the rest again, as after an add.
+ * ALL OR NOTHING: every refusal comes before anything is enqueued or changed.  RR_ERR_BAD_ARG: a NULL bank, NULL indices with
+ * n > 0, a capturing stream.  RR_ERR_BAD_SHAPE: n < 0, an index outside the bank, an index given twice (rr_bank_last_error names
+ * it).  RR_ERR_OOM: the staging block cannot be allocated; the bank is unchanged.  THE ONE EXCEPTION: the inverted file is rebuilt
+ * after the rows have moved.  If that fails, the passages ARE removed (new_index_host_out is written), the file is dropped, and the
+ * call returns the builder's status (RR_ERR_OOM / RR_ERR_HIP); rr_bank_last_error says that the file is gone and must be built
+ * again (rr_bank_build_ivf).
+ * HOW (csrc/bank_move.hip): from the host table the runs of surviving rows behind the first removed passage, each moving down by a
+ * shift that never decreases.  Moving them all in one launch would overwrite rows another workgroup has yet to read, and nothing
+ * here waits for another workgroup: the destination rows are cut into windows, per window one launch gathers the window's rows
+ * into the staging block and one device-to-device copy puts it in place, in stream order; a later window reads nothing an earlier
+ * one wrote.  64-bit byte offsets; 16-byte accesses where source and destination are aligned alike, narrower ones elsewhere (the
+ * 4-byte codes, the mask bytes and residual rows under 16 bytes land misaligned relative to their sources).  The plan in host
+ * code: rr_util_bank_remove_plan (rerank_mi355_diag.h).  (Python: PassageBank.remove.) */
+int rr_bank_remove(rr_bank_handle b, const int32_t* indices_host, int n, int32_t* new_index_host_out, void* hip_stream);
 
 /* rr_bank_export_plaid: a range of a COMPRESSED bank as a ColBERTv2 / PLAID index stores it, written on the device: the way back to
  * disk of what rr_bank_add_plaid / rr_bank_add_compress put in (Python: PassageBank.export_compressed / save_plaid_index).

@@ -398,6 +398,28 @@ int rr_op_bank_merge_topk(const int32_t* indices_in, const float* scores_in, con
 int rr_util_bank_merge_topk(const int32_t* indices_in, const float* scores_in, const int32_t* counts_in, int64_t part_stride,
                             int64_t count_stride, int n_parts, const int32_t* part_offsets, int n_queries, int k_in, int k,
                             int32_t* indices_out, float* scores_out, int32_t* counts_out, int32_t* parts_out);
+/* rr_util_bank_remove_plan: what rr_bank_remove (rerank_mi355.h, "REMOVING PASSAGES") does to a bank whose n passages have
+ * `lengths` (int32 [n], each >= 1) when the m distinct indices `remove` (int32 [m], each in [0, n)) go, in pure HOST code, usable
+ * without a GPU: the written-down definition, and the function rr_bank_remove itself calls.  new_index_out int32 [n] (or NULL): old
+ * dense index -> new, -1 for a removed passage.  moves_out int64 [moves_cap][4] (or NULL, to size it first): the moves (window,
+ * src_row, dst_row, rows) in the order they are carried out: the destination rows from the first moved row on are cut into windows
+ * of window_rows rows (>= 1), and every maximal run of consecutive surviving rows behind the first removed passage is cut at the
+ * window borders.  A window's moves are gathered into a staging block of window_rows rows and copied to dst_row of its first move;
+ * the passages in front of the first removed one give no move.  *n_moves_out (or NULL): the number of moves.  RR_ERR_BAD_SHAPE,
+ * with NOTHING written, for an index outside [0, n) or given twice, a length below 1, window_rows < 1, or more moves than moves_cap.
+ * rr_op_bank_move_rows: that plan carried out by rr_bank_remove's kernel and copies (csrc/bank_move.hip) on ONE raw DEVICE array of
+ * sum(lengths) rows of row_bytes bytes (16-byte aligned; row_bytes a power of two or a multiple of 16, at most 1024:
+ * RR_ERR_UNSUPPORTED otherwise), without a bank, so that row sizes no handle's li_dim gives (a handle takes multiples of 64) can be
+ * moved: 16-byte fp16 rows of D = 8, residual rows of 1 to 8 bytes.  Afterwards the array holds the survivors' rows back to back;
+ * the bytes behind them are unspecified.  The refusals of the plan (RR_ERR_BAD_SHAPE), a NULL or misaligned array and a capturing
+ * stream (RR_ERR_BAD_ARG) come before anything is enqueued.  Allocates its staging per call ("bank_move_kb") and synchronises
+ * hip_stream.
+ * rr_set_tuning("bank_move_kb") (262144; 4 .. 1048576): the KiB of rr_bank_remove's staging block; window_rows = that over the
+ * bytes of the bank's widest per-row array.  It selects no algorithm: tests reach many windows at a small shape, the bench sweeps it. */
+int rr_op_bank_move_rows(void* array, int row_bytes, const int32_t* lengths_host, int32_t n, const int32_t* remove_host, int32_t m,
+                         void* hip_stream);
+int rr_util_bank_remove_plan(const int32_t* lengths, int32_t n, const int32_t* remove, int32_t m, int64_t window_rows,
+                             int32_t* new_index_out, int64_t* moves_out, int64_t moves_cap, int64_t* n_moves_out);
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,7 @@ _SIGS = {
     "rr_bank_create": (C.c_int, [_P, C.c_int64, C.c_int32, C.POINTER(_P)]),
     "rr_bank_destroy": (C.c_int, [_P]),
     "rr_bank_clear": (C.c_int, [_P]),
+    "rr_bank_remove": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "rr_bank_last_error": (C.c_char_p, [_P]),
     "rr_bank_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "rr_bank_add": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_int32), _P]),
@@ -133,6 +134,8 @@ _SIGS = {
                                                     C.c_int, _P, C.c_int, C.c_int64, _P, _P, _P, _P]),
     "rr_bank_filter_fill": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int64, _P]),
     "rr_util_bank_filter_bits": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int32, _P, C.c_int64]),
+    "rr_op_bank_move_rows": (C.c_int, [_P, C.c_int, _P, C.c_int32, _P, C.c_int32, _P]),
+    "rr_util_bank_remove_plan": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int64, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "rr_bank_merge_topk": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "rr_op_bank_merge_topk": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "rr_util_bank_merge_topk": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),

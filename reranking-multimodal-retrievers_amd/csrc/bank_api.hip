@@ -1165,6 +1165,159 @@ int rr_util_bank_merge_topk(const int32_t* indices_in, const float* scores_in, c
   });
 }
 
+// The moves of a plan carried out over `arrays` (widest: the bytes of a row of the widest of them): one block for the move table
+// and the staging of the longest window, the moves enqueued on st, st synchronised, the block freed.  *allocated: the block was
+// there (a failure before it changed nothing); *bytes: its size.
+static hipError_t bank_move_block(const std::vector<rr_bank_move>& moves, const rr_move_array* arrays, int na, size_t widest, hipStream_t st,
+                                  bool* allocated, size_t* bytes) {
+  int64_t longest = 0, rows = 0;                  // of a window: the moves of one lie side by side
+  for (size_t i = 0; i < moves.size(); ++i) {
+    rows = (i && moves[i].window == moves[i - 1].window ? rows : 0) + moves[i].rows;
+    longest = std::max(longest, rows);
+  }
+  const size_t table_bytes = (moves.size() * sizeof(rr_bank_move) + 15) & ~(size_t)15;
+  *bytes = table_bytes + (((size_t)longest * widest + 15) & ~(size_t)15);
+  *allocated = false;
+  char* blk = nullptr;
+  hipError_t e = hipMalloc((void**)&blk, *bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return e;
+  }
+  *allocated = true;
+  e = hipMemcpyAsync(blk, moves.data(), moves.size() * sizeof(rr_bank_move), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = rr_bank_move_run(moves.data(), moves.size(), (const rr_bank_move*)blk, arrays, na, blk + table_bytes, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = es;
+  (void)hipFree(blk);
+  if (e != hipSuccess) (void)hipGetLastError();
+  return e;
+}
+
+// rr_bank_remove (include/rerank_mi355.h, REMOVING PASSAGES): the plan on the host (rr_bank_remove_plan, bank_move.hip: every refusal
+// comes out of it or stands in front of it), the staging block and the move table on the device, the moves over every per-row
+// array window by window, one synchronisation; the host table only then.  Last, the inverted file over the surviving prefix,
+// from the builder rr_bank_build_ivf uses.
+int rr_bank_remove(rr_bank_handle b, const int32_t* indices_host, int n, int32_t* new_index_host_out, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int {
+    const char* what = "rr_bank_remove";
+    if (!b) return RR_ERR_BAD_ARG;
+    if (n < 0) return bfail(b, RR_ERR_BAD_SHAPE, "%s: n=%d", what, n);
+    if (n > 0 && !indices_host) return bfail(b, RR_ERR_BAD_ARG, "%s: null indices", what);
+    hipStream_t st = (hipStream_t)hip_stream;
+    RR_TRY(bank_capture_guard(b, st, "%s cannot be captured into a graph (it allocates its staging block and synchronises)", what));
+    const int held = (int)b->first.size();
+    const size_t rb = b->resid_row_bytes();
+    const size_t widest = b->nbits ? std::max<size_t>(rb, sizeof(int32_t)) : (size_t)b->D * sizeof(uint16_t);
+    const int64_t window_rows = (int64_t)(rr_bank_move_staging_bytes() / widest);      // at least 4: 4 KiB over 1024 bytes a row
+    std::vector<int32_t> new_index;
+    std::vector<rr_bank_move> moves;
+    int32_t bad = -1;
+    const int prc = rr_bank_remove_plan(b->len.data(), held, indices_host, n, window_rows, &new_index, &moves, &bad);
+    if (prc == RR_REMOVE_PLAN_OUTSIDE) return bfail(b, RR_ERR_BAD_SHAPE, "%s: index %d lies outside the bank's %d passages", what, bad, held);
+    if (prc == RR_REMOVE_PLAN_TWICE) return bfail(b, RR_ERR_BAD_SHAPE, "%s: index %d is given twice", what, bad);
+    if (prc) return bfail(b, RR_ERR_BAD_SHAPE, "%s: n=%d of %d passages", what, n, held);
+    if (n == 0) {
+      if (new_index_host_out && held) memcpy(new_index_host_out, new_index.data(), (size_t)held * sizeof(int32_t));
+      return RR_OK;
+    }
+    RR_BHIP(b, hipSetDevice(b->device));
+    if (!moves.empty()) {
+      rr_move_array arrays[3];
+      int na = 0;
+      if (b->nbits) {
+        arrays[na++] = rr_move_array{b->resid, (int)rb};
+        arrays[na++] = rr_move_array{b->codes, (int)sizeof(int32_t)};
+      } else {
+        arrays[na++] = rr_move_array{b->rows, (int)widest};
+      }
+      arrays[na++] = rr_move_array{b->mask, 1};
+      bool allocated = false;
+      size_t bytes = 0;
+      const hipError_t e = bank_move_block(moves, arrays, na, widest, st, &allocated, &bytes);
+      if (e != hipSuccess && !allocated)
+        return bfail(b, e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP, "%s: a staging block of %zu bytes: %s (the bank is unchanged)", what, bytes,
+                     hipGetErrorString(e));
+      if (e != hipSuccess)
+        return bfail(b, RR_ERR_HIP, "%s: moving the rows failed: %s (the bank's rows are undefined: clear it)", what, hipGetErrorString(e));
+    } else {
+      RR_BHIP(b, hipStreamSynchronize(st));         // only trailing passages go: nothing moves
+    }
+    // the host table: the survivors back to back, in their order
+    int first_gone = held;
+    int64_t row = 0;
+    size_t kept = 0;
+    for (int p = 0; p < held; ++p) {
+      if (new_index[(size_t)p] < 0) {
+        first_gone = std::min(first_gone, p);
+        continue;
+      }
+      b->first[kept] = row;
+      b->len[kept] = b->len[(size_t)p];
+      row += b->len[kept++];
+    }
+    b->first.resize(kept);
+    b->len.resize(kept);
+    b->used_rows = row;
+    b->table_n = std::min(b->table_n, (size_t)first_gone);    // the search's device table is current up to the first moved passage
+    if (new_index_host_out) memcpy(new_index_host_out, new_index.data(), (size_t)held * sizeof(int32_t));
+    // the inverted file covered passages 0 .. P - 1: it now covers the survivors among them, a prefix of the bank
+    const int P = b->ivf.passages;
+    if (P > first_gone) {
+      int P2 = 0;
+      for (int p = 0; p < P; ++p) P2 += new_index[(size_t)p] >= 0;
+      rr_ivf f{};
+      const hipError_t e = P2 ? rr_ivf_build(bank_view(b), b->first.data(), b->len.data(), P2, st, &f) : hipSuccess;
+      rr_ivf_free(&b->ivf);                           // hipFree waits for a search that still reads the previous file
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return bfail(b, e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP, "%s: the %d passages are removed, but the inverted file over the "
+                     "remaining %d of its passages could not be built: %s; the file is gone and must be built again (rr_bank_build_ivf)", what, n,
+                     P2, hipGetErrorString(e));
+      }
+      b->ivf = f;
+    }
+    return RR_OK;
+  });
+}
+
+// rr_op_bank_move_rows (include/rerank_mi355_diag.h): the plan and the moves of rr_bank_remove over one raw device array
+int rr_op_bank_move_rows(void* array, int row_bytes, const int32_t* lengths_host, int32_t n, const int32_t* remove_host, int32_t m, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int {
+    if (!array || (((uintptr_t)array) & 15) || (n > 0 && !lengths_host) || (m > 0 && !remove_host)) return RR_ERR_BAD_ARG;
+    if (!rr_bank_move_row_bytes_ok(row_bytes)) return RR_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)hip_stream;
+    RR_TRY(capture_guard(nullptr, st, "%s cannot be captured into a graph", "rr_op_bank_move_rows"));
+    std::vector<int32_t> new_index;
+    std::vector<rr_bank_move> moves;
+    const int64_t window_rows = (int64_t)(rr_bank_move_staging_bytes() / (size_t)row_bytes);
+    if (rr_bank_remove_plan(lengths_host, n, remove_host, m, window_rows, &new_index, &moves, nullptr)) return RR_ERR_BAD_SHAPE;
+    if (moves.empty()) return RR_OK;
+    const rr_move_array one{array, row_bytes};
+    bool allocated = false;
+    size_t bytes = 0;
+    const hipError_t e = bank_move_block(moves, &one, 1, (size_t)row_bytes, st, &allocated, &bytes);
+    return e == hipSuccess ? RR_OK : e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP;
+  });
+}
+
+// rr_util_bank_remove_plan (include/rerank_mi355_diag.h): rr_bank_remove's plan over the caller's arrays
+int rr_util_bank_remove_plan(const int32_t* lengths, int32_t n, const int32_t* remove, int32_t m, int64_t window_rows, int32_t* new_index_out,
+                             int64_t* moves_out, int64_t moves_cap, int64_t* n_moves_out) {
+  return guarded(nullptr, [&]() -> int {
+    if ((n > 0 && !lengths) || (m > 0 && !remove) || (moves_out && moves_cap < 0)) return RR_ERR_BAD_ARG;
+    std::vector<int32_t> new_index;
+    std::vector<rr_bank_move> moves;
+    if (rr_bank_remove_plan(lengths, n, remove, m, window_rows, &new_index, &moves, nullptr)) return RR_ERR_BAD_SHAPE;
+    if (moves_out && (int64_t)moves.size() > moves_cap) return RR_ERR_BAD_SHAPE;
+    static_assert(sizeof(rr_bank_move) == 4 * sizeof(int64_t), "a move is four int64");
+    if (new_index_out && n) memcpy(new_index_out, new_index.data(), (size_t)n * sizeof(int32_t));
+    if (moves_out && !moves.empty()) memcpy(moves_out, moves.data(), moves.size() * sizeof(rr_bank_move));
+    if (n_moves_out) *n_moves_out = (int64_t)moves.size();
+    return RR_OK;
+  });
+}
+
 // ---- the entry points that share a body above (run through guarded(): no C++ exception crosses the ABI), and the small ones
 int rr_bank_clear(rr_bank_handle b) {
   if (!b) return RR_ERR_BAD_ARG;

@@ -2290,6 +2290,7 @@ int rr_set_tuning(const char* key, int value) {
   if (!strcmp(key, "m_alternate")) return rr_set_m_alternate(value);
   if (!strcmp(key, "li_lds_kb")) return rr_set_li_lds_kb(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
   if (!strcmp(key, "search_chunk")) return rr_set_search_chunk(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
+  if (!strcmp(key, "bank_move_kb")) return rr_set_bank_move_kb(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
   if (!strcmp(key, "compress_chunk")) return rr_set_compress_chunk(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
   if (!strcmp(key, "compress_stop_after")) return rr_set_compress_stop_after(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;
   if (!strcmp(key, "kmeans_stop_after")) return rr_set_kmeans_stop_after(value) == 0 ? RR_OK : RR_ERR_BAD_ARG;

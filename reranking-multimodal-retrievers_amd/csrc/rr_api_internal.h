@@ -145,7 +145,7 @@ struct rr_model {
   int asm_next = 0;
 };
 
-// rr_bank_* (include/rerank_mi355.h): an append-only device store of passages.  rows [capacity_rows][D] fp16 bits, one mask byte
+// rr_bank_* (include/rerank_mi355.h): a device store of passages, rows back to back (appended; rr_bank_remove compacts).  rows [capacity_rows][D] fp16 bits, one mask byte
 // per row, and the host table (first row, length) per passage.  Its own staging slots: rr_bank_add belongs to no handle.
 // A compressed bank (rr_bank_create_plaid, nbits != 0) holds per row a centroid code and D * nbits / 8 residual bytes in place of
 // `rows`, and the codec's tables: centroids [n_centroids][D] fp16 bits, weights [2^nbits] float32.

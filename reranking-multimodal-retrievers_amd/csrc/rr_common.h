@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 typedef uint16_t bf16_t;  // raw bf16 bit pattern
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -547,6 +549,26 @@ hipError_t rr_launch_bank_merge(const int32_t* indices_in, const float* scores_i
 void rr_bank_merge_host(const int32_t* indices_in, const float* scores_in, const int32_t* counts_in, long long part_stride,
                         long long count_stride, int n_parts, const int32_t* part_offsets, int n_queries, int k_in, int k,
                         int32_t* indices_out, float* scores_out, int32_t* counts_out, int32_t* parts_out);
+// rr_bank_remove (bank_move.hip; "REMOVING PASSAGES", include/rerank_mi355.h).  rr_bank_remove_plan is the one definition of what a
+// removal does: new_index [n] (old dense index -> new, -1: removed) and the moves, the runs of surviving rows behind the first
+// removed passage cut at the borders of the windows of window_rows destination rows, in order.  0, or one of the statuses below
+// with nothing written (*bad_index: the index outside [0, n) or named twice).  rr_launch_bank_move_gather: the rows of one window
+// ([win_dst_row, + win_rows), covered by moves_dev[0 .. n_moves)) of one array (rb bytes a row: a power of two, or a multiple of 16,
+// at most 1024; src and staging 16-byte aligned) from their sources to the front of `staging`.  rr_bank_move_run: a whole plan over
+// several arrays, per window and array that launch and one device-to-device copy; enqueues only.
+struct rr_bank_move { int64_t window, src_row, dst_row, rows; };
+struct rr_move_array { void* base; int rb; };
+constexpr int RR_REMOVE_PLAN_BAD_SHAPE = 1, RR_REMOVE_PLAN_OUTSIDE = 2, RR_REMOVE_PLAN_TWICE = 3;
+constexpr int RR_BANK_MOVE_KB_DEFAULT = 262144;
+int rr_bank_remove_plan(const int32_t* lengths, int n, const int32_t* remove, int m, int64_t window_rows, std::vector<int32_t>* new_index,
+                        std::vector<rr_bank_move>* moves, int32_t* bad_index);
+bool rr_bank_move_row_bytes_ok(int rb);
+hipError_t rr_launch_bank_move_gather(const rr_bank_move* moves_dev, int n_moves, long long win_dst_row, long long win_rows, const void* src,
+                                      void* staging, int rb, hipStream_t st);
+hipError_t rr_bank_move_run(const rr_bank_move* moves_host, size_t n_moves, const rr_bank_move* moves_dev, const rr_move_array* arrays,
+                            int n_arrays, void* staging, hipStream_t st);
+int rr_set_bank_move_kb(int kb);            // rr_set_tuning("bank_move_kb"): 4 .. 1048576, -1 outside
+size_t rr_bank_move_staging_bytes();
 // The inverted file of a compressed bank (bank_ivf.hip; "THE INVERTED FILE", include/rerank_mi355.h): offsets [n_centroids + 1] and
 // pids [postings] on the device, the passages it covers and its longest list.  rr_ivf_build fills an EMPTY one over the host table
 // (first, len) of P passages (it allocates and synchronises st; hipErrorOutOfMemory: an allocation failed, nothing is kept);

@@ -84,10 +84,11 @@ class PlaidSearch:
 class BankFilter:
     """A candidate filter of the bank searches (PassageBank.filter; "CANDIDATE FILTERS", include/rerank_mi355.h): `bits`, the device
     bitmap int32 [rows, ld] (bit i & 31 of word i >> 5 of a row: dense bank index i), `rows` (1: one set for every query; else one
-    row per query) and `passages`, the passage count of the bank when it was built: passages added later are not allowed by it."""
+    row per query) and `passages`, the passage count of the bank when it was built: passages added later are not allowed by it;
+    `generation`, the bank's generation then: a removal renumbers the passages, and a filter from before it names the old ones."""
 
-    def __init__(self, bits, rows: int, passages: int):
-        self.bits, self.rows, self.passages = bits, int(rows), int(passages)
+    def __init__(self, bits, rows: int, passages: int, generation: int = 0):
+        self.bits, self.rows, self.passages, self.generation = bits, int(rows), int(passages), int(generation)
 
     def __repr__(self) -> str:
         return f"BankFilter(rows={self.rows}, passages={self.passages})"
@@ -140,6 +141,43 @@ class BankTable:
                 raise KeyError(f"passage id {pid!r} is not in the bank") from None
             idx[i], lens[i] = j, self.lengths[j]
         return idx, lens
+
+    def check_remove(self, passage_ids: Sequence):
+        """The dense indices of `passage_ids` as a list; KeyError names an id the table does not hold, ValueError one given
+        twice; nothing is changed."""
+        idx = self.lookup(passage_ids)[0].tolist()
+        if len(set(idx)) != len(idx):
+            seen = set()
+            for pid in passage_ids:
+                if pid in seen:
+                    raise ValueError(f"passage id {pid!r} is given twice: an id is removed once")
+                seen.add(pid)
+        return idx
+
+    def remove(self, indices: Sequence[int]) -> list:
+        """Drop the passages at the dense `indices` (distinct, inside the table: IndexError / ValueError, nothing changed): the
+        others keep their order and are renumbered from 0; `index_of`, `ids` and `lengths` are rebuilt.  Returns the map old
+        dense index -> new dense index, -1 for a removed passage."""
+        n = len(self.lengths)
+        gone = set()
+        for i in indices:
+            i = int(i)
+            if not 0 <= i < n:
+                raise IndexError(f"index {i} lies outside the table's {n} passages")
+            if i in gone:
+                raise ValueError(f"index {i} is given twice")
+            gone.add(i)
+        new_index, ids, lengths = [], [], []
+        for i in range(n):
+            if i in gone:
+                new_index.append(-1)
+            else:
+                new_index.append(len(ids))
+                ids.append(self.ids[i])
+                lengths.append(self.lengths[i])
+        self.ids, self.lengths = ids, lengths
+        self.index_of = {pid: j for j, pid in enumerate(ids)}
+        return new_index
 
     def clear(self) -> None:
         self.index_of.clear()
@@ -530,9 +568,11 @@ def write_plaid_index(index_path: str, codec: "PlaidCodec", chunks, *, ivf=None,
 
 
 class PassageBank:
-    """An append-only device store of passage token embeddings under the caller's ids: fp16 rows, or with a `codec` (PlaidCodec)
+    """A device store of passage token embeddings under the caller's ids (`add`, `remove`): fp16 rows, or with a `codec` (PlaidCodec)
     the residual codes of a ColBERTv2 / PLAID index, decoded on the device in every forward; one mask byte per row either way.
     Created by RerankEngine.create_bank; usable by every interaction engine of the same device and li_dim."""
+
+    generation = 0                           # incremented by `remove`: dense indices from before it (a BankFilter's) are stale
 
     def __init__(self, engine, capacity_rows: int, max_passages: int, codec: Optional[PlaidCodec] = None):
         from . import _lib as L
@@ -880,7 +920,7 @@ class PassageBank:
         bits = torch.empty((rows, ld), device=self.device, dtype=torch.int32)
         self._check(self.lib.rr_bank_filter_fill(self.h, indices.ctypes.data if indices.size else None, offsets.ctypes.data, rows, int(exclude),
                                                  bits.data_ptr(), ld, self._stream()), "rr_bank_filter_fill", bad_shape=ValueError)
-        return BankFilter(bits, rows, passages)
+        return BankFilter(bits, rows, passages, self.generation)
 
     def search(self, engine, query_li, k: int, first: int = 0, count: Optional[int] = None, plaid: Optional[PlaidSearch] = None,
                filter: Optional[BankFilter] = None):
@@ -895,6 +935,9 @@ class PassageBank:
         length on the exact path too.  A filter built for fewer passages than the range ends at raises ValueError."""
         ids = self.table.ids
         if filter is not None:
+            if getattr(filter, "generation", self.generation) != self.generation:
+                raise ValueError(f"search: the filter was built at generation {filter.generation} of the bank, a removal has renumbered "
+                                 f"its passages since (generation {self.generation}): build it again (PassageBank.filter)")
             end = len(self.table) if count is None else int(first) + int(count)
             if filter.passages < end:
                 raise ValueError(f"search: the filter was built for {filter.passages} passages, the range ends at {end}: build it again "
@@ -985,6 +1028,34 @@ class PassageBank:
         self._check(self.lib.rr_bank_load_ivf(self.h, offsets.data_ptr(), pids.data_ptr() if pids.numel() else None, int(bool(verify)),
                                               self._stream()), "rr_bank_load_ivf", bad_shape=ValueError)
         return self.ivf_info()
+
+    def remove(self, passage_ids: Sequence) -> dict:
+        """Remove the passages `passage_ids` and compact the rest on the device (rr_bank_remove): afterwards the bank is what a
+        fresh bank filled with the survivors in their order would be, bit for bit; their dense indices are renumbered from 0,
+        and the freed rows and passage slots serve later adds (a removed id may be added again).  An inverted file stays, rebuilt
+        over the survivors of the passages it covered.  Returns {"passages": held now, "rows_freed", "new_index": int32 numpy
+        array, old dense index -> new, -1 for a removed passage}.  A load-time call: it allocates its staging block and
+        synchronises the current stream; work on other streams that reads the bank must have completed.  An id the bank does not
+        hold raises KeyError, an id given twice ValueError, a staging block that cannot be allocated MemoryError, each with the
+        bank unchanged.  `generation` goes up by one: filters built before (PassageBank.filter) and a ShardedBank's refresh() are
+        stale.  If only the rebuild of the inverted file fails, the passages are removed, the file is gone (build_ivf) and the
+        library's error is raised."""
+        import numpy as np
+        ids = list(passage_ids)
+        idx = np.ascontiguousarray(self.table.check_remove(ids), dtype=np.int32)
+        held = len(self.table)
+        before = self.info()["rows_used"]
+        new_index = np.empty(held, dtype=np.int32)
+        rc = self.lib.rr_bank_remove(self.h, idx.ctypes.data if idx.size else None, int(idx.size), new_index.ctypes.data if held else None,
+                                     self._stream())
+        now = self.info()
+        if rc < 0 and now["passages"] == held:                   # refused, or failed before anything changed
+            self._check(rc, "rr_bank_remove", bad_shape=ValueError)
+        if idx.size:
+            self.table.remove(idx.tolist())
+            self.generation += 1
+        self._check(rc, "rr_bank_remove", bad_shape=ValueError)   # the passages went, the inverted file's rebuild failed
+        return dict(passages=now["passages"], rows_freed=before - now["rows_used"], new_index=new_index)
 
     def clear(self) -> None:
         """Forget every passage (rr_bank_clear; the capacity stays; the inverted file goes).  Forwards that read the bank must have completed."""

@@ -382,13 +382,15 @@ def exchange_bank_results(local, part_offsets, k: int, group=None, merge: Option
 class ShardedBank:
     """This rank's PassageBank as one part of a corpus split over the ranks of `group`, rank after rank in corpus order.
     `refresh()` is a load-time collective: it all-gathers every rank's passage count into `part_offsets` and the passage ids
-    (all_gather_object) into the global id table `ids`; call it again after adds.  `search` is the local search plus the
+    (all_gather_object) into the global id table `ids`, and records the bank's `generation`; call it again after adds and after
+    a removal (each rank removes locally, PassageBank.remove, then all refresh).  `search` is the local search plus the
     exchange.  The queries are the caller's to replicate: every rank passes the same `query_li`."""
 
     def __init__(self, bank, group=None):
         self.bank, self.group = bank, group
         self.part_offsets = None
         self.ids = None
+        self.generation = None
 
     def refresh(self) -> None:
         world = dist.get_world_size(self.group)
@@ -403,6 +405,7 @@ class ShardedBank:
         if self.part_offsets[-1] >= 1 << 31:
             raise OverflowError(f"ShardedBank: {self.part_offsets[-1]} passages (global indices are int32)")
         self.ids = [pid for t in tables for pid in t]
+        self.generation = getattr(self.bank, "generation", 0)
 
     def search_merged(self, engine, query_li, k: int, plaid=None, filter=None, merge: Optional[Callable] = None) -> dict:
         """The merged result on the device, as exchange_bank_results returns it (global indices, scores, counts, parts)."""
@@ -410,7 +413,7 @@ class ShardedBank:
         if self.part_offsets is None:
             raise RuntimeError("ShardedBank: call refresh() (on every rank) before the first search, and again after adds")
         rank = dist.get_rank(self.group)
-        if self.part_offsets[rank + 1] - self.part_offsets[rank] != len(self.bank):
+        if self.part_offsets[rank + 1] - self.part_offsets[rank] != len(self.bank) or self.generation != getattr(self.bank, "generation", 0):
             raise RuntimeError("ShardedBank: the bank has changed since refresh(): call it again on every rank")
         return exchange_bank_results(lambda: search_bank_part(engine, self.bank, query_li, k, plaid, filter), self.part_offsets, k,
                                      self.group, merge=merge, engine=engine, n_queries=int(query_li.shape[0]))

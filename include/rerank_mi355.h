@@ -567,7 +567,8 @@ int rr_bank_add(rr_bank_handle b, const void* context_li, int dtype, const float
  * Checked on the host before anything is enqueued, a refused call leaves the bank unchanged: every length >= 1 and every code in
  * [0, n_centroids) (RR_ERR_BAD_SHAPE), the row and the passage capacity (RR_ERR_OOM).  A LOAD-TIME call: it copies from the
  * caller's host memory on hip_stream and synchronises that stream, so the host buffers may be reused when it returns; not
- * capturable into a graph (RR_ERR_BAD_ARG under stream capture).
+ * capturable into a graph (RR_ERR_BAD_ARG under stream capture).  An inverted file the bank holds (THE INVERTED FILE, below) does
+ * not cover the new passages until rr_bank_extend_ivf is called.
  * rr_bank_format: nbits (0 for an fp16 bank), the number of centroids (0) and the device bytes one row takes (mask byte included);
  * any pointer may be NULL.
  * The two formats do not mix: rr_bank_add on a compressed bank and rr_bank_add_plaid on an fp16 bank return RR_ERR_UNSUPPORTED.
@@ -611,7 +612,8 @@ int rr_bank_format(rr_bank_handle b, int32_t* nbits_out, int32_t* n_centroids_ou
  * cutoffs, and for an li_dim that is not a multiple of 16 (the matrix-core step; li_dim 8, which a compressed bank otherwise
  * takes, is out); the rest as rr_bank_add.  It enqueues on hip_stream and does not synchronise, except when the bank's scratch
  * (8 bytes per kept row of the call, times 1 + the number of centroid splits; grow-only) has to grow: then it synchronises the
- * device once.  Two adds of one bank in flight on different streams would share that scratch: order them.
+ * device once.  Two adds of one bank in flight on different streams would share that scratch: order them.  As after
+ * rr_bank_add_plaid, an inverted file covers the new passages only after rr_bank_extend_ivf (on the same stream, or behind the add).
  * rr_bank_add on a compressed bank still refuses.  Python: PlaidCodec(bucket_cutoffs=...), PassageBank.add_compress. */
 int rr_bank_set_plaid_cutoffs(rr_bank_handle b, const float* cutoffs_host);
 int rr_bank_add_compress(rr_bank_handle b, const void* context_li, int dtype, const float* context_mask, const int32_t* lengths, int n,
@@ -824,9 +826,9 @@ int rr_bank_search_plaid(rr_handle h, rr_bank_handle b, const float* query_li, i
  * (8 (C + 1) + 4 postings bytes kept; 16 P + 4 C + P / 8 bytes for the call), reads the postings total and the longest list back
  * and synchronises hip_stream; not capturable into a graph (RR_ERR_BAD_ARG).  An fp16 bank: RR_ERR_UNSUPPORTED; an empty bank:
  * RR_ERR_BAD_SHAPE; a failed allocation: RR_ERR_OOM with the bank unchanged: a previous file survives a failed rebuild.
- * LIFETIME: rr_bank_clear drops the file; passages added after a build leave it valid for its prefix 0 .. P-1 (build again to
- * cover them; there is no incremental update); rr_bank_remove leaves the bank with the file over the survivors of that prefix,
- * rebuilt by this builder when one of them went; rr_bank_destroy frees it.
+ * LIFETIME: rr_bank_clear drops the file; passages added after a build (rr_bank_add_plaid, rr_bank_add_compress) leave it valid
+ * for its prefix 0 .. P-1 until rr_bank_extend_ivf (below) extends it over them, or a new build covers them; rr_bank_remove leaves
+ * the bank with the file over the survivors of that prefix, rebuilt by this builder when one of them went; rr_bank_destroy frees it.
  * rr_bank_ivf_info: passages_covered (0: no file), the postings total and the longest list; any pointer may be NULL.
  * rr_bank_ivf_read copies offsets [C + 1] and pids [postings] to HOST buffers (either may be NULL) and synchronises hip_stream;
  * RR_ERR_BAD_ARG without a file.  Errors of these calls: rr_bank_last_error.
@@ -841,11 +843,33 @@ int rr_bank_search_plaid(rr_handle h, rr_bank_handle b, const float* query_li, i
  * results silently; verify == 0 trusts the caller and costs the upload alone.  After every refusal and failure the bank keeps the
  * file it had.  A load-time call: it allocates and synchronises hip_stream.
  *
+ * rr_bank_extend_ivf extends the file over the passages added since it was built.  CONTRACT: afterwards the bank holds the
+ * inverted file over EVERY passage it holds now, byte for byte the file rr_bank_build_ivf would build at that moment: offsets, pids,
+ * passages_covered, postings and longest_list, the same bytes from run to run; so every rr_bank_search_plaid_ivf*, rr_bank_ivf_read
+ * and saved file equals that of a fresh build.  A file over P0 < P passages is extended as under HOW; P0 == P: RR_OK, nothing is
+ * allocated, enqueued or synchronised and the file is untouched; with no file the call IS rr_bank_build_ivf (the same builder), so
+ * a caller may call this one entry after every add.  The refusals are those of rr_bank_build_ivf, in its order: a NULL bank
+ * (RR_ERR_BAD_ARG), an fp16 bank (RR_ERR_UNSUPPORTED), an empty bank (RR_ERR_BAD_SHAPE), a capturing stream (RR_ERR_BAD_ARG).
+ * ALL OR NOTHING: the extended file is built beside the old one and takes its place only when complete; after RR_ERR_OOM or
+ * RR_ERR_HIP the bank keeps the file it had and rr_bank_last_error names the step that failed.  A load-time call: it allocates
+ * (8 (C + 1) + 4 (postings_old + postings_new) bytes kept; for the call the old file, which is freed when the new one has taken its
+ * place, 16 (P - P0) + 4 C bytes, and (P - P0) / 8 bytes of bitmap when a list gains more than 4096 passages), reads the new
+ * postings total and the longest list back and synchronises hip_stream.
+ * HOW (csrc/bank_ivf.hip).  An add only brings indices above every index of the file, so a new list is the old list followed by
+ * the sorted new entries.  The count walks the passages P0 .. P-1 alone; one scan launch turns the old offsets and the new counts
+ * into the new offsets, the total and the longest merged list; one launch copies the old postings to their new places, the work
+ * cut into runs of 512 postings (not by list: one list holding every passage costs what many short ones cost; the grid does not
+ * depend on longest_list), 16-byte accesses where source and destination are aligned alike and narrower ones elsewhere; the fill
+ * walks the new passages again and writes through cursors that start behind each list's old entries; and only the TAILS are
+ * sorted, in LDS up to 4096 entries, through a bitmap of P - P0 bits above.  The old part of a list is never touched again.
+ * Integer vector atomics only, 64-bit offsets.  Against a rebuild it saves the two walks over the old rows and the sort of the old
+ * entries: tools/bench_bank_ivf_extend.py, profiles/bank_ivf_extend_bench.json.log.
+ *
  * rr_bank_search_plaid_ivf takes exactly the arguments of rr_bank_search_plaid.  CONTRACT: indices_out, scores_out and counts_out
  * are bit for bit those of rr_bank_search_plaid with the same arguments, the -1 / -inf behind the count included; its checks, its
  * refusals and the graph-capture refusal are those of rr_bank_search_plaid, in the same order.  One refusal more, behind the
  * others: RR_ERR_UNSUPPORTED when the bank has no inverted file, or when [first_passage, first_passage + n_passages) reaches
- * beyond passages_covered; rr_last_error says to call rr_bank_build_ivf.
+ * beyond passages_covered; rr_last_error says to call rr_bank_build_ivf (rr_bank_extend_ivf serves as well).
  * Stages 0 - 2 (centroid scores, cells, bitmaps) are rr_bank_search_plaid's.  Its scan and its selection over the dense rows are
  * replaced: CANDIDATES: per query a bitmap over the passages of the range; every distinct cell of the query ORs in the passages of
  * its list that lie in the range (a set: no order enters), and the bitmap is compacted into an ASCENDING candidate list [nq][cap]
@@ -861,9 +885,10 @@ int rr_bank_search_plaid(rr_handle h, rr_bank_handle b, const float* query_li, i
  * bytes: with cap <= n never more than rr_bank_search_plaid's but for the bitmap and the candidate list (8 nq n against
  * 4 nq (n / 32 + 3 cap)).  Ten launches, a memset and the selection passes, booked in the profile's `tail` class.
  * LIMITS: those of rr_bank_search_plaid (ndocs <= 1024, one device per call with rr_bank_merge_topk behind it for a split bank, compressed banks); rr_bank_search_plaid_tap does not cover
- * this entry.  Under a candidate filter: rr_bank_search_plaid_ivf_filtered below.  (Python: RerankEngine.bank_build_ivf / bank_search_plaid_ivf, PassageBank.build_ivf / ivf / save_ivf / load_ivf,
+ * this entry.  Under a candidate filter: rr_bank_search_plaid_ivf_filtered below.  (Python: RerankEngine.bank_build_ivf / bank_extend_ivf / bank_search_plaid_ivf, PassageBank.build_ivf / extend_ivf / ivf / save_ivf / load_ivf,
  * PlaidSearch(..., ivf=True).) */
 int rr_bank_build_ivf(rr_bank_handle b, void* hip_stream);
+int rr_bank_extend_ivf(rr_bank_handle b, void* hip_stream);
 int rr_bank_ivf_info(rr_bank_handle b, int32_t* passages_covered_out, int64_t* postings_out, int32_t* longest_list_out);
 int rr_bank_ivf_read(rr_bank_handle b, int64_t* offsets_host_out, int32_t* pids_host_out, void* hip_stream);
 int rr_bank_load_ivf(rr_bank_handle b, const int64_t* offsets_host, const int32_t* pids_host, int verify, void* hip_stream);
@@ -880,7 +905,8 @@ int rr_bank_load_ivf(rr_bank_handle b, const int64_t* offsets_host, const int32_
  * passage leaves the state of rr_bank_clear.
  * THE INVERTED FILE: a bank that holds a file over its first P passages holds afterwards the file over the survivors among those P
  * (a prefix of the new bank), built by rr_bank_build_ivf's builder and so with the bytes a fresh build gives; with no survivor
- * among them the file is dropped; with no removed passage among them it stays as it is.
+ * among them the file is dropped; with no removed passage among them it stays as it is.  Passages behind the prefix stay
+ * uncovered: rr_bank_extend_ivf takes the file over them, as after an add.
  * A LOAD-TIME CALL, like rr_bank_build_ivf: it allocates a staging block (at most 256 MiB, and 32 bytes per run of surviving rows and window),
  * enqueues on hip_stream and synchronises it before it returns; not capturable into a graph.  Work on OTHER streams that reads the
  * bank must have completed, as for rr_bank_clear.  A bank is still not thread-safe: in particular, no removal while another thread

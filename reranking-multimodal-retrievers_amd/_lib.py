@@ -140,6 +140,7 @@ _SIGS = {
     "rr_op_bank_merge_topk": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "rr_util_bank_merge_topk": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "rr_bank_build_ivf": (C.c_int, [_P, _P]),
+    "rr_bank_extend_ivf": (C.c_int, [_P, _P]),
     "rr_bank_ivf_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "rr_bank_ivf_read": (C.c_int, [_P, _P, _P, _P]),
     "rr_bank_load_ivf": (C.c_int, [_P, _P, _P, C.c_int, _P]),

@@ -466,28 +466,41 @@ int rr_bank_read_plaid(rr_bank_handle b, int32_t index, int32_t* codes_out, uint
   });
 }
 
-// rr_bank_build_ivf (include/rerank_mi355.h): the file is built beside the one the bank holds and takes its place only when complete
+// rr_bank_build_ivf and rr_bank_extend_ivf (include/rerank_mi355.h): one body, the same refusals in the same order.  The file is
+// built beside the one the bank holds and takes its place only when complete.  `extend`: a file that covers every passage is left as
+// it is, one over a prefix is extended (rr_ivf_build reads it), and without a file the call is the build.
+static int bank_ivf_call(rr_bank* b, bool extend, void* hip_stream) {
+  const char* what = extend ? "rr_bank_extend_ivf" : "rr_bank_build_ivf";
+  if (!b) return RR_ERR_BAD_ARG;
+  if (!b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it holds no codes", what);
+  const long long held = (long long)b->first.size();
+  if (held < 1) return bfail(b, RR_ERR_BAD_SHAPE, "%s: the bank holds no passage", what);
+  hipStream_t st = (hipStream_t)hip_stream;
+  RR_TRY(bank_capture_guard(b, st, "%s cannot be captured into a graph (it allocates and synchronises)", what));
+  const int covered = b->ivf.passages;
+  if (extend && covered == held) return RR_OK;            // nothing to add: nothing allocated, enqueued or synchronised
+  RR_BHIP(b, hipSetDevice(b->device));
+  rr_ivf f{};
+  const bool from_old = extend && covered > 0 && covered < held;
+  const char* step = "";
+  const hipError_t e = rr_ivf_build(bank_view(b), b->first.data(), b->len.data(), (int)held, st, &f, from_old ? &b->ivf : nullptr, &step);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (extend)
+      return bfail(b, e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP, "%s: %lld passages behind the %d the file covers, %d centroids: %s "
+                   "failed: %s (the bank and its file are unchanged)", what, held - covered, covered, b->n_centroids, step, hipGetErrorString(e));
+    return bfail(b, e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP, "%s: %lld passages, %d centroids: %s (the bank is unchanged)", what, held,
+                 b->n_centroids, hipGetErrorString(e));
+  }
+  rr_ivf_free(&b->ivf);                               // hipFree waits for a search that still reads the previous file
+  b->ivf = f;
+  return RR_OK;
+}
 int rr_bank_build_ivf(rr_bank_handle b, void* hip_stream) {
-  return guarded(nullptr, [&]() -> int {
-    const char* what = "rr_bank_build_ivf";
-    if (!b) return RR_ERR_BAD_ARG;
-    if (!b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it holds no codes", what);
-    const long long held = (long long)b->first.size();
-    if (held < 1) return bfail(b, RR_ERR_BAD_SHAPE, "%s: the bank holds no passage", what);
-    hipStream_t st = (hipStream_t)hip_stream;
-    RR_TRY(bank_capture_guard(b, st, "%s cannot be captured into a graph (it allocates and synchronises)", what));
-    RR_BHIP(b, hipSetDevice(b->device));
-    rr_ivf f{};
-    const hipError_t e = rr_ivf_build(bank_view(b), b->first.data(), b->len.data(), (int)held, st, &f);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      return bfail(b, e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP, "%s: %lld passages, %d centroids: %s (the bank is unchanged)", what, held,
-                   b->n_centroids, hipGetErrorString(e));
-    }
-    rr_ivf_free(&b->ivf);                             // hipFree waits for a search that still reads the previous file
-    b->ivf = f;
-    return RR_OK;
-  });
+  return guarded(nullptr, [&]() -> int { return bank_ivf_call(b, false, hip_stream); });
+}
+int rr_bank_extend_ivf(rr_bank_handle b, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int { return bank_ivf_call(b, true, hip_stream); });
 }
 
 int rr_bank_ivf_info(rr_bank_handle b, int32_t* passages_covered_out, int64_t* postings_out, int32_t* longest_list_out) {

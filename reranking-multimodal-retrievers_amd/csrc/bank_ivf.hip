@@ -15,6 +15,20 @@
 //   (d) ivf_sort_kernel: a workgroup per list of 2 .. 4096 entries sorts it ascending in LDS (a bitonic network over distinct
 //       integers: one result).  A longer list is rebuilt: its passages set their bits in a bitmap of P bits (atomicOr: a set has
 //       no order) and ivf_compact_kernel writes the set bits out in ascending order.
+// EXTEND, rr_ivf_build with `old`, the file over the first P0 < P passages (rr_bank_extend_ivf; a load-time call like the build, the
+// same function): an add only brings indices above every index of the file, so a new list is the old list followed by the sorted
+// new entries.  The file is written into fresh allocations; `old` is only read.
+//   (a) ivf_mark_kernel<false> over the passages P0 .. P - 1 alone: the table holds the new slots, p_base = P0 makes slot p the
+//       bank passage P0 + p.
+//   (b) ivf_scan_kernel with the old offsets: offsets[c] = old[c] + the exclusive scan of the new counts, the total, the longest
+//       MERGED list and the longest TAIL (what (d) has to sort), one launch, int64.  A list's tail starts at offsets[c] +
+//       (old[c + 1] - old[c]): both offset arrays are live for the call, so (c) and (d) compute it and no array holds it.
+//   (s) ivf_shift_copy_kernel: the old postings to their new places.  The shift offsets[c] - old[c] never decreases with c and the
+//       destination is fresh, so one launch does it; the work is cut into runs of IVF_SHIFT_RUN old postings, not by list (one list
+//       holding every passage costs what many short ones cost; the grid is postings_old / IVF_SHIFT_RUN, whatever the longest list).
+//   (c) ivf_mark_kernel<true> over the new passages, the cursors starting at the tails.
+//   (d) ivf_sort_kernel over the tails of 2 .. 4096 entries; a longer tail through the bitmap, which covers the P - P0 new passages
+//       (bit i: passage P0 + i; the compaction adds P0 back).  The old part of a list is never touched again.
 // SEARCH, rr_launch_ivf_candidates: per query a bitmap over the passages of the range is cleared, ivf_candidates_kernel (a
 // workgroup per (query, cell entry); an entry that repeats an earlier one of its query ends at once) ORs in the passages of the
 // cell's list that lie inside the range (found by two binary searches: the list is sorted), and ivf_compact_kernel turns every
@@ -40,16 +54,21 @@ namespace {
 
 constexpr int IVF_SORT_MAX = 4096;       // entries ivf_sort_kernel sorts in LDS
 constexpr int IVF_COMPACT_THREADS = 1024;
+constexpr int IVF_SHIFT_THREADS = 128;   // ivf_shift_copy_kernel: a workgroup and
+constexpr int IVF_SHIFT_RUN = 512;       // the old postings it moves: 2 KB, one 16-byte access a thread
 
 __device__ __forceinline__ long long shfl_up_i64(long long v, int d) {
   const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_up((int)(uint32_t)((unsigned long long)v >> 32), d, 64);
   return (long long)(((unsigned long long)hi << 32) | lo);
 }
 
+// table [P]: the passages the launch walks; slot p is bank passage p_base + p, the index a list holds.  old_offsets (or null; the
+// extend): a list's cursor starts behind the old_offsets[c + 1] - old_offsets[c] entries it holds already, at its tail.
 template <bool FILL>
 __global__ __launch_bounds__(256) void ivf_mark_kernel(const int32_t* __restrict__ codes, const uint8_t* __restrict__ mask,
-                                                       const rr_bank_slot* __restrict__ table, int P, int C, uint32_t* __restrict__ counts,
-                                                       const int64_t* __restrict__ offsets, int32_t* __restrict__ pids) {
+                                                       const rr_bank_slot* __restrict__ table, int P, int p_base, int C,
+                                                       uint32_t* __restrict__ counts, const int64_t* __restrict__ offsets,
+                                                       const int64_t* __restrict__ old_offsets, int32_t* __restrict__ pids) {
   const int lane = threadIdx.x & 63;
   const long long pl = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (pl >= P) return;                                        // the whole wave
@@ -74,26 +93,30 @@ __global__ __launch_bounds__(256) void ivf_mark_kernel(const int32_t* __restrict
     if (first) {
       const uint32_t pos = atomicAdd(&counts[code], 1u);
       if constexpr (FILL) {
-        const int64_t o = offsets[code];
-        if ((int64_t)pos < offsets[code + 1] - o) pids[o + pos] = p;
+        int64_t o = offsets[code];
+        if (old_offsets) o += old_offsets[code + 1] - old_offsets[code];
+        if ((int64_t)pos < offsets[code + 1] - o) pids[o + pos] = p_base + p;
       }
     }
   }
 }
 
-// info[0]: the postings total, info[1]: the longest list
-__global__ __launch_bounds__(1024) void ivf_scan_kernel(const uint32_t* __restrict__ counts, int C, int64_t* __restrict__ offsets,
-                                                        int64_t* __restrict__ info) {
+// info[0]: the postings total, info[1]: the longest list.  old (or null; the extend) [C + 1]: the offsets of a file whose lists the
+// counts are appended to: offsets[c] = old[c] + the exclusive scan, the total and the longest list are those of the merged lists
+// (old[c + 1] - old[c] + counts[c]: at most the passages held, 32 bits), and info[2] is the longest tail, max counts[c].
+__global__ __launch_bounds__(1024) void ivf_scan_kernel(const uint32_t* __restrict__ counts, int C, const int64_t* __restrict__ old,
+                                                        int64_t* __restrict__ offsets, int64_t* __restrict__ info) {
   __shared__ long long wsum[16];
-  __shared__ uint32_t wmax[16];
+  __shared__ uint32_t wmax[16], wtail[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long per = ((long long)C + 1023) / 1024;
   const int c0 = tid * per < C ? (int)(tid * per) : C, c1 = c0 + per < C ? (int)(c0 + per) : C;
   long long s = 0;
-  uint32_t mx = 0;
+  uint32_t mx = 0, tl = 0;
   for (int c = c0; c < c1; ++c) {
     s += counts[c];
-    mx = max(mx, counts[c]);
+    mx = max(mx, counts[c] + (old ? (uint32_t)(old[c + 1] - old[c]) : 0u));
+    tl = max(tl, counts[c]);
   }
   long long incl = s;
 #pragma unroll
@@ -102,30 +125,45 @@ __global__ __launch_bounds__(1024) void ivf_scan_kernel(const uint32_t* __restri
     if (lane >= d) incl += o;
   }
 #pragma unroll
-  for (int m = 32; m > 0; m >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, m, 64));
+  for (int m = 32; m > 0; m >>= 1) {
+    mx = max(mx, (uint32_t)__shfl_xor((int)mx, m, 64));
+    tl = max(tl, (uint32_t)__shfl_xor((int)tl, m, 64));
+  }
   if (lane == 63) wsum[wave] = incl;
-  if (lane == 0) wmax[wave] = mx;
+  if (lane == 0) {
+    wmax[wave] = mx;
+    wtail[wave] = tl;
+  }
   __syncthreads();
   long long run = incl - s;
   for (int w = 0; w < wave; ++w) run += wsum[w];
   for (int c = c0; c < c1; ++c) {
-    offsets[c] = run;
+    offsets[c] = run + (old ? old[c] : 0);
     run += counts[c];
   }
   if (tid == 1023) {                                          // the last thread ends at the total
+    if (old) run += old[C];
     offsets[C] = run;
     info[0] = run;
   }
   if (tid == 0) {
-    uint32_t m = 0;
-    for (int w = 0; w < 16; ++w) m = max(m, wmax[w]);
+    uint32_t m = 0, t = 0;
+    for (int w = 0; w < 16; ++w) {
+      m = max(m, wmax[w]);
+      t = max(t, wtail[w]);
+    }
     info[1] = m;
+    if (old) info[2] = t;
   }
 }
 
-__global__ __launch_bounds__(256) void ivf_sort_kernel(const int64_t* __restrict__ offsets, int32_t* __restrict__ pids) {
+// workgroup c sorts list c, or with old_offsets (the extend) its tail alone: the entries behind the old_offsets[c + 1] -
+// old_offsets[c] the list held before
+__global__ __launch_bounds__(256) void ivf_sort_kernel(const int64_t* __restrict__ offsets, const int64_t* __restrict__ old_offsets,
+                                                       int32_t* __restrict__ pids) {
   __shared__ uint32_t key[IVF_SORT_MAX];
-  const int64_t o = offsets[blockIdx.x], cnt64 = offsets[blockIdx.x + 1] - o;
+  const int64_t o = offsets[blockIdx.x] + (old_offsets ? old_offsets[blockIdx.x + 1] - old_offsets[blockIdx.x] : 0);
+  const int64_t cnt64 = offsets[blockIdx.x + 1] - o;
   if (cnt64 < 2 || cnt64 > IVF_SORT_MAX) return;              // the whole workgroup
   const int cnt = (int)cnt64, tid = threadIdx.x;
   int n2 = 2;
@@ -146,6 +184,62 @@ __global__ __launch_bounds__(256) void ivf_sort_kernel(const int64_t* __restrict
     }
   }
   for (int i = tid; i < cnt; i += 256) pids[o + i] = (int32_t)key[i];
+}
+
+// n units of U bytes from s to d, both U-aligned, by the IVF_SHIFT_THREADS threads of the workgroup
+template <typename unit_t>
+__device__ __forceinline__ void shift_units(const int32_t* __restrict__ s, int32_t* __restrict__ d, int n, int tid) {
+  const unit_t* __restrict__ su = (const unit_t*)s;
+  unit_t* __restrict__ du = (unit_t*)d;
+  for (int i = tid; i < n; i += IVF_SHIFT_THREADS) du[i] = su[i];
+}
+
+// The extend's copy of the old postings to their places in the new file: entry i of list c goes from old_pids[old_offsets[c] + i] to
+// new_pids[new_offsets[c] + i].  The work is cut by POSTINGS: workgroup g owns old_pids[g * IVF_SHIFT_RUN ...), IVF_SHIFT_RUN entries,
+// finds the list of its first entry by binary search over old_offsets (block-uniform: the loads are scalar) and walks the lists
+// from there.  A piece, the entries of one list inside the run, is contiguous on both sides; the two sides are aligned alike modulo
+// w = the lowest set bit of the byte shift (at most 16): 4-byte accesses up to the first w-aligned source byte, w-byte accesses
+// from there, 4-byte accesses for the rest (the piece copy of bank_move.hip at E = 4).  Plain vector loads and stores.
+__global__ __launch_bounds__(IVF_SHIFT_THREADS) void ivf_shift_copy_kernel(const int64_t* __restrict__ old_offsets,
+                                                                           const int64_t* __restrict__ new_offsets, int C,
+                                                                           const int32_t* __restrict__ old_pids, int32_t* __restrict__ new_pids) {
+  const int tid = threadIdx.x;
+  const long long total = uniform_i64(old_offsets[C]);
+  const long long r0 = (long long)blockIdx.x * IVF_SHIFT_RUN;
+  if (r0 >= total) return;                                    // the whole workgroup
+  const long long r1 = r0 + IVF_SHIFT_RUN < total ? r0 + IVF_SHIFT_RUN : total;
+  int lo = 0, hi = C - 1;                                     // the last list that starts at or below r0: the one that holds entry r0
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (uniform_i64(old_offsets[mid]) <= r0) lo = mid;
+    else hi = mid - 1;
+  }
+  int c = lo;
+  long long r = r0;
+  while (r < r1 && c < C) {
+    const long long end = uniform_i64(old_offsets[c + 1]);
+    const long long stop = end < r1 ? end : r1;
+    const int cnt = (int)(stop - r);                          // at most IVF_SHIFT_RUN; none for an empty list
+    if (cnt > 0) {
+      const int32_t* s = old_pids + r;
+      int32_t* d = new_pids + r + (uniform_i64(new_offsets[c]) - uniform_i64(old_offsets[c]));
+      const unsigned rel = ((unsigned)(uintptr_t)s - (unsigned)(uintptr_t)d) & 15u;
+      const int w = rel ? (int)(rel & (0u - rel)) : 16;       // 4, 8 or 16
+      if (w == 4) {
+        shift_units<uint32_t>(s, d, cnt, tid);
+      } else {
+        int head = (int)(((unsigned)w - ((unsigned)(uintptr_t)s & (unsigned)(w - 1))) & (unsigned)(w - 1)) >> 2;
+        if (head > cnt) head = cnt;
+        const int per = w >> 2, body = (cnt - head) / per;
+        shift_units<uint32_t>(s, d, head, tid);
+        if (w == 8) shift_units<uint2>(s + head, d + head, body, tid);
+        else shift_units<uint4>(s + head, d + head, body, tid);
+        shift_units<uint32_t>(s + head + body * per, d + head + body * per, cnt - head - body * per, tid);
+      }
+    }
+    r = stop;
+    ++c;
+  }
 }
 
 // the passages list[0 .. cnt) as bits of bm (bit pid - first; a passage outside [first, first + n) sets none)
@@ -288,7 +382,7 @@ bool rr_filter_bits_host(const int32_t* indices, const int64_t* offsets, int row
 // info[0] their total, info[1] the largest
 hipError_t rr_launch_count_scan(const uint32_t* counts, int n, int64_t* offsets, int64_t* info, hipStream_t st) {
   if (!counts || !offsets || !info || n < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), dim3(1024), 0, st, counts, n, offsets, info);
+  hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), dim3(1024), 0, st, counts, n, nullptr, offsets, info);
   return hipGetLastError();
 }
 
@@ -298,64 +392,93 @@ void rr_ivf_free(rr_ivf* f) {
   *f = rr_ivf{};
 }
 
-// The inverted file over the P passages (first[i], len[i]) of a compressed bank (host table), into *out (which must be empty).  On
-// a failure nothing is left allocated and *out stays empty; hipErrorOutOfMemory: an allocation failed.  Synchronises `st`.
-hipError_t rr_ivf_build(const rr_bank_view& bank, const int64_t* first, const int32_t* len, int P, hipStream_t st, rr_ivf* out) {
+// The inverted file over the P passages (first[i], len[i]) of a compressed bank (host table), into *out (which must be empty).  With
+// `old`, a file over the first old->passages < P of them, the file is EXTENDED (rr_bank_extend_ivf): only the passages behind the
+// old ones are walked, and *old is read, never written.  On a failure nothing is left allocated and *out stays empty;
+// hipErrorOutOfMemory: an allocation failed.  Synchronises `st`.
+hipError_t rr_ivf_build(const rr_bank_view& bank, const int64_t* first, const int32_t* len, int P, hipStream_t st, rr_ivf* out, const rr_ivf* old,
+                        const char** failed_step) {
   const int C = bank.n_centroids;
   if (!bank.nbits || !bank.codes || !bank.mask || C < 1 || P < 1 || !first || !len || out->offsets || out->pids) return hipErrorInvalidValue;
-  const size_t Wn = ((size_t)P + 31) / 32;
+  if (old && (!old->offsets || !old->pids || old->passages < 1 || old->passages >= P || old->postings < 0)) return hipErrorInvalidValue;
+  const int P0 = old ? old->passages : 0, N = P - P0;         // the passages P0 .. P - 1 are walked
+  const int64_t* old_offsets = old ? old->offsets : nullptr;
+  const size_t Wn = ((size_t)N + 31) / 32;
   rr_bank_slot* table = nullptr;
   uint32_t* counts = nullptr;
   int64_t* info = nullptr;
   uint32_t* bm = nullptr;
   rr_ivf f{};
   hipError_t e = hipSuccess;
-  auto ok = [&](hipError_t x) { if (e == hipSuccess && x != hipSuccess) e = x; return e == hipSuccess; };
-  std::vector<rr_bank_slot> slots((size_t)P);
-  for (int i = 0; i < P; ++i) slots[(size_t)i] = rr_bank_slot{first[i], len[i], 0};
-  int64_t host_info[2] = {0, 0};
-  const unsigned mark_blocks = (unsigned)(((long long)P + 3) / 4);
-  if (ok(hipMalloc((void**)&table, (size_t)P * sizeof(rr_bank_slot))) && ok(hipMalloc((void**)&counts, (size_t)C * sizeof(uint32_t))) &&
-      ok(hipMalloc((void**)&info, 2 * sizeof(int64_t))) && ok(hipMalloc((void**)&f.offsets, ((size_t)C + 1) * sizeof(int64_t))) &&
+  const char* step = "allocating the table, the counts and the offsets";      // what a failure is booked under
+  auto ok = [&](hipError_t x) {
+    if (e == hipSuccess && x != hipSuccess) {
+      e = x;
+      if (failed_step) *failed_step = step;
+    }
+    return e == hipSuccess;
+  };
+  std::vector<rr_bank_slot> slots((size_t)N);
+  for (int i = 0; i < N; ++i) slots[(size_t)i] = rr_bank_slot{first[P0 + i], len[P0 + i], 0};
+  int64_t host_info[3] = {0, 0, 0};
+  const unsigned mark_blocks = (unsigned)(((long long)N + 3) / 4);
+  if (ok(hipMalloc((void**)&table, (size_t)N * sizeof(rr_bank_slot))) && ok(hipMalloc((void**)&counts, (size_t)C * sizeof(uint32_t))) &&
+      ok(hipMalloc((void**)&info, 3 * sizeof(int64_t))) && ok(hipMalloc((void**)&f.offsets, ((size_t)C + 1) * sizeof(int64_t))) &&
       ok(hipMemcpyAsync(table, slots.data(), slots.size() * sizeof(rr_bank_slot), hipMemcpyHostToDevice, st)) &&
       ok(hipMemsetAsync(counts, 0, (size_t)C * sizeof(uint32_t), st))) {
-    hipLaunchKernelGGL(ivf_mark_kernel<false>, dim3(mark_blocks), dim3(256), 0, st, bank.codes, bank.mask, table, P, C, counts, nullptr, nullptr);
-    hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), dim3(1024), 0, st, counts, C, f.offsets, info);
+    step = "the count and the scan";
+    hipLaunchKernelGGL(ivf_mark_kernel<false>, dim3(mark_blocks), dim3(256), 0, st, bank.codes, bank.mask, table, N, P0, C, counts, nullptr, nullptr,
+                       nullptr);
+    hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), dim3(1024), 0, st, counts, C, old_offsets, f.offsets, info);
     ok(hipGetLastError());
-    ok(hipMemcpyAsync(host_info, info, sizeof host_info, hipMemcpyDeviceToHost, st));
+    ok(hipMemcpyAsync(host_info, info, (old ? 3 : 2) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     ok(hipStreamSynchronize(st));                             // `slots` and host_info are pageable memory of this call
   }
+  int64_t longest_sorted = 0;                                 // the longest run the sort has to order: a list, or a tail
   if (e == hipSuccess) {
     f.passages = P;
     f.postings = host_info[0];
     f.longest = (int32_t)host_info[1];
-    if (f.postings < 0 || f.longest < 0 || f.longest > P) e = hipErrorUnknown;
+    longest_sorted = old ? host_info[2] : host_info[1];
+    if (f.postings < (old ? old->postings : 0) || f.longest < 0 || f.longest > P || longest_sorted < 0 || longest_sorted > N)
+      ok(hipErrorUnknown);
   }
+  const int64_t shift_blocks = old ? (old->postings + IVF_SHIFT_RUN - 1) / IVF_SHIFT_RUN : 0;
+  if (e == hipSuccess && shift_blocks > 0x7fffffffLL) ok(hipErrorInvalidValue);
+  step = "allocating the postings";
   if (e == hipSuccess && ok(hipMalloc((void**)&f.pids, (size_t)std::max<int64_t>(f.postings, 1) * sizeof(int32_t))) &&
       ok(hipMemsetAsync(counts, 0, (size_t)C * sizeof(uint32_t), st))) {
-    hipLaunchKernelGGL(ivf_mark_kernel<true>, dim3(mark_blocks), dim3(256), 0, st, bank.codes, bank.mask, table, P, C, counts, f.offsets, f.pids);
-    hipLaunchKernelGGL(ivf_sort_kernel, dim3((unsigned)C), dim3(256), 0, st, f.offsets, f.pids);
+    step = old ? "the copy of the old postings, the fill and the sort of the tails" : "the fill and the sort";
+    if (shift_blocks > 0)
+      hipLaunchKernelGGL(ivf_shift_copy_kernel, dim3((unsigned)shift_blocks), dim3(IVF_SHIFT_THREADS), 0, st, old_offsets, f.offsets, C, old->pids,
+                         f.pids);
+    hipLaunchKernelGGL(ivf_mark_kernel<true>, dim3(mark_blocks), dim3(256), 0, st, bank.codes, bank.mask, table, N, P0, C, counts, f.offsets,
+                       old_offsets, f.pids);
+    hipLaunchKernelGGL(ivf_sort_kernel, dim3((unsigned)C), dim3(256), 0, st, f.offsets, old_offsets, f.pids);
     ok(hipGetLastError());
   }
-  if (e == hipSuccess && f.longest > IVF_SORT_MAX) {          // the lists one LDS slice does not hold, one after the other
-    std::vector<int64_t> off((size_t)C + 1);
+  if (e == hipSuccess && longest_sorted > IVF_SORT_MAX) {     // the lists (tails) one LDS slice does not hold, one after the other
+    std::vector<int64_t> off((size_t)C + 1), was(old ? (size_t)C + 1 : 0);
     int32_t* cnt_dev = (int32_t*)info;                        // the compaction's count: not needed again
+    step = "the bitmap pass over the long lists";
     if (ok(hipMalloc((void**)&bm, Wn * sizeof(uint32_t))) &&
-        ok(hipMemcpyAsync(off.data(), f.offsets, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st)) && ok(hipStreamSynchronize(st))) {
+        ok(hipMemcpyAsync(off.data(), f.offsets, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st)) &&
+        (!old || ok(hipMemcpyAsync(was.data(), old_offsets, was.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st))) &&
+        ok(hipStreamSynchronize(st))) {
       for (int c = 0; c < C && e == hipSuccess; ++c) {
-        const int64_t cnt = off[(size_t)c + 1] - off[(size_t)c];
+        const int64_t start = off[(size_t)c] + (old ? was[(size_t)c + 1] - was[(size_t)c] : 0), cnt = off[(size_t)c + 1] - start;
         if (cnt <= IVF_SORT_MAX) continue;
         if (!ok(hipMemsetAsync(bm, 0, Wn * sizeof(uint32_t), st))) break;
         const unsigned blocks = (unsigned)std::min<int64_t>((cnt + 255) / 256, 4096);
-        hipLaunchKernelGGL(ivf_list_bits_kernel, dim3(blocks), dim3(256), 0, st, f.pids + off[(size_t)c], (long long)cnt, 0, P, bm);
-        hipLaunchKernelGGL(ivf_compact_kernel, dim3(1), dim3(IVF_COMPACT_THREADS), 0, st, bm, (int)Wn, f.pids + off[(size_t)c], 0LL, (int)cnt,
-                           cnt_dev, 0, nullptr, nullptr, rr_passage_filter{}, P);
+        // bit i: passage P0 + i; the compaction adds P0 back
+        hipLaunchKernelGGL(ivf_list_bits_kernel, dim3(blocks), dim3(256), 0, st, f.pids + start, (long long)cnt, P0, N, bm);
+        hipLaunchKernelGGL(ivf_compact_kernel, dim3(1), dim3(IVF_COMPACT_THREADS), 0, st, bm, (int)Wn, f.pids + start, 0LL, (int)cnt, cnt_dev, P0,
+                           nullptr, nullptr, rr_passage_filter{}, N);
         ok(hipGetLastError());
       }
     }
   }
-  const hipError_t es = hipStreamSynchronize(st);             // before the scratch goes
-  ok(es);
+  ok(hipStreamSynchronize(st));                               // before the scratch goes
   if (e != hipSuccess) (void)hipGetLastError();
   if (table) (void)hipFree(table);
   if (counts) (void)hipFree(counts);

@@ -571,11 +571,14 @@ int rr_set_bank_move_kb(int kb);            // rr_set_tuning("bank_move_kb"): 4 
 size_t rr_bank_move_staging_bytes();
 // The inverted file of a compressed bank (bank_ivf.hip; "THE INVERTED FILE", include/rerank_mi355.h): offsets [n_centroids + 1] and
 // pids [postings] on the device, the passages it covers and its longest list.  rr_ivf_build fills an EMPTY one over the host table
-// (first, len) of P passages (it allocates and synchronises st; hipErrorOutOfMemory: an allocation failed, nothing is kept);
+// (first, len) of P passages (it allocates and synchronises st; hipErrorOutOfMemory: an allocation failed, nothing is kept), with
+// `old`, a file over the first old->passages < P of them, by extending that one (rr_bank_extend_ivf; *old is only read); *failed_step (or null) names
+// the step a failure came from;
 // rr_ivf_read copies it to host buffers (either may be null) and synchronises; rr_ivf_host is the definition in host code: it
 // always writes offsets_out and returns the postings total, pids_out (or null) with room for pids_capacity entries.
 struct rr_ivf { int64_t* offsets; int32_t* pids; int32_t passages; int64_t postings; int32_t longest; };
-hipError_t rr_ivf_build(const rr_bank_view& bank, const int64_t* first, const int32_t* len, int P, hipStream_t st, rr_ivf* out);
+hipError_t rr_ivf_build(const rr_bank_view& bank, const int64_t* first, const int32_t* len, int P, hipStream_t st, rr_ivf* out,
+                        const rr_ivf* old = nullptr, const char** failed_step = nullptr);
 void rr_ivf_free(rr_ivf* f);
 hipError_t rr_ivf_read(const rr_ivf& f, int C, int64_t* offsets_host, int32_t* pids_host, hipStream_t st);
 int64_t rr_ivf_host(const int32_t* codes, const uint8_t* mask, const int32_t* lengths, int n, int C, int64_t* offsets_out, int32_t* pids_out,

@@ -954,6 +954,12 @@ class RerankEngine:
         on this engine's current stream: it allocates and synchronises.  Returns bank.ivf_info()."""
         return bank.build_ivf()
 
+    def bank_extend_ivf(self, bank) -> dict:
+        """Take the inverted file of a COMPRESSED `bank` over the passages added since it was built (rr_bank_extend_ivf): the bytes
+        of a fresh bank_build_ivf, from a walk of the new passages alone.  Nothing happens when the file covers the bank; without a
+        file it is bank_build_ivf.  A load-time call on this engine's current stream.  Returns bank.ivf_info()."""
+        return bank.extend_ivf()
+
     def bank_export_plaid(self, bank, first: int = 0, count: Optional[int] = None):
         """A range of a COMPRESSED `bank` as an index stores it, on the device (rr_bank_export_plaid): (codes int32 [R], residuals
         uint8 [R, li_dim * nbits / 8], doclens list), the unmasked rows of every passage back to back: bank.export_compressed.  A

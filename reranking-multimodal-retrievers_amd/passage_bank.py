@@ -19,8 +19,8 @@ score, exactly (rr_bank_search): every passage is scored, nothing is pruned.  Wi
 staged search over a compressed bank (rr_bank_search_plaid, RerankEngine.bank_search_plaid): candidates by centroid, two
 centroid-only pruning passes, exact MaxSim on the survivors.  `PassageBank.build_ivf` builds the bank's inverted file on the
 device (rr_bank_build_ivf: per centroid the sorted unique passages holding a token of that code, the reference's ivf.pid.pt;
-`ivf` / `save_ivf` read and write it), and `PlaidSearch(..., ivf=True)` takes the candidates from it (rr_bank_search_plaid_ivf):
-the same result, with work that follows the lists of the query's cells instead of the rows of the bank.  `PassageBank.filter`
+`extend_ivf` takes it over passages added later, rr_bank_extend_ivf; `ivf` / `save_ivf` read and write it), and
+`PlaidSearch(..., ivf=True)` takes the candidates from it (rr_bank_search_plaid_ivf): the same result, with work that follows the lists of the query's cells instead of the rows of the bank.  `PassageBank.filter`
 makes a candidate filter (a `BankFilter`: a device bitmap over the bank's passages, one set for every query or one per query,
 rr_bank_filter_fill) and `search(..., filter=)` restricts any of the three searches to it (rr_bank_search_filtered,
 rr_bank_search_plaid_filtered, rr_bank_search_plaid_ivf_filtered): the reference's filter_fn.
@@ -655,14 +655,19 @@ class PassageBank:
             raise NotImplementedError("a compressed bank takes residual codes (add_compressed): nothing here compresses embeddings")
         return self._add_padded("rr_bank_add", passage_ids, context_li, context_mask, lengths)
 
-    def add_compress(self, passage_ids: Sequence, context_li, context_mask, lengths: Optional[Sequence[int]] = None) -> int:
+    def add_compress(self, passage_ids: Sequence, context_li, context_mask, lengths: Optional[Sequence[int]] = None,
+                     extend_ivf: bool = False) -> int:
         """`add` for a compressed bank (rr_bank_add_compress): the padded tensors a retriever produces are compressed on the
         device against the codec's centroids and cutoffs and appended as codes and residual bytes — the compressed row of
         include/rerank_mi355.h, what the reference's indexer computes from `context_li.half()`.  Arguments, return value and
-        errors as `add`; an fp16 bank, a codec without cutoffs and an li_dim that is no multiple of 16 raise NotImplementedError."""
+        errors as `add`; an fp16 bank, a codec without cutoffs and an li_dim that is no multiple of 16 raise NotImplementedError.
+        `extend_ivf`: after a successful add, take the inverted file over the new passages (extend_ivf(): a load-time call)."""
         if self.codec is None:
             raise NotImplementedError("add_compress on an fp16 bank: it keeps embeddings as they are (add)")
-        return self._add_padded("rr_bank_add_compress", passage_ids, context_li, context_mask, lengths)
+        first = self._add_padded("rr_bank_add_compress", passage_ids, context_li, context_mask, lengths)
+        if extend_ivf:
+            self.extend_ivf()
+        return first
 
     def _add_padded(self, entry_name: str, passage_ids, context_li, context_mask, lengths) -> int:
         """`add` and `add_compress` behind their own refusals: the padded tensors brought to the device as the entry point
@@ -692,14 +697,15 @@ class PassageBank:
         self.padded_len = max(self.padded_len, Lc)
         return int(first.value)
 
-    def add_compressed(self, passage_ids: Sequence, codes, residuals, doclens: Sequence[int], mask=None) -> int:
+    def add_compressed(self, passage_ids: Sequence, codes, residuals, doclens: Sequence[int], mask=None, extend_ivf: bool = False) -> int:
         """Append the passages `passage_ids` of a compressed bank from an index's own arrays (rr_bank_add_plaid): `codes` [R]
         integer centroid codes and `residuals` [R, D * nbits / 8] uint8, the rows of the passages one after the other, R =
         sum(doclens); `doclens` the rows of each passage; `mask` [R] (non-zero = a token that counts) or None = all ones — the
         ColBERT indexer has dropped the skiplist tokens already.  Host tensors / arrays (a device tensor is copied back).  A
         load-time call: it synchronises the current stream.  Returns the first of the dense indices.  An id added twice, a code
         outside the codec's centroids, a length below 1 or arrays that do not fit the lengths raise ValueError, rows or passage
-        slots that do not suffice MemoryError, an fp16 bank NotImplementedError; the bank is unchanged then."""
+        slots that do not suffice MemoryError, an fp16 bank NotImplementedError; the bank is unchanged then.
+        `extend_ivf`: after a successful add, take the inverted file over the new passages (extend_ivf())."""
         import numpy as np
         import torch
 
@@ -738,15 +744,19 @@ class PassageBank:
                     bad_shape=ValueError)
         self.table.append(ids, ln32.tolist(), int(first.value))
         self.padded_len = max(self.padded_len, int(ln.max()))
+        if extend_ivf:
+            self.extend_ivf()
         return int(first.value)
 
-    def load_plaid_index(self, index_path: str, passage_ids: Optional[Sequence] = None, ivf: bool = False) -> int:
+    def load_plaid_index(self, index_path: str, passage_ids: Optional[Sequence] = None, ivf: bool = False, extend_ivf: bool = False) -> int:
         """Fill a compressed bank from a ColBERTv2 / PLAID index directory (read_plaid_index), chunk by chunk through
         add_compressed.  The bank's codec must hold the index's tables (create the bank with the codec read_plaid_index returns).
         `passage_ids`: the caller's id of passage number i of the index at position i; default: the ids of the directory's
         passage_ids.json when it has one (save_plaid_index writes it), else the passage numbers themselves.
         `ivf`: also load the directory's ivf.pid.pt (load_ivf, verified against the bank) instead of leaving the inverted file to a
         build_ivf; the file numbers passages as the index does, so the bank must be empty before the call (ValueError).
+        `extend_ivf`: after the last chunk, take the bank's inverted file over the passages added (extend_ivf(): once, not per chunk;
+        a bank that held passages and a file before the load keeps that file's lists and gains the new entries).
         Returns the number of passages added."""
         import json
         import os
@@ -776,6 +786,8 @@ class PassageBank:
             added += len(doclens)
         if ivf:
             self.load_ivf(index_path)
+        if extend_ivf:
+            self.extend_ivf()
         return added
 
     def export_compressed(self, first: int = 0, count: Optional[int] = None):
@@ -820,8 +832,8 @@ class PassageBank:
         reference's loader open: the bank walked in chunks of `chunk_passages` passages (the reference's chunk size:
         collection_indexer.py's min(25000, ...)), each exported on the device (rr_bank_export_plaid) and copied to the host; the
         codec; metadata.json ({"dim", "nbits", **config} as its config); the passage ids as passage_ids.json when they are ints or
-        strs; with `ivf` the bank's inverted file as ivf.pid.pt, built first when the bank has none or it covers fewer passages than
-        the bank holds.  The index holds the unmasked rows only, as the reference's indexer would have stored the passages.
+        strs; with `ivf` the bank's inverted file as ivf.pid.pt, extended first (extend_ivf: the bytes of a fresh build) when the bank
+        has none or it covers fewer passages than the bank holds.  The index holds the unmasked rows only, as the reference's indexer would have stored the passages.
         Every sizing call runs before the first file is written: a bank with a passage that has no unmasked row cannot be
         represented (an index's doclens are at least 1) and raises ValueError naming up to eight ids, with nothing written.  An
         fp16 bank raises NotImplementedError, a codec without cutoffs PlaidCodec.save's ValueError, an empty bank ValueError.
@@ -845,7 +857,7 @@ class PassageBank:
         pair = None
         if ivf:
             if self.ivf_info()["passages_covered"] < P:
-                self.build_ivf()
+                self.extend_ivf()
             pair = self.ivf()
 
         def chunks():
@@ -969,6 +981,18 @@ class PassageBank:
         self._check(self.lib.rr_bank_build_ivf(self.h, self._stream()), "rr_bank_build_ivf", bad_shape=ValueError)
         return self.ivf_info()
 
+    def extend_ivf(self) -> dict:
+        """Take the inverted file over the passages added since it was built (rr_bank_extend_ivf): afterwards the bank holds, byte for
+        byte, the file build_ivf would build now.  Only the new passages are walked; the old postings are copied to their new places
+        and the new entries of every list sorted behind them.  A file that covers every passage is left untouched (nothing is
+        allocated or synchronised); without a file the call is build_ivf.  A load-time call otherwise: it allocates the new file
+        beside the old one and synchronises the current stream.  tools/bench_bank_ivf_extend.py times it against build_ivf.
+        Returns ivf_info().  An fp16 bank raises NotImplementedError, a failed allocation MemoryError with the previous file kept."""
+        if self.codec is None:
+            raise NotImplementedError("extend_ivf on an fp16 bank: it holds no centroid codes")
+        self._check(self.lib.rr_bank_extend_ivf(self.h, self._stream()), "rr_bank_extend_ivf", bad_shape=ValueError)
+        return self.ivf_info()
+
     def ivf_info(self) -> dict:
         """rr_bank_ivf_info: passages_covered (0: no inverted file), postings (entries of all lists), longest_list."""
         p, n, m = C.c_int32(0), C.c_int64(0), C.c_int32(0)
@@ -1033,7 +1057,7 @@ class PassageBank:
         """Remove the passages `passage_ids` and compact the rest on the device (rr_bank_remove): afterwards the bank is what a
         fresh bank filled with the survivors in their order would be, bit for bit; their dense indices are renumbered from 0,
         and the freed rows and passage slots serve later adds (a removed id may be added again).  An inverted file stays, rebuilt
-        over the survivors of the passages it covered.  Returns {"passages": held now, "rows_freed", "new_index": int32 numpy
+        over the survivors of the passages it covered (passages behind them stay uncovered: extend_ivf).  Returns {"passages": held now, "rows_freed", "new_index": int32 numpy
         array, old dense index -> new, -1 for a removed passage}.  A load-time call: it allocates its staging block and
         synchronises the current stream; work on other streams that reads the bank must have completed.  An id the bank does not
         hold raises KeyError, an id given twice ValueError, a staging block that cannot be allocated MemoryError, each with the

@@ -85,7 +85,8 @@ class BankFilter:
     """A candidate filter of the bank searches (PassageBank.filter; "CANDIDATE FILTERS", include/rerank_mi355.h): `bits`, the device
     bitmap int32 [rows, ld] (bit i & 31 of word i >> 5 of a row: dense bank index i), `rows` (1: one set for every query; else one
     row per query) and `passages`, the passage count of the bank when it was built: passages added later are not allowed by it;
-    `generation`, the bank's generation then: a removal renumbers the passages, and a filter from before it names the old ones."""
+    `generation`, the bank's generation then: a removal renumbers the passages and a `clear` forgets them (a refill puts other
+    passages under the old numbers), so a filter from before either names passages the bank no longer holds there."""
 
     def __init__(self, bits, rows: int, passages: int, generation: int = 0):
         self.bits, self.rows, self.passages, self.generation = bits, int(rows), int(passages), int(generation)
@@ -572,14 +573,15 @@ class PassageBank:
     the residual codes of a ColBERTv2 / PLAID index, decoded on the device in every forward; one mask byte per row either way.
     Created by RerankEngine.create_bank; usable by every interaction engine of the same device and li_dim."""
 
-    generation = 0                           # incremented by `remove`: dense indices from before it (a BankFilter's) are stale
+    generation = 0                           # incremented by `remove` and by `clear`: dense indices from before (a BankFilter's) are stale
 
     def __init__(self, engine, capacity_rows: int, max_passages: int, codec: Optional[PlaidCodec] = None):
         from . import _lib as L
         self._L, self.lib = L, engine.lib
         self.device, self.li_dim = engine.device, int(engine.arch["li_dim"])
         self.table = BankTable()
-        self.padded_len = 0                  # the longest Lc (compressed: passage) an add has seen: a forward's default padded length
+        self.padded_len = 0                  # the longest Lc (compressed: passage) an add has seen, a high-water mark that `remove`
+                                             # and `clear` never lower: a forward's default padded length
         self.codec = codec
         h = C.c_void_p()
         if codec is None:
@@ -1061,9 +1063,13 @@ class PassageBank:
         array, old dense index -> new, -1 for a removed passage}.  A load-time call: it allocates its staging block and
         synchronises the current stream; work on other streams that reads the bank must have completed.  An id the bank does not
         hold raises KeyError, an id given twice ValueError, a staging block that cannot be allocated MemoryError, each with the
-        bank unchanged.  `generation` goes up by one: filters built before (PassageBank.filter) and a ShardedBank's refresh() are
-        stale.  If only the rebuild of the inverted file fails, the passages are removed, the file is gone (build_ivf) and the
-        library's error is raised."""
+        bank unchanged.  `generation` goes up by one (as `clear` raises it): filters built before (PassageBank.filter) and a
+        ShardedBank's refresh() are stale.  If only the rebuild of the inverted file fails, the passages are removed, the file is
+        gone (build_ivf) and the library's error is raised.
+        `padded_len` stays: it is the high-water mark of the adds (the longest Lc, or compressed passage, an add has seen), not a
+        function of the contents, and it is the default padded context length of the bank forwards, whose fusion normalisers run
+        over the padded axis.  A bank after a removal and a fresh bank of the survivors can therefore differ in their DEFAULT
+        logits; pass `padded_len` to the forward where the two must agree."""
         import numpy as np
         ids = list(passage_ids)
         idx = np.ascontiguousarray(self.table.check_remove(ids), dtype=np.int32)
@@ -1082,9 +1088,13 @@ class PassageBank:
         return dict(passages=now["passages"], rows_freed=before - now["rows_used"], new_index=new_index)
 
     def clear(self) -> None:
-        """Forget every passage (rr_bank_clear; the capacity stays; the inverted file goes).  Forwards that read the bank must have completed."""
+        """Forget every passage (rr_bank_clear; the capacity stays; the inverted file goes).  Forwards that read the bank must have
+        completed.  `generation` goes up by one, as after `remove`: a refill puts other passages under the old dense indices, so
+        filters built before (PassageBank.filter) and a ShardedBank's refresh() are stale.  `padded_len` stays, as after `remove`:
+        the high-water mark of the adds, not a function of the contents."""
         self._check(self.lib.rr_bank_clear(self.h), "rr_bank_clear")
         self.table.clear()
+        self.generation += 1
 
 
 def search_bank_part(engine, bank, query_li, k: int, plaid: Optional[PlaidSearch] = None, filter: Optional[BankFilter] = None) -> dict:

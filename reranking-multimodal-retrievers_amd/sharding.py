@@ -382,8 +382,9 @@ def exchange_bank_results(local, part_offsets, k: int, group=None, merge: Option
 class ShardedBank:
     """This rank's PassageBank as one part of a corpus split over the ranks of `group`, rank after rank in corpus order.
     `refresh()` is a load-time collective: it all-gathers every rank's passage count into `part_offsets` and the passage ids
-    (all_gather_object) into the global id table `ids`, and records the bank's `generation`; call it again after adds and after
-    a removal (each rank removes locally, PassageBank.remove, then all refresh).  `search` is the local search plus the
+    (all_gather_object) into the global id table `ids`, and records the bank's `generation` (raised by PassageBank.remove and by
+    PassageBank.clear); call it again after adds, after a removal (each rank removes locally, then all refresh) and after a clear:
+    until then a search raises, also when the bank has been refilled to its old count.  `search` is the local search plus the
     exchange.  The queries are the caller's to replicate: every rank passes the same `query_li`."""
 
     def __init__(self, bank, group=None):

@@ -983,9 +983,34 @@ int rr_bank_search_plaid_ivf(rr_handle h, rr_bank_handle b, const float* query_l
  * reads no row of the bank and issues no matrix instruction; the bit is a scalar load.  Then rr_bank_search's selection passes over
  * the dense row, unchanged, and one pass of the pruned search's list kernel over their k survivors, which drops the absent, writes
  * the tail and counts.  The block grows by 4 n_queries k bytes over rr_bank_search's.
- * LIMIT: the selection still walks the dense row of n_passages scores per query, however few bits are set, and there is no
- * list-driven exact form: for a filter of a few thousand passages rr_bank_li_scores over the explicit pair list and a top-k of its
- * maxsim_out remains the cheaper route.
+ * LIMIT: the selection walks the dense row of n_passages scores per query, however few bits are set; the list-driven form below
+ * does not.  Measured on one MI355X (tools/bench_bank_search_filter.py --sparse, profiles/bank_search_sparse_bench.json.log; a
+ * compressed bank of 12 M rows as 100 000 and as 800 000 passages, 1 and 16 queries, one filter row and a row per query): the
+ * list-driven form is the faster one at every measured density below 1.0 (sparse / dense 0.87 .. 0.77 at 50 % allowed, 0.64 ..
+ * 0.44 at 10 %, 0.91 .. 0.33 at 1 %, 0.95 .. 0.28 at 0.1 %, the larger gains at 16 queries and at 800 000 passages); with every
+ * bit set it equals this entry at 16 queries and costs 3 % (100 000 passages) to 10 % (800 000) more at one query.  Against
+ * rr_bank_li_scores over the explicit pair list and a top-k of its maxsim_out, the route this paragraph used to recommend, the
+ * list-driven form is 1.6 to 60 times faster, except at ONE query over 100 000 passages with about a thousand allowed passages or
+ * fewer, where the pair list is still ahead (1.3 x at 1 %, 2.9 x at 0.1 %).
+ *
+ * rr_bank_search_filtered_sparse: the list-driven form of rr_bank_search_filtered.  DEFINITION: for every argument set
+ * rr_bank_search_filtered accepts, indices_out, scores_out and counts_out are that entry's bytes; its checks, check order, refusals
+ * (k > 1024: RR_ERR_UNSUPPORTED; a NULL counts_out: RR_ERR_BAD_ARG; ...), graph-capture refusal and "a refused call writes nothing"
+ * are that entry's, its own name in rr_last_error aside.  What differs is the work: every stage runs over the passages the filter
+ * allows, not over the range.  (1) One workgroup per filter row writes the set bits of the range as an ascending list of
+ * range-relative indices cand[row][0 .. cnt[row]) and cnt[row] (csrc/bank_ivf.hip: the compaction kernel of the inverted-file search
+ * over the filter's own words, the last word cut to the range; no atomics).  (2) The scoring kernel under one more picker
+ * (csrc/bank_search.hip, pick_places): a workgroup owns search_chunk consecutive PLACES of its query's candidate row (one shared
+ * filter row: every query's) and writes their scores to those places of a compact row of pitch n_passages; a workgroup behind the
+ * count returns before it stages its query block.  fp16 and compressed banks.  (3) topk_select_counted_kernel: rr_bank_search's
+ * selection over the first cnt places of the compact rows, the place in the key (places ascend with the bank index: ties break as
+ * before); the host launches the passes n_passages would need, each pass derives its list's length from cnt on the device, a slice
+ * behind it ends at once, and the last pass maps a place to first_passage + cand[row][place], drops the -inf scorers, writes
+ * -1 / -inf behind the count and counts_out.  Nothing is read back: the call is as asynchronous as the dense form.
+ * SCRATCH (the handle's grow-only search block): the dense form's bytes, 4 n_queries n_passages + 2 * 4 n_queries ceil(n_passages /
+ * 4096) k (none at n_passages <= 4096) + 4 n_queries k, plus 4 filter_rows n_passages for cand and 4 filter_rows for cnt, each
+ * term rounded up to 16 bytes.  The profile books the three launches in the `tail` class, FLOPs and bytes for the range's mean
+ * passage length times the pitch: an upper bound, as the pruned search books its survivors.
  *
  * rr_bank_search_plaid_filtered: rr_bank_search_plaid with CANDIDATES read as: the passage's bit is set AND at least one of its
  * unmasked rows has a code in the cell set.  Stages 0 to 3 and OUTPUT are otherwise word for word rr_bank_search_plaid's.
@@ -1011,11 +1036,14 @@ int rr_bank_search_plaid_ivf(rr_handle h, rr_bank_handle b, const float* query_l
  * the listed bits with 32-bit vector atomicAnd / atomicOr; an AND or an OR has one result, so the bytes do not depend on
  * scheduling).  Errors: rr_bank_last_error.  In host code: rr_util_bank_filter_bits (rerank_mi355_diag.h).  A filter describes
  * the bank it was filled for: passages added later have clear bits under exclude == 0 and under exclude != 0 alike.
- * (Python: RerankEngine.bank_search_filtered / bank_search_plaid_filtered / bank_search_plaid_ivf_filtered, PassageBank.filter,
+ * (Python: RerankEngine.bank_search_filtered / bank_search_filtered_sparse / bank_search_plaid_filtered / bank_search_plaid_ivf_filtered, PassageBank.filter,
  * PassageBank.search(filter=), InteractionRerankModel.retrieve / retrieve_and_rerank(allowed=, excluded=, filter=).) */
 int rr_bank_search_filtered(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage,
                             int32_t n_passages, int k, const uint32_t* filter_bits, int filter_rows, int64_t filter_ld,
                             int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream);
+int rr_bank_search_filtered_sparse(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage,
+                                   int32_t n_passages, int k, const uint32_t* filter_bits, int filter_rows, int64_t filter_ld,
+                                   int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream);
 int rr_bank_search_plaid_filtered(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse,
                                   int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k,
                                   const uint32_t* filter_bits, int filter_rows, int64_t filter_ld, int32_t* indices_out,

@@ -326,12 +326,25 @@ int rr_op_bank_li_scores(const float* query_li, int Lq, int D, const void* pairs
  * rr_op_topk_select: the selection alone: scores float32 [n_lists, n] -> the first k of every list in the order of
  * torch.sort(descending=True, stable=True) (NaN first, ties by ascending index): indices_out int32 [n_lists, k], scores_out
  * float32 [n_lists, k] or NULL; n_lists <= 65535.
+ * rr_op_filter_compact: the first stage of rr_bank_search_filtered_sparse alone: filter_bits as that entry takes them (DEVICE uint32
+ * [filter_rows, filter_ld], bit = absolute bank index) -> cand_out int32 [filter_rows, n_passages]: the set bits of [first_passage,
+ * first_passage + n_passages) of a row as ascending range-relative indices, counts_out int32 [filter_rows] their numbers; entries
+ * behind a count are not written.  filter_rows 1 .. 65535, filter_ld >= ceil((first_passage + n_passages) / 32).
+ * rr_op_topk_select_counted: its last stage alone: list l is the first counts[r] entries of scores float32 [n_lists, n] (r = 0 if
+ * rows == 1, else l; rows is 1 or n_lists; counts int32 [rows], clamped into [0, n]); whatever lies behind a count is never read.
+ * Of the entries that are not -inf the first k in rr_op_topk_select's order: indices_out int32 [n_lists, k] = first_passage +
+ * cand[r][place] (cand int32 [rows, n]; NULL: first_passage + place), scores_out float32 [n_lists, k] or NULL, -1 / -inf behind
+ * them, counts_out int32 [n_lists] their numbers.  1 <= k <= min(n, 1024).
  * rr_set_tuning("search_chunk") (16; 4 .. 128): the passages one workgroup of the scoring kernel walks. */
 int rr_op_bank_search(const float* query_li, int n_queries, int Lq, int D, const void* table, int32_t first_passage,
                       int32_t n_passages, int k, const uint16_t* rows_f16, const uint8_t* mask_bytes, int nbits, const int32_t* codes,
                       const uint8_t* residuals, const uint16_t* centroids_f16, const float* bucket_weights, int32_t n_centroids,
                       int32_t* indices_out, float* scores_out, void* hip_stream);
 int rr_op_topk_select(const float* scores, int n_lists, int n, int k, int32_t* indices_out, float* scores_out, void* hip_stream);
+int rr_op_filter_compact(const uint32_t* filter_bits, int filter_rows, int64_t filter_ld, int32_t first_passage, int32_t n_passages,
+                         int32_t* cand_out, int32_t* counts_out, void* hip_stream);
+int rr_op_topk_select_counted(const float* scores, int n_lists, int n, const int32_t* counts, const int32_t* cand, int rows, int k,
+                              int32_t first_passage, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream);
 
 /* rr_bank_search_plaid (rerank_mi355.h) from the inside.
  * rr_op_bank_search_plaid: the stages over raw DEVICE pointers, as rr_op_bank_search takes a compressed bank's (table, mask, codes,
@@ -350,6 +363,8 @@ int rr_op_topk_select(const float* scores, int n_lists, int n, int k, int32_t* i
  * rr_set_tuning("plaid_stop_after") (7; 0 .. 7): the last stage a call runs (timing by difference; below 7 nothing is output).
  * rr_set_tuning("plaid_ivf_stop_after") (8; 0 .. 8): the same for rr_bank_search_plaid_ivf: 0 - 2 as above, 3 candidates, 4 the
  * listed A1 / A2, 5 the selection of ndocs, 6 the selection of ndocs / 4, 7 the exact scores, 8 the output.
+ * rr_set_tuning("sparse_stop_after") (2; 0 .. 2): the last stage an rr_bank_search_filtered_sparse call runs: 0 the compaction of the
+ * filter rows, 1 the scores of the places, 2 the counted selection (timing by difference; below 2 nothing is output).
  * rr_util_plaid_ivf: THE INVERTED FILE (rerank_mi355.h) in pure HOST code, usable without a GPU: the written-down definition
  * rr_bank_build_ivf is held to.  codes int32 / mask uint8 (NULL: all ones) over the rows of the n_passages passages back to back,
  * lengths int32 [n_passages] (each >= 1); codes are clamped into [0, n_centroids).  offsets_out int64 [n_centroids + 1] is always

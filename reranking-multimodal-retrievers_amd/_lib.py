@@ -128,6 +128,10 @@ _SIGS = {
     "rr_bank_search_plaid_ivf": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int, C.c_float, C.c_int, C.c_int,
                                            _P, _P, _P, _P]),
     "rr_bank_search_filtered": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int, _P, C.c_int, C.c_int64, _P, _P, _P, _P]),
+    "rr_bank_search_filtered_sparse": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int, _P, C.c_int, C.c_int64, _P, _P, _P,
+                                                 _P]),
+    "rr_op_filter_compact": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
+    "rr_op_topk_select_counted": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int32, _P, _P, _P, _P]),
     "rr_bank_search_plaid_filtered": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int, C.c_float, C.c_int,
                                                 C.c_int, _P, C.c_int, C.c_int64, _P, _P, _P, _P]),
     "rr_bank_search_plaid_ivf_filtered": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int, C.c_float, C.c_int,

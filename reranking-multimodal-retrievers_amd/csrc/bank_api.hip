@@ -702,12 +702,24 @@ static int bank_filter_check(rr_model* m, const char* what, const FilterArg& f, 
   return RR_OK;
 }
 
+// rr_set_tuning("sparse_stop_after"): the last stage an rr_bank_search_filtered_sparse call runs (0 the compaction, 1 the scores, 2
+// all); below 2 the outputs are not written: tools/bench_bank_search_filter.py --sparse --profile times the stages by difference.
+// A diagnostic switch, set between calls (as the pruned search's).
+static int g_sparse_stop_after = 2;
+int set_sparse_stop_after(int value) {
+  if (value < 0 || value > 2) return RR_ERR_BAD_ARG;
+  g_sparse_stop_after = value;
+  return RR_OK;
+}
+
 // rr_bank_search (include/rerank_mi355.h): one scoring launch over the range and the selection passes.  filter (or null):
-// rr_bank_search_filtered, the scores under the filter, the same selection, then one list pass that drops the absent and counts
+// rr_bank_search_filtered, the scores under the filter, the same selection, then one list pass that drops the absent and counts.
+// sparse (with a filter): rr_bank_search_filtered_sparse, the same checks in the same order, then the filter's rows compacted into
+// candidate lists, the scores of their places and the counted selection: every stage over the allowed passages alone
 static int bank_search_call(rr_handle h, rr_bank* b, const float* query_li, int n_queries, int Lq, int32_t first_passage,
-                            int32_t n_passages, int k, const FilterArg* filter, int32_t* indices_out, float* scores_out,
+                            int32_t n_passages, int k, const FilterArg* filter, bool sparse, int32_t* indices_out, float* scores_out,
                             int32_t* counts_out, void* hip_stream) {
-  const char* what = filter ? "rr_bank_search_filtered" : "rr_bank_search";
+  const char* what = sparse ? "rr_bank_search_filtered_sparse" : filter ? "rr_bank_search_filtered" : "rr_bank_search";
   if (!h) return RR_ERR_BAD_ARG;
   rr_model* m = h;
   hipStream_t st = (hipStream_t)hip_stream;
@@ -723,7 +735,11 @@ static int bank_search_call(rr_handle h, rr_bank* b, const float* query_li, int 
   const size_t sc_bytes = (((size_t)n_queries * n * sizeof(float)) + 15) & ~(size_t)15;
   const size_t tmp_bytes = ((rr_topk_select_scratch(n_queries, n, k) * sizeof(int32_t)) + 15) & ~(size_t)15;
   const size_t top_bytes = filter ? (((size_t)n_queries * k * sizeof(int32_t)) + 15) & ~(size_t)15 : 0;      // the selection's k, before the list pass
-  RR_TRY(ensure_block(m, m->search_blk, m->search_blk_cap, sc_bytes + 2 * tmp_bytes + top_bytes, st, "the bank search's block"));
+  // (the sparse form: the dense form's bytes, so that calls of both forms grow the block once, then cand [filter_rows][n] and cnt)
+  const size_t cand_bytes = sparse ? (((size_t)filter->rows * n * sizeof(int32_t)) + 15) & ~(size_t)15 : 0;
+  const size_t cnt_bytes = sparse ? (((size_t)filter->rows * sizeof(int32_t)) + 15) & ~(size_t)15 : 0;
+  RR_TRY(ensure_block(m, m->search_blk, m->search_blk_cap, sc_bytes + 2 * tmp_bytes + top_bytes + cand_bytes + cnt_bytes, st,
+                      "the bank search's block"));
   m->plaid_last_ok = false;                         // the block no longer holds a pruned search's intermediates
   float* sc = (float*)m->search_blk;
   int32_t* tmp_a = tmp_bytes ? (int32_t*)(m->search_blk + sc_bytes) : nullptr;
@@ -733,6 +749,22 @@ static int bank_search_call(rr_handle h, rr_bank* b, const float* query_li, int 
   // bytes: the range's rows and mask bytes once (the queries of a chunk run side by side), the table, the query block per
   // workgroup of 16 passages, one float per (query, passage)
   const double bytes = rows * (rr_bank_row_bytes(bank, D) + 1.0) + 16.0 * n + (double)n_queries * (n / 16.0 + 1.0) * 4.0 * Lq * D + 4.0 * n_queries * (double)n;
+  if (sparse) {
+    // how many passages a row allows is known on the device only: FLOPs and bytes are booked for the range's mean passage length
+    // times the pitch, an upper bound (as the pruned search books its survivors)
+    int32_t* cand = (int32_t*)(m->search_blk + sc_bytes + 2 * tmp_bytes + top_bytes);
+    int32_t* cnt = (int32_t*)(m->search_blk + sc_bytes + 2 * tmp_bytes + top_bytes + cand_bytes);
+    const rr_passage_filter f{filter->bits, filter->rows, (long long)filter->ld, first_passage};
+    RR_RUN(m, st, RR_K_TAIL, 0.0, (double)filter->rows * (n / 8.0 + 4.0 * n + 4.0), rr_launch_filter_compact(f, n, cand, cnt, st));
+    if (g_sparse_stop_after < 1) return RR_OK;
+    RR_RUN(m, st, RR_K_TAIL, 2.0 * n_queries * rows * Lq * D, bytes + 4.0 * n_queries * (double)n,
+           rr_launch_bank_search_scores_places(b->table + first_passage, n, n_queries, Lq, D, query_li, bank, cand, cnt, filter->rows, n, sc, st));
+    if (g_sparse_stop_after < 2) return RR_OK;
+    RR_RUN(m, st, RR_K_TAIL, 0.0, 12.0 * n_queries * (double)n + 16.0 * n_queries * (double)k,
+           rr_launch_topk_select_counted(sc, n_queries, n, cnt, cand, (long long)n, filter->rows, k, first_passage, tmp_a, tmp_b, indices_out,
+                                         scores_out, counts_out, st));
+    return RR_OK;
+  }
   RR_RUN(m, st, RR_K_TAIL, 2.0 * n_queries * rows * Lq * D, bytes,
          rr_launch_bank_search_scores(b->table + first_passage, n, n_queries, Lq, D, query_li, bank,
                                       filter ? rr_passage_filter{filter->bits, filter->rows, (long long)filter->ld, first_passage} : rr_passage_filter{},
@@ -769,6 +801,42 @@ int rr_op_topk_select(const float* scores, int n_lists, int n, int k, int32_t* i
     if (n_lists <= 0 || n_lists > 65535 || n <= 0 || k < 1 || k > n) return RR_ERR_BAD_SHAPE;
     if (k > 1024) return RR_ERR_UNSUPPORTED;
     return op_select_with_scratch(scores, n_lists, n, k, 0, indices_out, scores_out, (hipStream_t)hip_stream);
+  });
+}
+
+// rr_op_filter_compact and rr_op_topk_select_counted (include/rerank_mi355_diag.h): the first and the last stage of
+// rr_bank_search_filtered_sparse over loose device pointers
+int rr_op_filter_compact(const uint32_t* filter_bits, int filter_rows, int64_t filter_ld, int32_t first_passage, int32_t n_passages,
+                         int32_t* cand_out, int32_t* counts_out, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int {
+    if (!filter_bits || !cand_out || !counts_out) return RR_ERR_BAD_ARG;
+    if ((((uintptr_t)filter_bits) | ((uintptr_t)cand_out) | ((uintptr_t)counts_out)) & 3) return RR_ERR_BAD_ARG;
+    if (filter_rows < 1 || filter_rows > 65535 || first_passage < 0 || n_passages < 1 ||
+        filter_ld < ((long long)first_passage + n_passages + 31) / 32)
+      return RR_ERR_BAD_SHAPE;
+    const rr_passage_filter f{filter_bits, filter_rows, (long long)filter_ld, first_passage};
+    return rr_launch_filter_compact(f, n_passages, cand_out, counts_out, (hipStream_t)hip_stream) == hipSuccess ? RR_OK : RR_ERR_HIP;
+  });
+}
+
+int rr_op_topk_select_counted(const float* scores, int n_lists, int n, const int32_t* counts, const int32_t* cand, int rows, int k,
+                              int32_t first_passage, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int {
+    if (!scores || !counts || !indices_out || !counts_out) return RR_ERR_BAD_ARG;
+    if (n_lists <= 0 || n_lists > 65535 || n <= 0 || k < 1 || k > n || (rows != 1 && rows != n_lists)) return RR_ERR_BAD_SHAPE;
+    if (k > 1024) return RR_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)hip_stream;
+    const size_t entries = rr_topk_select_scratch(n_lists, n, k);
+    int32_t* tmp = nullptr;
+    if (entries && hipMalloc((void**)&tmp, 2 * entries * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); return RR_ERR_OOM; }
+    hipError_t e = rr_launch_topk_select_counted(scores, n_lists, n, counts, cand, (long long)n, rows, k, first_passage, tmp,
+                                                 tmp ? tmp + entries : nullptr, indices_out, scores_out, counts_out, st);
+    if (tmp) {
+      const hipError_t e2 = hipStreamSynchronize(st);
+      if (e == hipSuccess) e = e2;
+      (void)hipFree(tmp);
+    }
+    return e == hipSuccess ? RR_OK : RR_ERR_HIP;
   });
 }
 
@@ -1406,11 +1474,15 @@ int rr_bank_li_scores(rr_handle h, rr_bank_handle b, const float* query_li, int 
   return guarded(h, [&]() -> int { return bank_li_scores_call(h, b, query_li, n_queries, Lq, pair_passage, pair_query, n_pairs, padded_context_len, scores_out, maxsim_out, hip_stream); });
 }
 int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage, int32_t n_passages, int k, int32_t* indices_out, float* scores_out, void* hip_stream) {
-  return guarded(h, [&]() -> int { return bank_search_call(h, b, query_li, n_queries, Lq, first_passage, n_passages, k, nullptr, indices_out, scores_out, nullptr, hip_stream); });
+  return guarded(h, [&]() -> int { return bank_search_call(h, b, query_li, n_queries, Lq, first_passage, n_passages, k, nullptr, false, indices_out, scores_out, nullptr, hip_stream); });
 }
 int rr_bank_search_filtered(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage, int32_t n_passages, int k, const uint32_t* filter_bits, int filter_rows, int64_t filter_ld, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream) {
   const FilterArg f{filter_bits, filter_rows, filter_ld};
-  return guarded(h, [&]() -> int { return bank_search_call(h, b, query_li, n_queries, Lq, first_passage, n_passages, k, &f, indices_out, scores_out, counts_out, hip_stream); });
+  return guarded(h, [&]() -> int { return bank_search_call(h, b, query_li, n_queries, Lq, first_passage, n_passages, k, &f, false, indices_out, scores_out, counts_out, hip_stream); });
+}
+int rr_bank_search_filtered_sparse(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage, int32_t n_passages, int k, const uint32_t* filter_bits, int filter_rows, int64_t filter_ld, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream) {
+  const FilterArg f{filter_bits, filter_rows, filter_ld};
+  return guarded(h, [&]() -> int { return bank_search_call(h, b, query_li, n_queries, Lq, first_passage, n_passages, k, &f, true, indices_out, scores_out, counts_out, hip_stream); });
 }
 int rr_bank_search_plaid_filtered(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse, int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k, const uint32_t* filter_bits, int filter_rows, int64_t filter_ld, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream) {
   const FilterArg f{filter_bits, filter_rows, filter_ld};

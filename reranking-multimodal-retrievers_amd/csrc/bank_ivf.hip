@@ -42,6 +42,9 @@
 // or an OR has one result.  rr_filter_bits_host restates it (rr_util_bank_filter_bits).
 // ivf_compact_kernel: ONE workgroup of 1024 per bitmap walks it 1024 words a time: a popcount per word, an inclusive scan over the
 // workgroup (wave shuffles, the sixteen wave totals through LDS), and every thread writes the bits of its word from its place on.
+// WHERE a word comes from is a type (WORDS): words_bitmap, the bitmap ANDed with a filter, as above; words_filter, the filter's own
+// bits of the range and no bitmap (rr_launch_filter_compact: the candidate rows of rr_bank_search_filtered_sparse), the last word cut
+// to the range.  The type holds no data, so the bitmap form keeps its arguments and its instructions.
 // rr_ivf_host restates the definition in host code (rr_util_plaid_ivf).
 #include <algorithm>
 #include <cmath>
@@ -280,9 +283,15 @@ __global__ __launch_bounds__(256) void ivf_candidates_kernel(const int32_t* __re
   }
 }
 
+// the word source of ivf_compact_kernel: a bitmap row (ANDed with the filter, if one is given), or the filter's bits of the range alone
+struct words_bitmap { static constexpr bool FILTER_ALONE = false; };
+struct words_filter { static constexpr bool FILTER_ALONE = true; };
+
 // Workgroup q: the set bits of bm[q][0 .. Wn) in ascending order, bit + add, to out[q * out_ld ...] (at most cap of them), their
 // number to cnt_out[q]; fill_a / fill_b (or null) [nq][cap] get -inf behind the count.  filter.bits given: a word is ANDed with the
-// filter's bits of its passages (n: the passages of the range) as it is read.
+// filter's bits of its passages (n: the passages of the range) as it is read.  words_filter: bm is not read, word w is the filter's
+// bits of the range-relative passages 32 w .. 32 w + 31 below n, and workgroup q is filter row q.
+template <class WORDS>
 __global__ __launch_bounds__(IVF_COMPACT_THREADS) void ivf_compact_kernel(const uint32_t* __restrict__ bm, int Wn, int32_t* __restrict__ out,
                                                                           long long out_ld, int cap, int32_t* __restrict__ cnt_out, int add,
                                                                           float* __restrict__ fill_a, float* __restrict__ fill_b,
@@ -295,8 +304,14 @@ __global__ __launch_bounds__(IVF_COMPACT_THREADS) void ivf_compact_kernel(const 
   int round = 0;
   for (int w0 = 0; w0 < Wn; w0 += IVF_COMPACT_THREADS, round ^= 1) {
     const int w = w0 + tid;
-    uint32_t word = w < Wn ? row[w] : 0u;
-    if (filter.bits && word) word &= filter.range_word(q, w, n);
+    uint32_t word;
+    if constexpr (WORDS::FILTER_ALONE) {
+      word = w < Wn ? filter.range_word(q, w, n) : 0u;
+      if (w == Wn - 1 && (n & 31)) word &= (1u << (n & 31)) - 1u;      // the last word ends with the range
+    } else {
+      word = w < Wn ? row[w] : 0u;
+      if (filter.bits && word) word &= filter.range_word(q, w, n);
+    }
     const int pc = __popc(word);
     int incl = pc;
 #pragma unroll
@@ -472,7 +487,7 @@ hipError_t rr_ivf_build(const rr_bank_view& bank, const int64_t* first, const in
         const unsigned blocks = (unsigned)std::min<int64_t>((cnt + 255) / 256, 4096);
         // bit i: passage P0 + i; the compaction adds P0 back
         hipLaunchKernelGGL(ivf_list_bits_kernel, dim3(blocks), dim3(256), 0, st, f.pids + start, (long long)cnt, P0, N, bm);
-        hipLaunchKernelGGL(ivf_compact_kernel, dim3(1), dim3(IVF_COMPACT_THREADS), 0, st, bm, (int)Wn, f.pids + start, 0LL, (int)cnt, cnt_dev, P0,
+        hipLaunchKernelGGL(ivf_compact_kernel<words_bitmap>, dim3(1), dim3(IVF_COMPACT_THREADS), 0, st, bm, (int)Wn, f.pids + start, 0LL, (int)cnt, cnt_dev, P0,
                            nullptr, nullptr, rr_passage_filter{}, N);
         ok(hipGetLastError());
       }
@@ -507,8 +522,19 @@ hipError_t rr_launch_ivf_candidates(const rr_ivf& f, int C, const int32_t* cells
   hipLaunchKernelGGL(ivf_candidates_kernel, dim3((unsigned)E, (unsigned)nq), dim3(256), 0, st, cells, E, C, f.offsets, f.pids, first, n, bm, Wn);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(ivf_compact_kernel, dim3((unsigned)nq), dim3(IVF_COMPACT_THREADS), 0, st, bm, Wn, cand, (long long)cap, cap, ccnt, 0, a1, a2,
+  hipLaunchKernelGGL(ivf_compact_kernel<words_bitmap>, dim3((unsigned)nq), dim3(IVF_COMPACT_THREADS), 0, st, bm, Wn, cand, (long long)cap, cap, ccnt, 0, a1, a2,
                      filter, n);
+  return hipGetLastError();
+}
+
+// the candidate rows of rr_bank_search_filtered_sparse: cand [filter.rows][n] gets the range-relative passages of [filter.first,
+// filter.first + n) whose bit is set in filter row r, ascending, cnt [filter.rows] their numbers.  One workgroup per row, no atomics.
+hipError_t rr_launch_filter_compact(const rr_passage_filter& filter, int n, int32_t* cand, int32_t* cnt, hipStream_t st) {
+  if (!filter.bits || !cand || !cnt || filter.rows < 1 || filter.rows > 65535 || filter.first < 0 || n < 1 ||
+      filter.ld < ((long long)filter.first + n + 31) / 32)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ivf_compact_kernel<words_filter>, dim3((unsigned)filter.rows), dim3(IVF_COMPACT_THREADS), 0, st, nullptr, (n + 31) / 32, cand,
+                     (long long)n, n, cnt, 0, nullptr, nullptr, filter, n);
   return hipGetLastError();
 }
 

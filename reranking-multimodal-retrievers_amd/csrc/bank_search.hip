@@ -35,14 +35,19 @@
 //     filter (rr_bank_search_filtered): a workgroup whose chunk has no set bit writes its -inf entries and ends before it stages
 //     the query block, and a wave whose passage has a clear bit writes -inf, reads no row and issues no matrix instruction.  The
 //     bit is read wave-uniformly (a scalar load of the word).  The selection (b) runs over the dense row as it is, then one
-//     plaid_list_select_kernel pass over its k survivors drops the -inf and writes the tail and the count.
+//     plaid_list_select_kernel pass over its k survivors drops the -inf and writes the tail and the count.  pick_places is the
+//     list-driven form of that search (rr_bank_search_filtered_sparse): pick_range's chunk over the PLACES of a candidate row
+//     (the filter's set bits, compacted by ivf_compact_kernel, bank_ivf.hip) with a count; a workgroup behind the count ends before
+//     it stages the query block, and the scores go to a compact row that topk_select_counted_kernel selects from: (b) over the
+//     first `count` places, each pass's length derived from the count on the device, the list pass folded into its last pass.
 // (b) topk_select_kernel: each workgroup sorts a slice of at most 4096 (score, index) in LDS by ONE total order and keeps its
 //     first k (k <= 1024, so a pass is a strict reduction); passes repeat over the survivors until one slice is left.  The order
 //     and its 64-bit key are rank_order.h's, shared with the pruned search: keys are distinct, so the bitonic network (written out
 //     here and in plaid_list_select_kernel, see rank_order.h) has one possible result.  Survivors travel as indices; a pass reads
 //     their scores again from the score row.
 // LAUNCHERS: rr_launch_bank_search_scores and rr_launch_bank_search_scores_listed take an rr_bank_view (rr_common.h), fp16 or
-// compressed (the listed form: compressed only; pick_list or, given a candidate list, pick_via), and rr_launch_topk_select.  The
+// compressed (the listed form: compressed only; pick_list or, given a candidate list, pick_via), rr_launch_bank_search_scores_places
+// (pick_places; fp16 or compressed), rr_launch_topk_select and rr_launch_topk_select_counted.  The
 // operand sources, the view-to-source dispatch (li_with_bank_source), the once-per-device LDS attribute (li_lds_attr) and the
 // width of the column block (li_pick_jt, here with a fixed 72 KB) live in li_sources.h, shared with li_scores.hip; the tile step
 // is written out in this kernel body and in li_scores_kernel's (see li_scores.hip's header).
@@ -128,6 +133,27 @@ struct pick_via {
     return min(max(__builtin_amdgcn_readfirstlane(cand[(size_t)q * cap + place(q, p0, i)]), 0), n - 1);
   }
   __device__ __forceinline__ size_t slot(int q, int, int p0, int i, int) const { return (size_t)q * cap + place(q, p0, i); }
+};
+// pick_places: `chunk` consecutive PLACES of the query's candidate row cand[r][0 .. pitch), r = 0 for one shared row (rows == 1), else
+// the query; the first cnt[r] places hold passages (clamped into [0, n)), and a score goes to its place of the compact row
+// out[q][0 .. pitch).  pick_range's chunk over a list: the query block is staged once per chunk, not once per four entries.  A
+// workgroup behind the count has nothing to do.
+struct pick_places {
+  int chunk;
+  const int32_t* cand;
+  const int32_t* cnt;
+  int rows;
+  int pitch;
+  static constexpr int PSUM = BS_CHUNK_MAX;
+  static constexpr bool LISTED = true;
+  static constexpr bool FILTERED = false;
+  __device__ __forceinline__ int row(int q) const { return rows == 1 ? 0 : q; }
+  __device__ __forceinline__ int first(int c) const { return c * chunk; }
+  __device__ __forceinline__ int count(int q, int p0, int) const { return min(chunk, min(cnt[row(q)], pitch) - p0); }
+  __device__ __forceinline__ int at(int q, int p0, int i, int n) const {
+    return min(max(__builtin_amdgcn_readfirstlane(cand[(size_t)row(q) * pitch + p0 + i]), 0), n - 1);
+  }
+  __device__ __forceinline__ size_t slot(int q, int, int p0, int i, int) const { return (size_t)q * pitch + p0 + i; }
 };
 
 template <int JT, class SRC, class PICK>
@@ -313,6 +339,85 @@ __global__ __launch_bounds__(SEL_THREADS) void topk_select_kernel(const float* _
   }
 }
 
+// the entries a list of cnt entries still has at pass `pass` of the selection: the host loop of rr_launch_topk_select, on the device
+__device__ __forceinline__ int counted_entries(int cnt, int k, int pass) {
+  int n_in = cnt;
+  for (int p = 0; p < pass; ++p) {
+    const int slices = (n_in + SEL_SLICE - 1) / SEL_SLICE;
+    n_in = slices ? (slices - 1) * k + min(k, n_in - (slices - 1) * SEL_SLICE) : 0;      // (one slice: its min(k, n_in) survivors again)
+  }
+  return n_in;
+}
+
+// topk_select_kernel over COMPACT rows: list `blockIdx.y` is the first cnt_in[r] places of scores[list][0 .. pitch), r = 0 for one
+// shared row (rows == 1), else the list; whatever lies behind the count is never read.  The key holds the place, and places ascend
+// with the bank index, so the order is topk_select_kernel's.  The grid is the one the whole pitch would need; what a list holds at
+// pass `pass` follows from its count (counted_entries), and a slice behind that ends at once.  The last pass (one slice) drops the
+// -inf scorers, maps a place to add + cand[r][place] (cand null: add + place) and writes -1 / -inf behind the survivors up to k and
+// their number to counts_out: what plaid_list_select_kernel does for the dense form.
+__global__ __launch_bounds__(SEL_THREADS) void topk_select_counted_kernel(const float* __restrict__ scores, int pitch, const int32_t* __restrict__ cnt_in,
+                                                                          const int32_t* __restrict__ cand, long long cand_ld, int rows,
+                                                                          const int32_t* __restrict__ idx_in, long long in_ld, int pass, int k,
+                                                                          int32_t* __restrict__ idx_out, long long out_ld, int add,
+                                                                          float* __restrict__ scores_out, int32_t* __restrict__ counts_out) {
+  __shared__ unsigned long long key[SEL_SLICE];
+  __shared__ int valid;
+  const int list = blockIdx.y, r = rows == 1 ? 0 : list, base = blockIdx.x * SEL_SLICE, tid = threadIdx.x;
+  const bool final_pass = gridDim.x == 1;
+  const int n_in = counted_entries(min(max(cnt_in[r], 0), pitch), k, pass);
+  const int cnt = max(min(SEL_SLICE, n_in - base), 0);
+  if (!final_pass && cnt == 0) return;                        // the whole workgroup: the slice lies behind the list
+  const float* row = scores + (size_t)list * pitch;
+  int n2 = 1;
+  while (n2 < cnt) n2 <<= 1;
+  if (tid == 0) valid = 0;
+  for (int i = tid; i < n2; i += SEL_THREADS) {
+    unsigned long long kv = 0ull;                             // padding, and in the last pass the absent, rank behind every entry
+    if (i < cnt) {
+      const int idx = idx_in ? idx_in[(size_t)list * in_ld + base + i] : base + i;
+      const float s = row[idx];
+      if (!final_pass || s != -INFINITY) kv = rank_key(s, (uint32_t)idx);
+    }
+    key[i] = kv;
+  }
+  __syncthreads();
+  for (int kk = 2; kk <= n2; kk <<= 1) {
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < n2; i += SEL_THREADS) {
+        const int l = i ^ j;
+        if (l > i) {
+          const bool up = (i & kk) == 0;                      // a run in rank order (larger key first)
+          const unsigned long long a = key[i], b = key[l];
+          if (up ? a < b : a > b) { key[i] = b; key[l] = a; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (!final_pass) {
+    const int keep = min(k, cnt);
+    for (int i = tid; i < keep; i += SEL_THREADS)
+      idx_out[(size_t)list * out_ld + (size_t)blockIdx.x * k + i] = (int)rank_key_index(key[i]);
+    return;
+  }
+  for (int i = tid; i < n2; i += SEL_THREADS)
+    if (key[i] != 0ull && (i == n2 - 1 || key[i + 1] == 0ull)) valid = i + 1;      // one thread at most
+  __syncthreads();
+  const int kept = min(k, valid);
+  for (int i = tid; i < k; i += SEL_THREADS) {
+    int32_t o = -1;
+    float s = -INFINITY;
+    if (i < kept) {
+      const int idx = (int)rank_key_index(key[i]);
+      o = (cand ? cand[(size_t)r * cand_ld + idx] : idx) + add;
+      s = row[idx];
+    }
+    idx_out[(size_t)list * out_ld + i] = o;
+    if (scores_out) scores_out[(size_t)list * out_ld + i] = s;
+  }
+  if (tid == 0) counts_out[list] = kept;
+}
+
 }  // namespace
 
 int rr_set_search_chunk(int passages) {
@@ -356,6 +461,20 @@ hipError_t rr_launch_bank_search_scores_listed(const rr_bank_slot* table, int n,
   return !cand ? with(pick_list{list, list_ld, cnt}) : with(pick_via{list, list_ld, cnt, cand, cap});
 }
 
+// the same MaxSim for the passages cand[r][0 .. cnt[r]) (range-relative entries of table[0 .. n); r = 0 if rows == 1, else the query;
+// cand [rows][pitch], cnt[r] <= pitch) of every query, written to the passage's PLACE of the compact out [nq][pitch]; the places
+// behind a count are left as they are.  pick_places: chunks of search_chunk places, fp16 and compressed banks alike.
+hipError_t rr_launch_bank_search_scores_places(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
+                                               const rr_bank_view& bank, const int32_t* cand, const int32_t* cnt, int rows, int pitch,
+                                               float* out, hipStream_t st) {
+  if (!scores_args_ok(table, n, nq, Lq, query_li, out) || !cand || !cnt || (rows != 1 && rows != nq) || pitch <= 0) return hipErrorInvalidValue;
+  const int chunk = g_search_chunk.load(std::memory_order_relaxed);
+  return li_with_bank_source(nullptr, nullptr, bank, D, [&](const auto& src, size_t tile_bytes) {
+    return search_launch(query_li, src, table, n, nq, ((long long)pitch + chunk - 1) / chunk, pick_places{chunk, cand, cnt, rows, pitch}, Lq, D,
+                         tile_bytes, out, st);
+  });
+}
+
 // int32 entries of EACH of the two survivor buffers rr_launch_topk_select needs (0: one slice, none)
 size_t rr_topk_select_scratch(int n_lists, int n, int k) {
   if (n <= SEL_SLICE) return 0;
@@ -382,6 +501,37 @@ hipError_t rr_launch_topk_select(const float* scores, int n_lists, int n, int k,
     if (e != hipSuccess || final_pass) return e;
     // every slice but the last is full and leaves k; the last leaves what it holds, at most k: the survivors are contiguous
     n_in = (slices - 1) * k + std::min(k, n_in - (slices - 1) * SEL_SLICE);
+    in = o;
+    ++pass;
+  }
+}
+
+// rr_launch_topk_select over compact rows (topk_select_counted_kernel): list l is the first cnt[r] entries of scores[l][0 .. pitch),
+// r = 0 if rows == 1, else l; rows is 1 or n_lists.  Of their entries that are not -inf the first k in rank order go to indices_out
+// [n_lists][k] as add + cand[r][place] (cand [rows][cand_ld >= pitch]; null: add + place) and to scores_out (or null), -1 / -inf behind
+// them, their number to counts_out [n_lists].  The passes are those `pitch` entries would need: the counts stay on the device, and
+// nothing is read back.  1 <= k <= min(pitch, 1024); tmp_a / tmp_b: rr_topk_select_scratch(n_lists, pitch, k) entries each.
+hipError_t rr_launch_topk_select_counted(const float* scores, int n_lists, int pitch, const int32_t* cnt, const int32_t* cand, long long cand_ld,
+                                         int rows, int k, int add, int32_t* tmp_a, int32_t* tmp_b, int32_t* indices_out, float* scores_out,
+                                         int32_t* counts_out, hipStream_t st) {
+  if (!scores || !cnt || !indices_out || !counts_out || n_lists <= 0 || n_lists > 65535 || pitch <= 0 || k < 1 || k > pitch || k > 1024)
+    return hipErrorInvalidValue;
+  if ((rows != 1 && rows != n_lists) || (cand && cand_ld < pitch)) return hipErrorInvalidValue;
+  if (pitch > SEL_SLICE && (!tmp_a || !tmp_b)) return hipErrorInvalidValue;
+  const long long ld = (long long)((pitch + SEL_SLICE - 1) / SEL_SLICE) * k;  // row pitch of both survivor buffers
+  const int32_t* in = nullptr;
+  int32_t* bufs[2] = {tmp_a, tmp_b};
+  int n_in = pitch, pass = 0;
+  for (;;) {
+    const int slices = (n_in + SEL_SLICE - 1) / SEL_SLICE;
+    const bool final_pass = slices == 1;
+    int32_t* o = final_pass ? indices_out : bufs[pass & 1];
+    hipLaunchKernelGGL(topk_select_counted_kernel, dim3((unsigned)slices, (unsigned)n_lists), dim3(SEL_THREADS), 0, st, scores, pitch, cnt, cand,
+                       cand_ld, rows, in, ld, pass, k, o, final_pass ? (long long)k : ld, add, final_pass ? scores_out : nullptr,
+                       final_pass ? counts_out : nullptr);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || final_pass) return e;
+    n_in = (slices - 1) * k + std::min(k, n_in - (slices - 1) * SEL_SLICE);    // (a shorter list's own length: counted_entries)
     in = o;
     ++pass;
   }

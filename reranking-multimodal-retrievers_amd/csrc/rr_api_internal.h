@@ -287,6 +287,7 @@ hipError_t stage_slot(rr_model::AsmSlot& a, const void* data, size_t bytes, size
 int asm_stage(rr_model* m, const char* what, const void* data, size_t bytes, hipStream_t st, void** dev);
 int asm_done(rr_model* m, hipStream_t st);
 int set_plaid_stop_after(bool ivf, int value);
+int set_sparse_stop_after(int value);
 
 const char* const CAP_GROWS = "%s would have to grow during stream capture; call rr_reserve for the largest shape before capturing";
 const char* const CAP_STAGES = "%s cannot be captured into a graph (it stages its descriptors from the host)";

@@ -533,6 +533,21 @@ hipError_t rr_launch_list_select(const float* scores, long long n, int nq, const
 size_t rr_topk_select_scratch(int n_lists, int n, int k);
 hipError_t rr_launch_topk_select(const float* scores, int n_lists, int n, int k, int add, int32_t* tmp_a, int32_t* tmp_b,
                                  int32_t* indices_out, float* scores_out, hipStream_t st);
+// The list-driven form of the filtered exact search (rr_bank_search_filtered_sparse), stage by stage.
+// rr_launch_filter_compact (bank_ivf.hip): cand [filter.rows][n] = the range-relative passages of [filter.first, filter.first + n) whose
+// bit is set, ascending, cnt [filter.rows] their numbers; a workgroup per row, no atomics.
+// rr_launch_bank_search_scores_places (bank_search.hip): the MaxSim of query q against the passages cand[r][0 .. cnt[r]) (r = 0 if
+// rows == 1, else q) to those places of the compact out [nq][pitch]; nothing behind a count is read or written.
+// rr_launch_topk_select_counted: rr_launch_topk_select over the first cnt[r] places of the compact rows, with rr_launch_list_select's
+// ending: the -inf scorers dropped, add + cand[r][place] (cand null: add + place), -1 / -inf behind, counts_out.  The scratch is
+// rr_topk_select_scratch(n_lists, pitch, k); the counts are read on the device alone.
+hipError_t rr_launch_filter_compact(const rr_passage_filter& filter, int n, int32_t* cand, int32_t* cnt, hipStream_t st);
+hipError_t rr_launch_bank_search_scores_places(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
+                                               const rr_bank_view& bank, const int32_t* cand, const int32_t* cnt, int rows, int pitch,
+                                               float* out, hipStream_t st);
+hipError_t rr_launch_topk_select_counted(const float* scores, int n_lists, int pitch, const int32_t* cnt, const int32_t* cand, long long cand_ld,
+                                         int rows, int k, int add, int32_t* tmp_a, int32_t* tmp_b, int32_t* indices_out, float* scores_out,
+                                         int32_t* counts_out, hipStream_t st);
 int rr_set_search_chunk(int passages);      // rr_set_tuning("search_chunk"): 4 .. 128, -1 outside
 // rr_bank_merge_topk (bank_merge.hip; "THE MERGED LIST", include/rerank_mi355.h): per-part k-lists over local indices into one list
 // over global indices, one workgroup per query.  rr_merge_check: what the three entry points refuse alike before anything is read

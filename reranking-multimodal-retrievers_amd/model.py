@@ -207,6 +207,24 @@ def _bank_search_args(eng, name: str, bank, query_li: torch.Tensor, first: int, 
     return first, n, nq, Lq, query_li.to(device=eng.device, dtype=torch.float32).contiguous()
 
 
+def _bank_search_filtered(eng, what: str, bank, query_li, k, filter, first, count) -> dict:
+    """RerankEngine.bank_search_filtered and bank_search_filtered_sparse (`what`; the entry is rr_ + what): one set of checks, one
+    result dict."""
+    first, n, nq, Lq, q = _bank_search_args(eng, what, bank, query_li, first, count)
+    k = int(k)
+    if k < 1 or k > n:
+        raise ValueError(f"{what}: k = {k} of {n} passages")
+    if k > 1024:
+        raise NotImplementedError(f"{what}: k = {k} (at most 1024)")
+    fargs = _bank_filter_args(what, filter, nq, first, n)
+    out = dict(indices=torch.empty((nq, k), device=eng.device, dtype=torch.int32),
+               scores=torch.empty((nq, k), device=eng.device, dtype=torch.float32),
+               counts=torch.empty((nq,), device=eng.device, dtype=torch.int32))
+    L.check(getattr(eng.lib, "rr_" + what)(eng.h, bank.h, L.ptr(q), nq, Lq, first, n, k, *fargs, L.ptr(out["indices"]),
+                                           L.ptr(out["scores"]), L.ptr(out["counts"]), eng._stream()), eng.h, "rr_" + what)
+    return out
+
+
 def _bank_filter_args(name: str, filter, nq: int, first: int, n: int) -> list:
     """The three filter arguments of a filtered search (bits, rows, words per row) from a BankFilter, checked against the call:
     one row or one per query, built for at least the passages of the range (ValueError)."""
@@ -921,21 +939,16 @@ class RerankEngine:
         or one per query) allows (rr_bank_search_filtered): a passage outside the set is not scored.  {"indices": int32
         [n_queries, k] dense bank indices, -1 behind the count; "scores": float32 [n_queries, k], -inf there; "counts": int32
         [n_queries]}, on the device; k may exceed the number of allowed passages.  With every passage allowed: bank_search's
-        result.  The selection still walks one score per passage of the range: for a filter of a few thousand passages
-        bank_li_scores over those pairs and torch.topk is the cheaper route."""
-        first, n, nq, Lq, q = _bank_search_args(self, "bank_search_filtered", bank, query_li, first, count)
-        k = int(k)
-        if k < 1 or k > n:
-            raise ValueError(f"bank_search_filtered: k = {k} of {n} passages")
-        if k > 1024:
-            raise NotImplementedError(f"bank_search_filtered: k = {k} (at most 1024)")
-        fargs = _bank_filter_args("bank_search_filtered", filter, nq, first, n)
-        out = dict(indices=torch.empty((nq, k), device=self.device, dtype=torch.int32),
-                   scores=torch.empty((nq, k), device=self.device, dtype=torch.float32),
-                   counts=torch.empty((nq,), device=self.device, dtype=torch.int32))
-        L.check(self.lib.rr_bank_search_filtered(self.h, bank.h, L.ptr(q), nq, Lq, first, n, k, *fargs, L.ptr(out["indices"]),
-                                                 L.ptr(out["scores"]), L.ptr(out["counts"]), self._stream()), self.h, "rr_bank_search_filtered")
-        return out
+        result.  The selection still walks one score per passage of the range, however few the filter allows:
+        bank_search_filtered_sparse returns the same bytes with every stage over the allowed passages alone
+        (profiles/bank_search_sparse_bench.json.log says from which density on it is the faster one)."""
+        return _bank_search_filtered(self, "bank_search_filtered", bank, query_li, k, filter, first, count)
+
+    def bank_search_filtered_sparse(self, bank, query_li: torch.Tensor, k: int, filter, first: int = 0, count: Optional[int] = None) -> dict:
+        """bank_search_filtered, list-driven (rr_bank_search_filtered_sparse): the same arguments, checks and result, byte for byte.
+        The filter's rows are compacted into candidate lists on the device, the scoring workgroups walk those lists and the
+        selection reads their counts, so the work of the call follows the passages the filter allows, not the range."""
+        return _bank_search_filtered(self, "bank_search_filtered_sparse", bank, query_li, k, filter, first, count)
 
     def bank_search_plaid_filtered(self, bank, query_li: torch.Tensor, k: int, filter, **kw) -> dict:
         """bank_search_plaid with the candidates restricted to what `filter` (a BankFilter) allows (rr_bank_search_plaid_filtered):
@@ -1492,15 +1505,22 @@ class InteractionRerankModel(_DropIn):
             raise RuntimeError("retriever_scores needs a bank: model.create_bank(capacity_rows, max_passages), then bank.add(...)")
         return self.engine.bank_li_scores(self.bank, query_late_interaction, passage_ids, **kw)
 
-    def retrieve(self, query_late_interaction, k: int, plaid=None, allowed=None, excluded=None, filter=None, **kw):
+    def retrieve(self, query_late_interaction, k: int, plaid=None, allowed=None, excluded=None, filter=None, sparse: bool = False, **kw):
         """The k best passages of `self.bank` per query by the frozen retriever's MaxSim, every passage scored
         (PassageBank.search): (passage_ids: one list per query, best first; scores float32 [n_queries, k] on the device).
         `plaid` (a PlaidSearch): PLAID's pruned search over a compressed bank instead; a query's list may then be shorter than k.
         `allowed` / `excluded` (passage ids: a flat sequence for every query, or a list of lists, one per query), or `filter` (a
         BankFilter built by bank.filter): only the allowed passages compete (the reference's filter_fn); one of the three at most.
-        A query's list then has its true length, at most k."""
+        A query's list then has its true length, at most k.  `sparse` (with one of the three, without `plaid`; ValueError
+        otherwise): the filtered exact search in its list-driven form (RerankEngine.bank_search_filtered_sparse), the same result."""
         if self.bank is None:
             raise RuntimeError("retrieve needs a bank: model.create_bank(capacity_rows, max_passages), then bank.add(...)")
+        if sparse:                                # before a filter is built or the library is called
+            if allowed is None and excluded is None and filter is None:
+                raise ValueError("retrieve: sparse=True needs allowed / excluded or a filter")
+            if plaid is not None:
+                raise ValueError("retrieve: sparse=True with plaid (the pruned searches touch candidates only already)")
+            kw["sparse"] = True
         if plaid is not None:
             kw["plaid"] = plaid
         if allowed is not None or excluded is not None:
@@ -1511,17 +1531,22 @@ class InteractionRerankModel(_DropIn):
             kw["filter"] = filter
         return self.bank.search(self.engine, query_late_interaction, k, **kw)
 
-    def retrieve_and_rerank(self, query_late_interaction, query_mask, k: int, plaid=None, allowed=None, excluded=None, filter=None, **kw):
+    def retrieve_and_rerank(self, query_late_interaction, query_mask, k: int, plaid=None, allowed=None, excluded=None, filter=None,
+                            sparse: bool = False, **kw):
         """`retrieve` then `forward_passages` on what it found, k candidates per query in retrieval order: (passage_ids, the
         RerankOutput).  `kw` goes to forward_passages (labels default as there: candidate 0 of every query).  With `plaid`, or
         under `allowed` / `excluded` / `filter` (as retrieve takes them), the lists may be of unequal length: they go to
-        forward_passages as candidates_per_query; a query that found no candidate raises ValueError."""
+        forward_passages as candidates_per_query; a query that found no candidate raises ValueError.  `sparse`: as retrieve takes
+        it."""
         filtered = allowed is not None or excluded is not None or filter is not None
+        if sparse and (plaid is not None or not filtered):
+            raise ValueError("retrieve_and_rerank: sparse=True needs allowed / excluded or a filter, and no plaid")
         if plaid is None and not filtered:
             ids, _ = self.retrieve(query_late_interaction, k)
             flat = [pid for row in ids for pid in row]
             return ids, self.forward_passages(query_late_interaction, query_mask, flat, int(k) - 1, **kw)
-        ids, _ = self.retrieve(query_late_interaction, k, plaid=plaid, allowed=allowed, excluded=excluded, filter=filter)
+        ids, _ = self.retrieve(query_late_interaction, k, plaid=plaid, allowed=allowed, excluded=excluded, filter=filter,
+                               **(dict(sparse=True) if sparse else {}))
         sizes = [len(row) for row in ids]
         if min(sizes) < 1:
             under = " and ".join((["its filter"] if filtered else []) + ([repr(plaid)] if plaid is not None else []))

@@ -937,7 +937,7 @@ class PassageBank:
         return BankFilter(bits, rows, passages, self.generation)
 
     def search(self, engine, query_li, k: int, first: int = 0, count: Optional[int] = None, plaid: Optional[PlaidSearch] = None,
-               filter: Optional[BankFilter] = None):
+               filter: Optional[BankFilter] = None, sparse: bool = False):
         """The k best passages per query by the retriever's MaxSim, every passage of the bank scored (engine.bank_search;
         `first` / `count`: a range of dense indices).  Returns (passage_ids, scores): passage_ids[q] the ids of query q best
         first, scores float32 [n_queries, k] on the device.  Copies the indices to the host (synchronises).
@@ -946,7 +946,10 @@ class PassageBank:
         PlaidSearch with ivf=True takes the candidates from the inverted file (build_ivf first): the same result.
         With `filter` (a BankFilter, `filter`) only the passages it allows compete, in the exact and in the pruned search
         (engine.bank_search_filtered / bank_search_plaid_filtered / bank_search_plaid_ivf_filtered): passage_ids[q] has its true
-        length on the exact path too.  A filter built for fewer passages than the range ends at raises ValueError."""
+        length on the exact path too.  A filter built for fewer passages than the range ends at raises ValueError.
+        `sparse` (with `filter`, exact search only; ValueError otherwise): the list-driven form of the filtered exact search
+        (engine.bank_search_filtered_sparse): the same result, with work that follows the allowed passages, not the range."""
+        _sparse_check("search", sparse, filter, plaid)
         ids = self.table.ids
         if filter is not None:
             if getattr(filter, "generation", self.generation) != self.generation:
@@ -957,7 +960,8 @@ class PassageBank:
                 raise ValueError(f"search: the filter was built for {filter.passages} passages, the range ends at {end}: build it again "
                                  "(PassageBank.filter)")
             if plaid is None:
-                r = engine.bank_search_filtered(self, query_li, k, filter, first=first, count=count)
+                entry = engine.bank_search_filtered_sparse if sparse else engine.bank_search_filtered
+                r = entry(self, query_li, k, filter, first=first, count=count)
             else:
                 entry = engine.bank_search_plaid_ivf_filtered if getattr(plaid, "ivf", False) else engine.bank_search_plaid_filtered
                 r = entry(self, query_li, k, filter, ncells=plaid.ncells, centroid_score_threshold=plaid.centroid_score_threshold,
@@ -1097,13 +1101,23 @@ class PassageBank:
         self.generation += 1
 
 
-def search_bank_part(engine, bank, query_li, k: int, plaid: Optional[PlaidSearch] = None, filter: Optional[BankFilter] = None) -> dict:
+def _sparse_check(name: str, sparse: bool, filter, plaid) -> None:
+    """`sparse` names the list-driven form of the FILTERED EXACT search: without a filter, or with `plaid`, there is none."""
+    if sparse and filter is None:
+        raise ValueError(f"{name}: sparse=True needs a filter (the list-driven form walks the passages a filter allows)")
+    if sparse and plaid is not None:
+        raise ValueError(f"{name}: sparse=True with plaid (the pruned searches touch candidates only already)")
+
+
+def search_bank_part(engine, bank, query_li, k: int, plaid: Optional[PlaidSearch] = None, filter: Optional[BankFilter] = None,
+                     sparse: bool = False) -> dict:
     """One part's list for RerankEngine.bank_merge_topk: the search of `bank` (the exact one, or with `plaid` / `filter` what
     PassageBank.search runs for them) with k_local = min(k, len(bank)), as {"indices": int32 [n_queries, k] dense indices of
     THIS bank, "scores": float32 [n_queries, k], "counts": int32 [n_queries]} on the device.  Behind k_local the rows hold -1 /
     -inf; an exact search, which returns no counts, gets k_local as its count; an empty bank contributes count 0 and no search
-    call."""
+    call.  `sparse`: as PassageBank.search takes it."""
     import torch
+    _sparse_check("search_bank_part", sparse, filter, plaid)
     nq, k, dev = int(query_li.shape[0]), int(k), engine.device
     k_local = min(k, len(bank))
     out = dict(indices=torch.full((nq, k), -1, device=dev, dtype=torch.int32),
@@ -1120,7 +1134,7 @@ def search_bank_part(engine, bank, query_li, k: int, plaid: Optional[PlaidSearch
         else:
             r = (engine.bank_search_plaid_ivf_filtered if ivf else engine.bank_search_plaid_filtered)(bank, query_li, k_local, filter, **kw)
     elif filter is not None:
-        r = engine.bank_search_filtered(bank, query_li, k_local, filter)
+        r = (engine.bank_search_filtered_sparse if sparse else engine.bank_search_filtered)(bank, query_li, k_local, filter)
     else:
         r = engine.bank_search(bank, query_li, k_local)
     if k_local == k and "counts" in r:
@@ -1134,7 +1148,8 @@ def search_bank_part(engine, bank, query_li, k: int, plaid: Optional[PlaidSearch
     return out
 
 
-def search_banks(engine, banks: Sequence, query_li, k: int, plaid: Optional[PlaidSearch] = None, filters: Optional[Sequence] = None):
+def search_banks(engine, banks: Sequence, query_li, k: int, plaid: Optional[PlaidSearch] = None, filters: Optional[Sequence] = None,
+                 sparse: bool = False):
     """PassageBank.search over several banks held by one process (a corpus loaded bank by bank, an fp16 bank beside a compressed
     one of the same li_dim) as over one bank holding their passages in the order of `banks`: every bank is searched
     (search_bank_part: `plaid` for each, `filters[i]` a BankFilter of bank i or None), the lists are merged on the device
@@ -1142,7 +1157,8 @@ def search_banks(engine, banks: Sequence, query_li, k: int, plaid: Optional[Plai
     counts): passage_ids[q] the ids of query q best first, at its true length (at most k); scores float32 [n_queries, k] on the
     device, -inf behind the count; counts int32 [n_queries] on the device.  With the exact search this is, byte for byte, the
     search of the one bank; with `plaid` it is by definition the merge of the per-bank pruned searches (each bank keeps its own
-    ndocs).  Copies the merged indices to the host (synchronises).  At most 64 banks, len(banks) * k <= 8192."""
+    ndocs).  Copies the merged indices to the host (synchronises).  At most 64 banks, len(banks) * k <= 8192.  `sparse`: every
+    bank's filtered exact search in its list-driven form (a filter for every bank, no `plaid`; ValueError otherwise)."""
     import numpy as np
     import torch
     banks = list(banks)
@@ -1150,9 +1166,13 @@ def search_banks(engine, banks: Sequence, query_li, k: int, plaid: Optional[Plai
         raise ValueError("search_banks: no bank")
     if filters is not None and len(filters) != len(banks):
         raise ValueError(f"search_banks: {len(filters)} filters for {len(banks)} banks (one each, or None)")
+    if sparse:
+        for f in (filters if filters is not None else [None]):
+            _sparse_check("search_banks", sparse, f, plaid)
     offsets = np.zeros(len(banks) + 1, dtype=np.int64)
     np.cumsum([len(b) for b in banks], out=offsets[1:])
-    parts = [search_bank_part(engine, b, query_li, k, plaid, None if filters is None else filters[i]) for i, b in enumerate(banks)]
+    more = dict(sparse=True) if sparse else {}
+    parts = [search_bank_part(engine, b, query_li, k, plaid, None if filters is None else filters[i], **more) for i, b in enumerate(banks)]
     r = engine.bank_merge_topk(torch.stack([p["indices"] for p in parts]), torch.stack([p["scores"] for p in parts]),
                                torch.stack([p["counts"] for p in parts]), offsets, k, want_parts=True)
     counts = r["counts"].tolist()

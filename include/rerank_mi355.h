@@ -569,7 +569,8 @@ int rr_bank_add(rr_bank_handle b, const void* context_li, int dtype, const float
  * caller's host memory on hip_stream and synchronises that stream, so the host buffers may be reused when it returns; not
  * capturable into a graph (RR_ERR_BAD_ARG under stream capture).  An inverted file the bank holds (THE INVERTED FILE, below) does
  * not cover the new passages until rr_bank_extend_ivf is called.
- * rr_bank_format: nbits (0 for an fp16 bank), the number of centroids (0) and the device bytes one row takes (mask byte included);
+ * rr_bank_format: nbits (0 for an fp16 bank), the number of centroids (0; an fp16 bank with a centroid table, rr_bank_set_centroids
+ * below: its number) and the device bytes one row takes (mask byte included);
  * any pointer may be NULL.
  * The two formats do not mix: rr_bank_add on a compressed bank and rr_bank_add_plaid on an fp16 bank return RR_ERR_UNSUPPORTED.
  * rr_bank_clear / rr_bank_info / rr_bank_destroy / rr_bank_read and rr_forward_interaction_bank take either kind unchanged.
@@ -618,6 +619,38 @@ int rr_bank_format(rr_bank_handle b, int32_t* nbits_out, int32_t* n_centroids_ou
 int rr_bank_set_plaid_cutoffs(rr_bank_handle b, const float* cutoffs_host);
 int rr_bank_add_compress(rr_bank_handle b, const void* context_li, int dtype, const float* context_mask, const int32_t* lengths, int n,
                          int Lc, int32_t* first_index_out, void* hip_stream);
+/* ---- An fp16 bank with a centroid table: a "coded" fp16 bank.  The pruned searches and the inverted file read one centroid code
+ * per row, the centroid table, the mask bytes and the passage table; their last stage is the exact score, which an fp16 bank
+ * defines on its own rows.  rr_bank_set_centroids gives an fp16 bank the table and the code per row; the bank keeps its fp16 rows,
+ * and every entry that reads them (rr_bank_read, rr_bank_li_scores, rr_bank_search and its filtered forms,
+ * rr_forward_interaction_bank) gives the bits it gave before.
+ *   centroids_f16_host : HOST fp16 bits [n_centroids, li_dim] (PlaidCodec.train's table, or any other)
+ *   n_centroids        : 1 .. 262144 (RR_ERR_BAD_SHAPE outside; the limit of the pruned search)
+ * RR_ERR_UNSUPPORTED on a compressed bank (its codes belong to its residuals) and for an li_dim that is not a multiple of 16 (the
+ * matrix-core step of the assignment and of stage 0).  A LOAD-TIME call: it synchronises the device (adds on any stream have
+ * written their rows), allocates 4 bytes per row of capacity and the table, copies the table, assigns a code to every row the
+ * bank holds now (in launches of at most 2^20 rows, 64-bit row offsets; their scratch follows rr_bank_add_compress's grow-only
+ * rule) and synchronises hip_stream.  RR_ERR_BAD_ARG under stream capture.  A refusal or a failed allocation leaves the bank as
+ * it was (RR_ERR_OOM).  Called again it replaces the table and assigns every row anew (centroids retrained after the bank has
+ * grown), and it drops an inverted file the bank holds, whose lists name the old codes.
+ * THE CODE OF A ROW is THE COMPRESSED ROW steps 2 - 3 with x = the stored fp16 row: the same rank key, the same tie rule, the
+ * same independence of how the centroid range is split (rr_set_tuning("compress_chunk")); interior masked rows get a code like any
+ * other row.  So for equal input the codes are bit for bit those rr_bank_add_compress writes into a compressed bank of the same
+ * table, whatever its nbits and cutoffs.
+ * On a coded bank rr_bank_add ingests as before and assigns the codes of the new rows behind the ingest on the same stream
+ * (the assignment kernel of rr_bank_add_compress with a codes-only ending: its 64-bit key per row and centroid split is the only
+ * intermediate, no residual is formed or written); admission, refusal before the first enqueue and the capture refusal are unchanged, and the
+ * scratch grows as rr_bank_add_compress's does (one device synchronisation when it has to).  rr_bank_add_compress,
+ * rr_bank_add_plaid and rr_bank_set_plaid_cutoffs keep refusing an fp16 bank, coded or not.  rr_bank_format reports nbits 0,
+ * n_centroids and 2 li_dim + 1 + 4 bytes per row.
+ * A coded bank is taken, under the contract they have on a compressed bank, by rr_bank_search_plaid, rr_bank_search_plaid_ivf and
+ * their _filtered forms (stage 3 reads the fp16 rows: bit for bit rr_bank_search's score on this bank), rr_bank_build_ivf,
+ * rr_bank_extend_ivf, rr_bank_ivf_info, rr_bank_ivf_read, rr_bank_load_ivf, rr_bank_remove (rows, codes and mask bytes move
+ * together) and rr_bank_clear (the table stays).  rr_bank_export_plaid and rr_bank_read_plaid (rerank_mi355_diag.h) refuse it with
+ * RR_ERR_UNSUPPORTED: there are no residuals; rr_bank_read_codes there reads the codes.  An fp16 bank WITHOUT a table behaves in
+ * every entry as it always has.  Python: RerankEngine.create_bank(centroids=...), PassageBank.set_centroids / centroids /
+ * n_centroids / codes. */
+int rr_bank_set_centroids(rr_bank_handle b, const uint16_t* centroids_f16_host, int32_t n_centroids, void* hip_stream);
 /* ---- Training a PLAID codec on the device: the centroid table by k-means and the residuals the bucket statistics are taken
  * from.  Replaces, in third_party/ColBERT/colbert/indexing/collection_indexer.py of the reference, train (:211-228),
  * _concatenate_and_split_sample (:230-261), _train_kmeans (:263-293), _compute_avg_residual (:295-319) and compute_faiss_kmeans
@@ -770,7 +803,8 @@ int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_q
  * reference reads from its IVF (per centroid the passages holding a token with that code: _build_ivf, indexing/
  * collection_indexer.py:393-431, sorts the embedding ids by code and counts them per centroid; optimize_ivf, indexing/utils.py:8-48,
  * maps every embedding id to its passage and keeps the unique passages of each centroid) comes from one scan over the codes of
- * the range.  An fp16 bank: RR_ERR_UNSUPPORTED.  Handles, li_dim, query_li,
+ * the range.  An fp16 bank without a centroid table (rr_bank_set_centroids): RR_ERR_UNSUPPORTED; with one, stage 3 reads its
+ * fp16 rows.  Handles, li_dim, query_li,
  * first_passage / n_passages, alignment, device checks and the graph-capture refusal exactly as rr_bank_search has them.
  *   Lq_coarse : 1 <= Lq_coarse <= Lq (RR_ERR_BAD_SHAPE): stages 0-2 use the first Lq_coarse query tokens, the exact stage all Lq
  *       (the reference cuts the query to query_maxlen for the approximate stages, index_storage.py:77).
@@ -804,14 +838,16 @@ int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_q
  * k2 = min(ndocs / 4, n): 4 nq Cp Lq + 16 nq Cp / 64 + Cp + 4 nq Lq_coarse ncells + 8 nq W + 8 nq n + 4 nq (k1 + k2 + 1)
  * + 8 * (n > 4096 ? nq ceil(n / 4096) k1 : 0) bytes.
  * Checked on the host BEFORE anything is enqueued; a refused call writes nothing.  Not capturable into a graph (RR_ERR_BAD_ARG).
- * Out of scope: ndocs > 1024, fp16 banks.  A bank split over ranks: the per-part results merged by rr_bank_merge_topk below (which DEFINES the sharded pruned search).  A caller-supplied candidate filter: rr_bank_search_plaid_filtered
+ * Out of scope: ndocs > 1024, fp16 banks without a centroid table.  A bank split over ranks: the per-part results merged by rr_bank_merge_topk below (which DEFINES the sharded pruned search).  A caller-supplied candidate filter: rr_bank_search_plaid_filtered
  * below; candidates from an IVF: rr_bank_build_ivf / rr_bank_search_plaid_ivf below.  (Python:
  * RerankEngine.bank_search_plaid, PlaidSearch with PassageBank.search / InteractionRerankModel.retrieve / retrieve_and_rerank.) */
 int rr_bank_search_plaid(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int Lq_coarse,
                          int32_t first_passage, int32_t n_passages, int ncells, float centroid_score_threshold, int ndocs, int k,
                          int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream);
 
-/* THE INVERTED FILE of a compressed bank, and the pruned search that takes its candidates from it.
+/* THE INVERTED FILE of a compressed bank (or of an fp16 bank with a centroid table, rr_bank_set_centroids: every entry of this
+ * section takes it as it takes a compressed bank; "an fp16 bank" below is one without a table), and the pruned search that takes
+ * its candidates from it.
  * DEFINITION.  The file covers the passages 0 .. P-1 the bank held when it was built.  With C = n_centroids, list[c], c < C, is the
  * set of passages that have at least one UNMASKED row r with clamp(code_r, 0, C-1) == c (the clamp of rr_bank_search_plaid's
  * scan), in ascending bank index, every passage once per list.  Stored as offsets int64 [C + 1] (offsets[0] = 0, list[c] =
@@ -826,7 +862,7 @@ int rr_bank_search_plaid(rr_handle h, rr_bank_handle b, const float* query_li, i
  * (8 (C + 1) + 4 postings bytes kept; 16 P + 4 C + P / 8 bytes for the call), reads the postings total and the longest list back
  * and synchronises hip_stream; not capturable into a graph (RR_ERR_BAD_ARG).  An fp16 bank: RR_ERR_UNSUPPORTED; an empty bank:
  * RR_ERR_BAD_SHAPE; a failed allocation: RR_ERR_OOM with the bank unchanged: a previous file survives a failed rebuild.
- * LIFETIME: rr_bank_clear drops the file; passages added after a build (rr_bank_add_plaid, rr_bank_add_compress) leave it valid
+ * LIFETIME: rr_bank_clear drops the file; passages added after a build (rr_bank_add_plaid, rr_bank_add_compress, rr_bank_add) leave it valid
  * for its prefix 0 .. P-1 until rr_bank_extend_ivf (below) extends it over them, or a new build covers them; rr_bank_remove leaves
  * the bank with the file over the survivors of that prefix, rebuilt by this builder when one of them went; rr_bank_destroy frees it.
  * rr_bank_ivf_info: passages_covered (0: no file), the postings total and the longest list; any pointer may be NULL.
@@ -943,7 +979,8 @@ int rr_bank_remove(rr_bank_handle b, const int32_t* indices_host, int n, int32_t
  * inside their passage, are gone.  A passage of doclen 0 cannot be added again (rr_bank_add_plaid refuses it).
  * SIZING CALL: codes_out and residuals_out both NULL: only doclens_host_out and *rows_host_out are written.
  * REFUSALS, every one from the host, writing nothing: exactly one of codes_out / residuals_out NULL, a NULL doclens_host_out or
- * rows_host_out, a misaligned output, a capturing stream (RR_ERR_BAD_ARG); an fp16 bank (RR_ERR_UNSUPPORTED); n_passages < 1 or a
+ * rows_host_out, a misaligned output, a capturing stream (RR_ERR_BAD_ARG); an fp16 bank, with or without a centroid table: it holds no residuals
+ * (RR_ERR_UNSUPPORTED); n_passages < 1 or a
  * range that is not inside the bank (RR_ERR_BAD_SHAPE); both outputs given and capacity_rows < R (RR_ERR_BAD_SHAPE, decided after
  * the count and before any row is moved; rr_bank_last_error names R).
  * Three kernels (csrc/bank_export.hip), no global atomics, the same bytes from run to run: a count (a wave per passage, 64 mask

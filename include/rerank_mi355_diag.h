@@ -279,13 +279,17 @@ int rr_op_plaid_decode_rows(const uint16_t* centroids_f16, int32_t n_centroids, 
  * rr_bank_read_plaid: the STORED form of one passage of a compressed bank, the raw twin of rr_bank_read: codes_out int32 [len],
  * residuals_out uint8 [len, li_dim * nbits / 8], mask_out [len] in HOST memory (any may be NULL; all NULL = only the length),
  * buffers of capacity_rows rows.  Synchronises hip_stream and copies synchronously.  Returns the length or < 0
- * (RR_ERR_UNSUPPORTED on an fp16 bank). */
+ * (RR_ERR_UNSUPPORTED on an fp16 bank, with or without a centroid table: it holds no residuals).
+ * rr_bank_read_codes: the centroid codes of one passage, codes_out int32 [len] in HOST memory (NULL = only the length), from a
+ * compressed bank or an fp16 bank with a centroid table (rr_bank_set_centroids); RR_ERR_UNSUPPORTED on an fp16 bank without one.
+ * Synchronises hip_stream and copies synchronously, as rr_bank_read. */
 int rr_util_plaid_compress_rows(const void* rows, int dtype, int64_t n_rows, int D, const uint16_t* centroids_f16, int32_t n_centroids,
                                 const float* cutoffs, int nbits, int32_t* codes_out, uint8_t* residuals_out);
 int rr_op_plaid_compress_rows(const void* rows, int dtype, int64_t n_rows, int D, const uint16_t* centroids_f16, int32_t n_centroids,
                               const float* cutoffs, int nbits, int32_t* codes_out, uint8_t* residuals_out, void* hip_stream);
 int rr_bank_read_plaid(rr_bank_handle b, int32_t index, int32_t* codes_out, uint8_t* residuals_out, uint8_t* mask_out,
                        int32_t capacity_rows, void* hip_stream);
+int rr_bank_read_codes(rr_bank_handle b, int32_t index, int32_t* codes_out, int32_t capacity_rows, void* hip_stream);
 /* PLAID codec training (THE TRAINED CENTROIDS: rerank_mi355.h, rr_plaid_kmeans).
  * rr_util_plaid_kmeans: pure HOST code, usable without a GPU: the definition, every step in the stated order.  rows [n_rows, D]
  * float32 (RR_F32) or fp16 bits (RR_F16), init_rows int32 [n_centroids] -> centroids_f16_out [n_centroids, D] fp16 bits, counts_out

@@ -108,6 +108,8 @@ _SIGS = {
     "rr_op_plaid_residuals": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _P, C.c_int32, _P, _P, _P]),
     "rr_util_plaid_kmeans": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _P, C.c_int32, C.c_int, C.c_uint64, _P, _P, _P]),
     "rr_bank_read_plaid": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P]),
+    "rr_bank_set_centroids": (C.c_int, [_P, _P, C.c_int32, _P]),
+    "rr_bank_read_codes": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P]),
     "rr_bank_format": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "rr_util_plaid_decode_rows": (C.c_int, [_P, C.c_int32, _P, C.c_int, C.c_int, _P, _P, C.c_int64, _P]),
     "rr_op_plaid_decode_rows": (C.c_int, [_P, C.c_int32, _P, C.c_int, C.c_int, _P, _P, C.c_int64, C.c_int64, _P, _P]),

@@ -171,8 +171,8 @@ static int bank_add_padded(rr_bank* b, const char* what, const void* context_li,
   RR_TRY(bank_admit(b, what, lengths, n, Lc, &rows));
   hipStream_t st = (hipStream_t)hip_stream;
   RR_TRY(bank_capture_guard(b, st, CAP_STAGES, what));
-  const rr_compress_plan pl = b->nbits ? rr_plaid_compress_plan(rows, b->n_centroids, b->D) : rr_compress_plan{};
-  if (b->nbits && pl.jt == 0)
+  const rr_compress_plan pl = b->has_codes() ? rr_plaid_compress_plan(rows, b->n_centroids, b->D) : rr_compress_plan{};      // (coded fp16: the codes behind the ingest)
+  if (b->has_codes() && pl.jt == 0)
     return bfail(b, RR_ERR_BAD_SHAPE, "%s: %lld rows against %d centroids at the compress_chunk in force do not fit a launch", what,
                  (long long)rows, b->n_centroids);
   RR_BHIP(b, hipSetDevice(b->device));
@@ -197,6 +197,8 @@ static int bank_add_padded(rr_bank* b, const char* what, const void* context_li,
                                         b->resid + (size_t)r0 * b->resid_row_bytes(), b->mask + r0, st));
   else
     RR_BHIP(b, rr_launch_bank_ingest(in, b->D, b->rows, b->mask, st));
+  if (b->coded())                                    // the new rows' codes, from the fp16 rows the ingest has just written
+    RR_BHIP(b, rr_launch_plaid_assign_codes(b->rows + (size_t)r0 * b->D, rows, b->D, b->centroids, b->n_centroids, b->cscratch, pl, b->codes + r0, st));
   RR_BHIP(b, hipEventRecord(a.done, st));
   b->next ^= 1;
   bank_append(b, lengths, n, first_index_out);
@@ -275,6 +277,68 @@ int rr_bank_add_compress(rr_bank_handle b, const void* context_li, int dtype, co
     if (!b->has_cutoffs) return bfail(b, RR_ERR_UNSUPPORTED, "%s: the bank has no bucket cutoffs (rr_bank_set_plaid_cutoffs)", what);
     if (b->D % 16) return bfail(b, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a multiple of 16: the matrix-core step of the centroid search)", what, b->D);
     return bank_add_padded(b, what, context_li, dtype, context_mask, lengths, n, Lc, first_index_out, hip_stream);
+  });
+}
+
+// rr_bank_set_centroids (include/rerank_mi355.h): an fp16 bank becomes, or stays, a coded one.  Every refusal on the host; then
+// every allocation (the new table, the codes of a first call, the scratch grown), so that a failure leaves the bank as it was; only
+// then the table is copied and takes its place, an inverted file over the old codes goes, and the rows the bank holds are assigned
+// in launches of at most SET_CENTROIDS_ROWS rows (the keys of a launch bound the scratch, not the bank)
+constexpr int64_t SET_CENTROIDS_ROWS = (int64_t)1 << 20;
+int rr_bank_set_centroids(rr_bank_handle b, const uint16_t* centroids_f16_host, int32_t n_centroids, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int {
+    const char* what = "rr_bank_set_centroids";
+    if (!b) return RR_ERR_BAD_ARG;
+    if (b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on a compressed bank: its codes belong to its residuals (rr_bank_create_plaid)", what);
+    if (!centroids_f16_host) return bfail(b, RR_ERR_BAD_ARG, "%s: null argument", what);
+    if (b->D % 16) return bfail(b, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a multiple of 16: the matrix-core step of the centroid search)", what, b->D);
+    if (n_centroids < 1 || n_centroids > RR_PLAID_SEARCH_MAX_CENTROIDS)
+      return bfail(b, RR_ERR_BAD_SHAPE, "%s: n_centroids=%d (1..%d)", what, n_centroids, RR_PLAID_SEARCH_MAX_CENTROIDS);
+    const int64_t held_rows = b->used_rows, step = std::min(held_rows, SET_CENTROIDS_ROWS);
+    const rr_compress_plan pl = step ? rr_plaid_compress_plan(step, n_centroids, b->D) : rr_compress_plan{};
+    const int64_t tail = step ? held_rows % step : 0;       // the rows of a shorter last launch, with a plan of its own
+    const rr_compress_plan pl_tail = tail ? rr_plaid_compress_plan(tail, n_centroids, b->D) : pl;
+    if (step && (pl.jt == 0 || pl_tail.jt == 0))
+      return bfail(b, RR_ERR_BAD_SHAPE, "%s: %lld rows against %d centroids at the compress_chunk in force do not fit a launch", what,
+                   (long long)step, n_centroids);
+    const size_t need = std::max(pl.total, pl_tail.total);
+    hipStream_t st = (hipStream_t)hip_stream;
+    RR_TRY(bank_capture_guard(b, st, "%s cannot be captured into a graph (it allocates, copies from host memory and synchronises)", what));
+    RR_BHIP(b, hipSetDevice(b->device));
+    RR_BHIP(b, hipDeviceSynchronize());              // adds in flight write the rows read below; searches read the table that goes
+    const size_t cbytes = (size_t)n_centroids * b->D * sizeof(uint16_t);
+    uint16_t* table = nullptr;
+    int32_t* codes = b->codes;
+    char* scratch = nullptr;
+    hipError_t e = hipMalloc((void**)&table, cbytes);
+    if (e == hipSuccess && !codes) e = hipMalloc((void**)&codes, (size_t)b->cap_rows * sizeof(int32_t));
+    if (e == hipSuccess && b->cscratch_cap < need) e = hipMalloc((void**)&scratch, need);
+    if (e == hipSuccess) e = hipMemcpy(table, centroids_f16_host, cbytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      if (table) (void)hipFree(table);
+      if (codes && codes != b->codes) (void)hipFree(codes);
+      if (scratch) (void)hipFree(scratch);
+      return bfail(b, e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP, "%s: %lld rows of capacity, %d centroids of %d: %s (the bank is unchanged)",
+                   what, (long long)b->cap_rows, n_centroids, b->D, hipGetErrorString(e));
+    }
+    if (scratch) {                                   // grow-only, as an add grows it (the device was synchronised above: no add still reads the old block)
+      if (b->cscratch) (void)hipFree(b->cscratch);
+      b->cscratch = scratch;
+      b->cscratch_cap = need;
+    }
+    if (b->centroids) (void)hipFree(b->centroids);
+    b->centroids = table;
+    b->codes = codes;
+    b->n_centroids = n_centroids;
+    rr_ivf_free(&b->ivf);                            // its lists name the codes of the table that went
+    for (int64_t r0 = 0; r0 < held_rows; r0 += step) {
+      const int64_t R = std::min(step, held_rows - r0);
+      const rr_compress_plan& p = R == step ? pl : pl_tail;
+      RR_BHIP(b, rr_launch_plaid_assign_codes(b->rows + (size_t)r0 * b->D, R, b->D, b->centroids, n_centroids, b->cscratch, p, b->codes + r0, st));
+    }
+    RR_BHIP(b, hipStreamSynchronize(st));
+    return RR_OK;
   });
 }
 
@@ -461,8 +525,20 @@ int rr_bank_read_plaid(rr_bank_handle b, int32_t index, int32_t* codes_out, uint
   return guarded(nullptr, [&]() -> int {
     const char* what = "rr_bank_read_plaid";
     if (!b) return RR_ERR_BAD_ARG;
+    if (b->coded())
+      return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank with a centroid table: it holds codes but no residuals (rr_bank_read_codes, rr_bank_read)", what);
     if (!b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it holds no codes (rr_bank_read)", what);
     return bank_read(b, what, index, nullptr, codes_out, resid_out, mask_out, capacity_rows, hip_stream);
+  });
+}
+
+// rr_bank_read_codes (include/rerank_mi355_diag.h): the codes of one passage, of a compressed or a coded fp16 bank
+int rr_bank_read_codes(rr_bank_handle b, int32_t index, int32_t* codes_out, int32_t capacity_rows, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int {
+    const char* what = "rr_bank_read_codes";
+    if (!b) return RR_ERR_BAD_ARG;
+    if (!b->has_codes()) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank without a centroid table: it holds no codes (rr_bank_set_centroids)", what);
+    return bank_read(b, what, index, nullptr, codes_out, nullptr, nullptr, capacity_rows, hip_stream);
   });
 }
 
@@ -472,7 +548,7 @@ int rr_bank_read_plaid(rr_bank_handle b, int32_t index, int32_t* codes_out, uint
 static int bank_ivf_call(rr_bank* b, bool extend, void* hip_stream) {
   const char* what = extend ? "rr_bank_extend_ivf" : "rr_bank_build_ivf";
   if (!b) return RR_ERR_BAD_ARG;
-  if (!b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it holds no codes", what);
+  if (!b->has_codes()) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it holds no codes", what);
   const long long held = (long long)b->first.size();
   if (held < 1) return bfail(b, RR_ERR_BAD_SHAPE, "%s: the bank holds no passage", what);
   hipStream_t st = (hipStream_t)hip_stream;
@@ -661,7 +737,7 @@ static int bank_table_current(rr_model* m, rr_bank* b, hipStream_t st) {
   return RR_OK;
 }
 
-// What rr_bank_search and rr_bank_search_plaid (`pruned`: compressed banks only; `counted`: counts_out is required, as in the pruned and
+// What rr_bank_search and rr_bank_search_plaid (`pruned`: banks with codes only, compressed or coded fp16; `counted`: counts_out is required, as in the pruned and
 // the filtered entries, and null with the other null arguments) do alike before their first launch: the
 // shared checks, the range resolved into (first_passage, *n), then `limits(n)`, the call's own refusals, where they have always stood;
 // the device, the bank's table brought up to date, and *rows: the rows of the range (passages lie back to back), for the profile
@@ -670,7 +746,7 @@ static int bank_search_begin(rr_model* m, const char* what, bool pruned, bool co
                              const int32_t* counts_out, hipStream_t st, int* n, double* rows, const std::function<int(int)>& limits) {
   if (!b || !query_li || !indices_out || (counted && !counts_out)) return fail(m, RR_ERR_BAD_ARG, "%s: null argument", what);
   RR_TRY(bank_usable(m, what, b));
-  if (pruned && !b->nbits) return fail(m, RR_ERR_UNSUPPORTED, "%s: an fp16 bank (compressed banks only: the stages read the centroid codes)", what);
+  if (pruned && !b->has_codes()) return fail(m, RR_ERR_UNSUPPORTED, "%s: an fp16 bank (compressed banks only: the stages read the centroid codes)", what);
   if (m->cfg.li_dim % 16) return fail(m, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a multiple of 16)", what, m->cfg.li_dim);
   if (((uintptr_t)query_li) & 15) return fail(m, RR_ERR_BAD_ARG, "%s: query_li must be 16-byte aligned", what);
   if ((((uintptr_t)indices_out) | ((uintptr_t)scores_out) | ((uintptr_t)counts_out)) & 3) return fail(m, RR_ERR_BAD_ARG, "%s: misaligned output", what);
@@ -1061,6 +1137,9 @@ int rr_bank_export_plaid(rr_bank_handle b, int32_t first_passage, int32_t n_pass
     if (!doclens_host_out || !rows_host_out) return bfail(b, RR_ERR_BAD_ARG, "%s: null doclens_host_out or rows_host_out", what);
     if ((codes_out == nullptr) != (residuals_out == nullptr))
       return bfail(b, RR_ERR_BAD_ARG, "%s: codes_out and residuals_out are given together, or both NULL (a sizing call)", what);
+    if (b->coded())
+      return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank with a centroid table: it holds codes but no residuals (rr_bank_add_compress into a "
+                   "compressed bank writes them)", what);
     if (!b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it holds no codes", what);
     const long long held = (long long)b->first.size();
     if (n_passages < 1 || first_passage < 0 || (long long)first_passage + n_passages > held)
@@ -1119,7 +1198,7 @@ int rr_bank_load_ivf(rr_bank_handle b, const int64_t* offsets_host, const int32_
     const char* what = "rr_bank_load_ivf";
     if (!b) return RR_ERR_BAD_ARG;
     if (!offsets_host) return bfail(b, RR_ERR_BAD_ARG, "%s: null offsets", what);
-    if (!b->nbits) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it holds no codes", what);
+    if (!b->has_codes()) return bfail(b, RR_ERR_UNSUPPORTED, "%s on an fp16 bank: it holds no codes", what);
     const long long held = (long long)b->first.size();
     if (held < 1) return bfail(b, RR_ERR_BAD_SHAPE, "%s: the bank holds no passage", what);
     const int C = b->n_centroids;
@@ -1311,6 +1390,7 @@ int rr_bank_remove(rr_bank_handle b, const int32_t* indices_host, int n, int32_t
         arrays[na++] = rr_move_array{b->codes, (int)sizeof(int32_t)};
       } else {
         arrays[na++] = rr_move_array{b->rows, (int)widest};
+        if (b->coded()) arrays[na++] = rr_move_array{b->codes, (int)sizeof(int32_t)};      // the codes travel with their rows
       }
       arrays[na++] = rr_move_array{b->mask, 1};
       bool allocated = false;
@@ -1459,7 +1539,7 @@ int rr_bank_format(rr_bank_handle b, int32_t* nbits_out, int32_t* n_centroids_ou
   if (!b) return RR_ERR_BAD_ARG;
   if (nbits_out) *nbits_out = b->nbits;
   if (n_centroids_out) *n_centroids_out = b->n_centroids;
-  if (bytes_per_row_out) *bytes_per_row_out = b->nbits ? (int64_t)(4 + b->resid_row_bytes() + 1) : (int64_t)b->D * 2 + 1;
+  if (bytes_per_row_out) *bytes_per_row_out = b->nbits ? (int64_t)(4 + b->resid_row_bytes() + 1) : (int64_t)b->D * 2 + 1 + (b->coded() ? 4 : 0);
   return RR_OK;
 }
 int rr_util_plaid_decode_rows(const uint16_t* centroids_f16, int32_t n_centroids, const float* bucket_weights, int nbits, int D, const int32_t* codes, const uint8_t* residuals, int64_t n_rows, uint16_t* rows_out_f16) {

@@ -24,6 +24,9 @@
 //                             maximum over the splits' keys, the int32 code, the residual against that centroid row, the bucket by
 //                             a branch-free binary search over the cutoffs in LDS (at most 255, non-decreasing: the count of
 //                             cutoffs below r), nbits packed bytes per lane and the mask byte.  Plain vector stores only.
+//   compress_codes_kernel     the codes-only ending that takes (b)'s place for an fp16 bank with a centroid table
+//                             (rr_launch_plaid_assign_codes: rr_bank_set_centroids, rr_bank_add): the maximum over the splits' keys
+//                             and the int32 code, 4 bytes written per row; (a) then reads the bank's fp16 rows where they lie, no map.
 // Traffic of (a): C * D * 2 bytes of centroids per row block (from L2 after the first), 8 bytes written per row and split.
 // Measured on one MI355X (profiles/bank_compress_bench.json.log, tools/bench_bank_compress.py): 512 passages padded to 180 rows,
 // 61 250 kept rows, D 128, nbits 8, 65 536 centroids: rr_bank_add_compress 10.2 ms per call with its synchronisation, 10.12 ms on
@@ -113,6 +116,17 @@ __global__ __launch_bounds__(256) void compress_residual_kernel(const void* __re
     codes[r] = code;
     if (mask_bytes) mask_bytes[r] = mask[s] != 0.f ? 1 : 0;
   }
+}
+
+// the codes-only ending of the assignment (rr_launch_plaid_assign_codes): one thread per row, the maximum over the splits' keys as
+// compress_residual_kernel takes it, the int32 code, nothing else read or written
+__global__ __launch_bounds__(256) void compress_codes_kernel(const unsigned long long* __restrict__ keys, int splits, long long R, int C,
+                                                             int32_t* __restrict__ codes) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= R) return;
+  unsigned long long key = 0ull;
+  for (int s = 0; s < splits; ++s) key = key_max(key, keys[(size_t)s * (size_t)R + (size_t)r]);
+  codes[r] = (int)min(rank_key_index(key), (uint32_t)(C - 1));
 }
 
 // rr_set_tuning("compress_chunk"): the centroids of one split of the assignment kernel; 0: chosen by the launch (below)
@@ -209,5 +223,21 @@ hipError_t rr_launch_plaid_compress(const rr_padded_rows& in, long long base, lo
       hipLaunchKernelGGL((compress_residual_kernel<NB, false>), dim3((unsigned)blocks), dim3(256), 0, st, src, map, in.mask, R, D, lpr, rpw,
                          centroids, C, cutoffs, keys, pl.splits, codes, resid, mask_bytes);
   });
+  return hipGetLastError();
+}
+
+// The codes of R fp16 rows that lie back to back (an fp16 bank with a centroid table): compress_assign_kernel as above, without a
+// row map, then compress_codes_kernel.  The keys are the only intermediate: 8 bytes per row and split.
+hipError_t rr_launch_plaid_assign_codes(const uint16_t* rows_f16, long long R, int D, const uint16_t* centroids, int C, char* scratch,
+                                        const rr_compress_plan& pl, int32_t* codes, hipStream_t st) {
+  if (!rows_f16 || !centroids || !scratch || !codes || R <= 0 || pl.jt == 0 || D < 16 || D > 512 || D % 16 || C <= 0)
+    return hipErrorInvalidValue;
+  if (((((uintptr_t)rows_f16) | ((uintptr_t)centroids)) & 7) || (((uintptr_t)scratch) & 15) || (((uintptr_t)codes) & 3)) return hipErrorInvalidValue;
+  unsigned long long* keys = (unsigned long long*)(scratch + pl.keys_off);
+  const hipError_t e = assign_pick<true, false>(rows_f16, nullptr, R, D, centroids, C, pl, keys, nullptr, st);
+  if (e != hipSuccess) return e;
+  const long long blocks = (R + 255) / 256;
+  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(compress_codes_kernel, dim3((unsigned)blocks), dim3(256), 0, st, keys, pl.splits, R, C, codes);
   return hipGetLastError();
 }

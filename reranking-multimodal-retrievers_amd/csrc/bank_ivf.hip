@@ -407,14 +407,15 @@ void rr_ivf_free(rr_ivf* f) {
   *f = rr_ivf{};
 }
 
-// The inverted file over the P passages (first[i], len[i]) of a compressed bank (host table), into *out (which must be empty).  With
+// The inverted file over the P passages (first[i], len[i]) of a bank with codes (compressed, or fp16 rows with a centroid table: the
+// view's codes, mask and n_centroids are all that is read; host table), into *out (which must be empty).  With
 // `old`, a file over the first old->passages < P of them, the file is EXTENDED (rr_bank_extend_ivf): only the passages behind the
 // old ones are walked, and *old is read, never written.  On a failure nothing is left allocated and *out stays empty;
 // hipErrorOutOfMemory: an allocation failed.  Synchronises `st`.
 hipError_t rr_ivf_build(const rr_bank_view& bank, const int64_t* first, const int32_t* len, int P, hipStream_t st, rr_ivf* out, const rr_ivf* old,
                         const char** failed_step) {
   const int C = bank.n_centroids;
-  if (!bank.nbits || !bank.codes || !bank.mask || C < 1 || P < 1 || !first || !len || out->offsets || out->pids) return hipErrorInvalidValue;
+  if (!bank.codes || !bank.mask || C < 1 || P < 1 || !first || !len || out->offsets || out->pids) return hipErrorInvalidValue;
   if (old && (!old->offsets || !old->pids || old->passages < 1 || old->passages >= P || old->postings < 0)) return hipErrorInvalidValue;
   const int P0 = old ? old->passages : 0, N = P - P0;         // the passages P0 .. P - 1 are walked
   const int64_t* old_offsets = old ? old->offsets : nullptr;

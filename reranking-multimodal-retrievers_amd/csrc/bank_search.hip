@@ -46,7 +46,7 @@
 //     here and in plaid_list_select_kernel, see rank_order.h) has one possible result.  Survivors travel as indices; a pass reads
 //     their scores again from the score row.
 // LAUNCHERS: rr_launch_bank_search_scores and rr_launch_bank_search_scores_listed take an rr_bank_view (rr_common.h), fp16 or
-// compressed (the listed form: compressed only; pick_list or, given a candidate list, pick_via), rr_launch_bank_search_scores_places
+// compressed (the listed form too: pick_list or, given a candidate list, pick_via), rr_launch_bank_search_scores_places
 // (pick_places; fp16 or compressed), rr_launch_topk_select and rr_launch_topk_select_counted.  The
 // operand sources, the view-to-source dispatch (li_with_bank_source), the once-per-device LDS attribute (li_lds_attr) and the
 // width of the column block (li_pick_jt, here with a fixed 72 KB) live in li_sources.h, shared with li_scores.hip; the tile step
@@ -443,7 +443,8 @@ hipError_t rr_launch_bank_search_scores(const rr_bank_slot* table, int n, int nq
 }
 
 // the same MaxSim for the passages list[q][0 .. cnt[q]) (entries of table[0 .. n), cnt[q] <= list_ld) of every query q, written to
-// out[q][entry] of the dense [nq][n]; the rest of `out` is left as it is.  Compressed banks only (the pruned search is the caller).
+// out[q][entry] of the dense [nq][n]; the rest of `out` is left as it is.  The pruned search is the caller: a compressed bank, or
+// an fp16 bank with codes (the view's nbits == 0: li_src_f16, the rows rr_bank_search reads).
 // cand / cap null / 0: pick_list.  Given: pick_via, a list entry is a place in cand [nq][cap] and out the compact [nq][cap].
 hipError_t rr_launch_bank_search_scores_listed(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
                                                const rr_bank_view& bank, const int32_t* list, int list_ld, const int32_t* cnt,
@@ -452,10 +453,7 @@ hipError_t rr_launch_bank_search_scores_listed(const rr_bank_slot* table, int n,
     return hipErrorInvalidValue;
   auto with = [&](const auto& pick) {    // (a dispatch per picker: the kernels stay in the order the object had them in)
     return li_with_bank_source(nullptr, nullptr, bank, D, [&](const auto& src, size_t tile_bytes) -> hipError_t {
-      if constexpr (!std::decay_t<decltype(src)>::TILE)
-        return hipErrorInvalidValue;
-      else
-        return search_launch(query_li, src, table, n, nq, (list_ld + 3) / 4, pick, Lq, D, tile_bytes, out, st);
+      return search_launch(query_li, src, table, n, nq, (list_ld + 3) / 4, pick, Lq, D, tile_bytes, out, st);
     });
   };
   return !cand ? with(pick_list{list, list_ld, cnt}) : with(pick_via{list, list_ld, cnt, cand, cap});

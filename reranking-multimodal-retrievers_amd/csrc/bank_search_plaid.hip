@@ -1,6 +1,8 @@
 // PLAID-pruned top-k search over a range of a COMPRESSED passage bank (rr_bank_search_plaid, include/rerank_mi355.h): the staged
 // search of the reference (third_party/ColBERT/colbert/search/index_storage.py:86-184, candidate_generation.py) with every tie made
 // definite, from what a compressed bank already holds: one int32 centroid code per row, the fp16 centroid table, the passage table.
+// An fp16 bank that holds these too (rr_bank_set_centroids; the view's nbits == 0 with codes and centroids) runs the same stages; only
+// the exact stage reads rows, and it reads the bank's fp16 rows (rr_launch_bank_search_scores_listed decides by the view).
 // Two forms, one plan (rr_plaid_search_plan) and one stage driver (rr_launch_plaid_search_stage): rr_bank_search_plaid takes the
 // candidate set from one scan over the codes of the range, rr_bank_search_plaid_ivf from the bank's inverted file.  A call is a
 // HEAD of three stages, a CANDIDATE STEP of one stage (scan) or two (inverted file) that leaves A1 and A2 in two rows of `pitch`
@@ -361,7 +363,8 @@ rr_plaid_search_layout rr_plaid_search_plan(int nq, int n, int C, int Lq, int Lq
 hipError_t rr_launch_plaid_search_stage(int stage, const rr_plaid_search_args& a, const rr_plaid_search_layout& l, hipStream_t st) {
   const int C = a.bank.n_centroids;
   const bool ivf = l.stages == RR_PLAID_IVF_SEARCH_STAGES;
-  if (!a.scratch || !a.query_li || !a.table || !a.bank.nbits || !a.bank.codes || !a.bank.mask || !a.bank.centroids || C < 1 ||
+  // (a row source for the exact stage: residual codes, or the fp16 rows of a bank with a centroid table)
+  if (!a.scratch || !a.query_li || !a.table || (!a.bank.nbits && !a.bank.rows) || !a.bank.codes || !a.bank.mask || !a.bank.centroids || C < 1 ||
       C > RR_PLAID_SEARCH_MAX_CENTROIDS || a.nq < 1 || a.n < 1 || a.Lqc < 1 || a.Lqc > a.Lq || a.ncells < 1 || a.ncells > std::min(C, 16) ||
       a.ndocs < 4 || a.ndocs > LIST_MAX || a.k < 1 || a.k > l.k2 || !a.indices_out || !a.counts_out ||
       (l.stages != RR_PLAID_SEARCH_STAGES && !ivf) || l.pitch != (ivf ? l.cap : a.n) || l.k1 < 1 || l.k1 > l.pitch ||

@@ -102,6 +102,8 @@ struct li_src_plaid {
 
 // f(source, tile_bytes) over the rows of `bank`; tile_bytes: the decoded tiles of the four waves behind the query block (0 for
 // fp16 rows).  16-byte query loads are the caller's check; here: 8-byte loads of fp16 rows, plaid_tables_ok of compressed ones.
+// nbits == 0 is the fp16 source whether or not the view also carries codes and a centroid table (rr_bank_set_centroids): the codes
+// are the pruned stages' business, the rows scored are the fp16 rows.
 template <class F>
 hipError_t li_with_bank_source(const rr_bank_pair* pairs, const int32_t* slot, const rr_bank_view& bank, int D, F&& f) {
   if (D <= 0 || D % 16 || !bank.mask) return hipErrorInvalidValue;

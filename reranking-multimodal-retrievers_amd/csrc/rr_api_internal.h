@@ -161,6 +161,10 @@ struct rr_bank {
   uint16_t* centroids = nullptr;
   float* weights = nullptr;
   size_t resid_row_bytes() const { return (size_t)D / 8 * (size_t)nbits; }
+  // an fp16 bank that rr_bank_set_centroids gave a table: nbits == 0, `rows` AND codes [capacity_rows] / centroids / n_centroids
+  // (no resid, no weights); has_codes(): what the pruned searches and the inverted file ask of a bank
+  bool coded() const { return !nbits && codes != nullptr; }
+  bool has_codes() const { return nbits != 0 || codes != nullptr; }
   std::vector<int64_t> first;
   std::vector<int32_t> len;
   // the device copy of (first, len) that rr_bank_search's kernel walks: 16 bytes per passage, allocated and brought up to date

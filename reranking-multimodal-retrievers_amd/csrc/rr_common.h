@@ -457,7 +457,9 @@ hipError_t rr_launch_bank_ingest(const rr_padded_rows& in, int D, uint16_t* rows
 // The context rows of a bank as the launchers take them, fp16 or compressed (PLAID residual codes): nbits == 0: `rows` [.][D] fp16
 // bits; else codes [.] int32, resid [.][D * nbits / 8], centroids [n_centroids][D] fp16 bits, weights [2^nbits] float32.  mask:
 // one byte per row.  All on the device.  bank_api.hip builds it from an rr_bank (bank_view), the diagnostic operators from their
-// loose pointers; every launcher below decides between the two kinds inside.
+// loose pointers; every launcher below decides between the two kinds inside.  nbits == 0 with non-null codes and centroids: fp16
+// rows WITH codes (rr_bank_set_centroids): a row source reads `rows` as of any fp16 bank, the pruned stages and the inverted file
+// read codes / centroids / n_centroids as of a compressed bank.
 struct rr_bank_view {
   int nbits, n_centroids;
   const uint16_t* rows;
@@ -512,7 +514,7 @@ struct rr_passage_filter {
 hipError_t rr_launch_bank_search_scores(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
                                         const rr_bank_view& bank, const rr_passage_filter& filter, float* out, hipStream_t st);
 // the same for the passages list[q][0 .. cnt[q]) of every query (cnt[q] <= list_ld; entries of table[0 .. n)), written to the
-// passage's entry of the dense out [nq][n]; compressed banks only.  With cand (cap > 0; or null and 0) for the passages
+// passage's entry of the dense out [nq][n]; fp16 rows or compressed.  With cand (cap > 0; or null and 0) for the passages
 // cand[q][list[q][i]], i < cnt[q]: a list entry is a PLACE in the query's candidate list cand [nq][cap] (entries of table[0 .. n)),
 // and the score goes to that place of the compact out [nq][cap] (rr_bank_search_plaid_ivf)
 hipError_t rr_launch_bank_search_scores_listed(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li,
@@ -669,6 +671,11 @@ rr_compress_plan rr_plaid_compress_plan(long long R, int C, int D);
 hipError_t rr_launch_plaid_compress(const rr_padded_rows& in, long long base, long long R, int D, int nbits, const uint16_t* centroids, int C,
                                     const float* cutoffs, char* scratch, const rr_compress_plan& pl, int32_t* codes, uint8_t* resid,
                                     uint8_t* mask_bytes, hipStream_t st);
+// The codes alone (rr_bank_set_centroids, rr_bank_add on an fp16 bank with a centroid table): the assignment kernel over the R fp16
+// rows that lie back to back at rows_f16 (the caller's first row; 64-bit offsets inside), then the maximum over the splits' keys as
+// the int32 code, 4 bytes a row.  No residual is formed.  scratch: pl.total bytes (the map part unused); codes: the first row's.
+hipError_t rr_launch_plaid_assign_codes(const uint16_t* rows_f16, long long R, int D, const uint16_t* centroids, int C, char* scratch,
+                                        const rr_compress_plan& pl, int32_t* codes, hipStream_t st);
 // rr_util_plaid_compress_rows: the definition in host code (passage_bank.hip, beside the host decoder)
 bool rr_plaid_compress_rows_host(const void* rows, int rows_f16, long long n_rows, int D, const uint16_t* centroids, int C,
                                  const float* cutoffs, int nbits, int32_t* codes_out, uint8_t* resid_out);

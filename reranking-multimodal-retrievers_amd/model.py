@@ -188,13 +188,22 @@ def _ptrs(out: dict) -> list:
     return [L.ptr(out[k]) for k in ("logits", "logits2", "loss", "scores", "order") if k in out]
 
 
-def _bank_search_args(eng, name: str, bank, query_li: torch.Tensor, first: int, count: Optional[int], compressed_only: bool = False):
+def _bank_centroids(bank) -> int:
+    """The centroids a bank's codes index: a compressed bank's codec's, an fp16 bank's table's (PassageBank.set_centroids); 0: no codes."""
+    n = getattr(bank, "n_centroids", None)
+    if n is None:
+        codec = getattr(bank, "codec", None)
+        n = 0 if codec is None else codec.n_centroids
+    return int(n)
+
+
+def _bank_search_args(eng, name: str, bank, query_li: torch.Tensor, first: int, count: Optional[int], needs_codes: bool = False):
     """What RerankEngine.bank_search and bank_search_plaid (`name`) check and prepare alike: (first, n, n_queries, Lq, the queries
     as contiguous float32 on the engine's device)."""
     D = eng.arch["li_dim"]
     if query_li.dim() != 3 or query_li.shape[2] != D:
         raise ValueError(f"query_li {tuple(query_li.shape)}: [n_queries, Lq, {D}]")
-    if compressed_only and getattr(bank, "codec", None) is None:
+    if needs_codes and not _bank_centroids(bank):      # a compressed bank, or an fp16 bank with a centroid table
         raise NotImplementedError(f"{name}: an fp16 bank (the pruned search reads the centroid codes of a compressed bank)")
     held = len(bank)
     first = int(first)
@@ -241,14 +250,14 @@ def _bank_search_plaid(eng, entry: str, bank, query_li: torch.Tensor, k: int, *,
                        coarse_tokens: Optional[int] = None, first: int = 0, count: Optional[int] = None, filter=None) -> dict:
     """RerankEngine.bank_search_plaid and bank_search_plaid_ivf, and their filtered entries (`filter`: a BankFilter): the checks
     before the library, the outputs, the call of `entry`."""
-    first, n, nq, Lq, q = _bank_search_args(eng, "bank_search_plaid", bank, query_li, first, count, compressed_only=True)
-    codec = bank.codec
+    first, n, nq, Lq, q = _bank_search_args(eng, "bank_search_plaid", bank, query_li, first, count, needs_codes=True)
+    n_centroids = _bank_centroids(bank)
     Lqc = Lq if coarse_tokens is None else int(coarse_tokens)
     if Lqc < 1 or Lqc > Lq:
         raise ValueError(f"bank_search_plaid: coarse_tokens = {Lqc} of {Lq} query tokens")
     ncells, ndocs, k = int(ncells), int(ndocs), int(k)
-    if ncells < 1 or ncells > codec.n_centroids:
-        raise ValueError(f"bank_search_plaid: ncells = {ncells} of {codec.n_centroids} centroids")
+    if ncells < 1 or ncells > n_centroids:
+        raise ValueError(f"bank_search_plaid: ncells = {ncells} of {n_centroids} centroids")
     if ncells > 16:
         raise NotImplementedError(f"bank_search_plaid: ncells = {ncells} (at most 16)")
     if ndocs < 4:
@@ -819,15 +828,18 @@ class RerankEngine:
         out.update(extra)
         return out
 
-    def create_bank(self, capacity_rows: int, max_passages: int, codec=None):
+    def create_bank(self, capacity_rows: int, max_passages: int, codec=None, centroids=None):
         """A device-resident passage-embedding bank (rr_bank_create; passage_bank.PassageBank) of `capacity_rows` token rows
         and at most `max_passages` passages on this engine's device with its li_dim.  It outlives the engine and serves every
         interaction engine of the device with the same li_dim (NORMAL and MORES).  `codec` (passage_bank.PlaidCodec): a
         compressed bank (rr_bank_create_plaid) that holds the residual codes of a ColBERTv2 / PLAID index and decodes them in the
         forward; filled with add_compressed / load_plaid_index, or, when the codec carries its bucket cutoffs (they are set on the
-        bank here, rr_bank_set_plaid_cutoffs), from embeddings on the device with add_compress."""
+        bank here, rr_bank_set_plaid_cutoffs), from embeddings on the device with add_compress.  `centroids` ([C, li_dim], e.g.
+        PlaidCodec.train(...).centroids; not with `codec`): an fp16 bank with a centroid table (PassageBank.set_centroids,
+        rr_bank_set_centroids): it keeps the fp16 rows, every `add` assigns a centroid code per row on the device, and the pruned
+        searches, the inverted file and the filters take it as they take a compressed bank."""
         from .passage_bank import PassageBank
-        return PassageBank(self, capacity_rows, max_passages, codec)
+        return PassageBank(self, capacity_rows, max_passages, codec, centroids=centroids)
 
     def forward_interaction_bank(self, bank, query_li: torch.Tensor, query_mask: torch.Tensor, passage_ids, Bq: int, K: int,
                                  labels: Optional[torch.Tensor] = None, list_sizes: Optional[Sequence[int]] = None,
@@ -962,7 +974,7 @@ class RerankEngine:
         return _bank_search_plaid(self, "rr_bank_search_plaid_ivf_filtered", bank, query_li, k, filter=filter, **kw)
 
     def bank_build_ivf(self, bank) -> dict:
-        """Build, or rebuild, the inverted file of a COMPRESSED `bank` over every passage it holds now (rr_bank_build_ivf; per
+        """Build, or rebuild, the inverted file of a COMPRESSED `bank` (or an fp16 one with a centroid table) over every passage it holds now (rr_bank_build_ivf; per
         centroid the sorted unique passages with an unmasked token of that code, the reference's ivf.pid.pt).  A load-time call
         on this engine's current stream: it allocates and synchronises.  Returns bank.ivf_info()."""
         return bank.build_ivf()
@@ -993,7 +1005,7 @@ class RerankEngine:
 
     def bank_search_plaid(self, bank, query_li: torch.Tensor, k: int, *, ncells: int, centroid_score_threshold: float, ndocs: int,
                           coarse_tokens: Optional[int] = None, first: int = 0, count: Optional[int] = None) -> dict:
-        """PLAID's pruned top-k search over a COMPRESSED `bank` (rr_bank_search_plaid; the reference's
+        """PLAID's pruned top-k search over a COMPRESSED `bank`, or an fp16 one with a centroid table (rr_bank_search_plaid; the reference's
         colbert/search/index_storage.py:86-184): per query the cells of the first `coarse_tokens` query tokens (None: all) give
         the candidates, two centroid-only passes keep `ndocs` and then ndocs // 4 of them, and the survivors get the exact MaxSim
         of bank_search.  {"indices": int32 [n_queries, k] dense bank indices, -1 behind the count; "scores": float32
@@ -1468,10 +1480,10 @@ class InteractionRerankModel(_DropIn):
         if state_dict is not None:
             self.engine.load_state_dict(state_dict)
 
-    def create_bank(self, capacity_rows: int, max_passages: int, codec=None):
-        """Give the model a passage-embedding bank (RerankEngine.create_bank; `codec`: a compressed one) and return it; `bank` may also be assigned a bank
+    def create_bank(self, capacity_rows: int, max_passages: int, codec=None, centroids=None):
+        """Give the model a passage-embedding bank (RerankEngine.create_bank; `codec`: a compressed one; `centroids`: an fp16 one with a centroid table) and return it; `bank` may also be assigned a bank
         another model of the same device and li_dim created."""
-        self.bank = self.engine.create_bank(capacity_rows, max_passages, codec)
+        self.bank = self.engine.create_bank(capacity_rows, max_passages, codec, centroids=centroids)
         return self.bank
 
     def forward_passages(self, query_late_interaction, query_mask, passage_ids, num_negative_examples, labels=None,
@@ -1508,7 +1520,7 @@ class InteractionRerankModel(_DropIn):
     def retrieve(self, query_late_interaction, k: int, plaid=None, allowed=None, excluded=None, filter=None, sparse: bool = False, **kw):
         """The k best passages of `self.bank` per query by the frozen retriever's MaxSim, every passage scored
         (PassageBank.search): (passage_ids: one list per query, best first; scores float32 [n_queries, k] on the device).
-        `plaid` (a PlaidSearch): PLAID's pruned search over a compressed bank instead; a query's list may then be shorter than k.
+        `plaid` (a PlaidSearch): PLAID's pruned search over a compressed bank, or an fp16 bank with a centroid table, instead; a query's list may then be shorter than k.
         `allowed` / `excluded` (passage ids: a flat sequence for every query, or a list of lists, one per query), or `filter` (a
         BankFilter built by bank.filter): only the allowed passages compete (the reference's filter_fn); one of the three at most.
         A query's list then has its true length, at most k.  `sparse` (with one of the three, without `plaid`; ValueError

@@ -37,6 +37,11 @@ index stores it.  With it a compressed bank is built from a retriever's embeddin
 (`export_compressed`: the unmasked rows of a range back to back, compacted by a kernel); `load_plaid_index(..., ivf=True)` brings the
 directory back with its inverted file (`load_ivf`, rr_bank_load_ivf) instead of rebuilding it.
 
+An fp16 bank WITH A CENTROID TABLE (`create_bank(..., centroids=)`, `PassageBank.set_centroids`; rr_bank_set_centroids) keeps its fp16
+rows and holds one centroid code per row beside them, assigned on the device by every `add`: the pruned searches, the inverted file,
+the filters, `remove` and the sharded search take it as they take a compressed bank, with the exact stage on the fp16 rows; there
+are no residuals, so `save_plaid_index` / `export_compressed` refuse it.  `PassageBank.codes` reads a passage's codes.
+
 `search_banks` searches several banks of one process as one (every bank searched, the k-lists merged on the device over global
 indices by rr_bank_merge_topk); a bank split over RANKS is sharding.ShardedBank.
 
@@ -571,18 +576,22 @@ def write_plaid_index(index_path: str, codec: "PlaidCodec", chunks, *, ivf=None,
 class PassageBank:
     """A device store of passage token embeddings under the caller's ids (`add`, `remove`): fp16 rows, or with a `codec` (PlaidCodec)
     the residual codes of a ColBERTv2 / PLAID index, decoded on the device in every forward; one mask byte per row either way.
+    With `centroids` (no codec): fp16 rows and a centroid code per row beside them (`set_centroids`).
     Created by RerankEngine.create_bank; usable by every interaction engine of the same device and li_dim."""
 
     generation = 0                           # incremented by `remove` and by `clear`: dense indices from before (a BankFilter's) are stale
 
-    def __init__(self, engine, capacity_rows: int, max_passages: int, codec: Optional[PlaidCodec] = None):
+    def __init__(self, engine, capacity_rows: int, max_passages: int, codec: Optional[PlaidCodec] = None, centroids=None):
         from . import _lib as L
+        if codec is not None and centroids is not None:
+            raise ValueError("give a codec (a compressed bank) or centroids (an fp16 bank with a centroid table), not both")
         self._L, self.lib = L, engine.lib
         self.device, self.li_dim = engine.device, int(engine.arch["li_dim"])
         self.table = BankTable()
         self.padded_len = 0                  # the longest Lc (compressed: passage) an add has seen, a high-water mark that `remove`
                                              # and `clear` never lower: a forward's default padded length
         self.codec = codec
+        self._centroids = None               # an fp16 bank's centroid table (set_centroids), host fp16 [C, D]
         h = C.c_void_p()
         if codec is None:
             L.check(self.lib.rr_bank_create(engine.h, int(capacity_rows), int(max_passages), C.byref(h)), engine.h, "rr_bank_create")
@@ -598,6 +607,46 @@ class PassageBank:
         if codec is not None and codec.bucket_cutoffs is not None:
             self._check(self.lib.rr_bank_set_plaid_cutoffs(h, codec.bucket_cutoffs.data_ptr()), "rr_bank_set_plaid_cutoffs",
                         bad_shape=ValueError)
+        if centroids is not None:
+            self.set_centroids(centroids)
+
+    @property
+    def centroids(self):
+        """The centroid table the bank's codes index, host fp16 [C, D]: the codec's of a compressed bank, the one `set_centroids`
+        gave an fp16 bank; None for an fp16 bank without one."""
+        return self.codec.centroids if self.codec is not None else getattr(self, "_centroids", None)
+
+    @property
+    def n_centroids(self) -> int:
+        """The rows of `centroids`; 0 for an fp16 bank without a table (which the pruned searches and the inverted file refuse)."""
+        c = self.centroids
+        return 0 if c is None else int(c.shape[0])
+
+    def set_centroids(self, centroids) -> None:
+        """Give an fp16 bank a centroid table (rr_bank_set_centroids): `centroids` [C, li_dim], 1 <= C <= 262144 (kept as fp16;
+        PlaidCodec.train(...).centroids fits).  Every row the bank holds is assigned its code on the device now (the code of the
+        compressed row, include/rerank_mi355.h: for equal rows the codes `add_compress` writes), and every later `add` assigns
+        the codes of its rows behind the ingest.  Called again it replaces the table, assigns every row anew and drops the
+        inverted file.  A load-time call: it allocates and synchronises the current stream.  A compressed bank and an li_dim
+        that is no multiple of 16 raise NotImplementedError, a table of another shape or size ValueError, a failed allocation
+        MemoryError; the bank is unchanged then."""
+        import torch
+        if self.codec is not None:
+            raise NotImplementedError("set_centroids on a compressed bank: its codes belong to its residuals (the codec holds the table)")
+        cen = torch.as_tensor(centroids).detach().to(device="cpu", dtype=torch.float16).contiguous()
+        if cen.dim() != 2 or cen.shape[1] != self.li_dim:
+            raise ValueError(f"centroids must be [C, {self.li_dim}], got {tuple(cen.shape)}")
+        self._check(self.lib.rr_bank_set_centroids(self.h, cen.data_ptr(), int(cen.shape[0]), self._stream()), "rr_bank_set_centroids",
+                    bad_shape=ValueError)
+        self._centroids = cen
+
+    def codes(self, passage_id):
+        """The centroid codes of one passage on the host, int32 [len] (rr_bank_read_codes; synchronises the current stream), of a
+        compressed bank or an fp16 bank with a centroid table; NotImplementedError for an fp16 bank without one."""
+        import torch
+        if not self.n_centroids:
+            raise NotImplementedError("codes on an fp16 bank without a centroid table: it holds no codes (set_centroids)")
+        return self._read("rr_bank_read_codes", passage_id, ((), torch.int32))[0]
 
     def __del__(self):
         self.close()
@@ -807,6 +856,9 @@ class PassageBank:
     def _export_sizes(self, first: int, n: int):
         """The sizing call of rr_bank_export_plaid: (doclens list, R)."""
         import numpy as np
+        if self.codec is None and self.n_centroids:
+            raise NotImplementedError("export_compressed on an fp16 bank with a centroid table: it holds codes but no residuals; "
+                                      "add_compress into a compressed bank (create_bank(codec=...)) writes them")
         if self.codec is None:
             raise NotImplementedError("export_compressed on an fp16 bank: it holds no codes")
         doclens = np.empty(max(n, 1), dtype=np.int32)
@@ -840,6 +892,9 @@ class PassageBank:
         represented (an index's doclens are at least 1) and raises ValueError naming up to eight ids, with nothing written.  An
         fp16 bank raises NotImplementedError, a codec without cutoffs PlaidCodec.save's ValueError, an empty bank ValueError.
         Returns metadata.json's dict."""
+        if self.codec is None and self.n_centroids:
+            raise NotImplementedError("save_plaid_index on an fp16 bank with a centroid table: an index stores residuals, which it does "
+                                      "not hold; add_compress into a compressed bank (create_bank(codec=...)) and save that one")
         if self.codec is None:
             raise NotImplementedError("save_plaid_index on an fp16 bank: it holds no codes")
         if self.codec.bucket_cutoffs is None:
@@ -941,7 +996,7 @@ class PassageBank:
         """The k best passages per query by the retriever's MaxSim, every passage of the bank scored (engine.bank_search;
         `first` / `count`: a range of dense indices).  Returns (passage_ids, scores): passage_ids[q] the ids of query q best
         first, scores float32 [n_queries, k] on the device.  Copies the indices to the host (synchronises).
-        With `plaid` (a PlaidSearch; compressed banks) the pruned search runs instead (engine.bank_search_plaid): passage_ids[q]
+        With `plaid` (a PlaidSearch; compressed banks and fp16 banks with a centroid table) the pruned search runs instead (engine.bank_search_plaid): passage_ids[q]
         has its true length, at most k (a query may find fewer candidates, or none), and scores holds -inf behind it.  A
         PlaidSearch with ivf=True takes the candidates from the inverted file (build_ivf first): the same result.
         With `filter` (a BankFilter, `filter`) only the passages it allows compete, in the exact and in the pruned search
@@ -982,7 +1037,7 @@ class PassageBank:
         unique passages (dense indices) with an unmasked token of that code.  On the device; a load-time call that allocates and
         synchronises the current stream.  Passages added later are not covered until the next build; `clear` drops the file.
         Returns ivf_info().  An fp16 bank raises NotImplementedError, a failed allocation MemoryError with the previous file kept."""
-        if self.codec is None:
+        if not self.n_centroids:
             raise NotImplementedError("build_ivf on an fp16 bank: it holds no centroid codes")
         self._check(self.lib.rr_bank_build_ivf(self.h, self._stream()), "rr_bank_build_ivf", bad_shape=ValueError)
         return self.ivf_info()
@@ -994,7 +1049,7 @@ class PassageBank:
         allocated or synchronised); without a file the call is build_ivf.  A load-time call otherwise: it allocates the new file
         beside the old one and synchronises the current stream.  tools/bench_bank_ivf_extend.py times it against build_ivf.
         Returns ivf_info().  An fp16 bank raises NotImplementedError, a failed allocation MemoryError with the previous file kept."""
-        if self.codec is None:
+        if not self.n_centroids:
             raise NotImplementedError("extend_ivf on an fp16 bank: it holds no centroid codes")
         self._check(self.lib.rr_bank_extend_ivf(self.h, self._stream()), "rr_bank_extend_ivf", bad_shape=ValueError)
         return self.ivf_info()
@@ -1013,7 +1068,7 @@ class PassageBank:
         info = self.ivf_info()
         if not info["passages_covered"]:
             raise ValueError("ivf: the bank has no inverted file (build_ivf)")
-        offsets = torch.empty(self.codec.n_centroids + 1, dtype=torch.int64)
+        offsets = torch.empty(self.n_centroids + 1, dtype=torch.int64)
         pids = torch.empty(info["postings"], dtype=torch.int32)
         self._check(self.lib.rr_bank_ivf_read(self.h, offsets.data_ptr(), pids.data_ptr() if pids.numel() else None, self._stream()),
                     "rr_bank_ivf_read")
@@ -1037,7 +1092,7 @@ class PassageBank:
         import os
 
         import torch
-        if self.codec is None:
+        if not self.n_centroids:
             raise NotImplementedError("load_ivf on an fp16 bank: it holds no centroid codes")
         pair = path_or_pair
         if isinstance(pair, (str, os.PathLike)):
@@ -1049,8 +1104,8 @@ class PassageBank:
         pids, lengths = pair
         pids = torch.as_tensor(pids).detach().to(device="cpu", dtype=torch.int32).reshape(-1).contiguous()
         lengths = torch.as_tensor(lengths).detach().to(device="cpu", dtype=torch.int64).reshape(-1)
-        if lengths.numel() != self.codec.n_centroids:
-            raise ValueError(f"load_ivf: {lengths.numel()} lists, the codec holds {self.codec.n_centroids} centroids")
+        if lengths.numel() != self.n_centroids:
+            raise ValueError(f"load_ivf: {lengths.numel()} lists, the codec holds {self.n_centroids} centroids")
         offsets = torch.zeros(lengths.numel() + 1, dtype=torch.int64)
         offsets[1:] = torch.cumsum(lengths, 0)
         if int(offsets[-1]) != pids.numel():

@@ -385,7 +385,8 @@ class ShardedBank:
     (all_gather_object) into the global id table `ids`, and records the bank's `generation` (raised by PassageBank.remove and by
     PassageBank.clear); call it again after adds, after a removal (each rank removes locally, then all refresh) and after a clear:
     until then a search raises, also when the bank has been refilled to its old count.  `search` is the local search plus the
-    exchange.  The queries are the caller's to replicate: every rank passes the same `query_li`."""
+    exchange.  The queries are the caller's to replicate: every rank passes the same `query_li`.  A pruned search (`plaid`) needs
+    codes on every rank: compressed banks, or fp16 banks with a centroid table (PassageBank.set_centroids), each rank's its own."""
 
     def __init__(self, bank, group=None):
         self.bank, self.group = bank, group

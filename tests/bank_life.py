@@ -11,6 +11,11 @@ the mutators of PassageBank and predict what they return and leave behind (inclu
 unchanged; REMOVING PASSAGES; THE INVERTED FILE, LIFETIME).  `expected_ivf` is the definition of the file (ivf_numpy of
 tests/test_bank_ivf_cpu.py) over the covered prefix.
 
+The kind `coded` is an fp16 bank with a centroid table (rr_bank_set_centroids): its passages hold fp16 row bits and, under each of the
+two tables of `tables()`, the codes of their rows (`codes2` int32 [2, len]: a float64 argmax with an asserted margin, _coded_rows).
+It has nbits 0 and so `info()` of an fp16 bank, but it holds codes: the file motifs apply to it, and its scripts have the operation
+set_centroids, which switches to the other table (the codes switch, the file goes, the generation stays).
+
 `script(seed, kind, steps)` draws a deterministic list of operations with numpy.random.default_rng.  The operations are drawn as
 short motifs (a search, a removal, an add; an add, an extend, a removal inside the prefix; ...) so that the situations the tests
 count occur within 40 steps; which of them occurred is counted by tests/test_bank_life_cpu.py, not assumed here.  The capacity is
@@ -27,7 +32,9 @@ from test_gpu_bank_search_plaid import _codec, _topic_rows
 
 D = 64
 C_CENTROIDS = 16
-KINDS = {"fp16": 0, "plaid2": 2, "plaid8": 8}              # kind -> nbits (0: an fp16 bank); residual rows of 16 and 64 bytes
+KINDS = {"fp16": 0, "plaid2": 2, "plaid8": 8, "coded": 0}  # kind -> nbits (0: an fp16 bank); residual rows of 16 and 64 bytes
+STREAMS = {"fp16": 0, "plaid2": 1, "plaid8": 2, "coded": 3}         # the generator's stream of a kind: fixed, so that a new kind leaves the others' scripts alone
+TABLE_SIZES = (16, 12)                                     # the two centroid tables a coded bank switches between (set_centroids)
 TARGET_ROWS, TARGET_SLOTS = 1200, 48                       # what the generator fills up to; capacity() is what a script reached
 MAX_ADD = 12
 FULLY_MASKED = 5                                           # the serial number of the passage without an unmasked row
@@ -47,6 +54,33 @@ def codec_of(kind):
     return PlaidCodec(base.centroids, base.bucket_weights, nbits, bucket_cutoffs=cutoffs)
 
 
+def holds_codes(kind):
+    """A compressed bank, or an fp16 bank with a centroid table (a "coded" one): what the inverted file and the pruned searches need."""
+    return bool(KINDS[kind]) or kind == "coded"
+
+
+@functools.lru_cache(maxsize=None)
+def tables():
+    """The two tables of the coded kind, host fp16 [16, D] and [12, D]: unit centroids, unrelated to one another."""
+    return tuple(_codec(D, 8, n, seed=40 + i).centroids.half() for i, n in enumerate(TABLE_SIZES))
+
+
+def _coded_rows(n, gen):
+    """fp16 rows [n, D] near one centroid of EACH table (as via="add_compress" draws x near one), and their codes under both tables,
+    int32 [2, n]: the first maximum of the float64 product with the fp16 row, asserted to lead the second best by a margin (as
+    _assert_exact_input), so that the code hangs on no order of a float32 sum and owes nothing to the library."""
+    cens = [t.double() for t in tables()]
+    picks = [torch.randint(0, len(c), (n,), generator=gen) for c in cens]
+    x = sum(c[p].float() for c, p in zip(cens, picks)) + 0.5 * torch.randn(n, D, generator=gen) / D ** 0.5
+    rows = torch.nn.functional.normalize(x, dim=-1).half()
+    codes = []
+    for c in cens:
+        top =(rows.double() @ c.T).topk(2, dim=1)
+        assert float((top.values[:, 0] - top.values[:, 1]).min()) > 1e-3, "two centroids nearly tie for a row"
+        codes.append(top.indices[:, 0].to(torch.int32).numpy())
+    return rows.view(torch.int16).numpy(), np.stack(codes)
+
+
 def _mask_of(serial, length):
     """Every third passage of three rows or more has interior masked rows; one passage has no unmasked row at all."""
     m = np.ones(length, dtype=np.uint8)
@@ -64,7 +98,9 @@ def make_passages(kind, ids, lens, serial0, seed, via="add"):
     codec = codec_of(kind)
     out, r0 = [], 0
     gen = torch.Generator().manual_seed(int(seed))
-    if codec is None:
+    if kind == "coded":
+        rows, codes2 = _coded_rows(sum(lens), gen)
+    elif codec is None:
         rows = torch.nn.functional.normalize(torch.randn(sum(lens), D, generator=gen), dim=-1).half().view(torch.int16).numpy()
     elif via == "add_compress":
         cen = codec.centroids.float()
@@ -79,6 +115,8 @@ def make_passages(kind, ids, lens, serial0, seed, via="add"):
         p = dict(id=pid, length=int(ln), mask=_mask_of(serial0 + i, ln))
         if codec is None:
             p["rows"] = rows[r0:r0 + ln].copy()
+            if kind == "coded":
+                p["codes2"] = codes2[:, r0:r0 + ln].copy()
         elif via == "add_compress":
             p["x"] = x[r0:r0 + ln].copy()
         else:
@@ -113,6 +151,9 @@ def materialise(ops, compress):
 class Shadow:
     def __init__(self, kind, capacity_rows, max_passages):
         self.kind, self.nbits = kind, KINDS[kind]
+        self.coded = kind == "coded"
+        self.has_codes = holds_codes(kind)
+        self.table = 0                       # which of tables() a coded bank holds
         self.capacity_rows, self.max_passages = int(capacity_rows), int(max_passages)
         self.passages = []
         self.covered = 0                     # passages the inverted file covers; 0: no file
@@ -178,13 +219,26 @@ class Shadow:
         self.table_current = False
         return dict(new_index=new_index, passages=len(keep), rows_freed=freed)
 
+    @property
+    def n_centroids(self):
+        return TABLE_SIZES[self.table] if self.coded else C_CENTROIDS
+
+    def codes_of(self, p):
+        return p["codes2"][self.table] if self.coded else p["codes"]
+
+    def set_centroids(self, table):
+        """A coded bank takes table `table` of tables(): every row is assigned anew and the inverted file is dropped; the passages,
+        the generation (a filter stays valid) and the searches' device table are as they were."""
+        assert self.coded
+        self.table, self.covered = int(table), 0
+
     def build_ivf(self):
-        assert self.nbits and len(self)
+        assert self.has_codes and len(self)
         self.covered = len(self)
 
     def extend_ivf(self):
         """True when there was something to do (a file over fewer passages than held, or none: then the call is the build)."""
-        assert self.nbits and len(self)
+        assert self.has_codes and len(self)
         work = self.covered < len(self)
         self.covered = len(self)
         return work
@@ -205,8 +259,8 @@ class Shadow:
         """(codes, residuals, mask, lengths) of passages first .. first + count - 1, rows back to back."""
         ps = self.passages[first:None if count is None else first + count]
         rb = D * self.nbits // 8
-        codes = np.concatenate([p["codes"] for p in ps]) if ps else np.zeros(0, dtype=np.int32)
-        res = np.concatenate([p["res"] for p in ps]) if ps else np.zeros((0, rb), dtype=np.uint8)
+        codes = np.concatenate([self.codes_of(p) for p in ps]) if ps else np.zeros(0, dtype=np.int32)
+        res = np.concatenate([p["res"] for p in ps]) if ps and self.nbits else np.zeros((sum(p["length"] for p in ps), rb), dtype=np.uint8)
         mask = np.concatenate([p["mask"] for p in ps]) if ps else np.zeros(0, dtype=np.uint8)
         return codes, res, mask, [p["length"] for p in ps]
 
@@ -220,7 +274,7 @@ class Shadow:
         """(pids int32 [postings], lengths int64 [C]) of the file over the covered prefix, as PassageBank.ivf returns them."""
         assert self.covered
         codes, _, mask, lens = self.concat(0, self.covered)
-        offsets, pids = ivf_numpy(codes, mask, lens, C_CENTROIDS)
+        offsets, pids = ivf_numpy(codes, mask, lens, self.n_centroids)
         return pids, np.diff(offsets)
 
 
@@ -230,7 +284,7 @@ def expected_ivf(shadow):
 
 
 # ---- the script generator ---------------------------------------------------------------------------------------------------------------
-_MOTIFS = [                                                # (weight, operations, compressed banks only)
+_MOTIFS = [                                                # (weight, operations, False: any bank / True: banks with codes / "coded")
     (20, ["add"], False), (8, ["remove"], False), (6, ["search"], False), (4, ["add_refused"], False), (1, ["clear"], False),
     (6, ["extend_ivf"], True), (3, ["build_ivf"], True),
     (4, ["remove", "remove"], False),
@@ -244,6 +298,11 @@ _MOTIFS = [                                                # (weight, operations
     (7, ["fill", "remove", "add"], False),
     (3, ["stale_filter", "remove"], False),
     (2, ["stale_filter", "clear", "add", "add"], False),
+    (4, ["file", "set_centroids", "search"], "coded"),
+    (4, ["set_centroids", "add", "build_ivf"], "coded"),
+    (4, ["file", "add", "set_centroids", "extend_ivf"], "coded"),
+    (3, ["set_centroids", "remove", "set_centroids"], "coded"),
+    (3, ["stale_filter", "set_centroids"], "coded"),
 ]
 _SHAPE_WEIGHTS = dict(leading=2, trailing=2, interior=4, any=3, behind_prefix=1, whole_prefix=0.5, everything=0.3)
 
@@ -284,12 +343,12 @@ def _coins(rows, most):
 @functools.lru_cache(maxsize=None)
 def script(seed, kind, steps=40, prefix="p"):
     """`steps` operations: dicts with "op" in add (passages, via: add / add_compressed / add_compress), add_refused (passages),
-    remove (ids, shape), build_ivf, extend_ivf, clear, search, stale_filter.  Deterministic in (seed, kind, steps, prefix)."""
-    rng = np.random.default_rng([int(seed), sorted(KINDS).index(kind)])
-    compressed = bool(KINDS[kind])
+    remove (ids, shape), build_ivf, extend_ivf, clear, search, stale_filter, set_centroids (table; the coded kind).  Deterministic in (seed, kind, steps, prefix)."""
+    rng = np.random.default_rng([int(seed), STREAMS[kind]])
+    compressed, files, coded = bool(KINDS[kind]), holds_codes(kind), kind == "coded"
     sh = Shadow(kind, 1 << 40, 1 << 40)                    # ids, lengths and coverage; the targets bound the adds
     ops, queue, gone, serial = [], [], [], [0]
-    motifs = [m for m in _MOTIFS if compressed or not m[2]]
+    motifs = [m for m in _MOTIFS if m[2] is False or (m[2] is True and files) or (m[2] == "coded" and coded)]
     weights = np.array([m[0] for m in motifs], dtype=np.float64)
     compress_left = [compressed]
 
@@ -374,6 +433,9 @@ def script(seed, kind, steps=40, prefix="p"):
             gone.extend(sh.ids)
             sh.clear()
             ops.append(dict(op="clear"))
+        elif what == "set_centroids":
+            ops.append(dict(op="set_centroids", table=1 - sh.table))
+            sh.set_centroids(1 - sh.table)
         elif what == "add_refused":
             ops.append(dict(op="add_refused", how="rows" if rng.random() < 0.5 else "slots", seed=int(rng.integers(1 << 30))))
         else:

@@ -114,7 +114,12 @@ def _assert_exact(a, b, g, what):
 
 def build(name, seed=None):
     """The case `name` of CASES as a dict: the codec's tables, the bank's rows, the queries and the float64 oracle's S / exact."""
-    p = dict(CASES[name])
+    return build_from(CASES[name], name, seed)
+
+
+def build_from(params, name, seed=None):
+    """`build` for parameters of the form of a CASES entry that need not be one (tests/coded_exact_cases.py derives cases)."""
+    p = dict(params)
     C, D, nbits, Lq, nq = p["C"], p["D"], p["nbits"], p["Lq"], p["nq"]
     rng = np.random.default_rng(p["seed"] if seed is None else seed)
     weights = weights_of(nbits)

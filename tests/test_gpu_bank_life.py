@@ -25,8 +25,17 @@ was waiting for; tests/test_bank_life_cpu.py counts the two situations only wher
 
 Everything is equality of bytes; there is no tolerance anywhere.
 
+THE CODED KIND is an fp16 bank with a centroid table (rr_bank_set_centroids): fp16 rows, one code a row, a mask byte, three arrays of
+2 D / 4 / 1 bytes that a removal moves together.  It is checked as an fp16 bank (rows and mask read back, the exact and the filtered
+search, bank_li_scores) AND as a bank with codes (the codes read back, the file against its definition, the pruned searches and
+their covered-prefix forms).  Its scripts switch between two tables of 16 and 12 centroids: after a set_centroids the codes are
+the Shadow's codes under the new table (a float64 argmax, tests/bank_life.py), the file is gone, the generation is unchanged and
+a filter built before the call is still accepted.  It has no residuals: export_compressed and save_plaid_index refuse.
+
 A saved index holds the unmasked rows alone (rr_bank_export_plaid), so the loaded bank C is compared with the Shadow's unmasked rows
 and with A's export, file and searches, not with A's masked rows."""
+import types
+
 import numpy as np
 import pytest
 import torch
@@ -70,9 +79,15 @@ def _add(bank, passages, via):
                                lens, mask=_t(np.concatenate([p["mask"] for p in passages])))
 
 
+def _create(eng, sh, rows=None, slots=None):
+    """An empty bank of the Shadow's kind, for a coded kind with the table the Shadow holds."""
+    return eng.create_bank(sh.capacity_rows if rows is None else rows, sh.max_passages if slots is None else slots, codec=BL.codec_of(sh.kind),
+                           centroids=BL.tables()[sh.table] if sh.coded else None)
+
+
 def _fresh(eng, sh):
     """A fresh bank of the Shadow's contents: the covered prefix in one call, build_ivf, the rest in one call."""
-    B = eng.create_bank(sh.capacity_rows, sh.max_passages, codec=BL.codec_of(sh.kind))
+    B = _create(eng, sh)
     via = "add_compressed" if sh.nbits else "add"
     if sh.covered:
         _add(B, sh.passages[:sh.covered], via)
@@ -93,13 +108,17 @@ def _check_against_shadow(A, sh, what, export=True):
         for p in sh.passages:
             rows, mask = A.read(p["id"])
             assert torch.equal(_bits(rows), _t(p["rows"])) and torch.equal(mask, _t(p["mask"])), f"{what}: passage {p['id']}"
-        return
+            if sh.coded:
+                assert torch.equal(A.codes(p["id"]), _t(sh.codes_of(p))), f"{what}: the codes of passage {p['id']} under table {sh.table}"
+        if not sh.coded:
+            return
+        assert A.n_centroids == sh.n_centroids and A.format() == dict(nbits=0, n_centroids=sh.n_centroids, bytes_per_row=2 * D + 1 + 4), what
     assert A.ivf_info()["passages_covered"] == sh.covered, f"{what}: coverage {A.ivf_info()} for {sh.covered}"
-    for p in sh.passages:
+    for p in sh.passages if sh.nbits else []:
         codes, res, mask = A.read_compressed(p["id"])
         assert torch.equal(codes, _t(p["codes"])) and torch.equal(res, _t(p["res"])) and torch.equal(mask, _t(p["mask"])), \
             f"{what}: passage {p['id']}"
-    if len(sh) and export:
+    if len(sh) and export and sh.nbits:
         sh.search()                                        # the table is whole again
         codes, res, doclens = A.export_compressed()
         want_codes, want_res, want_doclens = sh.export()
@@ -119,12 +138,16 @@ def _same_bank(A, B, sh, what):
     for pid in sh.ids:
         got, want = (A.read_compressed(pid), B.read_compressed(pid)) if sh.nbits else (A.read(pid), B.read(pid))
         assert all(torch.equal(_bits(a), _bits(b)) for a, b in zip(got, want)), f"{what}: passage {pid}"
+        if sh.coded:
+            assert torch.equal(A.codes(pid), B.codes(pid)), f"{what}: the codes of passage {pid}"
     if sh.nbits:
         (ca, ra, da), (cb, rb, db) = A.export_compressed(), B.export_compressed()
         assert list(da) == list(db) and torch.equal(ca, cb) and torch.equal(ra, rb), f"{what}: the export"
 
 
 def _queries_of(sh, seed):
+    if sh.coded:                                           # near centroids of the first table: a passage's rows lie near one of each table
+        return _near_queries(types.SimpleNamespace(centroids=BL.tables()[0]), 2, 9, seed=seed)
     return _near_queries(BL.codec_of(sh.kind), 2, 9, seed=seed) if sh.nbits else _queries(2, 9, D, seed=seed)
 
 
@@ -133,7 +156,7 @@ def _check_against_fresh(eng, A, sh, what, seed):
     n, q = len(sh), _queries_of(sh, seed)
     sh.search()                                            # the searches below bring A's device table up to date
     _same_bank(A, B, sh, what)
-    if sh.nbits:
+    if sh.has_codes:
         if sh.covered:
             _same_ivf(A, B)
         else:
@@ -143,7 +166,7 @@ def _check_against_fresh(eng, A, sh, what, seed):
             _same_searches(eng, A, B, q, ivf=False)
         else:
             _same_searches(eng, A, B, q, ivf=sh.covered == n)
-    else:
+    if not sh.nbits:
         (ia, sa), (ib, sb) = A.search(eng, q, n), B.search(eng, q, n)
         assert ia == ib and torch.equal(sa.view(torch.int32), sb.view(torch.int32)), f"{what}: the exact search"
     # the exact search under a fresh filter that excludes every third passage
@@ -171,7 +194,7 @@ class _Life:
         self.ops = ops_of(seed, kind, prefix)
         rows, slots = BL.capacity(self.ops)
         self.sh = BL.Shadow(kind, rows, slots)
-        self.A = eng.create_bank(rows, slots, codec=BL.codec_of(kind))
+        self.A = _create(eng, self.sh)
         self.pending, self.stale = None, False             # a filter built at a stale_filter step; a remove or clear has run since
         self.watch = False                                 # a comparison with a fresh bank is due besides those of every eighth step
         self.q = _queries_of(self.sh, 5)
@@ -202,6 +225,18 @@ class _Life:
         elif what == "clear":
             step(sh, op)
             A.clear()
+        elif what == "set_centroids":
+            gen, held = A.generation, A.filter(excluded=sh.ids[:1]) if len(sh) else None
+            step(sh, op)
+            A.set_centroids(BL.tables()[op["table"]])
+            assert A.generation == gen == sh.generation and A.n_centroids == BL.TABLE_SIZES[op["table"]], where
+            assert A.ivf_info() == dict(passages_covered=0, postings=0, longest_list=0), f"{where}: the file goes with the table it named"
+            if held is not None:                           # the passages are as they were: a filter from before the call is accepted
+                ids, _ = A.search(self.eng, self.q, len(sh), filter=held)
+                assert all(sorted(row) == sorted(sh.ids[1:]) for row in ids), where
+                sh.search()
+            if self.pending is not None and not self.stale and self.ops[i - 1]["op"] == "stale_filter":
+                A.search(self.eng, self.q, 1, filter=self.pending)             # so is the one of the stale_filter step before it
         elif what == "search":
             step(sh, op)
             ids, scores = A.search(self.eng, self.q, min(3, len(sh)))
@@ -252,6 +287,11 @@ def test_a_lived_bank_equals_its_shadow_after_every_step_and_a_fresh_bank_every_
                 compared += 1
         if sh.nbits:
             _save_and_load(eng, life, str(tmp_path / "index"))
+        elif sh.coded:                                     # no residuals: nothing to export or to save
+            for call in (A.export_compressed, lambda: A.save_plaid_index(str(tmp_path / "index"))):
+                with pytest.raises(NotImplementedError):
+                    call()
+            assert not (tmp_path / "index").exists()
     assert compared >= STEPS // EVERY - 1, f"{compared} comparisons with a fresh bank"
     A.close()
 
@@ -299,10 +339,10 @@ def test_two_lived_banks_searched_as_one_equal_one_fresh_bank(kind):
         due = [life.checkpoint(i) for life in lives]
         if any(due) and held:
             assert len(set(p["id"] for p in held)) == len(held), "the two banks hold disjoint ids"
-            F = eng.create_bank(sum(p["length"] for p in held), len(held), codec=BL.codec_of(kind))
+            F = _create(eng, lives[0].sh, sum(p["length"] for p in held), len(held))
             for life in lives:
                 if len(life.sh):
-                    _add(F, life.sh.passages, "add_compressed")
+                    _add(F, life.sh.passages, "add_compressed" if life.sh.nbits else "add")
             q, k = _queries_of(lives[0].sh, 61 + i), min(8, len(held))
             ids, scores, counts = search_banks(eng, [life.A for life in lives], q, k)
             want_ids, want_scores = F.search(eng, q, k)

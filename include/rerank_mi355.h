@@ -796,6 +796,46 @@ int rr_bank_li_scores(rr_handle h, rr_bank_handle b, const float* query_li, int 
 int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage,
                    int32_t n_passages, int k, int32_t* indices_out, float* scores_out, void* hip_stream);
 
+/* rr_bank_search_f16: exhaustive search over a range of an FP16 bank (plain or coded) whose first pass runs on the fp16 matrix
+ * core and whose survivors are rescored exactly: every returned score is rr_bank_search's score of that passage bit for bit, and
+ * certified_out says per query whether the k results are PROVABLY rr_bank_search's.  PLAID's shape (approximate, then exact)
+ * without centroids: no recall is lost to cells.  Arguments, range, alignment, device checks, the table upload and the
+ * graph-capture refusal exactly as rr_bank_search has them; scores_out may be NULL.
+ *   ndocs : the survivors per query that are rescored, k <= ndocs <= 1024.   k : 1 <= k <= min(ndocs, n_passages).
+ *   slack : a bound on |A - E| over the range (below), >= 0.   certified_out : DEVICE int32 [n_queries], required.
+ * STAGES per query, n the passages of the range, "order" rr_bank_search's one total order (NaN first, higher score, lower index):
+ *   1. A[p] for every passage: its MaxSim with the query rounded once to fp16 (round to nearest even) and the fp16 rows as they
+ *      lie in the bank, accumulated by v_mfma_f32_16x16x32_f16 (csrc/bank_search_f16.hip: a workgroup owns a chunk of passages and
+ *      a block of queries, so a row is read from HBM once per query block, not once per query).  A product of two fp16 values is
+ *      exact in float32: only the query's rounding and the accumulation differ from the exact score E[p].
+ *   2. the first m = min(ndocs, n) passages in order over A: the survivors.
+ *   3. E of every survivor: the listed form of rr_bank_search's scoring kernel, hence its bits.
+ *   4. the first k survivors in order over (E, bank index): indices_out = bank indices, scores_out = E.
+ *   5. certified_out = 1 if m == n; else 1 iff score_k and a* are not NaN and score_k > a* + slack (a float32 sum), score_k the
+ *      k-th returned score and a* = A of the last survivor.  (An exact score of -inf is absent, as in the pruned searches: -1 /
+ *      -inf at the end of the list, and the query is not certified.)
+ * PROOF.  A passage outside the survivors has A <= a*.  If slack bounds |A - E| over the range, its E <= a* + slack < score_k:
+ * strictly below the k-th result.  The survivors hold every passage that can rank among the first k, stage 4 orders them as
+ * rr_bank_search does, so indices_out and scores_out are rr_bank_search's bytes.  A query that is not certified still gets exact
+ * scores of real passages, in order: the best k among its ndocs approximately best.
+ * SLACK.  The bound it stands for: |A - E| <= sum_j ||q_j||2 * R * (2^-11 + D * 2^-22) + Lq * 2^-22 * |E|, R the largest row norm
+ * (<= 1 + 2^-10 for unit rows stored as fp16).  2^-11 is the query's rounding to fp16 (relative, per element: derivable).  D * 2^-24
+ * would cover ANY order of float32 additions of the exact products under round to nearest; the matrix core's internal order and
+ * rounding are not documented, so the constant is 4 times that, and how far the hardware stays under it is MEASURED
+ * (tests/test_gpu_bank_search_f16.py, profiles/bank_f16_parity_margins.json).  The last term is the column sum.  Python's default
+ * (F16Search(slack=None)) evaluates the bound with R = 1 + 2^-10 and |E| <= sum_j ||q_j||2 * R, maximised over the call's queries.
+ * SCRATCH in the grow-only block rr_bank_search uses, each term rounded up to 16 bytes: A and E (4 n_queries n each), the two
+ * survivor buffers of the selection (4 n_queries ceil(n / 4096) m each, none for n <= 4096), the survivors (4 n_queries m), two
+ * counts (4 n_queries each) and, without scores_out, 4 n_queries k: at most 4 n_queries n (2 + ndocs / 2048) + O(n_queries ndocs).
+ * Five launches (one more per further selection pass above 4096 passages) and one memset, booked in the profile's `tail` class; no atomics: the same bytes from run to run.
+ * REFUSED before anything is enqueued, nothing written: what rr_bank_search refuses, a null certified_out, a NaN or negative slack
+ * (RR_ERR_BAD_ARG); k < 1, k > ndocs, k > n_passages (RR_ERR_BAD_SHAPE); ndocs > 1024, a compressed bank (its exhaustive search
+ * is bound by the decode, not by the matrix core), li_dim not a multiple of 32 (RR_ERR_UNSUPPORTED).
+ * WHICH TO USE: profiles/README.md "bank_search_f16_bench".  (Python: RerankEngine.bank_search_f16, PassageBank.search(fast=F16Search(ndocs)).) */
+int rr_bank_search_f16(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage,
+                       int32_t n_passages, int ndocs, int k, float slack, int32_t* indices_out, float* scores_out,
+                       int32_t* certified_out, void* hip_stream);
+
 /* rr_bank_search_plaid: PLAID's staged, centroid-pruned top-k search over a range of a COMPRESSED bank (the reference:
  * third_party/ColBERT/colbert/search/index_storage.py:86-184, candidate_generation.py, filter_pids.cpp), from what the bank holds
  * already: a centroid code per row, the fp16 centroid table, the passage table.  This entry reads no IVF (rr_bank_search_plaid_ivf

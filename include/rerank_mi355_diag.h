@@ -350,6 +350,17 @@ int rr_op_filter_compact(const uint32_t* filter_bits, int filter_rows, int64_t f
 int rr_op_topk_select_counted(const float* scores, int n_lists, int n, const int32_t* counts, const int32_t* cand, int rows, int k,
                               int32_t first_passage, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream);
 
+/* rr_op_bank_scores_f16: the first pass of rr_bank_search_f16 (rerank_mi355.h) alone, over raw DEVICE pointers: scores_out float32
+ * [n_queries, n_passages] = A, the MaxSim of every query, rounded once to fp16, against the passages first_passage ..
+ * first_passage + n_passages - 1 of `table` (as rr_op_bank_search takes it), accumulated on v_mfma_f32_16x16x32_f16
+ * (csrc/bank_search_f16.hip).  rows_f16 DEVICE fp16 bits, 16-byte aligned; mask_bytes one byte per row; D a multiple of 32
+ * (otherwise RR_ERR_UNSUPPORTED).  On inputs whose partial sums are all exact in float32 and whose query is exact in fp16, A is the
+ * exact score bit for bit.  No scratch, no synchronisation.
+ * rr_set_tuning("f16_stop_after") (3; 0 .. 3): the last stage an rr_bank_search_f16 call runs: 0 the approximate scores, 1 the
+ * survivors, 2 their exact scores, 3 all; below 3 the outputs are not written (tools/bench_bank_search_f16.py times the stages). */
+int rr_op_bank_scores_f16(const float* query_li, int n_queries, int Lq, int D, const void* table, int32_t first_passage,
+                          int32_t n_passages, const uint16_t* rows_f16, const uint8_t* mask_bytes, float* scores_out, void* hip_stream);
+
 /* rr_bank_search_plaid (rerank_mi355.h) from the inside.
  * rr_op_bank_search_plaid: the stages over raw DEVICE pointers, as rr_op_bank_search takes a compressed bank's (table, mask, codes,
  * residuals, tables; codes are clamped into [0, n_centroids)); allocates its scratch per call and synchronises hip_stream.

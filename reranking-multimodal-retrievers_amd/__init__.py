@@ -15,6 +15,7 @@ from .sharding import (ShardedBank, ShardedReranker, combine_owned, exchange_ban
 from .ranking import rank_descending_stable, recall_precision_at_k  # noqa: F401
 from .evaluate import build_records, compute_rerank_scores, rerank_dataset  # noqa: F401
 from .pipeline import rerank_dataset_pipelined  # noqa: F401
+from .passage_bank import F16Search, f16_default_slack  # noqa: F401
 from .passage_bank import (BankFilter, BankTable, PassageBank, PlaidCodec, PlaidSearch, plaid_num_partitions, plan_bank_batch,  # noqa: F401
                            plan_bank_scores, read_plaid_index, search_bank_part, search_banks, write_ivf, write_plaid_index)
 

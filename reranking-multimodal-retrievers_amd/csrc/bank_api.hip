@@ -857,6 +857,77 @@ static int bank_search_call(rr_handle h, rr_bank* b, const float* query_li, int 
   return RR_OK;
 }
 
+// rr_set_tuning("f16_stop_after"): the last stage an rr_bank_search_f16 call runs (0 the approximate scores, 1 the survivors, 2 their
+// exact scores, 3 all); below 3 the outputs are not written: tools/bench_bank_search_f16.py times the stages by difference.  A
+// diagnostic switch, set between calls (as the sparse form's).
+static int g_f16_stop_after = 3;
+int set_f16_stop_after(int value) {
+  if (value < 0 || value > 3) return RR_ERR_BAD_ARG;
+  g_f16_stop_after = value;
+  return RR_OK;
+}
+
+// rr_bank_search_f16 (include/rerank_mi355.h): A over the range on the fp16 matrix core, its m = min(ndocs, n) first per query, their
+// exact scores by the listed form of rr_bank_search's kernel, the first k of those, and the certificate
+static int bank_search_f16_call(rr_handle h, rr_bank* b, const float* query_li, int n_queries, int Lq, int32_t first_passage, int32_t n_passages,
+                                int ndocs, int k, float slack, int32_t* indices_out, float* scores_out, int32_t* certified_out, void* hip_stream) {
+  const char* what = "rr_bank_search_f16";
+  if (!h) return RR_ERR_BAD_ARG;
+  rr_model* m = h;
+  hipStream_t st = (hipStream_t)hip_stream;
+  int n = 0;
+  double rows = 0.0;
+  RR_TRY(bank_search_begin(m, what, false, true, b, query_li, n_queries, Lq, first_passage, n_passages, indices_out, scores_out, certified_out, st, &n,
+                           &rows, [&](int np) {
+                             if (k < 1 || k > ndocs || k > np) return fail(m, RR_ERR_BAD_SHAPE, "%s: k=%d ndocs=%d of %d passages", what, k, ndocs, np);
+                             if (ndocs > 1024) return fail(m, RR_ERR_UNSUPPORTED, "%s: ndocs=%d (at most 1024: a selection pass keeps ndocs of 4096)", what, ndocs);
+                             if (!(slack >= 0.0f)) return fail(m, RR_ERR_BAD_ARG, "%s: slack=%g (>= 0, not NaN)", what, (double)slack);
+                             if (bank_view(b).nbits) return fail(m, RR_ERR_UNSUPPORTED, "%s: a compressed bank (fp16 banks only: the first pass reads fp16 rows)", what);
+                             if (m->cfg.li_dim % 32) return fail(m, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a multiple of 32)", what, m->cfg.li_dim);
+                             return (int)RR_OK;
+                           }));
+  const int D = m->cfg.li_dim, nd = std::min(ndocs, n);
+  auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  const size_t sc_bytes = up((size_t)n_queries * n * sizeof(float));                             // A, and E behind it
+  const size_t tmp_bytes = up(rr_topk_select_scratch(n_queries, n, nd) * sizeof(int32_t));
+  const size_t surv_bytes = up((size_t)n_queries * nd * sizeof(int32_t)), cnt_bytes = up((size_t)n_queries * sizeof(int32_t));
+  const size_t ks_bytes = scores_out ? 0 : up((size_t)n_queries * k * sizeof(float));           // the certificate reads the k-th score
+  RR_TRY(ensure_block(m, m->search_blk, m->search_blk_cap, 2 * sc_bytes + 2 * tmp_bytes + surv_bytes + 2 * cnt_bytes + ks_bytes, st,
+                      "the bank search's block"));
+  m->plaid_last_ok = false;                         // the block no longer holds a pruned search's intermediates
+  char* p = m->search_blk;
+  float* A = (float*)p;
+  float* E = (float*)(p + sc_bytes);
+  int32_t* tmp_a = tmp_bytes ? (int32_t*)(p + 2 * sc_bytes) : nullptr;
+  int32_t* tmp_b = tmp_bytes ? (int32_t*)(p + 2 * sc_bytes + tmp_bytes) : nullptr;
+  int32_t* surv = (int32_t*)(p + 2 * sc_bytes + 2 * tmp_bytes);
+  int32_t* cnt_in = (int32_t*)(p + 2 * sc_bytes + 2 * tmp_bytes + surv_bytes);
+  int32_t* cnt_out = (int32_t*)(p + 2 * sc_bytes + 2 * tmp_bytes + surv_bytes + cnt_bytes);
+  float* ks = scores_out ? scores_out : (float*)(p + 2 * sc_bytes + 2 * tmp_bytes + surv_bytes + 2 * cnt_bytes);
+  m->last_stream = st;
+  const rr_bank_view bank = bank_view(b);
+  const rr_bank_slot* table = b->table + first_passage;
+  const double tiles = std::ceil(Lq / 16.0);
+  // A: the rows and mask bytes once (the query blocks of a chunk run side by side), the table, the query block per workgroup of 32
+  // passages, one float per (query, passage); FLOPs of whole column tiles are what the matrix core runs, Lq columns what is booked
+  RR_RUN(m, st, RR_K_TAIL, 2.0 * n_queries * rows * Lq * D, rows * (2.0 * D + 1.0) + 16.0 * n + (n / 32.0 + 1.0) * n_queries * tiles * 16.0 * 4.0 * D + 4.0 * n_queries * (double)n,
+         rr_launch_bank_scores_f16(table, n, n_queries, Lq, D, query_li, bank, A, st));
+  if (g_f16_stop_after < 1) return RR_OK;
+  RR_RUN(m, st, RR_K_TAIL, 0.0, 12.0 * n_queries * (double)n, rr_launch_topk_select(A, n_queries, n, nd, 0, tmp_a, tmp_b, surv, nullptr, st));
+  if (g_f16_stop_after < 2) return RR_OK;
+  RR_HIP(m, hipMemsetD32Async((hipDeviceptr_t)cnt_in, nd, (size_t)n_queries, st));      // every query's list is full
+  // E: booked for the range's mean passage length, as the pruned search books its survivors
+  const double srows = rows / n * nd * n_queries;
+  RR_RUN(m, st, RR_K_TAIL, 2.0 * srows * Lq * D, srows * (2.0 * D + 1.0) + (double)n_queries * nd * (20.0 + Lq * D),
+         rr_launch_bank_search_scores_listed(table, n, n_queries, Lq, D, query_li, bank, surv, nd, cnt_in, nullptr, 0, E, st));
+  if (g_f16_stop_after < 3) return RR_OK;
+  RR_RUN(m, st, RR_K_TAIL, 0.0, 16.0 * n_queries * (double)nd,
+         rr_launch_list_select(E, (long long)n, n_queries, surv, nd, k, indices_out, cnt_out, first_passage, ks, st));
+  RR_RUN(m, st, RR_K_TAIL, 0.0, 24.0 * n_queries,
+         rr_launch_f16_certify(A, (long long)n, surv, nd, ks, cnt_out, k, slack, n_queries, certified_out, st));
+  return RR_OK;
+}
+
 // the scratch of the diagnostic search operators: allocated per call and freed behind a synchronisation of the stream
 static int op_select_with_scratch(const float* scores, int n_lists, int n, int k, int add, int32_t* indices_out, float* scores_out, hipStream_t st) {
   const size_t entries = rr_topk_select_scratch(n_lists, n, k);
@@ -938,6 +1009,21 @@ int rr_op_bank_search(const float* query_li, int n_queries, int Lq, int D, const
     if (hipStreamSynchronize(st) != hipSuccess && rc == RR_OK) rc = RR_ERR_HIP;
     (void)hipFree(sc);
     return rc;
+  });
+}
+
+// rr_op_bank_scores_f16 (include/rerank_mi355_diag.h): the first pass of rr_bank_search_f16 over raw device pointers
+int rr_op_bank_scores_f16(const float* query_li, int n_queries, int Lq, int D, const void* table, int32_t first_passage, int32_t n_passages,
+                          const uint16_t* rows_f16, const uint8_t* mask_bytes, float* scores_out, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int {
+    if (!query_li || !table || !rows_f16 || !mask_bytes || !scores_out) return RR_ERR_BAD_ARG;
+    if ((((uintptr_t)query_li) | ((uintptr_t)table) | ((uintptr_t)rows_f16)) & 15) return RR_ERR_BAD_ARG;
+    if (D <= 0 || D % 32) return RR_ERR_UNSUPPORTED;
+    if (n_queries <= 0 || n_queries > 65535 || Lq <= 0 || first_passage < 0 || n_passages <= 0) return RR_ERR_BAD_SHAPE;
+    const rr_bank_view bank{0, 0, rows_f16, nullptr, nullptr, nullptr, nullptr, mask_bytes};
+    const hipError_t e = rr_launch_bank_scores_f16((const rr_bank_slot*)table + first_passage, n_passages, n_queries, Lq, D, query_li, bank, scores_out,
+                                                   (hipStream_t)hip_stream);
+    return e == hipSuccess ? RR_OK : RR_ERR_HIP;
   });
 }
 
@@ -1555,6 +1641,9 @@ int rr_bank_li_scores(rr_handle h, rr_bank_handle b, const float* query_li, int 
 }
 int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage, int32_t n_passages, int k, int32_t* indices_out, float* scores_out, void* hip_stream) {
   return guarded(h, [&]() -> int { return bank_search_call(h, b, query_li, n_queries, Lq, first_passage, n_passages, k, nullptr, false, indices_out, scores_out, nullptr, hip_stream); });
+}
+int rr_bank_search_f16(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage, int32_t n_passages, int ndocs, int k, float slack, int32_t* indices_out, float* scores_out, int32_t* certified_out, void* hip_stream) {
+  return guarded(h, [&]() -> int { return bank_search_f16_call(h, b, query_li, n_queries, Lq, first_passage, n_passages, ndocs, k, slack, indices_out, scores_out, certified_out, hip_stream); });
 }
 int rr_bank_search_filtered(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage, int32_t n_passages, int k, const uint32_t* filter_bits, int filter_rows, int64_t filter_ld, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream) {
   const FilterArg f{filter_bits, filter_rows, filter_ld};

@@ -2297,6 +2297,7 @@ int rr_set_tuning(const char* key, int value) {
   if (!strcmp(key, "plaid_stop_after")) return set_plaid_stop_after(false, value);
   if (!strcmp(key, "plaid_ivf_stop_after")) return set_plaid_stop_after(true, value);
   if (!strcmp(key, "sparse_stop_after")) return set_sparse_stop_after(value);
+  if (!strcmp(key, "f16_stop_after")) return set_f16_stop_after(value);
   if (!strcmp(key, "attn_prio")) return rr_set_attn_prio(value);
   if (!strcmp(key, "attn_fixed_ref")) return rr_set_attn_fixed_ref(value);
   return RR_ERR_BAD_ARG;

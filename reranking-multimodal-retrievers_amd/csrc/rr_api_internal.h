@@ -292,6 +292,7 @@ int asm_stage(rr_model* m, const char* what, const void* data, size_t bytes, hip
 int asm_done(rr_model* m, hipStream_t st);
 int set_plaid_stop_after(bool ivf, int value);
 int set_sparse_stop_after(int value);
+int set_f16_stop_after(int value);
 
 const char* const CAP_GROWS = "%s would have to grow during stream capture; call rr_reserve for the largest shape before capturing";
 const char* const CAP_STAGES = "%s cannot be captured into a graph (it stages its descriptors from the host)";

@@ -535,6 +535,15 @@ hipError_t rr_launch_list_select(const float* scores, long long n, int nq, const
 size_t rr_topk_select_scratch(int n_lists, int n, int k);
 hipError_t rr_launch_topk_select(const float* scores, int n_lists, int n, int k, int add, int32_t* tmp_a, int32_t* tmp_b,
                                  int32_t* indices_out, float* scores_out, hipStream_t st);
+// rr_bank_search_f16 (bank_search_f16.hip): out [nq][n] = the MaxSim of every query, rounded once to fp16, against the passages
+// table[0 .. n) of an fp16 bank (plain or coded), accumulated by v_mfma_f32_16x16x32_f16: an approximation of
+// rr_launch_bank_search_scores' row, a query block per workgroup.  D a multiple of 32, rows 16-byte aligned.
+// rr_launch_f16_certify: certified [nq] from A [nq][n], the survivors surv [nq][m] in rank order over A, the k exact scores
+// [nq][k] and their counts cnt [nq] (rr_launch_list_select's): cnt == k and (m == n or score_k > A[last survivor] + slack).
+hipError_t rr_launch_bank_scores_f16(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li, const rr_bank_view& bank,
+                                     float* out, hipStream_t st);
+hipError_t rr_launch_f16_certify(const float* A, long long n, const int32_t* surv, int m, const float* scores, const int32_t* cnt, int k, float slack,
+                                 int nq, int32_t* certified, hipStream_t st);
 // The list-driven form of the filtered exact search (rr_bank_search_filtered_sparse), stage by stage.
 // rr_launch_filter_compact (bank_ivf.hip): cand [filter.rows][n] = the range-relative passages of [filter.first, filter.first + n) whose
 // bit is set, ascending, cnt [filter.rows] their numbers; a workgroup per row, no atomics.

@@ -946,6 +946,31 @@ class RerankEngine:
                                         self._stream()), self.h, "rr_bank_search")
         return out
 
+    def bank_search_f16(self, bank, query_li: torch.Tensor, k: int, ndocs: int, slack: Optional[float] = None, first: int = 0,
+                        count: Optional[int] = None) -> dict:
+        """Exhaustive search of an fp16 `bank` (plain or coded) whose first pass runs on the fp16 matrix core (rr_bank_search_f16):
+        every passage of the range gets an approximate MaxSim, the `ndocs` approximately best per query are rescored exactly and
+        the k best of those are returned: {"indices": int32 [n_queries, k], "scores": float32 [n_queries, k], each score bit for
+        bit bank_search's for that passage, "certified": int32 [n_queries]}, on the device.  certified[q] = 1: the row is provably
+        bank_search's, bytes included (include/rerank_mi355.h gives the proof); 0: still the exact best k of the query's ndocs
+        approximately best.  `slack`: the bound on |approximate - exact| the certificate uses; None: the header's bound evaluated
+        on `query_li` for unit rows (passage_bank.f16_default_slack: one small reduction on the device and one read-back).
+        1 <= k <= min(ndocs, count), ndocs <= 1024; compressed banks: NotImplementedError."""
+        from .passage_bank import F16Search
+        first, n, nq, Lq, q = _bank_search_args(self, "bank_search_f16", bank, query_li, first, count)
+        fast = F16Search(ndocs, slack)
+        k = int(k)
+        if k < 1 or k > n or k > fast.ndocs:
+            raise ValueError(f"bank_search_f16: k = {k}, ndocs = {fast.ndocs}, {n} passages")
+        if getattr(bank, "codec", None) is not None:
+            raise NotImplementedError("bank_search_f16: a compressed bank (fp16 banks only)")
+        out = dict(indices=torch.empty((nq, k), device=self.device, dtype=torch.int32),
+                   scores=torch.empty((nq, k), device=self.device, dtype=torch.float32),
+                   certified=torch.empty((nq,), device=self.device, dtype=torch.int32))
+        L.check(self.lib.rr_bank_search_f16(self.h, bank.h, L.ptr(q), nq, Lq, first, n, fast.ndocs, k, fast.slack_for(q), L.ptr(out["indices"]),
+                                            L.ptr(out["scores"]), L.ptr(out["certified"]), self._stream()), self.h, "rr_bank_search_f16")
+        return out
+
     def bank_search_filtered(self, bank, query_li: torch.Tensor, k: int, filter, first: int = 0, count: Optional[int] = None) -> dict:
         """bank_search over the passages of the range that `filter` (a BankFilter, PassageBank.filter: one set for every query,
         or one per query) allows (rr_bank_search_filtered): a passage outside the set is not scored.  {"indices": int32
@@ -1517,16 +1542,29 @@ class InteractionRerankModel(_DropIn):
             raise RuntimeError("retriever_scores needs a bank: model.create_bank(capacity_rows, max_passages), then bank.add(...)")
         return self.engine.bank_li_scores(self.bank, query_late_interaction, passage_ids, **kw)
 
-    def retrieve(self, query_late_interaction, k: int, plaid=None, allowed=None, excluded=None, filter=None, sparse: bool = False, **kw):
+    def retrieve(self, query_late_interaction, k: int, plaid=None, allowed=None, excluded=None, filter=None, sparse: bool = False,
+                 fast=None, return_certified: bool = False, **kw):
         """The k best passages of `self.bank` per query by the frozen retriever's MaxSim, every passage scored
         (PassageBank.search): (passage_ids: one list per query, best first; scores float32 [n_queries, k] on the device).
         `plaid` (a PlaidSearch): PLAID's pruned search over a compressed bank, or an fp16 bank with a centroid table, instead; a query's list may then be shorter than k.
         `allowed` / `excluded` (passage ids: a flat sequence for every query, or a list of lists, one per query), or `filter` (a
         BankFilter built by bank.filter): only the allowed passages compete (the reference's filter_fn); one of the three at most.
         A query's list then has its true length, at most k.  `sparse` (with one of the three, without `plaid`; ValueError
-        otherwise): the filtered exact search in its list-driven form (RerankEngine.bank_search_filtered_sparse), the same result."""
+        otherwise): the filtered exact search in its list-driven form (RerankEngine.bank_search_filtered_sparse), the same result.
+        `fast` (an F16Search; fp16 banks, with none of the above: ValueError otherwise): the exhaustive search whose first pass
+        runs on the fp16 matrix core (RerankEngine.bank_search_f16): exact scores, and with `return_certified` the tuple ends in
+        the certificate, int32 [n_queries] on the device (1: the list is provably the exact search's)."""
         if self.bank is None:
             raise RuntimeError("retrieve needs a bank: model.create_bank(capacity_rows, max_passages), then bank.add(...)")
+        if return_certified and fast is None:
+            raise ValueError("retrieve: return_certified=True needs fast= (an F16Search)")
+        if fast is not None:
+            if plaid is not None or allowed is not None or excluded is not None or filter is not None or sparse:
+                raise ValueError("retrieve: fast= with plaid, a filter or sparse (the fp16 first pass scores every passage of the bank)")
+            r = self.bank.search(self.engine, query_late_interaction, k, fast=fast, **kw)
+            ids = self.bank.table.ids
+            out = ([[ids[j] for j in row] for row in r["indices"].tolist()], r["scores"])
+            return out + (r["certified"],) if return_certified else out
         if sparse:                                # before a filter is built or the library is called
             if allowed is None and excluded is None and filter is None:
                 raise ValueError("retrieve: sparse=True needs allowed / excluded or a filter")
@@ -1544,13 +1582,19 @@ class InteractionRerankModel(_DropIn):
         return self.bank.search(self.engine, query_late_interaction, k, **kw)
 
     def retrieve_and_rerank(self, query_late_interaction, query_mask, k: int, plaid=None, allowed=None, excluded=None, filter=None,
-                            sparse: bool = False, **kw):
+                            sparse: bool = False, fast=None, **kw):
         """`retrieve` then `forward_passages` on what it found, k candidates per query in retrieval order: (passage_ids, the
         RerankOutput).  `kw` goes to forward_passages (labels default as there: candidate 0 of every query).  With `plaid`, or
         under `allowed` / `excluded` / `filter` (as retrieve takes them), the lists may be of unequal length: they go to
-        forward_passages as candidates_per_query; a query that found no candidate raises ValueError.  `sparse`: as retrieve takes
-        it."""
+        forward_passages as candidates_per_query; a query that found no candidate raises ValueError.  `sparse`, `fast`: as retrieve
+        takes them (`fast` returns k candidates per query, as the exact search does)."""
         filtered = allowed is not None or excluded is not None or filter is not None
+        if fast is not None:
+            if plaid is not None or filtered or sparse:
+                raise ValueError("retrieve_and_rerank: fast= with plaid, a filter or sparse")
+            ids, _ = self.retrieve(query_late_interaction, k, fast=fast)
+            flat = [pid for row in ids for pid in row]
+            return ids, self.forward_passages(query_late_interaction, query_mask, flat, int(k) - 1, **kw)
         if sparse and (plaid is not None or not filtered):
             raise ValueError("retrieve_and_rerank: sparse=True needs allowed / excluded or a filter, and no plaid")
         if plaid is None and not filtered:

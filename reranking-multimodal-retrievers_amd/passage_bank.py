@@ -86,6 +86,46 @@ class PlaidSearch:
                 f"coarse_tokens={self.coarse_tokens}" + (", ivf=True)" if self.ivf else ")"))
 
 
+def f16_default_slack(query_norm_sum: float, li_dim: int, Lq: int) -> float:
+    """The bound on |A - E| that rr_bank_search_f16's certificate stands on (include/rerank_mi355.h, SLACK), for unit rows stored as
+    fp16 (R = 1 + 2^-10) and |E| <= S R: S R (2^-11 + D 2^-22) + Lq 2^-22 S R, S = `query_norm_sum`, the sum over a query's tokens of
+    their 2-norms (the largest over the queries of a call)."""
+    sr = float(query_norm_sum) * (1.0 + 2.0 ** -10)
+    return sr * (2.0 ** -11 + int(li_dim) * 2.0 ** -22) + int(Lq) * 2.0 ** -22 * sr
+
+
+class F16Search:
+    """The parameters of the exhaustive search whose first pass runs on the fp16 matrix core (rr_bank_search_f16): the `ndocs`
+    (1 .. 1024) approximately best passages per query are rescored exactly; `slack`: the bound on |approximate - exact| its
+    certificate uses, None: f16_default_slack on the call's queries."""
+
+    def __init__(self, ndocs: int, slack: Optional[float] = None):
+        self.ndocs = int(ndocs)
+        if self.ndocs < 1:
+            raise ValueError(f"F16Search: ndocs = {ndocs}")
+        if self.ndocs > 1024:
+            raise NotImplementedError(f"F16Search: ndocs = {ndocs} (at most 1024, the selection kernel's limit)")
+        self.slack = None if slack is None else float(slack)
+        if self.slack is not None and not self.slack >= 0.0:
+            raise ValueError(f"F16Search: slack = {slack} (>= 0, not NaN)")
+
+    def slack_for(self, query_li) -> float:
+        """`slack`, or the default bound for `query_li` [n_queries, Lq, D] (one reduction on its device, one read-back)."""
+        if self.slack is not None:
+            return self.slack
+        s = float(query_li.double().norm(dim=-1).sum(dim=-1).max().item())
+        return f16_default_slack(s, int(query_li.shape[-1]), int(query_li.shape[-2]))
+
+    def __repr__(self) -> str:
+        return f"F16Search(ndocs={self.ndocs}, slack={self.slack})"
+
+
+def _fast_check(name: str, fast, plaid, filter, sparse) -> None:
+    """`fast` names the unfiltered exhaustive search: with `plaid`, a filter or `sparse` there is no such entry."""
+    if fast is not None and (plaid is not None or filter is not None or sparse):
+        raise ValueError(f"{name}: fast= with plaid=, filter= or sparse= (the fp16 first pass scores every passage of the range)")
+
+
 class BankFilter:
     """A candidate filter of the bank searches (PassageBank.filter; "CANDIDATE FILTERS", include/rerank_mi355.h): `bits`, the device
     bitmap int32 [rows, ld] (bit i & 31 of word i >> 5 of a row: dense bank index i), `rows` (1: one set for every query; else one
@@ -992,7 +1032,7 @@ class PassageBank:
         return BankFilter(bits, rows, passages, self.generation)
 
     def search(self, engine, query_li, k: int, first: int = 0, count: Optional[int] = None, plaid: Optional[PlaidSearch] = None,
-               filter: Optional[BankFilter] = None, sparse: bool = False):
+               filter: Optional[BankFilter] = None, sparse: bool = False, fast: Optional[F16Search] = None):
         """The k best passages per query by the retriever's MaxSim, every passage of the bank scored (engine.bank_search;
         `first` / `count`: a range of dense indices).  Returns (passage_ids, scores): passage_ids[q] the ids of query q best
         first, scores float32 [n_queries, k] on the device.  Copies the indices to the host (synchronises).
@@ -1003,8 +1043,14 @@ class PassageBank:
         (engine.bank_search_filtered / bank_search_plaid_filtered / bank_search_plaid_ivf_filtered): passage_ids[q] has its true
         length on the exact path too.  A filter built for fewer passages than the range ends at raises ValueError.
         `sparse` (with `filter`, exact search only; ValueError otherwise): the list-driven form of the filtered exact search
-        (engine.bank_search_filtered_sparse): the same result, with work that follows the allowed passages, not the range."""
+        (engine.bank_search_filtered_sparse): the same result, with work that follows the allowed passages, not the range.
+        `fast` (an F16Search; fp16 banks; with `plaid`, `filter` or `sparse`: ValueError): the exhaustive search whose first pass runs
+        on the fp16 matrix core (engine.bank_search_f16).  Returns its dict instead, on the device, nothing copied: {"indices" int32
+        [n_queries, k] dense indices, "scores" float32 [n_queries, k] exact, "certified" int32 [n_queries]}."""
+        _fast_check("search", fast, plaid, filter, sparse)
         _sparse_check("search", sparse, filter, plaid)
+        if fast is not None:
+            return engine.bank_search_f16(self, query_li, k, fast.ndocs, fast.slack, first=first, count=count)
         ids = self.table.ids
         if filter is not None:
             if getattr(filter, "generation", self.generation) != self.generation:
@@ -1165,22 +1211,29 @@ def _sparse_check(name: str, sparse: bool, filter, plaid) -> None:
 
 
 def search_bank_part(engine, bank, query_li, k: int, plaid: Optional[PlaidSearch] = None, filter: Optional[BankFilter] = None,
-                     sparse: bool = False) -> dict:
+                     sparse: bool = False, fast: Optional[F16Search] = None) -> dict:
     """One part's list for RerankEngine.bank_merge_topk: the search of `bank` (the exact one, or with `plaid` / `filter` what
     PassageBank.search runs for them) with k_local = min(k, len(bank)), as {"indices": int32 [n_queries, k] dense indices of
     THIS bank, "scores": float32 [n_queries, k], "counts": int32 [n_queries]} on the device.  Behind k_local the rows hold -1 /
     -inf; an exact search, which returns no counts, gets k_local as its count; an empty bank contributes count 0 and no search
-    call.  `sparse`: as PassageBank.search takes it."""
+    call.  `sparse`: as PassageBank.search takes it.  `fast` (an F16Search): engine.bank_search_f16 with ndocs = max(fast.ndocs,
+    k_local) capped at 1024, and one more entry, "certified" int32 [n_queries] (an empty bank: all 1)."""
     import torch
+    _fast_check("search_bank_part", fast, plaid, filter, sparse)
     _sparse_check("search_bank_part", sparse, filter, plaid)
     nq, k, dev = int(query_li.shape[0]), int(k), engine.device
     k_local = min(k, len(bank))
     out = dict(indices=torch.full((nq, k), -1, device=dev, dtype=torch.int32),
                scores=torch.full((nq, k), float("-inf"), device=dev, dtype=torch.float32),
                counts=torch.zeros((nq,), device=dev, dtype=torch.int32))
+    if fast is not None:
+        out["certified"] = torch.ones((nq,), device=dev, dtype=torch.int32)
     if k_local < 1:
         return out
-    if plaid is not None:
+    if fast is not None:
+        r = engine.bank_search_f16(bank, query_li, k_local, min(max(fast.ndocs, k_local), 1024), fast.slack)
+        out["certified"] = r["certified"]
+    elif plaid is not None:
         kw = dict(ncells=plaid.ncells, centroid_score_threshold=plaid.centroid_score_threshold, ndocs=plaid.ndocs,
                   coarse_tokens=plaid.coarse_tokens)
         ivf = getattr(plaid, "ivf", False)
@@ -1204,7 +1257,7 @@ def search_bank_part(engine, bank, query_li, k: int, plaid: Optional[PlaidSearch
 
 
 def search_banks(engine, banks: Sequence, query_li, k: int, plaid: Optional[PlaidSearch] = None, filters: Optional[Sequence] = None,
-                 sparse: bool = False):
+                 sparse: bool = False, fast: Optional[F16Search] = None):
     """PassageBank.search over several banks held by one process (a corpus loaded bank by bank, an fp16 bank beside a compressed
     one of the same li_dim) as over one bank holding their passages in the order of `banks`: every bank is searched
     (search_bank_part: `plaid` for each, `filters[i]` a BankFilter of bank i or None), the lists are merged on the device
@@ -1213,7 +1266,9 @@ def search_banks(engine, banks: Sequence, query_li, k: int, plaid: Optional[Plai
     device, -inf behind the count; counts int32 [n_queries] on the device.  With the exact search this is, byte for byte, the
     search of the one bank; with `plaid` it is by definition the merge of the per-bank pruned searches (each bank keeps its own
     ndocs).  Copies the merged indices to the host (synchronises).  At most 64 banks, len(banks) * k <= 8192.  `sparse`: every
-    bank's filtered exact search in its list-driven form (a filter for every bank, no `plaid`; ValueError otherwise)."""
+    bank's filtered exact search in its list-driven form (a filter for every bank, no `plaid`; ValueError otherwise).  `fast` (an
+    F16Search; no `plaid`, filters or `sparse`): every bank by engine.bank_search_f16, and a fourth result, certified int32
+    [n_queries] on the device: the AND of the parts' certificates (every part's list provably exact: so is the merged one)."""
     import numpy as np
     import torch
     banks = list(banks)
@@ -1221,16 +1276,19 @@ def search_banks(engine, banks: Sequence, query_li, k: int, plaid: Optional[Plai
         raise ValueError("search_banks: no bank")
     if filters is not None and len(filters) != len(banks):
         raise ValueError(f"search_banks: {len(filters)} filters for {len(banks)} banks (one each, or None)")
+    _fast_check("search_banks", fast, plaid, filters, sparse)
     if sparse:
         for f in (filters if filters is not None else [None]):
             _sparse_check("search_banks", sparse, f, plaid)
     offsets = np.zeros(len(banks) + 1, dtype=np.int64)
     np.cumsum([len(b) for b in banks], out=offsets[1:])
-    more = dict(sparse=True) if sparse else {}
+    more = dict(sparse=True) if sparse else dict(fast=fast) if fast is not None else {}
     parts = [search_bank_part(engine, b, query_li, k, plaid, None if filters is None else filters[i], **more) for i, b in enumerate(banks)]
     r = engine.bank_merge_topk(torch.stack([p["indices"] for p in parts]), torch.stack([p["scores"] for p in parts]),
                                torch.stack([p["counts"] for p in parts]), offsets, k, want_parts=True)
     counts = r["counts"].tolist()
     ids = [[banks[p].table.ids[g - int(offsets[p])] for g, p in zip(row[:c], prow[:c])]
            for row, prow, c in zip(r["indices"].tolist(), r["parts"].tolist(), counts)]
+    if fast is not None:
+        return ids, r["scores"], r["counts"], torch.stack([p["certified"] for p in parts]).min(dim=0).values
     return ids, r["scores"], r["counts"]

@@ -830,11 +830,33 @@ int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_q
  * Five launches (one more per further selection pass above 4096 passages) and one memset, booked in the profile's `tail` class; no atomics: the same bytes from run to run.
  * REFUSED before anything is enqueued, nothing written: what rr_bank_search refuses, a null certified_out, a NaN or negative slack
  * (RR_ERR_BAD_ARG); k < 1, k > ndocs, k > n_passages (RR_ERR_BAD_SHAPE); ndocs > 1024, a compressed bank (its exhaustive search
- * is bound by the decode, not by the matrix core), li_dim not a multiple of 32 (RR_ERR_UNSUPPORTED).
+ * is bound by the decode, not by the matrix core: this entry's first pass reads fp16 rows; rr_bank_search_f16_plaid below decodes a
+ * row once per query block and takes compressed banks), li_dim not a multiple of 32 (RR_ERR_UNSUPPORTED).
  * WHICH TO USE: profiles/README.md "bank_search_f16_bench".  (Python: RerankEngine.bank_search_f16, PassageBank.search(fast=F16Search(ndocs)).) */
 int rr_bank_search_f16(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage,
                        int32_t n_passages, int ndocs, int k, float slack, int32_t* indices_out, float* scores_out,
                        int32_t* certified_out, void* hip_stream);
+
+/* rr_bank_search_f16_plaid: rr_bank_search_f16 over a range of a COMPRESSED bank.  Arguments, stages 1 - 5, the certificate and its
+ * proof, SLACK, SCRATCH, the launches and the graph-capture refusal are rr_bank_search_f16's, word for word.  ITS RESULTS ARE THOSE
+ * OF rr_bank_search_f16 ON THE FP16 BANK THAT HOLDS THE DECODED ROWS, BYTE FOR BYTE, certified_out included; every returned score is
+ * rr_bank_search's score of that passage on the compressed bank, and a certified row is rr_bank_search's row on it.
+ *   Stage 1 (csrc/bank_search_f16_plaid.hip): a wave decodes the two 16-row tiles it is about to multiply into an LDS tile of its
+ * own (THE DECODED ROW, "a compressed bank is bit for bit an fp16 bank that holds the decoded rows": a decoded row IS fp16) and
+ * feeds them to v_mfma_f32_16x16x32_f16 in the order of the fp16 kernel: equal operand bits, the same instruction chain, so A is the
+ * fp16 entry's A over the decoded rows bit for bit, and the slack bound with its measured accumulation constant
+ * (profiles/bank_f16_parity_margins.json) stands without a new measurement.  A row is decoded once per QUERY BLOCK (4 queries at
+ * Lq 32), not once per query as rr_bank_search decodes it.  Stage 3 is the listed form of rr_bank_search's kernel on the compressed
+ * rows.  A decoded row's norm is within the R = 1 + 2^-10 that Python's default slack assumes.
+ * REFUSED before anything is enqueued, nothing written: what rr_bank_search_f16 refuses, but an fp16 bank, plain or coded, in place
+ * of a compressed one (RR_ERR_UNSUPPORTED: rr_bank_search_f16 is the entry for it), and li_dim other than 32, 64, 128 or 256
+ * (RR_ERR_UNSUPPORTED: the four decoded tiles [32][li_dim + 16] fp16 of a workgroup take 132 KB of LDS at li_dim 512 and leave no
+ * room for a query block).  rr_set_tuning("f16_stop_after") applies to both entries.
+ * WHICH TO USE: profiles/README.md "bank_search_f16_plaid_bench".  (Python: RerankEngine.bank_search_f16_plaid; PassageBank.search(
+ * fast=F16Search(ndocs)) picks the entry by the bank's format.) */
+int rr_bank_search_f16_plaid(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage,
+                             int32_t n_passages, int ndocs, int k, float slack, int32_t* indices_out, float* scores_out,
+                             int32_t* certified_out, void* hip_stream);
 
 /* rr_bank_search_plaid: PLAID's staged, centroid-pruned top-k search over a range of a COMPRESSED bank (the reference:
  * third_party/ColBERT/colbert/search/index_storage.py:86-184, candidate_generation.py, filter_pids.cpp), from what the bank holds

@@ -360,6 +360,16 @@ int rr_op_topk_select_counted(const float* scores, int n_lists, int n, const int
  * survivors, 2 their exact scores, 3 all; below 3 the outputs are not written (tools/bench_bank_search_f16.py times the stages). */
 int rr_op_bank_scores_f16(const float* query_li, int n_queries, int Lq, int D, const void* table, int32_t first_passage,
                           int32_t n_passages, const uint16_t* rows_f16, const uint8_t* mask_bytes, float* scores_out, void* hip_stream);
+/* rr_op_bank_scores_f16_plaid: the first pass of rr_bank_search_f16_plaid (rerank_mi355.h) alone: rr_op_bank_scores_f16 over the
+ * rows of a compressed bank, given as rr_op_bank_li_scores takes them (mask_bytes, nbits 1, 2, 4 or 8, codes, residuals,
+ * centroids_f16, bucket_weights, n_centroids; codes are clamped into [0, n_centroids)).  scores_out is BIT FOR BIT what
+ * rr_op_bank_scores_f16 writes over the rows rr_op_plaid_decode_rows decodes (csrc/bank_search_f16_plaid.hip).  D 32, 64, 128 or
+ * 256 (otherwise RR_ERR_UNSUPPORTED).  No scratch, no synchronisation.  rr_set_tuning("f16_stop_after") applies to
+ * rr_bank_search_f16_plaid as to rr_bank_search_f16. */
+int rr_op_bank_scores_f16_plaid(const float* query_li, int n_queries, int Lq, int D, const void* table, int32_t first_passage,
+                                int32_t n_passages, const uint8_t* mask_bytes, int nbits, const int32_t* codes, const uint8_t* residuals,
+                                const uint16_t* centroids_f16, const float* bucket_weights, int32_t n_centroids, float* scores_out,
+                                void* hip_stream);
 
 /* rr_bank_search_plaid (rerank_mi355.h) from the inside.
  * rr_op_bank_search_plaid: the stages over raw DEVICE pointers, as rr_op_bank_search takes a compressed bank's (table, mask, codes,

@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librerank_mi355.so")
-SOURCES = ["rr_api.hip", "bank_api.hip", "gemm_bf16.hip", "gemm_fp8.hip", "attention_bf16.hip", "elementwise.hip", "head.hip", "pair_assembly.hip", "li_scores.hip", "passage_bank.hip", "bank_search.hip", "bank_search_f16.hip", "bank_search_plaid.hip", "bank_compress.hip", "plaid_train.hip", "bank_ivf.hip", "bank_export.hip", "bank_merge.hip", "bank_move.hip",
+SOURCES = ["rr_api.hip", "bank_api.hip", "gemm_bf16.hip", "gemm_fp8.hip", "attention_bf16.hip", "elementwise.hip", "head.hip", "pair_assembly.hip", "li_scores.hip", "passage_bank.hip", "bank_search.hip", "bank_search_f16.hip", "bank_search_f16_plaid.hip", "bank_search_plaid.hip", "bank_compress.hip", "plaid_train.hip", "bank_ivf.hip", "bank_export.hip", "bank_merge.hip", "bank_move.hip",
            "pair_tokenizer.cpp"]
 HEADERS = [os.path.join(CSRC, "rr_common.h"), os.path.join(os.path.dirname(HERE), "include", "rerank_mi355.h"),
            os.path.join(os.path.dirname(HERE), "include", "rerank_mi355_diag.h"),
@@ -48,7 +48,7 @@ OBJDUMP = os.path.join(os.path.dirname(os.path.dirname(HIPCC)), "lib", "llvm", "
 # objects whose device code must hold NO packed-f32 arithmetic (see the -fno-slp-vectorize note above): every epilogue that adds
 # freshly loaded fp32 / 16-bit rows lives in these.  attention_bf16 is exempt: its hand-written v_pk_add_f32 row sums only
 # touch VALU-produced values (checked in the disassembly: the ones behind a vmcnt wait add the constant 0 to a row sum).
-NO_PACKED_F32 = ["gemm_bf16.o", "gemm_fp8.o", "elementwise.o", "pair_assembly.o", "li_scores.o", "passage_bank.o", "bank_search.o", "bank_search_f16.o", "bank_search_plaid.o", "bank_compress.o", "plaid_train.o", "bank_ivf.o", "bank_export.o", "bank_merge.o", "bank_move.o"]
+NO_PACKED_F32 = ["gemm_bf16.o", "gemm_fp8.o", "elementwise.o", "pair_assembly.o", "li_scores.o", "passage_bank.o", "bank_search.o", "bank_search_f16.o", "bank_search_f16_plaid.o", "bank_search_plaid.o", "bank_compress.o", "plaid_train.o", "bank_ivf.o", "bank_export.o", "bank_merge.o", "bank_move.o"]
 
 
 def check_no_packed_f32(obj: str) -> None:

@@ -857,7 +857,7 @@ static int bank_search_call(rr_handle h, rr_bank* b, const float* query_li, int 
   return RR_OK;
 }
 
-// rr_set_tuning("f16_stop_after"): the last stage an rr_bank_search_f16 call runs (0 the approximate scores, 1 the survivors, 2 their
+// rr_set_tuning("f16_stop_after"): the last stage an rr_bank_search_f16 or rr_bank_search_f16_plaid call runs (0 the approximate scores, 1 the survivors, 2 their
 // exact scores, 3 all); below 3 the outputs are not written: tools/bench_bank_search_f16.py times the stages by difference.  A
 // diagnostic switch, set between calls (as the sparse form's).
 static int g_f16_stop_after = 3;
@@ -867,11 +867,13 @@ int set_f16_stop_after(int value) {
   return RR_OK;
 }
 
-// rr_bank_search_f16 (include/rerank_mi355.h): A over the range on the fp16 matrix core, its m = min(ndocs, n) first per query, their
-// exact scores by the listed form of rr_bank_search's kernel, the first k of those, and the certificate
-static int bank_search_f16_call(rr_handle h, rr_bank* b, const float* query_li, int n_queries, int Lq, int32_t first_passage, int32_t n_passages,
+// rr_bank_search_f16 and, `plaid`, rr_bank_search_f16_plaid (include/rerank_mi355.h): A over the range on the fp16 matrix core, its
+// m = min(ndocs, n) first per query, their exact scores by the listed form of rr_bank_search's kernel, the first k of those, and the
+// certificate.  One function under both entries: the kind of bank each takes and the launch that writes A are all that differ (the
+// listed kernel reads fp16 and compressed rows alike, as stage 3 of the pruned search has it).
+static int bank_search_f16_call(rr_handle h, bool plaid, rr_bank* b, const float* query_li, int n_queries, int Lq, int32_t first_passage, int32_t n_passages,
                                 int ndocs, int k, float slack, int32_t* indices_out, float* scores_out, int32_t* certified_out, void* hip_stream) {
-  const char* what = "rr_bank_search_f16";
+  const char* what = plaid ? "rr_bank_search_f16_plaid" : "rr_bank_search_f16";
   if (!h) return RR_ERR_BAD_ARG;
   rr_model* m = h;
   hipStream_t st = (hipStream_t)hip_stream;
@@ -882,6 +884,12 @@ static int bank_search_f16_call(rr_handle h, rr_bank* b, const float* query_li, 
                              if (k < 1 || k > ndocs || k > np) return fail(m, RR_ERR_BAD_SHAPE, "%s: k=%d ndocs=%d of %d passages", what, k, ndocs, np);
                              if (ndocs > 1024) return fail(m, RR_ERR_UNSUPPORTED, "%s: ndocs=%d (at most 1024: a selection pass keeps ndocs of 4096)", what, ndocs);
                              if (!(slack >= 0.0f)) return fail(m, RR_ERR_BAD_ARG, "%s: slack=%g (>= 0, not NaN)", what, (double)slack);
+                             if (plaid) {
+                               if (!bank_view(b).nbits) return fail(m, RR_ERR_UNSUPPORTED, "%s: an fp16 bank (compressed banks only: rr_bank_search_f16 searches an fp16 bank)", what);
+                               if (!rr_bank_scores_f16_plaid_dim_ok(m->cfg.li_dim))
+                                 return fail(m, RR_ERR_UNSUPPORTED, "%s: li_dim %d (32, 64, 128 or 256: the decoded tiles must fit the LDS)", what, m->cfg.li_dim);
+                               return (int)RR_OK;
+                             }
                              if (bank_view(b).nbits) return fail(m, RR_ERR_UNSUPPORTED, "%s: a compressed bank (fp16 banks only: the first pass reads fp16 rows)", what);
                              if (m->cfg.li_dim % 32) return fail(m, RR_ERR_UNSUPPORTED, "%s: li_dim %d (a multiple of 32)", what, m->cfg.li_dim);
                              return (int)RR_OK;
@@ -910,15 +918,17 @@ static int bank_search_f16_call(rr_handle h, rr_bank* b, const float* query_li, 
   const double tiles = std::ceil(Lq / 16.0);
   // A: the rows and mask bytes once (the query blocks of a chunk run side by side), the table, the query block per workgroup of 32
   // passages, one float per (query, passage); FLOPs of whole column tiles are what the matrix core runs, Lq columns what is booked
-  RR_RUN(m, st, RR_K_TAIL, 2.0 * n_queries * rows * Lq * D, rows * (2.0 * D + 1.0) + 16.0 * n + (n / 32.0 + 1.0) * n_queries * tiles * 16.0 * 4.0 * D + 4.0 * n_queries * (double)n,
-         rr_launch_bank_scores_f16(table, n, n_queries, Lq, D, query_li, bank, A, st));
+  // (a compressed row: its residual bytes, its code, its mask byte and the centroid it names: rr_bank_row_bytes)
+  RR_RUN(m, st, RR_K_TAIL, 2.0 * n_queries * rows * Lq * D, rows * (rr_bank_row_bytes(bank, D) + 1.0) + 16.0 * n + (n / 32.0 + 1.0) * n_queries * tiles * 16.0 * 4.0 * D + 4.0 * n_queries * (double)n,
+         plaid ? rr_launch_bank_scores_f16_plaid(table, n, n_queries, Lq, D, query_li, bank, A, st)
+               : rr_launch_bank_scores_f16(table, n, n_queries, Lq, D, query_li, bank, A, st));
   if (g_f16_stop_after < 1) return RR_OK;
   RR_RUN(m, st, RR_K_TAIL, 0.0, 12.0 * n_queries * (double)n, rr_launch_topk_select(A, n_queries, n, nd, 0, tmp_a, tmp_b, surv, nullptr, st));
   if (g_f16_stop_after < 2) return RR_OK;
   RR_HIP(m, hipMemsetD32Async((hipDeviceptr_t)cnt_in, nd, (size_t)n_queries, st));      // every query's list is full
   // E: booked for the range's mean passage length, as the pruned search books its survivors
   const double srows = rows / n * nd * n_queries;
-  RR_RUN(m, st, RR_K_TAIL, 2.0 * srows * Lq * D, srows * (2.0 * D + 1.0) + (double)n_queries * nd * (20.0 + Lq * D),
+  RR_RUN(m, st, RR_K_TAIL, 2.0 * srows * Lq * D, srows * (rr_bank_row_bytes(bank, D) + 1.0) + (double)n_queries * nd * (20.0 + Lq * D),
          rr_launch_bank_search_scores_listed(table, n, n_queries, Lq, D, query_li, bank, surv, nd, cnt_in, nullptr, 0, E, st));
   if (g_f16_stop_after < 3) return RR_OK;
   RR_RUN(m, st, RR_K_TAIL, 0.0, 16.0 * n_queries * (double)nd,
@@ -1023,6 +1033,23 @@ int rr_op_bank_scores_f16(const float* query_li, int n_queries, int Lq, int D, c
     const rr_bank_view bank{0, 0, rows_f16, nullptr, nullptr, nullptr, nullptr, mask_bytes};
     const hipError_t e = rr_launch_bank_scores_f16((const rr_bank_slot*)table + first_passage, n_passages, n_queries, Lq, D, query_li, bank, scores_out,
                                                    (hipStream_t)hip_stream);
+    return e == hipSuccess ? RR_OK : RR_ERR_HIP;
+  });
+}
+
+// rr_op_bank_scores_f16_plaid (include/rerank_mi355_diag.h): the first pass of rr_bank_search_f16_plaid over raw device pointers
+int rr_op_bank_scores_f16_plaid(const float* query_li, int n_queries, int Lq, int D, const void* table, int32_t first_passage, int32_t n_passages,
+                                const uint8_t* mask_bytes, int nbits, const int32_t* codes, const uint8_t* residuals, const uint16_t* centroids_f16,
+                                const float* bucket_weights, int32_t n_centroids, float* scores_out, void* hip_stream) {
+  return guarded(nullptr, [&]() -> int {
+    if (!query_li || !table || !mask_bytes || !codes || !residuals || !centroids_f16 || !bucket_weights || !scores_out) return RR_ERR_BAD_ARG;
+    if (((((uintptr_t)query_li) | ((uintptr_t)table) | ((uintptr_t)centroids_f16)) & 15) || (((uintptr_t)residuals) & 7) || (((uintptr_t)codes) & 3))
+      return RR_ERR_BAD_ARG;
+    if (!rr_bank_scores_f16_plaid_dim_ok(D) || !rr_plaid_shape_ok(nbits, D)) return RR_ERR_UNSUPPORTED;
+    if (n_queries <= 0 || n_queries > 65535 || Lq <= 0 || first_passage < 0 || n_passages <= 0 || n_centroids <= 0) return RR_ERR_BAD_SHAPE;
+    const rr_bank_view bank{nbits, n_centroids, nullptr, codes, residuals, centroids_f16, bucket_weights, mask_bytes};
+    const hipError_t e = rr_launch_bank_scores_f16_plaid((const rr_bank_slot*)table + first_passage, n_passages, n_queries, Lq, D, query_li, bank,
+                                                         scores_out, (hipStream_t)hip_stream);
     return e == hipSuccess ? RR_OK : RR_ERR_HIP;
   });
 }
@@ -1643,7 +1670,10 @@ int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_q
   return guarded(h, [&]() -> int { return bank_search_call(h, b, query_li, n_queries, Lq, first_passage, n_passages, k, nullptr, false, indices_out, scores_out, nullptr, hip_stream); });
 }
 int rr_bank_search_f16(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage, int32_t n_passages, int ndocs, int k, float slack, int32_t* indices_out, float* scores_out, int32_t* certified_out, void* hip_stream) {
-  return guarded(h, [&]() -> int { return bank_search_f16_call(h, b, query_li, n_queries, Lq, first_passage, n_passages, ndocs, k, slack, indices_out, scores_out, certified_out, hip_stream); });
+  return guarded(h, [&]() -> int { return bank_search_f16_call(h, false, b, query_li, n_queries, Lq, first_passage, n_passages, ndocs, k, slack, indices_out, scores_out, certified_out, hip_stream); });
+}
+int rr_bank_search_f16_plaid(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage, int32_t n_passages, int ndocs, int k, float slack, int32_t* indices_out, float* scores_out, int32_t* certified_out, void* hip_stream) {
+  return guarded(h, [&]() -> int { return bank_search_f16_call(h, true, b, query_li, n_queries, Lq, first_passage, n_passages, ndocs, k, slack, indices_out, scores_out, certified_out, hip_stream); });
 }
 int rr_bank_search_filtered(rr_handle h, rr_bank_handle b, const float* query_li, int n_queries, int Lq, int32_t first_passage, int32_t n_passages, int k, const uint32_t* filter_bits, int filter_rows, int64_t filter_ld, int32_t* indices_out, float* scores_out, int32_t* counts_out, void* hip_stream) {
   const FilterArg f{filter_bits, filter_rows, filter_ld};

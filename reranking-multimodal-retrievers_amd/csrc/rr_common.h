@@ -544,6 +544,12 @@ hipError_t rr_launch_bank_scores_f16(const rr_bank_slot* table, int n, int nq, i
                                      float* out, hipStream_t st);
 hipError_t rr_launch_f16_certify(const float* A, long long n, const int32_t* surv, int m, const float* scores, const int32_t* cnt, int k, float slack,
                                  int nq, int32_t* certified, hipStream_t st);
+// rr_bank_search_f16_plaid (bank_search_f16_plaid.hip): rr_launch_bank_scores_f16's out over a COMPRESSED bank, bit for bit what that
+// launch gives over the decoded rows; a row is decoded once per query block, into LDS.  rr_bank_scores_f16_plaid_dim_ok: the D it
+// takes (32, 64, 128, 256: the decoded tiles of D 512 leave no room for a query block).
+bool rr_bank_scores_f16_plaid_dim_ok(int D);
+hipError_t rr_launch_bank_scores_f16_plaid(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li, const rr_bank_view& bank,
+                                           float* out, hipStream_t st);
 // The list-driven form of the filtered exact search (rr_bank_search_filtered_sparse), stage by stage.
 // rr_launch_filter_compact (bank_ivf.hip): cand [filter.rows][n] = the range-relative passages of [filter.first, filter.first + n) whose
 // bit is set, ascending, cnt [filter.rows] their numbers; a workgroup per row, no atomics.

@@ -955,7 +955,7 @@ class RerankEngine:
         bank_search's, bytes included (include/rerank_mi355.h gives the proof); 0: still the exact best k of the query's ndocs
         approximately best.  `slack`: the bound on |approximate - exact| the certificate uses; None: the header's bound evaluated
         on `query_li` for unit rows (passage_bank.f16_default_slack: one small reduction on the device and one read-back).
-        1 <= k <= min(ndocs, count), ndocs <= 1024; compressed banks: NotImplementedError."""
+        1 <= k <= min(ndocs, count), ndocs <= 1024; compressed banks: NotImplementedError (bank_search_f16_plaid takes them)."""
         from .passage_bank import F16Search
         first, n, nq, Lq, q = _bank_search_args(self, "bank_search_f16", bank, query_li, first, count)
         fast = F16Search(ndocs, slack)
@@ -969,6 +969,28 @@ class RerankEngine:
                    certified=torch.empty((nq,), device=self.device, dtype=torch.int32))
         L.check(self.lib.rr_bank_search_f16(self.h, bank.h, L.ptr(q), nq, Lq, first, n, fast.ndocs, k, fast.slack_for(q), L.ptr(out["indices"]),
                                             L.ptr(out["scores"]), L.ptr(out["certified"]), self._stream()), self.h, "rr_bank_search_f16")
+        return out
+
+    def bank_search_f16_plaid(self, bank, query_li: torch.Tensor, k: int, ndocs: int, slack: Optional[float] = None, first: int = 0,
+                              count: Optional[int] = None) -> dict:
+        """bank_search_f16 for a COMPRESSED `bank` (rr_bank_search_f16_plaid): the first pass decodes the rows it multiplies, once
+        per block of queries, and feeds them to the fp16 matrix core.  The same arguments and the same dict, and byte for byte
+        what bank_search_f16 returns on the fp16 bank that holds the bank's decoded rows (`PassageBank.read`), "certified"
+        included; every score is bank_search's on the compressed bank, and a certified row is bank_search's row.  li_dim 64, 128
+        or 256; an fp16 bank: NotImplementedError (bank_search_f16 is its entry)."""
+        from .passage_bank import F16Search
+        first, n, nq, Lq, q = _bank_search_args(self, "bank_search_f16_plaid", bank, query_li, first, count)
+        fast = F16Search(ndocs, slack)
+        k = int(k)
+        if k < 1 or k > n or k > fast.ndocs:
+            raise ValueError(f"bank_search_f16_plaid: k = {k}, ndocs = {fast.ndocs}, {n} passages")
+        if getattr(bank, "codec", None) is None:
+            raise NotImplementedError("bank_search_f16_plaid: an fp16 bank (compressed banks only; bank_search_f16 searches an fp16 bank)")
+        out = dict(indices=torch.empty((nq, k), device=self.device, dtype=torch.int32),
+                   scores=torch.empty((nq, k), device=self.device, dtype=torch.float32),
+                   certified=torch.empty((nq,), device=self.device, dtype=torch.int32))
+        L.check(self.lib.rr_bank_search_f16_plaid(self.h, bank.h, L.ptr(q), nq, Lq, first, n, fast.ndocs, k, fast.slack_for(q), L.ptr(out["indices"]),
+                                                  L.ptr(out["scores"]), L.ptr(out["certified"]), self._stream()), self.h, "rr_bank_search_f16_plaid")
         return out
 
     def bank_search_filtered(self, bank, query_li: torch.Tensor, k: int, filter, first: int = 0, count: Optional[int] = None) -> dict:
@@ -1551,7 +1573,7 @@ class InteractionRerankModel(_DropIn):
         BankFilter built by bank.filter): only the allowed passages compete (the reference's filter_fn); one of the three at most.
         A query's list then has its true length, at most k.  `sparse` (with one of the three, without `plaid`; ValueError
         otherwise): the filtered exact search in its list-driven form (RerankEngine.bank_search_filtered_sparse), the same result.
-        `fast` (an F16Search; fp16 banks, with none of the above: ValueError otherwise): the exhaustive search whose first pass
+        `fast` (an F16Search; fp16 and compressed banks, with none of the above: ValueError otherwise): the exhaustive search whose first pass
         runs on the fp16 matrix core (RerankEngine.bank_search_f16): exact scores, and with `return_certified` the tuple ends in
         the certificate, int32 [n_queries] on the device (1: the list is provably the exact search's)."""
         if self.bank is None:

@@ -120,6 +120,12 @@ class F16Search:
         return f"F16Search(ndocs={self.ndocs}, slack={self.slack})"
 
 
+def _f16_entry(engine, bank):
+    """The entry `fast=` names for `bank`: a compressed bank (one with a codec) takes engine.bank_search_f16_plaid, whose first pass
+    decodes the rows it multiplies; an fp16 bank, plain or coded, engine.bank_search_f16.  The same arguments, the same dict."""
+    return engine.bank_search_f16_plaid if getattr(bank, "codec", None) is not None else engine.bank_search_f16
+
+
 def _fast_check(name: str, fast, plaid, filter, sparse) -> None:
     """`fast` names the unfiltered exhaustive search: with `plaid`, a filter or `sparse` there is no such entry."""
     if fast is not None and (plaid is not None or filter is not None or sparse):
@@ -1044,13 +1050,13 @@ class PassageBank:
         length on the exact path too.  A filter built for fewer passages than the range ends at raises ValueError.
         `sparse` (with `filter`, exact search only; ValueError otherwise): the list-driven form of the filtered exact search
         (engine.bank_search_filtered_sparse): the same result, with work that follows the allowed passages, not the range.
-        `fast` (an F16Search; fp16 banks; with `plaid`, `filter` or `sparse`: ValueError): the exhaustive search whose first pass runs
-        on the fp16 matrix core (engine.bank_search_f16).  Returns its dict instead, on the device, nothing copied: {"indices" int32
+        `fast` (an F16Search; with `plaid`, `filter` or `sparse`: ValueError): the exhaustive search whose first pass runs
+        on the fp16 matrix core (engine.bank_search_f16; on a compressed bank engine.bank_search_f16_plaid).  Returns its dict instead, on the device, nothing copied: {"indices" int32
         [n_queries, k] dense indices, "scores" float32 [n_queries, k] exact, "certified" int32 [n_queries]}."""
         _fast_check("search", fast, plaid, filter, sparse)
         _sparse_check("search", sparse, filter, plaid)
         if fast is not None:
-            return engine.bank_search_f16(self, query_li, k, fast.ndocs, fast.slack, first=first, count=count)
+            return _f16_entry(engine, self)(self, query_li, k, fast.ndocs, fast.slack, first=first, count=count)
         ids = self.table.ids
         if filter is not None:
             if getattr(filter, "generation", self.generation) != self.generation:
@@ -1216,7 +1222,7 @@ def search_bank_part(engine, bank, query_li, k: int, plaid: Optional[PlaidSearch
     PassageBank.search runs for them) with k_local = min(k, len(bank)), as {"indices": int32 [n_queries, k] dense indices of
     THIS bank, "scores": float32 [n_queries, k], "counts": int32 [n_queries]} on the device.  Behind k_local the rows hold -1 /
     -inf; an exact search, which returns no counts, gets k_local as its count; an empty bank contributes count 0 and no search
-    call.  `sparse`: as PassageBank.search takes it.  `fast` (an F16Search): engine.bank_search_f16 with ndocs = max(fast.ndocs,
+    call.  `sparse`: as PassageBank.search takes it.  `fast` (an F16Search): engine.bank_search_f16 (a compressed bank: bank_search_f16_plaid) with ndocs = max(fast.ndocs,
     k_local) capped at 1024, and one more entry, "certified" int32 [n_queries] (an empty bank: all 1)."""
     import torch
     _fast_check("search_bank_part", fast, plaid, filter, sparse)
@@ -1231,7 +1237,7 @@ def search_bank_part(engine, bank, query_li, k: int, plaid: Optional[PlaidSearch
     if k_local < 1:
         return out
     if fast is not None:
-        r = engine.bank_search_f16(bank, query_li, k_local, min(max(fast.ndocs, k_local), 1024), fast.slack)
+        r = _f16_entry(engine, bank)(bank, query_li, k_local, min(max(fast.ndocs, k_local), 1024), fast.slack)
         out["certified"] = r["certified"]
     elif plaid is not None:
         kw = dict(ncells=plaid.ncells, centroid_score_threshold=plaid.centroid_score_threshold, ndocs=plaid.ndocs,
@@ -1267,7 +1273,7 @@ def search_banks(engine, banks: Sequence, query_li, k: int, plaid: Optional[Plai
     search of the one bank; with `plaid` it is by definition the merge of the per-bank pruned searches (each bank keeps its own
     ndocs).  Copies the merged indices to the host (synchronises).  At most 64 banks, len(banks) * k <= 8192.  `sparse`: every
     bank's filtered exact search in its list-driven form (a filter for every bank, no `plaid`; ValueError otherwise).  `fast` (an
-    F16Search; no `plaid`, filters or `sparse`): every bank by engine.bank_search_f16, and a fourth result, certified int32
+    F16Search; no `plaid`, filters or `sparse`): every bank by engine.bank_search_f16 or, compressed, bank_search_f16_plaid, and a fourth result, certified int32
     [n_queries] on the device: the AND of the parts' certificates (every part's list provably exact: so is the merged one)."""
     import numpy as np
     import torch

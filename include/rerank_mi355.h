@@ -818,12 +818,18 @@ int rr_bank_search(rr_handle h, rr_bank_handle b, const float* query_li, int n_q
  * strictly below the k-th result.  The survivors hold every passage that can rank among the first k, stage 4 orders them as
  * rr_bank_search does, so indices_out and scores_out are rr_bank_search's bytes.  A query that is not certified still gets exact
  * scores of real passages, in order: the best k among its ndocs approximately best.
- * SLACK.  The bound it stands for: |A - E| <= sum_j ||q_j||2 * R * (2^-11 + D * 2^-22) + Lq * 2^-22 * |E|, R the largest row norm
- * (<= 1 + 2^-10 for unit rows stored as fp16).  2^-11 is the query's rounding to fp16 (relative, per element: derivable).  D * 2^-24
+ * SLACK.  The bound it stands for: |A - E| <= sum_j ||q_j||2 * R * (2^-11 + D * 2^-22) + Lq * 2^-22 * |E| + Lq * sqrt(D) * 2^-25 * R,
+ * R the largest row norm (<= 1 + 2^-10 for unit rows stored as fp16), FOR QUERY ELEMENTS BELOW 65520 IN MAGNITUDE.  2^-11 is the
+ * query's rounding to fp16 (relative, per element: derivable) inside fp16's normal range; below 2^-14 the error of an element is
+ * absolute, at most 2^-25 (half the subnormal spacing), so ||q_j - fp16(q_j)|| <= 2^-11 ||q_j|| + sqrt(D) * 2^-25: the last term,
+ * without which a query of elements below 2^-25 (all zero in fp16) was certified falsely.  An element of magnitude >= 65520
+ * rounds to infinity: NO finite slack bounds |A - E| then, and a caller that certifies such queries must pass +inf (accepted:
+ * the query is certified only when every passage of the range is rescored, m == n).  D * 2^-24
  * would cover ANY order of float32 additions of the exact products under round to nearest; the matrix core's internal order and
  * rounding are not documented, so the constant is 4 times that, and how far the hardware stays under it is MEASURED
- * (tests/test_gpu_bank_search_f16.py, profiles/bank_f16_parity_margins.json).  The last term is the column sum.  Python's default
- * (F16Search(slack=None)) evaluates the bound with R = 1 + 2^-10 and |E| <= sum_j ||q_j||2 * R, maximised over the call's queries.
+ * (tests/test_gpu_bank_search_f16.py, tests/test_gpu_bank_f16_forms.py, profiles/bank_f16_parity_margins.json).  Lq * 2^-22 * |E| is
+ * the column sum.  Python's default (F16Search(slack=None)) evaluates the bound with R = 1 + 2^-10 and |E| <= sum_j ||q_j||2 * R,
+ * maximised over the call's queries, and is +inf when an element of the call's queries is infinite or >= 65520 in magnitude.
  * SCRATCH in the grow-only block rr_bank_search uses, each term rounded up to 16 bytes: A and E (4 n_queries n each), the two
  * survivor buffers of the selection (4 n_queries ceil(n / 4096) m each, none for n <= 4096), the survivors (4 n_queries m), two
  * counts (4 n_queries each) and, without scores_out, 4 n_queries k: at most 4 n_queries n (2 + ndocs / 2048) + O(n_queries ndocs).

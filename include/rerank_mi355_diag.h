@@ -370,6 +370,14 @@ int rr_op_bank_scores_f16_plaid(const float* query_li, int n_queries, int Lq, in
                                 int32_t n_passages, const uint8_t* mask_bytes, int nbits, const int32_t* codes, const uint8_t* residuals,
                                 const uint16_t* centroids_f16, const float* bucket_weights, int32_t n_centroids, float* scores_out,
                                 void* hip_stream);
+/* rr_op_bank_scores_f16_form: the launch form rr_op_bank_scores_f16 (plaid == 0) or rr_op_bank_scores_f16_plaid (plaid != 0) takes
+ * for n_queries queries of Lq tokens at D, from the very host function the launch calls: *nt_out the column tiles (16 query tokens
+ * each) of a workgroup's query block, *tp_out the tiles of one query in a pass (a power of two <= nt; nt / tp queries share a
+ * block), *passes_out the passes over a query, ceil(ceil(Lq / 16) / tp).  The kernel instantiated is <nt, tp>.  HOST pointers.
+ * Launches nothing and touches no device.  Returns what the operator returns for a refused shape: RR_ERR_UNSUPPORTED for a D it
+ * does not take (fp16: not a multiple of 32; plaid: not 32, 64, 128 or 256), RR_ERR_BAD_SHAPE for n_queries or Lq out of range,
+ * RR_ERR_HIP where the launch itself refuses (a D whose narrowest block does not fit the LDS), and writes nothing then. */
+int rr_op_bank_scores_f16_form(int n_queries, int Lq, int D, int plaid, int* nt_out, int* tp_out, int* passes_out);
 
 /* rr_bank_search_plaid (rerank_mi355.h) from the inside.
  * rr_op_bank_search_plaid: the stages over raw DEVICE pointers, as rr_op_bank_search takes a compressed bank's (table, mask, codes,

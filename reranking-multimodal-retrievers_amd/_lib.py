@@ -126,6 +126,7 @@ _SIGS = {
     "rr_op_bank_scores_f16": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rr_bank_search_f16_plaid": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P]),
     "rr_op_bank_scores_f16_plaid": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int32, C.c_int32, _P, C.c_int, _P, _P, _P, _P, C.c_int32, _P, _P]),
+    "rr_op_bank_scores_f16_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rr_bank_search_plaid": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int, C.c_float, C.c_int, C.c_int,
                                        _P, _P, _P, _P]),
     "rr_op_bank_search_plaid": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int32, C.c_int32, C.c_int, C.c_float, C.c_int,

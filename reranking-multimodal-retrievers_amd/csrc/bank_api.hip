@@ -1054,6 +1054,18 @@ int rr_op_bank_scores_f16_plaid(const float* query_li, int n_queries, int Lq, in
   });
 }
 
+// rr_op_bank_scores_f16_form (include/rerank_mi355_diag.h): the launch form of either first pass; host arithmetic, no device
+int rr_op_bank_scores_f16_form(int n_queries, int Lq, int D, int plaid, int* nt_out, int* tp_out, int* passes_out) {
+  return guarded(nullptr, [&]() -> int {
+    if (!nt_out || !tp_out || !passes_out) return RR_ERR_BAD_ARG;
+    if (plaid ? !rr_bank_scores_f16_plaid_dim_ok(D) : (D <= 0 || D % 32)) return RR_ERR_UNSUPPORTED;      // the operators' checks, in their order
+    if (n_queries <= 0 || n_queries > 65535 || Lq <= 0) return RR_ERR_BAD_SHAPE;
+    const hipError_t e = plaid ? rr_bank_scores_f16_plaid_form(n_queries, Lq, D, nt_out, tp_out, passes_out)
+                               : rr_bank_scores_f16_form(n_queries, Lq, D, nt_out, tp_out, passes_out);
+    return e == hipSuccess ? RR_OK : RR_ERR_HIP;
+  });
+}
+
 // rr_set_tuning("plaid_stop_after") [0] and ("plaid_ivf_stop_after") [1]: the last stage an rr_bank_search_plaid call (7: all) and
 // an rr_bank_search_plaid_ivf call (8: all) runs; below it the outputs are not written: tools/bench_bank_search_plaid.py times the
 // stages by difference.  Diagnostic switches, set between calls (as g_op_dt).

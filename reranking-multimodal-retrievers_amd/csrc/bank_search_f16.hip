@@ -192,21 +192,36 @@ int pow2_ceil(int v) {
   return p;
 }
 
+size_t f16_lds_bytes(int nt, int D) { return (size_t)16 * nt * (D + F16_PAD) * sizeof(uint16_t); }
+
 }  // namespace
+
+// The form of a launch of bank_scores_f16_kernel for nq queries of Lq tokens at D: the block's column tiles *nt, the tiles of one
+// query in a pass *tp, the passes over a query.  Host arithmetic alone; hipErrorInvalidValue for a shape the launch refuses.
+hipError_t rr_bank_scores_f16_form(int nq, int Lq, int D, int* nt_out, int* tp_out, int* passes_out) {
+  if (nq <= 0 || Lq <= 0 || D <= 0 || D % 32) return hipErrorInvalidValue;
+  int nt = F16_NT_MAX;
+  while (nt > 1 && f16_lds_bytes(nt, D) > (size_t)64 * 1024) nt /= 2;
+  if (f16_lds_bytes(nt, D) > (size_t)150 * 1024) return hipErrorInvalidValue;
+  const int tiles = (Lq + 15) / 16;
+  const int tp = std::min(pow2_ceil(tiles), nt);               // tiles of one query in a pass
+  nt = (int)std::min<long long>(nt, (long long)tp * pow2_ceil(nq));      // no wider than the call's queries
+  *nt_out = nt;
+  *tp_out = tp;
+  *passes_out = (tiles + tp - 1) / tp;                         // as the kernel counts them
+  return hipSuccess;
+}
 
 // out [nq][n]: the approximate MaxSim (fp16 matrix core) of every query against the passages table[0 .. n) of an fp16 bank
 hipError_t rr_launch_bank_scores_f16(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li, const rr_bank_view& bank,
                                      float* out, hipStream_t st) {
   if (n <= 0 || nq <= 0 || Lq <= 0 || D <= 0 || D % 32 || !table || !query_li || !out || bank.nbits || !bank.rows || !bank.mask) return hipErrorInvalidValue;
   if ((((uintptr_t)query_li) | ((uintptr_t)table) | ((uintptr_t)bank.rows)) & 15) return hipErrorInvalidValue;
-  auto lds_bytes = [&](int t) { return (size_t)16 * t * (D + F16_PAD) * sizeof(uint16_t); };
-  int nt = F16_NT_MAX;
-  while (nt > 1 && lds_bytes(nt) > (size_t)64 * 1024) nt /= 2;
-  if (lds_bytes(nt) > (size_t)150 * 1024) return hipErrorInvalidValue;
-  const int tp = std::min(pow2_ceil((Lq + 15) / 16), nt);      // tiles of one query in a pass
-  nt = (int)std::min<long long>(nt, (long long)tp * pow2_ceil(nq));      // no wider than the call's queries
+  int nt = 0, tp = 0, passes = 0;
+  const hipError_t fe = rr_bank_scores_f16_form(nq, Lq, D, &nt, &tp, &passes);
+  if (fe != hipSuccess) return fe;
   const int qpb = nt / tp, nqb = (nq + qpb - 1) / qpb;
-  const size_t lds = lds_bytes(nt);
+  const size_t lds = f16_lds_bytes(nt, D);
 #define F16_CASE(NT_, TP_) \
   if (nt == NT_ && tp == TP_) return f16_launch_nt<NT_, TP_>(query_li, bank, table, n, nq, nqb, Lq, D, lds, out, st)
   F16_CASE(1, 1); F16_CASE(2, 1); F16_CASE(2, 2); F16_CASE(4, 1); F16_CASE(4, 2); F16_CASE(4, 4);

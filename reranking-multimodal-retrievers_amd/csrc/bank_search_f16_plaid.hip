@@ -254,9 +254,33 @@ int f16p_pow2_ceil(int v) {
   return p;
 }
 
+size_t f16p_tile_bytes(int D) { return (size_t)4 * 32 * (D + F16P_PAD) * sizeof(uint16_t); }                  // the four waves' decoded tiles
+size_t f16p_q_bytes(int nt, int D) { return (size_t)16 * nt * (D + F16P_PAD) * sizeof(uint16_t); }           // the block's query rows
+
 }  // namespace
 
 bool rr_bank_scores_f16_plaid_dim_ok(int D) { return D >= 32 && D <= F16P_D_MAX && !(D & (D - 1)); }
+
+// The form of a launch of bank_scores_f16_plaid_kernel, as rr_bank_scores_f16_form gives the fp16 kernel's; the D-dependent cap of
+// the block (the four decoded tiles share the LDS with it) is part of it.  Host arithmetic alone.
+hipError_t rr_bank_scores_f16_plaid_form(int nq, int Lq, int D, int* nt_out, int* tp_out, int* passes_out) {
+  if (nq <= 0 || Lq <= 0 || !rr_bank_scores_f16_plaid_dim_ok(D)) return hipErrorInvalidValue;
+  const size_t tile_bytes = f16p_tile_bytes(D);
+  int nt = F16P_NT_MAX;
+  while (nt > 1 && f16p_q_bytes(nt, D) > (size_t)64 * 1024) nt /= 2;           // as rr_bank_scores_f16_form
+  int nt2 = nt;                                                                // two workgroups per CU where a block allows it
+  while (nt2 > 1 && f16p_q_bytes(nt2, D) + tile_bytes > (size_t)72 * 1024) nt2 /= 2;
+  if (f16p_q_bytes(nt2, D) + tile_bytes <= (size_t)72 * 1024) nt = nt2;
+  while (nt > 1 && f16p_q_bytes(nt, D) + tile_bytes > (size_t)150 * 1024) nt /= 2;
+  if (f16p_q_bytes(nt, D) + tile_bytes > (size_t)150 * 1024) return hipErrorInvalidValue;
+  const int tiles = (Lq + 15) / 16;
+  const int tp = std::min(f16p_pow2_ceil(tiles), nt);               // tiles of one query in a pass
+  nt = (int)std::min<long long>(nt, (long long)tp * f16p_pow2_ceil(nq));      // no wider than the call's queries
+  *nt_out = nt;
+  *tp_out = tp;
+  *passes_out = (tiles + tp - 1) / tp;                              // as the kernel counts them
+  return hipSuccess;
+}
 
 // out [nq][n]: the approximate MaxSim (fp16 matrix core) of every query against the passages table[0 .. n) of a compressed bank
 hipError_t rr_launch_bank_scores_f16_plaid(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li, const rr_bank_view& bank,
@@ -265,19 +289,11 @@ hipError_t rr_launch_bank_scores_f16_plaid(const rr_bank_slot* table, int n, int
       !plaid_tables_ok(bank, D))
     return hipErrorInvalidValue;
   if ((((uintptr_t)query_li) | ((uintptr_t)table)) & 15) return hipErrorInvalidValue;
-  const size_t tile_bytes = (size_t)4 * 32 * (D + F16P_PAD) * sizeof(uint16_t);
-  auto q_bytes = [&](int t) { return (size_t)16 * t * (D + F16P_PAD) * sizeof(uint16_t); };
-  int nt = F16P_NT_MAX;
-  while (nt > 1 && q_bytes(nt) > (size_t)64 * 1024) nt /= 2;                   // as rr_launch_bank_scores_f16
-  int nt2 = nt;                                                                // two workgroups per CU where a block allows it
-  while (nt2 > 1 && q_bytes(nt2) + tile_bytes > (size_t)72 * 1024) nt2 /= 2;
-  if (q_bytes(nt2) + tile_bytes <= (size_t)72 * 1024) nt = nt2;
-  while (nt > 1 && q_bytes(nt) + tile_bytes > (size_t)150 * 1024) nt /= 2;
-  if (q_bytes(nt) + tile_bytes > (size_t)150 * 1024) return hipErrorInvalidValue;
-  const int tp = std::min(f16p_pow2_ceil((Lq + 15) / 16), nt);      // tiles of one query in a pass
-  nt = (int)std::min<long long>(nt, (long long)tp * f16p_pow2_ceil(nq));      // no wider than the call's queries
+  int nt = 0, tp = 0, passes = 0;
+  const hipError_t fe = rr_bank_scores_f16_plaid_form(nq, Lq, D, &nt, &tp, &passes);
+  if (fe != hipSuccess) return fe;
   const int qpb = nt / tp, nqb = (nq + qpb - 1) / qpb;
-  const size_t lds = q_bytes(nt) + tile_bytes;
+  const size_t lds = f16p_q_bytes(nt, D) + f16p_tile_bytes(D);
   return plaid_with_nbits(bank.nbits, [&](auto nb) -> hipError_t {
     constexpr int NB = decltype(nb)::value;
     if constexpr (NB <= 4)

@@ -548,6 +548,11 @@ hipError_t rr_launch_f16_certify(const float* A, long long n, const int32_t* sur
 // launch gives over the decoded rows; a row is decoded once per query block, into LDS.  rr_bank_scores_f16_plaid_dim_ok: the D it
 // takes (32, 64, 128, 256: the decoded tiles of D 512 leave no room for a query block).
 bool rr_bank_scores_f16_plaid_dim_ok(int D);
+// rr_bank_scores_f16_form / rr_bank_scores_f16_plaid_form: what the two launches above and below choose for (nq, Lq, D), and nothing
+// else: the block's column tiles nt, the tiles of one query in a pass tp (the kernel instantiated is <nt, tp>), the passes over a
+// query; hipErrorInvalidValue for a shape the launch refuses.  The launches call them (rr_op_bank_scores_f16_form reads them out).
+hipError_t rr_bank_scores_f16_form(int nq, int Lq, int D, int* nt_out, int* tp_out, int* passes_out);
+hipError_t rr_bank_scores_f16_plaid_form(int nq, int Lq, int D, int* nt_out, int* tp_out, int* passes_out);
 hipError_t rr_launch_bank_scores_f16_plaid(const rr_bank_slot* table, int n, int nq, int Lq, int D, const float* query_li, const rr_bank_view& bank,
                                            float* out, hipStream_t st);
 // The list-driven form of the filtered exact search (rr_bank_search_filtered_sparse), stage by stage.

@@ -88,10 +88,16 @@ class PlaidSearch:
 
 def f16_default_slack(query_norm_sum: float, li_dim: int, Lq: int) -> float:
     """The bound on |A - E| that rr_bank_search_f16's certificate stands on (include/rerank_mi355.h, SLACK), for unit rows stored as
-    fp16 (R = 1 + 2^-10) and |E| <= S R: S R (2^-11 + D 2^-22) + Lq 2^-22 S R, S = `query_norm_sum`, the sum over a query's tokens of
-    their 2-norms (the largest over the queries of a call)."""
-    sr = float(query_norm_sum) * (1.0 + 2.0 ** -10)
-    return sr * (2.0 ** -11 + int(li_dim) * 2.0 ** -22) + int(Lq) * 2.0 ** -22 * sr
+    fp16 (R = 1 + 2^-10) and |E| <= S R: S R (2^-11 + D 2^-22) + Lq 2^-22 S R + Lq sqrt(D) 2^-25 R, S = `query_norm_sum`, the sum
+    over a query's tokens of their 2-norms (the largest over the queries of a call).  The last term: below fp16's normal range
+    (2^-14) an element's rounding error is absolute, at most 2^-25, not 2^-11 of the element.  For query elements below
+    F16_QUERY_LIMIT in magnitude only: one at or above it rounds to infinity, and no finite slack bounds that (F16Search.slack_for)."""
+    r = 1.0 + 2.0 ** -10
+    sr = float(query_norm_sum) * r
+    return sr * (2.0 ** -11 + int(li_dim) * 2.0 ** -22) + int(Lq) * 2.0 ** -22 * sr + int(Lq) * float(li_dim) ** 0.5 * 2.0 ** -25 * r
+
+
+F16_QUERY_LIMIT = 65520.0          # the least magnitude that round-to-nearest-even takes to fp16's infinity
 
 
 class F16Search:
@@ -110,11 +116,18 @@ class F16Search:
             raise ValueError(f"F16Search: slack = {slack} (>= 0, not NaN)")
 
     def slack_for(self, query_li) -> float:
-        """`slack`, or the default bound for `query_li` [n_queries, Lq, D] (one reduction on its device, one read-back)."""
+        """`slack`, or the default bound for `query_li` [n_queries, Lq, D] (two reductions on its device, one read-back): +inf
+        when an element is infinite or rounds to infinity in fp16 (the query is then certified only if every passage is
+        rescored), NaN for a NaN query (the entries refuse it)."""
         if self.slack is not None:
             return self.slack
-        s = float(query_li.double().norm(dim=-1).sum(dim=-1).max().item())
-        return f16_default_slack(s, int(query_li.shape[-1]), int(query_li.shape[-2]))
+        import torch
+        q = query_li.double()
+        s, top = torch.stack([q.norm(dim=-1).sum(dim=-1).max(), q.abs().max()]).tolist()
+        d = f16_default_slack(s, int(query_li.shape[-1]), int(query_li.shape[-2]))
+        if d == d and top >= F16_QUERY_LIMIT:
+            return float("inf")
+        return d
 
     def __repr__(self) -> str:
         return f"F16Search(ndocs={self.ndocs}, slack={self.slack})"

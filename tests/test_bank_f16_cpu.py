@@ -56,7 +56,8 @@ def test_f16search_arguments():
     q = torch.nn.functional.normalize(torch.randn(3, 7, 64), dim=-1)
     q[1] *= 2.0
     assert F16Search(8).slack_for(q) == pytest.approx(f16_default_slack(14.0, 64, 7), rel=1e-6)
-    assert f16_default_slack(32.0, 128, 32) == pytest.approx(32 * (1 + 2 ** -10) * (2 ** -11 + 128 * 2 ** -22 + 32 * 2 ** -22))
+    assert f16_default_slack(32.0, 128, 32) == pytest.approx((1 + 2 ** -10) * (32 * (2 ** -11 + 128 * 2 ** -22 + 32 * 2 ** -22) + 32 * 128 ** 0.5 * 2 ** -25),
+                                                             rel=1e-12)
 
 
 def test_fast_is_refused_with_plaid_filter_or_sparse_before_an_engine_is_touched():

@@ -169,6 +169,17 @@ def _check_against_fresh(eng, A, sh, what, seed):
     if not sh.nbits:
         (ia, sa), (ib, sb) = A.search(eng, q, n), B.search(eng, q, n)
         assert ia == ib and torch.equal(sa.view(torch.int32), sb.view(torch.int32)), f"{what}: the exact search"
+    # the searches whose first pass runs on the fp16 matrix core read the same cached device table: with every passage rescored
+    # (ndocs 1024 >= n) they must give the plain search's ids and score bytes on both banks, every query certified
+    if n <= 1024 and D % 32 == 0 and (not sh.nbits or D in (32, 64, 128, 256)):
+        from rmr_amd import F16Search
+        for name, bank in (("the lived bank", A), ("the fresh bank", B)):
+            ids, scores = bank.search(eng, q, n)
+            r = bank.search(eng, q, n, fast=F16Search(1024))
+            torch.cuda.synchronize()
+            assert [[bank.table.ids[j] for j in row] for row in r["indices"].tolist()] == ids, f"{what}: the fp16 matrix-core search of {name}"
+            assert torch.equal(r["scores"].view(torch.int32), scores.view(torch.int32)), f"{what}: the fp16 matrix-core search of {name}"
+            assert r["certified"].tolist() == [1] * q.shape[0], f"{what}: every passage of {name} is rescored, the query is certified"
     # the exact search under a fresh filter that excludes every third passage
     out = sh.ids[::3]
     (ia, sa), (ib, sb) = A.search(eng, q, n, filter=A.filter(excluded=out)), B.search(eng, q, n, filter=B.filter(excluded=out))
